@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — frame-pairs/s of the optical-flow -> ego-velocity hot path on N MI355X GPUs.
 
-  python bench.py [--gpus N --steps K --warmup W --batch B] [--config c1|c2|c4]
+  python bench.py [--gpus N --steps K --warmup W --batch B] [--config c1|c2|c4] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the JSON line with the headline figures (metric, value, unit,
+ms_per_step, higher_is_better, dtype, config).  --full adds everything else listed below (the stage and serial passes behind the
+timed region, roofline, CPU baseline, ingest legs, Monte-Carlo sweep); --cpu-sample, --no-ingest and --no-isolated act on those.
+--dump-outputs DIR writes what the timed path computed in its last step (what FlowPipeline.run returns: records, counts, points,
+status, err; the filter state for c2) as DIR/<name>.npy in float32 / float64.  Point slots past a pair's corner count are zeroed;
+above 64 MB in all, a fixed seeded sample of the pairs is written with its indices (pair_index.npy).  Rank 0 writes its own pairs.
 
 Default (--config c1) = BASELINE.json configs[1], the configuration the metric is quoted on: 1920x1080 frame pairs, 500 Shi-Tomasi
 corners, 3-level LK pyramid.  --config c2 = configs[2] (1024 independent 640x480 pairs per step + the per-pair 6-state filter update
@@ -27,7 +34,7 @@ Schedule (default): one stage chain (response -> selection -> LK -> solve) on th
 conversions and pyramids of the NEXT step on an auxiliary stream beside it; B = 512 pairs per step at 1080p.
 c2 runs two free-running slices (at 480p LK is the longest stage and the latency-bound phases weigh more: +10 %).
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     : the dominant kernel = the longest stage of the step's critical chain (response -> select -> LK -> solve).
                  Its duration is taken from the SERIAL pass that follows the timed region (same process, same resident
                  frames, every stage alone on one stream, HIP events on that stream): under the overlapped schedule
@@ -318,6 +325,35 @@ def cpu_baseline(prev, nxt, sensors, cfg, sample, threads=1):
     return sample / dt, v[-1]
 
 
+DUMP_LIMIT = 64 << 20        # bytes written by --dump-outputs at most
+
+
+def dump_outputs(path, out, extra=None, limit=DUMP_LIMIT):
+    """The arrays FlowPipeline.run returns (ofk_pairs_download with points) as path/<name>.npy, f64 for the records and counts,
+    f32 for the rest.  Point slots at or past a pair's corner count are never written by the device and are zeroed here, so that
+    two runs compare slot for slot.  `extra`: more per-pair f64 arrays (the filter state).  Above `limit` bytes a fixed seeded
+    sample of the pairs is kept, its indices in pair_index.npy."""
+    cnt = out["counts"]
+    B, S = out["prev_pts"].shape[:2]
+    valid = np.arange(S)[None, :] < cnt[:, None]
+    arrays = {"records": out["records"].astype(np.float64), "counts": cnt.astype(np.float64)}
+    for name in ("prev_pts", "next_pts"):
+        arrays[name] = np.where(valid[..., None], out[name], 0).astype(np.float32)
+    for name in ("status", "err"):
+        arrays[name] = np.where(valid, out[name], 0).astype(np.float32)
+    for name, a in (extra or {}).items():
+        arrays[name] = np.asarray(a, np.float64)
+    per_pair = sum(a.nbytes for a in arrays.values()) / B
+    if per_pair * B > limit:
+        k = max(1, int(limit // (per_pair + 8)))
+        idx = np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["pair_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -328,10 +364,14 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="frame pairs per GPU per step (default: 512 at 1080p = 14 GB of the 288 GB; 1024 for c2; 256 for c4)")
     ap.add_argument("--streams", type=int, default=0, help="free-running slices of the batch (HIP streams) per GPU (default: 1; 2 for c2)")
     ap.add_argument("--no-overlap", action="store_true", help="run every stage of a step serially on one stream")
-    ap.add_argument("--no-isolated", action="store_true", help="skip the serial pass behind the timed region (profiling: the kernel "
-                    "trace then holds the timed schedule's launches only)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="pairs timed on the CPU oracle (0 = skip; default 24 at 1080p, 128 for c2, 8 for c4)")
-    ap.add_argument("--no-ingest", action="store_true", help="skip the ingest-inclusive legs (raw BGR upload / JPEG decode every step)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure everything beyond the headline: stage "
+                    "brackets, the serial pass and roofline, the CPU baseline, the ingest legs, c4's Monte-Carlo sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (f32 / f64)")
+    ap.add_argument("--no-isolated", action="store_true", help="with --full: skip the serial pass behind the timed region (profiling: "
+                    "the kernel trace then holds the timed schedule's launches only)")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="with --full: pairs timed on the CPU oracle (0 = skip; default 24 at 1080p, "
+                    "128 for c2, 8 for c4)")
+    ap.add_argument("--no-ingest", action="store_true", help="with --full: skip the ingest-inclusive legs (raw BGR upload / JPEG decode every step)")
     ap.add_argument("--comms", type=int, default=1, help="RCCL communicators per rank under a launcher: 1 (default) = one gather per step behind the "
                     "last slice - the plain usage every RCCL build supports; S = --streams: one communicator per slice, every slice gathers its own "
                     "records on its own stream (+0.8 %% at N = 1; two collectives of one rank then run concurrently)")
@@ -428,6 +468,50 @@ def main():
     run_steps(args.steps, args.warmup)
     sync_all()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                          # the last timed step's outputs, before anything runs again
+        extra = None
+        if C["ekf"]:
+            fx, fP = pipe.ctx.filter_state(B)
+            extra = {"filter_x": fx, "filter_P": fP}
+        dump_outputs(args.dump_outputs, pipe.ctx.pairs_download(points=True), extra)
+
+    def headline(rec, counts, dt):
+        """The keys every run prints (the metric and how it was obtained)."""
+        n_pts = float(np.mean(counts))
+        n_cand = float(np.mean(rec[:, 14]))
+        return {
+            "metric": f"frame-pairs/sec @{W}x{H} (LK+velocity)",
+            "value": round(world * B * args.steps / dt, 2),
+            "unit": "frame-pairs/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8/i32 image stages, f32 LK solve, f64 velocity solve",
+            "data": "synthetic",
+            "config": {"workload": C["workload"], "pairs_per_gpu_per_step": B, "streams_per_gpu": args.streams, "corners_mean": round(n_pts, 1), "candidates_mean": round(n_cand, 1), "win": cfg.win, "max_level": cfg.max_level,
+                       "sharding": f"{world} x independent pair batches, RCCL all_gather of [B,8] f32 records on the library's stream" + (f", {comm.n_comms} communicator(s) per rank" if launched else " (single process: nothing to exchange)")},
+        }
+
+    if not args.full:
+        if comm is not None:
+            dt = comm.max(dt)
+        if rank == 0:
+            out = pipe.ctx.pairs_download(points=False)
+            line = headline(out["records"], out["counts"], dt)
+            line["velocity_sample"] = [round(float(x), 6) for x in out["records"][0, :3]]
+            line["velocity_truth"] = list(truth["v"])
+            print(json.dumps(line), flush=True)
+        if comm is not None:
+            comm.barrier()
+            comm.close()
+        pipe.close()
+        return
+
+    # --full from here on.
     # the same K steps once more under the same schedule with every stage bracketed by events: the `stages` object (outside the timed region)
     pipe.ctx.profile_enable(0x7f)
     run_steps(args.steps, args.warmup + args.steps)
@@ -515,21 +599,8 @@ def main():
                              "traffic": pyr_tr, "achieved_traffic": gb(pyr_tr) if pyr_tr else None, "frac_traffic": fr(pyr_tr) if pyr_tr else None}
         t_grp = iso_ms["pyr"] * max(1, iso["pyr"][1] // max(1, args.steps)) + iso_ms["lk"]
         grp_bytes = (ab["pyr"] + ab["lk"]) * iso_pairs
-        line = {
-            "metric": f"frame-pairs/sec @{W}x{H} (LK+velocity)",
-            "value": round(world * B * args.steps / dt, 2),
-            "unit": "frame-pairs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8/i32 image stages, f32 LK solve, f64 velocity solve",
-            "data": "synthetic",
-            "config": {"workload": C["workload"], "pairs_per_gpu_per_step": B, "streams_per_gpu": args.streams, "corners_mean": round(n_pts, 1), "candidates_mean": round(n_cand, 1), "win": cfg.win, "max_level": cfg.max_level,
-                       "sharding": f"{world} x independent pair batches, RCCL all_gather of [B,8] f32 records on the library's stream" + (f", {comm.n_comms} communicator(s) per rank" if launched else " (single process: nothing to exchange)")},
+        line = headline(rec, out["counts"], dt)
+        line.update({
             "roofline": roof,
             # "Pyramid+LK group (north-star kernel)" = G_pyr + G_lk (Scharr fused into LK), serial-pass durations
             "north_star_group": {"kernels": f"{KERNEL_OF['pyr']} + {KERNEL_OF['lk']}", "bound": "hbm",
@@ -551,7 +622,7 @@ def main():
             "north_star_kernel": north_star_kernel,
             "velocity_sample": [round(float(x), 6) for x in rec[0, :3]],
             "velocity_truth": list(truth["v"]),
-        }
+        })
         if world == 1 and args.cpu_sample > 0:
             sample = min(args.cpu_sample, B)
             cps, v_cpu = cpu_baseline(prev, nxt, sensors, cfg, sample)

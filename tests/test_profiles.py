@@ -102,6 +102,34 @@ def test_bench_algorithmic_bytes_follow_survey_8d():
     assert "1920" in base["configs"][1] and "1024" in base["configs"][2] and "3840" in base["configs"][4]
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: every array a FlowPipeline.run caller receives, f32 / f64 only, point slots past a pair's count zeroed;
+    above the byte limit the same seeded sample of pairs every time, with its indices."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    B, S = 8, 6
+    rng = np.random.default_rng(5)
+    out = dict(records=rng.random((B, 16)), counts=np.array([6, 0, 3, 1, 6, 2, 5, 4], np.int32),
+               prev_pts=rng.random((B, S, 2), dtype=np.float32), next_pts=rng.random((B, S, 2), dtype=np.float32),
+               status=np.ones((B, S), np.uint8), err=rng.random((B, S), dtype=np.float32))
+    bench.dump_outputs(str(tmp_path / "all"), out, {"filter_x": rng.random((B, 6))})
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert set(got) == {"records", "counts", "prev_pts", "next_pts", "status", "err", "filter_x"}
+    assert all(a.dtype in (np.float32, np.float64) and a.shape[0] == B for a in got.values())
+    assert np.array_equal(got["records"], out["records"]) and np.array_equal(got["counts"], out["counts"])
+    assert np.array_equal(got["prev_pts"][2, :3], out["prev_pts"][2, :3]) and not got["prev_pts"][2, 3:].any()
+    assert not got["status"][1].any() and got["status"][0].all() and not got["err"][3, 1:].any()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, limit=900)
+    idx = np.load(tmp_path / "a" / "pair_index.npy")
+    assert 0 < len(idx) < B and np.array_equal(idx, np.load(tmp_path / "b" / "pair_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "records.npy"), out["records"][idx.astype(int)])
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in os.listdir(tmp_path / "a")) <= 900
+
+
 def test_decoder_profile_and_the_bench_line_agree():
     """profiles/<tag>_jpeg_decoder.json (SQ counter passes over the decoder alone) is what bench.py reports as ingest_inclusive.decoder:
     the per-kernel times add up to the total, the committed bench line of configs[1] carries exactly these numbers, its double-buffered

@@ -2,6 +2,7 @@
 # SQ counters of one kernel of bench.py (GPU box).  Each --pmc group is its own run (the hardware has few SQ counters),
 # with --kernel-trace only, as the pool requires.   tools/pmc_kernel.sh <kernel-name-substring> [bench flags]
 K=${1:-k_mineig_stream}; shift
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=/root/repo/gpurun_out/pmc
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
@@ -11,7 +12,7 @@ G3="SQ_IFETCH SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VMEM SQ_THREAD_CY
 i=0
 for G in "$G1" "$G2" "$G3"; do
     i=$((i + 1))
-    rocprofv3 --pmc $G --kernel-trace --output-format csv -d "$OUT/g$i" -o pmc -- python3 /root/repo/bench.py --no-overlap --steps 2 --warmup 1 --cpu-sample 0 "$@" > "$OUT/g$i.log" 2>&1 || { tail -5 "$OUT/g$i.log"; exit 1; }
+    rocprofv3 --pmc $G --kernel-trace --output-format csv -d "$OUT/g$i" -o pmc -- python3 $R/bench.py --full --no-overlap --steps 2 --warmup 1 --cpu-sample 0 "$@" > "$OUT/g$i.log" 2>&1 || { tail -5 "$OUT/g$i.log"; exit 1; }
 done
 cd /root/repo && python3 - "$K" <<'PY'
 import csv, glob, sys, collections

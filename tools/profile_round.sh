@@ -7,7 +7,7 @@
 #   2. SQ counters (SQ_INSTS_VALU ...) of every kernel, two runs  -> gpurun_out/<tag>_valu_pmc.json (tools/make_valu_json.py)
 #   3. rocprofv3 --kernel-trace --stats of the default bench command and of --no-overlap --streams 1 (every kernel alone on the chip)
 #      -> gpurun_out/<tag>_kernel_stats_{overlap,serial}.csv
-#   4. the plain bench line -> gpurun_out/<tag>_bench.json
+#   4. the bench line with --full -> <tag>_bench.json
 TAG=${1:-r04}; BATCH=${2:-512}; CONFIG=${3:-c1}
 case $CONFIG in c2) HW="480 640";; c4) HW="2160 3840";; *) HW="1080 1920";; esac
 R=${GRAFT_REPO_ROOT:-/root/repo}
@@ -15,7 +15,7 @@ O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 if [ $CONFIG = c1 ] && [ -x $R/build_variants/valu_rates ]; then $R/build_variants/valu_rates > $O/${TAG}_valu_rates.txt 2>&1 || exit 1; fi
-QUIET="--cpu-sample 0 --no-ingest --config $CONFIG"
+QUIET="--full --cpu-sample 0 --no-ingest --config $CONFIG"
 #   0b. FETCH_SIZE calibration on known byte counts (tools/fetch_calib.hip) -> gpurun_out/<tag>_fetch_calibration.json
 if [ $CONFIG = c1 ] && [ -x $R/build_variants/fetch_calib ]; then
   rm -rf $O/pmc_calib $O/pmc_calib_raw
@@ -39,4 +39,4 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_overlap -
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_serial -o p -- python3 $R/bench.py --batch $BATCH --steps 10 --warmup 2 $QUIET --no-overlap --streams 1 > $O/prof_${TAG}_serial.log 2>&1 || exit 1
 cp $(find $O/prof_${TAG}_overlap -name '*kernel_stats.csv' | head -1) $O/${TAG}_kernel_stats_overlap.csv
 cp $(find $O/prof_${TAG}_serial -name '*kernel_stats.csv' | head -1) $O/${TAG}_kernel_stats_serial.csv
-cd $R && python3 bench.py --batch $BATCH --config $CONFIG > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err && python3 tools/show_bench.py gpurun_out/${TAG}_bench.json
+cd $R && python3 bench.py --full --batch $BATCH --config $CONFIG > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err && python3 tools/show_bench.py $O/${TAG}_bench.json

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Steady-state timeline of the default schedule from a rocprofv3 kernel trace:
-     rocprofv3 --kernel-trace --output-format csv -d gpurun_out/tl -o t -- python3 bench.py --cpu-sample 0 --no-ingest --no-isolated
-     python tools/timeline.py gpurun_out/tl/t_kernel_trace.csv
+     rocprofv3 --kernel-trace --output-format csv -d out/tl -o t -- python3 bench.py --full --cpu-sample 0 --no-ingest --no-isolated
+     python tools/timeline.py out/tl/t_kernel_trace.csv
    Prints one period (from one response-kernel launch of slice 0 to the next) with start offset, duration and queue of every kernel,
    and the busy time of every queue over the period."""
 import collections

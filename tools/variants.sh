@@ -26,11 +26,11 @@ build)
     done ;;
 run)
     shift
-    mkdir -p "$ROOT/gpurun_out"
+    LOGS=${OUT:-$ROOT/out}; mkdir -p "$LOGS"                # OUT: where the logs go
     for lib in "$OUT"/libofk_*.so; do
         name=$(basename "$lib" .so); name=${name#libofk_}
         cp "$lib" "$PKG/libofk.so"
-        timeout -k 10 200 python "$ROOT/bench.py" --cpu-sample 0 "$@" > "$ROOT/gpurun_out/var_$name.log" 2>&1 || { echo "$name failed"; tail -3 "$ROOT/gpurun_out/var_$name.log"; exit 1; }
-        echo "== $name"; python "$ROOT/tools/show_bench.py" "$ROOT/gpurun_out/var_$name.log" | grep -E "frame-pairs|eig|lk |pyr|gray"
+        timeout -k 10 200 python "$ROOT/bench.py" --full --cpu-sample 0 "$@" > "$LOGS/var_$name.log" 2>&1 || { echo "$name failed"; tail -3 "$LOGS/var_$name.log"; exit 1; }
+        echo "== $name"; python "$ROOT/tools/show_bench.py" "$LOGS/var_$name.log" | grep -E "frame-pairs|eig|lk |pyr|gray"
     done ;;
 esac
