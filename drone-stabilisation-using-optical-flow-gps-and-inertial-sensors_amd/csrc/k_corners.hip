@@ -27,6 +27,7 @@
 //              minimum-distance pass in a 256-thread workgroup per image (described in front of them).
 //              Result identical to a full sort (value desc, index desc) followed by the serial greedy pass.
 #include "ofk_internal.h"
+#include <type_traits>
 
 __device__ __forceinline__ int reflect101(int i, int n)
 {
@@ -627,6 +628,42 @@ __device__ __forceinline__ int lambda_min_bits(int vxx, int vxy, int vyy, float 
     return __float_as_int((a + c) - sqrt_rn_normal(__builtin_fmaf(4.f, y2, amc2)));
 }
 
+// ---- the f32 datapath of k_mineig_pair (round 5).  Every value of the integer datapath is an integer: |dx|, |dy| <= 1020, products
+// <= 1 040 400, horizontal box sums <= 7.3 M, and the vertical 7x7 sums are the only ones that can pass 2^24 (51 M at most).  An f32
+// add, multiply or fused multiply-add of integers whose exact result lies within 2^24 is exact whatever the order of the operations,
+// so as long as Sxx + Syy stays within 2^24 (|Sxy| <= (Sxx + Syy) / 2) the f32 loop computes the integer loop's Sxx, Sxy and Syy bit
+// for bit - and v_mul_f32 / v_fmac_f32 / v_add_f32 issue at full rate where v_mul_i32_i24, v_add3_u32 and the six v_cvt_f32_i32 per
+// row that fed the f32 formula take four clocks.  Above 2^24 the wave restarts its strip on the integer loop (k_mineig_pair).
+#define DPP_SHR1F(v) __int_as_float(DPP_SHR1(__float_as_int(v)))
+#define DPP_SHL1F(v) __int_as_float(DPP_SHL1(__float_as_int(v)))
+__device__ __forceinline__ float bperm_f(int addr, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v))); }
+
+// The box sums of one product kind for both slots from the even product ae = x_e y_e, the pair sum q = ae + x_o y_o and the odd
+// factors of lane l - K (gx, gy: gathered once per row for all three kinds).  With W(l) = q(l-K+1) + .. + q(l):
+//   s_o(l) = x_o(l-K) y_o(l-K) + W(l)   -> one fma, the odd product of lane l - K never formed on its own
+//   s_e(l) = ae(l) + W(l-1)             -> one v_add_f32_dpp
+// 6 VALU for BS = 7 (two products, W = shr(q) + q + q(l-2), two sums) where the integer pair sums took 7 (one of them the pair sum
+// q = ae + ao that the fma makes free) and 24 issue clocks against 16; one ds_bpermute per kind instead of three, plus two for gx, gy.
+template <int K>
+__device__ __forceinline__ void box_pair_f(float ae, float q, float gx, float gy, int ad2, float &he, float &ho)
+{
+    float W = q;
+    if constexpr (K >= 2) W = DPP_SHR1F(q) + q;
+    if constexpr (K == 3) W = W + bperm_f(ad2, q);
+    ho = __builtin_fmaf(gx, gy, W);
+    he = DPP_SHR1F(W) + ae;
+}
+
+// lambda_min_bits on f32 sums (equal to the integers lambda_min_bits converts: see above); apc = a + c, the guard's operand
+__device__ __forceinline__ int lambda_min_bits_f(float vxx, float vxy, float vyy, float kd, float &apc)
+{
+    const float a = vxx * kd, y = vxy * kd, c = vyy * kd;
+    const float amc = a - c;
+    const float y2 = y * y, amc2 = amc * amc;
+    apc = a + c;
+    return __float_as_int(apc - sqrt_rn_normal(__builtin_fmaf(4.f, y2, amc2)));
+}
+
 // (Measured and dropped: the same formula on float PAIRS — v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 — executes 11 fewer
 //  instructions per row and is 10 % SLOWER: plain f32 add/mul/fma issue at twice the rate of the packed and VOP3 forms,
 //  tools/valu_rates.hip.)
@@ -646,8 +683,8 @@ __device__ __forceinline__ int lambda_min_bits(int vxx, int vxy, int vyy, float 
         cnt -= nchunk * 64;                                                                                            \
     }
 #define OFK_RING_READ(i)                                                                                               \
-        const int oyye = s_ring[(4 * (i)) * 64 + lane], oyyo = s_ring[(4 * (i) + 1) * 64 + lane];                      \
-        const int oxye = s_ring[(4 * (i) + 2) * 64 + lane], oxyo = s_ring[(4 * (i) + 3) * 64 + lane];
+        const auto oyye = s_ring[(4 * (i)) * 64 + lane], oyyo = s_ring[(4 * (i) + 1) * 64 + lane];                     \
+        const auto oxye = s_ring[(4 * (i) + 2) * 64 + lane], oxyo = s_ring[(4 * (i) + 3) * 64 + lane];
 // One block of BS rows (expanded twice: IN = true for interior blocks); see OFK_EIG_ROWS for the conventions.
 #define OFK_PAIR_ROWS(IN)                                                                                             \
     _Pragma("unroll") for (int i = 0; i < BS; ++i) {                                                                   \
@@ -687,6 +724,55 @@ __device__ __forceinline__ int lambda_min_bits(int vxx, int vxy, int vyy, float 
         s_ring[(4 * i + 2) * 64 + lane] = hxye; s_ring[(4 * i + 3) * 64 + lane] = hxyo;                                \
         const int yo = ya - 2 + r - BS;                                                                                \
         const int e2e = lambda_min_bits(vxxe, vxye, vyye, kdv), e2o = lambda_min_bits(vxxo, vxyo, vyyo, kdv);    \
+        OFK_PAIR_ROW_TAIL(IN)                                                                                          \
+        r01e = r12e; r01o = r12o; g1e = ge2; g1o = go2;                                                                  \
+    }
+// The f32 rows: the integer rows' arithmetic on floats (see box_pair_f), then the same maximum, NMS and keys on the lambda bits.
+//  * a lane's byte pair is shifted to bytes 0-1 once, v_cvt_f32_ubyte0/1 replace the two v_bfe_u32;
+//  * dx_e = s_o - shr(s_o) is v_subrev_f32_dpp and dx_o = shl(s_e) - s_e is v_sub_f32_dpp: no negated copies;
+//  * mirrored product rows / columns negate dx instead of dx dy: xx is a square, xy flips as in the integer rows;
+//  * inexact = the lanes whose a + c reached lim in some row so far (a sticky SGPR ballot): the 2^24 guard (k_mineig_pair).
+#define OFK_PAIR_ROWS_F32(IN)                                                                                          \
+    _Pragma("unroll") for (int i = 0; i < BS; ++i) {                                                                   \
+        const int r = base + i;                                                                                        \
+        const unsigned gw_ = (unsigned)curv[i] >> bsh;                                                                 \
+        float ge2 = (float)(gw_ & 255u), go2 = (float)((gw_ >> 8) & 255u);                                             \
+        asm("" : "+v"(ge2), "+v"(go2));                  /* or the int-to-float fold moves the Sobel sums back to integers */ \
+        if (!(IN)) {                                                                                                   \
+            if (edge_strip) { ge2 = bperm_f(mir_e, ge2); go2 = bperm_f(mir_o, go2); }                                   \
+        }                                                                                                              \
+        if (i > 0 && (i & 1) == 0 && cnt >= 64) OFK_PAIR_SPILL_KEYS()                                                  \
+        OFK_RING_READ(i)                                                                                               \
+        const float r12e = g1e + ge2, r12o = g1o + go2;                                                                \
+        const float se = r01e + r12e, so = r01o + r12o, te = r12e - r01e, to = r12o - r01o, tt = te + to;              \
+        float dxe = so - DPP_SHR1F(so), dxo = DPP_SHL1F(se) - se;                                                      \
+        const float dye = (DPP_SHR1F(to) + te) + tt, dyo = (DPP_SHL1F(te) + to) + tt;                                  \
+        if (!(IN)) {                                                                                                   \
+            const int Y = Yp0 + r - 2;                                                                                 \
+            const bool rowflip = (Y < 0) | (Y >= h);                                                                   \
+            dxe = (rowflip != flip_e) ? -dxe : dxe;                                                                    \
+            dxo = (rowflip != flip_o) ? -dxo : dxo;                                                                    \
+        }                                                                                                              \
+        const float gx = bperm_f(adk, dxo), gy = bperm_f(adk, dyo);                                                    \
+        float hxxe, hxxo, hxye, hxyo, hyye, hyyo;                                                                      \
+        const float pxxe = dxe * dxe, pxye = dxe * dye, pyye = dye * dye;                                              \
+        box_pair_f<BS / 2>(pxxe, __builtin_fmaf(dxo, dxo, pxxe), gx, gx, ad2, hxxe, hxxo);                              \
+        box_pair_f<BS / 2>(pxye, __builtin_fmaf(dxo, dyo, pxye), gx, gy, ad2, hxye, hxyo);                              \
+        box_pair_f<BS / 2>(pyye, __builtin_fmaf(dyo, dyo, pyye), gy, gy, ad2, hyye, hyyo);                              \
+        vxxe += hxxe - rxxe[i]; vxye += hxye - oxye; vyye += hyye - oyye;                                              \
+        vxxo += hxxo - rxxo[i]; vxyo += hxyo - oxyo; vyyo += hyyo - oyyo;                                              \
+        rxxe[i] = hxxe; rxxo[i] = hxxo;                                                                                \
+        s_ring[(4 * i) * 64 + lane] = hyye; s_ring[(4 * i + 1) * 64 + lane] = hyyo;                                    \
+        s_ring[(4 * i + 2) * 64 + lane] = hxye; s_ring[(4 * i + 3) * 64 + lane] = hxyo;                                \
+        const int yo = ya - 2 + r - BS;                                                                                \
+        float apce, apco;                                                                                              \
+        const int e2e = lambda_min_bits_f(vxxe, vxye, vyye, kdv, apce), e2o = lambda_min_bits_f(vxxo, vxyo, vyyo, kdv, apco); \
+        inexact |= __builtin_amdgcn_ballot_w64(fmaxf(apce, apco) >= lim);                                              \
+        OFK_PAIR_ROW_TAIL(IN)                                                                                          \
+        r01e = r12e; r01o = r12o; g1e = ge2; g1o = go2;                                                                  \
+    }
+// Running maximum, 3x3 NMS and keys of one row (both datapaths).
+#define OFK_PAIR_ROW_TAIL(IN)                                                                                          \
         if ((IN) && !MASK) {                                                                                           \
             lmaxi = max(max(lmaxi, e2e), e2o);                                                                         \
         } else {                                                                                                       \
@@ -715,9 +801,7 @@ __device__ __forceinline__ int lambda_min_bits(int vxx, int vxy, int vyy, float 
         const int ne = (int)__popcll(bale);                                                                            \
         OFK_PAIR_KEY_STORE()                                                                                           \
         cnt += ne + (int)__popcll(balo);                                                                               \
-        e1e = e2e; e1o = e2o; hm0e = hm1e; hm0o = hm1o; hm1e = hm2e; hm1o = hm2o;                                      \
-        r01e = r12e; r01o = r12o; g1e = ge2; g1o = go2;                                                                  \
-    }
+        e1e = e2e; e1o = e2o; hm0e = hm1e; hm0o = hm1o; hm1e = hm2e; hm1o = hm2o;
 
 template <int BS> struct pair_geom {
     static constexpr int AN = BS / 2, PAD = (2 + AN + 3) & ~3, D = PAD - 2 - AN, SW = (125 - BS) & ~3;
@@ -744,7 +828,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void
     // worth of keys instead of a block's: 125 VGPRs and 10 KB of LDS per wave = FOUR waves per SIMD (all 42 ring values in
     // registers: 168 VGPRs, three waves).  Alone on the chip 1.03 -> 0.96 ms; with the yy ring only (150 VGPRs, three waves, room
     // for a gray wave beside them) the kernel alone was no faster but the step 2.4 % shorter — four waves are another 1 % on top.
-    __shared__ int s_ring[4 * BS * 64];
+    __shared__ int s_ring_mem[4 * BS * 64];
     const int lane = threadIdx.x;
     // XCD-aware block -> (image, chunk, strip block) map: workgroups are dealt round-robin over the 8 XCDs (blocks n and
     // n + 8 share one L2); an image's strips and chunks go to ONE XCD, so the halo columns and rows they share are fetched once.
@@ -776,11 +860,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void
     const int nstrips = (w + D + SW - 1) / SW;
     const int nseg = nstrips * (int)gridDim.y, segid = byi * nstrips + sx;
     unsigned long long *myseg = seg + ((size_t)b * nseg + segid) * seg_cap;
-    int written = 0, cnt = 0;
-    int lmaxi = 0;
-    float published = 0.f;
-    unsigned mb_seen = __hip_atomic_load(maxbits + b * OFK_MAX_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    float thr = (float)((double)__uint_as_float(mb_seen) * quality);
 
     // loader role: lane (lrow, lk) fetches dword lk of the 128-byte row segment of row lrow of a row pair (clamped into the
     // image: the clamped dwords only ever feed mirrored columns, which are patched below).  consumer role: the pair of
@@ -808,56 +887,95 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void
 
     float kdv = kd;
     asm volatile("" : "+v"(kdv));                               // keep the scale factor in a VGPR (see lambda_min_bits)
-    int r01e = 0, r01o = 0, g1e = 0, g1o = 0;                   // previous gray row and the sum of the two before it (per slot)
-    int rxxe[BS], rxxo[BS];
+    const int adk = ((lane - AN) & 63) * 4;                     // f32 rows: the odd factors of lane l - BS/2 (box_pair_f)
+    // The 2^24 guard of the f32 rows.  A row sets the lanes of `inexact` where fl(fl(Sxx kd) + fl(Syy kd)) >= lim; the rows stay
+    // exact while every Sxx + Syy <= 2^24 (box_pair_f).  Let row r be the first with an inexact value: before it every f32 value is
+    // the integer, and the only operation that can round is the add that completes a vertical sum (every other result is below
+    // 2^23), so its exact result passed 2^24 and Sxx + Syy >= 2^24 + 1.  The f32 Sxx and Syy of row r are those integers rounded once,
+    // and a, c, a + c three more roundings, each monotone with a relative error <= 2^-24: a + c >= (2^24 + 1) kd (1 - 2^-24)^3
+    // > (2^24 - 3) kd, while lim <= (2^24 - 256) kd (1 + 2^-24) < (2^24 - 255) kd.  So row r itself sets the flag, which is never
+    // cleared (an SGPR pair: a running maximum in a VGPR cost the loop five registers and its fourth wave).  The flag is tested at every block boundary before the strip maximum is published and before the tail: keys
+    // spilled to the segment in between are overwritten by the integer pass, which restarts the strip from scratch.  Rows of warm-up
+    // garbage and lanes outside the strip hold bounded sums of the same kind, so they can only fire the guard early (never on
+    // 8-bit footage: Sxx + Syy near 2^24 needs a mean gradient above ~580 over a whole 7x7 window).
+    const float lim = kd * 16776960.f;                          // (2^24 - 256) kd
+    // One march down the strip on the f32 (FP) or the integer rows; false = the guard fired, nothing was published.
+    auto march = [&](auto fp) -> bool {
+        constexpr bool FP = decltype(fp)::value;
+        using T = typename std::conditional<FP, float, int>::type;
+        T *const s_ring = reinterpret_cast<T *>(s_ring_mem);
+        int written = 0, cnt = 0;
+        int lmaxi = 0;
+        float published = 0.f;
+        unsigned mb_seen = __hip_atomic_load(maxbits + b * OFK_MAX_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        float thr = (float)((double)__uint_as_float(mb_seen) * quality);
+        T r01e = 0, r01o = 0, g1e = 0, g1o = 0;                 // previous gray row and the sum of the two before it (per slot)
+        T rxxe[BS], rxxo[BS];
 #pragma unroll
-    for (int i = 0; i < BS; ++i) { rxxe[i] = rxxo[i] = 0; }
+        for (int i = 0; i < BS; ++i) { rxxe[i] = rxxo[i] = 0; }
 #pragma unroll
-    for (int i = 0; i < 4 * BS; ++i) s_ring[i * 64 + lane] = 0;
-    int vxxe = 0, vxye = 0, vyye = 0, vxxo = 0, vxyo = 0, vyyo = 0;
-    int e1e = 0, e1o = 0, hm0e = 0, hm0o = 0, hm1e = 0, hm1o = 0;
-    int nextg[NL];
-    OFK_PAIR_LOAD(0, nextg)
+        for (int i = 0; i < 4 * BS; ++i) s_ring[i * 64 + lane] = 0;
+        T vxxe = 0, vxye = 0, vyye = 0, vxxo = 0, vxyo = 0, vyyo = 0;
+        int e1e = 0, e1o = 0, hm0e = 0, hm0o = 0, hm1e = 0, hm1o = 0;
+        unsigned long long inexact = 0;                         // lanes whose a + c reached lim (the guard; an SGPR pair)
+        int nextg[NL];
+        OFK_PAIR_LOAD(0, nextg)
 
-    for (int base = 0; base < nsteps; base += BS) {
-        int curv[BS];
+        for (int base = 0; base < nsteps; base += BS) {
+            int curv[BS];
 #pragma unroll
-        for (int i = 0; i < BS; ++i) curv[i] = __builtin_amdgcn_ds_bpermute(srcsel + 128 * (i & 1), nextg[i >> 1]);
-        {
-            unsigned cur_seen = (unsigned)__builtin_amdgcn_readfirstlane((int)mb_seen);
-            if (__float_as_uint(published) > cur_seen) cur_seen = __float_as_uint(published);
-            thr = (float)((double)__uint_as_float(cur_seen) * quality);
-        }
-        if (cnt >= 64) {                                        // move full 64-key chunks to this strip's segment, publish the maximum
-            OFK_PAIR_SPILL_KEYS()
-            const float mw = wave_max_f32(lane_ok ? __int_as_float(lmaxi) : 0.f);
-            if (mw > published) {
-                if (lane == 0) (void)atomicMax(maxbits + b * OFK_MAX_STRIDE, __float_as_uint(mw));
-                published = mw;
+            for (int i = 0; i < BS; ++i) curv[i] = __builtin_amdgcn_ds_bpermute(srcsel + 128 * (i & 1), nextg[i >> 1]);
+            if constexpr (FP) {
+                if (inexact) return false;
             }
-            mb_seen = __hip_atomic_load(maxbits + b * OFK_MAX_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            {
+                unsigned cur_seen = (unsigned)__builtin_amdgcn_readfirstlane((int)mb_seen);
+                if (__float_as_uint(published) > cur_seen) cur_seen = __float_as_uint(published);
+                thr = (float)((double)__uint_as_float(cur_seen) * quality);
+            }
+            if (cnt >= 64) {                                    // move full 64-key chunks to this strip's segment, publish the maximum
+                OFK_PAIR_SPILL_KEYS()
+                const float mw = wave_max_f32(lane_ok ? __int_as_float(lmaxi) : 0.f);
+                if (mw > published) {
+                    if (lane == 0) (void)atomicMax(maxbits + b * OFK_MAX_STRIDE, __float_as_uint(mw));
+                    published = mw;
+                }
+                mb_seen = __hip_atomic_load(maxbits + b * OFK_MAX_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            OFK_PAIR_LOAD(base + BS, nextg)                     // prefetch the next block of rows
+            const int r1 = base + BS - 1;
+            const bool interior = !edge_strip && Yp0 + base - 2 >= 0 && Yp0 + r1 - 2 < h && base >= BS + 3 && ya - 3 + base - BS >= 1 &&
+                                  ya - 2 + r1 - BS < yb && ya - 3 + r1 - BS < h - 1;
+            const int thrb = __float_as_int(fmaxf(thr, 0.f)) + 1;
+            const int thr1e = nms_e ? thrb : 0x7fffffff, thr1o = nms_o ? thrb : 0x7fffffff;
+            if constexpr (FP) {
+                if (interior) { OFK_PAIR_ROWS_F32(true) } else { OFK_PAIR_ROWS_F32(false) }
+            } else {
+                if (interior) { OFK_PAIR_ROWS(true) } else { OFK_PAIR_ROWS(false) }
+            }
         }
-        OFK_PAIR_LOAD(base + BS, nextg)                         // prefetch the next block of rows
-        const int r1 = base + BS - 1;
-        const bool interior = !edge_strip && Yp0 + base - 2 >= 0 && Yp0 + r1 - 2 < h && base >= BS + 3 && ya - 3 + base - BS >= 1 &&
-                              ya - 2 + r1 - BS < yb && ya - 3 + r1 - BS < h - 1;
-        const int thrb = __float_as_int(fmaxf(thr, 0.f)) + 1;
-        const int thr1e = nms_e ? thrb : 0x7fffffff, thr1o = nms_o ? thrb : 0x7fffffff;
-        if (interior) { OFK_PAIR_ROWS(true) } else { OFK_PAIR_ROWS(false) }
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (int i = lane; i < cnt; i += 64)
-        if (written + i < seg_cap) myseg[written + i] = buf[i];
-    if (lane == 0) {
-        seg_count[(size_t)b * nseg + segid] = min(written + cnt, seg_cap);
-        if (written + cnt > seg_cap) (void)atomicOr(flags, 1);
-    }
-    const float mw = wave_max_f32(lane_ok ? __int_as_float(lmaxi) : 0.f);
-    if (lane == 0 && mw > published) (void)atomicMax(maxbits + b * OFK_MAX_STRIDE, __float_as_uint(mw));
+        if constexpr (FP) {
+            if (inexact) return false;
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (int i = lane; i < cnt; i += 64)
+            if (written + i < seg_cap) myseg[written + i] = buf[i];
+        if (lane == 0) {
+            seg_count[(size_t)b * nseg + segid] = min(written + cnt, seg_cap);
+            if (written + cnt > seg_cap) (void)atomicOr(flags, 1);
+        }
+        const float mw = wave_max_f32(lane_ok ? __int_as_float(lmaxi) : 0.f);
+        if (lane == 0 && mw > published) (void)atomicMax(maxbits + b * OFK_MAX_STRIDE, __float_as_uint(mw));
+        return true;
+    };
+    if (!march(std::true_type{})) march(std::false_type{});
 }
 
 #undef OFK_PAIR_LOAD
 #undef OFK_PAIR_ROWS
+#undef OFK_PAIR_ROWS_F32
+#undef OFK_PAIR_ROW_TAIL
+#undef OFK_RING_READ
 #undef OFK_PAIR_SPILL_KEYS
 #undef OFK_LOAD_BLOCK
 #undef OFK_EIG_ROWS

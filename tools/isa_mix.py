@@ -4,9 +4,9 @@
   python tools/isa_mix.py [--rates profiles/r04_valu_rates.txt] [--valu profiles/r04_valu_pmc.json] > profiles/r04_isa_mix.json
 
 1. hipcc -S (device only, the product's flags) of k_corners.hip and k_lk.hip.
-2. k_mineig_pair<7,false>: the main loop holds 7 unrolled rows twice (border version, interior version; 2 v_rsq_f32 per row since round 4).
-   The INTERIOR version (the one almost every row of a 1080p frame runs) is the half of the loop body with fewer instructions;
-   its instructions are counted per mnemonic.  k_lk15q: the whole kernel body (level set-up + Newton loop).
+2. k_mineig_pair<7,false>: each march holds 7 unrolled rows twice (border version, interior version; 2 v_rsq_f32 per row since round 4);
+   since round 5 there are two marches, f32 rows and the integer rows of the 2^24 fallback.  The INTERIOR version of the f32 rows (the one
+   almost every row of a 1080p frame runs) is counted per mnemonic; the integer rows' total is reported beside it.  k_lk15q: the whole kernel body (level set-up + Newton loop).
 3. Every VALU mnemonic is priced with its measured issue cost (tools/valu_rates.hip on the GPU box: ns per wave-instruction
    per SIMD with 8 waves per SIMD, converted to clocks at the clock the probe ran at = cost relative to v_add_u32 x 2).
 4. issue floor per pair = (dynamic wave-level VALU instructions per pair, SQ_INSTS_VALU from the committed PMC pass)
@@ -125,16 +125,22 @@ def mix(instrs, rates):
             "vmem_instructions": other["vmem"], "by_mnemonic": {k: {"count": by[k], "clocks_each": cyc[k] // by[k]} for k in sorted(by, key=lambda k: -cyc[k])}}
 
 
-def pair_interior_rows(body):
-    """The interior 7-row version of k_mineig_pair's loop: split the loop body at the label in front of the 15th v_rsq_f32 (the square root of lambda_min: v_sqrt_f32 until round 3)."""
+def pair_row_versions(body):
+    """The 7-row versions of k_mineig_pair's loops, split at the label in front of every 14th v_rsq_f32 (the square root of lambda_min,
+    two per row).  Since round 5 the kernel holds two marches - f32 rows and the integer rows a strip restarts on past 2^24 - each with a
+    border and an interior version: 56 v_rsq_f32 (28 before)."""
     sq = [i for i, l in enumerate(body) if "v_rsq_f32" in l]
-    if len(sq) != 28:
-        raise SystemExit(f"expected 28 v_rsq_f32 in k_mineig_pair<7,false> (2 versions x 7 rows x 2 columns), found {len(sq)}")
+    if len(sq) not in (28, 56):
+        raise SystemExit(f"expected 28 or 56 v_rsq_f32 in k_mineig_pair<7,false> (versions x 7 rows x 2 columns), found {len(sq)}")
     label = lambda i: max(j for j in range(i) if body[j].startswith(".LBB"))
-    start_a, start_b = label(sq[0]), label(sq[14])
-    end_b = next(j for j in range(sq[27], len(body)) if body[j].startswith(".LBB") and "s_cbranch" not in body[j] and j > sq[27] + 40)
-    half_a, half_b = body[start_a:start_b], body[start_b:end_b]
-    return (half_a, "first") if len(mnemonics(half_a)) < len(mnemonics(half_b)) else (half_b, "second")
+    end = lambda i: next(j for j in range(i, len(body)) if body[j].startswith(".LBB") and "s_cbranch" not in body[j] and j > i + 40)
+    return [body[label(sq[k]):end(sq[k + 13])] for k in range(0, len(sq), 14)]
+
+
+def pair_interior_rows(body, f32=True):
+    """The interior version (fewer instructions than the border one) of the f32 rows (no v_cvt_f32_i32) or of the integer rows."""
+    versions = [v for v in pair_row_versions(body) if any("v_cvt_f32_i32" in l for l in v) != f32] or pair_row_versions(body)
+    return min(versions, key=lambda v: len(mnemonics(v))), ("f32" if f32 else "integer")
 
 
 def main():
@@ -156,10 +162,14 @@ def main():
     body = body_of(corners, "_Z13k_mineig_pairILi7ELb0EEvPKhmiiiffPjS1_mdPyiPiS4_")
     rows, which = pair_interior_rows(body)
     m = mix(mnemonics(rows), rates)
-    m["scope"] = (f"interior version of the 7 unrolled rows ({which} half of the loop body, the three rarely taken key-spill blocks included): "
+    m["scope"] = (f"interior version of the 7 unrolled {which} rows (the three rarely taken key-spill blocks included): "
                   "per wave-row = these counts / 7; the issue floor uses the DYNAMIC instruction count (PMC) with this mix's mean cost")
     m["valu_per_wave_row"] = round(m["valu_instructions"] / 7, 1)
     m["issue_cycles_per_wave_row"] = round(m["valu_issue_cycles"] / 7, 1)
+    irows, _ = pair_interior_rows(body, f32=False)
+    im = mix(mnemonics(irows), rates)
+    m["integer_rows_valu_per_wave_row"] = round(im["valu_instructions"] / 7, 1)
+    m["integer_rows_issue_cycles_per_wave_row"] = round(im["valu_issue_cycles"] / 7, 1)
     dyn = valu["stages"]["eig"]["SQ_INSTS_VALU_per_launch"] / valu["batch"]
     m["SQ_INSTS_VALU_per_pair"] = int(dyn)
     m["valu_issue_cycles_per_pair"] = int(dyn * m["mean_cycles_per_valu_instr"])

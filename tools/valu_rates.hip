@@ -104,6 +104,10 @@
 #define A_ADD_SDWA(r) "v_add_u32_sdwa " r ", " r ", " r " dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:DWORD\n"
 #define A_DOT2_S(r) "v_dot2_i32_i16 " r ", " r ", " r ", s10\n"
 #define A_ALIGNBYTE_V(r) "v_alignbyte_b32 " r ", " r ", " r ", %8\n"
+#define A_CVTUB1(r) "v_cvt_f32_ubyte1 " r ", " r "\n"
+#define A_ADDF_DPP(r) "v_add_f32_dpp " r ", " r ", " r " wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
+#define A_SUBREVF_DPP(r) "v_subrev_f32_dpp " r ", " r ", " r " wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
+#define A_SUBF_DPP(r) "v_sub_f32_dpp " r ", " r ", " r " wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
 
 KERNEL(k_add, A_ADD)
 KERNEL(k_add3, A_ADD3)
@@ -178,6 +182,10 @@ KERNEL(k_mul24_sdwa, A_MUL24_SDWA)
 KERNEL(k_add_sdwa, A_ADD_SDWA)
 KERNEL(k_alignbyte_v, A_ALIGNBYTE_V)
 KERNEL(k_dot2_s, A_DOT2_S)
+KERNEL(k_cvtub1, A_CVTUB1)
+KERNEL(k_addf_dpp, A_ADDF_DPP)
+KERNEL(k_subrevf_dpp, A_SUBREVF_DPP)
+KERNEL(k_subf_dpp, A_SUBF_DPP)
 
 // Which clock does the chip hold while every SIMD issues VALU instructions back to back?  One lane per workgroup reads the shader
 // cycle counter (s_memtime) and the constant-rate counter (s_memrealtime) around ITER x 32 x 8 dependent-free v_add_u32 per wave.
@@ -224,7 +232,8 @@ int main()
         {"v_mad_i32_i16 op_sel", k_madi16}, {"v_cvt_flr_i32_f32", k_cvtflr}, {"v_add_u32_dpp row_ror", k_add_dpp_ror},
         {"v_add_u32_dpp row_shl", k_add_dpp_rshl}, {"v_dot2c_i32_i16 (VOP2)", k_dot2c}, {"v_mul_i32_i24_sdwa", k_mul24_sdwa},
         {"v_add_u32_sdwa", k_add_sdwa}, {"v_alignbyte_b32 (vgpr shift)", k_alignbyte_v},
-        {"v_dot2_i32_i16 (sgpr acc)", k_dot2_s}};
+        {"v_dot2_i32_i16 (sgpr acc)", k_dot2_s}, {"v_cvt_f32_ubyte1", k_cvtub1}, {"v_add_f32_dpp wave_shr", k_addf_dpp},
+        {"v_subrev_f32_dpp wave_shr", k_subrevf_dpp}, {"v_sub_f32_dpp wave_shl", k_subf_dpp}};
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     double base = 0;
