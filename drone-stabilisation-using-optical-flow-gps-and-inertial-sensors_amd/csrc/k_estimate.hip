@@ -67,7 +67,7 @@ __device__ __forceinline__ double block_minmax(double v, bool want_max, double *
 
 // All eleven sums at once: the wave reductions are independent shuffle chains the scheduler interleaves, and ONE LDS exchange
 // (two barriers) replaces eleven; the order of the additions is block_sum's, so the results are the same bit for bit.
-__device__ void acc_block_sum(Acc &a, double *)
+__device__ void acc_block_sum(Acc &a)
 {
     __shared__ double s_part[4][11];
     double v[11] = {a.m00, a.m01, a.m02, a.m11, a.m12, a.m22, a.g0, a.g1, a.g2, a.bb, a.cnt};
@@ -163,6 +163,60 @@ __device__ __forceinline__ void point_terms(int variant, double x, double y, dou
     }
 }
 
+// o = v - a x b
+__device__ __forceinline__ void sub_cross(const double *v, const double *a, const double *b, double *o)
+{
+    o[0] = v[0] - (a[1] * b[2] - a[2] * b[1]); o[1] = v[1] - (a[2] * b[0] - a[0] * b[2]); o[2] = v[2] - (a[0] * b[1] - a[1] * b[0]);
+}
+
+// v_uav = R (v_obs - [w]x offset): lever arm, then rotation (node:258)
+__device__ __forceinline__ void lever_rotate(const double *v, const double *om, const double *off, const double *R, double *vu)
+{
+    double e[3];
+    sub_cross(v, om, off, e);
+    vu[0] = R[0] * e[0] + R[1] * e[1] + R[2] * e[2]; vu[1] = R[3] * e[0] + R[4] * e[1] + R[5] * e[2]; vu[2] = R[6] * e[0] + R[7] * e[1] + R[8] * e[2];
+}
+
+// Fields 0-13 of a pair record (ofk.h); 14 and 15 are the caller's.  vu receives v_uav.
+__device__ __forceinline__ void write_record(double *o, const double *v, double r, double rank, const double *s3, const double *om,
+                                             const double *off, const double *R, double cnt, int n, double tracked, double *vu)
+{
+    lever_rotate(v, om, off, R, vu);
+    o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = r; o[4] = rank; o[5] = s3[0]; o[6] = s3[1]; o[7] = s3[2];
+    o[8] = vu[0]; o[9] = vu[1]; o[10] = vu[2]; o[11] = cnt; o[12] = (double)n; o[13] = tracked;
+}
+
+struct Solved { double v[3], rank, s3[3], cnt; };
+
+// The least squares of one 256-thread block: point(i, a) adds point i = tid, tid + 256, ... to a (or skips it), the sums meet
+// in acc_block_sum, thread 0 solves when more than min_cnt points entered (else v = s = 0, rank 0), every thread gets the result.
+// The broadcast's barrier also orders any global writes of point() before what the block does next.
+template <class Point>
+__device__ __forceinline__ Solved block_lstsq(int n, double min_cnt, Point point)
+{
+    __shared__ double s_v[7];
+    Acc a; acc_zero(a);
+    for (int i = threadIdx.x; i < n; i += 256) point(i, a);
+    acc_block_sum(a);
+    if (threadIdx.x == 0) {
+        double v[3] = {0, 0, 0}, s3[3] = {0, 0, 0};
+        const int rank = a.cnt > min_cnt ? solve_from_acc(a, v, s3) : 0;
+        s_v[0] = v[0]; s_v[1] = v[1]; s_v[2] = v[2]; s_v[3] = (double)rank; s_v[4] = s3[0]; s_v[5] = s3[1]; s_v[6] = s3[2];
+    }
+    __syncthreads();
+    return Solved{{s_v[0], s_v[1], s_v[2]}, s_v[3], {s_v[4], s_v[5], s_v[6]}, a.cnt};
+}
+
+// The same walk over the points for a second pass: point(i, r) adds point i's term to r; the block's sum in every thread.
+template <class Point>
+__device__ __forceinline__ double block_point_sum(int n, Point point)
+{
+    __shared__ double s_red[4];
+    double r = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) point(i, r);
+    return block_sum(r, s_red);
+}
+
 // ------------------------------------------------------------------------------------------------ generic batched solve
 __global__ __launch_bounds__(256) void k_solve(int variant, const double *__restrict__ x, const double *__restrict__ u,
                                                const uint8_t *__restrict__ valid, int n, const double *__restrict__ d,
@@ -170,9 +224,7 @@ __global__ __launch_bounds__(256) void k_solve(int variant, const double *__rest
                                                const double *__restrict__ t, const double *__restrict__ wgt,
                                                double *__restrict__ out)
 {
-    __shared__ double s_red[4];
-    __shared__ double s_v[8];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x;
     const double *xb = x + (size_t)b * n * 2, *ub = u + (size_t)b * n * 2;
     const uint8_t *vb = valid ? valid + (size_t)b * n : nullptr;
     const double *wb = wgt ? wgt + (size_t)b * n : nullptr;
@@ -180,39 +232,24 @@ __global__ __launch_bounds__(256) void k_solve(int variant, const double *__rest
     double ob[3] = {0, 0, 0};
     if (omega) { ob[0] = omega[3 * b]; ob[1] = omega[3 * b + 1]; ob[2] = omega[3 * b + 2]; }
     const double db = d ? d[b] : 1.0;
-    Acc a; acc_zero(a);
-    for (int i = tid; i < n; i += 256) {
-        if (vb && !vb[i]) continue;
-        double q0, q1, q2, sA, sB;
+    auto terms = [&](int i, double &q0, double &q1, double &q2, double &sA, double &sB) {
+        if (vb && !vb[i]) return false;
         point_terms(variant, xb[2 * i], xb[2 * i + 1], ub[2 * i], ub[2 * i + 1], nb, ob, db, wb ? wb[i] : 1.0, q0, q1, q2, sA, sB);
-        acc_point(a, xb[2 * i], xb[2 * i + 1], q0, q1, q2, sA, sB);
-    }
-    acc_block_sum(a, s_red);
-    if (tid == 0) {
-        double v[3], s3[3];
-        const int rank = a.cnt > 0.0 ? solve_from_acc(a, v, s3) : 0;
-        if (a.cnt <= 0.0) { v[0] = v[1] = v[2] = 0.0; s3[0] = s3[1] = s3[2] = 0.0; }
-        s_v[0] = v[0]; s_v[1] = v[1]; s_v[2] = v[2]; s_v[3] = (double)rank; s_v[4] = s3[0]; s_v[5] = s3[1]; s_v[6] = s3[2];
-        s_v[7] = a.cnt;
-    }
-    __syncthreads();
-    const double v[3] = {s_v[0], s_v[1], s_v[2]};
-    double r = 0.0;
-    for (int i = tid; i < n; i += 256) {
-        if (vb && !vb[i]) continue;
+        return true;
+    };
+    const Solved s = block_lstsq(n, 0.0, [&](int i, Acc &a) {
         double q0, q1, q2, sA, sB;
-        point_terms(variant, xb[2 * i], xb[2 * i + 1], ub[2 * i], ub[2 * i + 1], nb, ob, db, wb ? wb[i] : 1.0, q0, q1, q2, sA, sB);
-        r += resid_point(xb[2 * i], xb[2 * i + 1], q0, q1, q2, sA, sB, v);
-    }
-    r = block_sum(r, s_red);
-    if (tid == 0) {
+        if (terms(i, q0, q1, q2, sA, sB)) acc_point(a, xb[2 * i], xb[2 * i + 1], q0, q1, q2, sA, sB);
+    });
+    const double r = block_point_sum(n, [&](int i, double &r) {
+        double q0, q1, q2, sA, sB;
+        if (terms(i, q0, q1, q2, sA, sB)) r += resid_point(xb[2 * i], xb[2 * i + 1], q0, q1, q2, sA, sB, s.v);
+    });
+    if (threadIdx.x == 0) {
         double *o = out + (size_t)b * OFK_SOLVE_DOUBLES;
-        double vx = v[0], vy = v[1], vz = v[2];
-        if (t) {                                              // v - omega x t
-            const double *tb = t + 3 * b;
-            vx -= ob[1] * tb[2] - ob[2] * tb[1]; vy -= ob[2] * tb[0] - ob[0] * tb[2]; vz -= ob[0] * tb[1] - ob[1] * tb[0];
-        }
-        o[0] = vx; o[1] = vy; o[2] = vz; o[3] = r; o[4] = s_v[3]; o[5] = s_v[4]; o[6] = s_v[5]; o[7] = s_v[6];
+        if (t) sub_cross(s.v, ob, t + 3 * b, o);                // v - omega x t
+        else { o[0] = s.v[0]; o[1] = s.v[1]; o[2] = s.v[2]; }
+        o[3] = r; o[4] = s.rank; o[5] = s.s3[0]; o[6] = s.s3[1]; o[7] = s.s3[2];
     }
 }
 
@@ -238,6 +275,35 @@ __device__ __forceinline__ void rtilde_point(double x, double y, double ux, doub
     const double pn = x * n[0] + y * n[1] + n[2];
     if (pn < 0.0) r = -r;
     dd = pn * vn * iun / dist;
+}
+
+// pixhawk_pure_IMU/of_library.py:365-380 (4-arg r_tilde): no zero guard, no division by the distance
+__device__ __forceinline__ void legacy_point(double x, double y, double ux, double uy, const double *n, const double *v, double &r, double &dd)
+{
+    double vc0, vc1, vc2, uc0, uc1, uc2;
+    cross_p(x, y, v[0], v[1], v[2], vc0, vc1, vc2);
+    vc0 = -vc0; vc1 = -vc1; vc2 = -vc2;
+    cross_p(x, y, ux, uy, 0.0, uc0, uc1, uc2);
+    const double vn = sqrt(vc0 * vc0 + vc1 * vc1 + vc2 * vc2), iun = 1.0 / sqrt(uc0 * uc0 + uc1 * uc1 + uc2 * uc2);
+    r = (vc0 * uc0 + vc1 * uc1 + vc2 * uc2) * iun / vn;
+    const double pn = x * n[0] + y * n[1] + n[2];
+    if (pn < 0.0) r = -r;
+    dd = pn * vn * iun;
+}
+
+// simulation.py:108-120: feasibility of velocity vv (less omega x t) against the flow less the rotational part omega x p
+__device__ __forceinline__ void feas_sim_point(double px, double py, double ux, double uy, const double *vv, const double *om,
+                                               const double *tb, const double *nn, double &rr, double &dv)
+{
+    double l[3];
+    sub_cross(vv, om, tb, l);
+    const double w0 = om[1] - om[2] * py, w1 = om[2] * px - om[0], w2 = om[0] * py - om[1] * px;   // omega x p
+    double f0, f1, f2, g0, g1, g2;
+    cross_p(px, py, l[0], l[1], l[2], f0, f1, f2);
+    cross_p(px, py, ux - w0, uy - w1, -w2, g0, g1, g2);
+    const double n1 = sqrt(f0 * f0 + f1 * f1 + f2 * f2), n2 = sqrt(g0 * g0 + g1 * g1 + g2 * g2);
+    rr = (f0 * g0 + f1 * g1 + f2 * g2) / (n1 * n2);
+    dv = n1 / n2 * (px * nn[0] + py * nn[1] + nn[2]);
 }
 
 // ------------------------------------------------------------------------------------------------ frame-pair solve
@@ -320,15 +386,9 @@ __global__ __launch_bounds__(64) void k_pairs_solve(const float *__restrict__ pr
     __builtin_amdgcn_wave_barrier();
     const double r = (part[0][12] + part[1][12]) + (part[2][12] + part[3][12]);
     if (lane == 0) {
-        double *o = records + (size_t)b * OFK_RECORD_DOUBLES;
-        const double *R = sn + 7, *off = sn + 16;
-        // v_obs - [w]x offset, then rotate (node:258)
-        const double e0 = v[0] - (om[1] * off[2] - om[2] * off[1]);
-        const double e1 = v[1] - (om[2] * off[0] - om[0] * off[2]);
-        const double e2 = v[2] - (om[0] * off[1] - om[1] * off[0]);
-        o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = r; o[4] = (double)rank; o[5] = s3[0]; o[6] = s3[1]; o[7] = s3[2];
-        o[8] = R[0] * e0 + R[1] * e1 + R[2] * e2; o[9] = R[3] * e0 + R[4] * e1 + R[5] * e2; o[10] = R[6] * e0 + R[7] * e1 + R[8] * e2;
-        o[11] = a.cnt; o[12] = (double)n; o[13] = tracked; o[14] = cand_count ? (double)cand_count[b * OFK_CNT_STRIDE] : 0.0; o[15] = 0.0;
+        double *o = records + (size_t)b * OFK_RECORD_DOUBLES, vu[3];
+        write_record(o, v, r, (double)rank, s3, om, sn + 16, sn + 7, a.cnt, n, tracked, vu);
+        o[14] = cand_count ? (double)cand_count[b * OFK_CNT_STRIDE] : 0.0; o[15] = 0.0;
     }
 }
 
@@ -342,64 +402,35 @@ __global__ __launch_bounds__(256) void k_pairs_solve_wg(const float *__restrict_
                                                      double *__restrict__ records)
 {
     __shared__ double s_red[4];
-    __shared__ double s_v[8];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x;
     const double *sn = sensors + (size_t)b * OFK_SENSOR_DOUBLES;
     const double d = sn[0], nrm[3] = {sn[1], sn[2], sn[3]}, om[3] = {sn[4], sn[5], sn[6]};
     const double scaling = sn[19], cx = sn[20], cy = sn[21], vp[3] = {sn[22], sn[23], sn[24]};
     const int n = counts[b];
     const float *pp = prev_pts + (size_t)b * pts_stride * 2, *np_ = next_pts + (size_t)b * pts_stride * 2;
     const uint8_t *st = status + (size_t)b * pts_stride;
-    Acc a; acc_zero(a);
+    auto terms = [&](int i, double &x, double &y, double &q0, double &q1, double &q2, double &sA, double &sB) {
+        double ux, uy;
+        if (!pair_point(pp, np_, i, cx, cy, scaling, use_feas, feas_T, nrm, vp, d, x, y, ux, uy)) return false;
+        point_terms(variant, x, y, ux, uy, nrm, om, d, 1.0, q0, q1, q2, sA, sB);
+        return true;
+    };
     double tracked = 0.0;
-    for (int i = tid; i < n; i += 256) {
-        if (!st[i]) continue;
+    const Solved s = block_lstsq(n, 0.0, [&](int i, Acc &a) {
+        if (!st[i]) return;
         tracked += 1.0;
-        const double x = ((double)np_[2 * i] - cx) * scaling, y = ((double)np_[2 * i + 1] - cy) * scaling;
-        const double ux = ((double)np_[2 * i] - (double)pp[2 * i]) * scaling, uy = ((double)np_[2 * i + 1] - (double)pp[2 * i + 1]) * scaling;
-        if (use_feas) {
-            double r, dd;
-            rtilde_point(x, y, ux, uy, nrm, vp, d, r, dd);
-            if (!(r <= feas_T)) continue;
-        }
-        double q0, q1, q2, sA, sB;
-        point_terms(variant, x, y, ux, uy, nrm, om, d, 1.0, q0, q1, q2, sA, sB);
-        acc_point(a, x, y, q0, q1, q2, sA, sB);
-    }
-    acc_block_sum(a, s_red);
+        double x, y, q0, q1, q2, sA, sB;
+        if (terms(i, x, y, q0, q1, q2, sA, sB)) acc_point(a, x, y, q0, q1, q2, sA, sB);
+    });
     tracked = block_sum(tracked, s_red);
-    if (tid == 0) {
-        double v[3] = {0, 0, 0}, s3[3] = {0, 0, 0};
-        const int rank = a.cnt > 0.0 ? solve_from_acc(a, v, s3) : 0;
-        s_v[0] = v[0]; s_v[1] = v[1]; s_v[2] = v[2]; s_v[3] = (double)rank; s_v[4] = s3[0]; s_v[5] = s3[1]; s_v[6] = s3[2];
-    }
-    __syncthreads();
-    const double v[3] = {s_v[0], s_v[1], s_v[2]};
-    double r = 0.0;
-    for (int i = tid; i < n; i += 256) {
-        if (!st[i]) continue;
-        const double x = ((double)np_[2 * i] - cx) * scaling, y = ((double)np_[2 * i + 1] - cy) * scaling;
-        const double ux = ((double)np_[2 * i] - (double)pp[2 * i]) * scaling, uy = ((double)np_[2 * i + 1] - (double)pp[2 * i + 1]) * scaling;
-        if (use_feas) {
-            double rr, dd;
-            rtilde_point(x, y, ux, uy, nrm, vp, d, rr, dd);
-            if (!(rr <= feas_T)) continue;
-        }
-        double q0, q1, q2, sA, sB;
-        point_terms(variant, x, y, ux, uy, nrm, om, d, 1.0, q0, q1, q2, sA, sB);
-        r += resid_point(x, y, q0, q1, q2, sA, sB, v);
-    }
-    r = block_sum(r, s_red);
-    if (tid == 0) {
-        double *o = records + (size_t)b * OFK_RECORD_DOUBLES;
-        const double *R = sn + 7, *off = sn + 16;
-        // v_obs - [w]x offset, then rotate (node:258)
-        const double e0 = v[0] - (om[1] * off[2] - om[2] * off[1]);
-        const double e1 = v[1] - (om[2] * off[0] - om[0] * off[2]);
-        const double e2 = v[2] - (om[0] * off[1] - om[1] * off[0]);
-        o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = r; o[4] = s_v[3]; o[5] = s_v[4]; o[6] = s_v[5]; o[7] = s_v[6];
-        o[8] = R[0] * e0 + R[1] * e1 + R[2] * e2; o[9] = R[3] * e0 + R[4] * e1 + R[5] * e2; o[10] = R[6] * e0 + R[7] * e1 + R[8] * e2;
-        o[11] = a.cnt; o[12] = (double)n; o[13] = tracked; o[14] = cand_count ? (double)cand_count[b * OFK_CNT_STRIDE] : 0.0; o[15] = 0.0;
+    const double r = block_point_sum(n, [&](int i, double &r) {
+        double x, y, q0, q1, q2, sA, sB;
+        if (st[i] && terms(i, x, y, q0, q1, q2, sA, sB)) r += resid_point(x, y, q0, q1, q2, sA, sB, s.v);
+    });
+    if (threadIdx.x == 0) {
+        double *o = records + (size_t)b * OFK_RECORD_DOUBLES, vu[3];
+        write_record(o, s.v, r, s.rank, s.s3, om, sn + 16, sn + 7, s.cnt, n, tracked, vu);
+        o[14] = cand_count ? (double)cand_count[b * OFK_CNT_STRIDE] : 0.0; o[15] = 0.0;
     }
 }
 
@@ -474,26 +505,9 @@ __global__ void k_feasibility(int variant, const double *__restrict__ x, const d
     if (variant == OFK_FEAS_RTILDE) {
         rtilde_point(px, py, ux, uy, nn, vv, dist[b], rr, dv);
     } else if (variant == OFK_FEAS_LEGACY) {
-        double vc0, vc1, vc2, uc0, uc1, uc2;
-        cross_p(px, py, vv[0], vv[1], vv[2], vc0, vc1, vc2);
-        vc0 = -vc0; vc1 = -vc1; vc2 = -vc2;
-        cross_p(px, py, ux, uy, 0.0, uc0, uc1, uc2);
-        const double vn = sqrt(vc0 * vc0 + vc1 * vc1 + vc2 * vc2), iun = 1.0 / sqrt(uc0 * uc0 + uc1 * uc1 + uc2 * uc2);
-        rr = (vc0 * uc0 + vc1 * uc1 + vc2 * uc2) * iun / vn;
-        const double pn = px * nn[0] + py * nn[1] + nn[2];
-        if (pn < 0.0) rr = -rr;
-        dv = pn * vn * iun;
-    } else {                                                  // simulation.py:108-120
-        const double *om = omega + 3 * b, *tb = t + 3 * b;
-        const double l0 = vv[0] - (om[1] * tb[2] - om[2] * tb[1]), l1 = vv[1] - (om[2] * tb[0] - om[0] * tb[2]),
-                     l2 = vv[2] - (om[0] * tb[1] - om[1] * tb[0]);
-        const double w0 = om[1] - om[2] * py, w1 = om[2] * px - om[0], w2 = om[0] * py - om[1] * px;   // omega x p
-        double f0, f1, f2, g0, g1, g2;
-        cross_p(px, py, l0, l1, l2, f0, f1, f2);
-        cross_p(px, py, ux - w0, uy - w1, -w2, g0, g1, g2);
-        const double n1 = sqrt(f0 * f0 + f1 * f1 + f2 * f2), n2 = sqrt(g0 * g0 + g1 * g1 + g2 * g2);
-        rr = (f0 * g0 + f1 * g1 + f2 * g2) / (n1 * n2);
-        dv = n1 / n2 * (px * nn[0] + py * nn[1] + nn[2]);
+        legacy_point(px, py, ux, uy, nn, vv, rr, dv);
+    } else {
+        feas_sim_point(px, py, ux, uy, vv, omega + 3 * b, t + 3 * b, nn, rr, dv);
     }
     r[k] = rr; dd[k] = dv;
 }
@@ -567,11 +581,7 @@ __global__ void k_post_solve(const double *__restrict__ v_obs, const double *__r
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
-    const double *v = v_obs + 3 * b, *R = rot + 9 * b, *w = ang + 3 * b, *o = offset + 3 * b;
-    const double e0 = v[0] - (w[1] * o[2] - w[2] * o[1]), e1 = v[1] - (w[2] * o[0] - w[0] * o[2]), e2 = v[2] - (w[0] * o[1] - w[1] * o[0]);
-    v_uav[3 * b] = R[0] * e0 + R[1] * e1 + R[2] * e2;
-    v_uav[3 * b + 1] = R[3] * e0 + R[4] * e1 + R[5] * e2;
-    v_uav[3 * b + 2] = R[6] * e0 + R[7] * e1 + R[8] * e2;
+    lever_rotate(v_obs + 3 * b, ang + 3 * b, offset + 3 * b, rot + 9 * b, v_uav + 3 * b);
 }
 
 void ofk_launch_post_solve(hipStream_t s, const double *v_obs, const double *rot, const double *ang,
@@ -627,6 +637,17 @@ __device__ void kf_correct_dev(int ns, int nm, const double *H, const double *Rm
     for (int i = 0; i < ns; ++i) for (int j = 0; j < ns; ++j) { double s = 0; for (int k = 0; k < nm; ++k) s += K[i][k] * T[k][j]; P[i][j] -= s; }
 }
 
+// filter b's state (x, P) of a batch of ns-state filters, loaded into registers and stored back
+__device__ __forceinline__ void kf_load(int ns, size_t b, const double *xs, const double *Ps, double *x, double (*P)[KF_MAX])
+{
+    for (int i = 0; i < ns; ++i) { x[i] = xs[b * ns + i]; for (int j = 0; j < ns; ++j) P[i][j] = Ps[(b * ns + i) * ns + j]; }
+}
+
+__device__ __forceinline__ void kf_store(int ns, size_t b, const double *x, const double (*P)[KF_MAX], double *xs, double *Ps)
+{
+    for (int i = 0; i < ns; ++i) { xs[b * ns + i] = x[i]; for (int j = 0; j < ns; ++j) Ps[(b * ns + i) * ns + j] = P[i][j]; }
+}
+
 __global__ void k_kf(int ns, int nm, int nc, const double *__restrict__ F, const double *__restrict__ Bm,
                      const double *__restrict__ H, const double *__restrict__ Q, const double *__restrict__ Rm,
                      double *__restrict__ xs, double *__restrict__ Ps, const double *__restrict__ us,
@@ -635,10 +656,10 @@ __global__ void k_kf(int ns, int nm, int nc, const double *__restrict__ F, const
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
     double x[KF_MAX], P[KF_MAX][KF_MAX];
-    for (int i = 0; i < ns; ++i) { x[i] = xs[(size_t)b * ns + i]; for (int j = 0; j < ns; ++j) P[i][j] = Ps[((size_t)b * ns + i) * ns + j]; }
+    kf_load(ns, b, xs, Ps, x, P);
     if (do_predict) kf_predict_dev(ns, nc, F, Bm, Q, (Bm && us) ? us + (size_t)b * nc : nullptr, x, P);
     if (zs) kf_correct_dev(ns, nm, H, Rm, zs + (size_t)b * nm, x, P);
-    for (int i = 0; i < ns; ++i) { xs[(size_t)b * ns + i] = x[i]; for (int j = 0; j < ns; ++j) Ps[((size_t)b * ns + i) * ns + j] = P[i][j]; }
+    kf_store(ns, b, x, P, xs, Ps);
 }
 
 // The per-pair filter of a resident batch (BASELINE configs[2]: "batch of independent frame pairs + per-frame EKF update"): one
@@ -650,7 +671,7 @@ __global__ void k_kf_records(int ns, int nm, const double *__restrict__ mats, do
     if (b >= batch) return;
     const double *F = mats, *H = mats + 72, *Q = mats + 108, *Rm = mats + 144;
     double x[KF_MAX], P[KF_MAX][KF_MAX];
-    for (int i = 0; i < ns; ++i) { x[i] = xs[(size_t)b * ns + i]; for (int j = 0; j < ns; ++j) P[i][j] = Ps[((size_t)b * ns + i) * ns + j]; }
+    kf_load(ns, b, xs, Ps, x, P);
     kf_predict_dev(ns, 0, F, nullptr, Q, nullptr, x, P);
     const double *r = records + (size_t)b * OFK_RECORD_DOUBLES;
     if (r[4] == 3.0) {                                          // a full-rank solve: there is a measurement
@@ -659,7 +680,7 @@ __global__ void k_kf_records(int ns, int nm, const double *__restrict__ mats, do
         for (int k = 3; k < nm; ++k) z[k] = z[k - 3];
         kf_correct_dev(ns, nm, H, Rm, z, x, P);
     }
-    for (int i = 0; i < ns; ++i) { xs[(size_t)b * ns + i] = x[i]; for (int j = 0; j < ns; ++j) Ps[((size_t)b * ns + i) * ns + j] = P[i][j]; }
+    kf_store(ns, b, x, P, xs, Ps);
 }
 
 void ofk_launch_kf_records(hipStream_t s, int ns, int nm, const double *mats, double *x, double *P, const double *records, double z_sign,
@@ -684,19 +705,6 @@ void ofk_launch_kf(hipStream_t s, int ns, int nm, int nc, const double *F, const
 //   node:229-261          centre + scale; r_tilde with the dead-reckoned velocity :238-245; solve_lgs :257; lever arm + rotation
 //                         :258; self.vel = v_uav :261 (the IMU state's velocity, dead-reckoned again by the next IMU messages)
 // The keep mask replaces `status` so that k_update_tracks carries exactly the kept points into the next frame.
-__device__ __forceinline__ void legacy_point(double x, double y, double ux, double uy, const double *n, const double *v, double &r, double &dd)
-{
-    double vc0, vc1, vc2, uc0, uc1, uc2;                          // pixhawk_pure_IMU/of_library.py:365-380 (4-arg r_tilde)
-    cross_p(x, y, v[0], v[1], v[2], vc0, vc1, vc2);
-    vc0 = -vc0; vc1 = -vc1; vc2 = -vc2;
-    cross_p(x, y, ux, uy, 0.0, uc0, uc1, uc2);
-    const double vn = sqrt(vc0 * vc0 + vc1 * vc1 + vc2 * vc2), iun = 1.0 / sqrt(uc0 * uc0 + uc1 * uc1 + uc2 * uc2);
-    r = (vc0 * uc0 + vc1 * uc1 + vc2 * uc2) * iun / vn;
-    const double pn = x * n[0] + y * n[1] + n[2];
-    if (pn < 0.0) r = -r;
-    dd = pn * vn * iun;
-}
-
 struct fuse_args {
     const float *prev_pts, *next_pts; uint8_t *status; const int *counts; int pts_stride;
     const double *sensors; double *imu_state, *imu_dv;
@@ -705,9 +713,10 @@ struct fuse_args {
     double *records, *fused;
 };
 
-__device__ __forceinline__ bool fuse_point(const fuse_args &g, int i, const float *pp, const float *np_, int st, double cx, double cy,
-                                           double scaling, const double *nrm, const double *om, const double *vp, double d, double &x,
-                                           double &y, double &ux, double &uy, double &wgt)
+// Point i's terms: x, y (centred, scaled), the flow u, and in the legacy keep mode the weight dist_i with its r_tilde (rl).
+__device__ __forceinline__ void fuse_terms(const fuse_args &g, int i, const float *pp, const float *np_, double cx, double cy, double scaling,
+                                           const double *nrm, const double *om, const double *vp, double &x, double &y, double &ux,
+                                           double &uy, double &wgt, double &rl)
 {
     const double X = (double)np_[2 * i], Y = (double)np_[2 * i + 1];
     x = (X - cx) * scaling; y = (Y - cy) * scaling;
@@ -717,14 +726,17 @@ __device__ __forceinline__ bool fuse_point(const fuse_args &g, int i, const floa
     } else {
         ux = (X - (double)pp[2 * i]) * scaling; uy = (Y - (double)pp[2 * i + 1]) * scaling;
     }
-    wgt = 1.0;
-    if (g.f.keep == OFK_KEEP_LEGACY) {
-        double r;
-        legacy_point(x, y, ux, uy, nrm, vp, r, wgt);
-        // of_module.py:129 `feasibility-(status-1)>=T`: status is cv2's uint8 array (:93), so for a lost point status-1 wraps to 255:
-        // r - 255 >= T, which a cosine never reaches for any sensible T; for a tracked point it is r - 0 >= T
-        return r - (st ? 0.0 : 255.0) >= g.feas_T;
-    }
+    wgt = 1.0; rl = 0.0;
+    if (g.f.keep == OFK_KEEP_LEGACY) legacy_point(x, y, ux, uy, nrm, vp, rl, wgt);
+}
+
+// Whether point i (status st, terms from fuse_terms) enters the solve.
+__device__ __forceinline__ bool fuse_keep(const fuse_args &g, int st, double x, double y, double ux, double uy, double rl, const double *nrm,
+                                          const double *vp, double d)
+{
+    // of_module.py:129 `feasibility-(status-1)>=T`: status is cv2's uint8 array (:93), so for a lost point status-1 wraps to 255:
+    // r - 255 >= T, which a cosine never reaches for any sensible T; for a tracked point it is r - 0 >= T
+    if (g.f.keep == OFK_KEEP_LEGACY) return rl - (st ? 0.0 : 255.0) >= g.feas_T;
     if (!st) return false;
     if (g.use_feas) {
         double r, dd;
@@ -737,7 +749,6 @@ __device__ __forceinline__ bool fuse_point(const fuse_args &g, int i, const floa
 __global__ __launch_bounds__(256) void k_stream_fuse(fuse_args g)
 {
     __shared__ double s_red[4];
-    __shared__ double s_v[8];
     __shared__ double s_pre[12];                                // nrm 0-2, omega 3-5, prior velocity 6-8
     const int b = blockIdx.x, tid = threadIdx.x;
     const double *sn = g.sensors + (size_t)b * OFK_SENSOR_DOUBLES;
@@ -747,7 +758,7 @@ __global__ __launch_bounds__(256) void k_stream_fuse(fuse_args g)
     if (tid == 0) {
         for (int k = 0; k < 3; ++k) { s_pre[k] = ist ? ist[15 + k] : sn[1 + k]; s_pre[3 + k] = ist ? ist[18 + k] : sn[4 + k]; s_pre[6 + k] = ist ? ist[k] : sn[22 + k]; }
         if (g.f.filter) {
-            for (int i = 0; i < g.ns; ++i) { kx[i] = g.kf_x[(size_t)b * g.ns + i]; for (int j = 0; j < g.ns; ++j) kP[i][j] = g.kf_P[((size_t)b * g.ns + i) * g.ns + j]; }
+            kf_load(g.ns, b, g.kf_x, g.kf_P, kx, kP);
             double u[KF_MAX] = {0, 0, 0, 0, 0, 0};
             if (g.f.control == OFK_CONTROL_IMU && g.imu_dv) for (int k = 0; k < 3; ++k) u[k] = g.imu_dv[3 * (size_t)b + k];
             else for (int k = 0; k < 3; ++k) u[k] = sn[25 + k];
@@ -761,64 +772,45 @@ __global__ __launch_bounds__(256) void k_stream_fuse(fuse_args g)
     const int n = g.counts[b];
     const float *pp = g.prev_pts + (size_t)b * g.pts_stride * 2, *np_ = g.next_pts + (size_t)b * g.pts_stride * 2;
     uint8_t *st = g.status + (size_t)b * g.pts_stride;
-    Acc a; acc_zero(a);
     double tracked = 0.0;
-    for (int i = tid; i < n; i += 256) {
+    const Solved s = block_lstsq(n, (double)g.f.min_solve, [&](int i, Acc &a) {   // of_module.py:138: more than 3 points; node:256: at least 3
         const int s0 = st[i];
         tracked += s0 ? 1.0 : 0.0;
-        double x, y, ux, uy, wgt;
-        const bool keep = fuse_point(g, i, pp, np_, s0, cx, cy, scaling, nrm, om, vp, d, x, y, ux, uy, wgt);
+        double x, y, ux, uy, wgt, rl;
+        fuse_terms(g, i, pp, np_, cx, cy, scaling, nrm, om, vp, x, y, ux, uy, wgt, rl);
+        const bool keep = fuse_keep(g, s0, x, y, ux, uy, rl, nrm, vp, d);
         st[i] = keep ? 1 : 0;
-        if (!keep) continue;
+        if (!keep) return;
         double q0, q1, q2, sA, sB;
         point_terms(g.variant, x, y, ux, uy, nrm, om, d, wgt, q0, q1, q2, sA, sB);
         acc_point(a, x, y, q0, q1, q2, sA, sB);
-    }
-    acc_block_sum(a, s_red);
+    });
+    // block_lstsq ends on a block barrier: the keep flags written above are visible to the whole block from here on
     tracked = block_sum(tracked, s_red);
-    const bool solved = a.cnt > (double)g.f.min_solve;          // of_module.py:138: more than 3 points; node:256: at least 3
+    const bool solved = s.cnt > (double)g.f.min_solve;
+    const double r = block_point_sum(solved ? n : 0, [&](int i, double &r) {
+        if (!st[i]) return;
+        double x, y, ux, uy, wgt, rl;
+        fuse_terms(g, i, pp, np_, cx, cy, scaling, nrm, om, vp, x, y, ux, uy, wgt, rl);
+        double q0, q1, q2, sA, sB;
+        point_terms(g.variant, x, y, ux, uy, nrm, om, d, wgt, q0, q1, q2, sA, sB);
+        r += resid_point(x, y, q0, q1, q2, sA, sB, s.v);
+    });
     if (tid == 0) {
-        double v[3] = {0, 0, 0}, s3[3] = {0, 0, 0};
-        const int rank = solved ? solve_from_acc(a, v, s3) : 0;
-        s_v[0] = v[0]; s_v[1] = v[1]; s_v[2] = v[2]; s_v[3] = (double)rank; s_v[4] = s3[0]; s_v[5] = s3[1]; s_v[6] = s3[2];
-    }
-    __syncthreads();                                            // the keep flags written above are visible to the whole block from here on
-    const double v[3] = {s_v[0], s_v[1], s_v[2]};
-    double r = 0.0;
-    if (solved)
-        for (int i = tid; i < n; i += 256) {
-            if (!st[i]) continue;
-            const double X = (double)np_[2 * i], Y = (double)np_[2 * i + 1];
-            const double x = (X - cx) * scaling, y = (Y - cy) * scaling;
-            double ux, uy, wgt = 1.0;
-            if (g.f.flow == OFK_FLOW_ROTATIONAL) { ux = X * Y * om[0] + (1.0 + X * X) * om[1] - Y * om[2]; uy = -(1.0 + Y * Y) * om[0] + X * Y * om[1] + X * om[2]; }
-            else { ux = (X - (double)pp[2 * i]) * scaling; uy = (Y - (double)pp[2 * i + 1]) * scaling; }
-            if (g.f.keep == OFK_KEEP_LEGACY) { double rr; legacy_point(x, y, ux, uy, nrm, vp, rr, wgt); }
-            double q0, q1, q2, sA, sB;
-            point_terms(g.variant, x, y, ux, uy, nrm, om, d, wgt, q0, q1, q2, sA, sB);
-            r += resid_point(x, y, q0, q1, q2, sA, sB, v);
-        }
-    r = block_sum(r, s_red);
-    if (tid == 0) {
-        double *o = g.records + (size_t)b * OFK_RECORD_DOUBLES;
-        const double *R = ist ? ist + 6 : sn + 7, *off = sn + 16;
-        const double e0 = v[0] - (om[1] * off[2] - om[2] * off[1]);                 // v_obs - [w]x offset, then rotate (node:258)
-        const double e1 = v[1] - (om[2] * off[0] - om[0] * off[2]);
-        const double e2 = v[2] - (om[0] * off[1] - om[1] * off[0]);
-        const double vu[3] = {R[0] * e0 + R[1] * e1 + R[2] * e2, R[3] * e0 + R[4] * e1 + R[5] * e2, R[6] * e0 + R[7] * e1 + R[8] * e2};
-        o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = r; o[4] = s_v[3]; o[5] = s_v[4]; o[6] = s_v[5]; o[7] = s_v[6];
-        o[8] = vu[0]; o[9] = vu[1]; o[10] = vu[2];
-        o[11] = a.cnt; o[12] = (double)n; o[13] = tracked; o[14] = 0.0; o[15] = solved ? 1.0 : 0.0;
+        double *o = g.records + (size_t)b * OFK_RECORD_DOUBLES, vu[3];
+        write_record(o, s.v, r, s.rank, s.s3, om, sn + 16, ist ? ist + 6 : sn + 7, s.cnt, n, tracked, vu);
+        o[14] = 0.0; o[15] = solved ? 1.0 : 0.0;
         double *fu = g.fused + (size_t)b * 8;
         if (g.f.filter) {
             if (solved) {
                 double z[KF_MAX] = {0, 0, 0, 0, 0, 0};
-                for (int k = 0; k < 3; ++k) z[k] = g.f.z_sign * (g.f.z_source ? vu[k] : v[k]);
+                for (int k = 0; k < 3; ++k) z[k] = g.f.z_sign * (g.f.z_source ? vu[k] : s.v[k]);
                 for (int k = 3; k < g.nm; ++k) z[k] = sn[22 + (k - 3)];               // a second velocity measurement (FilterModel.ekf6(gps=True)): the sensors' prior slot
                 kf_correct_dev(g.ns, g.nm, g.H, g.Rm, z, kx, kP);
             }
+            kf_store(g.ns, b, kx, kP, g.kf_x, g.kf_P);
             double tr = 0.0;
-            for (int i = 0; i < g.ns; ++i) { g.kf_x[(size_t)b * g.ns + i] = kx[i]; tr += kP[i][i]; for (int j = 0; j < g.ns; ++j) g.kf_P[((size_t)b * g.ns + i) * g.ns + j] = kP[i][j]; }
+            for (int i = 0; i < g.ns; ++i) tr += kP[i][i];
             for (int k = 0; k < 6; ++k) fu[k] = k < g.ns ? kx[k] : 0.0;
             fu[6] = tr; fu[7] = solved ? 1.0 : 0.0;
         } else {
@@ -891,9 +883,7 @@ __global__ __launch_bounds__(256) void k_of_simulation(const double *__restrict_
                                                        int n, const double *__restrict__ z, double *__restrict__ v_obs,
                                                        double *__restrict__ bound, ofk_noise rng)
 {
-    __shared__ double s_red[4];
-    __shared__ double s_v[8];
-    const int trial = blockIdx.x, tid = threadIdx.x;
+    const int trial = blockIdx.x;
     rng.trial += (unsigned)trial;
     // element e of this trial's row of 10 + 4 n normals
     auto Z = [&](size_t e) -> double { return RNG ? ofk_noise_normal(rng, (unsigned)e) : z[(size_t)trial * (10 + 4 * (size_t)n) + e]; };
@@ -906,24 +896,15 @@ __global__ __launch_bounds__(256) void k_of_simulation(const double *__restrict_
     const double h_err = hgt + sig[2] * zi[6];
     const double nn = sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
     const double ne[3] = {nv[0] / nn, nv[1] / nn, nv[2] / nn};      // normal noise is discarded (simulation.py:46)
-    Acc a; acc_zero(a);
-    for (int i = tid; i < n; i += 256) {
+    const Solved s = block_lstsq(n, -1.0, [&](int i, Acc &a) {         // no guard: every trial solves
         const double x = pos[2 * i] + sig[4] * Z(zp + 2 * i), y = pos[2 * i + 1] + sig[4] * Z(zp + 2 * i + 1);
         const double ux = true_flow[2 * i] + sig[3] * Z(zf + 2 * i), uy = true_flow[2 * i + 1] + sig[3] * Z(zf + 2 * i + 1);
         double q0, q1, q2, sA, sB;
         point_terms(OFK_SOLVE_SIM, x, y, ux, uy, ne, ang, h_err, 1.0, q0, q1, q2, sA, sB);
         acc_point(a, x, y, q0, q1, q2, sA, sB);
-    }
-    acc_block_sum(a, s_red);
-    if (tid == 0) {
-        double v[3], s3[3];
-        solve_from_acc(a, v, s3);
-        s_v[0] = v[0]; s_v[1] = v[1]; s_v[2] = v[2]; s_v[3] = s3[2];      // min singular value
-    }
-    __syncthreads();
-    const double smin = s_v[3];
-    double part2 = 0.0;
-    for (int i = tid; i < n; i += 256) {
+    });
+    const double smin = s.s3[2];                                  // min singular value
+    const double part2 = block_point_sum(n, [&](int i, double &p2) {
         const double xp0 = pos[2 * i], xp1 = pos[2 * i + 1];
         const double dx0 = sig[4] * Z(zp + 2 * i), dx1 = sig[4] * Z(zp + 2 * i + 1);         // dxp = (pos_err - pos, 0)
         const double dd0 = sig[3] * Z(zf + 2 * i), dd1 = sig[3] * Z(zf + 2 * i + 1);         // ddotx
@@ -943,14 +924,10 @@ __global__ __launch_bounds__(256) void k_of_simulation(const double *__restrict_
         double k0, k1, k2;
         cross_p(xp0, xp1, w0, w1, w2, k0, k1, k2);
         const double pe = sqrt(k0 * k0 + k1 * k1 + k2 * k2) / smin;
-        part2 += pe * pe;
-    }
-    part2 = block_sum(part2, s_red);
-    if (tid == 0) {
-        const double v0 = s_v[0] - (ang[1] * trn[2] - ang[2] * trn[1]);
-        const double v1 = s_v[1] - (ang[2] * trn[0] - ang[0] * trn[2]);
-        const double v2 = s_v[2] - (ang[0] * trn[1] - ang[1] * trn[0]);
-        v_obs[3 * trial] = v0; v_obs[3 * trial + 1] = v1; v_obs[3 * trial + 2] = v2;
+        p2 += pe * pe;
+    });
+    if (threadIdx.x == 0) {
+        sub_cross(s.v, ang, trn, v_obs + 3 * trial);
         const double avn = sqrt(av[0] * av[0] + av[1] * av[1] + av[2] * av[2]), trnorm = sqrt(tr[0] * tr[0] + tr[1] * tr[1] + tr[2] * tr[2]);
         bound[trial] = sqrt(part2) + avn * sig[1] + sig[0] * trnorm + sig[0] * sig[1];
     }
@@ -978,28 +955,12 @@ void ofk_launch_of_simulation_rng(hipStream_t s, const double *truth, const doub
 // true_vel[13..15]; sig: ang_vel, translation, height, flow, position, normal, velocity.  z: the reference's draw order
 // (omega 3, t 3, height 1, flow 2n, position 2n, velocity 3, orient 1, orient2 1).  per [trial][6][n] in the reference's return
 // order: backward_para, backward_dist, forward_para, forward_dist, backward_res, forward_res.
-__device__ __forceinline__ void feas_sim_point(double px, double py, double ux, double uy, const double *vv, const double *om,
-                                               const double *tb, const double *nn, double &rr, double &dv)
-{
-    const double l0 = vv[0] - (om[1] * tb[2] - om[2] * tb[1]), l1 = vv[1] - (om[2] * tb[0] - om[0] * tb[2]),
-                 l2 = vv[2] - (om[0] * tb[1] - om[1] * tb[0]);
-    const double w0 = om[1] - om[2] * py, w1 = om[2] * px - om[0], w2 = om[0] * py - om[1] * px;   // omega x p
-    double f0, f1, f2, g0, g1, g2;
-    cross_p(px, py, l0, l1, l2, f0, f1, f2);
-    cross_p(px, py, ux - w0, uy - w1, -w2, g0, g1, g2);
-    const double n1 = sqrt(f0 * f0 + f1 * f1 + f2 * f2), n2 = sqrt(g0 * g0 + g1 * g1 + g2 * g2);
-    rr = (f0 * g0 + f1 * g1 + f2 * g2) / (n1 * n2);
-    dv = n1 / n2 * (px * nn[0] + py * nn[1] + nn[2]);
-}
-
 __global__ __launch_bounds__(256) void k_feas_simulation(const double *__restrict__ truth, const double *__restrict__ sig,
                                                          const double *__restrict__ pos, const double *__restrict__ true_flow,
                                                          int n, const double *__restrict__ z, double *__restrict__ per,
                                                          double *__restrict__ v_obs)
 {
-    __shared__ double s_red[4];
-    __shared__ double s_v[4];
-    const int trial = blockIdx.x, tid = threadIdx.x;
+    const int trial = blockIdx.x;
     const double *zi = z + (size_t)trial * (12 + 4 * (size_t)n);
     const double ang[3] = {truth[3] + sig[0] * zi[0], truth[4] + sig[0] * zi[1], truth[5] + sig[0] * zi[2]};
     const double trn[3] = {truth[10] + sig[1] * zi[3], truth[11] + sig[1] * zi[4], truth[12] + sig[1] * zi[5]};
@@ -1011,30 +972,23 @@ __global__ __launch_bounds__(256) void k_feas_simulation(const double *__restric
     const double c1 = cos(o1), s1 = sin(o1), c2 = cos(o2), s2 = sin(o2);
     const double r0 = truth[7], r1 = c1 * truth[8] - s1 * truth[9], r2 = s1 * truth[8] + c1 * truth[9];      // Rx n
     const double ne[3] = {c2 * r0 + s2 * r2, r1, -s2 * r0 + c2 * r2};                                        // Ry (Rx n)
-    Acc a; acc_zero(a);
-    for (int i = tid; i < n; i += 256) {
-        const double x = pos[2 * i] + sig[4] * zp[2 * i], y = pos[2 * i + 1] + sig[4] * zp[2 * i + 1];
-        const double ux = true_flow[2 * i] + sig[3] * zf[2 * i], uy = true_flow[2 * i + 1] + sig[3] * zf[2 * i + 1];
-        double q0, q1, q2, sA, sB;
+    auto perturbed = [&](int i, double &x, double &y, double &ux, double &uy) {
+        x = pos[2 * i] + sig[4] * zp[2 * i]; y = pos[2 * i + 1] + sig[4] * zp[2 * i + 1];
+        ux = true_flow[2 * i] + sig[3] * zf[2 * i]; uy = true_flow[2 * i + 1] + sig[3] * zf[2 * i + 1];
+    };
+    const Solved s = block_lstsq(n, -1.0, [&](int i, Acc &a) {         // no guard: every trial solves
+        double x, y, ux, uy, q0, q1, q2, sA, sB;
+        perturbed(i, x, y, ux, uy);
         point_terms(OFK_SOLVE_SIM, x, y, ux, uy, ne, ang, h_err, 1.0, q0, q1, q2, sA, sB);
         acc_point(a, x, y, q0, q1, q2, sA, sB);
-    }
-    acc_block_sum(a, s_red);
-    if (tid == 0) {
-        double v[3], s3[3];
-        solve_from_acc(a, v, s3);
-        s_v[0] = v[0] - (ang[1] * trn[2] - ang[2] * trn[1]);      // v - omega x t (simulation.py:28)
-        s_v[1] = v[1] - (ang[2] * trn[0] - ang[0] * trn[2]);
-        s_v[2] = v[2] - (ang[0] * trn[1] - ang[1] * trn[0]);
-        if (v_obs) { v_obs[3 * trial] = s_v[0]; v_obs[3 * trial + 1] = s_v[1]; v_obs[3 * trial + 2] = s_v[2]; }
-    }
-    __syncthreads();
-    const double vo[3] = {s_v[0], s_v[1], s_v[2]};
+    });
+    double vo[3];
+    sub_cross(s.v, ang, trn, vo);                               // v - omega x t (simulation.py:28)
+    if (v_obs && threadIdx.x == 0) { v_obs[3 * trial] = vo[0]; v_obs[3 * trial + 1] = vo[1]; v_obs[3 * trial + 2] = vo[2]; }
     double *o = per + (size_t)trial * 6 * n;
-    for (int i = tid; i < n; i += 256) {
-        const double x = pos[2 * i] + sig[4] * zp[2 * i], y = pos[2 * i + 1] + sig[4] * zp[2 * i + 1];
-        const double ux = true_flow[2 * i] + sig[3] * zf[2 * i], uy = true_flow[2 * i + 1] + sig[3] * zf[2 * i + 1];
-        double bp, bd, fp, fd;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        double x, y, ux, uy, bp, bd, fp, fd;
+        perturbed(i, x, y, ux, uy);
         feas_sim_point(x, y, ux, uy, vo, ang, trn, ne, bp, bd);
         feas_sim_point(x, y, ux, uy, vel, ang, trn, ne, fp, fd);
         double q0, q1, q2, sA, sB;

@@ -270,7 +270,20 @@ def test_solve_kernels_agree_bit_for_bit(pkg, ofk, use_feas):
                                                    cx=pairs[b % D]["cx"], cy=pairs[b % D]["cy"], v_prior=pairs[b % D]["v"]) for b in range(B)])
         pipe = FlowPipeline(w, h, B, cfg)
         pipe.upload(prev, nxt, sensors)
-        outs.append(pipe.run(points=False)["records"])
+        out = pipe.run()
+        rec = out["records"]
+        # the stand-alone k_solve on x, u formed on the host from the same points (padded with invalid points) forms the same sums
+        n = out["counts"]; S = int(n.max())
+        nx = out["next_pts"][:, :S].astype(np.float64); pv = out["prev_pts"][:, :S].astype(np.float64)
+        x = (nx - sensors[:, None, 20:22]) * sensors[:, 19, None, None]; u = (nx - pv) * sensors[:, 19, None, None]
+        valid = (out["status"][:, :S] != 0) & (np.arange(S) < n[:, None])
+        if use_feas:                                             # r_tilde with the prior velocity, as the pair kernels filter
+            r, _ = pipe.ctx.feasibility(ofk.FEAS_RTILDE, x, u, sensors[:, 1:4], sensors[:, 22:25], dist=sensors[:, 0])
+            valid &= r <= cfg.feas_T
+        sol = pipe.ctx.velocity_solve(ofk.SOLVE_NODE, x, u, d=sensors[:, 0], nrm=sensors[:, 1:4], omega=sensors[:, 4:7],
+                                      valid=valid.astype(np.uint8))
+        assert np.array_equal(sol.view(np.uint64), rec[:, :8].view(np.uint64)), np.argwhere(sol != rec[:, :8])[:4]
+        outs.append(rec)
         pipe.close()
     small, big = outs
     assert np.all(small[:, 11] > 100)                            # > 256 corners per pair: every virtual wave has points
