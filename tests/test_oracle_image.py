@@ -46,8 +46,8 @@ def test_scharr_vs_numpy(img):
     assert np.array_equal(d[..., 1], np_conv_sep(img, [3, 10, 3], [-1, 0, 1]))
 
 
-@pytest.mark.parametrize("bs", [3, 6, 7])
-def test_mineig_vs_numpy(img, bs):
+def np_mineig(img, bs):
+    """Independent numpy restatement of the min-eigenvalue response (Sobel, box sums of the products, f32 formula)."""
     dx = np_conv_sep(img, [-1, 0, 1], [1, 2, 1]); dy = np_conv_sep(img, [1, 2, 1], [-1, 0, 1])
     h, w = img.shape
     an = bs // 2
@@ -61,8 +61,34 @@ def test_mineig_vs_numpy(img, bs):
     kd, ko = np.float32(0.5 * scale * scale), np.float32(scale * scale)
     a = sxx.astype(np.float32) * kd; b = sxy.astype(np.float32) * ko; c = syy.astype(np.float32) * kd
     amc = a - c
-    ref = (a + c) - np.sqrt(amc * amc + b * b, dtype=np.float32)
-    assert np.array_equal(io.mineig(img, bs).view(np.uint32), ref.astype(np.float32).view(np.uint32))
+    return ((a + c) - np.sqrt(amc * amc + b * b, dtype=np.float32)).astype(np.float32)
+
+
+@pytest.mark.parametrize("bs", [3, 6, 7, 1, 2, 4, 12, 31, 45])
+def test_mineig_vs_numpy(img, bs):
+    assert np.array_equal(io.mineig(img, bs).view(np.uint32), np_mineig(img, bs).view(np.uint32))
+
+
+@pytest.mark.parametrize("bs", [1, 2, 4, 12, 31, 45])
+def test_mineig_vs_numpy_full_contrast_and_minimum_size(bs):
+    """The GPU block-size sweep leans on the oracle at every block size: full-contrast patterns (period-4 stripes put Sxx at
+    bs^2 * 1020^2, 98 % of 2^31 at 45 x 45, where the int32 box sums must still be exact) and the smallest image the library accepts."""
+    from param_ranges import diagonal, plaid, sobel_box_sums, stripes
+    rng = np.random.default_rng(bs)
+    imgs = [stripes((61, 83)), stripes((61, 83), axis=0), plaid((61, 83)), diagonal((61, 83)),
+            rng.integers(0, 256, (bs + 4, bs + 4), dtype=np.uint8), (rng.integers(0, 2, (bs + 4, bs + 5)) * 255).astype(np.uint8)]
+    for k, im in enumerate(imgs):
+        assert np.array_equal(io.mineig(im, bs).view(np.uint32), np_mineig(im, bs).view(np.uint32)), k
+    sxx = sobel_box_sums(imgs[0], bs)[0]
+    assert sxx.max() == bs * bs * 1020 ** 2 and np.array_equal(sxx, np_sobel_box(imgs[0], bs))
+
+
+def np_sobel_box(img, bs):
+    dx = np_conv_sep(img, [-1, 0, 1], [1, 2, 1])
+    h, w = img.shape
+    an = bs // 2
+    t = sum((dx * dx)[:, r101(np.arange(w) - an + i, w)] for i in range(bs))
+    return sum(t[r101(np.arange(h) - an + j, h), :] for j in range(bs))
 
 
 def test_corner_kats():
@@ -116,3 +142,40 @@ def test_lk_kats():
     flat = np.full_like(img, 90)
     n, s, e = io.lk_pyr(flat, flat, pts)
     assert np.all(s == 0)
+
+
+@pytest.fixture(scope="module")
+def smooth():
+    rng = np.random.default_rng(5)
+    t = rng.standard_normal((200, 260))
+    k = np.exp(-0.5 * (np.arange(-6, 7) / 2.0) ** 2); k /= k.sum()
+    t = np.apply_along_axis(lambda r: np.convolve(r, k, "same"), 1, t); t = np.apply_along_axis(lambda r: np.convolve(r, k, "same"), 0, t)
+    return np.clip(127 + 60 * t / t.std(), 0, 255).astype(np.uint8)
+
+
+@pytest.mark.parametrize("win", range(3, 32, 2))
+def test_lk_kats_every_window(smooth, win):
+    """Known answers at every window the library accepts: identical frames give zero flow, status 1, err 0; an integer translation
+    of a smooth texture is recovered."""
+    pts = io.good_features(smooth, 40, 0.05, 12, 7)
+    n, s, e = io.lk_pyr(smooth, smooth, pts, win=win)
+    assert np.all(s == 1) and np.array_equal(n, pts) and np.all(e == 0)
+    n, s, e = io.lk_pyr(smooth, np.roll(smooth, (3, -2), axis=(0, 1)), pts, win=win)
+    p2 = pts.reshape(-1, 2)
+    inner = (p2[:, 0] > 40) & (p2[:, 0] < 220) & (p2[:, 1] > 40) & (p2[:, 1] < 160) & (s.ravel() == 1)
+    dev = np.abs((n.reshape(-1, 2) - p2)[inner] - [-2, 3])
+    hit = (dev < 0.05).all(1).mean()                          # a 3 x 3 window can lock onto a wrong match of a smooth texture
+    assert inner.sum() > 8 and np.median(dev) < 0.02 and hit >= (0.7 if win == 3 else 1.0), (win, np.median(dev), hit)
+
+
+def test_lk_levels_at_the_cut():
+    """io.lk_levels against the level rule restated (tests/param_ranges.py), on sides where a level lands on win or win + 1."""
+    from param_ranges import cut_sizes, lk_level_sizes
+    for win in range(3, 32, 2):
+        sizes = cut_sizes(win) + [1000]
+        for h in sizes:
+            for w in sizes:
+                for ml in (0, 1, 2, 3, 8):
+                    assert io.lk_levels(h, w, win, ml) == len(lk_level_sizes(h, w, win, ml)) - 1, (h, w, win, ml)
+    assert io.lk_levels(29, 1000, 15, 8) == 0 and io.lk_levels(31, 1000, 15, 8) == 1 and io.lk_levels(64, 1000, 15, 8) == 2
+    assert io.lk_levels(5, 6, 3, 8) == 0 and io.lk_levels(8, 8, 3, 8) == 1 and io.lk_levels(16, 16, 3, 8) == 2
