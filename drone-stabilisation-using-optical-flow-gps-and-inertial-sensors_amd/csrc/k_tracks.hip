@@ -105,3 +105,43 @@ void ofk_launch_replace_tracks(hipStream_t s, const int *limit, const float *new
 {
     hipLaunchKernelGGL(k_replace_tracks, dim3(batch), dim3(256), 0, s, limit, new_pts, new_counts, pts_stride, tracks, counts);
 }
+
+// Start positions of a seeded LK (ofk.h: ofk_set_lk_seed): the flow the pair's sensors predict, added to every point.  One thread
+// per point, float64 in the order ofk.h states (the build has no FMA contraction); k_flow_model's expression with the pixel
+// scaling folded in.  mode OFK_SEED_ROTATION drops the translational part (v = 0).  imu != NULL: normal, omega and velocity come
+// from the resident IMU state, as k_stream_fuse takes them.  A seed LK could not use (scaling or d zero, not finite, beyond
+// 1e6) is replaced by the point itself, which is the unseeded start.
+__global__ __launch_bounds__(256) void k_seed_points(const float *__restrict__ pts, const int *__restrict__ counts, int pts_stride,
+                                                     const double *__restrict__ sensors, const double *__restrict__ imu, int mode,
+                                                     double gain, float *__restrict__ seed)
+{
+    const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= pts_stride || p >= counts[b]) return;
+    const double *sn = sensors + (size_t)b * OFK_SENSOR_DOUBLES;
+    const double *ist = imu ? imu + (size_t)b * OFK_IMU_STATE : nullptr;
+    const double d = sn[0], scaling = sn[19], cx = sn[20], cy = sn[21];
+    const double n0 = ist ? ist[15] : sn[1], n1 = ist ? ist[16] : sn[2], n2 = ist ? ist[17] : sn[3];
+    const double o0 = ist ? ist[18] : sn[4], o1 = ist ? ist[19] : sn[5], o2 = ist ? ist[20] : sn[6];
+    const bool rot = mode == OFK_SEED_ROTATION;
+    const double v0 = rot ? 0.0 : ist ? ist[0] : sn[22], v1 = rot ? 0.0 : ist ? ist[1] : sn[23], v2 = rot ? 0.0 : ist ? ist[2] : sn[24];
+    const size_t pi = (size_t)b * pts_stride + p;
+    const float fpx = pts[2 * pi], fpy = pts[2 * pi + 1];
+    float sx = fpx, sy = fpy;
+    if (scaling != 0.0 && d != 0.0) {
+        const double px = (double)fpx, py = (double)fpy;
+        const double x = (px - cx) * scaling, y = (py - cy) * scaling;
+        const double k = (n0 * x + n1 * y + n2) / d;
+        const double w0 = o1 - o2 * y, w1 = o2 * x - o0, w2 = o0 * y - o1 * x;
+        const double fx = k * (v0 - v2 * x) + (w0 - w2 * x), fy = k * (v1 - v2 * y) + (w1 - w2 * y);
+        const float tx = (float)(px + gain * fx / scaling), ty = (float)(py + gain * fy / scaling);
+        if (fabsf(tx) <= 1e6f && fabsf(ty) <= 1e6f) { sx = tx; sy = ty; }      // false for NaN and infinity too
+    }
+    seed[2 * pi] = sx; seed[2 * pi + 1] = sy;
+}
+
+void ofk_launch_seed_points(hipStream_t s, const float *pts, const int *counts, int pts_stride, const double *sensors,
+                            const double *imu_state, int mode, double gain, float *seed_out, int batch)
+{
+    hipLaunchKernelGGL(k_seed_points, dim3((pts_stride + 255) / 256, batch), dim3(256), 0, s, pts, counts, pts_stride, sensors, imu_state,
+                       mode, gain, seed_out);
+}

@@ -145,6 +145,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->streams[0] = c->stream;
     c->overlap = 1;
     c->gray_direct_set = -1;
+    c->lk_seed_mode = OFK_SEED_OFF; c->lk_seed_gain = 1.0;
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -500,30 +501,103 @@ static void build_pyramids(ofk_ctx *c, const ofk_levels &lv, int batch, int whic
     }
 }
 
-extern "C" int ofk_lk_pyr(ofk_ctx *c, const uint8_t *prev, const uint8_t *next, int batch, int h, int w, const float *prev_pts,
-                          const int *counts, int pts_stride, int win, int max_level, int max_count, double eps, double min_eig_thr,
-                          float *next_pts, uint8_t *status, float *err)
+static int lk_pyr_impl(ofk_ctx *c, const char *who, const uint8_t *prev, const uint8_t *next, int batch, int h, int w, const float *prev_pts,
+                       const int *counts, int pts_stride, int win, int max_level, int max_count, double eps, double min_eig_thr,
+                       const float *init_pts, int flags, float *next_pts, uint8_t *status, float *err)
 {
-    TRY(check_geom(c, batch, h, w, "ofk_lk_pyr"));
-    if (!prev || !next || !prev_pts || !counts || !next_pts || !status || !err) return ofk_fail(c, OFK_E_INVALID, "ofk_lk_pyr: NULL buffer");
+    TRY(check_geom(c, batch, h, w, who));
+    if (!prev || !next || !prev_pts || !counts || !next_pts || !status || !err) return ofk_fail(c, OFK_E_INVALID, "%s: NULL buffer", who);
     TRY(check_lk(c, h, w, win, max_level));
     if (pts_stride < 1 || pts_stride > c->max_pts) return ofk_fail(c, OFK_E_INVALID, "pts_stride %d outside 1..%d", pts_stride, c->max_pts);
     for (int b = 0; b < batch; ++b)
         if (counts[b] < 0 || counts[b] > pts_stride) return ofk_fail(c, OFK_E_INVALID, "counts[%d]=%d outside 0..%d", b, counts[b], pts_stride);
+    if (flags & ~(OFK_LK_USE_INITIAL_FLOW | OFK_LK_GET_MIN_EIGENVALS)) return ofk_fail(c, OFK_E_INVALID, "%s: unknown flag bits 0x%x", who, flags);
+    const bool seeded = (flags & OFK_LK_USE_INITIAL_FLOW) != 0;
+    if (seeded) {
+        if (!init_pts) return ofk_fail(c, OFK_E_INVALID, "%s: OFK_LK_USE_INITIAL_FLOW needs init_pts", who);
+        for (int b = 0; b < batch; ++b)
+            for (int i = 0; i < 2 * counts[b]; ++i) {
+                const float v = init_pts[(size_t)b * pts_stride * 2 + i];
+                if (!(fabsf(v) <= 1e6f)) return ofk_fail(c, OFK_E_INVALID, "%s: init_pts[%d][%d] = %g is not a finite coordinate within 1e6", who, b, i / 2, (double)v);
+            }
+    }
     const size_t px = (size_t)h * w;
     const ofk_levels lv = ofk_make_levels(h, w, win, max_level);
     TRY(h2d(c, c->pyr[0], c->pyr_stride, prev, px, batch));
     TRY(h2d(c, c->pyr[1], c->pyr_stride, next, px, batch));
     TRY(h2d(c, c->pts_prev, (size_t)c->max_pts * 8, prev_pts, (size_t)pts_stride * 8, batch));
+    if (seeded) TRY(h2d(c, c->pts_next, (size_t)c->max_pts * 8, init_pts, (size_t)pts_stride * 8, batch));   // in/out, as cv2's nextPts
     OFK_HIP(c, hipMemcpyAsync(c->counts, counts, (size_t)batch * 4, hipMemcpyHostToDevice, c->stream));
     build_pyramids(c, lv, batch, 3);
     ofk_launch_lk(c->stream, c->pyr[0], c->pyr[1], c->pyr_stride, lv, c->pts_prev, c->counts, c->max_pts, win, max_count, eps,
-                  min_eig_thr, c->pts_next, c->status, c->err, batch);
+                  min_eig_thr, c->pts_next, c->status, c->err, batch, flags);
     TRY(check_launch(c, "k_lk"));
     OFK_HIP(c, hipMemcpy2DAsync(next_pts, (size_t)pts_stride * 8, c->pts_next, (size_t)c->max_pts * 8, (size_t)pts_stride * 8, batch,
                                 hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipMemcpy2DAsync(status, pts_stride, c->status, c->max_pts, pts_stride, batch, hipMemcpyDeviceToHost, c->stream));
     return d2h(c, err, c->err, (size_t)c->max_pts * 4, (size_t)pts_stride * 4, batch);
+}
+
+extern "C" int ofk_lk_pyr(ofk_ctx *c, const uint8_t *prev, const uint8_t *next, int batch, int h, int w, const float *prev_pts,
+                          const int *counts, int pts_stride, int win, int max_level, int max_count, double eps, double min_eig_thr,
+                          float *next_pts, uint8_t *status, float *err)
+{
+    return lk_pyr_impl(c, "ofk_lk_pyr", prev, next, batch, h, w, prev_pts, counts, pts_stride, win, max_level, max_count, eps, min_eig_thr,
+                       nullptr, 0, next_pts, status, err);
+}
+
+extern "C" int ofk_lk_pyr_ex(ofk_ctx *c, const uint8_t *prev, const uint8_t *next, int batch, int h, int w, const float *prev_pts,
+                             const int *counts, int pts_stride, int win, int max_level, int max_count, double eps, double min_eig_thr,
+                             const float *init_pts, int flags, float *next_pts, uint8_t *status, float *err)
+{
+    return lk_pyr_impl(c, "ofk_lk_pyr_ex", prev, next, batch, h, w, prev_pts, counts, pts_stride, win, max_level, max_count, eps, min_eig_thr,
+                       init_pts, flags, next_pts, status, err);
+}
+
+static bool seed_mode_ok(int mode) { return mode == OFK_SEED_OFF || mode == OFK_SEED_MODEL || mode == OFK_SEED_ROTATION; }
+
+extern "C" int ofk_set_lk_seed(ofk_ctx *c, int mode, double gain)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!seed_mode_ok(mode)) return ofk_fail(c, OFK_E_INVALID, "ofk_set_lk_seed: mode %d is none of OFK_SEED_OFF, _MODEL, _ROTATION", mode);
+    if (!(fabs(gain) <= 1e12)) return ofk_fail(c, OFK_E_INVALID, "ofk_set_lk_seed: gain %g is not finite", gain);
+    c->lk_seed_mode = mode; c->lk_seed_gain = gain;
+    return OFK_OK;
+}
+
+extern "C" int ofk_get_lk_seed(const ofk_ctx *c, int *mode, double *gain)
+{
+    if (!c) return OFK_E_INVALID;
+    if (mode) *mode = c->lk_seed_mode;
+    if (gain) *gain = c->lk_seed_gain;
+    return OFK_OK;
+}
+
+// the predictor on host buffers; device scratch only, so resident points, sensors and filter states are not touched
+extern "C" int ofk_predict_points(ofk_ctx *c, const float *pts, const int *counts, int batch, int stride, const double *sensors, int mode,
+                                  double gain, float *seed_out)
+{
+    if (!c || !pts || !counts || !sensors || !seed_out || batch < 1 || stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_predict_points: bad argument");
+    if (mode != OFK_SEED_MODEL && mode != OFK_SEED_ROTATION) return ofk_fail(c, OFK_E_INVALID, "ofk_predict_points: mode must be OFK_SEED_MODEL or OFK_SEED_ROTATION");
+    for (int b = 0; b < batch; ++b)
+        if (counts[b] < 0 || counts[b] > stride) return ofk_fail(c, OFK_E_INVALID, "counts[%d]=%d outside 0..%d", b, counts[b], stride);
+    if (hipSetDevice(c->device) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "hipSetDevice failed");
+    TRY(join_slices(c));
+    const size_t pb = up((size_t)batch * stride * 8, 256), cb = up((size_t)batch * 4, 256), sb = up((size_t)batch * OFK_SENSOR_DOUBLES * 8, 256);
+    TRY(ofk_need_scratch(c, 2 * pb + cb + sb));
+    char *base = (char *)c->scratch;
+    float *dp = (float *)base, *ds = (float *)(base + pb);
+    int *dc = (int *)(base + 2 * pb);
+    double *dsn = (double *)(base + 2 * pb + cb);
+    OFK_HIP(c, hipMemcpyAsync(dp, pts, (size_t)batch * stride * 8, hipMemcpyHostToDevice, c->stream));
+    OFK_HIP(c, hipMemcpyAsync(ds, pts, (size_t)batch * stride * 8, hipMemcpyHostToDevice, c->stream));     // entries beyond counts[b]: the points
+    OFK_HIP(c, hipMemcpyAsync(dc, counts, (size_t)batch * 4, hipMemcpyHostToDevice, c->stream));
+    OFK_HIP(c, hipMemcpyAsync(dsn, sensors, (size_t)batch * OFK_SENSOR_DOUBLES * 8, hipMemcpyHostToDevice, c->stream));
+    ofk_launch_seed_points(c->stream, dp, dc, stride, dsn, nullptr, mode, gain, ds, batch);
+    TRY(check_launch(c, "k_seed_points"));
+    OFK_HIP(c, hipMemcpyAsync(seed_out, ds, (size_t)batch * stride * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
 }
 
 // levels 1..L of a batch of gray images, built exactly as ofk_lk_pyr / ofk_pairs_run build them (three levels per pass where the
@@ -1044,8 +1118,11 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
         if (overlap) OFK_HIP(c, hipStreamWaitEvent(st, c->ev_aux[k], 0));    // LK needs both pyramids
         {
             StageTimer t(c, OFK_STAGE_LK, st);
+            if (c->lk_seed_mode != OFK_SEED_OFF)                 // start positions from the pair's sensors, written where LK reads them
+                ofk_launch_seed_points(st, pts_prev, counts, c->max_pts, c->sensors + (size_t)b0 * OFK_SENSOR_DOUBLES, nullptr, c->lk_seed_mode,
+                                       c->lk_seed_gain, pts_next, nb);
             ofk_launch_lk(st, pyr0, pyr1, c->pyr_stride, lv, pts_prev, counts, c->max_pts, p->win, p->max_count, p->eps, p->min_eig_thr,
-                          pts_next, status, err, nb);
+                          pts_next, status, err, nb, c->lk_seed_mode != OFK_SEED_OFF ? OFK_LK_USE_INITIAL_FLOW : 0);
         }
         if (overlap) OFK_HIP(c, hipEventRecord(c->ev_lkdone[set][k], st));   // this pyramid set may be rewritten from here on
         if (c->x_pending) OFK_HIP(c, hipStreamWaitEvent(st, c->ev_x, 0));    // the previous call's records are still being exported
@@ -1343,8 +1420,11 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     }
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)
+    if (c->lk_seed_mode != OFK_SEED_OFF)                         // the sources k_stream_fuse uses: the IMU state under use_imu, else the sensors
+        ofk_launch_seed_points(c->stream, c->pts_prev, c->counts, c->max_pts, c->sensors, fu && fu->use_imu ? c->imu_state : nullptr,
+                               c->lk_seed_mode, c->lk_seed_gain, c->pts_next, B);
     ofk_launch_lk(c->stream, c->pyr[0], c->pyr[1], c->pyr_stride, lv, c->pts_prev, c->counts, c->max_pts, p->win, p->max_count, p->eps,
-                  p->min_eig_thr, c->pts_next, c->status, c->err, B);
+                  p->min_eig_thr, c->pts_next, c->status, c->err, B, c->lk_seed_mode != OFK_SEED_OFF ? OFK_LK_USE_INITIAL_FLOW : 0);
     if (fu)
         ofk_launch_stream_fuse(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
                                c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, p->use_feasibility, p->feas_T,

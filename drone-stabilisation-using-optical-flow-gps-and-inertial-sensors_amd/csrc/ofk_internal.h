@@ -83,6 +83,7 @@ struct ofk_ctx {
     int kf_ns, kf_nm, kf_nc;
     int cur_batch, cur_h, cur_w;    // resident pair geometry (ofk_pairs_upload)
     int prof_mask;
+    int lk_seed_mode; double lk_seed_gain;   // ofk_set_lk_seed: OFK_SEED_OFF unless set
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -149,7 +150,10 @@ void ofk_launch_update_tracks(hipStream_t s, const float *next_pts, const uint8_
                               const float *new_pts, const int *new_counts, float *tracks, int *counts_out, int max_total, int batch);
 void ofk_launch_lk(hipStream_t s, const uint8_t *prev, const uint8_t *next, size_t pyr_stride, const ofk_levels &lv,
                    const float *prev_pts, const int *counts, int pts_stride, int win, int max_count, double eps,
-                   double min_eig_thr, float *next_pts, uint8_t *status, float *err, int batch);
+                   double min_eig_thr, float *next_pts, uint8_t *status, float *err, int batch, int flags = 0);   // flags: OFK_LK_*
+// start positions of a seeded LK (ofk.h: ofk_set_lk_seed): seed_out[b][p] for p < counts[b]; imu_state NULL = sensors only
+void ofk_launch_seed_points(hipStream_t s, const float *pts, const int *counts, int pts_stride, const double *sensors,
+                            const double *imu_state, int mode, double gain, float *seed_out, int batch);
 void ofk_launch_pairs_solve(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status,
                             const int *counts, int pts_stride, const double *sensors, int variant, int use_feas,
                             double feas_T, const int *cand_count, double *records, int batch);

@@ -17,6 +17,8 @@ COLOR_BGR2GRAY = 6
 TERM_CRITERIA_COUNT = 1
 TERM_CRITERIA_MAX_ITER = 1
 TERM_CRITERIA_EPS = 2
+OPTFLOW_USE_INITIAL_FLOW = 4
+OPTFLOW_LK_GET_MIN_EIGENVALS = 8
 
 
 def cvtColor(src, code):
@@ -75,8 +77,11 @@ def _criteria(criteria):
 
 def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts=None, status=None, err=None, winSize=(21, 21), maxLevel=3,
                          criteria=(TERM_CRITERIA_COUNT | TERM_CRITERIA_EPS, 30, 0.01), flags=0, minEigThreshold=1e-4):
-    if flags:
-        raise NotImplementedError("OPTFLOW_USE_INITIAL_FLOW / LK_GET_MIN_EIGENVALS are not used by the reference")
+    """flags: OPTFLOW_USE_INITIAL_FLOW (nextPts holds the start positions; ofk.h: at the top pyramid level) and
+    OPTFLOW_LK_GET_MIN_EIGENVALS (err = minimum eigenvalue of the level-0 normal matrix per window pixel)."""
+    flags = int(flags)
+    if flags & ~(OPTFLOW_USE_INITIAL_FLOW | OPTFLOW_LK_GET_MIN_EIGENVALS):
+        raise ValueError(f"calcOpticalFlowPyrLK: unknown flag bits {flags:#x}")
     if winSize[0] != winSize[1]:
         raise NotImplementedError("square windows only (the reference uses (15,15))")
     prevImg = np.asarray(prevImg); nextImg = np.asarray(nextImg)
@@ -84,10 +89,19 @@ def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts=None, status=None, e
         raise ValueError("calcOpticalFlowPyrLK expects two HxW uint8 images of equal size")
     h, w = prevImg.shape
     pts = np.asarray(prevPts, np.float32).reshape(-1, 2)
+    init = None
+    if flags & OPTFLOW_USE_INITIAL_FLOW:
+        if nextPts is None:
+            raise ValueError("calcOpticalFlowPyrLK: OPTFLOW_USE_INITIAL_FLOW needs nextPts")
+        init = np.asarray(nextPts, np.float32).reshape(-1, 2)
+        if len(init) != len(pts):                       # OpenCV asserts nextPts.checkVector(2) == npoints
+            raise ValueError(f"calcOpticalFlowPyrLK: nextPts has {len(init)} points, prevPts {len(pts)}")
+        if not np.all(np.abs(init) <= 1e6):
+            raise ValueError("calcOpticalFlowPyrLK: nextPts must be finite coordinates within 1e6")
     cnt, eps = _criteria(criteria)
     ctx = ofk.default_context(w, h, min_pts=max(1, len(pts)), min_level=int(maxLevel))
     return ctx.lk_pyr(prevImg, nextImg, pts, win=int(winSize[0]), max_level=int(maxLevel), max_count=cnt, eps=eps,
-                      min_eig_thr=float(minEigThreshold))
+                      min_eig_thr=float(minEigThreshold), next_pts=init, flags=flags)
 
 
 class KalmanFilter:

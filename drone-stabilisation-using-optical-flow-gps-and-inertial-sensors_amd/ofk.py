@@ -25,7 +25,7 @@ STAGES = ("gray", "pyr", "eig", "nms", "select", "lk", "solve")
 SYMBOLS = (
     "ofk_version", "ofk_last_error", "ofk_device_count", "ofk_create", "ofk_destroy", "ofk_sync", "ofk_device_sync",
     "ofk_gray_bgr8", "ofk_pyr_down_u8", "ofk_pyramid_u8", "ofk_scharr_s16", "ofk_mineig_response", "ofk_select_corners",
-    "ofk_good_features", "ofk_lk_pyr", "ofk_flow_model", "ofk_feasibility", "ofk_velocity_solve", "ofk_imu_propagate",
+    "ofk_good_features", "ofk_lk_pyr", "ofk_lk_pyr_ex", "ofk_predict_points", "ofk_set_lk_seed", "ofk_get_lk_seed", "ofk_flow_model", "ofk_feasibility", "ofk_velocity_solve", "ofk_imu_propagate",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
     "ofk_stream_begin_jpeg", "ofk_stream_step_jpeg",
@@ -49,6 +49,9 @@ class Params(C.Structure):
                 ("min_eig_thr", C.c_double), ("solve_variant", C.c_int), ("use_feasibility", C.c_int), ("feas_T", C.c_double)]
 
 
+LK_USE_INITIAL_FLOW, LK_GET_MIN_EIGENVALS = 4, 8         # cv2's OPTFLOW_* values (ofk_lk_pyr_ex)
+SEED_OFF, SEED_MODEL, SEED_ROTATION = 0, 1, 2           # ofk_set_lk_seed / ofk_predict_points
+SEED_MODES = {"off": SEED_OFF, "model": SEED_MODEL, "rotation": SEED_ROTATION}
 FLOW_LK, FLOW_ROTATIONAL = 0, 1
 KEEP_STATUS, KEEP_LEGACY = 0, 1
 CONTROL_SENSORS, CONTROL_IMU = 0, 1
@@ -117,6 +120,9 @@ def load_library():
         L.ofk_select_corners.argtypes = [vp, vp, vp, i, i, i, i, d, d, vp, vp]
         L.ofk_good_features.argtypes = [vp, vp, vp, i, i, i, i, d, d, i, vp, vp]
         L.ofk_lk_pyr.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, vp, vp]
+        L.ofk_lk_pyr_ex.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, i, vp, vp, vp]
+        L.ofk_predict_points.argtypes = [vp, vp, vp, i, i, vp, i, d, vp]
+        L.ofk_set_lk_seed.argtypes = [vp, i, d]; L.ofk_get_lk_seed.argtypes = [vp, C.POINTER(i), C.POINTER(d)]
         L.ofk_flow_model.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp, vp]
         L.ofk_feasibility.argtypes = [vp, i, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp]
         L.ofk_velocity_solve.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp]
@@ -321,9 +327,17 @@ class Context:
             return pts[0, :n].reshape(n, 1, 2).copy()
         return pts, cnt
 
-    def lk_pyr(self, prev, nxt, prev_pts, counts=None, win=15, max_level=3, max_count=20, eps=0.03, min_eig_thr=1e-4):
+    def lk_pyr(self, prev, nxt, prev_pts, counts=None, win=15, max_level=3, max_count=20, eps=0.03, min_eig_thr=1e-4, next_pts=None,
+               flags=0):
         """Batched calcOpticalFlowPyrLK.  Single image: prev_pts (N,1,2)/(N,2) -> (next (N,1,2), status (N,1), err (N,1)).
-        Batch: prev_pts [B,S,2] + counts [B] -> (next [B,S,2], status [B,S], err [B,S])."""
+        Batch: prev_pts [B,S,2] + counts [B] -> (next [B,S,2], status [B,S], err [B,S]).
+        flags: LK_USE_INITIAL_FLOW (the search starts at next_pts, same shape as prev_pts) | LK_GET_MIN_EIGENVALS (err = level-0
+        minEig); with flags == 0 and no next_pts this is ofk_lk_pyr, otherwise ofk_lk_pyr_ex."""
+        flags = int(flags)
+        if flags & ~(LK_USE_INITIAL_FLOW | LK_GET_MIN_EIGENVALS):
+            raise ValueError(f"lk_pyr: unknown flag bits {flags:#x}")
+        if flags & LK_USE_INITIAL_FLOW and next_pts is None:
+            raise ValueError("lk_pyr: LK_USE_INITIAL_FLOW needs next_pts")
         prev, single = self._batched(prev, 2)
         nxt, _ = self._batched(nxt, 2)
         prev = _arr(prev, np.uint8); nxt = _arr(nxt, np.uint8)
@@ -341,16 +355,53 @@ class Context:
         S = pp.shape[1]
         if np.any(counts < 0) or np.any(counts > S):
             raise ValueError("lk_pyr: counts outside 0..S")
+        init = None
+        if flags & LK_USE_INITIAL_FLOW:
+            init = _arr(next_pts, np.float32)
+            if init.size != pp.size:
+                raise ValueError(f"lk_pyr: next_pts {init.shape} does not match prev_pts {pp.shape}")
+            init = np.ascontiguousarray(init.reshape(pp.shape))
         if S == 0:
             z = np.zeros((0, 1, 2), np.float32)
             return z, np.zeros((0, 1), np.uint8), np.zeros((0, 1), np.float32)
         nxt_pts = np.zeros((B, S, 2), np.float32); st = np.zeros((B, S), np.uint8); err = np.zeros((B, S), np.float32)
         with self._lock:
-            self._ck(self._L.ofk_lk_pyr(self._h, _p(prev), _p(nxt), B, h, w, _p(pp), _p(counts), S, int(win), int(max_level),
-                                        int(max_count), float(eps), float(min_eig_thr), _p(nxt_pts), _p(st), _p(err)))
+            if flags == 0:
+                self._ck(self._L.ofk_lk_pyr(self._h, _p(prev), _p(nxt), B, h, w, _p(pp), _p(counts), S, int(win), int(max_level),
+                                            int(max_count), float(eps), float(min_eig_thr), _p(nxt_pts), _p(st), _p(err)))
+            else:
+                self._ck(self._L.ofk_lk_pyr_ex(self._h, _p(prev), _p(nxt), B, h, w, _p(pp), _p(counts), S, int(win), int(max_level),
+                                               int(max_count), float(eps), float(min_eig_thr), _p(init) if init is not None else None,
+                                               flags, _p(nxt_pts), _p(st), _p(err)))
         if single:
             return nxt_pts[0].reshape(S, 1, 2), st[0].reshape(S, 1), err[0].reshape(S, 1)
         return nxt_pts, st, err
+
+    def predict_points(self, pts, counts, sensors, mode=SEED_MODEL, gain=1.0):
+        """ofk_predict_points: the start positions a seeded LK takes for pts [B,S,2] (counts [B]) under sensors [B,28]; entries
+        beyond counts[b] are the points themselves.  Touches no resident state."""
+        pp = _arr(pts, np.float32)
+        if pp.ndim != 3 or pp.shape[2] != 2:
+            raise ValueError(f"predict_points: pts {pp.shape} is not [B, S, 2]")
+        B, S = pp.shape[:2]
+        counts = _arr(counts, np.int32, (B,))
+        sensors = _arr(sensors, np.float64, (B, SENSOR_DOUBLES))
+        out = np.zeros((B, S, 2), np.float32)
+        if S == 0:
+            return out
+        with self._lock:
+            self._ck(self._L.ofk_predict_points(self._h, _p(pp), _p(counts), B, S, _p(sensors), _seed_mode(mode), float(gain), _p(out)))
+        return out
+
+    def set_lk_seed(self, mode, gain=1.0):
+        """ofk_set_lk_seed: "off" / "model" / "rotation" (or SEED_*): every later pairs_run and stream step starts LK at the position
+        the sensors predict."""
+        self._ck(self._L.ofk_set_lk_seed(self._h, _seed_mode(mode), float(gain)))
+
+    def get_lk_seed(self):
+        m = C.c_int(0); g = C.c_double(0)
+        self._ck(self._L.ofk_get_lk_seed(self._h, C.byref(m), C.byref(g)))
+        return m.value, g.value
 
     # ------------------------------------------------------------------ estimation
     def flow_model(self, x, v, omega, d, nrm, t=None):
@@ -885,6 +936,14 @@ def get_tuning(knob):
     if L.ofk_get_tuning(str(knob).encode(), C.byref(v)) != OK:
         raise OfkError(E_INVALID, L.ofk_last_error(None).decode())
     return v.value
+
+
+def _seed_mode(mode):
+    if isinstance(mode, str):
+        if mode not in SEED_MODES:
+            raise ValueError(f"seed mode {mode!r} is none of {sorted(SEED_MODES)}")
+        return SEED_MODES[mode]
+    return int(mode)
 
 
 def make_sensors(batch, d=1.0, normal=(0, 0, 1), omega=(0, 0, 0), rotation=None, offset=(0, 0, 0.1), scaling=0.01,

@@ -29,6 +29,10 @@ class PipelineConfig:
     solve_variant: int = ofk.SOLVE_NODE
     use_feasibility: bool = False
     feas_T: float = 0.0
+    # LK start positions from the sensor model (ofk.h: ofk_set_lk_seed): "off", "model" (omega and the prior velocity) or
+    # "rotation" (omega alone); seed_gain scales the predicted flow (omega per second against flow per frame)
+    lk_seed: str = "off"
+    seed_gain: float = 1.0
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -169,6 +173,8 @@ class FlowStream:
         self.min_features, self.mask_radius = int(min_features), int(mask_radius)
         self.ctx = ofk.Context(device, width, height, batch, max(1, self.cfg.max_corners), max(0, self.cfg.max_level))
         self._params = self.cfg.to_params()
+        if self.cfg.lk_seed != "off":
+            self.ctx.set_lk_seed(self.cfg.lk_seed, self.cfg.seed_gain)
         self.fusion = fusion
         if fusion is not None:                                  # the per-stream filter state lives on the device from here on
             self._fusion = fusion.to_struct()
@@ -221,6 +227,8 @@ class FlowPipeline:
         self.streams = streams
         self.ctx = ofk.Context(device, width, height, batch, max(1, self.cfg.max_corners), max(0, self.cfg.max_level))
         self._params = self.cfg.to_params()
+        if self.cfg.lk_seed != "off":
+            self.ctx.set_lk_seed(self.cfg.lk_seed, self.cfg.seed_gain)
         if streams > 1:
             self.ctx.set_streams(streams)
 

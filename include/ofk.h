@@ -95,6 +95,43 @@ int ofk_lk_pyr(ofk_ctx *ctx, const uint8_t *prev, const uint8_t *next, int batch
                const int *counts, int pts_stride, int win, int max_level, int max_count, double eps, double min_eig_thr,
                float *next_pts, uint8_t *status, float *err);
 
+/* cv2's operation flags of calcOpticalFlowPyrLK (same values).  Semantics against oracle/image_oracle.c:orc_lk_pyr:
+ *   OFK_LK_USE_INITIAL_FLOW   at the TOP pyramid level the search starts at init_pts * 2^-L instead of at the point; everything else
+ *                             (per-level bounds tests, the carry through a skipped level, criteria clamps) is unchanged, so
+ *                             init_pts == prev_pts gives the plain result bit for bit;
+ *   OFK_LK_GET_MIN_EIGENVALS  next_pts and status as without the flag; err = the f32 minEig of the level-0 normal matrix (before the
+ *                             threshold test, whatever the status becomes), 0 where level 0 was skipped.  No L1 residual is computed.
+ * ofk_lk_pyr_ex = ofk_lk_pyr plus `flags` and the start positions init_pts [batch][pts_stride][2] (NULL unless USE_INITIAL_FLOW is
+ * set; then required, every used coordinate finite with |c| <= 1e6, else OFK_E_INVALID before any launch). */
+#define OFK_LK_USE_INITIAL_FLOW   4
+#define OFK_LK_GET_MIN_EIGENVALS  8
+int ofk_lk_pyr_ex(ofk_ctx *ctx, const uint8_t *prev, const uint8_t *next, int batch, int h, int w, const float *prev_pts,
+                  const int *counts, int pts_stride, int win, int max_level, int max_count, double eps, double min_eig_thr,
+                  const float *init_pts, int flags, float *next_pts, uint8_t *status, float *err);
+
+/* Seeding LK from the sensor model: the flow the pair's sensors predict (ofk_flow_model's expression) is applied BEFORE tracking.
+ * Per point, float64, in this order, no contraction:
+ *   x = (px - cx) * scaling, y likewise; k = (n0 x + n1 y + n2) / d;
+ *   w0 = om1 - om2 y, w1 = om2 x - om0, w2 = om0 y - om1 x;
+ *   fx = k (v0 - v2 x) + (w0 - w2 x), fy = k (v1 - v2 y) + (w1 - w2 y);
+ *   seed = (float)(px + gain * fx / scaling), y likewise.
+ * OFK_SEED_MODEL: v = the prior velocity; OFK_SEED_ROTATION: v = 0 (gyro-aided tracking when height or velocity are not trusted);
+ * OFK_SEED_OFF: no seeding (the default).  Sources: sensors[0] d, [1..3] normal, [4..6] omega, [19..21] scaling, cx, cy, [22..24] prior
+ * velocity; with ofk_fusion.use_imu the normal, omega and velocity of the resident IMU state (state[15..17], [18..20], [0..2]).
+ * scaling == 0, d == 0 or a seed coordinate that is not finite or exceeds 1e6 in magnitude: the seed is the point itself.
+ * `gain` (default 1) reconciles units, e.g. omega per second against flow per frame.
+ * ofk_set_lk_seed is a context setting read by ofk_pairs_run (every slice), ofk_stream_step[_jpeg] and ofk_stream_step_fused[_jpeg]:
+ * a k_seed_points launch writes the start positions in front of LK, which then runs with OFK_LK_USE_INITIAL_FLOW.
+ * ofk_predict_points is the predictor as a stage entry on host buffers (pts, seed_out [batch][stride][2] f32, counts [batch],
+ * sensors [batch][OFK_SENSOR_DOUBLES]); it touches no resident state, so it returns the exact seeds a resident run used. */
+#define OFK_SEED_OFF       0
+#define OFK_SEED_MODEL     1
+#define OFK_SEED_ROTATION  2
+int ofk_set_lk_seed(ofk_ctx *ctx, int mode, double gain);
+int ofk_get_lk_seed(const ofk_ctx *ctx, int *mode, double *gain);
+int ofk_predict_points(ofk_ctx *ctx, const float *pts, const int *counts, int batch, int stride, const double *sensors, int mode,
+                       double gain, float *seed_out);
+
 /* ------------------------------------------------- estimation (float64, batched over `batch` independent problems) */
 
 /* generate_test_data(x, v, omega, d, n[, t]) — node:25-29; simulation.py:7-12.
