@@ -1661,9 +1661,8 @@ void ofk_launch_zero_detect_state(hipStream_t s, unsigned int *maxbits, int *can
 void ofk_launch_select(hipStream_t s, unsigned long long *cand, int cand_cap, int *cand_count, const unsigned long long *seg,
                        int seg_cap, const int *seg_count, int nseg, const unsigned int *maxbits, double quality, int h, int w,
                        int max_corners, float min_distance, float *pts, int pts_stride, int *counts, const int *limit, int batch,
-                       unsigned *sel_hist, unsigned long long *sel_keys, bool hist_is_zero)
+                       unsigned *sel_hist, unsigned long long *sel_keys)
 {
-    if (!hist_is_zero) (void)hipMemsetAsync(sel_hist, 0, (size_t)batch * SEL_HB * sizeof(unsigned), s);
     // (SEL_G = 16 workgroups per image walk ~4 segments each; one segment per workgroup - 64 per image - was measured: 44 -> 67 us, the
     //  histogram flush of four times as many workgroups costs more than the shorter chains save)
     hipLaunchKernelGGL(k_select_prep, dim3(SEL_G, batch), dim3(256), 0, s, cand, cand_cap, cand_count, seg, seg_cap, seg_count, nseg, maxbits,

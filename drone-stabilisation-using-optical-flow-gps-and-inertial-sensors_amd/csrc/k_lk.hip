@@ -318,29 +318,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(64))) void k_lk1
 }
 
 
-// flags: OFK_LK_USE_INITIAL_FLOW (next_pts holds the start positions on entry) | OFK_LK_GET_MIN_EIGENVALS; 0 launches the plain kernels.
-// The routing by window and level geometry is the same for every variant.
+// The one routing ladder, by window and level geometry.  FLAGS == 0 launches the plain symbols, not *_f<0> instantiations (see "Variants"
+// above: the plain kernels are translation-unit text of their own); __restrict__ is no part of a function's type, so a plain kernel
+// and its flagged variants share one pointer type.
 template <int FLAGS>
 static void launch_lk_flagged(hipStream_t s, bool quad, const uint8_t *prev, const uint8_t *next, size_t pyr_stride, const ofk_levels &lv,
                               const float *prev_pts, const int *counts, int pts_stride, int win, int max_count, double eps2,
                               double min_eig_thr, float *next_pts, uint8_t *status, float *err, int batch)
 {
+    decltype(&k_lk15q) k15q;
+    decltype(&k_lk15) k15;
+    decltype(&k_lk<21>) k21, k31;
+    if constexpr (FLAGS == 0) { k15q = k_lk15q; k15 = k_lk15; k21 = k_lk<21>; k31 = k_lk<31>; }
+    else { k15q = k_lk15q_f<FLAGS>; k15 = k_lk15_f<FLAGS>; k21 = k_lk_f<21, FLAGS>; k31 = k_lk_f<31, FLAGS>; }
     const dim3 grid(pts_stride, batch);
     const float lo = (float)(eps2 * (1.0 - 1e-5)), hi = (float)(eps2 * (1.0 + 1e-5));
     if (quad)
-        hipLaunchKernelGGL(k_lk15q_f<FLAGS>, dim3((pts_stride + 3) / 4, batch), dim3(64), 0, s, prev, next, pyr_stride, lv, prev_pts, counts,
-                           pts_stride, max_count, eps2, lo, hi, min_eig_thr, next_pts, status, err);
+        hipLaunchKernelGGL(k15q, dim3((pts_stride + 3) / 4, batch), dim3(64), 0, s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride,
+                           max_count, eps2, lo, hi, min_eig_thr, next_pts, status, err);
     else if (win <= 15)
-        hipLaunchKernelGGL(k_lk15_f<FLAGS>, grid, dim3(64), 0, s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win, max_count,
-                           eps2, lo, hi, min_eig_thr, next_pts, status, err);
-    else if (win <= 21)
-        hipLaunchKernelGGL((k_lk_f<21, FLAGS>), grid, dim3(64), 0, s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win,
-                           max_count, eps2, min_eig_thr, next_pts, status, err);
+        hipLaunchKernelGGL(k15, grid, dim3(64), 0, s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win, max_count, eps2, lo, hi,
+                           min_eig_thr, next_pts, status, err);
     else
-        hipLaunchKernelGGL((k_lk_f<31, FLAGS>), grid, dim3(64), 0, s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win,
-                           max_count, eps2, min_eig_thr, next_pts, status, err);
+        hipLaunchKernelGGL(win <= 21 ? k21 : k31, grid, dim3(64), 0, s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win, max_count,
+                           eps2, min_eig_thr, next_pts, status, err);
 }
 
+// flags: OFK_LK_USE_INITIAL_FLOW (next_pts holds the start positions on entry) | OFK_LK_GET_MIN_EIGENVALS
 void ofk_launch_lk(hipStream_t s, const uint8_t *prev, const uint8_t *next, size_t pyr_stride, const ofk_levels &lv,
                    const float *prev_pts, const int *counts, int pts_stride, int win, int max_count, double eps,
                    double min_eig_thr, float *next_pts, uint8_t *status, float *err, int batch, int flags)
@@ -349,31 +353,17 @@ void ofk_launch_lk(hipStream_t s, const uint8_t *prev, const uint8_t *next, size
     if (max_count > 100) max_count = 100;
     if (eps < 0) eps = 0;
     if (eps > 10) eps = 10;
-    const double eps2 = eps * eps;
-    dim3 grid(pts_stride, batch);
     // four points per wave when the window is the reference's 15 x 15 and every level allows dword rows with ONE reflection
     // (staged columns reach 27 past a border, staged rows 23, and the 36-byte strip of a row has to fit: levels of at least 40 x 32)
     bool quad = win == 15 && (pyr_stride & 3) == 0;
     for (int l = 0; l <= lv.n; ++l) quad = quad && (lv.w[l] & 3) == 0 && lv.w[l] >= 40 && lv.h[l] >= 32 && (lv.off[l] & 3) == 0;
+#define LK_ROUTE(F) \
+    launch_lk_flagged<F>(s, quad, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win, max_count, eps * eps, min_eig_thr, next_pts, status, err, batch)
     switch (flags & (LK_SEED | LK_EIG)) {
-    case LK_SEED:
-        return launch_lk_flagged<LK_SEED>(s, quad, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win, max_count, eps2, min_eig_thr, next_pts, status, err, batch);
-    case LK_EIG:
-        return launch_lk_flagged<LK_EIG>(s, quad, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win, max_count, eps2, min_eig_thr, next_pts, status, err, batch);
-    case LK_SEED | LK_EIG:
-        return launch_lk_flagged<LK_SEED | LK_EIG>(s, quad, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win, max_count, eps2, min_eig_thr, next_pts, status, err, batch);
-    default: break;
+    case LK_SEED: return LK_ROUTE(LK_SEED);
+    case LK_EIG: return LK_ROUTE(LK_EIG);
+    case LK_SEED | LK_EIG: return LK_ROUTE(LK_SEED | LK_EIG);
+    default: return LK_ROUTE(0);
     }
-    if (quad)
-        hipLaunchKernelGGL(k_lk15q, dim3((pts_stride + 3) / 4, batch), dim3(64), 0, s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride,
-                           max_count, eps2, (float)(eps2 * (1.0 - 1e-5)), (float)(eps2 * (1.0 + 1e-5)), min_eig_thr, next_pts, status, err);
-    else if (win <= 15)
-        hipLaunchKernelGGL(k_lk15, grid, dim3(64), 0, s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win,
-                           max_count, eps2, (float)(eps2 * (1.0 - 1e-5)), (float)(eps2 * (1.0 + 1e-5)), min_eig_thr, next_pts, status, err);
-    else if (win <= 21)
-        hipLaunchKernelGGL(k_lk<21>, grid, dim3(64), 0, s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win,
-                           max_count, eps2, min_eig_thr, next_pts, status, err);
-    else
-        hipLaunchKernelGGL(k_lk<31>, grid, dim3(64), 0, s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win,
-                           max_count, eps2, min_eig_thr, next_pts, status, err);
+#undef LK_ROUTE
 }

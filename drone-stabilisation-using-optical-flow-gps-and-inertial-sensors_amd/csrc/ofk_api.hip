@@ -262,6 +262,14 @@ static int join_slices(ofk_ctx *c)
     return OFK_OK;
 }
 
+// Preamble of the entry points.  Those that leave the slices running (ofk_pairs_run and what is queued behind it) take use_device alone.
+static int use_device(ofk_ctx *c) { return hipSetDevice(c->device) == hipSuccess ? OFK_OK : ofk_fail(c, OFK_E_HIP, "hipSetDevice failed"); }
+static int enter(ofk_ctx *c)
+{
+    TRY(use_device(c));
+    return join_slices(c);
+}
+
 int ofk_join_slices(ofk_ctx *c) { return join_slices(c); }
 int ofk_prepare_streams(ofk_ctx *c) { return need_streams(c, c->nstreams < 1 ? 1 : c->nstreams, c->overlap != 0); }
 
@@ -276,8 +284,7 @@ extern "C" int ofk_sync(ofk_ctx *c)
 // every stream of the context idle (slice, auxiliary and context stream)
 static int drain_all(ofk_ctx *c)
 {
-    OFK_HIP(c, hipSetDevice(c->device));
-    TRY(join_slices(c));
+    TRY(enter(c));
     OFK_HIP(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < OFK_MAX_STREAMS; ++k) {
         if (k && c->streams[k]) OFK_HIP(c, hipStreamSynchronize(c->streams[k]));
@@ -309,11 +316,9 @@ int ofk_need_scratch(ofk_ctx *c, size_t bytes)
 static int check_geom(ofk_ctx *c, int batch, int h, int w, const char *who)
 {
     if (!c) return OFK_E_INVALID;
-    if (hipSetDevice(c->device) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "hipSetDevice failed");
     if (batch < 1 || batch > c->max_batch || h < 1 || w < 1 || (size_t)h * w > c->P || h > 16384 || w > 16384)
         return ofk_fail(c, OFK_E_INVALID, "%s: batch %d / %dx%d exceeds the context (batch %d, %zu px)", who, batch, w, h, c->max_batch, c->P);
-    TRY(join_slices(c));
-    return OFK_OK;
+    return enter(c);
 }
 
 // host [batch][bytes_per] (tight) <-> device base + b*stride
@@ -405,20 +410,75 @@ static int check_select(ofk_ctx *c, int max_corners, double quality, double min_
     return OFK_OK;
 }
 
-// device-side: eig (+mask) resident in ctx -> corners in pts_prev / counts
-static int run_select(ofk_ctx *c, bool have_max, const uint8_t *dmask, int batch, int h, int w, int max_corners, double quality,
-                      double min_distance)
+static uint8_t *const *pyr_set(ofk_ctx *c, int set) { return set ? c->pyr_alt : c->pyr; }   // set 1: the overlapped schedule's second one
+
+// The context's per-image buffers from image b0 on, for nb images: the one place that knows their strides.  A slice of ofk_pairs_run
+// builds one per stream; every other entry point works on the whole batch (b0 = 0, pyramid set 0).
+struct View {
+    int nb;
+    uint8_t *bgr[2], *pyr[2];
+    unsigned int *maxbits; int *cand_count; unsigned long long *cand, *cand_seg; int *seg_count;
+    int nseg, segcap;                                            // key segments the latest detect_response filled (0: the flat list)
+    unsigned *sel_hist; unsigned long long *sel_keys;
+    float *pts_prev, *pts_next; uint8_t *status; float *err; int *counts;
+    double *sensors, *records;
+};
+static View view_of(ofk_ctx *c, int b0, int nb, int set)
 {
-    if (!have_max) {
-        OFK_HIP(c, hipMemsetAsync(c->maxbits, 0, (size_t)batch * OFK_MAX_STRIDE * 4, c->stream));
-        ofk_launch_maxbits(c->stream, c->eig, c->img_stride, dmask, c->img_stride, h, w, c->maxbits, batch);
-    }
-    OFK_HIP(c, hipMemsetAsync(c->cand_count, 0, (size_t)batch * OFK_CNT_STRIDE * 4, c->stream));
-    ofk_launch_nms(c->stream, c->eig, c->img_stride, dmask, c->img_stride, h, w, c->maxbits, quality, c->cand, c->cand_cap,
-                   c->cand_count, c->dev_flags, batch);
-    ofk_launch_select(c->stream, c->cand, c->cand_cap, c->cand_count, nullptr, 0, nullptr, 0, c->maxbits, quality, h, w, max_corners,
-                      (float)min_distance, c->pts_prev, c->max_pts, c->counts, nullptr, batch, c->sel_hist, c->sel_keys);
+    const size_t b = (size_t)b0;
+    uint8_t *const *pyr = pyr_set(c, set);
+    View v;
+    v.nb = nb;
+    for (int k = 0; k < 2; ++k) { v.bgr[k] = c->bgr[k] + b * c->bgr_stride; v.pyr[k] = pyr[k] + b * c->pyr_stride; }
+    v.maxbits = c->maxbits + b * OFK_MAX_STRIDE; v.cand_count = c->cand_count + b * OFK_CNT_STRIDE;
+    v.cand = c->cand + b * c->cand_cap; v.cand_seg = c->cand_seg + b * c->seg_keys; v.seg_count = c->seg_count + b * OFK_SEG_MAX;
+    v.nseg = v.segcap = 0;
+    v.sel_hist = c->sel_hist + b * 1024; v.sel_keys = c->sel_keys + b * OFK_CHUNK;
+    v.pts_prev = c->pts_prev + b * c->max_pts * 2; v.pts_next = c->pts_next + b * c->max_pts * 2;
+    v.status = c->status + b * c->max_pts; v.err = c->err + b * c->max_pts; v.counts = c->counts + b;
+    v.sensors = c->sensors + b * OFK_SENSOR_DOUBLES; v.records = c->records + b * OFK_RECORD_DOUBLES;
+    return v;
+}
+
+// Detection, first half: the detection state zeroed in one launch (histogram of the selection included), then response + 3x3 NMS +
+// candidate keys of level 0 of v.pyr[0], no map in HBM.  dmask (optional) belongs to image 0 of the view.
+static int detect_response(ofk_ctx *c, hipStream_t s, View &v, const uint8_t *dmask, int h, int w, int block, double quality)
+{
+    ofk_launch_zero_detect_state(s, v.maxbits, v.cand_count, v.sel_hist, v.nb);
+    if (ofk_launch_mineig_cand(s, v.pyr[0], c->pyr_stride, h, w, block, v.maxbits, dmask, dmask ? c->img_stride : 0, quality, v.cand, c->cand_cap,
+                               v.cand_count, v.cand_seg, c->seg_keys, v.seg_count, OFK_SEG_MAX, c->dev_flags, v.nb, &v.nseg, &v.segcap))
+        return ofk_fail(c, OFK_E_INVALID, "corner response: block_size %d does not fit (LDS tile / key segments)", block);
+    return OFK_OK;
+}
+// Second half: the candidates of the view -> at most max_corners (limit[b], where given) corners per image in dst / dst_counts
+static void detect_select(ofk_ctx *c, hipStream_t s, const View &v, int h, int w, int max_corners, double quality, double min_distance,
+                          float *dst, int *dst_counts, const int *limit)
+{
+    ofk_launch_select(s, v.cand, c->cand_cap, v.cand_count, v.cand_seg, v.segcap, v.seg_count, v.nseg, v.maxbits, quality, h, w, max_corners,
+                      (float)min_distance, dst, c->max_pts, dst_counts, limit, v.nb, v.sel_hist, v.sel_keys);
+}
+
+// device-side: eig (+mask) resident in ctx -> corners in pts_prev / counts
+static int run_select(ofk_ctx *c, const uint8_t *dmask, int batch, int h, int w, int max_corners, double quality, double min_distance)
+{
+    const View v = view_of(c, 0, batch, 0);                      // nseg = 0: k_nms fills the flat list
+    ofk_launch_zero_detect_state(c->stream, v.maxbits, v.cand_count, v.sel_hist, batch);
+    ofk_launch_maxbits(c->stream, c->eig, c->img_stride, dmask, c->img_stride, h, w, v.maxbits, batch);
+    ofk_launch_nms(c->stream, c->eig, c->img_stride, dmask, c->img_stride, h, w, v.maxbits, quality, v.cand, c->cand_cap, v.cand_count,
+                   c->dev_flags, batch);
+    detect_select(c, c->stream, v, h, w, max_corners, quality, min_distance, v.pts_prev, v.counts, nullptr);
     return check_launch(c, "corner selection");
+}
+
+// flags = the host's copy of dev_flags.  A negative count or flag bit 0 is a candidate overflow: the counts (where the caller asked for
+// them) read 0 for those images and the device flags are cleared for the next call.
+static int check_capacity(ofk_ctx *c, const int *flags, int *counts, int batch)
+{
+    bool over = (flags[0] & 1) != 0;
+    for (int b = 0; counts && b < batch; ++b) if (counts[b] < 0) { over = true; counts[b] = 0; }
+    if (!over) return OFK_OK;
+    hipMemsetAsync(c->dev_flags, 0, 16, c->stream);
+    return ofk_fail(c, OFK_E_CAPACITY, "corner candidates exceeded the per-image capacity (%d)", c->cand_cap);
 }
 
 static int fetch_corners(ofk_ctx *c, int batch, int max_corners, float *pts, int *counts)
@@ -427,13 +487,7 @@ static int fetch_corners(ofk_ctx *c, int batch, int max_corners, float *pts, int
     OFK_HIP(c, hipMemcpyAsync(flags, c->dev_flags, 16, hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipMemcpyAsync(counts, c->counts, (size_t)batch * 4, hipMemcpyDeviceToHost, c->stream));
     TRY(d2h(c, pts, c->pts_prev, (size_t)c->max_pts * 8, (size_t)max_corners * 8, batch));
-    bool over = (flags[0] & 1) != 0;
-    for (int b = 0; b < batch; ++b) if (counts[b] < 0) { over = true; counts[b] = 0; }
-    if (over) {
-        hipMemsetAsync(c->dev_flags, 0, 16, c->stream);
-        return ofk_fail(c, OFK_E_CAPACITY, "corner candidates exceeded the per-image capacity (%d)", c->cand_cap);
-    }
-    return OFK_OK;
+    return check_capacity(c, flags, counts, batch);
 }
 
 extern "C" int ofk_select_corners(ofk_ctx *c, const float *eig, const uint8_t *mask, int batch, int h, int w, int max_corners,
@@ -447,7 +501,7 @@ extern "C" int ofk_select_corners(ofk_ctx *c, const float *eig, const uint8_t *m
     TRY(h2d(c, c->eig, c->img_stride * 4, eig, px * 4, batch));
     const uint8_t *dmask = nullptr;
     if (mask) { TRY(lazy_mask(c)); TRY(h2d(c, c->mask, c->img_stride, mask, px, batch)); dmask = c->mask; }
-    TRY(run_select(c, false, dmask, batch, h, w, max_corners, quality, min_distance));
+    TRY(run_select(c, dmask, batch, h, w, max_corners, quality, min_distance));
     return fetch_corners(c, batch, max_corners, pts, counts);
 }
 
@@ -462,15 +516,9 @@ extern "C" int ofk_good_features(ofk_ctx *c, const uint8_t *gray, const uint8_t 
     TRY(h2d(c, c->pyr[0], c->pyr_stride, gray, px, batch));
     const uint8_t *dmask = nullptr;
     if (mask) { TRY(lazy_mask(c)); TRY(h2d(c, c->mask, c->img_stride, mask, px, batch)); dmask = c->mask; }
-    OFK_HIP(c, hipMemsetAsync(c->maxbits, 0, (size_t)batch * OFK_MAX_STRIDE * 4, c->stream));
-    OFK_HIP(c, hipMemsetAsync(c->cand_count, 0, (size_t)batch * OFK_CNT_STRIDE * 4, c->stream));
-    int nseg = 0, segcap = 0;
-    if (ofk_launch_mineig_cand(c->stream, c->pyr[0], c->pyr_stride, h, w, block, c->maxbits, dmask, c->img_stride, quality, c->cand,
-                               c->cand_cap, c->cand_count, c->cand_seg, c->seg_keys, c->seg_count, OFK_SEG_MAX, c->dev_flags, batch,
-                               &nseg, &segcap))
-        return ofk_fail(c, OFK_E_INVALID, "corner response: block_size %d does not fit (LDS tile / key segments)", block);
-    ofk_launch_select(c->stream, c->cand, c->cand_cap, c->cand_count, c->cand_seg, segcap, c->seg_count, nseg, c->maxbits, quality, h, w,
-                      max_corners, (float)min_distance, c->pts_prev, c->max_pts, c->counts, nullptr, batch, c->sel_hist, c->sel_keys);
+    View v = view_of(c, 0, batch, 0);
+    TRY(detect_response(c, c->stream, v, dmask, h, w, block, quality));
+    detect_select(c, c->stream, v, h, w, max_corners, quality, min_distance, v.pts_prev, v.counts, nullptr);
     TRY(check_launch(c, "corner detection"));
     return fetch_corners(c, batch, max_corners, pts, counts);
 }
@@ -483,22 +531,27 @@ static int check_lk(ofk_ctx *c, int h, int w, int win, int max_level)
     return OFK_OK;
 }
 
-// builds levels 1..L of both resident pyramids
-static void build_pyramids(ofk_ctx *c, const ofk_levels &lv, int batch, int which_mask)
+// Levels 1..lv.n of nb resident pyramids (pyr1 == NULL) or of nb pairs of them: levels 1..3 in one pass where the geometry allows it,
+// then level by level
+static void build_pyramids(ofk_ctx *c, hipStream_t s, uint8_t *pyr0, uint8_t *pyr1, const ofk_levels &lv, int nb)
 {
-    int l0 = 1;                                                  // levels 1..3 in one pass where the geometry allows it
-    if (which_mask == 3 ? ofk_launch_pyr3(c->stream, c->pyr[0], c->pyr[1], c->pyr_stride, lv, batch, 2 * batch)
-                        : ofk_launch_pyr3(c->stream, c->pyr[which_mask == 1 ? 0 : 1], nullptr, c->pyr_stride, lv, batch, batch)) l0 = 4;
-    for (int l = l0; l <= lv.n; ++l) {
-        if (which_mask == 3)
-            ofk_launch_pyr_down2(c->stream, c->pyr[0] + lv.off[l - 1], c->pyr[1] + lv.off[l - 1], c->pyr_stride, lv.h[l - 1], lv.w[l - 1],
-                                 c->pyr[0] + lv.off[l], c->pyr[1] + lv.off[l], c->pyr_stride, batch);
-        else {
-            const int k = which_mask == 1 ? 0 : 1;
-            ofk_launch_pyr_down(c->stream, c->pyr[k] + lv.off[l - 1], c->pyr_stride, lv.h[l - 1], lv.w[l - 1], c->pyr[k] + lv.off[l],
-                                c->pyr_stride, batch);
-        }
+    for (int l = ofk_launch_pyr3(s, pyr0, pyr1, c->pyr_stride, lv, nb, pyr1 ? 2 * nb : nb) ? 4 : 1; l <= lv.n; ++l) {
+        if (pyr1)
+            ofk_launch_pyr_down2(s, pyr0 + lv.off[l - 1], pyr1 + lv.off[l - 1], c->pyr_stride, lv.h[l - 1], lv.w[l - 1], pyr0 + lv.off[l],
+                                 pyr1 + lv.off[l], c->pyr_stride, nb);
+        else
+            ofk_launch_pyr_down(s, pyr0 + lv.off[l - 1], c->pyr_stride, lv.h[l - 1], lv.w[l - 1], pyr0 + lv.off[l], c->pyr_stride, nb);
     }
+}
+
+// The track step of the resident chains: with ofk_set_lk_seed on, the start positions are written where LK reads them (imu_state: the
+// source k_stream_fuse uses under use_imu, NULL = the sensors only) and LK starts there
+static void track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, const ofk_params *p, const double *imu_state)
+{
+    const bool seeded = c->lk_seed_mode != OFK_SEED_OFF;
+    if (seeded) ofk_launch_seed_points(s, v.pts_prev, v.counts, c->max_pts, v.sensors, imu_state, c->lk_seed_mode, c->lk_seed_gain, v.pts_next, v.nb);
+    ofk_launch_lk(s, v.pyr[0], v.pyr[1], c->pyr_stride, lv, v.pts_prev, v.counts, c->max_pts, p->win, p->max_count, p->eps, p->min_eig_thr,
+                  v.pts_next, v.status, v.err, v.nb, seeded ? OFK_LK_USE_INITIAL_FLOW : 0);
 }
 
 static int lk_pyr_impl(ofk_ctx *c, const char *who, const uint8_t *prev, const uint8_t *next, int batch, int h, int w, const float *prev_pts,
@@ -528,7 +581,7 @@ static int lk_pyr_impl(ofk_ctx *c, const char *who, const uint8_t *prev, const u
     TRY(h2d(c, c->pts_prev, (size_t)c->max_pts * 8, prev_pts, (size_t)pts_stride * 8, batch));
     if (seeded) TRY(h2d(c, c->pts_next, (size_t)c->max_pts * 8, init_pts, (size_t)pts_stride * 8, batch));   // in/out, as cv2's nextPts
     OFK_HIP(c, hipMemcpyAsync(c->counts, counts, (size_t)batch * 4, hipMemcpyHostToDevice, c->stream));
-    build_pyramids(c, lv, batch, 3);
+    build_pyramids(c, c->stream, c->pyr[0], c->pyr[1], lv, batch);
     ofk_launch_lk(c->stream, c->pyr[0], c->pyr[1], c->pyr_stride, lv, c->pts_prev, c->counts, c->max_pts, win, max_count, eps,
                   min_eig_thr, c->pts_next, c->status, c->err, batch, flags);
     TRY(check_launch(c, "k_lk"));
@@ -581,8 +634,7 @@ extern "C" int ofk_predict_points(ofk_ctx *c, const float *pts, const int *count
     if (mode != OFK_SEED_MODEL && mode != OFK_SEED_ROTATION) return ofk_fail(c, OFK_E_INVALID, "ofk_predict_points: mode must be OFK_SEED_MODEL or OFK_SEED_ROTATION");
     for (int b = 0; b < batch; ++b)
         if (counts[b] < 0 || counts[b] > stride) return ofk_fail(c, OFK_E_INVALID, "counts[%d]=%d outside 0..%d", b, counts[b], stride);
-    if (hipSetDevice(c->device) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "hipSetDevice failed");
-    TRY(join_slices(c));
+    TRY(enter(c));
     const size_t pb = up((size_t)batch * stride * 8, 256), cb = up((size_t)batch * 4, 256), sb = up((size_t)batch * OFK_SENSOR_DOUBLES * 8, 256);
     TRY(ofk_need_scratch(c, 2 * pb + cb + sb));
     char *base = (char *)c->scratch;
@@ -609,7 +661,7 @@ extern "C" int ofk_pyramid_u8(ofk_ctx *c, const uint8_t *gray, int batch, int h,
     if (max_level < 0 || max_level > c->max_level) return ofk_fail(c, OFK_E_INVALID, "max_level %d outside 0..%d", max_level, c->max_level);
     const ofk_levels lv = ofk_make_levels(h, w, 0, max_level);
     TRY(h2d(c, c->pyr[0], c->pyr_stride, gray, (size_t)h * w, batch));
-    build_pyramids(c, lv, batch, 1);
+    build_pyramids(c, c->stream, c->pyr[0], nullptr, lv, batch);
     TRY(check_launch(c, "pyramid"));
     size_t total = 0, o = 0;
     for (int l = 1; l <= lv.n; ++l) total += (size_t)lv.h[l] * lv.w[l];
@@ -645,8 +697,7 @@ static int get(ofk_ctx *c, void *host, const void *dev, size_t bytes)
 static int est_begin(ofk_ctx *c, size_t bytes, Bump &bp)
 {
     if (!c) return OFK_E_INVALID;
-    if (hipSetDevice(c->device) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "hipSetDevice failed");
-    TRY(join_slices(c));
+    TRY(enter(c));
     TRY(ofk_need_scratch(c, bytes + 64 * 256));
     bp.c = c; bp.base = (char *)c->scratch; bp.off = 0; bp.rc = OFK_OK;
     return OFK_OK;
@@ -910,6 +961,19 @@ extern "C" int ofk_hist_overlap(ofk_ctx *c, const double *data1, int n1, const d
 }
 
 // ------------------------------------------------------------------------------------------------ resident pipeline
+// The second pyramid set of the overlapped schedule, allocated on first use: true when the schedule is on and the set exists.  Where it
+// does not fit, the context falls back to the one-set schedule for good.
+static bool need_pyr_alt(ofk_ctx *c)
+{
+    if (!c->overlap) return false;
+    for (int k = 0; k < 2; ++k)
+        if (!c->pyr_alt[k] && hipMalloc((void **)&c->pyr_alt[k], (size_t)c->max_batch * c->pyr_stride) != hipSuccess) c->overlap = 0;
+    if (c->overlap) return true;
+    (void)hipGetLastError();
+    for (int k = 0; k < 2; ++k) if (c->pyr_alt[k]) { hipFree(c->pyr_alt[k]); c->pyr_alt[k] = nullptr; }
+    return false;
+}
+
 extern "C" int ofk_pairs_upload(ofk_ctx *c, const uint8_t *prev_bgr, const uint8_t *next_bgr, int batch, int h, int w)
 {
     TRY(check_geom(c, batch, h, w, "ofk_pairs_upload"));
@@ -958,22 +1022,20 @@ extern "C" const char *ofk_jpeg_stage_error(const ofk_ctx *c, int slot) { return
 extern "C" int ofk_pairs_upload_staged(ofk_ctx *c, int slot)
 {
     if (!c) return OFK_E_INVALID;
-    if (hipSetDevice(c->device) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "hipSetDevice failed");
+    TRY(use_device(c));
     // With one slice and the double-buffered pyramid sets of the overlapped schedule the decoder's colour kernel writes GRAY straight
     // into level 0 of the set the next ofk_pairs_run will take (the one the run in flight is NOT reading), on the ingest stream: the
     // decoder passes of batch k + 1 go on beside the run of batch k, and that run's first stage is already done (gray_direct_set).  The
     // set was last read by the LK of the run before the latest one (ev_lkdone).  With several slices, or without the second set, the
     // old way: BGR into bgr[] on the context's stream, behind everything.
-    bool direct = c->nstreams <= 1 && c->overlap != 0;
-    for (int k = 0; k < 2 && direct; ++k)
-        if (!c->pyr_alt[k] && hipMalloc((void **)&c->pyr_alt[k], (size_t)c->max_batch * c->pyr_stride) != hipSuccess) { (void)hipGetLastError(); direct = false; }
+    const bool direct = c->nstreams <= 1 && need_pyr_alt(c);
     int h = 0, w = 0, batch = 0;
     c->cur_batch = 0;
     c->gray_direct_set = -1;
     if (direct) {
         const int set = c->pyr_set;
-        uint8_t *const P0 = set ? c->pyr_alt[0] : c->pyr[0], *const P1 = set ? c->pyr_alt[1] : c->pyr[1];
-        TRY(ofk_jpeg_decode_staged_pairs(c, slot, P0, P1, c->pyr_stride, c->P, &batch, &h, &w, c->ev_lkdone[set], OFK_MAX_STREAMS, 1));
+        uint8_t *const *pyr = pyr_set(c, set);
+        TRY(ofk_jpeg_decode_staged_pairs(c, slot, pyr[0], pyr[1], c->pyr_stride, c->P, &batch, &h, &w, c->ev_lkdone[set], OFK_MAX_STREAMS, 1));
         c->gray_direct_set = set;
     } else {
         TRY(join_slices(c));
@@ -987,9 +1049,8 @@ extern "C" int ofk_pairs_upload_staged(ofk_ctx *c, int slot)
 extern "C" int ofk_jpeg_decode_bgr8(ofk_ctx *c, const uint8_t *const *jpeg, const size_t *nbytes, int batch, uint8_t *bgr)
 {
     if (!c) return OFK_E_INVALID;
-    if (hipSetDevice(c->device) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "hipSetDevice failed");
     if (!bgr) return ofk_fail(c, OFK_E_INVALID, "ofk_jpeg_decode_bgr8: NULL output");
-    TRY(join_slices(c));
+    TRY(enter(c));
     int h = 0, w = 0;
     uint8_t *dev = nullptr;
     size_t stride = 0;
@@ -1000,7 +1061,7 @@ extern "C" int ofk_jpeg_decode_bgr8(ofk_ctx *c, const uint8_t *const *jpeg, cons
 extern "C" int ofk_pairs_set_sensors(ofk_ctx *c, const double *sensors, int batch)
 {
     if (!c || !sensors || batch < 1 || batch > c->max_batch) return ofk_fail(c, OFK_E_INVALID, "ofk_pairs_set_sensors: bad argument");
-    TRY(join_slices(c));
+    TRY(enter(c));
     OFK_HIP(c, hipMemcpyAsync(c->sensors, sensors, (size_t)batch * OFK_SENSOR_DOUBLES * 8, hipMemcpyHostToDevice, c->stream));
     OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
@@ -1028,7 +1089,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
 {
     if (!c || !p) return OFK_E_INVALID;
     if (c->cur_batch < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_pairs_run: no resident frame pairs (call ofk_pairs_upload)");
-    if (hipSetDevice(c->device) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "hipSetDevice failed");
+    TRY(use_device(c));
     const int B = c->cur_batch, h = c->cur_h, w = c->cur_w;
     TRY(check_block(c, h, w, p->block_size));
     TRY(check_select(c, p->max_corners, p->quality, p->min_distance));
@@ -1043,18 +1104,12 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
     // pyramids HBM-bound, so the two kinds run beside each other.  The gray conversions and the pyramids (HBM-bound) run on an auxiliary stream and may even run AHEAD of the context's
     // stream: they write one of two pyramid buffer sets, alternating per call, so the next call's conversions overlap this
     // call's LK.  The only hazard is the set itself, still read by the LK of the call that used it last (ev_lkdone).
-    bool overlap = c->overlap != 0;
-    if (overlap && !c->pyr_alt[0]) {
-        for (int k = 0; k < 2 && overlap; ++k)
-            if (hipMalloc((void **)&c->pyr_alt[k], (size_t)c->max_batch * c->pyr_stride) != hipSuccess) { (void)hipGetLastError(); overlap = false; }
-        if (!overlap) { for (int k = 0; k < 2; ++k) if (c->pyr_alt[k]) { hipFree(c->pyr_alt[k]); c->pyr_alt[k] = nullptr; } c->overlap = 0; }
-    }
+    const bool overlap = need_pyr_alt(c);
     int set = 0;
     if (overlap) { set = c->pyr_set; c->pyr_set ^= 1; }
     const bool have_gray = c->gray_direct_set >= 0;               // compressed ingest: the frames came in as gray level 0 of that set (and only there)
     if (have_gray) { set = c->gray_direct_set; c->pyr_set = set ^ 1; }
     c->pyr_last = set;
-    uint8_t *const P0 = set ? c->pyr_alt[0] : c->pyr[0], *const P1 = set ? c->pyr_alt[1] : c->pyr[1];
     // Slices are forked off the context's stream once and then free-run over consecutive calls: nothing joins them until an
     // entry point needs the context's stream to see their results (join_slices).  On the fork the response kernels are chained
     // slice after slice, which offsets the slices by one response kernel for as long as they run.
@@ -1070,31 +1125,19 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
         hipStream_t st = k == 0 ? c->stream : c->streams[k];
         hipStream_t sa = overlap ? c->aux[k] : st;
         if (overlap) OFK_HIP(c, hipStreamWaitEvent(sa, c->ev_lkdone[set][k], 0));
-        uint8_t *bgr0 = c->bgr[0] + (size_t)b0 * c->bgr_stride, *bgr1 = c->bgr[1] + (size_t)b0 * c->bgr_stride;
-        uint8_t *pyr0 = P0 + (size_t)b0 * c->pyr_stride, *pyr1 = P1 + (size_t)b0 * c->pyr_stride;
-        unsigned int *maxbits = c->maxbits + (size_t)b0 * OFK_MAX_STRIDE;
-        int *cand_count = c->cand_count + (size_t)b0 * OFK_CNT_STRIDE;
-        unsigned long long *cand = c->cand + (size_t)b0 * c->cand_cap, *cand_seg = c->cand_seg + (size_t)b0 * c->seg_keys;
-        int *seg_count = c->seg_count + (size_t)b0 * OFK_SEG_MAX;
-        float *pts_prev = c->pts_prev + (size_t)b0 * c->max_pts * 2, *pts_next = c->pts_next + (size_t)b0 * c->max_pts * 2;
-        uint8_t *status = c->status + (size_t)b0 * c->max_pts;
-        float *err = c->err + (size_t)b0 * c->max_pts;
-        int *counts = c->counts + b0;
-        int nseg = 0, segcap = 0;
+        View v = view_of(c, b0, nb, set);
         if (!have_gray) {
             StageTimer t(c, OFK_STAGE_GRAY, sa);
-            ofk_launch_gray(sa, bgr0, c->bgr_stride, pyr0, c->pyr_stride, nb, h, w);
+            ofk_launch_gray(sa, v.bgr[0], c->bgr_stride, v.pyr[0], c->pyr_stride, nb, h, w);
         }
         if (overlap) OFK_HIP(c, hipEventRecord(c->ev_g0[k], sa));
         if (!have_gray) {
             StageTimer t(c, OFK_STAGE_GRAY, sa);
-            ofk_launch_gray(sa, bgr1, c->bgr_stride, pyr1, c->pyr_stride, nb, h, w);
+            ofk_launch_gray(sa, v.bgr[1], c->bgr_stride, v.pyr[1], c->pyr_stride, nb, h, w);
         }
         {
             StageTimer t(c, OFK_STAGE_PYR, sa);
-            for (int l = ofk_launch_pyr3(sa, pyr0, pyr1, c->pyr_stride, lv, nb, 2 * nb) ? 4 : 1; l <= lv.n; ++l)
-                ofk_launch_pyr_down2(sa, pyr0 + lv.off[l - 1], pyr1 + lv.off[l - 1], c->pyr_stride, lv.h[l - 1], lv.w[l - 1], pyr0 + lv.off[l],
-                                     pyr1 + lv.off[l], c->pyr_stride, nb);
+            build_pyramids(c, sa, v.pyr[0], v.pyr[1], lv, nb);
         }
         if (overlap) {
             OFK_HIP(c, hipEventRecord(c->ev_aux[k], sa));
@@ -1102,34 +1145,25 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
         }
         if (fork && k > 0) OFK_HIP(c, hipStreamWaitEvent(st, c->ev_stagger[k - 1], 0));
         {
-            StageTimer t(c, OFK_STAGE_EIG, st);                  // response + 3x3 NMS + candidate keys, no map in HBM
-            ofk_launch_zero_detect_state(st, maxbits, cand_count, c->sel_hist + (size_t)b0 * 1024, nb);   // one launch, histogram of the selection included
-            if (ofk_launch_mineig_cand(st, pyr0, c->pyr_stride, h, w, p->block_size, maxbits, nullptr, 0, p->quality, cand, c->cand_cap,
-                                       cand_count, cand_seg, c->seg_keys, seg_count, OFK_SEG_MAX, c->dev_flags, nb, &nseg, &segcap))
-                return ofk_fail(c, OFK_E_INVALID, "corner response: block_size %d does not fit (LDS tile / key segments)", p->block_size);
+            StageTimer t(c, OFK_STAGE_EIG, st);
+            TRY(detect_response(c, st, v, nullptr, h, w, p->block_size, p->quality));
         }
         if (fork) OFK_HIP(c, hipEventRecord(c->ev_stagger[k], st));
         {
             StageTimer t(c, OFK_STAGE_SELECT, st);
-            ofk_launch_select(st, cand, c->cand_cap, cand_count, cand_seg, segcap, seg_count, nseg, maxbits, p->quality, h, w, p->max_corners,
-                              (float)p->min_distance, pts_prev, c->max_pts, counts, nullptr, nb, c->sel_hist + (size_t)b0 * 1024,
-                              c->sel_keys + (size_t)b0 * OFK_CHUNK, true);
+            detect_select(c, st, v, h, w, p->max_corners, p->quality, p->min_distance, v.pts_prev, v.counts, nullptr);
         }
         if (overlap) OFK_HIP(c, hipStreamWaitEvent(st, c->ev_aux[k], 0));    // LK needs both pyramids
         {
             StageTimer t(c, OFK_STAGE_LK, st);
-            if (c->lk_seed_mode != OFK_SEED_OFF)                 // start positions from the pair's sensors, written where LK reads them
-                ofk_launch_seed_points(st, pts_prev, counts, c->max_pts, c->sensors + (size_t)b0 * OFK_SENSOR_DOUBLES, nullptr, c->lk_seed_mode,
-                                       c->lk_seed_gain, pts_next, nb);
-            ofk_launch_lk(st, pyr0, pyr1, c->pyr_stride, lv, pts_prev, counts, c->max_pts, p->win, p->max_count, p->eps, p->min_eig_thr,
-                          pts_next, status, err, nb, c->lk_seed_mode != OFK_SEED_OFF ? OFK_LK_USE_INITIAL_FLOW : 0);
+            track(c, st, v, lv, p, nullptr);                     // a seed comes from the pair's sensors
         }
         if (overlap) OFK_HIP(c, hipEventRecord(c->ev_lkdone[set][k], st));   // this pyramid set may be rewritten from here on
         if (c->x_pending) OFK_HIP(c, hipStreamWaitEvent(st, c->ev_x, 0));    // the previous call's records are still being exported
         {
             StageTimer t(c, OFK_STAGE_SOLVE, st);
-            ofk_launch_pairs_solve(st, pts_prev, pts_next, status, counts, c->max_pts, c->sensors + (size_t)b0 * OFK_SENSOR_DOUBLES,
-                                   p->solve_variant, p->use_feasibility, p->feas_T, cand_count, c->records + (size_t)b0 * OFK_RECORD_DOUBLES, nb);
+            ofk_launch_pairs_solve(st, v.pts_prev, v.pts_next, v.status, v.counts, c->max_pts, v.sensors, p->solve_variant, p->use_feasibility,
+                                   p->feas_T, v.cand_count, v.records, nb);
         }
         if (S > 1) OFK_HIP(c, hipEventRecord(c->ev_end[k], st));             // joined lazily (join_slices), not here
     }
@@ -1141,11 +1175,10 @@ extern "C" int ofk_pairs_download(ofk_ctx *c, double *records, float *prev_pts, 
                                   int *counts)
 {
     if (!c || c->cur_batch < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_pairs_download: nothing resident");
-    if (hipSetDevice(c->device) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "hipSetDevice failed");
+    TRY(enter(c));
     const int B = c->cur_batch;
     const size_t np = (size_t)B * c->max_pts;
     int flags[4];
-    TRY(join_slices(c));
     OFK_HIP(c, hipMemcpyAsync(flags, c->dev_flags, 16, hipMemcpyDeviceToHost, c->stream));
     if (records) OFK_HIP(c, hipMemcpyAsync(records, c->records, (size_t)B * OFK_RECORD_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
     if (prev_pts) OFK_HIP(c, hipMemcpyAsync(prev_pts, c->pts_prev, np * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1154,12 +1187,15 @@ extern "C" int ofk_pairs_download(ofk_ctx *c, double *records, float *prev_pts, 
     if (err) OFK_HIP(c, hipMemcpyAsync(err, c->err, np * 4, hipMemcpyDeviceToHost, c->stream));
     if (counts) OFK_HIP(c, hipMemcpyAsync(counts, c->counts, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipStreamSynchronize(c->stream));
-    bool over = (flags[0] & 1) != 0;
-    if (counts)
-        for (int b = 0; b < B; ++b) if (counts[b] < 0) { over = true; counts[b] = 0; }
-    if (over) {
-        hipMemsetAsync(c->dev_flags, 0, 16, c->stream);
-        return ofk_fail(c, OFK_E_CAPACITY, "corner candidates exceeded the per-image capacity (%d)", c->cand_cap);
+    return check_capacity(c, flags, counts, B);
+}
+
+// What was just queued on the tail stream reads the records: while the slices are open, their next solve must not overtake it
+static int tail_done(ofk_ctx *c, hipStream_t s)
+{
+    if (c->slices_open) {
+        OFK_HIP(c, hipEventRecord(c->ev_x, s));
+        c->x_pending = 1;
     }
     return OFK_OK;
 }
@@ -1171,10 +1207,7 @@ int ofk_export_records_stream(ofk_ctx *c, float *device_dst, int batch, hipStrea
     hipStream_t s;
     TRY(tail_stream(c, &s));
     ofk_launch_records_f32(s, c->records, device_dst, batch);
-    if (c->slices_open) {                                        // the other slices' next solve must not overtake the export
-        OFK_HIP(c, hipEventRecord(c->ev_x, s));
-        c->x_pending = 1;
-    }
+    TRY(tail_done(c, s));
     if (stream_out) *stream_out = s;
     return check_launch(c, "k_records_f32");
 }
@@ -1202,25 +1235,17 @@ static int stream_ingest(ofk_ctx *c, int k, const uint8_t *bgr, int batch, int h
     if (bgr) TRY(h2d(c, c->bgr[k], c->bgr_stride, bgr, (size_t)h * w * 3, batch));      // NULL: the frames are in bgr[k] already (JPEG ingest)
     c->pyr_last = 0;
     ofk_launch_gray(c->stream, c->bgr[k], c->bgr_stride, c->pyr[k], c->pyr_stride, batch, h, w);
-    for (int l = ofk_launch_pyr3(c->stream, c->pyr[k], nullptr, c->pyr_stride, lv, batch, batch) ? 4 : 1; l <= lv.n; ++l)
-        ofk_launch_pyr_down(c->stream, c->pyr[k] + lv.off[l - 1], c->pyr_stride, lv.h[l - 1], lv.w[l - 1], c->pyr[k] + lv.off[l],
-                            c->pyr_stride, batch);
+    build_pyramids(c, c->stream, c->pyr[k], nullptr, lv, batch);
     return OFK_OK;
 }
 
-// corners of pyramid slot k (level 0) -> dst/dst_counts, optional mask and per-stream budget
-static int stream_detect(ofk_ctx *c, int k, const uint8_t *dmask, const int *limit, int batch, int h, int w, const ofk_params *p,
-                         float *dst, int *dst_counts)
+// corners of the previous frame (pyramid slot 0, level 0) -> dst/dst_counts, optional mask and per-stream budget
+static int stream_detect(ofk_ctx *c, const uint8_t *dmask, const int *limit, int batch, int h, int w, const ofk_params *p, float *dst,
+                         int *dst_counts)
 {
-    int nseg = 0, segcap = 0;
-    OFK_HIP(c, hipMemsetAsync(c->maxbits, 0, (size_t)batch * OFK_MAX_STRIDE * 4, c->stream));
-    OFK_HIP(c, hipMemsetAsync(c->cand_count, 0, (size_t)batch * OFK_CNT_STRIDE * 4, c->stream));
-    if (ofk_launch_mineig_cand(c->stream, c->pyr[k], c->pyr_stride, h, w, p->block_size, c->maxbits, dmask, c->img_stride, p->quality, c->cand,
-                               c->cand_cap, c->cand_count, c->cand_seg, c->seg_keys, c->seg_count, OFK_SEG_MAX, c->dev_flags, batch, &nseg,
-                               &segcap))
-        return ofk_fail(c, OFK_E_INVALID, "corner response: block_size %d does not fit (LDS tile / key segments)", p->block_size);
-    ofk_launch_select(c->stream, c->cand, c->cand_cap, c->cand_count, c->cand_seg, segcap, c->seg_count, nseg, c->maxbits, p->quality, h, w,
-                      p->max_corners, (float)p->min_distance, dst, c->max_pts, dst_counts, limit, batch, c->sel_hist, c->sel_keys);
+    View v = view_of(c, 0, batch, 0);
+    TRY(detect_response(c, c->stream, v, dmask, h, w, p->block_size, p->quality));
+    detect_select(c, c->stream, v, h, w, p->max_corners, p->quality, p->min_distance, dst, dst_counts, limit);
     return check_launch(c, "stream corner detection");
 }
 
@@ -1233,14 +1258,9 @@ static int stream_fetch_tracks(ofk_ctx *c, int batch, int max_corners, float *tr
     if (tracks) OFK_HIP(c, hipMemcpy2DAsync(tracks, (size_t)max_corners * 8, c->pts_prev, (size_t)c->max_pts * 8, (size_t)max_corners * 8, batch,
                                             hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipStreamSynchronize(c->stream));
-    bool over = (flags[0] & 1) != 0;
-    for (int b = 0; b < batch; ++b) if (c->h_counts[b] < 0) { over = true; c->h_counts[b] = 0; }
+    const int rc = check_capacity(c, flags, c->h_counts, batch);
     if (counts) memcpy(counts, c->h_counts, (size_t)batch * 4);
-    if (over) {
-        hipMemsetAsync(c->dev_flags, 0, 16, c->stream);
-        return ofk_fail(c, OFK_E_CAPACITY, "corner candidates exceeded the per-image capacity (%d)", c->cand_cap);
-    }
-    return OFK_OK;
+    return rc;
 }
 
 // first_bgr == NULL: the first frames have been decoded into bgr[0] already (ofk_stream_begin_jpeg)
@@ -1252,7 +1272,7 @@ static int stream_begin_impl(ofk_ctx *c, const uint8_t *first_bgr, int batch, in
     TRY(stream_alloc(c));
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     TRY(stream_ingest(c, 0, first_bgr, batch, h, w, lv));
-    TRY(stream_detect(c, 0, nullptr, nullptr, batch, h, w, p, c->pts_prev, c->counts));
+    TRY(stream_detect(c, nullptr, nullptr, batch, h, w, p, c->pts_prev, c->counts));
     c->stream_h = h; c->stream_w = w; c->stream_batch = batch;
     return stream_fetch_tracks(c, batch, p->max_corners, tracks, counts);
 }
@@ -1279,7 +1299,9 @@ extern "C" int ofk_stream_begin_jpeg(ofk_ctx *c, const uint8_t *const *jpeg, con
     return stream_begin_impl(c, nullptr, batch, h, w, p, tracks, counts);
 }
 
-// next_bgr == NULL: the new frames are in bgr[1] already (ofk_stream_step_jpeg)
+// the node's initial state (node:182-217): vel 0.1, first message pending, rotation I, normal e_z
+static const double k_imu_init[OFK_IMU_STATE] = {0.1, 0.1, 0.1, 0, 0, 1, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 1, 0, 0, 0, 0, 0, 0};
+
 static int filters_alloc(ofk_ctx *c)
 {
     const size_t B = (size_t)c->max_batch;
@@ -1289,9 +1311,8 @@ static int filters_alloc(ofk_ctx *c)
         OFK_HIP(c, hipMalloc((void **)&c->kf_P, B * 36 * 8)); OFK_HIP(c, hipMalloc((void **)&c->fused, B * 8 * 8));
         OFK_HIP(c, hipMemsetAsync(c->imu_dv, 0, B * 24, c->stream)); OFK_HIP(c, hipMemsetAsync(c->fused, 0, B * 64, c->stream));
         OFK_HIP(c, hipMemsetAsync(c->kf_mats, 0, 5 * 36 * 8, c->stream));
-        // the node's initial state (node:182-217): vel 0.1, first message pending, rotation I, normal e_z
-        double init[OFK_IMU_STATE] = {0.1, 0.1, 0.1, 0, 0, 1, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 1, 0, 0, 0, 0, 0, 0};
-        for (size_t b = 0; b < B; ++b) OFK_HIP(c, hipMemcpyAsync(c->imu_state + b * OFK_IMU_STATE, init, sizeof init, hipMemcpyHostToDevice, c->stream));
+        for (size_t b = 0; b < B; ++b)
+            OFK_HIP(c, hipMemcpyAsync(c->imu_state + b * OFK_IMU_STATE, k_imu_init, sizeof k_imu_init, hipMemcpyHostToDevice, c->stream));
         OFK_HIP(c, hipStreamSynchronize(c->stream));
     }
     return OFK_OK;
@@ -1300,12 +1321,11 @@ static int filters_alloc(ofk_ctx *c)
 extern "C" int ofk_imu_reset(ofk_ctx *c, const double *state0, int batch)
 {
     if (!c || batch < 1 || batch > c->max_batch) return ofk_fail(c, OFK_E_INVALID, "ofk_imu_reset: bad argument");
-    OFK_HIP(c, hipSetDevice(c->device));
-    TRY(join_slices(c));
+    TRY(enter(c));
     TRY(filters_alloc(c));
-    double init[OFK_IMU_STATE] = {0.1, 0.1, 0.1, 0, 0, 1, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 1, 0, 0, 0, 0, 0, 0};
-    const double *src = state0 ? state0 : init;
-    for (int b = 0; b < batch; ++b) OFK_HIP(c, hipMemcpyAsync(c->imu_state + (size_t)b * OFK_IMU_STATE, src, sizeof init, hipMemcpyHostToDevice, c->stream));
+    const double *src = state0 ? state0 : k_imu_init;
+    for (int b = 0; b < batch; ++b)
+        OFK_HIP(c, hipMemcpyAsync(c->imu_state + (size_t)b * OFK_IMU_STATE, src, sizeof k_imu_init, hipMemcpyHostToDevice, c->stream));
     OFK_HIP(c, hipMemsetAsync(c->imu_dv, 0, (size_t)batch * 24, c->stream));
     OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
@@ -1314,8 +1334,7 @@ extern "C" int ofk_imu_reset(ofk_ctx *c, const double *state0, int batch)
 extern "C" int ofk_imu_push(ofk_ctx *c, const double *msgs, const int *counts, int max_msgs, int batch)
 {
     if (!c || !msgs || !counts || max_msgs < 1 || batch < 1 || batch > c->max_batch) return ofk_fail(c, OFK_E_INVALID, "ofk_imu_push: bad argument");
-    OFK_HIP(c, hipSetDevice(c->device));
-    TRY(join_slices(c));
+    TRY(enter(c));
     TRY(filters_alloc(c));
     const size_t mb = (size_t)batch * max_msgs * OFK_IMU_MSG * 8;
     if (mb > c->imu_msgs_bytes) {
@@ -1335,8 +1354,7 @@ extern "C" int ofk_imu_push(ofk_ctx *c, const double *msgs, const int *counts, i
 extern "C" int ofk_imu_state(ofk_ctx *c, double *state, double *dv, int batch)
 {
     if (!c || !state || batch < 1 || batch > c->max_batch) return ofk_fail(c, OFK_E_INVALID, "ofk_imu_state: bad argument");
-    OFK_HIP(c, hipSetDevice(c->device));
-    TRY(join_slices(c));
+    TRY(enter(c));
     TRY(filters_alloc(c));
     if (dv) OFK_HIP(c, hipMemcpyAsync(dv, c->imu_dv, (size_t)batch * 24, hipMemcpyDeviceToHost, c->stream));
     return get(c, state, c->imu_state, (size_t)batch * OFK_IMU_STATE * 8);
@@ -1348,8 +1366,7 @@ extern "C" int ofk_filter_configure(ofk_ctx *c, int ns, int nm, int nc, const do
     if (!c || ns < 1 || ns > 6 || nm < 1 || nm > 6 || nc < 0 || nc > 6 || !F || !H || !Q || !Rm || !x0 || !P0 || (nc && !Bm) || batch < 1 ||
         batch > c->max_batch)
         return ofk_fail(c, OFK_E_INVALID, "ofk_filter_configure: bad argument");
-    OFK_HIP(c, hipSetDevice(c->device));
-    TRY(join_slices(c));
+    TRY(enter(c));
     TRY(filters_alloc(c));
     double mats[5 * 36] = {0};
     memcpy(mats, F, (size_t)ns * ns * 8); if (nc) memcpy(mats + 36, Bm, (size_t)ns * nc * 8);
@@ -1367,8 +1384,7 @@ extern "C" int ofk_filter_configure(ofk_ctx *c, int ns, int nm, int nc, const do
 extern "C" int ofk_filter_state(ofk_ctx *c, double *x, double *P, int batch)
 {
     if (!c || !x || !P || batch < 1 || batch > c->max_batch || c->kf_ns < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_filter_state: no filter configured / bad argument");
-    OFK_HIP(c, hipSetDevice(c->device));
-    TRY(join_slices(c));
+    TRY(enter(c));
     OFK_HIP(c, hipMemcpyAsync(x, c->kf_x, (size_t)batch * c->kf_ns * 8, hipMemcpyDeviceToHost, c->stream));
     return get(c, P, c->kf_P, (size_t)batch * c->kf_ns * c->kf_ns * 8);
 }
@@ -1378,18 +1394,16 @@ extern "C" int ofk_filter_state(ofk_ctx *c, double *x, double *P, int batch)
 extern "C" int ofk_pairs_filter_step(ofk_ctx *c, double z_sign, int z_source, int batch)
 {
     if (!c || batch < 1 || batch > c->cur_batch || c->kf_ns < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_pairs_filter_step: no filter configured / bad batch");
-    OFK_HIP(c, hipSetDevice(c->device));
+    TRY(use_device(c));
     hipStream_t s;
     TRY(tail_stream(c, &s));
     ofk_launch_kf_records(s, c->kf_ns, c->kf_nm, c->kf_mats, c->kf_x, c->kf_P, c->records, z_sign, z_source, batch);
-    if (c->slices_open) {                                        // the next solves must not overwrite the records the filter still reads
-        OFK_HIP(c, hipEventRecord(c->ev_x, s));
-        c->x_pending = 1;
-    }
+    TRY(tail_done(c, s));
     return check_launch(c, "k_kf_records");
 }
 
-// fu == NULL: the plain step (status filter, node-style solve, no resident filters)
+// fu == NULL: the plain step (status filter, node-style solve, no resident filters); next_bgr == NULL: the new frames are in bgr[1]
+// already (stream_step_jpeg)
 static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *sensors, const ofk_params *p, const ofk_fusion *fu,
                             int min_features, int mask_radius, double *records, double *fused, float *tracks, int *counts)
 {
@@ -1415,16 +1429,12 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     if (fu && fu->redetect_replace && few) {
         // of_module.py:83-86: before tracking, streams with few tracks replace them by fresh corners of the PREVIOUS frame (no mask)
         ofk_launch_redetect_limits(c->stream, c->counts, min_features, p->max_corners, c->limit, B);
-        TRY(stream_detect(c, 0, nullptr, c->limit, B, h, w, p, c->pts_new, c->new_counts));
+        TRY(stream_detect(c, nullptr, c->limit, B, h, w, p, c->pts_new, c->new_counts));
         ofk_launch_replace_tracks(c->stream, c->limit, c->pts_new, c->new_counts, c->max_pts, c->pts_prev, c->counts, B);
     }
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)
-    if (c->lk_seed_mode != OFK_SEED_OFF)                         // the sources k_stream_fuse uses: the IMU state under use_imu, else the sensors
-        ofk_launch_seed_points(c->stream, c->pts_prev, c->counts, c->max_pts, c->sensors, fu && fu->use_imu ? c->imu_state : nullptr,
-                               c->lk_seed_mode, c->lk_seed_gain, c->pts_next, B);
-    ofk_launch_lk(c->stream, c->pyr[0], c->pyr[1], c->pyr_stride, lv, c->pts_prev, c->counts, c->max_pts, p->win, p->max_count, p->eps,
-                  p->min_eig_thr, c->pts_next, c->status, c->err, B, c->lk_seed_mode != OFK_SEED_OFF ? OFK_LK_USE_INITIAL_FLOW : 0);
+    track(c, c->stream, view_of(c, 0, B, 0), lv, p, fu && fu->use_imu ? c->imu_state : nullptr);
     if (fu)
         ofk_launch_stream_fuse(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
                                c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, p->use_feasibility, p->feas_T,
@@ -1448,7 +1458,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         ofk_launch_redetect_limits(c->stream, c->counts, min_features, p->max_corners, c->limit, B);
         OFK_HIP(c, hipMemsetAsync(c->mask, 1, (size_t)B * c->img_stride, c->stream));
         ofk_launch_disc_mask(c->stream, c->mask, c->img_stride, h, w, c->pts_prev, c->counts, c->max_pts, mask_radius, c->limit, B);
-        TRY(stream_detect(c, 0, c->mask, c->limit, B, h, w, p, c->pts_new, c->new_counts));
+        TRY(stream_detect(c, c->mask, c->limit, B, h, w, p, c->pts_new, c->new_counts));
     }
     // tracks := new[status == 1] ++ re-detected (node:134,166); the new frame becomes the previous one (node:175)
     if (!hold)
@@ -1471,23 +1481,30 @@ extern "C" int ofk_stream_step(ofk_ctx *c, const uint8_t *next_bgr, const double
 {
     if (!c || !next_bgr || !sensors || !p) return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step: NULL argument");
     if (c->stream_batch < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step: call ofk_stream_begin first");
-    if (hipSetDevice(c->device) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "hipSetDevice failed");
-    TRY(join_slices(c));
+    TRY(enter(c));
     return stream_step_impl(c, next_bgr, sensors, p, nullptr, min_features, mask_radius, records, nullptr, tracks, counts);
+}
+
+// the JPEG variants: the new frames decoded on the device into bgr[1], which must come out with the streams' geometry, then the step
+static int stream_step_jpeg(ofk_ctx *c, const char *who, const uint8_t *const *jpeg, const size_t *nbytes, const double *sensors,
+                            const ofk_params *p, const ofk_fusion *fu, int min_features, int mask_radius, double *records, double *fused,
+                            float *tracks, int *counts)
+{
+    if (c->stream_batch < 1) return ofk_fail(c, OFK_E_INVALID, "%s: call ofk_stream_begin / ofk_stream_begin_jpeg first", who);
+    TRY(enter(c));
+    int h = 0, w = 0;
+    TRY(ofk_jpeg_decode_device(c, jpeg, nbytes, c->stream_batch, c->bgr[1], c->bgr_stride, c->P, &h, &w, nullptr, nullptr));
+    if (h != c->stream_h || w != c->stream_w)
+        return ofk_fail(c, OFK_E_INVALID, "%s: frames are %dx%d, the streams were begun with %dx%d", who, w, h, c->stream_w, c->stream_h);
+    return stream_step_impl(c, nullptr, sensors, p, fu, min_features, mask_radius, records, fused, tracks, counts);
 }
 
 extern "C" int ofk_stream_step_jpeg(ofk_ctx *c, const uint8_t *const *jpeg, const size_t *nbytes, const double *sensors, const ofk_params *p,
                                     int min_features, int mask_radius, double *records, float *tracks, int *counts)
 {
     if (!c || !jpeg || !nbytes || !sensors || !p) return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_jpeg: NULL argument");
-    if (c->stream_batch < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_jpeg: call ofk_stream_begin / ofk_stream_begin_jpeg first");
-    if (hipSetDevice(c->device) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "hipSetDevice failed");
-    TRY(join_slices(c));
-    int h = 0, w = 0;
-    TRY(ofk_jpeg_decode_device(c, jpeg, nbytes, c->stream_batch, c->bgr[1], c->bgr_stride, c->P, &h, &w, nullptr, nullptr));
-    if (h != c->stream_h || w != c->stream_w)
-        return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_jpeg: frames are %dx%d, the streams were begun with %dx%d", w, h, c->stream_w, c->stream_h);
-    return stream_step_impl(c, nullptr, sensors, p, nullptr, min_features, mask_radius, records, nullptr, tracks, counts);
+    return stream_step_jpeg(c, "ofk_stream_step_jpeg", jpeg, nbytes, sensors, p, nullptr, min_features, mask_radius, records, nullptr, tracks,
+                            counts);
 }
 
 // next positions and keep flags of the LATEST stream step (they stay in place until the next step): what a caller needs to form
@@ -1496,8 +1513,7 @@ extern "C" int ofk_stream_last_points(ofk_ctx *c, float *next_pts, uint8_t *keep
 {
     if (!c || !next_pts || !keep || stride < 1 || stride > c->max_pts) return ofk_fail(c, OFK_E_INVALID, "ofk_stream_last_points: bad argument");
     if (c->stream_batch < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_stream_last_points: no active streams");
-    OFK_HIP(c, hipSetDevice(c->device));
-    TRY(join_slices(c));
+    TRY(enter(c));
     OFK_HIP(c, hipMemcpy2DAsync(next_pts, (size_t)stride * 8, c->pts_next, (size_t)c->max_pts * 8, (size_t)stride * 8, c->stream_batch, hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipMemcpy2DAsync(keep, stride, c->status, c->max_pts, stride, c->stream_batch, hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipStreamSynchronize(c->stream));
@@ -1509,8 +1525,7 @@ extern "C" int ofk_stream_step_fused(ofk_ctx *c, const uint8_t *next_bgr, const 
 {
     if (!c || !next_bgr || !sensors || !p || !f) return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused: NULL argument");
     if (c->stream_batch < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused: call ofk_stream_begin first");
-    if (hipSetDevice(c->device) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "hipSetDevice failed");
-    TRY(join_slices(c));
+    TRY(enter(c));
     return stream_step_impl(c, next_bgr, sensors, p, f, min_features, mask_radius, records, fused, tracks, counts);
 }
 
@@ -1519,14 +1534,8 @@ extern "C" int ofk_stream_step_fused_jpeg(ofk_ctx *c, const uint8_t *const *jpeg
                                           int *counts)
 {
     if (!c || !jpeg || !nbytes || !sensors || !p || !f) return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused_jpeg: NULL argument");
-    if (c->stream_batch < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused_jpeg: call ofk_stream_begin / ofk_stream_begin_jpeg first");
-    if (hipSetDevice(c->device) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "hipSetDevice failed");
-    TRY(join_slices(c));
-    int h = 0, w = 0;
-    TRY(ofk_jpeg_decode_device(c, jpeg, nbytes, c->stream_batch, c->bgr[1], c->bgr_stride, c->P, &h, &w, nullptr, nullptr));
-    if (h != c->stream_h || w != c->stream_w)
-        return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused_jpeg: frames are %dx%d, the streams were begun with %dx%d", w, h, c->stream_w, c->stream_h);
-    return stream_step_impl(c, nullptr, sensors, p, f, min_features, mask_radius, records, fused, tracks, counts);
+    return stream_step_jpeg(c, "ofk_stream_step_fused_jpeg", jpeg, nbytes, sensors, p, f, min_features, mask_radius, records, fused, tracks,
+                            counts);
 }
 
 extern "C" int ofk_set_streams(ofk_ctx *c, int nstreams)
@@ -1563,7 +1572,7 @@ extern "C" int ofk_set_overlap(ofk_ctx *c, int on)
 extern "C" int ofk_mark(ofk_ctx *c, int slot)
 {
     if (!c || slot < 0 || slot >= 8) return ofk_fail(c, OFK_E_INVALID, "ofk_mark: slot 0..7");
-    OFK_HIP(c, hipSetDevice(c->device));
+    TRY(use_device(c));
     if (!c->marks[slot]) OFK_HIP(c, hipEventCreateWithFlags(&c->marks[slot], hipEventDisableTiming));
     hipStream_t s;
     TRY(tail_stream(c, &s));                                     // "everything enqueued so far" includes every slice
