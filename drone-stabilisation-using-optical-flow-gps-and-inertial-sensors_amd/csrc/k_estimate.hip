@@ -1251,3 +1251,6 @@ void ofk_launch_associate(hipStream_t s, const double *t_img, int n_img, int n_i
     hipLaunchKernelGGL(k_associate, dim3(n_img), dim3(256), 0, s, t_img, n_imu, imu_t, imu_q, imu_w, n_hgt, hgt_t, hgt_r, sensors,
                        imu_idx, hgt_idx);
 }
+
+// ------------------------------------------------------------------------------------------------ robust solve
+#include "k_robust.inc"

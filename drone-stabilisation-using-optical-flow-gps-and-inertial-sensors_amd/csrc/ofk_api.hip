@@ -2,6 +2,7 @@
 // points and the resident frame-pair pipeline.  No CPU fallback anywhere: every entry point launches HIP
 // kernels on the context's stream or returns an error.
 #include "ofk_internal.h"
+#include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -146,6 +147,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->overlap = 1;
     c->gray_direct_set = -1;
     c->lk_seed_mode = OFK_SEED_OFF; c->lk_seed_gain = 1.0;
+    c->robust = ofk_robust{OFK_ROBUST_OFF, 4.685, 5, 64, 0ull, 0};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -198,7 +200,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     for (int k = 0; k < 2; ++k) { if (c->bgr[k]) hipFree(c->bgr[k]); if (c->pyr[k]) hipFree(c->pyr[k]); }
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
-                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts};
+                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
@@ -626,6 +628,101 @@ extern "C" int ofk_get_lk_seed(const ofk_ctx *c, int *mode, double *gain)
     return OFK_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ robust solve setting
+static int check_robust(ofk_ctx *c, const ofk_robust *r, const char *who)
+{
+    if (r->loss != OFK_ROBUST_HUBER && r->loss != OFK_ROBUST_TUKEY) return ofk_fail(c, OFK_E_INVALID, "%s: loss %d is neither OFK_ROBUST_HUBER nor _TUKEY", who, r->loss);
+    if (!(std::isfinite(r->c) && r->c > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: c = %g must be finite and positive", who, r->c);
+    if (r->iters < 0 || r->iters > 32) return ofk_fail(c, OFK_E_INVALID, "%s: iters %d outside 0..32", who, r->iters);
+    if (r->hypotheses < 0 || r->hypotheses > 256) return ofk_fail(c, OFK_E_INVALID, "%s: hypotheses %d outside 0..256", who, r->hypotheses);
+    if (r->drop != 0 && r->drop != 1) return ofk_fail(c, OFK_E_INVALID, "%s: drop %d is neither 0 nor 1", who, r->drop);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_robust(ofk_ctx *c, const ofk_robust *r)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!r || r->loss == OFK_ROBUST_OFF) { c->robust.loss = OFK_ROBUST_OFF; return OFK_OK; }
+    TRY(check_robust(c, r, "ofk_set_robust"));
+    c->robust = *r;
+    return OFK_OK;
+}
+
+extern "C" int ofk_get_robust(const ofk_ctx *c, ofk_robust *r)
+{
+    if (!c || !r) return OFK_E_INVALID;
+    *r = c->robust;
+    return OFK_OK;
+}
+
+// the resident buffers of the robust solve, allocated when a run first needs them
+static int robust_alloc(ofk_ctx *c)
+{
+    if (c->rob_work) return OFK_OK;                              // one allocation, carved into the four buffers: all of them or none
+    const size_t B = (size_t)c->max_batch, np = B * c->max_pts;
+    double *base = nullptr;
+    OFK_HIP(c, hipMalloc((void **)&base, (np * 9 + B * OFK_ROBUST_DOUBLES) * 8));
+    c->rob_work = base; c->rob_w = base + np * 7; c->rob_wtmp = base + np * 8; c->rob_stats = base + np * 9;
+    return OFK_OK;
+}
+
+// The solve of nb pairs from pair b0 on (their views' pointers): the plain kernels, or with ofk_set_robust on the robust ones.
+// drop_status: the stream steps' keep flags (cleared for zero-weight points when the setting asks for it), NULL for frame pairs.
+static void solve_pairs(ofk_ctx *c, hipStream_t st, const float *pts_prev, const float *pts_next, uint8_t *status, const int *counts,
+                        const double *sensors, const ofk_params *p, const int *cand_count, double *records, int b0, int nb, bool stream)
+{
+    if (c->robust.loss == OFK_ROBUST_OFF) {
+        ofk_launch_pairs_solve(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
+                               cand_count, records, nb);
+        return;
+    }
+    const size_t o = (size_t)b0 * c->max_pts;
+    ofk_launch_pairs_robust(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
+                            cand_count, &c->robust, b0, c->rob_work + o * 7, c->rob_w + o, c->rob_wtmp + o,
+                            c->rob_stats + (size_t)b0 * OFK_ROBUST_DOUBLES, stream && c->robust.drop ? status : nullptr, records, nb);
+}
+
+extern "C" int ofk_robust_download(ofk_ctx *c, double *weights, int stride, double *stats)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->rob_batch < 1 || !c->rob_work) return ofk_fail(c, OFK_E_INVALID, "ofk_robust_download: no run or step with ofk_set_robust on yet");
+    if (weights && stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_robust_download: stride %d", stride);
+    TRY(enter(c));
+    const int B = c->rob_batch;
+    if (weights) {
+        const size_t wb = (size_t)(stride < c->max_pts ? stride : c->max_pts) * 8;
+        OFK_HIP(c, hipMemcpy2DAsync(weights, (size_t)stride * 8, c->rob_w, (size_t)c->max_pts * 8, wb, B, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (stats) OFK_HIP(c, hipMemcpyAsync(stats, c->rob_stats, (size_t)B * OFK_ROBUST_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+static void philox4x32_10_host(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4])
+{
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// host only: the two kept-point numbers of every hypothesis, as the kernels draw them (k_robust.inc)
+extern "C" int ofk_robust_pairs(unsigned long long seed, unsigned problem, int hypotheses, int m, int *i, int *j)
+{
+    if (hypotheses < 0 || hypotheses > 256 || m < 2 || (hypotheses > 0 && (!i || !j))) return OFK_E_INVALID;
+    for (int h = 0; h < hypotheses; ++h) {
+        unsigned x[4];
+        philox4x32_10_host((unsigned)h, problem, 0u, 0u, (unsigned)seed, (unsigned)(seed >> 32), x);
+        i[h] = (int)(x[0] % (unsigned)m);
+        j[h] = (int)(x[1] % (unsigned)(m - 1));
+        j[h] += j[h] >= i[h] ? 1 : 0;
+    }
+    return OFK_OK;
+}
+
 // the predictor on host buffers; device scratch only, so resident points, sensors and filter states are not touched
 extern "C" int ofk_predict_points(ofk_ctx *c, const float *pts, const int *counts, int batch, int stride, const double *sensors, int mode,
                                   double gain, float *seed_out)
@@ -755,6 +852,30 @@ extern "C" int ofk_velocity_solve(ofk_ctx *c, int variant, const double *x, cons
     if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve: upload failed");
     ofk_launch_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, dw, dout);
     TRY(check_launch(c, "k_solve"));
+    return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
+}
+
+extern "C" int ofk_velocity_solve_robust(ofk_ctx *c, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                                         const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
+                                         const ofk_robust *r, double *out, double *weights, double *stats)
+{
+    if (!c || !x || !u || !nrm || !out || !r || batch < 1 || n < 1 || n > 4096 || variant < 0 || variant > 2)
+        return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_robust: bad argument");
+    if (variant == OFK_SOLVE_OFMODULE ? !wgt : (!d || !omega)) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_robust: missing input for variant %d", variant);
+    TRY(check_robust(c, r, "ofk_velocity_solve_robust"));
+    const size_t pb = (size_t)batch * n * 16, wb = (size_t)batch * n * 8;
+    Bump bp;
+    TRY(est_begin(c, 2 * pb + (size_t)batch * n * 9 + 9 * wb + (size_t)batch * 256 * 8, bp));
+    double *dx = bp.put(x, pb), *du = bp.put(u, pb);
+    uint8_t *dval = (uint8_t *)bp.put(valid, (size_t)batch * n);
+    double *dd = bp.put(d, batch * 8), *dn = bp.put(nrm, batch * 24), *dom = bp.put(omega, batch * 24), *dt = bp.put(t, batch * 24),
+           *dw = bp.put(wgt, wb), *dout = bp.take((size_t)batch * OFK_SOLVE_DOUBLES * 8), *dwork = bp.take(7 * wb), *dwts = bp.take(wb),
+           *dtmp = bp.take(wb), *dst = bp.take((size_t)batch * OFK_ROBUST_DOUBLES * 8);
+    if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_robust: upload failed");
+    ofk_launch_solve_robust(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, dw, r, dwork, dwts, dtmp, dst, dout);
+    TRY(check_launch(c, "k_solve_robust"));
+    if (weights) TRY(get(c, weights, dwts, wb));
+    if (stats) TRY(get(c, stats, dst, (size_t)batch * OFK_ROBUST_DOUBLES * 8));
     return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
 }
 
@@ -1114,6 +1235,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
     // entry point needs the context's stream to see their results (join_slices).  On the fork the response kernels are chained
     // slice after slice, which offsets the slices by one response kernel for as long as they run.
     const bool fork = S > 1 && !c->slices_open;
+    if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
     TRY(need_streams(c, S, overlap));
     if (fork) {
         OFK_HIP(c, hipEventRecord(c->ev_fork, c->stream));
@@ -1162,8 +1284,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
         if (c->x_pending) OFK_HIP(c, hipStreamWaitEvent(st, c->ev_x, 0));    // the previous call's records are still being exported
         {
             StageTimer t(c, OFK_STAGE_SOLVE, st);
-            ofk_launch_pairs_solve(st, v.pts_prev, v.pts_next, v.status, v.counts, c->max_pts, v.sensors, p->solve_variant, p->use_feasibility,
-                                   p->feas_T, v.cand_count, v.records, nb);
+            solve_pairs(c, st, v.pts_prev, v.pts_next, v.status, v.counts, v.sensors, p, v.cand_count, v.records, b0, nb, false);
         }
         if (S > 1) OFK_HIP(c, hipEventRecord(c->ev_end[k], st));             // joined lazily (join_slices), not here
     }
@@ -1423,6 +1544,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         TRY(filters_alloc(c));
     } else if (p->solve_variant != OFK_SOLVE_NODE && p->solve_variant != OFK_SOLVE_SIM) return ofk_fail(c, OFK_E_INVALID, "solve_variant must be NODE or SIM");
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
+    if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
     OFK_HIP(c, hipMemcpyAsync(c->sensors, sensors, (size_t)B * OFK_SENSOR_DOUBLES * 8, hipMemcpyHostToDevice, c->stream));
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
@@ -1435,13 +1557,16 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)
     track(c, c->stream, view_of(c, 0, B, 0), lv, p, fu && fu->use_imu ? c->imu_state : nullptr);
-    if (fu)
+    if (fu && c->robust.loss != OFK_ROBUST_OFF)
+        ofk_launch_stream_fuse_robust(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
+                                      c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, p->use_feasibility, p->feas_T,
+                                      c->records, c->fused, &c->robust, c->rob_work, c->rob_w, c->rob_wtmp, c->rob_stats, B);
+    else if (fu)
         ofk_launch_stream_fuse(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
                                c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, p->use_feasibility, p->feas_T,
                                c->records, c->fused, B);
     else
-        ofk_launch_pairs_solve(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, p->solve_variant,
-                               p->use_feasibility, p->feas_T, nullptr, c->records, B);
+        solve_pairs(c, c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->sensors, p, nullptr, c->records, 0, B, true);
     // re-detection for the streams that had few features (node:157-166): mask = discs around the OLD positions, image = OLD frame.
     // The host knows the track counts from the previous call, so the whole branch is skipped when no stream needs it.
     // of_module.py:138 `continue`: a step of the ONE stream that did not solve leaves old_gray / old_pos as they were.  The host has to

@@ -84,6 +84,9 @@ struct ofk_ctx {
     int cur_batch, cur_h, cur_w;    // resident pair geometry (ofk_pairs_upload)
     int prof_mask;
     int lk_seed_mode; double lk_seed_gain;   // ofk_set_lk_seed: OFK_SEED_OFF unless set
+    ofk_robust robust;                       // ofk_set_robust: loss OFK_ROBUST_OFF unless set
+    double *rob_work, *rob_w, *rob_wtmp, *rob_stats;   // [B][7][max_pts] per-point terms, [B][max_pts] weights (+ a scratch copy), [B][OFK_ROBUST_DOUBLES]; one lazy allocation (rob_work owns it)
+    int rob_batch;                           // problems of the latest robust run / step (ofk_robust_download), 0 = none
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -158,6 +161,18 @@ void ofk_launch_seed_points(hipStream_t s, const float *pts, const int *counts, 
 void ofk_launch_pairs_solve(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status,
                             const int *counts, int pts_stride, const double *sensors, int variant, int use_feas,
                             double feas_T, const int *cand_count, double *records, int batch);
+// the robust forms (k_robust.inc); work / weights / wtmp / stats: the slice's rows of the context's rob_* buffers
+void ofk_launch_pairs_robust(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts,
+                             int pts_stride, const double *sensors, int variant, int use_feas, double feas_T, const int *cand_count,
+                             const ofk_robust *r, int problem0, double *work, double *weights, double *wtmp, double *stats,
+                             uint8_t *drop_status, double *records, int batch);
+void ofk_launch_solve_robust(hipStream_t s, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                             const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
+                             const ofk_robust *r, double *work, double *weights, double *wtmp, double *stats, double *out);
+void ofk_launch_stream_fuse_robust(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
+                                   const double *sensors, double *imu_state, double *imu_dv, int ns, int nm, int nc, const double *kf_mats,
+                                   double *kf_x, double *kf_P, const ofk_fusion *f, int variant, int use_feas, double feas_T, double *records,
+                                   double *fused, const ofk_robust *r, double *work, double *weights, double *wtmp, double *stats, int batch);
 void ofk_launch_records_f32(hipStream_t s, const double *records, float *dst, int batch);
 
 void ofk_launch_flow_model(hipStream_t s, const double *x, int batch, int n, const double *v, const double *omega,

@@ -26,6 +26,7 @@ SYMBOLS = (
     "ofk_version", "ofk_last_error", "ofk_device_count", "ofk_create", "ofk_destroy", "ofk_sync", "ofk_device_sync",
     "ofk_gray_bgr8", "ofk_pyr_down_u8", "ofk_pyramid_u8", "ofk_scharr_s16", "ofk_mineig_response", "ofk_select_corners",
     "ofk_good_features", "ofk_lk_pyr", "ofk_lk_pyr_ex", "ofk_predict_points", "ofk_set_lk_seed", "ofk_get_lk_seed", "ofk_flow_model", "ofk_feasibility", "ofk_velocity_solve", "ofk_imu_propagate",
+    "ofk_set_robust", "ofk_get_robust", "ofk_robust_download", "ofk_velocity_solve_robust", "ofk_robust_pairs",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
     "ofk_stream_begin_jpeg", "ofk_stream_step_jpeg",
@@ -52,9 +53,41 @@ class Params(C.Structure):
 LK_USE_INITIAL_FLOW, LK_GET_MIN_EIGENVALS = 4, 8         # cv2's OPTFLOW_* values (ofk_lk_pyr_ex)
 SEED_OFF, SEED_MODEL, SEED_ROTATION = 0, 1, 2           # ofk_set_lk_seed / ofk_predict_points
 SEED_MODES = {"off": SEED_OFF, "model": SEED_MODEL, "rotation": SEED_ROTATION}
+ROBUST_OFF, ROBUST_HUBER, ROBUST_TUKEY = 0, 1, 2         # ofk_set_robust / ofk_velocity_solve_robust
+ROBUST_LOSSES = {"off": ROBUST_OFF, "huber": ROBUST_HUBER, "tukey": ROBUST_TUKEY}
+ROBUST_DEFAULT_C = {ROBUST_HUBER: 1.345, ROBUST_TUKEY: 4.685}     # 95 % efficiency on Gaussian residuals
+ROBUST_MIN_POINTS, ROBUST_DOUBLES = 8, 8
 FLOW_LK, FLOW_ROTATIONAL = 0, 1
 KEEP_STATUS, KEEP_LEGACY = 0, 1
 CONTROL_SENSORS, CONTROL_IMU = 0, 1
+
+
+class Robust(C.Structure):
+    """ofk_robust (include/ofk.h): the robust velocity solve's setting."""
+    _fields_ = [("loss", C.c_int), ("c", C.c_double), ("iters", C.c_int), ("hypotheses", C.c_int), ("seed", C.c_ulonglong),
+                ("drop", C.c_int)]
+
+
+def robust_setting(loss="tukey", c=None, iters=5, hypotheses=64, seed=0, drop=False):
+    """A Robust structure from names: loss "off" / "huber" / "tukey" (or ROBUST_*); c None = the loss's usual tuning constant."""
+    if isinstance(loss, str):
+        if loss not in ROBUST_LOSSES:
+            raise ValueError(f"robust loss {loss!r} is none of {sorted(ROBUST_LOSSES)}")
+        loss = ROBUST_LOSSES[loss]
+    loss = int(loss)
+    if c is None:
+        c = ROBUST_DEFAULT_C.get(loss, ROBUST_DEFAULT_C[ROBUST_TUKEY])
+    return Robust(loss, float(c), int(iters), int(hypotheses), int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(drop)))
+
+
+def robust_pairs(seed, problem, hypotheses, m):
+    """ofk_robust_pairs (host only): the kept-point numbers (i, j) of the hypotheses 0..hypotheses-1 of problem `problem`."""
+    n = int(hypotheses)
+    i = np.zeros(max(n, 1), np.int32); j = np.zeros(max(n, 1), np.int32)
+    rc = load_library().ofk_robust_pairs(C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint(int(problem)), n, int(m), _p(i), _p(j))
+    if rc != 0:
+        raise OfkError(rc, f"ofk_robust_pairs: hypotheses {n} outside 0..256 or m {m} < 2")
+    return i[:max(n, 0)], j[:max(n, 0)]
 
 
 class Fusion(C.Structure):
@@ -126,6 +159,10 @@ def load_library():
         L.ofk_flow_model.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp, vp]
         L.ofk_feasibility.argtypes = [vp, i, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp]
         L.ofk_velocity_solve.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp]
+        L.ofk_set_robust.argtypes = [vp, C.POINTER(Robust)]; L.ofk_get_robust.argtypes = [vp, C.POINTER(Robust)]
+        L.ofk_robust_download.argtypes = [vp, vp, i, vp]
+        L.ofk_velocity_solve_robust.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), vp, vp, vp]
+        L.ofk_robust_pairs.argtypes = [C.c_ulonglong, C.c_uint, i, i, vp, vp]
         L.ofk_imu_propagate.argtypes = [vp, vp, vp, i]
         L.ofk_post_solve.argtypes = [vp, vp, vp, vp, vp, i, vp]
         L.ofk_associate_sensors.argtypes = [vp, vp, i, vp, vp, vp, i, vp, vp, i, vp, vp, vp]
@@ -456,6 +493,48 @@ class Context:
                 self._ck(self._L.ofk_velocity_solve(self._h, int(variant), _p(x), _p(u), _p(valid), B, n, _p(d), _p(nrm),
                                                     _p(omega), _p(t), _p(wgt), _p(out)))
         return out[0] if single else out
+
+    def velocity_solve_robust(self, variant, x, u, d=None, nrm=None, omega=None, t=None, wgt=None, valid=None, robust=None, **settings):
+        """ofk_velocity_solve_robust: velocity_solve's arguments plus the setting (a Robust, or robust_setting's keywords).
+        Returns out [B,8], weights [B,n], stats [B,8] (single problem: [8], [n], [8])."""
+        r = robust if robust is not None else robust_setting(**settings)
+        x = _arr(x, np.float64); u = _arr(u, np.float64)
+        if u.shape[:-1] != x.shape[:-1] or x.shape[-1] != 2 or u.shape[-1] < 2:
+            raise ValueError(f"velocity_solve_robust: x {x.shape} must be [..., n, 2] and u {u.shape} [..., n, >=2] over the same points")
+        single = x.ndim == 2
+        if single:
+            x = x[None]; u = u[None]
+        B, n, _ = x.shape
+        u = _arr(u[..., :2], np.float64)
+        nrm = _arr(nrm, np.float64, (B, 3))
+        d = _opt(d, np.float64, (B,)); omega = _opt(omega, np.float64, (B, 3)); t = _opt(t, np.float64, (B, 3))
+        wgt = _opt(wgt, np.float64, (B, n)); valid = _opt(valid, np.uint8, (B, n))
+        out = np.zeros((B, SOLVE_DOUBLES), np.float64); w = np.zeros((B, n), np.float64); st = np.zeros((B, ROBUST_DOUBLES), np.float64)
+        if not n:                                               # no points: velocity_solve's zeros, flag 1
+            st[:, 4] = -1.0; st[:, 7] = 1.0
+            return (out[0], w[0], st[0]) if single else (out, w, st)
+        with self._lock:
+            self._ck(self._L.ofk_velocity_solve_robust(self._h, int(variant), _p(x), _p(u), _p(valid), B, n, _p(d), _p(nrm), _p(omega),
+                                                       _p(t), _p(wgt), C.byref(r), _p(out), _p(w), _p(st)))
+        return (out[0], w[0], st[0]) if single else (out, w, st)
+
+    def set_robust(self, robust=None, **settings):
+        """ofk_set_robust: a Robust (or robust_setting's keywords); None or loss "off" switches it off.  Every later pairs_run and
+        stream step solves robustly."""
+        r = robust if robust is not None or not settings else robust_setting(**settings)
+        self._ck(self._L.ofk_set_robust(self._h, C.byref(r) if r is not None else None))
+
+    def get_robust(self):
+        r = Robust()
+        self._ck(self._L.ofk_get_robust(self._h, C.byref(r)))
+        return r
+
+    def robust_download(self, batch):
+        """(weights [batch, max_pts], stats [batch, 8]) of the latest run / step with the setting on."""
+        w = np.zeros((self.max_batch, self.max_pts), np.float64); st = np.zeros((self.max_batch, ROBUST_DOUBLES), np.float64)
+        with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
+            self._ck(self._L.ofk_robust_download(self._h, _p(w), self.max_pts, _p(st)))
+        return w[:batch].copy(), st[:batch].copy()
 
     def imu_propagate(self, state, msg):
         state = _arr(state, np.float64).copy(); msg = _arr(msg, np.float64)

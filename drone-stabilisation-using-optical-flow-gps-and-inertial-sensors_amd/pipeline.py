@@ -33,6 +33,14 @@ class PipelineConfig:
     # "rotation" (omega alone); seed_gain scales the predicted flow (omega per second against flow per frame)
     lk_seed: str = "off"
     seed_gain: float = 1.0
+    # robust velocity solve (ofk.h: ofk_set_robust): "off", "huber" or "tukey"; robust_c None = 1.345 / 4.685; a sampled start of
+    # robust_hypotheses two-point solves, robust_iters reweighting rounds; robust_drop: stream steps drop zero-weight points
+    robust: str = "off"
+    robust_c: float = None
+    robust_iters: int = 5
+    robust_hypotheses: int = 64
+    robust_seed: int = 0
+    robust_drop: bool = False
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -51,6 +59,12 @@ class PipelineConfig:
     @classmethod
     def baseline_1080p(cls):     # BASELINE.json configs[1]: 500 corners, 3-level pyramid
         return cls(max_corners=500, quality=0.01, min_distance=10, block_size=7, win=15, max_level=3, max_count=20, eps=0.03)
+
+    def robust_setting(self):
+        """The ofk.Robust structure of this configuration, None when the robust solve is off."""
+        if self.robust == "off":
+            return None
+        return ofk.robust_setting(self.robust, self.robust_c, self.robust_iters, self.robust_hypotheses, self.robust_seed, self.robust_drop)
 
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
@@ -175,6 +189,8 @@ class FlowStream:
         self._params = self.cfg.to_params()
         if self.cfg.lk_seed != "off":
             self.ctx.set_lk_seed(self.cfg.lk_seed, self.cfg.seed_gain)
+        if self.cfg.robust != "off":
+            self.ctx.set_robust(self.cfg.robust_setting())
         self.fusion = fusion
         if fusion is not None:                                  # the per-stream filter state lives on the device from here on
             self._fusion = fusion.to_struct()
@@ -229,6 +245,8 @@ class FlowPipeline:
         self._params = self.cfg.to_params()
         if self.cfg.lk_seed != "off":
             self.ctx.set_lk_seed(self.cfg.lk_seed, self.cfg.seed_gain)
+        if self.cfg.robust != "off":
+            self.ctx.set_robust(self.cfg.robust_setting())
         if streams > 1:
             self.ctx.set_streams(streams)
 

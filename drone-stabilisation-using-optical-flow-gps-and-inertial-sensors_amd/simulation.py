@@ -39,6 +39,16 @@ def solve_lgs(x, u, d, n, omega, t):
         return np.zeros(3), 10000 * np.ones(3 * len(x)), np.array([0, 0, 0])
 
 
+def solve_lgs_robust(x, u, d, n, omega, t, **settings):
+    """solve_lgs with the robust estimator of ofk.h (ofk_velocity_solve_robust; settings: ofk.robust_setting's keywords).
+    Returns (v - omega x t, R, s, weights [N], stats [8]) with R the weighted residual sum."""
+    x = np.asarray(x, np.float64)
+    out, w, st = ofk.default_context().velocity_solve_robust(ofk.SOLVE_SIM, x[:, :2], np.asarray(u, np.float64)[:, :2], d=float(np.ravel(d)[0]),
+                                                             nrm=n, omega=omega, t=t, **settings)
+    R = np.array([out[3]]) if (int(out[4]) == 3 and 3 * len(x) > 3) else np.empty(0)
+    return out[:3].copy(), R, out[5:8].copy(), w, st
+
+
 def feasibility(position, linear_velocity, flow, angular_velocity, translation, normal):
     r, length = ofk.default_context().feasibility(ofk.FEAS_SIM, np.asarray(position, np.float64)[:, :2],
                                                   np.asarray(flow, np.float64)[:, :2], normal, linear_velocity,

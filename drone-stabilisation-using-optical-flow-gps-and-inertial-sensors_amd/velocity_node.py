@@ -61,6 +61,17 @@ def solve_lgs(x, u, d, n, omega):
     return out[:3].copy(), R, rank, out[5:8].copy()
 
 
+def solve_lgs_robust(x, u, d, n, omega, **settings):
+    """solve_lgs with the robust estimator of ofk.h (ofk_velocity_solve_robust): a sampled least-median-of-squares start, then
+    reweighting rounds.  settings: ofk.robust_setting's keywords (loss="tukey", c, iters, hypotheses, seed).
+    Returns (v, R, rank, s, weights [N], stats [8]): R = the weighted residual sum (shape (1,) when rank == 3 and 3N > 3)."""
+    x = np.asarray(x, np.float64); u = np.asarray(u, np.float64)
+    out, w, st = ofk.default_context().velocity_solve_robust(ofk.SOLVE_NODE, x[:, :2], u[:, :2], d=float(d), nrm=n, omega=omega, **settings)
+    rank = int(out[4])
+    R = np.array([out[3]]) if (rank == 3 and 3 * len(x) > 3) else np.empty(0)
+    return out[:3].copy(), R, rank, out[5:8].copy(), w, st
+
+
 def feasible(x, v, omega, T, u, d, n):
     """node:44-50 (reference not executable: uses v_cr/u_cr before definition, returns nothing).  The evident
     intent — parallelity and distance of each point given the lever-arm corrected velocity — is returned."""
@@ -79,6 +90,7 @@ class optical_fusion:
     # parameters the reference sets inline (node:96-107, :182, :241)
     min_feat = 20
     max_feat = 100
+    _robust = {}                                                 # PipelineConfig's robust_* settings (see __init__); empty: the plain solve
     feature_params = dict(qualityLevel=0.7, minDistance=10, blockSize=12)
     lk_params = dict(winSize=(15, 15), maxLevel=3, criteria=(cv2.TERM_CRITERIA_EPS | cv2.TERM_CRITERIA_COUNT, 20, 0.03))
     scaling = 0.01
@@ -232,7 +244,7 @@ class optical_fusion:
             cfg = PipelineConfig(max_corners=int(self.max_feat), quality=float(self.feature_params["qualityLevel"]),
                                  min_distance=float(self.feature_params["minDistance"]), block_size=int(self.feature_params["blockSize"]),
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
-                                 use_feasibility=True, feas_T=float(self.T))
+                                 use_feasibility=True, feas_T=float(self.T), **self._robust)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -307,8 +319,12 @@ class optical_fusion:
             self.got_picture_ = False
             return v_obs
 
-    def __init__(self, spin=True, synthetic_test=True):
+    def __init__(self, spin=True, synthetic_test=True, robust=None):
+        """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
+        dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust)."""
         self._lock = threading.RLock()
+        r = dict(robust or {})
+        self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

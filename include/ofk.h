@@ -158,6 +158,49 @@ int ofk_velocity_solve(ofk_ctx *ctx, int variant, const double *x, const double 
                        const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
                        double *out);
 
+/* The robust velocity solve: a sampled least-median-of-squares start, then iteratively reweighted least squares.  Off by default;
+ * with it off every entry point launches the kernels and returns the bits it always did.
+ * For one problem let the kept points be those that enter the plain solve (status / valid / feasibility / legacy keep), m of them,
+ * numbered 0..m-1 in point-index order, with the plain solve's per-point terms q, sA, sB.  r_i(v) = sA [p]x v - sB [p]x q,
+ * rho_i = |r_i|.  A weighted solve multiplies point i's contributions to the 3x3 normal equations by w_i, counts the points with
+ * w_i > 0 as its rows and is otherwise the plain solve (rank rule included).  sel(a) = the element of index m / 2 of a sorted
+ * ascending: an exact selection, never an interpolation.
+ *   1. m < OFK_ROBUST_MIN_POINTS (or the plain solve's own point guard fails): the plain result, all kept weights 1, flag 1.
+ *   2. Start: v = the plain solve, hyp = -1.  For h = 0..hypotheses-1: (x0, x1, ., .) = Philox4x32-10(counter (h, b, 0, 0),
+ *      key (seed & 0xffffffff, seed >> 32)), b = the problem's index in the call's whole batch; i = x0 mod m, j = x1 mod (m - 1),
+ *      j += (j >= i); v_h = the weighted solve with weight 1 on kept points i and j only (rank < 3: void);
+ *      score_h = sel(rho^2(v_h)) over all kept points.  The start is the non-void hypothesis of smallest score (ties: smaller h).
+ *   3. Exactly `iters` times: s = 1.4826 sel(rho(v)); if !(s^2 > 1e-24 bb / m), bb = sum sB^2 |[p]x q|^2: the data fit exactly,
+ *      flag 2, stop with v and the previous weights.  t_i = rho_i / (c s); HUBER w_i = t_i <= 1 ? 1 : 1 / t_i;
+ *      TUKEY w_i = t_i < 1 ? (1 - t_i^2)^2 : 0.  v' = the weighted solve; rank < 3: flag 3, keep v and the previous weights, stop.
+ *   4. Record / out fields: 0-2 v; 3 sum w_i rho_i^2(v); 4 rank and 5-7 singular values of the system of the final weights;
+ *      8-10 v_uav from the robust v; 11 points with w_i > 0; 12-15 as always.  weights: w_i per point, 0 for points not kept.
+ *      stats, OFK_ROBUST_DOUBLES per problem: s of the last round, sum w, count w > 0, m, hyp, score (0 without a hypothesis),
+ *      rounds completed, flag.
+ * ofk_set_robust (NULL or loss OFK_ROBUST_OFF: off, the default) is a context setting read by ofk_pairs_run (every slice),
+ * ofk_stream_step[_jpeg] and ofk_stream_step_fused[_jpeg]; in the fused step the filter's correct takes the robust v / v_uav.  With
+ * drop = 1 the stream steps clear the keep flag of every point whose final weight is 0 before the tracks are updated, so such points
+ * leave the tracks as infeasible ones do.  Invalid settings (unknown loss, c not finite or <= 0, iters outside 0..32, hypotheses
+ * outside 0..256, drop not 0/1) return OFK_E_INVALID and leave the previous setting in place.  Records are bit-identical across
+ * launch forms (one wave per pair from 128 pairs per slice on, a 256-thread workgroup below), slice counts and overlap settings.
+ * ofk_robust_download: weights [batch][stride] (the first min(stride, max_pts) of every row are written) and stats
+ * [batch][OFK_ROBUST_DOUBLES] of the latest run / step with the setting on; either may be NULL; OFK_E_INVALID before such a run.
+ * ofk_velocity_solve_robust = ofk_velocity_solve's arguments (n <= 4096) plus the setting; weights [batch][n], stats nullable.
+ * ofk_robust_pairs (host only; no context, no GPU): the sample of step 2 for h = 0..hypotheses-1; m >= 2. */
+#define OFK_ROBUST_OFF 0
+#define OFK_ROBUST_HUBER 1
+#define OFK_ROBUST_TUKEY 2
+#define OFK_ROBUST_MIN_POINTS 8
+#define OFK_ROBUST_DOUBLES 8
+typedef struct ofk_robust { int loss; double c; int iters; int hypotheses; unsigned long long seed; int drop; } ofk_robust;
+int ofk_set_robust(ofk_ctx *ctx, const ofk_robust *r);
+int ofk_get_robust(const ofk_ctx *ctx, ofk_robust *r);
+int ofk_robust_download(ofk_ctx *ctx, double *weights, int stride, double *stats);
+int ofk_velocity_solve_robust(ofk_ctx *ctx, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                              const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
+                              const ofk_robust *r, double *out, double *weights, double *stats);
+int ofk_robust_pairs(unsigned long long seed, unsigned problem, int hypotheses, int m, int *i, int *j);
+
 /* optical_fusion.call_imu — node:61-89, batched over independent IMU streams, one message each.
  * state [batch][OFK_IMU_STATE]: vel[3], old_time, time_zero, first(0/1), rotation[9], normal[3], ang[3], ang_err[3]
  * msg   [batch][OFK_IMU_MSG]  : secs, nsecs, qx,qy,qz,qw, wx,wy,wz, cov0,cov4,cov8, ax,ay,az */
