@@ -12,20 +12,9 @@ that owns the stream").
 import numpy as np
 import pytest
 
-from stream_oracle import oracle_of_module, oracle_node_fused
+from stream_oracle import oracle_of_module, oracle_node_fused, imu_messages
 
 pytestmark = pytest.mark.gpu
-
-
-def make_imu_msgs(rng, t0, n, tilt=0.02):
-    """n messages 20 ms apart from time t0 (seconds): a slightly tilted, slowly rotating vehicle."""
-    out = np.zeros((n, 15))
-    for k in range(n):
-        t = t0 + 0.02 * (k + 1)
-        ax = rng.normal(0, tilt, 3)
-        q = np.array([ax[0] / 2, ax[1] / 2, ax[2] / 2, 1.0]); q /= np.linalg.norm(q)
-        out[k] = [int(t), int((t - int(t)) * 1e9), *q, *rng.normal(0, 0.002, 3), 1e-4, 2e-4, 3e-4, *(rng.normal(0, 0.05, 3) + [0, 0, 9.81])]
-    return out
 
 
 @pytest.mark.parametrize("synthetic", [True, False])
@@ -86,7 +75,7 @@ def test_node_loop_with_resident_imu_and_filter(pkg, ofk, use_ekf):
     frames = np.stack([s[0] for s in seqs]); info = seqs[0][1]
     statics = dict(d=1.0, offset=(0.0, 0.0, 0.1), scaling=info["scaling"], cx=info["cx"], cy=info["cy"])
     rng = np.random.default_rng(5)
-    msgs = np.stack([[make_imu_msgs(rng, 100.0 + 0.1 * t + 7 * b, 3) for b in range(B)] for t in range(nf - 1)])     # [nf-1, B, 3, 15]
+    msgs = np.stack([[imu_messages(rng, 100.0 + 0.1 * t + 7 * b, 3) for b in range(B)] for t in range(nf - 1)])     # [nf-1, B, 3, 15]
     fusion = FusionConfig.ekf6(dt=0.1) if use_ekf else FusionConfig.node()
     fs = FlowStream(w, h, batch=B, cfg=cfg, min_features=115, mask_radius=15, fusion=fusion)
     tracks, counts = fs.begin(frames[:, 0])
@@ -109,7 +98,7 @@ def test_node_loop_with_resident_imu_and_filter(pkg, ofk, use_ekf):
     assert np.all(dv == 0)                                       # a step starts a new dead-reckoning interval
     # ragged message counts: a stream with fewer messages only applies those
     before, _ = fs.ctx.imu_state(B)
-    extra = np.stack([make_imu_msgs(rng, 300.0 + b, 4) for b in range(B)])
+    extra = np.stack([imu_messages(rng, 300.0 + b, 4) for b in range(B)])
     fs.push_imu(extra, np.array([4, 1], np.int32))
     after, _ = fs.ctx.imu_state(B)
     assert after[0, 3] != before[0, 3] and abs(after[1, 3] - (300.0 + 1 + 0.02 - after[1, 4])) < 1e-6
@@ -205,7 +194,7 @@ def test_ekf6_with_gps_measurement_block(pkg, ofk, gpu_ctx):
     cfg = PipelineConfig(max_corners=80, quality=0.02, min_distance=8, block_size=7, max_level=2)
     frames, info = synth.render_sequence(h, w, 951, nf, v=(0.004, -0.003, 0.002), omega=(0.002, 0.001, -0.003), d=1.0)
     statics = dict(d=1.0, offset=(0.0, 0.0, 0.1), scaling=info["scaling"], cx=info["cx"], cy=info["cy"])
-    msgs = np.stack([make_imu_msgs(rng, 50.0 + 0.1 * t, 3) for t in range(nf - 1)])          # [nf-1, 3, 15]
+    msgs = np.stack([imu_messages(rng, 50.0 + 0.1 * t, 3) for t in range(nf - 1)])          # [nf-1, 3, 15]
     gps = rng.normal(0.0, 0.01, (nf - 1, 3)) + [0.004, -0.003, 0.002]
     fusion = FusionConfig.ekf6(dt=0.1, gps=True, r=4.0, r_gps=0.5)
     fs = FlowStream(w, h, batch=1, cfg=cfg, min_features=70, mask_radius=12, fusion=fusion)

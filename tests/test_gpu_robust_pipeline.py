@@ -17,6 +17,7 @@ from batch_oracle import assert_records_identical
 from oracle import estimation_oracle as eo
 import robust_reference as rr
 import robust_stream_oracle as rso
+from stream_oracle import NodeLoop, imu_messages
 
 pytestmark = pytest.mark.gpu
 
@@ -248,17 +249,6 @@ def test_moving_object_experiment_on_the_device(pkg, ofk, size):
         rr.check_experiment(size, ep, er, (size, rr.SCENE_SEEDS[b]))
 
 
-def make_imu_msgs(rng, t0, n):
-    out = np.zeros((n, 15))
-    for k in range(n):
-        t = t0 + 0.02 * (k + 1)
-        ax = rng.normal(0, 0.02, 3)
-        q = np.array([ax[0] / 2, ax[1] / 2, ax[2] / 2, 1.0]); q /= np.linalg.norm(q)
-        out[k] = [int(t), int((t - int(t)) * 1e9), *q, *(np.asarray(MOTION["omega"]) + rng.normal(0, 0.0005, 3)), 1e-4, 2e-4, 3e-4,
-                  *(rng.normal(0, 0.05, 3) + [0, 0, 9.81])]
-    return out
-
-
 @pytest.mark.parametrize("drop", [False, True], ids=["keep", "drop"])
 @pytest.mark.parametrize("kind", ["step", "fused", "ekf6"])
 def test_stream_steps_robust(pkg, ofk, kind, drop):
@@ -278,14 +268,15 @@ def test_stream_steps_robust(pkg, ofk, kind, drop):
     share = []
     try:
         tracks, counts = fs.begin(frames[:, 0])
-        loops = [rso.RobustLoop(frames[b, 0], cfg, min_feat, radius, kind, b, drop, model=fusion.model if kind == "ekf6" else None) for b in range(B)]
+        loops = [NodeLoop(frames[b, 0], cfg, min_feat, radius, solve=rso.robust_solver(b, drop, kind != "step"),
+                          **(dict(imu_offset=(0.0, 0.0, 0.1), model=fusion.model) if kind == "ekf6" else {})) for b in range(B)]
         for b in range(B):
             assert counts[b] == len(loops[b].tracks) and np.array_equal(tracks[b, :counts[b]], loops[b].tracks)
         dropped = 0
         for t in range(1, nf):
             msgs = None
             if kind == "ekf6":
-                msgs = np.stack([make_imu_msgs(rng, 50.0 + 0.1 * t + 3 * b, 3) for b in range(B)])
+                msgs = np.stack([imu_messages(rng, 50.0 + 0.1 * t + 3 * b, 3, rate=MOTION["omega"], rate_sigma=0.0005) for b in range(B)])
                 fs.push_imu(msgs)
             if kind == "step":
                 rec, tracks, counts = fs.step(frames[:, t], sensors)
@@ -293,7 +284,7 @@ def test_stream_steps_robust(pkg, ofk, kind, drop):
                 rec, fused, tracks, counts = fs.step_fused(frames[:, t], sensors)
             wts, st = fs.ctx.robust_download(B)
             for b in range(B):
-                o = loops[b].step(frames[b, t], sensors[b], None if msgs is None else msgs[b])
+                o = loops[b].step(frames[b, t], sensors[b], () if msgs is None else msgs[b])
                 tag = (kind, drop, t, b)
                 assert o["gap"] >= 1e-6 and o["near"] == 0, tag
                 assert rec[b, 12] == o["n_old"] and rec[b, 13] == o["n_tracked"] and rec[b, 11] == o["used"] and counts[b] == len(o["tracks"]), \
@@ -353,7 +344,7 @@ def test_without_hypotheses_and_rounds_the_robust_kernels_are_the_plain_ones(pkg
                 steps = []
                 for t in range(1, nf):
                     if name != "sensors":
-                        fs.push_imu(np.stack([make_imu_msgs(rng, 50.0 + 0.1 * t + 3 * b, 3) for b in range(B)]))
+                        fs.push_imu(np.stack([imu_messages(rng, 50.0 + 0.1 * t + 3 * b, 3, rate=MOTION["omega"], rate_sigma=0.0005) for b in range(B)]))
                     steps.append(fs.step_fused(frames[:, t], sensors))
                 runs.append((steps, fs.ctx.filter_state(B) if name == "ekf6" else None, fs.ctx.imu_state(B)))
             finally:

@@ -12,7 +12,7 @@ import pytest
 
 from oracle import image_oracle as io, estimation_oracle as eo
 import lk_seed_reference as R  # noqa: E402  (tests/lk_seed_reference.py)
-import seed_stream_oracle as sso  # noqa: E402  (tests/seed_stream_oracle.py)
+from stream_oracle import NodeLoop, imu_messages  # noqa: E402  (tests/stream_oracle.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -166,16 +166,6 @@ def test_fast_manoeuvre_rows_on_the_device(pkg, ofk, exp_pipe, row):
 YAW = dict(v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.08), d=1.0)
 
 
-def imu_msgs(rng, t0, n, ang):
-    out = np.zeros((n, 15))
-    for k in range(n):
-        t = t0 + 0.02 * (k + 1)
-        ax = rng.normal(0, 0.02, 3)
-        q = np.array([ax[0] / 2, ax[1] / 2, ax[2] / 2, 1.0]); q /= np.linalg.norm(q)
-        out[k] = [int(t), int((t - int(t)) * 1e9), *q, *(np.asarray(ang) + rng.normal(0, 0.001, 3)), 1e-4, 2e-4, 3e-4, *(rng.normal(0, 0.05, 3) + [0, 0, 9.81])]
-    return out
-
-
 @pytest.mark.parametrize("kind", ["step", "fused-sensors", "fused-imu"])
 @pytest.mark.parametrize("mode", ["model", "rotation"])
 def test_stream_steps_seeded(pkg, ofk, gpu_ctx, kind, mode):
@@ -195,14 +185,14 @@ def test_stream_steps_seeded(pkg, ofk, gpu_ctx, kind, mode):
     smode = ofk.SEED_MODES[mode]
     try:
         tracks, counts = fs.begin(frames[:, 0])
-        loops = [sso.StreamLoop(frames[b, 0], cfg, min_feat, radius) for b in range(B)]
+        loops = [NodeLoop(frames[b, 0], cfg, min_feat, radius) for b in range(B)]
         for b in range(B):
             assert counts[b] == len(loops[b].tracks) and np.array_equal(tracks[b, :counts[b]], loops[b].tracks)
         moved = redetected = 0
         for t in range(1, nf):
             src = sensors.copy()
             if kind == "fused-imu":
-                fs.push_imu(np.stack([imu_msgs(rng, 50.0 + 0.1 * t + 3 * b, 3, YAW["omega"]) for b in range(B)]))
+                fs.push_imu(np.stack([imu_messages(rng, 50.0 + 0.1 * t + 3 * b, 3, rate=YAW["omega"], rate_sigma=0.001) for b in range(B)]))
                 st, _ = fs.ctx.imu_state(B)                     # what the step will read: normal 15..17, omega 18..20, velocity 0..2
                 src[:, 1:4] = st[:, 15:18]; src[:, 4:7] = st[:, 18:21]; src[:, 22:25] = st[:, 0:3]
             old = np.zeros((B, cfg.max_corners, 2), np.float32)
@@ -219,7 +209,8 @@ def test_stream_steps_seeded(pkg, ofk, gpu_ctx, kind, mode):
                 sd = seeds[b, :oc[b]]
                 lk = lambda g0, g1, o: R.lk_pyr(g0, g1, o, cfg.win, cfg.max_level, cfg.max_count, cfg.eps, cfg.min_eig_thr, seed=sd, flags=R.USE_INITIAL_FLOW)
                 moved += int(np.sum(np.abs(sd - old[b, :oc[b]]) > 2))
-                v, tr, n_old, n_tr = loops[b].step(frames[b, t], src[b], lk)
+                o = loops[b].step(frames[b, t], src[b], lk=lk)
+                v, tr, n_old, n_tr = o["v"], o["tracks"], o["n_old"], o["n_tracked"]
                 assert rec[b, 12] == n_old and rec[b, 13] == n_tr and counts[b] == len(tr), (t, b, rec[b, 12:14], n_old, n_tr, counts[b], len(tr))
                 assert np.array_equal(bits(tracks[b, :counts[b]]), bits(tr.astype(np.float32))), (t, b)
                 if v is not None:

@@ -153,25 +153,31 @@ def test_predictor_falls_back_to_the_point():
 
 
 def test_stream_loop_helper_equals_the_stream_oracle_with_seeding_off(pkg):
-    """tests/seed_stream_oracle.py restates tests/stream_oracle.py::oracle_stream with the tracker as a parameter."""
+    """The stream loop with its tracker plug (tests/stream_oracle.py::NodeLoop) gives what oracle_stream gave while it was a loop of
+    its own (tests/golden/stream_loops.npz, recorded from it), and the restated tracker in the plug changes nothing."""
+    import os
     from of_amd import synth
     from of_amd.pipeline import PipelineConfig
-    from stream_oracle import oracle_stream
-    import seed_stream_oracle as sso
+    from stream_oracle import NodeLoop, oracle_stream
     cfg = PipelineConfig(max_corners=60, quality=0.04, min_distance=9, block_size=7, win=15, max_level=2, max_count=20, eps=0.03)
     frames, info = synth.render_sequence(240, 320, 77, 5, v=(0.03, 0.012, 0.0), omega=(0.0, 0.0, 0.01), d=1.0)
     s = R.experiment_sensors(info, v_prior=(0, 0, 0))
+    pinned = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stream_loops.npz"))
     redetected = False
     for min_feat in (59, 10):
         first, steps = oracle_stream(frames, cfg, s, min_feat, 12)
-        first2, steps2 = sso.run(frames, cfg, s, min_feat, 12, sso.plain_lk(cfg))
+        rec = {f: pinned[f"plain-{min_feat}/{f}"] for f in ("first", "v", "v.size", "tracks", "tracks.size", "n_old", "n_tracked")}
+        first2 = rec["first"]
+        steps2 = list(zip([None if n < 0 else v for n, v in zip(rec["v.size"], np.split(rec["v"], np.cumsum(np.maximum(rec["v.size"], 0))[:-1]))],
+                          [t.reshape(-1, 2) for t in np.split(rec["tracks"], np.cumsum(rec["tracks.size"])[:-1])], rec["n_old"], rec["n_tracked"]))
         assert np.array_equal(first, first2) and len(steps) == len(steps2)
         for a, b in zip(steps, steps2):
             assert (a[0] is None) == (b[0] is None) and (a[0] is None or np.array_equal(a[0], b[0]))
-            assert np.array_equal(bits(a[1].astype(np.float32)), bits(b[1].astype(np.float32))) and a[2:] == b[2:]
+            assert np.array_equal(bits(a[1].astype(np.float32)), bits(b[1].astype(np.float32))) and a[2:] == tuple(b[2:])
             redetected = redetected or len(a[1]) > a[3]
         # the restated tracker without a seed is the oracle's tracker, so the loop does not change either
         ref_lk = lambda g0, g1, old: R.lk_pyr(g0, g1, old, cfg.win, cfg.max_level, cfg.max_count, cfg.eps, cfg.min_eig_thr)
-        steps3 = sso.run(frames, cfg, s, min_feat, 12, ref_lk)[1]
-        assert all(np.array_equal(a[1], b[1]) for a, b in zip(steps, steps3))
+        loop = NodeLoop(frames[0], cfg, min_feat, 12, lk=ref_lk)
+        steps3 = [loop.step(frames[t], s)["tracks"] for t in range(1, len(frames))]
+        assert all(np.array_equal(a[1], b) for a, b in zip(steps, steps3))
     assert redetected

@@ -112,6 +112,7 @@ def test_drop_removes_the_object_from_the_tracks_of_the_restated_loop(pkg):
     from of_amd import synth, ofk
     from of_amd.pipeline import PipelineConfig
     import robust_stream_oracle as rso
+    from stream_oracle import NodeLoop
     h, w, nf = 480, 640, 6
     cfg = PipelineConfig(max_corners=200, quality=0.01, min_distance=10, block_size=7, win=15, max_level=3, max_count=20, eps=0.03)
     for seed in (900, 901):
@@ -119,7 +120,7 @@ def test_drop_removes_the_object_from_the_tracks_of_the_restated_loop(pkg):
         sr = ofk.make_sensors(1, d=info["d"], normal=info["n"], omega=info["omega"], scaling=info["scaling"], cx=info["cx"], cy=info["cy"])[0]
         share = {}
         for drop in (False, True):
-            loop = rso.RobustLoop(frames[0], cfg, 150, 15, "step", 0, drop)
+            loop = NodeLoop(frames[0], cfg, 150, 15, solve=rso.robust_solver(0, drop, False))
             for t in range(1, nf):
                 out = loop.step(frames[t], sr)
                 assert rr.rel_err(out["v"], info["v"]) <= rr.ROBUST_MAX, (seed, drop, t)
