@@ -145,3 +145,51 @@ void ofk_launch_seed_points(hipStream_t s, const float *pts, const int *counts, 
     hipLaunchKernelGGL(k_seed_points, dim3((pts_stride + 255) / 256, batch), dim3(256), 0, s, pts, counts, pts_stride, sensors, imu_state,
                        mode, gain, seed_out);
 }
+
+// The track gates (ofk.h: ofk_set_track_gate, rules 3-5): per used point the squared forward-backward distance in float32 as
+// written there (the build has no FMA contraction), status := keep, and the image's four counts.  One workgroup per image, threads
+// stride over its points; the counts are ballots summed per wave, then across the four waves through LDS, and written by one thread
+// with plain stores: no atomics, so a second launch on the same buffers gives the same bits.
+__global__ __launch_bounds__(256) void k_track_gate(const float *__restrict__ prev_pts, const float *__restrict__ back_pts,
+                                                    const uint8_t *__restrict__ st_back, const float *__restrict__ err,
+                                                    const int *__restrict__ counts, int pts_stride, int fb_on, float thr2, int err_on,
+                                                    float err_max, uint8_t *__restrict__ status, float *__restrict__ fb2,
+                                                    int *__restrict__ stats)
+{
+    __shared__ int s_cnt[4][4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(counts[b], pts_stride);
+    const size_t base = (size_t)b * pts_stride;
+    int c_fwd = 0, c_lost = 0, c_far = 0, c_cap = 0;             // wave-uniform
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + tid;
+        const bool in = i < n;
+        const size_t pi = base + (in ? i : 0);
+        const bool fwd = in && status[pi] == 1;
+        bool lost = false, far = false;
+        if (fb_on) {
+            const bool sb = st_back[pi] == 1;
+            const float dx = back_pts[2 * pi] - prev_pts[2 * pi], dy = back_pts[2 * pi + 1] - prev_pts[2 * pi + 1];
+            const float d2 = dx * dx + dy * dy;
+            lost = fwd && !sb;
+            far = fwd && sb && !(d2 <= thr2);                    // a NaN fails the comparison
+            if (in) fb2[pi] = fwd && sb ? d2 : __builtin_inff();
+        }
+        const bool cap = fwd && !lost && !far && err_on && !(err[pi] <= err_max);
+        if (in) status[pi] = fwd && !lost && !far && !cap;
+        c_fwd += __popcll(__ballot(fwd)); c_lost += __popcll(__ballot(lost));
+        c_far += __popcll(__ballot(far)); c_cap += __popcll(__ballot(cap));
+    }
+    if (lane == 0) { s_cnt[wave][0] = c_fwd; s_cnt[wave][1] = c_lost; s_cnt[wave][2] = c_far; s_cnt[wave][3] = c_cap; }
+    __syncthreads();
+    if (tid == 0)
+        for (int k = 0; k < 4; ++k) stats[4 * b + k] = s_cnt[0][k] + s_cnt[1][k] + s_cnt[2][k] + s_cnt[3][k];
+}
+
+void ofk_launch_track_gate(hipStream_t s, const float *prev_pts, const float *back_pts, const uint8_t *st_back, const float *err,
+                           const int *counts, int pts_stride, int fb_on, float thr2, int err_on, float err_max, uint8_t *status, float *fb2,
+                           int *stats, int batch)
+{
+    hipLaunchKernelGGL(k_track_gate, dim3(batch), dim3(256), 0, s, prev_pts, back_pts, st_back, err, counts, pts_stride, fb_on, thr2, err_on,
+                       err_max, status, fb2, stats);
+}

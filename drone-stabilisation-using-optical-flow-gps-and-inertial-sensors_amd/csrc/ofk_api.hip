@@ -148,6 +148,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->gray_direct_set = -1;
     c->lk_seed_mode = OFK_SEED_OFF; c->lk_seed_gain = 1.0;
     c->robust = ofk_robust{OFK_ROBUST_OFF, 4.685, 5, 64, 0ull, 0};
+    c->gate = ofk_track_gate{OFK_FB_OFF, 0.5, -1, 0.0};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -200,7 +201,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     for (int k = 0; k < 2; ++k) { if (c->bgr[k]) hipFree(c->bgr[k]); if (c->pyr[k]) hipFree(c->pyr[k]); }
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
-                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work};
+                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
@@ -424,6 +425,7 @@ struct View {
     unsigned *sel_hist; unsigned long long *sel_keys;
     float *pts_prev, *pts_next; uint8_t *status; float *err; int *counts;
     double *sensors, *records;
+    float *pts_back, *err_back, *fb2; uint8_t *status_back; int *gate_stats;   // NULL until a run with a track gate on (gate_alloc)
 };
 static View view_of(ofk_ctx *c, int b0, int nb, int set)
 {
@@ -439,6 +441,11 @@ static View view_of(ofk_ctx *c, int b0, int nb, int set)
     v.pts_prev = c->pts_prev + b * c->max_pts * 2; v.pts_next = c->pts_next + b * c->max_pts * 2;
     v.status = c->status + b * c->max_pts; v.err = c->err + b * c->max_pts; v.counts = c->counts + b;
     v.sensors = c->sensors + b * OFK_SENSOR_DOUBLES; v.records = c->records + b * OFK_RECORD_DOUBLES;
+    v.pts_back = v.err_back = v.fb2 = nullptr; v.status_back = nullptr; v.gate_stats = nullptr;
+    if (c->pts_back) {
+        v.pts_back = c->pts_back + b * c->max_pts * 2; v.err_back = c->err_back + b * c->max_pts; v.fb2 = c->fb2 + b * c->max_pts;
+        v.status_back = c->status_back + b * c->max_pts; v.gate_stats = c->gate_stats + b * 4;
+    }
     return v;
 }
 
@@ -546,19 +553,112 @@ static void build_pyramids(ofk_ctx *c, hipStream_t s, uint8_t *pyr0, uint8_t *py
     }
 }
 
+static bool gate_on(const ofk_track_gate &g) { return g.fb_mode != OFK_FB_OFF || g.err_max != 0.0; }
+
+// Rules 2-5 of the track gates (ofk.h) behind a forward LK of the view on stream s: the backward LK, which is the forward launch with
+// the two pyramids swapped and a level table of the gate's depth, then k_track_gate.  The view's gate buffers exist (gate_alloc).
+static int gate_tracks(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, int win, int max_level, int max_count, double eps,
+                       double min_eig_thr, const ofk_track_gate &g)
+{
+    const bool fb = g.fb_mode != OFK_FB_OFF;
+    if (fb) {
+        const int depth = g.fb_level < 0 || g.fb_level > max_level ? max_level : g.fb_level;
+        const ofk_levels lb = ofk_make_levels(lv.h[0], lv.w[0], win, depth);
+        const bool seeded = g.fb_mode == OFK_FB_SEEDED;            // LK's next_pts is in/out: the search starts at the original points
+        if (seeded) OFK_HIP(c, hipMemcpyAsync(v.pts_back, v.pts_prev, (size_t)v.nb * c->max_pts * 8, hipMemcpyDeviceToDevice, s));
+        ofk_launch_lk(s, v.pyr[1], v.pyr[0], c->pyr_stride, lb, v.pts_next, v.counts, c->max_pts, win, max_count, eps, min_eig_thr, v.pts_back,
+                      v.status_back, v.err_back, v.nb, seeded ? OFK_LK_USE_INITIAL_FLOW : 0);
+    }
+    ofk_launch_track_gate(s, v.pts_prev, fb ? v.pts_back : nullptr, fb ? v.status_back : nullptr, v.err, v.counts, c->max_pts, fb ? 1 : 0,
+                          (float)(g.fb_thr * g.fb_thr), g.err_max != 0.0 ? 1 : 0, (float)g.err_max, v.status, fb ? v.fb2 : nullptr, v.gate_stats,
+                          v.nb);
+    return OFK_OK;
+}
+
 // The track step of the resident chains: with ofk_set_lk_seed on, the start positions are written where LK reads them (imu_state: the
-// source k_stream_fuse uses under use_imu, NULL = the sensors only) and LK starts there
-static void track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, const ofk_params *p, const double *imu_state)
+// source k_stream_fuse uses under use_imu, NULL = the sensors only) and LK starts there;
+// with ofk_set_track_gate on, the gates follow on the same stream
+static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, const ofk_params *p, const double *imu_state)
 {
     const bool seeded = c->lk_seed_mode != OFK_SEED_OFF;
     if (seeded) ofk_launch_seed_points(s, v.pts_prev, v.counts, c->max_pts, v.sensors, imu_state, c->lk_seed_mode, c->lk_seed_gain, v.pts_next, v.nb);
     ofk_launch_lk(s, v.pyr[0], v.pyr[1], c->pyr_stride, lv, v.pts_prev, v.counts, c->max_pts, p->win, p->max_count, p->eps, p->min_eig_thr,
                   v.pts_next, v.status, v.err, v.nb, seeded ? OFK_LK_USE_INITIAL_FLOW : 0);
+    if (gate_on(c->gate)) TRY(gate_tracks(c, s, v, lv, p->win, p->max_level, p->max_count, p->eps, p->min_eig_thr, c->gate));
+    return OFK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ track gate setting
+static int check_gate(ofk_ctx *c, const ofk_track_gate *g, const char *who)
+{
+    if (g->fb_mode != OFK_FB_OFF && g->fb_mode != OFK_FB_PLAIN && g->fb_mode != OFK_FB_SEEDED)
+        return ofk_fail(c, OFK_E_INVALID, "%s: fb_mode %d is none of OFK_FB_OFF, _PLAIN, _SEEDED", who, g->fb_mode);
+    if (g->fb_mode != OFK_FB_OFF && !(std::isfinite(g->fb_thr) && g->fb_thr > 0.0))
+        return ofk_fail(c, OFK_E_INVALID, "%s: fb_thr = %g must be finite and positive", who, g->fb_thr);
+    if (g->fb_level < -1 || g->fb_level > c->max_level)
+        return ofk_fail(c, OFK_E_INVALID, "%s: fb_level %d outside -1..%d", who, g->fb_level, c->max_level);
+    if (!(std::isfinite(g->err_max) && g->err_max >= 0.0))
+        return ofk_fail(c, OFK_E_INVALID, "%s: err_max = %g must be finite and not negative (0 = off)", who, g->err_max);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_track_gate(ofk_ctx *c, const ofk_track_gate *g)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!g) { c->gate.fb_mode = OFK_FB_OFF; c->gate.err_max = 0.0; return OFK_OK; }
+    TRY(check_gate(c, g, "ofk_set_track_gate"));
+    c->gate = *g;
+    return OFK_OK;
+}
+
+extern "C" int ofk_get_track_gate(const ofk_ctx *c, ofk_track_gate *g)
+{
+    if (!c || !g) return OFK_E_INVALID;
+    *g = c->gate;
+    return OFK_OK;
+}
+
+// the resident buffers of the gates, allocated when a run first needs them
+static int gate_alloc(ofk_ctx *c)
+{
+    if (c->pts_back) return OFK_OK;                              // one allocation, carved into the five buffers: all of them or none
+    const size_t B = (size_t)c->max_batch, np = B * c->max_pts;
+    const size_t o_err = np * 8, o_fb2 = o_err + np * 4, o_stats = o_fb2 + np * 4, o_st = o_stats + B * 16;
+    uint8_t *base = nullptr;
+    OFK_HIP(c, hipMalloc((void **)&base, o_st + np));
+    c->pts_back = (float *)base; c->err_back = (float *)(base + o_err); c->fb2 = (float *)(base + o_fb2);
+    c->gate_stats = (int *)(base + o_stats); c->status_back = base + o_st;
+    return OFK_OK;
+}
+
+extern "C" int ofk_track_gate_download(ofk_ctx *c, float *fb2, float *back_pts, uint8_t *back_status, int stride, int *stats)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->gate_batch < 1 || !c->pts_back) return ofk_fail(c, OFK_E_INVALID, "ofk_track_gate_download: no run or step with ofk_set_track_gate on yet");
+    if ((fb2 || back_pts || back_status) && stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_track_gate_download: stride %d", stride);
+    TRY(enter(c));
+    const int B = c->gate_batch;
+    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    if (c->gate_fb) {
+        if (fb2) OFK_HIP(c, hipMemcpy2DAsync(fb2, (size_t)stride * 4, c->fb2, mp * 4, n * 4, B, hipMemcpyDeviceToHost, c->stream));
+        if (back_pts) OFK_HIP(c, hipMemcpy2DAsync(back_pts, (size_t)stride * 8, c->pts_back, mp * 8, n * 8, B, hipMemcpyDeviceToHost, c->stream));
+        if (back_status) OFK_HIP(c, hipMemcpy2DAsync(back_status, stride, c->status_back, mp, n, B, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        for (int b = 0; b < B; ++b) {                            // the err cap alone: there was no backward pass
+            if (fb2) memset(fb2 + (size_t)b * stride, 0, n * 4);
+            if (back_pts) memset(back_pts + (size_t)b * stride * 2, 0, n * 8);
+            if (back_status) memset(back_status + (size_t)b * stride, 0, n);
+        }
+    }
+    if (stats) OFK_HIP(c, hipMemcpyAsync(stats, c->gate_stats, (size_t)B * 16, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
 }
 
 static int lk_pyr_impl(ofk_ctx *c, const char *who, const uint8_t *prev, const uint8_t *next, int batch, int h, int w, const float *prev_pts,
                        const int *counts, int pts_stride, int win, int max_level, int max_count, double eps, double min_eig_thr,
-                       const float *init_pts, int flags, float *next_pts, uint8_t *status, float *err)
+                       const float *init_pts, int flags, float *next_pts, uint8_t *status, float *err, const ofk_track_gate *g = nullptr,
+                       float *back_pts = nullptr, uint8_t *back_status = nullptr, float *fb2 = nullptr)
 {
     TRY(check_geom(c, batch, h, w, who));
     if (!prev || !next || !prev_pts || !counts || !next_pts || !status || !err) return ofk_fail(c, OFK_E_INVALID, "%s: NULL buffer", who);
@@ -567,6 +667,12 @@ static int lk_pyr_impl(ofk_ctx *c, const char *who, const uint8_t *prev, const u
     for (int b = 0; b < batch; ++b)
         if (counts[b] < 0 || counts[b] > pts_stride) return ofk_fail(c, OFK_E_INVALID, "counts[%d]=%d outside 0..%d", b, counts[b], pts_stride);
     if (flags & ~(OFK_LK_USE_INITIAL_FLOW | OFK_LK_GET_MIN_EIGENVALS)) return ofk_fail(c, OFK_E_INVALID, "%s: unknown flag bits 0x%x", who, flags);
+    if (g) {                                                     // the setting's rules hold for a structure that switches nothing on, too
+        TRY(check_gate(c, g, who));
+        if ((flags & OFK_LK_GET_MIN_EIGENVALS) && g->err_max != 0.0)
+            return ofk_fail(c, OFK_E_INVALID, "%s: err_max with OFK_LK_GET_MIN_EIGENVALS: err is no residual then", who);
+    }
+    const bool gated = g && gate_on(*g);
     const bool seeded = (flags & OFK_LK_USE_INITIAL_FLOW) != 0;
     if (seeded) {
         if (!init_pts) return ofk_fail(c, OFK_E_INVALID, "%s: OFK_LK_USE_INITIAL_FLOW needs init_pts", who);
@@ -576,6 +682,7 @@ static int lk_pyr_impl(ofk_ctx *c, const char *who, const uint8_t *prev, const u
                 if (!(fabsf(v) <= 1e6f)) return ofk_fail(c, OFK_E_INVALID, "%s: init_pts[%d][%d] = %g is not a finite coordinate within 1e6", who, b, i / 2, (double)v);
             }
     }
+    if (gated) TRY(gate_alloc(c));                               // behind every refusal
     const size_t px = (size_t)h * w;
     const ofk_levels lv = ofk_make_levels(h, w, win, max_level);
     TRY(h2d(c, c->pyr[0], c->pyr_stride, prev, px, batch));
@@ -586,7 +693,18 @@ static int lk_pyr_impl(ofk_ctx *c, const char *who, const uint8_t *prev, const u
     build_pyramids(c, c->stream, c->pyr[0], c->pyr[1], lv, batch);
     ofk_launch_lk(c->stream, c->pyr[0], c->pyr[1], c->pyr_stride, lv, c->pts_prev, c->counts, c->max_pts, win, max_count, eps,
                   min_eig_thr, c->pts_next, c->status, c->err, batch, flags);
+    if (gated) {
+        TRY(gate_tracks(c, c->stream, view_of(c, 0, batch, 0), lv, win, max_level, max_count, eps, min_eig_thr, *g));
+        c->gate_batch = batch; c->gate_fb = g->fb_mode != OFK_FB_OFF;
+    }
     TRY(check_launch(c, "k_lk"));
+    if (gated && g->fb_mode != OFK_FB_OFF) {
+        if (back_pts) OFK_HIP(c, hipMemcpy2DAsync(back_pts, (size_t)pts_stride * 8, c->pts_back, (size_t)c->max_pts * 8, (size_t)pts_stride * 8, batch,
+                                                  hipMemcpyDeviceToHost, c->stream));
+        if (back_status) OFK_HIP(c, hipMemcpy2DAsync(back_status, pts_stride, c->status_back, c->max_pts, pts_stride, batch, hipMemcpyDeviceToHost, c->stream));
+        if (fb2) OFK_HIP(c, hipMemcpy2DAsync(fb2, (size_t)pts_stride * 4, c->fb2, (size_t)c->max_pts * 4, (size_t)pts_stride * 4, batch,
+                                             hipMemcpyDeviceToHost, c->stream));
+    }
     OFK_HIP(c, hipMemcpy2DAsync(next_pts, (size_t)pts_stride * 8, c->pts_next, (size_t)c->max_pts * 8, (size_t)pts_stride * 8, batch,
                                 hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipMemcpy2DAsync(status, pts_stride, c->status, c->max_pts, pts_stride, batch, hipMemcpyDeviceToHost, c->stream));
@@ -607,6 +725,15 @@ extern "C" int ofk_lk_pyr_ex(ofk_ctx *c, const uint8_t *prev, const uint8_t *nex
 {
     return lk_pyr_impl(c, "ofk_lk_pyr_ex", prev, next, batch, h, w, prev_pts, counts, pts_stride, win, max_level, max_count, eps, min_eig_thr,
                        init_pts, flags, next_pts, status, err);
+}
+
+extern "C" int ofk_lk_pyr_fb(ofk_ctx *c, const uint8_t *prev, const uint8_t *next, int batch, int h, int w, const float *prev_pts,
+                             const int *counts, int pts_stride, int win, int max_level, int max_count, double eps, double min_eig_thr,
+                             const float *init_pts, int flags, float *next_pts, uint8_t *status, float *err, const ofk_track_gate *g,
+                             float *back_pts, uint8_t *back_status, float *fb2)
+{
+    return lk_pyr_impl(c, "ofk_lk_pyr_fb", prev, next, batch, h, w, prev_pts, counts, pts_stride, win, max_level, max_count, eps, min_eig_thr,
+                       init_pts, flags, next_pts, status, err, g, back_pts, back_status, fb2);
 }
 
 static bool seed_mode_ok(int mode) { return mode == OFK_SEED_OFF || mode == OFK_SEED_MODEL || mode == OFK_SEED_ROTATION; }
@@ -1236,11 +1363,14 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
     // slice after slice, which offsets the slices by one response kernel for as long as they run.
     const bool fork = S > 1 && !c->slices_open;
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
+    if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
     TRY(need_streams(c, S, overlap));
     if (fork) {
         OFK_HIP(c, hipEventRecord(c->ev_fork, c->stream));
         for (int k = 1; k < S; ++k) OFK_HIP(c, hipStreamWaitEvent(c->streams[k], c->ev_fork, 0));
     }
+    int rc_track = OFK_OK;                                       // a failed gate copy is reported behind the loop: the slices' events and
+                                                                 // the bookkeeping below stay whole, so the next call joins what this one forked
     for (int k = 0; k < S; ++k) {
         const int b0 = (int)((long long)B * k / S), nb = (int)((long long)B * (k + 1) / S) - b0;
         if (nb <= 0) continue;
@@ -1278,9 +1408,10 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
         if (overlap) OFK_HIP(c, hipStreamWaitEvent(st, c->ev_aux[k], 0));    // LK needs both pyramids
         {
             StageTimer t(c, OFK_STAGE_LK, st);
-            track(c, st, v, lv, p, nullptr);                     // a seed comes from the pair's sensors
+            const int rc = track(c, st, v, lv, p, nullptr);      // a seed comes from the pair's sensors
+            if (rc != OFK_OK && rc_track == OFK_OK) rc_track = rc;
         }
-        if (overlap) OFK_HIP(c, hipEventRecord(c->ev_lkdone[set][k], st));   // this pyramid set may be rewritten from here on
+        if (overlap) OFK_HIP(c, hipEventRecord(c->ev_lkdone[set][k], st));   // behind the set's last reader (the gate's backward pass, when on): it may be rewritten from here on
         if (c->x_pending) OFK_HIP(c, hipStreamWaitEvent(st, c->ev_x, 0));    // the previous call's records are still being exported
         {
             StageTimer t(c, OFK_STAGE_SOLVE, st);
@@ -1289,6 +1420,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
         if (S > 1) OFK_HIP(c, hipEventRecord(c->ev_end[k], st));             // joined lazily (join_slices), not here
     }
     if (S > 1) { c->slices_open = 1; c->open_slices = S; }
+    if (rc_track != OFK_OK) return rc_track;
     return check_launch(c, "ofk_pairs_run");
 }
 
@@ -1545,6 +1677,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     } else if (p->solve_variant != OFK_SOLVE_NODE && p->solve_variant != OFK_SOLVE_SIM) return ofk_fail(c, OFK_E_INVALID, "solve_variant must be NODE or SIM");
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
+    if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
     OFK_HIP(c, hipMemcpyAsync(c->sensors, sensors, (size_t)B * OFK_SENSOR_DOUBLES * 8, hipMemcpyHostToDevice, c->stream));
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
@@ -1556,7 +1689,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     }
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)
-    track(c, c->stream, view_of(c, 0, B, 0), lv, p, fu && fu->use_imu ? c->imu_state : nullptr);
+    TRY(track(c, c->stream, view_of(c, 0, B, 0), lv, p, fu && fu->use_imu ? c->imu_state : nullptr));
     if (fu && c->robust.loss != OFK_ROBUST_OFF)
         ofk_launch_stream_fuse_robust(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
                                       c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, p->use_feasibility, p->feas_T,

@@ -87,6 +87,10 @@ struct ofk_ctx {
     ofk_robust robust;                       // ofk_set_robust: loss OFK_ROBUST_OFF unless set
     double *rob_work, *rob_w, *rob_wtmp, *rob_stats;   // [B][7][max_pts] per-point terms, [B][max_pts] weights (+ a scratch copy), [B][OFK_ROBUST_DOUBLES]; one lazy allocation (rob_work owns it)
     int rob_batch;                           // problems of the latest robust run / step (ofk_robust_download), 0 = none
+    ofk_track_gate gate;                     // ofk_set_track_gate: fb_mode OFK_FB_OFF and err_max 0 unless set
+    float *pts_back, *err_back, *fb2;        // [B][max_pts][2] end points of the backward pass, [B][max_pts] its err (discarded) and the squared
+    uint8_t *status_back; int *gate_stats;   // distances; [B][max_pts] its status, [B][4] the gate's counts; one lazy allocation (pts_back owns it)
+    int gate_batch, gate_fb;                 // images of the latest gated run / step (ofk_track_gate_download), 0 = none / it ran a backward pass
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -158,6 +162,10 @@ void ofk_launch_lk(hipStream_t s, const uint8_t *prev, const uint8_t *next, size
 // start positions of a seeded LK (ofk.h: ofk_set_lk_seed): seed_out[b][p] for p < counts[b]; imu_state NULL = sensors only
 void ofk_launch_seed_points(hipStream_t s, const float *pts, const int *counts, int pts_stride, const double *sensors,
                             const double *imu_state, int mode, double gain, float *seed_out, int batch);
+// the track gates behind LK (ofk.h: ofk_set_track_gate): status := keep, fb2 (fb_on) and stats[b][4]; back / st_back / fb2 NULL without fb_on
+void ofk_launch_track_gate(hipStream_t s, const float *prev_pts, const float *back_pts, const uint8_t *st_back, const float *err,
+                           const int *counts, int pts_stride, int fb_on, float thr2, int err_on, float err_max, uint8_t *status, float *fb2,
+                           int *stats, int batch);
 void ofk_launch_pairs_solve(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status,
                             const int *counts, int pts_stride, const double *sensors, int variant, int use_feas,
                             double feas_T, const int *cand_count, double *records, int batch);

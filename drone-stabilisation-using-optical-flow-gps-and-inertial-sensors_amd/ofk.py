@@ -27,6 +27,7 @@ SYMBOLS = (
     "ofk_gray_bgr8", "ofk_pyr_down_u8", "ofk_pyramid_u8", "ofk_scharr_s16", "ofk_mineig_response", "ofk_select_corners",
     "ofk_good_features", "ofk_lk_pyr", "ofk_lk_pyr_ex", "ofk_predict_points", "ofk_set_lk_seed", "ofk_get_lk_seed", "ofk_flow_model", "ofk_feasibility", "ofk_velocity_solve", "ofk_imu_propagate",
     "ofk_set_robust", "ofk_get_robust", "ofk_robust_download", "ofk_velocity_solve_robust", "ofk_robust_pairs",
+    "ofk_set_track_gate", "ofk_get_track_gate", "ofk_track_gate_download", "ofk_lk_pyr_fb",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
     "ofk_stream_begin_jpeg", "ofk_stream_step_jpeg",
@@ -57,6 +58,8 @@ ROBUST_OFF, ROBUST_HUBER, ROBUST_TUKEY = 0, 1, 2         # ofk_set_robust / ofk_
 ROBUST_LOSSES = {"off": ROBUST_OFF, "huber": ROBUST_HUBER, "tukey": ROBUST_TUKEY}
 ROBUST_DEFAULT_C = {ROBUST_HUBER: 1.345, ROBUST_TUKEY: 4.685}     # 95 % efficiency on Gaussian residuals
 ROBUST_MIN_POINTS, ROBUST_DOUBLES = 8, 8
+FB_OFF, FB_PLAIN, FB_SEEDED = 0, 1, 2                    # ofk_set_track_gate / ofk_lk_pyr_fb
+FB_MODES = {"off": FB_OFF, "plain": FB_PLAIN, "seeded": FB_SEEDED}
 FLOW_LK, FLOW_ROTATIONAL = 0, 1
 KEEP_STATUS, KEEP_LEGACY = 0, 1
 CONTROL_SENSORS, CONTROL_IMU = 0, 1
@@ -88,6 +91,30 @@ def robust_pairs(seed, problem, hypotheses, m):
     if rc != 0:
         raise OfkError(rc, f"ofk_robust_pairs: hypotheses {n} outside 0..256 or m {m} < 2")
     return i[:max(n, 0)], j[:max(n, 0)]
+
+
+class TrackGate(C.Structure):
+    """ofk_track_gate (include/ofk.h): the forward-backward check and the err cap behind LK."""
+    _fields_ = [("fb_mode", C.c_int), ("fb_thr", C.c_double), ("fb_level", C.c_int), ("err_max", C.c_double)]
+
+
+def track_gate_setting(fb="off", fb_thr=0.5, fb_level=-1, err_max=0.0):
+    """A TrackGate structure from names: fb "off" / "plain" (the backward search starts at the forward result) / "seeded" (it starts
+    at the original point), or FB_*; fb_thr in pixels; fb_level -1 = the forward pass's maxLevel; err_max 0 = no cap on LK's err."""
+    if isinstance(fb, str):
+        if fb not in FB_MODES:
+            raise ValueError(f"track gate fb {fb!r} is none of {sorted(FB_MODES)}")
+        fb = FB_MODES[fb]
+    fb, fb_thr, fb_level, err_max = int(fb), float(fb_thr), int(fb_level), float(err_max)
+    if fb not in FB_MODES.values():
+        raise ValueError(f"track gate fb mode {fb} is none of FB_OFF, FB_PLAIN, FB_SEEDED")
+    if fb != FB_OFF and not (np.isfinite(fb_thr) and fb_thr > 0.0):
+        raise ValueError(f"track gate fb_thr {fb_thr} must be finite and positive")
+    if fb_level < -1:
+        raise ValueError(f"track gate fb_level {fb_level} must be -1 (the forward pass's) or a pyramid depth")
+    if not (np.isfinite(err_max) and err_max >= 0.0):
+        raise ValueError(f"track gate err_max {err_max} must be finite and not negative (0 = off)")
+    return TrackGate(fb, fb_thr, fb_level, err_max)
 
 
 class Fusion(C.Structure):
@@ -163,6 +190,9 @@ def load_library():
         L.ofk_robust_download.argtypes = [vp, vp, i, vp]
         L.ofk_velocity_solve_robust.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), vp, vp, vp]
         L.ofk_robust_pairs.argtypes = [C.c_ulonglong, C.c_uint, i, i, vp, vp]
+        L.ofk_set_track_gate.argtypes = [vp, C.POINTER(TrackGate)]; L.ofk_get_track_gate.argtypes = [vp, C.POINTER(TrackGate)]
+        L.ofk_track_gate_download.argtypes = [vp, vp, vp, vp, i, vp]
+        L.ofk_lk_pyr_fb.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, i, vp, vp, vp, C.POINTER(TrackGate), vp, vp, vp]
         L.ofk_imu_propagate.argtypes = [vp, vp, vp, i]
         L.ofk_post_solve.argtypes = [vp, vp, vp, vp, vp, i, vp]
         L.ofk_associate_sensors.argtypes = [vp, vp, i, vp, vp, vp, i, vp, vp, i, vp, vp, vp]
@@ -439,6 +469,70 @@ class Context:
         m = C.c_int(0); g = C.c_double(0)
         self._ck(self._L.ofk_get_lk_seed(self._h, C.byref(m), C.byref(g)))
         return m.value, g.value
+
+    def set_track_gate(self, gate=None, **settings):
+        """ofk_set_track_gate: a TrackGate (or track_gate_setting's keywords); None switches both gates off.  Every later pairs_run
+        and stream step clears the status of the points the gates reject, behind LK and in front of the solve."""
+        g = gate if gate is not None or not settings else track_gate_setting(**settings)
+        self._ck(self._L.ofk_set_track_gate(self._h, C.byref(g) if g is not None else None))
+
+    def get_track_gate(self):
+        g = TrackGate()
+        self._ck(self._L.ofk_get_track_gate(self._h, C.byref(g)))
+        return g
+
+    def track_gate_download(self, batch, points=True):
+        """ofk_track_gate_download of the latest gated run / step -> dict(stats [batch,4] i32: forward-tracked, of those lost by the
+        backward pass, of the rest beyond fb_thr, of the rest over err_max; and, with points, fb2 [batch,max_pts] f32, back_pts
+        [batch,max_pts,2] f32, back_status [batch,max_pts] u8 - zeros when only the err cap was on).  The library writes the rows of
+        the latest run, whatever `batch` says, so the buffers have max_batch rows and the first `batch` are returned."""
+        B, S = self.max_batch, self.max_pts
+        if not 0 <= int(batch) <= B:
+            raise ValueError(f"track_gate_download: batch {batch} outside 0..{B}")
+        st = np.zeros((B, 4), np.int32)
+        fb2 = bp = bs = None
+        if points:
+            fb2 = np.zeros((B, S), np.float32); bp = np.zeros((B, S, 2), np.float32); bs = np.zeros((B, S), np.uint8)
+        with self._lock:
+            self._ck(self._L.ofk_track_gate_download(self._h, _p(fb2), _p(bp), _p(bs), S, _p(st)))
+        out = dict(stats=st[:batch].copy())
+        if points:
+            out.update(fb2=fb2[:batch].copy(), back_pts=bp[:batch].copy(), back_status=bs[:batch].copy())
+        return out
+
+    def track_gate_stats(self, batch):
+        """The four counts per image of the latest gated run / step alone ([batch,4] int32): no per-point array is copied."""
+        return self.track_gate_download(batch, points=False)["stats"]
+
+    def lk_pyr_fb(self, prev, nxt, prev_pts, counts, gate=None, win=15, max_level=3, max_count=20, eps=0.03, min_eig_thr=1e-4,
+                  next_pts=None, flags=0, **settings):
+        """ofk_lk_pyr_fb: the batched lk_pyr (prev, nxt [B,h,w]; prev_pts [B,S,2]; counts [B]) with the track gates behind it.
+        gate: a TrackGate, or track_gate_setting's keywords.  -> dict(next_pts, status (gated), err, back_pts, back_status, fb2)."""
+        g = gate if gate is not None else track_gate_setting(**settings)
+        flags = int(flags)
+        if flags & LK_USE_INITIAL_FLOW and next_pts is None:
+            raise ValueError("lk_pyr_fb: LK_USE_INITIAL_FLOW needs next_pts")
+        prev = _arr(prev, np.uint8); nxt = _arr(nxt, np.uint8)
+        if prev.ndim != 3 or nxt.shape != prev.shape:
+            raise ValueError(f"lk_pyr_fb: frames {prev.shape} / {nxt.shape} are not two [B, h, w] batches of one shape")
+        B, h, w = prev.shape
+        pp = _arr(prev_pts, np.float32)
+        if pp.ndim != 3 or pp.shape[0] != B or pp.shape[2] != 2 or pp.shape[1] < 1:
+            raise ValueError(f"lk_pyr_fb: prev_pts {pp.shape} is not [{B}, S >= 1, 2]")
+        S = pp.shape[1]
+        counts = _arr(counts, np.int32, (B,))
+        init = None
+        if flags & LK_USE_INITIAL_FLOW:
+            init = _arr(next_pts, np.float32)
+            if init.shape != pp.shape:
+                raise ValueError(f"lk_pyr_fb: next_pts {init.shape} does not match prev_pts {pp.shape}")
+        out = dict(next_pts=np.zeros((B, S, 2), np.float32), status=np.zeros((B, S), np.uint8), err=np.zeros((B, S), np.float32),
+                   back_pts=np.zeros((B, S, 2), np.float32), back_status=np.zeros((B, S), np.uint8), fb2=np.zeros((B, S), np.float32))
+        with self._lock:
+            self._ck(self._L.ofk_lk_pyr_fb(self._h, _p(prev), _p(nxt), B, h, w, _p(pp), _p(counts), S, int(win), int(max_level), int(max_count),
+                                           float(eps), float(min_eig_thr), _p(init), flags, _p(out["next_pts"]), _p(out["status"]),
+                                           _p(out["err"]), C.byref(g), _p(out["back_pts"]), _p(out["back_status"]), _p(out["fb2"])))
+        return out
 
     # ------------------------------------------------------------------ estimation
     def flow_model(self, x, v, omega, d, nrm, t=None):

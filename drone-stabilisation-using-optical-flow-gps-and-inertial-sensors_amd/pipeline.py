@@ -41,6 +41,13 @@ class PipelineConfig:
     robust_hypotheses: int = 64
     robust_seed: int = 0
     robust_drop: bool = False
+    # track gates behind LK (ofk.h: ofk_set_track_gate): fb_check "off", "plain" (track the result back from where it landed) or
+    # "seeded" (the backward search starts at the original point); a point stays tracked when it comes home within fb_thr pixels;
+    # fb_level: pyramid depth of the backward pass, -1 = max_level; err_max > 0 also drops points whose LK err exceeds it
+    fb_check: str = "off"
+    fb_thr: float = 0.5
+    fb_level: int = -1
+    err_max: float = 0.0
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -65,6 +72,12 @@ class PipelineConfig:
         if self.robust == "off":
             return None
         return ofk.robust_setting(self.robust, self.robust_c, self.robust_iters, self.robust_hypotheses, self.robust_seed, self.robust_drop)
+
+    def track_gate_setting(self):
+        """The ofk.TrackGate structure of this configuration, None when both gates are off."""
+        if self.fb_check == "off" and self.err_max == 0.0:
+            return None
+        return ofk.track_gate_setting(self.fb_check, self.fb_thr, self.fb_level, self.err_max)
 
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
@@ -191,6 +204,8 @@ class FlowStream:
             self.ctx.set_lk_seed(self.cfg.lk_seed, self.cfg.seed_gain)
         if self.cfg.robust != "off":
             self.ctx.set_robust(self.cfg.robust_setting())
+        if self.cfg.track_gate_setting() is not None:
+            self.ctx.set_track_gate(self.cfg.track_gate_setting())
         self.fusion = fusion
         if fusion is not None:                                  # the per-stream filter state lives on the device from here on
             self._fusion = fusion.to_struct()
@@ -208,6 +223,11 @@ class FlowStream:
         if self.fusion is None:
             raise ValueError("construct FlowStream(..., fusion=FusionConfig...) for step_fused")
         return self.ctx.stream_step_fused(next_frames, sensors, self._params, self._fusion, self.min_features, self.mask_radius)
+
+    def track_gate_stats(self):
+        """[batch, 4] int32 of the latest step with a track gate on: forward-tracked points, of those lost by the backward pass, of
+        the rest beyond fb_thr, of the rest over err_max."""
+        return self.ctx.track_gate_stats(self.batch)
 
     def begin(self, first_bgr):
         return self.ctx.stream_begin(first_bgr, self._params)
@@ -247,6 +267,8 @@ class FlowPipeline:
             self.ctx.set_lk_seed(self.cfg.lk_seed, self.cfg.seed_gain)
         if self.cfg.robust != "off":
             self.ctx.set_robust(self.cfg.robust_setting())
+        if self.cfg.track_gate_setting() is not None:
+            self.ctx.set_track_gate(self.cfg.track_gate_setting())
         if streams > 1:
             self.ctx.set_streams(streams)
 
@@ -285,6 +307,10 @@ class FlowPipeline:
                     on_step(n)
                 n += 1
         return n
+
+    def track_gate_stats(self):
+        """[batch, 4] int32 of the latest run with a track gate on (see FlowStream.track_gate_stats)."""
+        return self.ctx.track_gate_stats(self.batch)
 
     def run_async(self):
         self.ctx.pairs_run(self._params)

@@ -201,6 +201,54 @@ int ofk_velocity_solve_robust(ofk_ctx *ctx, int variant, const double *x, const 
                               const ofk_robust *r, double *out, double *weights, double *stats);
 int ofk_robust_pairs(unsigned long long seed, unsigned problem, int hypotheses, int m, int *i, int *j);
 
+/* Track gates: the forward-backward check of KLT trackers and a cap on LK's err, applied on the device behind LK and in front of
+ * everything that keys on status == 1.  Both are off by default; with them off every entry point launches the kernels and returns
+ * the bits it always did.  Per used point i < counts[b]:
+ *   1. Forward pass: the LK the entry point always ran (seeded or not by ofk_set_lk_seed / init_pts) -> next, st_f, err.
+ *   2. Backward pass (fb_mode != OFK_FB_OFF): the same LK with the NEXT frame's pyramid as "prev" and the previous frame's as "next",
+ *      from next[i] for EVERY used point whatever st_f is (no compaction).  Window, criteria and min_eig_thr are the forward pass's;
+ *      maxLevel is fb_level, -1 = the forward pass's, else min(fb_level, forward maxLevel); the level table is that of a pyramid of
+ *      this depth (level offsets do not depend on the depth, so it addresses the same resident pyramids).  OFK_FB_PLAIN runs without
+ *      flags (the search starts at next[i]: cv2.calcOpticalFlowPyrLK called a second time); OFK_FB_SEEDED runs with
+ *      OFK_LK_USE_INITIAL_FLOW and start positions equal to the ORIGINAL points -> back, st_b (its err is discarded).
+ *   3. Distance, float32, no contraction, in this order: dx = back.x - prev.x; dy = back.y - prev.y; fb2 = dx*dx + dy*dy.  The
+ *      stored fb2 is that value where st_f == 1 && st_b == 1 and +infinity otherwise.
+ *   4. keep = st_f == 1 && (fb off || (st_b == 1 && fb2 <= (float)(fb_thr * fb_thr))) && (err_max == 0 || err <= (float)err_max);
+ *      the square is formed in double and rounded once; a NaN fails every comparison.
+ *   5. status := keep; next and err stay as the forward pass left them (cv2 leaves the position of a lost point too).
+ *      stats, 4 x int32 per image: points with st_f == 1; of those st_b == 0; of the rest fb2 over the threshold; of the rest err
+ *      over the cap.
+ * ofk_set_track_gate (NULL, or fb_mode OFK_FB_OFF with err_max 0: off) is a context setting read by ofk_pairs_run (every slice),
+ * ofk_stream_step[_jpeg] and ofk_stream_step_fused[_jpeg]: the solve, the feasibility and legacy keep rules, the robust solve and its
+ * drop, record field 13, the track update and ofk_stream_last_points all see the gated status.  Invalid settings (unknown mode;
+ * fb_thr not finite or <= 0 with a mode other than OFK_FB_OFF; fb_level < -1 or above the context's max_level; err_max negative or
+ * not finite) return OFK_E_INVALID and leave the previous setting in place.
+ * ofk_track_gate_download: fb2 [batch][stride] f32, back_pts [batch][stride][2] f32, back_status [batch][stride] u8 (the first
+ * min(stride, max_pts) of every row; zeros when the latest run had the err cap alone) and stats [batch][4] i32 of the latest run /
+ * step with a gate on; any may be NULL; OFK_E_INVALID before such a run.  `batch` here is that run's own (the resident pairs, the
+ * streams, or the batch of the latest gated ofk_lk_pyr_fb): the call writes that many rows, so size the buffers for it, or for the
+ * context's max_batch.
+ * ofk_lk_pyr_fb = ofk_lk_pyr_ex plus the gates as a stage entry on host buffers: status is the gated one; back_pts, back_status and
+ * fb2 ([batch][pts_stride]..., nullable) are written only when fb_mode != OFK_FB_OFF.  g == NULL: no gate (ofk_lk_pyr_ex); any other
+ * g is held to ofk_set_track_gate's rules, one that switches nothing on included, before any launch or allocation.
+ * OFK_LK_GET_MIN_EIGENVALS with err_max != 0 is refused: err is no residual then. */
+#define OFK_FB_OFF     0
+#define OFK_FB_PLAIN   1   /* backward search starts at the forward result (cv2 called twice) */
+#define OFK_FB_SEEDED  2   /* backward search starts at the ORIGINAL point (OFK_LK_USE_INITIAL_FLOW) */
+typedef struct ofk_track_gate {
+    int    fb_mode;     /* OFK_FB_* */
+    double fb_thr;      /* pixels, > 0 and finite when fb_mode != OFK_FB_OFF */
+    int    fb_level;    /* maxLevel of the backward pass; -1 = the forward pass's; effective value min(fb_level, forward maxLevel) */
+    double err_max;     /* 0 = off; else status also needs err <= (float)err_max */
+} ofk_track_gate;
+int ofk_set_track_gate(ofk_ctx *ctx, const ofk_track_gate *g);
+int ofk_get_track_gate(const ofk_ctx *ctx, ofk_track_gate *g);
+int ofk_track_gate_download(ofk_ctx *ctx, float *fb2, float *back_pts, uint8_t *back_status, int stride, int *stats);
+int ofk_lk_pyr_fb(ofk_ctx *ctx, const uint8_t *prev, const uint8_t *next, int batch, int h, int w, const float *prev_pts,
+                  const int *counts, int pts_stride, int win, int max_level, int max_count, double eps, double min_eig_thr,
+                  const float *init_pts, int flags, float *next_pts, uint8_t *status, float *err, const ofk_track_gate *g,
+                  float *back_pts, uint8_t *back_status, float *fb2);
+
 /* optical_fusion.call_imu — node:61-89, batched over independent IMU streams, one message each.
  * state [batch][OFK_IMU_STATE]: vel[3], old_time, time_zero, first(0/1), rotation[9], normal[3], ang[3], ang_err[3]
  * msg   [batch][OFK_IMU_MSG]  : secs, nsecs, qx,qy,qz,qw, wx,wy,wz, cov0,cov4,cov8, ax,ay,az */
