@@ -1,7 +1,8 @@
 // k_jpeg.hip — baseline JPEG -> BGR8 on the device: the ingest in front of the hot path (the reference decodes
 // every sensor_msgs/CompressedImage with cv_bridge.compressed_imgmsg_to_cv2 = cv::imdecode = libjpeg,
 // velocity_measurment_node.py:112).  Output is bit-identical to libjpeg's default decompressor (ISLOW integer IDCT, "fancy"
-// triangle chroma upsampling, 16-bit fixed-point YCbCr->RGB).  The host parses the marker segments, packs the tables and takes the
+// triangle chroma upsampling - plain replication where the subsampled plane is one or two samples wide, libjpeg's own choice -,
+// 16-bit fixed-point YCbCr->RGB).  The host parses the marker segments, packs the tables and takes the
 // byte stuffing out of the entropy segments while it copies them (jdestuff: memchr + memcpy); entropy decoding, IDCT, upsampling
 // and colour conversion run on the GPU.
 //
@@ -9,14 +10,21 @@
 // Weissenberger & Schmidt, "Massively parallel Huffman decoding on GPUs", ICPP 2018, and their 2021 JPEG follow-up): the entropy
 // segment is cut into chunks of `jch` bytes, one decoder thread per chunk.  A decoder that starts at a wrong bit position / block
 // position produces garbage for a while but, because Huffman codes are prefix codes, falls into step with the true symbol sequence
-// after a few dozen symbols with overwhelming probability.
+// after a few dozen symbols - on textured content.  On periodic or flat content (stripes, a test card, a lens cap, saturated sky) it
+// falls into a stable WRONG cycle instead and never meets the truth: see the worst case below.
 //   1. k_jpeg_sync, iteration 0: every thread decodes its chunk from a guessed state (chunk start, block start) and publishes the
 //      state in which it crossed into the next chunk; iteration n > 0: every thread whose predecessor published a different state
 //      than the one it started from last time decodes its chunk again from that state.  Chunk 0 starts from the true state, so the
-//      truth advances at least one chunk per iteration; in practice half of the chunks agree after two iterations and the rest
-//      after four to six.  An iteration in which no thread changed its published state is a fixed point, and a fixed point that
-//      starts from the true state is the true decode (induction over the chunks) — the result never depends on the probabilistic
-//      argument, only the run time does.
+//      truth advances at least one chunk per iteration; on textured frames half of the chunks agree after two iterations and the
+//      rest after four to eleven.  An iteration in which no thread changed its published state is a fixed point, and a fixed point
+//      that starts from the true state is the true decode (induction over the chunks) — the result never depends on the
+//      probabilistic argument, only the run time does.
+//      Worst case: ONE chunk per iteration, as many iterations as the image has chunks.  tests/jpeg_sync_model.py (a Python
+//      restatement of these passes) at 64-byte chunks: vertical stripes of period 8, 4:4:4, 72x320: 66 chunks, 65 passes; 240x320:
+//      218 / 217; flat black 480x640 4:2:0: 76 / 76; flat black 1080p 4:2:0: 511 / 511; for comparison 240x320 noise: 1674 chunks,
+//      12 passes.  The host loop (jdecode_staged) is built for it - JMAX_ITERS flag slots, the last one cleared and reused by every
+//      pass from JMAX_ITERS on - and tests/test_gpu_jpeg_edges.py decodes such streams; ofk_jpeg_last_iterations reports the passes
+//      a decode queued.  What such a frame costs in time has not been measured on the device.
 //   2. k_jpeg_scan: exclusive prefix sum of the blocks completed per chunk = index of the block a chunk starts in.
 //   3. k_jpeg_write: every thread decodes its chunk once more from its (now true) entry state and stores the coefficients
 //      (k_jpeg_zero_heads zeroes the few blocks that more than one thread writes).
@@ -584,9 +592,19 @@ __device__ inline int jclamp8(int x) { return x < 0 ? 0 : x > 255 ? 255 : x; }
 // general formula (3 v + neighbour + r) >> s with the neighbour replaced by the column: the left neighbour of column 0 and the right
 // one of the group's last column come in replicated by the clamped loads (cl, cr); only where the image's last column sits INSIDE
 // a group of four (cw not a multiple of four: one thread per row) the columns behind it are patched.  No select per output.
+// NARROW: a subsampled plane of one or two samples per row.  libjpeg takes the fancy routines only for downsampled_width > 2
+// (jdsample.c jinit_upsampler) and replicates otherwise (h2v1_upsample / h2v2_upsample: no filter in either direction) - frames of up
+// to four pixels across, an instantiation of their own so that the code every other frame runs does not know about them.
 #define JCHROMA_EDGE() do { if (cx0 + 3 > cw - 1) { for (int k = 1; k < 4; ++k) if (cx0 + k > cw - 1) t[k + 1] = t[k]; } } while (0)
+template <bool NARROW>
 __device__ inline void jchroma8(const uint8_t *__restrict__ pl, int pitch, int cw, int ch, int hmax, int vmax, int x0, int y, int *out)
 {   // (offsets inside a plane are 32-bit: the plane base is uniform, so the loads take it from scalar registers)
+    if (NARROW) {                                                 // hmax == 2, x0 == 0; the plane's rows are whole blocks: 8 bytes are there
+        const uint32_t m = *(const uint32_t *)(pl + (unsigned)((vmax == 2 ? y >> 1 : y) * pitch));
+#pragma unroll
+        for (int k = 0; k < 8; ++k) out[k] = (m >> (8 * (k >> 1))) & 255;
+        return;
+    }
     if (hmax == 1) {
         const uint2 v = *(const uint2 *)(pl + (unsigned)(y * pitch + x0));
 #pragma unroll
@@ -633,6 +651,7 @@ __device__ inline void jchroma8(const uint8_t *__restrict__ pl, int pitch, int c
 // as_gray: bgr / bgr2 are gray planes (rows of g.w bytes) and receive what k_gray_bgr8 (k_image.hip: cv2.cvtColor BGR2GRAY) makes of the
 // pixel - the pipeline's first stage fused into the decoder's last, the BGR frame (three times the bytes, written here and read there)
 // never exists.
+template <bool NARROW>
 __device__ inline void jcolor8(const jpeg_geom &g, const uint8_t *__restrict__ pl, uint2 y8, int b, int x0, int y, uint8_t *__restrict__ bgr,
                                uint8_t *__restrict__ bgr2, int split, size_t bgr_stride, int as_gray)
 {
@@ -644,8 +663,8 @@ __device__ inline void jcolor8(const jpeg_geom &g, const uint8_t *__restrict__ p
     } else {
         const int cw = (g.w + g.hmax - 1) >> (g.hmax - 1), ch = (g.h + g.vmax - 1) >> (g.vmax - 1);    // sampling factors are 1 or 2
         int cb[8], cr[8];
-        jchroma8(pl + g.plane_off[1], g.pw[1], cw, ch, g.hmax, g.vmax, x0, y, cb);
-        jchroma8(pl + g.plane_off[2], g.pw[2], cw, ch, g.hmax, g.vmax, x0, y, cr);
+        jchroma8<NARROW>(pl + g.plane_off[1], g.pw[1], cw, ch, g.hmax, g.vmax, x0, y, cb);
+        jchroma8<NARROW>(pl + g.plane_off[2], g.pw[2], cw, ch, g.hmax, g.vmax, x0, y, cr);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int Y = (int)(((k < 4 ? y8.x : y8.y) >> (8 * (k & 3))) & 255);
@@ -693,7 +712,7 @@ __device__ inline void jcolor8(const jpeg_geom &g, const uint8_t *__restrict__ p
 //                 take eight pixels each: chroma from the planes, colour conversion, BGR or gray out (jcolor8).  The Y plane never
 //                 exists: its 8-byte row stores from lanes that sit in different image rows were a quarter of the IDCT's time, and the
 //                 colour pass read it back (k_jpeg_idct + k_jpeg_color 2.65 -> 0.39 + 1.71 ms per 512 frames).
-template <bool LUMA>
+template <bool LUMA, bool NARROW = false>
 __global__ __launch_bounds__(256) void k_jpeg_idct(const jpeg_tab *__restrict__ tabs, jpeg_geom g, const int16_t *__restrict__ coef,
                                                    const int16_t *__restrict__ dcarr, uint8_t *__restrict__ planes, uint8_t *__restrict__ bgr,
                                                    uint8_t *__restrict__ bgr2, int split, size_t bgr_stride, int as_gray)
@@ -762,7 +781,7 @@ __global__ __launch_bounds__(256) void k_jpeg_idct(const jpeg_tab *__restrict__ 
             __syncthreads();
             const int r = threadIdx.x >> (5 - vsl), xg = threadIdx.x & ((32 >> vsl) - 1);
             const int y = (mrow << (3 + vsl)) + r, x0 = ((l0 >> sh) * hs + xg) * 8;
-            if (x0 < g.w && y < g.h) jcolor8(g, pl, ytile[r][xg], b, x0, y, bgr, bgr2, split, bgr_stride, as_gray);
+            if (x0 < g.w && y < g.h) jcolor8<NARROW>(g, pl, ytile[r][xg], b, x0, y, bgr, bgr2, split, bgr_stride, as_gray);
         }
     }
 }
@@ -1011,6 +1030,7 @@ struct jstage {
 struct jstages {
     jstage slot[2]; hipStream_t copy;
     hipStream_t dec;                          // the decoder passes of a double-buffered frame-pair ingest: beside the pipeline run of the batch before
+    int last_iters;                           // synchronisation passes behind the first that the latest decode queued (ofk_jpeg_last_iterations)
     int *hmap, *hmap_dev; size_t hmap_ints;   // host memory the device writes its convergence flags / end-of-stream records into (pinned,
                                               // mapped): the host reads them after a stream wait, no copy engine in the round trip - a D2H
                                               // copy queues behind the other slot's 200 MB H2D transfer and stalls the decoder for its length
@@ -1190,6 +1210,7 @@ static int jdecode_staged(ofk_ctx *c, int slot, uint8_t *dst, uint8_t *dst2, int
     if (!js || slot < 0 || slot > 1 || !js->slot[slot].valid) return ofk_fail(c, OFK_E_INVALID, "ofk_jpeg: slot %d holds no staged streams (ofk_jpeg_stage)", slot);
     jstage &J = js->slot[slot];
     J.valid = 0;                                                 // a slot is decoded once
+    js->last_iters = 0;
     const jpeg_geom g = J.g;
     const int batch = J.batch, nch_max = J.nch_max;
     if (dst && (size_t)g.w * g.h > dst_capacity_px) return ofk_fail(c, OFK_E_INVALID, "ofk_jpeg: %dx%d frames exceed the destination", g.w, g.h);
@@ -1249,6 +1270,7 @@ static int jdecode_staged(ofk_ctx *c, int slot, uint8_t *dst, uint8_t *dst2, int
         }
         hipLaunchKernelGGL(k_jpeg_ints_to_host, dim3(1), dim3(64), 0, st, flags, js->hmap_dev, JMAX_ITERS);
         OFK_HIP(c, hipStreamSynchronize(st));
+        js->last_iters = iter;
         for (int k = first; k <= iter; ++k)
             if (!hflags[k < JMAX_ITERS ? k : JMAX_ITERS - 1]) converged = true;
         if (!converged && iter > nch_max + 2) return ofk_fail(c, OFK_E_INVALID, "ofk_jpeg: entropy decoders did not converge");
@@ -1258,7 +1280,9 @@ static int jdecode_staged(ofk_ctx *c, int slot, uint8_t *dst, uint8_t *dst2, int
     hipLaunchKernelGGL(write_pass, dim3((nch_max + JTPW - 1) / JTPW, batch), dim3(JTPW), 0, st, dt, dent, drst, g, nch_max, state, base, coef, dcarr, endinfo);
     hipLaunchKernelGGL(k_jpeg_dc, dim3(batch, g.ncomp), dim3(1024), 0, st, dt, g, dcarr);
     if (g.ncomp > 1) hipLaunchKernelGGL(k_jpeg_idct<false>, dim3(g.mcuy, batch), dim3(256), 0, st, dt, g, coef, dcarr, planes, dst, dst2, split, dst_stride, as_gray);
-    hipLaunchKernelGGL(k_jpeg_idct<true>, dim3(g.mcuy, batch), dim3(256), 0, st, dt, g, coef, dcarr, planes, dst, dst2, split, dst_stride, as_gray);
+    // (a subsampled chroma plane of one or two samples per row - frames of up to four pixels across - is replicated, not filtered: jchroma8)
+    auto luma_pass = g.hmax == 2 && (g.w + 1) / 2 <= 2 ? k_jpeg_idct<true, true> : k_jpeg_idct<true, false>;
+    hipLaunchKernelGGL(luma_pass, dim3(g.mcuy, batch), dim3(256), 0, st, dt, g, coef, dcarr, planes, dst, dst2, split, dst_stride, as_gray);
     hipLaunchKernelGGL(k_jpeg_ints_to_host, dim3(4), dim3(256), 0, st, endinfo, js->hmap_dev + JMAX_ITERS, 2 * batch);
     hipError_t e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipGetLastError();
@@ -1288,6 +1312,12 @@ const char *ofk_jpeg_slot_error(const ofk_ctx *c, int slot)
 {
     const jstages *js = c ? (const jstages *)c->jstage : nullptr;
     return (js && slot >= 0 && slot <= 1) ? js->slot[slot].err : "";
+}
+
+extern "C" int ofk_jpeg_last_iterations(const ofk_ctx *c)
+{
+    const jstages *js = c ? (const jstages *)c->jstage : nullptr;
+    return js ? js->last_iters : 0;
 }
 
 int ofk_jpeg_decode_staged_pairs(ofk_ctx *c, int slot, uint8_t *dst_prev, uint8_t *dst_next, size_t dst_stride, size_t dst_capacity_px, int *batch_out,

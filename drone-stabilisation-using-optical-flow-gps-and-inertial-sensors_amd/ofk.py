@@ -28,7 +28,7 @@ SYMBOLS = (
     "ofk_good_features", "ofk_lk_pyr", "ofk_lk_pyr_ex", "ofk_predict_points", "ofk_set_lk_seed", "ofk_get_lk_seed", "ofk_flow_model", "ofk_feasibility", "ofk_velocity_solve", "ofk_imu_propagate",
     "ofk_set_robust", "ofk_get_robust", "ofk_robust_download", "ofk_velocity_solve_robust", "ofk_robust_pairs",
     "ofk_set_track_gate", "ofk_get_track_gate", "ofk_track_gate_download", "ofk_lk_pyr_fb",
-    "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_pairs_set_sensors",
+    "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
     "ofk_stream_begin_jpeg", "ofk_stream_step_jpeg",
     "ofk_set_streams", "ofk_set_overlap", "ofk_set_tuning", "ofk_get_tuning", "ofk_mark", "ofk_mark_wait", "ofk_profile_enable", "ofk_profile_read", "ofk_resident_pyramid",
@@ -211,6 +211,7 @@ def load_library():
         L.ofk_jpeg_info.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
         L.ofk_jpeg_destuff.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), i, C.POINTER(i)]
         L.ofk_jpeg_decode_bgr8.argtypes = [vp, vp, vp, i, vp]
+        L.ofk_jpeg_last_iterations.argtypes = [vp]
         L.ofk_pairs_set_sensors.argtypes = [vp, vp, i]
         L.ofk_pairs_run.argtypes = [vp, C.POINTER(Params)]
         L.ofk_pairs_download.argtypes = [vp, vp, vp, vp, vp, vp, vp]
@@ -837,6 +838,12 @@ class Context:
         with self._lock:
             self._ck(self._L.ofk_jpeg_decode_bgr8(self._h, ptrs, sizes, len(keep), _p(out)))
         return out
+
+    def jpeg_last_iterations(self):
+        """Synchronisation passes the latest JPEG decode of this context queued behind the first (ofk_jpeg_last_iterations): 0 before any
+        decode and for single-chunk streams."""
+        with self._lock:
+            return int(self._L.ofk_jpeg_last_iterations(self._h))
 
     def pairs_set_sensors(self, sensors):
         s = _arr(sensors, np.float64).reshape(-1, SENSOR_DOUBLES)

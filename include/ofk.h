@@ -490,7 +490,7 @@ int ofk_stream_step_fused_jpeg(ofk_ctx *ctx, const uint8_t *const *jpeg, const s
  * without restart intervals.
  * ofk_jpeg_decode_bgr8: decodes `batch` streams of equal size and sampling on the device into bgr [batch][h][w][3] (host; gray
  * streams are replicated over the three channels like cv2.IMREAD_COLOR).  Bit-identical to libjpeg's default decompressor (ISLOW
- * IDCT, fancy upsampling) - what cv::imdecode returns.  Entropy decoding runs on the GPU too (self-synchronising chunked Huffman
+ * IDCT, fancy upsampling - replication where a chroma plane is one or two samples wide, as libjpeg chooses) - what cv::imdecode returns.  Entropy decoding runs on the GPU too (self-synchronising chunked Huffman
  * decoders); truncated or corrupt entropy data is an error, not a partially grey picture. */
 int ofk_jpeg_info(const uint8_t *jpeg, size_t nbytes, int *h, int *w, int *components);
 /* ofk_jpeg_destuff (host only; no context, no GPU): the entropy-coded segment of the stream's scan as the device decoders read it -
@@ -501,6 +501,12 @@ int ofk_jpeg_info(const uint8_t *jpeg, size_t nbytes, int *h, int *w, int *compo
  * (ofk_jpeg_stage, ofk_pairs_upload_jpeg ...) runs the same routine; this entry exists so that it can be tested without a GPU. */
 int ofk_jpeg_destuff(const uint8_t *jpeg, size_t nbytes, uint8_t *out, size_t out_capacity, size_t *out_len, uint32_t *rst, int rst_capacity, int *nrst);
 int ofk_jpeg_decode_bgr8(ofk_ctx *ctx, const uint8_t *const *jpeg, const size_t *nbytes, int batch, uint8_t *bgr);
+/* ofk_jpeg_last_iterations: how many synchronisation passes the context's latest decode (any entry that takes JPEG streams) queued
+ * behind the first one, in which every chunk decoder starts from its guess.  The host queues them in bursts (seven, then four at a
+ * time) and looks at the convergence flags in between, so this is the fixed point's pass number rounded up to the end of its burst.
+ * 0 before any decode and for a batch whose streams are a single chunk each (nothing to synchronise).  Read-only: for tests and
+ * measurements, it has no effect on any result.  Textured frames take 7 to 15; flat or periodic content one pass per chunk. */
+int ofk_jpeg_last_iterations(const ofk_ctx *ctx);
 
 /* ------------------------------------------------- multi-GPU exchange: RCCL over xGMI, no PyTorch
  * The reference has no distributed code; frame pairs (and Monte-Carlo trials) are independent, so each rank (one process per

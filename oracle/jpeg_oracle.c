@@ -7,7 +7,8 @@
  * here from its published form with libjpeg's default decompression parameters (the ones cv::imdecode uses):
  *   - sequential Huffman entropy decoding              (ITU-T T.81 Annex F.2.2; libjpeg jdhuff.c decode_mcu)
  *   - dequantisation + "ISLOW" integer inverse DCT      (libjpeg jidctint.c jpeg_idct_islow: CONST_BITS 13, PASS1_BITS 2)
- *   - "fancy" (triangle filter) chroma upsampling       (libjpeg jdsample.c h2v1_fancy_upsample / h2v2_fancy_upsample)
+ *   - "fancy" (triangle filter) chroma upsampling       (libjpeg jdsample.c h2v1_fancy_upsample / h2v2_fancy_upsample; chroma planes
+ *     of one or two samples per row are replicated instead, as jinit_upsampler chooses: tests/golden/jpeg_edges.npz)
  *   - YCbCr -> RGB with 16-bit fixed-point tables       (libjpeg jdcolor.c build_ycc_rgb_table / ycc_rgb_convert)
  * Pinned by tests/golden/jpeg_golden.npz: JPEG byte streams with the pixels libjpeg-turbo returned for them (generated through
  * Pillow, which drives the same library with the same defaults; tests/golden/make_golden_jpeg.py).
@@ -298,6 +299,12 @@ int orc_jpeg_decode(const uint8_t *d, size_t n, int16_t *coef_out, uint8_t *bgr)
                 const uint8_t *src = pl[c]; const int sp = pw[c];
                 if (j.hmax == 1) {
                     for (int y = 0; y < j.h; ++y) memcpy(up[c - 1] + (size_t)y * uw, src + (size_t)y * sp, j.w);
+                } else if (cw <= 2) {                          /* jdsample.c jinit_upsampler: the fancy routines need downsampled_width > 2;
+                                                                  a narrower plane takes h2v1_upsample / h2v2_upsample = replication */
+                    for (int y = 0; y < j.h; ++y) {
+                        const uint8_t *in = src + (size_t)(y / j.vmax) * sp; uint8_t *o = up[c - 1] + (size_t)y * uw;
+                        for (int x = 0; x < cw; ++x) o[2 * x] = o[2 * x + 1] = in[x];
+                    }
                 } else if (j.vmax == 1) {                      /* h2v1_fancy_upsample */
                     for (int y = 0; y < j.h; ++y) {
                         const uint8_t *in = src + (size_t)y * sp; uint8_t *o = up[c - 1] + (size_t)y * uw;

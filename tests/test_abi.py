@@ -63,3 +63,12 @@ def test_no_gpu_fails_loudly(built, ofk):
         pytest.skip("a GPU is present")
     with pytest.raises(ofk.OfkError):
         ofk.Context(0, 640, 480, 1, 64, 3)
+
+
+def test_jpeg_pass_counter_is_declared_bound_and_null_safe(built, ofk):
+    """ofk_jpeg_last_iterations: in the header, in the binding, exported; a read-only query that answers 0 where no decode has run -
+    a NULL context included (no GPU needed for that)."""
+    assert "ofk_jpeg_last_iterations" in header_symbols() and "ofk_jpeg_last_iterations" in ofk.SYMBOLS
+    lib = ofk.load_library()
+    assert lib.ofk_jpeg_last_iterations(None) == 0
+    assert callable(ofk.Context.jpeg_last_iterations)

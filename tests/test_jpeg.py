@@ -30,6 +30,31 @@ def test_oracle_reproduces_libjpeg_pixels(gold):
         assert np.array_equal(got, gold[f"bgr_{n}"]), n
 
 
+def test_oracle_reproduces_libjpeg_pixels_at_the_edges():
+    """tests/golden/jpeg_edges.npz: slow-synchronising streams (stripes, flat frames, fitted one-bit tables, a restart variant) and
+    frames of 1x1 ... 24x40 pixels in every sampling, with the pixels libjpeg returned.  Where a subsampled chroma plane is one or
+    two samples wide libjpeg replicates it instead of filtering (jdsample.c jinit_upsampler); the oracle must make the same choice:
+    3x3 4:2:2 and 4:2:0, 33x1 and 31x2 4:2:0 are the streams of the file on which the triangle filter gives other pixels."""
+    from jpeg_edges_cases import Edges, TINY_SIZES, TINY_MODES, TINY_CONTENTS, narrow_chroma
+    e = Edges()
+    tiny = [f"tiny_{h}x{w}_{m}_{c}" for h, w in TINY_SIZES for m in TINY_MODES for c in TINY_CONTENTS]
+    assert len(tiny) == 17 * 4 * 3 and set(tiny) <= set(e.names)
+    assert sum(narrow_chroma(h, w, m) for h, w in TINY_SIZES for m in TINY_MODES) == 12      # the six sizes of width 1 .. 3, in 4:2:2 and 4:2:0
+    assert {str(n) for n in e.conditions} <= set(e.names) and "libjpeg-turbo" in e.libjpeg
+    bad = [n for n in e.names if jo.decode(e.jpg(n)).shape != e.bgr(n).shape or not np.array_equal(jo.decode(e.jpg(n)), e.bgr(n))]
+    assert not bad, bad
+
+
+def test_tiny_fixtures_hold_single_chunk_batches(pkg, ofk):
+    """(host only) every stream of the 1x1 batches is shorter than one 64-byte chunk, those of the 24x40 batches are longer: the GPU
+    test of the tiny frames meets both the single-chunk path of the host loop and the other one."""
+    from jpeg_edges_cases import Edges, TINY_MODES
+    e = Edges()
+    for mode in TINY_MODES:
+        assert all(len(ofk.jpeg_destuff(e.jpg(n))[0]) < 64 for n in e.tiny(1, 1, mode)), mode
+        assert any(len(ofk.jpeg_destuff(e.jpg(n))[0]) >= 64 for n in e.tiny(24, 40, mode)), mode
+
+
 def test_oracle_refuses_progressive(gold):
     with pytest.raises(ValueError):
         jo.decode(gold["jpg_progressive"].tobytes())
