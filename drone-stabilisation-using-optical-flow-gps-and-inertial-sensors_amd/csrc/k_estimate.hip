@@ -1059,6 +1059,9 @@ void ofk_launch_hist_overlap(hipStream_t s, const double *d1, int n1, const doub
 // of_library.py:270-286 (calc_height), :53-75 + :100-114 (convert_to_of inside dynamic_immobile), :291-317 (eval_ft), batched
 // over track sets: one block per set.  The reference's functions carry undefined names; the formulas are the
 // ones they spell out, restated in oracle/estimation_oracle.py.  f64 throughout, same operation order as the oracle.
+// eval_ft's ranges are np.amin / np.amax, which return NaN when the set holds one (level flight: e v_z / u_x = 0 / 0 for a
+// feature without flow on one axis), and the term is then zero for the whole set; fmin / fmax drop NaN, so each range
+// carries a "saw a NaN" flag that turns it into NaN.
 
 __global__ __launch_bounds__(256) void k_feature_eval(const double *__restrict__ pos, const double *__restrict__ pos_err,
                                                       const double *__restrict__ oldpos, const double *__restrict__ oldpos_err,
@@ -1076,6 +1079,7 @@ __global__ __launch_bounds__(256) void k_feature_eval(const double *__restrict__
     const double vex = vel_err[3 * b], vey = vel_err[3 * b + 1], vez = vel_err[3 * b + 2];
     double hmin = INFINITY, hmax = -INFINITY, emin = INFINITY, emax = -INFINITY, pmin = INFINITY, pmax = -INFINITY, qmax = -INFINITY;
     bool bad = false;
+    int hnan = 0, enan = 0, pnan = 0, qnan = 0;
     for (int i = tid; i < n; i += 256) {
         const double px = pos[2 * (o + i)], py = pos[2 * (o + i) + 1], e = pos_err[o + i];
         const double ox = oldpos[2 * (o + i)], oy = oldpos[2 * (o + i) + 1], oe = oldpos_err[o + i];
@@ -1100,11 +1104,16 @@ __global__ __launch_bounds__(256) void k_feature_eval(const double *__restrict__
         const double q = (px - tx) * (px - tx) + (py - ty) * (py - ty);
         hmin = fmin(hmin, h); hmax = fmax(hmax, h); emin = fmin(emin, he); emax = fmax(emax, he);
         pmin = fmin(pmin, e); pmax = fmax(pmax, e); qmax = fmax(qmax, q);
+        hnan |= h != h; enan |= he != he; pnan |= e != e; qnan |= q != q;
     }
     hmin = block_minmax(hmin, false, s_red); hmax = block_minmax(hmax, true, s_red);
     emin = block_minmax(emin, false, s_red); emax = block_minmax(emax, true, s_red);
     pmin = block_minmax(pmin, false, s_red); pmax = block_minmax(pmax, true, s_red);
     qmax = block_minmax(qmax, true, s_red);
+    if (__syncthreads_or(hnan)) hmin = hmax = NAN;
+    if (__syncthreads_or(enan)) emin = emax = NAN;
+    if (__syncthreads_or(pnan)) pmin = pmax = NAN;
+    if (__syncthreads_or(qnan)) qmax = NAN;
     if (bad) atomicOr(flags + 1, 1);
     // eval_ft: weighted score of normalised height, height variance, centre distance and track error
     const double w0 = weight[0], w1 = weight[1], w2 = weight[2], w3 = weight[3];
@@ -1145,7 +1154,9 @@ void ofk_launch_feature_eval(hipStream_t s, const double *pos, const double *pos
 // ------------------------------------------------------------------------------------------------ plane-distance statistics
 // velocity_measurment_node:249-252 — d_sorted = np.sort(d); d_diff = consecutive differences; the commented line there marks a
 // split where a gap reaches the expected distance error (several ground planes in view).  One block per set: bitonic sort in
-// LDS (sets are padded with +inf to a power of two <= 4096), gaps, and the number of gaps >= d_exp_err.
+// LDS, gaps, and the number of gaps >= d_exp_err.  The order is np.sort's: NaN after +inf; sets are padded with NaN to a power
+// of two <= 4096, so the padding sorts behind every value of the set (a +inf in the data included) and only the count tells the
+// two apart.  A gap next to a NaN, or inf - inf, is NaN and is not counted.
 #define DSPLIT_MAX 4096
 __global__ __launch_bounds__(256) void k_d_split(const double *__restrict__ d, const int *__restrict__ counts, int stride, double d_exp_err,
                                                  double *__restrict__ sorted, double *__restrict__ diff, int *__restrict__ nsplit)
@@ -1156,7 +1167,7 @@ __global__ __launch_bounds__(256) void k_d_split(const double *__restrict__ d, c
     const int n = min(max(counts[b], 0), stride);
     int m = 1;
     while (m < n) m <<= 1;
-    for (int i = tid; i < m; i += 256) s[i] = i < n ? d[(size_t)b * stride + i] : INFINITY;
+    for (int i = tid; i < m; i += 256) s[i] = i < n ? d[(size_t)b * stride + i] : NAN;
     if (tid == 0) s_cnt = 0;
     __syncthreads();
     for (int k = 2; k <= m; k <<= 1)
@@ -1166,7 +1177,7 @@ __global__ __launch_bounds__(256) void k_d_split(const double *__restrict__ d, c
                 if (p > i) {
                     const double a = s[i], c = s[p];
                     const bool up = (i & k) == 0;
-                    if ((a > c) == up) { s[i] = c; s[p] = a; }
+                    if ((a > c || (a != a && c == c)) == up) { s[i] = c; s[p] = a; }
                 }
             }
             __syncthreads();
@@ -1199,7 +1210,7 @@ __device__ int nearest_sample(const double *__restrict__ ts, int n, double t, do
 {
     const int tid = threadIdx.x;
     double best = INFINITY;
-    int bi = 0x7fffffff;
+    int bi = 0;                                                 // np.argmin of nothing smaller than inf: never an index outside the log
     for (int i = tid; i < n; i += 256) {
         const double d = fabs(ts[i] - t);
         if (d < best) { best = d; bi = i; }                     // strict: the earliest of equal distances stays

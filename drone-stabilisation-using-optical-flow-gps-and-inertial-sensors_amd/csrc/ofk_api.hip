@@ -918,6 +918,12 @@ static int get(ofk_ctx *c, void *host, const void *dev, size_t bytes)
     OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
 }
+static bool all_finite(const double *a, size_t n)
+{
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(a[i])) return false;
+    return true;
+}
 static int est_begin(ofk_ctx *c, size_t bytes, Bump &bp)
 {
     if (!c) return OFK_E_INVALID;
@@ -1038,6 +1044,9 @@ extern "C" int ofk_associate_sensors(ofk_ctx *c, const double *t_img, int n_img,
 {
     if (!c || !t_img || !imu_t || !imu_quat || !imu_omega || !hgt_t || !hgt_range || !sensors || n_img < 1 || n_imu < 1 || n_hgt < 1)
         return ofk_fail(c, OFK_E_INVALID, "ofk_associate_sensors: bad argument (every log needs at least one sample)");
+    // np.argmin over distances that are all inf or NaN names no nearest sample: refused before anything is uploaded
+    if (!all_finite(t_img, n_img) || !all_finite(imu_t, n_imu) || !all_finite(hgt_t, n_hgt) || !all_finite(hgt_range, n_hgt))
+        return ofk_fail(c, OFK_E_INVALID, "ofk_associate_sensors: non-finite image time, sample time or range");
     Bump bp;
     TRY(est_begin(c, ((size_t)n_img * (1 + OFK_SENSOR_DOUBLES + 1) + (size_t)n_imu * 8 + (size_t)n_hgt * 2) * 8, bp));
     double *dt = bp.put(t_img, (size_t)n_img * 8), *dit = bp.put(imu_t, (size_t)n_imu * 8), *diq = bp.put(imu_quat, (size_t)n_imu * 32),
@@ -1198,6 +1207,8 @@ extern "C" int ofk_hist_overlap(ofk_ctx *c, const double *data1, int n1, const d
 {
     if (!c || !data1 || !data2 || !overlap || n1 < 1 || n2 < 1 || bins < 1 || bins > 1024)
         return ofk_fail(c, OFK_E_INVALID, "ofk_hist_overlap: bad argument (bins 1..1024, both samples non-empty)");
+    if (!all_finite(data1, n1) || !all_finite(data2, n2))        // np.histogram raises ValueError on a non-finite range
+        return ofk_fail(c, OFK_E_INVALID, "ofk_hist_overlap: non-finite sample");
     Bump bp;
     TRY(est_begin(c, ((size_t)n1 + n2) * 8 + 1024, bp));
     double *d1 = bp.put(data1, (size_t)n1 * 8), *d2 = bp.put(data2, (size_t)n2 * 8);

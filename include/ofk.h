@@ -262,6 +262,10 @@ int ofk_imu_propagate(ofk_ctx *ctx, double *state, const double *msg, int batch)
  * vel[b] +- vel_err[b]; immobile[i] = (observed - expected flow)^2 < var(observed) + var(expected) on both axes and neither old
  * coordinate equals dummy_value; score = w0 (1 - height_n) + w1 height_err_n + w2 (1 - centre_dist_n) + w3 pos_err_n with the
  * min/max normalisations of eval_ft; order = feature indices by ascending score (ties by index, NaN last; -1 past the count).
+ * NaN follows numpy: the ranges are np.amin / np.amax, so ONE NaN among a set's heights, height variances, centre distances or
+ * position errors makes that term zero for every feature of the set (level flight, v_z = 0: a feature without flow on one
+ * axis has height_err = 0/0; a stationary one whose two estimates are infinities of opposite sign has height = NaN), and the
+ * feature's own score is NaN where its own term is.  counts[b] is clamped to 0..stride; past it the outputs read 0 (order -1).
  * *bad_height is set non-zero when a height is not positive (where the reference raises ValueError).  pos, oldpos
  * [batch][stride][2] in pixels; pos_err, oldpos_err [batch][stride]; vel, vel_err [batch][3]; weight [4]. */
 int ofk_feature_eval(ofk_ctx *ctx, const double *pos, const double *pos_err, const double *oldpos, const double *oldpos_err,
@@ -271,7 +275,9 @@ int ofk_feature_eval(ofk_ctx *ctx, const double *pos, const double *pos_err, con
 
 /* velocity_measurment_node:249-252 — statistics of the per-feature plane distances d_i that r_tilde returns (ofk_feasibility):
  * sorted[b] = np.sort(d[b][:counts[b]]), diff[b][i] = sorted[i+1] - sorted[i], nsplit[b] = number of gaps >= d_exp_err (the
- * split the node's commented line describes: several ground planes in view).  Arrays [batch][stride], stride <= 4096. */
+ * split the node's commented line describes: several ground planes in view).  Arrays [batch][stride], stride <= 4096.
+ * The order is np.sort's: -inf first, +inf after every finite value, NaN last; a gap next to a NaN, or inf - inf, is NaN
+ * and is not counted.  counts[b] is clamped to 0..stride; sorted and diff read 0 past the count, diff[b][counts[b]-1] too. */
 int ofk_d_split(ofk_ctx *ctx, const double *d, const int *counts, int batch, int stride, double d_exp_err, double *sorted,
                 double *diff, int *nsplit);
 
@@ -279,7 +285,8 @@ int ofk_d_split(ofk_ctx *ctx, const double *d, const int *counts, int batch, int
  * them: float(secs - secs0) + float(nsecs)/1e9) the nearest IMU and range samples (np.argmin(np.abs(values - t)): the first
  * minimum), then d = range, R from the IMU quaternion (x,y,z,w), normal = R e_z, omega = angular velocity.  Fills fields
  * 0-15 of sensors[k] (see OFK_SENSOR_DOUBLES below; the other fields keep their values) and, when not NULL, the chosen
- * indices.  imu_quat [n_imu][4], imu_omega [n_imu][3]. */
+ * indices.  imu_quat [n_imu][4], imu_omega [n_imu][3].  A non-finite image time, sample time or range is refused with
+ * OFK_E_INVALID before anything is uploaded (no sample is nearest to it). */
 int ofk_associate_sensors(ofk_ctx *ctx, const double *t_img, int n_img, const double *imu_t, const double *imu_quat,
                           const double *imu_omega, int n_imu, const double *hgt_t, const double *hgt_range, int n_hgt,
                           double *sensors, int *imu_index, int *hgt_index);
@@ -328,7 +335,8 @@ int ofk_feas_simulation(ofk_ctx *ctx, const double *truth, const double *sig, co
                         const double *z, int trials, double *mean, double *per_trial, double *v_obs);
 
 /* overlap(data1, data2) - simulation.py:124-136: histogram both samples over the `bins` (reference: 100, at most 1024) equal
- * bins spanning their joint range (np.histogram's edges and bin rule) and sum the bin-wise minima. */
+ * bins spanning their joint range (np.histogram's edges and bin rule) and sum the bin-wise minima.  A non-finite sample is
+ * refused with OFK_E_INVALID (np.histogram raises ValueError on a non-finite range). */
 int ofk_hist_overlap(ofk_ctx *ctx, const double *data1, int n1, const double *data2, int n2, int bins, int *overlap);
 
 /* ------------------------------------------------- resident frame-pair pipeline (the benchmarked path) */

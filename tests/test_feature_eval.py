@@ -24,6 +24,32 @@ def test_oracle_known_answer():
     assert list(order) == [0, 1] and score[0] == 0.0 and score[1] == 1.0       # weight on height only: the highest feature scores 0
 
 
+def test_oracle_stationary_feature_in_level_flight():
+    """v_z = 0 and a feature that did not move: both height estimates are +inf (200 / 0, 100 / 0), its variance holds e v_z / u =
+    0 / 0 = NaN.  np.amin / np.amax of the variances are NaN, so that term is zero for the WHOLE set; the height range is inf, so
+    the finite heights normalise to 0 and the infinite one to inf / inf = NaN.  Weights (1, 1, 0, 0.5):
+        score = 1 - (0, 0, NaN) + 0 + 0.5 * ((0.3, 0.1, 0.2) - 0.1) / 0.2 = (1.5, 1.0, NaN)  ->  order 1, 0, 2.
+    A range taken over the non-NaN variances (70.3125, 2000) would give (1.5, 2.0, NaN) and the order 0, 1, 2."""
+    pos = np.array([[200.0, 140.0], [100.0, 100.0], [150.0, 110.0]]); old = np.array([[196.0, 138.0], [99.0, 99.5], [150.0, 110.0]])
+    h, he, imm, score, order = eo.feature_eval(pos, [0.3, 0.1, 0.2], old, [0.1, 0.1, 0.1], [2.0, 1.0, 0.0], [0.0, 0.0, 0.0], 100.0, -1.0,
+                                               (320, 240), [1.0, 1.0, 0.0, 0.5])
+    assert np.array_equal(h, [50.0, 200.0, np.inf])
+    np.testing.assert_allclose(he[:2], [(200 * 0.3 / 16) ** 2 + (100 * 0.3 / 4) ** 2, (200 * 0.1 / 1) ** 2 + (100 * 0.1 / 0.25) ** 2])
+    assert np.isnan(he[2]) and not imm[2]                                      # its expected-flow variance is NaN: no comparison holds
+    np.testing.assert_allclose(score[:2], [1.5, 1.0], rtol=1e-15)
+    assert np.isnan(score[2]) and list(order) == [1, 0, 2]
+
+
+def test_oracle_d_split_with_nan_and_infinities():
+    """np.sort puts NaN after +inf; the gap next to it is NaN and is not counted: gaps 0, 1, 0, 2, inf, NaN -> 3 reach 0.5."""
+    with np.errstate(invalid="ignore"):
+        s, g, n = eo.d_split([3.0, np.nan, 1.0, -0.0, 0.0, np.inf, 1.0], 0.5)
+        s2, g2, n2 = eo.d_split([np.inf, -np.inf, np.inf, 2.0], 0.0)           # inf - inf is NaN too
+    assert np.array_equal(s, [0.0, 0.0, 1.0, 1.0, 3.0, np.inf, np.nan], equal_nan=True)      # -0.0 == 0.0: their order is not promised
+    assert np.array_equal(g, [0.0, 1.0, 0.0, 2.0, np.inf, np.nan], equal_nan=True) and n == 3
+    assert np.array_equal(s2, [-np.inf, 2.0, np.inf, np.inf]) and np.array_equal(g2, [np.inf, np.inf, np.nan], equal_nan=True) and n2 == 2
+
+
 def _g12():
     import os
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_association.npz"))

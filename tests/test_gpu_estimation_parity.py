@@ -301,6 +301,13 @@ def test_hist_overlap_edges_and_degenerate_samples(gpu_ctx, feas_golden):
     for n1, n2, bins in ((1, 1, 100), (1000, 3, 7), (257, 4096, 1024), (50, 50, 1)):
         a, b = rng.normal(0, 1, n1), rng.normal(0.3, 2, n2)
         assert gpu_ctx.hist_overlap(a, b, bins) == eo.overlap(a, b, bins), (n1, n2, bins)
+    # integer-valued samples over 0 .. 10: with 10, 5, 2 or 20 bins every edge is exact (a multiple of 0.5), so the values sit ON
+    # the edges: an inner edge belongs to the bin on its right, the maximum to the last bin
+    a = np.concatenate([[0.0, 10.0], rng.integers(0, 11, 400)]).astype(np.float64); b = rng.integers(2, 11, 300).astype(np.float64)
+    for bins in (10, 5, 2, 20):
+        edges = np.histogram(np.hstack((a, b)), bins=bins)[1]
+        assert np.array_equal(edges, np.arange(bins + 1) * (10.0 / bins)) and np.isin(np.arange(11.0), a).all() and (a == 10.0).sum() > 1
+        assert gpu_ctx.hist_overlap(a, b, bins) == eo.overlap(a, b, bins), bins
     with pytest.raises(Exception):
         gpu_ctx.hist_overlap(a, b, 2000)
 
