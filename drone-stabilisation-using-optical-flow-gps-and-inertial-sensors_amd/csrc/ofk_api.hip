@@ -201,7 +201,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     for (int k = 0; k < 2; ++k) { if (c->bgr[k]) hipFree(c->bgr[k]); if (c->pyr[k]) hipFree(c->pyr[k]); }
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
-                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back};
+                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
@@ -426,6 +426,7 @@ struct View {
     float *pts_prev, *pts_next; uint8_t *status; float *err; int *counts;
     double *sensors, *records;
     float *pts_back, *err_back, *fb2; uint8_t *status_back; int *gate_stats;   // NULL until a run with a track gate on (gate_alloc)
+    int *grid_stats;                                             // NULL until a selection with a corner grid on (grid_alloc)
 };
 static View view_of(ofk_ctx *c, int b0, int nb, int set)
 {
@@ -446,6 +447,7 @@ static View view_of(ofk_ctx *c, int b0, int nb, int set)
         v.pts_back = c->pts_back + b * c->max_pts * 2; v.err_back = c->err_back + b * c->max_pts; v.fb2 = c->fb2 + b * c->max_pts;
         v.status_back = c->status_back + b * c->max_pts; v.gate_stats = c->gate_stats + b * 4;
     }
+    v.grid_stats = c->grid_stats ? c->grid_stats + b * 2 : nullptr;
     return v;
 }
 
@@ -460,22 +462,90 @@ static int detect_response(ofk_ctx *c, hipStream_t s, View &v, const uint8_t *dm
     return OFK_OK;
 }
 // Second half: the candidates of the view -> at most max_corners (limit[b], where given) corners per image in dst / dst_counts
+// g (cell > 0: the corner grid, checked by check_grid; the view's grid_stats exist then) with the occupancy list of the view's images
 static void detect_select(ofk_ctx *c, hipStream_t s, const View &v, int h, int w, int max_corners, double quality, double min_distance,
-                          float *dst, int *dst_counts, const int *limit)
+                          float *dst, int *dst_counts, const int *limit, const ofk_corner_grid &g, const float *occ_pts = nullptr,
+                          const int *occ_counts = nullptr, int occ_stride = 0)
 {
+    const ofk_sel_grid sg = {g.cell, g.cap, g.max_rank, occ_pts, occ_counts, occ_stride, v.grid_stats};
     ofk_launch_select(s, v.cand, c->cand_cap, v.cand_count, v.cand_seg, v.segcap, v.seg_count, v.nseg, v.maxbits, quality, h, w, max_corners,
-                      (float)min_distance, dst, c->max_pts, dst_counts, limit, v.nb, v.sel_hist, v.sel_keys);
+                      (float)min_distance, dst, c->max_pts, dst_counts, limit, v.nb, v.sel_hist, v.sel_keys, g.cell > 0 ? &sg : nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ corner grid setting
+// h == 0: the frame is not known yet (ofk_set_corner_grid); the cell count is checked by the call that selects
+static int check_grid(ofk_ctx *c, const ofk_corner_grid *g, int h, int w, const char *who)
+{
+    if (g->cell < 0) return ofk_fail(c, OFK_E_INVALID, "%s: corner grid cell %d is negative", who, g->cell);
+    if (g->cell == 0) return OFK_OK;
+    if (g->cap < 1) return ofk_fail(c, OFK_E_INVALID, "%s: corner grid cap %d must be at least 1", who, g->cap);
+    if (g->max_rank < 0) return ofk_fail(c, OFK_E_INVALID, "%s: corner grid max_rank %d is negative (0 = unlimited)", who, g->max_rank);
+    if (h > 0) {
+        const long long cells = (long long)((w + g->cell - 1) / g->cell) * ((h + g->cell - 1) / g->cell);
+        if (cells > OFK_GRID_MAX_CELLS)
+            return ofk_fail(c, OFK_E_INVALID, "%s: corner grid cell %d makes %lld cells of a %dx%d frame, more than OFK_GRID_MAX_CELLS = %d", who,
+                            g->cell, cells, w, h, OFK_GRID_MAX_CELLS);
+    }
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_corner_grid(ofk_ctx *c, const ofk_corner_grid *g)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!g) { c->grid.cell = 0; return OFK_OK; }
+    TRY(check_grid(c, g, 0, 0, "ofk_set_corner_grid"));
+    c->grid = *g;
+    return OFK_OK;
+}
+
+extern "C" int ofk_get_corner_grid(const ofk_ctx *c, ofk_corner_grid *g)
+{
+    if (!c || !g) return OFK_E_INVALID;
+    *g = c->grid;
+    return OFK_OK;
+}
+
+// the grid's resident buffers (statistics, the stage entries' occupancy list), allocated when a selection first needs them
+static int grid_alloc(ofk_ctx *c)
+{
+    if (c->grid_stats) return OFK_OK;                            // one allocation, carved into the three buffers
+    const size_t B = (size_t)c->max_batch, o_cnt = B * 8, o_pts = up(o_cnt + B * 4, 256);
+    uint8_t *base = nullptr;
+    OFK_HIP(c, hipMalloc((void **)&base, o_pts + B * c->max_pts * 8));
+    c->grid_stats = (int *)base; c->grid_occ_counts = (int *)(base + o_cnt); c->grid_occ = (float *)(base + o_pts);
+    return OFK_OK;
+}
+// what every entry point that selects does before its first launch: the setting against the frame, the buffers, the batch on record
+static int grid_prepare(ofk_ctx *c, const ofk_corner_grid &g, int batch, int h, int w, const char *who)
+{
+    TRY(check_grid(c, &g, h, w, who));
+    if (g.cell == 0) return OFK_OK;
+    TRY(grid_alloc(c));
+    c->grid_batch = batch;
+    return OFK_OK;
+}
+
+extern "C" int ofk_corner_grid_download(ofk_ctx *c, int *stats)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!stats) return ofk_fail(c, OFK_E_INVALID, "ofk_corner_grid_download: stats is NULL");
+    if (c->grid_batch < 1 || !c->grid_stats) return ofk_fail(c, OFK_E_INVALID, "ofk_corner_grid_download: no selection with a corner grid on yet");
+    TRY(enter(c));
+    OFK_HIP(c, hipMemcpyAsync(stats, c->grid_stats, (size_t)c->grid_batch * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
 }
 
 // device-side: eig (+mask) resident in ctx -> corners in pts_prev / counts
-static int run_select(ofk_ctx *c, const uint8_t *dmask, int batch, int h, int w, int max_corners, double quality, double min_distance)
+static int run_select(ofk_ctx *c, const uint8_t *dmask, int batch, int h, int w, int max_corners, double quality, double min_distance,
+                      const ofk_corner_grid &g, const float *occ_pts, const int *occ_counts, int occ_stride)
 {
     const View v = view_of(c, 0, batch, 0);                      // nseg = 0: k_nms fills the flat list
     ofk_launch_zero_detect_state(c->stream, v.maxbits, v.cand_count, v.sel_hist, batch);
     ofk_launch_maxbits(c->stream, c->eig, c->img_stride, dmask, c->img_stride, h, w, v.maxbits, batch);
     ofk_launch_nms(c->stream, c->eig, c->img_stride, dmask, c->img_stride, h, w, v.maxbits, quality, v.cand, c->cand_cap, v.cand_count,
                    c->dev_flags, batch);
-    detect_select(c, c->stream, v, h, w, max_corners, quality, min_distance, v.pts_prev, v.counts, nullptr);
+    detect_select(c, c->stream, v, h, w, max_corners, quality, min_distance, v.pts_prev, v.counts, nullptr, g, occ_pts, occ_counts, occ_stride);
     return check_launch(c, "corner selection");
 }
 
@@ -499,37 +569,95 @@ static int fetch_corners(ofk_ctx *c, int batch, int max_corners, float *pts, int
     return check_capacity(c, flags, counts, batch);
 }
 
-extern "C" int ofk_select_corners(ofk_ctx *c, const float *eig, const uint8_t *mask, int batch, int h, int w, int max_corners,
-                                  double quality, double min_distance, float *pts, int *counts)
+// The occupancy list of a stage entry (host, nullable) -> the context's buffer; *dev / *dev_counts NULL without a list or a grid
+static int grid_occupancy(ofk_ctx *c, const ofk_corner_grid &g, const float *occ_pts, const int *occ_counts, int occ_stride, int batch,
+                          const float **dev, const int **dev_counts, const char *who)
 {
-    TRY(check_geom(c, batch, h, w, "ofk_select_corners"));
-    if (!eig || !pts || !counts) return ofk_fail(c, OFK_E_INVALID, "ofk_select_corners: NULL buffer");
-    if (h < 3 || w < 3) return ofk_fail(c, OFK_E_INVALID, "ofk_select_corners: image smaller than 3x3");
+    *dev = nullptr; *dev_counts = nullptr;
+    if (g.cell == 0 || !occ_pts) return OFK_OK;
+    if (!occ_counts || occ_stride < 1 || occ_stride > c->max_pts)
+        return ofk_fail(c, OFK_E_INVALID, "%s: an occupancy list needs its counts and occ_stride in 1..%d (%d)", who, c->max_pts, occ_stride);
+    OFK_HIP(c, hipMemcpyAsync(c->grid_occ, occ_pts, (size_t)batch * occ_stride * 8, hipMemcpyHostToDevice, c->stream));
+    OFK_HIP(c, hipMemcpyAsync(c->grid_occ_counts, occ_counts, (size_t)batch * 4, hipMemcpyHostToDevice, c->stream));
+    *dev = c->grid_occ; *dev_counts = c->grid_occ_counts;
+    return OFK_OK;
+}
+
+static int select_corners_impl(ofk_ctx *c, const char *who, const float *eig, const uint8_t *mask, int batch, int h, int w, int max_corners,
+                               double quality, double min_distance, float *pts, int *counts, const ofk_corner_grid &g, const float *occ_pts,
+                               const int *occ_counts, int occ_stride)
+{
+    TRY(check_geom(c, batch, h, w, who));
+    if (!eig || !pts || !counts) return ofk_fail(c, OFK_E_INVALID, "%s: NULL buffer", who);
+    if (h < 3 || w < 3) return ofk_fail(c, OFK_E_INVALID, "%s: image smaller than 3x3", who);
     TRY(check_select(c, max_corners, quality, min_distance));
+    TRY(grid_prepare(c, g, batch, h, w, who));
+    const float *docc; const int *dcnt;
+    TRY(grid_occupancy(c, g, occ_pts, occ_counts, occ_stride, batch, &docc, &dcnt, who));
     const size_t px = (size_t)h * w;
     TRY(h2d(c, c->eig, c->img_stride * 4, eig, px * 4, batch));
     const uint8_t *dmask = nullptr;
     if (mask) { TRY(lazy_mask(c)); TRY(h2d(c, c->mask, c->img_stride, mask, px, batch)); dmask = c->mask; }
-    TRY(run_select(c, dmask, batch, h, w, max_corners, quality, min_distance));
+    TRY(run_select(c, dmask, batch, h, w, max_corners, quality, min_distance, g, docc, dcnt, occ_stride));
     return fetch_corners(c, batch, max_corners, pts, counts);
 }
 
-extern "C" int ofk_good_features(ofk_ctx *c, const uint8_t *gray, const uint8_t *mask, int batch, int h, int w, int max_corners,
-                                 double quality, double min_distance, int block, float *pts, int *counts)
+static int good_features_impl(ofk_ctx *c, const char *who, const uint8_t *gray, const uint8_t *mask, int batch, int h, int w, int max_corners,
+                              double quality, double min_distance, int block, float *pts, int *counts, const ofk_corner_grid &g,
+                              const float *occ_pts, const int *occ_counts, int occ_stride)
 {
-    TRY(check_geom(c, batch, h, w, "ofk_good_features"));
-    if (!gray || !pts || !counts) return ofk_fail(c, OFK_E_INVALID, "ofk_good_features: NULL buffer");
+    TRY(check_geom(c, batch, h, w, who));
+    if (!gray || !pts || !counts) return ofk_fail(c, OFK_E_INVALID, "%s: NULL buffer", who);
     TRY(check_block(c, h, w, block));
     TRY(check_select(c, max_corners, quality, min_distance));
+    TRY(grid_prepare(c, g, batch, h, w, who));
+    const float *docc; const int *dcnt;
+    TRY(grid_occupancy(c, g, occ_pts, occ_counts, occ_stride, batch, &docc, &dcnt, who));
     const size_t px = (size_t)h * w;
     TRY(h2d(c, c->pyr[0], c->pyr_stride, gray, px, batch));
     const uint8_t *dmask = nullptr;
     if (mask) { TRY(lazy_mask(c)); TRY(h2d(c, c->mask, c->img_stride, mask, px, batch)); dmask = c->mask; }
     View v = view_of(c, 0, batch, 0);
     TRY(detect_response(c, c->stream, v, dmask, h, w, block, quality));
-    detect_select(c, c->stream, v, h, w, max_corners, quality, min_distance, v.pts_prev, v.counts, nullptr);
+    detect_select(c, c->stream, v, h, w, max_corners, quality, min_distance, v.pts_prev, v.counts, nullptr, g, docc, dcnt, occ_stride);
     TRY(check_launch(c, "corner detection"));
     return fetch_corners(c, batch, max_corners, pts, counts);
+}
+
+static const ofk_corner_grid k_grid_off = {0, 0, 0};
+
+extern "C" int ofk_select_corners(ofk_ctx *c, const float *eig, const uint8_t *mask, int batch, int h, int w, int max_corners,
+                                  double quality, double min_distance, float *pts, int *counts)
+{
+    if (!c) return OFK_E_INVALID;
+    return select_corners_impl(c, "ofk_select_corners", eig, mask, batch, h, w, max_corners, quality, min_distance, pts, counts, c->grid, nullptr,
+                               nullptr, 0);
+}
+
+extern "C" int ofk_select_corners_grid(ofk_ctx *c, const float *eig, const uint8_t *mask, int batch, int h, int w, int max_corners,
+                                       double quality, double min_distance, float *pts, int *counts, const ofk_corner_grid *g,
+                                       const float *occ_pts, const int *occ_counts, int occ_stride)
+{
+    if (!c) return OFK_E_INVALID;
+    return select_corners_impl(c, "ofk_select_corners_grid", eig, mask, batch, h, w, max_corners, quality, min_distance, pts, counts,
+                               g ? *g : k_grid_off, occ_pts, occ_counts, occ_stride);
+}
+
+extern "C" int ofk_good_features(ofk_ctx *c, const uint8_t *gray, const uint8_t *mask, int batch, int h, int w, int max_corners,
+                                 double quality, double min_distance, int block, float *pts, int *counts)
+{
+    if (!c) return OFK_E_INVALID;
+    return good_features_impl(c, "ofk_good_features", gray, mask, batch, h, w, max_corners, quality, min_distance, block, pts, counts, c->grid,
+                              nullptr, nullptr, 0);
+}
+
+extern "C" int ofk_good_features_grid(ofk_ctx *c, const uint8_t *gray, const uint8_t *mask, int batch, int h, int w, int max_corners,
+                                      double quality, double min_distance, int block, float *pts, int *counts, const ofk_corner_grid *g,
+                                      const float *occ_pts, const int *occ_counts, int occ_stride)
+{
+    if (!c) return OFK_E_INVALID;
+    return good_features_impl(c, "ofk_good_features_grid", gray, mask, batch, h, w, max_corners, quality, min_distance, block, pts, counts,
+                              g ? *g : k_grid_off, occ_pts, occ_counts, occ_stride);
 }
 
 static int check_lk(ofk_ctx *c, int h, int w, int win, int max_level)
@@ -1354,6 +1482,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
     TRY(check_select(c, p->max_corners, p->quality, p->min_distance));
     TRY(check_lk(c, h, w, p->win, p->max_level));
     if (p->solve_variant != OFK_SOLVE_NODE && p->solve_variant != OFK_SOLVE_SIM) return ofk_fail(c, OFK_E_INVALID, "solve_variant must be NODE or SIM");
+    TRY(grid_prepare(c, c->grid, B, h, w, "ofk_pairs_run"));
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     // The batch is cut into `nstreams` contiguous slices, each running the whole stage chain on its own stream: the
     // latency-bound stages of one slice (corner selection: one workgroup per image; the per-pair solve) overlap with the
@@ -1414,7 +1543,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
         if (fork) OFK_HIP(c, hipEventRecord(c->ev_stagger[k], st));
         {
             StageTimer t(c, OFK_STAGE_SELECT, st);
-            detect_select(c, st, v, h, w, p->max_corners, p->quality, p->min_distance, v.pts_prev, v.counts, nullptr);
+            detect_select(c, st, v, h, w, p->max_corners, p->quality, p->min_distance, v.pts_prev, v.counts, nullptr, c->grid);
         }
         if (overlap) OFK_HIP(c, hipStreamWaitEvent(st, c->ev_aux[k], 0));    // LK needs both pyramids
         {
@@ -1505,11 +1634,11 @@ static int stream_ingest(ofk_ctx *c, int k, const uint8_t *bgr, int batch, int h
 
 // corners of the previous frame (pyramid slot 0, level 0) -> dst/dst_counts, optional mask and per-stream budget
 static int stream_detect(ofk_ctx *c, const uint8_t *dmask, const int *limit, int batch, int h, int w, const ofk_params *p, float *dst,
-                         int *dst_counts)
+                         int *dst_counts, const float *occ_pts = nullptr, const int *occ_counts = nullptr)   // the corner grid's occupancy list, rows of max_pts
 {
     View v = view_of(c, 0, batch, 0);
     TRY(detect_response(c, c->stream, v, dmask, h, w, p->block_size, p->quality));
-    detect_select(c, c->stream, v, h, w, p->max_corners, p->quality, p->min_distance, dst, dst_counts, limit);
+    detect_select(c, c->stream, v, h, w, p->max_corners, p->quality, p->min_distance, dst, dst_counts, limit, c->grid, occ_pts, occ_counts, c->max_pts);
     return check_launch(c, "stream corner detection");
 }
 
@@ -1533,6 +1662,7 @@ static int stream_begin_impl(ofk_ctx *c, const uint8_t *first_bgr, int batch, in
     TRY(check_block(c, h, w, p->block_size));
     TRY(check_select(c, p->max_corners, p->quality, p->min_distance));
     TRY(check_lk(c, h, w, p->win, p->max_level));
+    TRY(grid_prepare(c, c->grid, batch, h, w, "ofk_stream_begin"));
     TRY(stream_alloc(c));
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     TRY(stream_ingest(c, 0, first_bgr, batch, h, w, lv));
@@ -1686,6 +1816,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         if (fu->hold_on_skip && B != 1) return ofk_fail(c, OFK_E_INVALID, "ofk_fusion.hold_on_skip needs a context with one stream (%d here): a batch shares one frame swap", B);
         TRY(filters_alloc(c));
     } else if (p->solve_variant != OFK_SOLVE_NODE && p->solve_variant != OFK_SOLVE_SIM) return ofk_fail(c, OFK_E_INVALID, "solve_variant must be NODE or SIM");
+    TRY(check_grid(c, &c->grid, h, w, "ofk_stream_step"));
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
@@ -1695,6 +1826,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     if (fu && fu->redetect_replace && few) {
         // of_module.py:83-86: before tracking, streams with few tracks replace them by fresh corners of the PREVIOUS frame (no mask)
         ofk_launch_redetect_limits(c->stream, c->counts, min_features, p->max_corners, c->limit, B);
+        TRY(grid_prepare(c, c->grid, B, h, w, "ofk_stream_step_fused"));
         TRY(stream_detect(c, nullptr, c->limit, B, h, w, p, c->pts_new, c->new_counts));
         ofk_launch_replace_tracks(c->stream, c->limit, c->pts_new, c->new_counts, c->max_pts, c->pts_prev, c->counts, B);
     }
@@ -1727,7 +1859,9 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         ofk_launch_redetect_limits(c->stream, c->counts, min_features, p->max_corners, c->limit, B);
         OFK_HIP(c, hipMemsetAsync(c->mask, 1, (size_t)B * c->img_stride, c->stream));
         ofk_launch_disc_mask(c->stream, c->mask, c->img_stride, h, w, c->pts_prev, c->counts, c->max_pts, mask_radius, c->limit, B);
-        TRY(stream_detect(c, c->mask, c->limit, B, h, w, p, c->pts_new, c->new_counts));
+        // with a corner grid the old tracks are its occupancy list as well: the new corners go to the cells the tracks have left
+        TRY(grid_prepare(c, c->grid, B, h, w, "ofk_stream_step"));
+        TRY(stream_detect(c, c->mask, c->limit, B, h, w, p, c->pts_new, c->new_counts, c->pts_prev, c->counts));
     }
     // tracks := new[status == 1] ++ re-detected (node:134,166); the new frame becomes the previous one (node:175)
     if (!hold)

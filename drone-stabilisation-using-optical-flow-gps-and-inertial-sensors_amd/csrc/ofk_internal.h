@@ -91,6 +91,9 @@ struct ofk_ctx {
     float *pts_back, *err_back, *fb2;        // [B][max_pts][2] end points of the backward pass, [B][max_pts] its err (discarded) and the squared
     uint8_t *status_back; int *gate_stats;   // distances; [B][max_pts] its status, [B][4] the gate's counts; one lazy allocation (pts_back owns it)
     int gate_batch, gate_fb;                 // images of the latest gated run / step (ofk_track_gate_download), 0 = none / it ran a backward pass
+    ofk_corner_grid grid;                    // ofk_set_corner_grid: cell 0 (off) unless set
+    int *grid_stats; int *grid_occ_counts; float *grid_occ;   // [B][2] statistics, [B] / [B][max_pts][2] occupancy list of the stage entries; one lazy allocation (grid_stats owns it)
+    int grid_batch;                          // images of the latest selection with a grid on (ofk_corner_grid_download), 0 = none
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -122,6 +125,10 @@ int ofk_jpeg_decode_staged_pairs(ofk_ctx *c, int slot, uint8_t *dst_prev, uint8_
 int ofk_jpeg_decode_device(ofk_ctx *c, const uint8_t *const *jpeg, const size_t *nbytes, int batch, uint8_t *dst, size_t dst_stride,
                            size_t dst_capacity_px, int *h_out, int *w_out, uint8_t **out, size_t *out_stride);   // k_jpeg.hip
 
+// the corner grid of one selection launch (ofk.h: ofk_corner_grid): setting, occupancy list (occ_pts NULL = empty) and the
+// [batch][2] statistics, all of the launch's first image on
+struct ofk_sel_grid { int cell, cap, max_rank; const float *occ_pts; const int *occ_counts; int occ_stride; int *stats; };
+
 // --- launchers (all asynchronous on `s`; pointers are device pointers)
 void ofk_launch_gray(hipStream_t s, const uint8_t *bgr, size_t bgr_stride, uint8_t *gray, size_t gray_stride, int batch,
                      int h, int w);
@@ -148,7 +155,8 @@ void ofk_stream_geometry(int h, int w, int block, int batch, int *rows, int *nse
 void ofk_launch_select(hipStream_t s, unsigned long long *cand, int cand_cap, int *cand_count, const unsigned long long *seg,
                        int seg_cap, const int *seg_count, int nseg, const unsigned int *maxbits, double quality, int h, int w,
                        int max_corners, float min_distance, float *pts, int pts_stride, int *counts, const int *limit, int batch,
-                       unsigned *sel_hist, unsigned long long *sel_keys);   // nseg == 0: the flat list holds the candidates already
+                       unsigned *sel_hist, unsigned long long *sel_keys, const ofk_sel_grid *g = nullptr);
+                       // nseg == 0: the flat list holds the candidates already; g with cell > 0: k_select_greedy_grid
 // what a detection starts from, zeroed in one launch: response maxima, candidate counters and sel_hist ([batch][1024], the selection's prefilter)
 void ofk_launch_zero_detect_state(hipStream_t s, unsigned int *maxbits, int *cand_count, unsigned *sel_hist, int batch);
 void ofk_launch_disc_mask(hipStream_t s, uint8_t *mask, size_t mask_stride, int h, int w, const float *pts, const int *counts,

@@ -28,6 +28,7 @@ SYMBOLS = (
     "ofk_good_features", "ofk_lk_pyr", "ofk_lk_pyr_ex", "ofk_predict_points", "ofk_set_lk_seed", "ofk_get_lk_seed", "ofk_flow_model", "ofk_feasibility", "ofk_velocity_solve", "ofk_imu_propagate",
     "ofk_set_robust", "ofk_get_robust", "ofk_robust_download", "ofk_velocity_solve_robust", "ofk_robust_pairs",
     "ofk_set_track_gate", "ofk_get_track_gate", "ofk_track_gate_download", "ofk_lk_pyr_fb",
+    "ofk_set_corner_grid", "ofk_get_corner_grid", "ofk_corner_grid_download", "ofk_select_corners_grid", "ofk_good_features_grid",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
     "ofk_stream_begin_jpeg", "ofk_stream_step_jpeg",
@@ -60,6 +61,7 @@ ROBUST_DEFAULT_C = {ROBUST_HUBER: 1.345, ROBUST_TUKEY: 4.685}     # 95 % efficie
 ROBUST_MIN_POINTS, ROBUST_DOUBLES = 8, 8
 FB_OFF, FB_PLAIN, FB_SEEDED = 0, 1, 2                    # ofk_set_track_gate / ofk_lk_pyr_fb
 FB_MODES = {"off": FB_OFF, "plain": FB_PLAIN, "seeded": FB_SEEDED}
+GRID_MAX_CELLS = 2048                                   # OFK_GRID_MAX_CELLS: cells of a corner grid over one frame
 FLOW_LK, FLOW_ROTATIONAL = 0, 1
 KEEP_STATUS, KEEP_LEGACY = 0, 1
 CONTROL_SENSORS, CONTROL_IMU = 0, 1
@@ -115,6 +117,24 @@ def track_gate_setting(fb="off", fb_thr=0.5, fb_level=-1, err_max=0.0):
     if not (np.isfinite(err_max) and err_max >= 0.0):
         raise ValueError(f"track gate err_max {err_max} must be finite and not negative (0 = off)")
     return TrackGate(fb, fb_thr, fb_level, err_max)
+
+
+class CornerGrid(C.Structure):
+    """ofk_corner_grid (include/ofk.h): the per-cell cap inside the greedy corner selection."""
+    _fields_ = [("cell", C.c_int), ("cap", C.c_int), ("max_rank", C.c_int)]
+
+
+def corner_grid_setting(cell=0, cap=0, max_rank=0):
+    """A CornerGrid structure: cell = the cell edge in pixels (0 = off, the other fields are ignored then), cap = the most corners a
+    cell may hold (>= 1), max_rank = 0 (every candidate may be examined) or the number of leading candidates the pass looks at."""
+    cell, cap, max_rank = int(cell), int(cap), int(max_rank)
+    if cell < 0:
+        raise ValueError(f"corner grid cell {cell} must not be negative (0 = off)")
+    if cell > 0 and cap < 1:
+        raise ValueError(f"corner grid cap {cap} must be at least 1")
+    if max_rank < 0:
+        raise ValueError(f"corner grid max_rank {max_rank} must not be negative (0 = unlimited)")
+    return CornerGrid(cell, cap, max_rank)
 
 
 class Fusion(C.Structure):
@@ -192,6 +212,10 @@ def load_library():
         L.ofk_robust_pairs.argtypes = [C.c_ulonglong, C.c_uint, i, i, vp, vp]
         L.ofk_set_track_gate.argtypes = [vp, C.POINTER(TrackGate)]; L.ofk_get_track_gate.argtypes = [vp, C.POINTER(TrackGate)]
         L.ofk_track_gate_download.argtypes = [vp, vp, vp, vp, i, vp]
+        L.ofk_set_corner_grid.argtypes = [vp, C.POINTER(CornerGrid)]; L.ofk_get_corner_grid.argtypes = [vp, C.POINTER(CornerGrid)]
+        L.ofk_corner_grid_download.argtypes = [vp, vp]
+        L.ofk_select_corners_grid.argtypes = [vp, vp, vp, i, i, i, i, d, d, vp, vp, C.POINTER(CornerGrid), vp, vp, i]
+        L.ofk_good_features_grid.argtypes = [vp, vp, vp, i, i, i, i, d, d, i, vp, vp, C.POINTER(CornerGrid), vp, vp, i]
         L.ofk_lk_pyr_fb.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, i, vp, vp, vp, C.POINTER(TrackGate), vp, vp, vp]
         L.ofk_imu_propagate.argtypes = [vp, vp, vp, i]
         L.ofk_post_solve.argtypes = [vp, vp, vp, vp, vp, i, vp]
@@ -368,28 +392,54 @@ class Context:
             self._ck(self._L.ofk_mineig_response(self._h, _p(gray), B, h, w, int(block_size), _p(out)))
         return out[0] if single else out
 
-    def select_corners(self, eig, max_corners, quality, min_distance, mask=None):
+    @staticmethod
+    def _occupancy(occupied, B):
+        """The occupancy list of a grid entry: None, or (points [B,S,2], counts [B]) -> (points f32 [B,S,2], counts i32 [B], S >= 1)."""
+        if occupied is None:
+            return None, None, 0
+        pts, counts = occupied
+        pts = _arr(pts, np.float32)
+        pts = pts.reshape(B, -1, 2) if pts.size else np.zeros((B, 1, 2), np.float32)
+        return np.ascontiguousarray(pts), _arr(counts, np.int32, (B,)), pts.shape[1]
+
+    def select_corners(self, eig, max_corners, quality, min_distance, mask=None, grid=None, occupied=None):
+        """grid: None = the context's setting (ofk_select_corners); a CornerGrid = ofk_select_corners_grid with that setting and
+        `occupied` (None, or (points [B,S,2], counts [B])) as the occupancy list."""
         eig, single = self._batched(eig, 2)
         eig = _arr(eig, np.float32)
         B, h, w = eig.shape
         mask = _opt(mask, np.uint8, (B, h, w))
         pts = np.zeros((B, max_corners, 2), np.float32); cnt = np.zeros(B, np.int32)
+        if grid is None and occupied is not None:
+            raise ValueError("an occupancy list needs grid=")
         with self._lock:
-            self._ck(self._L.ofk_select_corners(self._h, _p(eig), _p(mask), B, h, w, int(max_corners), float(quality),
-                                                float(min_distance), _p(pts), _p(cnt)))
+            if grid is None:
+                self._ck(self._L.ofk_select_corners(self._h, _p(eig), _p(mask), B, h, w, int(max_corners), float(quality),
+                                                    float(min_distance), _p(pts), _p(cnt)))
+            else:
+                op, oc, S = self._occupancy(occupied, B)
+                self._ck(self._L.ofk_select_corners_grid(self._h, _p(eig), _p(mask), B, h, w, int(max_corners), float(quality),
+                                                         float(min_distance), _p(pts), _p(cnt), C.byref(grid), _p(op), _p(oc), S))
         return (pts[0], int(cnt[0])) if single else (pts, cnt)
 
-    def good_features(self, gray, max_corners, quality, min_distance, block_size, mask=None):
+    def good_features(self, gray, max_corners, quality, min_distance, block_size, mask=None, grid=None, occupied=None):
         """Batched goodFeaturesToTrack.  Returns (pts [B,max_corners,2] f32, counts [B]) or, for a single
-        image, the OpenCV-shaped (N,1,2) float32 array."""
+        image, the OpenCV-shaped (N,1,2) float32 array.  grid / occupied: as in select_corners (ofk_good_features_grid)."""
         gray, single = self._batched(gray, 2)
         gray = _arr(gray, np.uint8)
         B, h, w = gray.shape
         mask = _opt(mask, np.uint8, (B, h, w))
         pts = np.zeros((B, max_corners, 2), np.float32); cnt = np.zeros(B, np.int32)
+        if grid is None and occupied is not None:
+            raise ValueError("an occupancy list needs grid=")
         with self._lock:
-            self._ck(self._L.ofk_good_features(self._h, _p(gray), _p(mask), B, h, w, int(max_corners), float(quality),
-                                               float(min_distance), int(block_size), _p(pts), _p(cnt)))
+            if grid is None:
+                self._ck(self._L.ofk_good_features(self._h, _p(gray), _p(mask), B, h, w, int(max_corners), float(quality),
+                                                   float(min_distance), int(block_size), _p(pts), _p(cnt)))
+            else:
+                op, oc, S = self._occupancy(occupied, B)
+                self._ck(self._L.ofk_good_features_grid(self._h, _p(gray), _p(mask), B, h, w, int(max_corners), float(quality),
+                                                        float(min_distance), int(block_size), _p(pts), _p(cnt), C.byref(grid), _p(op), _p(oc), S))
         if single:
             n = int(cnt[0])
             return pts[0, :n].reshape(n, 1, 2).copy()
@@ -481,6 +531,28 @@ class Context:
         g = TrackGate()
         self._ck(self._L.ofk_get_track_gate(self._h, C.byref(g)))
         return g
+
+    def set_corner_grid(self, grid=None, **settings):
+        """ofk_set_corner_grid: a CornerGrid (or corner_grid_setting's keywords); None switches the grid off.  Every later corner
+        selection of the context (good_features, select_corners, pairs_run, stream begin and re-detection) caps the corners per cell."""
+        g = grid if grid is not None or not settings else corner_grid_setting(**settings)
+        with self._lock:
+            self._ck(self._L.ofk_set_corner_grid(self._h, C.byref(g) if g is not None else None))
+
+    def get_corner_grid(self):
+        g = CornerGrid()
+        self._ck(self._L.ofk_get_corner_grid(self._h, C.byref(g)))
+        return g
+
+    def corner_grid_stats(self, batch):
+        """ofk_corner_grid_download: [batch,2] int32 = (corners accepted, candidates examined) per image of the latest selection with
+        a grid on.  The library writes that selection's rows, so the buffer has max_batch of them and the first `batch` are returned."""
+        if not 0 <= int(batch) <= self.max_batch:
+            raise ValueError(f"corner_grid_stats: batch {batch} outside 0..{self.max_batch}")
+        st = np.zeros((self.max_batch, 2), np.int32)
+        with self._lock:
+            self._ck(self._L.ofk_corner_grid_download(self._h, _p(st)))
+        return st[:batch].copy()
 
     def track_gate_download(self, batch, points=True):
         """ofk_track_gate_download of the latest gated run / step -> dict(stats [batch,4] i32: forward-tracked, of those lost by the

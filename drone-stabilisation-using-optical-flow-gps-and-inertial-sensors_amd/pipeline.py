@@ -48,6 +48,11 @@ class PipelineConfig:
     fb_thr: float = 0.5
     fb_level: int = -1
     err_max: float = 0.0
+    # corner grid (ofk.h: ofk_set_corner_grid): at most grid_cap corners per grid_cell x grid_cell pixel cell in every selection,
+    # grid_cell 0 = off; grid_max_rank > 0: only that many leading candidates are looked at
+    grid_cell: int = 0
+    grid_cap: int = 0
+    grid_max_rank: int = 0
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -78,6 +83,12 @@ class PipelineConfig:
         if self.fb_check == "off" and self.err_max == 0.0:
             return None
         return ofk.track_gate_setting(self.fb_check, self.fb_thr, self.fb_level, self.err_max)
+
+    def corner_grid_setting(self):
+        """The ofk.CornerGrid structure of this configuration, None when the grid is off."""
+        if self.grid_cell == 0:
+            return None
+        return ofk.corner_grid_setting(self.grid_cell, self.grid_cap, self.grid_max_rank)
 
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
@@ -206,6 +217,8 @@ class FlowStream:
             self.ctx.set_robust(self.cfg.robust_setting())
         if self.cfg.track_gate_setting() is not None:
             self.ctx.set_track_gate(self.cfg.track_gate_setting())
+        if self.cfg.corner_grid_setting() is not None:
+            self.ctx.set_corner_grid(self.cfg.corner_grid_setting())
         self.fusion = fusion
         if fusion is not None:                                  # the per-stream filter state lives on the device from here on
             self._fusion = fusion.to_struct()
@@ -228,6 +241,10 @@ class FlowStream:
         """[batch, 4] int32 of the latest step with a track gate on: forward-tracked points, of those lost by the backward pass, of
         the rest beyond fb_thr, of the rest over err_max."""
         return self.ctx.track_gate_stats(self.batch)
+
+    def corner_grid_stats(self):
+        """[batch, 2] int32 of the latest detection (begin or re-detection) with a corner grid on: corners accepted, candidates examined."""
+        return self.ctx.corner_grid_stats(self.batch)
 
     def begin(self, first_bgr):
         return self.ctx.stream_begin(first_bgr, self._params)
@@ -269,6 +286,8 @@ class FlowPipeline:
             self.ctx.set_robust(self.cfg.robust_setting())
         if self.cfg.track_gate_setting() is not None:
             self.ctx.set_track_gate(self.cfg.track_gate_setting())
+        if self.cfg.corner_grid_setting() is not None:
+            self.ctx.set_corner_grid(self.cfg.corner_grid_setting())
         if streams > 1:
             self.ctx.set_streams(streams)
 
@@ -311,6 +330,10 @@ class FlowPipeline:
     def track_gate_stats(self):
         """[batch, 4] int32 of the latest run with a track gate on (see FlowStream.track_gate_stats)."""
         return self.ctx.track_gate_stats(self.batch)
+
+    def corner_grid_stats(self):
+        """[batch, 2] int32 of the latest run with a corner grid on: corners accepted, candidates examined."""
+        return self.ctx.corner_grid_stats(self.batch)
 
     def run_async(self):
         self.ctx.pairs_run(self._params)

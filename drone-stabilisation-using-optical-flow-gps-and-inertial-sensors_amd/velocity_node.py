@@ -92,6 +92,7 @@ class optical_fusion:
     max_feat = 100
     _robust = {}                                                 # PipelineConfig's robust_* settings (see __init__); empty: the plain solve
     _track_gate = {}                                             # PipelineConfig's fb_check / fb_thr / fb_level / err_max; empty: no gate
+    _corner_grid = {}                                            # PipelineConfig's grid_cell / grid_cap / grid_max_rank; empty: no grid
     feature_params = dict(qualityLevel=0.7, minDistance=10, blockSize=12)
     lk_params = dict(winSize=(15, 15), maxLevel=3, criteria=(cv2.TERM_CRITERIA_EPS | cv2.TERM_CRITERIA_COUNT, 20, 0.03))
     scaling = 0.01
@@ -245,7 +246,7 @@ class optical_fusion:
             cfg = PipelineConfig(max_corners=int(self.max_feat), quality=float(self.feature_params["qualityLevel"]),
                                  min_distance=float(self.feature_params["minDistance"]), block_size=int(self.feature_params["blockSize"]),
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
-                                 use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate)
+                                 use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -320,12 +321,15 @@ class optical_fusion:
             self.got_picture_ = False
             return v_obs
 
-    def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None):
+    def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
         dict(fb="seeded", fb_thr=0.5, fb_level=0): the restored pipeline then drops the points that fail the forward-backward check
-        or exceed err_max before the solve and from the tracks (ofk.h: ofk_set_track_gate)."""
+        or exceed err_max before the solve and from the tracks (ofk.h: ofk_set_track_gate).
+        corner_grid: None (goodFeaturesToTrack's selection) or a dict of ofk.corner_grid_setting's keywords, e.g. dict(cell=64, cap=4):
+        detection and re-detection then hold at most `cap` corners per cell, the re-detection counting the tracks that are still
+        alive (ofk.h: ofk_set_corner_grid)."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -333,6 +337,10 @@ class optical_fusion:
         if g:
             ofk.track_gate_setting(**g)                          # unknown or invalid keywords fail here, not at the first frame
         self._track_gate = dict(fb_check=g.pop("fb", "off"), **g) if track_gate else {}
+        k = dict(corner_grid or {})
+        if k:
+            ofk.corner_grid_setting(**k)                         # unknown or invalid keywords fail here, not at the first frame
+        self._corner_grid = {"grid_" + n: v for n, v in k.items()}
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

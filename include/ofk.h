@@ -87,6 +87,53 @@ int ofk_select_corners(ofk_ctx *ctx, const float *eig, const uint8_t *mask, int 
 int ofk_good_features(ofk_ctx *ctx, const uint8_t *gray, const uint8_t *mask, int batch, int h, int w, int max_corners,
                       double quality, double min_distance, int block_size, float *pts, int *counts);
 
+/* The corner grid: a per-cell cap inside the greedy selection (the bucketing the reference gestures at with its cluster and mask
+ * helpers, of_library.py:116-226, and what the re-detection of velocity_measurment_node.py:157-166 lacks: it only masks discs around
+ * the old tracks, nothing steers the new corners towards the parts of the frame that have none).  Off by default; with it off every
+ * entry point launches the kernels and returns the bits it always did.
+ * Candidates and their order are unchanged: a candidate passes the mask, is > f32(f64(max) * quality) and a 3x3 local maximum; order
+ * is value descending, then linear index descending; a candidate's rank is its place in that order, from 0.
+ * The acceptance test, applied to each candidate in rank order, with occ[] the corners per cell:
+ *   1. Stop if max_corners corners are accepted, if every cell holds occ >= cap, or if the candidate's rank >= max_rank (max_rank != 0).
+ *   2. c = (y / cell) * gw + x / cell, integer division, gw = ceil(w / cell).  If occ[c] >= cap, skip the candidate.
+ *   3. The minDistance test against all accepted corners, as always.  If it fails, skip.
+ *   4. Accept the candidate and increment occ[c].
+ * (The stop on full cells cannot change the corners: no later candidate passes step 2.  It is part of the rule because it fixes the
+ * statistics.)  occ starts at zero, or, with an occupancy list occ_pts [batch][occ_stride][2] f32 / occ_counts [batch], as the number
+ * of listed points i < min(occ_counts[b], occ_stride) whose truncated position ((int)x, (int)y) lies in the cell; points whose
+ * truncated position is outside the image (or not a number) are ignored.  Occupancy points take no part in the minDistance test (a
+ * stream step keeps its disc mask for that).  A cap that can never bind (>= max_corners with an empty list, say) gives exactly the
+ * plain result.
+ * Statistics, 2 x int32 per image: corners accepted; candidates examined = rank of the last candidate steps 2-4 decided, plus one
+ * (the rank of the acceptance that filled the budget or the last open cell, plus one, when the pass stopped there; 0 when nothing was
+ * decided, an image without budget in a re-detection included).
+ * Refused with OFK_E_INVALID before any launch, a setting staying as it was: cell < 0; cap < 1 with cell > 0; max_rank < 0;
+ * ceil(w / cell) * ceil(h / cell) > OFK_GRID_MAX_CELLS for the frame at hand (checked by the call that selects, the frame being
+ * unknown to ofk_set_corner_grid); occ_stride outside 1..ctx max_pts with an occupancy list.
+ * ofk_set_corner_grid (NULL or cell 0: off) is a context setting read by ofk_good_features, ofk_select_corners, ofk_pairs_run (every
+ * slice), ofk_stream_begin[_jpeg], the replace-mode re-detection of ofk_stream_step_fused[_jpeg] and the append-mode re-detection of
+ * every stream step.  The append-mode re-detection passes the OLD tracks (the points and counts its disc mask is drawn from) as the
+ * occupancy list, so it refills the cells the tracks have left; all others start from empty cells.
+ * ofk_good_features_grid / ofk_select_corners_grid: the two stage entries with the grid (g NULL or cell 0: off) and the occupancy
+ * list (occ_pts NULL: empty) as arguments; they ignore the context setting.
+ * ofk_corner_grid_download: stats [batch][2] i32 of the latest selection that ran with a grid on (`batch` is that selection's own);
+ * OFK_E_INVALID before such a selection. */
+#define OFK_GRID_MAX_CELLS 2048
+typedef struct ofk_corner_grid {
+    int cell;      /* cell edge in pixels; 0 = off (every other field ignored) */
+    int cap;       /* most corners a cell may hold, >= 1 */
+    int max_rank;  /* 0 = unlimited; else only the first max_rank candidates in rank order are ever examined */
+} ofk_corner_grid;
+int ofk_set_corner_grid(ofk_ctx *ctx, const ofk_corner_grid *g);
+int ofk_get_corner_grid(const ofk_ctx *ctx, ofk_corner_grid *g);
+int ofk_corner_grid_download(ofk_ctx *ctx, int *stats);
+int ofk_select_corners_grid(ofk_ctx *ctx, const float *eig, const uint8_t *mask, int batch, int h, int w, int max_corners,
+                            double quality, double min_distance, float *pts, int *counts, const ofk_corner_grid *g,
+                            const float *occ_pts, const int *occ_counts, int occ_stride);
+int ofk_good_features_grid(ofk_ctx *ctx, const uint8_t *gray, const uint8_t *mask, int batch, int h, int w, int max_corners,
+                           double quality, double min_distance, int block_size, float *pts, int *counts, const ofk_corner_grid *g,
+                           const float *occ_pts, const int *occ_counts, int occ_stride);
+
 /* cv2.calcOpticalFlowPyrLK(prev, next, prevPts, None, winSize=(win,win), maxLevel, criteria=(EPS|COUNT, max_count, eps))
  * — of_module.py:88; node:133; evaluate_exp.py:98; of_library.py:249.
  * prev_pts/next_pts [batch][pts_stride][2] f32, counts [batch] (points used per image, <= pts_stride),
