@@ -1,0 +1,428 @@
+// k_cov.inc — the velocity covariance (ofk.h: ofk_set_cov): first-order error propagation through the velocity solve, and the filter
+// correct that uses it.  Included by k_estimate.hip, whose helpers (point_terms, pair_point, fuse_terms, wave_sum, jacobi3, the Kalman
+// recursions) it shares.  DESIGN.md, "velocity covariance", has the derivation.
+//
+// One team per problem behind whichever solve kernel ran, plain or robust: a single wave (NW = 1, beside the response kernel / LK of
+// large batches) or a 256-thread workgroup (NW = 4).  The team reads v from the record, walks the kept points once and sums, with
+// p = (x, y, 1), N = |p|^2 I - p p^T, q, a = sA, b = sB the solve's per-point terms and w the final robust weight (or 1):
+//   M   = sum w a^2 N                                       in the solve's own order, so jacobi3 sees the solve's bits
+//   Sf  = sum_k e e^T, e = w a b N e_k                      flow u_k (2 per point)
+//   Sp  = sum_k e e^T, e = n_k h + w [a b (dN q + N (e_k x omega)) - a^2 dN v]      position x_k (2 per point, u held fixed)
+//   Eg_k = sum w a b |p|^2 (p x e_k)                        gyro omega_k
+//   Ed  = sum w a db N q                                    range d: db = 1 / (n.p) (NODE), 1 (SIM)
+//   En_k = sum p_k h                                        normal n_k
+// where h = w [(A b + a B) N q - 2 a A N v] is the response to a unit change of n.p: (A, B) = (0, -d / (n.p)^2) (NODE), (1, 0) (SIM),
+// and dN r = 2 p_k r - e_k (p.r) - p r_k.  That is 40 sums.  Both forms add them as the solve adds its own - four "virtual waves" take
+// the points vw * 64 + lane + 256 k, each is reduced by the shuffle butterfly, the partial sums are added as (s0 + s1) + (s2 + s3) -
+// so the records are the same bit for bit across forms, slice counts and overlap settings.  One lane applies M^-1 from the
+// eigen-decomposition and writes the record.  No atomics, no MFMA, vector stores only.
+#define COV_SUMS 40
+#define COV_M 0
+#define COV_CNT 6
+#define COV_SF 7
+#define COV_SP 13
+#define COV_EG 19
+#define COV_ED 28
+#define COV_EN 31
+
+struct cov_cfg { int mode; double sf, sp, sd, so[3], sn, soff; int omega_from_imu, filter_r; double r_floor, nis_max; };
+
+__device__ __forceinline__ void cov_outer(double *s, const double *e)
+{
+    s[0] += e[0] * e[0]; s[1] += e[0] * e[1]; s[2] += e[0] * e[2]; s[3] += e[1] * e[1]; s[4] += e[1] * e[2]; s[5] += e[2] * e[2];
+}
+
+// One kept point's contributions to the 40 sums.
+__device__ __forceinline__ void cov_point(double *s, int variant, double x, double y, double ux, double uy, double w, const double *nrm,
+                                          const double *om, double d, const double *v)
+{
+    double q0, q1, q2, a, b;
+    point_terms(variant, x, y, ux, uy, nrm, om, d, 1.0, q0, q1, q2, a, b);
+    const double pp = x * x + y * y + 1.0, sa2 = a * a * w;
+    s[COV_M + 0] += sa2 * (pp - x * x); s[COV_M + 1] += sa2 * (-x * y); s[COV_M + 2] += sa2 * (-x);
+    s[COV_M + 3] += sa2 * (pp - y * y); s[COV_M + 4] += sa2 * (-y);     s[COV_M + 5] += sa2 * (pp - 1.0);
+    s[COV_CNT] += 1.0;
+    const double p[3] = {x, y, 1.0}, q[3] = {q0, q1, q2};
+    const double pq = x * q0 + y * q1 + q2, pv = x * v[0] + y * v[1] + v[2];
+    const double Nq[3] = {pp * q0 - x * pq, pp * q1 - y * pq, pp * q2 - pq}, Nv[3] = {pp * v[0] - x * pv, pp * v[1] - y * pv, pp * v[2] - pv};
+    const double wab = w * a * b, wa2 = w * a * a;
+    // flow
+    const double f0[3] = {wab * (pp - x * x), wab * (-x * y), wab * (-x)}, f1[3] = {wab * (-x * y), wab * (pp - y * y), wab * (-y)};
+    cov_outer(s + COV_SF, f0); cov_outer(s + COV_SF, f1);
+    // gyro: N (p x e_k) = |p|^2 (p x e_k)
+    const double g = wab * pp;
+    s[COV_EG + 1] += g;      s[COV_EG + 2] += g * (-y);
+    s[COV_EG + 3] += -g;     s[COV_EG + 5] += g * x;
+    s[COV_EG + 6] += g * y;  s[COV_EG + 7] += g * (-x);
+    // range, and the response h to n.p
+    const double ndp = nrm[0] * x + nrm[1] * y + nrm[2];
+    double h[3];
+    if (variant == OFK_SOLVE_SIM) {
+        const double wa = w * a;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { s[COV_ED + j] += wa * Nq[j]; h[j] = w * (b * Nq[j] - 2.0 * a * Nv[j]); }
+    } else {
+        const double wa = w * a, dbd = 1.0 / ndp, B = -d / (ndp * ndp);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { s[COV_ED + j] += wa * dbd * Nq[j]; h[j] = wa * B * Nq[j]; }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) s[COV_EN + 3 * k + j] += p[k] * h[j];
+    // position
+    const double dq[2][3] = {{0.0, -om[2], om[1]}, {om[2], 0.0, -om[0]}};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double pdq = x * dq[k][0] + y * dq[k][1] + dq[k][2];
+        double e[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double ek = j == k ? 1.0 : 0.0;
+            const double dNq = 2.0 * p[k] * q[j] - ek * pq - p[j] * q[k], dNv = 2.0 * p[k] * v[j] - ek * pv - p[j] * v[k];
+            const double Ndq = pp * dq[k][j] - p[j] * pdq;
+            e[j] = nrm[k] * h[j] + (wab * (dNq + Ndq) - wa2 * dNv);
+        }
+        cov_outer(s + COV_SP, e);
+    }
+}
+
+// The walk and the reduction: terms(i, x, y, ux, uy, w) -> point i enters (the set the solve used).  The sums end in part[0], for
+// thread 0 alone (it wrote them: no barrier behind this).
+template <int NW, class Terms>
+__device__ __forceinline__ void cov_core(double (*part)[COV_SUMS], int n, int variant, const double *nrm, const double *om, double d,
+                                         const double *v, Terms terms)
+{
+    const int lane = threadIdx.x & 63, wave = NW == 1 ? 0 : (int)(threadIdx.x >> 6);
+#pragma unroll 1
+    for (int vw = wave; vw < 4; vw += NW) {
+        double s[COV_SUMS];
+#pragma unroll
+        for (int k = 0; k < COV_SUMS; ++k) s[k] = 0.0;
+#pragma unroll 1
+        for (int i = vw * 64 + lane; i < n; i += 256) {
+            double x, y, ux, uy, w;
+            if (terms(i, x, y, ux, uy, w)) cov_point(s, variant, x, y, ux, uy, w, nrm, om, d, v);
+        }
+#pragma unroll
+        for (int k = 0; k < COV_SUMS; ++k) { const double t = wave_sum(s[k]); if (lane == 0) part[vw][k] = t; }
+    }
+    if (NW == 1) __builtin_amdgcn_wave_barrier(); else __syncthreads();
+    if (threadIdx.x == 0)
+        for (int k = 0; k < COV_SUMS; ++k) part[0][k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+}
+
+__device__ __forceinline__ void cov_void(double *o)
+{
+    for (int k = 0; k < OFK_COV_DOUBLES; ++k) o[k] = 0.0;
+    o[13] = 1.0;
+}
+
+// A (symmetric, upper triangle s6) sandwiched: Mi S Mi, scaled; Mi full 3x3.
+__device__ void cov_sandwich(const double Mi[3][3], const double *s6, double scale, double C[3][3])
+{
+    const double S[3][3] = {{s6[0], s6[1], s6[2]}, {s6[1], s6[3], s6[4]}, {s6[2], s6[4], s6[5]}};
+    double T[3][3];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) T[i][j] = Mi[i][0] * S[0][j] + Mi[i][1] * S[1][j] + Mi[i][2] * S[2][j];
+    for (int i = 0; i < 3; ++i) for (int j = i; j < 3; ++j) C[i][j] = C[j][i] = scale * (T[i][0] * Mi[j][0] + T[i][1] * Mi[j][1] + T[i][2] * Mi[j][2]);
+}
+
+// One lane: the record from the sums.  sf, sp: sigma_flow / sigma_pos in the units of the points; ovar: the gyro's variances;
+// t: lever arm (NULL: none, C_uav = C_v); R: rotation (NULL: I); rss, rank: the solve's own.  Slots 14, 15 (NIS, gated) are zeroed.
+__device__ void cov_finish(const double *s, const cov_cfg &cc, double sf, double sp, const double *ovar, const double *om, const double *t,
+                           const double *R, double rss, double rank, bool usable, double *o)
+{
+    const double m = s[COV_CNT];
+    if (!usable || !(rank >= 3.0) || !(m > 0.0) || (cc.mode == OFK_COV_RESIDUAL && !(2.0 * m > 3.0))) { cov_void(o); return; }
+    double A[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}}, lam[3], V[3][3], Mi[3][3];
+    jacobi3(A, lam, V);
+    if (!(lam[2] > 0.0)) { cov_void(o); return; }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) Mi[i][j] = V[i][0] * V[j][0] / lam[0] + V[i][1] * V[j][1] / lam[1] + V[i][2] * V[j][2] / lam[2];
+    const double s2 = 2.0 * m > 3.0 ? rss / (2.0 * m - 3.0) : 0.0;
+    double Cf[3][3], Cx[3][3];
+    if (cc.mode == OFK_COV_RESIDUAL) {
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { Cf[i][j] = s2 * Mi[i][j]; Cx[i][j] = 0.0; }
+    } else {
+        cov_sandwich(Mi, s + COV_SF, sf * sf, Cf);
+        cov_sandwich(Mi, s + COV_SP, sp * sp, Cx);
+    }
+    double Jw[3][3], Jn[3][3], Jd[3];                            // column k: dv / d omega_k, dv / d n_k
+    for (int i = 0; i < 3; ++i) {
+        for (int k = 0; k < 3; ++k) {
+            Jw[i][k] = Mi[i][0] * s[COV_EG + 3 * k] + Mi[i][1] * s[COV_EG + 3 * k + 1] + Mi[i][2] * s[COV_EG + 3 * k + 2];
+            Jn[i][k] = Mi[i][0] * s[COV_EN + 3 * k] + Mi[i][1] * s[COV_EN + 3 * k + 1] + Mi[i][2] * s[COV_EN + 3 * k + 2];
+        }
+        Jd[i] = Mi[i][0] * s[COV_ED] + Mi[i][1] * s[COV_ED + 1] + Mi[i][2] * s[COV_ED + 2];
+    }
+    double Jt[3][3];                                             // the gyro's total Jacobian into v - omega x t: Jw + [t]x
+    const double tt[3] = {t ? t[0] : 0.0, t ? t[1] : 0.0, t ? t[2] : 0.0};
+    const double Tx[3][3] = {{0.0, -tt[2], tt[1]}, {tt[2], 0.0, -tt[0]}, {-tt[1], tt[0], 0.0}};
+    const double Wx[3][3] = {{0.0, -om[2], om[1]}, {om[2], 0.0, -om[0]}, {-om[1], om[0], 0.0}};
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Jt[i][j] = Jw[i][j] + Tx[i][j];
+    const double sd2 = cc.sd * cc.sd, sn2 = cc.sn * cc.sn, so2 = t ? cc.soff * cc.soff : 0.0;
+    double Cv[3][3], Cu[3][3], tr[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double cg = Jw[i][0] * ovar[0] * Jw[j][0] + Jw[i][1] * ovar[1] * Jw[j][1] + Jw[i][2] * ovar[2] * Jw[j][2];
+            const double cgt = Jt[i][0] * ovar[0] * Jt[j][0] + Jt[i][1] * ovar[1] * Jt[j][1] + Jt[i][2] * ovar[2] * Jt[j][2];
+            const double cd = sd2 * (Jd[i] * Jd[j]);
+            const double cn = sn2 * (Jn[i][0] * Jn[j][0] + Jn[i][1] * Jn[j][1] + Jn[i][2] * Jn[j][2]);
+            const double cl = so2 * (Wx[i][0] * Wx[j][0] + Wx[i][1] * Wx[j][1] + Wx[i][2] * Wx[j][2]);
+            Cv[i][j] = Cf[i][j] + Cx[i][j] + cg + cd + cn;
+            Cu[i][j] = Cf[i][j] + Cx[i][j] + cgt + cd + cn + cl;
+            if (i == j) { tr[0] += Cf[i][i]; tr[1] += Cx[i][i]; tr[2] += cg; tr[3] += cd; tr[4] += cn; tr[5] += cl; }
+        }
+    if (R) {                                                     // C_uav = R Cu R^T, R taken as exact
+        double T[3][3];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) T[i][j] = R[3 * i] * Cu[0][j] + R[3 * i + 1] * Cu[1][j] + R[3 * i + 2] * Cu[2][j];
+        for (int i = 0; i < 3; ++i) for (int j = i; j < 3; ++j) Cu[i][j] = Cu[j][i] = T[i][0] * R[3 * j] + T[i][1] * R[3 * j + 1] + T[i][2] * R[3 * j + 2];
+    }
+    o[0] = Cv[0][0]; o[1] = Cv[0][1]; o[2] = Cv[0][2]; o[3] = Cv[1][1]; o[4] = Cv[1][2]; o[5] = Cv[2][2];
+    o[6] = Cu[0][0]; o[7] = Cu[0][1]; o[8] = Cu[0][2]; o[9] = Cu[1][1]; o[10] = Cu[1][2]; o[11] = Cu[2][2];
+    o[12] = s2; o[13] = 0.0; o[14] = 0.0; o[15] = 0.0;
+    for (int k = 0; k < 6; ++k) o[16 + k] = tr[k];
+    o[22] = 0.0; o[23] = 0.0;
+    bool fin = true;
+    for (int k = 0; k < OFK_COV_DOUBLES; ++k) fin = fin && isfinite(o[k]);
+    if (!fin) cov_void(o);
+}
+
+static cov_cfg cov_make_cfg(const ofk_cov *c)
+{
+    cov_cfg cc;
+    cc.mode = c->mode; cc.sf = c->sigma_flow; cc.sp = c->sigma_pos; cc.sd = c->sigma_d;
+    for (int k = 0; k < 3; ++k) cc.so[k] = c->sigma_omega[k];
+    cc.sn = c->sigma_normal; cc.soff = c->sigma_offset; cc.omega_from_imu = c->omega_from_imu; cc.filter_r = c->filter_r;
+    cc.r_floor = c->r_floor; cc.nis_max = c->nis_max;
+    return cc;
+}
+
+// ------------------------------------------------------------------------------------------------ stage entry (host buffers)
+// Behind k_solve / k_solve_robust: out holds the solve's eight doubles (v less omega x t when t is given), weights (nullable) the robust
+// solve's.  sigma_flow / sigma_pos are in the units of x and u.
+__global__ __launch_bounds__(256) void k_cov_solve(int variant, const double *__restrict__ x, const double *__restrict__ u,
+                                                   const uint8_t *__restrict__ valid, int n, const double *__restrict__ d,
+                                                   const double *__restrict__ nrm, const double *__restrict__ omega,
+                                                   const double *__restrict__ t, const double *__restrict__ weights, cov_cfg cc,
+                                                   const double *__restrict__ out, double *__restrict__ cov)
+{
+    __shared__ double part[4][COV_SUMS];
+    const int b = blockIdx.x;
+    const double *xb = x + (size_t)b * n * 2, *ub = u + (size_t)b * n * 2;
+    const uint8_t *vb = valid ? valid + (size_t)b * n : nullptr;
+    const double *wb = weights ? weights + (size_t)b * n : nullptr;
+    const double nb[3] = {nrm[3 * b], nrm[3 * b + 1], nrm[3 * b + 2]}, ob[3] = {omega[3 * b], omega[3 * b + 1], omega[3 * b + 2]};
+    const double db = d[b];
+    const double *o = out + (size_t)b * OFK_SOLVE_DOUBLES;
+    double v[3] = {o[0], o[1], o[2]};
+    if (t) {                                                    // the record holds v - omega x t
+        const double *tb = t + 3 * b;
+        v[0] += ob[1] * tb[2] - ob[2] * tb[1]; v[1] += ob[2] * tb[0] - ob[0] * tb[2]; v[2] += ob[0] * tb[1] - ob[1] * tb[0];
+    }
+    cov_core<4>(part, n, variant, nb, ob, db, v, [&](int i, double &px, double &py, double &ux, double &uy, double &w) {
+        if (vb && !vb[i]) return false;
+        w = wb ? wb[i] : 1.0;
+        if (!(w > 0.0)) return false;
+        px = xb[2 * i]; py = xb[2 * i + 1]; ux = ub[2 * i]; uy = ub[2 * i + 1];
+        return true;
+    });
+    if (threadIdx.x == 0) {
+        const double ovar[3] = {cc.so[0] * cc.so[0], cc.so[1] * cc.so[1], cc.so[2] * cc.so[2]};
+        cov_finish(part[0], cc, cc.sf, cc.sp, ovar, ob, t ? t + 3 * b : nullptr, nullptr, o[3], o[4], db != 0.0, cov + (size_t)b * OFK_COV_DOUBLES);
+    }
+}
+
+void ofk_launch_cov_solve(hipStream_t s, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                          const double *d, const double *nrm, const double *omega, const double *t, const double *weights,
+                          const ofk_cov *c, const double *out, double *cov)
+{
+    hipLaunchKernelGGL(k_cov_solve, dim3(batch), dim3(256), 0, s, variant, x, u, valid, n, d, nrm, omega, t, weights, cov_make_cfg(c), out, cov);
+}
+
+// ------------------------------------------------------------------------------------------------ frame pairs / plain stream step
+// Behind k_pairs_solve[_wg] / k_pairs_robust: the same inputs, the pair's record and (robust) weight row.  sigma_flow / sigma_pos are
+// pixels: the points are scaled by the pair's `scaling`, so are they.
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_pairs_cov(const float *__restrict__ prev_pts, const float *__restrict__ next_pts,
+                                                       const uint8_t *__restrict__ status, const int *__restrict__ counts, int pts_stride,
+                                                       const double *__restrict__ sensors, int variant, int use_feas, double feas_T,
+                                                       const double *__restrict__ weights, cov_cfg cc,
+                                                       const double *__restrict__ records, double *__restrict__ cov)
+{
+    __shared__ double part[4][COV_SUMS];
+    const int b = blockIdx.x;
+    const double *sn = sensors + (size_t)b * OFK_SENSOR_DOUBLES;
+    const double d = sn[0], nrm[3] = {sn[1], sn[2], sn[3]}, om[3] = {sn[4], sn[5], sn[6]};
+    const double scaling = sn[19], cx = sn[20], cy = sn[21], vp[3] = {sn[22], sn[23], sn[24]};
+    const int n = min(max(counts[b], 0), pts_stride);
+    const float *pp = prev_pts + (size_t)b * pts_stride * 2, *np_ = next_pts + (size_t)b * pts_stride * 2;
+    const uint8_t *st = status + (size_t)b * pts_stride;
+    const double *wrow = weights ? weights + (size_t)b * pts_stride : nullptr;
+    const double *r = records + (size_t)b * OFK_RECORD_DOUBLES;
+    const double v[3] = {r[0], r[1], r[2]};
+    cov_core<NW>(part, n, variant, nrm, om, d, v, [&](int i, double &x, double &y, double &ux, double &uy, double &w) {
+        if (!st[i]) return false;
+        w = wrow ? wrow[i] : 1.0;
+        if (!(w > 0.0)) return false;
+        return pair_point(pp, np_, i, cx, cy, scaling, use_feas, feas_T, nrm, vp, d, x, y, ux, uy);
+    });
+    if (threadIdx.x == 0) {
+        const double ovar[3] = {cc.so[0] * cc.so[0], cc.so[1] * cc.so[1], cc.so[2] * cc.so[2]};
+        cov_finish(part[0], cc, cc.sf * scaling, cc.sp * scaling, ovar, om, sn + 16, sn + 7, r[3], r[4], scaling != 0.0 && d != 0.0,
+                   cov + (size_t)b * OFK_COV_DOUBLES);
+    }
+}
+
+void ofk_launch_pairs_cov(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts,
+                          int pts_stride, const double *sensors, int variant, int use_feas, double feas_T, const double *weights,
+                          const ofk_cov *c, const double *records, double *cov, int batch)
+{
+    const cov_cfg cc = cov_make_cfg(c);
+    // ofk_launch_pairs_solve's rule and reason
+    if (batch >= 128)
+        hipLaunchKernelGGL(k_pairs_cov<1>, dim3(batch), dim3(64), 0, s, prev_pts, next_pts, status, counts, pts_stride, sensors, variant,
+                           use_feas, feas_T, weights, cc, records, cov);
+    else
+        hipLaunchKernelGGL(k_pairs_cov<4>, dim3(batch), dim3(256), 0, s, prev_pts, next_pts, status, counts, pts_stride, sensors, variant,
+                           use_feas, feas_T, weights, cc, records, cov);
+}
+
+// ------------------------------------------------------------------------------------------------ the filter's correct with R_eff
+// R_eff = Rm with its top-left 3x3 block replaced by z_sign^2 C + r_floor I (filter_r, a covariance that is not void), else Rm;
+// NIS = nu^T S^-1 nu of the correct; with nis_max > 0 a correct whose NIS exceeds it is skipped (x, P stay at the prediction).
+// The correct itself is kf_correct_dev: with R_eff = Rm it is the constant-R correct bit for bit.  Returns whether it was gated.
+__device__ bool kf_correct_cov_dev(int ns, int nm, const double *H, const double *Rm, const double *z, const double *cv, const cov_cfg &cc,
+                                   double z_sign, int z_source, double *x, double (*P)[KF_MAX], double &nis)
+{
+    double Re[KF_MAX * KF_MAX];
+    for (int i = 0; i < nm * nm; ++i) Re[i] = Rm[i];
+    if (cc.filter_r && cv[13] == 0.0) {
+        const double *t6 = cv + (z_source ? 6 : 0);
+        const double C[3][3] = {{t6[0], t6[1], t6[2]}, {t6[1], t6[3], t6[4]}, {t6[2], t6[4], t6[5]}};
+        for (int i = 0; i < 3 && i < nm; ++i)
+            for (int j = 0; j < 3 && j < nm; ++j) Re[i * nm + j] = z_sign * z_sign * C[i][j] + (i == j ? cc.r_floor : 0.0);
+    }
+    double S[KF_MAX][KF_MAX + 1];                                // [S | nu], solved in place
+    for (int i = 0; i < nm; ++i) {
+        double hx = 0;
+        for (int k = 0; k < ns; ++k) hx += H[i * ns + k] * x[k];
+        S[i][nm] = z[i] - hx;
+        for (int j = 0; j < nm; ++j) {
+            double s = 0;
+            for (int k = 0; k < ns; ++k) for (int l = 0; l < ns; ++l) s += H[i * ns + k] * P[k][l] * H[j * ns + l];
+            S[i][j] = s + Re[i * nm + j];
+        }
+    }
+    double nu[KF_MAX];
+    for (int i = 0; i < nm; ++i) nu[i] = S[i][nm];
+    for (int c = 0; c < nm; ++c) {
+        int piv = c; double best = fabs(S[c][c]);
+        for (int r2 = c + 1; r2 < nm; ++r2) if (fabs(S[r2][c]) > best) { best = fabs(S[r2][c]); piv = r2; }
+        if (piv != c) for (int j = 0; j <= nm; ++j) { const double tmp = S[c][j]; S[c][j] = S[piv][j]; S[piv][j] = tmp; }
+        const double inv = 1.0 / S[c][c];
+        for (int j = 0; j <= nm; ++j) S[c][j] *= inv;
+        for (int r2 = 0; r2 < nm; ++r2) if (r2 != c) {
+            const double f = S[r2][c];
+            if (f != 0.0) for (int j = 0; j <= nm; ++j) S[r2][j] -= f * S[c][j];
+        }
+    }
+    nis = 0.0;
+    for (int i = 0; i < nm; ++i) nis += nu[i] * S[i][nm];
+    if (cc.nis_max > 0.0 && nis > cc.nis_max) return true;
+    kf_correct_dev(ns, nm, H, Re, z, x, P);
+    return false;
+}
+
+// k_kf_records with R_eff, NIS and the gate: one thread per pair, behind the pairs' covariance kernel.
+__global__ void k_kf_records_cov(int ns, int nm, const double *__restrict__ mats, double *__restrict__ xs, double *__restrict__ Ps,
+                                 const double *__restrict__ records, double *__restrict__ cov, cov_cfg cc, double z_sign, int z_source, int batch)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    const double *F = mats, *H = mats + 72, *Q = mats + 108, *Rm = mats + 144;
+    double x[KF_MAX], P[KF_MAX][KF_MAX];
+    kf_load(ns, b, xs, Ps, x, P);
+    kf_predict_dev(ns, 0, F, nullptr, Q, nullptr, x, P);
+    const double *r = records + (size_t)b * OFK_RECORD_DOUBLES;
+    double *cv = cov + (size_t)b * OFK_COV_DOUBLES;
+    double nis = 0.0, gated = 0.0;
+    if (r[4] == 3.0) {
+        double z[KF_MAX] = {0, 0, 0, 0, 0, 0};
+        for (int k = 0; k < 3; ++k) z[k] = z_sign * r[(z_source ? 8 : 0) + k];
+        for (int k = 3; k < nm; ++k) z[k] = z[k - 3];
+        gated = kf_correct_cov_dev(ns, nm, H, Rm, z, cv, cc, z_sign, z_source, x, P, nis) ? 1.0 : 0.0;
+    }
+    cv[14] = nis; cv[15] = gated;
+    kf_store(ns, b, x, P, xs, Ps);
+}
+
+void ofk_launch_kf_records_cov(hipStream_t s, int ns, int nm, const double *mats, double *x, double *P, const double *records, double *cov,
+                               const ofk_cov *c, double z_sign, int z_source, int batch)
+{
+    hipLaunchKernelGGL(k_kf_records_cov, dim3((batch + 63) / 64), dim3(64), 0, s, ns, nm, mats, x, P, records, cov, cov_make_cfg(c), z_sign,
+                       z_source, batch);
+}
+
+// ------------------------------------------------------------------------------------------------ fused stream step
+// Behind k_stream_fuse / k_stream_fuse_robust, which with a covariance setting on leave the filter at its prediction (fuse_args.defer):
+// `status` holds the keep flags by now, so the set is status (and w > 0).  The correct runs here, with R_eff, and fused[0..7] is rewritten.
+__global__ __launch_bounds__(256) void k_stream_cov(fuse_args g, const double *__restrict__ weights, cov_cfg cc, double *__restrict__ cov)
+{
+    __shared__ double part[4][COV_SUMS];
+    const int b = blockIdx.x;
+    const double *sn = g.sensors + (size_t)b * OFK_SENSOR_DOUBLES;
+    const double d = sn[0], scaling = sn[19], cx = sn[20], cy = sn[21];
+    const double *ist = g.f.use_imu && g.imu_state ? g.imu_state + (size_t)b * OFK_IMU_STATE : nullptr;
+    double nrm[3], om[3];
+    for (int k = 0; k < 3; ++k) { nrm[k] = ist ? ist[15 + k] : sn[1 + k]; om[k] = ist ? ist[18 + k] : sn[4 + k]; }
+    const int n = min(max(g.counts[b], 0), g.pts_stride);
+    const float *pp = g.prev_pts + (size_t)b * g.pts_stride * 2, *np_ = g.next_pts + (size_t)b * g.pts_stride * 2;
+    const uint8_t *st = g.status + (size_t)b * g.pts_stride;
+    const double *wrow = weights ? weights + (size_t)b * g.pts_stride : nullptr;
+    const double *r = g.records + (size_t)b * OFK_RECORD_DOUBLES;
+    const double v[3] = {r[0], r[1], r[2]};
+    cov_core<4>(part, n, g.variant, nrm, om, d, v, [&](int i, double &x, double &y, double &ux, double &uy, double &w) {
+        if (!st[i]) return false;
+        w = wrow ? wrow[i] : 1.0;
+        if (!(w > 0.0)) return false;
+        return pair_point(pp, np_, i, cx, cy, scaling, 0, 0.0, nrm, v, d, x, y, ux, uy);     // fuse_terms' x, y, u of OFK_FLOW_LK
+    });
+    if (threadIdx.x == 0) {
+        double *cv = cov + (size_t)b * OFK_COV_DOUBLES;
+        double ovar[3];
+        for (int k = 0; k < 3; ++k) ovar[k] = cc.omega_from_imu && ist ? ist[21 + k] : cc.so[k] * cc.so[k];
+        cov_finish(part[0], cc, cc.sf * scaling, cc.sp * scaling, ovar, om, sn + 16, ist ? ist + 6 : sn + 7, r[3], r[4],
+                   scaling != 0.0 && d != 0.0, cv);
+        if (g.f.filter && g.defer) {
+            double kx[KF_MAX], kP[KF_MAX][KF_MAX], nis = 0.0, gated = 0.0;
+            kf_load(g.ns, b, g.kf_x, g.kf_P, kx, kP);
+            const bool solved = r[15] != 0.0;
+            if (solved) {
+                double z[KF_MAX] = {0, 0, 0, 0, 0, 0};
+                for (int k = 0; k < 3; ++k) z[k] = g.f.z_sign * r[(g.f.z_source ? 8 : 0) + k];
+                for (int k = 3; k < g.nm; ++k) z[k] = sn[22 + (k - 3)];
+                gated = kf_correct_cov_dev(g.ns, g.nm, g.H, g.Rm, z, cv, cc, g.f.z_sign, g.f.z_source, kx, kP, nis) ? 1.0 : 0.0;
+                kf_store(g.ns, b, kx, kP, g.kf_x, g.kf_P);
+            }
+            cv[14] = nis; cv[15] = gated;
+            double *fu = g.fused + (size_t)b * 8, tr = 0.0;
+            for (int i = 0; i < g.ns; ++i) tr += kP[i][i];
+            for (int k = 0; k < 6; ++k) fu[k] = k < g.ns ? kx[k] : 0.0;
+            fu[6] = tr; fu[7] = solved ? 1.0 : 0.0;
+        }
+    }
+}
+
+void ofk_launch_stream_cov(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
+                           const double *sensors, double *imu_state, int ns, int nm, int nc, const double *kf_mats, double *kf_x, double *kf_P,
+                           const ofk_fusion *f, int variant, double *records, double *fused, const double *weights, const ofk_cov *c,
+                           double *cov, int batch)
+{
+    fuse_args g;
+    g.prev_pts = prev_pts; g.next_pts = next_pts; g.status = status; g.counts = counts; g.pts_stride = pts_stride; g.sensors = sensors;
+    g.imu_state = imu_state; g.imu_dv = nullptr; g.ns = ns; g.nm = nm; g.nc = nc;
+    g.F = kf_mats; g.Bm = kf_mats + 36; g.H = kf_mats + 72; g.Q = kf_mats + 108; g.Rm = kf_mats + 144; g.kf_x = kf_x; g.kf_P = kf_P;
+    g.f = *f; g.variant = variant; g.use_feas = 0; g.feas_T = 0.0; g.records = records; g.fused = fused; g.defer = 1;
+    hipLaunchKernelGGL(k_stream_cov, dim3(batch), dim3(256), 0, s, g, weights, cov_make_cfg(c), cov);
+}

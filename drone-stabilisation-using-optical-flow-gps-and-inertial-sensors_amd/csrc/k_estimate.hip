@@ -711,6 +711,7 @@ struct fuse_args {
     int ns, nm, nc; const double *F, *Bm, *H, *Q, *Rm; double *kf_x, *kf_P;
     ofk_fusion f; int variant, use_feas; double feas_T;
     double *records, *fused;
+    int defer;                                                   // 1: the filter stays at its prediction, k_stream_cov corrects (k_cov.inc)
 };
 
 // Point i's terms: x, y (centred, scaled), the flow u, and in the legacy keep mode the weight dist_i with its r_tilde (rl).
@@ -802,7 +803,7 @@ __global__ __launch_bounds__(256) void k_stream_fuse(fuse_args g)
         o[14] = 0.0; o[15] = solved ? 1.0 : 0.0;
         double *fu = g.fused + (size_t)b * 8;
         if (g.f.filter) {
-            if (solved) {
+            if (solved && !g.defer) {
                 double z[KF_MAX] = {0, 0, 0, 0, 0, 0};
                 for (int k = 0; k < 3; ++k) z[k] = g.f.z_sign * (g.f.z_source ? vu[k] : s.v[k]);
                 for (int k = 3; k < g.nm; ++k) z[k] = sn[22 + (k - 3)];               // a second velocity measurement (FilterModel.ekf6(gps=True)): the sensors' prior slot
@@ -824,13 +825,13 @@ __global__ __launch_bounds__(256) void k_stream_fuse(fuse_args g)
 void ofk_launch_stream_fuse(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
                             const double *sensors, double *imu_state, double *imu_dv, int ns, int nm, int nc, const double *kf_mats,
                             double *kf_x, double *kf_P, const ofk_fusion *f, int variant, int use_feas, double feas_T, double *records,
-                            double *fused, int batch)
+                            double *fused, int batch, int defer_correct)
 {
     fuse_args g;
     g.prev_pts = prev_pts; g.next_pts = next_pts; g.status = status; g.counts = counts; g.pts_stride = pts_stride; g.sensors = sensors;
     g.imu_state = imu_state; g.imu_dv = imu_dv; g.ns = ns; g.nm = nm; g.nc = nc;
     g.F = kf_mats; g.Bm = kf_mats + 36; g.H = kf_mats + 72; g.Q = kf_mats + 108; g.Rm = kf_mats + 144; g.kf_x = kf_x; g.kf_P = kf_P;
-    g.f = *f; g.variant = variant; g.use_feas = use_feas; g.feas_T = feas_T; g.records = records; g.fused = fused;
+    g.f = *f; g.variant = variant; g.use_feas = use_feas; g.feas_T = feas_T; g.records = records; g.fused = fused; g.defer = defer_correct;
     hipLaunchKernelGGL(k_stream_fuse, dim3(batch), dim3(256), 0, s, g);
 }
 
@@ -1265,3 +1266,6 @@ void ofk_launch_associate(hipStream_t s, const double *t_img, int n_img, int n_i
 
 // ------------------------------------------------------------------------------------------------ robust solve
 #include "k_robust.inc"
+
+// ------------------------------------------------------------------------------------------------ velocity covariance
+#include "k_cov.inc"

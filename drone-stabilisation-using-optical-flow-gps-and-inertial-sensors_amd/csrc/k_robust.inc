@@ -453,7 +453,7 @@ __global__ __launch_bounds__(256) void k_stream_fuse_robust(fuse_args g, rob_fus
         o[14] = 0.0; o[15] = solved ? 1.0 : 0.0;
         double *fu = g.fused + (size_t)b * 8;
         if (g.f.filter) {
-            if (solved) {
+            if (solved && !g.defer) {
                 double z[KF_MAX] = {0, 0, 0, 0, 0, 0};
                 for (int k = 0; k < 3; ++k) z[k] = g.f.z_sign * (g.f.z_source ? vu[k] : R.v[k]);
                 for (int k = 3; k < g.nm; ++k) z[k] = sn[22 + (k - 3)];
@@ -475,13 +475,14 @@ __global__ __launch_bounds__(256) void k_stream_fuse_robust(fuse_args g, rob_fus
 void ofk_launch_stream_fuse_robust(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
                                    const double *sensors, double *imu_state, double *imu_dv, int ns, int nm, int nc, const double *kf_mats,
                                    double *kf_x, double *kf_P, const ofk_fusion *f, int variant, int use_feas, double feas_T, double *records,
-                                   double *fused, const ofk_robust *r, double *work, double *weights, double *wtmp, double *stats, int batch)
+                                   double *fused, const ofk_robust *r, double *work, double *weights, double *wtmp, double *stats, int batch,
+                                   int defer_correct)
 {
     fuse_args g;
     g.prev_pts = prev_pts; g.next_pts = next_pts; g.status = status; g.counts = counts; g.pts_stride = pts_stride; g.sensors = sensors;
     g.imu_state = imu_state; g.imu_dv = imu_dv; g.ns = ns; g.nm = nm; g.nc = nc;
     g.F = kf_mats; g.Bm = kf_mats + 36; g.H = kf_mats + 72; g.Q = kf_mats + 108; g.Rm = kf_mats + 144; g.kf_x = kf_x; g.kf_P = kf_P;
-    g.f = *f; g.variant = variant; g.use_feas = use_feas; g.feas_T = feas_T; g.records = records; g.fused = fused;
+    g.f = *f; g.variant = variant; g.use_feas = use_feas; g.feas_T = feas_T; g.records = records; g.fused = fused; g.defer = defer_correct;
     const rob_fuse_args ra = {{r->loss, r->c, r->iters, r->hypotheses, (unsigned)r->seed, (unsigned)(r->seed >> 32), r->drop}, work, weights, wtmp, stats};
     hipLaunchKernelGGL(k_stream_fuse_robust, dim3(batch), dim3(256), 0, s, g, ra);
 }

@@ -149,6 +149,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->lk_seed_mode = OFK_SEED_OFF; c->lk_seed_gain = 1.0;
     c->robust = ofk_robust{OFK_ROBUST_OFF, 4.685, 5, 64, 0ull, 0};
     c->gate = ofk_track_gate{OFK_FB_OFF, 0.5, -1, 0.0};
+    c->cov = ofk_cov{OFK_COV_OFF, 0.0, 0.0, 0.0, {0.0, 0.0, 0.0}, 0.0, 0.0, 0, 0, 0.0, 0.0};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -201,7 +202,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     for (int k = 0; k < 2; ++k) { if (c->bgr[k]) hipFree(c->bgr[k]); if (c->pyr[k]) hipFree(c->pyr[k]); }
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
-                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats};
+                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
@@ -921,20 +922,76 @@ static int robust_alloc(ofk_ctx *c)
     return OFK_OK;
 }
 
-// The solve of nb pairs from pair b0 on (their views' pointers): the plain kernels, or with ofk_set_robust on the robust ones.
+// ------------------------------------------------------------------------------------------------ velocity covariance setting
+static int check_cov(ofk_ctx *c, const ofk_cov *v, const char *who)
+{
+    if (v->mode != OFK_COV_OFF && v->mode != OFK_COV_PROPAGATE && v->mode != OFK_COV_RESIDUAL)
+        return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is none of OFK_COV_OFF, _PROPAGATE, _RESIDUAL", who, v->mode);
+    const double vals[10] = {v->sigma_flow, v->sigma_pos, v->sigma_d, v->sigma_omega[0], v->sigma_omega[1], v->sigma_omega[2], v->sigma_normal,
+                             v->sigma_offset, v->r_floor, v->nis_max};
+    for (int k = 0; k < 10; ++k)
+        if (!(std::isfinite(vals[k]) && vals[k] >= 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: a sigma, r_floor or nis_max is negative or not finite (%g)", who, vals[k]);
+    if ((v->omega_from_imu != 0 && v->omega_from_imu != 1) || (v->filter_r != 0 && v->filter_r != 1))
+        return ofk_fail(c, OFK_E_INVALID, "%s: omega_from_imu and filter_r are 0 or 1", who);
+    if (v->filter_r && v->mode == OFK_COV_OFF) return ofk_fail(c, OFK_E_INVALID, "%s: filter_r needs a covariance: mode is OFK_COV_OFF", who);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_cov(ofk_ctx *c, const ofk_cov *v)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!v) { c->cov.mode = OFK_COV_OFF; c->cov.filter_r = 0; return OFK_OK; }
+    TRY(check_cov(c, v, "ofk_set_cov"));
+    c->cov = *v;
+    return OFK_OK;
+}
+
+extern "C" int ofk_get_cov(const ofk_ctx *c, ofk_cov *v)
+{
+    if (!c || !v) return OFK_E_INVALID;
+    *v = c->cov;
+    return OFK_OK;
+}
+
+static int cov_alloc(ofk_ctx *c)
+{
+    if (c->cov_rec) return OFK_OK;
+    OFK_HIP(c, hipMalloc((void **)&c->cov_rec, (size_t)c->max_batch * OFK_COV_DOUBLES * 8));
+    return OFK_OK;
+}
+
+extern "C" int ofk_cov_download(ofk_ctx *c, double *cov)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->cov_batch < 1 || !c->cov_rec) return ofk_fail(c, OFK_E_INVALID, "ofk_cov_download: no run or step with ofk_set_cov on yet");
+    if (!cov) return ofk_fail(c, OFK_E_INVALID, "ofk_cov_download: NULL buffer");
+    TRY(enter(c));
+    OFK_HIP(c, hipMemcpyAsync(cov, c->cov_rec, (size_t)c->cov_batch * OFK_COV_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+// The solve of nb pairs from pair b0 on (their views' pointers): the plain kernels, or with ofk_set_robust on the robust ones; with
+// ofk_set_cov on the covariance kernel behind either.
 // drop_status: the stream steps' keep flags (cleared for zero-weight points when the setting asks for it), NULL for frame pairs.
 static void solve_pairs(ofk_ctx *c, hipStream_t st, const float *pts_prev, const float *pts_next, uint8_t *status, const int *counts,
                         const double *sensors, const ofk_params *p, const int *cand_count, double *records, int b0, int nb, bool stream)
 {
+    const size_t o = (size_t)b0 * c->max_pts;
     if (c->robust.loss == OFK_ROBUST_OFF) {
         ofk_launch_pairs_solve(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
                                cand_count, records, nb);
+        if (c->cov.mode != OFK_COV_OFF)
+            ofk_launch_pairs_cov(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
+                                 nullptr, &c->cov, records, c->cov_rec + (size_t)b0 * OFK_COV_DOUBLES, nb);
         return;
     }
-    const size_t o = (size_t)b0 * c->max_pts;
     ofk_launch_pairs_robust(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
                             cand_count, &c->robust, b0, c->rob_work + o * 7, c->rob_w + o, c->rob_wtmp + o,
                             c->rob_stats + (size_t)b0 * OFK_ROBUST_DOUBLES, stream && c->robust.drop ? status : nullptr, records, nb);
+    if (c->cov.mode != OFK_COV_OFF)
+        ofk_launch_pairs_cov(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
+                             c->rob_w + o, &c->cov, records, c->cov_rec + (size_t)b0 * OFK_COV_DOUBLES, nb);
 }
 
 extern "C" int ofk_robust_download(ofk_ctx *c, double *weights, int stride, double *stats)
@@ -1137,6 +1194,42 @@ extern "C" int ofk_velocity_solve_robust(ofk_ctx *c, int variant, const double *
     TRY(check_launch(c, "k_solve_robust"));
     if (weights) TRY(get(c, weights, dwts, wb));
     if (stats) TRY(get(c, stats, dst, (size_t)batch * OFK_ROBUST_DOUBLES * 8));
+    return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
+}
+
+extern "C" int ofk_velocity_solve_cov(ofk_ctx *c, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                                      const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
+                                      const ofk_robust *r, const ofk_cov *cv, double *out, double *cov)
+{
+    if (!c || !x || !u || !nrm || !out || !cov || !cv || batch < 1 || n < 1 || n > 4096 || variant < 0 || variant > 2)
+        return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_cov: bad argument");
+    if (variant == OFK_SOLVE_OFMODULE) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_cov: OFK_SOLVE_OFMODULE is not the sensor model: no covariance");
+    if (!d || !omega) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_cov: missing input for variant %d", variant);
+    (void)wgt;
+    TRY(check_cov(c, cv, "ofk_velocity_solve_cov"));
+    if (cv->mode == OFK_COV_OFF || cv->filter_r) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_cov: mode must be PROPAGATE or RESIDUAL, filter_r 0");
+    const bool rob = r && r->loss != OFK_ROBUST_OFF;
+    if (rob) TRY(check_robust(c, r, "ofk_velocity_solve_cov"));
+    const size_t pb = (size_t)batch * n * 16, wb = (size_t)batch * n * 8;
+    Bump bp;
+    TRY(est_begin(c, 2 * pb + (size_t)batch * n * 9 + 9 * wb + (size_t)batch * 256 * 10, bp));
+    double *dx = bp.put(x, pb), *du = bp.put(u, pb);
+    uint8_t *dval = (uint8_t *)bp.put(valid, (size_t)batch * n);
+    double *dd = bp.put(d, batch * 8), *dn = bp.put(nrm, batch * 24), *dom = bp.put(omega, batch * 24), *dt = bp.put(t, batch * 24),
+           *dout = bp.take((size_t)batch * OFK_SOLVE_DOUBLES * 8), *dcov = bp.take((size_t)batch * OFK_COV_DOUBLES * 8), *dwts = nullptr;
+    if (rob) {
+        double *dwork = bp.take(7 * wb);
+        dwts = bp.take(wb);
+        double *dtmp = bp.take(wb), *dst = bp.take((size_t)batch * OFK_ROBUST_DOUBLES * 8);
+        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_cov: upload failed");
+        ofk_launch_solve_robust(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, r, dwork, dwts, dtmp, dst, dout);
+    } else {
+        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_cov: upload failed");
+        ofk_launch_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, dout);
+    }
+    ofk_launch_cov_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, dwts, cv, dout, dcov);
+    TRY(check_launch(c, "k_cov_solve"));
+    TRY(get(c, cov, dcov, (size_t)batch * OFK_COV_DOUBLES * 8));
     return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
 }
 
@@ -1504,6 +1597,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
     const bool fork = S > 1 && !c->slices_open;
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
+    if (c->cov.mode != OFK_COV_OFF) { TRY(cov_alloc(c)); c->cov_batch = B; }
     TRY(need_streams(c, S, overlap));
     if (fork) {
         OFK_HIP(c, hipEventRecord(c->ev_fork, c->stream));
@@ -1791,7 +1885,10 @@ extern "C" int ofk_pairs_filter_step(ofk_ctx *c, double z_sign, int z_source, in
     TRY(use_device(c));
     hipStream_t s;
     TRY(tail_stream(c, &s));
-    ofk_launch_kf_records(s, c->kf_ns, c->kf_nm, c->kf_mats, c->kf_x, c->kf_P, c->records, z_sign, z_source, batch);
+    if (c->cov.mode != OFK_COV_OFF && c->cov_rec && c->cov_batch >= batch)       // behind a run with the setting on: R_eff, NIS, the gate
+        ofk_launch_kf_records_cov(s, c->kf_ns, c->kf_nm, c->kf_mats, c->kf_x, c->kf_P, c->records, c->cov_rec, &c->cov, z_sign, z_source, batch);
+    else
+        ofk_launch_kf_records(s, c->kf_ns, c->kf_nm, c->kf_mats, c->kf_x, c->kf_P, c->records, z_sign, z_source, batch);
     TRY(tail_done(c, s));
     return check_launch(c, "k_kf_records");
 }
@@ -1817,6 +1914,11 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         TRY(filters_alloc(c));
     } else if (p->solve_variant != OFK_SOLVE_NODE && p->solve_variant != OFK_SOLVE_SIM) return ofk_fail(c, OFK_E_INVALID, "solve_variant must be NODE or SIM");
     TRY(check_grid(c, &c->grid, h, w, "ofk_stream_step"));
+    const bool cov_on = c->cov.mode != OFK_COV_OFF;
+    if (cov_on && fu && (p->solve_variant == OFK_SOLVE_OFMODULE || fu->flow == OFK_FLOW_ROTATIONAL))
+        return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused: OFK_SOLVE_OFMODULE / OFK_FLOW_ROTATIONAL are not the sensor model: no covariance (ofk_set_cov is on)");
+    if (cov_on) { TRY(cov_alloc(c)); c->cov_batch = B; }
+    const int defer = cov_on && fu && fu->filter ? 1 : 0;          // the covariance kernel corrects
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
@@ -1836,13 +1938,17 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     if (fu && c->robust.loss != OFK_ROBUST_OFF)
         ofk_launch_stream_fuse_robust(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
                                       c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, p->use_feasibility, p->feas_T,
-                                      c->records, c->fused, &c->robust, c->rob_work, c->rob_w, c->rob_wtmp, c->rob_stats, B);
+                                      c->records, c->fused, &c->robust, c->rob_work, c->rob_w, c->rob_wtmp, c->rob_stats, B, defer);
     else if (fu)
         ofk_launch_stream_fuse(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
                                c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, p->use_feasibility, p->feas_T,
-                               c->records, c->fused, B);
+                               c->records, c->fused, B, defer);
     else
         solve_pairs(c, c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->sensors, p, nullptr, c->records, 0, B, true);
+    if (cov_on && fu)
+        ofk_launch_stream_cov(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm,
+                              c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, c->records, c->fused,
+                              c->robust.loss != OFK_ROBUST_OFF ? c->rob_w : nullptr, &c->cov, c->cov_rec, B);
     // re-detection for the streams that had few features (node:157-166): mask = discs around the OLD positions, image = OLD frame.
     // The host knows the track counts from the previous call, so the whole branch is skipped when no stream needs it.
     // of_module.py:138 `continue`: a step of the ONE stream that did not solve leaves old_gray / old_pos as they were.  The host has to

@@ -94,6 +94,8 @@ struct ofk_ctx {
     ofk_corner_grid grid;                    // ofk_set_corner_grid: cell 0 (off) unless set
     int *grid_stats; int *grid_occ_counts; float *grid_occ;   // [B][2] statistics, [B] / [B][max_pts][2] occupancy list of the stage entries; one lazy allocation (grid_stats owns it)
     int grid_batch;                          // images of the latest selection with a grid on (ofk_corner_grid_download), 0 = none
+    ofk_cov cov;                             // ofk_set_cov: mode OFK_COV_OFF unless set
+    double *cov_rec; int cov_batch;          // [B][OFK_COV_DOUBLES] (lazily allocated); problems of the latest run / step with it on, 0 = none
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -188,7 +190,21 @@ void ofk_launch_solve_robust(hipStream_t s, int variant, const double *x, const 
 void ofk_launch_stream_fuse_robust(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
                                    const double *sensors, double *imu_state, double *imu_dv, int ns, int nm, int nc, const double *kf_mats,
                                    double *kf_x, double *kf_P, const ofk_fusion *f, int variant, int use_feas, double feas_T, double *records,
-                                   double *fused, const ofk_robust *r, double *work, double *weights, double *wtmp, double *stats, int batch);
+                                   double *fused, const ofk_robust *r, double *work, double *weights, double *wtmp, double *stats, int batch,
+                                   int defer_correct = 0);
+// the velocity covariance (k_cov.inc), behind the solve kernels; weights NULL = the plain solve ran; cov: the slice's rows of cov_rec
+void ofk_launch_cov_solve(hipStream_t s, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                          const double *d, const double *nrm, const double *omega, const double *t, const double *weights,
+                          const ofk_cov *c, const double *out, double *cov);
+void ofk_launch_pairs_cov(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts,
+                          int pts_stride, const double *sensors, int variant, int use_feas, double feas_T, const double *weights,
+                          const ofk_cov *c, const double *records, double *cov, int batch);
+void ofk_launch_stream_cov(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
+                           const double *sensors, double *imu_state, int ns, int nm, int nc, const double *kf_mats, double *kf_x, double *kf_P,
+                           const ofk_fusion *f, int variant, double *records, double *fused, const double *weights, const ofk_cov *c,
+                           double *cov, int batch);
+void ofk_launch_kf_records_cov(hipStream_t s, int ns, int nm, const double *mats, double *x, double *P, const double *records, double *cov,
+                               const ofk_cov *c, double z_sign, int z_source, int batch);
 void ofk_launch_records_f32(hipStream_t s, const double *records, float *dst, int batch);
 
 void ofk_launch_flow_model(hipStream_t s, const double *x, int batch, int n, const double *v, const double *omega,
@@ -206,7 +222,7 @@ void ofk_launch_imu_seq(hipStream_t s, double *state, double *dv, const double *
 void ofk_launch_stream_fuse(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
                             const double *sensors, double *imu_state, double *imu_dv, int ns, int nm, int nc, const double *kf_mats,
                             double *kf_x, double *kf_P, const ofk_fusion *f, int variant, int use_feas, double feas_T, double *records,
-                            double *fused, int batch);
+                            double *fused, int batch, int defer_correct = 0);     // defer_correct: see fuse_args.defer
 void ofk_launch_replace_tracks(hipStream_t s, const int *limit, const float *new_pts, const int *new_counts, int pts_stride, float *tracks,
                                int *counts, int batch);
 void ofk_launch_post_solve(hipStream_t s, const double *v_obs, const double *rot, const double *ang,

@@ -27,6 +27,7 @@ SYMBOLS = (
     "ofk_gray_bgr8", "ofk_pyr_down_u8", "ofk_pyramid_u8", "ofk_scharr_s16", "ofk_mineig_response", "ofk_select_corners",
     "ofk_good_features", "ofk_lk_pyr", "ofk_lk_pyr_ex", "ofk_predict_points", "ofk_set_lk_seed", "ofk_get_lk_seed", "ofk_flow_model", "ofk_feasibility", "ofk_velocity_solve", "ofk_imu_propagate",
     "ofk_set_robust", "ofk_get_robust", "ofk_robust_download", "ofk_velocity_solve_robust", "ofk_robust_pairs",
+    "ofk_set_cov", "ofk_get_cov", "ofk_cov_download", "ofk_velocity_solve_cov",
     "ofk_set_track_gate", "ofk_get_track_gate", "ofk_track_gate_download", "ofk_lk_pyr_fb",
     "ofk_set_corner_grid", "ofk_get_corner_grid", "ofk_corner_grid_download", "ofk_select_corners_grid", "ofk_good_features_grid",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
@@ -59,6 +60,9 @@ ROBUST_OFF, ROBUST_HUBER, ROBUST_TUKEY = 0, 1, 2         # ofk_set_robust / ofk_
 ROBUST_LOSSES = {"off": ROBUST_OFF, "huber": ROBUST_HUBER, "tukey": ROBUST_TUKEY}
 ROBUST_DEFAULT_C = {ROBUST_HUBER: 1.345, ROBUST_TUKEY: 4.685}     # 95 % efficiency on Gaussian residuals
 ROBUST_MIN_POINTS, ROBUST_DOUBLES = 8, 8
+COV_OFF, COV_PROPAGATE, COV_RESIDUAL = 0, 1, 2           # ofk_set_cov / ofk_velocity_solve_cov
+COV_MODES = {"off": COV_OFF, "propagate": COV_PROPAGATE, "residual": COV_RESIDUAL}
+COV_DOUBLES = 24
 FB_OFF, FB_PLAIN, FB_SEEDED = 0, 1, 2                    # ofk_set_track_gate / ofk_lk_pyr_fb
 FB_MODES = {"off": FB_OFF, "plain": FB_PLAIN, "seeded": FB_SEEDED}
 GRID_MAX_CELLS = 2048                                   # OFK_GRID_MAX_CELLS: cells of a corner grid over one frame
@@ -93,6 +97,32 @@ def robust_pairs(seed, problem, hypotheses, m):
     if rc != 0:
         raise OfkError(rc, f"ofk_robust_pairs: hypotheses {n} outside 0..256 or m {m} < 2")
     return i[:max(n, 0)], j[:max(n, 0)]
+
+
+class Cov(C.Structure):
+    """ofk_cov (include/ofk.h): the velocity covariance's setting."""
+    _fields_ = [("mode", C.c_int), ("sigma_flow", C.c_double), ("sigma_pos", C.c_double), ("sigma_d", C.c_double),
+                ("sigma_omega", C.c_double * 3), ("sigma_normal", C.c_double), ("sigma_offset", C.c_double), ("omega_from_imu", C.c_int),
+                ("filter_r", C.c_int), ("r_floor", C.c_double), ("nis_max", C.c_double)]
+
+
+def cov_setting(mode="propagate", sigma_flow=0.0, sigma_pos=0.0, sigma_d=0.0, sigma_omega=0.0, sigma_normal=0.0, sigma_offset=0.0,
+                omega_from_imu=False, filter_r=False, r_floor=0.0, nis_max=0.0):
+    """A Cov structure from names: mode "off" / "propagate" / "residual" (or COV_*); sigma_omega a scalar or three values; sigma_flow
+    and sigma_pos in the units of the points the entry takes (pixels in the resident paths)."""
+    if isinstance(mode, str):
+        if mode not in COV_MODES:
+            raise ValueError(f"cov mode {mode!r} is none of {sorted(COV_MODES)}")
+        mode = COV_MODES[mode]
+    so = np.broadcast_to(np.asarray(sigma_omega, np.float64), (3,))
+    return Cov(int(mode), float(sigma_flow), float(sigma_pos), float(sigma_d), (C.c_double * 3)(*so.tolist()), float(sigma_normal),
+               float(sigma_offset), int(bool(omega_from_imu)), int(bool(filter_r)), float(r_floor), float(nis_max))
+
+
+def cov_matrix(t6):
+    """The symmetric 3x3 of six record slots (xx xy xz yy yz zz); leading dimensions are kept."""
+    t = np.asarray(t6, np.float64)
+    return np.stack([t[..., [0, 1, 2]], t[..., [1, 3, 4]], t[..., [2, 4, 5]]], -2)
 
 
 class TrackGate(C.Structure):
@@ -210,6 +240,9 @@ def load_library():
         L.ofk_robust_download.argtypes = [vp, vp, i, vp]
         L.ofk_velocity_solve_robust.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), vp, vp, vp]
         L.ofk_robust_pairs.argtypes = [C.c_ulonglong, C.c_uint, i, i, vp, vp]
+        L.ofk_set_cov.argtypes = [vp, C.POINTER(Cov)]; L.ofk_get_cov.argtypes = [vp, C.POINTER(Cov)]
+        L.ofk_cov_download.argtypes = [vp, vp]
+        L.ofk_velocity_solve_cov.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Cov), vp, vp]
         L.ofk_set_track_gate.argtypes = [vp, C.POINTER(TrackGate)]; L.ofk_get_track_gate.argtypes = [vp, C.POINTER(TrackGate)]
         L.ofk_track_gate_download.argtypes = [vp, vp, vp, vp, i, vp]
         L.ofk_set_corner_grid.argtypes = [vp, C.POINTER(CornerGrid)]; L.ofk_get_corner_grid.argtypes = [vp, C.POINTER(CornerGrid)]
@@ -702,6 +735,48 @@ class Context:
         with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
             self._ck(self._L.ofk_robust_download(self._h, _p(w), self.max_pts, _p(st)))
         return w[:batch].copy(), st[:batch].copy()
+
+    def velocity_solve_cov(self, variant, x, u, d=None, nrm=None, omega=None, t=None, valid=None, robust=None, cov=None, **settings):
+        """ofk_velocity_solve_cov: velocity_solve's arguments (NODE or SIM), an optional Robust and the covariance setting (a Cov, or
+        cov_setting's keywords).  Returns out [B,8], cov [B,24] (single problem: [8], [24])."""
+        cv = cov if cov is not None else cov_setting(**settings)
+        x = _arr(x, np.float64); u = _arr(u, np.float64)
+        if u.shape[:-1] != x.shape[:-1] or x.shape[-1] != 2 or u.shape[-1] < 2:
+            raise ValueError(f"velocity_solve_cov: x {x.shape} must be [..., n, 2] and u {u.shape} [..., n, >=2] over the same points")
+        single = x.ndim == 2
+        if single:
+            x = x[None]; u = u[None]
+        B, n, _ = x.shape
+        u = _arr(u[..., :2], np.float64)
+        nrm = _arr(nrm, np.float64, (B, 3))
+        d = _opt(d, np.float64, (B,)); omega = _opt(omega, np.float64, (B, 3)); t = _opt(t, np.float64, (B, 3))
+        valid = _opt(valid, np.uint8, (B, n))
+        out = np.zeros((B, SOLVE_DOUBLES), np.float64); rec = np.zeros((B, COV_DOUBLES), np.float64)
+        if not n:                                               # no points: velocity_solve's zeros, a void covariance
+            rec[:, 13] = 1.0
+            return (out[0], rec[0]) if single else (out, rec)
+        with self._lock:
+            self._ck(self._L.ofk_velocity_solve_cov(self._h, int(variant), _p(x), _p(u), _p(valid), B, n, _p(d), _p(nrm), _p(omega), _p(t),
+                                                    None, C.byref(robust) if robust is not None else None, C.byref(cv), _p(out), _p(rec)))
+        return (out[0], rec[0]) if single else (out, rec)
+
+    def set_cov(self, cov=None, **settings):
+        """ofk_set_cov: a Cov (or cov_setting's keywords); None or mode "off" switches it off.  Every later pairs_run, pairs filter step
+        and stream step computes the covariance records (and, with filter_r / nis_max, corrects its filter with them)."""
+        cv = cov if cov is not None or not settings else cov_setting(**settings)
+        self._ck(self._L.ofk_set_cov(self._h, C.byref(cv) if cv is not None else None))
+
+    def get_cov(self):
+        cv = Cov()
+        self._ck(self._L.ofk_get_cov(self._h, C.byref(cv)))
+        return cv
+
+    def cov_download(self, batch):
+        """cov [batch, 24] of the latest run / step with the setting on."""
+        rec = np.zeros((self.max_batch, COV_DOUBLES), np.float64)
+        with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
+            self._ck(self._L.ofk_cov_download(self._h, _p(rec)))
+        return rec[:batch].copy()
 
     def imu_propagate(self, state, msg):
         state = _arr(state, np.float64).copy(); msg = _arr(msg, np.float64)

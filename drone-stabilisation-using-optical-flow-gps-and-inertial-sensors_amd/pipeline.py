@@ -53,6 +53,21 @@ class PipelineConfig:
     grid_cell: int = 0
     grid_cap: int = 0
     grid_max_rank: int = 0
+    # velocity covariance (ofk.h: ofk_set_cov): "off", "propagate" (first-order propagation of the six input sigmas through the solve)
+    # or "residual" (flow and position terms from the solve's own residual); sigma_flow_px / sigma_pos_px in pixels, sigma_omega a
+    # scalar or three values, omega_from_imu: the resident IMU state's angular-velocity variances; cov_filter: the filter's correct
+    # uses the covariance (+ r_floor I) in the place of its constant R; nis_max > 0 skips a correct whose NIS exceeds it
+    cov: str = "off"
+    sigma_flow_px: float = 0.0
+    sigma_pos_px: float = 0.0
+    sigma_d: float = 0.0
+    sigma_omega: object = 0.0
+    sigma_normal: float = 0.0
+    sigma_offset: float = 0.0
+    omega_from_imu: bool = False
+    cov_filter: bool = False
+    r_floor: float = 0.0
+    nis_max: float = 0.0
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -89,6 +104,13 @@ class PipelineConfig:
         if self.grid_cell == 0:
             return None
         return ofk.corner_grid_setting(self.grid_cell, self.grid_cap, self.grid_max_rank)
+
+    def cov_setting(self):
+        """The ofk.Cov structure of this configuration, None when the covariance is off."""
+        if self.cov == "off":
+            return None
+        return ofk.cov_setting(self.cov, self.sigma_flow_px, self.sigma_pos_px, self.sigma_d, self.sigma_omega, self.sigma_normal,
+                               self.sigma_offset, self.omega_from_imu, self.cov_filter, self.r_floor, self.nis_max)
 
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
@@ -219,6 +241,8 @@ class FlowStream:
             self.ctx.set_track_gate(self.cfg.track_gate_setting())
         if self.cfg.corner_grid_setting() is not None:
             self.ctx.set_corner_grid(self.cfg.corner_grid_setting())
+        if self.cfg.cov != "off":
+            self.ctx.set_cov(self.cfg.cov_setting())
         self.fusion = fusion
         if fusion is not None:                                  # the per-stream filter state lives on the device from here on
             self._fusion = fusion.to_struct()
@@ -245,6 +269,11 @@ class FlowStream:
     def corner_grid_stats(self):
         """[batch, 2] int32 of the latest detection (begin or re-detection) with a corner grid on: corners accepted, candidates examined."""
         return self.ctx.corner_grid_stats(self.batch)
+
+    def covariances(self):
+        """[batch, 24] cov records (ofk.h: ofk_set_cov) of the latest step with the covariance on; ofk.cov_matrix(rec[:, 0:6]) is C_v,
+        rec[:, 6:12] C_uav, 14 the NIS of the filter's correct, 15 whether it was gated."""
+        return self.ctx.cov_download(self.batch)
 
     def begin(self, first_bgr):
         return self.ctx.stream_begin(first_bgr, self._params)
@@ -288,6 +317,8 @@ class FlowPipeline:
             self.ctx.set_track_gate(self.cfg.track_gate_setting())
         if self.cfg.corner_grid_setting() is not None:
             self.ctx.set_corner_grid(self.cfg.corner_grid_setting())
+        if self.cfg.cov != "off":
+            self.ctx.set_cov(self.cfg.cov_setting())
         if streams > 1:
             self.ctx.set_streams(streams)
 
@@ -334,6 +365,10 @@ class FlowPipeline:
     def corner_grid_stats(self):
         """[batch, 2] int32 of the latest run with a corner grid on: corners accepted, candidates examined."""
         return self.ctx.corner_grid_stats(self.batch)
+
+    def covariances(self):
+        """[batch, 24] cov records (ofk.h: ofk_set_cov) of the latest run with the covariance on (see FlowStream.covariances)."""
+        return self.ctx.cov_download(self.batch)
 
     def run_async(self):
         self.ctx.pairs_run(self._params)

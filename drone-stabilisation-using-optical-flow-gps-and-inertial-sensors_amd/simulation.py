@@ -213,6 +213,25 @@ def sweep(axis, data, linear_velocity, angular_velocity, height_above_gr, normal
     return np.append(v_mean, v_std)
 
 
+def predict_sweep(axis, data, linear_velocity, angular_velocity, height_above_gr, normal_vector, translation, sigmas=None, k=100, steps=None):
+    """The first-order prediction of what sweep(axis, ...) estimates from `trials` noisy solves per step: the standard deviations of
+    v_obs, [k, 3] (or [len(steps), 3]), from ONE ofk_velocity_solve_cov call per step on the noise-free flow (ofk.h: ofk_set_cov;
+    sqrt of the diagonal of C_uav, the covariance of v - omega x t).  The step's six sigmas map to the setting's: ang_vel ->
+    sigma_omega, translation -> sigma_offset, height -> sigma_d, flow -> sigma_flow, position -> sigma_pos; of_simulation draws the
+    normal's noise and discards it (simulation.py:45-46), so sigma_normal stays 0."""
+    idx = list(range(k)) if steps is None else [int(i) for i in steps]
+    out = np.zeros((len(idx), 3))
+    om = np.asarray(angular_velocity, np.float64); t = np.asarray(translation, np.float64)
+    for row, i in enumerate(idx):
+        d, h, n, sig = sweep_step(axis, i, k, data, height_above_gr, normal_vector, sigmas)
+        n = np.asarray(n, np.float64) / np.linalg.norm(n)       # of_simulation normalises it (simulation.py:46)
+        flow = generate_test_data(d, linear_velocity, om, h, n, t)
+        _, cov = ofk.default_context().velocity_solve_cov(ofk.SOLVE_SIM, d, flow, d=float(h), nrm=n, omega=om, t=t, mode="propagate",
+                                                          sigma_omega=sig[0], sigma_offset=sig[1], sigma_d=sig[2], sigma_flow=sig[3], sigma_pos=sig[4])
+        out[row] = np.sqrt(np.maximum(cov[[6, 9, 11]], 0.0))
+    return out
+
+
 def sweep_flow_errors(data, linear_velocity, angular_velocity, height_above_gr, normal_vector, translation, sigmas,
                       k=100, trials=100, generator=None, comm=None):
     """The "Effect of flow errors" driver (simulation.py:183-202) on points that are ALREADY centred / scaled (kept from round 2 for

@@ -72,6 +72,18 @@ def solve_lgs_robust(x, u, d, n, omega, **settings):
     return out[:3].copy(), R, rank, out[5:8].copy(), w, st
 
 
+def solve_lgs_cov(x, u, d, n, omega, mode="propagate", **sigmas):
+    """solve_lgs with the covariance of its result (ofk.h: ofk_velocity_solve_cov): first-order propagation of the input sigmas
+    through the solve.  sigmas: ofk.cov_setting's keywords (sigma_flow, sigma_pos in the units of x and u; sigma_d; sigma_omega;
+    sigma_normal); mode "residual" takes the flow and position terms from the solve's own residual.
+    Returns (v, R, rank, s, C_v [3,3], cov [24]); C_v is zero and cov[13] == 1 where there is no covariance (rank < 3)."""
+    x = np.asarray(x, np.float64); u = np.asarray(u, np.float64)
+    out, cov = ofk.default_context().velocity_solve_cov(ofk.SOLVE_NODE, x[:, :2], u[:, :2], d=float(d), nrm=n, omega=omega, mode=mode, **sigmas)
+    rank = int(out[4])
+    R = np.array([out[3]]) if (rank == 3 and 3 * len(x) > 3) else np.empty(0)
+    return out[:3].copy(), R, rank, out[5:8].copy(), ofk.cov_matrix(cov[0:6]), cov
+
+
 def feasible(x, v, omega, T, u, d, n):
     """node:44-50 (reference not executable: uses v_cr/u_cr before definition, returns nothing).  The evident
     intent — parallelity and distance of each point given the lever-arm corrected velocity — is returned."""
@@ -93,6 +105,7 @@ class optical_fusion:
     _robust = {}                                                 # PipelineConfig's robust_* settings (see __init__); empty: the plain solve
     _track_gate = {}                                             # PipelineConfig's fb_check / fb_thr / fb_level / err_max; empty: no gate
     _corner_grid = {}                                            # PipelineConfig's grid_cell / grid_cap / grid_max_rank; empty: no grid
+    _cov = {}                                                    # PipelineConfig's covariance fields (cov, sigma_*, ...); empty: no covariance
     feature_params = dict(qualityLevel=0.7, minDistance=10, blockSize=12)
     lk_params = dict(winSize=(15, 15), maxLevel=3, criteria=(cv2.TERM_CRITERIA_EPS | cv2.TERM_CRITERIA_COUNT, 20, 0.03))
     scaling = 0.01
@@ -246,7 +259,8 @@ class optical_fusion:
             cfg = PipelineConfig(max_corners=int(self.max_feat), quality=float(self.feature_params["qualityLevel"]),
                                  min_distance=float(self.feature_params["minDistance"]), block_size=int(self.feature_params["blockSize"]),
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
-                                 use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid)
+                                 use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
+                                 **self._cov)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -278,6 +292,11 @@ class optical_fusion:
         r = rec[0]
         self._resident_result = (r[0:3].copy(), r[8:11].copy(), (np.array([r[3]]) if (r[4] == 3 and 3 * r[11] > 3) else np.empty(0)), int(r[4]),
                                  r[5:8].copy()) if r[15] else None
+        if self._cov and r[15]:                                  # the attribute the reference carries and never fills (node:184)
+            cv = fs.covariances()[0]
+            self.last_cov = cv
+            if cv[13] == 0:
+                self.vel_err = np.sqrt(np.maximum(cv[[6, 9, 11]], 0.0))
         self.init = False
         self.got_picture_ = True
 
@@ -315,13 +334,28 @@ class optical_fusion:
             if len(x) >= 3:
                 v_obs, R, rank, s = solve_lgs(x, u, self.d, self.normal, self.ang)
                 v_uav = self._ctx().post_solve(v_obs, self.rotation, self.ang, self.offset)                        # node:258
+                if self._cov:
+                    self._vel_err_from_solve(x, u)
                 print('    '.join(map(str, v_obs)))
                 self.vel = v_uav
                 self.last_residual, self.last_rank, self.last_s = R, rank, s
             self.got_picture_ = False
             return v_obs
 
-    def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None):
+    def _vel_err_from_solve(self, x, u):
+        """self.vel_err = sqrt(diag(C_uav)) of the solve just made (the node as shipped solves on the host's points): the stage entry
+        with the lever arm, then the rotation, which is taken as exact."""
+        c = PipelineConfig(**self._cov)
+        setting = ofk.cov_setting(c.cov, c.sigma_flow_px * self.scaling, c.sigma_pos_px * self.scaling, c.sigma_d, c.sigma_omega, c.sigma_normal,
+                                  c.sigma_offset)
+        _, cv = self._ctx().velocity_solve_cov(ofk.SOLVE_NODE, x[:, :2], u[:, :2], d=float(self.d), nrm=self.normal, omega=self.ang,
+                                               t=self.offset, cov=setting)
+        self.last_cov = cv
+        if cv[13] == 0:
+            Rm = np.asarray(self.rotation, np.float64).reshape(3, 3)
+            self.vel_err = np.sqrt(np.maximum(np.diag(Rm @ ofk.cov_matrix(cv[6:12]) @ Rm.T), 0.0))
+
+    def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -329,7 +363,10 @@ class optical_fusion:
         or exceed err_max before the solve and from the tracks (ofk.h: ofk_set_track_gate).
         corner_grid: None (goodFeaturesToTrack's selection) or a dict of ofk.corner_grid_setting's keywords, e.g. dict(cell=64, cap=4):
         detection and re-detection then hold at most `cap` corners per cell, the re-detection counting the tracks that are still
-        alive (ofk.h: ofk_set_corner_grid)."""
+        alive (ofk.h: ofk_set_corner_grid).
+        cov: None or a dict of PipelineConfig's covariance fields with `mode` for its `cov`, e.g. dict(mode="propagate",
+        sigma_flow_px=0.3, sigma_d=0.05, sigma_omega=0.01): every solved step then fills self.vel_err = sqrt(diag(C_uav)), the
+        attribute the reference carries through its callbacks and never reads (ofk.h: ofk_set_cov); self.last_cov is the record."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -341,6 +378,11 @@ class optical_fusion:
         if k:
             ofk.corner_grid_setting(**k)                         # unknown or invalid keywords fail here, not at the first frame
         self._corner_grid = {"grid_" + n: v for n, v in k.items()}
+        cv = dict(cov or {})
+        self._cov = dict(cov=cv.pop("mode", "propagate"), **cv) if cov else {}
+        if self._cov:
+            PipelineConfig(**self._cov).cov_setting()            # unknown or invalid keywords fail here, not at the first frame
+        self.last_cov = None
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

@@ -296,6 +296,67 @@ int ofk_lk_pyr_fb(ofk_ctx *ctx, const uint8_t *prev, const uint8_t *next, int ba
                   const float *init_pts, int flags, float *next_pts, uint8_t *status, float *err, const ofk_track_gate *g,
                   float *back_pts, uint8_t *back_status, float *fb2);
 
+/* The velocity covariance: first-order error propagation through the velocity solve, and a filter correct that uses it in the place of
+ * the constant R.  (The reference carries vel_err, feat_err, flow_err, ang_err, d_err, normal_err through every callback of its node
+ * and never reads them; its simulation.py estimates the same dependence from 100 noisy re-solves per step.)  Off by default; with it
+ * off every entry point launches the kernels and returns the bits it always did.
+ * For one problem let the kept points be those the solve used (gated status / valid / feasibility keep / legacy keep, and with the
+ * robust solve on those of final weight w > 0), with the solve's per-point terms q, sA, sB and M = sum w sA^2 X^T X,
+ * g = sum w sA sB X^T X q.  The plain solve's v = M^+ g is a function of its inputs; C_v = J Sigma J^T with J its exact first
+ * derivative and Sigma diagonal: all inputs independent and zero-mean (the noise model of simulation.py:40-45).  The robust weights
+ * are held fixed (the usual IRLS sandwich) and v is the solve's own, read from its record.
+ *   source     inputs                                            variance each
+ *   flow       u_i, 2 per kept point                             sigma_flow^2
+ *   position   x_i, 2 per kept point, u_i held fixed             sigma_pos^2
+ *   gyro       omega, 3                                          sigma_omega[k]^2; with omega_from_imu and ofk_fusion.use_imu the resident
+ *                                                                IMU state's slots 21-23 (variances already)
+ *   range      d                                                 sigma_d^2
+ *   normal     n, 3 components, isotropic                        sigma_normal^2
+ *   lever arm  t / offset, 3, isotropic; only through v - w x t  sigma_offset^2
+ * C_uav is the same propagation through v_uav = R (v - omega x offset) (node:258; R taken as exact), in the stage entry through
+ * v - omega x t (R = I; t == NULL: C_uav = C_v, no lever-arm term).  The gyro reaches C_uav by both routes: its Jacobian there is
+ * dv/domega + [offset]x.
+ * OFK_COV_PROPAGATE: all six terms.  OFK_COV_RESIDUAL: the flow and position terms are replaced by s^2 M^+, s^2 = RSS / (2 m - 3)
+ * with RSS the record's field 3 (the weighted sum of a robust run) and m the kept points (each point's three rows have rank 2); the
+ * common-mode terms (gyro, range, normal, lever arm) stay as given: no residual sees them.
+ * Void - all zeros with flag 1 - when the solve's rank is below 3, in residual mode when 2 m <= 3, when an entry is not finite, and
+ * for a pair with scaling == 0 or d == 0.
+ * Cov record, OFK_COV_DOUBLES per problem: 0-5 C_v upper triangle (xx xy xz yy yz zz); 6-11 C_uav likewise; 12 s^2 (0 when
+ * 2 m <= 3); 13 flag; 14 NIS of the filter's correct (0 where none ran); 15 gated; 16-21 the trace of each source's share of C_v:
+ * flow, position, gyro, range, normal, lever arm (the last of C_uav before the rotation; in residual mode 16 holds the trace of
+ * s^2 M^+ and 17 is 0); 22-23 reserved, 0.
+ * Units: sigma_flow and sigma_pos are in the units of the points an entry takes - scaled units in ofk_velocity_solve_cov, pixels in
+ * the resident paths, where the kernel multiplies them by the pair's `scaling` (sensor slot 19).
+ * The filter: every correct of ofk_stream_step_fused[_jpeg] and ofk_pairs_filter_step that runs with a setting on reports its
+ * normalised innovation squared NIS = nu^T S^-1 nu.  With filter_r = 1 it uses R_eff = the configured R with its top-left 3x3 block
+ * replaced by z_sign^2 C + r_floor I, C = C_uav when z_source is 1, else C_v; rows 3.. of a 6-row measurement keep R; a void
+ * covariance falls back to the whole of R.  With nis_max > 0 a correct whose NIS exceeds it is skipped: state and P stay at the
+ * prediction and gated = 1.  (With a setting on the fuse kernel leaves the filter at its prediction and the covariance kernel behind
+ * it corrects and rewrites fused[0..7].)
+ * ofk_set_cov (NULL or mode OFK_COV_OFF: off) is a context setting read by ofk_pairs_run (every slice), ofk_pairs_filter_step,
+ * ofk_stream_step[_jpeg] and ofk_stream_step_fused[_jpeg].  Refused with OFK_E_INVALID before any launch, the previous setting staying
+ * in place: an unknown mode; a sigma, r_floor or nis_max that is negative or not finite; omega_from_imu or filter_r not 0/1; filter_r
+ * with mode OFF.  OFK_SOLVE_OFMODULE (no omega, no d, a per-point weight that is itself a function of the flow) and OFK_FLOW_ROTATIONAL
+ * (a flow that is no measurement) are not the sensor model: refused with OFK_E_INVALID wherever a setting is on.
+ * Records are bit-identical across launch forms (one wave per pair from 128 pairs per slice on, a 256-thread workgroup below), slice
+ * counts and overlap settings.
+ * ofk_cov_download: cov [batch][OFK_COV_DOUBLES] of the latest run / step with the setting on (`batch` is that run's own);
+ * OFK_E_INVALID before such a run.
+ * ofk_velocity_solve_cov = ofk_velocity_solve's arguments (n <= 4096; NODE or SIM) plus the robust setting (NULL: the plain solve) and
+ * the covariance setting (mode PROPAGATE or RESIDUAL; filter_r 0); out as ofk_velocity_solve, cov [batch][OFK_COV_DOUBLES]. */
+#define OFK_COV_OFF 0
+#define OFK_COV_PROPAGATE 1
+#define OFK_COV_RESIDUAL 2
+#define OFK_COV_DOUBLES 24
+typedef struct ofk_cov { int mode; double sigma_flow, sigma_pos, sigma_d, sigma_omega[3], sigma_normal, sigma_offset;
+                         int omega_from_imu; int filter_r; double r_floor; double nis_max; } ofk_cov;
+int ofk_set_cov(ofk_ctx *ctx, const ofk_cov *c);
+int ofk_get_cov(const ofk_ctx *ctx, ofk_cov *c);
+int ofk_cov_download(ofk_ctx *ctx, double *cov);
+int ofk_velocity_solve_cov(ofk_ctx *ctx, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                           const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
+                           const ofk_robust *r, const ofk_cov *c, double *out, double *cov);
+
 /* optical_fusion.call_imu — node:61-89, batched over independent IMU streams, one message each.
  * state [batch][OFK_IMU_STATE]: vel[3], old_time, time_zero, first(0/1), rotation[9], normal[3], ang[3], ang_err[3]
  * msg   [batch][OFK_IMU_MSG]  : secs, nsecs, qx,qy,qz,qw, wx,wy,wz, cov0,cov4,cov8, ax,ay,az */
