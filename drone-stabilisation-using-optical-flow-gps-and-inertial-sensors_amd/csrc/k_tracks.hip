@@ -193,3 +193,5 @@ void ofk_launch_track_gate(hipStream_t s, const float *prev_pts, const float *ba
     hipLaunchKernelGGL(k_track_gate, dim3(batch), dim3(256), 0, s, prev_pts, back_pts, st_back, err, counts, pts_stride, fb_on, thr2, err_on,
                        err_max, status, fb2, stats);
 }
+
+#include "k_zones.inc"

@@ -150,6 +150,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->robust = ofk_robust{OFK_ROBUST_OFF, 4.685, 5, 64, 0ull, 0};
     c->gate = ofk_track_gate{OFK_FB_OFF, 0.5, -1, 0.0};
     c->cov = ofk_cov{OFK_COV_OFF, 0.0, 0.0, 0.0, {0.0, 0.0, 0.0}, 0.0, 0.0, 0, 0, 0.0, 0.0};
+    c->zones = ofk_zones{OFK_ZONES_OFF, 48, 3, 20, 30, OFK_ZONE_MAX};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -202,7 +203,8 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     for (int k = 0; k < 2; ++k) { if (c->bgr[k]) hipFree(c->bgr[k]); if (c->pyr[k]) hipFree(c->pyr[k]); }
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
-                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec};
+                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec,
+                    c->zone_tab};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
@@ -1705,6 +1707,108 @@ extern "C" int ofk_pairs_export_records_f32(ofk_ctx *c, void *device_dst, int ba
     return ofk_export_records_stream(c, (float *)device_dst, batch, nullptr);
 }
 
+// ------------------------------------------------------------------------------------------------ exclusion zones
+static int check_zones(ofk_ctx *c, const ofk_zones *z, const char *who)
+{
+    if (z->mode != OFK_ZONES_OFF && z->mode != OFK_ZONES_HULL) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_ZONES_OFF nor OFK_ZONES_HULL", who, z->mode);
+    if (z->mode == OFK_ZONES_OFF) return OFK_OK;
+    if (z->link < 1 || z->link > 4096) return ofk_fail(c, OFK_E_INVALID, "%s: link %d outside 1..4096", who, z->link);
+    if (z->min_members < 1 || z->min_members > c->max_pts) return ofk_fail(c, OFK_E_INVALID, "%s: min_members %d outside 1..%d", who, z->min_members, c->max_pts);
+    if (z->radius < 0 || z->radius > 255) return ofk_fail(c, OFK_E_INVALID, "%s: radius %d outside 0..255", who, z->radius);
+    if (z->ttl < 1 || z->ttl > 65535) return ofk_fail(c, OFK_E_INVALID, "%s: ttl %d outside 1..65535", who, z->ttl);
+    if (z->max_zones < 1 || z->max_zones > OFK_ZONE_MAX) return ofk_fail(c, OFK_E_INVALID, "%s: max_zones %d outside 1..%d", who, z->max_zones, OFK_ZONE_MAX);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_zones(ofk_ctx *c, const ofk_zones *z)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!z) { c->zones.mode = OFK_ZONES_OFF; return OFK_OK; }
+    TRY(check_zones(c, z, "ofk_set_zones"));
+    if (z->mode == OFK_ZONES_OFF) { c->zones.mode = OFK_ZONES_OFF; return OFK_OK; }
+    c->zones = *z;
+    return OFK_OK;
+}
+
+extern "C" int ofk_get_zones(const ofk_ctx *c, ofk_zones *z)
+{
+    if (!c || !z) return OFK_E_INVALID;
+    *z = c->zones;
+    return OFK_OK;
+}
+
+// bytes of the tables, the motion rows and the statistics of `batch` streams (each kind lies back to back)
+static size_t zones_tab_bytes(int batch) { return (size_t)batch * OFK_ZONE_MAX * OFK_ZONE_INTS * 4; }
+static size_t zones_mot_bytes(int batch) { return (size_t)batch * OFK_ZONE_MAX * OFK_ZONE_FLOATS * 4; }
+static size_t zones_stat_bytes(int batch) { return (size_t)batch * OFK_ZONE_STATS * 4; }
+static int zones_clear(ofk_ctx *c, int batch)
+{
+    OFK_HIP(c, hipMemsetAsync(c->zone_tab, 0, zones_tab_bytes(batch), c->stream));
+    OFK_HIP(c, hipMemsetAsync(c->zone_mot, 0, zones_mot_bytes(batch), c->stream));
+    OFK_HIP(c, hipMemsetAsync(c->zone_stats, 0, zones_stat_bytes(batch), c->stream));
+    return OFK_OK;
+}
+// the zones' resident buffers, allocated (and cleared) when a step or an entry first needs them
+static int zones_alloc(ofk_ctx *c)
+{
+    if (c->zone_tab) return OFK_OK;                              // one allocation, carved into the five buffers
+    const size_t B = (size_t)c->max_batch, o_mot = up(zones_tab_bytes(c->max_batch), 256), o_st = o_mot + up(zones_mot_bytes(c->max_batch), 256),
+                 o_wk = o_st + up(zones_stat_bytes(c->max_batch), 256), o_ss = o_wk + up(B * 2 * c->max_pts * 4, 256);
+    uint8_t *base = nullptr;
+    OFK_HIP(c, hipMalloc((void **)&base, o_ss + B * c->max_pts));
+    c->zone_tab = (int *)base; c->zone_mot = (float *)(base + o_mot); c->zone_stats = (int *)(base + o_st); c->zone_work = (int *)(base + o_wk);
+    c->zone_status = base + o_ss;
+    return zones_clear(c, c->max_batch);
+}
+
+extern "C" int ofk_zones_reset(ofk_ctx *c, int batch)
+{
+    if (!c) return OFK_E_INVALID;
+    if (batch < 1 || batch > c->max_batch) return ofk_fail(c, OFK_E_INVALID, "ofk_zones_reset: batch %d outside 1..%d", batch, c->max_batch);
+    TRY(enter(c));
+    TRY(zones_alloc(c));
+    TRY(zones_clear(c, batch));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+extern "C" int ofk_zones_download(ofk_ctx *c, int *zones, float *motion, int *stats)
+{
+    if (!c) return OFK_E_INVALID;
+    TRY(enter(c));
+    TRY(zones_alloc(c));
+    if (zones) OFK_HIP(c, hipMemcpyAsync(zones, c->zone_tab, zones_tab_bytes(c->max_batch), hipMemcpyDeviceToHost, c->stream));
+    if (motion) OFK_HIP(c, hipMemcpyAsync(motion, c->zone_mot, zones_mot_bytes(c->max_batch), hipMemcpyDeviceToHost, c->stream));
+    if (stats) OFK_HIP(c, hipMemcpyAsync(stats, c->zone_stats, zones_stat_bytes(c->max_batch), hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+extern "C" int ofk_zones_step(ofk_ctx *c, const float *old_pts, const float *new_pts, const uint8_t *status, const uint8_t *keep, const int *counts,
+                              int batch, int stride, int h, int w, const uint8_t *mask_in, uint8_t *mask_out)
+{
+    TRY(check_geom(c, batch, h, w, "ofk_zones_step"));
+    if (!old_pts || !new_pts || !status || !keep || !counts || !mask_out) return ofk_fail(c, OFK_E_INVALID, "ofk_zones_step: NULL argument");
+    if (stride < 1 || stride > c->max_pts) return ofk_fail(c, OFK_E_INVALID, "ofk_zones_step: stride %d outside 1..%d", stride, c->max_pts);
+    if (c->zones.mode == OFK_ZONES_OFF) return ofk_fail(c, OFK_E_INVALID, "ofk_zones_step: ofk_set_zones is off");
+    TRY(zones_alloc(c));
+    TRY(lazy_mask(c));
+    const size_t np = (size_t)batch * stride;
+    Bump bp;
+    TRY(est_begin(c, np * 18 + (size_t)batch * 4, bp));
+    const float *d_old = (const float *)bp.put(old_pts, np * 8), *d_new = (const float *)bp.put(new_pts, np * 8);
+    const uint8_t *d_st = (const uint8_t *)bp.put(status, np), *d_keep = (const uint8_t *)bp.put(keep, np);
+    const int *d_cnt = (const int *)bp.put(counts, (size_t)batch * 4);
+    if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_zones_step: upload failed");
+    ofk_launch_zones_update(c->stream, d_old, d_new, d_st, d_keep, d_cnt, stride, &c->zones, c->zone_tab, c->zone_mot, c->zone_stats, c->zone_work, 0, batch);
+    if (mask_in) TRY(h2d(c, c->mask, c->img_stride, mask_in, (size_t)h * w, batch));
+    else OFK_HIP(c, hipMemsetAsync(c->mask, 1, (size_t)batch * c->img_stride, c->stream));
+    ofk_launch_zone_mask(c->stream, c->mask, c->img_stride, h, w, c->zone_tab, c->zone_mot, c->zones.radius, nullptr, batch);
+    ofk_launch_zones_age(c->stream, c->zone_tab, c->zone_mot, c->zone_stats, batch);
+    TRY(check_launch(c, "ofk_zones_step"));
+    return d2h(c, mask_out, c->mask, c->img_stride, (size_t)h * w, batch);
+}
+
 // ------------------------------------------------------------------------------------------------ video streams
 static int stream_alloc(ofk_ctx *c)
 {
@@ -1758,6 +1862,7 @@ static int stream_begin_impl(ofk_ctx *c, const uint8_t *first_bgr, int batch, in
     TRY(check_lk(c, h, w, p->win, p->max_level));
     TRY(grid_prepare(c, c->grid, batch, h, w, "ofk_stream_begin"));
     TRY(stream_alloc(c));
+    if (c->zone_tab) TRY(zones_clear(c, c->max_batch));          // new streams start without zones (a table that was never used is clear)
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     TRY(stream_ingest(c, 0, first_bgr, batch, h, w, lv));
     TRY(stream_detect(c, nullptr, nullptr, batch, h, w, p, c->pts_prev, c->counts));
@@ -1922,6 +2027,8 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
+    const bool zones_on = c->zones.mode != OFK_ZONES_OFF;
+    if (zones_on) { TRY(check_zones(c, &c->zones, "ofk_stream_step")); TRY(zones_alloc(c)); }
     OFK_HIP(c, hipMemcpyAsync(c->sensors, sensors, (size_t)B * OFK_SENSOR_DOUBLES * 8, hipMemcpyHostToDevice, c->stream));
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
@@ -1929,12 +2036,18 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         // of_module.py:83-86: before tracking, streams with few tracks replace them by fresh corners of the PREVIOUS frame (no mask)
         ofk_launch_redetect_limits(c->stream, c->counts, min_features, p->max_corners, c->limit, B);
         TRY(grid_prepare(c, c->grid, B, h, w, "ofk_stream_step_fused"));
-        TRY(stream_detect(c, nullptr, c->limit, B, h, w, p, c->pts_new, c->new_counts));
+        if (zones_on) {                                          // the zones alone, where they stand in the previous frame
+            OFK_HIP(c, hipMemsetAsync(c->mask, 1, (size_t)B * c->img_stride, c->stream));
+            ofk_launch_zone_mask(c->stream, c->mask, c->img_stride, h, w, c->zone_tab, c->zone_mot, c->zones.radius, c->limit, B);
+        }
+        TRY(stream_detect(c, zones_on ? c->mask : nullptr, c->limit, B, h, w, p, c->pts_new, c->new_counts));
         ofk_launch_replace_tracks(c->stream, c->limit, c->pts_new, c->new_counts, c->max_pts, c->pts_prev, c->counts, B);
     }
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)
     TRY(track(c, c->stream, view_of(c, 0, B, 0), lv, p, fu && fu->use_imu ? c->imu_state : nullptr));
+    if (zones_on)                                                // the solve stage turns the status into its keep flags: rule 1 needs both
+        OFK_HIP(c, hipMemcpyAsync(c->zone_status, c->status, (size_t)B * c->max_pts, hipMemcpyDeviceToDevice, c->stream));
     if (fu && c->robust.loss != OFK_ROBUST_OFF)
         ofk_launch_stream_fuse_robust(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
                                       c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, p->use_feasibility, p->feas_T,
@@ -1961,10 +2074,17 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         hold = solved == 0.0;
     }
     const bool any = few && !(fu && fu->redetect_replace) && !hold;
+    if (zones_on && !hold)                                       // rules 1-4; rule 7 in the same launch unless the mask comes between them
+        ofk_launch_zones_update(c->stream, c->pts_prev, c->pts_next, c->zone_status, c->status, c->counts, c->max_pts, &c->zones, c->zone_tab,
+                                c->zone_mot, c->zone_stats, c->zone_work, any ? 0 : 1, B);
     if (any) {
         ofk_launch_redetect_limits(c->stream, c->counts, min_features, p->max_corners, c->limit, B);
         OFK_HIP(c, hipMemsetAsync(c->mask, 1, (size_t)B * c->img_stride, c->stream));
         ofk_launch_disc_mask(c->stream, c->mask, c->img_stride, h, w, c->pts_prev, c->counts, c->max_pts, mask_radius, c->limit, B);
+        if (zones_on) {
+            ofk_launch_zone_mask(c->stream, c->mask, c->img_stride, h, w, c->zone_tab, c->zone_mot, c->zones.radius, c->limit, B);
+            ofk_launch_zones_age(c->stream, c->zone_tab, c->zone_mot, c->zone_stats, B);
+        }
         // with a corner grid the old tracks are its occupancy list as well: the new corners go to the cells the tracks have left
         TRY(grid_prepare(c, c->grid, B, h, w, "ofk_stream_step"));
         TRY(stream_detect(c, c->mask, c->limit, B, h, w, p, c->pts_new, c->new_counts, c->pts_prev, c->counts));

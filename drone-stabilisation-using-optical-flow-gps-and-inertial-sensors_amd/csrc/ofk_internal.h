@@ -96,6 +96,9 @@ struct ofk_ctx {
     int grid_batch;                          // images of the latest selection with a grid on (ofk_corner_grid_download), 0 = none
     ofk_cov cov;                             // ofk_set_cov: mode OFK_COV_OFF unless set
     double *cov_rec; int cov_batch;          // [B][OFK_COV_DOUBLES] (lazily allocated); problems of the latest run / step with it on, 0 = none
+    ofk_zones zones;                         // ofk_set_zones: mode OFK_ZONES_OFF unless set
+    int *zone_tab; float *zone_mot; int *zone_stats, *zone_work;   // [B][OFK_ZONE_MAX][OFK_ZONE_INTS], [B][OFK_ZONE_MAX][OFK_ZONE_FLOATS], [B][OFK_ZONE_STATS], [B][2][max_pts] hull stacks;
+    uint8_t *zone_status;                    // [B][max_pts] status in front of the solve stage; one lazy allocation (zone_tab owns it)
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -166,6 +169,13 @@ void ofk_launch_disc_mask(hipStream_t s, uint8_t *mask, size_t mask_stride, int 
 void ofk_launch_redetect_limits(hipStream_t s, const int *counts, int min_feat, int max_feat, int *limit, int batch);
 void ofk_launch_update_tracks(hipStream_t s, const float *next_pts, const uint8_t *status, const int *counts_in, int pts_stride,
                               const float *new_pts, const int *new_counts, float *tracks, int *counts_out, int max_total, int batch);
+// exclusion zones (ofk.h: ofk_set_zones; k_zones.inc): rules 1-4 per stream (do_age: rule 7 behind them), rule 7 alone, rule 6
+// (limit NULL = every stream)
+void ofk_launch_zones_update(hipStream_t s, const float *old_pts, const float *new_pts, const uint8_t *st_pre, const uint8_t *keep, const int *counts,
+                             int pts_stride, const ofk_zones *set, int *tab, float *mot, int *stats, int *work, int do_age, int batch);
+void ofk_launch_zones_age(hipStream_t s, int *tab, float *mot, int *stats, int batch);
+void ofk_launch_zone_mask(hipStream_t s, uint8_t *mask, size_t mask_stride, int h, int w, const int *tab, const float *mot, int radius,
+                          const int *limit, int batch);
 void ofk_launch_lk(hipStream_t s, const uint8_t *prev, const uint8_t *next, size_t pyr_stride, const ofk_levels &lv,
                    const float *prev_pts, const int *counts, int pts_stride, int win, int max_count, double eps,
                    double min_eig_thr, float *next_pts, uint8_t *status, float *err, int batch, int flags = 0);   // flags: OFK_LK_*

@@ -30,6 +30,7 @@ SYMBOLS = (
     "ofk_set_cov", "ofk_get_cov", "ofk_cov_download", "ofk_velocity_solve_cov",
     "ofk_set_track_gate", "ofk_get_track_gate", "ofk_track_gate_download", "ofk_lk_pyr_fb",
     "ofk_set_corner_grid", "ofk_get_corner_grid", "ofk_corner_grid_download", "ofk_select_corners_grid", "ofk_good_features_grid",
+    "ofk_set_zones", "ofk_get_zones", "ofk_zones_step", "ofk_zones_reset", "ofk_zones_download",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
     "ofk_stream_begin_jpeg", "ofk_stream_step_jpeg",
@@ -66,6 +67,9 @@ COV_DOUBLES = 24
 FB_OFF, FB_PLAIN, FB_SEEDED = 0, 1, 2                    # ofk_set_track_gate / ofk_lk_pyr_fb
 FB_MODES = {"off": FB_OFF, "plain": FB_PLAIN, "seeded": FB_SEEDED}
 GRID_MAX_CELLS = 2048                                   # OFK_GRID_MAX_CELLS: cells of a corner grid over one frame
+ZONES_OFF, ZONES_HULL = 0, 1                             # ofk_set_zones
+ZONES_MODES = {"off": ZONES_OFF, "hull": ZONES_HULL}
+ZONE_MAX, ZONE_VERTS, ZONE_INTS, ZONE_FLOATS, ZONE_STATS = 16, 32, 67, 4, 8    # OFK_ZONE_*: slots per stream, vertices per zone, the download's rows
 FLOW_LK, FLOW_ROTATIONAL = 0, 1
 KEEP_STATUS, KEEP_LEGACY = 0, 1
 CONTROL_SENSORS, CONTROL_IMU = 0, 1
@@ -167,6 +171,30 @@ def corner_grid_setting(cell=0, cap=0, max_rank=0):
     return CornerGrid(cell, cap, max_rank)
 
 
+class Zones(C.Structure):
+    """ofk_zones (include/ofk.h): the exclusion zones a stream builds from the points its solve stage rejected."""
+    _fields_ = [("mode", C.c_int), ("link", C.c_int), ("min_members", C.c_int), ("radius", C.c_int), ("ttl", C.c_int), ("max_zones", C.c_int)]
+
+
+def zones_setting(mode="hull", link=48, min_members=3, radius=20, ttl=30, max_zones=ZONE_MAX):
+    """A Zones structure from names: mode "off" / "hull" (or ZONES_*); link = the per-axis distance in pixels below which two rejects
+    belong to one cluster, min_members = the smallest cluster that becomes a zone, radius = the margin around the hull in pixels,
+    ttl = the steps a zone lives without a refresh, max_zones = the slots in use (at most ZONE_MAX)."""
+    if isinstance(mode, str):
+        if mode not in ZONES_MODES:
+            raise ValueError(f"zones mode {mode!r} is none of {sorted(ZONES_MODES)}")
+        mode = ZONES_MODES[mode]
+    mode, link, min_members, radius, ttl, max_zones = int(mode), int(link), int(min_members), int(radius), int(ttl), int(max_zones)
+    if mode not in ZONES_MODES.values():
+        raise ValueError(f"zones mode {mode} is neither ZONES_OFF nor ZONES_HULL")
+    if mode != ZONES_OFF:
+        for name, v, lo, hi in (("link", link, 1, 4096), ("min_members", min_members, 1, 4096), ("radius", radius, 0, 255), ("ttl", ttl, 1, 65535),
+                                ("max_zones", max_zones, 1, ZONE_MAX)):
+            if not lo <= v <= hi:
+                raise ValueError(f"zones {name} {v} outside {lo}..{hi}")
+    return Zones(mode, link, min_members, radius, ttl, max_zones)
+
+
 class Fusion(C.Structure):
     """ofk_fusion (include/ofk.h): what ofk_stream_step_fused does between LK and the next frame."""
     _fields_ = [("use_imu", C.c_int), ("flow", C.c_int), ("keep", C.c_int), ("filter", C.c_int), ("control", C.c_int),
@@ -249,6 +277,9 @@ def load_library():
         L.ofk_corner_grid_download.argtypes = [vp, vp]
         L.ofk_select_corners_grid.argtypes = [vp, vp, vp, i, i, i, i, d, d, vp, vp, C.POINTER(CornerGrid), vp, vp, i]
         L.ofk_good_features_grid.argtypes = [vp, vp, vp, i, i, i, i, d, d, i, vp, vp, C.POINTER(CornerGrid), vp, vp, i]
+        L.ofk_set_zones.argtypes = [vp, C.POINTER(Zones)]; L.ofk_get_zones.argtypes = [vp, C.POINTER(Zones)]
+        L.ofk_zones_step.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, vp, vp]
+        L.ofk_zones_reset.argtypes = [vp, i]; L.ofk_zones_download.argtypes = [vp, vp, vp, vp]
         L.ofk_lk_pyr_fb.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, i, vp, vp, vp, C.POINTER(TrackGate), vp, vp, vp]
         L.ofk_imu_propagate.argtypes = [vp, vp, vp, i]
         L.ofk_post_solve.argtypes = [vp, vp, vp, vp, vp, i, vp]
@@ -586,6 +617,55 @@ class Context:
         with self._lock:
             self._ck(self._L.ofk_corner_grid_download(self._h, _p(st)))
         return st[:batch].copy()
+
+    def set_zones(self, zones=None, **settings):
+        """ofk_set_zones: a Zones (or zones_setting's keywords); None or mode "off" switches the feature off.  Every later stream
+        step feeds the points its solve stage rejected into the stream's zone table and keeps its re-detection out of the zones;
+        pairs_run ignores the setting."""
+        z = zones if zones is not None or not settings else zones_setting(**settings)
+        with self._lock:
+            self._ck(self._L.ofk_set_zones(self._h, C.byref(z) if z is not None else None))
+
+    def get_zones(self):
+        z = Zones()
+        self._ck(self._L.ofk_get_zones(self._h, C.byref(z)))
+        return z
+
+    def zones_reset(self, batch=None):
+        """ofk_zones_reset: the zone tables of the first `batch` streams (all by default) are cleared."""
+        with self._lock:
+            self._ck(self._L.ofk_zones_reset(self._h, int(self.max_batch if batch is None else batch)))
+
+    def zones_download(self, batch=None):
+        """ofk_zones_download -> dict(zones [batch,16,67] i32: ttl (0 = free), vertices, members, 32 x (x, y); motion [batch,16,4] f32:
+        off x, y, flow x, y; stats [batch,8] i32 of the latest step: live, inserted, refreshed, evicted, rejects, absorbed, label
+        sweeps, a reserved 0).  The library writes all max_batch streams; the first `batch` are returned."""
+        B = self.max_batch
+        batch = B if batch is None else int(batch)
+        if not 0 <= batch <= B:
+            raise ValueError(f"zones_download: batch {batch} outside 0..{B}")
+        zn = np.zeros((B, ZONE_MAX, ZONE_INTS), np.int32); mo = np.zeros((B, ZONE_MAX, ZONE_FLOATS), np.float32); st = np.zeros((B, ZONE_STATS), np.int32)
+        with self._lock:
+            self._ck(self._L.ofk_zones_download(self._h, _p(zn), _p(mo), _p(st)))
+        return dict(zones=zn[:batch].copy(), motion=mo[:batch].copy(), stats=st[:batch].copy())
+
+    def zones_step(self, old_pts, new_pts, status, keep, counts, h, w, mask=None):
+        """ofk_zones_step, the stage entry: one step of the zone rules on host arrays (old_pts / new_pts [B,S,2] f32, status / keep
+        [B,S] u8, counts [B]) against the resident table -> the re-detection mask [B,h,w] u8 (mask, or all ones, with the zones zeroed)."""
+        op = _arr(old_pts, np.float32)
+        if op.ndim != 3 or op.shape[2] != 2 or op.shape[1] < 1:
+            raise ValueError(f"zones_step: old_pts {op.shape} is not [B, S >= 1, 2]")
+        B, S, _ = op.shape
+        nw = _arr(new_pts, np.float32)
+        if nw.shape != op.shape:
+            raise ValueError(f"zones_step: new_pts {nw.shape} does not match old_pts {op.shape}")
+        st = _arr(status, np.uint8, (B, S)); kp = _arr(keep, np.uint8, (B, S)); counts = _arr(counts, np.int32, (B,))
+        h, w = int(h), int(w)
+        mi = _opt(mask, np.uint8, (B, h, w))
+        out = np.zeros((B, h, w), np.uint8)
+        with self._lock:
+            self._ck(self._L.ofk_zones_step(self._h, _p(op), _p(nw), _p(st), _p(kp), _p(counts), B, S, h, w, _p(mi), _p(out)))
+        return out
 
     def track_gate_download(self, batch, points=True):
         """ofk_track_gate_download of the latest gated run / step -> dict(stats [batch,4] i32: forward-tracked, of those lost by the

@@ -68,6 +68,15 @@ class PipelineConfig:
     cov_filter: bool = False
     r_floor: float = 0.0
     nis_max: float = 0.0
+    # exclusion zones (ofk.h: ofk_set_zones; streams only): None or "hull"; rejects of the solve stage closer than zone_link pixels
+    # per axis form a cluster, one of at least zone_min becomes a zone (its hull grown by zone_radius) that moves with the cluster's
+    # mean flow, keeps the re-detection out and lives zone_ttl steps behind its last refresh; at most zone_max zones per stream
+    zones: str = None
+    zone_link: int = 48
+    zone_min: int = 3
+    zone_radius: int = 20
+    zone_ttl: int = 30
+    zone_max: int = 16
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -111,6 +120,12 @@ class PipelineConfig:
             return None
         return ofk.cov_setting(self.cov, self.sigma_flow_px, self.sigma_pos_px, self.sigma_d, self.sigma_omega, self.sigma_normal,
                                self.sigma_offset, self.omega_from_imu, self.cov_filter, self.r_floor, self.nis_max)
+
+    def zones_setting(self):
+        """The ofk.Zones structure of this configuration, None when the zones are off."""
+        if self.zones is None or self.zones == "off":
+            return None
+        return ofk.zones_setting(self.zones, self.zone_link, self.zone_min, self.zone_radius, self.zone_ttl, self.zone_max)
 
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
@@ -243,6 +258,8 @@ class FlowStream:
             self.ctx.set_corner_grid(self.cfg.corner_grid_setting())
         if self.cfg.cov != "off":
             self.ctx.set_cov(self.cfg.cov_setting())
+        if self.cfg.zones_setting() is not None:
+            self.ctx.set_zones(self.cfg.zones_setting())
         self.fusion = fusion
         if fusion is not None:                                  # the per-stream filter state lives on the device from here on
             self._fusion = fusion.to_struct()
@@ -274,6 +291,11 @@ class FlowStream:
         """[batch, 24] cov records (ofk.h: ofk_set_cov) of the latest step with the covariance on; ofk.cov_matrix(rec[:, 0:6]) is C_v,
         rec[:, 6:12] C_uav, 14 the NIS of the filter's correct, 15 whether it was gated."""
         return self.ctx.cov_download(self.batch)
+
+    def zones(self):
+        """The streams' exclusion zones behind the latest step (ofk.Context.zones_download): dict(zones [batch,16,67] i32, motion
+        [batch,16,4] f32, stats [batch,8] i32)."""
+        return self.ctx.zones_download(self.batch)
 
     def begin(self, first_bgr):
         return self.ctx.stream_begin(first_bgr, self._params)

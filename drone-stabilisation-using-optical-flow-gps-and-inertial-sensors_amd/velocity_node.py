@@ -106,6 +106,7 @@ class optical_fusion:
     _track_gate = {}                                             # PipelineConfig's fb_check / fb_thr / fb_level / err_max; empty: no gate
     _corner_grid = {}                                            # PipelineConfig's grid_cell / grid_cap / grid_max_rank; empty: no grid
     _cov = {}                                                    # PipelineConfig's covariance fields (cov, sigma_*, ...); empty: no covariance
+    _zones = {}                                                  # PipelineConfig's zones / zone_* fields; empty: no exclusion zones
     feature_params = dict(qualityLevel=0.7, minDistance=10, blockSize=12)
     lk_params = dict(winSize=(15, 15), maxLevel=3, criteria=(cv2.TERM_CRITERIA_EPS | cv2.TERM_CRITERIA_COUNT, 20, 0.03))
     scaling = 0.01
@@ -260,7 +261,7 @@ class optical_fusion:
                                  min_distance=float(self.feature_params["minDistance"]), block_size=int(self.feature_params["blockSize"]),
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
-                                 **self._cov)
+                                 **self._cov, **self._zones)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -355,7 +356,7 @@ class optical_fusion:
             Rm = np.asarray(self.rotation, np.float64).reshape(3, 3)
             self.vel_err = np.sqrt(np.maximum(np.diag(Rm @ ofk.cov_matrix(cv[6:12]) @ Rm.T), 0.0))
 
-    def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None):
+    def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -366,7 +367,10 @@ class optical_fusion:
         alive (ofk.h: ofk_set_corner_grid).
         cov: None or a dict of PipelineConfig's covariance fields with `mode` for its `cov`, e.g. dict(mode="propagate",
         sigma_flow_px=0.3, sigma_d=0.05, sigma_omega=0.01): every solved step then fills self.vel_err = sqrt(diag(C_uav)), the
-        attribute the reference carries through its callbacks and never reads (ofk.h: ofk_set_cov); self.last_cov is the record."""
+        attribute the reference carries through its callbacks and never reads (ofk.h: ofk_set_cov); self.last_cov is the record.
+        zones: None or a dict of ofk.zones_setting's keywords (an empty selection of them: dict(mode="hull")), e.g. dict(link=48,
+        radius=20, ttl=30): the points the solve stage rejects build exclusion zones that move with them and keep the re-detection
+        off an independently moving object (ofk.h: ofk_set_zones); self._stream.zones() reads the table."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -383,6 +387,11 @@ class optical_fusion:
         if self._cov:
             PipelineConfig(**self._cov).cov_setting()            # unknown or invalid keywords fail here, not at the first frame
         self.last_cov = None
+        z = dict(zones or {})
+        if zones is not None:
+            ofk.zones_setting(**z)                               # unknown or invalid keywords fail here, not at the first frame
+        names = dict(link="zone_link", min_members="zone_min", radius="zone_radius", ttl="zone_ttl", max_zones="zone_max")
+        self._zones = dict(zones=z.pop("mode", "hull"), **{names[k]: v for k, v in z.items()}) if zones is not None else {}
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

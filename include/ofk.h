@@ -134,6 +134,63 @@ int ofk_good_features_grid(ofk_ctx *ctx, const uint8_t *gray, const uint8_t *mas
                            double quality, double min_distance, int block_size, float *pts, int *counts, const ofk_corner_grid *g,
                            const float *occ_pts, const int *occ_counts, int occ_stride);
 
+/* Exclusion zones: the solve stage's verdict fed back into the re-detection.  The reference's earlier tracker looped "find cluster ->
+ * mask -> re-detect" on the host (of_library.py:146-226: distancecluster, convexhull, circles); here a per-stream table of zones lives
+ * on the device, is built from the points the solve stage rejected, moves along with the object and is zeroed in the re-detection mask
+ * beside the track discs, so a re-detection does not put corners straight back on an independently moving object.  Off by default;
+ * with it off every stream step launches the kernels and returns the bits it always did.  Streams only: ofk_pairs_run ignores the
+ * setting.
+ * Per stream and per step, in this order; all image arithmetic is integer (64-bit where products need it):
+ *   1. Rejects: the points i < count whose status behind the track gates is 1 and whose keep flag behind the solve stage (the
+ *      feasibility rule, the legacy keep, the robust drop) is 0; lost tracks never count.  A reject's position is ((int)x, (int)y) of
+ *      its OLD position - k_disc_mask's convention and the frame the re-detection runs on - each axis first brought into
+ *      -32768..32767 (not a number: -32768); its flow is (double)new - (double)old per axis.
+ *   2. Refresh: a reject whose position lies inside the shape (rule 5) of a live zone sets that zone's ttl back to the setting's, for
+ *      every such zone, and takes no part in rule 3.
+ *   3. Cluster: the remaining rejects fall into connected components, two of them linked when |dx| < link && |dy| < link
+ *      (of_library.distancecluster's rule); a component's id is its smallest point index; components are handled in ascending id.
+ *   4. Insert: a component of at least min_members rejects becomes a zone.  Vertices: the convex hull of the members' positions,
+ *      duplicates merged, collinear points removed, in the order of Andrew's chain (points sorted by x then y; lower chain, then upper);
+ *      a hull of more than OFK_ZONE_VERTS vertices is replaced by the bounding box (x0,y0),(x1,y0),(x1,y1),(x0,y1).  flow = f32 of the
+ *      members' f64 flow sum (ascending index) divided by their number; off = (0,0); ttl = the setting's.  The zone goes to the free
+ *      slot of lowest index below max_zones; with none free it replaces the zone of smallest ttl among them, ties to the lowest slot.
+ *   5. Shape: V = the vertices + rint(off) (half to even; each axis brought into +-2^20, not a number: -2^20).  A pixel p is in the
+ *      zone when (a) there are at least 3 vertices and cross(b - a, p - a) >= 0 for every edge a -> b, or (b) for some edge, with
+ *      t = (p - a).(b - a) and L = |b - a|^2: |p - a|^2 <= r^2, or |p - b|^2 <= r^2, or 0 < t < L and cross^2 <= r^2 L.  One vertex
+ *      is a disc, two are a capsule.
+ *   6. Mask: on a step that re-detects, every live zone's pixels are zeroed in the mask behind the track discs; the replace-mode
+ *      re-detection of ofk_stream_step_fused (no mask without zones) runs behind a mask of the zones alone, which are in the previous
+ *      frame's coordinates at that point.
+ *   7. Advect and age, at the end of the step, the zones inserted in it included: off = off + flow in f32, ttl -= 1, a zone at 0 is
+ *      freed (its slot reads all zero).
+ * ofk_stream_begin[_jpeg] clears the table; a held step (ofk_fusion.hold_on_skip) leaves it untouched.
+ * ofk_set_zones: NULL or mode OFK_ZONES_OFF switches the feature off.  OFK_E_INVALID, the setting staying as it was: a mode that is
+ * neither, link outside 1..4096, min_members outside 1..ctx max_pts, radius outside 0..255, ttl outside 1..65535, max_zones outside
+ * 1..OFK_ZONE_MAX.
+ * ofk_zones_step, the stage entry: rules 1-7 on host arrays (old_pts / new_pts [batch][stride][2] f32, status / keep [batch][stride]
+ * u8, counts [batch]) against the context's resident table with the context's setting (which must be on); mask_out [batch][h][w] u8 =
+ * mask_in (NULL: all ones) with every stream's live zones zeroed (rule 6).  Positions beyond +-32767 are taken as rule 1 states.
+ * ofk_zones_reset: clears the tables of the first `batch` streams.
+ * ofk_zones_download, all of the context's max_batch streams (a NULL buffer is skipped):
+ *   zones  [max_batch][OFK_ZONE_MAX][OFK_ZONE_INTS] i32: ttl (0 = free), vertices, members, then OFK_ZONE_VERTS x (x, y)
+ *   motion [max_batch][OFK_ZONE_MAX][OFK_ZONE_FLOATS] f32: off x, y; flow x, y
+ *   stats  [max_batch][OFK_ZONE_STATS] i32 of the latest step: live zones behind rule 7, zones inserted, zones refreshed, inserts that
+ *          replaced a live zone, rejects seen, rejects absorbed by rule 2, sweeps of rule 3's labelling; the eighth slot is reserved and reads 0. */
+#define OFK_ZONES_OFF  0
+#define OFK_ZONES_HULL 1
+#define OFK_ZONE_MAX   16
+#define OFK_ZONE_VERTS 32
+#define OFK_ZONE_INTS  67
+#define OFK_ZONE_FLOATS 4
+#define OFK_ZONE_STATS 8
+typedef struct ofk_zones { int mode; int link; int min_members; int radius; int ttl; int max_zones; } ofk_zones;
+int ofk_set_zones(ofk_ctx *ctx, const ofk_zones *z);
+int ofk_get_zones(const ofk_ctx *ctx, ofk_zones *z);
+int ofk_zones_step(ofk_ctx *ctx, const float *old_pts, const float *new_pts, const uint8_t *status, const uint8_t *keep, const int *counts,
+                   int batch, int stride, int h, int w, const uint8_t *mask_in, uint8_t *mask_out);
+int ofk_zones_reset(ofk_ctx *ctx, int batch);
+int ofk_zones_download(ofk_ctx *ctx, int *zones, float *motion, int *stats);
+
 /* cv2.calcOpticalFlowPyrLK(prev, next, prevPts, None, winSize=(win,win), maxLevel, criteria=(EPS|COUNT, max_count, eps))
  * — of_module.py:88; node:133; evaluate_exp.py:98; of_library.py:249.
  * prev_pts/next_pts [batch][pts_stride][2] f32, counts [batch] (points used per image, <= pts_stride),
