@@ -361,7 +361,9 @@ int ofk_lk_pyr_fb(ofk_ctx *ctx, const uint8_t *prev, const uint8_t *next, int ba
  * robust solve on those of final weight w > 0), with the solve's per-point terms q, sA, sB and M = sum w sA^2 X^T X,
  * g = sum w sA sB X^T X q.  The plain solve's v = M^+ g is a function of its inputs; C_v = J Sigma J^T with J its exact first
  * derivative and Sigma diagonal: all inputs independent and zero-mean (the noise model of simulation.py:40-45).  The robust weights
- * are held fixed (the usual IRLS sandwich) and v is the solve's own, read from its record.
+ * are held fixed (the usual IRLS sandwich) and v is the solve's own, read from its record.  A point the robust drop takes out of a
+ * stream's tracks in the same step has w = 0 and a cleared keep flag by the time the covariance kernel runs behind the solve: it is no
+ * kept point by either, and that step's record is the same with drop 0 and drop 1.
  *   source     inputs                                            variance each
  *   flow       u_i, 2 per kept point                             sigma_flow^2
  *   position   x_i, 2 per kept point, u_i held fixed             sigma_pos^2

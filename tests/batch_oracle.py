@@ -1,5 +1,5 @@
 """The CPU oracle chain of one frame pair (gray -> corners -> pyramidal LK -> node solve -> lever arm and rotation), run over many
-pairs on a thread pool, and the comparisons the batch-shape GPU tests apply to ofk_pairs_run's outputs.  Test infrastructure only."""
+pairs on a thread pool, the same chain with the corner grid and with every pair setting composed, and the comparisons the batch-shape GPU tests apply to ofk_pairs_run's outputs.  Test infrastructure only."""
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -27,6 +27,51 @@ def oracle_chain(prev, nxt, cfg, sr):
     v_uav = eo.post_solve(v, sr[7:16].reshape(3, 3), om, sr[16:19])
     return dict(pts=pts.reshape(-1, 2), nxt=n.reshape(-1, 2), status=s.ravel(), err=e.ravel(), v=v, R=R, rank=int(rank), s=sv,
                 v_uav=v_uav, used=len(x), tracked=int(ok.sum()))
+
+
+def grid_chain(prev, nxt, cfg, sr, grid):
+    """oracle_chain with the corners taken from the corner grid's reference selection (tests/corner_grid_reference.py)."""
+    import corner_grid_reference as R
+    g0, g1 = io.gray_bgr8(prev), io.gray_bgr8(nxt)
+    pts, stats, _ = R.good_features(g0, cfg.max_corners, cfg.quality, cfg.min_distance, cfg.block_size, grid=grid)
+    n, s, e = io.lk_pyr(g0, g1, pts.reshape(-1, 1, 2), cfg.win, cfg.max_level, cfg.max_count, cfg.eps, cfg.min_eig_thr)
+    ok = s.ravel() == 1
+    new = n.reshape(-1, 2).astype(np.float64); old = pts.astype(np.float64)
+    x = (new[ok] - [sr[20], sr[21]]) * sr[19]; u = (new[ok] - old[ok]) * sr[19]
+    v, Rr, rank, sv = eo.solve_lgs_node(x, u, sr[0], sr[1:4], sr[4:7])
+    return dict(pts=pts, nxt=n.reshape(-1, 2), status=s.ravel(), err=e.ravel(), v=v, R=Rr, rank=int(rank), s=sv,
+                v_uav=eo.post_solve(v, sr[7:16].reshape(3, 3), sr[4:7], sr[16:19]), used=len(x), tracked=int(ok.sum()), stats=stats,
+                plain=io.good_features(g0, cfg.max_corners, cfg.quality, cfg.min_distance, cfg.block_size).reshape(-1, 2))
+
+
+def combined_chain(prev, nxt, cfg, sr, problem, grid, gate, seed_mode, robust, cov, gain=1.0, predict=None):
+    """One frame pair with the settings composed as ofk_pairs_run composes them: the grid's selection (corner_grid_reference) -> the
+    seeded forward pass and the gates (track_gate_reference.gated_cfg with seed= and flags=) -> the robust solve on the gated status
+    (robust_reference; `problem` = the pair's index in the batch, it picks the sample) -> the covariance behind it (cov_reference).
+    robust: robust_reference.robust_solve's keywords; cov: cov_reference.pair_record's cfg.  predict(pts, sr, mode, gain) puts
+    another seed predictor in the place of lk_seed_reference.predict.  A dict assert_pair_matches accepts, plus gate, weights,
+    robust (the solve's full result), grid_stats and cov (the 24-double record)."""
+    import corner_grid_reference as CG
+    import cov_reference as CR
+    import lk_seed_reference as LS
+    import robust_reference as RR
+    import track_gate_reference as TG
+    g0, g1 = io.gray_bgr8(prev), io.gray_bgr8(nxt)
+    pts, stats, _ = CG.good_features(g0, cfg.max_corners, cfg.quality, cfg.min_distance, cfg.block_size, grid=grid)
+    if seed_mode and len(pts):
+        seed = np.ascontiguousarray((predict or LS.predict)(pts, sr, seed_mode, gain), np.float32).reshape(-1, 2)
+        r = TG.gated_cfg(g0, g1, pts, cfg, gate, seed=seed, flags=LS.USE_INITIAL_FLOW)
+    else:
+        r = TG.gated_cfg(g0, g1, pts, cfg, gate)
+    ok = r["keep"]
+    new = r["next"].astype(np.float64); old = pts.astype(np.float64)
+    x = (new - [sr[20], sr[21]]) * sr[19]; u = (new - old) * sr[19]
+    rb = RR.robust_solve(RR.NODE, x, u, sr[0], sr[1:4], sr[4:7], valid=ok, problem=problem, **robust)
+    rec = np.zeros(16); rec[0:3] = rb["v"]; rec[3] = rb["r"]; rec[4] = rb["rank"]
+    cv = CR.pair_record(CR.NODE, pts, r["next"], r["status"], sr, cov, rec, w=rb["weights"])
+    return dict(pts=pts, nxt=r["next"], status=r["status"], err=r["err"], v=rb["v"], R=np.array([rb["r"]]), rank=int(rb["rank"]), s=rb["s"],
+                v_uav=eo.post_solve(rb["v"], sr[7:16].reshape(3, 3), sr[4:7], sr[16:19]), used=int(rb["cnt"]), tracked=int(ok.sum()),
+                gate=r, weights=rb["weights"], robust=rb, grid_stats=stats, cov=cv)
 
 
 def oracle_many(prev, nxt, cfg, sensors, idx):

@@ -4,7 +4,7 @@ off it is goodFeaturesToTrack's selection (oracle.image_oracle.select_corners, t
 import numpy as np
 
 from oracle import image_oracle as io
-from stream_oracle import NodeLoop, disc_mask
+from stream_oracle import NodeLoop
 
 MAX_CELLS = 2048                                                 # OFK_GRID_MAX_CELLS
 OFF = (0, 0, 0)                                                  # (cell, cap, max_rank)
@@ -78,23 +78,20 @@ def good_features(gray, max_corners, quality, min_distance, block, mask=None, gr
     return select(io.mineig(gray, block), max_corners, quality, min_distance, mask, grid, occ_pts)
 
 
+def grid_detect(cfg, grid, log=None):
+    """stream_oracle.NodeLoop's detection plug through the grid.  log (a list) receives every call's (accepted, examined)."""
+    def detect(gray, budget, mask, occ_pts):
+        pts, stats, _ = good_features(gray, budget, cfg.quality, cfg.min_distance, cfg.block_size, mask=mask, grid=grid, occ_pts=occ_pts)
+        if log is not None:
+            log.append(stats)
+        return pts
+    return detect
+
+
 class GridNodeLoop(NodeLoop):
     """NodeLoop whose first detection runs through the grid with empty cells and whose re-detection (append mode, node:160-172) runs
-    through it behind the same disc mask with the old tracks as the occupancy list."""
+    through it behind the same disc mask with the old tracks as the occupancy list (stream_oracle.NodeLoop's detect=)."""
 
     def __init__(self, first_frame, cfg, min_feat, radius, grid, **kw):
-        super().__init__(first_frame, cfg, min_feat, radius, **kw)
+        super().__init__(first_frame, cfg, min_feat, radius, detect=grid_detect(cfg, grid), **kw)
         self.grid = grid
-        self.tracks = good_features(self.g_prev, cfg.max_corners, cfg.quality, cfg.min_distance, cfg.block_size, grid=grid)[0]
-
-    def step(self, frame, sr, msgs=(), gps=None, lk=None):
-        cfg, old, g_old = self.cfg, self.tracks, self.g_prev
-        out = super().step(frame, sr, msgs, gps, lk)
-        n_old = len(old)
-        if n_old <= self.min_feat and cfg.max_corners - n_old > 0:
-            base = out["tracks"][:int(np.count_nonzero(out["keep"]))]        # the kept tracks stand in front of what NodeLoop appended
-            newf = good_features(g_old, cfg.max_corners - n_old, cfg.quality, cfg.min_distance, cfg.block_size,
-                                 mask=disc_mask(*g_old.shape, old, self.radius), grid=self.grid, occ_pts=old)[0]
-            self.tracks = np.concatenate([base, newf])[:cfg.max_corners]
-            out["tracks"] = self.tracks.copy()
-        return out

@@ -38,11 +38,11 @@ def on_object(pts, t):
 def robust_solver(problem, drop, fused, setting=SETTING):
     """stream_oracle.NodeLoop's solver plug for a stream under ofk_set_robust.  problem: the stream's index in the batch (it picks the
     sample).  fused: step_fused solves with more than min_solve = 2 kept points, the plain stream step whenever one is kept.
-    Extras of the step's record: used, weights, stats, rank, gap, near."""
+    Extras of the step's record: used, weights, stats, rank, gap, near, rss."""
     min_cnt = 2 if fused else 0
 
     def solve(x, u, ok, d, nrm, om):
         r = rr.robust_solve(rr.NODE, x, u, d, nrm, om, valid=ok, problem=problem, min_cnt=min_cnt, **setting)
         return dict(v=r["v"], solved=int(ok.sum()) > min_cnt, keep=ok & (r["weights"] > 0) if drop else ok,
-                    used=r["cnt"], weights=r["weights"], stats=r["stats"], rank=r["rank"], gap=r["gap"], near=r["near"])
+                    used=r["cnt"], weights=r["weights"], stats=r["stats"], rank=r["rank"], gap=r["gap"], near=r["near"], rss=r["r"])
     return solve

@@ -8,7 +8,7 @@ import pytest
 from oracle import image_oracle as io, estimation_oracle as eo
 import corner_grid_cases as K
 import corner_grid_reference as R
-from batch_oracle import assert_pair_matches  # noqa: E402  (tests/batch_oracle.py)
+from batch_oracle import assert_pair_matches, grid_chain  # noqa: E402  (tests/batch_oracle.py)
 from stream_oracle import NodeLoop, disc_mask, track  # noqa: E402  (tests/stream_oracle.py)
 
 pytestmark = pytest.mark.gpu
@@ -125,20 +125,6 @@ CORNERS = dict(max_corners=60, quality=0.01, min_distance=5, block_size=5)
 LK = dict(win=15, max_level=2, max_count=20, eps=0.03, min_eig_thr=1e-4)
 MOTION = dict(v=(0.003, -0.002, 0.001), omega=(0.03, -0.02, 0.1))
 STREAM_MOTION = dict(v=(0.003, -0.002, 0.001), omega=(0.015, -0.01, 0.05), d=1.0)
-
-
-def grid_chain(prev, nxt, cfg, sr, grid):
-    """tests/batch_oracle.oracle_chain with the corners taken from the reference selection."""
-    g0, g1 = io.gray_bgr8(prev), io.gray_bgr8(nxt)
-    pts, stats, _ = R.good_features(g0, cfg.max_corners, cfg.quality, cfg.min_distance, cfg.block_size, grid=grid)
-    n, s, e = io.lk_pyr(g0, g1, pts.reshape(-1, 1, 2), cfg.win, cfg.max_level, cfg.max_count, cfg.eps, cfg.min_eig_thr)
-    ok = s.ravel() == 1
-    new = n.reshape(-1, 2).astype(np.float64); old = pts.astype(np.float64)
-    x = (new[ok] - [sr[20], sr[21]]) * sr[19]; u = (new[ok] - old[ok]) * sr[19]
-    v, Rr, rank, sv = eo.solve_lgs_node(x, u, sr[0], sr[1:4], sr[4:7])
-    return dict(pts=pts, nxt=n.reshape(-1, 2), status=s.ravel(), err=e.ravel(), v=v, R=Rr, rank=int(rank), s=sv,
-                v_uav=eo.post_solve(v, sr[7:16].reshape(3, 3), sr[4:7], sr[16:19]), used=len(x), tracked=int(ok.sum()), stats=stats,
-                plain=io.good_features(g0, cfg.max_corners, cfg.quality, cfg.min_distance, cfg.block_size).reshape(-1, 2))
 
 
 @pytest.mark.parametrize("slices", [1, 2])

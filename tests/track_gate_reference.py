@@ -4,6 +4,7 @@ cap on LK's err, rule by rule in numpy over tests/lk_seed_reference.lk_pyr for b
 gate         a dict(fb="off"|"plain"|"seeded", fb_thr, fb_level, err_max) - the keywords of ofk.track_gate_setting.
 gated        the five rules for one image -> dict(next, status, st_f, err, back, st_b, fb2, stats, keep).
 gated_lk     the tracker plug lk(g_prev, g, old) of stream_oracle.NodeLoop.
+seeded_gated_lk  the tracker plug lk(g_prev, g, old, src) of stream_oracle.NodeLoop (lk_src=): the gates over the seeded forward pass.
 gated_chain  batch_oracle.oracle_chain with the gate between LK and the solve (a dict batch_oracle.assert_pair_matches accepts).
 experiment   the rows of lk_seed_reference.ROWS gated: tracked / wrong / good-lost counts and the NODE solve's relative error.
 """
@@ -77,6 +78,22 @@ def gated_lk(cfg, gate, log=None):
     """The tracker plug of NodeLoop: (next, gated status, err).  log (a list) receives every call's full result."""
     def lk(g_prev, g, old):
         r = gated_cfg(g_prev, g, old, cfg, gate)
+        if log is not None:
+            log.append(r)
+        return r["next"].reshape(-1, 1, 2), r["status"].reshape(-1, 1), r["err"].reshape(-1, 1)
+    return lk
+
+
+def seeded_gated_lk(cfg, gate, mode, gain=1.0, log=None, predict=None):
+    """NodeLoop's lk_src plug under ofk_set_lk_seed + ofk_set_track_gate: the forward pass starts at the seeds predicted from the
+    row `src` (lk_seed_reference.predict; mode 0 = unseeded), the gates follow.  predict(old, src, mode, gain) -> seeds [n,2] f32
+    puts another predictor in its place (the device's ofk_predict_points).  log (a list) receives every call's full result."""
+    def lk(g_prev, g, old, src):
+        if mode and len(old):
+            seed = np.ascontiguousarray((predict or R.predict)(old, src, mode, gain), np.float32).reshape(-1, 2)
+            r = gated_cfg(g_prev, g, old, cfg, gate, seed=seed, flags=R.USE_INITIAL_FLOW)
+        else:
+            r = gated_cfg(g_prev, g, old, cfg, gate)
         if log is not None:
             log.append(r)
         return r["next"].reshape(-1, 1, 2), r["status"].reshape(-1, 1), r["err"].reshape(-1, 1)

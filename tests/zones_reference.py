@@ -1,5 +1,5 @@
 """Exclusion zones (include/ofk.h: ofk_zones) restated in numpy: the reference the zone tests compare the device against bit for bit,
-and a NodeLoop whose re-detection mask carries the zones.  All image arithmetic is Python / int64 integers, the two float steps (the
+and the constructor of a NodeLoop whose re-detection mask carries the zones.  All image arithmetic is Python / int64 integers, the two float steps (the
 mean flow, the advection) are written in the precision the header states.  Test infrastructure only.
 
 What the zones achieve is stated on this loop (tests/test_zones_reference.py): robust_stream_oracle.sequence at 480 x 640, 12 frames,
@@ -13,8 +13,7 @@ ttl 30, 16 zones).  Measured with the committed code, seeds 900 and 901, without
     relative velocity error, largest                        0.0050 -> 0.0050  0.0048 -> 0.0048"""
 import numpy as np
 
-from oracle import image_oracle as io
-from stream_oracle import NodeLoop, disc_mask
+from stream_oracle import NodeLoop
 
 OFF, HULL = 0, 1
 ZONE_MAX, ZONE_VERTS = 16, 32
@@ -206,48 +205,9 @@ def step(table, s, old, new, status, keep, h, w, mask_in=None):
 
 
 class ZoneNodeLoop(NodeLoop):
-    """NodeLoop with the zone table of one stream: the step's rejects (tracked, not kept by the solver) update the table, an
-    append-mode re-detection runs behind the disc mask with the zones zeroed in it, then the zones move on and age.
-    replace: the re-detection of ofk_fusion.redetect_replace instead - before tracking, a stream with few tracks replaces them by
-    fresh corners of its previous frame, found behind a mask of the zones alone; nothing is appended behind the solve."""
+    """NodeLoop with the zone table of one stream (stream_oracle.NodeLoop's zones= and replace=): the step's rejects (tracked, not kept
+    by the solver) update the table, an append-mode re-detection runs behind the disc mask with the zones zeroed in it, a
+    replace-mode one behind a mask of the zones alone, then the zones move on and age."""
 
     def __init__(self, first_frame, cfg, min_feat, radius, setting=None, replace=False, **kw):
-        super().__init__(first_frame, cfg, min_feat, radius, **kw)
-        self.setting = dict(DEFAULT, **(setting or {}))
-        self.table = Table()
-        self.replace = replace
-
-    def step(self, frame, sr, msgs=(), gps=None, lk=None):
-        cfg, g_old = self.cfg, self.g_prev
-        budget = cfg.max_corners - len(self.tracks)
-        redetected = bool(len(self.tracks) <= self.min_feat and budget > 0)
-        if self.replace and redetected:
-            mask = render(self.table, self.setting, np.ones(g_old.shape, np.uint8))
-            self.tracks = io.good_features(g_old, budget, cfg.quality, cfg.min_distance, cfg.block_size, mask=mask).reshape(-1, 2)
-        old = self.tracks
-        inner, seen = lk or self.lk, {}
-
-        def spy(g_prev, g, pts):
-            seen["r"] = inner(g_prev, g, pts)
-            return seen["r"]
-        min_feat = self.min_feat
-        if self.replace:
-            self.min_feat = -1                                   # NodeLoop appends nothing
-        try:
-            out = super().step(frame, sr, msgs, gps, spy)
-        finally:
-            self.min_feat = min_feat
-        n_old = len(old)
-        new = seen["r"][0].reshape(-1, 2) if n_old else np.zeros((0, 2), np.float32)
-        st = seen["r"][1].ravel() if n_old else np.zeros(0, np.uint8)
-        update(self.table, self.setting, old, new, st, np.asarray(out["keep"]).astype(np.uint8))
-        out["redetected"] = redetected
-        if redetected and not self.replace:
-            base = out["tracks"][:int(np.count_nonzero(out["keep"]))]        # the kept tracks stand in front of what NodeLoop appended
-            mask = render(self.table, self.setting, disc_mask(*g_old.shape, old, self.radius))
-            newf = io.good_features(g_old, budget, cfg.quality, cfg.min_distance, cfg.block_size, mask=mask).reshape(-1, 2)
-            self.tracks = np.concatenate([base, newf])[:cfg.max_corners]
-            out["tracks"] = self.tracks.copy()
-        age(self.table)
-        out["zones"] = self.table.copy()
-        return out
+        super().__init__(first_frame, cfg, min_feat, radius, zones=dict(setting or {}), replace=replace, **kw)
