@@ -151,6 +151,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->gate = ofk_track_gate{OFK_FB_OFF, 0.5, -1, 0.0};
     c->cov = ofk_cov{OFK_COV_OFF, 0.0, 0.0, 0.0, {0.0, 0.0, 0.0}, 0.0, 0.0, 0, 0, 0.0, 0.0};
     c->zones = ofk_zones{OFK_ZONES_OFF, 48, 3, 20, 30, OFK_ZONE_MAX};
+    c->camera = ofk_camera{OFK_CAMERA_OFF, 20, 1.0, 1.0, 0.0, 0.0, {0, 0, 0, 0, 0, 0, 0, 0}, 1.0, 1.0, 0.0, 0.0};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -204,7 +205,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
                     c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec,
-                    c->zone_tab};
+                    c->zone_tab, c->pts_prev_u};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
@@ -430,6 +431,7 @@ struct View {
     double *sensors, *records;
     float *pts_back, *err_back, *fb2; uint8_t *status_back; int *gate_stats;   // NULL until a run with a track gate on (gate_alloc)
     int *grid_stats;                                             // NULL until a selection with a corner grid on (grid_alloc)
+    float *pts_prev_u, *pts_next_u;                              // NULL until a run with the camera on (camera_alloc)
 };
 static View view_of(ofk_ctx *c, int b0, int nb, int set)
 {
@@ -451,6 +453,8 @@ static View view_of(ofk_ctx *c, int b0, int nb, int set)
         v.status_back = c->status_back + b * c->max_pts; v.gate_stats = c->gate_stats + b * 4;
     }
     v.grid_stats = c->grid_stats ? c->grid_stats + b * 2 : nullptr;
+    v.pts_prev_u = c->pts_prev_u ? c->pts_prev_u + b * c->max_pts * 2 : nullptr;
+    v.pts_next_u = c->pts_next_u ? c->pts_next_u + b * c->max_pts * 2 : nullptr;
     return v;
 }
 
@@ -686,6 +690,58 @@ static void build_pyramids(ofk_ctx *c, hipStream_t s, uint8_t *pyr0, uint8_t *py
 
 static bool gate_on(const ofk_track_gate &g) { return g.fb_mode != OFK_FB_OFF || g.err_max != 0.0; }
 
+// ------------------------------------------------------------------------------------------------ camera setting
+static bool camera_on(const ofk_ctx *c) { return c->camera.model != OFK_CAMERA_OFF; }
+
+// one_focal: ofk_set_camera's extra rule (the solve has one scaling)
+static int check_camera(ofk_ctx *c, const ofk_camera *m, bool one_focal, const char *who)
+{
+    if (m->model != OFK_CAMERA_BROWN && m->model != OFK_CAMERA_FISHEYE)
+        return ofk_fail(c, OFK_E_INVALID, "%s: model %d is neither OFK_CAMERA_BROWN nor OFK_CAMERA_FISHEYE", who, m->model);
+    if (m->iters < 1 || m->iters > 50) return ofk_fail(c, OFK_E_INVALID, "%s: iters %d outside 1..50", who, m->iters);
+    const double vals[8] = {m->fx, m->fy, m->cx, m->cy, m->fo_x, m->fo_y, m->co_x, m->co_y};
+    for (int k = 0; k < 8; ++k)
+        if (!std::isfinite(vals[k]) || !std::isfinite(m->k[k])) return ofk_fail(c, OFK_E_INVALID, "%s: a field is not finite", who);
+    if (m->fx == 0.0 || m->fy == 0.0 || m->fo_x == 0.0 || m->fo_y == 0.0) return ofk_fail(c, OFK_E_INVALID, "%s: fx, fy, fo_x and fo_y must not be 0", who);
+    if (m->model == OFK_CAMERA_FISHEYE && (m->k[4] != 0.0 || m->k[5] != 0.0 || m->k[6] != 0.0 || m->k[7] != 0.0))
+        return ofk_fail(c, OFK_E_INVALID, "%s: the fisheye model has four coefficients: k[4..7] must be 0", who);
+    if (one_focal && m->fo_x != m->fo_y)
+        return ofk_fail(c, OFK_E_INVALID, "%s: fo_x = %g and fo_y = %g differ: the solve has one scaling (sensors[19] = 1 / fo_x)", who, m->fo_x, m->fo_y);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_camera(ofk_ctx *c, const ofk_camera *m)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!m || m->model == OFK_CAMERA_OFF) { c->camera.model = OFK_CAMERA_OFF; return OFK_OK; }
+    TRY(check_camera(c, m, true, "ofk_set_camera"));
+    c->camera = *m;
+    return OFK_OK;
+}
+
+extern "C" int ofk_get_camera(const ofk_ctx *c, ofk_camera *m)
+{
+    if (!c || !m) return OFK_E_INVALID;
+    *m = c->camera;
+    return OFK_OK;
+}
+
+// the ideal points' resident buffers, allocated when a run first needs them; `batch`: the run's images, for ofk_camera_download
+static int camera_prepare(ofk_ctx *c, int batch)
+{
+    if (!camera_on(c)) return OFK_OK;
+    if (!c->pts_prev_u) {                                        // one allocation, carved into the two buffers
+        const size_t np = (size_t)c->max_batch * c->max_pts;
+        float *base = nullptr;
+        OFK_HIP(c, hipMalloc((void **)&base, np * 16));
+        OFK_HIP(c, hipMemsetAsync(base, 0, np * 16, c->stream));
+        OFK_HIP(c, hipStreamSynchronize(c->stream));
+        c->pts_prev_u = base; c->pts_next_u = base + np * 2;
+    }
+    c->cam_batch = batch;
+    return OFK_OK;
+}
+
 // Rules 2-5 of the track gates (ofk.h) behind a forward LK of the view on stream s: the backward LK, which is the forward launch with
 // the two pyramids swapped and a level table of the gate's depth, then k_track_gate.  The view's gate buffers exist (gate_alloc).
 static int gate_tracks(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, int win, int max_level, int max_count, double eps,
@@ -708,14 +764,24 @@ static int gate_tracks(ofk_ctx *c, hipStream_t s, const View &v, const ofk_level
 
 // The track step of the resident chains: with ofk_set_lk_seed on, the start positions are written where LK reads them (imu_state: the
 // source k_stream_fuse uses under use_imu, NULL = the sensors only) and LK starts there;
-// with ofk_set_track_gate on, the gates follow on the same stream
+// with ofk_set_track_gate on, the gates follow on the same stream.  With ofk_set_camera on (the view's ideal buffers exist:
+// camera_alloc) the sensors speak of the ideal image, so the predictor runs on the ideal points and its seeds are brought back into
+// the image; behind the gates the ideal points of both sets are written for the solve stage - one launch, unless the seed needed
+// the previous points' earlier.
 static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, const ofk_params *p, const double *imu_state)
 {
-    const bool seeded = c->lk_seed_mode != OFK_SEED_OFF;
-    if (seeded) ofk_launch_seed_points(s, v.pts_prev, v.counts, c->max_pts, v.sensors, imu_state, c->lk_seed_mode, c->lk_seed_gain, v.pts_next, v.nb);
+    const bool seeded = c->lk_seed_mode != OFK_SEED_OFF, cam = camera_on(c);
+    if (seeded && cam) {
+        ofk_launch_camera(s, &c->camera, 0, v.pts_prev, v.pts_prev_u, nullptr, nullptr, v.counts, c->max_pts, v.nb);
+        ofk_launch_seed_points(s, v.pts_prev_u, v.counts, c->max_pts, v.sensors, imu_state, c->lk_seed_mode, c->lk_seed_gain, v.pts_next, v.nb);
+        ofk_launch_camera(s, &c->camera, 1, v.pts_next, v.pts_next, nullptr, nullptr, v.counts, c->max_pts, v.nb);
+    } else if (seeded)
+        ofk_launch_seed_points(s, v.pts_prev, v.counts, c->max_pts, v.sensors, imu_state, c->lk_seed_mode, c->lk_seed_gain, v.pts_next, v.nb);
     ofk_launch_lk(s, v.pyr[0], v.pyr[1], c->pyr_stride, lv, v.pts_prev, v.counts, c->max_pts, p->win, p->max_count, p->eps, p->min_eig_thr,
                   v.pts_next, v.status, v.err, v.nb, seeded ? OFK_LK_USE_INITIAL_FLOW : 0);
     if (gate_on(c->gate)) TRY(gate_tracks(c, s, v, lv, p->win, p->max_level, p->max_count, p->eps, p->min_eig_thr, c->gate));
+    if (cam && seeded) ofk_launch_camera(s, &c->camera, 0, v.pts_next, v.pts_next_u, nullptr, nullptr, v.counts, c->max_pts, v.nb);
+    else if (cam) ofk_launch_camera(s, &c->camera, 0, v.pts_prev, v.pts_prev_u, v.pts_next, v.pts_next_u, v.counts, c->max_pts, v.nb);
     return OFK_OK;
 }
 
@@ -1600,6 +1666,8 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
     if (c->cov.mode != OFK_COV_OFF) { TRY(cov_alloc(c)); c->cov_batch = B; }
+    TRY(camera_prepare(c, B));
+    const bool cam = camera_on(c);                               // the solve stage reads the ideal points
     TRY(need_streams(c, S, overlap));
     if (fork) {
         OFK_HIP(c, hipEventRecord(c->ev_fork, c->stream));
@@ -1651,7 +1719,8 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
         if (c->x_pending) OFK_HIP(c, hipStreamWaitEvent(st, c->ev_x, 0));    // the previous call's records are still being exported
         {
             StageTimer t(c, OFK_STAGE_SOLVE, st);
-            solve_pairs(c, st, v.pts_prev, v.pts_next, v.status, v.counts, v.sensors, p, v.cand_count, v.records, b0, nb, false);
+            solve_pairs(c, st, cam ? v.pts_prev_u : v.pts_prev, cam ? v.pts_next_u : v.pts_next, v.status, v.counts, v.sensors, p, v.cand_count,
+                        v.records, b0, nb, false);
         }
         if (S > 1) OFK_HIP(c, hipEventRecord(c->ev_end[k], st));             // joined lazily (join_slices), not here
     }
@@ -1705,6 +1774,51 @@ extern "C" int ofk_pairs_export_records_f32(ofk_ctx *c, void *device_dst, int ba
 {
     if (!c || !device_dst || batch < 1 || batch > c->cur_batch) return ofk_fail(c, OFK_E_INVALID, "ofk_pairs_export_records_f32: bad argument");
     return ofk_export_records_stream(c, (float *)device_dst, batch, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ camera stage entries
+// device scratch only, so resident points and settings are not touched; `out` goes up first: entries beyond counts[b] keep its contents
+static int camera_points(ofk_ctx *c, const char *who, int distort, const ofk_camera *m, const float *pts, const int *counts, int batch, int stride,
+                         float *out)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!m || !pts || !counts || !out || batch < 1 || stride < 1) return ofk_fail(c, OFK_E_INVALID, "%s: bad argument", who);
+    TRY(check_camera(c, m, false, who));
+    for (int b = 0; b < batch; ++b)
+        if (counts[b] < 0 || counts[b] > stride) return ofk_fail(c, OFK_E_INVALID, "%s: counts[%d]=%d outside 0..%d", who, b, counts[b], stride);
+    const size_t pb = (size_t)batch * stride * 8;
+    Bump bp;
+    TRY(est_begin(c, 2 * pb + (size_t)batch * 4, bp));
+    const float *dp = (const float *)bp.put(pts, pb);
+    float *dout = (float *)bp.put(out, pb);
+    const int *dc = (const int *)bp.put(counts, (size_t)batch * 4);
+    if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    ofk_launch_camera(c->stream, m, distort, dp, dout, nullptr, nullptr, dc, stride, batch);
+    TRY(check_launch(c, who));
+    return get(c, out, dout, pb);
+}
+
+extern "C" int ofk_undistort_points(ofk_ctx *c, const ofk_camera *m, const float *pts, const int *counts, int batch, int stride, float *out)
+{
+    return camera_points(c, "ofk_undistort_points", 0, m, pts, counts, batch, stride, out);
+}
+
+extern "C" int ofk_distort_points(ofk_ctx *c, const ofk_camera *m, const float *pts, const int *counts, int batch, int stride, float *out)
+{
+    return camera_points(c, "ofk_distort_points", 1, m, pts, counts, batch, stride, out);
+}
+
+extern "C" int ofk_camera_download(ofk_ctx *c, float *prev_ideal, float *next_ideal, int stride)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->cam_batch < 1 || !c->pts_prev_u) return ofk_fail(c, OFK_E_INVALID, "ofk_camera_download: no run or step with ofk_set_camera on yet");
+    if (stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_camera_download: stride %d", stride);
+    TRY(enter(c));
+    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    if (prev_ideal) OFK_HIP(c, hipMemcpy2DAsync(prev_ideal, (size_t)stride * 8, c->pts_prev_u, mp * 8, n * 8, c->cam_batch, hipMemcpyDeviceToHost, c->stream));
+    if (next_ideal) OFK_HIP(c, hipMemcpy2DAsync(next_ideal, (size_t)stride * 8, c->pts_next_u, mp * 8, n * 8, c->cam_batch, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ exclusion zones
@@ -2029,6 +2143,9 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
     const bool zones_on = c->zones.mode != OFK_ZONES_OFF;
     if (zones_on) { TRY(check_zones(c, &c->zones, "ofk_stream_step")); TRY(zones_alloc(c)); }
+    TRY(camera_prepare(c, B));
+    const bool cam = camera_on(c);                               // the solve stage reads the ideal points; the tracks, the zones and the
+    const float *sp = cam ? c->pts_prev_u : c->pts_prev, *sn = cam ? c->pts_next_u : c->pts_next;   // re-detection stay in the image
     OFK_HIP(c, hipMemcpyAsync(c->sensors, sensors, (size_t)B * OFK_SENSOR_DOUBLES * 8, hipMemcpyHostToDevice, c->stream));
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
@@ -2049,17 +2166,17 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     if (zones_on)                                                // the solve stage turns the status into its keep flags: rule 1 needs both
         OFK_HIP(c, hipMemcpyAsync(c->zone_status, c->status, (size_t)B * c->max_pts, hipMemcpyDeviceToDevice, c->stream));
     if (fu && c->robust.loss != OFK_ROBUST_OFF)
-        ofk_launch_stream_fuse_robust(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
+        ofk_launch_stream_fuse_robust(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
                                       c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, p->use_feasibility, p->feas_T,
                                       c->records, c->fused, &c->robust, c->rob_work, c->rob_w, c->rob_wtmp, c->rob_stats, B, defer);
     else if (fu)
-        ofk_launch_stream_fuse(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
+        ofk_launch_stream_fuse(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
                                c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, p->use_feasibility, p->feas_T,
                                c->records, c->fused, B, defer);
     else
-        solve_pairs(c, c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->sensors, p, nullptr, c->records, 0, B, true);
+        solve_pairs(c, c->stream, sp, sn, c->status, c->counts, c->sensors, p, nullptr, c->records, 0, B, true);
     if (cov_on && fu)
-        ofk_launch_stream_cov(c->stream, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm,
+        ofk_launch_stream_cov(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm,
                               c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, c->records, c->fused,
                               c->robust.loss != OFK_ROBUST_OFF ? c->rob_w : nullptr, &c->cov, c->cov_rec, B);
     // re-detection for the streams that had few features (node:157-166): mask = discs around the OLD positions, image = OLD frame.

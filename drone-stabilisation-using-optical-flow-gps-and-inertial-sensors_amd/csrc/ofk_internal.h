@@ -99,6 +99,9 @@ struct ofk_ctx {
     ofk_zones zones;                         // ofk_set_zones: mode OFK_ZONES_OFF unless set
     int *zone_tab; float *zone_mot; int *zone_stats, *zone_work;   // [B][OFK_ZONE_MAX][OFK_ZONE_INTS], [B][OFK_ZONE_MAX][OFK_ZONE_FLOATS], [B][OFK_ZONE_STATS], [B][2][max_pts] hull stacks;
     uint8_t *zone_status;                    // [B][max_pts] status in front of the solve stage; one lazy allocation (zone_tab owns it)
+    ofk_camera camera;                       // ofk_set_camera: model OFK_CAMERA_OFF unless set
+    float *pts_prev_u, *pts_next_u;          // [B][max_pts][2] ideal pixels of pts_prev / pts_next, what the solve stage reads with the camera on; one lazy allocation (pts_prev_u owns it)
+    int cam_batch;                           // images of the latest run / step with the camera on (ofk_camera_download), 0 = none
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -176,6 +179,10 @@ void ofk_launch_zones_update(hipStream_t s, const float *old_pts, const float *n
 void ofk_launch_zones_age(hipStream_t s, int *tab, float *mot, int *stats, int batch);
 void ofk_launch_zone_mask(hipStream_t s, uint8_t *mask, size_t mask_stride, int h, int w, const int *tab, const float *mot, int radius,
                           const int *limit, int batch);
+// the camera model (ofk.h: ofk_set_camera; k_camera.inc): src0 -> dst0 and, with src1 not NULL, src1 -> dst1 in the same launch;
+// distort 0 = image pixels -> ideal pixels, 1 = the forward map; src may be dst
+void ofk_launch_camera(hipStream_t s, const ofk_camera *cam, int distort, const float *src0, float *dst0, const float *src1, float *dst1,
+                       const int *counts, int pts_stride, int batch);
 void ofk_launch_lk(hipStream_t s, const uint8_t *prev, const uint8_t *next, size_t pyr_stride, const ofk_levels &lv,
                    const float *prev_pts, const int *counts, int pts_stride, int win, int max_count, double eps,
                    double min_eig_thr, float *next_pts, uint8_t *status, float *err, int batch, int flags = 0);   // flags: OFK_LK_*

@@ -1,6 +1,7 @@
 """cv2_hip.py — the cv2 calls on the reference's hot path, with OpenCV's names, signatures and array
 conventions, executed by the HIP kernels of libofk.so.  `import cv2_hip as cv2` in the reference's scripts
-covers: cvtColor(COLOR_BGR2GRAY), goodFeaturesToTrack, calcOpticalFlowPyrLK, KalmanFilter, TERM_CRITERIA_*.
+covers: cvtColor(COLOR_BGR2GRAY), goodFeaturesToTrack, calcOpticalFlowPyrLK, KalmanFilter, TERM_CRITERIA_*; undistortPoints and
+fisheye.undistortPoints / distortPoints belong to the camera model (ofk.h: ofk_set_camera), which the reference does not have.
 
 Reference call sites: of_module.py:40,44,63-76,80,86,88,122,152; velocity_measurment_node:113,120,133,163;
 evaluate_exp.py:65,66,85,98,106; of_library.py:236,238,248,249.
@@ -102,6 +103,83 @@ def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts=None, status=None, e
     ctx = ofk.default_context(w, h, min_pts=max(1, len(pts)), min_level=int(maxLevel))
     return ctx.lk_pyr(prevImg, nextImg, pts, win=int(winSize[0]), max_level=int(maxLevel), max_count=cnt, eps=eps,
                       min_eig_thr=float(minEigThreshold), next_pts=init, flags=flags)
+
+
+def _camera_matrix(m, what):
+    m = np.asarray(m, np.float64)
+    if m.ndim != 2 or m.shape[0] != 3 or m.shape[1] not in (3, 4):
+        raise ValueError(f"{what} must be 3x3 (P: or 3x4)")
+    if m[0, 1] != 0.0:
+        raise NotImplementedError(f"{what}: no skew term")
+    return float(m[0, 0]), float(m[1, 1]), float(m[0, 2]), float(m[1, 2])
+
+
+def _points_32fc2(src, who):
+    src = np.asarray(src)
+    if src.dtype != np.float32:
+        raise ValueError(f"{who}: CV_32FC2 points only (got {src.dtype})")
+    if src.size % 2 or src.shape[-1] != 2:
+        raise ValueError(f"{who}: points must be (N,1,2) or (N,2)")
+    return src, np.ascontiguousarray(src.reshape(-1, 2))
+
+
+def _identity_only(R, who):
+    if R is not None and not np.array_equal(np.asarray(R, np.float64), np.eye(3)):
+        raise NotImplementedError(f"{who}: a rectification R other than the identity is not supported")
+
+
+def _lens_points(who, distort, model, src, K, k, P, iters):
+    src, pts = _points_32fc2(src, who)
+    fx, fy, cx, cy = _camera_matrix(K, "cameraMatrix")
+    fo_x, fo_y, co_x, co_y = (1.0, 1.0, 0.0, 0.0) if P is None else _camera_matrix(P, "P")
+    cam = ofk.camera_setting(model, fx, fy, cx, cy, k, iters, fo_x, fo_y, co_x, co_y)
+    if not len(pts):
+        return src.copy()
+    ctx = ofk.default_context()
+    out = (ctx.distort_points if distort else ctx.undistort_points)(cam, pts)
+    return out.reshape(src.shape)
+
+
+def undistortPoints(src, cameraMatrix, distCoeffs, R=None, P=None, criteria=None):
+    """cv2.undistortPoints / undistortPointsIter for CV_32FC2 points ((N,1,2) or (N,2) float32; float64 raises): 4, 5 or 8 distortion
+    coefficients (k1 k2 p1 p2 [k3 [k4 k5 k6]]), no R other than the identity, P None = normalised output.  The fixed-point count is
+    cv2's 5 unless `criteria` carries TERM_CRITERIA_COUNT; it is a FIXED count (an EPS in the criteria is not looked at), see
+    ofk.camera_setting for what 5 leaves on a wide-angle lens."""
+    _identity_only(R, "undistortPoints")
+    k = [] if distCoeffs is None else np.asarray(distCoeffs, np.float64).reshape(-1)
+    if len(k) not in (0, 4, 5, 8):
+        raise ValueError(f"undistortPoints: {len(k)} distortion coefficients (4, 5 or 8 are supported)")
+    iters = 5
+    if criteria is not None and int(criteria[0]) & TERM_CRITERIA_COUNT:
+        iters = int(criteria[1])
+    return _lens_points("undistortPoints", False, "brown", src, cameraMatrix, k, P, iters)
+
+
+class fisheye:
+    """cv2.fisheye's point functions (the equidistant model, D = k1..k4)."""
+
+    @staticmethod
+    def _d(D, who):
+        k = np.asarray(D, np.float64).reshape(-1)
+        if len(k) != 4:
+            raise ValueError(f"fisheye.{who}: D must hold 4 coefficients")
+        return k
+
+    @staticmethod
+    def undistortPoints(distorted, K, D, R=None, P=None, criteria=None):
+        """cv2.fisheye.undistortPoints: pixels -> normalised (or P's) coordinates; 10 Newton steps unless criteria carries a COUNT."""
+        _identity_only(R, "fisheye.undistortPoints")
+        iters = 10
+        if criteria is not None and int(criteria[0]) & TERM_CRITERIA_COUNT:
+            iters = int(criteria[1])
+        return _lens_points("fisheye.undistortPoints", False, "fisheye", distorted, K, fisheye._d(D, "undistortPoints"), P, iters)
+
+    @staticmethod
+    def distortPoints(undistorted, K, D, alpha=0.0):
+        """cv2.fisheye.distortPoints: NORMALISED ideal coordinates -> pixels of the fisheye image (alpha, the skew, must be 0)."""
+        if alpha != 0.0:
+            raise NotImplementedError("fisheye.distortPoints: no skew (alpha)")
+        return _lens_points("fisheye.distortPoints", True, "fisheye", undistorted, K, fisheye._d(D, "distortPoints"), None, 10)
 
 
 class KalmanFilter:

@@ -31,6 +31,7 @@ SYMBOLS = (
     "ofk_set_track_gate", "ofk_get_track_gate", "ofk_track_gate_download", "ofk_lk_pyr_fb",
     "ofk_set_corner_grid", "ofk_get_corner_grid", "ofk_corner_grid_download", "ofk_select_corners_grid", "ofk_good_features_grid",
     "ofk_set_zones", "ofk_get_zones", "ofk_zones_step", "ofk_zones_reset", "ofk_zones_download",
+    "ofk_set_camera", "ofk_get_camera", "ofk_undistort_points", "ofk_distort_points", "ofk_camera_download",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
     "ofk_stream_begin_jpeg", "ofk_stream_step_jpeg",
@@ -70,6 +71,9 @@ GRID_MAX_CELLS = 2048                                   # OFK_GRID_MAX_CELLS: ce
 ZONES_OFF, ZONES_HULL = 0, 1                             # ofk_set_zones
 ZONES_MODES = {"off": ZONES_OFF, "hull": ZONES_HULL}
 ZONE_MAX, ZONE_VERTS, ZONE_INTS, ZONE_FLOATS, ZONE_STATS = 16, 32, 67, 4, 8    # OFK_ZONE_*: slots per stream, vertices per zone, the download's rows
+CAMERA_OFF, CAMERA_BROWN, CAMERA_FISHEYE = 0, 1, 2       # ofk_set_camera / ofk_undistort_points / ofk_distort_points
+CAMERA_MODELS = {"off": CAMERA_OFF, "brown": CAMERA_BROWN, "fisheye": CAMERA_FISHEYE}
+CAMERA_DEFAULT_ITERS = {CAMERA_BROWN: 20, CAMERA_FISHEYE: 10}
 FLOW_LK, FLOW_ROTATIONAL = 0, 1
 KEEP_STATUS, KEEP_LEGACY = 0, 1
 CONTROL_SENSORS, CONTROL_IMU = 0, 1
@@ -195,6 +199,49 @@ def zones_setting(mode="hull", link=48, min_members=3, radius=20, ttl=30, max_zo
     return Zones(mode, link, min_members, radius, ttl, max_zones)
 
 
+class Camera(C.Structure):
+    """ofk_camera (include/ofk.h): the lens model whose distortion is undone in front of the solve stage."""
+    _fields_ = [("model", C.c_int), ("iters", C.c_int), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("k", C.c_double * 8), ("fo_x", C.c_double), ("fo_y", C.c_double), ("co_x", C.c_double), ("co_y", C.c_double)]
+
+
+def camera_setting(model="brown", fx=1.0, fy=None, cx=0.0, cy=0.0, k=(), iters=None, fo_x=None, fo_y=None, co_x=None, co_y=None):
+    """A Camera structure from names: model "off" / "brown" (cv2's pinhole model: k1 k2 p1 p2 [k3 [k4 k5 k6]]) / "fisheye" (cv2.fisheye,
+    equidistant: k1..k4), or CAMERA_*; fx, fy, cx, cy = the camera matrix (fy None = fx); k = the coefficients in cv2's order, missing
+    ones 0; fo_x, fo_y, co_x, co_y = the output matrix the ideal pixels are written in (None = fx for both focal lengths and the
+    camera's centre: ONE focal length, as ofk_set_camera and the solve's one scaling ask for).
+
+    iters is a fixed count; None = 20 for Brown and 10 for the fisheye, not cv2.undistortPoints' 5: on a strong wide-angle lens
+    (k1 = -0.28, 1280 x 960, f = 1000) five fixed-point rounds leave up to 0.47 px of round-trip error at the frame's corners, 8 leave
+    0.018 px, 10 leave 0.0021 px, 15 leave 1e-5 px and 20 leave 4e-8 px, while the fisheye's Newton iteration is at 5e-13 px after 3
+    (tests/test_camera_reference.py pins the 5-round figure)."""
+    if isinstance(model, str):
+        if model not in CAMERA_MODELS:
+            raise ValueError(f"camera model {model!r} is none of {sorted(CAMERA_MODELS)}")
+        model = CAMERA_MODELS[model]
+    model = int(model)
+    if model not in CAMERA_MODELS.values():
+        raise ValueError(f"camera model {model} is none of CAMERA_OFF, CAMERA_BROWN, CAMERA_FISHEYE")
+    kk = [float(v) for v in np.asarray(k, np.float64).reshape(-1)]
+    if len(kk) > 8:
+        raise ValueError(f"camera k has {len(kk)} coefficients, more than 8")
+    kk += [0.0] * (8 - len(kk))
+    iters = CAMERA_DEFAULT_ITERS.get(model, 20) if iters is None else int(iters)
+    fx = float(fx); fy = fx if fy is None else float(fy); cx = float(cx); cy = float(cy)
+    fo_x = fx if fo_x is None else float(fo_x); fo_y = fo_x if fo_y is None else float(fo_y)
+    co_x = cx if co_x is None else float(co_x); co_y = cy if co_y is None else float(co_y)
+    if model != CAMERA_OFF:
+        if not 1 <= iters <= 50:
+            raise ValueError(f"camera iters {iters} outside 1..50")
+        if not np.all(np.isfinite([fx, fy, cx, cy, fo_x, fo_y, co_x, co_y] + kk)):
+            raise ValueError("camera: a field is not finite")
+        if 0.0 in (fx, fy, fo_x, fo_y):
+            raise ValueError("camera fx, fy, fo_x and fo_y must not be 0")
+        if model == CAMERA_FISHEYE and any(kk[4:]):
+            raise ValueError("camera: the fisheye model has four coefficients, k[4..7] must be 0")
+    return Camera(model, iters, fx, fy, cx, cy, (C.c_double * 8)(*kk), fo_x, fo_y, co_x, co_y)
+
+
 class Fusion(C.Structure):
     """ofk_fusion (include/ofk.h): what ofk_stream_step_fused does between LK and the next frame."""
     _fields_ = [("use_imu", C.c_int), ("flow", C.c_int), ("keep", C.c_int), ("filter", C.c_int), ("control", C.c_int),
@@ -280,6 +327,10 @@ def load_library():
         L.ofk_set_zones.argtypes = [vp, C.POINTER(Zones)]; L.ofk_get_zones.argtypes = [vp, C.POINTER(Zones)]
         L.ofk_zones_step.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, vp, vp]
         L.ofk_zones_reset.argtypes = [vp, i]; L.ofk_zones_download.argtypes = [vp, vp, vp, vp]
+        L.ofk_set_camera.argtypes = [vp, C.POINTER(Camera)]; L.ofk_get_camera.argtypes = [vp, C.POINTER(Camera)]
+        L.ofk_undistort_points.argtypes = [vp, C.POINTER(Camera), vp, vp, i, i, vp]
+        L.ofk_distort_points.argtypes = [vp, C.POINTER(Camera), vp, vp, i, i, vp]
+        L.ofk_camera_download.argtypes = [vp, vp, vp, i]
         L.ofk_lk_pyr_fb.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, i, vp, vp, vp, C.POINTER(TrackGate), vp, vp, vp]
         L.ofk_imu_propagate.argtypes = [vp, vp, vp, i]
         L.ofk_post_solve.argtypes = [vp, vp, vp, vp, vp, i, vp]
@@ -666,6 +717,53 @@ class Context:
         with self._lock:
             self._ck(self._L.ofk_zones_step(self._h, _p(op), _p(nw), _p(st), _p(kp), _p(counts), B, S, h, w, _p(mi), _p(out)))
         return out
+
+    def set_camera(self, camera=None, **settings):
+        """ofk_set_camera: a Camera (or camera_setting's keywords); None or model "off" switches it off.  Every later pairs_run and
+        stream step hands its solve stage the ideal pixels of the tracked points; everything in the image keeps the raw ones.  The
+        caller keeps the sensors' scaling, cx, cy at 1 / fo_x, co_x, co_y."""
+        m = camera if camera is not None or not settings else camera_setting(**settings)
+        with self._lock:
+            self._ck(self._L.ofk_set_camera(self._h, C.byref(m) if m is not None else None))
+
+    def get_camera(self):
+        m = Camera()
+        self._ck(self._L.ofk_get_camera(self._h, C.byref(m)))
+        return m
+
+    def _camera_points(self, fn, camera, pts, counts, out):
+        pp = _arr(pts, np.float32)
+        single = pp.ndim == 2
+        if single:
+            pp = pp[None]
+        if pp.ndim != 3 or pp.shape[2] != 2:
+            raise ValueError(f"{fn}: pts {pp.shape} is not [B, S, 2]")
+        B, S = pp.shape[:2]
+        counts = _arr(S if counts is None else counts, np.int32, (B,))
+        res = np.zeros((B, S, 2), np.float32) if out is None else np.array(out, np.float32).reshape(B, S, 2)
+        if S > 0:
+            with self._lock:
+                self._ck(getattr(self._L, fn)(self._h, C.byref(camera), _p(pp), _p(counts), B, S, _p(res)))
+        return res[0] if single else res
+
+    def undistort_points(self, camera, pts, counts=None, out=None):
+        """ofk_undistort_points: image pixels pts [B,S,2] (or [S,2]) f32 -> ideal pixels under `camera` (a Camera; fo_x != fo_y is
+        accepted here); counts None = every point; entries beyond counts[b] keep what `out` holds (zeros without it)."""
+        return self._camera_points("ofk_undistort_points", camera, pts, counts, out)
+
+    def distort_points(self, camera, pts, counts=None, out=None):
+        """ofk_distort_points: the forward map, ideal pixels -> image pixels; arguments as undistort_points."""
+        return self._camera_points("ofk_distort_points", camera, pts, counts, out)
+
+    def camera_download(self, batch):
+        """ofk_camera_download: (prev_ideal, next_ideal) [batch,max_pts,2] f32, the ideal points the solve stage of the latest run or
+        step with the camera on saw.  The library writes that run's rows, so the buffers have max_batch of them."""
+        if not 0 <= int(batch) <= self.max_batch:
+            raise ValueError(f"camera_download: batch {batch} outside 0..{self.max_batch}")
+        a = np.zeros((self.max_batch, self.max_pts, 2), np.float32); b = np.zeros_like(a)
+        with self._lock:
+            self._ck(self._L.ofk_camera_download(self._h, _p(a), _p(b), self.max_pts))
+        return a[:batch].copy(), b[:batch].copy()
 
     def track_gate_download(self, batch, points=True):
         """ofk_track_gate_download of the latest gated run / step -> dict(stats [batch,4] i32: forward-tracked, of those lost by the

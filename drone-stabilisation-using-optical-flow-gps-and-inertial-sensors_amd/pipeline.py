@@ -16,6 +16,33 @@ except ImportError:      # package directory put on sys.path directly
 
 
 @dataclass
+class CameraModel:
+    """The camera of a pipeline (ofk.h: ofk_set_camera): the camera matrix, the lens coefficients in cv2's order ("brown": k1 k2 p1 p2
+    [k3 [k4 k5 k6]]; "fisheye": k1..k4) and the ideal pinhole the solve stage is handed: one focal length fo (None = fx) and the centre
+    co_x, co_y (None = cx, cy).  iters None = ofk.camera_setting's defaults (20 / 10, not cv2's 5)."""
+    fx: float
+    fy: float = None
+    cx: float = 0.0
+    cy: float = 0.0
+    k: tuple = ()
+    model: str = "brown"
+    iters: int = None
+    fo: float = None
+    co_x: float = None
+    co_y: float = None
+
+    def setting(self):
+        """The ofk.Camera structure (range-checked)."""
+        fo = self.fx if self.fo is None else self.fo
+        return ofk.camera_setting(self.model, self.fx, self.fy, self.cx, self.cy, self.k, self.iters, fo, fo, self.co_x, self.co_y)
+
+    def sensor_slots(self):
+        """(scaling, cx, cy) for sensors[19..21]: the ideal pinhole's 1 / fo, co_x, co_y."""
+        m = self.setting()
+        return 1.0 / m.fo_x, m.co_x, m.co_y
+
+
+@dataclass
 class PipelineConfig:
     max_corners: int = 500
     quality: float = 0.01
@@ -77,6 +104,9 @@ class PipelineConfig:
     zone_radius: int = 20
     zone_ttl: int = 30
     zone_max: int = 16
+    # camera model (ofk.h: ofk_set_camera): None, or a CameraModel whose lens distortion is undone on the device in front of the solve
+    # stage; the sensors' scaling, cx, cy are then camera.sensor_slots()
+    camera: object = None
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -126,6 +156,13 @@ class PipelineConfig:
         if self.zones is None or self.zones == "off":
             return None
         return ofk.zones_setting(self.zones, self.zone_link, self.zone_min, self.zone_radius, self.zone_ttl, self.zone_max)
+
+    def camera_setting(self):
+        """The ofk.Camera structure of this configuration, None when no camera model is set."""
+        if self.camera is None:
+            return None
+        m = self.camera.setting() if hasattr(self.camera, "setting") else self.camera
+        return None if m.model == ofk.CAMERA_OFF else m
 
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
@@ -260,6 +297,8 @@ class FlowStream:
             self.ctx.set_cov(self.cfg.cov_setting())
         if self.cfg.zones_setting() is not None:
             self.ctx.set_zones(self.cfg.zones_setting())
+        if self.cfg.camera_setting() is not None:
+            self.ctx.set_camera(self.cfg.camera_setting())
         self.fusion = fusion
         if fusion is not None:                                  # the per-stream filter state lives on the device from here on
             self._fusion = fusion.to_struct()
@@ -296,6 +335,10 @@ class FlowStream:
         """The streams' exclusion zones behind the latest step (ofk.Context.zones_download): dict(zones [batch,16,67] i32, motion
         [batch,16,4] f32, stats [batch,8] i32)."""
         return self.ctx.zones_download(self.batch)
+
+    def ideal_points(self):
+        """(prev, next) [batch, max_pts, 2] f32: the ideal pixels the solve stage of the latest step saw (camera model on)."""
+        return self.ctx.camera_download(self.batch)
 
     def begin(self, first_bgr):
         return self.ctx.stream_begin(first_bgr, self._params)
@@ -341,6 +384,8 @@ class FlowPipeline:
             self.ctx.set_corner_grid(self.cfg.corner_grid_setting())
         if self.cfg.cov != "off":
             self.ctx.set_cov(self.cfg.cov_setting())
+        if self.cfg.camera_setting() is not None:
+            self.ctx.set_camera(self.cfg.camera_setting())
         if streams > 1:
             self.ctx.set_streams(streams)
 
@@ -391,6 +436,10 @@ class FlowPipeline:
     def covariances(self):
         """[batch, 24] cov records (ofk.h: ofk_set_cov) of the latest run with the covariance on (see FlowStream.covariances)."""
         return self.ctx.cov_download(self.batch)
+
+    def ideal_points(self):
+        """(prev, next) [batch, max_pts, 2] f32: the ideal pixels the solve stage of the latest run saw (camera model on)."""
+        return self.ctx.camera_download(self.batch)
 
     def run_async(self):
         self.ctx.pairs_run(self._params)

@@ -62,9 +62,61 @@ def _bilinear(img, xs, ys):
     return (i00 * (1 - a) + i01 * a) * (1 - b) + (i10 * (1 - a) + i11 * a) * b
 
 
+def ideal_grid(h, w, camera):
+    """The ideal pixel (float64 xx, yy) every raw pixel of an h x w frame looks at through `camera` (a pipeline.CameraModel): the
+    lens undone as ofk.h writes it (ofk_set_camera), in float64 and with the model's iteration count."""
+    m = camera.setting()
+    k = list(m.k)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    x0 = (xx - m.cx) / m.fx; y0 = (yy - m.cy) / m.fy
+    if m.model == 1:                                             # Brown: the fixed-point iteration
+        k1, k2, p1, p2, k3, k4, k5, k6 = k
+        x, y = x0, y0
+        for _ in range(m.iters):
+            r2 = x * x + y * y
+            icd = (1.0 + ((k6 * r2 + k5) * r2 + k4) * r2) / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2)
+            dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x); dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+            x = (x0 - dx) * icd; y = (y0 - dy) * icd
+    else:                                                        # equidistant fisheye: Newton on theta
+        k1, k2, k3, k4 = k[:4]
+        td = np.sqrt(x0 * x0 + y0 * y0); t = td
+        for _ in range(m.iters):
+            t2 = t * t; t4 = t2 * t2; t6 = t4 * t2; t8 = t4 * t4
+            t = t - (t * (1.0 + k1 * t2 + k2 * t4 + k3 * t6 + k4 * t8) - td) / (1.0 + 3.0 * k1 * t2 + 5.0 * k2 * t4 + 7.0 * k3 * t6 + 9.0 * k4 * t8)
+        sc = np.where(td < 1e-8, 1.0, np.tan(t) / np.maximum(td, 1e-300))
+        x = x0 * sc; y = y0 * sc
+    return x * m.fo_x + m.co_x, y * m.fo_y + m.co_y
+
+
+def _camera_view(h, w, camera, margin):
+    """(scaling, cx, cy of the ideal pinhole, the ideal grid, a margin that holds it): the frame is what `camera` sees."""
+    scaling, cx, cy = camera.sensor_slots()
+    xx, yy = ideal_grid(h, w, camera)
+    over = max(0.0, -xx.min(), -yy.min(), xx.max() - (w - 1), yy.max() - (h - 1))
+    return scaling, cx, cy, xx, yy, max(int(margin), int(np.ceil(over)) + 16)
+
+
 def render_pair(h, w, seed, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.003), d=1.0, n=(0, 0, 1), scaling=None,
-                margin=48):
-    """Returns dict(prev, next: [h,w,3] uint8 BGR; H: 3x3 pixel homography prev->next; scaling, cx, cy)."""
+                margin=48, camera=None):
+    """Returns dict(prev, next: [h,w,3] uint8 BGR; H: 3x3 pixel homography prev->next; scaling, cx, cy).
+    camera (a pipeline.CameraModel, default None): the frames are what that camera sees - every raw pixel is undistorted to the ideal
+    pixel it looks at, sent through the homography and sampled bilinearly (the previous frame too, at the ideal pixel itself);
+    scaling, cx, cy are then the ideal pinhole's (camera.sensor_slots()) and H lives in ideal pixels."""
+    if camera is not None:
+        scaling, cx, cy, xx, yy, margin = _camera_view(h, w, camera, margin)
+        T = make_texture(h + 2 * margin, w + 2 * margin, seed)
+        T2 = make_texture(h + 2 * margin, w + 2 * margin, seed + 7919, sigma=3.0)
+        H = pixel_homography(v, omega, d, n, scaling, cx, cy)
+        Hi = np.linalg.inv(H)
+        den = Hi[2, 0] * xx + Hi[2, 1] * yy + Hi[2, 2]
+        sx = (Hi[0, 0] * xx + Hi[0, 1] * yy + Hi[0, 2]) / den + margin
+        sy = (Hi[1, 0] * xx + Hi[1, 1] * yy + Hi[1, 2]) / den + margin
+        out = {}
+        for name, (ax, ay) in (("prev", (xx + margin, yy + margin)), ("next", (sx, sy))):
+            base, tint = _bilinear(T, ax, ay), _bilinear(T2, ax, ay)
+            out[name] = np.stack([np.clip(np.rint(base + g * (tint - 127.5)), 0, 255).astype(np.uint8) for g in (0.10, -0.06, 0.08)], -1)
+        return dict(prev=out["prev"], next=out["next"], H=H, scaling=scaling, cx=cx, cy=cy, v=np.asarray(v, np.float64),
+                    omega=np.asarray(omega, np.float64), d=float(d), n=np.asarray(n, np.float64), camera=camera)
     scaling = scaling or 1.0 / max(h, w)
     cx, cy = w / 2.0, h / 2.0
     T = make_texture(h + 2 * margin, w + 2 * margin, seed)
@@ -104,15 +156,18 @@ def warp_frame(bgr, H):
 
 
 def render_sequence(h, w, seed, n_frames, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.003), d=1.0, n=(0, 0, 1),
-                    scaling=None, margin=96):
+                    scaling=None, margin=96, camera=None):
     """`n_frames` BGR frames of one stream under constant per-frame motion: frame k shows the texture through H^k.
-    Returns (frames [n,h,w,3] uint8, info dict as render_pair)."""
-    scaling = scaling or 1.0 / max(h, w)
-    cx, cy = w / 2.0, h / 2.0
+    Returns (frames [n,h,w,3] uint8, info dict as render_pair).  camera: as in render_pair."""
+    if camera is not None:
+        scaling, cx, cy, xx, yy, margin = _camera_view(h, w, camera, margin)
+    else:
+        scaling = scaling or 1.0 / max(h, w)
+        cx, cy = w / 2.0, h / 2.0
+        yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
     T = make_texture(h + 2 * margin, w + 2 * margin, seed)
     T2 = make_texture(h + 2 * margin, w + 2 * margin, seed + 7919, sigma=3.0)
     H = pixel_homography(v, omega, d, n, scaling, cx, cy)
-    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
     frames = np.empty((n_frames, h, w, 3), np.uint8)
     Hk = np.eye(3)
     for k in range(n_frames):

@@ -24,12 +24,12 @@ import numpy as np
 
 try:
     from . import ofk, cv2_hip as cv2, of_library as of
-    from .pipeline import FlowStream, FusionConfig, PipelineConfig
+    from .pipeline import CameraModel, FlowStream, FusionConfig, PipelineConfig
 except ImportError:
     import ofk
     import cv2_hip as cv2
     import of_library as of
-    from pipeline import FlowStream, FusionConfig, PipelineConfig
+    from pipeline import CameraModel, FlowStream, FusionConfig, PipelineConfig
 
 try:                                    # ROS is optional (absent in this image)
     import rospy
@@ -107,6 +107,7 @@ class optical_fusion:
     _corner_grid = {}                                            # PipelineConfig's grid_cell / grid_cap / grid_max_rank; empty: no grid
     _cov = {}                                                    # PipelineConfig's covariance fields (cov, sigma_*, ...); empty: no covariance
     _zones = {}                                                  # PipelineConfig's zones / zone_* fields; empty: no exclusion zones
+    _camera = {}                                                 # PipelineConfig's camera field; empty: the points are taken as ideal pinhole samples
     feature_params = dict(qualityLevel=0.7, minDistance=10, blockSize=12)
     lk_params = dict(winSize=(15, 15), maxLevel=3, criteria=(cv2.TERM_CRITERIA_EPS | cv2.TERM_CRITERIA_COUNT, 20, 0.03))
     scaling = 0.01
@@ -261,7 +262,7 @@ class optical_fusion:
                                  min_distance=float(self.feature_params["minDistance"]), block_size=int(self.feature_params["blockSize"]),
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
-                                 **self._cov, **self._zones)
+                                 **self._cov, **self._zones, **self._camera)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -281,7 +282,8 @@ class optical_fusion:
         self._imu_flush()                                        # host-side assignments, then the IMU messages since the last frame: one upload
         # normal / omega / R / prior velocity come from the resident IMU state (FusionConfig.node(): use_imu); the record only
         # carries what call_imu does not own
-        sensors = ofk.make_sensors(1, d=self.d, offset=self.offset, scaling=self.scaling, cx=translation[0], cy=translation[1])
+        sc, ccx, ccy = self._camera["camera"].sensor_slots() if self._camera else (self.scaling, translation[0], translation[1])
+        sensors = ofk.make_sensors(1, d=self.d, offset=self.offset, scaling=sc, cx=ccx, cy=ccy)
         rec, fused, tracks, counts = fs.step_fused([frame] if is_jpeg else frame[None], sensors)
         self._imu_stale = True                                   # the step wrote self.vel = v_uav on the device (node:261)
         nxt, keep = fs.ctx.stream_last_points(max(1, len(old)))
@@ -356,7 +358,7 @@ class optical_fusion:
             Rm = np.asarray(self.rotation, np.float64).reshape(3, 3)
             self.vel_err = np.sqrt(np.maximum(np.diag(Rm @ ofk.cov_matrix(cv[6:12]) @ Rm.T), 0.0))
 
-    def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None):
+    def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -370,7 +372,11 @@ class optical_fusion:
         attribute the reference carries through its callbacks and never reads (ofk.h: ofk_set_cov); self.last_cov is the record.
         zones: None or a dict of ofk.zones_setting's keywords (an empty selection of them: dict(mode="hull")), e.g. dict(link=48,
         radius=20, ttl=30): the points the solve stage rejects build exclusion zones that move with them and keep the re-detection
-        off an independently moving object (ofk.h: ofk_set_zones); self._stream.zones() reads the table."""
+        off an independently moving object (ofk.h: ofk_set_zones); self._stream.zones() reads the table.
+        camera: None (every point is a sample of an ideal pinhole image, centred and scaled with the node's constants) or a
+        pipeline.CameraModel (or a dict of its fields), e.g. dict(fx=1000, fy=1010, cx=652.3, cy=470.1, k=(-0.28, 0.09, 0, 0)): the
+        restored pipeline then undoes the lens distortion on the device in front of the solve (ofk.h: ofk_set_camera) and takes
+        scaling and centre from the model (1 / fo, co_x, co_y) in the place of self.scaling and the node's (160, 120)."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -392,6 +398,12 @@ class optical_fusion:
             ofk.zones_setting(**z)                               # unknown or invalid keywords fail here, not at the first frame
         names = dict(link="zone_link", min_members="zone_min", radius="zone_radius", ttl="zone_ttl", max_zones="zone_max")
         self._zones = dict(zones=z.pop("mode", "hull"), **{names[k]: v for k, v in z.items()}) if zones is not None else {}
+        if camera is not None:
+            cm = camera if isinstance(camera, CameraModel) else CameraModel(**dict(camera))
+            cm.setting()                                         # unknown or invalid fields fail here, not at the first frame
+            self._camera = dict(camera=cm)
+        else:
+            self._camera = {}
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

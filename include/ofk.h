@@ -236,6 +236,66 @@ int ofk_get_lk_seed(const ofk_ctx *ctx, int *mode, double *gain);
 int ofk_predict_points(ofk_ctx *ctx, const float *pts, const int *counts, int batch, int stride, const double *sensors, int mode,
                        double gain, float *seed_out);
 
+/* Camera model: the lens distortion undone on the device before the solve.  The solve stage reads a point as a sample of an ideal
+ * pinhole image, x = (px - cx) * scaling (sensors[19..21]); the reference's camera is a wide-angle module whose lens moves a point by
+ * tens of pixels at the border.  With ofk_set_camera on, the resident chains keep everything that lives in the image on the raw
+ * pixels (LK, the track gates, the tracks, the disc mask, the zones, the corner grid, every download of points) and hand the solve
+ * stage (plain, robust and covariance kernels, the fused stream kernels and the feasibility rule inside them) the IDEAL pixels of the
+ * same points.  Off by default; with it off every chain launches the kernels and returns the bits it always did.
+ * k in cv2's order.  OFK_CAMERA_BROWN: k1 k2 p1 p2 k3 k4 k5 k6 (cv2's pinhole model; the rational terms k4..k6 may be 0).
+ * OFK_CAMERA_FISHEYE: cv2.fisheye's equidistant model, k1..k4 in k[0..3]; k[4..7] must be 0.
+ * Per point, float64, in the order written, no contraction, ONE rounding to float32 at the end:
+ *   Undistort (image pixel p -> ideal pixel): x0 = (px - cx) / fx, y0 = (py - cy) / fy.
+ *     Brown: x = x0, y = y0, then `iters` times
+ *       r2 = x*x + y*y
+ *       icd = (1 + ((k6 r2 + k5) r2 + k4) r2) / (1 + ((k3 r2 + k2) r2 + k1) r2)
+ *       dx = 2 p1 x y + p2 (r2 + 2 x x)          [((2 p1) x) y, 2 x x = (2 x) x]
+ *       dy = p1 (r2 + 2 y y) + 2 p2 x y
+ *       x = (x0 - dx) icd, y = (y0 - dy) icd
+ *     Fisheye: td = sqrt(x0*x0 + y0*y0), t = td, then `iters` Newton steps
+ *       t2 = t*t, t4 = t2*t2, t6 = t4*t2, t8 = t4*t4
+ *       t = t - (t (1 + k1 t2 + k2 t4 + k3 t6 + k4 t8) - td) / (1 + 3 k1 t2 + 5 k2 t4 + 7 k3 t6 + 9 k4 t8)     [sums left to right]
+ *       s = tan(t) / td, s = 1 where td < 1e-8; x = x0 s, y = y0 s
+ *     out = ((float)(x fo_x + co_x), (float)(y fo_y + co_y)).
+ *   Distort (ideal pixel q -> image pixel), the closed-form forward map: x = (qx - co_x) / fo_x, y likewise.
+ *     Brown: r2 = x*x + y*y, cd = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2), dx, dy as above,
+ *       xd = x cd + dx, yd = y cd + dy.
+ *     Fisheye: r = sqrt(x*x + y*y), t = atan(r), td = t (1 + k1 t2 + k2 t4 + k3 t6 + k4 t8), s = td / r, s = 1 where r < 1e-8,
+ *       xd = x s, yd = y s.
+ *     out = ((float)(xd fx + cx), (float)(yd fy + cy)).
+ *   Fallback: a point one of whose two results is not finite or exceeds 1e6 in magnitude takes, for both coordinates, the linear map
+ *     of the input with no lens term ((float)(x0 fo_x + co_x) / (float)(x fx + cx)) - k_seed_points' rule for a seed LK could not use.
+ *     Its status is not touched.
+ * `iters` is a FIXED count (deterministic, no data-dependent exit).  cv2.undistortPoints' default of 5 leaves up to 0.47 px of
+ * round-trip error at the corners of a strong wide-angle lens (k1 = -0.28): 8 -> 0.018, 10 -> 0.0021, 15 -> 1e-5 px; the fisheye's
+ * Newton iteration is at 5e-13 px after 3.
+ * Refused with OFK_E_INVALID before any launch, a setting staying as it was: model none of the three, iters outside 1..50, a field
+ * that is not finite, fx, fy, fo_x or fo_y zero, k[4..7] != 0 for the fisheye.  ofk_set_camera also refuses fo_x != fo_y: the solve
+ * has ONE scaling, and the caller keeps sensors[19..21] = 1 / fo_x, co_x, co_y.  NULL or model OFK_CAMERA_OFF switches it off.
+ * Resident chains (ofk_pairs_run with every slice count and overlap on and off, ofk_stream_step[_jpeg], ofk_stream_step_fused[_jpeg]):
+ * behind the track step (forward LK, backward pass and gates) ONE k_camera_undistort launch per call and slice writes the ideal points
+ * of pts_prev and pts_next.  With ofk_set_lk_seed on: undistort pts_prev, k_seed_points on the ideal points as it is, k_camera_distort
+ * in place on the seeds, LK, undistort pts_next - three camera launches.
+ * ofk_undistort_points / ofk_distort_points, the stage entries on host buffers (pts, out [batch][stride][2] f32, counts [batch]):
+ * entries of `out` beyond counts[b] keep what the caller put there; they accept fo_x != fo_y; a camera with model OFK_CAMERA_OFF is
+ * refused.  They touch no resident state.
+ * ofk_camera_download: the ideal points the solve stage of the latest run / step with the setting on saw, [batch][stride][2] f32 each
+ * (either may be NULL; at most the context's max_pts points per row are written); OFK_E_INVALID before such a run. */
+#define OFK_CAMERA_OFF 0
+#define OFK_CAMERA_BROWN 1
+#define OFK_CAMERA_FISHEYE 2
+typedef struct ofk_camera {
+    int model; int iters;
+    double fx; double fy; double cx; double cy;
+    double k[8];
+    double fo_x; double fo_y; double co_x; double co_y;
+} ofk_camera;
+int ofk_set_camera(ofk_ctx *ctx, const ofk_camera *cam);
+int ofk_get_camera(const ofk_ctx *ctx, ofk_camera *cam);
+int ofk_undistort_points(ofk_ctx *ctx, const ofk_camera *cam, const float *pts, const int *counts, int batch, int stride, float *out);
+int ofk_distort_points(ofk_ctx *ctx, const ofk_camera *cam, const float *pts, const int *counts, int batch, int stride, float *out);
+int ofk_camera_download(ofk_ctx *ctx, float *prev_ideal, float *next_ideal, int stride);
+
 /* ------------------------------------------------- estimation (float64, batched over `batch` independent problems) */
 
 /* generate_test_data(x, v, omega, d, n[, t]) — node:25-29; simulation.py:7-12.
