@@ -152,6 +152,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->cov = ofk_cov{OFK_COV_OFF, 0.0, 0.0, 0.0, {0.0, 0.0, 0.0}, 0.0, 0.0, 0, 0, 0.0, 0.0};
     c->zones = ofk_zones{OFK_ZONES_OFF, 48, 3, 20, 30, OFK_ZONE_MAX};
     c->camera = ofk_camera{OFK_CAMERA_OFF, 20, 1.0, 1.0, 0.0, 0.0, {0, 0, 0, 0, 0, 0, 0, 0}, 1.0, 1.0, 0.0, 0.0};
+    c->rs = ofk_rshutter{OFK_RS_OFF, 0, 0.0, 0.5, 1.0};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -431,7 +432,7 @@ struct View {
     double *sensors, *records;
     float *pts_back, *err_back, *fb2; uint8_t *status_back; int *gate_stats;   // NULL until a run with a track gate on (gate_alloc)
     int *grid_stats;                                             // NULL until a selection with a corner grid on (grid_alloc)
-    float *pts_prev_u, *pts_next_u;                              // NULL until a run with the camera on (camera_alloc)
+    float *pts_prev_u, *pts_next_u;                              // NULL until a run with the camera or the rolling shutter on (camera_prepare)
 };
 static View view_of(ofk_ctx *c, int b0, int nb, int set)
 {
@@ -726,10 +727,46 @@ extern "C" int ofk_get_camera(const ofk_ctx *c, ofk_camera *m)
     return OFK_OK;
 }
 
-// the ideal points' resident buffers, allocated when a run first needs them; `batch`: the run's images, for ofk_camera_download
+// ------------------------------------------------------------------------------------------------ rolling-shutter setting
+static bool rs_on(const ofk_ctx *c) { return c->rs.mode != OFK_RS_OFF; }
+
+// stage: ofk_rs_correct_points' extra rule (no run to take the frame height from)
+static int check_rs(ofk_ctx *c, const ofk_rshutter *r, bool stage, const char *who)
+{
+    if (r->mode != OFK_RS_FLOW && r->mode != OFK_RS_GYRO)
+        return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_RS_FLOW nor OFK_RS_GYRO", who, r->mode);
+    if (!std::isfinite(r->readout) || !std::isfinite(r->anchor) || !std::isfinite(r->omega_gain))
+        return ofk_fail(c, OFK_E_INVALID, "%s: a field is not finite", who);
+    if (fabs(r->readout) > 1.0) return ofk_fail(c, OFK_E_INVALID, "%s: readout %g outside -1..1 frame intervals", who, r->readout);
+    if (r->anchor < 0.0 || r->anchor > 1.0) return ofk_fail(c, OFK_E_INVALID, "%s: anchor %g outside 0..1", who, r->anchor);
+    if (r->rows < 0 || r->rows > 65536) return ofk_fail(c, OFK_E_INVALID, "%s: rows %d outside 0..65536", who, r->rows);
+    if (stage && r->rows == 0) return ofk_fail(c, OFK_E_INVALID, "%s: rows 0 means the frame height of a run: the stage entry needs rows > 0", who);
+    if (r->omega_gain == 0.0) return ofk_fail(c, OFK_E_INVALID, "%s: omega_gain must not be 0", who);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_rolling_shutter(ofk_ctx *c, const ofk_rshutter *r)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!r || r->mode == OFK_RS_OFF) { c->rs.mode = OFK_RS_OFF; return OFK_OK; }
+    TRY(check_rs(c, r, false, "ofk_set_rolling_shutter"));
+    c->rs = *r;
+    return OFK_OK;
+}
+
+extern "C" int ofk_get_rolling_shutter(const ofk_ctx *c, ofk_rshutter *r)
+{
+    if (!c || !r) return OFK_E_INVALID;
+    *r = c->rs;
+    return OFK_OK;
+}
+
+// the solve stage's own points (the camera's ideal pixels, the rolling shutter's corrected ones, or both): their resident buffers,
+// allocated when a run first needs them; `batch`: the run's images, for ofk_camera_download / ofk_rs_download
 static int camera_prepare(ofk_ctx *c, int batch)
 {
-    if (!camera_on(c)) return OFK_OK;
+    if (rs_on(c)) c->rs_batch = batch;
+    if (!camera_on(c) && !rs_on(c)) return OFK_OK;
     if (!c->pts_prev_u) {                                        // one allocation, carved into the two buffers
         const size_t np = (size_t)c->max_batch * c->max_pts;
         float *base = nullptr;
@@ -738,7 +775,7 @@ static int camera_prepare(ofk_ctx *c, int batch)
         OFK_HIP(c, hipStreamSynchronize(c->stream));
         c->pts_prev_u = base; c->pts_next_u = base + np * 2;
     }
-    c->cam_batch = batch;
+    if (camera_on(c)) c->cam_batch = batch;
     return OFK_OK;
 }
 
@@ -767,7 +804,8 @@ static int gate_tracks(ofk_ctx *c, hipStream_t s, const View &v, const ofk_level
 // with ofk_set_track_gate on, the gates follow on the same stream.  With ofk_set_camera on (the view's ideal buffers exist:
 // camera_alloc) the sensors speak of the ideal image, so the predictor runs on the ideal points and its seeds are brought back into
 // the image; behind the gates the ideal points of both sets are written for the solve stage - one launch, unless the seed needed
-// the previous points' earlier.
+// the previous points' earlier.  With ofk_set_rolling_shutter on, one k_rs_correct launch follows: it reads the raw rows and the
+// ideal points (the camera's, corrected in place, or the raw points themselves) and writes what the solve stage reads.
 static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, const ofk_params *p, const double *imu_state)
 {
     const bool seeded = c->lk_seed_mode != OFK_SEED_OFF, cam = camera_on(c);
@@ -782,6 +820,12 @@ static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv,
     if (gate_on(c->gate)) TRY(gate_tracks(c, s, v, lv, p->win, p->max_level, p->max_count, p->eps, p->min_eig_thr, c->gate));
     if (cam && seeded) ofk_launch_camera(s, &c->camera, 0, v.pts_next, v.pts_next_u, nullptr, nullptr, v.counts, c->max_pts, v.nb);
     else if (cam) ofk_launch_camera(s, &c->camera, 0, v.pts_prev, v.pts_prev_u, v.pts_next, v.pts_next_u, v.counts, c->max_pts, v.nb);
+    if (rs_on(c)) {
+        ofk_rshutter r = c->rs;
+        if (r.rows == 0) r.rows = lv.h[0];                       // the frame height of the run
+        ofk_launch_rs_correct(s, &r, v.pts_prev, v.pts_next, cam ? v.pts_prev_u : nullptr, cam ? v.pts_next_u : nullptr, v.pts_prev_u, v.pts_next_u,
+                              v.counts, c->max_pts, v.sensors, imu_state, v.nb);
+    }
     return OFK_OK;
 }
 
@@ -1667,7 +1711,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
     if (c->cov.mode != OFK_COV_OFF) { TRY(cov_alloc(c)); c->cov_batch = B; }
     TRY(camera_prepare(c, B));
-    const bool cam = camera_on(c);                               // the solve stage reads the ideal points
+    const bool cam = camera_on(c) || rs_on(c);                   // the solve stage reads the ideal / corrected points
     TRY(need_streams(c, S, overlap));
     if (fork) {
         OFK_HIP(c, hipEventRecord(c->ev_fork, c->stream));
@@ -1817,6 +1861,48 @@ extern "C" int ofk_camera_download(ofk_ctx *c, float *prev_ideal, float *next_id
     const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
     if (prev_ideal) OFK_HIP(c, hipMemcpy2DAsync(prev_ideal, (size_t)stride * 8, c->pts_prev_u, mp * 8, n * 8, c->cam_batch, hipMemcpyDeviceToHost, c->stream));
     if (next_ideal) OFK_HIP(c, hipMemcpy2DAsync(next_ideal, (size_t)stride * 8, c->pts_next_u, mp * 8, n * 8, c->cam_batch, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ rolling-shutter stage entries
+// device scratch only, so resident points and settings are not touched; the outputs go up first: entries beyond counts[b] keep their contents
+extern "C" int ofk_rs_correct_points(ofk_ctx *c, const ofk_rshutter *r, const float *raw_prev, const float *raw_next, const float *ideal_prev,
+                                     const float *ideal_next, const int *counts, int batch, int stride, const double *sensors, float *out_prev,
+                                     float *out_next)
+{
+    const char *who = "ofk_rs_correct_points";
+    if (!c) return OFK_E_INVALID;
+    if (!r || !raw_prev || !raw_next || !counts || !out_prev || !out_next || batch < 1 || stride < 1 || !ideal_prev != !ideal_next)
+        return ofk_fail(c, OFK_E_INVALID, "%s: bad argument", who);
+    TRY(check_rs(c, r, true, who));
+    if (r->mode == OFK_RS_GYRO && !sensors) return ofk_fail(c, OFK_E_INVALID, "%s: OFK_RS_GYRO needs the sensors", who);
+    for (int b = 0; b < batch; ++b)
+        if (counts[b] < 0 || counts[b] > stride) return ofk_fail(c, OFK_E_INVALID, "%s: counts[%d]=%d outside 0..%d", who, b, counts[b], stride);
+    const size_t pb = (size_t)batch * stride * 8, sb = (size_t)batch * OFK_SENSOR_DOUBLES * 8;
+    Bump bp;
+    TRY(est_begin(c, 6 * pb + sb + (size_t)batch * 4, bp));
+    const float *dr0 = (const float *)bp.put(raw_prev, pb), *dr1 = (const float *)bp.put(raw_next, pb);
+    const float *di0 = (const float *)bp.put(ideal_prev, pb), *di1 = (const float *)bp.put(ideal_next, pb);      // NULL stays NULL
+    float *do0 = (float *)bp.put(out_prev, pb), *do1 = (float *)bp.put(out_next, pb);
+    const double *dsn = bp.put(sensors, sb);
+    const int *dc = (const int *)bp.put(counts, (size_t)batch * 4);
+    if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    ofk_launch_rs_correct(c->stream, r, dr0, dr1, di0, di1, do0, do1, dc, stride, dsn, nullptr, batch);
+    TRY(check_launch(c, who));
+    OFK_HIP(c, hipMemcpyAsync(out_prev, do0, pb, hipMemcpyDeviceToHost, c->stream));
+    return get(c, out_next, do1, pb);
+}
+
+extern "C" int ofk_rs_download(ofk_ctx *c, float *prev, float *next, int stride)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->rs_batch < 1 || !c->pts_prev_u) return ofk_fail(c, OFK_E_INVALID, "ofk_rs_download: no run or step with ofk_set_rolling_shutter on yet");
+    if (stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_rs_download: stride %d", stride);
+    TRY(enter(c));
+    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    if (prev) OFK_HIP(c, hipMemcpy2DAsync(prev, (size_t)stride * 8, c->pts_prev_u, mp * 8, n * 8, c->rs_batch, hipMemcpyDeviceToHost, c->stream));
+    if (next) OFK_HIP(c, hipMemcpy2DAsync(next, (size_t)stride * 8, c->pts_next_u, mp * 8, n * 8, c->rs_batch, hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
 }
@@ -2144,7 +2230,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     const bool zones_on = c->zones.mode != OFK_ZONES_OFF;
     if (zones_on) { TRY(check_zones(c, &c->zones, "ofk_stream_step")); TRY(zones_alloc(c)); }
     TRY(camera_prepare(c, B));
-    const bool cam = camera_on(c);                               // the solve stage reads the ideal points; the tracks, the zones and the
+    const bool cam = camera_on(c) || rs_on(c);                   // the solve stage reads the ideal / corrected points; the tracks, the zones and the
     const float *sp = cam ? c->pts_prev_u : c->pts_prev, *sn = cam ? c->pts_next_u : c->pts_next;   // re-detection stay in the image
     OFK_HIP(c, hipMemcpyAsync(c->sensors, sensors, (size_t)B * OFK_SENSOR_DOUBLES * 8, hipMemcpyHostToDevice, c->stream));
     bool few = false;                                            // the host knows the track counts from the previous call

@@ -102,6 +102,8 @@ struct ofk_ctx {
     ofk_camera camera;                       // ofk_set_camera: model OFK_CAMERA_OFF unless set
     float *pts_prev_u, *pts_next_u;          // [B][max_pts][2] ideal pixels of pts_prev / pts_next, what the solve stage reads with the camera on; one lazy allocation (pts_prev_u owns it)
     int cam_batch;                           // images of the latest run / step with the camera on (ofk_camera_download), 0 = none
+    ofk_rshutter rs;                         // ofk_set_rolling_shutter: mode OFK_RS_OFF unless set; with it on the solve stage reads pts_prev_u / pts_next_u too
+    int rs_batch;                            // images of the latest run / step with the rolling shutter on (ofk_rs_download), 0 = none
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -183,6 +185,10 @@ void ofk_launch_zone_mask(hipStream_t s, uint8_t *mask, size_t mask_stride, int 
 // distort 0 = image pixels -> ideal pixels, 1 = the forward map; src may be dst
 void ofk_launch_camera(hipStream_t s, const ofk_camera *cam, int distort, const float *src0, float *dst0, const float *src1, float *dst1,
                        const int *counts, int pts_stride, int batch);
+// the rolling shutter (ofk.h: ofk_set_rolling_shutter; k_rshutter.inc): both ends of every point in ONE launch; id0 / id1 NULL = the raw
+// points are the ideal ones; id may be out; rs->rows > 0; sensors may be NULL for OFK_RS_FLOW; imu_state != NULL: its omega
+void ofk_launch_rs_correct(hipStream_t s, const ofk_rshutter *rs, const float *raw0, const float *raw1, const float *id0, const float *id1,
+                           float *out0, float *out1, const int *counts, int pts_stride, const double *sensors, const double *imu_state, int batch);
 void ofk_launch_lk(hipStream_t s, const uint8_t *prev, const uint8_t *next, size_t pyr_stride, const ofk_levels &lv,
                    const float *prev_pts, const int *counts, int pts_stride, int win, int max_count, double eps,
                    double min_eig_thr, float *next_pts, uint8_t *status, float *err, int batch, int flags = 0);   // flags: OFK_LK_*

@@ -32,6 +32,7 @@ SYMBOLS = (
     "ofk_set_corner_grid", "ofk_get_corner_grid", "ofk_corner_grid_download", "ofk_select_corners_grid", "ofk_good_features_grid",
     "ofk_set_zones", "ofk_get_zones", "ofk_zones_step", "ofk_zones_reset", "ofk_zones_download",
     "ofk_set_camera", "ofk_get_camera", "ofk_undistort_points", "ofk_distort_points", "ofk_camera_download",
+    "ofk_set_rolling_shutter", "ofk_get_rolling_shutter", "ofk_rs_correct_points", "ofk_rs_download",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
     "ofk_stream_begin_jpeg", "ofk_stream_step_jpeg",
@@ -74,6 +75,9 @@ ZONE_MAX, ZONE_VERTS, ZONE_INTS, ZONE_FLOATS, ZONE_STATS = 16, 32, 67, 4, 8    #
 CAMERA_OFF, CAMERA_BROWN, CAMERA_FISHEYE = 0, 1, 2       # ofk_set_camera / ofk_undistort_points / ofk_distort_points
 CAMERA_MODELS = {"off": CAMERA_OFF, "brown": CAMERA_BROWN, "fisheye": CAMERA_FISHEYE}
 CAMERA_DEFAULT_ITERS = {CAMERA_BROWN: 20, CAMERA_FISHEYE: 10}
+RS_OFF, RS_FLOW, RS_GYRO = 0, 1, 2                       # ofk_set_rolling_shutter / ofk_rs_correct_points
+RS_MODES = {"off": RS_OFF, "flow": RS_FLOW, "gyro": RS_GYRO}
+RS_MAX_ROWS = 65536
 FLOW_LK, FLOW_ROTATIONAL = 0, 1
 KEEP_STATUS, KEEP_LEGACY = 0, 1
 CONTROL_SENSORS, CONTROL_IMU = 0, 1
@@ -242,6 +246,41 @@ def camera_setting(model="brown", fx=1.0, fy=None, cx=0.0, cy=0.0, k=(), iters=N
     return Camera(model, iters, fx, fy, cx, cy, (C.c_double * 8)(*kk), fo_x, fo_y, co_x, co_y)
 
 
+class RShutter(C.Structure):
+    """ofk_rshutter (include/ofk.h): the rolling shutter whose per-row capture time is undone in front of the solve stage."""
+    _fields_ = [("mode", C.c_int), ("rows", C.c_int), ("readout", C.c_double), ("anchor", C.c_double), ("omega_gain", C.c_double)]
+
+
+def rshutter_setting(mode="gyro", readout=0.0, anchor=0.5, rows=0, omega_gain=1.0):
+    """An RShutter structure from names: mode "off" / "flow" (constant image velocity from the measured flow, needs no sensor) /
+    "gyro" (the rotation over the row time from the sensors' omega, exactly; the rest of the flow held constant), or RS_*;
+    readout = the time from the first to the last row in frame intervals (negative: read from the bottom row up, |readout| <= 1);
+    anchor = the row fraction in [0, 1] whose exposure the frame's time stamp belongs to; rows = the raw frame's row count (0 or
+    None: the frame height of the run; the stage entry needs it > 0); omega_gain turns the sensors' omega into radians per frame
+    interval (not 0)."""
+    if isinstance(mode, str):
+        if mode not in RS_MODES:
+            raise ValueError(f"rolling-shutter mode {mode!r} is none of {sorted(RS_MODES)}")
+        mode = RS_MODES[mode]
+    mode = int(mode)
+    if mode not in RS_MODES.values():
+        raise ValueError(f"rolling-shutter mode {mode} is none of RS_OFF, RS_FLOW, RS_GYRO")
+    rows = 0 if rows is None else int(rows)
+    readout = float(readout); anchor = float(anchor); omega_gain = float(omega_gain)
+    if mode != RS_OFF:
+        if not np.all(np.isfinite([readout, anchor, omega_gain])):
+            raise ValueError("rolling shutter: a field is not finite")
+        if abs(readout) > 1.0:
+            raise ValueError(f"rolling-shutter readout {readout} outside -1..1 frame intervals")
+        if not 0.0 <= anchor <= 1.0:
+            raise ValueError(f"rolling-shutter anchor {anchor} outside 0..1")
+        if not 0 <= rows <= RS_MAX_ROWS:
+            raise ValueError(f"rolling-shutter rows {rows} outside 0..{RS_MAX_ROWS}")
+        if omega_gain == 0.0:
+            raise ValueError("rolling-shutter omega_gain must not be 0")
+    return RShutter(mode, rows, readout, anchor, omega_gain)
+
+
 class Fusion(C.Structure):
     """ofk_fusion (include/ofk.h): what ofk_stream_step_fused does between LK and the next frame."""
     _fields_ = [("use_imu", C.c_int), ("flow", C.c_int), ("keep", C.c_int), ("filter", C.c_int), ("control", C.c_int),
@@ -331,6 +370,9 @@ def load_library():
         L.ofk_undistort_points.argtypes = [vp, C.POINTER(Camera), vp, vp, i, i, vp]
         L.ofk_distort_points.argtypes = [vp, C.POINTER(Camera), vp, vp, i, i, vp]
         L.ofk_camera_download.argtypes = [vp, vp, vp, i]
+        L.ofk_set_rolling_shutter.argtypes = [vp, C.POINTER(RShutter)]; L.ofk_get_rolling_shutter.argtypes = [vp, C.POINTER(RShutter)]
+        L.ofk_rs_correct_points.argtypes = [vp, C.POINTER(RShutter), vp, vp, vp, vp, vp, i, i, vp, vp, vp]
+        L.ofk_rs_download.argtypes = [vp, vp, vp, i]
         L.ofk_lk_pyr_fb.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, i, vp, vp, vp, C.POINTER(TrackGate), vp, vp, vp]
         L.ofk_imu_propagate.argtypes = [vp, vp, vp, i]
         L.ofk_post_solve.argtypes = [vp, vp, vp, vp, vp, i, vp]
@@ -763,6 +805,56 @@ class Context:
         a = np.zeros((self.max_batch, self.max_pts, 2), np.float32); b = np.zeros_like(a)
         with self._lock:
             self._ck(self._L.ofk_camera_download(self._h, _p(a), _p(b), self.max_pts))
+        return a[:batch].copy(), b[:batch].copy()
+
+    def set_rolling_shutter(self, rshutter=None, **settings):
+        """ofk_set_rolling_shutter: an RShutter (or rshutter_setting's keywords); None or mode "off" switches it off.  Every later
+        pairs_run and stream step hands its solve stage the positions a global shutter would have seen at the two time stamps;
+        everything in the image keeps the raw pixels."""
+        m = rshutter if rshutter is not None or not settings else rshutter_setting(**settings)
+        with self._lock:
+            self._ck(self._L.ofk_set_rolling_shutter(self._h, C.byref(m) if m is not None else None))
+
+    def get_rolling_shutter(self):
+        m = RShutter()
+        self._ck(self._L.ofk_get_rolling_shutter(self._h, C.byref(m)))
+        return m
+
+    def rs_correct_points(self, rshutter, raw_prev, raw_next, counts=None, sensors=None, ideal_prev=None, ideal_next=None, out=None):
+        """ofk_rs_correct_points: raw_prev, raw_next [B,S,2] (or [S,2]) f32 image pixels of the tracked points (their rows give the
+        capture times), ideal_prev / ideal_next the ideal pixels of the same points (both None: the raw ones) -> (prev, next) as a
+        global shutter would have seen them at the two time stamps.  rshutter: an RShutter with rows > 0; sensors [B,28] (needed in
+        gyro mode); counts None = every point; entries beyond counts[b] keep what out = (prev, next) holds (zeros without it)."""
+        rp, rn = _arr(raw_prev, np.float32), _arr(raw_next, np.float32)
+        single = rp.ndim == 2
+        if single:
+            rp, rn = rp[None], rn[None]
+        if rp.ndim != 3 or rp.shape[2] != 2 or rn.shape != rp.shape:
+            raise ValueError(f"rs_correct_points: points {rp.shape} / {rn.shape} are not two [B, S, 2] arrays")
+        B, S = rp.shape[:2]
+        if (ideal_prev is None) != (ideal_next is None):
+            raise ValueError("rs_correct_points: ideal_prev and ideal_next come together")
+        ip = None if ideal_prev is None else _arr(ideal_prev, np.float32).reshape(rp.shape)
+        inx = None if ideal_next is None else _arr(ideal_next, np.float32).reshape(rp.shape)
+        counts = _arr(S if counts is None else counts, np.int32, (B,))
+        sn = None if sensors is None else _arr(sensors, np.float64, (B, SENSOR_DOUBLES))
+        if out is None:
+            o0 = np.zeros((B, S, 2), np.float32); o1 = np.zeros((B, S, 2), np.float32)
+        else:
+            o0 = np.array(out[0], np.float32).reshape(B, S, 2); o1 = np.array(out[1], np.float32).reshape(B, S, 2)
+        if S > 0:
+            with self._lock:
+                self._ck(self._L.ofk_rs_correct_points(self._h, C.byref(rshutter), _p(rp), _p(rn), _p(ip), _p(inx), _p(counts), B, S, _p(sn), _p(o0), _p(o1)))
+        return (o0[0], o1[0]) if single else (o0, o1)
+
+    def rs_download(self, batch):
+        """ofk_rs_download: (prev, next) [batch,max_pts,2] f32, the points the solve stage of the latest run or step with the rolling
+        shutter on saw.  The library writes that run's rows, so the buffers have max_batch of them."""
+        if not 0 <= int(batch) <= self.max_batch:
+            raise ValueError(f"rs_download: batch {batch} outside 0..{self.max_batch}")
+        a = np.zeros((self.max_batch, self.max_pts, 2), np.float32); b = np.zeros_like(a)
+        with self._lock:
+            self._ck(self._L.ofk_rs_download(self._h, _p(a), _p(b), self.max_pts))
         return a[:batch].copy(), b[:batch].copy()
 
     def track_gate_download(self, batch, points=True):

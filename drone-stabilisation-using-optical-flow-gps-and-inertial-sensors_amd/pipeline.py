@@ -43,6 +43,23 @@ class CameraModel:
 
 
 @dataclass
+class RollingShutter:
+    """The rolling shutter of a pipeline (ofk.h: ofk_set_rolling_shutter): readout = the time from the first to the last row in frame
+    intervals (negative: bottom row first); mode "gyro" (rotation over the row time from the sensors' omega, the rest of the flow
+    held constant) or "flow" (constant image velocity, no sensor needed); anchor = the row fraction the frame's time stamp belongs
+    to; rows None = the frame height of the run; omega_gain turns the sensors' omega into radians per frame interval."""
+    readout: float
+    mode: str = "gyro"
+    anchor: float = 0.5
+    rows: int = None
+    omega_gain: float = 1.0
+
+    def setting(self):
+        """The ofk.RShutter structure (range-checked)."""
+        return ofk.rshutter_setting(self.mode, self.readout, self.anchor, self.rows, self.omega_gain)
+
+
+@dataclass
 class PipelineConfig:
     max_corners: int = 500
     quality: float = 0.01
@@ -107,6 +124,9 @@ class PipelineConfig:
     # camera model (ofk.h: ofk_set_camera): None, or a CameraModel whose lens distortion is undone on the device in front of the solve
     # stage; the sensors' scaling, cx, cy are then camera.sensor_slots()
     camera: object = None
+    # rolling shutter (ofk.h: ofk_set_rolling_shutter): None, or a RollingShutter whose per-row capture time is undone on the device
+    # in front of the solve stage
+    rolling_shutter: object = None
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -163,6 +183,13 @@ class PipelineConfig:
             return None
         m = self.camera.setting() if hasattr(self.camera, "setting") else self.camera
         return None if m.model == ofk.CAMERA_OFF else m
+
+    def rolling_shutter_setting(self):
+        """The ofk.RShutter structure of this configuration, None when no rolling shutter is set."""
+        if self.rolling_shutter is None:
+            return None
+        m = self.rolling_shutter.setting() if hasattr(self.rolling_shutter, "setting") else self.rolling_shutter
+        return None if m.mode == ofk.RS_OFF else m
 
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
@@ -299,6 +326,8 @@ class FlowStream:
             self.ctx.set_zones(self.cfg.zones_setting())
         if self.cfg.camera_setting() is not None:
             self.ctx.set_camera(self.cfg.camera_setting())
+        if self.cfg.rolling_shutter_setting() is not None:
+            self.ctx.set_rolling_shutter(self.cfg.rolling_shutter_setting())
         self.fusion = fusion
         if fusion is not None:                                  # the per-stream filter state lives on the device from here on
             self._fusion = fusion.to_struct()
@@ -337,8 +366,8 @@ class FlowStream:
         return self.ctx.zones_download(self.batch)
 
     def ideal_points(self):
-        """(prev, next) [batch, max_pts, 2] f32: the ideal pixels the solve stage of the latest step saw (camera model on)."""
-        return self.ctx.camera_download(self.batch)
+        """(prev, next) [batch, max_pts, 2] f32: the points the solve stage of the latest step saw (camera model or rolling shutter on)."""
+        return self.ctx.rs_download(self.batch) if self.ctx.get_rolling_shutter().mode != ofk.RS_OFF else self.ctx.camera_download(self.batch)
 
     def begin(self, first_bgr):
         return self.ctx.stream_begin(first_bgr, self._params)
@@ -386,6 +415,8 @@ class FlowPipeline:
             self.ctx.set_cov(self.cfg.cov_setting())
         if self.cfg.camera_setting() is not None:
             self.ctx.set_camera(self.cfg.camera_setting())
+        if self.cfg.rolling_shutter_setting() is not None:
+            self.ctx.set_rolling_shutter(self.cfg.rolling_shutter_setting())
         if streams > 1:
             self.ctx.set_streams(streams)
 
@@ -438,8 +469,8 @@ class FlowPipeline:
         return self.ctx.cov_download(self.batch)
 
     def ideal_points(self):
-        """(prev, next) [batch, max_pts, 2] f32: the ideal pixels the solve stage of the latest run saw (camera model on)."""
-        return self.ctx.camera_download(self.batch)
+        """(prev, next) [batch, max_pts, 2] f32: the points the solve stage of the latest run saw (camera model or rolling shutter on)."""
+        return self.ctx.rs_download(self.batch) if self.ctx.get_rolling_shutter().mode != ofk.RS_OFF else self.ctx.camera_download(self.batch)
 
     def run_async(self):
         self.ctx.pairs_run(self._params)

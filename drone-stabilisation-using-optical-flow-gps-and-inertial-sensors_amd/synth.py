@@ -96,12 +96,52 @@ def _camera_view(h, w, camera, margin):
     return scaling, cx, cy, xx, yy, max(int(margin), int(np.ceil(over)) + 16)
 
 
+def _row_times(h, rolling_shutter):
+    """The capture time of every raw row against its frame's time stamp, in frame intervals: readout * (y / rows - anchor)."""
+    m = rolling_shutter.setting()
+    return m.readout * (np.arange(h, dtype=np.float64) / (m.rows or h) - m.anchor)
+
+
+def _row_sources(xx, yy, M, margin):
+    """Texture coordinates of the ideal pixels (xx, yy) [h,w] where row y was exposed under its own homography M[y] (texture -> image)."""
+    Hi = np.linalg.inv(M)[:, None]                               # [h,1,3,3]
+    den = Hi[..., 2, 0] * xx + Hi[..., 2, 1] * yy + Hi[..., 2, 2]
+    return (Hi[..., 0, 0] * xx + Hi[..., 0, 1] * yy + Hi[..., 0, 2]) / den + margin, (Hi[..., 1, 0] * xx + Hi[..., 1, 1] * yy + Hi[..., 1, 2]) / den + margin
+
+
+def _colour(T, T2, ax, ay):
+    base, tint = _bilinear(T, ax, ay), _bilinear(T2, ax, ay)
+    return np.stack([np.clip(np.rint(base + g * (tint - 127.5)), 0, 255).astype(np.uint8) for g in (0.10, -0.06, 0.08)], -1)
+
+
 def render_pair(h, w, seed, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.003), d=1.0, n=(0, 0, 1), scaling=None,
-                margin=48, camera=None):
+                margin=48, camera=None, rolling_shutter=None):
     """Returns dict(prev, next: [h,w,3] uint8 BGR; H: 3x3 pixel homography prev->next; scaling, cx, cy).
     camera (a pipeline.CameraModel, default None): the frames are what that camera sees - every raw pixel is undistorted to the ideal
     pixel it looks at, sent through the homography and sampled bilinearly (the previous frame too, at the ideal pixel itself);
-    scaling, cx, cy are then the ideal pinhole's (camera.sensor_slots()) and H lives in ideal pixels."""
+    scaling, cx, cy are then the ideal pinhole's (camera.sensor_slots()) and H lives in ideal pixels.
+    rolling_shutter (a pipeline.RollingShutter, default None): raw row y of frame k (0 = prev, 1 = next) is exposed at the time
+    t = k + readout * (y / h - anchor) and rendered through the pair's linearised homography at that time,
+    K (I + t (W + v n' / d)) K^-1 - pixel_homography's own form with t v, t omega; H stays the global shutter's.  Works behind a
+    camera as well (the rows are the raw image's)."""
+    if rolling_shutter is not None:
+        if camera is not None:
+            scaling, cx, cy, xx, yy, margin = _camera_view(h, w, camera, margin)
+        else:
+            scaling = scaling or 1.0 / max(h, w)
+            cx, cy = w / 2.0, h / 2.0
+            yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+        T = make_texture(h + 2 * margin, w + 2 * margin, seed)
+        T2 = make_texture(h + 2 * margin, w + 2 * margin, seed + 7919, sigma=3.0)
+        H = pixel_homography(v, omega, d, n, scaling, cx, cy)
+        G = H - np.eye(3)                                        # K (W + v n' / d) K^-1
+        tau = _row_times(h, rolling_shutter)
+        out = {name: _colour(T, T2, *_row_sources(xx, yy, np.eye(3) + (k + tau)[:, None, None] * G, margin)) for k, name in enumerate(("prev", "next"))}
+        info = dict(prev=out["prev"], next=out["next"], H=H, scaling=scaling, cx=cx, cy=cy, v=np.asarray(v, np.float64),
+                    omega=np.asarray(omega, np.float64), d=float(d), n=np.asarray(n, np.float64), rolling_shutter=rolling_shutter)
+        if camera is not None:
+            info["camera"] = camera
+        return info
     if camera is not None:
         scaling, cx, cy, xx, yy, margin = _camera_view(h, w, camera, margin)
         T = make_texture(h + 2 * margin, w + 2 * margin, seed)
@@ -156,9 +196,11 @@ def warp_frame(bgr, H):
 
 
 def render_sequence(h, w, seed, n_frames, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.003), d=1.0, n=(0, 0, 1),
-                    scaling=None, margin=96, camera=None):
+                    scaling=None, margin=96, camera=None, rolling_shutter=None):
     """`n_frames` BGR frames of one stream under constant per-frame motion: frame k shows the texture through H^k.
-    Returns (frames [n,h,w,3] uint8, info dict as render_pair).  camera: as in render_pair."""
+    Returns (frames [n,h,w,3] uint8, info dict as render_pair).  camera: as in render_pair.  rolling_shutter: as in render_pair, with
+    row y of frame k seen through (I + tau G) H^k, tau = readout * (y / h - anchor), G = H - I: the linearised motion over the row
+    time behind the k whole steps (I + (k + tau) G itself would drift from H^k with k)."""
     if camera is not None:
         scaling, cx, cy, xx, yy, margin = _camera_view(h, w, camera, margin)
     else:
@@ -170,11 +212,15 @@ def render_sequence(h, w, seed, n_frames, v=(0.003, -0.002, 0.001), omega=(0.002
     H = pixel_homography(v, omega, d, n, scaling, cx, cy)
     frames = np.empty((n_frames, h, w, 3), np.uint8)
     Hk = np.eye(3)
+    tau = None if rolling_shutter is None else _row_times(h, rolling_shutter)
     for k in range(n_frames):
-        Hi = np.linalg.inv(Hk)
-        den = Hi[2, 0] * xx + Hi[2, 1] * yy + Hi[2, 2]
-        sx = (Hi[0, 0] * xx + Hi[0, 1] * yy + Hi[0, 2]) / den + margin
-        sy = (Hi[1, 0] * xx + Hi[1, 1] * yy + Hi[1, 2]) / den + margin
+        if tau is not None:
+            sx, sy = _row_sources(xx, yy, (np.eye(3) + tau[:, None, None] * (H - np.eye(3))) @ Hk, margin)
+        else:
+            Hi = np.linalg.inv(Hk)
+            den = Hi[2, 0] * xx + Hi[2, 1] * yy + Hi[2, 2]
+            sx = (Hi[0, 0] * xx + Hi[0, 1] * yy + Hi[0, 2]) / den + margin
+            sy = (Hi[1, 0] * xx + Hi[1, 1] * yy + Hi[1, 2]) / den + margin
         base, tint = _bilinear(T, sx, sy), _bilinear(T2, sx, sy)
         for ch, g in enumerate((0.10, -0.06, 0.08)):
             frames[k, ..., ch] = np.clip(np.rint(base + g * (tint - 127.5)), 0, 255).astype(np.uint8)

@@ -24,12 +24,12 @@ import numpy as np
 
 try:
     from . import ofk, cv2_hip as cv2, of_library as of
-    from .pipeline import CameraModel, FlowStream, FusionConfig, PipelineConfig
+    from .pipeline import CameraModel, FlowStream, FusionConfig, PipelineConfig, RollingShutter
 except ImportError:
     import ofk
     import cv2_hip as cv2
     import of_library as of
-    from pipeline import CameraModel, FlowStream, FusionConfig, PipelineConfig
+    from pipeline import CameraModel, FlowStream, FusionConfig, PipelineConfig, RollingShutter
 
 try:                                    # ROS is optional (absent in this image)
     import rospy
@@ -108,6 +108,7 @@ class optical_fusion:
     _cov = {}                                                    # PipelineConfig's covariance fields (cov, sigma_*, ...); empty: no covariance
     _zones = {}                                                  # PipelineConfig's zones / zone_* fields; empty: no exclusion zones
     _camera = {}                                                 # PipelineConfig's camera field; empty: the points are taken as ideal pinhole samples
+    _rolling_shutter = {}                                        # PipelineConfig's rolling_shutter field; empty: every row is taken as exposed at the time stamp
     feature_params = dict(qualityLevel=0.7, minDistance=10, blockSize=12)
     lk_params = dict(winSize=(15, 15), maxLevel=3, criteria=(cv2.TERM_CRITERIA_EPS | cv2.TERM_CRITERIA_COUNT, 20, 0.03))
     scaling = 0.01
@@ -262,7 +263,7 @@ class optical_fusion:
                                  min_distance=float(self.feature_params["minDistance"]), block_size=int(self.feature_params["blockSize"]),
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
-                                 **self._cov, **self._zones, **self._camera)
+                                 **self._cov, **self._zones, **self._camera, **self._rolling_shutter)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -358,7 +359,8 @@ class optical_fusion:
             Rm = np.asarray(self.rotation, np.float64).reshape(3, 3)
             self.vel_err = np.sqrt(np.maximum(np.diag(Rm @ ofk.cov_matrix(cv[6:12]) @ Rm.T), 0.0))
 
-    def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None):
+    def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
+                 rolling_shutter=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -376,7 +378,11 @@ class optical_fusion:
         camera: None (every point is a sample of an ideal pinhole image, centred and scaled with the node's constants) or a
         pipeline.CameraModel (or a dict of its fields), e.g. dict(fx=1000, fy=1010, cx=652.3, cy=470.1, k=(-0.28, 0.09, 0, 0)): the
         restored pipeline then undoes the lens distortion on the device in front of the solve (ofk.h: ofk_set_camera) and takes
-        scaling and centre from the model (1 / fo, co_x, co_y) in the place of self.scaling and the node's (160, 120)."""
+        scaling and centre from the model (1 / fo, co_x, co_y) in the place of self.scaling and the node's (160, 120).
+        rolling_shutter: None (every row is taken as exposed at the frame's time stamp) or a pipeline.RollingShutter (or a dict of its
+        fields), e.g. dict(readout=0.9, mode="gyro", anchor=0.5): the restored pipeline then undoes the per-row capture time on the
+        device in front of the solve (ofk.h: ofk_set_rolling_shutter); the node's omega is per frame interval as it stands only if
+        omega_gain says so."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -404,6 +410,12 @@ class optical_fusion:
             self._camera = dict(camera=cm)
         else:
             self._camera = {}
+        if rolling_shutter is not None:
+            rs = rolling_shutter if isinstance(rolling_shutter, RollingShutter) else RollingShutter(**dict(rolling_shutter))
+            rs.setting()                                         # unknown or invalid fields fail here, not at the first frame
+            self._rolling_shutter = dict(rolling_shutter=rs)
+        else:
+            self._rolling_shutter = {}
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

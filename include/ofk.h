@@ -296,6 +296,75 @@ int ofk_undistort_points(ofk_ctx *ctx, const ofk_camera *cam, const float *pts, 
 int ofk_distort_points(ofk_ctx *ctx, const ofk_camera *cam, const float *pts, const int *counts, int batch, int stride, float *out);
 int ofk_camera_download(ofk_ctx *ctx, float *prev_ideal, float *next_ideal, int stride);
 
+/* Rolling shutter: the per-row capture time undone on the device before the solve.  The reference's camera exposes its rows one after
+ * the other: a point in row y of a frame of H rows is seen readout * (y / H - anchor) frame intervals away from the frame's time
+ * stamp, so the measured flow of a point that changes row spans 1 + readout * dy / H frame intervals, and neither end sits where the
+ * sensor record (omega, d, n at the time stamp) says the camera was.  With ofk_set_rolling_shutter on, the resident chains hand the
+ * solve stage (plain, robust and covariance kernels, the fused stream kernels and the feasibility rule inside them) the positions a
+ * global shutter would have seen at the two time stamps; everything that lives in the image (LK and its seeds, the track gates, the
+ * tracks, the disc mask, the zones, the corner grid, every download of points) keeps the raw pixels.  Off by default; with it off
+ * every chain launches the kernels and returns the bits it always did.
+ *   readout: the time from the first to the last row in frame intervals; negative = read from the bottom row up.
+ *   rows:    H, the RAW frame's row count; 0 = the frame height of the run (resident chains only; the stage entry needs rows > 0).
+ *   anchor:  the row fraction in [0, 1] whose exposure the frame's time stamp, and so the sensor record, belongs to.
+ *   omega_gain: turns the sensors' omega into radians per frame interval, as `gain` does for ofk_set_lk_seed.
+ * Per point i < counts[b], float64, in the order written, no contraction, ONE rounding to float32 at the end.  The rows are the raw
+ * image's (r0, r1 = the point in the previous / next frame); positions and flow are the ideal ones (q0, q1 = the camera's ideal pixels
+ * of r0, r1, or r0, r1 themselves with no camera):
+ *   t0 = readout * (r0.y / H - anchor), t1 = readout * (r1.y / H - anchor), span = 1 + (t1 - t0)
+ *   OFK_RS_FLOW (constant image velocity; needs no sensor):
+ *     f = (q1 - q0) / span;  out_prev = (float)(q0 - t0 f), out_next = (float)(q1 - t1 f)
+ *   OFK_RS_GYRO (the rotation over the row time from omega, exactly; the rest of the flow held constant): scaling, cx, cy =
+ *   sensors[19..21]; om = omega_gain * omega, omega = sensors[4..6] or, under ofk_fusion.use_imu, the resident IMU state's (what
+ *   k_seed_points takes):
+ *     x0 = (q0 - c) * scaling, x1 = (q1 - c) * scaling                                           [per coordinate]
+ *     rot(x, y, t), the point (x, y) as the rotation alone had it t frame intervals earlier:
+ *       p = (-t) om;  th2 = p0 p0 + p1 p1 + p2 p2
+ *       A = sin(th) / th, B = (1 - cos(th)) / th2 with th = sqrt(th2);  A = 1, B = 0.5 where th2 < 1e-16
+ *       c = p x (x, y, 1):  c0 = p1 - p2 y, c1 = p2 x - p0, c2 = p0 y - p1 x
+ *       d = p x c:          d0 = p1 c2 - p2 c1, d1 = p2 c0 - p0 c2, d2 = p0 c1 - p1 c0
+ *       X = x + A c0 + B d0, Y = y + A c1 + B d1, Z = 1 + A c2 + B d2                            [Rodrigues; sums left to right]
+ *       rot = (X / Z, Y / Z)
+ *     hs = span / 2;  r = rot(x0, -hs), m = rot(x1, hs): both observations carried to the middle of the span by the rotation alone
+ *     ft = ((m.x - r.x) / span, (m.y - r.y) / span): the rest of the flow, held constant
+ *     for each end k: e = rot(xk, tk)
+ *       out = ((float)((e.x - tk ft.x) / scaling + cx), (float)((e.y - tk ft.y) / scaling + cy))
+ *     The rest of the flow is taken against the EXACT rotation, symmetrically about the middle of the span, not against the seed
+ *     formula's rotational part at the mid point ((x1 - x0) / span - frot((x0 + x1) / 2)): that is a mid-point rule, whose error of
+ *     the third order in omega leaves a point under pure rotation 0.1 px from its place at a yaw of 0.15 rad per frame.  With the
+ *     exact rotation such a point comes back to 1e-12, and on combined motions the two forms agree (tests/rs_reference.py).
+ *     The sign is the project's: the seed's field is dP/dt = omega x P.
+ *   Fallback: a point whose span is not finite or < 0.5, or one of whose four results is not finite or exceeds 1e6 in magnitude, or
+ *     (GYRO) whose scaling is 0, takes q0 and q1 unchanged; its status is not touched - k_seed_points' and the camera's rule.  Points
+ *     with status 0 carry garbage in `next` and come out finite or as they went in.
+ * What the model assumes: the image velocity of a point is constant between its two exposures (FLOW: all of it; GYRO: what is left
+ * of it once the rotation is taken out), and omega is constant over a frame.  The covariance (ofk_set_cov) takes the corrected
+ * points as its inputs and does not propagate an error of readout.  Out of scope: exposure blur, per-row IMU samples, a readout
+ * estimated from data, vibration within a frame.  A seeded LK predicts its seeds exactly as with the setting off: a seed is a start
+ * position, and the row time's effect on it is of second order.
+ * Refused with OFK_E_INVALID before any launch, a setting staying as it was: mode none of the three, a field that is not finite,
+ * |readout| > 1, anchor outside [0, 1], rows < 0 or > 65536, omega_gain == 0; in the stage entry also rows == 0 and OFK_RS_GYRO with
+ * sensors == NULL.  NULL or mode OFK_RS_OFF switches the setting off.
+ * Resident chains (ofk_pairs_run with every slice count and overlap on and off, ofk_stream_step[_jpeg], ofk_stream_step_fused[_jpeg],
+ * append and replace mode): behind the track step, and behind k_camera_undistort when a camera is set, ONE k_rs_correct launch per
+ * call and slice writes the corrected ideal points of both sets into the buffers the solve stage reads.
+ * ofk_rs_correct_points, the stage entry on host buffers (points [batch][stride][2] f32, counts [batch], sensors [batch][28] f64,
+ * NULL allowed for FLOW): ideal_prev and ideal_next both NULL = the raw points; entries of out_prev / out_next beyond counts[b] keep
+ * what the caller put there.  It touches no resident state.
+ * ofk_rs_download: the points the solve stage of the latest run / step with the setting on saw, [batch][stride][2] f32 each (either
+ * may be NULL; at most the context's max_pts points per row are written); OFK_E_INVALID before such a run.  With ofk_set_camera on as
+ * well, ofk_camera_download returns the same arrays: both are "what the solve stage saw". */
+#define OFK_RS_OFF 0
+#define OFK_RS_FLOW 1    /* constant image velocity from the measured flow; needs no sensor */
+#define OFK_RS_GYRO 2    /* rotation over the row time from omega (exact), the rest of the flow held constant */
+typedef struct ofk_rshutter { int mode; int rows; double readout; double anchor; double omega_gain; } ofk_rshutter;
+int ofk_set_rolling_shutter(ofk_ctx *ctx, const ofk_rshutter *rs);
+int ofk_get_rolling_shutter(const ofk_ctx *ctx, ofk_rshutter *rs);
+int ofk_rs_correct_points(ofk_ctx *ctx, const ofk_rshutter *rs, const float *raw_prev, const float *raw_next, const float *ideal_prev,
+                          const float *ideal_next, const int *counts, int batch, int stride, const double *sensors, float *out_prev,
+                          float *out_next);
+int ofk_rs_download(ofk_ctx *ctx, float *prev, float *next, int stride);
+
 /* ------------------------------------------------- estimation (float64, batched over `batch` independent problems) */
 
 /* generate_test_data(x, v, omega, d, n[, t]) — node:25-29; simulation.py:7-12.
