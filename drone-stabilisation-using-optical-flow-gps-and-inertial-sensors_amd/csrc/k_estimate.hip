@@ -114,11 +114,17 @@ __device__ void jacobi3(double A[3][3], double lam[3], double V[3][3])
 }
 
 // Solve from accumulated sums.  out8 = v[3], (residual filled later), rank, s[3].  Returns rank.
-__device__ int solve_from_acc(const Acc &a, double *v, double *s3)
+// fin: whether M, g and the eigenvalues are all finite; where they are not the problem is not solved (ofk.h, "non-finite sums"):
+// rank 0, v = s = 0, and the caller leaves the residual at 0.  Finite sums take the path they always took.
+__device__ int solve_from_acc(const Acc &a, double *v, double *s3, bool &fin)
 {
     double A[3][3] = {{a.m00, a.m01, a.m02}, {a.m01, a.m11, a.m12}, {a.m02, a.m12, a.m22}};
     double lam[3], V[3][3];
     jacobi3(A, lam, V);
+    // x - x is 0 for a finite x and NaN otherwise, and a NaN in a sum stays: one compare covers the twelve values
+    fin = (a.m00 - a.m00) + (a.m01 - a.m01) + (a.m02 - a.m02) + (a.m11 - a.m11) + (a.m12 - a.m12) + (a.m22 - a.m22) + (a.g0 - a.g0) +
+          (a.g1 - a.g1) + (a.g2 - a.g2) + (lam[0] - lam[0]) + (lam[1] - lam[1]) + (lam[2] - lam[2]) == 0.0;
+    if (!fin) { v[0] = v[1] = v[2] = 0.0; s3[0] = s3[1] = s3[2] = 0.0; return 0; }
     const double rows = 3.0 * a.cnt;
     // lstsq's cut is s_k <= eps*max(M,N)*s_max; on the squared spectrum the resolvable floor is eps*lambda_max,
     // so singular-value ratios below sqrt(eps*rows) count as zero ("rank").
@@ -186,7 +192,7 @@ __device__ __forceinline__ void write_record(double *o, const double *v, double 
     o[8] = vu[0]; o[9] = vu[1]; o[10] = vu[2]; o[11] = cnt; o[12] = (double)n; o[13] = tracked;
 }
 
-struct Solved { double v[3], rank, s3[3], cnt; };
+struct Solved { double v[3], rank, s3[3], cnt; bool fin; };    // fin: solve_from_acc's (true where nothing was solved)
 
 // The least squares of one 256-thread block: point(i, a) adds point i = tid, tid + 256, ... to a (or skips it), the sums meet
 // in acc_block_sum, thread 0 solves when more than min_cnt points entered (else v = s = 0, rank 0), every thread gets the result.
@@ -194,17 +200,19 @@ struct Solved { double v[3], rank, s3[3], cnt; };
 template <class Point>
 __device__ __forceinline__ Solved block_lstsq(int n, double min_cnt, Point point)
 {
-    __shared__ double s_v[7];
+    __shared__ double s_v[8];
     Acc a; acc_zero(a);
     for (int i = threadIdx.x; i < n; i += 256) point(i, a);
     acc_block_sum(a);
     if (threadIdx.x == 0) {
         double v[3] = {0, 0, 0}, s3[3] = {0, 0, 0};
-        const int rank = a.cnt > min_cnt ? solve_from_acc(a, v, s3) : 0;
+        bool fin = true;
+        const int rank = a.cnt > min_cnt ? solve_from_acc(a, v, s3, fin) : 0;
         s_v[0] = v[0]; s_v[1] = v[1]; s_v[2] = v[2]; s_v[3] = (double)rank; s_v[4] = s3[0]; s_v[5] = s3[1]; s_v[6] = s3[2];
+        s_v[7] = fin ? 1.0 : 0.0;
     }
     __syncthreads();
-    return Solved{{s_v[0], s_v[1], s_v[2]}, s_v[3], {s_v[4], s_v[5], s_v[6]}, a.cnt};
+    return Solved{{s_v[0], s_v[1], s_v[2]}, s_v[3], {s_v[4], s_v[5], s_v[6]}, a.cnt, s_v[7] != 0.0};
 }
 
 // The same walk over the points for a second pass: point(i, r) adds point i's term to r; the block's sum in every thread.
@@ -241,13 +249,13 @@ __global__ __launch_bounds__(256) void k_solve(int variant, const double *__rest
         double q0, q1, q2, sA, sB;
         if (terms(i, q0, q1, q2, sA, sB)) acc_point(a, xb[2 * i], xb[2 * i + 1], q0, q1, q2, sA, sB);
     });
-    const double r = block_point_sum(n, [&](int i, double &r) {
+    const double r = block_point_sum(s.fin ? n : 0, [&](int i, double &r) {
         double q0, q1, q2, sA, sB;
         if (terms(i, q0, q1, q2, sA, sB)) r += resid_point(xb[2 * i], xb[2 * i + 1], q0, q1, q2, sA, sB, s.v);
     });
     if (threadIdx.x == 0) {
         double *o = out + (size_t)b * OFK_SOLVE_DOUBLES;
-        if (t) sub_cross(s.v, ob, t + 3 * b, o);                // v - omega x t
+        if (t && s.fin) sub_cross(s.v, ob, t + 3 * b, o);       // v - omega x t
         else { o[0] = s.v[0]; o[1] = s.v[1]; o[2] = s.v[2]; }
         o[3] = r; o[4] = s.rank; o[5] = s.s3[0]; o[6] = s.s3[1]; o[7] = s.s3[2];
     }
@@ -368,11 +376,13 @@ __global__ __launch_bounds__(64) void k_pairs_solve(const float *__restrict__ pr
     a.m00 = t[0]; a.m01 = t[1]; a.m02 = t[2]; a.m11 = t[3]; a.m12 = t[4]; a.m22 = t[5]; a.g0 = t[6]; a.g1 = t[7]; a.g2 = t[8]; a.bb = t[9]; a.cnt = t[10];
     const double tracked = t[11];
     double v[3] = {0, 0, 0}, s3[3] = {0, 0, 0};                  // every lane solves the same 3x3 system: no broadcast, no barrier
-    const int rank = a.cnt > 0.0 ? solve_from_acc(a, v, s3) : 0;
+    bool fin = true;
+    const int rank = a.cnt > 0.0 ? solve_from_acc(a, v, s3, fin) : 0;
+    const int nr = fin ? n : 0;                                  // non-finite sums: the residual stays 0
 #pragma unroll 1
     for (int vw = 0; vw < 4; ++vw) {
         double r = 0.0;
-        for (int i = vw * 64 + lane; i < n; i += 256) {
+        for (int i = vw * 64 + lane; i < nr; i += 256) {
             if (!st[i]) continue;
             double x, y, ux, uy;
             if (!pair_point(pp, np_, i, cx, cy, scaling, use_feas, feas_T, nrm, vp, d, x, y, ux, uy)) continue;
@@ -423,7 +433,7 @@ __global__ __launch_bounds__(256) void k_pairs_solve_wg(const float *__restrict_
         if (terms(i, x, y, q0, q1, q2, sA, sB)) acc_point(a, x, y, q0, q1, q2, sA, sB);
     });
     tracked = block_sum(tracked, s_red);
-    const double r = block_point_sum(n, [&](int i, double &r) {
+    const double r = block_point_sum(s.fin ? n : 0, [&](int i, double &r) {
         double x, y, q0, q1, q2, sA, sB;
         if (st[i] && terms(i, x, y, q0, q1, q2, sA, sB)) r += resid_point(x, y, q0, q1, q2, sA, sB, s.v);
     });
@@ -788,7 +798,7 @@ __global__ __launch_bounds__(256) void k_stream_fuse(fuse_args g)
     });
     // block_lstsq ends on a block barrier: the keep flags written above are visible to the whole block from here on
     tracked = block_sum(tracked, s_red);
-    const bool solved = s.cnt > (double)g.f.min_solve;
+    const bool solved = s.cnt > (double)g.f.min_solve && s.fin;
     const double r = block_point_sum(solved ? n : 0, [&](int i, double &r) {
         if (!st[i]) return;
         double x, y, ux, uy, wgt, rl;

@@ -19,7 +19,7 @@
 #define ROB_MAX_PTS 4096
 
 struct rob_cfg { int loss; double c; int iters, hyps; unsigned k0, k1; int drop; };
-struct rob_result { double v[3], r, rank, s3[3], cnt, kept, tracked; };   // cnt: points with w > 0; kept: points that entered
+struct rob_result { double v[3], r, rank, s3[3], cnt, kept, tracked; bool fin; };   // cnt: points with w > 0; kept: points that entered; fin: the plain sums are finite
 
 struct rob_lds {
     unsigned long long keep[ROB_MAX_PTS / 64];                   // bit `lane` of keep[c]: point c * 64 + lane enters the solve
@@ -27,7 +27,7 @@ struct rob_lds {
     double part[4][14];                                          // wave-reduced sums of the four virtual waves
     double best[4][5];                                           // per wave: score, hypothesis, its velocity (kept here, not in registers)
     double plain[4][8];                                          // per wave: the plain start 0-2, then singular values 3-5 and rank 6 of the current system
-    double sums[4][4];                                           // per wave: bb, kept count, tracked count of the plain sums
+    double sums[4][4];                                           // per wave: bb, kept count, tracked count of the plain sums, whether they are finite
 };
 
 __device__ __forceinline__ void acc_point_w(Acc &a, double x, double y, double q0, double q1, double q2, double sA, double sB, double w)
@@ -138,12 +138,15 @@ __device__ __forceinline__ void robust_core(rob_lds &L, const rob_cfg &rc, int n
         // back its own store, so no barrier is involved
         L.sums[wave][0] = t[9]; L.sums[wave][1] = t[10]; L.sums[wave][2] = t[11];
     }
-    const bool solvable = a0.cnt > min_cnt;
+    bool solvable = a0.cnt > min_cnt;
     double v[3] = {0, 0, 0};
     double *plain = L.plain[wave];
     {
         double s3[3] = {0, 0, 0};
-        const int rank = solvable ? solve_from_acc(a0, v, s3) : 0;   // today's plain result; every thread solves the same system
+        bool fin = true;
+        const int rank = solvable ? solve_from_acc(a0, v, s3, fin) : 0;   // today's plain result; every thread solves the same system
+        solvable = solvable && fin;                              // non-finite sums: not solved - flag 1, weights 1, residual 0
+        L.sums[wave][3] = fin ? 1.0 : 0.0;
         plain[0] = v[0]; plain[1] = v[1]; plain[2] = v[2]; plain[3] = s3[0]; plain[4] = s3[1]; plain[5] = s3[2]; plain[6] = (double)rank;
     }
     // kept point number -> index: an exclusive scan of the chunks' populations, then each kept point's place inside its chunk
@@ -203,7 +206,8 @@ __device__ __forceinline__ void robust_core(rob_lds &L, const rob_cfg &rc, int n
                 acc_point(a, T[pi], T[S + pi], T[2 * S + pi], T[3 * S + pi], T[4 * S + pi], T[5 * S + pi], T[6 * S + pi]);
                 acc_point(a, T[pj], T[S + pj], T[2 * S + pj], T[3 * S + pj], T[4 * S + pj], T[5 * S + pj], T[6 * S + pj]);
                 double hs[3];
-                hrank = solve_from_acc(a, hv, hs);
+                bool hfin;
+                hrank = solve_from_acc(a, hv, hs, hfin);
             }
             const int nh = rc.hyps - h0 < 64 ? rc.hyps - h0 : 64;
             for (int hl = wave; hl < nh; hl += NW) {
@@ -258,7 +262,8 @@ __device__ __forceinline__ void robust_core(rob_lds &L, const rob_cfg &rc, int n
                 aw.m00 = t[0]; aw.m01 = t[1]; aw.m02 = t[2]; aw.m11 = t[3]; aw.m12 = t[4]; aw.m22 = t[5]; aw.g0 = t[6]; aw.g1 = t[7]; aw.g2 = t[8]; aw.cnt = t[9];
             }
             double v2[3], s2[3];
-            const int rk = solve_from_acc(aw, v2, s2);
+            bool wfin;
+            const int rk = solve_from_acc(aw, v2, s2, wfin);
             if (rk < 3) { flag = 3; break; }
             v[0] = v2[0]; v[1] = v2[1]; v[2] = v2[2]; plain[3] = s2[0]; plain[4] = s2[1]; plain[5] = s2[2]; plain[6] = (double)rk;
             wcur = wn; ones = false; ++done;
@@ -288,7 +293,7 @@ __device__ __forceinline__ void robust_core(rob_lds &L, const rob_cfg &rc, int n
     const double sw = (L.part[0][1] + L.part[1][1]) + (L.part[2][1] + L.part[3][1]);
     R.cnt = (L.part[0][2] + L.part[1][2]) + (L.part[2][2] + L.part[3][2]);
     R.v[0] = v[0]; R.v[1] = v[1]; R.v[2] = v[2]; R.rank = plain[6]; R.s3[0] = plain[3]; R.s3[1] = plain[4]; R.s3[2] = plain[5];
-    R.kept = L.sums[wave][1]; R.tracked = L.sums[wave][2];
+    R.kept = L.sums[wave][1]; R.tracked = L.sums[wave][2]; R.fin = L.sums[wave][3] != 0.0;
     if (threadIdx.x == 0) {
         stats[0] = s; stats[1] = sw; stats[2] = R.cnt; stats[3] = (double)m; stats[4] = (double)hyp; stats[5] = score;
         stats[6] = (double)done; stats[7] = (double)flag;
@@ -323,7 +328,7 @@ __global__ __launch_bounds__(256) void k_solve_robust(int variant, const double 
                    }, R);
     if (threadIdx.x == 0) {
         double *o = out + (size_t)b * OFK_SOLVE_DOUBLES;
-        if (t) sub_cross(R.v, ob, t + 3 * b, o);
+        if (t && R.fin) sub_cross(R.v, ob, t + 3 * b, o);
         else { o[0] = R.v[0]; o[1] = R.v[1]; o[2] = R.v[2]; }
         o[3] = R.r; o[4] = R.rank; o[5] = R.s3[0]; o[6] = R.s3[1]; o[7] = R.s3[2];
     }
@@ -446,7 +451,7 @@ __global__ __launch_bounds__(256) void k_stream_fuse_robust(fuse_args g, rob_fus
     if (ra.rc.drop)
         for (int i = tid; i < n; i += 256)
             if (((L.keep[i >> 6] >> (i & 63)) & 1ull) && wrow[i] == 0.0) st[i] = 0;
-    const bool solved = R.kept > (double)g.f.min_solve;
+    const bool solved = R.kept > (double)g.f.min_solve && R.fin;
     if (tid == 0) {
         double *o = g.records + (size_t)b * OFK_RECORD_DOUBLES, vu[3];
         write_record(o, R.v, R.r, R.rank, R.s3, om, sn + 16, ist ? ist + 6 : sn + 7, R.cnt, n, R.tracked, vu);

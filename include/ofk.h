@@ -386,7 +386,16 @@ int ofk_feasibility(ofk_ctx *ctx, int variant, const double *x, const double *u,
 #define OFK_SOLVE_DOUBLES   8   /* out per problem: v[3], residual SS, rank, s[3] (singular values, descending) */
 /* x,u [batch][n][2]; valid (nullable) [batch][n] u8, 0 = skip the point; d [batch]; nrm, omega [batch][3];
  * t (nullable) [batch][3]: subtract omega x t from v (simulation.py:28, evaluate_exp.py:29);
- * wgt (OFMODULE only) [batch][n] per-point distance.  Fewer than 1 valid point -> rank 0, v = 0. */
+ * wgt (OFMODULE only) [batch][n] per-point distance.  Fewer than 1 valid point -> rank 0, v = 0.
+ * Non-finite sums.  Every solve of the library (this entry, the robust and covariance entries, the pair and stream kernels) forms
+ * the 3 x 3 normal equations M v = g.  A problem whose sums - M, g, and the eigenvalues of M - are not all finite (a NaN or inf
+ * range, gyro or point; a valid point with n.p == 0 in the NODE system) is not solved: rank 0, v = 0 (no omega x t taken off),
+ * s = 0, residual 0, the point count as counted.  It counts as not solved everywhere: record[15] = 0 and fused[7] = 0, the filters
+ * stay at their prediction (record[4] != 3), vel_overwrite does not fire, the covariance record is void, the robust stats carry
+ * flag 1 with all kept weights 1.  Problems whose sums are finite are not touched by this, bit for bit.
+ * Accuracy.  v comes from the normal equations, so a rank-3 result is accurate to about C kappa^2 eps relative, kappa = s[0] / s[2]
+ * (record fields 5 and 7), C a few tens ("rank"); the rank cut only fires at kappa = 1 / sqrt(eps 3N).  A
+ * consumer that needs a given accuracy gates on kappa, not on rank 3. */
 int ofk_velocity_solve(ofk_ctx *ctx, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
                        const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
                        double *out);
