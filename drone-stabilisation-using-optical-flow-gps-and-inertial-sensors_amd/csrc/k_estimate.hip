@@ -1279,3 +1279,6 @@ void ofk_launch_associate(hipStream_t s, const double *t_img, int n_img, int n_i
 
 // ------------------------------------------------------------------------------------------------ velocity covariance
 #include "k_cov.inc"
+
+// ------------------------------------------------------------------------------------------------ joint velocity and rotation solve
+#include "k_joint.inc"

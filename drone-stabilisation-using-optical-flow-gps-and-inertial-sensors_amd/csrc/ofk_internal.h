@@ -96,6 +96,8 @@ struct ofk_ctx {
     int grid_batch;                          // images of the latest selection with a grid on (ofk_corner_grid_download), 0 = none
     ofk_cov cov;                             // ofk_set_cov: mode OFK_COV_OFF unless set
     double *cov_rec; int cov_batch;          // [B][OFK_COV_DOUBLES] (lazily allocated); problems of the latest run / step with it on, 0 = none
+    ofk_joint joint;                         // ofk_set_joint: mode OFK_JOINT_OFF unless set
+    double *joint_rec; int joint_batch;      // [B][OFK_JOINT_DOUBLES] (lazily allocated); problems of the latest run / step with it on, 0 = none
     ofk_zones zones;                         // ofk_set_zones: mode OFK_ZONES_OFF unless set
     int *zone_tab; float *zone_mot; int *zone_stats, *zone_work;   // [B][OFK_ZONE_MAX][OFK_ZONE_INTS], [B][OFK_ZONE_MAX][OFK_ZONE_FLOATS], [B][OFK_ZONE_STATS], [B][2][max_pts] hull stacks;
     uint8_t *zone_status;                    // [B][max_pts] status in front of the solve stage; one lazy allocation (zone_tab owns it)
@@ -228,6 +230,18 @@ void ofk_launch_stream_cov(hipStream_t s, const float *prev_pts, const float *ne
                            double *cov, int batch);
 void ofk_launch_kf_records_cov(hipStream_t s, int ns, int nm, const double *mats, double *x, double *P, const double *records, double *cov,
                                const ofk_cov *c, double z_sign, int z_source, int batch);
+// the joint velocity and rotation solve (k_joint.inc), behind the solve kernels: rewrites out / records in place; weights NULL = the
+// plain solve ran; joint: the slice's rows of joint_rec
+void ofk_launch_joint_solve(hipStream_t s, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                            const double *d, const double *nrm, const double *omega, const double *t, const double *weights,
+                            const ofk_joint *j, double *out, double *joint);
+void ofk_launch_pairs_joint(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts,
+                            int pts_stride, const double *sensors, int variant, int use_feas, double feas_T, const double *weights,
+                            const ofk_joint *j, double *records, double *joint, int batch);
+void ofk_launch_stream_joint(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
+                             const double *sensors, double *imu_state, int ns, int nm, int nc, const double *kf_mats, double *kf_x, double *kf_P,
+                             const ofk_fusion *f, int variant, double *records, double *fused, const double *weights, const ofk_joint *j,
+                             double *joint, int batch, int defer);
 void ofk_launch_records_f32(hipStream_t s, const double *records, float *dst, int batch);
 
 void ofk_launch_flow_model(hipStream_t s, const double *x, int batch, int n, const double *v, const double *omega,

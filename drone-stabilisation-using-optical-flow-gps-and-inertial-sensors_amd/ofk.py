@@ -28,6 +28,7 @@ SYMBOLS = (
     "ofk_good_features", "ofk_lk_pyr", "ofk_lk_pyr_ex", "ofk_predict_points", "ofk_set_lk_seed", "ofk_get_lk_seed", "ofk_flow_model", "ofk_feasibility", "ofk_velocity_solve", "ofk_imu_propagate",
     "ofk_set_robust", "ofk_get_robust", "ofk_robust_download", "ofk_velocity_solve_robust", "ofk_robust_pairs",
     "ofk_set_cov", "ofk_get_cov", "ofk_cov_download", "ofk_velocity_solve_cov",
+    "ofk_set_joint", "ofk_get_joint", "ofk_joint_download", "ofk_velocity_solve_joint",
     "ofk_set_track_gate", "ofk_get_track_gate", "ofk_track_gate_download", "ofk_lk_pyr_fb",
     "ofk_set_corner_grid", "ofk_get_corner_grid", "ofk_corner_grid_download", "ofk_select_corners_grid", "ofk_good_features_grid",
     "ofk_set_zones", "ofk_get_zones", "ofk_zones_step", "ofk_zones_reset", "ofk_zones_download",
@@ -66,6 +67,8 @@ ROBUST_MIN_POINTS, ROBUST_DOUBLES = 8, 8
 COV_OFF, COV_PROPAGATE, COV_RESIDUAL = 0, 1, 2           # ofk_set_cov / ofk_velocity_solve_cov
 COV_MODES = {"off": COV_OFF, "propagate": COV_PROPAGATE, "residual": COV_RESIDUAL}
 COV_DOUBLES = 24
+JOINT_OFF, JOINT_ON = 0, 1                               # ofk_set_joint / ofk_velocity_solve_joint
+JOINT_DOUBLES = 32
 FB_OFF, FB_PLAIN, FB_SEEDED = 0, 1, 2                    # ofk_set_track_gate / ofk_lk_pyr_fb
 FB_MODES = {"off": FB_OFF, "plain": FB_PLAIN, "seeded": FB_SEEDED}
 GRID_MAX_CELLS = 2048                                   # OFK_GRID_MAX_CELLS: cells of a corner grid over one frame
@@ -129,6 +132,18 @@ def cov_setting(mode="propagate", sigma_flow=0.0, sigma_pos=0.0, sigma_d=0.0, si
     so = np.broadcast_to(np.asarray(sigma_omega, np.float64), (3,))
     return Cov(int(mode), float(sigma_flow), float(sigma_pos), float(sigma_d), (C.c_double * 3)(*so.tolist()), float(sigma_normal),
                float(sigma_offset), int(bool(omega_from_imu)), int(bool(filter_r)), float(r_floor), float(nis_max))
+
+
+class Joint(C.Structure):
+    """ofk_joint (include/ofk.h): the joint velocity and rotation solve's setting."""
+    _fields_ = [("mode", C.c_int), ("sigma_flow", C.c_double), ("sigma_omega", C.c_double * 3), ("omega_from_imu", C.c_int)]
+
+
+def joint_setting(mode=True, sigma_flow=0.2, sigma_omega=None, omega_from_imu=False):
+    """A Joint structure from names: mode True / False (or JOINT_*); sigma_flow in the units of the points the entry takes (pixels in
+    the resident paths); sigma_omega None = every axis free (+inf), a scalar or three values (+inf: free, 0: held)."""
+    so = np.broadcast_to(np.asarray(np.inf if sigma_omega is None else sigma_omega, np.float64), (3,))
+    return Joint(int(mode), float(sigma_flow), (C.c_double * 3)(*so.tolist()), int(bool(omega_from_imu)))
 
 
 def cov_matrix(t6):
@@ -356,6 +371,9 @@ def load_library():
         L.ofk_robust_pairs.argtypes = [C.c_ulonglong, C.c_uint, i, i, vp, vp]
         L.ofk_set_cov.argtypes = [vp, C.POINTER(Cov)]; L.ofk_get_cov.argtypes = [vp, C.POINTER(Cov)]
         L.ofk_cov_download.argtypes = [vp, vp]
+        L.ofk_set_joint.argtypes = [vp, C.POINTER(Joint)]; L.ofk_get_joint.argtypes = [vp, C.POINTER(Joint)]
+        L.ofk_joint_download.argtypes = [vp, vp]
+        L.ofk_velocity_solve_joint.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Joint), vp, vp]
         L.ofk_velocity_solve_cov.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Cov), vp, vp]
         L.ofk_set_track_gate.argtypes = [vp, C.POINTER(TrackGate)]; L.ofk_get_track_gate.argtypes = [vp, C.POINTER(TrackGate)]
         L.ofk_track_gate_download.argtypes = [vp, vp, vp, vp, i, vp]
@@ -1046,6 +1064,50 @@ class Context:
         rec = np.zeros((self.max_batch, COV_DOUBLES), np.float64)
         with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
             self._ck(self._L.ofk_cov_download(self._h, _p(rec)))
+        return rec[:batch].copy()
+
+    def velocity_solve_joint(self, variant, x, u, d=None, nrm=None, omega=None, t=None, valid=None, robust=None, joint=None, **settings):
+        """ofk_velocity_solve_joint: velocity_solve's arguments (NODE or SIM), an optional Robust and the joint setting (a Joint, or
+        joint_setting's keywords).  Returns out [B,8] after the joint rewrite, joint [B,32] (single problem: [8], [32])."""
+        jv = joint if joint is not None else joint_setting(**settings)
+        x = _arr(x, np.float64); u = _arr(u, np.float64)
+        if u.shape[:-1] != x.shape[:-1] or x.shape[-1] != 2 or u.shape[-1] < 2:
+            raise ValueError(f"velocity_solve_joint: x {x.shape} must be [..., n, 2] and u {u.shape} [..., n, >=2] over the same points")
+        single = x.ndim == 2
+        if single:
+            x = x[None]; u = u[None]
+        B, n, _ = x.shape
+        u = _arr(u[..., :2], np.float64)
+        nrm = _arr(nrm, np.float64, (B, 3))
+        d = _opt(d, np.float64, (B,)); omega = _opt(omega, np.float64, (B, 3)); t = _opt(t, np.float64, (B, 3))
+        valid = _opt(valid, np.uint8, (B, n))
+        out = np.zeros((B, SOLVE_DOUBLES), np.float64); rec = np.zeros((B, JOINT_DOUBLES), np.float64)
+        if not n:                                               # no points: velocity_solve's zeros, nothing attempted
+            if omega is not None:
+                rec[:, 0:3] = omega
+            rec[:, 10] = 1.0
+            return (out[0], rec[0]) if single else (out, rec)
+        with self._lock:
+            self._ck(self._L.ofk_velocity_solve_joint(self._h, int(variant), _p(x), _p(u), _p(valid), B, n, _p(d), _p(nrm), _p(omega), _p(t),
+                                                      None, C.byref(robust) if robust is not None else None, C.byref(jv), _p(out), _p(rec)))
+        return (out[0], rec[0]) if single else (out, rec)
+
+    def set_joint(self, joint=None, **settings):
+        """ofk_set_joint: a Joint (or joint_setting's keywords); None or mode False switches it off.  Every later pairs_run and stream
+        step refines the gyro from the flow and rewrites v, the residual and v_uav of its records."""
+        jv = joint if joint is not None or not settings else joint_setting(**settings)
+        self._ck(self._L.ofk_set_joint(self._h, C.byref(jv) if jv is not None else None))
+
+    def get_joint(self):
+        jv = Joint()
+        self._ck(self._L.ofk_get_joint(self._h, C.byref(jv)))
+        return jv
+
+    def joint_download(self, batch):
+        """joint [batch, 32] of the latest run / step with the setting on."""
+        rec = np.zeros((self.max_batch, JOINT_DOUBLES), np.float64)
+        with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
+            self._ck(self._L.ofk_joint_download(self._h, _p(rec)))
         return rec[:batch].copy()
 
     def imu_propagate(self, state, msg):

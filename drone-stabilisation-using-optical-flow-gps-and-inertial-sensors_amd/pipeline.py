@@ -112,6 +112,13 @@ class PipelineConfig:
     cov_filter: bool = False
     r_floor: float = 0.0
     nis_max: float = 0.0
+    # joint velocity and rotation solve (ofk.h: ofk_set_joint): the gyro refined from the flow behind every solve; joint_sigma_flow_px
+    # the flow noise in pixels; omega_prior None (every axis free), a scalar or three values (rad per frame; inf: free, 0: held);
+    # omega_prior_from_imu: the resident IMU state's angular-velocity variances under use_imu
+    joint: bool = False
+    joint_sigma_flow_px: float = 0.2
+    omega_prior: object = None
+    omega_prior_from_imu: bool = False
     # exclusion zones (ofk.h: ofk_set_zones; streams only): None or "hull"; rejects of the solve stage closer than zone_link pixels
     # per axis form a cluster, one of at least zone_min becomes a zone (its hull grown by zone_radius) that moves with the cluster's
     # mean flow, keeps the re-detection out and lives zone_ttl steps behind its last refresh; at most zone_max zones per stream
@@ -170,6 +177,12 @@ class PipelineConfig:
             return None
         return ofk.cov_setting(self.cov, self.sigma_flow_px, self.sigma_pos_px, self.sigma_d, self.sigma_omega, self.sigma_normal,
                                self.sigma_offset, self.omega_from_imu, self.cov_filter, self.r_floor, self.nis_max)
+
+    def joint_setting(self):
+        """The ofk.Joint structure of this configuration, None when the joint solve is off."""
+        if not self.joint:
+            return None
+        return ofk.joint_setting(True, self.joint_sigma_flow_px, self.omega_prior, self.omega_prior_from_imu)
 
     def zones_setting(self):
         """The ofk.Zones structure of this configuration, None when the zones are off."""
@@ -322,6 +335,8 @@ class FlowStream:
             self.ctx.set_corner_grid(self.cfg.corner_grid_setting())
         if self.cfg.cov != "off":
             self.ctx.set_cov(self.cfg.cov_setting())
+        if self.cfg.joint:
+            self.ctx.set_joint(self.cfg.joint_setting())
         if self.cfg.zones_setting() is not None:
             self.ctx.set_zones(self.cfg.zones_setting())
         if self.cfg.camera_setting() is not None:
@@ -354,6 +369,11 @@ class FlowStream:
     def corner_grid_stats(self):
         """[batch, 2] int32 of the latest detection (begin or re-detection) with a corner grid on: corners accepted, candidates examined."""
         return self.ctx.corner_grid_stats(self.batch)
+
+    def rotations(self):
+        """[batch, 32] joint records (ofk.h: ofk_set_joint) of the latest step with the joint solve on: rec[:, 0:3] is the refined omega,
+        rec[:, 3:6] its correction, rec[:, 10] the flag, ofk.cov_matrix(rec[:, 15:21]) C_omega, ofk.cov_matrix(rec[:, 21:27]) C_v."""
+        return self.ctx.joint_download(self.batch)
 
     def covariances(self):
         """[batch, 24] cov records (ofk.h: ofk_set_cov) of the latest step with the covariance on; ofk.cov_matrix(rec[:, 0:6]) is C_v,
@@ -413,6 +433,8 @@ class FlowPipeline:
             self.ctx.set_corner_grid(self.cfg.corner_grid_setting())
         if self.cfg.cov != "off":
             self.ctx.set_cov(self.cfg.cov_setting())
+        if self.cfg.joint:
+            self.ctx.set_joint(self.cfg.joint_setting())
         if self.cfg.camera_setting() is not None:
             self.ctx.set_camera(self.cfg.camera_setting())
         if self.cfg.rolling_shutter_setting() is not None:
@@ -463,6 +485,10 @@ class FlowPipeline:
     def corner_grid_stats(self):
         """[batch, 2] int32 of the latest run with a corner grid on: corners accepted, candidates examined."""
         return self.ctx.corner_grid_stats(self.batch)
+
+    def rotations(self):
+        """[batch, 32] joint records (ofk.h: ofk_set_joint) of the latest run with the joint solve on (see FlowStream.rotations)."""
+        return self.ctx.joint_download(self.batch)
 
     def covariances(self):
         """[batch, 24] cov records (ofk.h: ofk_set_cov) of the latest run with the covariance on (see FlowStream.covariances)."""

@@ -49,6 +49,17 @@ def solve_lgs_robust(x, u, d, n, omega, t, **settings):
     return out[:3].copy(), R, out[5:8].copy(), w, st
 
 
+def solve_lgs_joint(x, u, d, n, omega, t, sigma_flow, sigma_omega=None):
+    """solve_lgs with the gyro refined from the flow (ofk.h: ofk_velocity_solve_joint).  sigma_flow: the flow noise in the units of x
+    and u; sigma_omega: None (every axis free), a scalar or three values (inf: free, 0: held).
+    Returns (v - omega_hat x t, R, s, omega_hat, joint [32]); joint[10] != 0 where the plain result stands."""
+    x = np.asarray(x, np.float64)
+    out, jr = ofk.default_context().velocity_solve_joint(ofk.SOLVE_SIM, x[:, :2], np.asarray(u, np.float64)[:, :2], d=float(np.ravel(d)[0]),
+                                                         nrm=n, omega=omega, t=t, sigma_flow=sigma_flow, sigma_omega=sigma_omega)
+    R = np.array([out[3]]) if (int(out[4]) == 3 and 3 * len(x) > 3) else np.empty(0)
+    return out[:3].copy(), R, out[5:8].copy(), jr[0:3].copy(), jr
+
+
 def feasibility(position, linear_velocity, flow, angular_velocity, translation, normal):
     r, length = ofk.default_context().feasibility(ofk.FEAS_SIM, np.asarray(position, np.float64)[:, :2],
                                                   np.asarray(flow, np.float64)[:, :2], normal, linear_velocity,

@@ -84,6 +84,19 @@ def solve_lgs_cov(x, u, d, n, omega, mode="propagate", **sigmas):
     return out[:3].copy(), R, rank, out[5:8].copy(), ofk.cov_matrix(cov[0:6]), cov
 
 
+def solve_lgs_joint(x, u, d, n, omega, sigma_flow, sigma_omega=None):
+    """solve_lgs with the gyro refined from the flow (ofk.h: ofk_velocity_solve_joint): velocity and rotation from one 6-unknown
+    least squares.  sigma_flow: the flow noise in the units of x and u; sigma_omega: None (every axis free), a scalar or three
+    values - the prior on omega's error (inf: free, 0: held).
+    Returns (v, R, rank, s, omega_hat, joint [32]); joint[10] != 0 where the joint solve left the plain result alone."""
+    x = np.asarray(x, np.float64); u = np.asarray(u, np.float64)
+    out, jr = ofk.default_context().velocity_solve_joint(ofk.SOLVE_NODE, x[:, :2], u[:, :2], d=float(d), nrm=n, omega=omega,
+                                                         sigma_flow=sigma_flow, sigma_omega=sigma_omega)
+    rank = int(out[4])
+    R = np.array([out[3]]) if (rank == 3 and 3 * len(x) > 3) else np.empty(0)
+    return out[:3].copy(), R, rank, out[5:8].copy(), jr[0:3].copy(), jr
+
+
 def feasible(x, v, omega, T, u, d, n):
     """node:44-50 (reference not executable: uses v_cr/u_cr before definition, returns nothing).  The evident
     intent — parallelity and distance of each point given the lever-arm corrected velocity — is returned."""
@@ -106,6 +119,7 @@ class optical_fusion:
     _track_gate = {}                                             # PipelineConfig's fb_check / fb_thr / fb_level / err_max; empty: no gate
     _corner_grid = {}                                            # PipelineConfig's grid_cell / grid_cap / grid_max_rank; empty: no grid
     _cov = {}                                                    # PipelineConfig's covariance fields (cov, sigma_*, ...); empty: no covariance
+    _joint = {}                                                  # PipelineConfig's joint fields (joint, joint_sigma_flow_px, omega_prior, ...); empty: the gyro is taken as exact
     _zones = {}                                                  # PipelineConfig's zones / zone_* fields; empty: no exclusion zones
     _camera = {}                                                 # PipelineConfig's camera field; empty: the points are taken as ideal pinhole samples
     _rolling_shutter = {}                                        # PipelineConfig's rolling_shutter field; empty: every row is taken as exposed at the time stamp
@@ -263,7 +277,7 @@ class optical_fusion:
                                  min_distance=float(self.feature_params["minDistance"]), block_size=int(self.feature_params["blockSize"]),
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
-                                 **self._cov, **self._zones, **self._camera, **self._rolling_shutter)
+                                 **self._cov, **self._joint, **self._zones, **self._camera, **self._rolling_shutter)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -301,6 +315,8 @@ class optical_fusion:
             self.last_cov = cv
             if cv[13] == 0:
                 self.vel_err = np.sqrt(np.maximum(cv[[6, 9, 11]], 0.0))
+        if self._joint and r[15]:
+            self.last_joint = fs.rotations()[0]
         self.init = False
         self.got_picture_ = True
 
@@ -360,7 +376,7 @@ class optical_fusion:
             self.vel_err = np.sqrt(np.maximum(np.diag(Rm @ ofk.cov_matrix(cv[6:12]) @ Rm.T), 0.0))
 
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
-                 rolling_shutter=None):
+                 rolling_shutter=None, joint=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -382,7 +398,10 @@ class optical_fusion:
         rolling_shutter: None (every row is taken as exposed at the frame's time stamp) or a pipeline.RollingShutter (or a dict of its
         fields), e.g. dict(readout=0.9, mode="gyro", anchor=0.5): the restored pipeline then undoes the per-row capture time on the
         device in front of the solve (ofk.h: ofk_set_rolling_shutter); the node's omega is per frame interval as it stands only if
-        omega_gain says so."""
+        omega_gain says so.
+        joint: None (the gyro is taken as exact), True, or a dict of sigma_flow_px, omega_prior, omega_prior_from_imu (PipelineConfig's
+        joint fields), e.g. dict(sigma_flow_px=0.2, omega_prior=1e-3): every solved step then refines the gyro from the flow and
+        reports the joint velocity (ofk.h: ofk_set_joint); self.last_joint is the record, its slots 0-2 the refined omega."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -399,6 +418,15 @@ class optical_fusion:
         if self._cov:
             PipelineConfig(**self._cov).cov_setting()            # unknown or invalid keywords fail here, not at the first frame
         self.last_cov = None
+        if joint:
+            j = {} if joint is True else dict(joint)
+            if "sigma_flow_px" in j:
+                j["joint_sigma_flow_px"] = j.pop("sigma_flow_px")
+            self._joint = dict(joint=True, **j)
+            PipelineConfig(**self._joint).joint_setting()        # unknown or invalid keywords fail here, not at the first frame
+        else:
+            self._joint = {}
+        self.last_joint = None
         z = dict(zones or {})
         if zones is not None:
             ofk.zones_setting(**z)                               # unknown or invalid keywords fail here, not at the first frame

@@ -554,6 +554,63 @@ int ofk_velocity_solve_cov(ofk_ctx *ctx, int variant, const double *x, const dou
                            const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
                            const ofk_robust *r, const ofk_cov *c, double *out, double *cov);
 
+/* The joint velocity and rotation solve: the gyro refined from the flow.  Every solve of the library takes the sensor record's omega as
+ * exact when it forms q = u + p x omega; a gyro sample associated by nearest time stamp (evaluate_exp.py:68-80) lags by up to half an
+ * IMU period, a common-mode error no per-point repair sees.  The flow is linear in (v, omega), so both come from one 6-unknown linear
+ * least squares on sums of the solve's own kind.  Off by default; with it off every entry point launches the kernels and returns the
+ * bits it always did, with no allocation and no launch.  All arithmetic is f64.
+ * Point set: the kept points are exactly the solve's - gated status / valid / pair feasibility keep, and behind a robust run those of
+ * final weight w > 0, w used as the weight and held fixed (the weights are not re-run at the refined omega).
+ * Model: with omega0 the sensors' omega, p = (x, y, 1), X = [p]x, N = X^T X = |p|^2 I - p p^T and the solve's per-point terms at omega0,
+ * q0 = (u, 0) + p x omega0, a = sA, b = sB, point i's rows for omega = omega0 + delta are  a X v + b N delta = b X q0  (X X = -N).
+ * With the prior delta_k ~ N(0, sigma_omega[k]^2) the normal equations are [M, K; K^T, D + Lambda] (v, delta) = (g_v, g_delta):
+ *   M = sum w a^2 N (the solve's own matrix)     K = -sum w a b |p|^2 X (three sums)     D = sum w b^2 |p|^2 N (six sums)
+ *   Lambda = diag((d sigma_f / sigma_omega[k])^2)
+ * sigma_f is sigma_flow in the units of the points: scaled units in ofk_velocity_solve_joint, pixels x `scaling` (sensor slot 19) in the
+ * resident paths, as for the covariance.  Solution by the Schur complement, with v_s = M^+ g_v read from the solve's record:
+ *   c = sum w b |p|^2 X (b q0 - a v_s)   (three sums; the reduced right-hand side g_delta - K^T v_s)
+ *   S = D + Lambda - K^T M^-1 K,   delta = S^-1 c,   v = v_s - M^-1 K delta,   omega^ = omega0 + delta
+ * M is accumulated again in the solve's own order; M^-1 and S^-1 both come from the eigen-decomposition (cyclic Jacobi) the solve uses;
+ * all 19 sums are added over four virtual waves as (s0 + s1) + (s2 + s3), so records are bit-identical across launch forms (one wave
+ * per pair from 128 pairs per slice on, a 256-thread workgroup below), slice counts and overlap settings.
+ * Per-axis prior sigma_omega[k]: +inf = the axis is free (Lambda_k = 0); 0 = the axis is held: it is taken out of S and delta_k = 0;
+ * anything else is the prior's standard deviation.  With omega_from_imu under ofk_fusion.use_imu the variances are the resident IMU
+ * state's slots 21-23 (variances already; 0 holds, +inf frees).  With all three axes held every record is bit-identical to the
+ * setting off (the joint record reports flag 0, delta = 0 and C_v = (d sigma_f)^2 M^-1).
+ * Not attempted, flag 1 - the record is untouched, omega^ = omega0: the solve did not solve (rank < 3, non-finite sums, in the stream
+ * steps record[15] == 0), `scaling` == 0 or d == 0, or any joint sum or result is not finite.
+ * Unobservable, flag 2 - the record is untouched, omega^ = omega0: among the estimated axes an eigenvalue of S is not positive or falls
+ * below sqrt(eps 3 m) times the largest, m the kept points.  Slots 12-14 report the eigenvalues.
+ * On success, flag 0: record / out fields 0-2 become v (the stage entry takes omega^ x t off when t is given); field 3 the residual sum
+ * of squares sum w |a X v - b X q(omega^)|^2, without the prior term, from a second walk over the points in the solve's order; record
+ * fields 8-10 become R (v - omega^ x offset).  Fields 4-7 and 11-15 stay.
+ * Joint record, OFK_JOINT_DOUBLES per problem: 0-2 omega^; 3-5 delta; 6-8 fields 0-2 of the solve's record before; 9 its residual
+ * before; 10 flag; 11 kept points; 12-14 eigenvalues of S, descending, 0 for held axes (0 with flag 1); 15-20 C_omega =
+ * (d sigma_f)^2 S^-1, upper triangle (xx xy xz yy yz zz; 0 in held rows); 21-26 C_v = (d sigma_f)^2 (M^-1 + G S^-1 G^T), G = M^-1 K;
+ * 27-31 reserved, 0.  With a flag set 3-5 and 15-26 are 0.
+ * ofk_set_joint (NULL or mode OFK_JOINT_OFF: off) is a context setting read by ofk_pairs_run (every slice), ofk_stream_step[_jpeg] and
+ * ofk_stream_step_fused[_jpeg]; ofk_pairs_filter_step behind such a run reads the rewritten records.  In the fused step with a filter
+ * the fuse kernel leaves the filter at its prediction and the joint kernel behind it corrects with the joint v / v_uav, rewrites
+ * fused[0..7] and repeats vel_overwrite with the joint v_uav; under use_imu omega0, the normal and R are the IMU state's.
+ * Refused with OFK_E_INVALID before any launch, the previous setting staying in place: an unknown mode; a sigma_omega that is negative
+ * or NaN; sigma_flow not finite or <= 0; omega_from_imu not 0/1.  Refused with OFK_E_INVALID by the runs and steps where the setting is
+ * on: OFK_SOLVE_OFMODULE, OFK_FLOW_ROTATIONAL and OFK_KEEP_LEGACY (not the sensor model, as for the covariance), and the covariance
+ * setting together with this one (its propagation treats omega as an input, not an estimate; the joint record's C_v is the stopgap).
+ * ofk_joint_download: joint [batch][OFK_JOINT_DOUBLES] of the latest run / step with the setting on (`batch` is that run's own);
+ * OFK_E_INVALID before such a run.
+ * ofk_velocity_solve_joint = ofk_velocity_solve's arguments (n <= 4096; NODE or SIM) plus the robust setting (NULL: the plain solve)
+ * and the joint setting (mode OFK_JOINT_ON); out as ofk_velocity_solve after the rewrite, joint [batch][OFK_JOINT_DOUBLES]. */
+#define OFK_JOINT_OFF 0
+#define OFK_JOINT_ON 1
+#define OFK_JOINT_DOUBLES 32
+typedef struct ofk_joint { int mode; double sigma_flow; double sigma_omega[3]; int omega_from_imu; } ofk_joint;
+int ofk_set_joint(ofk_ctx *ctx, const ofk_joint *j);
+int ofk_get_joint(const ofk_ctx *ctx, ofk_joint *j);
+int ofk_joint_download(ofk_ctx *ctx, double *joint);
+int ofk_velocity_solve_joint(ofk_ctx *ctx, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                             const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
+                             const ofk_robust *r, const ofk_joint *j, double *out, double *joint);
+
 /* optical_fusion.call_imu — node:61-89, batched over independent IMU streams, one message each.
  * state [batch][OFK_IMU_STATE]: vel[3], old_time, time_zero, first(0/1), rotation[9], normal[3], ang[3], ang_err[3]
  * msg   [batch][OFK_IMU_MSG]  : secs, nsecs, qx,qy,qz,qw, wx,wy,wz, cov0,cov4,cov8, ax,ay,az */
