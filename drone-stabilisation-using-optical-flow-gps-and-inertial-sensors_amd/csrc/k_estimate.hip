@@ -1282,3 +1282,6 @@ void ofk_launch_associate(hipStream_t s, const double *t_img, int n_img, int n_i
 
 // ------------------------------------------------------------------------------------------------ joint velocity and rotation solve
 #include "k_joint.inc"
+
+// ------------------------------------------------------------------------------------------------ plane solve
+#include "k_plane.inc"

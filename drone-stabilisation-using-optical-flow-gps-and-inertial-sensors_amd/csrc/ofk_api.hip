@@ -151,6 +151,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->gate = ofk_track_gate{OFK_FB_OFF, 0.5, -1, 0.0};
     c->cov = ofk_cov{OFK_COV_OFF, 0.0, 0.0, 0.0, {0.0, 0.0, 0.0}, 0.0, 0.0, 0, 0, 0.0, 0.0};
     c->joint = ofk_joint{OFK_JOINT_OFF, 0.2, {INFINITY, INFINITY, INFINITY}, 0};
+    c->plane = ofk_plane{OFK_PLANE_OFF, 0.2, INFINITY, 0.1, {0.0, 0.0, 1.0}, 6};
     c->zones = ofk_zones{OFK_ZONES_OFF, 48, 3, 20, 30, OFK_ZONE_MAX};
     c->camera = ofk_camera{OFK_CAMERA_OFF, 20, 1.0, 1.0, 0.0, 0.0, {0, 0, 0, 0, 0, 0, 0, 0}, 1.0, 1.0, 0.0, 0.0};
     c->rs = ofk_rshutter{OFK_RS_OFF, 0, 0.0, 0.5, 1.0};
@@ -206,7 +207,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     for (int k = 0; k < 2; ++k) { if (c->bgr[k]) hipFree(c->bgr[k]); if (c->pyr[k]) hipFree(c->pyr[k]); }
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
-                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec, c->joint_rec,
+                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec, c->joint_rec, c->plane_rec,
                     c->zone_tab, c->pts_prev_u};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
@@ -1140,8 +1141,64 @@ extern "C" int ofk_joint_download(ofk_ctx *c, double *joint)
     return OFK_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ plane setting
+static int check_plane(ofk_ctx *c, const ofk_plane *v, const char *who)
+{
+    if (v->mode != OFK_PLANE_OFF && v->mode != OFK_PLANE_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_PLANE_OFF nor OFK_PLANE_ON", who, v->mode);
+    if (!(std::isfinite(v->sigma_flow) && v->sigma_flow > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: sigma_flow %g is not finite or not positive", who, v->sigma_flow);
+    if (!(v->sigma_normal >= 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: sigma_normal is negative or NaN (%g)", who, v->sigma_normal);
+    if (!(v->sigma_max > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: sigma_max is not positive or NaN (%g)", who, v->sigma_max);
+    const double bb = v->beam[0] * v->beam[0] + v->beam[1] * v->beam[1] + v->beam[2] * v->beam[2];
+    if (!(std::isfinite(v->beam[0]) && std::isfinite(v->beam[1]) && std::isfinite(v->beam[2]) && std::isfinite(bb) && bb > 0.0))
+        return ofk_fail(c, OFK_E_INVALID, "%s: the beam (%g, %g, %g) has no length or is not finite", who, v->beam[0], v->beam[1], v->beam[2]);
+    if (v->iters < 1 || v->iters > 16) return ofk_fail(c, OFK_E_INVALID, "%s: iters %d is outside 1..16", who, v->iters);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_plane(ofk_ctx *c, const ofk_plane *v)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!v) { c->plane.mode = OFK_PLANE_OFF; return OFK_OK; }
+    TRY(check_plane(c, v, "ofk_set_plane"));
+    c->plane = *v;
+    return OFK_OK;
+}
+
+extern "C" int ofk_get_plane(const ofk_ctx *c, ofk_plane *v)
+{
+    if (!c || !v) return OFK_E_INVALID;
+    *v = c->plane;
+    return OFK_OK;
+}
+
+// The runs' and steps' own refusals with the setting on (ofk.h); allocates the rows on first use.
+static int plane_prepare(ofk_ctx *c, int B, int variant, const char *who)
+{
+    if (c->plane.mode == OFK_PLANE_OFF) return OFK_OK;
+    if (c->cov.mode != OFK_COV_OFF || c->joint.mode != OFK_JOINT_OFF)
+        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_plane is on beside %s: both take the normal as an input, not an estimate", who,
+                        c->cov.mode != OFK_COV_OFF ? "ofk_set_cov" : "ofk_set_joint");
+    if (variant == OFK_SOLVE_OFMODULE)
+        return ofk_fail(c, OFK_E_INVALID, "%s: OFK_SOLVE_OFMODULE is not the sensor model: no plane solve (ofk_set_plane is on)", who);
+    if (!c->plane_rec) OFK_HIP(c, hipMalloc((void **)&c->plane_rec, (size_t)c->max_batch * OFK_PLANE_DOUBLES * 8));
+    c->plane_batch = B;
+    return OFK_OK;
+}
+
+extern "C" int ofk_plane_download(ofk_ctx *c, double *plane)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->plane_batch < 1 || !c->plane_rec) return ofk_fail(c, OFK_E_INVALID, "ofk_plane_download: no run or step with ofk_set_plane on yet");
+    if (!plane) return ofk_fail(c, OFK_E_INVALID, "ofk_plane_download: NULL buffer");
+    TRY(enter(c));
+    OFK_HIP(c, hipMemcpyAsync(plane, c->plane_rec, (size_t)c->plane_batch * OFK_PLANE_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
 // The solve of nb pairs from pair b0 on (their views' pointers): the plain kernels, or with ofk_set_robust on the robust ones; with
-// ofk_set_cov on the covariance kernel behind either, with ofk_set_joint on the joint kernel (the callers refuse both at once).
+// ofk_set_cov on the covariance kernel behind either, with ofk_set_joint on the joint kernel, with ofk_set_plane on the
+// plane kernel (the callers refuse any two of the three at once).
 // drop_status: the stream steps' keep flags (cleared for zero-weight points when the setting asks for it), NULL for frame pairs.
 static void solve_pairs(ofk_ctx *c, hipStream_t st, const float *pts_prev, const float *pts_next, uint8_t *status, const int *counts,
                         const double *sensors, const ofk_params *p, const int *cand_count, double *records, int b0, int nb, bool stream)
@@ -1156,6 +1213,9 @@ static void solve_pairs(ofk_ctx *c, hipStream_t st, const float *pts_prev, const
         if (c->joint.mode != OFK_JOINT_OFF)
             ofk_launch_pairs_joint(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
                                    nullptr, &c->joint, records, c->joint_rec + (size_t)b0 * OFK_JOINT_DOUBLES, nb);
+        if (c->plane.mode != OFK_PLANE_OFF)
+            ofk_launch_pairs_plane(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
+                                   nullptr, &c->plane, records, c->plane_rec + (size_t)b0 * OFK_PLANE_DOUBLES, nb);
         return;
     }
     ofk_launch_pairs_robust(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
@@ -1167,6 +1227,9 @@ static void solve_pairs(ofk_ctx *c, hipStream_t st, const float *pts_prev, const
     if (c->joint.mode != OFK_JOINT_OFF)
         ofk_launch_pairs_joint(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
                                c->rob_w + o, &c->joint, records, c->joint_rec + (size_t)b0 * OFK_JOINT_DOUBLES, nb);
+    if (c->plane.mode != OFK_PLANE_OFF)
+        ofk_launch_pairs_plane(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
+                               c->rob_w + o, &c->plane, records, c->plane_rec + (size_t)b0 * OFK_PLANE_DOUBLES, nb);
 }
 
 extern "C" int ofk_robust_download(ofk_ctx *c, double *weights, int stride, double *stats)
@@ -1441,6 +1504,42 @@ extern "C" int ofk_velocity_solve_joint(ofk_ctx *c, int variant, const double *x
     ofk_launch_joint_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, dwts, jv, dout, djr);
     TRY(check_launch(c, "k_joint_solve"));
     TRY(get(c, joint, djr, (size_t)batch * OFK_JOINT_DOUBLES * 8));
+    return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
+}
+
+extern "C" int ofk_velocity_solve_plane(ofk_ctx *c, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                                        const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
+                                        const ofk_robust *r, const ofk_plane *jv, double *out, double *plane)
+{
+    if (!c || !x || !u || !nrm || !out || !plane || !jv || batch < 1 || n < 1 || n > 4096 || variant < 0 || variant > 2)
+        return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_plane: bad argument");
+    if (variant == OFK_SOLVE_OFMODULE) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_plane: OFK_SOLVE_OFMODULE is not the sensor model: no plane solve");
+    if (!d || !omega) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_plane: missing input for variant %d", variant);
+    if (wgt) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_plane: wgt must be NULL (the argument is there for the solve entries' signature; the weights are the robust setting's)");
+    TRY(check_plane(c, jv, "ofk_velocity_solve_plane"));
+    if (jv->mode != OFK_PLANE_ON) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_plane: mode must be OFK_PLANE_ON");
+    const bool rob = r && r->loss != OFK_ROBUST_OFF;
+    if (rob) TRY(check_robust(c, r, "ofk_velocity_solve_plane"));
+    const size_t pb = (size_t)batch * n * 16, wb = (size_t)batch * n * 8;
+    Bump bp;
+    TRY(est_begin(c, 2 * pb + (size_t)batch * n * 9 + 9 * wb + (size_t)batch * 256 * 11, bp));
+    double *dx = bp.put(x, pb), *du = bp.put(u, pb);
+    uint8_t *dval = (uint8_t *)bp.put(valid, (size_t)batch * n);
+    double *dd = bp.put(d, batch * 8), *dn = bp.put(nrm, batch * 24), *dom = bp.put(omega, batch * 24), *dt = bp.put(t, batch * 24),
+           *dout = bp.take((size_t)batch * OFK_SOLVE_DOUBLES * 8), *djr = bp.take((size_t)batch * OFK_PLANE_DOUBLES * 8), *dwts = nullptr;
+    if (rob) {
+        double *dwork = bp.take(7 * wb);
+        dwts = bp.take(wb);
+        double *dtmp = bp.take(wb), *dst = bp.take((size_t)batch * OFK_ROBUST_DOUBLES * 8);
+        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_plane: upload failed");
+        ofk_launch_solve_robust(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, r, dwork, dwts, dtmp, dst, dout);
+    } else {
+        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_plane: upload failed");
+        ofk_launch_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, dout);
+    }
+    ofk_launch_plane_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, dwts, jv, dout, djr);
+    TRY(check_launch(c, "k_plane_solve"));
+    TRY(get(c, plane, djr, (size_t)batch * OFK_PLANE_DOUBLES * 8));
     return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
 }
 
@@ -1810,6 +1909,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
     if (c->cov.mode != OFK_COV_OFF) { TRY(cov_alloc(c)); c->cov_batch = B; }
     TRY(joint_prepare(c, B, "ofk_pairs_run"));
+    TRY(plane_prepare(c, B, p->solve_variant, "ofk_pairs_run"));
     TRY(camera_prepare(c, B));
     const bool cam = camera_on(c) || rs_on(c);                   // the solve stage reads the ideal / corrected points
     TRY(need_streams(c, S, overlap));
@@ -2327,7 +2427,11 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused: OFK_SOLVE_OFMODULE / OFK_FLOW_ROTATIONAL / OFK_KEEP_LEGACY are not the sensor model: no joint solve (ofk_set_joint is on)");
     if (cov_on) { TRY(cov_alloc(c)); c->cov_batch = B; }
     TRY(joint_prepare(c, B, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
-    const int defer = (cov_on || joint_on) && fu && fu->filter ? 1 : 0;   // the covariance / joint kernel corrects
+    const bool plane_on = c->plane.mode != OFK_PLANE_OFF;
+    if (plane_on && fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY))
+        return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused: OFK_FLOW_ROTATIONAL / OFK_KEEP_LEGACY are not the sensor model: no plane solve (ofk_set_plane is on)");
+    TRY(plane_prepare(c, B, p->solve_variant, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
+    const int defer = (cov_on || joint_on || plane_on) && fu && fu->filter ? 1 : 0;   // the covariance / joint / plane kernel corrects
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
@@ -2373,6 +2477,10 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         ofk_launch_stream_joint(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm,
                                 c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, c->records, c->fused,
                                 c->robust.loss != OFK_ROBUST_OFF ? c->rob_w : nullptr, &c->joint, c->joint_rec, B, defer);
+    if (plane_on && fu)
+        ofk_launch_stream_plane(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm,
+                                c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, c->records, c->fused,
+                                c->robust.loss != OFK_ROBUST_OFF ? c->rob_w : nullptr, &c->plane, c->plane_rec, B, defer);
     // re-detection for the streams that had few features (node:157-166): mask = discs around the OLD positions, image = OLD frame.
     // The host knows the track counts from the previous call, so the whole branch is skipped when no stream needs it.
     // of_module.py:138 `continue`: a step of the ONE stream that did not solve leaves old_gray / old_pos as they were.  The host has to

@@ -29,6 +29,7 @@ SYMBOLS = (
     "ofk_set_robust", "ofk_get_robust", "ofk_robust_download", "ofk_velocity_solve_robust", "ofk_robust_pairs",
     "ofk_set_cov", "ofk_get_cov", "ofk_cov_download", "ofk_velocity_solve_cov",
     "ofk_set_joint", "ofk_get_joint", "ofk_joint_download", "ofk_velocity_solve_joint",
+    "ofk_set_plane", "ofk_get_plane", "ofk_plane_download", "ofk_velocity_solve_plane",
     "ofk_set_track_gate", "ofk_get_track_gate", "ofk_track_gate_download", "ofk_lk_pyr_fb",
     "ofk_set_corner_grid", "ofk_get_corner_grid", "ofk_corner_grid_download", "ofk_select_corners_grid", "ofk_good_features_grid",
     "ofk_set_zones", "ofk_get_zones", "ofk_zones_step", "ofk_zones_reset", "ofk_zones_download",
@@ -69,6 +70,8 @@ COV_MODES = {"off": COV_OFF, "propagate": COV_PROPAGATE, "residual": COV_RESIDUA
 COV_DOUBLES = 24
 JOINT_OFF, JOINT_ON = 0, 1                               # ofk_set_joint / ofk_velocity_solve_joint
 JOINT_DOUBLES = 32
+PLANE_OFF, PLANE_ON = 0, 1                               # ofk_set_plane / ofk_velocity_solve_plane
+PLANE_DOUBLES = 32
 FB_OFF, FB_PLAIN, FB_SEEDED = 0, 1, 2                    # ofk_set_track_gate / ofk_lk_pyr_fb
 FB_MODES = {"off": FB_OFF, "plain": FB_PLAIN, "seeded": FB_SEEDED}
 GRID_MAX_CELLS = 2048                                   # OFK_GRID_MAX_CELLS: cells of a corner grid over one frame
@@ -144,6 +147,22 @@ def joint_setting(mode=True, sigma_flow=0.2, sigma_omega=None, omega_from_imu=Fa
     the resident paths); sigma_omega None = every axis free (+inf), a scalar or three values (+inf: free, 0: held)."""
     so = np.broadcast_to(np.asarray(np.inf if sigma_omega is None else sigma_omega, np.float64), (3,))
     return Joint(int(mode), float(sigma_flow), (C.c_double * 3)(*so.tolist()), int(bool(omega_from_imu)))
+
+
+class Plane(C.Structure):
+    """ofk_plane (include/ofk.h): the plane solve's setting."""
+    _fields_ = [("mode", C.c_int), ("sigma_flow", C.c_double), ("sigma_normal", C.c_double), ("sigma_max", C.c_double),
+                ("beam", C.c_double * 3), ("iters", C.c_int)]
+
+
+def plane_setting(mode=True, sigma_flow=0.2, sigma_normal=None, sigma_max=0.1, beam=(0.0, 0.0, 1.0), iters=6):
+    """A Plane structure from names: mode True / False (or PLANE_*); sigma_flow in the units of the points the entry takes (pixels in
+    the resident paths); sigma_normal None = the tilt is free (+inf), else the prior's standard deviation in radians (0: held);
+    sigma_max the largest predicted 1 sigma of the normal's angle that is accepted (radians, inf: no gate); beam the range sensor's
+    direction in the camera frame; iters Gauss-Newton steps (1..16)."""
+    b = np.broadcast_to(np.asarray(beam, np.float64), (3,))
+    return Plane(int(mode), float(sigma_flow), float(np.inf if sigma_normal is None else sigma_normal), float(sigma_max),
+                 (C.c_double * 3)(*b.tolist()), int(iters))
 
 
 def cov_matrix(t6):
@@ -375,6 +394,9 @@ def load_library():
         L.ofk_joint_download.argtypes = [vp, vp]
         L.ofk_velocity_solve_joint.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Joint), vp, vp]
         L.ofk_velocity_solve_cov.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Cov), vp, vp]
+        L.ofk_set_plane.argtypes = [vp, C.POINTER(Plane)]; L.ofk_get_plane.argtypes = [vp, C.POINTER(Plane)]
+        L.ofk_plane_download.argtypes = [vp, vp]
+        L.ofk_velocity_solve_plane.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Plane), vp, vp]
         L.ofk_set_track_gate.argtypes = [vp, C.POINTER(TrackGate)]; L.ofk_get_track_gate.argtypes = [vp, C.POINTER(TrackGate)]
         L.ofk_track_gate_download.argtypes = [vp, vp, vp, vp, i, vp]
         L.ofk_set_corner_grid.argtypes = [vp, C.POINTER(CornerGrid)]; L.ofk_get_corner_grid.argtypes = [vp, C.POINTER(CornerGrid)]
@@ -1108,6 +1130,51 @@ class Context:
         rec = np.zeros((self.max_batch, JOINT_DOUBLES), np.float64)
         with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
             self._ck(self._L.ofk_joint_download(self._h, _p(rec)))
+        return rec[:batch].copy()
+
+    def velocity_solve_plane(self, variant, x, u, d=None, nrm=None, omega=None, t=None, valid=None, robust=None, plane=None, **settings):
+        """ofk_velocity_solve_plane: velocity_solve's arguments (NODE or SIM), an optional Robust and the plane setting (a Plane, or
+        plane_setting's keywords).  Returns out [B,8] after the rewrite, plane [B,32] (single problem: [8], [32])."""
+        pv = plane if plane is not None else plane_setting(**settings)
+        x = _arr(x, np.float64); u = _arr(u, np.float64)
+        if u.shape[:-1] != x.shape[:-1] or x.shape[-1] != 2 or u.shape[-1] < 2:
+            raise ValueError(f"velocity_solve_plane: x {x.shape} must be [..., n, 2] and u {u.shape} [..., n, >=2] over the same points")
+        single = x.ndim == 2
+        if single:
+            x = x[None]; u = u[None]
+        B, n, _ = x.shape
+        u = _arr(u[..., :2], np.float64)
+        nrm = _arr(nrm, np.float64, (B, 3))
+        d = _opt(d, np.float64, (B,)); omega = _opt(omega, np.float64, (B, 3)); t = _opt(t, np.float64, (B, 3))
+        valid = _opt(valid, np.uint8, (B, n))
+        out = np.zeros((B, SOLVE_DOUBLES), np.float64); rec = np.zeros((B, PLANE_DOUBLES), np.float64)
+        if not n:                                               # no points: velocity_solve's zeros, nothing attempted
+            rec[:, 0:3] = nrm
+            if d is not None:
+                rec[:, 3] = d
+            rec[:, 10] = 1.0
+            return (out[0], rec[0]) if single else (out, rec)
+        with self._lock:
+            self._ck(self._L.ofk_velocity_solve_plane(self._h, int(variant), _p(x), _p(u), _p(valid), B, n, _p(d), _p(nrm), _p(omega), _p(t),
+                                                      None, C.byref(robust) if robust is not None else None, C.byref(pv), _p(out), _p(rec)))
+        return (out[0], rec[0]) if single else (out, rec)
+
+    def set_plane(self, plane=None, **settings):
+        """ofk_set_plane: a Plane (or plane_setting's keywords); None or mode False switches it off.  Every later pairs_run and stream
+        step refines the ground normal from the flow and rewrites v, the residual and v_uav of its records."""
+        pv = plane if plane is not None or not settings else plane_setting(**settings)
+        self._ck(self._L.ofk_set_plane(self._h, C.byref(pv) if pv is not None else None))
+
+    def get_plane(self):
+        pv = Plane()
+        self._ck(self._L.ofk_get_plane(self._h, C.byref(pv)))
+        return pv
+
+    def plane_download(self, batch):
+        """plane [batch, 32] of the latest run / step with the setting on."""
+        rec = np.zeros((self.max_batch, PLANE_DOUBLES), np.float64)
+        with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
+            self._ck(self._L.ofk_plane_download(self._h, _p(rec)))
         return rec[:batch].copy()
 
     def imu_propagate(self, state, msg):

@@ -119,6 +119,15 @@ class PipelineConfig:
     joint_sigma_flow_px: float = 0.2
     omega_prior: object = None
     omega_prior_from_imu: bool = False
+    # plane solve (ofk.h: ofk_set_plane): the ground normal refined from the flow behind every solve; plane_sigma_flow_px the flow noise
+    # in pixels; normal_prior None (the tilt is free) or its standard deviation in radians (0: held); plane_sigma_max the largest
+    # predicted 1 sigma of the normal's angle that is accepted; range_beam the range sensor's direction in the camera frame
+    plane: bool = False
+    plane_sigma_flow_px: float = 0.2
+    normal_prior: object = None
+    plane_sigma_max: float = 0.1
+    range_beam: tuple = (0.0, 0.0, 1.0)
+    plane_iters: int = 6
     # exclusion zones (ofk.h: ofk_set_zones; streams only): None or "hull"; rejects of the solve stage closer than zone_link pixels
     # per axis form a cluster, one of at least zone_min becomes a zone (its hull grown by zone_radius) that moves with the cluster's
     # mean flow, keeps the re-detection out and lives zone_ttl steps behind its last refresh; at most zone_max zones per stream
@@ -183,6 +192,12 @@ class PipelineConfig:
         if not self.joint:
             return None
         return ofk.joint_setting(True, self.joint_sigma_flow_px, self.omega_prior, self.omega_prior_from_imu)
+
+    def plane_setting(self):
+        """The ofk.Plane structure of this configuration, None when the plane solve is off."""
+        if not self.plane:
+            return None
+        return ofk.plane_setting(True, self.plane_sigma_flow_px, self.normal_prior, self.plane_sigma_max, self.range_beam, self.plane_iters)
 
     def zones_setting(self):
         """The ofk.Zones structure of this configuration, None when the zones are off."""
@@ -337,6 +352,8 @@ class FlowStream:
             self.ctx.set_cov(self.cfg.cov_setting())
         if self.cfg.joint:
             self.ctx.set_joint(self.cfg.joint_setting())
+        if self.cfg.plane:
+            self.ctx.set_plane(self.cfg.plane_setting())
         if self.cfg.zones_setting() is not None:
             self.ctx.set_zones(self.cfg.zones_setting())
         if self.cfg.camera_setting() is not None:
@@ -369,6 +386,12 @@ class FlowStream:
     def corner_grid_stats(self):
         """[batch, 2] int32 of the latest detection (begin or re-detection) with a corner grid on: corners accepted, candidates examined."""
         return self.ctx.corner_grid_stats(self.batch)
+
+    def planes(self):
+        """[batch, 32] plane records (ofk.h: ofk_set_plane) of the latest step with the plane solve on: rec[:, 0:3] is the refined normal,
+        rec[:, 3] the refined distance, rec[:, 4:6] the tilt, rec[:, 10] the flag, rec[:, 14] the predicted 1 sigma of the normal's angle,
+        ofk.cov_matrix(rec[:, 20:26]) C_v."""
+        return self.ctx.plane_download(self.batch)
 
     def rotations(self):
         """[batch, 32] joint records (ofk.h: ofk_set_joint) of the latest step with the joint solve on: rec[:, 0:3] is the refined omega,
@@ -435,6 +458,8 @@ class FlowPipeline:
             self.ctx.set_cov(self.cfg.cov_setting())
         if self.cfg.joint:
             self.ctx.set_joint(self.cfg.joint_setting())
+        if self.cfg.plane:
+            self.ctx.set_plane(self.cfg.plane_setting())
         if self.cfg.camera_setting() is not None:
             self.ctx.set_camera(self.cfg.camera_setting())
         if self.cfg.rolling_shutter_setting() is not None:
@@ -485,6 +510,10 @@ class FlowPipeline:
     def corner_grid_stats(self):
         """[batch, 2] int32 of the latest run with a corner grid on: corners accepted, candidates examined."""
         return self.ctx.corner_grid_stats(self.batch)
+
+    def planes(self):
+        """[batch, 32] plane records (ofk.h: ofk_set_plane) of the latest run with the plane solve on (see FlowStream.planes)."""
+        return self.ctx.plane_download(self.batch)
 
     def rotations(self):
         """[batch, 32] joint records (ofk.h: ofk_set_joint) of the latest run with the joint solve on (see FlowStream.rotations)."""

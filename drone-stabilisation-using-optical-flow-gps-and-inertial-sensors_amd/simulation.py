@@ -60,6 +60,18 @@ def solve_lgs_joint(x, u, d, n, omega, t, sigma_flow, sigma_omega=None):
     return out[:3].copy(), R, out[5:8].copy(), jr[0:3].copy(), jr
 
 
+def solve_lgs_plane(x, u, d, n, omega, t, sigma_flow, sigma_normal=None, **settings):
+    """solve_lgs with the ground normal refined from the flow (ofk.h: ofk_velocity_solve_plane).  sigma_flow: the flow noise in the
+    units of x and u; sigma_normal: None (the tilt is free) or the prior's standard deviation in radians (0: held); settings:
+    sigma_max, beam, iters of ofk.plane_setting.
+    Returns (v - omega x t, R, s, n_hat, d_hat, plane [32]); plane[10] != 0 where the plain result stands."""
+    x = np.asarray(x, np.float64)
+    out, pr = ofk.default_context().velocity_solve_plane(ofk.SOLVE_SIM, x[:, :2], np.asarray(u, np.float64)[:, :2], d=float(np.ravel(d)[0]),
+                                                         nrm=n, omega=omega, t=t, sigma_flow=sigma_flow, sigma_normal=sigma_normal, **settings)
+    R = np.array([out[3]]) if (int(out[4]) == 3 and 3 * len(x) > 3) else np.empty(0)
+    return out[:3].copy(), R, out[5:8].copy(), pr[0:3].copy(), float(pr[3]), pr
+
+
 def feasibility(position, linear_velocity, flow, angular_velocity, translation, normal):
     r, length = ofk.default_context().feasibility(ofk.FEAS_SIM, np.asarray(position, np.float64)[:, :2],
                                                   np.asarray(flow, np.float64)[:, :2], normal, linear_velocity,

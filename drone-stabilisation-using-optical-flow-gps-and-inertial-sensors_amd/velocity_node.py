@@ -97,6 +97,20 @@ def solve_lgs_joint(x, u, d, n, omega, sigma_flow, sigma_omega=None):
     return out[:3].copy(), R, rank, out[5:8].copy(), jr[0:3].copy(), jr
 
 
+def solve_lgs_plane(x, u, d, n, omega, sigma_flow, sigma_normal=None, **settings):
+    """solve_lgs with the ground normal refined from the flow (ofk.h: ofk_velocity_solve_plane): velocity and the plane's tilt from
+    one 5-unknown Gauss-Newton iteration, the range along the beam held.  sigma_flow: the flow noise in the units of x and u;
+    sigma_normal: None (the tilt is free) or the prior's standard deviation in radians (0: held); settings: sigma_max, beam, iters of
+    ofk.plane_setting.
+    Returns (v, R, rank, s, n_hat, d_hat, plane [32]); plane[10] != 0 where the plane solve left the plain result alone."""
+    x = np.asarray(x, np.float64); u = np.asarray(u, np.float64)
+    out, pr = ofk.default_context().velocity_solve_plane(ofk.SOLVE_NODE, x[:, :2], u[:, :2], d=float(d), nrm=n, omega=omega,
+                                                         sigma_flow=sigma_flow, sigma_normal=sigma_normal, **settings)
+    rank = int(out[4])
+    R = np.array([out[3]]) if (rank == 3 and 3 * len(x) > 3) else np.empty(0)
+    return out[:3].copy(), R, rank, out[5:8].copy(), pr[0:3].copy(), float(pr[3]), pr
+
+
 def feasible(x, v, omega, T, u, d, n):
     """node:44-50 (reference not executable: uses v_cr/u_cr before definition, returns nothing).  The evident
     intent — parallelity and distance of each point given the lever-arm corrected velocity — is returned."""
@@ -120,6 +134,7 @@ class optical_fusion:
     _corner_grid = {}                                            # PipelineConfig's grid_cell / grid_cap / grid_max_rank; empty: no grid
     _cov = {}                                                    # PipelineConfig's covariance fields (cov, sigma_*, ...); empty: no covariance
     _joint = {}                                                  # PipelineConfig's joint fields (joint, joint_sigma_flow_px, omega_prior, ...); empty: the gyro is taken as exact
+    _plane = {}                                                  # PipelineConfig's plane fields (plane, plane_sigma_flow_px, normal_prior, ...); empty: the normal is taken as exact
     _zones = {}                                                  # PipelineConfig's zones / zone_* fields; empty: no exclusion zones
     _camera = {}                                                 # PipelineConfig's camera field; empty: the points are taken as ideal pinhole samples
     _rolling_shutter = {}                                        # PipelineConfig's rolling_shutter field; empty: every row is taken as exposed at the time stamp
@@ -277,7 +292,7 @@ class optical_fusion:
                                  min_distance=float(self.feature_params["minDistance"]), block_size=int(self.feature_params["blockSize"]),
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
-                                 **self._cov, **self._joint, **self._zones, **self._camera, **self._rolling_shutter)
+                                 **self._cov, **self._joint, **self._plane, **self._zones, **self._camera, **self._rolling_shutter)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -317,6 +332,8 @@ class optical_fusion:
                 self.vel_err = np.sqrt(np.maximum(cv[[6, 9, 11]], 0.0))
         if self._joint and r[15]:
             self.last_joint = fs.rotations()[0]
+        if self._plane and r[15]:
+            self.last_plane = fs.planes()[0]
         self.init = False
         self.got_picture_ = True
 
@@ -376,7 +393,7 @@ class optical_fusion:
             self.vel_err = np.sqrt(np.maximum(np.diag(Rm @ ofk.cov_matrix(cv[6:12]) @ Rm.T), 0.0))
 
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
-                 rolling_shutter=None, joint=None):
+                 rolling_shutter=None, joint=None, plane=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -401,7 +418,11 @@ class optical_fusion:
         omega_gain says so.
         joint: None (the gyro is taken as exact), True, or a dict of sigma_flow_px, omega_prior, omega_prior_from_imu (PipelineConfig's
         joint fields), e.g. dict(sigma_flow_px=0.2, omega_prior=1e-3): every solved step then refines the gyro from the flow and
-        reports the joint velocity (ofk.h: ofk_set_joint); self.last_joint is the record, its slots 0-2 the refined omega."""
+        reports the joint velocity (ofk.h: ofk_set_joint); self.last_joint is the record, its slots 0-2 the refined omega.
+        plane: None (the normal is taken as exact), True, or a dict of sigma_flow_px, normal_prior, sigma_max, range_beam, iters
+        (PipelineConfig's plane fields), e.g. dict(normal_prior=0.05): every solved step then refines the ground normal from the flow
+        and reports the velocity over the refined plane (ofk.h: ofk_set_plane); self.last_plane is the record, its slots 0-2 the
+        refined normal, 3 the refined distance.  Refused beside joint and cov at the first frame."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -427,6 +448,16 @@ class optical_fusion:
         else:
             self._joint = {}
         self.last_joint = None
+        if plane:
+            pl = {} if plane is True else dict(plane)
+            for short, full in (("sigma_flow_px", "plane_sigma_flow_px"), ("sigma_max", "plane_sigma_max"), ("iters", "plane_iters")):
+                if short in pl:
+                    pl[full] = pl.pop(short)
+            self._plane = dict(plane=True, **pl)
+            PipelineConfig(**self._plane).plane_setting()        # unknown or invalid keywords fail here, not at the first frame
+        else:
+            self._plane = {}
+        self.last_plane = None
         z = dict(zones or {})
         if zones is not None:
             ofk.zones_setting(**z)                               # unknown or invalid keywords fail here, not at the first frame

@@ -611,6 +611,74 @@ int ofk_velocity_solve_joint(ofk_ctx *ctx, int variant, const double *x, const d
                              const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
                              const ofk_robust *r, const ofk_joint *j, double *out, double *joint);
 
+/* The plane solve: the ground normal refined from the flow.  Every solve of the library - plain, robust, joint, the covariance, the
+ * feasibility rule - takes the plane's normal as exact: the IMU's R [0,0,1], under ofk_fusion.use_imu the resident IMU state's, so
+ * level ground is assumed.  A normal that is off is a common-mode error no residual sees (ofk_cov's sigma_normal only books it); the
+ * flow itself determines it.  Off by default; with it off every entry point launches the kernels and returns the bits it always did,
+ * with no allocation and no launch.  All arithmetic is f64.
+ * Point set: the kept points are exactly the solve's - gated status / valid / pair feasibility keep, and behind a robust run those of
+ * final weight w > 0, w used as the weight and held fixed (the weights, the feasibility keep, the LK seed, the camera model and the
+ * rolling-shutter correction go on reading the sensors' normal).
+ * Model: with p = (x, y, 1), X = [p]x, N = X^T X, the solve's per-point terms q = (u, 0) + p x omega, sA, sB at the sensors' normal n0
+ * and distance d0, and m = n / d the plane's inverse-distance vector, point i's three rows are
+ *   r_i = sB_i [ (m.p_i) X_i v - X_i q_i ];
+ * at m0 = n0 / d0 these are the solve's rows sA X v - sB X q, for NODE and for SIM.  The rows are bilinear in (v, m) and (s m, v / s)
+ * is a gauge freedom, which the range sensor fixes: it measured a range along the body-fixed beam e (`beam`, normalised here; default
+ * the optical axis), so m.e = (n0.e) / d0 is held and m = m0 + T tau, tau in R^2, T = [t1 t2], t1 = normalize(e x a) with a the
+ * coordinate axis of smallest |e_k| (lowest index on a tie), t2 = e x t1.  The unknowns are (v, tau).  The prior on the tilt is
+ * isotropic, tau ~ N(0, (sigma_normal / d0)^2 I), sigma_normal in radians, and enters as Lambda = (d0^2 sigma_f / sigma_normal)^2 I;
+ * sigma_f is sigma_flow in the units of the points: scaled units in ofk_velocity_solve_plane, pixels x `scaling` (sensor slot 19) in
+ * the resident paths.  sigma_normal = +inf leaves the tilt free; 0 holds it: nothing is estimated, every record is bit-identical to
+ * the setting off (the plane record reports flag 0, tau = 0 and C_v = (d0 sigma_f)^2 M^-1).
+ * Iteration: Gauss-Newton from the solve's v (read from the record) and tau = 0, iters + 1 walks over the kept points (iters 1..16).
+ * Each walk sums at the current (v, tau), with c = m.p, a = sB c (first walk: a = sA, the solve's own rows), h = T^T p, y = X v:
+ *   M = sum w a^2 N (6; the first walk's is the solve's own matrix in its order)   K = sum w sB a (X^T y) h^T (6)
+ *   D = sum w sB^2 |y|^2 h h^T (3)   g_v = -sum w a X^T r (3)   g_tau = -sum w sB (y.r) h (2)   sum w |r|^2 and the count
+ * 22 sums, added over four virtual waves as (s0 + s1) + (s2 + s3), so records are bit-identical across launch forms (one wave per
+ * pair from 128 pairs per slice on, a 256-thread workgroup below), slice counts and overlap settings.  After walks 0 .. iters-1 the
+ * step is taken by the Schur complement: S = D + Lambda - K^T M^-1 K (2 x 2), dtau = S^-1 (g_tau - Lambda tau - K^T M^-1 g_v),
+ * dv = M^-1 (g_v - K dtau); M^-1 from the cyclic Jacobi the solve uses, S^-1 in closed form from its eigen-decomposition.  The last
+ * walk does not step: it gives the residual at the solution and the Hessian there.
+ * Flags (plane record slot 10); with a flag other than 0 the record / out is untouched and slots 0-3 report n0, d0:
+ *   0 success.
+ *   1 not attempted: the solve did not solve (rank < 3; in the stream steps record[15] == 0), `scaling` == 0, d0 == 0 or n0.e == 0, or
+ *     any sum or result is not finite.
+ *   2 unobservable: a walk's S has an eigenvalue that is not positive, or the predicted 1 sigma of the normal's angle,
+ *     d0 sqrt(lambda_max((d0 sigma_f)^2 S^-1)) of the last walk, exceeds sigma_max (radians; +inf disables the gate).  This is what
+ *     stops a hover: the information about tau scales with |v|^2, which is why the threshold is absolute.
+ *   3 rejected: the final objective sum w |r|^2 + tau^T Lambda tau is larger than the first walk's.
+ * On flag 0 with the tilt estimated: record / out fields 0-2 become v (the stage entry takes omega x t off when t is given); field 3
+ * the last walk's sum w |r|^2, without the prior term; record fields 8-10 become R (v - omega x offset).  Everything else stays.
+ * Plane record, OFK_PLANE_DOUBLES per problem: 0-2 n^ = m^ / |m^|; 3 d^ = 1 / |m^|; 4-5 tau; 6-8 fields 0-2 of the solve's record
+ * before; 9 its residual before; 10 flag; 11 kept points; 12-13 eigenvalues of the last S formed, descending; 14 predicted 1 sigma
+ * of the angle; 15 angle between n^ and n0; 16 |last step| = sqrt(|dv|^2 + d0^2 |dtau|^2) over |v|; 17-19 C_tau = (d0 sigma_f)^2 S^-1,
+ * upper triangle; 20-25 C_v = (d0 sigma_f)^2 (M^-1 + G S^-1 G^T), G = M^-1 K, upper triangle (xx xy xz yy yz zz); 26 the first walk's
+ * objective; 27 the final objective; 28-31 reserved, 0.  With a flag set 4-5 and 14-25 are 0.
+ * ofk_set_plane (NULL or mode OFK_PLANE_OFF: off) is a context setting read by ofk_pairs_run (every slice), ofk_stream_step[_jpeg] and
+ * ofk_stream_step_fused[_jpeg]; ofk_pairs_filter_step behind such a run reads the rewritten records.  In the fused step with a filter
+ * the fuse kernel leaves the filter at its prediction and the plane kernel behind it corrects with the refined v / v_uav, rewrites
+ * fused[0..7] and repeats vel_overwrite; under use_imu n0, omega and R are the IMU state's.  OFK_IMU_STATE carries the normal but no
+ * variance of it (vel, times, rotation, normal, ang, ang_err), so there is no normal_from_imu field: the prior is sigma_normal.
+ * Refused with OFK_E_INVALID before any launch, the previous setting staying in place: an unknown mode; sigma_flow not finite or <= 0;
+ * sigma_normal negative or NaN; sigma_max <= 0 or NaN; a beam of zero length or not finite; iters outside 1..16.  Refused with
+ * OFK_E_INVALID by the runs and steps where the setting is on: OFK_SOLVE_OFMODULE, OFK_FLOW_ROTATIONAL and OFK_KEEP_LEGACY (not the
+ * sensor model), and ofk_set_joint or ofk_set_cov together with this one (both take the normal as an input).
+ * ofk_plane_download: plane [batch][OFK_PLANE_DOUBLES] of the latest run / step with the setting on (`batch` is that run's own);
+ * OFK_E_INVALID before such a run.
+ * ofk_velocity_solve_plane = ofk_velocity_solve_joint's arguments with the plane setting (mode OFK_PLANE_ON) in the joint setting's
+ * place; out as ofk_velocity_solve after the rewrite, plane [batch][OFK_PLANE_DOUBLES].  wgt is there for the solve entries' common
+ * signature alone and must be NULL (OFK_E_INVALID otherwise): the only weights the plane solve takes are the robust setting's. */
+#define OFK_PLANE_OFF 0
+#define OFK_PLANE_ON 1
+#define OFK_PLANE_DOUBLES 32
+typedef struct ofk_plane { int mode; double sigma_flow; double sigma_normal; double sigma_max; double beam[3]; int iters; } ofk_plane;
+int ofk_set_plane(ofk_ctx *ctx, const ofk_plane *p);
+int ofk_get_plane(const ofk_ctx *ctx, ofk_plane *p);
+int ofk_plane_download(ofk_ctx *ctx, double *plane);
+int ofk_velocity_solve_plane(ofk_ctx *ctx, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                             const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
+                             const ofk_robust *r, const ofk_plane *p, double *out, double *plane);
+
 /* optical_fusion.call_imu — node:61-89, batched over independent IMU streams, one message each.
  * state [batch][OFK_IMU_STATE]: vel[3], old_time, time_zero, first(0/1), rotation[9], normal[3], ang[3], ang_err[3]
  * msg   [batch][OFK_IMU_MSG]  : secs, nsecs, qx,qy,qz,qw, wx,wy,wz, cov0,cov4,cov8, ax,ay,az */
