@@ -9,9 +9,10 @@
 // before it writes it.
 
 struct rs_xy { double x, y; };
+struct rs_xyz { double X, Y, Z; };
 
-// the exact rotation of P = (x, y, 1) by phi = -t * omega, projected back: where the rotation had the point t frame intervals earlier
-__device__ __forceinline__ rs_xy rs_rotate(double x, double y, double t, double o0, double o1, double o2)
+// the exact rotation of P = (x, y, 1) by phi = -t * omega (Rodrigues), before the projection; k_finite.inc reads Z
+__device__ __forceinline__ rs_xyz rs_rotate3(double x, double y, double t, double o0, double o1, double o2)
 {
     const double p0 = -t * o0, p1 = -t * o1, p2 = -t * o2;
     const double th2 = p0 * p0 + p1 * p1 + p2 * p2;
@@ -24,7 +25,14 @@ __device__ __forceinline__ rs_xy rs_rotate(double x, double y, double t, double 
     const double c0 = p1 - p2 * y, c1 = p2 * x - p0, c2 = p0 * y - p1 * x;                       // phi x P
     const double d0 = p1 * c2 - p2 * c1, d1 = p2 * c0 - p0 * c2, d2 = p0 * c1 - p1 * c0;          // phi x (phi x P)
     const double X = x + A * c0 + B * d0, Y = y + A * c1 + B * d1, Z = 1.0 + A * c2 + B * d2;
-    return {X / Z, Y / Z};
+    return {X, Y, Z};
+}
+
+// projected back: where the rotation had the point t frame intervals earlier
+__device__ __forceinline__ rs_xy rs_rotate(double x, double y, double t, double o0, double o1, double o2)
+{
+    const rs_xyz r = rs_rotate3(x, y, t, o0, o1, o2);
+    return {r.X / r.Z, r.Y / r.Z};
 }
 
 template <int MODE>

@@ -197,3 +197,4 @@ void ofk_launch_track_gate(hipStream_t s, const float *prev_pts, const float *ba
 #include "k_zones.inc"
 #include "k_camera.inc"
 #include "k_rshutter.inc"
+#include "k_finite.inc"

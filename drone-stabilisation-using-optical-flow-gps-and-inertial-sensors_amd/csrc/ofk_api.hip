@@ -155,6 +155,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->zones = ofk_zones{OFK_ZONES_OFF, 48, 3, 20, 30, OFK_ZONE_MAX};
     c->camera = ofk_camera{OFK_CAMERA_OFF, 20, 1.0, 1.0, 0.0, 0.0, {0, 0, 0, 0, 0, 0, 0, 0}, 1.0, 1.0, 0.0, 0.0};
     c->rs = ofk_rshutter{OFK_RS_OFF, 0, 0.0, 0.5, 1.0};
+    c->fm = ofk_finite_motion{OFK_FM_OFF, 0.1};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -763,12 +764,50 @@ extern "C" int ofk_get_rolling_shutter(const ofk_ctx *c, ofk_rshutter *r)
     return OFK_OK;
 }
 
-// the solve stage's own points (the camera's ideal pixels, the rolling shutter's corrected ones, or both): their resident buffers,
-// allocated when a run first needs them; `batch`: the run's images, for ofk_camera_download / ofk_rs_download
+// ------------------------------------------------------------------------------------------------ finite-motion setting
+static bool fm_on(const ofk_ctx *c) { return c->fm.mode != OFK_FM_OFF; }
+
+static int check_fm(ofk_ctx *c, const ofk_finite_motion *f, const char *who)
+{
+    if (f->mode != OFK_FM_EXACT) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is not OFK_FM_EXACT", who, f->mode);
+    if (!std::isfinite(f->min_depth) || !(f->min_depth > 0.0) || f->min_depth > 1.0)
+        return ofk_fail(c, OFK_E_INVALID, "%s: min_depth %g outside (0, 1]", who, f->min_depth);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_finite_motion(ofk_ctx *c, const ofk_finite_motion *f)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!f || f->mode == OFK_FM_OFF) { c->fm.mode = OFK_FM_OFF; return OFK_OK; }
+    TRY(check_fm(c, f, "ofk_set_finite_motion"));
+    c->fm = *f;
+    return OFK_OK;
+}
+
+extern "C" int ofk_get_finite_motion(const ofk_ctx *c, ofk_finite_motion *f)
+{
+    if (!c || !f) return OFK_E_INVALID;
+    *f = c->fm;
+    return OFK_OK;
+}
+
+// The fused steps' own refusals with the setting on (ofk.h): the rewrite is of the sensor model's rows.
+static int fm_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const char *who)
+{
+    if (!fm_on(c)) return OFK_OK;
+    if (variant == OFK_SOLVE_OFMODULE || (fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY)))
+        return ofk_fail(c, OFK_E_INVALID, "%s: OFK_SOLVE_OFMODULE / OFK_FLOW_ROTATIONAL / OFK_KEEP_LEGACY are not the sensor model: no finite motion (ofk_set_finite_motion is on)", who);
+    return OFK_OK;
+}
+
+// the solve stage's own points (the camera's ideal pixels, the rolling shutter's corrected ones, the finite motion's rewritten ones, or
+// any of them in turn): their resident buffers, allocated when a run first needs them; `batch`: the run's images, for
+// ofk_camera_download / ofk_rs_download / ofk_finite_download
 static int camera_prepare(ofk_ctx *c, int batch)
 {
     if (rs_on(c)) c->rs_batch = batch;
-    if (!camera_on(c) && !rs_on(c)) return OFK_OK;
+    if (fm_on(c)) c->fm_batch = batch;
+    if (!camera_on(c) && !rs_on(c) && !fm_on(c)) return OFK_OK;
     if (!c->pts_prev_u) {                                        // one allocation, carved into the two buffers
         const size_t np = (size_t)c->max_batch * c->max_pts;
         float *base = nullptr;
@@ -807,7 +846,8 @@ static int gate_tracks(ofk_ctx *c, hipStream_t s, const View &v, const ofk_level
 // camera_alloc) the sensors speak of the ideal image, so the predictor runs on the ideal points and its seeds are brought back into
 // the image; behind the gates the ideal points of both sets are written for the solve stage - one launch, unless the seed needed
 // the previous points' earlier.  With ofk_set_rolling_shutter on, one k_rs_correct launch follows: it reads the raw rows and the
-// ideal points (the camera's, corrected in place, or the raw points themselves) and writes what the solve stage reads.
+// ideal points (the camera's, corrected in place, or the raw points themselves) and writes what the solve stage reads.  With
+// ofk_set_finite_motion on, one k_finite_correct launch follows that: in place on those buffers, or from the raw points into them.
 static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, const ofk_params *p, const double *imu_state)
 {
     const bool seeded = c->lk_seed_mode != OFK_SEED_OFF, cam = camera_on(c);
@@ -827,6 +867,11 @@ static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv,
         if (r.rows == 0) r.rows = lv.h[0];                       // the frame height of the run
         ofk_launch_rs_correct(s, &r, v.pts_prev, v.pts_next, cam ? v.pts_prev_u : nullptr, cam ? v.pts_next_u : nullptr, v.pts_prev_u, v.pts_next_u,
                               v.counts, c->max_pts, v.sensors, imu_state, v.nb);
+    }
+    if (fm_on(c)) {
+        const bool id = cam || rs_on(c);
+        ofk_launch_finite_correct(s, &c->fm, id ? v.pts_prev_u : v.pts_prev, id ? v.pts_next_u : v.pts_next, v.pts_prev_u, v.pts_next_u, v.counts,
+                                  c->max_pts, v.sensors, imu_state, v.nb);
     }
     return OFK_OK;
 }
@@ -1911,7 +1956,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
     TRY(joint_prepare(c, B, "ofk_pairs_run"));
     TRY(plane_prepare(c, B, p->solve_variant, "ofk_pairs_run"));
     TRY(camera_prepare(c, B));
-    const bool cam = camera_on(c) || rs_on(c);                   // the solve stage reads the ideal / corrected points
+    const bool cam = camera_on(c) || rs_on(c) || fm_on(c);       // the solve stage reads the ideal / corrected / rewritten points
     TRY(need_streams(c, S, overlap));
     if (fork) {
         OFK_HIP(c, hipEventRecord(c->ev_fork, c->stream));
@@ -2103,6 +2148,45 @@ extern "C" int ofk_rs_download(ofk_ctx *c, float *prev, float *next, int stride)
     const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
     if (prev) OFK_HIP(c, hipMemcpy2DAsync(prev, (size_t)stride * 8, c->pts_prev_u, mp * 8, n * 8, c->rs_batch, hipMemcpyDeviceToHost, c->stream));
     if (next) OFK_HIP(c, hipMemcpy2DAsync(next, (size_t)stride * 8, c->pts_next_u, mp * 8, n * 8, c->rs_batch, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ finite-motion stage entries
+// device scratch only, so resident points and settings are not touched; the outputs go up first: entries beyond counts[b] keep their contents
+extern "C" int ofk_finite_correct_points(ofk_ctx *c, const ofk_finite_motion *f, const float *prev, const float *next, const int *counts, int batch,
+                                         int stride, const double *sensors, float *out_prev, float *out_next)
+{
+    const char *who = "ofk_finite_correct_points";
+    if (!c) return OFK_E_INVALID;
+    if (!f || !prev || !next || !counts || !out_prev || !out_next || batch < 1 || stride < 1) return ofk_fail(c, OFK_E_INVALID, "%s: bad argument", who);
+    TRY(check_fm(c, f, who));
+    if (!sensors) return ofk_fail(c, OFK_E_INVALID, "%s: the rewrite needs the sensors", who);
+    for (int b = 0; b < batch; ++b)
+        if (counts[b] < 0 || counts[b] > stride) return ofk_fail(c, OFK_E_INVALID, "%s: counts[%d]=%d outside 0..%d", who, b, counts[b], stride);
+    const size_t pb = (size_t)batch * stride * 8, sb = (size_t)batch * OFK_SENSOR_DOUBLES * 8;
+    Bump bp;
+    TRY(est_begin(c, 4 * pb + sb + (size_t)batch * 4, bp));
+    const float *di0 = (const float *)bp.put(prev, pb), *di1 = (const float *)bp.put(next, pb);
+    float *do0 = (float *)bp.put(out_prev, pb), *do1 = (float *)bp.put(out_next, pb);
+    const double *dsn = bp.put(sensors, sb);
+    const int *dc = (const int *)bp.put(counts, (size_t)batch * 4);
+    if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    ofk_launch_finite_correct(c->stream, f, di0, di1, do0, do1, dc, stride, dsn, nullptr, batch);
+    TRY(check_launch(c, who));
+    OFK_HIP(c, hipMemcpyAsync(out_prev, do0, pb, hipMemcpyDeviceToHost, c->stream));
+    return get(c, out_next, do1, pb);
+}
+
+extern "C" int ofk_finite_download(ofk_ctx *c, float *prev, float *next, int stride)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->fm_batch < 1 || !c->pts_prev_u) return ofk_fail(c, OFK_E_INVALID, "ofk_finite_download: no run or step with ofk_set_finite_motion on yet");
+    if (stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_finite_download: stride %d", stride);
+    TRY(enter(c));
+    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    if (prev) OFK_HIP(c, hipMemcpy2DAsync(prev, (size_t)stride * 8, c->pts_prev_u, mp * 8, n * 8, c->fm_batch, hipMemcpyDeviceToHost, c->stream));
+    if (next) OFK_HIP(c, hipMemcpy2DAsync(next, (size_t)stride * 8, c->pts_next_u, mp * 8, n * 8, c->fm_batch, hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
 }
@@ -2419,6 +2503,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         TRY(filters_alloc(c));
     } else if (p->solve_variant != OFK_SOLVE_NODE && p->solve_variant != OFK_SOLVE_SIM) return ofk_fail(c, OFK_E_INVALID, "solve_variant must be NODE or SIM");
     TRY(check_grid(c, &c->grid, h, w, "ofk_stream_step"));
+    TRY(fm_check_step(c, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     const bool cov_on = c->cov.mode != OFK_COV_OFF;
     if (cov_on && fu && (p->solve_variant == OFK_SOLVE_OFMODULE || fu->flow == OFK_FLOW_ROTATIONAL))
         return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused: OFK_SOLVE_OFMODULE / OFK_FLOW_ROTATIONAL are not the sensor model: no covariance (ofk_set_cov is on)");
@@ -2438,7 +2523,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     const bool zones_on = c->zones.mode != OFK_ZONES_OFF;
     if (zones_on) { TRY(check_zones(c, &c->zones, "ofk_stream_step")); TRY(zones_alloc(c)); }
     TRY(camera_prepare(c, B));
-    const bool cam = camera_on(c) || rs_on(c);                   // the solve stage reads the ideal / corrected points; the tracks, the zones and the
+    const bool cam = camera_on(c) || rs_on(c) || fm_on(c);       // the solve stage reads the ideal / corrected / rewritten points; the tracks, the zones and the
     const float *sp = cam ? c->pts_prev_u : c->pts_prev, *sn = cam ? c->pts_next_u : c->pts_next;   // re-detection stay in the image
     OFK_HIP(c, hipMemcpyAsync(c->sensors, sensors, (size_t)B * OFK_SENSOR_DOUBLES * 8, hipMemcpyHostToDevice, c->stream));
     bool few = false;                                            // the host knows the track counts from the previous call

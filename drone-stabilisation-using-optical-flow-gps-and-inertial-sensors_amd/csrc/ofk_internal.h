@@ -108,6 +108,8 @@ struct ofk_ctx {
     int cam_batch;                           // images of the latest run / step with the camera on (ofk_camera_download), 0 = none
     ofk_rshutter rs;                         // ofk_set_rolling_shutter: mode OFK_RS_OFF unless set; with it on the solve stage reads pts_prev_u / pts_next_u too
     int rs_batch;                            // images of the latest run / step with the rolling shutter on (ofk_rs_download), 0 = none
+    ofk_finite_motion fm;                    // ofk_set_finite_motion: mode OFK_FM_OFF unless set; with it on the solve stage reads pts_prev_u / pts_next_u too
+    int fm_batch;                            // images of the latest run / step with the finite motion on (ofk_finite_download), 0 = none
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -193,6 +195,10 @@ void ofk_launch_camera(hipStream_t s, const ofk_camera *cam, int distort, const 
 // points are the ideal ones; id may be out; rs->rows > 0; sensors may be NULL for OFK_RS_FLOW; imu_state != NULL: its omega
 void ofk_launch_rs_correct(hipStream_t s, const ofk_rshutter *rs, const float *raw0, const float *raw1, const float *id0, const float *id1,
                            float *out0, float *out1, const int *counts, int pts_stride, const double *sensors, const double *imu_state, int batch);
+// the finite motion (ofk.h: ofk_set_finite_motion; k_finite.inc): both ends of every point in ONE launch; out may be in;
+// imu_state != NULL: its normal and omega
+void ofk_launch_finite_correct(hipStream_t s, const ofk_finite_motion *fm, const float *in0, const float *in1, float *out0, float *out1,
+                               const int *counts, int pts_stride, const double *sensors, const double *imu_state, int batch);
 void ofk_launch_lk(hipStream_t s, const uint8_t *prev, const uint8_t *next, size_t pyr_stride, const ofk_levels &lv,
                    const float *prev_pts, const int *counts, int pts_stride, int win, int max_count, double eps,
                    double min_eig_thr, float *next_pts, uint8_t *status, float *err, int batch, int flags = 0);   // flags: OFK_LK_*

@@ -35,6 +35,7 @@ SYMBOLS = (
     "ofk_set_zones", "ofk_get_zones", "ofk_zones_step", "ofk_zones_reset", "ofk_zones_download",
     "ofk_set_camera", "ofk_get_camera", "ofk_undistort_points", "ofk_distort_points", "ofk_camera_download",
     "ofk_set_rolling_shutter", "ofk_get_rolling_shutter", "ofk_rs_correct_points", "ofk_rs_download",
+    "ofk_set_finite_motion", "ofk_get_finite_motion", "ofk_finite_correct_points", "ofk_finite_download",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
     "ofk_stream_begin_jpeg", "ofk_stream_step_jpeg",
@@ -84,6 +85,8 @@ CAMERA_DEFAULT_ITERS = {CAMERA_BROWN: 20, CAMERA_FISHEYE: 10}
 RS_OFF, RS_FLOW, RS_GYRO = 0, 1, 2                       # ofk_set_rolling_shutter / ofk_rs_correct_points
 RS_MODES = {"off": RS_OFF, "flow": RS_FLOW, "gyro": RS_GYRO}
 RS_MAX_ROWS = 65536
+FM_OFF, FM_EXACT = 0, 1                                  # ofk_set_finite_motion / ofk_finite_correct_points
+FM_MODES = {"off": FM_OFF, "exact": FM_EXACT}
 FLOW_LK, FLOW_ROTATIONAL = 0, 1
 KEEP_STATUS, KEEP_LEGACY = 0, 1
 CONTROL_SENSORS, CONTROL_IMU = 0, 1
@@ -315,6 +318,28 @@ def rshutter_setting(mode="gyro", readout=0.0, anchor=0.5, rows=0, omega_gain=1.
     return RShutter(mode, rows, readout, anchor, omega_gain)
 
 
+class FiniteMotion(C.Structure):
+    """ofk_finite_motion (include/ofk.h): the frame pair's finite motion (exact rotation, plane displacement) written into the points
+    in front of the solve stage."""
+    _fields_ = [("mode", C.c_int), ("min_depth", C.c_double)]
+
+
+def finite_motion_setting(mode="exact", min_depth=0.1):
+    """A FiniteMotion structure from names: mode "off" / "exact", or FM_*; min_depth in (0, 1] = the smallest depth (in units of the
+    previous depth) a point may have once the rotation is applied: below it the point keeps its place."""
+    if isinstance(mode, str):
+        if mode not in FM_MODES:
+            raise ValueError(f"finite-motion mode {mode!r} is none of {sorted(FM_MODES)}")
+        mode = FM_MODES[mode]
+    mode = int(mode)
+    if mode not in FM_MODES.values():
+        raise ValueError(f"finite-motion mode {mode} is none of FM_OFF, FM_EXACT")
+    min_depth = float(min_depth)
+    if mode != FM_OFF and not (np.isfinite(min_depth) and 0.0 < min_depth <= 1.0):
+        raise ValueError(f"finite-motion min_depth {min_depth} outside (0, 1]")
+    return FiniteMotion(mode, min_depth)
+
+
 class Fusion(C.Structure):
     """ofk_fusion (include/ofk.h): what ofk_stream_step_fused does between LK and the next frame."""
     _fields_ = [("use_imu", C.c_int), ("flow", C.c_int), ("keep", C.c_int), ("filter", C.c_int), ("control", C.c_int),
@@ -413,6 +438,9 @@ def load_library():
         L.ofk_set_rolling_shutter.argtypes = [vp, C.POINTER(RShutter)]; L.ofk_get_rolling_shutter.argtypes = [vp, C.POINTER(RShutter)]
         L.ofk_rs_correct_points.argtypes = [vp, C.POINTER(RShutter), vp, vp, vp, vp, vp, i, i, vp, vp, vp]
         L.ofk_rs_download.argtypes = [vp, vp, vp, i]
+        L.ofk_set_finite_motion.argtypes = [vp, C.POINTER(FiniteMotion)]; L.ofk_get_finite_motion.argtypes = [vp, C.POINTER(FiniteMotion)]
+        L.ofk_finite_correct_points.argtypes = [vp, C.POINTER(FiniteMotion), vp, vp, vp, i, i, vp, vp, vp]
+        L.ofk_finite_download.argtypes = [vp, vp, vp, i]
         L.ofk_lk_pyr_fb.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, i, vp, vp, vp, C.POINTER(TrackGate), vp, vp, vp]
         L.ofk_imu_propagate.argtypes = [vp, vp, vp, i]
         L.ofk_post_solve.argtypes = [vp, vp, vp, vp, vp, i, vp]
@@ -895,6 +923,51 @@ class Context:
         a = np.zeros((self.max_batch, self.max_pts, 2), np.float32); b = np.zeros_like(a)
         with self._lock:
             self._ck(self._L.ofk_rs_download(self._h, _p(a), _p(b), self.max_pts))
+        return a[:batch].copy(), b[:batch].copy()
+
+    def set_finite_motion(self, finite_motion=None, **settings):
+        """ofk_set_finite_motion: a FiniteMotion (or finite_motion_setting's keywords); None or mode "off" switches it off.  Every
+        later pairs_run and stream step hands its solve stage the points for which the first-order system is the exact relation of
+        the frame pair; the velocity is then the displacement per frame interval.  Everything in the image keeps the raw pixels."""
+        m = finite_motion if finite_motion is not None or not settings else finite_motion_setting(**settings)
+        with self._lock:
+            self._ck(self._L.ofk_set_finite_motion(self._h, C.byref(m) if m is not None else None))
+
+    def get_finite_motion(self):
+        m = FiniteMotion()
+        self._ck(self._L.ofk_get_finite_motion(self._h, C.byref(m)))
+        return m
+
+    def finite_correct_points(self, finite_motion, prev, next, counts=None, sensors=None, out=None):
+        """ofk_finite_correct_points: prev, next [B,S,2] (or [S,2]) f32, the points the solve would otherwise read -> (prev, next)
+        rewritten for the finite motion of sensors [B,28] (normal, omega, scaling, centre).  counts None = every point; entries
+        beyond counts[b] keep what out = (prev, next) holds (zeros without it)."""
+        pp, pn = _arr(prev, np.float32), _arr(next, np.float32)
+        single = pp.ndim == 2
+        if single:
+            pp, pn = pp[None], pn[None]
+        if pp.ndim != 3 or pp.shape[2] != 2 or pn.shape != pp.shape:
+            raise ValueError(f"finite_correct_points: points {pp.shape} / {pn.shape} are not two [B, S, 2] arrays")
+        B, S = pp.shape[:2]
+        counts = _arr(S if counts is None else counts, np.int32, (B,))
+        sn = None if sensors is None else _arr(sensors, np.float64, (B, SENSOR_DOUBLES))
+        if out is None:
+            o0 = np.zeros((B, S, 2), np.float32); o1 = np.zeros((B, S, 2), np.float32)
+        else:
+            o0 = np.array(out[0], np.float32).reshape(B, S, 2); o1 = np.array(out[1], np.float32).reshape(B, S, 2)
+        if S > 0:
+            with self._lock:
+                self._ck(self._L.ofk_finite_correct_points(self._h, C.byref(finite_motion), _p(pp), _p(pn), _p(counts), B, S, _p(sn), _p(o0), _p(o1)))
+        return (o0[0], o1[0]) if single else (o0, o1)
+
+    def finite_download(self, batch):
+        """ofk_finite_download: (prev, next) [batch,max_pts,2] f32, the points the solve stage of the latest run or step with the
+        finite motion on saw.  The library writes that run's rows, so the buffers have max_batch of them."""
+        if not 0 <= int(batch) <= self.max_batch:
+            raise ValueError(f"finite_download: batch {batch} outside 0..{self.max_batch}")
+        a = np.zeros((self.max_batch, self.max_pts, 2), np.float32); b = np.zeros_like(a)
+        with self._lock:
+            self._ck(self._L.ofk_finite_download(self._h, _p(a), _p(b), self.max_pts))
         return a[:batch].copy(), b[:batch].copy()
 
     def track_gate_download(self, batch, points=True):

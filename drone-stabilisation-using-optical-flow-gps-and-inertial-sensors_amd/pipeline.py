@@ -143,6 +143,10 @@ class PipelineConfig:
     # rolling shutter (ofk.h: ofk_set_rolling_shutter): None, or a RollingShutter whose per-row capture time is undone on the device
     # in front of the solve stage
     rolling_shutter: object = None
+    # finite motion (ofk.h: ofk_set_finite_motion): None, True (the defaults) or an ofk.FiniteMotion: the frame pair's exact rotation
+    # and plane displacement are written into the points on the device in front of the solve stage; the velocity is then the
+    # displacement per frame interval
+    finite_motion: object = None
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -218,6 +222,16 @@ class PipelineConfig:
             return None
         m = self.rolling_shutter.setting() if hasattr(self.rolling_shutter, "setting") else self.rolling_shutter
         return None if m.mode == ofk.RS_OFF else m
+
+    def finite_motion_setting(self):
+        """The ofk.FiniteMotion structure of this configuration, None when the finite motion is off."""
+        if self.finite_motion is None or self.finite_motion is False:
+            return None
+        m = ofk.finite_motion_setting() if self.finite_motion is True else self.finite_motion
+        if not isinstance(m, ofk.FiniteMotion):
+            raise ValueError(f"finite_motion {m!r} is neither None, True nor an ofk.FiniteMotion")
+        m = ofk.finite_motion_setting(m.mode, m.min_depth)       # range-checked
+        return None if m.mode == ofk.FM_OFF else m
 
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
@@ -360,6 +374,8 @@ class FlowStream:
             self.ctx.set_camera(self.cfg.camera_setting())
         if self.cfg.rolling_shutter_setting() is not None:
             self.ctx.set_rolling_shutter(self.cfg.rolling_shutter_setting())
+        if self.cfg.finite_motion_setting() is not None:
+            self.ctx.set_finite_motion(self.cfg.finite_motion_setting())
         self.fusion = fusion
         if fusion is not None:                                  # the per-stream filter state lives on the device from here on
             self._fusion = fusion.to_struct()
@@ -409,7 +425,10 @@ class FlowStream:
         return self.ctx.zones_download(self.batch)
 
     def ideal_points(self):
-        """(prev, next) [batch, max_pts, 2] f32: the points the solve stage of the latest step saw (camera model or rolling shutter on)."""
+        """(prev, next) [batch, max_pts, 2] f32: the points the solve stage of the latest step saw (camera model, rolling shutter or
+        finite motion on)."""
+        if self.ctx.get_finite_motion().mode != ofk.FM_OFF:
+            return self.ctx.finite_download(self.batch)
         return self.ctx.rs_download(self.batch) if self.ctx.get_rolling_shutter().mode != ofk.RS_OFF else self.ctx.camera_download(self.batch)
 
     def begin(self, first_bgr):
@@ -464,6 +483,8 @@ class FlowPipeline:
             self.ctx.set_camera(self.cfg.camera_setting())
         if self.cfg.rolling_shutter_setting() is not None:
             self.ctx.set_rolling_shutter(self.cfg.rolling_shutter_setting())
+        if self.cfg.finite_motion_setting() is not None:
+            self.ctx.set_finite_motion(self.cfg.finite_motion_setting())
         if streams > 1:
             self.ctx.set_streams(streams)
 
@@ -524,7 +545,10 @@ class FlowPipeline:
         return self.ctx.cov_download(self.batch)
 
     def ideal_points(self):
-        """(prev, next) [batch, max_pts, 2] f32: the points the solve stage of the latest run saw (camera model or rolling shutter on)."""
+        """(prev, next) [batch, max_pts, 2] f32: the points the solve stage of the latest run saw (camera model, rolling shutter or
+        finite motion on)."""
+        if self.ctx.get_finite_motion().mode != ofk.FM_OFF:
+            return self.ctx.finite_download(self.batch)
         return self.ctx.rs_download(self.batch) if self.ctx.get_rolling_shutter().mode != ofk.RS_OFF else self.ctx.camera_download(self.batch)
 
     def run_async(self):

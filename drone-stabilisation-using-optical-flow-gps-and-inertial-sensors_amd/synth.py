@@ -45,10 +45,28 @@ def make_texture(h, w, seed, sigma=1.8):
     return np.clip(t, 8, 247).astype(np.float32)
 
 
-def pixel_homography(v, omega, d, n, scaling, cx, cy):
-    v = np.asarray(v, np.float64); om = np.asarray(omega, np.float64); n = np.asarray(n, np.float64)
+def rotation_matrix(omega):
+    """exp([omega]x) by Rodrigues' formula (the series' first terms below 1e-8 rad)."""
+    om = np.asarray(omega, np.float64)
     W = np.array([[0, -om[2], om[1]], [om[2], 0, -om[0]], [-om[1], om[0], 0]])
-    Hn = np.eye(3) + W + np.outer(v, n) / d
+    th2 = float(om @ om)
+    A, B = (1.0, 0.5) if th2 < 1e-16 else (np.sin(np.sqrt(th2)) / np.sqrt(th2), (1.0 - np.cos(np.sqrt(th2))) / th2)
+    return np.eye(3) + A * W + B * (W @ W)
+
+
+def pixel_homography(v, omega, d, n, scaling, cx, cy, motion="linear"):
+    """motion "linear" (the default): K (I + [w]x + v n' / d) K^-1, the first-order form of the module's text.  "finite": the frame
+    pair as the rigid motion P1 = R P0 + T it is, K (I + T n' / (d - n.T)) exp([w]x) K^-1, with v read as the displacement T per
+    frame interval and n, d the plane in the NEXT frame's camera axes, as the sensor record carries them (ofk.h:
+    ofk_set_finite_motion)."""
+    v = np.asarray(v, np.float64); om = np.asarray(omega, np.float64); n = np.asarray(n, np.float64)
+    if motion not in ("linear", "finite"):
+        raise ValueError(f"motion {motion!r} is neither 'linear' nor 'finite'")
+    W = np.array([[0, -om[2], om[1]], [om[2], 0, -om[0]], [-om[1], om[0], 0]])
+    if motion == "finite":
+        Hn = (np.eye(3) + np.outer(v, n) / (d - float(n @ v))) @ rotation_matrix(om)
+    else:
+        Hn = np.eye(3) + W + np.outer(v, n) / d
     K = np.array([[1 / scaling, 0, cx], [0, 1 / scaling, cy], [0, 0, 1.0]])
     return K @ Hn @ np.linalg.inv(K)
 
@@ -115,8 +133,10 @@ def _colour(T, T2, ax, ay):
 
 
 def render_pair(h, w, seed, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.003), d=1.0, n=(0, 0, 1), scaling=None,
-                margin=48, camera=None, rolling_shutter=None):
+                margin=48, camera=None, rolling_shutter=None, motion="linear"):
     """Returns dict(prev, next: [h,w,3] uint8 BGR; H: 3x3 pixel homography prev->next; scaling, cx, cy).
+    motion: pixel_homography's ("finite": the exact rigid motion of the pair; not with a rolling shutter, whose rows are rendered
+    through the linearised homography).
     camera (a pipeline.CameraModel, default None): the frames are what that camera sees - every raw pixel is undistorted to the ideal
     pixel it looks at, sent through the homography and sampled bilinearly (the previous frame too, at the ideal pixel itself);
     scaling, cx, cy are then the ideal pinhole's (camera.sensor_slots()) and H lives in ideal pixels.
@@ -124,6 +144,8 @@ def render_pair(h, w, seed, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.00
     t = k + readout * (y / h - anchor) and rendered through the pair's linearised homography at that time,
     K (I + t (W + v n' / d)) K^-1 - pixel_homography's own form with t v, t omega; H stays the global shutter's.  Works behind a
     camera as well (the rows are the raw image's)."""
+    if rolling_shutter is not None and motion != "linear":
+        raise ValueError("render_pair: a rolling shutter is rendered through the linearised homography: motion must be 'linear'")
     if rolling_shutter is not None:
         if camera is not None:
             scaling, cx, cy, xx, yy, margin = _camera_view(h, w, camera, margin)
@@ -146,7 +168,7 @@ def render_pair(h, w, seed, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.00
         scaling, cx, cy, xx, yy, margin = _camera_view(h, w, camera, margin)
         T = make_texture(h + 2 * margin, w + 2 * margin, seed)
         T2 = make_texture(h + 2 * margin, w + 2 * margin, seed + 7919, sigma=3.0)
-        H = pixel_homography(v, omega, d, n, scaling, cx, cy)
+        H = pixel_homography(v, omega, d, n, scaling, cx, cy, motion)
         Hi = np.linalg.inv(H)
         den = Hi[2, 0] * xx + Hi[2, 1] * yy + Hi[2, 2]
         sx = (Hi[0, 0] * xx + Hi[0, 1] * yy + Hi[0, 2]) / den + margin
@@ -161,7 +183,7 @@ def render_pair(h, w, seed, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.00
     cx, cy = w / 2.0, h / 2.0
     T = make_texture(h + 2 * margin, w + 2 * margin, seed)
     T2 = make_texture(h + 2 * margin, w + 2 * margin, seed + 7919, sigma=3.0)
-    H = pixel_homography(v, omega, d, n, scaling, cx, cy)
+    H = pixel_homography(v, omega, d, n, scaling, cx, cy, motion)
     Hi = np.linalg.inv(H)
     yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
     den = Hi[2, 0] * xx + Hi[2, 1] * yy + Hi[2, 2]
@@ -196,8 +218,10 @@ def warp_frame(bgr, H):
 
 
 def render_sequence(h, w, seed, n_frames, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.003), d=1.0, n=(0, 0, 1),
-                    scaling=None, margin=96, camera=None, rolling_shutter=None):
+                    scaling=None, margin=96, camera=None, rolling_shutter=None, motion="linear"):
     """`n_frames` BGR frames of one stream under constant per-frame motion: frame k shows the texture through H^k.
+    motion: pixel_homography's ("finite": every step is the exact rigid motion with the plane n, d in the axes of the step's later
+    frame; not with a rolling shutter).
     Returns (frames [n,h,w,3] uint8, info dict as render_pair).  camera: as in render_pair.  rolling_shutter: as in render_pair, with
     row y of frame k seen through (I + tau G) H^k, tau = readout * (y / h - anchor), G = H - I: the linearised motion over the row
     time behind the k whole steps (I + (k + tau) G itself would drift from H^k with k)."""
@@ -209,7 +233,9 @@ def render_sequence(h, w, seed, n_frames, v=(0.003, -0.002, 0.001), omega=(0.002
         yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
     T = make_texture(h + 2 * margin, w + 2 * margin, seed)
     T2 = make_texture(h + 2 * margin, w + 2 * margin, seed + 7919, sigma=3.0)
-    H = pixel_homography(v, omega, d, n, scaling, cx, cy)
+    if rolling_shutter is not None and motion != "linear":
+        raise ValueError("render_sequence: a rolling shutter is rendered through the linearised homography: motion must be 'linear'")
+    H = pixel_homography(v, omega, d, n, scaling, cx, cy, motion)
     frames = np.empty((n_frames, h, w, 3), np.uint8)
     Hk = np.eye(3)
     tau = None if rolling_shutter is None else _row_times(h, rolling_shutter)

@@ -111,6 +111,14 @@ def solve_lgs_plane(x, u, d, n, omega, sigma_flow, sigma_normal=None, **settings
     return out[:3].copy(), R, rank, out[5:8].copy(), pr[0:3].copy(), float(pr[3]), pr
 
 
+def finite_points(prev, next, sensors, min_depth=0.1):
+    """The finite motion's rewrite of tracked points (ofk.h: ofk_finite_correct_points): prev, next [N,2] (or [B,N,2]) pixels as the
+    solve would read them, sensors [28] (or [B,28]) the record of the next frame (normal, omega per frame interval, scaling, centre).
+    Returns (prev, next) f32 for which solve_lgs' first-order system is the exact relation of the frame pair: its velocity is then
+    the displacement per frame interval."""
+    return ofk.default_context().finite_correct_points(ofk.finite_motion_setting("exact", min_depth), prev, next, sensors=sensors)
+
+
 def feasible(x, v, omega, T, u, d, n):
     """node:44-50 (reference not executable: uses v_cr/u_cr before definition, returns nothing).  The evident
     intent — parallelity and distance of each point given the lever-arm corrected velocity — is returned."""
@@ -137,6 +145,7 @@ class optical_fusion:
     _plane = {}                                                  # PipelineConfig's plane fields (plane, plane_sigma_flow_px, normal_prior, ...); empty: the normal is taken as exact
     _zones = {}                                                  # PipelineConfig's zones / zone_* fields; empty: no exclusion zones
     _camera = {}                                                 # PipelineConfig's camera field; empty: the points are taken as ideal pinhole samples
+    _finite_motion = {}                                          # PipelineConfig's finite_motion field; empty: the solve takes the flow as the instantaneous field
     _rolling_shutter = {}                                        # PipelineConfig's rolling_shutter field; empty: every row is taken as exposed at the time stamp
     feature_params = dict(qualityLevel=0.7, minDistance=10, blockSize=12)
     lk_params = dict(winSize=(15, 15), maxLevel=3, criteria=(cv2.TERM_CRITERIA_EPS | cv2.TERM_CRITERIA_COUNT, 20, 0.03))
@@ -292,7 +301,8 @@ class optical_fusion:
                                  min_distance=float(self.feature_params["minDistance"]), block_size=int(self.feature_params["blockSize"]),
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
-                                 **self._cov, **self._joint, **self._plane, **self._zones, **self._camera, **self._rolling_shutter)
+                                 **self._cov, **self._joint, **self._plane, **self._zones, **self._camera, **self._rolling_shutter,
+                                 **self._finite_motion)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -393,7 +403,7 @@ class optical_fusion:
             self.vel_err = np.sqrt(np.maximum(np.diag(Rm @ ofk.cov_matrix(cv[6:12]) @ Rm.T), 0.0))
 
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
-                 rolling_shutter=None, joint=None, plane=None):
+                 rolling_shutter=None, joint=None, plane=None, finite_motion=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -422,7 +432,11 @@ class optical_fusion:
         plane: None (the normal is taken as exact), True, or a dict of sigma_flow_px, normal_prior, sigma_max, range_beam, iters
         (PipelineConfig's plane fields), e.g. dict(normal_prior=0.05): every solved step then refines the ground normal from the flow
         and reports the velocity over the refined plane (ofk.h: ofk_set_plane); self.last_plane is the record, its slots 0-2 the
-        refined normal, 3 the refined distance.  Refused beside joint and cov at the first frame."""
+        refined normal, 3 the refined distance.  Refused beside joint and cov at the first frame.
+        finite_motion: None (the flow is taken as the instantaneous motion field), True, an ofk.FiniteMotion or a dict of
+        ofk.finite_motion_setting's keywords, e.g. dict(min_depth=0.1): the restored pipeline then writes the frame pair's exact
+        rotation and plane displacement into the points on the device in front of the solve (ofk.h: ofk_set_finite_motion); the
+        velocity is then the mean over the frame interval, and the node's omega has to be per frame interval."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -475,6 +489,12 @@ class optical_fusion:
             self._rolling_shutter = dict(rolling_shutter=rs)
         else:
             self._rolling_shutter = {}
+        if finite_motion is not None and finite_motion is not False:
+            fm = finite_motion if finite_motion is True or isinstance(finite_motion, ofk.FiniteMotion) else ofk.finite_motion_setting(**dict(finite_motion))
+            self._finite_motion = dict(finite_motion=fm)
+            PipelineConfig(**self._finite_motion).finite_motion_setting()   # invalid fields fail here, not at the first frame
+        else:
+            self._finite_motion = {}
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

@@ -365,6 +365,61 @@ int ofk_rs_correct_points(ofk_ctx *ctx, const ofk_rshutter *rs, const float *raw
                           float *out_next);
 int ofk_rs_download(ofk_ctx *ctx, float *prev, float *next, int stride);
 
+/* Finite motion: exact rotation and plane displacement before the solve.  Every solve builds the instantaneous motion field
+ * u = (n.p)/d (v - v_z p) + (omega x p - (omega x p)_z p); a frame pair is a finite motion P1 = R P0 + T, R = exp([omega]x), and the
+ * difference is the largest model error left: 0.3 % of the velocity at a flow of 5 px (at a focal length of 800 px), 3 % at 39 px,
+ * 10 % at 128 px, 18 % at 149 px, and a false velocity of 0.011 per frame under a pure rotation of 0.15 rad (tests/finite_reference.py).
+ * For points on the plane n.P1 = d (n, d in the NEXT frame's camera axes, which is what the sensor record carries and where the solves
+ * evaluate n.p):  R P0 = (I - T n^T / d) P1.  With q~ the previous point rotated by R and renormalised, and p1 the next point,
+ *   (n.p1)/d [q~]x T = [q~]x (p1 - q~),
+ * the NODE system with [.]x taken from q~.  The solves build their system from ONE position x^ and ONE flow u^ and subtract the
+ * first-order rotational field of omega at x^ themselves, so with ofk_set_finite_motion on, the resident chains hand the solve stage
+ *   x^ = q~,   u^ = s (p1 - q~) + rotfield(q~, omega),   s = (n.q~)/(n.p1),   rotfield(p, w) = w x p - (w x p)_z p,
+ * for which the first-order system IS the finite relation ([q~]x q~ = 0 absorbs the third component; d does not enter the rewrite).
+ * The solve then returns T, the displacement per frame interval in the next frame's camera axes; it equals v to first order.
+ * WHAT THE RECORD MEANS WITH THE SETTING ON: fields 0-2 are T, and v_uav = R_world (T - omega x offset), fields 8-10, is the MEAN
+ * world-frame velocity over the frame interval, not the instantaneous one at the next frame.
+ * Everything that lives in the image (LK and its seeds, the track gates, the tracks, the masks, the zones, the corner grid, every
+ * download of points) keeps the raw pixels.  Off by default; with it off every chain launches the kernels and returns the bits it
+ * always did.
+ * Per point i < counts[b], float64, in the order written, no contraction, ONE rounding to float32 at the end.  q0, q1 = the points the
+ * solve would otherwise have read (raw, the camera's ideal ones, or the rolling shutter's corrected ones):
+ *   sc, cx, cy = sensors[19..21];  n = sensors[1..3], om = sensors[4..6] or, under ofk_fusion.use_imu, the resident IMU state's
+ *   [15..17], [18..20] (what k_stream_fuse takes); om is exactly the vector the solve subtracts: no gain
+ *   x0 = (q0.x - cx) sc, y0 = (q0.y - cy) sc;  x1, y1 likewise from q1
+ *   (X, Y, Z) = the rotation of (x0, y0, 1) by +om: the rolling shutter's rot() above with t = -1, before its projection
+ *   a = X / Z, b = Y / Z
+ *   den = n0 x1 + n1 y1 + n2;  s = (n0 a + n1 b + n2) / den
+ *   c0 = om1 - om2 b, c1 = om2 a - om0, c2 = om0 b - om1 a
+ *   ux = s (x1 - a) + (c0 - c2 a),  uy = s (y1 - b) + (c1 - c2 b)
+ *   out_next = ((float)(a / sc + cx), (float)(b / sc + cy))
+ *   out_prev = ((float)((a - ux) / sc + cx), (float)((b - uy) / sc + cy))
+ *   Fallback: a point with sc == 0, !(Z >= min_depth), !(|den| >= 1e-12), !(s > 0), or one of whose four results is not finite or
+ *   exceeds 1e6 in magnitude keeps q0 and q1 as they came; its status is not touched - the camera's and the rolling shutter's rule.
+ * The rewrite takes omega and n as the record gives them: with ofk_set_joint or ofk_set_plane on, which refine one of them, an error
+ * of second order (correction x flow) remains.  The covariance takes the rewritten points as its inputs.
+ * Out of scope: a plane given at the previous frame (non-linear in T), exact seeds for LK, the rewrite's own Jacobian in the
+ * covariance, re-running the rewrite at the joint solve's omega or the plane solve's normal, a body-constant velocity V(omega)^-1 T.
+ * Refused with OFK_E_INVALID before any launch, a setting staying as it was: an unknown mode, min_depth not finite or outside (0, 1];
+ * in the stage entry sensors == NULL; in the runs and steps with the setting on OFK_SOLVE_OFMODULE, OFK_FLOW_ROTATIONAL and
+ * OFK_KEEP_LEGACY, which are not the sensor model.  NULL or mode OFK_FM_OFF switches the setting off.
+ * Resident chains (ofk_pairs_run with every slice count and overlap on and off, ofk_stream_step[_jpeg], ofk_stream_step_fused[_jpeg],
+ * append and replace mode): behind the track step, k_camera_undistort and k_rs_correct, ONE k_finite_correct launch per call and
+ * slice rewrites both sets in the buffers the solve stage reads (in place, or from the raw points when neither of the two is on).
+ * ofk_finite_correct_points, the stage entry on host buffers (points [batch][stride][2] f32, counts [batch], sensors [batch][28] f64):
+ * entries of out_prev / out_next beyond counts[b] keep what the caller put there.  It touches no resident state.
+ * ofk_finite_download: the points the solve stage of the latest run / step with the setting on saw, [batch][stride][2] f32 each
+ * (either may be NULL; at most the context's max_pts points per row are written); OFK_E_INVALID before such a run.  With
+ * ofk_set_camera or ofk_set_rolling_shutter on as well, their downloads return the same arrays: all are "what the solve stage saw". */
+#define OFK_FM_OFF 0
+#define OFK_FM_EXACT 1
+typedef struct ofk_finite_motion { int mode; double min_depth; } ofk_finite_motion;
+int ofk_set_finite_motion(ofk_ctx *ctx, const ofk_finite_motion *fm);   /* NULL or OFF: off */
+int ofk_get_finite_motion(const ofk_ctx *ctx, ofk_finite_motion *fm);
+int ofk_finite_correct_points(ofk_ctx *ctx, const ofk_finite_motion *fm, const float *prev, const float *next, const int *counts,
+                              int batch, int stride, const double *sensors, float *out_prev, float *out_next);
+int ofk_finite_download(ofk_ctx *ctx, float *prev, float *next, int stride);
+
 /* ------------------------------------------------- estimation (float64, batched over `batch` independent problems) */
 
 /* generate_test_data(x, v, omega, d, n[, t]) — node:25-29; simulation.py:7-12.
