@@ -1285,3 +1285,6 @@ void ofk_launch_associate(hipStream_t s, const double *t_img, int n_img, int n_i
 
 // ------------------------------------------------------------------------------------------------ plane solve
 #include "k_plane.inc"
+
+// ------------------------------------------------------------------------------------------------ epipolar solve
+#include "k_epi.inc"

@@ -152,6 +152,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->cov = ofk_cov{OFK_COV_OFF, 0.0, 0.0, 0.0, {0.0, 0.0, 0.0}, 0.0, 0.0, 0, 0, 0.0, 0.0};
     c->joint = ofk_joint{OFK_JOINT_OFF, 0.2, {INFINITY, INFINITY, INFINITY}, 0};
     c->plane = ofk_plane{OFK_PLANE_OFF, 0.2, INFINITY, 0.1, {0.0, 0.0, 1.0}, 6};
+    c->epi = ofk_epipolar{OFK_EPI_OFF, INFINITY, 5, 0.008, {0.0, 0.0, 1.0}, OFK_EPI_W_ONE};
     c->zones = ofk_zones{OFK_ZONES_OFF, 48, 3, 20, 30, OFK_ZONE_MAX};
     c->camera = ofk_camera{OFK_CAMERA_OFF, 20, 1.0, 1.0, 0.0, 0.0, {0, 0, 0, 0, 0, 0, 0, 0}, 1.0, 1.0, 0.0, 0.0};
     c->rs = ofk_rshutter{OFK_RS_OFF, 0, 0.0, 0.5, 1.0};
@@ -208,7 +209,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     for (int k = 0; k < 2; ++k) { if (c->bgr[k]) hipFree(c->bgr[k]); if (c->pyr[k]) hipFree(c->pyr[k]); }
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
-                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec, c->joint_rec, c->plane_rec,
+                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec, c->joint_rec, c->plane_rec, c->epi_rec,
                     c->zone_tab, c->pts_prev_u};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
@@ -1241,9 +1242,80 @@ extern "C" int ofk_plane_download(ofk_ctx *c, double *plane)
     return OFK_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ epipolar setting
+static int check_epipolar(ofk_ctx *c, const ofk_epipolar *v, const char *who)
+{
+    if (v->mode != OFK_EPI_OFF && v->mode != OFK_EPI_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_EPI_OFF nor OFK_EPI_ON", who, v->mode);
+    if (v->weights != OFK_EPI_W_ONE && v->weights != OFK_EPI_W_ROBUST)
+        return ofk_fail(c, OFK_E_INVALID, "%s: weights %d is neither OFK_EPI_W_ONE nor OFK_EPI_W_ROBUST", who, v->weights);
+    if (!(v->anchor > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: anchor is not positive or NaN (%g)", who, v->anchor);
+    if (v->anchor_min < 1) return ofk_fail(c, OFK_E_INVALID, "%s: anchor_min %d is below 1", who, v->anchor_min);
+    if (!(v->sigma_max > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: sigma_max is not positive or NaN (%g)", who, v->sigma_max);
+    const double bb = v->beam[0] * v->beam[0] + v->beam[1] * v->beam[1] + v->beam[2] * v->beam[2];
+    if (!(std::isfinite(v->beam[0]) && std::isfinite(v->beam[1]) && std::isfinite(v->beam[2]) && std::isfinite(bb) && bb > 0.0))
+        return ofk_fail(c, OFK_E_INVALID, "%s: the beam (%g, %g, %g) has no length or is not finite", who, v->beam[0], v->beam[1], v->beam[2]);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_epipolar(ofk_ctx *c, const ofk_epipolar *v)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!v) { c->epi.mode = OFK_EPI_OFF; return OFK_OK; }
+    TRY(check_epipolar(c, v, "ofk_set_epipolar"));
+    c->epi = *v;
+    return OFK_OK;
+}
+
+extern "C" int ofk_get_epipolar(const ofk_ctx *c, ofk_epipolar *v)
+{
+    if (!c || !v) return OFK_E_INVALID;
+    *v = c->epi;
+    return OFK_OK;
+}
+
+// The runs' and steps' own refusals with the setting on (ofk.h); allocates the rows on first use.
+static int epi_prepare(ofk_ctx *c, int B, int variant, const char *who)
+{
+    if (c->epi.mode == OFK_EPI_OFF) return OFK_OK;
+    if (c->cov.mode != OFK_COV_OFF || c->joint.mode != OFK_JOINT_OFF || c->plane.mode != OFK_PLANE_OFF)
+        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_epipolar is on beside %s: that setting rests on the plane this one replaces", who,
+                        c->cov.mode != OFK_COV_OFF ? "ofk_set_cov" : c->joint.mode != OFK_JOINT_OFF ? "ofk_set_joint" : "ofk_set_plane");
+    if (variant == OFK_SOLVE_OFMODULE)
+        return ofk_fail(c, OFK_E_INVALID, "%s: OFK_SOLVE_OFMODULE is not the sensor model: no epipolar solve (ofk_set_epipolar is on)", who);
+    if (!c->epi_rec) {
+        const size_t rec = (size_t)c->max_batch * OFK_EPI_DOUBLES * 8;
+        OFK_HIP(c, hipMalloc((void **)&c->epi_rec, rec + (size_t)c->max_batch * c->max_pts * 32));
+        c->epi_pts = c->epi_rec + (size_t)c->max_batch * OFK_EPI_DOUBLES;
+    }
+    c->epi_batch = B;
+    return OFK_OK;
+}
+
+extern "C" int ofk_epipolar_download(ofk_ctx *c, double *epi)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->epi_batch < 1 || !c->epi_rec) return ofk_fail(c, OFK_E_INVALID, "ofk_epipolar_download: no run or step with ofk_set_epipolar on yet");
+    if (!epi) return ofk_fail(c, OFK_E_INVALID, "ofk_epipolar_download: NULL buffer");
+    TRY(enter(c));
+    OFK_HIP(c, hipMemcpyAsync(epi, c->epi_rec, (size_t)c->epi_batch * OFK_EPI_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+extern "C" int ofk_epipolar_points_download(ofk_ctx *c, double *points)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->epi_batch < 1 || !c->epi_rec) return ofk_fail(c, OFK_E_INVALID, "ofk_epipolar_points_download: no run or step with ofk_set_epipolar on yet");
+    if (!points) return ofk_fail(c, OFK_E_INVALID, "ofk_epipolar_points_download: NULL buffer");
+    TRY(enter(c));
+    OFK_HIP(c, hipMemcpyAsync(points, c->epi_pts, (size_t)c->epi_batch * c->max_pts * 32, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
 // The solve of nb pairs from pair b0 on (their views' pointers): the plain kernels, or with ofk_set_robust on the robust ones; with
 // ofk_set_cov on the covariance kernel behind either, with ofk_set_joint on the joint kernel, with ofk_set_plane on the
-// plane kernel (the callers refuse any two of the three at once).
+// plane kernel, with ofk_set_epipolar on the epipolar kernel (the callers refuse any two of the four at once).
 // drop_status: the stream steps' keep flags (cleared for zero-weight points when the setting asks for it), NULL for frame pairs.
 static void solve_pairs(ofk_ctx *c, hipStream_t st, const float *pts_prev, const float *pts_next, uint8_t *status, const int *counts,
                         const double *sensors, const ofk_params *p, const int *cand_count, double *records, int b0, int nb, bool stream)
@@ -1261,6 +1333,9 @@ static void solve_pairs(ofk_ctx *c, hipStream_t st, const float *pts_prev, const
         if (c->plane.mode != OFK_PLANE_OFF)
             ofk_launch_pairs_plane(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
                                    nullptr, &c->plane, records, c->plane_rec + (size_t)b0 * OFK_PLANE_DOUBLES, nb);
+        if (c->epi.mode != OFK_EPI_OFF)
+            ofk_launch_pairs_epi(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->use_feasibility, p->feas_T, nullptr, &c->epi,
+                                 records, c->epi_rec + (size_t)b0 * OFK_EPI_DOUBLES, c->epi_pts + o * 4, nb);
         return;
     }
     ofk_launch_pairs_robust(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
@@ -1275,6 +1350,9 @@ static void solve_pairs(ofk_ctx *c, hipStream_t st, const float *pts_prev, const
     if (c->plane.mode != OFK_PLANE_OFF)
         ofk_launch_pairs_plane(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
                                c->rob_w + o, &c->plane, records, c->plane_rec + (size_t)b0 * OFK_PLANE_DOUBLES, nb);
+    if (c->epi.mode != OFK_EPI_OFF)
+        ofk_launch_pairs_epi(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->use_feasibility, p->feas_T, c->rob_w + o, &c->epi,
+                             records, c->epi_rec + (size_t)b0 * OFK_EPI_DOUBLES, c->epi_pts + o * 4, nb);
 }
 
 extern "C" int ofk_robust_download(ofk_ctx *c, double *weights, int stride, double *stats)
@@ -1585,6 +1663,44 @@ extern "C" int ofk_velocity_solve_plane(ofk_ctx *c, int variant, const double *x
     ofk_launch_plane_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, dwts, jv, dout, djr);
     TRY(check_launch(c, "k_plane_solve"));
     TRY(get(c, plane, djr, (size_t)batch * OFK_PLANE_DOUBLES * 8));
+    return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
+}
+
+extern "C" int ofk_velocity_solve_epipolar(ofk_ctx *c, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                                           const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
+                                           const ofk_robust *r, const ofk_epipolar *ev, double *out, double *epi, double *points)
+{
+    if (!c || !x || !u || !nrm || !out || !epi || !points || !ev || batch < 1 || n < 1 || n > 4096 || variant < 0 || variant > 2)
+        return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_epipolar: bad argument");
+    if (variant == OFK_SOLVE_OFMODULE) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_epipolar: OFK_SOLVE_OFMODULE is not the sensor model: no epipolar solve");
+    if (!d || !omega) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_epipolar: missing input for variant %d", variant);
+    if (wgt) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_epipolar: wgt must be NULL (the argument is there for the solve entries' signature; the weights are the robust setting's)");
+    TRY(check_epipolar(c, ev, "ofk_velocity_solve_epipolar"));
+    if (ev->mode != OFK_EPI_ON) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_epipolar: mode must be OFK_EPI_ON");
+    const bool rob = r && r->loss != OFK_ROBUST_OFF;
+    if (rob) TRY(check_robust(c, r, "ofk_velocity_solve_epipolar"));
+    const size_t pb = (size_t)batch * n * 16, wb = (size_t)batch * n * 8;
+    Bump bp;
+    TRY(est_begin(c, 2 * pb + (size_t)batch * n * 9 + 9 * wb + 4 * wb + (size_t)batch * 256 * 12, bp));
+    double *dx = bp.put(x, pb), *du = bp.put(u, pb);
+    uint8_t *dval = (uint8_t *)bp.put(valid, (size_t)batch * n);
+    double *dd = bp.put(d, batch * 8), *dn = bp.put(nrm, batch * 24), *dom = bp.put(omega, batch * 24), *dt = bp.put(t, batch * 24),
+           *dout = bp.take((size_t)batch * OFK_SOLVE_DOUBLES * 8), *der = bp.take((size_t)batch * OFK_EPI_DOUBLES * 8), *dpt = bp.take(4 * wb),
+           *dwts = nullptr;
+    if (rob) {
+        double *dwork = bp.take(7 * wb);
+        dwts = bp.take(wb);
+        double *dtmp = bp.take(wb), *dst = bp.take((size_t)batch * OFK_ROBUST_DOUBLES * 8);
+        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_epipolar: upload failed");
+        ofk_launch_solve_robust(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, r, dwork, dwts, dtmp, dst, dout);
+    } else {
+        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_epipolar: upload failed");
+        ofk_launch_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, dout);
+    }
+    ofk_launch_epi_solve(c->stream, dx, du, dval, batch, n, dd, dn, dom, dt, dwts, ev, dout, der, dpt);
+    TRY(check_launch(c, "k_epi_solve"));
+    TRY(get(c, epi, der, (size_t)batch * OFK_EPI_DOUBLES * 8));
+    TRY(get(c, points, dpt, 4 * wb));
     return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
 }
 
@@ -1955,6 +2071,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
     if (c->cov.mode != OFK_COV_OFF) { TRY(cov_alloc(c)); c->cov_batch = B; }
     TRY(joint_prepare(c, B, "ofk_pairs_run"));
     TRY(plane_prepare(c, B, p->solve_variant, "ofk_pairs_run"));
+    TRY(epi_prepare(c, B, p->solve_variant, "ofk_pairs_run"));
     TRY(camera_prepare(c, B));
     const bool cam = camera_on(c) || rs_on(c) || fm_on(c);       // the solve stage reads the ideal / corrected / rewritten points
     TRY(need_streams(c, S, overlap));
@@ -2516,7 +2633,11 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     if (plane_on && fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY))
         return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused: OFK_FLOW_ROTATIONAL / OFK_KEEP_LEGACY are not the sensor model: no plane solve (ofk_set_plane is on)");
     TRY(plane_prepare(c, B, p->solve_variant, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
-    const int defer = (cov_on || joint_on || plane_on) && fu && fu->filter ? 1 : 0;   // the covariance / joint / plane kernel corrects
+    const bool epi_on = c->epi.mode != OFK_EPI_OFF;
+    if (epi_on && fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY))
+        return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused: OFK_FLOW_ROTATIONAL / OFK_KEEP_LEGACY are not the sensor model: no epipolar solve (ofk_set_epipolar is on)");
+    TRY(epi_prepare(c, B, p->solve_variant, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
+    const int defer = (cov_on || joint_on || plane_on || epi_on) && fu && fu->filter ? 1 : 0;   // the covariance / joint / plane / epipolar kernel corrects
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
@@ -2566,6 +2687,10 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         ofk_launch_stream_plane(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm,
                                 c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, c->records, c->fused,
                                 c->robust.loss != OFK_ROBUST_OFF ? c->rob_w : nullptr, &c->plane, c->plane_rec, B, defer);
+    if (epi_on && fu)
+        ofk_launch_stream_epi(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm,
+                              c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, c->records, c->fused,
+                              c->robust.loss != OFK_ROBUST_OFF ? c->rob_w : nullptr, &c->epi, c->epi_rec, c->epi_pts, B, defer);
     // re-detection for the streams that had few features (node:157-166): mask = discs around the OLD positions, image = OLD frame.
     // The host knows the track counts from the previous call, so the whole branch is skipped when no stream needs it.
     // of_module.py:138 `continue`: a step of the ONE stream that did not solve leaves old_gray / old_pos as they were.  The host has to

@@ -100,6 +100,8 @@ struct ofk_ctx {
     double *joint_rec; int joint_batch;      // [B][OFK_JOINT_DOUBLES] (lazily allocated); problems of the latest run / step with it on, 0 = none
     ofk_plane plane;                         // ofk_set_plane: mode OFK_PLANE_OFF unless set
     double *plane_rec; int plane_batch;      // [B][OFK_PLANE_DOUBLES] (lazily allocated); problems of the latest run / step with it on, 0 = none
+    ofk_epipolar epi;                        // ofk_set_epipolar: mode OFK_EPI_OFF unless set
+    double *epi_rec, *epi_pts; int epi_batch;   // [B][OFK_EPI_DOUBLES] and [B][max_pts][4] (one lazy allocation, epi_rec owns it); problems of the latest run / step with it on, 0 = none
     ofk_zones zones;                         // ofk_set_zones: mode OFK_ZONES_OFF unless set
     int *zone_tab; float *zone_mot; int *zone_stats, *zone_work;   // [B][OFK_ZONE_MAX][OFK_ZONE_INTS], [B][OFK_ZONE_MAX][OFK_ZONE_FLOATS], [B][OFK_ZONE_STATS], [B][2][max_pts] hull stacks;
     uint8_t *zone_status;                    // [B][max_pts] status in front of the solve stage; one lazy allocation (zone_tab owns it)
@@ -250,6 +252,18 @@ void ofk_launch_stream_joint(hipStream_t s, const float *prev_pts, const float *
                              const double *sensors, double *imu_state, int ns, int nm, int nc, const double *kf_mats, double *kf_x, double *kf_P,
                              const ofk_fusion *f, int variant, double *records, double *fused, const double *weights, const ofk_joint *j,
                              double *joint, int batch, int defer);
+// the epipolar solve (k_epi.inc), behind the solve kernels: rewrites out / records in place; weights NULL = the plain solve ran; epi /
+// pts: the slice's rows of epi_rec / epi_pts
+void ofk_launch_epi_solve(hipStream_t s, const double *x, const double *u, const uint8_t *valid, int batch, int n, const double *d,
+                          const double *nrm, const double *omega, const double *t, const double *weights, const ofk_epipolar *e,
+                          double *out, double *epi, double *pts);
+void ofk_launch_pairs_epi(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts,
+                          int pts_stride, const double *sensors, int use_feas, double feas_T, const double *weights, const ofk_epipolar *e,
+                          double *records, double *epi, double *pts, int batch);
+void ofk_launch_stream_epi(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
+                           const double *sensors, double *imu_state, int ns, int nm, int nc, const double *kf_mats, double *kf_x, double *kf_P,
+                           const ofk_fusion *f, int variant, double *records, double *fused, const double *weights, const ofk_epipolar *e,
+                           double *epi, double *pts, int batch, int defer);
 // the plane solve (k_plane.inc), behind the solve kernels: rewrites out / records in place; weights NULL = the plain solve ran;
 // plane: the slice's rows of plane_rec
 void ofk_launch_plane_solve(hipStream_t s, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,

@@ -30,6 +30,7 @@ SYMBOLS = (
     "ofk_set_cov", "ofk_get_cov", "ofk_cov_download", "ofk_velocity_solve_cov",
     "ofk_set_joint", "ofk_get_joint", "ofk_joint_download", "ofk_velocity_solve_joint",
     "ofk_set_plane", "ofk_get_plane", "ofk_plane_download", "ofk_velocity_solve_plane",
+    "ofk_set_epipolar", "ofk_get_epipolar", "ofk_epipolar_download", "ofk_epipolar_points_download", "ofk_velocity_solve_epipolar",
     "ofk_set_track_gate", "ofk_get_track_gate", "ofk_track_gate_download", "ofk_lk_pyr_fb",
     "ofk_set_corner_grid", "ofk_get_corner_grid", "ofk_corner_grid_download", "ofk_select_corners_grid", "ofk_good_features_grid",
     "ofk_set_zones", "ofk_get_zones", "ofk_zones_step", "ofk_zones_reset", "ofk_zones_download",
@@ -73,6 +74,11 @@ JOINT_OFF, JOINT_ON = 0, 1                               # ofk_set_joint / ofk_v
 JOINT_DOUBLES = 32
 PLANE_OFF, PLANE_ON = 0, 1                               # ofk_set_plane / ofk_velocity_solve_plane
 PLANE_DOUBLES = 32
+EPI_OFF, EPI_ON = 0, 1                                   # ofk_set_epipolar / ofk_velocity_solve_epipolar
+EPI_W_ONE, EPI_W_ROBUST = 0, 1
+EPI_WEIGHTS = {"one": EPI_W_ONE, "robust": EPI_W_ROBUST}
+EPI_DOUBLES = 32
+EPI_SIGMA_MAX = 0.008                                    # radians; tests/test_epi_reference.py measures it
 FB_OFF, FB_PLAIN, FB_SEEDED = 0, 1, 2                    # ofk_set_track_gate / ofk_lk_pyr_fb
 FB_MODES = {"off": FB_OFF, "plain": FB_PLAIN, "seeded": FB_SEEDED}
 GRID_MAX_CELLS = 2048                                   # OFK_GRID_MAX_CELLS: cells of a corner grid over one frame
@@ -166,6 +172,25 @@ def plane_setting(mode=True, sigma_flow=0.2, sigma_normal=None, sigma_max=0.1, b
     b = np.broadcast_to(np.asarray(beam, np.float64), (3,))
     return Plane(int(mode), float(sigma_flow), float(np.inf if sigma_normal is None else sigma_normal), float(sigma_max),
                  (C.c_double * 3)(*b.tolist()), int(iters))
+
+
+class Epipolar(C.Structure):
+    """ofk_epipolar (include/ofk.h): the epipolar solve's setting."""
+    _fields_ = [("mode", C.c_int), ("anchor", C.c_double), ("anchor_min", C.c_int), ("sigma_max", C.c_double), ("beam", C.c_double * 3),
+                ("weights", C.c_int)]
+
+
+def epipolar_setting(mode=True, anchor=np.inf, anchor_min=5, sigma_max=EPI_SIGMA_MAX, beam=(0.0, 0.0, 1.0), weights="one"):
+    """An Epipolar structure from names: mode True / False (or EPI_*); anchor the radius around the beam's foot inside which the
+    ground is the sensors' plane, in the units of the points the entry takes (pixels in the resident paths; inf: every kept point);
+    anchor_min the fewest anchor points a scale is taken from; sigma_max the largest predicted 1 sigma of the direction that is
+    accepted (radians, inf: no gate); beam the range sensor's direction in the camera frame; weights "one" / "robust" (or EPI_W_*)."""
+    if isinstance(weights, str):
+        if weights not in EPI_WEIGHTS:
+            raise ValueError(f"epipolar weights {weights!r} is none of {sorted(EPI_WEIGHTS)}")
+        weights = EPI_WEIGHTS[weights]
+    b = np.broadcast_to(np.asarray(beam, np.float64), (3,))
+    return Epipolar(int(mode), float(anchor), int(anchor_min), float(sigma_max), (C.c_double * 3)(*b.tolist()), int(weights))
 
 
 def cov_matrix(t6):
@@ -422,6 +447,9 @@ def load_library():
         L.ofk_set_plane.argtypes = [vp, C.POINTER(Plane)]; L.ofk_get_plane.argtypes = [vp, C.POINTER(Plane)]
         L.ofk_plane_download.argtypes = [vp, vp]
         L.ofk_velocity_solve_plane.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Plane), vp, vp]
+        L.ofk_set_epipolar.argtypes = [vp, C.POINTER(Epipolar)]; L.ofk_get_epipolar.argtypes = [vp, C.POINTER(Epipolar)]
+        L.ofk_epipolar_download.argtypes = [vp, vp]; L.ofk_epipolar_points_download.argtypes = [vp, vp]
+        L.ofk_velocity_solve_epipolar.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Epipolar), vp, vp, vp]
         L.ofk_set_track_gate.argtypes = [vp, C.POINTER(TrackGate)]; L.ofk_get_track_gate.argtypes = [vp, C.POINTER(TrackGate)]
         L.ofk_track_gate_download.argtypes = [vp, vp, vp, vp, i, vp]
         L.ofk_set_corner_grid.argtypes = [vp, C.POINTER(CornerGrid)]; L.ofk_get_corner_grid.argtypes = [vp, C.POINTER(CornerGrid)]
@@ -1249,6 +1277,53 @@ class Context:
         with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
             self._ck(self._L.ofk_plane_download(self._h, _p(rec)))
         return rec[:batch].copy()
+
+    def velocity_solve_epipolar(self, variant, x, u, d=None, nrm=None, omega=None, t=None, valid=None, robust=None, epipolar=None, **settings):
+        """ofk_velocity_solve_epipolar: velocity_solve's arguments (NODE or SIM), an optional Robust and the epipolar setting (an
+        Epipolar, or epipolar_setting's keywords).  Returns out [B,8] after the rewrite, the record [B,32] and the point rows
+        [B,n,4] (single problem: [8], [32], [n,4])."""
+        ev = epipolar if epipolar is not None else epipolar_setting(**settings)
+        x = _arr(x, np.float64); u = _arr(u, np.float64)
+        if u.shape[:-1] != x.shape[:-1] or x.shape[-1] != 2 or u.shape[-1] < 2:
+            raise ValueError(f"velocity_solve_epipolar: x {x.shape} must be [..., n, 2] and u {u.shape} [..., n, >=2] over the same points")
+        single = x.ndim == 2
+        if single:
+            x = x[None]; u = u[None]
+        B, n, _ = x.shape
+        u = _arr(u[..., :2], np.float64)
+        nrm = _arr(nrm, np.float64, (B, 3))
+        d = _opt(d, np.float64, (B,)); omega = _opt(omega, np.float64, (B, 3)); t = _opt(t, np.float64, (B, 3))
+        valid = _opt(valid, np.uint8, (B, n))
+        out = np.zeros((B, SOLVE_DOUBLES), np.float64); rec = np.zeros((B, EPI_DOUBLES), np.float64); pts = np.zeros((B, n, 4), np.float64)
+        if not n:                                               # no points: velocity_solve's zeros, nothing attempted
+            rec[:, 10] = 1.0
+            return (out[0], rec[0], pts[0]) if single else (out, rec, pts)
+        with self._lock:
+            self._ck(self._L.ofk_velocity_solve_epipolar(self._h, int(variant), _p(x), _p(u), _p(valid), B, n, _p(d), _p(nrm), _p(omega),
+                                                         _p(t), None, C.byref(robust) if robust is not None else None, C.byref(ev),
+                                                         _p(out), _p(rec), _p(pts)))
+        return (out[0], rec[0], pts[0]) if single else (out, rec, pts)
+
+    def set_epipolar(self, epipolar=None, **settings):
+        """ofk_set_epipolar: an Epipolar (or epipolar_setting's keywords); None or mode False switches it off.  Every later pairs_run
+        and stream step takes v from the epipolar constraint and the range at the beam's foot, and rewrites v, field 3 and v_uav of
+        its records."""
+        ev = epipolar if epipolar is not None or not settings else epipolar_setting(**settings)
+        self._ck(self._L.ofk_set_epipolar(self._h, C.byref(ev) if ev is not None else None))
+
+    def get_epipolar(self):
+        ev = Epipolar()
+        self._ck(self._L.ofk_get_epipolar(self._h, C.byref(ev)))
+        return ev
+
+    def epipolar_download(self, batch):
+        """The record [batch, 32] and the point rows [batch, max_pts, 4] (rho, r, |b|, flag) of the latest run / step with the
+        setting on."""
+        rec = np.zeros((self.max_batch, EPI_DOUBLES), np.float64); pts = np.zeros((self.max_batch, self.max_pts, 4), np.float64)
+        with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
+            self._ck(self._L.ofk_epipolar_download(self._h, _p(rec)))
+            self._ck(self._L.ofk_epipolar_points_download(self._h, _p(pts)))
+        return rec[:batch].copy(), pts[:batch].copy()
 
     def imu_propagate(self, state, msg):
         state = _arr(state, np.float64).copy(); msg = _arr(msg, np.float64)

@@ -128,6 +128,15 @@ class PipelineConfig:
     plane_sigma_max: float = 0.1
     range_beam: tuple = (0.0, 0.0, 1.0)
     plane_iters: int = 6
+    # epipolar solve (ofk.h: ofk_set_epipolar): velocity and per-point inverse depths over ground that is no plane, behind every solve;
+    # epi_anchor_px the radius in pixels around the foot of range_beam inside which the ground is the sensors' plane (inf: every kept
+    # point); epi_anchor_min the fewest anchor points; epi_sigma_max the largest predicted 1 sigma of the direction that is accepted
+    # (radians); epi_weights "one" (the robust weights are ignored) or "robust"
+    epipolar: bool = False
+    epi_anchor_px: float = float("inf")
+    epi_anchor_min: int = 5
+    epi_sigma_max: float = ofk.EPI_SIGMA_MAX
+    epi_weights: str = "one"
     # exclusion zones (ofk.h: ofk_set_zones; streams only): None or "hull"; rejects of the solve stage closer than zone_link pixels
     # per axis form a cluster, one of at least zone_min becomes a zone (its hull grown by zone_radius) that moves with the cluster's
     # mean flow, keeps the re-detection out and lives zone_ttl steps behind its last refresh; at most zone_max zones per stream
@@ -202,6 +211,12 @@ class PipelineConfig:
         if not self.plane:
             return None
         return ofk.plane_setting(True, self.plane_sigma_flow_px, self.normal_prior, self.plane_sigma_max, self.range_beam, self.plane_iters)
+
+    def epipolar_setting(self):
+        """The ofk.Epipolar structure of this configuration, None when the epipolar solve is off."""
+        if not self.epipolar:
+            return None
+        return ofk.epipolar_setting(True, self.epi_anchor_px, self.epi_anchor_min, self.epi_sigma_max, self.range_beam, self.epi_weights)
 
     def zones_setting(self):
         """The ofk.Zones structure of this configuration, None when the zones are off."""
@@ -368,6 +383,8 @@ class FlowStream:
             self.ctx.set_joint(self.cfg.joint_setting())
         if self.cfg.plane:
             self.ctx.set_plane(self.cfg.plane_setting())
+        if self.cfg.epipolar:
+            self.ctx.set_epipolar(self.cfg.epipolar_setting())
         if self.cfg.zones_setting() is not None:
             self.ctx.set_zones(self.cfg.zones_setting())
         if self.cfg.camera_setting() is not None:
@@ -408,6 +425,13 @@ class FlowStream:
         rec[:, 3] the refined distance, rec[:, 4:6] the tilt, rec[:, 10] the flag, rec[:, 14] the predicted 1 sigma of the normal's angle,
         ofk.cov_matrix(rec[:, 20:26]) C_v."""
         return self.ctx.plane_download(self.batch)
+
+    def structure(self):
+        """The epipolar record [batch, 32] and point rows [batch, max_pts, 4] (ofk.h: ofk_set_epipolar) of the latest step with the
+        epipolar solve on: rec[:, 0:3] is the direction t^, rec[:, 3] the scale s, rec[:, 4] the flow noise estimated from the
+        constraint, rec[:, 10] the flag, rec[:, 17] the predicted 1 sigma of the direction, ofk.cov_matrix(rec[:, 25:31]) C_v;
+        pts[..., 0] the inverse depths rho_i, pts[..., 1] the flow across the epipolar line, pts[..., 3] the point flag."""
+        return self.ctx.epipolar_download(self.batch)
 
     def rotations(self):
         """[batch, 32] joint records (ofk.h: ofk_set_joint) of the latest step with the joint solve on: rec[:, 0:3] is the refined omega,
@@ -479,6 +503,8 @@ class FlowPipeline:
             self.ctx.set_joint(self.cfg.joint_setting())
         if self.cfg.plane:
             self.ctx.set_plane(self.cfg.plane_setting())
+        if self.cfg.epipolar:
+            self.ctx.set_epipolar(self.cfg.epipolar_setting())
         if self.cfg.camera_setting() is not None:
             self.ctx.set_camera(self.cfg.camera_setting())
         if self.cfg.rolling_shutter_setting() is not None:
@@ -535,6 +561,11 @@ class FlowPipeline:
     def planes(self):
         """[batch, 32] plane records (ofk.h: ofk_set_plane) of the latest run with the plane solve on (see FlowStream.planes)."""
         return self.ctx.plane_download(self.batch)
+
+    def structure(self):
+        """The epipolar record [batch, 32] and point rows [batch, max_pts, 4] (ofk.h: ofk_set_epipolar) of the latest run with the
+        epipolar solve on (see FlowStream.structure)."""
+        return self.ctx.epipolar_download(self.batch)
 
     def rotations(self):
         """[batch, 32] joint records (ofk.h: ofk_set_joint) of the latest run with the joint solve on (see FlowStream.rotations)."""

@@ -72,6 +72,17 @@ def solve_lgs_plane(x, u, d, n, omega, t, sigma_flow, sigma_normal=None, **setti
     return out[:3].copy(), R, out[5:8].copy(), pr[0:3].copy(), float(pr[3]), pr
 
 
+def solve_lgs_epipolar(x, u, d, n, omega, t, **settings):
+    """solve_lgs over ground that is no plane (ofk.h: ofk_velocity_solve_epipolar).  settings: anchor (in the units of x), anchor_min,
+    sigma_max, beam, weights of ofk.epipolar_setting.
+    Returns (v - omega x t, R, s, rho [N], epi [32], points [N,4]); epi[10] != 0 where the plain result stands."""
+    x = np.asarray(x, np.float64)
+    out, er, pts = ofk.default_context().velocity_solve_epipolar(ofk.SOLVE_SIM, x[:, :2], np.asarray(u, np.float64)[:, :2],
+                                                                 d=float(np.ravel(d)[0]), nrm=n, omega=omega, t=t, **settings)
+    R = np.array([out[3]]) if (int(out[4]) == 3 and 3 * len(x) > 3) else np.empty(0)
+    return out[:3].copy(), R, out[5:8].copy(), pts[:, 0].copy(), er, pts
+
+
 def feasibility(position, linear_velocity, flow, angular_velocity, translation, normal):
     r, length = ofk.default_context().feasibility(ofk.FEAS_SIM, np.asarray(position, np.float64)[:, :2],
                                                   np.asarray(flow, np.float64)[:, :2], normal, linear_velocity,

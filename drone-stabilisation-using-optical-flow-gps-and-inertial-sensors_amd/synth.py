@@ -133,8 +133,12 @@ def _colour(T, T2, ax, ay):
 
 
 def render_pair(h, w, seed, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.003), d=1.0, n=(0, 0, 1), scaling=None,
-                margin=48, camera=None, rolling_shutter=None, motion="linear"):
+                margin=48, camera=None, rolling_shutter=None, motion="linear", relief=None):
     """Returns dict(prev, next: [h,w,3] uint8 BGR; H: 3x3 pixel homography prev->next; scaling, cx, cy).
+    relief (default None: the one plane): dict(rect=(x0, y0, x1, y1), height=h) composites a second plane at distance d (1 - h) with
+    the same normal over the pixels x0 <= x < x1, y0 <= y < y1 of the `next` frame: there the texture is seen through that plane's
+    own homography (info["H_relief"]), as a roof painted like the ground would be; `prev` is the one plane's.  Not with a camera or
+    a rolling shutter.
     motion: pixel_homography's ("finite": the exact rigid motion of the pair; not with a rolling shutter, whose rows are rendered
     through the linearised homography).
     camera (a pipeline.CameraModel, default None): the frames are what that camera sees - every raw pixel is undistorted to the ideal
@@ -144,6 +148,8 @@ def render_pair(h, w, seed, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.00
     t = k + readout * (y / h - anchor) and rendered through the pair's linearised homography at that time,
     K (I + t (W + v n' / d)) K^-1 - pixel_homography's own form with t v, t omega; H stays the global shutter's.  Works behind a
     camera as well (the rows are the raw image's)."""
+    if relief is not None and (camera is not None or rolling_shutter is not None):
+        raise ValueError("render_pair: relief is rendered for the ideal pinhole with a global shutter alone")
     if rolling_shutter is not None and motion != "linear":
         raise ValueError("render_pair: a rolling shutter is rendered through the linearised homography: motion must be 'linear'")
     if rolling_shutter is not None:
@@ -198,6 +204,20 @@ def render_pair(h, w, seed, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.00
 
     prev = colour(T[margin:margin + h, margin:margin + w], T2[margin:margin + h, margin:margin + w])
     nxt = colour(_bilinear(T, sx, sy), _bilinear(T2, sx, sy))
+    if relief is not None:
+        x0, y0, x1, y1 = (int(c) for c in relief["rect"])
+        hr = float(relief["height"])
+        if not (0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h and hr < 1.0):
+            raise ValueError(f"render_pair: relief rect {relief['rect']} outside the {w} x {h} frame or height {hr} not below 1")
+        Hr = pixel_homography(v, omega, d * (1.0 - hr), n, scaling, cx, cy, motion)
+        Hri = np.linalg.inv(Hr)
+        ry, rx = yy[y0:y1, x0:x1], xx[y0:y1, x0:x1]
+        den = Hri[2, 0] * rx + Hri[2, 1] * ry + Hri[2, 2]
+        qx = (Hri[0, 0] * rx + Hri[0, 1] * ry + Hri[0, 2]) / den + margin
+        qy = (Hri[1, 0] * rx + Hri[1, 1] * ry + Hri[1, 2]) / den + margin
+        nxt[y0:y1, x0:x1] = colour(_bilinear(T, qx, qy), _bilinear(T2, qx, qy))
+        return dict(prev=prev, next=nxt, H=H, H_relief=Hr, relief=dict(rect=(x0, y0, x1, y1), height=hr), scaling=scaling, cx=cx, cy=cy,
+                    v=np.asarray(v, np.float64), omega=np.asarray(omega, np.float64), d=float(d), n=np.asarray(n, np.float64))
     return dict(prev=prev, next=nxt, H=H, scaling=scaling, cx=cx, cy=cy, v=np.asarray(v, np.float64),
                 omega=np.asarray(omega, np.float64), d=float(d), n=np.asarray(n, np.float64))
 

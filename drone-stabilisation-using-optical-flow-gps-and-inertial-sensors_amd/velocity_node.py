@@ -111,6 +111,18 @@ def solve_lgs_plane(x, u, d, n, omega, sigma_flow, sigma_normal=None, **settings
     return out[:3].copy(), R, rank, out[5:8].copy(), pr[0:3].copy(), float(pr[3]), pr
 
 
+def solve_lgs_epipolar(x, u, d, n, omega, **settings):
+    """solve_lgs over ground that is no plane (ofk.h: ofk_velocity_solve_epipolar): the direction of v from the epipolar constraint,
+    its length from the range at the beam's foot, one inverse depth per point.  settings: anchor (in the units of x), anchor_min,
+    sigma_max, beam, weights of ofk.epipolar_setting.
+    Returns (v, R, rank, s, rho [N], epi [32], points [N,4]); epi[10] != 0 where the epipolar solve left the plain result alone."""
+    x = np.asarray(x, np.float64); u = np.asarray(u, np.float64)
+    out, er, pts = ofk.default_context().velocity_solve_epipolar(ofk.SOLVE_NODE, x[:, :2], u[:, :2], d=float(d), nrm=n, omega=omega, **settings)
+    rank = int(out[4])
+    R = np.array([out[3]]) if (rank == 3 and 3 * len(x) > 3) else np.empty(0)
+    return out[:3].copy(), R, rank, out[5:8].copy(), pts[:, 0].copy(), er, pts
+
+
 def finite_points(prev, next, sensors, min_depth=0.1):
     """The finite motion's rewrite of tracked points (ofk.h: ofk_finite_correct_points): prev, next [N,2] (or [B,N,2]) pixels as the
     solve would read them, sensors [28] (or [B,28]) the record of the next frame (normal, omega per frame interval, scaling, centre).
@@ -143,6 +155,7 @@ class optical_fusion:
     _cov = {}                                                    # PipelineConfig's covariance fields (cov, sigma_*, ...); empty: no covariance
     _joint = {}                                                  # PipelineConfig's joint fields (joint, joint_sigma_flow_px, omega_prior, ...); empty: the gyro is taken as exact
     _plane = {}                                                  # PipelineConfig's plane fields (plane, plane_sigma_flow_px, normal_prior, ...); empty: the normal is taken as exact
+    _epipolar = {}                                               # PipelineConfig's epipolar fields (epipolar, epi_anchor_px, epi_sigma_max, ...); empty: every depth is the plane's
     _zones = {}                                                  # PipelineConfig's zones / zone_* fields; empty: no exclusion zones
     _camera = {}                                                 # PipelineConfig's camera field; empty: the points are taken as ideal pinhole samples
     _finite_motion = {}                                          # PipelineConfig's finite_motion field; empty: the solve takes the flow as the instantaneous field
@@ -301,7 +314,7 @@ class optical_fusion:
                                  min_distance=float(self.feature_params["minDistance"]), block_size=int(self.feature_params["blockSize"]),
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
-                                 **self._cov, **self._joint, **self._plane, **self._zones, **self._camera, **self._rolling_shutter,
+                                 **self._cov, **self._joint, **self._plane, **self._epipolar, **self._zones, **self._camera, **self._rolling_shutter,
                                  **self._finite_motion)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
@@ -344,6 +357,9 @@ class optical_fusion:
             self.last_joint = fs.rotations()[0]
         if self._plane and r[15]:
             self.last_plane = fs.planes()[0]
+        if self._epipolar and r[15]:
+            rec, pts = fs.structure()
+            self.last_epipolar = (rec[0], pts[0])
         self.init = False
         self.got_picture_ = True
 
@@ -403,7 +419,7 @@ class optical_fusion:
             self.vel_err = np.sqrt(np.maximum(np.diag(Rm @ ofk.cov_matrix(cv[6:12]) @ Rm.T), 0.0))
 
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
-                 rolling_shutter=None, joint=None, plane=None, finite_motion=None):
+                 rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -433,6 +449,10 @@ class optical_fusion:
         (PipelineConfig's plane fields), e.g. dict(normal_prior=0.05): every solved step then refines the ground normal from the flow
         and reports the velocity over the refined plane (ofk.h: ofk_set_plane); self.last_plane is the record, its slots 0-2 the
         refined normal, 3 the refined distance.  Refused beside joint and cov at the first frame.
+        epipolar: None (every depth is the plane's), True, or a dict of anchor_px, anchor_min, sigma_max, weights, range_beam
+        (PipelineConfig's epipolar fields), e.g. dict(anchor_px=120): every solved step then takes the direction of v from the
+        epipolar constraint and its length from the range at the beam's foot (ofk.h: ofk_set_epipolar); self.last_epipolar is
+        (record [32], point rows [max_pts, 4]).  Refused beside joint, plane and cov at the first frame.
         finite_motion: None (the flow is taken as the instantaneous motion field), True, an ofk.FiniteMotion or a dict of
         ofk.finite_motion_setting's keywords, e.g. dict(min_depth=0.1): the restored pipeline then writes the frame pair's exact
         rotation and plane displacement into the points on the device in front of the solve (ofk.h: ofk_set_finite_motion); the
@@ -472,6 +492,16 @@ class optical_fusion:
         else:
             self._plane = {}
         self.last_plane = None
+        if epipolar:
+            ep = {} if epipolar is True else dict(epipolar)
+            for short in ("anchor_px", "anchor_min", "sigma_max", "weights"):
+                if short in ep:
+                    ep["epi_" + short] = ep.pop(short)
+            self._epipolar = dict(epipolar=True, **ep)
+            PipelineConfig(**self._epipolar).epipolar_setting()  # unknown or invalid keywords fail here, not at the first frame
+        else:
+            self._epipolar = {}
+        self.last_epipolar = None
         z = dict(zones or {})
         if zones is not None:
             ofk.zones_setting(**z)                               # unknown or invalid keywords fail here, not at the first frame

@@ -734,6 +734,87 @@ int ofk_velocity_solve_plane(ofk_ctx *ctx, int variant, const double *x, const d
                              const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
                              const ofk_robust *r, const ofk_plane *p, double *out, double *plane);
 
+/* The epipolar solve: velocity and per-point inverse depths over ground that is no plane.  Every other solve of the library - plain,
+ * robust, joint, plane, the covariance, the feasibility rule - takes each point's depth from one plane, Z = d / (n.p).  Roofs, trees,
+ * a ledge or a ramp are no plane, and the robust solve helps only while a single plane holds the majority of the points.  This solve
+ * needs the gyro and the range sensor alone.  Off by default; with it off every entry point launches the kernels and returns the bits
+ * it always did, with no allocation and no launch.  All arithmetic is f64.
+ * Point set: the solve's own - gated status / valid / pair feasibility keep.  weights = OFK_EPI_W_ONE (default) ignores the robust
+ * weights (they are the plane model's verdict, the thing being replaced): every kept point enters with w = 1.  OFK_EPI_W_ROBUST takes
+ * them as the joint solve does: points of final weight w > 0, w used as the weight.
+ * Flow equation: with p = (x, y, 1), X = [p]x and q = (u, 0) + p x omega (the solve's per-point term) the flow equation is
+ * rho_i X v = X q_i, rho_i point i's inverse depth.  Eliminating rho_i leaves one row per point, c_i.v = 0 with c_i = p_i x q_i: no
+ * plane appears, and only the direction of v is determined.
+ * Direction: the minimiser of sum w (c_i.t)^2 is badly biased at low flow-to-noise ratios.  Flow noise delta enters c_i as
+ * X_i (delta, 0), so E[sum w c c^T] = E0 + sigma^2 N0 with E = sum w c c^T (six sums) and N0 = sum w X_i D X_i^T, D = diag(1, 1, 0)
+ * (six sums).  t^ is the generalised eigenvector of (E, N0) for the smallest eigenvalue lambda_1 (Kanatani's renormalisation), without
+ * iteration: the cyclic Jacobi the solve uses gives W = N0^(-1/2), again the smallest eigenvector y of W E W, and t^ = W y / |W y|.
+ * Flow noise: sigma^ = sqrt(lambda_1 m / (m - 2)), m the kept points, in the units of the points.  lambda_1 is taken as t^'s Rayleigh
+ * quotient t^^T E t^ / t^^T N0 t^ = sum w (c_i.t^)^2 |W y|^2 with the numerator summed from the second walk's residuals: the value the
+ * decomposition returns carries a rounding floor of eps lambda_max, this one has none and is never negative.
+ * Per point (second walk): a_i = (q - q_z p)_xy, the derotated image flow; b_i = (t^_x - t^_z x, t^_y - t^_z y);
+ * kappa_i = a_i.b_i / |b_i|^2, the flow along the epipolar direction, = s rho_i; r_i = (a_i x b_i) / |b_i|, the flow across it
+ * (c_i.t^ = |b_i| r_i).
+ * Sign: t^ is flipped so that sum w a_i.b_i >= 0 (positive depths in aggregate); a point with kappa_i <= 0 then gets point flag 2.
+ * Scale: the range sensor measured along the body-fixed beam e (`beam`, normalised here; default the optical axis), whose foot in the
+ * image is p_e = e / e_z.  The anchor set is the kept points with |p_xy - p_e| <= anchor; over it s = sum w kappa_i m_i / sum w m_i^2,
+ * m_i = (n0.p_i) / d0: the ground is taken as the sensors' plane under the beam only.  anchor = +inf takes every kept point.  anchor is
+ * in the units of the points in ofk_velocity_solve_epipolar and pixels x `scaling` (sensor slot 19) in the resident paths.  Then
+ * v = s t^ and rho_i = kappa_i / s.
+ * Uncertainty: H = sum w c_i c_i^T / |b_i|^2 (six sums of the second walk); C_t = sigma^^2 (P H P)^+, P = I - t^ t^^T, the pseudo-inverse
+ * over the two largest eigenvalues; the predicted 1 sigma of the direction is sqrt(tr C_t), radians;
+ * var(s) = sigma^^2 sum_anchor w m_i^2 / |b_i|^2 / (sum_anchor w m_i^2)^2; C_v = s^2 C_t + var(s) t^ t^^T.
+ * All sums - 13 in the first walk (E, N0, the count), 15 in the second (H, sum w r^2, sum w a.b, the anchor set's three sums and
+ * count, the counts of kappa <= 0 and kappa >= 0, sum w (c.t^)^2) - are added over four virtual waves as (s0 + s1) + (s2 + s3), so records and point
+ * rows are bit-identical across launch forms (one wave per pair from 128 pairs per slice on, a 256-thread workgroup below), slice
+ * counts and overlap settings.
+ * Flags (epipolar record slot 10); with a flag other than 0 the record / out is untouched and every point row is 0:
+ *   0 success.
+ *   1 not attempted: fewer than 3 kept points; d0, `scaling` or n0.e is 0 or e_z == 0; N0 has an eigenvalue not above eps 3 m times
+ *     its largest; a sum, an input or a result is not finite (a kept point on the epipole, |b_i| = 0, is such a case); in the stream
+ *     steps the solve did not solve (record[15] == 0).
+ *   2 unobservable: P H P has fewer than two positive eigenvalues, or the predicted 1 sigma of the direction exceeds sigma_max
+ *     (radians; +inf disables the gate).  This is what stops a hover, where the direction is noise.
+ *   3 no scale: fewer than anchor_min anchor points, or s is not finite or s <= 0.
+ * On flag 0: record / out fields 0-2 become v (the stage entry takes omega x t off when t is given); field 3 becomes sum w r_i^2, the
+ * squared flow across the epipolar lines - NOT the solve's residual sum w |sA X v - sB X q|^2, and not comparable with it; record
+ * fields 8-10 become R (v - omega x offset).  Everything else stays.
+ * Epipolar record, OFK_EPI_DOUBLES per problem: 0-2 t^; 3 s; 4 sigma^; 5 sum w r_i^2; 6-8 fields 0-2 of the solve's record before;
+ * 9 its residual before; 10 flag; 11 kept points; 12 anchor points; 13 points with kappa <= 0; 14-16 the generalised eigenvalues of
+ * (E, N0), descending (16 is lambda_1, the Rayleigh quotient above); 17 predicted 1 sigma of the direction; 18-23 C_t, upper triangle (xx xy xz yy yz zz); 24 var(s);
+ * 25-30 C_v, upper triangle; 31 reserved, 0.  With flag 1 everything but 6-11 is 0; with flag 2 slots 3, 18-30 are 0
+ * (17 is +inf where P H P is singular); with flag 3 slots 3 and 24-30 are 0.
+ * Point rows, [max_pts][4] per problem (ofk_epipolar_points_download; [n][4] in the stage entry): rho_i, r_i, |b_i| and the point
+ * flag - 0 used, 1 not kept (or past the pair's count), 2 used with kappa_i <= 0 (rho_i <= 0).  Rows of a problem whose record
+ * carries a flag are 0 throughout.
+ * ofk_set_epipolar (NULL or mode OFK_EPI_OFF: off) is a context setting read by ofk_pairs_run (every slice), ofk_stream_step[_jpeg] and
+ * ofk_stream_step_fused[_jpeg]; ofk_pairs_filter_step behind such a run reads the rewritten records.  In the fused step with a filter
+ * the fuse kernel leaves the filter at its prediction and the epipolar kernel behind it corrects with the rewritten v / v_uav,
+ * rewrites fused[0..7] and repeats vel_overwrite; under use_imu n0, omega and R are the IMU state's.  The camera model, the rolling
+ * shutter and finite motion hand their ideal points to this solve as to every other.
+ * Refused with OFK_E_INVALID before any launch, the previous setting staying in place: an unknown mode or weights; anchor <= 0 or NaN;
+ * anchor_min < 1; sigma_max <= 0 or NaN; a beam of zero length or not finite.  Refused with OFK_E_INVALID by the runs and steps where
+ * the setting is on: OFK_SOLVE_OFMODULE, OFK_FLOW_ROTATIONAL and OFK_KEEP_LEGACY (not the sensor model), and ofk_set_joint,
+ * ofk_set_plane or ofk_set_cov together with this one (all three rest on the plane).
+ * ofk_epipolar_download: epi [batch][OFK_EPI_DOUBLES] of the latest run / step with the setting on (`batch` is that run's own);
+ * ofk_epipolar_points_download: points [batch][max_pts][4] of the same run; both OFK_E_INVALID before such a run.
+ * ofk_velocity_solve_epipolar = ofk_velocity_solve_joint's arguments with the epipolar setting (mode OFK_EPI_ON) in the joint
+ * setting's place; out as ofk_velocity_solve after the rewrite, epi [batch][OFK_EPI_DOUBLES], points [batch][n][4].  wgt is there for
+ * the solve entries' common signature alone and must be NULL. */
+#define OFK_EPI_OFF 0
+#define OFK_EPI_ON 1
+#define OFK_EPI_W_ONE 0
+#define OFK_EPI_W_ROBUST 1
+#define OFK_EPI_DOUBLES 32
+typedef struct ofk_epipolar { int mode; double anchor; int anchor_min; double sigma_max; double beam[3]; int weights; } ofk_epipolar;
+int ofk_set_epipolar(ofk_ctx *ctx, const ofk_epipolar *e);
+int ofk_get_epipolar(const ofk_ctx *ctx, ofk_epipolar *e);
+int ofk_epipolar_download(ofk_ctx *ctx, double *epi);
+int ofk_epipolar_points_download(ofk_ctx *ctx, double *points);
+int ofk_velocity_solve_epipolar(ofk_ctx *ctx, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                                const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
+                                const ofk_robust *r, const ofk_epipolar *e, double *out, double *epi, double *points);
+
 /* optical_fusion.call_imu — node:61-89, batched over independent IMU streams, one message each.
  * state [batch][OFK_IMU_STATE]: vel[3], old_time, time_zero, first(0/1), rotation[9], normal[3], ang[3], ang_err[3]
  * msg   [batch][OFK_IMU_MSG]  : secs, nsecs, qx,qy,qz,qw, wx,wy,wz, cov0,cov4,cov8, ax,ay,az */
