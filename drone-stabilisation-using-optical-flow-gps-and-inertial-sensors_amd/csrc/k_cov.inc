@@ -104,12 +104,10 @@ __device__ __forceinline__ void cov_core(double (*part)[COV_SUMS], int n, int va
             double x, y, ux, uy, w;
             if (terms(i, x, y, ux, uy, w)) cov_point(s, variant, x, y, ux, uy, w, nrm, om, d, v);
         }
-#pragma unroll
-        for (int k = 0; k < COV_SUMS; ++k) { const double t = wave_sum(s[k]); if (lane == 0) part[vw][k] = t; }
+        team_put<COV_SUMS>(part[vw], s);
     }
-    if (NW == 1) __builtin_amdgcn_wave_barrier(); else __syncthreads();
-    if (threadIdx.x == 0)
-        for (int k = 0; k < COV_SUMS; ++k) part[0][k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+    team_barrier<NW>();
+    if (threadIdx.x == 0) team_sums<COV_SUMS>(part, part[0]);
 }
 
 __device__ __forceinline__ void cov_void(double *o)
@@ -198,96 +196,6 @@ static cov_cfg cov_make_cfg(const ofk_cov *c)
     return cc;
 }
 
-// ------------------------------------------------------------------------------------------------ stage entry (host buffers)
-// Behind k_solve / k_solve_robust: out holds the solve's eight doubles (v less omega x t when t is given), weights (nullable) the robust
-// solve's.  sigma_flow / sigma_pos are in the units of x and u.
-__global__ __launch_bounds__(256) void k_cov_solve(int variant, const double *__restrict__ x, const double *__restrict__ u,
-                                                   const uint8_t *__restrict__ valid, int n, const double *__restrict__ d,
-                                                   const double *__restrict__ nrm, const double *__restrict__ omega,
-                                                   const double *__restrict__ t, const double *__restrict__ weights, cov_cfg cc,
-                                                   const double *__restrict__ out, double *__restrict__ cov)
-{
-    __shared__ double part[4][COV_SUMS];
-    const int b = blockIdx.x;
-    const double *xb = x + (size_t)b * n * 2, *ub = u + (size_t)b * n * 2;
-    const uint8_t *vb = valid ? valid + (size_t)b * n : nullptr;
-    const double *wb = weights ? weights + (size_t)b * n : nullptr;
-    const double nb[3] = {nrm[3 * b], nrm[3 * b + 1], nrm[3 * b + 2]}, ob[3] = {omega[3 * b], omega[3 * b + 1], omega[3 * b + 2]};
-    const double db = d[b];
-    const double *o = out + (size_t)b * OFK_SOLVE_DOUBLES;
-    double v[3] = {o[0], o[1], o[2]};
-    if (t) {                                                    // the record holds v - omega x t
-        const double *tb = t + 3 * b;
-        v[0] += ob[1] * tb[2] - ob[2] * tb[1]; v[1] += ob[2] * tb[0] - ob[0] * tb[2]; v[2] += ob[0] * tb[1] - ob[1] * tb[0];
-    }
-    cov_core<4>(part, n, variant, nb, ob, db, v, [&](int i, double &px, double &py, double &ux, double &uy, double &w) {
-        if (vb && !vb[i]) return false;
-        w = wb ? wb[i] : 1.0;
-        if (!(w > 0.0)) return false;
-        px = xb[2 * i]; py = xb[2 * i + 1]; ux = ub[2 * i]; uy = ub[2 * i + 1];
-        return true;
-    });
-    if (threadIdx.x == 0) {
-        const double ovar[3] = {cc.so[0] * cc.so[0], cc.so[1] * cc.so[1], cc.so[2] * cc.so[2]};
-        cov_finish(part[0], cc, cc.sf, cc.sp, ovar, ob, t ? t + 3 * b : nullptr, nullptr, o[3], o[4], db != 0.0, cov + (size_t)b * OFK_COV_DOUBLES);
-    }
-}
-
-void ofk_launch_cov_solve(hipStream_t s, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
-                          const double *d, const double *nrm, const double *omega, const double *t, const double *weights,
-                          const ofk_cov *c, const double *out, double *cov)
-{
-    hipLaunchKernelGGL(k_cov_solve, dim3(batch), dim3(256), 0, s, variant, x, u, valid, n, d, nrm, omega, t, weights, cov_make_cfg(c), out, cov);
-}
-
-// ------------------------------------------------------------------------------------------------ frame pairs / plain stream step
-// Behind k_pairs_solve[_wg] / k_pairs_robust: the same inputs, the pair's record and (robust) weight row.  sigma_flow / sigma_pos are
-// pixels: the points are scaled by the pair's `scaling`, so are they.
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void k_pairs_cov(const float *__restrict__ prev_pts, const float *__restrict__ next_pts,
-                                                       const uint8_t *__restrict__ status, const int *__restrict__ counts, int pts_stride,
-                                                       const double *__restrict__ sensors, int variant, int use_feas, double feas_T,
-                                                       const double *__restrict__ weights, cov_cfg cc,
-                                                       const double *__restrict__ records, double *__restrict__ cov)
-{
-    __shared__ double part[4][COV_SUMS];
-    const int b = blockIdx.x;
-    const double *sn = sensors + (size_t)b * OFK_SENSOR_DOUBLES;
-    const double d = sn[0], nrm[3] = {sn[1], sn[2], sn[3]}, om[3] = {sn[4], sn[5], sn[6]};
-    const double scaling = sn[19], cx = sn[20], cy = sn[21], vp[3] = {sn[22], sn[23], sn[24]};
-    const int n = min(max(counts[b], 0), pts_stride);
-    const float *pp = prev_pts + (size_t)b * pts_stride * 2, *np_ = next_pts + (size_t)b * pts_stride * 2;
-    const uint8_t *st = status + (size_t)b * pts_stride;
-    const double *wrow = weights ? weights + (size_t)b * pts_stride : nullptr;
-    const double *r = records + (size_t)b * OFK_RECORD_DOUBLES;
-    const double v[3] = {r[0], r[1], r[2]};
-    cov_core<NW>(part, n, variant, nrm, om, d, v, [&](int i, double &x, double &y, double &ux, double &uy, double &w) {
-        if (!st[i]) return false;
-        w = wrow ? wrow[i] : 1.0;
-        if (!(w > 0.0)) return false;
-        return pair_point(pp, np_, i, cx, cy, scaling, use_feas, feas_T, nrm, vp, d, x, y, ux, uy);
-    });
-    if (threadIdx.x == 0) {
-        const double ovar[3] = {cc.so[0] * cc.so[0], cc.so[1] * cc.so[1], cc.so[2] * cc.so[2]};
-        cov_finish(part[0], cc, cc.sf * scaling, cc.sp * scaling, ovar, om, sn + 16, sn + 7, r[3], r[4], scaling != 0.0 && d != 0.0,
-                   cov + (size_t)b * OFK_COV_DOUBLES);
-    }
-}
-
-void ofk_launch_pairs_cov(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts,
-                          int pts_stride, const double *sensors, int variant, int use_feas, double feas_T, const double *weights,
-                          const ofk_cov *c, const double *records, double *cov, int batch)
-{
-    const cov_cfg cc = cov_make_cfg(c);
-    // ofk_launch_pairs_solve's rule and reason
-    if (batch >= 128)
-        hipLaunchKernelGGL(k_pairs_cov<1>, dim3(batch), dim3(64), 0, s, prev_pts, next_pts, status, counts, pts_stride, sensors, variant,
-                           use_feas, feas_T, weights, cc, records, cov);
-    else
-        hipLaunchKernelGGL(k_pairs_cov<4>, dim3(batch), dim3(256), 0, s, prev_pts, next_pts, status, counts, pts_stride, sensors, variant,
-                           use_feas, feas_T, weights, cc, records, cov);
-}
-
 // ------------------------------------------------------------------------------------------------ the filter's correct with R_eff
 // R_eff = Rm with its top-left 3x3 block replaced by z_sign^2 C + r_floor I (filter_r, a covariance that is not void), else Rm;
 // NIS = nu^T S^-1 nu of the correct; with nis_max > 0 a correct whose NIS exceeds it is skipped (x, P stay at the prediction).
@@ -364,65 +272,85 @@ void ofk_launch_kf_records_cov(hipStream_t s, int ns, int nm, const double *mats
                        z_source, batch);
 }
 
-// ------------------------------------------------------------------------------------------------ fused stream step
-// Behind k_stream_fuse / k_stream_fuse_robust, which with a covariance setting on leave the filter at its prediction (fuse_args.defer):
-// `status` holds the keep flags by now, so the set is status (and w > 0).  The correct runs here, with R_eff, and fused[0..7] is rewritten.
+// ------------------------------------------------------------------------------------------------ the three forms (k_second.inc)
+// The covariance never rewrites the record: no write-back.  sigma_flow / sigma_pos are in the units of the points: of x and u at the
+// stage entry, pixels scaled by the pair's `scaling` in the resident forms.
+__global__ __launch_bounds__(256) void k_cov_solve(int variant, const double *__restrict__ x, const double *__restrict__ u,
+                                                   const uint8_t *__restrict__ valid, int n, const double *__restrict__ d,
+                                                   const double *__restrict__ nrm, const double *__restrict__ omega,
+                                                   const double *__restrict__ t, const double *__restrict__ weights, cov_cfg cc,
+                                                   const double *__restrict__ out, double *__restrict__ cov)
+{
+    __shared__ double part[4][COV_SUMS];
+    const int b = blockIdx.x;
+    stage_problem q;
+    stage_unpack(q, b, x, u, valid, n, d, nrm, omega, t, weights, out);
+    cov_core<4>(part, n, variant, q.nrm, q.om, q.d, q.vs, q.pts);
+    if (threadIdx.x == 0) {
+        double ovar[3];
+        gyro_variances(cc, nullptr, ovar);
+        cov_finish(part[0], cc, cc.sf, cc.sp, ovar, q.om, q.t, nullptr, q.rec03[3], q.rank, q.d != 0.0, cov + (size_t)b * OFK_COV_DOUBLES);
+    }
+}
+
+void ofk_launch_cov_solve(hipStream_t s, const ofk_stage_in &in, const double *weights, const ofk_cov *c, const double *out, double *cov)
+{
+    hipLaunchKernelGGL(k_cov_solve, dim3(in.batch), dim3(256), 0, s, in.variant, in.x, in.u, in.valid, in.n, in.d, in.nrm, in.omega, in.t,
+                       weights, cov_make_cfg(c), out, cov);
+}
+
+// thread 0, behind cov_core: the problem's record
+__device__ __forceinline__ void cov_resident_finish(const double *sums, const cov_cfg &cc, const resident_problem &q, double *cv)
+{
+    double ovar[3];
+    gyro_variances(cc, q.ist, ovar);
+    cov_finish(sums, cc, cc.sf * q.scaling, cc.sp * q.scaling, ovar, q.om, q.sn + 16, q.R, q.rec03[3], q.rank, q.scaling != 0.0 && q.d != 0.0, cv);
+}
+
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_pairs_cov(const float *__restrict__ prev_pts, const float *__restrict__ next_pts,
+                                                       const uint8_t *__restrict__ status, const int *__restrict__ counts, int pts_stride,
+                                                       const double *__restrict__ sensors, int variant, int use_feas, double feas_T,
+                                                       const double *__restrict__ weights, cov_cfg cc,
+                                                       const double *__restrict__ records, double *__restrict__ cov)
+{
+    __shared__ double part[4][COV_SUMS];
+    const int b = blockIdx.x;
+    resident_problem q;
+    resident_unpack(q, b, prev_pts, next_pts, status, counts, pts_stride, sensors, nullptr, false, use_feas, feas_T, weights, records);
+    cov_core<NW>(part, q.n, variant, q.nrm, q.om, q.d, q.rec03, q.pts);
+    if (threadIdx.x == 0) cov_resident_finish(part[0], cc, q, cov + (size_t)b * OFK_COV_DOUBLES);
+}
+
+void ofk_launch_pairs_cov(hipStream_t s, const ofk_pairs_in &in, const double *weights, const ofk_cov *c, double *cov)
+{
+    launch_pairs_form(s, in.batch, k_pairs_cov<1>, k_pairs_cov<4>, in.prev_pts, in.next_pts, in.status, in.counts, in.pts_stride, in.sensors,
+                      in.variant, in.use_feas, in.feas_T, weights, cov_make_cfg(c), (const double *)in.records, cov);
+}
+
+// With the filter on the fused kernel deferred its correct: it runs here, with R_eff, and writes NIS and the gate into the record.
 __global__ __launch_bounds__(256) void k_stream_cov(fuse_args g, const double *__restrict__ weights, cov_cfg cc, double *__restrict__ cov)
 {
     __shared__ double part[4][COV_SUMS];
     const int b = blockIdx.x;
-    const double *sn = g.sensors + (size_t)b * OFK_SENSOR_DOUBLES;
-    const double d = sn[0], scaling = sn[19], cx = sn[20], cy = sn[21];
-    const double *ist = g.f.use_imu && g.imu_state ? g.imu_state + (size_t)b * OFK_IMU_STATE : nullptr;
-    double nrm[3], om[3];
-    for (int k = 0; k < 3; ++k) { nrm[k] = ist ? ist[15 + k] : sn[1 + k]; om[k] = ist ? ist[18 + k] : sn[4 + k]; }
-    const int n = min(max(g.counts[b], 0), g.pts_stride);
-    const float *pp = g.prev_pts + (size_t)b * g.pts_stride * 2, *np_ = g.next_pts + (size_t)b * g.pts_stride * 2;
-    const uint8_t *st = g.status + (size_t)b * g.pts_stride;
-    const double *wrow = weights ? weights + (size_t)b * g.pts_stride : nullptr;
-    const double *r = g.records + (size_t)b * OFK_RECORD_DOUBLES;
-    const double v[3] = {r[0], r[1], r[2]};
-    cov_core<4>(part, n, g.variant, nrm, om, d, v, [&](int i, double &x, double &y, double &ux, double &uy, double &w) {
-        if (!st[i]) return false;
-        w = wrow ? wrow[i] : 1.0;
-        if (!(w > 0.0)) return false;
-        return pair_point(pp, np_, i, cx, cy, scaling, 0, 0.0, nrm, v, d, x, y, ux, uy);     // fuse_terms' x, y, u of OFK_FLOW_LK
-    });
+    resident_problem q;
+    stream_unpack(q, b, g, weights);
+    cov_core<4>(part, q.n, g.variant, q.nrm, q.om, q.d, q.rec03, q.pts);
     if (threadIdx.x == 0) {
         double *cv = cov + (size_t)b * OFK_COV_DOUBLES;
-        double ovar[3];
-        for (int k = 0; k < 3; ++k) ovar[k] = cc.omega_from_imu && ist ? ist[21 + k] : cc.so[k] * cc.so[k];
-        cov_finish(part[0], cc, cc.sf * scaling, cc.sp * scaling, ovar, om, sn + 16, ist ? ist + 6 : sn + 7, r[3], r[4],
-                   scaling != 0.0 && d != 0.0, cv);
+        cov_resident_finish(part[0], cc, q, cv);
         if (g.f.filter && g.defer) {
-            double kx[KF_MAX], kP[KF_MAX][KF_MAX], nis = 0.0, gated = 0.0;
-            kf_load(g.ns, b, g.kf_x, g.kf_P, kx, kP);
-            const bool solved = r[15] != 0.0;
-            if (solved) {
-                double z[KF_MAX] = {0, 0, 0, 0, 0, 0};
-                for (int k = 0; k < 3; ++k) z[k] = g.f.z_sign * r[(g.f.z_source ? 8 : 0) + k];
-                for (int k = 3; k < g.nm; ++k) z[k] = sn[22 + (k - 3)];
-                gated = kf_correct_cov_dev(g.ns, g.nm, g.H, g.Rm, z, cv, cc, g.f.z_sign, g.f.z_source, kx, kP, nis) ? 1.0 : 0.0;
-                kf_store(g.ns, b, kx, kP, g.kf_x, g.kf_P);
-            }
-            cv[14] = nis; cv[15] = gated;
-            double *fu = g.fused + (size_t)b * 8, tr = 0.0;
-            for (int i = 0; i < g.ns; ++i) tr += kP[i][i];
-            for (int k = 0; k < 6; ++k) fu[k] = k < g.ns ? kx[k] : 0.0;
-            fu[6] = tr; fu[7] = solved ? 1.0 : 0.0;
+            double kx[KF_MAX], kP[KF_MAX][KF_MAX], z[KF_MAX], nis = 0.0;
+            bool gated = false;
+            deferred_load(g, q, b, g.records + (size_t)b * OFK_RECORD_DOUBLES, kx, kP, z);
+            if (q.solved) gated = kf_correct_cov_dev(g.ns, g.nm, g.H, g.Rm, z, cv, cc, g.f.z_sign, g.f.z_source, kx, kP, nis);
+            cv[14] = nis; cv[15] = gated ? 1.0 : 0.0;
+            deferred_store(g, q, b, kx, kP);
         }
     }
 }
 
-void ofk_launch_stream_cov(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
-                           const double *sensors, double *imu_state, int ns, int nm, int nc, const double *kf_mats, double *kf_x, double *kf_P,
-                           const ofk_fusion *f, int variant, double *records, double *fused, const double *weights, const ofk_cov *c,
-                           double *cov, int batch)
+void ofk_launch_stream_cov(hipStream_t s, const ofk_stream_in &in, const double *weights, const ofk_cov *c, double *cov)
 {
-    fuse_args g;
-    g.prev_pts = prev_pts; g.next_pts = next_pts; g.status = status; g.counts = counts; g.pts_stride = pts_stride; g.sensors = sensors;
-    g.imu_state = imu_state; g.imu_dv = nullptr; g.ns = ns; g.nm = nm; g.nc = nc;
-    g.F = kf_mats; g.Bm = kf_mats + 36; g.H = kf_mats + 72; g.Q = kf_mats + 108; g.Rm = kf_mats + 144; g.kf_x = kf_x; g.kf_P = kf_P;
-    g.f = *f; g.variant = variant; g.use_feas = 0; g.feas_T = 0.0; g.records = records; g.fused = fused; g.defer = 1;
-    hipLaunchKernelGGL(k_stream_cov, dim3(batch), dim3(256), 0, s, g, weights, cov_make_cfg(c), cov);
+    hipLaunchKernelGGL(k_stream_cov, dim3(in.batch), dim3(256), 0, s, make_fuse_args(in, nullptr, 0, 0.0), weights, cov_make_cfg(c), cov);
 }

@@ -41,9 +41,10 @@
 struct epi_cfg { double anchor, smax, e[3]; int amin, wmode; };
 
 // Flag 1's rule on the inputs: range, scale and n0.e are finite and not 0, the beam leaves the image plane.
-__device__ __forceinline__ bool epi_usable(double d, double scaling, double ne, double ez)
+__device__ __forceinline__ bool epi_usable(const epi_cfg &ec, const double *nrm, double d, double scaling)
 {
-    return isfinite(d) && d != 0.0 && isfinite(scaling) && scaling != 0.0 && isfinite(ne) && ne != 0.0 && ez != 0.0;
+    const double ne = nrm[0] * ec.e[0] + nrm[1] * ec.e[1] + nrm[2] * ec.e[2];
+    return isfinite(d) && d != 0.0 && isfinite(scaling) && scaling != 0.0 && isfinite(ne) && ne != 0.0 && ec.e[2] != 0.0;
 }
 
 // One lane, after the first walk: t^ from the 13 sums, and tnt = t^^T N0 t^.  er is written in full (flag 1); returns whether the second
@@ -148,17 +149,16 @@ __device__ __forceinline__ bool epi_core(double (*part)[EPI_SUMS2], double *bc, 
             s[EPI_N + 3] += w; s[EPI_N + 4] += w * (-y); s[EPI_N + 5] += w * (x * x + y * y);
             s[EPI_CNT] += 1.0;
         }
-#pragma unroll
-        for (int k = 0; k < EPI_SUMS1; ++k) { const double t = wave_sum(s[k]); if (lane == 0) part[vw][k] = t; }
+        team_put<EPI_SUMS1>(part[vw], s);
     }
-    if (NW == 1) __builtin_amdgcn_wave_barrier(); else __syncthreads();
+    team_barrier<NW>();
     if (threadIdx.x == 0) {
         double t[EPI_SUMS1], th[3];
-        for (int k = 0; k < EPI_SUMS1; ++k) t[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+        team_sums<EPI_SUMS1>(part, t);
         const bool go = epi_direction(t, usable, rec03, th, tnt, er);
         bc[0] = th[0]; bc[1] = th[1]; bc[2] = th[2]; bc[3] = go ? 1.0 : 0.0;
     }
-    if (NW == 1) __builtin_amdgcn_wave_barrier(); else __syncthreads();
+    team_barrier<NW>();
     const double t0 = bc[0], t1 = bc[1], t2 = bc[2];
     const bool go = bc[3] != 0.0;
     const double pe0 = ec.e[0] / ec.e[2], pe1 = ec.e[1] / ec.e[2], an2 = anchor * anchor;
@@ -189,24 +189,23 @@ __device__ __forceinline__ bool epi_core(double (*part)[EPI_SUMS2], double *bc, 
                 s[EPI_NLE] += kap <= 0.0 ? 1.0 : 0.0; s[EPI_NGE] += kap >= 0.0 ? 1.0 : 0.0;
                 row[0] = kap; row[1] = r; row[2] = nb; row[3] = 0.0;
             }
-#pragma unroll
-            for (int k = 0; k < EPI_SUMS2; ++k) { const double t = wave_sum(s[k]); if (lane == 0) part[vw][k] = t; }
+            team_put<EPI_SUMS2>(part[vw], s);
         }
     }
-    if (NW == 1) __builtin_amdgcn_wave_barrier(); else __syncthreads();
+    team_barrier<NW>();
     if (threadIdx.x == 0) {
         double tv[3] = {0.0, 0.0, 0.0}, o[2] = {1.0, 1.0};
         int flag = 1;
         if (go) {
             double t[EPI_SUMS2], th[3] = {t0, t1, t2};
-            for (int k = 0; k < EPI_SUMS2; ++k) t[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+            team_sums<EPI_SUMS2>(part, t);
             flag = epi_finish(t, ec, tnt, th, tv, o, er);
             er[10] = (double)flag;
             bc[7] = t[EPI_RSS];
         }
         bc[0] = tv[0]; bc[1] = tv[1]; bc[2] = tv[2]; bc[4] = flag == 0 ? 1.0 : 0.0; bc[5] = o[0]; bc[6] = o[1];
     }
-    if (NW == 1) __builtin_amdgcn_wave_barrier(); else __syncthreads();
+    team_barrier<NW>();
     const bool rw = bc[4] != 0.0;
     const double sraw = bc[5], sgn = bc[6];
     for (int k = 0; k < 3; ++k) v[k] = bc[k];
@@ -234,9 +233,14 @@ static epi_cfg epi_make_cfg(const ofk_epipolar *e)
     return ec;
 }
 
-// ------------------------------------------------------------------------------------------------ stage entry (host buffers)
-// Behind k_solve / k_solve_robust: out holds the solve's eight doubles (v less omega x t when t is given) and is rewritten in place,
-// weights (nullable) the robust solve's, read only under OFK_EPI_W_ROBUST.  anchor is in the units of x and u.
+// ------------------------------------------------------------------------------------------------ the three forms (k_second.inc)
+// The robust weights are read only under OFK_EPI_W_ROBUST.  anchor is in the units of the points: of x and u at the stage entry, pixels
+// scaled by the pair's `scaling` in the resident forms.  A stream step whose solve did not solve (record[15] == 0) is not attempted.
+__device__ __forceinline__ const double *epi_weights(const epi_cfg &ec, const double *weights)
+{
+    return ec.wmode == OFK_EPI_W_ROBUST ? weights : nullptr;
+}
+
 __global__ __launch_bounds__(256) void k_epi_solve(const double *__restrict__ x, const double *__restrict__ u, const uint8_t *__restrict__ valid,
                                                    int n, const double *__restrict__ d, const double *__restrict__ nrm,
                                                    const double *__restrict__ omega, const double *__restrict__ t,
@@ -246,41 +250,21 @@ __global__ __launch_bounds__(256) void k_epi_solve(const double *__restrict__ x,
     __shared__ double part[4][EPI_SUMS2];
     __shared__ double bc[8];
     const int b = blockIdx.x;
-    const double *xb = x + (size_t)b * n * 2, *ub = u + (size_t)b * n * 2;
-    const uint8_t *vb = valid ? valid + (size_t)b * n : nullptr;
-    const double *wb = weights && ec.wmode == OFK_EPI_W_ROBUST ? weights + (size_t)b * n : nullptr;
-    const double nb[3] = {nrm[3 * b], nrm[3 * b + 1], nrm[3 * b + 2]}, ob[3] = {omega[3 * b], omega[3 * b + 1], omega[3 * b + 2]};
-    const double db = d[b];
-    double *o = out + (size_t)b * OFK_SOLVE_DOUBLES;
-    const double rec03[4] = {o[0], o[1], o[2], o[3]};
-    const double ne = nb[0] * ec.e[0] + nb[1] * ec.e[1] + nb[2] * ec.e[2];
+    stage_problem q;
+    stage_unpack(q, b, x, u, valid, n, d, nrm, omega, t, epi_weights(ec, weights), out);
     double v[3], rss;
-    const bool rw = epi_core<4>(part, bc, n, n, nb, ob, db, rec03, epi_usable(db, 1.0, ne, ec.e[2]), ec.anchor, ec,
-                                epi + (size_t)b * OFK_EPI_DOUBLES, pts + (size_t)b * n * 4, v, rss,
-                                [&](int i, double &px, double &py, double &ux, double &uy, double &w) {
-        if (vb && !vb[i]) return false;
-        w = wb ? wb[i] : 1.0;
-        if (!(w > 0.0)) return false;
-        px = xb[2 * i]; py = xb[2 * i + 1]; ux = ub[2 * i]; uy = ub[2 * i + 1];
-        return true;
-    });
-    if (rw && threadIdx.x == 0) {
-        if (t) sub_cross(v, ob, t + 3 * b, o);
-        else { o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; }
-        o[3] = rss;
-    }
+    const bool rw = epi_core<4>(part, bc, n, n, q.nrm, q.om, q.d, q.rec03, epi_usable(ec, q.nrm, q.d, 1.0), ec.anchor, ec,
+                                epi + (size_t)b * OFK_EPI_DOUBLES, pts + (size_t)b * n * 4, v, rss, q.pts);
+    stage_write(q, rw, v, q.om, rss, out + (size_t)b * OFK_SOLVE_DOUBLES);
 }
 
-void ofk_launch_epi_solve(hipStream_t s, const double *x, const double *u, const uint8_t *valid, int batch, int n, const double *d,
-                          const double *nrm, const double *omega, const double *t, const double *weights, const ofk_epipolar *e,
-                          double *out, double *epi, double *pts)
+void ofk_launch_epi_solve(hipStream_t s, const ofk_stage_in &in, const double *weights, const ofk_epipolar *e, double *out, double *epi,
+                          double *pts)
 {
-    hipLaunchKernelGGL(k_epi_solve, dim3(batch), dim3(256), 0, s, x, u, valid, n, d, nrm, omega, t, weights, epi_make_cfg(e), out, epi, pts);
+    hipLaunchKernelGGL(k_epi_solve, dim3(in.batch), dim3(256), 0, s, in.x, in.u, in.valid, in.n, in.d, in.nrm, in.omega, in.t, weights,
+                       epi_make_cfg(e), out, epi, pts);
 }
 
-// ------------------------------------------------------------------------------------------------ frame pairs / plain stream step
-// Behind k_pairs_solve[_wg] / k_pairs_robust: the same inputs, the pair's record (rewritten in place) and (robust) weight row.
-// anchor is pixels: the points are scaled by the pair's `scaling`, so is it.
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void k_pairs_epi(const float *__restrict__ prev_pts, const float *__restrict__ next_pts,
                                                        const uint8_t *__restrict__ status, const int *__restrict__ counts, int pts_stride,
@@ -291,117 +275,36 @@ __global__ __launch_bounds__(64 * NW) void k_pairs_epi(const float *__restrict__
     __shared__ double part[4][EPI_SUMS2];
     __shared__ double bc[8];
     const int b = blockIdx.x;
-    const double *sn = sensors + (size_t)b * OFK_SENSOR_DOUBLES;
-    const double d = sn[0], nrm[3] = {sn[1], sn[2], sn[3]}, om[3] = {sn[4], sn[5], sn[6]};
-    const double scaling = sn[19], cx = sn[20], cy = sn[21], vp[3] = {sn[22], sn[23], sn[24]};
-    const int n = min(max(counts[b], 0), pts_stride);
-    const float *pp = prev_pts + (size_t)b * pts_stride * 2, *np_ = next_pts + (size_t)b * pts_stride * 2;
-    const uint8_t *st = status + (size_t)b * pts_stride;
-    const double *wrow = weights && ec.wmode == OFK_EPI_W_ROBUST ? weights + (size_t)b * pts_stride : nullptr;
-    double *r = records + (size_t)b * OFK_RECORD_DOUBLES;
-    const double rec03[4] = {r[0], r[1], r[2], r[3]};
-    const double ne = nrm[0] * ec.e[0] + nrm[1] * ec.e[1] + nrm[2] * ec.e[2];
+    resident_problem q;
+    resident_unpack(q, b, prev_pts, next_pts, status, counts, pts_stride, sensors, nullptr, false, use_feas, feas_T, epi_weights(ec, weights),
+                    records);
     double v[3], rss;
-    const bool rw = epi_core<NW>(part, bc, n, pts_stride, nrm, om, d, rec03, epi_usable(d, scaling, ne, ec.e[2]),
-                                 ec.anchor * scaling, ec, epi + (size_t)b * OFK_EPI_DOUBLES, pts + (size_t)b * pts_stride * 4, v, rss,
-                                 [&](int i, double &x, double &y, double &ux, double &uy, double &w) {
-        if (!st[i]) return false;
-        w = wrow ? wrow[i] : 1.0;
-        if (!(w > 0.0)) return false;
-        return pair_point(pp, np_, i, cx, cy, scaling, use_feas, feas_T, nrm, vp, d, x, y, ux, uy);
-    });
-    if (rw && threadIdx.x == 0) {
-        double vu[3];
-        lever_rotate(v, om, sn + 16, sn + 7, vu);
-        r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = rss; r[8] = vu[0]; r[9] = vu[1]; r[10] = vu[2];
-    }
+    const bool rw = epi_core<NW>(part, bc, q.n, pts_stride, q.nrm, q.om, q.d, q.rec03, epi_usable(ec, q.nrm, q.d, q.scaling),
+                                 ec.anchor * q.scaling, ec, epi + (size_t)b * OFK_EPI_DOUBLES, pts + (size_t)b * pts_stride * 4, v, rss, q.pts);
+    pairs_write(q, rw, v, q.om, rss, records + (size_t)b * OFK_RECORD_DOUBLES);
 }
 
-void ofk_launch_pairs_epi(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts,
-                          int pts_stride, const double *sensors, int use_feas, double feas_T, const double *weights, const ofk_epipolar *e,
-                          double *records, double *epi, double *pts, int batch)
+void ofk_launch_pairs_epi(hipStream_t s, const ofk_pairs_in &in, const double *weights, const ofk_epipolar *e, double *epi, double *pts)
 {
-    const epi_cfg ec = epi_make_cfg(e);
-    // ofk_launch_pairs_solve's rule and reason
-    if (batch >= 128)
-        hipLaunchKernelGGL(k_pairs_epi<1>, dim3(batch), dim3(64), 0, s, prev_pts, next_pts, status, counts, pts_stride, sensors, use_feas, feas_T,
-                           weights, ec, records, epi, pts);
-    else
-        hipLaunchKernelGGL(k_pairs_epi<4>, dim3(batch), dim3(256), 0, s, prev_pts, next_pts, status, counts, pts_stride, sensors, use_feas, feas_T,
-                           weights, ec, records, epi, pts);
+    launch_pairs_form(s, in.batch, k_pairs_epi<1>, k_pairs_epi<4>, in.prev_pts, in.next_pts, in.status, in.counts, in.pts_stride, in.sensors,
+                      in.use_feas, in.feas_T, weights, epi_make_cfg(e), in.records, epi, pts);
 }
 
-// ------------------------------------------------------------------------------------------------ fused stream step
-// Behind k_stream_fuse / k_stream_fuse_robust, which with the setting on leave the filter at its prediction (fuse_args.defer): `status`
-// holds the keep flags by now, so the set is status (and, under OFK_EPI_W_ROBUST, w > 0).  A step whose solve did not solve
-// (record[15] == 0) is not attempted.  The correct runs here with the epipolar v / v_uav (the solve's own where the record was left
-// alone), fused[0..7] is rewritten and vel_overwrite is repeated with the epipolar v_uav.
 __global__ __launch_bounds__(256) void k_stream_epi(fuse_args g, const double *__restrict__ weights, epi_cfg ec, double *__restrict__ epi,
                                                     double *__restrict__ pts)
 {
     __shared__ double part[4][EPI_SUMS2];
     __shared__ double bc[8];
     const int b = blockIdx.x;
-    const double *sn = g.sensors + (size_t)b * OFK_SENSOR_DOUBLES;
-    const double d = sn[0], scaling = sn[19], cx = sn[20], cy = sn[21];
-    double *ist = g.f.use_imu && g.imu_state ? g.imu_state + (size_t)b * OFK_IMU_STATE : nullptr;
-    double nrm[3], om[3];
-    for (int k = 0; k < 3; ++k) { nrm[k] = ist ? ist[15 + k] : sn[1 + k]; om[k] = ist ? ist[18 + k] : sn[4 + k]; }
-    const int n = min(max(g.counts[b], 0), g.pts_stride);
-    const float *pp = g.prev_pts + (size_t)b * g.pts_stride * 2, *np_ = g.next_pts + (size_t)b * g.pts_stride * 2;
-    const uint8_t *st = g.status + (size_t)b * g.pts_stride;
-    const double *wrow = weights && ec.wmode == OFK_EPI_W_ROBUST ? weights + (size_t)b * g.pts_stride : nullptr;
-    double *r = g.records + (size_t)b * OFK_RECORD_DOUBLES;
-    const double rec03[4] = {r[0], r[1], r[2], r[3]};
-    const bool solved = r[15] != 0.0;
-    const double ne = nrm[0] * ec.e[0] + nrm[1] * ec.e[1] + nrm[2] * ec.e[2];
+    resident_problem q;
+    stream_unpack(q, b, g, epi_weights(ec, weights));
     double v[3], rss;
-    const bool rw = epi_core<4>(part, bc, n, g.pts_stride, nrm, om, d, rec03,
-                                solved && epi_usable(d, scaling, ne, ec.e[2]), ec.anchor * scaling, ec,
-                                epi + (size_t)b * OFK_EPI_DOUBLES, pts + (size_t)b * g.pts_stride * 4, v, rss,
-                                [&](int i, double &x, double &y, double &ux, double &uy, double &w) {
-        if (!st[i]) return false;
-        w = wrow ? wrow[i] : 1.0;
-        if (!(w > 0.0)) return false;
-        return pair_point(pp, np_, i, cx, cy, scaling, 0, 0.0, nrm, rec03, d, x, y, ux, uy);  // fuse_terms' x, y, u of OFK_FLOW_LK
-    });
-    if (threadIdx.x == 0) {
-        double vu[3] = {r[8], r[9], r[10]};
-        if (rw) {
-            lever_rotate(v, om, sn + 16, ist ? ist + 6 : sn + 7, vu);
-            r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = rss; r[8] = vu[0]; r[9] = vu[1]; r[10] = vu[2];
-        }
-        double *fu = g.fused + (size_t)b * 8;
-        if (g.f.filter && g.defer) {
-            double kx[KF_MAX], kP[KF_MAX][KF_MAX];
-            kf_load(g.ns, b, g.kf_x, g.kf_P, kx, kP);
-            if (solved) {
-                double z[KF_MAX] = {0, 0, 0, 0, 0, 0};
-                for (int k = 0; k < 3; ++k) z[k] = g.f.z_sign * r[(g.f.z_source ? 8 : 0) + k];
-                for (int k = 3; k < g.nm; ++k) z[k] = sn[22 + (k - 3)];
-                kf_correct_dev(g.ns, g.nm, g.H, g.Rm, z, kx, kP);
-                kf_store(g.ns, b, kx, kP, g.kf_x, g.kf_P);
-            }
-            double tr = 0.0;
-            for (int i = 0; i < g.ns; ++i) tr += kP[i][i];
-            for (int k = 0; k < 6; ++k) fu[k] = k < g.ns ? kx[k] : 0.0;
-            fu[6] = tr; fu[7] = solved ? 1.0 : 0.0;
-        } else if (!g.f.filter && rw) {
-            fu[0] = vu[0]; fu[1] = vu[1]; fu[2] = vu[2];
-        }
-        if (g.f.vel_overwrite && solved && ist && rw) { ist[0] = vu[0]; ist[1] = vu[1]; ist[2] = vu[2]; }   // node:261
-    }
+    const bool rw = epi_core<4>(part, bc, q.n, g.pts_stride, q.nrm, q.om, q.d, q.rec03, q.solved && epi_usable(ec, q.nrm, q.d, q.scaling),
+                                ec.anchor * q.scaling, ec, epi + (size_t)b * OFK_EPI_DOUBLES, pts + (size_t)b * g.pts_stride * 4, v, rss, q.pts);
+    stream_tail(g, q, b, rw, v, q.om, rss);
 }
 
-void ofk_launch_stream_epi(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
-                           const double *sensors, double *imu_state, int ns, int nm, int nc, const double *kf_mats, double *kf_x, double *kf_P,
-                           const ofk_fusion *f, int variant, double *records, double *fused, const double *weights, const ofk_epipolar *e,
-                           double *epi, double *pts, int batch, int defer)
+void ofk_launch_stream_epi(hipStream_t s, const ofk_stream_in &in, const double *weights, const ofk_epipolar *e, double *epi, double *pts)
 {
-    fuse_args g;
-    g.prev_pts = prev_pts; g.next_pts = next_pts; g.status = status; g.counts = counts; g.pts_stride = pts_stride; g.sensors = sensors;
-    g.imu_state = imu_state; g.imu_dv = nullptr; g.ns = ns; g.nm = nm; g.nc = nc;
-    g.F = kf_mats; g.Bm = kf_mats + 36; g.H = kf_mats + 72; g.Q = kf_mats + 108; g.Rm = kf_mats + 144; g.kf_x = kf_x; g.kf_P = kf_P;
-    g.f = *f; g.variant = variant; g.use_feas = 0; g.feas_T = 0.0; g.records = records; g.fused = fused; g.defer = defer;
-    hipLaunchKernelGGL(k_stream_epi, dim3(batch), dim3(256), 0, s, g, weights, epi_make_cfg(e), epi, pts);
+    hipLaunchKernelGGL(k_stream_epi, dim3(in.batch), dim3(256), 0, s, make_fuse_args(in, nullptr, 0, 0.0), weights, epi_make_cfg(e), epi, pts);
 }

@@ -724,6 +724,19 @@ struct fuse_args {
     int defer;                                                   // 1: the filter stays at its prediction, k_stream_cov corrects (k_cov.inc)
 };
 
+// The kernels behind the fused one (k_second.inc) get imu_dv NULL and use_feas 0: the step's increments are consumed and `status` holds
+// the keep flags by then.
+static fuse_args make_fuse_args(const ofk_stream_in &in, double *imu_dv, int use_feas, double feas_T)
+{
+    fuse_args g;
+    g.prev_pts = in.prev_pts; g.next_pts = in.next_pts; g.status = in.status; g.counts = in.counts; g.pts_stride = in.pts_stride;
+    g.sensors = in.sensors; g.imu_state = in.imu_state; g.imu_dv = imu_dv; g.ns = in.ns; g.nm = in.nm; g.nc = in.nc;
+    g.F = in.kf_mats; g.Bm = in.kf_mats + 36; g.H = in.kf_mats + 72; g.Q = in.kf_mats + 108; g.Rm = in.kf_mats + 144;
+    g.kf_x = in.kf_x; g.kf_P = in.kf_P; g.f = *in.f; g.variant = in.variant; g.use_feas = use_feas; g.feas_T = feas_T;
+    g.records = in.records; g.fused = in.fused; g.defer = in.defer;
+    return g;
+}
+
 // Point i's terms: x, y (centred, scaled), the flow u, and in the legacy keep mode the weight dist_i with its r_tilde (rl).
 __device__ __forceinline__ void fuse_terms(const fuse_args &g, int i, const float *pp, const float *np_, double cx, double cy, double scaling,
                                            const double *nrm, const double *om, const double *vp, double &x, double &y, double &ux,
@@ -832,17 +845,9 @@ __global__ __launch_bounds__(256) void k_stream_fuse(fuse_args g)
     }
 }
 
-void ofk_launch_stream_fuse(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
-                            const double *sensors, double *imu_state, double *imu_dv, int ns, int nm, int nc, const double *kf_mats,
-                            double *kf_x, double *kf_P, const ofk_fusion *f, int variant, int use_feas, double feas_T, double *records,
-                            double *fused, int batch, int defer_correct)
+void ofk_launch_stream_fuse(hipStream_t s, const ofk_stream_in &in, double *imu_dv, int use_feas, double feas_T)
 {
-    fuse_args g;
-    g.prev_pts = prev_pts; g.next_pts = next_pts; g.status = status; g.counts = counts; g.pts_stride = pts_stride; g.sensors = sensors;
-    g.imu_state = imu_state; g.imu_dv = imu_dv; g.ns = ns; g.nm = nm; g.nc = nc;
-    g.F = kf_mats; g.Bm = kf_mats + 36; g.H = kf_mats + 72; g.Q = kf_mats + 108; g.Rm = kf_mats + 144; g.kf_x = kf_x; g.kf_P = kf_P;
-    g.f = *f; g.variant = variant; g.use_feas = use_feas; g.feas_T = feas_T; g.records = records; g.fused = fused; g.defer = defer_correct;
-    hipLaunchKernelGGL(k_stream_fuse, dim3(batch), dim3(256), 0, s, g);
+    hipLaunchKernelGGL(k_stream_fuse, dim3(in.batch), dim3(256), 0, s, make_fuse_args(in, imu_dv, use_feas, feas_T));
 }
 
 // ------------------------------------------------------------------------------------------------ Monte-Carlo error simulation
@@ -1276,6 +1281,9 @@ void ofk_launch_associate(hipStream_t s, const double *t_img, int n_img, int n_i
 
 // ------------------------------------------------------------------------------------------------ robust solve
 #include "k_robust.inc"
+
+// ------------------------------------------------------------------------------------------------ second-stage solves: the shared shells
+#include "k_second.inc"
 
 // ------------------------------------------------------------------------------------------------ velocity covariance
 #include "k_cov.inc"

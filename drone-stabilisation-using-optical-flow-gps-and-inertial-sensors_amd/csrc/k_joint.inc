@@ -142,18 +142,17 @@ __device__ __forceinline__ bool joint_core(double (*part)[JOINT_SUMS], double *b
             double x, y, ux, uy, w;
             if (terms(i, x, y, ux, uy, w)) joint_point(s, variant, x, y, ux, uy, w, nrm, om, d, vs);
         }
-#pragma unroll
-        for (int k = 0; k < JOINT_SUMS; ++k) { const double t = wave_sum(s[k]); if (lane == 0) part[vw][k] = t; }
+        team_put<JOINT_SUMS>(part[vw], s);
     }
-    if (NW == 1) __builtin_amdgcn_wave_barrier(); else __syncthreads();
+    team_barrier<NW>();
     if (threadIdx.x == 0) {
         double t[JOINT_SUMS], tv[3], to[3];
-        for (int k = 0; k < JOINT_SUMS; ++k) t[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+        team_sums<JOINT_SUMS>(part, t);
         const bool rw = joint_finish(t, usable, vs, rec03, om, dsf2, ovar, tv, to, jr);
         for (int k = 0; k < 3; ++k) { bc[k] = tv[k]; bc[3 + k] = to[k]; }
         bc[6] = rw ? 1.0 : 0.0;
     }
-    if (NW == 1) __builtin_amdgcn_wave_barrier(); else __syncthreads();
+    team_barrier<NW>();
     for (int k = 0; k < 3; ++k) { v[k] = bc[k]; omh[k] = bc[3 + k]; }
     const bool rw = bc[6] != 0.0;
     rss = 0.0;
@@ -168,11 +167,10 @@ __device__ __forceinline__ bool joint_core(double (*part)[JOINT_SUMS], double *b
             point_terms(variant, x, y, ux, uy, nrm, omh, d, 1.0, q0, q1, q2, a, b);
             r += w * resid_point(x, y, q0, q1, q2, a, b, v);
         }
-        r = wave_sum(r);
-        if (lane == 0) part[vw][0] = r;
+        team_put<1>(part[vw], &r);
     }
-    if (NW == 1) __builtin_amdgcn_wave_barrier(); else __syncthreads();
-    if (threadIdx.x == 0) rss = (part[0][0] + part[1][0]) + (part[2][0] + part[3][0]);
+    team_barrier<NW>();
+    if (threadIdx.x == 0) team_sums<1>(part, &rss);
     return true;
 }
 
@@ -184,9 +182,8 @@ static joint_cfg joint_make_cfg(const ofk_joint *j)
     return jc;
 }
 
-// ------------------------------------------------------------------------------------------------ stage entry (host buffers)
-// Behind k_solve / k_solve_robust: out holds the solve's eight doubles (v less omega x t when t is given) and is rewritten in place,
-// weights (nullable) the robust solve's.  sigma_flow is in the units of x and u.
+// ------------------------------------------------------------------------------------------------ the three forms (k_second.inc)
+// sigma_flow is in the units of the points: of x and u at the stage entry, pixels scaled by the pair's `scaling` in the resident forms.
 __global__ __launch_bounds__(256) void k_joint_solve(int variant, const double *__restrict__ x, const double *__restrict__ u,
                                                      const uint8_t *__restrict__ valid, int n, const double *__restrict__ d,
                                                      const double *__restrict__ nrm, const double *__restrict__ omega,
@@ -196,47 +193,21 @@ __global__ __launch_bounds__(256) void k_joint_solve(int variant, const double *
     __shared__ double part[4][JOINT_SUMS];
     __shared__ double bc[8];
     const int b = blockIdx.x;
-    const double *xb = x + (size_t)b * n * 2, *ub = u + (size_t)b * n * 2;
-    const uint8_t *vb = valid ? valid + (size_t)b * n : nullptr;
-    const double *wb = weights ? weights + (size_t)b * n : nullptr;
-    const double nb[3] = {nrm[3 * b], nrm[3 * b + 1], nrm[3 * b + 2]}, ob[3] = {omega[3 * b], omega[3 * b + 1], omega[3 * b + 2]};
-    const double db = d[b];
-    double *o = out + (size_t)b * OFK_SOLVE_DOUBLES;
-    const double rec03[4] = {o[0], o[1], o[2], o[3]}, rank = o[4];
-    double vs[3] = {rec03[0], rec03[1], rec03[2]};
-    if (t) {                                                    // the record holds v - omega x t
-        const double *tb = t + 3 * b;
-        vs[0] += ob[1] * tb[2] - ob[2] * tb[1]; vs[1] += ob[2] * tb[0] - ob[0] * tb[2]; vs[2] += ob[0] * tb[1] - ob[1] * tb[0];
-    }
-    const double ovar[3] = {jc.so[0] * jc.so[0], jc.so[1] * jc.so[1], jc.so[2] * jc.so[2]};
-    double v[3], omh[3], rss;
-    const bool rw = joint_core<4>(part, bc, n, variant, nb, ob, db, vs, rec03, rank >= 3.0 && db != 0.0, (db * jc.sf) * (db * jc.sf), ovar,
-                                  joint + (size_t)b * OFK_JOINT_DOUBLES, v, omh, rss,
-                                  [&](int i, double &px, double &py, double &ux, double &uy, double &w) {
-        if (vb && !vb[i]) return false;
-        w = wb ? wb[i] : 1.0;
-        if (!(w > 0.0)) return false;
-        px = xb[2 * i]; py = xb[2 * i + 1]; ux = ub[2 * i]; uy = ub[2 * i + 1];
-        return true;
-    });
-    if (rw && threadIdx.x == 0) {
-        if (t) sub_cross(v, omh, t + 3 * b, o);
-        else { o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; }
-        o[3] = rss;
-    }
+    stage_problem q;
+    stage_unpack(q, b, x, u, valid, n, d, nrm, omega, t, weights, out);
+    double ovar[3], v[3], omh[3], rss;
+    gyro_variances(jc, nullptr, ovar);
+    const bool rw = joint_core<4>(part, bc, n, variant, q.nrm, q.om, q.d, q.vs, q.rec03, q.rank >= 3.0 && q.d != 0.0,
+                                  (q.d * jc.sf) * (q.d * jc.sf), ovar, joint + (size_t)b * OFK_JOINT_DOUBLES, v, omh, rss, q.pts);
+    stage_write(q, rw, v, omh, rss, out + (size_t)b * OFK_SOLVE_DOUBLES);
 }
 
-void ofk_launch_joint_solve(hipStream_t s, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
-                            const double *d, const double *nrm, const double *omega, const double *t, const double *weights,
-                            const ofk_joint *j, double *out, double *joint)
+void ofk_launch_joint_solve(hipStream_t s, const ofk_stage_in &in, const double *weights, const ofk_joint *j, double *out, double *joint)
 {
-    hipLaunchKernelGGL(k_joint_solve, dim3(batch), dim3(256), 0, s, variant, x, u, valid, n, d, nrm, omega, t, weights, joint_make_cfg(j), out,
-                       joint);
+    hipLaunchKernelGGL(k_joint_solve, dim3(in.batch), dim3(256), 0, s, in.variant, in.x, in.u, in.valid, in.n, in.d, in.nrm, in.omega, in.t,
+                       weights, joint_make_cfg(j), out, joint);
 }
 
-// ------------------------------------------------------------------------------------------------ frame pairs / plain stream step
-// Behind k_pairs_solve[_wg] / k_pairs_robust: the same inputs, the pair's record (rewritten in place) and (robust) weight row.
-// sigma_flow is pixels: the points are scaled by the pair's `scaling`, so is it.
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void k_pairs_joint(const float *__restrict__ prev_pts, const float *__restrict__ next_pts,
                                                          const uint8_t *__restrict__ status, const int *__restrict__ counts, int pts_stride,
@@ -247,118 +218,39 @@ __global__ __launch_bounds__(64 * NW) void k_pairs_joint(const float *__restrict
     __shared__ double part[4][JOINT_SUMS];
     __shared__ double bc[8];
     const int b = blockIdx.x;
-    const double *sn = sensors + (size_t)b * OFK_SENSOR_DOUBLES;
-    const double d = sn[0], nrm[3] = {sn[1], sn[2], sn[3]}, om[3] = {sn[4], sn[5], sn[6]};
-    const double scaling = sn[19], cx = sn[20], cy = sn[21], vp[3] = {sn[22], sn[23], sn[24]};
-    const int n = min(max(counts[b], 0), pts_stride);
-    const float *pp = prev_pts + (size_t)b * pts_stride * 2, *np_ = next_pts + (size_t)b * pts_stride * 2;
-    const uint8_t *st = status + (size_t)b * pts_stride;
-    const double *wrow = weights ? weights + (size_t)b * pts_stride : nullptr;
-    double *r = records + (size_t)b * OFK_RECORD_DOUBLES;
-    const double rec03[4] = {r[0], r[1], r[2], r[3]}, rank = r[4];
-    const double ovar[3] = {jc.so[0] * jc.so[0], jc.so[1] * jc.so[1], jc.so[2] * jc.so[2]};
-    const double dsf = d * jc.sf * scaling;
-    double v[3], omh[3], rss;
-    const bool rw = joint_core<NW>(part, bc, n, variant, nrm, om, d, rec03, rec03, rank >= 3.0 && scaling != 0.0 && d != 0.0, dsf * dsf, ovar,
-                                   joint + (size_t)b * OFK_JOINT_DOUBLES, v, omh, rss,
-                                   [&](int i, double &x, double &y, double &ux, double &uy, double &w) {
-        if (!st[i]) return false;
-        w = wrow ? wrow[i] : 1.0;
-        if (!(w > 0.0)) return false;
-        return pair_point(pp, np_, i, cx, cy, scaling, use_feas, feas_T, nrm, vp, d, x, y, ux, uy);
-    });
-    if (rw && threadIdx.x == 0) {
-        double vu[3];
-        lever_rotate(v, omh, sn + 16, sn + 7, vu);
-        r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = rss; r[8] = vu[0]; r[9] = vu[1]; r[10] = vu[2];
-    }
+    resident_problem q;
+    resident_unpack(q, b, prev_pts, next_pts, status, counts, pts_stride, sensors, nullptr, false, use_feas, feas_T, weights, records);
+    double ovar[3], v[3], omh[3], rss;
+    gyro_variances(jc, nullptr, ovar);
+    const double dsf = q.d * jc.sf * q.scaling;
+    const bool rw = joint_core<NW>(part, bc, q.n, variant, q.nrm, q.om, q.d, q.rec03, q.rec03, q.rank >= 3.0 && q.scaling != 0.0 && q.d != 0.0,
+                                   dsf * dsf, ovar, joint + (size_t)b * OFK_JOINT_DOUBLES, v, omh, rss, q.pts);
+    pairs_write(q, rw, v, omh, rss, records + (size_t)b * OFK_RECORD_DOUBLES);
 }
 
-void ofk_launch_pairs_joint(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts,
-                            int pts_stride, const double *sensors, int variant, int use_feas, double feas_T, const double *weights,
-                            const ofk_joint *j, double *records, double *joint, int batch)
+void ofk_launch_pairs_joint(hipStream_t s, const ofk_pairs_in &in, const double *weights, const ofk_joint *j, double *joint)
 {
-    const joint_cfg jc = joint_make_cfg(j);
-    // ofk_launch_pairs_solve's rule and reason
-    if (batch >= 128)
-        hipLaunchKernelGGL(k_pairs_joint<1>, dim3(batch), dim3(64), 0, s, prev_pts, next_pts, status, counts, pts_stride, sensors, variant,
-                           use_feas, feas_T, weights, jc, records, joint);
-    else
-        hipLaunchKernelGGL(k_pairs_joint<4>, dim3(batch), dim3(256), 0, s, prev_pts, next_pts, status, counts, pts_stride, sensors, variant,
-                           use_feas, feas_T, weights, jc, records, joint);
+    launch_pairs_form(s, in.batch, k_pairs_joint<1>, k_pairs_joint<4>, in.prev_pts, in.next_pts, in.status, in.counts, in.pts_stride, in.sensors,
+                      in.variant, in.use_feas, in.feas_T, weights, joint_make_cfg(j), in.records, joint);
 }
 
-// ------------------------------------------------------------------------------------------------ fused stream step
-// Behind k_stream_fuse / k_stream_fuse_robust, which with the setting on leave the filter at its prediction (fuse_args.defer): `status`
-// holds the keep flags by now, so the set is status (and w > 0).  The correct runs here with the joint v / v_uav (the solve's own where
-// the joint solve left the record alone), fused[0..7] is rewritten and vel_overwrite is repeated with the joint v_uav.
 __global__ __launch_bounds__(256) void k_stream_joint(fuse_args g, const double *__restrict__ weights, joint_cfg jc, double *__restrict__ joint)
 {
     __shared__ double part[4][JOINT_SUMS];
     __shared__ double bc[8];
     const int b = blockIdx.x;
-    const double *sn = g.sensors + (size_t)b * OFK_SENSOR_DOUBLES;
-    const double d = sn[0], scaling = sn[19], cx = sn[20], cy = sn[21];
-    double *ist = g.f.use_imu && g.imu_state ? g.imu_state + (size_t)b * OFK_IMU_STATE : nullptr;
-    double nrm[3], om[3], ovar[3];
-    for (int k = 0; k < 3; ++k) {
-        nrm[k] = ist ? ist[15 + k] : sn[1 + k]; om[k] = ist ? ist[18 + k] : sn[4 + k];
-        ovar[k] = jc.omega_from_imu && ist ? ist[21 + k] : jc.so[k] * jc.so[k];
-    }
-    const int n = min(max(g.counts[b], 0), g.pts_stride);
-    const float *pp = g.prev_pts + (size_t)b * g.pts_stride * 2, *np_ = g.next_pts + (size_t)b * g.pts_stride * 2;
-    const uint8_t *st = g.status + (size_t)b * g.pts_stride;
-    const double *wrow = weights ? weights + (size_t)b * g.pts_stride : nullptr;
-    double *r = g.records + (size_t)b * OFK_RECORD_DOUBLES;
-    const double rec03[4] = {r[0], r[1], r[2], r[3]};
-    const bool solved = r[15] != 0.0;
-    const double dsf = d * jc.sf * scaling;
-    double v[3], omh[3], rss;
-    const bool rw = joint_core<4>(part, bc, n, g.variant, nrm, om, d, rec03, rec03, solved && r[4] >= 3.0 && scaling != 0.0 && d != 0.0,
-                                  dsf * dsf, ovar, joint + (size_t)b * OFK_JOINT_DOUBLES, v, omh, rss,
-                                  [&](int i, double &x, double &y, double &ux, double &uy, double &w) {
-        if (!st[i]) return false;
-        w = wrow ? wrow[i] : 1.0;
-        if (!(w > 0.0)) return false;
-        return pair_point(pp, np_, i, cx, cy, scaling, 0, 0.0, nrm, rec03, d, x, y, ux, uy);  // fuse_terms' x, y, u of OFK_FLOW_LK
-    });
-    if (threadIdx.x == 0) {
-        double vu[3] = {r[8], r[9], r[10]};
-        if (rw) {
-            lever_rotate(v, omh, sn + 16, ist ? ist + 6 : sn + 7, vu);
-            r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = rss; r[8] = vu[0]; r[9] = vu[1]; r[10] = vu[2];
-        }
-        double *fu = g.fused + (size_t)b * 8;
-        if (g.f.filter && g.defer) {
-            double kx[KF_MAX], kP[KF_MAX][KF_MAX];
-            kf_load(g.ns, b, g.kf_x, g.kf_P, kx, kP);
-            if (solved) {
-                double z[KF_MAX] = {0, 0, 0, 0, 0, 0};
-                for (int k = 0; k < 3; ++k) z[k] = g.f.z_sign * r[(g.f.z_source ? 8 : 0) + k];
-                for (int k = 3; k < g.nm; ++k) z[k] = sn[22 + (k - 3)];
-                kf_correct_dev(g.ns, g.nm, g.H, g.Rm, z, kx, kP);
-                kf_store(g.ns, b, kx, kP, g.kf_x, g.kf_P);
-            }
-            double tr = 0.0;
-            for (int i = 0; i < g.ns; ++i) tr += kP[i][i];
-            for (int k = 0; k < 6; ++k) fu[k] = k < g.ns ? kx[k] : 0.0;
-            fu[6] = tr; fu[7] = solved ? 1.0 : 0.0;
-        } else if (!g.f.filter && rw) {
-            fu[0] = vu[0]; fu[1] = vu[1]; fu[2] = vu[2];
-        }
-        if (g.f.vel_overwrite && solved && ist && rw) { ist[0] = vu[0]; ist[1] = vu[1]; ist[2] = vu[2]; }   // node:261
-    }
+    resident_problem q;
+    stream_unpack(q, b, g, weights);
+    double ovar[3], v[3], omh[3], rss;
+    gyro_variances(jc, q.ist, ovar);
+    const double dsf = q.d * jc.sf * q.scaling;
+    const bool rw = joint_core<4>(part, bc, q.n, g.variant, q.nrm, q.om, q.d, q.rec03, q.rec03,
+                                  q.solved && q.rank >= 3.0 && q.scaling != 0.0 && q.d != 0.0, dsf * dsf, ovar,
+                                  joint + (size_t)b * OFK_JOINT_DOUBLES, v, omh, rss, q.pts);
+    stream_tail(g, q, b, rw, v, omh, rss);
 }
 
-void ofk_launch_stream_joint(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
-                             const double *sensors, double *imu_state, int ns, int nm, int nc, const double *kf_mats, double *kf_x, double *kf_P,
-                             const ofk_fusion *f, int variant, double *records, double *fused, const double *weights, const ofk_joint *j,
-                             double *joint, int batch, int defer)
+void ofk_launch_stream_joint(hipStream_t s, const ofk_stream_in &in, const double *weights, const ofk_joint *j, double *joint)
 {
-    fuse_args g;
-    g.prev_pts = prev_pts; g.next_pts = next_pts; g.status = status; g.counts = counts; g.pts_stride = pts_stride; g.sensors = sensors;
-    g.imu_state = imu_state; g.imu_dv = nullptr; g.ns = ns; g.nm = nm; g.nc = nc;
-    g.F = kf_mats; g.Bm = kf_mats + 36; g.H = kf_mats + 72; g.Q = kf_mats + 108; g.Rm = kf_mats + 144; g.kf_x = kf_x; g.kf_P = kf_P;
-    g.f = *f; g.variant = variant; g.use_feas = 0; g.feas_T = 0.0; g.records = records; g.fused = fused; g.defer = defer;
-    hipLaunchKernelGGL(k_stream_joint, dim3(batch), dim3(256), 0, s, g, weights, joint_make_cfg(j), joint);
+    hipLaunchKernelGGL(k_stream_joint, dim3(in.batch), dim3(256), 0, s, make_fuse_args(in, nullptr, 0, 0.0), weights, joint_make_cfg(j), joint);
 }

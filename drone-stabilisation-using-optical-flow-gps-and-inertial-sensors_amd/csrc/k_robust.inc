@@ -477,17 +477,9 @@ __global__ __launch_bounds__(256) void k_stream_fuse_robust(fuse_args g, rob_fus
     }
 }
 
-void ofk_launch_stream_fuse_robust(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
-                                   const double *sensors, double *imu_state, double *imu_dv, int ns, int nm, int nc, const double *kf_mats,
-                                   double *kf_x, double *kf_P, const ofk_fusion *f, int variant, int use_feas, double feas_T, double *records,
-                                   double *fused, const ofk_robust *r, double *work, double *weights, double *wtmp, double *stats, int batch,
-                                   int defer_correct)
+void ofk_launch_stream_fuse_robust(hipStream_t s, const ofk_stream_in &in, double *imu_dv, int use_feas, double feas_T, const ofk_robust *r,
+                                   double *work, double *weights, double *wtmp, double *stats)
 {
-    fuse_args g;
-    g.prev_pts = prev_pts; g.next_pts = next_pts; g.status = status; g.counts = counts; g.pts_stride = pts_stride; g.sensors = sensors;
-    g.imu_state = imu_state; g.imu_dv = imu_dv; g.ns = ns; g.nm = nm; g.nc = nc;
-    g.F = kf_mats; g.Bm = kf_mats + 36; g.H = kf_mats + 72; g.Q = kf_mats + 108; g.Rm = kf_mats + 144; g.kf_x = kf_x; g.kf_P = kf_P;
-    g.f = *f; g.variant = variant; g.use_feas = use_feas; g.feas_T = feas_T; g.records = records; g.fused = fused; g.defer = defer_correct;
     const rob_fuse_args ra = {{r->loss, r->c, r->iters, r->hypotheses, (unsigned)r->seed, (unsigned)(r->seed >> 32), r->drop}, work, weights, wtmp, stats};
-    hipLaunchKernelGGL(k_stream_fuse_robust, dim3(batch), dim3(256), 0, s, g, ra);
+    hipLaunchKernelGGL(k_stream_fuse_robust, dim3(in.batch), dim3(256), 0, s, make_fuse_args(in, imu_dv, use_feas, feas_T), ra);
 }

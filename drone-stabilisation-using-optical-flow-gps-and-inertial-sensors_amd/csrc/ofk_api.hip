@@ -1113,24 +1113,6 @@ extern "C" int ofk_get_cov(const ofk_ctx *c, ofk_cov *v)
     return OFK_OK;
 }
 
-static int cov_alloc(ofk_ctx *c)
-{
-    if (c->cov_rec) return OFK_OK;
-    OFK_HIP(c, hipMalloc((void **)&c->cov_rec, (size_t)c->max_batch * OFK_COV_DOUBLES * 8));
-    return OFK_OK;
-}
-
-extern "C" int ofk_cov_download(ofk_ctx *c, double *cov)
-{
-    if (!c) return OFK_E_INVALID;
-    if (c->cov_batch < 1 || !c->cov_rec) return ofk_fail(c, OFK_E_INVALID, "ofk_cov_download: no run or step with ofk_set_cov on yet");
-    if (!cov) return ofk_fail(c, OFK_E_INVALID, "ofk_cov_download: NULL buffer");
-    TRY(enter(c));
-    OFK_HIP(c, hipMemcpyAsync(cov, c->cov_rec, (size_t)c->cov_batch * OFK_COV_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
-}
-
 // ------------------------------------------------------------------------------------------------ joint velocity and rotation setting
 static int check_joint(ofk_ctx *c, const ofk_joint *v, const char *who)
 {
@@ -1155,35 +1137,6 @@ extern "C" int ofk_get_joint(const ofk_ctx *c, ofk_joint *v)
 {
     if (!c || !v) return OFK_E_INVALID;
     *v = c->joint;
-    return OFK_OK;
-}
-
-static int joint_alloc(ofk_ctx *c)
-{
-    if (c->joint_rec) return OFK_OK;
-    OFK_HIP(c, hipMalloc((void **)&c->joint_rec, (size_t)c->max_batch * OFK_JOINT_DOUBLES * 8));
-    return OFK_OK;
-}
-
-// The runs' and steps' own refusals with the setting on (ofk.h); allocates the rows on first use.
-static int joint_prepare(ofk_ctx *c, int B, const char *who)
-{
-    if (c->joint.mode == OFK_JOINT_OFF) return OFK_OK;
-    if (c->cov.mode != OFK_COV_OFF)
-        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_joint and ofk_set_cov are both on: the covariance takes omega as an input, not an estimate", who);
-    TRY(joint_alloc(c));
-    c->joint_batch = B;
-    return OFK_OK;
-}
-
-extern "C" int ofk_joint_download(ofk_ctx *c, double *joint)
-{
-    if (!c) return OFK_E_INVALID;
-    if (c->joint_batch < 1 || !c->joint_rec) return ofk_fail(c, OFK_E_INVALID, "ofk_joint_download: no run or step with ofk_set_joint on yet");
-    if (!joint) return ofk_fail(c, OFK_E_INVALID, "ofk_joint_download: NULL buffer");
-    TRY(enter(c));
-    OFK_HIP(c, hipMemcpyAsync(joint, c->joint_rec, (size_t)c->joint_batch * OFK_JOINT_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
 }
 
@@ -1214,31 +1167,6 @@ extern "C" int ofk_get_plane(const ofk_ctx *c, ofk_plane *v)
 {
     if (!c || !v) return OFK_E_INVALID;
     *v = c->plane;
-    return OFK_OK;
-}
-
-// The runs' and steps' own refusals with the setting on (ofk.h); allocates the rows on first use.
-static int plane_prepare(ofk_ctx *c, int B, int variant, const char *who)
-{
-    if (c->plane.mode == OFK_PLANE_OFF) return OFK_OK;
-    if (c->cov.mode != OFK_COV_OFF || c->joint.mode != OFK_JOINT_OFF)
-        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_plane is on beside %s: both take the normal as an input, not an estimate", who,
-                        c->cov.mode != OFK_COV_OFF ? "ofk_set_cov" : "ofk_set_joint");
-    if (variant == OFK_SOLVE_OFMODULE)
-        return ofk_fail(c, OFK_E_INVALID, "%s: OFK_SOLVE_OFMODULE is not the sensor model: no plane solve (ofk_set_plane is on)", who);
-    if (!c->plane_rec) OFK_HIP(c, hipMalloc((void **)&c->plane_rec, (size_t)c->max_batch * OFK_PLANE_DOUBLES * 8));
-    c->plane_batch = B;
-    return OFK_OK;
-}
-
-extern "C" int ofk_plane_download(ofk_ctx *c, double *plane)
-{
-    if (!c) return OFK_E_INVALID;
-    if (c->plane_batch < 1 || !c->plane_rec) return ofk_fail(c, OFK_E_INVALID, "ofk_plane_download: no run or step with ofk_set_plane on yet");
-    if (!plane) return ofk_fail(c, OFK_E_INVALID, "ofk_plane_download: NULL buffer");
-    TRY(enter(c));
-    OFK_HIP(c, hipMemcpyAsync(plane, c->plane_rec, (size_t)c->plane_batch * OFK_PLANE_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
 }
 
@@ -1273,86 +1201,120 @@ extern "C" int ofk_get_epipolar(const ofk_ctx *c, ofk_epipolar *v)
     return OFK_OK;
 }
 
-// The runs' and steps' own refusals with the setting on (ofk.h); allocates the rows on first use.
-static int epi_prepare(ofk_ctx *c, int B, int variant, const char *who)
+// ------------------------------------------------------------------------------------------------ the second-stage settings
+// One row per setting whose kernel runs behind the velocity solve, in the order of their checks and launches.  No two run together:
+// a row refuses every earlier row that is on.
+enum { NO_OFMODULE = 1, NO_ROTATIONAL = 2, NO_LEGACY = 4 };
+struct second_setting {
+    const char *set, *what;                                     // the setter's name, what the kernel adds
+    int (*mode)(const ofk_ctx *);                               // 0: off
+    double *ofk_ctx::*rec; int doubles; int ofk_ctx::*batch;    // the records' rows (allocated on first use), problems of the latest run / step
+    double *ofk_ctx::*pts;                                      // [max_pts][4] per problem behind the rows, or NULL
+    const char *beside;                                         // the refusal beside an earlier row: who, that row's setter
+    int fused_refuse;                                           // what a fused step may not have: not the sensor model
+    bool ofmodule_late;                                         // OFK_SOLVE_OFMODULE is refused behind `beside`, in words of its own
+    void (*pairs)(ofk_ctx *, hipStream_t, const ofk_pairs_in &, const double *weights, int b0);
+    void (*stream)(ofk_ctx *, const ofk_stream_in &, const double *weights);
+};
+enum { SECOND_COV, SECOND_JOINT, SECOND_PLANE, SECOND_EPI };
+static const second_setting SECOND[4] = {
+    {"ofk_set_cov", "covariance", [](const ofk_ctx *c) { return c->cov.mode; }, &ofk_ctx::cov_rec, OFK_COV_DOUBLES, &ofk_ctx::cov_batch, nullptr,
+     nullptr, NO_OFMODULE | NO_ROTATIONAL, false,
+     [](ofk_ctx *c, hipStream_t st, const ofk_pairs_in &in, const double *w, int b0) {
+         ofk_launch_pairs_cov(st, in, w, &c->cov, c->cov_rec + (size_t)b0 * OFK_COV_DOUBLES); },
+     [](ofk_ctx *c, const ofk_stream_in &in, const double *w) { ofk_launch_stream_cov(c->stream, in, w, &c->cov, c->cov_rec); }},
+    {"ofk_set_joint", "joint solve", [](const ofk_ctx *c) { return c->joint.mode; }, &ofk_ctx::joint_rec, OFK_JOINT_DOUBLES, &ofk_ctx::joint_batch,
+     nullptr, "%s: ofk_set_joint and %s are both on: the covariance takes omega as an input, not an estimate",
+     NO_OFMODULE | NO_ROTATIONAL | NO_LEGACY, false,
+     [](ofk_ctx *c, hipStream_t st, const ofk_pairs_in &in, const double *w, int b0) {
+         ofk_launch_pairs_joint(st, in, w, &c->joint, c->joint_rec + (size_t)b0 * OFK_JOINT_DOUBLES); },
+     [](ofk_ctx *c, const ofk_stream_in &in, const double *w) { ofk_launch_stream_joint(c->stream, in, w, &c->joint, c->joint_rec); }},
+    {"ofk_set_plane", "plane solve", [](const ofk_ctx *c) { return c->plane.mode; }, &ofk_ctx::plane_rec, OFK_PLANE_DOUBLES, &ofk_ctx::plane_batch,
+     nullptr, "%s: ofk_set_plane is on beside %s: both take the normal as an input, not an estimate", NO_ROTATIONAL | NO_LEGACY, true,
+     [](ofk_ctx *c, hipStream_t st, const ofk_pairs_in &in, const double *w, int b0) {
+         ofk_launch_pairs_plane(st, in, w, &c->plane, c->plane_rec + (size_t)b0 * OFK_PLANE_DOUBLES); },
+     [](ofk_ctx *c, const ofk_stream_in &in, const double *w) { ofk_launch_stream_plane(c->stream, in, w, &c->plane, c->plane_rec); }},
+    {"ofk_set_epipolar", "epipolar solve", [](const ofk_ctx *c) { return c->epi.mode; }, &ofk_ctx::epi_rec, OFK_EPI_DOUBLES, &ofk_ctx::epi_batch,
+     &ofk_ctx::epi_pts, "%s: ofk_set_epipolar is on beside %s: that setting rests on the plane this one replaces", NO_ROTATIONAL | NO_LEGACY, true,
+     [](ofk_ctx *c, hipStream_t st, const ofk_pairs_in &in, const double *w, int b0) {
+         ofk_launch_pairs_epi(st, in, w, &c->epi, c->epi_rec + (size_t)b0 * OFK_EPI_DOUBLES, c->epi_pts + (size_t)b0 * c->max_pts * 4); },
+     [](ofk_ctx *c, const ofk_stream_in &in, const double *w) { ofk_launch_stream_epi(c->stream, in, w, &c->epi, c->epi_rec, c->epi_pts); }},
+};
+
+static bool second_on(const ofk_ctx *c)
 {
-    if (c->epi.mode == OFK_EPI_OFF) return OFK_OK;
-    if (c->cov.mode != OFK_COV_OFF || c->joint.mode != OFK_JOINT_OFF || c->plane.mode != OFK_PLANE_OFF)
-        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_epipolar is on beside %s: that setting rests on the plane this one replaces", who,
-                        c->cov.mode != OFK_COV_OFF ? "ofk_set_cov" : c->joint.mode != OFK_JOINT_OFF ? "ofk_set_joint" : "ofk_set_plane");
-    if (variant == OFK_SOLVE_OFMODULE)
-        return ofk_fail(c, OFK_E_INVALID, "%s: OFK_SOLVE_OFMODULE is not the sensor model: no epipolar solve (ofk_set_epipolar is on)", who);
-    if (!c->epi_rec) {
-        const size_t rec = (size_t)c->max_batch * OFK_EPI_DOUBLES * 8;
-        OFK_HIP(c, hipMalloc((void **)&c->epi_rec, rec + (size_t)c->max_batch * c->max_pts * 32));
-        c->epi_pts = c->epi_rec + (size_t)c->max_batch * OFK_EPI_DOUBLES;
+    for (const second_setting &s : SECOND) if (s.mode(c)) return true;
+    return false;
+}
+
+// The runs' and steps' own refusals with a setting on (ofk.h), row by row; allocates the rows on first use.  fu: a fused step's.
+static int second_prepare(ofk_ctx *c, int B, int variant, const ofk_fusion *fu, const char *who)
+{
+    static const char *const names[3] = {"OFK_SOLVE_OFMODULE", "OFK_FLOW_ROTATIONAL", "OFK_KEEP_LEGACY"};
+    const int has = !fu ? 0 : (variant == OFK_SOLVE_OFMODULE ? NO_OFMODULE : 0) | (fu->flow == OFK_FLOW_ROTATIONAL ? NO_ROTATIONAL : 0) |
+                                  (fu->keep == OFK_KEEP_LEGACY ? NO_LEGACY : 0);
+    const second_setting *first = nullptr;                      // the row that is on already
+    for (const second_setting &s : SECOND) {
+        if (!s.mode(c)) continue;
+        if (has & s.fused_refuse) {
+            char list[64] = "";
+            for (int k = 0; k < 3; ++k)
+                if (s.fused_refuse >> k & 1) { if (list[0]) strcat(list, " / "); strcat(list, names[k]); }
+            return ofk_fail(c, OFK_E_INVALID, "%s: %s are not the sensor model: no %s (%s is on)", who, list, s.what, s.set);
+        }
+        if (first) return ofk_fail(c, OFK_E_INVALID, s.beside, who, first->set);
+        if (s.ofmodule_late && variant == OFK_SOLVE_OFMODULE)
+            return ofk_fail(c, OFK_E_INVALID, "%s: OFK_SOLVE_OFMODULE is not the sensor model: no %s (%s is on)", who, s.what, s.set);
+        if (!(c->*s.rec)) {
+            const size_t rows = (size_t)c->max_batch * s.doubles;
+            OFK_HIP(c, hipMalloc((void **)&(c->*s.rec), rows * 8 + (s.pts ? (size_t)c->max_batch * c->max_pts * 32 : 0)));
+            if (s.pts) c->*s.pts = c->*s.rec + rows;
+        }
+        c->*s.batch = B;
+        first = &s;
     }
-    c->epi_batch = B;
     return OFK_OK;
 }
 
-extern "C" int ofk_epipolar_download(ofk_ctx *c, double *epi)
+// A setting's rows of the latest run or step (points: its per-point rows) to the host.
+static int second_download(ofk_ctx *c, const second_setting &s, const char *who, double *dst, bool points = false)
 {
     if (!c) return OFK_E_INVALID;
-    if (c->epi_batch < 1 || !c->epi_rec) return ofk_fail(c, OFK_E_INVALID, "ofk_epipolar_download: no run or step with ofk_set_epipolar on yet");
-    if (!epi) return ofk_fail(c, OFK_E_INVALID, "ofk_epipolar_download: NULL buffer");
+    if (c->*s.batch < 1 || !(c->*s.rec)) return ofk_fail(c, OFK_E_INVALID, "%s: no run or step with %s on yet", who, s.set);
+    if (!dst) return ofk_fail(c, OFK_E_INVALID, "%s: NULL buffer", who);
     TRY(enter(c));
-    OFK_HIP(c, hipMemcpyAsync(epi, c->epi_rec, (size_t)c->epi_batch * OFK_EPI_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    const size_t per = points ? (size_t)c->max_pts * 32 : (size_t)s.doubles * 8;
+    OFK_HIP(c, hipMemcpyAsync(dst, points ? c->*s.pts : c->*s.rec, (size_t)(c->*s.batch) * per, hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
 }
 
+extern "C" int ofk_cov_download(ofk_ctx *c, double *cov) { return second_download(c, SECOND[SECOND_COV], "ofk_cov_download", cov); }
+extern "C" int ofk_joint_download(ofk_ctx *c, double *joint) { return second_download(c, SECOND[SECOND_JOINT], "ofk_joint_download", joint); }
+extern "C" int ofk_plane_download(ofk_ctx *c, double *plane) { return second_download(c, SECOND[SECOND_PLANE], "ofk_plane_download", plane); }
+extern "C" int ofk_epipolar_download(ofk_ctx *c, double *epi) { return second_download(c, SECOND[SECOND_EPI], "ofk_epipolar_download", epi); }
 extern "C" int ofk_epipolar_points_download(ofk_ctx *c, double *points)
 {
-    if (!c) return OFK_E_INVALID;
-    if (c->epi_batch < 1 || !c->epi_rec) return ofk_fail(c, OFK_E_INVALID, "ofk_epipolar_points_download: no run or step with ofk_set_epipolar on yet");
-    if (!points) return ofk_fail(c, OFK_E_INVALID, "ofk_epipolar_points_download: NULL buffer");
-    TRY(enter(c));
-    OFK_HIP(c, hipMemcpyAsync(points, c->epi_pts, (size_t)c->epi_batch * c->max_pts * 32, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
+    return second_download(c, SECOND[SECOND_EPI], "ofk_epipolar_points_download", points, true);
 }
 
-// The solve of nb pairs from pair b0 on (their views' pointers): the plain kernels, or with ofk_set_robust on the robust ones; with
-// ofk_set_cov on the covariance kernel behind either, with ofk_set_joint on the joint kernel, with ofk_set_plane on the
-// plane kernel, with ofk_set_epipolar on the epipolar kernel (the callers refuse any two of the four at once).
+// The solve of nb pairs from pair b0 on (their views' pointers): the plain kernels, or with ofk_set_robust on the robust ones, and
+// behind either the kernel of the second-stage setting that is on.
 // drop_status: the stream steps' keep flags (cleared for zero-weight points when the setting asks for it), NULL for frame pairs.
 static void solve_pairs(ofk_ctx *c, hipStream_t st, const float *pts_prev, const float *pts_next, uint8_t *status, const int *counts,
                         const double *sensors, const ofk_params *p, const int *cand_count, double *records, int b0, int nb, bool stream)
 {
     const size_t o = (size_t)b0 * c->max_pts;
-    if (c->robust.loss == OFK_ROBUST_OFF) {
+    const bool rob = c->robust.loss != OFK_ROBUST_OFF;
+    if (rob)
+        ofk_launch_pairs_robust(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
+                                cand_count, &c->robust, b0, c->rob_work + o * 7, c->rob_w + o, c->rob_wtmp + o,
+                                c->rob_stats + (size_t)b0 * OFK_ROBUST_DOUBLES, stream && c->robust.drop ? status : nullptr, records, nb);
+    else
         ofk_launch_pairs_solve(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
                                cand_count, records, nb);
-        if (c->cov.mode != OFK_COV_OFF)
-            ofk_launch_pairs_cov(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
-                                 nullptr, &c->cov, records, c->cov_rec + (size_t)b0 * OFK_COV_DOUBLES, nb);
-        if (c->joint.mode != OFK_JOINT_OFF)
-            ofk_launch_pairs_joint(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
-                                   nullptr, &c->joint, records, c->joint_rec + (size_t)b0 * OFK_JOINT_DOUBLES, nb);
-        if (c->plane.mode != OFK_PLANE_OFF)
-            ofk_launch_pairs_plane(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
-                                   nullptr, &c->plane, records, c->plane_rec + (size_t)b0 * OFK_PLANE_DOUBLES, nb);
-        if (c->epi.mode != OFK_EPI_OFF)
-            ofk_launch_pairs_epi(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->use_feasibility, p->feas_T, nullptr, &c->epi,
-                                 records, c->epi_rec + (size_t)b0 * OFK_EPI_DOUBLES, c->epi_pts + o * 4, nb);
-        return;
-    }
-    ofk_launch_pairs_robust(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
-                            cand_count, &c->robust, b0, c->rob_work + o * 7, c->rob_w + o, c->rob_wtmp + o,
-                            c->rob_stats + (size_t)b0 * OFK_ROBUST_DOUBLES, stream && c->robust.drop ? status : nullptr, records, nb);
-    if (c->cov.mode != OFK_COV_OFF)
-        ofk_launch_pairs_cov(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
-                             c->rob_w + o, &c->cov, records, c->cov_rec + (size_t)b0 * OFK_COV_DOUBLES, nb);
-    if (c->joint.mode != OFK_JOINT_OFF)
-        ofk_launch_pairs_joint(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
-                               c->rob_w + o, &c->joint, records, c->joint_rec + (size_t)b0 * OFK_JOINT_DOUBLES, nb);
-    if (c->plane.mode != OFK_PLANE_OFF)
-        ofk_launch_pairs_plane(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
-                               c->rob_w + o, &c->plane, records, c->plane_rec + (size_t)b0 * OFK_PLANE_DOUBLES, nb);
-    if (c->epi.mode != OFK_EPI_OFF)
-        ofk_launch_pairs_epi(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->use_feasibility, p->feas_T, c->rob_w + o, &c->epi,
-                             records, c->epi_rec + (size_t)b0 * OFK_EPI_DOUBLES, c->epi_pts + o * 4, nb);
+    const ofk_pairs_in in = {pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T, records, nb};
+    for (const second_setting &s : SECOND) if (s.mode(c)) s.pairs(c, st, in, rob ? c->rob_w + o : nullptr, b0);
 }
 
 extern "C" int ofk_robust_download(ofk_ctx *c, double *weights, int stride, double *stats)
@@ -1558,150 +1520,103 @@ extern "C" int ofk_velocity_solve_robust(ofk_ctx *c, int variant, const double *
     return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
 }
 
-extern "C" int ofk_velocity_solve_cov(ofk_ctx *c, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
-                                      const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
-                                      const ofk_robust *r, const ofk_cov *cv, double *out, double *cov)
+// The four second-stage stage entries: the plain or robust solve, the setting's kernel behind it.  what: what the kernel adds; have:
+// the entry's own pointers are there; wgt: refused unless NULL (the entries that ignore theirs pass NULL); check: the setting's own
+// check, the mode it needs included; points: the epipolar [batch][n][4], or NULL; launch(in, weights, out, rec, points) on the device.
+template <class Check, class Launch>
+static int solve_second_impl(ofk_ctx *c, const char *who, const char *what, bool have, int variant, const double *x, const double *u,
+                             const uint8_t *valid, int batch, int n, const double *d, const double *nrm, const double *omega, const double *t,
+                             const double *wgt, const ofk_robust *r, Check check, const char *kernel, Launch launch, double *out, double *rec,
+                             int rec_doubles, double *points)
 {
-    if (!c || !x || !u || !nrm || !out || !cov || !cv || batch < 1 || n < 1 || n > 4096 || variant < 0 || variant > 2)
-        return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_cov: bad argument");
-    if (variant == OFK_SOLVE_OFMODULE) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_cov: OFK_SOLVE_OFMODULE is not the sensor model: no covariance");
-    if (!d || !omega) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_cov: missing input for variant %d", variant);
-    (void)wgt;
-    TRY(check_cov(c, cv, "ofk_velocity_solve_cov"));
-    if (cv->mode == OFK_COV_OFF || cv->filter_r) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_cov: mode must be PROPAGATE or RESIDUAL, filter_r 0");
+    if (!c || !x || !u || !nrm || !out || !have || batch < 1 || n < 1 || n > 4096 || variant < 0 || variant > 2)
+        return ofk_fail(c, OFK_E_INVALID, "%s: bad argument", who);
+    if (variant == OFK_SOLVE_OFMODULE) return ofk_fail(c, OFK_E_INVALID, "%s: OFK_SOLVE_OFMODULE is not the sensor model: no %s", who, what);
+    if (!d || !omega) return ofk_fail(c, OFK_E_INVALID, "%s: missing input for variant %d", who, variant);
+    if (wgt) return ofk_fail(c, OFK_E_INVALID, "%s: wgt must be NULL (the argument is there for the solve entries' signature; the weights are the robust setting's)", who);
+    TRY(check());
     const bool rob = r && r->loss != OFK_ROBUST_OFF;
-    if (rob) TRY(check_robust(c, r, "ofk_velocity_solve_cov"));
-    const size_t pb = (size_t)batch * n * 16, wb = (size_t)batch * n * 8;
+    if (rob) TRY(check_robust(c, r, who));
+    const size_t pb = (size_t)batch * n * 16, wb = (size_t)batch * n * 8, ob = (size_t)batch * OFK_SOLVE_DOUBLES * 8, rb = (size_t)batch * rec_doubles * 8;
     Bump bp;
-    TRY(est_begin(c, 2 * pb + (size_t)batch * n * 9 + 9 * wb + (size_t)batch * 256 * 10, bp));
+    TRY(est_begin(c, 2 * pb + (size_t)batch * n * 9 + 9 * wb + 4 * wb + (size_t)batch * 256 * 12, bp));
     double *dx = bp.put(x, pb), *du = bp.put(u, pb);
     uint8_t *dval = (uint8_t *)bp.put(valid, (size_t)batch * n);
     double *dd = bp.put(d, batch * 8), *dn = bp.put(nrm, batch * 24), *dom = bp.put(omega, batch * 24), *dt = bp.put(t, batch * 24),
-           *dout = bp.take((size_t)batch * OFK_SOLVE_DOUBLES * 8), *dcov = bp.take((size_t)batch * OFK_COV_DOUBLES * 8), *dwts = nullptr;
+           *dout = bp.take(ob), *drec = bp.take(rb), *dpt = points ? bp.take(4 * wb) : nullptr, *dwts = nullptr;
     if (rob) {
         double *dwork = bp.take(7 * wb);
         dwts = bp.take(wb);
         double *dtmp = bp.take(wb), *dst = bp.take((size_t)batch * OFK_ROBUST_DOUBLES * 8);
-        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_cov: upload failed");
+        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
         ofk_launch_solve_robust(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, r, dwork, dwts, dtmp, dst, dout);
     } else {
-        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_cov: upload failed");
+        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
         ofk_launch_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, dout);
     }
-    ofk_launch_cov_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, dwts, cv, dout, dcov);
-    TRY(check_launch(c, "k_cov_solve"));
-    TRY(get(c, cov, dcov, (size_t)batch * OFK_COV_DOUBLES * 8));
-    return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
+    launch(ofk_stage_in{variant, dx, du, dval, batch, n, dd, dn, dom, dt}, dwts, dout, drec, dpt);
+    TRY(check_launch(c, kernel));
+    TRY(get(c, rec, drec, rb));
+    if (points) TRY(get(c, points, dpt, 4 * wb));
+    return get(c, out, dout, ob);
+}
+
+extern "C" int ofk_velocity_solve_cov(ofk_ctx *c, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                                      const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
+                                      const ofk_robust *r, const ofk_cov *cv, double *out, double *cov)
+{
+    const char *who = "ofk_velocity_solve_cov";
+    (void)wgt;
+    return solve_second_impl(c, who, "covariance", cv && cov, variant, x, u, valid, batch, n, d, nrm, omega, t, nullptr, r, [&] {
+        TRY(check_cov(c, cv, who));
+        if (cv->mode == OFK_COV_OFF || cv->filter_r) return ofk_fail(c, OFK_E_INVALID, "%s: mode must be PROPAGATE or RESIDUAL, filter_r 0", who);
+        return (int)OFK_OK;
+    }, "k_cov_solve", [&](const ofk_stage_in &in, const double *w, double *dout, double *drec, double *) {
+        ofk_launch_cov_solve(c->stream, in, w, cv, dout, drec);
+    }, out, cov, OFK_COV_DOUBLES, nullptr);
 }
 
 extern "C" int ofk_velocity_solve_joint(ofk_ctx *c, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
                                         const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
                                         const ofk_robust *r, const ofk_joint *jv, double *out, double *joint)
 {
-    if (!c || !x || !u || !nrm || !out || !joint || !jv || batch < 1 || n < 1 || n > 4096 || variant < 0 || variant > 2)
-        return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_joint: bad argument");
-    if (variant == OFK_SOLVE_OFMODULE) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_joint: OFK_SOLVE_OFMODULE is not the sensor model: no joint solve");
-    if (!d || !omega) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_joint: missing input for variant %d", variant);
+    const char *who = "ofk_velocity_solve_joint";
     (void)wgt;
-    TRY(check_joint(c, jv, "ofk_velocity_solve_joint"));
-    if (jv->mode != OFK_JOINT_ON) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_joint: mode must be OFK_JOINT_ON");
-    const bool rob = r && r->loss != OFK_ROBUST_OFF;
-    if (rob) TRY(check_robust(c, r, "ofk_velocity_solve_joint"));
-    const size_t pb = (size_t)batch * n * 16, wb = (size_t)batch * n * 8;
-    Bump bp;
-    TRY(est_begin(c, 2 * pb + (size_t)batch * n * 9 + 9 * wb + (size_t)batch * 256 * 11, bp));
-    double *dx = bp.put(x, pb), *du = bp.put(u, pb);
-    uint8_t *dval = (uint8_t *)bp.put(valid, (size_t)batch * n);
-    double *dd = bp.put(d, batch * 8), *dn = bp.put(nrm, batch * 24), *dom = bp.put(omega, batch * 24), *dt = bp.put(t, batch * 24),
-           *dout = bp.take((size_t)batch * OFK_SOLVE_DOUBLES * 8), *djr = bp.take((size_t)batch * OFK_JOINT_DOUBLES * 8), *dwts = nullptr;
-    if (rob) {
-        double *dwork = bp.take(7 * wb);
-        dwts = bp.take(wb);
-        double *dtmp = bp.take(wb), *dst = bp.take((size_t)batch * OFK_ROBUST_DOUBLES * 8);
-        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_joint: upload failed");
-        ofk_launch_solve_robust(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, r, dwork, dwts, dtmp, dst, dout);
-    } else {
-        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_joint: upload failed");
-        ofk_launch_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, dout);
-    }
-    ofk_launch_joint_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, dwts, jv, dout, djr);
-    TRY(check_launch(c, "k_joint_solve"));
-    TRY(get(c, joint, djr, (size_t)batch * OFK_JOINT_DOUBLES * 8));
-    return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
+    return solve_second_impl(c, who, "joint solve", jv && joint, variant, x, u, valid, batch, n, d, nrm, omega, t, nullptr, r, [&] {
+        TRY(check_joint(c, jv, who));
+        if (jv->mode != OFK_JOINT_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode must be OFK_JOINT_ON", who);
+        return (int)OFK_OK;
+    }, "k_joint_solve", [&](const ofk_stage_in &in, const double *w, double *dout, double *drec, double *) {
+        ofk_launch_joint_solve(c->stream, in, w, jv, dout, drec);
+    }, out, joint, OFK_JOINT_DOUBLES, nullptr);
 }
 
 extern "C" int ofk_velocity_solve_plane(ofk_ctx *c, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
                                         const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
                                         const ofk_robust *r, const ofk_plane *jv, double *out, double *plane)
 {
-    if (!c || !x || !u || !nrm || !out || !plane || !jv || batch < 1 || n < 1 || n > 4096 || variant < 0 || variant > 2)
-        return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_plane: bad argument");
-    if (variant == OFK_SOLVE_OFMODULE) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_plane: OFK_SOLVE_OFMODULE is not the sensor model: no plane solve");
-    if (!d || !omega) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_plane: missing input for variant %d", variant);
-    if (wgt) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_plane: wgt must be NULL (the argument is there for the solve entries' signature; the weights are the robust setting's)");
-    TRY(check_plane(c, jv, "ofk_velocity_solve_plane"));
-    if (jv->mode != OFK_PLANE_ON) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_plane: mode must be OFK_PLANE_ON");
-    const bool rob = r && r->loss != OFK_ROBUST_OFF;
-    if (rob) TRY(check_robust(c, r, "ofk_velocity_solve_plane"));
-    const size_t pb = (size_t)batch * n * 16, wb = (size_t)batch * n * 8;
-    Bump bp;
-    TRY(est_begin(c, 2 * pb + (size_t)batch * n * 9 + 9 * wb + (size_t)batch * 256 * 11, bp));
-    double *dx = bp.put(x, pb), *du = bp.put(u, pb);
-    uint8_t *dval = (uint8_t *)bp.put(valid, (size_t)batch * n);
-    double *dd = bp.put(d, batch * 8), *dn = bp.put(nrm, batch * 24), *dom = bp.put(omega, batch * 24), *dt = bp.put(t, batch * 24),
-           *dout = bp.take((size_t)batch * OFK_SOLVE_DOUBLES * 8), *djr = bp.take((size_t)batch * OFK_PLANE_DOUBLES * 8), *dwts = nullptr;
-    if (rob) {
-        double *dwork = bp.take(7 * wb);
-        dwts = bp.take(wb);
-        double *dtmp = bp.take(wb), *dst = bp.take((size_t)batch * OFK_ROBUST_DOUBLES * 8);
-        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_plane: upload failed");
-        ofk_launch_solve_robust(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, r, dwork, dwts, dtmp, dst, dout);
-    } else {
-        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_plane: upload failed");
-        ofk_launch_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, dout);
-    }
-    ofk_launch_plane_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, dwts, jv, dout, djr);
-    TRY(check_launch(c, "k_plane_solve"));
-    TRY(get(c, plane, djr, (size_t)batch * OFK_PLANE_DOUBLES * 8));
-    return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
+    const char *who = "ofk_velocity_solve_plane";
+    return solve_second_impl(c, who, "plane solve", jv && plane, variant, x, u, valid, batch, n, d, nrm, omega, t, wgt, r, [&] {
+        TRY(check_plane(c, jv, who));
+        if (jv->mode != OFK_PLANE_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode must be OFK_PLANE_ON", who);
+        return (int)OFK_OK;
+    }, "k_plane_solve", [&](const ofk_stage_in &in, const double *w, double *dout, double *drec, double *) {
+        ofk_launch_plane_solve(c->stream, in, w, jv, dout, drec);
+    }, out, plane, OFK_PLANE_DOUBLES, nullptr);
 }
 
 extern "C" int ofk_velocity_solve_epipolar(ofk_ctx *c, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
                                            const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
                                            const ofk_robust *r, const ofk_epipolar *ev, double *out, double *epi, double *points)
 {
-    if (!c || !x || !u || !nrm || !out || !epi || !points || !ev || batch < 1 || n < 1 || n > 4096 || variant < 0 || variant > 2)
-        return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_epipolar: bad argument");
-    if (variant == OFK_SOLVE_OFMODULE) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_epipolar: OFK_SOLVE_OFMODULE is not the sensor model: no epipolar solve");
-    if (!d || !omega) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_epipolar: missing input for variant %d", variant);
-    if (wgt) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_epipolar: wgt must be NULL (the argument is there for the solve entries' signature; the weights are the robust setting's)");
-    TRY(check_epipolar(c, ev, "ofk_velocity_solve_epipolar"));
-    if (ev->mode != OFK_EPI_ON) return ofk_fail(c, OFK_E_INVALID, "ofk_velocity_solve_epipolar: mode must be OFK_EPI_ON");
-    const bool rob = r && r->loss != OFK_ROBUST_OFF;
-    if (rob) TRY(check_robust(c, r, "ofk_velocity_solve_epipolar"));
-    const size_t pb = (size_t)batch * n * 16, wb = (size_t)batch * n * 8;
-    Bump bp;
-    TRY(est_begin(c, 2 * pb + (size_t)batch * n * 9 + 9 * wb + 4 * wb + (size_t)batch * 256 * 12, bp));
-    double *dx = bp.put(x, pb), *du = bp.put(u, pb);
-    uint8_t *dval = (uint8_t *)bp.put(valid, (size_t)batch * n);
-    double *dd = bp.put(d, batch * 8), *dn = bp.put(nrm, batch * 24), *dom = bp.put(omega, batch * 24), *dt = bp.put(t, batch * 24),
-           *dout = bp.take((size_t)batch * OFK_SOLVE_DOUBLES * 8), *der = bp.take((size_t)batch * OFK_EPI_DOUBLES * 8), *dpt = bp.take(4 * wb),
-           *dwts = nullptr;
-    if (rob) {
-        double *dwork = bp.take(7 * wb);
-        dwts = bp.take(wb);
-        double *dtmp = bp.take(wb), *dst = bp.take((size_t)batch * OFK_ROBUST_DOUBLES * 8);
-        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_epipolar: upload failed");
-        ofk_launch_solve_robust(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, r, dwork, dwts, dtmp, dst, dout);
-    } else {
-        if (bp.rc) return ofk_fail(c, OFK_E_HIP, "ofk_velocity_solve_epipolar: upload failed");
-        ofk_launch_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, dout);
-    }
-    ofk_launch_epi_solve(c->stream, dx, du, dval, batch, n, dd, dn, dom, dt, dwts, ev, dout, der, dpt);
-    TRY(check_launch(c, "k_epi_solve"));
-    TRY(get(c, epi, der, (size_t)batch * OFK_EPI_DOUBLES * 8));
-    TRY(get(c, points, dpt, 4 * wb));
-    return get(c, out, dout, (size_t)batch * OFK_SOLVE_DOUBLES * 8);
+    const char *who = "ofk_velocity_solve_epipolar";
+    return solve_second_impl(c, who, "epipolar solve", ev && epi && points, variant, x, u, valid, batch, n, d, nrm, omega, t, wgt, r, [&] {
+        TRY(check_epipolar(c, ev, who));
+        if (ev->mode != OFK_EPI_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode must be OFK_EPI_ON", who);
+        return (int)OFK_OK;
+    }, "k_epi_solve", [&](const ofk_stage_in &in, const double *w, double *dout, double *drec, double *dpt) {
+        ofk_launch_epi_solve(c->stream, in, w, ev, dout, drec, dpt);
+    }, out, epi, OFK_EPI_DOUBLES, points);
 }
 
 extern "C" int ofk_imu_propagate(ofk_ctx *c, double *state, const double *msg, int batch)
@@ -2068,10 +1983,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
     const bool fork = S > 1 && !c->slices_open;
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
-    if (c->cov.mode != OFK_COV_OFF) { TRY(cov_alloc(c)); c->cov_batch = B; }
-    TRY(joint_prepare(c, B, "ofk_pairs_run"));
-    TRY(plane_prepare(c, B, p->solve_variant, "ofk_pairs_run"));
-    TRY(epi_prepare(c, B, p->solve_variant, "ofk_pairs_run"));
+    TRY(second_prepare(c, B, p->solve_variant, nullptr, "ofk_pairs_run"));
     TRY(camera_prepare(c, B));
     const bool cam = camera_on(c) || rs_on(c) || fm_on(c);       // the solve stage reads the ideal / corrected / rewritten points
     TRY(need_streams(c, S, overlap));
@@ -2621,23 +2533,8 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     } else if (p->solve_variant != OFK_SOLVE_NODE && p->solve_variant != OFK_SOLVE_SIM) return ofk_fail(c, OFK_E_INVALID, "solve_variant must be NODE or SIM");
     TRY(check_grid(c, &c->grid, h, w, "ofk_stream_step"));
     TRY(fm_check_step(c, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
-    const bool cov_on = c->cov.mode != OFK_COV_OFF;
-    if (cov_on && fu && (p->solve_variant == OFK_SOLVE_OFMODULE || fu->flow == OFK_FLOW_ROTATIONAL))
-        return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused: OFK_SOLVE_OFMODULE / OFK_FLOW_ROTATIONAL are not the sensor model: no covariance (ofk_set_cov is on)");
-    const bool joint_on = c->joint.mode != OFK_JOINT_OFF;
-    if (joint_on && fu && (p->solve_variant == OFK_SOLVE_OFMODULE || fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY))
-        return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused: OFK_SOLVE_OFMODULE / OFK_FLOW_ROTATIONAL / OFK_KEEP_LEGACY are not the sensor model: no joint solve (ofk_set_joint is on)");
-    if (cov_on) { TRY(cov_alloc(c)); c->cov_batch = B; }
-    TRY(joint_prepare(c, B, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
-    const bool plane_on = c->plane.mode != OFK_PLANE_OFF;
-    if (plane_on && fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY))
-        return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused: OFK_FLOW_ROTATIONAL / OFK_KEEP_LEGACY are not the sensor model: no plane solve (ofk_set_plane is on)");
-    TRY(plane_prepare(c, B, p->solve_variant, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
-    const bool epi_on = c->epi.mode != OFK_EPI_OFF;
-    if (epi_on && fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY))
-        return ofk_fail(c, OFK_E_INVALID, "ofk_stream_step_fused: OFK_FLOW_ROTATIONAL / OFK_KEEP_LEGACY are not the sensor model: no epipolar solve (ofk_set_epipolar is on)");
-    TRY(epi_prepare(c, B, p->solve_variant, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
-    const int defer = (cov_on || joint_on || plane_on || epi_on) && fu && fu->filter ? 1 : 0;   // the covariance / joint / plane / epipolar kernel corrects
+    TRY(second_prepare(c, B, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
+    const int defer = second_on(c) && fu && fu->filter ? 1 : 0;   // the second-stage kernel corrects
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
@@ -2665,32 +2562,18 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     TRY(track(c, c->stream, view_of(c, 0, B, 0), lv, p, fu && fu->use_imu ? c->imu_state : nullptr));
     if (zones_on)                                                // the solve stage turns the status into its keep flags: rule 1 needs both
         OFK_HIP(c, hipMemcpyAsync(c->zone_status, c->status, (size_t)B * c->max_pts, hipMemcpyDeviceToDevice, c->stream));
-    if (fu && c->robust.loss != OFK_ROBUST_OFF)
-        ofk_launch_stream_fuse_robust(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
-                                      c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, p->use_feasibility, p->feas_T,
-                                      c->records, c->fused, &c->robust, c->rob_work, c->rob_w, c->rob_wtmp, c->rob_stats, B, defer);
-    else if (fu)
-        ofk_launch_stream_fuse(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->imu_dv,
-                               c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, p->use_feasibility, p->feas_T,
-                               c->records, c->fused, B, defer);
-    else
+    if (fu) {
+        const bool rob = c->robust.loss != OFK_ROBUST_OFF;
+        const ofk_stream_in in = {sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats,
+                                  c->kf_x, c->kf_P, fu, p->solve_variant, c->records, c->fused, B, defer};
+        if (rob)
+            ofk_launch_stream_fuse_robust(c->stream, in, c->imu_dv, p->use_feasibility, p->feas_T, &c->robust, c->rob_work, c->rob_w, c->rob_wtmp,
+                                          c->rob_stats);
+        else
+            ofk_launch_stream_fuse(c->stream, in, c->imu_dv, p->use_feasibility, p->feas_T);
+        for (const second_setting &s : SECOND) if (s.mode(c)) s.stream(c, in, rob ? c->rob_w : nullptr);
+    } else
         solve_pairs(c, c->stream, sp, sn, c->status, c->counts, c->sensors, p, nullptr, c->records, 0, B, true);
-    if (cov_on && fu)
-        ofk_launch_stream_cov(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm,
-                              c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, c->records, c->fused,
-                              c->robust.loss != OFK_ROBUST_OFF ? c->rob_w : nullptr, &c->cov, c->cov_rec, B);
-    if (joint_on && fu)
-        ofk_launch_stream_joint(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm,
-                                c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, c->records, c->fused,
-                                c->robust.loss != OFK_ROBUST_OFF ? c->rob_w : nullptr, &c->joint, c->joint_rec, B, defer);
-    if (plane_on && fu)
-        ofk_launch_stream_plane(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm,
-                                c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, c->records, c->fused,
-                                c->robust.loss != OFK_ROBUST_OFF ? c->rob_w : nullptr, &c->plane, c->plane_rec, B, defer);
-    if (epi_on && fu)
-        ofk_launch_stream_epi(c->stream, sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm,
-                              c->kf_nc, c->kf_mats, c->kf_x, c->kf_P, fu, p->solve_variant, c->records, c->fused,
-                              c->robust.loss != OFK_ROBUST_OFF ? c->rob_w : nullptr, &c->epi, c->epi_rec, c->epi_pts, B, defer);
     // re-detection for the streams that had few features (node:157-166): mask = discs around the OLD positions, image = OLD frame.
     // The host knows the track counts from the previous call, so the whole branch is skipped when no stream needs it.
     // of_module.py:138 `continue`: a step of the ONE stream that did not solve leaves old_gray / old_pos as they were.  The host has to

@@ -147,6 +147,18 @@ int ofk_jpeg_decode_device(ofk_ctx *c, const uint8_t *const *jpeg, const size_t 
 // [batch][2] statistics, all of the launch's first image on
 struct ofk_sel_grid { int cell, cap, max_rank; const float *occ_pts; const int *occ_counts; int occ_stride; int *stats; };
 
+// --- what the solve launchers of one form share: the stage entries' device arrays, a slice's resident pairs, a fused stream step
+struct ofk_stage_in { int variant; const double *x, *u; const uint8_t *valid; int batch, n; const double *d, *nrm, *omega, *t; };
+struct ofk_pairs_in {
+    const float *prev_pts, *next_pts; const uint8_t *status; const int *counts; int pts_stride; const double *sensors;
+    int variant, use_feas; double feas_T; double *records; int batch;
+};
+struct ofk_stream_in {
+    const float *prev_pts, *next_pts; uint8_t *status; const int *counts; int pts_stride; const double *sensors; double *imu_state;
+    int ns, nm, nc; const double *kf_mats; double *kf_x, *kf_P; const ofk_fusion *f; int variant; double *records, *fused; int batch;
+    int defer;                                                   // see fuse_args.defer
+};
+
 // --- launchers (all asynchronous on `s`; pointers are device pointers)
 void ofk_launch_gray(hipStream_t s, const uint8_t *bgr, size_t bgr_stride, uint8_t *gray, size_t gray_stride, int batch,
                      int h, int w);
@@ -222,60 +234,26 @@ void ofk_launch_pairs_robust(hipStream_t s, const float *prev_pts, const float *
 void ofk_launch_solve_robust(hipStream_t s, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
                              const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
                              const ofk_robust *r, double *work, double *weights, double *wtmp, double *stats, double *out);
-void ofk_launch_stream_fuse_robust(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
-                                   const double *sensors, double *imu_state, double *imu_dv, int ns, int nm, int nc, const double *kf_mats,
-                                   double *kf_x, double *kf_P, const ofk_fusion *f, int variant, int use_feas, double feas_T, double *records,
-                                   double *fused, const ofk_robust *r, double *work, double *weights, double *wtmp, double *stats, int batch,
-                                   int defer_correct = 0);
-// the velocity covariance (k_cov.inc), behind the solve kernels; weights NULL = the plain solve ran; cov: the slice's rows of cov_rec
-void ofk_launch_cov_solve(hipStream_t s, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
-                          const double *d, const double *nrm, const double *omega, const double *t, const double *weights,
-                          const ofk_cov *c, const double *out, double *cov);
-void ofk_launch_pairs_cov(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts,
-                          int pts_stride, const double *sensors, int variant, int use_feas, double feas_T, const double *weights,
-                          const ofk_cov *c, const double *records, double *cov, int batch);
-void ofk_launch_stream_cov(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
-                           const double *sensors, double *imu_state, int ns, int nm, int nc, const double *kf_mats, double *kf_x, double *kf_P,
-                           const ofk_fusion *f, int variant, double *records, double *fused, const double *weights, const ofk_cov *c,
-                           double *cov, int batch);
+void ofk_launch_stream_fuse_robust(hipStream_t s, const ofk_stream_in &in, double *imu_dv, int use_feas, double feas_T, const ofk_robust *r,
+                                   double *work, double *weights, double *wtmp, double *stats);
+// The second-stage solves (k_second.inc and k_cov / k_joint / k_plane / k_epi.inc), behind the solve kernels, in the three launch forms.
+// weights: the robust solve's rows, NULL = the plain solve ran.  The last pointers are the slice's rows of the setting's records (and
+// of epi_pts).  Joint, plane and epipolar rewrite out / records in place; the covariance only reads them.
+void ofk_launch_cov_solve(hipStream_t s, const ofk_stage_in &in, const double *weights, const ofk_cov *c, const double *out, double *cov);
+void ofk_launch_joint_solve(hipStream_t s, const ofk_stage_in &in, const double *weights, const ofk_joint *j, double *out, double *joint);
+void ofk_launch_plane_solve(hipStream_t s, const ofk_stage_in &in, const double *weights, const ofk_plane *p, double *out, double *plane);
+void ofk_launch_epi_solve(hipStream_t s, const ofk_stage_in &in, const double *weights, const ofk_epipolar *e, double *out, double *epi,
+                          double *pts);
+void ofk_launch_pairs_cov(hipStream_t s, const ofk_pairs_in &in, const double *weights, const ofk_cov *c, double *cov);
+void ofk_launch_pairs_joint(hipStream_t s, const ofk_pairs_in &in, const double *weights, const ofk_joint *j, double *joint);
+void ofk_launch_pairs_plane(hipStream_t s, const ofk_pairs_in &in, const double *weights, const ofk_plane *p, double *plane);
+void ofk_launch_pairs_epi(hipStream_t s, const ofk_pairs_in &in, const double *weights, const ofk_epipolar *e, double *epi, double *pts);
+void ofk_launch_stream_cov(hipStream_t s, const ofk_stream_in &in, const double *weights, const ofk_cov *c, double *cov);
+void ofk_launch_stream_joint(hipStream_t s, const ofk_stream_in &in, const double *weights, const ofk_joint *j, double *joint);
+void ofk_launch_stream_plane(hipStream_t s, const ofk_stream_in &in, const double *weights, const ofk_plane *p, double *plane);
+void ofk_launch_stream_epi(hipStream_t s, const ofk_stream_in &in, const double *weights, const ofk_epipolar *e, double *epi, double *pts);
 void ofk_launch_kf_records_cov(hipStream_t s, int ns, int nm, const double *mats, double *x, double *P, const double *records, double *cov,
                                const ofk_cov *c, double z_sign, int z_source, int batch);
-// the joint velocity and rotation solve (k_joint.inc), behind the solve kernels: rewrites out / records in place; weights NULL = the
-// plain solve ran; joint: the slice's rows of joint_rec
-void ofk_launch_joint_solve(hipStream_t s, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
-                            const double *d, const double *nrm, const double *omega, const double *t, const double *weights,
-                            const ofk_joint *j, double *out, double *joint);
-void ofk_launch_pairs_joint(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts,
-                            int pts_stride, const double *sensors, int variant, int use_feas, double feas_T, const double *weights,
-                            const ofk_joint *j, double *records, double *joint, int batch);
-void ofk_launch_stream_joint(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
-                             const double *sensors, double *imu_state, int ns, int nm, int nc, const double *kf_mats, double *kf_x, double *kf_P,
-                             const ofk_fusion *f, int variant, double *records, double *fused, const double *weights, const ofk_joint *j,
-                             double *joint, int batch, int defer);
-// the epipolar solve (k_epi.inc), behind the solve kernels: rewrites out / records in place; weights NULL = the plain solve ran; epi /
-// pts: the slice's rows of epi_rec / epi_pts
-void ofk_launch_epi_solve(hipStream_t s, const double *x, const double *u, const uint8_t *valid, int batch, int n, const double *d,
-                          const double *nrm, const double *omega, const double *t, const double *weights, const ofk_epipolar *e,
-                          double *out, double *epi, double *pts);
-void ofk_launch_pairs_epi(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts,
-                          int pts_stride, const double *sensors, int use_feas, double feas_T, const double *weights, const ofk_epipolar *e,
-                          double *records, double *epi, double *pts, int batch);
-void ofk_launch_stream_epi(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
-                           const double *sensors, double *imu_state, int ns, int nm, int nc, const double *kf_mats, double *kf_x, double *kf_P,
-                           const ofk_fusion *f, int variant, double *records, double *fused, const double *weights, const ofk_epipolar *e,
-                           double *epi, double *pts, int batch, int defer);
-// the plane solve (k_plane.inc), behind the solve kernels: rewrites out / records in place; weights NULL = the plain solve ran;
-// plane: the slice's rows of plane_rec
-void ofk_launch_plane_solve(hipStream_t s, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
-                            const double *d, const double *nrm, const double *omega, const double *t, const double *weights,
-                            const ofk_plane *p, double *out, double *plane);
-void ofk_launch_pairs_plane(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts,
-                            int pts_stride, const double *sensors, int variant, int use_feas, double feas_T, const double *weights,
-                            const ofk_plane *p, double *records, double *plane, int batch);
-void ofk_launch_stream_plane(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
-                             const double *sensors, double *imu_state, int ns, int nm, int nc, const double *kf_mats, double *kf_x, double *kf_P,
-                             const ofk_fusion *f, int variant, double *records, double *fused, const double *weights, const ofk_plane *p,
-                             double *plane, int batch, int defer);
 void ofk_launch_records_f32(hipStream_t s, const double *records, float *dst, int batch);
 
 void ofk_launch_flow_model(hipStream_t s, const double *x, int batch, int n, const double *v, const double *omega,
@@ -290,10 +268,7 @@ void ofk_launch_imu(hipStream_t s, double *state, const double *msg, int batch);
 void ofk_launch_kf_records(hipStream_t s, int ns, int nm, const double *mats, double *x, double *P, const double *records, double z_sign,
                            int z_source, int batch);
 void ofk_launch_imu_seq(hipStream_t s, double *state, double *dv, const double *msgs, const int *counts, int max_msgs, int batch);
-void ofk_launch_stream_fuse(hipStream_t s, const float *prev_pts, const float *next_pts, uint8_t *status, const int *counts, int pts_stride,
-                            const double *sensors, double *imu_state, double *imu_dv, int ns, int nm, int nc, const double *kf_mats,
-                            double *kf_x, double *kf_P, const ofk_fusion *f, int variant, int use_feas, double feas_T, double *records,
-                            double *fused, int batch, int defer_correct = 0);     // defer_correct: see fuse_args.defer
+void ofk_launch_stream_fuse(hipStream_t s, const ofk_stream_in &in, double *imu_dv, int use_feas, double feas_T);
 void ofk_launch_replace_tracks(hipStream_t s, const int *limit, const float *new_pts, const int *new_counts, int pts_stride, float *tracks,
                                int *counts, int batch);
 void ofk_launch_post_solve(hipStream_t s, const double *v_obs, const double *rot, const double *ang,

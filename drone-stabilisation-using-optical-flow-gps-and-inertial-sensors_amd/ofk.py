@@ -1147,13 +1147,12 @@ class Context:
             self._ck(self._L.ofk_robust_download(self._h, _p(w), self.max_pts, _p(st)))
         return w[:batch].copy(), st[:batch].copy()
 
-    def velocity_solve_cov(self, variant, x, u, d=None, nrm=None, omega=None, t=None, valid=None, robust=None, cov=None, **settings):
-        """ofk_velocity_solve_cov: velocity_solve's arguments (NODE or SIM), an optional Robust and the covariance setting (a Cov, or
-        cov_setting's keywords).  Returns out [B,8], cov [B,24] (single problem: [8], [24])."""
-        cv = cov if cov is not None else cov_setting(**settings)
+    def _velocity_solve_second(self, name, variant, x, u, d, nrm, omega, t, valid, robust, setting, doubles, no_points, points=False):
+        """ofk_velocity_solve_<name>: the marshalling the second-stage stage entries share.  no_points(rec, d, nrm, omega) fills the
+        records of a call without points.  Returns (out, rec) or, with points, (out, rec, point rows)."""
         x = _arr(x, np.float64); u = _arr(u, np.float64)
         if u.shape[:-1] != x.shape[:-1] or x.shape[-1] != 2 or u.shape[-1] < 2:
-            raise ValueError(f"velocity_solve_cov: x {x.shape} must be [..., n, 2] and u {u.shape} [..., n, >=2] over the same points")
+            raise ValueError(f"velocity_solve_{name}: x {x.shape} must be [..., n, 2] and u {u.shape} [..., n, >=2] over the same points")
         single = x.ndim == 2
         if single:
             x = x[None]; u = u[None]
@@ -1162,14 +1161,30 @@ class Context:
         nrm = _arr(nrm, np.float64, (B, 3))
         d = _opt(d, np.float64, (B,)); omega = _opt(omega, np.float64, (B, 3)); t = _opt(t, np.float64, (B, 3))
         valid = _opt(valid, np.uint8, (B, n))
-        out = np.zeros((B, SOLVE_DOUBLES), np.float64); rec = np.zeros((B, COV_DOUBLES), np.float64)
-        if not n:                                               # no points: velocity_solve's zeros, a void covariance
+        res = [np.zeros((B, SOLVE_DOUBLES), np.float64), np.zeros((B, doubles), np.float64)] + ([np.zeros((B, n, 4), np.float64)] if points else [])
+        if not n:                                               # no points: velocity_solve's zeros
+            no_points(res[1], d, nrm, omega)
+        else:
+            with self._lock:
+                self._ck(getattr(self._L, "ofk_velocity_solve_" + name)(
+                    self._h, int(variant), _p(x), _p(u), _p(valid), B, n, _p(d), _p(nrm), _p(omega), _p(t), None,
+                    C.byref(robust) if robust is not None else None, C.byref(setting), *[_p(a) for a in res]))
+        return tuple(a[0] for a in res) if single else tuple(res)
+
+    def _records_download(self, name, batch, *shape):
+        """ofk_<name>_download into [max_batch, *shape]: its first `batch` rows."""
+        rec = np.zeros((self.max_batch,) + shape, np.float64)
+        with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
+            self._ck(getattr(self._L, f"ofk_{name}_download")(self._h, _p(rec)))
+        return rec[:batch].copy()
+
+    def velocity_solve_cov(self, variant, x, u, d=None, nrm=None, omega=None, t=None, valid=None, robust=None, cov=None, **settings):
+        """ofk_velocity_solve_cov: velocity_solve's arguments (NODE or SIM), an optional Robust and the covariance setting (a Cov, or
+        cov_setting's keywords).  Returns out [B,8], cov [B,24] (single problem: [8], [24])."""
+        cv = cov if cov is not None else cov_setting(**settings)
+        def void(rec, d, nrm, omega):                           # a void covariance
             rec[:, 13] = 1.0
-            return (out[0], rec[0]) if single else (out, rec)
-        with self._lock:
-            self._ck(self._L.ofk_velocity_solve_cov(self._h, int(variant), _p(x), _p(u), _p(valid), B, n, _p(d), _p(nrm), _p(omega), _p(t),
-                                                    None, C.byref(robust) if robust is not None else None, C.byref(cv), _p(out), _p(rec)))
-        return (out[0], rec[0]) if single else (out, rec)
+        return self._velocity_solve_second("cov", variant, x, u, d, nrm, omega, t, valid, robust, cv, COV_DOUBLES, void)
 
     def set_cov(self, cov=None, **settings):
         """ofk_set_cov: a Cov (or cov_setting's keywords); None or mode "off" switches it off.  Every later pairs_run, pairs filter step
@@ -1184,36 +1199,17 @@ class Context:
 
     def cov_download(self, batch):
         """cov [batch, 24] of the latest run / step with the setting on."""
-        rec = np.zeros((self.max_batch, COV_DOUBLES), np.float64)
-        with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
-            self._ck(self._L.ofk_cov_download(self._h, _p(rec)))
-        return rec[:batch].copy()
+        return self._records_download("cov", batch, COV_DOUBLES)
 
     def velocity_solve_joint(self, variant, x, u, d=None, nrm=None, omega=None, t=None, valid=None, robust=None, joint=None, **settings):
         """ofk_velocity_solve_joint: velocity_solve's arguments (NODE or SIM), an optional Robust and the joint setting (a Joint, or
         joint_setting's keywords).  Returns out [B,8] after the joint rewrite, joint [B,32] (single problem: [8], [32])."""
         jv = joint if joint is not None else joint_setting(**settings)
-        x = _arr(x, np.float64); u = _arr(u, np.float64)
-        if u.shape[:-1] != x.shape[:-1] or x.shape[-1] != 2 or u.shape[-1] < 2:
-            raise ValueError(f"velocity_solve_joint: x {x.shape} must be [..., n, 2] and u {u.shape} [..., n, >=2] over the same points")
-        single = x.ndim == 2
-        if single:
-            x = x[None]; u = u[None]
-        B, n, _ = x.shape
-        u = _arr(u[..., :2], np.float64)
-        nrm = _arr(nrm, np.float64, (B, 3))
-        d = _opt(d, np.float64, (B,)); omega = _opt(omega, np.float64, (B, 3)); t = _opt(t, np.float64, (B, 3))
-        valid = _opt(valid, np.uint8, (B, n))
-        out = np.zeros((B, SOLVE_DOUBLES), np.float64); rec = np.zeros((B, JOINT_DOUBLES), np.float64)
-        if not n:                                               # no points: velocity_solve's zeros, nothing attempted
+        def nothing(rec, d, nrm, omega):                        # nothing attempted
             if omega is not None:
                 rec[:, 0:3] = omega
             rec[:, 10] = 1.0
-            return (out[0], rec[0]) if single else (out, rec)
-        with self._lock:
-            self._ck(self._L.ofk_velocity_solve_joint(self._h, int(variant), _p(x), _p(u), _p(valid), B, n, _p(d), _p(nrm), _p(omega), _p(t),
-                                                      None, C.byref(robust) if robust is not None else None, C.byref(jv), _p(out), _p(rec)))
-        return (out[0], rec[0]) if single else (out, rec)
+        return self._velocity_solve_second("joint", variant, x, u, d, nrm, omega, t, valid, robust, jv, JOINT_DOUBLES, nothing)
 
     def set_joint(self, joint=None, **settings):
         """ofk_set_joint: a Joint (or joint_setting's keywords); None or mode False switches it off.  Every later pairs_run and stream
@@ -1228,37 +1224,18 @@ class Context:
 
     def joint_download(self, batch):
         """joint [batch, 32] of the latest run / step with the setting on."""
-        rec = np.zeros((self.max_batch, JOINT_DOUBLES), np.float64)
-        with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
-            self._ck(self._L.ofk_joint_download(self._h, _p(rec)))
-        return rec[:batch].copy()
+        return self._records_download("joint", batch, JOINT_DOUBLES)
 
     def velocity_solve_plane(self, variant, x, u, d=None, nrm=None, omega=None, t=None, valid=None, robust=None, plane=None, **settings):
         """ofk_velocity_solve_plane: velocity_solve's arguments (NODE or SIM), an optional Robust and the plane setting (a Plane, or
         plane_setting's keywords).  Returns out [B,8] after the rewrite, plane [B,32] (single problem: [8], [32])."""
         pv = plane if plane is not None else plane_setting(**settings)
-        x = _arr(x, np.float64); u = _arr(u, np.float64)
-        if u.shape[:-1] != x.shape[:-1] or x.shape[-1] != 2 or u.shape[-1] < 2:
-            raise ValueError(f"velocity_solve_plane: x {x.shape} must be [..., n, 2] and u {u.shape} [..., n, >=2] over the same points")
-        single = x.ndim == 2
-        if single:
-            x = x[None]; u = u[None]
-        B, n, _ = x.shape
-        u = _arr(u[..., :2], np.float64)
-        nrm = _arr(nrm, np.float64, (B, 3))
-        d = _opt(d, np.float64, (B,)); omega = _opt(omega, np.float64, (B, 3)); t = _opt(t, np.float64, (B, 3))
-        valid = _opt(valid, np.uint8, (B, n))
-        out = np.zeros((B, SOLVE_DOUBLES), np.float64); rec = np.zeros((B, PLANE_DOUBLES), np.float64)
-        if not n:                                               # no points: velocity_solve's zeros, nothing attempted
+        def nothing(rec, d, nrm, omega):                        # nothing attempted
             rec[:, 0:3] = nrm
             if d is not None:
                 rec[:, 3] = d
             rec[:, 10] = 1.0
-            return (out[0], rec[0]) if single else (out, rec)
-        with self._lock:
-            self._ck(self._L.ofk_velocity_solve_plane(self._h, int(variant), _p(x), _p(u), _p(valid), B, n, _p(d), _p(nrm), _p(omega), _p(t),
-                                                      None, C.byref(robust) if robust is not None else None, C.byref(pv), _p(out), _p(rec)))
-        return (out[0], rec[0]) if single else (out, rec)
+        return self._velocity_solve_second("plane", variant, x, u, d, nrm, omega, t, valid, robust, pv, PLANE_DOUBLES, nothing)
 
     def set_plane(self, plane=None, **settings):
         """ofk_set_plane: a Plane (or plane_setting's keywords); None or mode False switches it off.  Every later pairs_run and stream
@@ -1273,36 +1250,16 @@ class Context:
 
     def plane_download(self, batch):
         """plane [batch, 32] of the latest run / step with the setting on."""
-        rec = np.zeros((self.max_batch, PLANE_DOUBLES), np.float64)
-        with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
-            self._ck(self._L.ofk_plane_download(self._h, _p(rec)))
-        return rec[:batch].copy()
+        return self._records_download("plane", batch, PLANE_DOUBLES)
 
     def velocity_solve_epipolar(self, variant, x, u, d=None, nrm=None, omega=None, t=None, valid=None, robust=None, epipolar=None, **settings):
         """ofk_velocity_solve_epipolar: velocity_solve's arguments (NODE or SIM), an optional Robust and the epipolar setting (an
         Epipolar, or epipolar_setting's keywords).  Returns out [B,8] after the rewrite, the record [B,32] and the point rows
         [B,n,4] (single problem: [8], [32], [n,4])."""
         ev = epipolar if epipolar is not None else epipolar_setting(**settings)
-        x = _arr(x, np.float64); u = _arr(u, np.float64)
-        if u.shape[:-1] != x.shape[:-1] or x.shape[-1] != 2 or u.shape[-1] < 2:
-            raise ValueError(f"velocity_solve_epipolar: x {x.shape} must be [..., n, 2] and u {u.shape} [..., n, >=2] over the same points")
-        single = x.ndim == 2
-        if single:
-            x = x[None]; u = u[None]
-        B, n, _ = x.shape
-        u = _arr(u[..., :2], np.float64)
-        nrm = _arr(nrm, np.float64, (B, 3))
-        d = _opt(d, np.float64, (B,)); omega = _opt(omega, np.float64, (B, 3)); t = _opt(t, np.float64, (B, 3))
-        valid = _opt(valid, np.uint8, (B, n))
-        out = np.zeros((B, SOLVE_DOUBLES), np.float64); rec = np.zeros((B, EPI_DOUBLES), np.float64); pts = np.zeros((B, n, 4), np.float64)
-        if not n:                                               # no points: velocity_solve's zeros, nothing attempted
+        def nothing(rec, d, nrm, omega):                        # nothing attempted
             rec[:, 10] = 1.0
-            return (out[0], rec[0], pts[0]) if single else (out, rec, pts)
-        with self._lock:
-            self._ck(self._L.ofk_velocity_solve_epipolar(self._h, int(variant), _p(x), _p(u), _p(valid), B, n, _p(d), _p(nrm), _p(omega),
-                                                         _p(t), None, C.byref(robust) if robust is not None else None, C.byref(ev),
-                                                         _p(out), _p(rec), _p(pts)))
-        return (out[0], rec[0], pts[0]) if single else (out, rec, pts)
+        return self._velocity_solve_second("epipolar", variant, x, u, d, nrm, omega, t, valid, robust, ev, EPI_DOUBLES, nothing, points=True)
 
     def set_epipolar(self, epipolar=None, **settings):
         """ofk_set_epipolar: an Epipolar (or epipolar_setting's keywords); None or mode False switches it off.  Every later pairs_run
@@ -1319,11 +1276,8 @@ class Context:
     def epipolar_download(self, batch):
         """The record [batch, 32] and the point rows [batch, max_pts, 4] (rho, r, |b|, flag) of the latest run / step with the
         setting on."""
-        rec = np.zeros((self.max_batch, EPI_DOUBLES), np.float64); pts = np.zeros((self.max_batch, self.max_pts, 4), np.float64)
-        with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
-            self._ck(self._L.ofk_epipolar_download(self._h, _p(rec)))
-            self._ck(self._L.ofk_epipolar_points_download(self._h, _p(pts)))
-        return rec[:batch].copy(), pts[:batch].copy()
+        with self._lock:                                         # both from the same run
+            return self._records_download("epipolar", batch, EPI_DOUBLES), self._records_download("epipolar_points", batch, self.max_pts, 4)
 
     def imu_propagate(self, state, msg):
         state = _arr(state, np.float64).copy(); msg = _arr(msg, np.float64)
