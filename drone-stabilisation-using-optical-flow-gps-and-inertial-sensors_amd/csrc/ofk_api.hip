@@ -351,6 +351,33 @@ static int check_launch(ofk_ctx *c, const char *who)
     if (e != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
     return OFK_OK;
 }
+// what the stage entries over [batch][stride] point arrays ask of their counts
+static int check_counts(ofk_ctx *c, const char *who, const int *counts, int batch, int stride)
+{
+    for (int b = 0; b < batch; ++b)
+        if (counts[b] < 0 || counts[b] > stride) return ofk_fail(c, OFK_E_INVALID, "%s: counts[%d]=%d outside 0..%d", who, b, counts[b], stride);
+    return OFK_OK;
+}
+
+// What every ofk_set_* / ofk_get_* pair of a struct setting does.  v == NULL: off(the context's copy) and nothing else; otherwise
+// check(v), the setter's rules (its check_* function, which composes the refusal), and the struct is copied whole.  A setter that
+// reads a struct whose mode is OFF like NULL hands NULL in for it.
+template <class T, class Off, class Check>
+static int setting_set(ofk_ctx *c, T ofk_ctx::*member, const T *v, Off off, Check check)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!v) { off(c->*member); return OFK_OK; }
+    TRY(check(v));
+    c->*member = *v;
+    return OFK_OK;
+}
+template <class T>
+static int setting_get(const ofk_ctx *c, T ofk_ctx::*member, T *out)
+{
+    if (!c || !out) return OFK_E_INVALID;
+    *out = c->*member;
+    return OFK_OK;
+}
 
 static int lazy_mask(ofk_ctx *c)
 {
@@ -424,6 +451,29 @@ static int check_select(ofk_ctx *c, int max_corners, double quality, double min_
 
 static uint8_t *const *pyr_set(ofk_ctx *c, int set) { return set ? c->pyr_alt : c->pyr; }   // set 1: the overlapped schedule's second one
 
+// ------------------------------------------------------------------------------------------------ the point corrections
+// One row per setting that rewrites the tracked points in front of the solve stage, in the order of their launches in track().  With
+// any of them on, the solve stage reads pts_prev_u / pts_next_u instead of pts_prev / pts_next; everything in the image keeps the raw ones.
+struct point_setting {
+    const char *set;                                            // the setter's name
+    bool (*on)(const ofk_ctx *);
+    int ofk_ctx::*batch;                                        // images of the latest run / step with it on (its download), 0 = none
+};
+static bool camera_on(const ofk_ctx *c) { return c->camera.model != OFK_CAMERA_OFF; }
+static bool rs_on(const ofk_ctx *c) { return c->rs.mode != OFK_RS_OFF; }
+static bool fm_on(const ofk_ctx *c) { return c->fm.mode != OFK_FM_OFF; }
+enum { POINTS_CAMERA, POINTS_RS, POINTS_FM };
+static const point_setting POINTS[3] = {
+    {"ofk_set_camera", camera_on, &ofk_ctx::cam_batch},
+    {"ofk_set_rolling_shutter", rs_on, &ofk_ctx::rs_batch},
+    {"ofk_set_finite_motion", fm_on, &ofk_ctx::fm_batch},
+};
+static bool solve_points_on(const ofk_ctx *c)
+{
+    for (const point_setting &s : POINTS) if (s.on(c)) return true;
+    return false;
+}
+
 // The context's per-image buffers from image b0 on, for nb images: the one place that knows their strides.  A slice of ofk_pairs_run
 // builds one per stream; every other entry point works on the whole batch (b0 = 0, pyramid set 0).
 struct View {
@@ -436,7 +486,8 @@ struct View {
     double *sensors, *records;
     float *pts_back, *err_back, *fb2; uint8_t *status_back; int *gate_stats;   // NULL until a run with a track gate on (gate_alloc)
     int *grid_stats;                                             // NULL until a selection with a corner grid on (grid_alloc)
-    float *pts_prev_u, *pts_next_u;                              // NULL until a run with the camera or the rolling shutter on (camera_prepare)
+    float *pts_prev_u, *pts_next_u;                              // NULL until a run with a point correction on (solve_points_prepare)
+    const float *solve_prev, *solve_next;                        // what the solve stage reads: those two with a point correction on, else pts_prev / pts_next
 };
 static View view_of(ofk_ctx *c, int b0, int nb, int set)
 {
@@ -460,6 +511,8 @@ static View view_of(ofk_ctx *c, int b0, int nb, int set)
     v.grid_stats = c->grid_stats ? c->grid_stats + b * 2 : nullptr;
     v.pts_prev_u = c->pts_prev_u ? c->pts_prev_u + b * c->max_pts * 2 : nullptr;
     v.pts_next_u = c->pts_next_u ? c->pts_next_u + b * c->max_pts * 2 : nullptr;
+    const bool u = solve_points_on(c);
+    v.solve_prev = u ? v.pts_prev_u : v.pts_prev; v.solve_next = u ? v.pts_next_u : v.pts_next;
     return v;
 }
 
@@ -503,19 +556,10 @@ static int check_grid(ofk_ctx *c, const ofk_corner_grid *g, int h, int w, const 
 
 extern "C" int ofk_set_corner_grid(ofk_ctx *c, const ofk_corner_grid *g)
 {
-    if (!c) return OFK_E_INVALID;
-    if (!g) { c->grid.cell = 0; return OFK_OK; }
-    TRY(check_grid(c, g, 0, 0, "ofk_set_corner_grid"));
-    c->grid = *g;
-    return OFK_OK;
+    return setting_set(c, &ofk_ctx::grid, g, [](ofk_corner_grid &s) { s.cell = 0; },
+                       [c](const ofk_corner_grid *v) { return check_grid(c, v, 0, 0, "ofk_set_corner_grid"); });
 }
-
-extern "C" int ofk_get_corner_grid(const ofk_ctx *c, ofk_corner_grid *g)
-{
-    if (!c || !g) return OFK_E_INVALID;
-    *g = c->grid;
-    return OFK_OK;
-}
+extern "C" int ofk_get_corner_grid(const ofk_ctx *c, ofk_corner_grid *g) { return setting_get(c, &ofk_ctx::grid, g); }
 
 // the grid's resident buffers (statistics, the stage entries' occupancy list), allocated when a selection first needs them
 static int grid_alloc(ofk_ctx *c)
@@ -696,8 +740,6 @@ static void build_pyramids(ofk_ctx *c, hipStream_t s, uint8_t *pyr0, uint8_t *py
 static bool gate_on(const ofk_track_gate &g) { return g.fb_mode != OFK_FB_OFF || g.err_max != 0.0; }
 
 // ------------------------------------------------------------------------------------------------ camera setting
-static bool camera_on(const ofk_ctx *c) { return c->camera.model != OFK_CAMERA_OFF; }
-
 // one_focal: ofk_set_camera's extra rule (the solve has one scaling)
 static int check_camera(ofk_ctx *c, const ofk_camera *m, bool one_focal, const char *who)
 {
@@ -717,23 +759,12 @@ static int check_camera(ofk_ctx *c, const ofk_camera *m, bool one_focal, const c
 
 extern "C" int ofk_set_camera(ofk_ctx *c, const ofk_camera *m)
 {
-    if (!c) return OFK_E_INVALID;
-    if (!m || m->model == OFK_CAMERA_OFF) { c->camera.model = OFK_CAMERA_OFF; return OFK_OK; }
-    TRY(check_camera(c, m, true, "ofk_set_camera"));
-    c->camera = *m;
-    return OFK_OK;
+    return setting_set(c, &ofk_ctx::camera, m && m->model == OFK_CAMERA_OFF ? nullptr : m, [](ofk_camera &s) { s.model = OFK_CAMERA_OFF; },
+                       [c](const ofk_camera *v) { return check_camera(c, v, true, "ofk_set_camera"); });
 }
-
-extern "C" int ofk_get_camera(const ofk_ctx *c, ofk_camera *m)
-{
-    if (!c || !m) return OFK_E_INVALID;
-    *m = c->camera;
-    return OFK_OK;
-}
+extern "C" int ofk_get_camera(const ofk_ctx *c, ofk_camera *m) { return setting_get(c, &ofk_ctx::camera, m); }
 
 // ------------------------------------------------------------------------------------------------ rolling-shutter setting
-static bool rs_on(const ofk_ctx *c) { return c->rs.mode != OFK_RS_OFF; }
-
 // stage: ofk_rs_correct_points' extra rule (no run to take the frame height from)
 static int check_rs(ofk_ctx *c, const ofk_rshutter *r, bool stage, const char *who)
 {
@@ -751,23 +782,12 @@ static int check_rs(ofk_ctx *c, const ofk_rshutter *r, bool stage, const char *w
 
 extern "C" int ofk_set_rolling_shutter(ofk_ctx *c, const ofk_rshutter *r)
 {
-    if (!c) return OFK_E_INVALID;
-    if (!r || r->mode == OFK_RS_OFF) { c->rs.mode = OFK_RS_OFF; return OFK_OK; }
-    TRY(check_rs(c, r, false, "ofk_set_rolling_shutter"));
-    c->rs = *r;
-    return OFK_OK;
+    return setting_set(c, &ofk_ctx::rs, r && r->mode == OFK_RS_OFF ? nullptr : r, [](ofk_rshutter &s) { s.mode = OFK_RS_OFF; },
+                       [c](const ofk_rshutter *v) { return check_rs(c, v, false, "ofk_set_rolling_shutter"); });
 }
-
-extern "C" int ofk_get_rolling_shutter(const ofk_ctx *c, ofk_rshutter *r)
-{
-    if (!c || !r) return OFK_E_INVALID;
-    *r = c->rs;
-    return OFK_OK;
-}
+extern "C" int ofk_get_rolling_shutter(const ofk_ctx *c, ofk_rshutter *r) { return setting_get(c, &ofk_ctx::rs, r); }
 
 // ------------------------------------------------------------------------------------------------ finite-motion setting
-static bool fm_on(const ofk_ctx *c) { return c->fm.mode != OFK_FM_OFF; }
-
 static int check_fm(ofk_ctx *c, const ofk_finite_motion *f, const char *who)
 {
     if (f->mode != OFK_FM_EXACT) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is not OFK_FM_EXACT", who, f->mode);
@@ -778,37 +798,37 @@ static int check_fm(ofk_ctx *c, const ofk_finite_motion *f, const char *who)
 
 extern "C" int ofk_set_finite_motion(ofk_ctx *c, const ofk_finite_motion *f)
 {
-    if (!c) return OFK_E_INVALID;
-    if (!f || f->mode == OFK_FM_OFF) { c->fm.mode = OFK_FM_OFF; return OFK_OK; }
-    TRY(check_fm(c, f, "ofk_set_finite_motion"));
-    c->fm = *f;
-    return OFK_OK;
+    return setting_set(c, &ofk_ctx::fm, f && f->mode == OFK_FM_OFF ? nullptr : f, [](ofk_finite_motion &s) { s.mode = OFK_FM_OFF; },
+                       [c](const ofk_finite_motion *v) { return check_fm(c, v, "ofk_set_finite_motion"); });
 }
+extern "C" int ofk_get_finite_motion(const ofk_ctx *c, ofk_finite_motion *f) { return setting_get(c, &ofk_ctx::fm, f); }
 
-extern "C" int ofk_get_finite_motion(const ofk_ctx *c, ofk_finite_motion *f)
+// What a fused step may not have beside a setting that rewrites the sensor model's rows (ofk.h), and the refusal that names them.
+enum { NO_OFMODULE = 1, NO_ROTATIONAL = 2, NO_LEGACY = 4 };
+static int refuse_not_sensor_model(ofk_ctx *c, const char *who, int refused, const char *what, const char *set)
 {
-    if (!c || !f) return OFK_E_INVALID;
-    *f = c->fm;
-    return OFK_OK;
+    static const char *const names[3] = {"OFK_SOLVE_OFMODULE", "OFK_FLOW_ROTATIONAL", "OFK_KEEP_LEGACY"};
+    char list[64] = "";
+    for (int k = 0; k < 3; ++k)
+        if (refused >> k & 1) { if (list[0]) strcat(list, " / "); strcat(list, names[k]); }
+    return ofk_fail(c, OFK_E_INVALID, "%s: %s are not the sensor model: no %s (%s is on)", who, list, what, set);
 }
 
-// The fused steps' own refusals with the setting on (ofk.h): the rewrite is of the sensor model's rows.
+// The fused steps' own refusals with the finite motion on (ofk.h): the rewrite is of the sensor model's rows.
 static int fm_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const char *who)
 {
     if (!fm_on(c)) return OFK_OK;
     if (variant == OFK_SOLVE_OFMODULE || (fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY)))
-        return ofk_fail(c, OFK_E_INVALID, "%s: OFK_SOLVE_OFMODULE / OFK_FLOW_ROTATIONAL / OFK_KEEP_LEGACY are not the sensor model: no finite motion (ofk_set_finite_motion is on)", who);
+        return refuse_not_sensor_model(c, who, NO_OFMODULE | NO_ROTATIONAL | NO_LEGACY, "finite motion", POINTS[POINTS_FM].set);
     return OFK_OK;
 }
 
 // the solve stage's own points (the camera's ideal pixels, the rolling shutter's corrected ones, the finite motion's rewritten ones, or
-// any of them in turn): their resident buffers, allocated when a run first needs them; `batch`: the run's images, for
-// ofk_camera_download / ofk_rs_download / ofk_finite_download
-static int camera_prepare(ofk_ctx *c, int batch)
+// any of them in turn): their resident buffers, allocated when a run first needs them; `batch`: the run's images, on record for the
+// download of every row that is on
+static int solve_points_prepare(ofk_ctx *c, int batch)
 {
-    if (rs_on(c)) c->rs_batch = batch;
-    if (fm_on(c)) c->fm_batch = batch;
-    if (!camera_on(c) && !rs_on(c) && !fm_on(c)) return OFK_OK;
+    if (!solve_points_on(c)) return OFK_OK;
     if (!c->pts_prev_u) {                                        // one allocation, carved into the two buffers
         const size_t np = (size_t)c->max_batch * c->max_pts;
         float *base = nullptr;
@@ -817,7 +837,21 @@ static int camera_prepare(ofk_ctx *c, int batch)
         OFK_HIP(c, hipStreamSynchronize(c->stream));
         c->pts_prev_u = base; c->pts_next_u = base + np * 2;
     }
-    if (camera_on(c)) c->cam_batch = batch;
+    for (const point_setting &s : POINTS) if (s.on(c)) c->*s.batch = batch;
+    return OFK_OK;
+}
+
+// The points the solve stage of the latest run or step with the row's setting on saw: the first min(stride, max_pts) of each image.
+static int points_download(ofk_ctx *c, const point_setting &s, const char *who, float *prev, float *next, int stride)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->*s.batch < 1 || !c->pts_prev_u) return ofk_fail(c, OFK_E_INVALID, "%s: no run or step with %s on yet", who, s.set);
+    if (stride < 1) return ofk_fail(c, OFK_E_INVALID, "%s: stride %d", who, stride);
+    TRY(enter(c));
+    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    if (prev) OFK_HIP(c, hipMemcpy2DAsync(prev, (size_t)stride * 8, c->pts_prev_u, mp * 8, n * 8, c->*s.batch, hipMemcpyDeviceToHost, c->stream));
+    if (next) OFK_HIP(c, hipMemcpy2DAsync(next, (size_t)stride * 8, c->pts_next_u, mp * 8, n * 8, c->*s.batch, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
 }
 
@@ -844,7 +878,7 @@ static int gate_tracks(ofk_ctx *c, hipStream_t s, const View &v, const ofk_level
 // The track step of the resident chains: with ofk_set_lk_seed on, the start positions are written where LK reads them (imu_state: the
 // source k_stream_fuse uses under use_imu, NULL = the sensors only) and LK starts there;
 // with ofk_set_track_gate on, the gates follow on the same stream.  With ofk_set_camera on (the view's ideal buffers exist:
-// camera_alloc) the sensors speak of the ideal image, so the predictor runs on the ideal points and its seeds are brought back into
+// solve_points_prepare) the sensors speak of the ideal image, so the predictor runs on the ideal points and its seeds are brought back into
 // the image; behind the gates the ideal points of both sets are written for the solve stage - one launch, unless the seed needed
 // the previous points' earlier.  With ofk_set_rolling_shutter on, one k_rs_correct launch follows: it reads the raw rows and the
 // ideal points (the camera's, corrected in place, or the raw points themselves) and writes what the solve stage reads.  With
@@ -893,19 +927,10 @@ static int check_gate(ofk_ctx *c, const ofk_track_gate *g, const char *who)
 
 extern "C" int ofk_set_track_gate(ofk_ctx *c, const ofk_track_gate *g)
 {
-    if (!c) return OFK_E_INVALID;
-    if (!g) { c->gate.fb_mode = OFK_FB_OFF; c->gate.err_max = 0.0; return OFK_OK; }
-    TRY(check_gate(c, g, "ofk_set_track_gate"));
-    c->gate = *g;
-    return OFK_OK;
+    return setting_set(c, &ofk_ctx::gate, g, [](ofk_track_gate &s) { s.fb_mode = OFK_FB_OFF; s.err_max = 0.0; },       // both gates
+                       [c](const ofk_track_gate *v) { return check_gate(c, v, "ofk_set_track_gate"); });
 }
-
-extern "C" int ofk_get_track_gate(const ofk_ctx *c, ofk_track_gate *g)
-{
-    if (!c || !g) return OFK_E_INVALID;
-    *g = c->gate;
-    return OFK_OK;
-}
+extern "C" int ofk_get_track_gate(const ofk_ctx *c, ofk_track_gate *g) { return setting_get(c, &ofk_ctx::gate, g); }
 
 // the resident buffers of the gates, allocated when a run first needs them
 static int gate_alloc(ofk_ctx *c)
@@ -1057,19 +1082,10 @@ static int check_robust(ofk_ctx *c, const ofk_robust *r, const char *who)
 
 extern "C" int ofk_set_robust(ofk_ctx *c, const ofk_robust *r)
 {
-    if (!c) return OFK_E_INVALID;
-    if (!r || r->loss == OFK_ROBUST_OFF) { c->robust.loss = OFK_ROBUST_OFF; return OFK_OK; }
-    TRY(check_robust(c, r, "ofk_set_robust"));
-    c->robust = *r;
-    return OFK_OK;
+    return setting_set(c, &ofk_ctx::robust, r && r->loss == OFK_ROBUST_OFF ? nullptr : r, [](ofk_robust &s) { s.loss = OFK_ROBUST_OFF; },
+                       [c](const ofk_robust *v) { return check_robust(c, v, "ofk_set_robust"); });
 }
-
-extern "C" int ofk_get_robust(const ofk_ctx *c, ofk_robust *r)
-{
-    if (!c || !r) return OFK_E_INVALID;
-    *r = c->robust;
-    return OFK_OK;
-}
+extern "C" int ofk_get_robust(const ofk_ctx *c, ofk_robust *r) { return setting_get(c, &ofk_ctx::robust, r); }
 
 // the resident buffers of the robust solve, allocated when a run first needs them
 static int robust_alloc(ofk_ctx *c)
@@ -1099,19 +1115,10 @@ static int check_cov(ofk_ctx *c, const ofk_cov *v, const char *who)
 
 extern "C" int ofk_set_cov(ofk_ctx *c, const ofk_cov *v)
 {
-    if (!c) return OFK_E_INVALID;
-    if (!v) { c->cov.mode = OFK_COV_OFF; c->cov.filter_r = 0; return OFK_OK; }
-    TRY(check_cov(c, v, "ofk_set_cov"));
-    c->cov = *v;
-    return OFK_OK;
+    return setting_set(c, &ofk_ctx::cov, v, [](ofk_cov &s) { s.mode = OFK_COV_OFF; s.filter_r = 0; },      // filter_r needs a covariance
+                       [c](const ofk_cov *x) { return check_cov(c, x, "ofk_set_cov"); });
 }
-
-extern "C" int ofk_get_cov(const ofk_ctx *c, ofk_cov *v)
-{
-    if (!c || !v) return OFK_E_INVALID;
-    *v = c->cov;
-    return OFK_OK;
-}
+extern "C" int ofk_get_cov(const ofk_ctx *c, ofk_cov *v) { return setting_get(c, &ofk_ctx::cov, v); }
 
 // ------------------------------------------------------------------------------------------------ joint velocity and rotation setting
 static int check_joint(ofk_ctx *c, const ofk_joint *v, const char *who)
@@ -1126,19 +1133,9 @@ static int check_joint(ofk_ctx *c, const ofk_joint *v, const char *who)
 
 extern "C" int ofk_set_joint(ofk_ctx *c, const ofk_joint *v)
 {
-    if (!c) return OFK_E_INVALID;
-    if (!v) { c->joint.mode = OFK_JOINT_OFF; return OFK_OK; }
-    TRY(check_joint(c, v, "ofk_set_joint"));
-    c->joint = *v;
-    return OFK_OK;
+    return setting_set(c, &ofk_ctx::joint, v, [](ofk_joint &s) { s.mode = OFK_JOINT_OFF; }, [c](const ofk_joint *x) { return check_joint(c, x, "ofk_set_joint"); });
 }
-
-extern "C" int ofk_get_joint(const ofk_ctx *c, ofk_joint *v)
-{
-    if (!c || !v) return OFK_E_INVALID;
-    *v = c->joint;
-    return OFK_OK;
-}
+extern "C" int ofk_get_joint(const ofk_ctx *c, ofk_joint *v) { return setting_get(c, &ofk_ctx::joint, v); }
 
 // ------------------------------------------------------------------------------------------------ plane setting
 static int check_plane(ofk_ctx *c, const ofk_plane *v, const char *who)
@@ -1156,19 +1153,9 @@ static int check_plane(ofk_ctx *c, const ofk_plane *v, const char *who)
 
 extern "C" int ofk_set_plane(ofk_ctx *c, const ofk_plane *v)
 {
-    if (!c) return OFK_E_INVALID;
-    if (!v) { c->plane.mode = OFK_PLANE_OFF; return OFK_OK; }
-    TRY(check_plane(c, v, "ofk_set_plane"));
-    c->plane = *v;
-    return OFK_OK;
+    return setting_set(c, &ofk_ctx::plane, v, [](ofk_plane &s) { s.mode = OFK_PLANE_OFF; }, [c](const ofk_plane *x) { return check_plane(c, x, "ofk_set_plane"); });
 }
-
-extern "C" int ofk_get_plane(const ofk_ctx *c, ofk_plane *v)
-{
-    if (!c || !v) return OFK_E_INVALID;
-    *v = c->plane;
-    return OFK_OK;
-}
+extern "C" int ofk_get_plane(const ofk_ctx *c, ofk_plane *v) { return setting_get(c, &ofk_ctx::plane, v); }
 
 // ------------------------------------------------------------------------------------------------ epipolar setting
 static int check_epipolar(ofk_ctx *c, const ofk_epipolar *v, const char *who)
@@ -1187,24 +1174,13 @@ static int check_epipolar(ofk_ctx *c, const ofk_epipolar *v, const char *who)
 
 extern "C" int ofk_set_epipolar(ofk_ctx *c, const ofk_epipolar *v)
 {
-    if (!c) return OFK_E_INVALID;
-    if (!v) { c->epi.mode = OFK_EPI_OFF; return OFK_OK; }
-    TRY(check_epipolar(c, v, "ofk_set_epipolar"));
-    c->epi = *v;
-    return OFK_OK;
+    return setting_set(c, &ofk_ctx::epi, v, [](ofk_epipolar &s) { s.mode = OFK_EPI_OFF; }, [c](const ofk_epipolar *x) { return check_epipolar(c, x, "ofk_set_epipolar"); });
 }
-
-extern "C" int ofk_get_epipolar(const ofk_ctx *c, ofk_epipolar *v)
-{
-    if (!c || !v) return OFK_E_INVALID;
-    *v = c->epi;
-    return OFK_OK;
-}
+extern "C" int ofk_get_epipolar(const ofk_ctx *c, ofk_epipolar *v) { return setting_get(c, &ofk_ctx::epi, v); }
 
 // ------------------------------------------------------------------------------------------------ the second-stage settings
 // One row per setting whose kernel runs behind the velocity solve, in the order of their checks and launches.  No two run together:
 // a row refuses every earlier row that is on.
-enum { NO_OFMODULE = 1, NO_ROTATIONAL = 2, NO_LEGACY = 4 };
 struct second_setting {
     const char *set, *what;                                     // the setter's name, what the kernel adds
     int (*mode)(const ofk_ctx *);                               // 0: off
@@ -1250,18 +1226,12 @@ static bool second_on(const ofk_ctx *c)
 // The runs' and steps' own refusals with a setting on (ofk.h), row by row; allocates the rows on first use.  fu: a fused step's.
 static int second_prepare(ofk_ctx *c, int B, int variant, const ofk_fusion *fu, const char *who)
 {
-    static const char *const names[3] = {"OFK_SOLVE_OFMODULE", "OFK_FLOW_ROTATIONAL", "OFK_KEEP_LEGACY"};
     const int has = !fu ? 0 : (variant == OFK_SOLVE_OFMODULE ? NO_OFMODULE : 0) | (fu->flow == OFK_FLOW_ROTATIONAL ? NO_ROTATIONAL : 0) |
                                   (fu->keep == OFK_KEEP_LEGACY ? NO_LEGACY : 0);
     const second_setting *first = nullptr;                      // the row that is on already
     for (const second_setting &s : SECOND) {
         if (!s.mode(c)) continue;
-        if (has & s.fused_refuse) {
-            char list[64] = "";
-            for (int k = 0; k < 3; ++k)
-                if (s.fused_refuse >> k & 1) { if (list[0]) strcat(list, " / "); strcat(list, names[k]); }
-            return ofk_fail(c, OFK_E_INVALID, "%s: %s are not the sensor model: no %s (%s is on)", who, list, s.what, s.set);
-        }
+        if (has & s.fused_refuse) return refuse_not_sensor_model(c, who, s.fused_refuse, s.what, s.set);
         if (first) return ofk_fail(c, OFK_E_INVALID, s.beside, who, first->set);
         if (s.ofmodule_late && variant == OFK_SOLVE_OFMODULE)
             return ofk_fail(c, OFK_E_INVALID, "%s: OFK_SOLVE_OFMODULE is not the sensor model: no %s (%s is on)", who, s.what, s.set);
@@ -1984,8 +1954,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
     TRY(second_prepare(c, B, p->solve_variant, nullptr, "ofk_pairs_run"));
-    TRY(camera_prepare(c, B));
-    const bool cam = camera_on(c) || rs_on(c) || fm_on(c);       // the solve stage reads the ideal / corrected / rewritten points
+    TRY(solve_points_prepare(c, B));
     TRY(need_streams(c, S, overlap));
     if (fork) {
         OFK_HIP(c, hipEventRecord(c->ev_fork, c->stream));
@@ -2037,8 +2006,7 @@ extern "C" int ofk_pairs_run(ofk_ctx *c, const ofk_params *p)
         if (c->x_pending) OFK_HIP(c, hipStreamWaitEvent(st, c->ev_x, 0));    // the previous call's records are still being exported
         {
             StageTimer t(c, OFK_STAGE_SOLVE, st);
-            solve_pairs(c, st, cam ? v.pts_prev_u : v.pts_prev, cam ? v.pts_next_u : v.pts_next, v.status, v.counts, v.sensors, p, v.cand_count,
-                        v.records, b0, nb, false);
+            solve_pairs(c, st, v.solve_prev, v.solve_next, v.status, v.counts, v.sensors, p, v.cand_count, v.records, b0, nb, false);
         }
         if (S > 1) OFK_HIP(c, hipEventRecord(c->ev_end[k], st));             // joined lazily (join_slices), not here
     }
@@ -2102,8 +2070,7 @@ static int camera_points(ofk_ctx *c, const char *who, int distort, const ofk_cam
     if (!c) return OFK_E_INVALID;
     if (!m || !pts || !counts || !out || batch < 1 || stride < 1) return ofk_fail(c, OFK_E_INVALID, "%s: bad argument", who);
     TRY(check_camera(c, m, false, who));
-    for (int b = 0; b < batch; ++b)
-        if (counts[b] < 0 || counts[b] > stride) return ofk_fail(c, OFK_E_INVALID, "%s: counts[%d]=%d outside 0..%d", who, b, counts[b], stride);
+    TRY(check_counts(c, who, counts, batch, stride));
     const size_t pb = (size_t)batch * stride * 8;
     Bump bp;
     TRY(est_begin(c, 2 * pb + (size_t)batch * 4, bp));
@@ -2128,96 +2095,73 @@ extern "C" int ofk_distort_points(ofk_ctx *c, const ofk_camera *m, const float *
 
 extern "C" int ofk_camera_download(ofk_ctx *c, float *prev_ideal, float *next_ideal, int stride)
 {
-    if (!c) return OFK_E_INVALID;
-    if (c->cam_batch < 1 || !c->pts_prev_u) return ofk_fail(c, OFK_E_INVALID, "ofk_camera_download: no run or step with ofk_set_camera on yet");
-    if (stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_camera_download: stride %d", stride);
-    TRY(enter(c));
-    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
-    if (prev_ideal) OFK_HIP(c, hipMemcpy2DAsync(prev_ideal, (size_t)stride * 8, c->pts_prev_u, mp * 8, n * 8, c->cam_batch, hipMemcpyDeviceToHost, c->stream));
-    if (next_ideal) OFK_HIP(c, hipMemcpy2DAsync(next_ideal, (size_t)stride * 8, c->pts_next_u, mp * 8, n * 8, c->cam_batch, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
+    return points_download(c, POINTS[POINTS_CAMERA], "ofk_camera_download", prev_ideal, next_ideal, stride);
 }
 
-// ------------------------------------------------------------------------------------------------ rolling-shutter stage entries
-// device scratch only, so resident points and settings are not touched; the outputs go up first: entries beyond counts[b] keep their contents
+// ------------------------------------------------------------------------------------------------ rolling-shutter and finite-motion stage entries
+// Both ends of every point through one launch.  Device scratch only, so resident points and settings are not touched; the outputs go
+// up first: entries beyond counts[b] keep their contents.  have: the setting's struct is there; id0 / id1: optional, both or neither;
+// rules(): the setting's check and its rule on the sensors; launch(in0, in1, id0, id1, out0, out1, counts, sensors) on device arrays.
+template <class Rules, class Launch>
+static int correct_points(ofk_ctx *c, const char *who, bool have, const float *in0, const float *in1, const float *id0, const float *id1,
+                          const int *counts, int batch, int stride, const double *sensors, float *out0, float *out1, Rules rules, Launch launch)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!have || !in0 || !in1 || !counts || !out0 || !out1 || batch < 1 || stride < 1 || !id0 != !id1) return ofk_fail(c, OFK_E_INVALID, "%s: bad argument", who);
+    TRY(rules());
+    TRY(check_counts(c, who, counts, batch, stride));
+    const size_t pb = (size_t)batch * stride * 8, sb = (size_t)batch * OFK_SENSOR_DOUBLES * 8;
+    Bump bp;
+    TRY(est_begin(c, (id0 ? 6 : 4) * pb + sb + (size_t)batch * 4, bp));
+    const float *d0 = (const float *)bp.put(in0, pb), *d1 = (const float *)bp.put(in1, pb);
+    const float *di0 = (const float *)bp.put(id0, pb), *di1 = (const float *)bp.put(id1, pb);                    // NULL stays NULL
+    float *do0 = (float *)bp.put(out0, pb), *do1 = (float *)bp.put(out1, pb);
+    const double *dsn = bp.put(sensors, sb);
+    const int *dc = (const int *)bp.put(counts, (size_t)batch * 4);
+    if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    launch(d0, d1, di0, di1, do0, do1, dc, dsn);
+    TRY(check_launch(c, who));
+    OFK_HIP(c, hipMemcpyAsync(out0, do0, pb, hipMemcpyDeviceToHost, c->stream));
+    return get(c, out1, do1, pb);
+}
+
 extern "C" int ofk_rs_correct_points(ofk_ctx *c, const ofk_rshutter *r, const float *raw_prev, const float *raw_next, const float *ideal_prev,
                                      const float *ideal_next, const int *counts, int batch, int stride, const double *sensors, float *out_prev,
                                      float *out_next)
 {
     const char *who = "ofk_rs_correct_points";
-    if (!c) return OFK_E_INVALID;
-    if (!r || !raw_prev || !raw_next || !counts || !out_prev || !out_next || batch < 1 || stride < 1 || !ideal_prev != !ideal_next)
-        return ofk_fail(c, OFK_E_INVALID, "%s: bad argument", who);
-    TRY(check_rs(c, r, true, who));
-    if (r->mode == OFK_RS_GYRO && !sensors) return ofk_fail(c, OFK_E_INVALID, "%s: OFK_RS_GYRO needs the sensors", who);
-    for (int b = 0; b < batch; ++b)
-        if (counts[b] < 0 || counts[b] > stride) return ofk_fail(c, OFK_E_INVALID, "%s: counts[%d]=%d outside 0..%d", who, b, counts[b], stride);
-    const size_t pb = (size_t)batch * stride * 8, sb = (size_t)batch * OFK_SENSOR_DOUBLES * 8;
-    Bump bp;
-    TRY(est_begin(c, 6 * pb + sb + (size_t)batch * 4, bp));
-    const float *dr0 = (const float *)bp.put(raw_prev, pb), *dr1 = (const float *)bp.put(raw_next, pb);
-    const float *di0 = (const float *)bp.put(ideal_prev, pb), *di1 = (const float *)bp.put(ideal_next, pb);      // NULL stays NULL
-    float *do0 = (float *)bp.put(out_prev, pb), *do1 = (float *)bp.put(out_next, pb);
-    const double *dsn = bp.put(sensors, sb);
-    const int *dc = (const int *)bp.put(counts, (size_t)batch * 4);
-    if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
-    ofk_launch_rs_correct(c->stream, r, dr0, dr1, di0, di1, do0, do1, dc, stride, dsn, nullptr, batch);
-    TRY(check_launch(c, who));
-    OFK_HIP(c, hipMemcpyAsync(out_prev, do0, pb, hipMemcpyDeviceToHost, c->stream));
-    return get(c, out_next, do1, pb);
+    return correct_points(c, who, r != nullptr, raw_prev, raw_next, ideal_prev, ideal_next, counts, batch, stride, sensors, out_prev, out_next,
+        [&] {
+            TRY(check_rs(c, r, true, who));
+            return r->mode == OFK_RS_GYRO && !sensors ? ofk_fail(c, OFK_E_INVALID, "%s: OFK_RS_GYRO needs the sensors", who) : OFK_OK;
+        },
+        [&](const float *d0, const float *d1, const float *di0, const float *di1, float *do0, float *do1, const int *dc, const double *dsn) {
+            ofk_launch_rs_correct(c->stream, r, d0, d1, di0, di1, do0, do1, dc, stride, dsn, nullptr, batch);
+        });
 }
 
 extern "C" int ofk_rs_download(ofk_ctx *c, float *prev, float *next, int stride)
 {
-    if (!c) return OFK_E_INVALID;
-    if (c->rs_batch < 1 || !c->pts_prev_u) return ofk_fail(c, OFK_E_INVALID, "ofk_rs_download: no run or step with ofk_set_rolling_shutter on yet");
-    if (stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_rs_download: stride %d", stride);
-    TRY(enter(c));
-    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
-    if (prev) OFK_HIP(c, hipMemcpy2DAsync(prev, (size_t)stride * 8, c->pts_prev_u, mp * 8, n * 8, c->rs_batch, hipMemcpyDeviceToHost, c->stream));
-    if (next) OFK_HIP(c, hipMemcpy2DAsync(next, (size_t)stride * 8, c->pts_next_u, mp * 8, n * 8, c->rs_batch, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
+    return points_download(c, POINTS[POINTS_RS], "ofk_rs_download", prev, next, stride);
 }
 
-// ------------------------------------------------------------------------------------------------ finite-motion stage entries
-// device scratch only, so resident points and settings are not touched; the outputs go up first: entries beyond counts[b] keep their contents
 extern "C" int ofk_finite_correct_points(ofk_ctx *c, const ofk_finite_motion *f, const float *prev, const float *next, const int *counts, int batch,
                                          int stride, const double *sensors, float *out_prev, float *out_next)
 {
     const char *who = "ofk_finite_correct_points";
-    if (!c) return OFK_E_INVALID;
-    if (!f || !prev || !next || !counts || !out_prev || !out_next || batch < 1 || stride < 1) return ofk_fail(c, OFK_E_INVALID, "%s: bad argument", who);
-    TRY(check_fm(c, f, who));
-    if (!sensors) return ofk_fail(c, OFK_E_INVALID, "%s: the rewrite needs the sensors", who);
-    for (int b = 0; b < batch; ++b)
-        if (counts[b] < 0 || counts[b] > stride) return ofk_fail(c, OFK_E_INVALID, "%s: counts[%d]=%d outside 0..%d", who, b, counts[b], stride);
-    const size_t pb = (size_t)batch * stride * 8, sb = (size_t)batch * OFK_SENSOR_DOUBLES * 8;
-    Bump bp;
-    TRY(est_begin(c, 4 * pb + sb + (size_t)batch * 4, bp));
-    const float *di0 = (const float *)bp.put(prev, pb), *di1 = (const float *)bp.put(next, pb);
-    float *do0 = (float *)bp.put(out_prev, pb), *do1 = (float *)bp.put(out_next, pb);
-    const double *dsn = bp.put(sensors, sb);
-    const int *dc = (const int *)bp.put(counts, (size_t)batch * 4);
-    if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
-    ofk_launch_finite_correct(c->stream, f, di0, di1, do0, do1, dc, stride, dsn, nullptr, batch);
-    TRY(check_launch(c, who));
-    OFK_HIP(c, hipMemcpyAsync(out_prev, do0, pb, hipMemcpyDeviceToHost, c->stream));
-    return get(c, out_next, do1, pb);
+    return correct_points(c, who, f != nullptr, prev, next, nullptr, nullptr, counts, batch, stride, sensors, out_prev, out_next,
+        [&] {
+            TRY(check_fm(c, f, who));
+            return !sensors ? ofk_fail(c, OFK_E_INVALID, "%s: the rewrite needs the sensors", who) : OFK_OK;
+        },
+        [&](const float *d0, const float *d1, const float *, const float *, float *do0, float *do1, const int *dc, const double *dsn) {
+            ofk_launch_finite_correct(c->stream, f, d0, d1, do0, do1, dc, stride, dsn, nullptr, batch);
+        });
 }
 
 extern "C" int ofk_finite_download(ofk_ctx *c, float *prev, float *next, int stride)
 {
-    if (!c) return OFK_E_INVALID;
-    if (c->fm_batch < 1 || !c->pts_prev_u) return ofk_fail(c, OFK_E_INVALID, "ofk_finite_download: no run or step with ofk_set_finite_motion on yet");
-    if (stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_finite_download: stride %d", stride);
-    TRY(enter(c));
-    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
-    if (prev) OFK_HIP(c, hipMemcpy2DAsync(prev, (size_t)stride * 8, c->pts_prev_u, mp * 8, n * 8, c->fm_batch, hipMemcpyDeviceToHost, c->stream));
-    if (next) OFK_HIP(c, hipMemcpy2DAsync(next, (size_t)stride * 8, c->pts_next_u, mp * 8, n * 8, c->fm_batch, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
+    return points_download(c, POINTS[POINTS_FM], "ofk_finite_download", prev, next, stride);
 }
 
 // ------------------------------------------------------------------------------------------------ exclusion zones
@@ -2235,20 +2179,10 @@ static int check_zones(ofk_ctx *c, const ofk_zones *z, const char *who)
 
 extern "C" int ofk_set_zones(ofk_ctx *c, const ofk_zones *z)
 {
-    if (!c) return OFK_E_INVALID;
-    if (!z) { c->zones.mode = OFK_ZONES_OFF; return OFK_OK; }
-    TRY(check_zones(c, z, "ofk_set_zones"));
-    if (z->mode == OFK_ZONES_OFF) { c->zones.mode = OFK_ZONES_OFF; return OFK_OK; }
-    c->zones = *z;
-    return OFK_OK;
+    return setting_set(c, &ofk_ctx::zones, z && z->mode == OFK_ZONES_OFF ? nullptr : z, [](ofk_zones &s) { s.mode = OFK_ZONES_OFF; },
+                       [c](const ofk_zones *v) { return check_zones(c, v, "ofk_set_zones"); });
 }
-
-extern "C" int ofk_get_zones(const ofk_ctx *c, ofk_zones *z)
-{
-    if (!c || !z) return OFK_E_INVALID;
-    *z = c->zones;
-    return OFK_OK;
-}
+extern "C" int ofk_get_zones(const ofk_ctx *c, ofk_zones *z) { return setting_get(c, &ofk_ctx::zones, z); }
 
 // bytes of the tables, the motion rows and the statistics of `batch` streams (each kind lies back to back)
 static size_t zones_tab_bytes(int batch) { return (size_t)batch * OFK_ZONE_MAX * OFK_ZONE_INTS * 4; }
@@ -2540,9 +2474,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     if (gate_on(c->gate)) { TRY(gate_alloc(c)); c->gate_batch = B; c->gate_fb = c->gate.fb_mode != OFK_FB_OFF; }
     const bool zones_on = c->zones.mode != OFK_ZONES_OFF;
     if (zones_on) { TRY(check_zones(c, &c->zones, "ofk_stream_step")); TRY(zones_alloc(c)); }
-    TRY(camera_prepare(c, B));
-    const bool cam = camera_on(c) || rs_on(c) || fm_on(c);       // the solve stage reads the ideal / corrected / rewritten points; the tracks, the zones and the
-    const float *sp = cam ? c->pts_prev_u : c->pts_prev, *sn = cam ? c->pts_next_u : c->pts_next;   // re-detection stay in the image
+    TRY(solve_points_prepare(c, B));
     OFK_HIP(c, hipMemcpyAsync(c->sensors, sensors, (size_t)B * OFK_SENSOR_DOUBLES * 8, hipMemcpyHostToDevice, c->stream));
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
@@ -2559,12 +2491,13 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     }
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)
-    TRY(track(c, c->stream, view_of(c, 0, B, 0), lv, p, fu && fu->use_imu ? c->imu_state : nullptr));
+    const View v = view_of(c, 0, B, 0);                          // the solve stage reads v.solve_*; the tracks, the zones and the re-detection stay in the image
+    TRY(track(c, c->stream, v, lv, p, fu && fu->use_imu ? c->imu_state : nullptr));
     if (zones_on)                                                // the solve stage turns the status into its keep flags: rule 1 needs both
         OFK_HIP(c, hipMemcpyAsync(c->zone_status, c->status, (size_t)B * c->max_pts, hipMemcpyDeviceToDevice, c->stream));
     if (fu) {
         const bool rob = c->robust.loss != OFK_ROBUST_OFF;
-        const ofk_stream_in in = {sp, sn, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats,
+        const ofk_stream_in in = {v.solve_prev, v.solve_next, c->status, c->counts, c->max_pts, c->sensors, c->imu_state, c->kf_ns, c->kf_nm, c->kf_nc, c->kf_mats,
                                   c->kf_x, c->kf_P, fu, p->solve_variant, c->records, c->fused, B, defer};
         if (rob)
             ofk_launch_stream_fuse_robust(c->stream, in, c->imu_dv, p->use_feasibility, p->feas_T, &c->robust, c->rob_work, c->rob_w, c->rob_wtmp,
@@ -2573,7 +2506,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
             ofk_launch_stream_fuse(c->stream, in, c->imu_dv, p->use_feasibility, p->feas_T);
         for (const second_setting &s : SECOND) if (s.mode(c)) s.stream(c, in, rob ? c->rob_w : nullptr);
     } else
-        solve_pairs(c, c->stream, sp, sn, c->status, c->counts, c->sensors, p, nullptr, c->records, 0, B, true);
+        solve_pairs(c, c->stream, v.solve_prev, v.solve_next, c->status, c->counts, c->sensors, p, nullptr, c->records, 0, B, true);
     // re-detection for the streams that had few features (node:157-166): mask = discs around the OLD positions, image = OLD frame.
     // The host knows the track counts from the previous call, so the whole branch is skipped when no stream needs it.
     // of_module.py:138 `continue`: a step of the ONE stream that did not solve leaves old_gray / old_pos as they were.  The host has to

@@ -4,6 +4,7 @@ This is the only place the package touches native code.  There is no CPU fallbac
 shared library is missing or no gfx950 device is usable, importing succeeds (so that
 CPU-only tooling can inspect the package) but the first call raises OfkError.
 """
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -372,6 +373,10 @@ class Fusion(C.Structure):
                 ("min_solve", C.c_int), ("hold_on_skip", C.c_int)]
 
 
+# the struct settings: ofk_set_<name> / ofk_get_<name> take the context and a pointer to the struct
+SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate),
+            ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion))
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -416,6 +421,8 @@ def load_library():
         L = C.CDLL(LIB_PATH)
         vp, i, d = C.c_void_p, C.c_int, C.c_double
         L.ofk_version.restype = i
+        for name, cls in SETTINGS:
+            getattr(L, "ofk_set_" + name).argtypes = getattr(L, "ofk_get_" + name).argtypes = [vp, C.POINTER(cls)]
         L.ofk_last_error.restype = C.c_char_p; L.ofk_last_error.argtypes = [vp]
         L.ofk_device_count.restype = i
         L.ofk_create.argtypes = [i, i, i, i, i, i, C.POINTER(vp)]
@@ -434,39 +441,28 @@ def load_library():
         L.ofk_flow_model.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp, vp]
         L.ofk_feasibility.argtypes = [vp, i, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp]
         L.ofk_velocity_solve.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp]
-        L.ofk_set_robust.argtypes = [vp, C.POINTER(Robust)]; L.ofk_get_robust.argtypes = [vp, C.POINTER(Robust)]
         L.ofk_robust_download.argtypes = [vp, vp, i, vp]
         L.ofk_velocity_solve_robust.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), vp, vp, vp]
         L.ofk_robust_pairs.argtypes = [C.c_ulonglong, C.c_uint, i, i, vp, vp]
-        L.ofk_set_cov.argtypes = [vp, C.POINTER(Cov)]; L.ofk_get_cov.argtypes = [vp, C.POINTER(Cov)]
         L.ofk_cov_download.argtypes = [vp, vp]
-        L.ofk_set_joint.argtypes = [vp, C.POINTER(Joint)]; L.ofk_get_joint.argtypes = [vp, C.POINTER(Joint)]
         L.ofk_joint_download.argtypes = [vp, vp]
         L.ofk_velocity_solve_joint.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Joint), vp, vp]
         L.ofk_velocity_solve_cov.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Cov), vp, vp]
-        L.ofk_set_plane.argtypes = [vp, C.POINTER(Plane)]; L.ofk_get_plane.argtypes = [vp, C.POINTER(Plane)]
         L.ofk_plane_download.argtypes = [vp, vp]
         L.ofk_velocity_solve_plane.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Plane), vp, vp]
-        L.ofk_set_epipolar.argtypes = [vp, C.POINTER(Epipolar)]; L.ofk_get_epipolar.argtypes = [vp, C.POINTER(Epipolar)]
         L.ofk_epipolar_download.argtypes = [vp, vp]; L.ofk_epipolar_points_download.argtypes = [vp, vp]
         L.ofk_velocity_solve_epipolar.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Epipolar), vp, vp, vp]
-        L.ofk_set_track_gate.argtypes = [vp, C.POINTER(TrackGate)]; L.ofk_get_track_gate.argtypes = [vp, C.POINTER(TrackGate)]
         L.ofk_track_gate_download.argtypes = [vp, vp, vp, vp, i, vp]
-        L.ofk_set_corner_grid.argtypes = [vp, C.POINTER(CornerGrid)]; L.ofk_get_corner_grid.argtypes = [vp, C.POINTER(CornerGrid)]
         L.ofk_corner_grid_download.argtypes = [vp, vp]
         L.ofk_select_corners_grid.argtypes = [vp, vp, vp, i, i, i, i, d, d, vp, vp, C.POINTER(CornerGrid), vp, vp, i]
         L.ofk_good_features_grid.argtypes = [vp, vp, vp, i, i, i, i, d, d, i, vp, vp, C.POINTER(CornerGrid), vp, vp, i]
-        L.ofk_set_zones.argtypes = [vp, C.POINTER(Zones)]; L.ofk_get_zones.argtypes = [vp, C.POINTER(Zones)]
         L.ofk_zones_step.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, vp, vp]
         L.ofk_zones_reset.argtypes = [vp, i]; L.ofk_zones_download.argtypes = [vp, vp, vp, vp]
-        L.ofk_set_camera.argtypes = [vp, C.POINTER(Camera)]; L.ofk_get_camera.argtypes = [vp, C.POINTER(Camera)]
         L.ofk_undistort_points.argtypes = [vp, C.POINTER(Camera), vp, vp, i, i, vp]
         L.ofk_distort_points.argtypes = [vp, C.POINTER(Camera), vp, vp, i, i, vp]
         L.ofk_camera_download.argtypes = [vp, vp, vp, i]
-        L.ofk_set_rolling_shutter.argtypes = [vp, C.POINTER(RShutter)]; L.ofk_get_rolling_shutter.argtypes = [vp, C.POINTER(RShutter)]
         L.ofk_rs_correct_points.argtypes = [vp, C.POINTER(RShutter), vp, vp, vp, vp, vp, i, i, vp, vp, vp]
         L.ofk_rs_download.argtypes = [vp, vp, vp, i]
-        L.ofk_set_finite_motion.argtypes = [vp, C.POINTER(FiniteMotion)]; L.ofk_get_finite_motion.argtypes = [vp, C.POINTER(FiniteMotion)]
         L.ofk_finite_correct_points.argtypes = [vp, C.POINTER(FiniteMotion), vp, vp, vp, i, i, vp, vp, vp]
         L.ofk_finite_download.argtypes = [vp, vp, vp, i]
         L.ofk_lk_pyr_fb.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, i, vp, vp, vp, C.POINTER(TrackGate), vp, vp, vp]
@@ -537,6 +533,23 @@ def _opt(a, dtype, shape):
     return None if a is None else _arr(a, dtype, shape)
 
 
+def _point_arrays(arrays, counts, sensors, out, message):
+    """What the point stage entries do with their arguments.  arrays: the inputs, [B,S,2] (or [S,2]: one image) f32 of one shape,
+    message(*shapes) the ValueError text otherwise; counts [B] or None = every point; sensors [B,28] or None; out: per output an
+    array to start from (copied) or None = zeros.  -> (single, inputs [B,S,2], counts, sensors, outputs [B,S,2])."""
+    a = [_arr(x, np.float32) for x in arrays]
+    single = a[0].ndim == 2
+    if single:
+        a = [x[None] for x in a]
+    if a[0].ndim != 3 or a[0].shape[2] != 2 or any(x.shape != a[0].shape for x in a[1:]):
+        raise ValueError(message(*[x.shape for x in a]))
+    B, S = a[0].shape[:2]
+    counts = _arr(S if counts is None else counts, np.int32, (B,))
+    sensors = _opt(sensors, np.float64, (B, SENSOR_DOUBLES))
+    outs = [np.zeros((B, S, 2), np.float32) if o is None else np.array(o, np.float32).reshape(B, S, 2) for o in out]
+    return single, a, counts, sensors, outs
+
+
 class Context:
     """One device + one HIP stream + all device buffers.  Calls are serialised by an internal lock
     (the C library is not thread-safe; rospy invokes callbacks from several threads)."""
@@ -576,6 +589,33 @@ class Context:
     def sync(self):
         with self._lock:
             self._ck(self._L.ofk_sync(self._h))
+
+    def _set_struct(self, fn, value, settings, maker, lock):
+        """ofk_set_*: the struct `value`, or maker(**settings), or without either NULL (off); lock: whether the call takes self._lock."""
+        v = value if value is not None or not settings else maker(**settings)
+        with self._lock if lock else contextlib.nullcontext():
+            self._ck(fn(self._h, C.byref(v) if v is not None else None))
+
+    def _get_struct(self, fn, cls):
+        v = cls()
+        self._ck(fn(self._h, C.byref(v)))
+        return v
+
+    def _rows(self, who, batch, call, *specs):
+        """A download whose rows the library writes for the latest run, whatever `batch` says: zeroed [max_batch, *shape] buffers for
+        specs = (shape, dtype), call(*pointers) under the lock, the first `batch` rows of each.  who: names the ValueError for a
+        batch outside 0..max_batch (None: not checked)."""
+        if who is not None and not 0 <= int(batch) <= self.max_batch:
+            raise ValueError(f"{who}: batch {batch} outside 0..{self.max_batch}")
+        bufs = [np.zeros((self.max_batch,) + tuple(shape), dtype) for shape, dtype in specs]
+        with self._lock:
+            self._ck(call(*[_p(b) for b in bufs]))
+        return [b[:batch].copy() for b in bufs]
+
+    def _points_download(self, fn, batch):
+        """ofk_camera_download / ofk_rs_download / ofk_finite_download: (prev, next) [batch,max_pts,2] f32."""
+        spec = ((self.max_pts, 2), np.float32)
+        return tuple(self._rows(fn[4:], batch, lambda a, b: getattr(self._L, fn)(self._h, a, b, self.max_pts), spec, spec))
 
     # ------------------------------------------------------------------ image stages
     @staticmethod
@@ -777,48 +817,32 @@ class Context:
     def set_track_gate(self, gate=None, **settings):
         """ofk_set_track_gate: a TrackGate (or track_gate_setting's keywords); None switches both gates off.  Every later pairs_run
         and stream step clears the status of the points the gates reject, behind LK and in front of the solve."""
-        g = gate if gate is not None or not settings else track_gate_setting(**settings)
-        self._ck(self._L.ofk_set_track_gate(self._h, C.byref(g) if g is not None else None))
+        self._set_struct(self._L.ofk_set_track_gate, gate, settings, track_gate_setting, lock=False)
 
     def get_track_gate(self):
-        g = TrackGate()
-        self._ck(self._L.ofk_get_track_gate(self._h, C.byref(g)))
-        return g
+        return self._get_struct(self._L.ofk_get_track_gate, TrackGate)
 
     def set_corner_grid(self, grid=None, **settings):
         """ofk_set_corner_grid: a CornerGrid (or corner_grid_setting's keywords); None switches the grid off.  Every later corner
         selection of the context (good_features, select_corners, pairs_run, stream begin and re-detection) caps the corners per cell."""
-        g = grid if grid is not None or not settings else corner_grid_setting(**settings)
-        with self._lock:
-            self._ck(self._L.ofk_set_corner_grid(self._h, C.byref(g) if g is not None else None))
+        self._set_struct(self._L.ofk_set_corner_grid, grid, settings, corner_grid_setting, lock=True)
 
     def get_corner_grid(self):
-        g = CornerGrid()
-        self._ck(self._L.ofk_get_corner_grid(self._h, C.byref(g)))
-        return g
+        return self._get_struct(self._L.ofk_get_corner_grid, CornerGrid)
 
     def corner_grid_stats(self, batch):
         """ofk_corner_grid_download: [batch,2] int32 = (corners accepted, candidates examined) per image of the latest selection with
         a grid on.  The library writes that selection's rows, so the buffer has max_batch of them and the first `batch` are returned."""
-        if not 0 <= int(batch) <= self.max_batch:
-            raise ValueError(f"corner_grid_stats: batch {batch} outside 0..{self.max_batch}")
-        st = np.zeros((self.max_batch, 2), np.int32)
-        with self._lock:
-            self._ck(self._L.ofk_corner_grid_download(self._h, _p(st)))
-        return st[:batch].copy()
+        return self._rows("corner_grid_stats", batch, lambda st: self._L.ofk_corner_grid_download(self._h, st), ((2,), np.int32))[0]
 
     def set_zones(self, zones=None, **settings):
         """ofk_set_zones: a Zones (or zones_setting's keywords); None or mode "off" switches the feature off.  Every later stream
         step feeds the points its solve stage rejected into the stream's zone table and keeps its re-detection out of the zones;
         pairs_run ignores the setting."""
-        z = zones if zones is not None or not settings else zones_setting(**settings)
-        with self._lock:
-            self._ck(self._L.ofk_set_zones(self._h, C.byref(z) if z is not None else None))
+        self._set_struct(self._L.ofk_set_zones, zones, settings, zones_setting, lock=True)
 
     def get_zones(self):
-        z = Zones()
-        self._ck(self._L.ofk_get_zones(self._h, C.byref(z)))
-        return z
+        return self._get_struct(self._L.ofk_get_zones, Zones)
 
     def zones_reset(self, batch=None):
         """ofk_zones_reset: the zone tables of the first `batch` streams (all by default) are cleared."""
@@ -829,14 +853,10 @@ class Context:
         """ofk_zones_download -> dict(zones [batch,16,67] i32: ttl (0 = free), vertices, members, 32 x (x, y); motion [batch,16,4] f32:
         off x, y, flow x, y; stats [batch,8] i32 of the latest step: live, inserted, refreshed, evicted, rejects, absorbed, label
         sweeps, a reserved 0).  The library writes all max_batch streams; the first `batch` are returned."""
-        B = self.max_batch
-        batch = B if batch is None else int(batch)
-        if not 0 <= batch <= B:
-            raise ValueError(f"zones_download: batch {batch} outside 0..{B}")
-        zn = np.zeros((B, ZONE_MAX, ZONE_INTS), np.int32); mo = np.zeros((B, ZONE_MAX, ZONE_FLOATS), np.float32); st = np.zeros((B, ZONE_STATS), np.int32)
-        with self._lock:
-            self._ck(self._L.ofk_zones_download(self._h, _p(zn), _p(mo), _p(st)))
-        return dict(zones=zn[:batch].copy(), motion=mo[:batch].copy(), stats=st[:batch].copy())
+        zn, mo, st = self._rows("zones_download", self.max_batch if batch is None else int(batch),
+                                lambda *p: self._L.ofk_zones_download(self._h, *p),
+                                ((ZONE_MAX, ZONE_INTS), np.int32), ((ZONE_MAX, ZONE_FLOATS), np.float32), ((ZONE_STATS,), np.int32))
+        return dict(zones=zn, motion=mo, stats=st)
 
     def zones_step(self, old_pts, new_pts, status, keep, counts, h, w, mask=None):
         """ofk_zones_step, the stage entry: one step of the zone rules on host arrays (old_pts / new_pts [B,S,2] f32, status / keep
@@ -860,25 +880,14 @@ class Context:
         """ofk_set_camera: a Camera (or camera_setting's keywords); None or model "off" switches it off.  Every later pairs_run and
         stream step hands its solve stage the ideal pixels of the tracked points; everything in the image keeps the raw ones.  The
         caller keeps the sensors' scaling, cx, cy at 1 / fo_x, co_x, co_y."""
-        m = camera if camera is not None or not settings else camera_setting(**settings)
-        with self._lock:
-            self._ck(self._L.ofk_set_camera(self._h, C.byref(m) if m is not None else None))
+        self._set_struct(self._L.ofk_set_camera, camera, settings, camera_setting, lock=True)
 
     def get_camera(self):
-        m = Camera()
-        self._ck(self._L.ofk_get_camera(self._h, C.byref(m)))
-        return m
+        return self._get_struct(self._L.ofk_get_camera, Camera)
 
     def _camera_points(self, fn, camera, pts, counts, out):
-        pp = _arr(pts, np.float32)
-        single = pp.ndim == 2
-        if single:
-            pp = pp[None]
-        if pp.ndim != 3 or pp.shape[2] != 2:
-            raise ValueError(f"{fn}: pts {pp.shape} is not [B, S, 2]")
+        single, (pp,), counts, _, (res,) = _point_arrays([pts], counts, None, [out], lambda shape: f"{fn}: pts {shape} is not [B, S, 2]")
         B, S = pp.shape[:2]
-        counts = _arr(S if counts is None else counts, np.int32, (B,))
-        res = np.zeros((B, S, 2), np.float32) if out is None else np.array(out, np.float32).reshape(B, S, 2)
         if S > 0:
             with self._lock:
                 self._ck(getattr(self._L, fn)(self._h, C.byref(camera), _p(pp), _p(counts), B, S, _p(res)))
@@ -896,48 +905,30 @@ class Context:
     def camera_download(self, batch):
         """ofk_camera_download: (prev_ideal, next_ideal) [batch,max_pts,2] f32, the ideal points the solve stage of the latest run or
         step with the camera on saw.  The library writes that run's rows, so the buffers have max_batch of them."""
-        if not 0 <= int(batch) <= self.max_batch:
-            raise ValueError(f"camera_download: batch {batch} outside 0..{self.max_batch}")
-        a = np.zeros((self.max_batch, self.max_pts, 2), np.float32); b = np.zeros_like(a)
-        with self._lock:
-            self._ck(self._L.ofk_camera_download(self._h, _p(a), _p(b), self.max_pts))
-        return a[:batch].copy(), b[:batch].copy()
+        return self._points_download("ofk_camera_download", batch)
 
     def set_rolling_shutter(self, rshutter=None, **settings):
         """ofk_set_rolling_shutter: an RShutter (or rshutter_setting's keywords); None or mode "off" switches it off.  Every later
         pairs_run and stream step hands its solve stage the positions a global shutter would have seen at the two time stamps;
         everything in the image keeps the raw pixels."""
-        m = rshutter if rshutter is not None or not settings else rshutter_setting(**settings)
-        with self._lock:
-            self._ck(self._L.ofk_set_rolling_shutter(self._h, C.byref(m) if m is not None else None))
+        self._set_struct(self._L.ofk_set_rolling_shutter, rshutter, settings, rshutter_setting, lock=True)
 
     def get_rolling_shutter(self):
-        m = RShutter()
-        self._ck(self._L.ofk_get_rolling_shutter(self._h, C.byref(m)))
-        return m
+        return self._get_struct(self._L.ofk_get_rolling_shutter, RShutter)
 
     def rs_correct_points(self, rshutter, raw_prev, raw_next, counts=None, sensors=None, ideal_prev=None, ideal_next=None, out=None):
         """ofk_rs_correct_points: raw_prev, raw_next [B,S,2] (or [S,2]) f32 image pixels of the tracked points (their rows give the
         capture times), ideal_prev / ideal_next the ideal pixels of the same points (both None: the raw ones) -> (prev, next) as a
         global shutter would have seen them at the two time stamps.  rshutter: an RShutter with rows > 0; sensors [B,28] (needed in
         gyro mode); counts None = every point; entries beyond counts[b] keep what out = (prev, next) holds (zeros without it)."""
-        rp, rn = _arr(raw_prev, np.float32), _arr(raw_next, np.float32)
-        single = rp.ndim == 2
-        if single:
-            rp, rn = rp[None], rn[None]
-        if rp.ndim != 3 or rp.shape[2] != 2 or rn.shape != rp.shape:
-            raise ValueError(f"rs_correct_points: points {rp.shape} / {rn.shape} are not two [B, S, 2] arrays")
+        single, (rp, rn), counts, sn, (o0, o1) = _point_arrays(
+            [raw_prev, raw_next], counts, sensors, [None, None] if out is None else [out[0], out[1]],
+            lambda a, b: f"rs_correct_points: points {a} / {b} are not two [B, S, 2] arrays")
         B, S = rp.shape[:2]
         if (ideal_prev is None) != (ideal_next is None):
             raise ValueError("rs_correct_points: ideal_prev and ideal_next come together")
         ip = None if ideal_prev is None else _arr(ideal_prev, np.float32).reshape(rp.shape)
         inx = None if ideal_next is None else _arr(ideal_next, np.float32).reshape(rp.shape)
-        counts = _arr(S if counts is None else counts, np.int32, (B,))
-        sn = None if sensors is None else _arr(sensors, np.float64, (B, SENSOR_DOUBLES))
-        if out is None:
-            o0 = np.zeros((B, S, 2), np.float32); o1 = np.zeros((B, S, 2), np.float32)
-        else:
-            o0 = np.array(out[0], np.float32).reshape(B, S, 2); o1 = np.array(out[1], np.float32).reshape(B, S, 2)
         if S > 0:
             with self._lock:
                 self._ck(self._L.ofk_rs_correct_points(self._h, C.byref(rshutter), _p(rp), _p(rn), _p(ip), _p(inx), _p(counts), B, S, _p(sn), _p(o0), _p(o1)))
@@ -946,43 +937,25 @@ class Context:
     def rs_download(self, batch):
         """ofk_rs_download: (prev, next) [batch,max_pts,2] f32, the points the solve stage of the latest run or step with the rolling
         shutter on saw.  The library writes that run's rows, so the buffers have max_batch of them."""
-        if not 0 <= int(batch) <= self.max_batch:
-            raise ValueError(f"rs_download: batch {batch} outside 0..{self.max_batch}")
-        a = np.zeros((self.max_batch, self.max_pts, 2), np.float32); b = np.zeros_like(a)
-        with self._lock:
-            self._ck(self._L.ofk_rs_download(self._h, _p(a), _p(b), self.max_pts))
-        return a[:batch].copy(), b[:batch].copy()
+        return self._points_download("ofk_rs_download", batch)
 
     def set_finite_motion(self, finite_motion=None, **settings):
         """ofk_set_finite_motion: a FiniteMotion (or finite_motion_setting's keywords); None or mode "off" switches it off.  Every
         later pairs_run and stream step hands its solve stage the points for which the first-order system is the exact relation of
         the frame pair; the velocity is then the displacement per frame interval.  Everything in the image keeps the raw pixels."""
-        m = finite_motion if finite_motion is not None or not settings else finite_motion_setting(**settings)
-        with self._lock:
-            self._ck(self._L.ofk_set_finite_motion(self._h, C.byref(m) if m is not None else None))
+        self._set_struct(self._L.ofk_set_finite_motion, finite_motion, settings, finite_motion_setting, lock=True)
 
     def get_finite_motion(self):
-        m = FiniteMotion()
-        self._ck(self._L.ofk_get_finite_motion(self._h, C.byref(m)))
-        return m
+        return self._get_struct(self._L.ofk_get_finite_motion, FiniteMotion)
 
     def finite_correct_points(self, finite_motion, prev, next, counts=None, sensors=None, out=None):
         """ofk_finite_correct_points: prev, next [B,S,2] (or [S,2]) f32, the points the solve would otherwise read -> (prev, next)
         rewritten for the finite motion of sensors [B,28] (normal, omega, scaling, centre).  counts None = every point; entries
         beyond counts[b] keep what out = (prev, next) holds (zeros without it)."""
-        pp, pn = _arr(prev, np.float32), _arr(next, np.float32)
-        single = pp.ndim == 2
-        if single:
-            pp, pn = pp[None], pn[None]
-        if pp.ndim != 3 or pp.shape[2] != 2 or pn.shape != pp.shape:
-            raise ValueError(f"finite_correct_points: points {pp.shape} / {pn.shape} are not two [B, S, 2] arrays")
+        single, (pp, pn), counts, sn, (o0, o1) = _point_arrays(
+            [prev, next], counts, sensors, [None, None] if out is None else [out[0], out[1]],
+            lambda a, b: f"finite_correct_points: points {a} / {b} are not two [B, S, 2] arrays")
         B, S = pp.shape[:2]
-        counts = _arr(S if counts is None else counts, np.int32, (B,))
-        sn = None if sensors is None else _arr(sensors, np.float64, (B, SENSOR_DOUBLES))
-        if out is None:
-            o0 = np.zeros((B, S, 2), np.float32); o1 = np.zeros((B, S, 2), np.float32)
-        else:
-            o0 = np.array(out[0], np.float32).reshape(B, S, 2); o1 = np.array(out[1], np.float32).reshape(B, S, 2)
         if S > 0:
             with self._lock:
                 self._ck(self._L.ofk_finite_correct_points(self._h, C.byref(finite_motion), _p(pp), _p(pn), _p(counts), B, S, _p(sn), _p(o0), _p(o1)))
@@ -991,31 +964,18 @@ class Context:
     def finite_download(self, batch):
         """ofk_finite_download: (prev, next) [batch,max_pts,2] f32, the points the solve stage of the latest run or step with the
         finite motion on saw.  The library writes that run's rows, so the buffers have max_batch of them."""
-        if not 0 <= int(batch) <= self.max_batch:
-            raise ValueError(f"finite_download: batch {batch} outside 0..{self.max_batch}")
-        a = np.zeros((self.max_batch, self.max_pts, 2), np.float32); b = np.zeros_like(a)
-        with self._lock:
-            self._ck(self._L.ofk_finite_download(self._h, _p(a), _p(b), self.max_pts))
-        return a[:batch].copy(), b[:batch].copy()
+        return self._points_download("ofk_finite_download", batch)
 
     def track_gate_download(self, batch, points=True):
         """ofk_track_gate_download of the latest gated run / step -> dict(stats [batch,4] i32: forward-tracked, of those lost by the
         backward pass, of the rest beyond fb_thr, of the rest over err_max; and, with points, fb2 [batch,max_pts] f32, back_pts
         [batch,max_pts,2] f32, back_status [batch,max_pts] u8 - zeros when only the err cap was on).  The library writes the rows of
         the latest run, whatever `batch` says, so the buffers have max_batch rows and the first `batch` are returned."""
-        B, S = self.max_batch, self.max_pts
-        if not 0 <= int(batch) <= B:
-            raise ValueError(f"track_gate_download: batch {batch} outside 0..{B}")
-        st = np.zeros((B, 4), np.int32)
-        fb2 = bp = bs = None
-        if points:
-            fb2 = np.zeros((B, S), np.float32); bp = np.zeros((B, S, 2), np.float32); bs = np.zeros((B, S), np.uint8)
-        with self._lock:
-            self._ck(self._L.ofk_track_gate_download(self._h, _p(fb2), _p(bp), _p(bs), S, _p(st)))
-        out = dict(stats=st[:batch].copy())
-        if points:
-            out.update(fb2=fb2[:batch].copy(), back_pts=bp[:batch].copy(), back_status=bs[:batch].copy())
-        return out
+        S = self.max_pts
+        per_point = [((S,), np.float32), ((S, 2), np.float32), ((S,), np.uint8)] if points else []
+        st, *pts = self._rows("track_gate_download", batch, lambda st, *p: self._L.ofk_track_gate_download(self._h, *(p or [None] * 3), S, st),
+                              ((4,), np.int32), *per_point)
+        return dict(stats=st, **dict(zip(("fb2", "back_pts", "back_status"), pts)))
 
     def track_gate_stats(self, batch):
         """The four counts per image of the latest gated run / step alone ([batch,4] int32): no per-point array is copied."""
@@ -1132,20 +1092,15 @@ class Context:
     def set_robust(self, robust=None, **settings):
         """ofk_set_robust: a Robust (or robust_setting's keywords); None or loss "off" switches it off.  Every later pairs_run and
         stream step solves robustly."""
-        r = robust if robust is not None or not settings else robust_setting(**settings)
-        self._ck(self._L.ofk_set_robust(self._h, C.byref(r) if r is not None else None))
+        self._set_struct(self._L.ofk_set_robust, robust, settings, robust_setting, lock=False)
 
     def get_robust(self):
-        r = Robust()
-        self._ck(self._L.ofk_get_robust(self._h, C.byref(r)))
-        return r
+        return self._get_struct(self._L.ofk_get_robust, Robust)
 
     def robust_download(self, batch):
         """(weights [batch, max_pts], stats [batch, 8]) of the latest run / step with the setting on."""
-        w = np.zeros((self.max_batch, self.max_pts), np.float64); st = np.zeros((self.max_batch, ROBUST_DOUBLES), np.float64)
-        with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
-            self._ck(self._L.ofk_robust_download(self._h, _p(w), self.max_pts, _p(st)))
-        return w[:batch].copy(), st[:batch].copy()
+        return tuple(self._rows(None, batch, lambda w, st: self._L.ofk_robust_download(self._h, w, self.max_pts, st),
+                                ((self.max_pts,), np.float64), ((ROBUST_DOUBLES,), np.float64)))
 
     def _velocity_solve_second(self, name, variant, x, u, d, nrm, omega, t, valid, robust, setting, doubles, no_points, points=False):
         """ofk_velocity_solve_<name>: the marshalling the second-stage stage entries share.  no_points(rec, d, nrm, omega) fills the
@@ -1173,10 +1128,7 @@ class Context:
 
     def _records_download(self, name, batch, *shape):
         """ofk_<name>_download into [max_batch, *shape]: its first `batch` rows."""
-        rec = np.zeros((self.max_batch,) + shape, np.float64)
-        with self._lock:                                         # the library writes the rows of the latest run, whatever `batch` says
-            self._ck(getattr(self._L, f"ofk_{name}_download")(self._h, _p(rec)))
-        return rec[:batch].copy()
+        return self._rows(None, batch, lambda rec: getattr(self._L, f"ofk_{name}_download")(self._h, rec), (shape, np.float64))[0]
 
     def velocity_solve_cov(self, variant, x, u, d=None, nrm=None, omega=None, t=None, valid=None, robust=None, cov=None, **settings):
         """ofk_velocity_solve_cov: velocity_solve's arguments (NODE or SIM), an optional Robust and the covariance setting (a Cov, or
@@ -1189,13 +1141,10 @@ class Context:
     def set_cov(self, cov=None, **settings):
         """ofk_set_cov: a Cov (or cov_setting's keywords); None or mode "off" switches it off.  Every later pairs_run, pairs filter step
         and stream step computes the covariance records (and, with filter_r / nis_max, corrects its filter with them)."""
-        cv = cov if cov is not None or not settings else cov_setting(**settings)
-        self._ck(self._L.ofk_set_cov(self._h, C.byref(cv) if cv is not None else None))
+        self._set_struct(self._L.ofk_set_cov, cov, settings, cov_setting, lock=False)
 
     def get_cov(self):
-        cv = Cov()
-        self._ck(self._L.ofk_get_cov(self._h, C.byref(cv)))
-        return cv
+        return self._get_struct(self._L.ofk_get_cov, Cov)
 
     def cov_download(self, batch):
         """cov [batch, 24] of the latest run / step with the setting on."""
@@ -1214,13 +1163,10 @@ class Context:
     def set_joint(self, joint=None, **settings):
         """ofk_set_joint: a Joint (or joint_setting's keywords); None or mode False switches it off.  Every later pairs_run and stream
         step refines the gyro from the flow and rewrites v, the residual and v_uav of its records."""
-        jv = joint if joint is not None or not settings else joint_setting(**settings)
-        self._ck(self._L.ofk_set_joint(self._h, C.byref(jv) if jv is not None else None))
+        self._set_struct(self._L.ofk_set_joint, joint, settings, joint_setting, lock=False)
 
     def get_joint(self):
-        jv = Joint()
-        self._ck(self._L.ofk_get_joint(self._h, C.byref(jv)))
-        return jv
+        return self._get_struct(self._L.ofk_get_joint, Joint)
 
     def joint_download(self, batch):
         """joint [batch, 32] of the latest run / step with the setting on."""
@@ -1240,13 +1186,10 @@ class Context:
     def set_plane(self, plane=None, **settings):
         """ofk_set_plane: a Plane (or plane_setting's keywords); None or mode False switches it off.  Every later pairs_run and stream
         step refines the ground normal from the flow and rewrites v, the residual and v_uav of its records."""
-        pv = plane if plane is not None or not settings else plane_setting(**settings)
-        self._ck(self._L.ofk_set_plane(self._h, C.byref(pv) if pv is not None else None))
+        self._set_struct(self._L.ofk_set_plane, plane, settings, plane_setting, lock=False)
 
     def get_plane(self):
-        pv = Plane()
-        self._ck(self._L.ofk_get_plane(self._h, C.byref(pv)))
-        return pv
+        return self._get_struct(self._L.ofk_get_plane, Plane)
 
     def plane_download(self, batch):
         """plane [batch, 32] of the latest run / step with the setting on."""
@@ -1265,13 +1208,10 @@ class Context:
         """ofk_set_epipolar: an Epipolar (or epipolar_setting's keywords); None or mode False switches it off.  Every later pairs_run
         and stream step takes v from the epipolar constraint and the range at the beam's foot, and rewrites v, field 3 and v_uav of
         its records."""
-        ev = epipolar if epipolar is not None or not settings else epipolar_setting(**settings)
-        self._ck(self._L.ofk_set_epipolar(self._h, C.byref(ev) if ev is not None else None))
+        self._set_struct(self._L.ofk_set_epipolar, epipolar, settings, epipolar_setting, lock=False)
 
     def get_epipolar(self):
-        ev = Epipolar()
-        self._ck(self._L.ofk_get_epipolar(self._h, C.byref(ev)))
-        return ev
+        return self._get_struct(self._L.ofk_get_epipolar, Epipolar)
 
     def epipolar_download(self, batch):
         """The record [batch, 32] and the point rows [batch, max_pts, 4] (rho, r, |b|, flag) of the latest run / step with the

@@ -354,6 +354,31 @@ class FusionConfig:
                           int(self.z_source), 1 if self.vel_overwrite else 0, 1 if self.redetect_replace else 0, int(self.min_solve), 1 if self.hold_on_skip else 0)
 
 
+def _apply_settings(ctx, cfg, zones):
+    """The settings a PipelineConfig switches on, on a fresh context, in the order the library's checks were written for; zones:
+    whether the exclusion zones are among them (they belong to the stream steps)."""
+    if cfg.lk_seed != "off":
+        ctx.set_lk_seed(cfg.lk_seed, cfg.seed_gain)
+    steps = [(ctx.set_robust, cfg.robust_setting), (ctx.set_track_gate, cfg.track_gate_setting), (ctx.set_corner_grid, cfg.corner_grid_setting),
+             (ctx.set_cov, cfg.cov_setting), (ctx.set_joint, cfg.joint_setting), (ctx.set_plane, cfg.plane_setting),
+             (ctx.set_epipolar, cfg.epipolar_setting)]
+    if zones:
+        steps.append((ctx.set_zones, cfg.zones_setting))
+    steps += [(ctx.set_camera, cfg.camera_setting), (ctx.set_rolling_shutter, cfg.rolling_shutter_setting),
+              (ctx.set_finite_motion, cfg.finite_motion_setting)]
+    for setter, setting in steps:                                # every *_setting() is None when its setting is off
+        value = setting()
+        if value is not None:
+            setter(value)
+
+
+def _ideal_points(ctx, batch):
+    """The download of the last point correction that is on: each one's output is the next one's input."""
+    if ctx.get_finite_motion().mode != ofk.FM_OFF:
+        return ctx.finite_download(batch)
+    return ctx.rs_download(batch) if ctx.get_rolling_shutter().mode != ofk.RS_OFF else ctx.camera_download(batch)
+
+
 class FlowStream:
     """`batch` independent video streams with persistent tracks on the device: the loop of velocity_measurment_node:92-177
     (commented-out blocks restored) / of_module.py:78-167 / evaluate_exp.py:77-121, one frame per `step`.
@@ -369,30 +394,7 @@ class FlowStream:
         self.min_features, self.mask_radius = int(min_features), int(mask_radius)
         self.ctx = ofk.Context(device, width, height, batch, max(1, self.cfg.max_corners), max(0, self.cfg.max_level))
         self._params = self.cfg.to_params()
-        if self.cfg.lk_seed != "off":
-            self.ctx.set_lk_seed(self.cfg.lk_seed, self.cfg.seed_gain)
-        if self.cfg.robust != "off":
-            self.ctx.set_robust(self.cfg.robust_setting())
-        if self.cfg.track_gate_setting() is not None:
-            self.ctx.set_track_gate(self.cfg.track_gate_setting())
-        if self.cfg.corner_grid_setting() is not None:
-            self.ctx.set_corner_grid(self.cfg.corner_grid_setting())
-        if self.cfg.cov != "off":
-            self.ctx.set_cov(self.cfg.cov_setting())
-        if self.cfg.joint:
-            self.ctx.set_joint(self.cfg.joint_setting())
-        if self.cfg.plane:
-            self.ctx.set_plane(self.cfg.plane_setting())
-        if self.cfg.epipolar:
-            self.ctx.set_epipolar(self.cfg.epipolar_setting())
-        if self.cfg.zones_setting() is not None:
-            self.ctx.set_zones(self.cfg.zones_setting())
-        if self.cfg.camera_setting() is not None:
-            self.ctx.set_camera(self.cfg.camera_setting())
-        if self.cfg.rolling_shutter_setting() is not None:
-            self.ctx.set_rolling_shutter(self.cfg.rolling_shutter_setting())
-        if self.cfg.finite_motion_setting() is not None:
-            self.ctx.set_finite_motion(self.cfg.finite_motion_setting())
+        _apply_settings(self.ctx, self.cfg, zones=True)
         self.fusion = fusion
         if fusion is not None:                                  # the per-stream filter state lives on the device from here on
             self._fusion = fusion.to_struct()
@@ -451,9 +453,7 @@ class FlowStream:
     def ideal_points(self):
         """(prev, next) [batch, max_pts, 2] f32: the points the solve stage of the latest step saw (camera model, rolling shutter or
         finite motion on)."""
-        if self.ctx.get_finite_motion().mode != ofk.FM_OFF:
-            return self.ctx.finite_download(self.batch)
-        return self.ctx.rs_download(self.batch) if self.ctx.get_rolling_shutter().mode != ofk.RS_OFF else self.ctx.camera_download(self.batch)
+        return _ideal_points(self.ctx, self.batch)
 
     def begin(self, first_bgr):
         return self.ctx.stream_begin(first_bgr, self._params)
@@ -489,28 +489,7 @@ class FlowPipeline:
         self.streams = streams
         self.ctx = ofk.Context(device, width, height, batch, max(1, self.cfg.max_corners), max(0, self.cfg.max_level))
         self._params = self.cfg.to_params()
-        if self.cfg.lk_seed != "off":
-            self.ctx.set_lk_seed(self.cfg.lk_seed, self.cfg.seed_gain)
-        if self.cfg.robust != "off":
-            self.ctx.set_robust(self.cfg.robust_setting())
-        if self.cfg.track_gate_setting() is not None:
-            self.ctx.set_track_gate(self.cfg.track_gate_setting())
-        if self.cfg.corner_grid_setting() is not None:
-            self.ctx.set_corner_grid(self.cfg.corner_grid_setting())
-        if self.cfg.cov != "off":
-            self.ctx.set_cov(self.cfg.cov_setting())
-        if self.cfg.joint:
-            self.ctx.set_joint(self.cfg.joint_setting())
-        if self.cfg.plane:
-            self.ctx.set_plane(self.cfg.plane_setting())
-        if self.cfg.epipolar:
-            self.ctx.set_epipolar(self.cfg.epipolar_setting())
-        if self.cfg.camera_setting() is not None:
-            self.ctx.set_camera(self.cfg.camera_setting())
-        if self.cfg.rolling_shutter_setting() is not None:
-            self.ctx.set_rolling_shutter(self.cfg.rolling_shutter_setting())
-        if self.cfg.finite_motion_setting() is not None:
-            self.ctx.set_finite_motion(self.cfg.finite_motion_setting())
+        _apply_settings(self.ctx, self.cfg, zones=False)         # pairs_run ignores the zones
         if streams > 1:
             self.ctx.set_streams(streams)
 
@@ -578,9 +557,7 @@ class FlowPipeline:
     def ideal_points(self):
         """(prev, next) [batch, max_pts, 2] f32: the points the solve stage of the latest run saw (camera model, rolling shutter or
         finite motion on)."""
-        if self.ctx.get_finite_motion().mode != ofk.FM_OFF:
-            return self.ctx.finite_download(self.batch)
-        return self.ctx.rs_download(self.batch) if self.ctx.get_rolling_shutter().mode != ofk.RS_OFF else self.ctx.camera_download(self.batch)
+        return _ideal_points(self.ctx, self.batch)
 
     def run_async(self):
         self.ctx.pairs_run(self._params)

@@ -19,6 +19,7 @@ import numpy as np
 from oracle import image_oracle as io
 import lk_seed_reference as R  # tests/lk_seed_reference.py
 import track_gate_reference as G  # tests/track_gate_reference.py
+from point_stage_helpers import bits  # tests/point_stage_helpers.py
 import robust_reference as rr  # tests/robust_reference.py
 import robust_stream_oracle as rso  # tests/robust_stream_oracle.py
 from stream_oracle import NodeLoop, oracle_of_module, track
@@ -32,11 +33,6 @@ SENTINEL = np.float32(-12345.678)                                           # wh
 FORWARD_SHIFT = np.array([3, -2], np.float32)                               # the seeded forward pass starts at points + this
 POINT_SEED = 1056          # of the random slots; chosen on the reference so that every chunk of every gate case meets the CPU companion's limits
 _cache = {}
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 def differing(got, want):

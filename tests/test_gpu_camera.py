@@ -16,8 +16,7 @@ import batch_oracle as BO
 import camera_reference as R
 import combined_cases as cc
 import cov_reference as cr
-import robust_reference as rr
-from oracle import estimation_oracle as eo
+from point_stage_helpers import ROBUST, SENTINEL, assert_image_side_identical, assert_plain_records, bits, robust_reference, same_points
 from stream_oracle import feasibility_solve
 
 pytestmark = pytest.mark.gpu
@@ -25,13 +24,7 @@ pytestmark = pytest.mark.gpu
 H, W, B, CORNERS = 240, 320, 4, 64
 MOTION = dict(v=(0.004, -0.003, 0.002), omega=(0.003, -0.002, 0.004), d=1.0)
 PAIR_CAM = dict(fx=320.0, fy=320.0, cx=160.0, cy=120.0, k=R.STRONG[1])
-SENTINEL = np.float32(-7.5)
 _cache = {}
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 def as_struct(ofk, cam):
@@ -39,17 +32,6 @@ def as_struct(ofk, cam):
     import ctypes as C
     return ofk.Camera(cam["model"], cam["iters"], cam["fx"], cam["fy"], cam["cx"], cam["cy"], (C.c_double * 8)(*cam["k"]), cam["fo_x"], cam["fo_y"],
                       cam["co_x"], cam["co_y"])
-
-
-def same_points(got, ref, ulp=0):
-    """Finite results within `ulp` float32 steps (0: the same bits); infinities equal; not-a-number where the reference is."""
-    got, ref = np.asarray(got, np.float32), np.asarray(ref, np.float32)
-    fin = np.isfinite(ref)
-    if not np.array_equal(np.isnan(got), np.isnan(ref)) or not np.array_equal(got[np.isinf(ref)], ref[np.isinf(ref)]):
-        return False
-    if ulp == 0:
-        return np.array_equal(bits(got[fin]), bits(ref[fin]))
-    return bool(np.all(np.abs(got[fin].astype(np.float64) - ref[fin].astype(np.float64)) <= ulp * np.spacing(np.maximum(np.abs(got[fin]), np.abs(ref[fin])))))
 
 
 @pytest.fixture(scope="module")
@@ -167,12 +149,6 @@ def pair_camera(ofk):
     return cm, R.camera(R.BROWN, PAIR_CAM["k"], PAIR_CAM["fx"], PAIR_CAM["fy"], PAIR_CAM["cx"], PAIR_CAM["cy"])
 
 
-def assert_image_side_identical(a, b, tag):
-    assert np.array_equal(a["counts"], b["counts"]), tag
-    for k in ("prev_pts", "next_pts", "status", "err"):
-        assert np.array_equal(bits(a[k]), bits(b[k])), (tag, k)
-
-
 def ideal_of_download(ctx, m, cam, out, tag):
     """ofk_camera_download == ofk_undistort_points of the downloaded raw points == the numpy reference, bit for bit, up to counts."""
     nb = len(out["counts"])
@@ -185,21 +161,6 @@ def ideal_of_download(ctx, m, cam, out, tag):
         assert np.array_equal(bits(pu[b, :n]), bits(R.undistort_points(cam, out["prev_pts"][b, :n]))), (tag, b)
         assert np.array_equal(bits(nu[b, :n]), bits(R.undistort_points(cam, out["next_pts"][b, :n]))), (tag, b)
     return pu, nu
-
-
-def assert_plain_records(out, pu, nu, sensors, tag):
-    """The records are the node solve of the ideal points with the downloaded status, within 1e-10."""
-    for b in range(len(out["counts"])):
-        n = int(out["counts"][b]); sr = sensors[b]
-        ok = out["status"][b, :n] == 1
-        new = nu[b, :n].astype(np.float64); old = pu[b, :n].astype(np.float64)
-        x = (new[ok] - [sr[20], sr[21]]) * sr[19]; u = (new[ok] - old[ok]) * sr[19]
-        v, _, rank, s = eo.solve_lgs_node(x, u, sr[0], sr[1:4], sr[4:7])
-        rec = out["records"][b]
-        assert rec[4] == rank and rec[11] == ok.sum() and rec[12] == n and rec[13] == ok.sum(), (tag, b, rec)
-        np.testing.assert_allclose(rec[0:3], v, rtol=0, atol=1e-10, err_msg=str((tag, b)))
-        np.testing.assert_allclose(rec[8:11], eo.post_solve(v, sr[7:16].reshape(3, 3), sr[4:7], sr[16:19]), rtol=0, atol=1e-10, err_msg=str((tag, b)))
-        np.testing.assert_allclose(rec[5:8], s, rtol=1e-9, err_msg=str((tag, b)))
 
 
 @pytest.mark.parametrize("streams,overlap", [(1, False), (1, True), (2, False), (2, True)])
@@ -229,21 +190,6 @@ def test_pairs_run_is_a_composition_of_stage_entries(pkg, ofk, streams, overlap)
     BO.assert_records_identical(again["records"], on["records"], tag)
     assert_image_side_identical(off, never, tag)
     BO.assert_records_identical(off["records"], never["records"], tag)
-
-
-ROBUST = dict(loss="tukey", c=4.685, iters=5, hypotheses=64, seed=0x1234ABCD5678)
-
-
-def robust_reference(b, x, u, ok, sr, st):
-    """robust_reference's solve of pair b, with the allowance of tests/test_gpu_robust_pipeline.py: two hypotheses whose scores tie to
-    1e-12 may be ranked either way, and the reference then follows the device's choice."""
-    kw = dict(valid=ok, loss=rr.TUKEY, c=ROBUST["c"], iters=ROBUST["iters"], hypotheses=ROBUST["hypotheses"], seed=ROBUST["seed"], problem=b)
-    ref = rr.robust_solve(rr.NODE, x, u, sr[0], sr[1:4], sr[4:7], **kw)
-    if int(st[4]) != int(ref["stats"][4]):
-        best = ref["stats"][5]
-        assert int(st[4]) >= 0 and abs(st[5] - best) <= 1e-12 * best, ("hyp", b, st, ref["stats"])
-        ref = rr.robust_solve(rr.NODE, x, u, sr[0], sr[1:4], sr[4:7], force_hyp=int(st[4]), **kw)
-    return ref
 
 
 @pytest.mark.parametrize("setting", ["robust", "cov", "gate", "seed"])

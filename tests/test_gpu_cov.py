@@ -9,6 +9,7 @@ import pytest
 
 import cov_reference as cr
 from oracle import estimation_oracle as eo
+from point_stage_helpers import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -17,11 +18,6 @@ COND_MAX = 1e3
 SIG = dict(sigma_flow=0.002, sigma_pos=0.003, sigma_d=0.04, sigma_omega=(0.01, 0.02, 0.015), sigma_normal=0.004, sigma_offset=0.006)
 SIG_PX = dict(SIG, sigma_flow=0.3, sigma_pos=0.5)                # the resident paths take pixels
 SEEN = dict(dev=0.0)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 def assert_cov_close(got, ref, tag):

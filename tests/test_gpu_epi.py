@@ -12,6 +12,7 @@ import pytest
 
 import epi_reference as er
 from oracle import estimation_oracle as eo
+from point_stage_helpers import bits
 from test_epi_reference import TOL
 
 pytestmark = pytest.mark.gpu
@@ -19,11 +20,6 @@ pytestmark = pytest.mark.gpu
 REC_TOL = 1e-9
 SEEN = dict(dev=0.0, rows=0.0, r=0.0)
 GPU_COUNTS = (3, 64, 65, 257, 1025)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 def assert_epi_close(v, rss, rec, rows, ref, tag):

@@ -7,7 +7,7 @@ Resident chains: every check is a composition of stage entries - the points the 
 rolling shutter's points of the camera's points of the downloaded raw points, the records are the reference solve of those points,
 and everything that lives in the image is bit-identical to a run with the setting off.  The stream steps are also held, step by step,
 to stream_oracle.NodeLoop with the solver fed from the rewritten points (finite_reference.finite_loop).  Frame sizes, slice counts
-and overlap settings are tests/test_gpu_rs.py's, whose helpers this module borrows.
+and overlap settings are tests/test_gpu_rs.py's: both take their scene from tests/rs_scene.py.
 
 The rendered scene (480 x 640, motion="finite", row 2's motion, LK on 4 levels, seeded from the sensor model), measured on an MI355X:
 190 tracked points, largest tracked flow 35.4 px, |v - T| / |T| 0.03330 with the setting off and 0.00422 with it on.  (Unseeded, LK
@@ -16,22 +16,20 @@ import numpy as np
 import pytest
 
 import batch_oracle as BO
-import camera_reference as CR
 import cov_reference as cr
 import finite_reference as F
 import joint_reference as J
 import plane_reference as P
 import rs_reference as R
-import test_gpu_joint as TJ
-import test_gpu_plane as TP
-import test_gpu_rs as TR
+import rs_scene as TR
+from joint_checks import JOINT, assert_joint_close
+from plane_checks import PLANE, assert_plane_close
+from point_stage_helpers import ROBUST, SENTINEL, assert_image_side_identical, assert_plain_records, bits, robust_reference, same_points
 from stream_oracle import feasibility_solve, imu_messages, plain_solve
 
 pytestmark = pytest.mark.gpu
 
 H, W, B = TR.H, TR.W, TR.B
-SENTINEL = TR.SENTINEL
-bits, same_points = TR.bits, TR.same_points
 FM = F.setting(F.EXACT, 0.1)
 
 
@@ -187,11 +185,11 @@ def test_pairs_run_is_a_composition_of_stage_entries(pkg, ofk, streams, overlap)
         off = pipe.run()
     finally:
         pipe.close()
-    TR.assert_image_side_identical(on, never, tag)
-    TR.assert_plain_records(on, pu, nu, sensors, tag)
+    assert_image_side_identical(on, never, tag)
+    assert_plain_records(on, pu, nu, sensors, tag)
     assert np.abs(on["records"][:, :3] - never["records"][:, :3]).max() > 1e-6           # the rewrite reached the solve
     BO.assert_records_identical(again["records"], on["records"], tag)
-    TR.assert_image_side_identical(off, never, tag)
+    assert_image_side_identical(off, never, tag)
     BO.assert_records_identical(off["records"], never["records"], tag)
 
 
@@ -208,15 +206,15 @@ def test_each_setting_with_the_finite_motion_on(pkg, ofk, setting):
     pipe = FlowPipeline(W, H, B, TR.pair_cfg(**cfg), streams=2)
     try:
         if setting == "robust":
-            pipe.ctx.set_robust(**TR.ROBUST)
+            pipe.ctx.set_robust(**ROBUST)
         if cam is not None:
             pipe.ctx.set_camera(cam)
         if rs is not None:
             pipe.ctx.set_rolling_shutter(TR.as_struct(ofk, dict(rs, rows=0)))
         if setting == "joint":
-            pipe.ctx.set_joint(**TJ.JOINT)
+            pipe.ctx.set_joint(**JOINT)
         if setting == "plane":
-            pipe.ctx.set_plane(**TP.PLANE)
+            pipe.ctx.set_plane(**PLANE)
         pipe.upload(prev, nxt, sensors)
         off = pipe.run()
         pipe.ctx.set_finite_motion(as_struct(ofk, FM))
@@ -244,10 +242,10 @@ def test_each_setting_with_the_finite_motion_on(pkg, ofk, setting):
             before = pipe.run()
     finally:
         pipe.close()
-    TR.assert_image_side_identical(on, off, setting)             # a seeded LK predicts its seeds exactly as with the setting off
+    assert_image_side_identical(on, off, setting)             # a seeded LK predicts its seeds exactly as with the setting off
     assert np.abs(on["records"][:, :3] - off["records"][:, :3]).max() > 1e-6
     if setting not in ("robust", "joint", "plane"):
-        TR.assert_plain_records(on, pu, nu, sensors, setting)
+        assert_plain_records(on, pu, nu, sensors, setting)
     if setting in ("gate", "several"):
         assert stats[:, 0].min() > 8, stats
     for b in range(B):
@@ -256,7 +254,7 @@ def test_each_setting_with_the_finite_motion_on(pkg, ofk, setting):
         new = nu[b, :n].astype(np.float64); old = pu[b, :n].astype(np.float64)
         x = (new - [sr[20], sr[21]]) * sr[19]; u = (new - old) * sr[19]
         if setting == "robust":
-            ref = TR.robust_reference(b, x, u, ok, sr, st[b])
+            ref = robust_reference(b, x, u, ok, sr, st[b])
             np.testing.assert_allclose(on["records"][b, 0:3], ref["v"], rtol=0, atol=1e-10, err_msg=str(b))
             np.testing.assert_allclose(wts[b, :n], ref["weights"], rtol=0, atol=1e-9, err_msg=str(b))
         if setting in ("cov", "several"):
@@ -265,13 +263,13 @@ def test_each_setting_with_the_finite_motion_on(pkg, ofk, setting):
             for sl in (slice(0, 6), slice(6, 12), slice(16, 22)):
                 assert np.abs(cov[b, sl] - ref[sl]).max() <= 1e-9 * np.abs(ref[sl]).max(), (b, sl)
         if setting == "joint":                                   # the joint solve of the rewritten points: its own reference and tolerances
-            ref = J.pair_joint(J.NODE, pu[b, :n], nu[b, :n], on["status"][b, :n], sr, TJ.JOINT["sigma_flow"], (TJ.JOINT["sigma_omega"],) * 3,
+            ref = J.pair_joint(J.NODE, pu[b, :n], nu[b, :n], on["status"][b, :n], sr, JOINT["sigma_flow"], (JOINT["sigma_omega"],) * 3,
                                before["records"][b])
-            TJ.assert_joint_close(on["records"][b, 0:3], on["records"][b, 3], jrec[b], ref, f"finite motion, pair {b}")
+            assert_joint_close(on["records"][b, 0:3], on["records"][b, 3], jrec[b], ref, f"finite motion, pair {b}")
         if setting == "plane":
-            ref = P.pair_plane(P.NODE, pu[b, :n], nu[b, :n], on["status"][b, :n], sr, TP.PLANE["sigma_flow"], TP.PLANE["sigma_normal"],
+            ref = P.pair_plane(P.NODE, pu[b, :n], nu[b, :n], on["status"][b, :n], sr, PLANE["sigma_flow"], PLANE["sigma_normal"],
                                before["records"][b])
-            TP.assert_plane_close(on["records"][b, 0:3], on["records"][b, 3], prec[b], ref, f"finite motion, pair {b}")
+            assert_plane_close(on["records"][b, 0:3], on["records"][b, 3], prec[b], ref, f"finite motion, pair {b}")
 
 
 # ---------------------------------------------------------------------------------------------------- streams
@@ -484,7 +482,7 @@ def test_rendered_scene_with_finite_motion_on_the_device(pkg, ofk):
     n = int(on["counts"][0])
     ok = on["status"][0, :n] == 1
     assert ok.sum() > 50
-    TR.assert_image_side_identical(on, off, "scene")
+    assert_image_side_identical(on, off, "scene")
     ra, rb = F.correct_points(FM, on["prev_pts"][0, :n], on["next_pts"][0, :n], sr[None])
     assert same_points(pu[0, :n], ra, 1) and same_points(nu[0, :n], rb, 1)
     np.testing.assert_allclose(on["records"][0, :3], F.solve_points(pu[0, :n][ok], nu[0, :n][ok], sr), rtol=0, atol=1e-10)

@@ -14,43 +14,11 @@ import pytest
 
 import plane_reference as pr
 from oracle import estimation_oracle as eo
-from test_plane_reference import TOL, COND_MAX
+from plane_checks import PLANE, SEEN, assert_plane_close
+from point_stage_helpers import bits
+from test_plane_reference import TOL
 
 pytestmark = pytest.mark.gpu
-
-RSS_TOL = 1e-10
-REC_TOL = 1e-9
-SEEN = dict(dev=0.0)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def assert_plane_close(v, rss, rec, ref, tag):
-    """The device's v, residual and plane record against plane_solve's dict."""
-    rr = ref["rec"]
-    assert rec[10] == ref["flag"], (tag, "flag", rec[10], ref["flag"], rec[12:15], rr[12:15])
-    assert rec[11] == rr[11] and np.all(rec[28:] == 0), tag
-    assert np.array_equal(rec[6:10], rr[6:10]), (tag, "the solve's v and residual before")
-    if ref["flag"] != 0:
-        assert np.array_equal(rec[0:4], rr[0:4]) and np.all(rec[4:6] == 0) and np.all(rec[14:26] == 0), tag
-        assert np.array_equal(v, ref["v"]) and rss == ref["rss"], (tag, "the record is untouched")
-        return
-    dev = pr.rel_dev(v, pr.record_m(rec), ref["v"], ref["m"])
-    SEEN["dev"] = max(SEEN["dev"], dev)
-    assert dev <= TOL, (tag, dev)
-    floor = 3 * rec[11] * ((TOL + 8 * pr.EPS) * ref["scale"]) ** 2
-    assert abs(rss - ref["rss"]) <= RSS_TOL * ref["rss"] + floor, (tag, "rss", rss, ref["rss"], floor)
-    for k in (26, 27):
-        assert abs(rec[k] - rr[k]) <= RSS_TOL * rr[k] + floor, (tag, k, rec[k], rr[k], floor)
-    np.testing.assert_allclose(rec[4:6], rr[4:6], rtol=0, atol=TOL * np.linalg.norm(ref["m"]), err_msg=tag)
-    for sl in (slice(12, 14), slice(14, 15), slice(15, 16), slice(17, 20), slice(20, 26)):
-        scale = np.abs(rr[sl]).max()
-        assert np.abs(rec[sl] - rr[sl]).max() <= REC_TOL * scale, (tag, sl, rec[sl], rr[sl])
-    assert abs(rec[16] - rr[16]) <= 1e-6 * rr[16] + 1e-11, (tag, "last step", rec[16], rr[16])
-    assert ref["cond"] < COND_MAX, (tag, ref["cond"])
 
 
 def batch3(n, **kw):
@@ -165,7 +133,6 @@ SLOPE = np.radians(10.0)
 GROUND = (np.sin(SLOPE) * 0.6, -np.sin(SLOPE) * 0.8, np.cos(SLOPE))      # what the frames show: a plane 10 degrees off the level one
 MOTION = dict(v=(0.012, -0.009, 0.004), omega=(0.003, -0.002, 0.004), d=1.0, n=GROUND)
 LEVEL = dict(d=1.0 / GROUND[2], normal=(0.0, 0.0, 1.0))          # what the sensors say: level ground at the range along the optical axis
-PLANE = dict(sigma_flow=0.2, sigma_normal=0.2)
 _frames = {}
 
 

@@ -15,6 +15,7 @@ import pytest
 
 from batch_oracle import assert_records_identical
 from oracle import estimation_oracle as eo
+from point_stage_helpers import bits
 import robust_reference as rr
 import robust_stream_oracle as rso
 from stream_oracle import NodeLoop, imu_messages
@@ -27,11 +28,6 @@ SETTING = dict(loss="tukey", c=4.685, iters=5, hypotheses=64, seed=0x1234ABCD567
 _batches = {}
 USED = dict(cases=0, hyp=0, count=0)
 USED_LOCK = threading.Lock()                                    # compare_pair runs on a thread pool
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 def batch_frames(h, w, B):

@@ -11,42 +11,14 @@ import numpy as np
 import pytest
 
 import batch_oracle as BO
-import camera_reference as CR
 import cov_reference as cr
-import robust_reference as rr
 import rs_reference as R
-from oracle import estimation_oracle as eo
+from point_stage_helpers import ROBUST, SENTINEL, assert_image_side_identical, assert_plain_records, bits, robust_reference, same_points
+from rs_scene import (B, COV, COVD, FEAS_T, GATE, H, MIN_FEAT, NB, NSTEPS, PAIR_CAM, RADIUS, SEED, SH, SW, W, as_struct, pair_batch, pair_cfg,
+                      stream_setup)
 from stream_oracle import feasibility_solve, plain_solve
 
 pytestmark = pytest.mark.gpu
-
-H, W, B, CORNERS = 120, 160, 4, 48
-F = 160.0
-MOTION = dict(v=(0.02, -0.03, 0.01), omega=(0.004, -0.003, 0.004), d=1.0)
-PAIR_CAM = dict(fx=F, fy=F, cx=80.0, cy=60.0, k=CR.STRONG[1])
-SENTINEL = np.float32(-7.5)
-_cache = {}
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def as_struct(ofk, rs):
-    """rs_reference's dict -> ofk.RShutter, field by field (no defaults in between)."""
-    return ofk.RShutter(rs["mode"], rs["rows"], rs["readout"], rs["anchor"], rs["omega_gain"])
-
-
-def same_points(got, ref, ulp=0):
-    """Finite results within `ulp` float32 steps (0: the same bits); infinities equal; not-a-number where the reference is."""
-    got, ref = np.asarray(got, np.float32), np.asarray(ref, np.float32)
-    fin = np.isfinite(ref)
-    if not np.array_equal(np.isnan(got), np.isnan(ref)) or not np.array_equal(got[np.isinf(ref)], ref[np.isinf(ref)]):
-        return False
-    if ulp == 0:
-        return np.array_equal(bits(got[fin]), bits(ref[fin]))
-    return bool(np.all(np.abs(got[fin].astype(np.float64) - ref[fin].astype(np.float64)) <= ulp * np.spacing(np.maximum(np.abs(got[fin]), np.abs(ref[fin])))))
 
 
 def ulp_of(mode):
@@ -141,25 +113,6 @@ def test_stage_entry_small_batches(ofk, sctx, mode):
 
 
 # ---------------------------------------------------------------------------------------------------- frame pairs
-def pair_batch(pkg, ofk):
-    if "pairs" not in _cache:
-        from of_amd import synth
-        prev, nxt, base = synth.make_batch(B, H, W, seed=5100, distinct=B, margin=64, scaling=1.0 / F, **MOTION)
-        sensors = ofk.make_sensors(B, d=MOTION["d"], normal=base[0]["n"], omega=MOTION["omega"], offset=(0.02, -0.01, 0.2), scaling=1.0 / F,
-                                   cx=W / 2.0, cy=H / 2.0, v_prior=MOTION["v"])
-        _cache["pairs"] = (prev, nxt, sensors)
-    return _cache["pairs"]
-
-
-def pair_cfg(**kw):
-    from of_amd.pipeline import PipelineConfig
-    return PipelineConfig(max_corners=CORNERS, quality=0.01, min_distance=6, block_size=7, win=15, max_level=2, max_count=20, eps=0.03, **kw)
-
-
-def assert_image_side_identical(a, b, tag):
-    assert np.array_equal(a["counts"], b["counts"]), tag
-    for k in ("prev_pts", "next_pts", "status", "err"):
-        assert np.array_equal(bits(a[k]), bits(b[k])), (tag, k)
 
 
 def corrected_of_download(ctx, ofk, rs, out, sensors, tag, camera=None):
@@ -183,21 +136,6 @@ def corrected_of_download(ctx, ofk, rs, out, sensors, tag, camera=None):
         moved = max(moved, float(np.abs(nu[b, :n][ok] - (kw["ideal_next"] if kw else out["next_pts"])[b, :n][ok]).max()))
     assert moved > 0.01, (tag, moved)                            # the correction is not the identity on this scene
     return pu, nu
-
-
-def assert_plain_records(out, pu, nu, sensors, tag):
-    """The records are the node solve of the corrected points with the downloaded status, within 1e-10."""
-    for b in range(len(out["counts"])):
-        n = int(out["counts"][b]); sr = sensors[b]
-        ok = out["status"][b, :n] == 1
-        new = nu[b, :n].astype(np.float64); old = pu[b, :n].astype(np.float64)
-        x = (new[ok] - [sr[20], sr[21]]) * sr[19]; u = (new[ok] - old[ok]) * sr[19]
-        v, _, rank, s = eo.solve_lgs_node(x, u, sr[0], sr[1:4], sr[4:7])
-        rec = out["records"][b]
-        assert rec[4] == rank and rec[11] == ok.sum() and rec[12] == n and rec[13] == ok.sum(), (tag, b, rec)
-        np.testing.assert_allclose(rec[0:3], v, rtol=0, atol=1e-10, err_msg=str((tag, b)))
-        np.testing.assert_allclose(rec[8:11], eo.post_solve(v, sr[7:16].reshape(3, 3), sr[4:7], sr[16:19]), rtol=0, atol=1e-10, err_msg=str((tag, b)))
-        np.testing.assert_allclose(rec[5:8], s, rtol=1e-9, err_msg=str((tag, b)))
 
 
 @pytest.mark.parametrize("streams,overlap,mode", [(1, False, "gyro"), (1, True, "flow"), (2, False, "flow"), (2, True, "gyro")])
@@ -233,26 +171,6 @@ def test_pairs_run_is_a_composition_of_stage_entries(pkg, ofk, streams, overlap,
     BO.assert_records_identical(again["records"], on["records"], tag)
     assert_image_side_identical(off, never, tag)
     BO.assert_records_identical(off["records"], never["records"], tag)
-
-
-ROBUST = dict(loss="tukey", c=4.685, iters=5, hypotheses=64, seed=0x1234ABCD5678)
-COVD = dict(mode=cr.PROPAGATE, sigma_flow=0.3, sigma_pos=0.5, sigma_d=0.04, sigma_omega=(0.01, 0.02, 0.015), sigma_normal=0.004, sigma_offset=0.006,
-            filter_r=False, r_floor=0.0, nis_max=0.0, omega_from_imu=False)
-COV = dict(cov="propagate", sigma_flow_px=0.3, sigma_pos_px=0.5, sigma_d=0.04, sigma_omega=(0.01, 0.02, 0.015), sigma_normal=0.004, sigma_offset=0.006)
-GATE = dict(fb_check="seeded", fb_thr=0.05, fb_level=0, err_max=6.0)
-SEED = dict(lk_seed="model", seed_gain=1.0)
-
-
-def robust_reference(b, x, u, ok, sr, st):
-    """robust_reference's solve of pair b, with the allowance of tests/test_gpu_robust_pipeline.py: two hypotheses whose scores tie to
-    1e-12 may be ranked either way, and the reference then follows the device's choice."""
-    kw = dict(valid=ok, loss=rr.TUKEY, c=ROBUST["c"], iters=ROBUST["iters"], hypotheses=ROBUST["hypotheses"], seed=ROBUST["seed"], problem=b)
-    ref = rr.robust_solve(rr.NODE, x, u, sr[0], sr[1:4], sr[4:7], **kw)
-    if int(st[4]) != int(ref["stats"][4]):
-        best = ref["stats"][5]
-        assert int(st[4]) >= 0 and abs(st[5] - best) <= 1e-12 * best, ("hyp", b, st, ref["stats"])
-        ref = rr.robust_solve(rr.NODE, x, u, sr[0], sr[1:4], sr[4:7], force_hyp=int(st[4]), **kw)
-    return ref
 
 
 @pytest.mark.parametrize("setting", ["robust", "cov", "gate", "seed", "camera", "several"])
@@ -308,22 +226,6 @@ def test_each_setting_with_the_rolling_shutter_on(pkg, ofk, setting):
 
 
 # ---------------------------------------------------------------------------------------------------- streams
-SH, SW, NB, NSTEPS, S_CORNERS, MIN_FEAT, RADIUS, FEAS_T = 96, 128, 2, 4, 40, 39, 8, 0.04
-S_MOTION = dict(v=(0.02, -0.03, 0.004), omega=(0.004, -0.003, 0.008), d=1.0)
-
-
-def stream_setup(pkg, ofk, kind):
-    from of_amd import synth
-    from of_amd.pipeline import PipelineConfig
-    if "seq" not in _cache:
-        seqs = [synth.render_sequence(SH, SW, 6100 + b, NSTEPS + 1, scaling=1.0 / SW, margin=64, **S_MOTION) for b in range(NB)]
-        _cache["seq"] = (np.stack([s[0] for s in seqs]), seqs[0][1])
-    frames, info = _cache["seq"]
-    sensors = ofk.make_sensors(NB, d=info["d"], normal=info["n"], omega=info["omega"], offset=(0.02, -0.01, 0.2), scaling=info["scaling"], cx=info["cx"],
-                               cy=info["cy"], v_prior=info["v"])
-    cfg = PipelineConfig(max_corners=S_CORNERS, quality=0.01, min_distance=6, block_size=7, win=15, max_level=2, max_count=20, eps=0.03, zones="hull",
-                         **({} if kind == "step" else dict(use_feasibility=True, feas_T=FEAS_T)))
-    return frames, sensors, cfg
 
 
 def run_stream(ofk, kind, frames, sensors, cfg, rshutter):

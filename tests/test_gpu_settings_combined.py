@@ -20,16 +20,12 @@ import pytest
 
 import combined_cases as cc
 import cov_reference as cr
+from point_stage_helpers import bits
 
 pytestmark = pytest.mark.gpu
 
 H, W, NB = cc.H, cc.W, cc.NB
 _cache = {}
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 def assert_cov_close(got, ref, tag):

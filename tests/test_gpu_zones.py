@@ -12,15 +12,11 @@ import pytest
 import robust_reference as rr
 import robust_stream_oracle as rso
 import zones_reference as zr
+from point_stage_helpers import bits
 
 pytestmark = pytest.mark.gpu
 
 H, W, B, S = 480, 640, 3, 512
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 @pytest.fixture(scope="module")
