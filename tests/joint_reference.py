@@ -154,12 +154,15 @@ def joint_solve(variant, x, u, d, n, omega, sigma_flow, sigma_omega, v_s=None, r
     est = np.flatnonzero(~held)
     S = D - K.T @ G
     S = 0.5 * (S + S.T)
-    for k in est:
-        if not np.isinf(ovar[k]):
-            S[k, k] += dsf2 / ovar[k]
+    with np.errstate(all="ignore"):                              # a prior term that overflows is the header's "sum ... not finite"
+        for k in est:
+            if not np.isinf(ovar[k]):
+                S[k, k] += dsf2 / ovar[k]
     S[held, :] = 0.0; S[:, held] = 0.0
     delta = np.zeros(3); Si = np.zeros((3, 3))
     if len(est):
+        if not np.all(np.isfinite(S)):                           # flag 1, slots 12-14 left 0: joint_finish ends before the eigenvalues
+            return out
         Si, ls = _sym_inverse(S, len(est))
         rec[12:15] = ls
         rec[12 + len(est):15] = 0.0                              # held axes: exact zeros on the device
@@ -183,9 +186,11 @@ def joint_solve(variant, x, u, d, n, omega, sigma_flow, sigma_omega, v_s=None, r
     return out
 
 
-def joint_lstsq(variant, x, u, d, n, omega, sigma_flow, sigma_omega, valid=None, w=None):
+def joint_lstsq(variant, x, u, d, n, omega, sigma_flow, sigma_omega, valid=None, w=None, scale_columns=False):
     """Independent: lstsq on the stacked rows sqrt(w) [a X, b N] (v, delta) = sqrt(w) b X q0 and the prior rows
-    (d sigma_f / sigma_k) delta_k = 0; a held axis has no column.  Returns v, omega."""
+    (d sigma_f / sigma_k) delta_k = 0; a held axis has no column.  scale_columns: every column is brought to unit length first (the
+    unknowns rescaled, the problem unchanged), so that lstsq's rank cut, relative to the largest singular value, does not take v's
+    columns for null beside a prior row of 1e150.  Returns v, omega."""
     x = np.asarray(x, np.float64).reshape(-1, 2); u = np.asarray(u, np.float64).reshape(-1, 2)
     om = np.asarray(omega, np.float64)
     idx, ww = _kept(x, valid, w)
@@ -202,7 +207,8 @@ def joint_lstsq(variant, x, u, d, n, omega, sigma_flow, sigma_omega, valid=None,
     cols = [0, 1, 2] + [3 + k for k in range(3) if so[k] > 0]
     A = np.concatenate([A, prior], 0)[:, cols]
     B = np.concatenate([B, np.zeros(3)])
-    sol = np.linalg.lstsq(A, B, rcond=None)[0]
+    cn = np.sqrt(np.sum(A * A, 0)) if scale_columns else np.ones(A.shape[1])
+    sol = np.linalg.lstsq(A / cn, B, rcond=None)[0] / cn
     delta = np.zeros(3)
     delta[[c_ - 3 for c_ in cols[3:]]] = sol[3:]
     return sol[:3], om + delta

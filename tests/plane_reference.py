@@ -93,7 +93,8 @@ def plane_solve(variant, x, u, d, n, omega, sigma_flow, sigma_normal, sigma_max=
     """One problem.  sigma_flow in the units of x and u; sigma_normal in radians (inf: free, 0: held).  v_s, rss_s, rank: the solve's
     own outputs (None: plain_solve's).  Returns a dict: v, rss (the record's fields after the plane solve), flag, rewritten (whether the
     record changes), rec (the 32 doubles), m (the refined inverse-distance vector), scale (the largest |sB X q| component), cond (the
-    condition number of the last walk's 5 x 5 system in the unknowns v / |v| and d0 tau), walks (the walks that were made)."""
+    condition number of the last walk's 5 x 5 system in the unknowns v / |v| and d0 tau), walks (the walks that were made), sigma (the
+    predicted 1 sigma of the angle, once the last walk formed it: what sigma_max gates)."""
     x = np.asarray(x, np.float64).reshape(-1, 2); u = np.asarray(u, np.float64).reshape(-1, 2)
     n0 = np.asarray(n, np.float64); om = np.asarray(omega, np.float64)
     if v_s is None:
@@ -119,7 +120,10 @@ def plane_solve(variant, x, u, d, n, omega, sigma_flow, sigma_normal, sigma_max=
     with np.errstate(all="ignore"):
         m0 = n0 / d0
         held = not sigma_normal > 0
-        lam = 0.0 if (held or np.isinf(sigma_normal)) else (d0 * d0 * float(sigma_flow) / float(sigma_normal)) ** 2
+        lroot = np.float64(0.0 if (held or np.isinf(sigma_normal)) else d0 * d0 * float(sigma_flow) / float(sigma_normal))
+        lam = float(lroot * lroot)                              # a numpy scalar: a prior term that overflows is +inf, not an OverflowError
+        if not np.isfinite(lam):                                # the header's "any sum or result is not finite": flag 1 before any sum is read
+            return out
         p, q, sA, sB = point_terms(variant, x[idx], u[idx], d0, n0, om)
         out["scale"] = float(np.abs(sB[:, None] * np.cross(p, q)).max())
         wk = ww[idx]
@@ -162,6 +166,7 @@ def plane_solve(variant, x, u, d, n, omega, sigma_flow, sigma_normal, sigma_max=
             step = np.sqrt(dv @ dv + d0 * d0 * (dtau @ dtau)) / vn if vn > 0 else 0.0
         rec[16] = step; rec[27] = F if np.isfinite(F) else 0.0
         sig = abs(d0) * np.sqrt(dsf2 / l2)
+        out["sigma"] = float(sig)                               # the predicted 1 sigma, kept for the caller where the gate zeroes slot 14
         mm = np.sqrt(m @ m)
         nh = m / mm; dh = 1.0 / mm
         ang = np.arctan2(np.sqrt(np.sum(np.cross(nh, n0) ** 2)), nh @ n0)

@@ -203,3 +203,36 @@ def test_filter_r_with_a_void_covariance_is_the_constant_r_filter():
     xh, Ph, nis_h, gated = cr.kf_correct_cov(x, P, H, Rm, z, cov_rec=rec, filter_r=True, nis_max=1e300)
     x0, P0, nis_0, _ = cr.kf_correct_cov(x, P, H, Rm, z, cov_rec=rec, filter_r=True)
     assert gated == 0 and np.array_equal(xh, x0) and np.array_equal(Ph, P0) and nis_h == nis_0
+
+
+def test_stream_loop_at_an_unsolved_step():
+    """CovStreamLoop.step with a record whose slot 15 is 0 (the step did not solve: v = 0, rank 0): the cov record is void with NIS
+    and gate 0, the filter stays at its prediction, fused[7] is 0 - and the next, solved, step corrects from that prediction."""
+    from types import SimpleNamespace
+    import joint_reference as jr
+    from test_joint_reference import pixel_points, sensor_row
+    x, u, d, nrm, om0, v, om = jr.scene(65, 1065)
+    sr = sensor_row(d, nrm, om)
+    prev, nxt = pixel_points(x, u, sr)
+    keep = np.ones(65, np.uint8); keep[7::9] = 0
+    model = SimpleNamespace(x0=np.zeros(3), P0=1e-4 * np.eye(3), F=np.eye(3), Q=1e-6 * np.eye(3), B=np.eye(3), nc=3, H=np.eye(3), R=1e-4 * np.eye(3),
+                            nm=3, ns=3)
+    cfg = dict(mode=cr.PROPAGATE, sigma_flow=0.3, sigma_pos=0.5, sigma_d=0.04, sigma_omega=(0.01, 0.02, 0.015), sigma_normal=0.004, sigma_offset=0.006,
+               filter_r=True, r_floor=1e-8)
+    loop = cr.CovStreamLoop(model, cfg, -1.0, 1)
+    control = np.array([1e-3, -2e-3, 5e-4])
+    unsolved = np.zeros(16); unsolved[11] = np.count_nonzero(keep)
+    srn = sr.copy(); srn[0] = np.nan                             # the dropout that left the step unsolved
+    cv, xk, Pk, fused = loop.step(prev, nxt, keep, srn, unsolved, control)
+    xp, Pp = eo.kf_predict(np.zeros(3), 1e-4 * np.eye(3), model.F, model.Q, model.B, control)
+    assert np.array_equal(cv, cr.void_record()) and cv[14] == 0 and cv[15] == 0
+    assert np.array_equal(xk, xp) and np.array_equal(Pk, Pp)
+    assert np.array_equal(fused, np.concatenate([xp, np.zeros(3), [np.trace(Pp), 0.0]]))
+    vs, rss, rank = jr.plain_solve(jr.NODE, *[a[keep.astype(bool)] for a in ((nxt - [640.0, 480.0]) * 1e-3, (nxt.astype(np.float64) - prev) * 1e-3)],
+                                   d, nrm, om)
+    rec = np.zeros(16); rec[0:3] = vs; rec[3] = rss; rec[4] = rank; rec[8:11] = vs; rec[15] = 1.0
+    cv, xk, Pk, fused = loop.step(prev, nxt, keep, sr, rec, control)
+    xp2, Pp2 = eo.kf_predict(xp, Pp, model.F, model.Q, model.B, control)
+    assert cv[13] == 0 and cv[14] > 0 and fused[7] == 1 and not np.array_equal(xk, xp2)
+    xr, Pr, nis, gated = cr.kf_correct_cov(xp2, Pp2, model.H, model.R, -vs, cov_rec=cv, z_sign=-1.0, z_source=1, filter_r=True, r_floor=1e-8)
+    assert np.array_equal(xk, xr) and np.array_equal(Pk, Pr) and nis == cv[14]

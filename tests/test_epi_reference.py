@@ -326,3 +326,21 @@ def test_rendered_pair_through_the_oracle_chain(pkg):
               f"sigma^ {sig:.3f} px, predicted {pred:.4f} rad, rho off by {100 * drho:.2f} %")
         assert flag == 0
         assert plain > 0.05 and epi < plain / 4, (seed, plain, epi)
+
+
+def test_pair_epi_behind_an_unsolved_step():
+    """solved=False (a stream step whose record[15] is 0): flag 1 in the header's layout - everything but slots 6-11 is 0, every point
+    row is 0 - and v / rss are the record's own; the same points with solved=True solve."""
+    from test_joint_reference import pixel_points, sensor_row
+    x, u, d, nrm, om, v, rho = er.scene(65, 1065)
+    sr = sensor_row(d, nrm, om)
+    prev, nxt = pixel_points(x, u, sr)
+    status = np.ones(65, np.uint8); status[10::9] = 0
+    for rec in (np.zeros(16), np.concatenate([[0.01, -0.02, 0.003, 4e-7, 3.0], np.zeros(11)])):
+        got = er.pair_epi(prev, nxt, status, sr, rec, anchor_px=120.0, solved=False)
+        r = got["rec"]
+        assert got["flag"] == 1 and r[10] == 1.0 and not got["rewritten"] and np.array_equal(got["v"], rec[0:3]) and got["rss"] == rec[3]
+        assert np.array_equal(r[6:10], rec[0:4]) and r[11] == np.count_nonzero(status) and not np.delete(r, [6, 7, 8, 9, 10, 11]).any()
+        assert got["rows"].shape == (65, 4) and not got["rows"].any()
+    on = er.pair_epi(prev, nxt, status, sr, rec, anchor_px=120.0, solved=True)
+    assert on["flag"] == 0 and on["rewritten"] and on["rows"][status == 0, 3].all()

@@ -112,6 +112,10 @@ def test_stage_entry_flags_return_the_solve_bits(gpu_ctx, ofk):
     for few in (1, 2):                                           # flag 1: one or two points
         rec = flagged(1, x[:, :few], u[:, :few], anchor=np.inf, anchor_min=1)
         assert np.all(rec[:, 11] == few) and np.all(np.delete(rec, [6, 7, 8, 9, 10, 11], 1) == 0)
+        pl = gpu_ctx.velocity_solve(ofk.SOLVE_NODE, x[:, :few], u[:, :few], d=d, nrm=nrm, omega=om)
+        for b in range(3):                                       # two points: rank 3 for the plain solve, no direction for this one - the reference's record
+            ref = er.epi_solve(x[b, :few], u[b, :few], d[b], nrm[b], om[b], anchor=np.inf, anchor_min=1, v_s=pl[b, :3], rss_s=pl[b, 3])
+            assert ref["flag"] == 1 and pl[b, 4] == (3 if few == 2 else 2) and np.array_equal(bits(rec[b]), bits(ref["rec"])), (few, b, rec[b])
     flagged(1, x, u, beam=(1.0, 0.0, 0.0))                       # e_z == 0
     flagged(1, x, u, nrm=np.array([[1.0, 0.0, 0.0]] * 3))        # n0.e == 0
     for bad in (0.0, np.nan):                                    # d0 = 0; a NaN range among finite problems, which keep their bits

@@ -155,12 +155,38 @@ def run_entry(ctx, ofk, entry, variant, a):
         return (ctx.velocity_solve(variant, x, u, **kw),)
     if entry == "robust":
         return ctx.velocity_solve_robust(variant, x, u, robust=ofk.robust_setting("tukey", hypotheses=16, iters=3, seed=5), **kw)
+    if entry == "joint":
+        return ctx.velocity_solve_joint(variant, x, u, **NF_SECOND["joint"], **kw)
+    if entry == "plane":
+        return ctx.velocity_solve_plane(variant, x, u, **NF_SECOND["plane"], **kw)
+    if entry == "epi":
+        return ctx.velocity_solve_epipolar(variant, x, u, **NF_SECOND["epi"], **kw)
     return ctx.velocity_solve_cov(variant, x, u, cov=ofk.cov_setting("propagate", sigma_flow=1e-4, sigma_pos=1e-4, sigma_d=0.01, sigma_omega=1e-3,
                                                                      sigma_normal=1e-3), **kw)
 
 
+# the second-stage settings of these runs: every one succeeds on the clean batch (the plane and epipolar gates are open)
+NF_SECOND = dict(joint=dict(sigma_flow=1e-4, sigma_omega=1e-3), plane=dict(sigma_flow=1e-4, sigma_normal=0.05, sigma_max=np.inf),
+                 epi=dict(anchor=np.inf, anchor_min=5, sigma_max=np.inf))
+
+
+def second_stage_flag1(entry, variant, a, b):
+    """The second-stage record of problem b behind a solve that did not solve (out = 0, rank 0), by the reference: flag 1 in the
+    layout of include/ofk.h."""
+    import epi_reference as er
+    import joint_reference as jr
+    import plane_reference as pr
+    args = (a["x"][b], a["u"][b], a["d"][b], a["nrm"][b], a["omega"][b])
+    kw = dict(v_s=np.zeros(3), rss_s=0.0, valid=a["valid"][b])
+    if entry == "joint":
+        return jr.joint_solve(variant, *args, 1e-4, (1e-3,) * 3, rank=0, **kw)
+    if entry == "plane":
+        return pr.plane_solve(variant, *args, 1e-4, 0.05, sigma_max=np.inf, rank=0, **kw)
+    return er.epi_solve(*args, anchor=np.inf, anchor_min=5, sigma_max=np.inf, **kw)
+
+
 @pytest.mark.parametrize("variant,bad", list(nonfinite_cases()))
-@pytest.mark.parametrize("entry", ("plain", "robust", "cov"))
+@pytest.mark.parametrize("entry", ("plain", "robust", "cov", "joint", "plane", "epi"))
 def test_nonfinite_values_at_the_stage_entries(gpu_ctx, ofk, entry, variant, bad):
     clean, dirty = nonfinite_batch(variant, bad)
     ref = run_entry(gpu_ctx, ofk, entry, variant, clean)
@@ -179,6 +205,16 @@ def test_nonfinite_values_at_the_stage_entries(gpu_ctx, ofk, entry, variant, bad
     if entry == "cov":
         cv = got[1][NF_BAD]
         assert cv[13] == 1 and not np.delete(cv, 13).any(), cv    # void
+    if entry in ("joint", "plane", "epi"):                       # flag 1 in the header's layout; the clean batch took the second stage
+        assert np.all(ref[1][:, 10] == 0), (entry, variant, ref[1][:, 10])
+        want = second_stage_flag1(entry, variant, dirty, NF_BAD)
+        rec = got[1][NF_BAD]
+        assert want["flag"] == 1 and rec[10] == 1 and rec[11] == m, (entry, variant, bad, rec)
+        assert np.array_equal(bits(rec), bits(want["rec"])), (entry, variant, bad, rec, want["rec"])
+        zero = dict(joint=[3, 4, 5] + list(range(12, 32)), plane=[4, 5] + list(range(12, 32)), epi=list(range(0, 6)) + list(range(12, 32)))[entry]
+        assert not rec[zero].any() and not rec[6:10].any(), (entry, variant, bad, rec)
+        if entry == "epi":
+            assert got[2].shape == (NF_B, NF_N, 4) and not got[2][NF_BAD].any(), (variant, bad)
 
 
 # ------------------------------------------------------------------------------------------------ 5. a rangefinder dropout in the resident paths

@@ -94,6 +94,32 @@ def test_stage_entry_flags_and_held_axes(gpu_ctx, ofk):
     assert np.all(plain[:, 4] == 3) and np.all(rec[:, 10] == 2) and np.array_equal(bits(out), bits(plain)) and np.array_equal(rec[:, 0:3], om0)
     assert np.all(rec[:, 12] > 0) and np.all(rec[:, 14] < np.sqrt(jr.EPS * 60) * rec[:, 12]) and np.all(rec[:, 15:27] == 0)
     assert np.all(gpu_ctx.velocity_solve_joint(ofk.SOLVE_NODE, xl, ul, d=d, sigma_omega=1e-3, **kw)[1][:, 10] == 0)
+    # two points: rank 3 for v, a singular S with every axis free (flag 2); a prior makes it a problem again - against the reference
+    x8, u8, d8, nrm8, om8, _, _ = (np.stack([jr.scene(8, 6 + b)[k] for b in range(3)]) for k in range(7))
+    plain = gpu_ctx.velocity_solve(ofk.SOLVE_NODE, x8[:, :2], u8[:, :2], d=d8, nrm=nrm8, omega=om8)
+    assert np.all(plain[:, 4] == 3)
+    for name, want in (("free", 2), ("prior", 0)):
+        out, rec = gpu_ctx.velocity_solve_joint(ofk.SOLVE_NODE, x8[:, :2], u8[:, :2], d=d8, nrm=nrm8, omega=om8, sigma_flow=jr.SIGMA_FLOW,
+                                                sigma_omega=jr.PRIORS[name])
+        for b in range(3):
+            ref = jr.joint_solve(jr.NODE, x8[b, :2], u8[b, :2], d8[b], nrm8[b], om8[b], jr.SIGMA_FLOW, jr.PRIORS[name], v_s=plain[b, :3], rss_s=plain[b, 3],
+                                 rank=plain[b, 4])
+            assert ref["flag"] == want and rec[b, 11] == 2, (name, b, ref["flag"])
+            if want == 2:                                        # the eigenvalues that are rounding alone are held to the size of the largest
+                assert np.array_equal(bits(out[b]), bits(plain[b])) and abs(rec[b, 12] - ref["rec"][12]) <= 1e-9 * ref["rec"][12], (b, rec[b, 12:15])
+                assert np.all(np.abs(rec[b, 13:15]) <= 1e-13 * rec[b, 12]), (b, rec[b, 12:15])
+            assert_joint_close(out[b, :3], out[b, 3], rec[b], ref, f"two points {name} problem {b}")
+    # a prior term that overflows: flag 1, out has the plain solve's bits, the record is the reference's to the bit
+    x, u, d, nrm, om0, v, om = batch3(65)
+    for variant in (ofk.SOLVE_NODE, ofk.SOLVE_SIM):
+        plain = gpu_ctx.velocity_solve(variant, x, u, d=d, nrm=nrm, omega=om0)
+        for prior in ((1e-160,) * 3, (1e-160, np.inf, 0.0)):
+            out, rec = gpu_ctx.velocity_solve_joint(variant, x, u, d=d, nrm=nrm, omega=om0, sigma_flow=jr.SIGMA_FLOW, sigma_omega=prior)
+            assert np.array_equal(bits(out), bits(plain)), (variant, prior)
+            for b in range(3):
+                ref = jr.joint_solve(variant, x[b], u[b], d[b], nrm[b], om0[b], jr.SIGMA_FLOW, prior, v_s=plain[b, :3], rss_s=plain[b, 3], rank=plain[b, 4])
+                assert ref["flag"] == 1 and np.array_equal(bits(rec[b]), bits(ref["rec"])), (variant, prior, b, rec[b])
+                assert not rec[b, 3:6].any() and not rec[b, 12:].any() and rec[b, 11] == 65
     # all axes held: the plain solve's bits; one axis held: its delta is exactly 0
     x, u, d, nrm, om0, v, om = batch3(65)
     kw = dict(nrm=nrm, omega=om0, sigma_flow=jr.SIGMA_FLOW)
@@ -271,54 +297,12 @@ def test_pairs_refusals_and_the_filter_step(pkg, ofk):
 
 # ---------------------------------------------------------------------------------------------------- stream steps
 def stream_run(ofk, joint, fusion_name, T=3):
-    """2 streams x T frames; per step what the device reported and what the reference needs."""
-    from of_amd import synth
-    from of_amd.pipeline import FlowStream, PipelineConfig, FusionConfig, FilterModel
-    from stream_oracle import imu_messages
-    B = 2
-    if "stream" not in _frames:
-        seqs = [synth.render_sequence(H, W, 7400 + s, 4, margin=64, **MOTION) for s in range(B)]
-        _frames["stream"] = (np.stack([s[0] for s in seqs]), seqs[0][1])
-    frames, info = _frames["stream"]
-    cfg = PipelineConfig(max_corners=CORNERS, quality=0.01, min_distance=6, block_size=5, win=15, max_level=2, max_count=20, eps=0.03)
-    if fusion_name == "ekf6":
-        fusion = FusionConfig.ekf6(r=1e-4, p0=1e-4)
-    elif fusion_name == "node":
-        fusion = FusionConfig.node()
-    elif fusion_name == "replace":
-        model = FilterModel.kf3()
-        model.R = 1e-4 * np.eye(3); model.P0 = 1e-4 * np.eye(3)
-        fusion = FusionConfig(filter=True, z_sign=-1.0, z_source=1, redetect_replace=True, model=model)
-    else:
-        fusion = None
-    sensors = ofk.make_sensors(B, d=info["d"], normal=info["n"], omega=np.asarray(info["omega"]) + GYRO_OFF, offset=(0.02, -0.01, 0.2),
-                               scaling=info["scaling"], cx=info["cx"], cy=info["cy"], v_prior=(0.004, -0.003, 0.002))
-    fs = FlowStream(W, H, batch=B, cfg=cfg, min_features=10, mask_radius=8, fusion=fusion)
-    steps = []
-    try:
-        if joint is not None:
-            fs.ctx.set_joint(**joint)
-        tracks, counts = fs.begin(frames[:, 0])
-        rng = np.random.default_rng(31)
-        for t in range(1, T):
-            imu = dv = None
-            if fusion is not None and fusion.use_imu:
-                msgs = np.stack([imu_messages(rng, 0.1 * t + 10 * s, 3, rate=np.asarray(info["omega"]) + GYRO_OFF) for s in range(B)])
-                fs.push_imu(msgs)
-                imu, dv = fs.ctx.imu_state(B)
-            old_tracks, old_counts = tracks.copy(), counts.copy()
-            if fusion is None:
-                rec, tracks, counts = fs.step(frames[:, t], sensors)
-                fused = x = P = None
-            else:
-                rec, fused, tracks, counts = fs.step_fused(frames[:, t], sensors)
-                x, P = fs.ctx.filter_state(B) if fusion.filter else (None, None)
-            nxt, keep = fs.ctx.stream_last_points(CORNERS)
-            imu_after = fs.ctx.imu_state(B)[0] if fusion is not None and fusion.use_imu else None
-            steps.append(dict(rec=rec, fused=fused, old=old_tracks, n=old_counts, nxt=nxt, keep=keep, imu=imu, dv=dv, x=x, P=P, imu_after=imu_after,
-                              joint=fs.rotations() if joint is not None else None))
-    finally:
-        fs.close()
+    """2 streams x T frames; per step what the device reported and what the reference needs (tests/second_stage_runs.py, which the
+    tests of the declined second stage share)."""
+    import second_stage_runs as ss
+    steps, sensors, fusion = ss.stream_run(ofk, ("joint", joint) if joint is not None else None, fusion_name, T=T)
+    for st in steps:
+        st["joint"] = st["second"]
     return steps, sensors, fusion
 
 

@@ -14,7 +14,7 @@ import pytest
 
 import plane_reference as pr
 from oracle import estimation_oracle as eo
-from plane_checks import PLANE, SEEN, assert_plane_close
+from plane_checks import PLANE, RSS_TOL, SEEN, assert_plane_close
 from point_stage_helpers import bits
 from test_plane_reference import TOL
 
@@ -107,6 +107,32 @@ def test_stage_entry_flags_and_the_held_prior(gpu_ctx, ofk):
     assert np.all(rec[:, 10] == 2) and np.array_equal(bits(out), bits(plain)) and np.array_equal(bits(rec[:, 12:14]), bits(frec[:, 12:14]))
     out, rec = gpu_ctx.velocity_solve_plane(ofk.SOLVE_NODE, x, u, d=d, sigma_max=np.inf, **kw)
     assert np.array_equal(bits(out), bits(full)) and np.array_equal(bits(rec), bits(frec))
+    # a prior term that overflows: flag 1, out has the plain solve's bits, the record is the reference's to the bit.  1e-160: Lambda is
+    # +inf and no walk is evaluated; 1e-153: Lambda is finite, the 2 x 2's determinant is not, the first objective stays in slot 26
+    for variant in (ofk.SOLVE_NODE, ofk.SOLVE_SIM):
+        pl = gpu_ctx.velocity_solve(variant, x, u, d=d, nrm=nrm, omega=om)
+        for prior in (1e-160, 1e-153):
+            out, rec = gpu_ctx.velocity_solve_plane(variant, x, u, d=d, sigma_normal=prior, **kw)
+            assert np.array_equal(bits(out), bits(pl)), (variant, prior)
+            for b in range(3):
+                ref = pr.plane_solve(variant, x[b], u[b], d[b], nrm[b], om[b], pr.SIGMA_FLOW, prior, v_s=pl[b, :3], rss_s=pl[b, 3], rank=pl[b, 4])
+                assert ref["flag"] == 1 and rec[b, 10] == 1 and rec[b, 11] == 65, (variant, prior, b, rec[b])
+                assert not rec[b, 4:6].any() and not rec[b, 12:26].any() and not rec[b, 27:].any(), (variant, prior, b, rec[b])
+                assert np.array_equal(bits(np.delete(rec[b], 26)), bits(np.delete(ref["rec"], 26))), (variant, prior, b, rec[b])
+                assert (rec[b, 26] == 0) if prior == 1e-160 else abs(rec[b, 26] - ref["rec"][26]) <= RSS_TOL * ref["rec"][26], (variant, prior, b, rec[b, 26])
+    # two points: rank 3 for v, a singular S with the tilt free (flag 2); three points are enough - against the reference
+    x8, u8, d8, nrm8, om8, _, _ = (np.stack([pr.scene(8, 6 + b)[k] for b in range(3)]) for k in range(7))
+    for count, want in ((2, 2), (3, 0)):
+        pl = gpu_ctx.velocity_solve(ofk.SOLVE_NODE, x8[:, :count], u8[:, :count], d=d8, nrm=nrm8, omega=om8)
+        out, rec = gpu_ctx.velocity_solve_plane(ofk.SOLVE_NODE, x8[:, :count], u8[:, :count], d=d8, nrm=nrm8, omega=om8, sigma_flow=pr.SIGMA_FLOW)
+        assert np.all(pl[:, 4] == 3)
+        for b in range(3):
+            ref = pr.plane_solve(pr.NODE, x8[b, :count], u8[b, :count], d8[b], nrm8[b], om8[b], pr.SIGMA_FLOW, np.inf, v_s=pl[b, :3], rss_s=pl[b, 3],
+                                 rank=pl[b, 4])
+            assert ref["flag"] == want and rec[b, 11] == count, (count, b, ref["flag"])
+            if want == 2:                                        # S is singular in every walk: which walk's rounding ends it is not pinned, the flag is
+                assert np.array_equal(bits(out[b]), bits(pl[b])), (b, rec[b, 12:14])
+            assert_plane_close(out[b, :3], out[b, 3], rec[b], ref, f"{count} points problem {b}")
     # held: the plain solve's bits
     plain_sim = gpu_ctx.velocity_solve(ofk.SOLVE_SIM, x, u, d=d, nrm=nrm, omega=om, t=om)
     out, rec = gpu_ctx.velocity_solve_plane(ofk.SOLVE_SIM, x, u, d=d, t=om, sigma_normal=0.0, **kw)

@@ -196,3 +196,83 @@ def test_rendered_pair_through_the_oracle_chain(pkg):
         print(f"seed {seed}: {m} points, exact gyro {exact:.4f}, plain {plain:.4f}, joint {joint:.4f}, flag {flag}, omega^ off by {dom:.2e}")
         assert flag == 0
         assert joint < plain / 2, (seed, plain, joint)
+
+
+# ---------------------------------------------------------------------------------------------------- a prior term that overflows
+OVERFLOWING = ((1e-160,) * 3, (1e-160, np.inf, 0.0))             # (d sigma_f)^2 / sigma^2 = 9e-8 / 1e-320 is +inf in f64
+FINITE_NEIGHBOUR = (1e-153,) * 3                                 # the prior term is 9e298: finite, and the variance 1e-306 still a normal f64
+
+
+@pytest.mark.parametrize("variant", (jr.NODE, jr.SIM))
+def test_a_prior_term_that_overflows_is_not_attempted(variant):
+    """ofk.h: flag 1 where "any joint sum or result is not finite".  joint_finish adds (d sigma_f)^2 / sigma_k^2 to S's diagonal and
+    ends, before the eigenvalues are formed, where an entry of S is not finite: flag 1, omega^ = omega0, the kept count and the
+    solve's fields before stay, slots 3-5 and 12-26 are 0.  A value just large enough for the term to stay finite is flag 0, delta
+    is of the order c / 9e298, and the stacked lstsq agrees (its columns scaled: beside prior rows of 3e149 lstsq's rank cut would
+    take v's columns for null)."""
+    import warnings
+    x, u, d, nrm, om0, v, om = jr.scene(65, 1065)
+    vs, rss, rank = jr.plain_solve(variant, x, u, d, nrm, om0)
+    for prior in OVERFLOWING:
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")
+            got = jr.joint_solve(variant, x, u, d, nrm, om0, jr.SIGMA_FLOW, prior)
+        rec = got["rec"]
+        assert got["flag"] == 1 and rec[10] == 1.0 and not got["rewritten"], prior
+        assert np.array_equal(got["v"], vs) and got["rss"] == rss and np.array_equal(got["omega"], om0)
+        assert np.array_equal(rec[0:3], om0) and np.array_equal(rec[6:9], vs) and rec[9] == rss and rec[11] == 65
+        assert not rec[3:6].any() and not rec[12:].any(), rec
+    got = jr.joint_solve(variant, x, u, d, nrm, om0, jr.SIGMA_FLOW, FINITE_NEIGHBOUR)
+    assert got["flag"] == 0 and got["rewritten"] and np.all(np.isfinite(got["rec"]))
+    assert np.all(got["rec"][12:15] > 1e298) and np.abs(got["rec"][3:6]).max() < 1e-290
+    vl, ol = jr.joint_lstsq(variant, x, u, d, nrm, om0, jr.SIGMA_FLOW, FINITE_NEIGHBOUR, scale_columns=True)
+    assert jr.rel_dev(got["v"], got["omega"], vl, ol) <= TOL
+    assert np.linalg.norm(got["v"] - vs) <= 1e-290                # ... which is the plain solve: the prior holds every axis
+
+
+def test_two_points():
+    """Two points: three independent rows for v (rank 3), but S is singular with every axis free - its eigenvalues about 3.8, 1e-15,
+    -3e-15: flag 2.  A prior of 1e-3 makes it a problem again."""
+    x, u, d, nrm, om0, v, om = jr.scene(8, 6)
+    vs, rss, rank = jr.plain_solve(jr.NODE, x[:2], u[:2], d, nrm, om0)
+    assert rank == 3
+    free = jr.joint_solve(jr.NODE, x[:2], u[:2], d, nrm, om0, jr.SIGMA_FLOW, jr.PRIORS["free"])
+    ls = free["rec"][12:15]
+    assert free["flag"] == 2 and free["rec"][11] == 2 and not free["rewritten"] and np.array_equal(free["v"], vs), free["rec"]
+    assert 3.0 < ls[0] < 5.0 and np.all(np.abs(ls[1:]) < 1e-13) and not free["rec"][3:6].any() and not free["rec"][15:].any()
+    prior = jr.joint_solve(jr.NODE, x[:2], u[:2], d, nrm, om0, jr.SIGMA_FLOW, jr.PRIORS["prior"])
+    assert prior["flag"] == 0 and prior["rewritten"]
+    vl, ol = jr.joint_lstsq(jr.NODE, x[:2], u[:2], d, nrm, om0, jr.SIGMA_FLOW, jr.PRIORS["prior"])
+    assert jr.rel_dev(prior["v"], prior["omega"], vl, ol) <= TOL
+
+
+def sensor_row(d, nrm, omega, scaling=1e-3, cx=640.0, cy=480.0):
+    """A sensor row (ofk.h) with the slots the resident references read."""
+    sr = np.zeros(32)
+    sr[0] = d; sr[1:4] = nrm; sr[4:7] = omega; sr[7:16] = np.eye(3).ravel(); sr[19] = scaling; sr[20] = cx; sr[21] = cy
+    return sr
+
+
+def pixel_points(x, u, sr):
+    """f32 pixel tracks whose scaled points are (close to) x, u."""
+    nxt = (x / sr[19] + [sr[20], sr[21]]).astype(np.float32)
+    prev = (nxt.astype(np.float64) - u / sr[19]).astype(np.float32)
+    return prev, nxt
+
+
+def test_pair_joint_behind_an_unsolved_step():
+    """solved=False (a stream step whose record[15] is 0): flag 1 in the header's layout whatever the points are, v / rss the record's
+    own - a step that did not solve leaves v = 0, rss = 0, rank 0 - and the same points with solved=True solve."""
+    x, u, d, nrm, om0, v, om = jr.scene(65, 1065)
+    sr = sensor_row(d, nrm, om0)
+    prev, nxt = pixel_points(x, u, sr)
+    status = np.ones(65, np.uint8); status[7::9] = 0
+    for rec in (np.zeros(16), np.concatenate([[0.01, -0.02, 0.003, 4e-7, 3.0], np.zeros(11)])):
+        got = jr.pair_joint(jr.NODE, prev, nxt, status, sr, 0.2, (1e-3,) * 3, rec, solved=False)
+        r = got["rec"]
+        assert got["flag"] == 1 and r[10] == 1.0 and not got["rewritten"]
+        assert np.array_equal(got["v"], rec[0:3]) and got["rss"] == rec[3] and np.array_equal(got["omega"], om0)
+        assert np.array_equal(r[0:3], om0) and np.array_equal(r[6:10], rec[0:4]) and r[11] == np.count_nonzero(status)
+        assert not r[3:6].any() and not r[12:].any()
+    on = jr.pair_joint(jr.NODE, prev, nxt, status, sr, 0.2, (1e-3,) * 3, rec, solved=True)
+    assert on["flag"] == 0 and on["rewritten"]

@@ -234,3 +234,73 @@ def test_rendered_pair_through_the_oracle_chain(pkg):
         print(f"seed {seed}: {m} points, true normal {exact:.4f}, plain {plain:.4f}, plane {plane:.4f}, flag {flag}, n^ off by {dn:.2f} deg")
         assert flag == 0
         assert plane < plain, (seed, plain, plane)
+
+
+# ---------------------------------------------------------------------------------------------------- a prior term that overflows
+OVERFLOWING = 1e-160                                             # Lambda = (d0^2 sigma_f / sigma_normal)^2 = (4.5e156)^2 is +inf in f64
+DETERMINANT_OVERFLOWS = 1e-153                                   # Lambda = 2e299 is finite, S's determinant in plane_sym2 is not
+FINITE_NEIGHBOUR = 1e-80                                         # Lambda = 2e153: the smallest decade at which S's determinant stays finite
+
+
+@pytest.mark.parametrize("variant", (pr.NODE, pr.SIM))
+def test_a_prior_term_that_overflows_is_not_attempted(variant):
+    """ofk.h: flag 1 where "any sum or result is not finite".  plane_finish takes Lambda among its inputs: where it is not finite no
+    walk is evaluated - flag 1, n0 and d0 in slots 0-3, the kept count and the solve's fields before, everything from slot 12 on 0
+    (the first objective too: it was never formed).  No OverflowError.  Where Lambda is finite and the closed-form 2 x 2 overflows
+    (l2 = (S00 S11 - S01^2) / l1) the first walk has been evaluated: flag 1 with the first objective in slot 26.  At 1e-80 every
+    intermediate is finite: the tilt is held by the prior, v stays the solve's, the Gauss-Newton on stacked lstsq agrees.  There the
+    final objective equals the first walk's up to the rounding of a = sB (m.p) against sA, so flag 3's comparison is a tie broken by
+    rounding: SIM ends in flag 0, NODE in flag 3 - neither is flag 1."""
+    import warnings
+    x, u, d0, n0, om, v, mt = pr.scene(65, 1065)
+    vs, rss, rank = pr.plain_solve(variant, x, u, d0, n0, om)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        got = pr.plane_solve(variant, x, u, d0, n0, om, pr.SIGMA_FLOW, OVERFLOWING)
+        mid = pr.plane_solve(variant, x, u, d0, n0, om, pr.SIGMA_FLOW, DETERMINANT_OVERFLOWS)
+    for g in (got, mid):
+        rec = g["rec"]
+        assert g["flag"] == 1 and rec[10] == 1.0 and not g["rewritten"]
+        assert np.array_equal(g["v"], vs) and g["rss"] == rss
+        assert np.array_equal(rec[0:3], n0) and rec[3] == d0 and np.array_equal(rec[6:9], vs) and rec[9] == rss and rec[11] == 65
+        assert not rec[4:6].any() and not rec[12:26].any() and not rec[27:].any(), rec
+    assert got["rec"][26] == 0 and mid["rec"][26] > 0
+    near = pr.plane_solve(variant, x, u, d0, n0, om, pr.SIGMA_FLOW, FINITE_NEIGHBOUR)
+    assert near["flag"] == (0 if variant == pr.SIM else 3), near["flag"]
+    assert np.all(near["rec"][12:14] > 1e150) and np.all(np.isfinite(near["rec"]))
+    assert abs(near["rec"][27] - near["rec"][26]) <= 4 * pr.EPS * near["rec"][26]          # the tie
+    if near["flag"] == 0:
+        vl, ml = pr.plane_lstsq(variant, x, u, d0, n0, om, pr.SIGMA_FLOW, FINITE_NEIGHBOUR, vs)
+        assert pr.rel_dev(near["v"], near["m"], vl, ml) <= TOL
+        assert np.linalg.norm(near["v"] - vs) <= 1e-14 * np.linalg.norm(vs) and np.abs(near["rec"][4:6]).max() < 1e-140
+
+
+def test_two_points():
+    """Two points: rank 3 for v, but with the tilt free the five unknowns have a singular S (eigenvalues 2e-3 and 0): flag 2.  Three
+    points are enough."""
+    x, u, d0, n0, om, v, mt = pr.scene(8, 6)
+    vs, rss, rank = pr.plain_solve(pr.NODE, x[:2], u[:2], d0, n0, om)
+    assert rank == 3
+    two = pr.plane_solve(pr.NODE, x[:2], u[:2], d0, n0, om, pr.SIGMA_FLOW, pr.PRIORS["free"])
+    assert two["flag"] == 2 and two["rec"][11] == 2 and not two["rewritten"] and np.array_equal(two["v"], vs)
+    assert two["rec"][12] > 0 and two["rec"][13] <= 1e-13 * two["rec"][12] and not two["rec"][4:6].any() and not two["rec"][14:26].any()
+    three = pr.plane_solve(pr.NODE, x[:3], u[:3], d0, n0, om, pr.SIGMA_FLOW, pr.PRIORS["free"])
+    assert three["flag"] == 0 and three["rewritten"]
+
+
+def test_pair_plane_behind_an_unsolved_step():
+    """solved=False (a stream step whose record[15] is 0): flag 1 in the header's layout, v / rss the record's own; the same points
+    with solved=True solve."""
+    from test_joint_reference import pixel_points, sensor_row
+    x, u, d0, n0, om, v, mt = pr.scene(65, 1065)
+    sr = sensor_row(d0, n0, om)
+    prev, nxt = pixel_points(x, u, sr)
+    status = np.ones(65, np.uint8); status[7::9] = 0
+    for rec in (np.zeros(16), np.concatenate([[0.01, -0.02, 0.003, 4e-7, 3.0], np.zeros(11)])):
+        got = pr.pair_plane(pr.NODE, prev, nxt, status, sr, 0.2, 0.2, rec, solved=False)
+        r = got["rec"]
+        assert got["flag"] == 1 and r[10] == 1.0 and not got["rewritten"] and np.array_equal(got["v"], rec[0:3]) and got["rss"] == rec[3]
+        assert np.array_equal(r[0:3], n0) and r[3] == d0 and np.array_equal(r[6:10], rec[0:4]) and r[11] == np.count_nonzero(status)
+        assert not r[4:6].any() and not r[12:].any()
+    on = pr.pair_plane(pr.NODE, prev, nxt, status, sr, 0.2, 0.2, rec, solved=True)
+    assert on["flag"] == 0 and on["rewritten"]
