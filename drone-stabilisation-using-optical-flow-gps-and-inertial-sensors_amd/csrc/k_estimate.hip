@@ -1291,6 +1291,9 @@ void ofk_launch_associate(hipStream_t s, const double *t_img, int n_img, int n_i
 // ------------------------------------------------------------------------------------------------ joint velocity and rotation solve
 #include "k_joint.inc"
 
+// ------------------------------------------------------------------------------------------------ gyro bias of a stream
+#include "k_bias.inc"
+
 // ------------------------------------------------------------------------------------------------ plane solve
 #include "k_plane.inc"
 

@@ -125,8 +125,9 @@ __device__ bool joint_finish(const double *s, bool usable, const double *vs, con
 
 // The two walks: terms(i, x, y, ux, uy, w) -> point i enters (the set the solve used).  Returns, in every thread, whether the record is
 // to be rewritten; then v, omh and rss (thread 0's alone is the sum) hold the joint solution and its residual sum of squares.
-// bc: 8 doubles of LDS.  jr: the problem's joint record, written by thread 0.
-template <int NW, class Terms>
+// bc: 8 doubles of LDS.  jr: the problem's joint record, written by thread 0.  RSS false (k_bias.inc): the sums and the record alone, no
+// second walk, rss stays 0.
+template <int NW, bool RSS = true, class Terms>
 __device__ __forceinline__ bool joint_core(double (*part)[JOINT_SUMS], double *bc, int n, int variant, const double *nrm, const double *om,
                                            double d, const double *vs, const double *rec03, bool usable, double dsf2, const double *ovar,
                                            double *jr, double *v, double *omh, double &rss, Terms terms)
@@ -157,6 +158,7 @@ __device__ __forceinline__ bool joint_core(double (*part)[JOINT_SUMS], double *b
     const bool rw = bc[6] != 0.0;
     rss = 0.0;
     if (!rw) return false;
+    if (!RSS) return true;
 #pragma unroll 1
     for (int vw = wave; vw < 4; vw += NW) {
         double r = 0.0;

@@ -151,6 +151,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->gate = ofk_track_gate{OFK_FB_OFF, 0.5, -1, 0.0};
     c->cov = ofk_cov{OFK_COV_OFF, 0.0, 0.0, 0.0, {0.0, 0.0, 0.0}, 0.0, 0.0, 0, 0, 0.0, 0.0};
     c->joint = ofk_joint{OFK_JOINT_OFF, 0.2, {INFINITY, INFINITY, INFINITY}, 0};
+    c->bias = ofk_gyro_bias{OFK_BIAS_OFF, 0.2, 0.0, 0.0, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, 0.0, 1};
     c->plane = ofk_plane{OFK_PLANE_OFF, 0.2, INFINITY, 0.1, {0.0, 0.0, 1.0}, 6};
     c->epi = ofk_epipolar{OFK_EPI_OFF, INFINITY, 5, 0.008, {0.0, 0.0, 1.0}, OFK_EPI_W_ONE};
     c->zones = ofk_zones{OFK_ZONES_OFF, 48, 3, 20, 30, OFK_ZONE_MAX};
@@ -209,7 +210,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     for (int k = 0; k < 2; ++k) { if (c->bgr[k]) hipFree(c->bgr[k]); if (c->pyr[k]) hipFree(c->pyr[k]); }
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
-                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec, c->joint_rec, c->plane_rec, c->epi_rec,
+                    c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec, c->joint_rec, c->bias_rec, c->plane_rec, c->epi_rec,
                     c->zone_tab, c->pts_prev_u};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
@@ -1178,6 +1179,95 @@ extern "C" int ofk_set_epipolar(ofk_ctx *c, const ofk_epipolar *v)
 }
 extern "C" int ofk_get_epipolar(const ofk_ctx *c, ofk_epipolar *v) { return setting_get(c, &ofk_ctx::epi, v); }
 
+// ------------------------------------------------------------------------------------------------ gyro bias setting
+static int check_bias(ofk_ctx *c, const ofk_gyro_bias *v, const char *who)
+{
+    if (v->mode != OFK_BIAS_OFF && v->mode != OFK_BIAS_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_BIAS_OFF nor OFK_BIAS_ON", who, v->mode);
+    if (!(std::isfinite(v->sigma_flow) && v->sigma_flow > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: sigma_flow %g is not finite or not positive", who, v->sigma_flow);
+    if (!(std::isfinite(v->sigma_gyro) && v->sigma_gyro >= 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: sigma_gyro %g is not finite or negative", who, v->sigma_gyro);
+    if (!(std::isfinite(v->q) && v->q >= 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: q %g is not finite or negative", who, v->q);
+    if (!(std::isfinite(v->nis_max) && v->nis_max >= 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: nis_max %g is not finite or negative", who, v->nis_max);
+    for (int k = 0; k < 3; ++k) {
+        if (!(std::isfinite(v->p0[k]) && v->p0[k] >= 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: p0[%d] is not finite or negative (%g)", who, k, v->p0[k]);
+        if (!std::isfinite(v->b0[k])) return ofk_fail(c, OFK_E_INVALID, "%s: b0[%d] is not finite (%g)", who, k, v->b0[k]);
+    }
+    if (v->update != 0 && v->update != 1) return ofk_fail(c, OFK_E_INVALID, "%s: update is 0 or 1", who);
+    return OFK_OK;
+}
+
+static bool bias_on(const ofk_ctx *c) { return c->bias.mode != OFK_BIAS_OFF; }
+static bool bias_estimates(const ofk_gyro_bias &g) { return g.update && (g.p0[0] > 0.0 || g.p0[1] > 0.0 || g.p0[2] > 0.0); }
+
+extern "C" int ofk_set_gyro_bias(ofk_ctx *c, const ofk_gyro_bias *v)
+{
+    TRY(setting_set(c, &ofk_ctx::bias, v && v->mode == OFK_BIAS_OFF ? nullptr : v, [](ofk_gyro_bias &s) { s.mode = OFK_BIAS_OFF; },
+                    [c](const ofk_gyro_bias *x) { return check_bias(c, x, "ofk_set_gyro_bias"); }));
+    c->bias_fresh = 1; c->bias_batch = 0;                        // the state is (b0, diag(p0^2)) again, set when a step or a reset first needs it
+    return OFK_OK;
+}
+extern "C" int ofk_get_gyro_bias(const ofk_ctx *c, ofk_gyro_bias *v) { return setting_get(c, &ofk_ctx::bias, v); }
+
+// one stream's state from a setting: b0, diag(p0^2), everything else 0
+static void bias_state_of(const ofk_gyro_bias &g, double *r)
+{
+    for (int k = 0; k < OFK_BIAS_DOUBLES; ++k) r[k] = 0.0;
+    for (int k = 0; k < 3; ++k) r[k] = g.b0[k];
+    r[3] = g.p0[0] * g.p0[0]; r[6] = g.p0[1] * g.p0[1]; r[8] = g.p0[2] * g.p0[2];
+}
+
+// the streams' rows, allocated on first use, and the state of the setting where it is still to be set
+static int bias_prepare(ofk_ctx *c)
+{
+    if (!c->bias_rec) { OFK_HIP(c, hipMalloc((void **)&c->bias_rec, (size_t)c->max_batch * OFK_BIAS_DOUBLES * 8)); c->bias_fresh = 1; }
+    if (!c->bias_fresh) return OFK_OK;
+    double row[OFK_BIAS_DOUBLES];
+    bias_state_of(c->bias, row);
+    for (int b = 0; b < c->max_batch; ++b)
+        OFK_HIP(c, hipMemcpyAsync(c->bias_rec + (size_t)b * OFK_BIAS_DOUBLES, row, sizeof row, hipMemcpyHostToDevice, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    c->bias_fresh = 0;
+    return OFK_OK;
+}
+
+extern "C" int ofk_gyro_bias_reset(ofk_ctx *c, const double *state, int batch)
+{
+    if (!c || !state || batch < 1 || batch > c->max_batch) return ofk_fail(c, OFK_E_INVALID, "ofk_gyro_bias_reset: bad argument");
+    if (!bias_on(c)) return ofk_fail(c, OFK_E_INVALID, "ofk_gyro_bias_reset: ofk_set_gyro_bias is off");
+    for (size_t k = 0; k < (size_t)batch * 9; ++k)
+        if (!std::isfinite(state[k])) return ofk_fail(c, OFK_E_INVALID, "ofk_gyro_bias_reset: a state value is not finite");
+    TRY(enter(c));
+    TRY(bias_prepare(c));
+    double *rows = (double *)calloc((size_t)batch * OFK_BIAS_DOUBLES, 8);
+    if (!rows) return ofk_fail(c, OFK_E_INVALID, "out of host memory");
+    for (int b = 0; b < batch; ++b) memcpy(rows + (size_t)b * OFK_BIAS_DOUBLES, state + (size_t)b * 9, 9 * 8);
+    const hipError_t e = hipMemcpy(c->bias_rec, rows, (size_t)batch * OFK_BIAS_DOUBLES * 8, hipMemcpyHostToDevice);
+    free(rows);
+    OFK_HIP(c, e);
+    return OFK_OK;
+}
+
+extern "C" int ofk_gyro_bias_download(ofk_ctx *c, double *rec)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->bias_batch < 1 || !c->bias_rec) return ofk_fail(c, OFK_E_INVALID, "ofk_gyro_bias_download: no step with ofk_set_gyro_bias on yet");
+    if (!rec) return ofk_fail(c, OFK_E_INVALID, "ofk_gyro_bias_download: NULL buffer");
+    TRY(enter(c));
+    OFK_HIP(c, hipMemcpyAsync(rec, c->bias_rec, (size_t)c->bias_batch * OFK_BIAS_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+// The steps' own refusals with the setting on and updating (ofk.h), then the rows; fu: a fused step's.
+static int bias_check_step(ofk_ctx *c, int B, int variant, const ofk_fusion *fu, const char *who)
+{
+    if (!bias_on(c)) return OFK_OK;
+    if (c->bias.update && (variant == OFK_SOLVE_OFMODULE || (fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY))))
+        return refuse_not_sensor_model(c, who, NO_OFMODULE | NO_ROTATIONAL | NO_LEGACY, "gyro bias update", "ofk_set_gyro_bias");
+    TRY(bias_prepare(c));
+    c->bias_batch = B;
+    return OFK_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ the second-stage settings
 // One row per setting whose kernel runs behind the velocity solve, in the order of their checks and launches.  No two run together:
 // a row refuses every earlier row that is on.
@@ -1283,6 +1373,13 @@ static void solve_pairs(ofk_ctx *c, hipStream_t st, const float *pts_prev, const
     else
         ofk_launch_pairs_solve(st, pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T,
                                cand_count, records, nb);
+    if (stream && bias_on(c) && bias_estimates(c->bias)) {       // the gyro bias's filter step: the record still holds the solve's own v
+        static const ofk_fusion none = {};
+        const ofk_stream_in bin = {pts_prev, pts_next, status, counts, c->max_pts, sensors, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, &none,
+                                   p->solve_variant, records, nullptr, nb, 0};
+        ofk_launch_stream_bias(st, bin, 0, p->use_feasibility, p->feas_T, rob ? c->rob_w + o : nullptr, &c->bias,
+                               c->bias_rec + (size_t)b0 * OFK_BIAS_DOUBLES);
+    }
     const ofk_pairs_in in = {pts_prev, pts_next, status, counts, c->max_pts, sensors, p->solve_variant, p->use_feasibility, p->feas_T, records, nb};
     for (const second_setting &s : SECOND) if (s.mode(c)) s.pairs(c, st, in, rob ? c->rob_w + o : nullptr, b0);
 }
@@ -1493,11 +1590,13 @@ extern "C" int ofk_velocity_solve_robust(ofk_ctx *c, int variant, const double *
 // The four second-stage stage entries: the plain or robust solve, the setting's kernel behind it.  what: what the kernel adds; have:
 // the entry's own pointers are there; wgt: refused unless NULL (the entries that ignore theirs pass NULL); check: the setting's own
 // check, the mode it needs included; points: the epipolar [batch][n][4], or NULL; launch(in, weights, out, rec, points) on the device.
-template <class Check, class Launch>
-static int solve_second_impl(ofk_ctx *c, const char *who, const char *what, bool have, int variant, const double *x, const double *u,
-                             const uint8_t *valid, int batch, int n, const double *d, const double *nrm, const double *omega, const double *t,
-                             const double *wgt, const ofk_robust *r, Check check, const char *kernel, Launch launch, double *out, double *rec,
-                             int rec_doubles, double *points)
+// rec_in: the record's rows are uploaded from it (the gyro bias's state), NULL: they are the kernel's to write; before(omega, rec) on
+// the device arrays in front of the solve.
+template <class Check, class Before, class Launch>
+static int solve_second_chain(ofk_ctx *c, const char *who, const char *what, bool have, int variant, const double *x, const double *u,
+                              const uint8_t *valid, int batch, int n, const double *d, const double *nrm, const double *omega, const double *t,
+                              const double *wgt, const ofk_robust *r, Check check, const double *rec_in, Before before, const char *kernel,
+                              Launch launch, double *out, double *rec, int rec_doubles, double *points)
 {
     if (!c || !x || !u || !nrm || !out || !have || batch < 1 || n < 1 || n > 4096 || variant < 0 || variant > 2)
         return ofk_fail(c, OFK_E_INVALID, "%s: bad argument", who);
@@ -1513,15 +1612,17 @@ static int solve_second_impl(ofk_ctx *c, const char *who, const char *what, bool
     double *dx = bp.put(x, pb), *du = bp.put(u, pb);
     uint8_t *dval = (uint8_t *)bp.put(valid, (size_t)batch * n);
     double *dd = bp.put(d, batch * 8), *dn = bp.put(nrm, batch * 24), *dom = bp.put(omega, batch * 24), *dt = bp.put(t, batch * 24),
-           *dout = bp.take(ob), *drec = bp.take(rb), *dpt = points ? bp.take(4 * wb) : nullptr, *dwts = nullptr;
+           *dout = bp.take(ob), *drec = rec_in ? bp.put(rec_in, rb) : bp.take(rb), *dpt = points ? bp.take(4 * wb) : nullptr, *dwts = nullptr;
     if (rob) {
         double *dwork = bp.take(7 * wb);
         dwts = bp.take(wb);
         double *dtmp = bp.take(wb), *dst = bp.take((size_t)batch * OFK_ROBUST_DOUBLES * 8);
         if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+        before(dom, drec);
         ofk_launch_solve_robust(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, r, dwork, dwts, dtmp, dst, dout);
     } else {
         if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+        before(dom, drec);
         ofk_launch_solve(c->stream, variant, dx, du, dval, batch, n, dd, dn, dom, dt, nullptr, dout);
     }
     launch(ofk_stage_in{variant, dx, du, dval, batch, n, dd, dn, dom, dt}, dwts, dout, drec, dpt);
@@ -1529,6 +1630,16 @@ static int solve_second_impl(ofk_ctx *c, const char *who, const char *what, bool
     TRY(get(c, rec, drec, rb));
     if (points) TRY(get(c, points, dpt, 4 * wb));
     return get(c, out, dout, ob);
+}
+
+template <class Check, class Launch>
+static int solve_second_impl(ofk_ctx *c, const char *who, const char *what, bool have, int variant, const double *x, const double *u,
+                             const uint8_t *valid, int batch, int n, const double *d, const double *nrm, const double *omega, const double *t,
+                             const double *wgt, const ofk_robust *r, Check check, const char *kernel, Launch launch, double *out, double *rec,
+                             int rec_doubles, double *points)
+{
+    return solve_second_chain(c, who, what, have, variant, x, u, valid, batch, n, d, nrm, omega, t, wgt, r, check, nullptr, [](double *, double *) {},
+                              kernel, launch, out, rec, rec_doubles, points);
 }
 
 extern "C" int ofk_velocity_solve_cov(ofk_ctx *c, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
@@ -1559,6 +1670,24 @@ extern "C" int ofk_velocity_solve_joint(ofk_ctx *c, int variant, const double *x
     }, "k_joint_solve", [&](const ofk_stage_in &in, const double *w, double *dout, double *drec, double *) {
         ofk_launch_joint_solve(c->stream, in, w, jv, dout, drec);
     }, out, joint, OFK_JOINT_DOUBLES, nullptr);
+}
+
+// One step of the gyro bias without images: the shared chain with the apply kernel in front of the solve and the state uploaded where
+// the other entries take their record's rows.
+extern "C" int ofk_gyro_bias_step(ofk_ctx *c, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                                  const double *d, const double *nrm, const double *omega_raw, const double *wgt, const ofk_robust *r,
+                                  const ofk_gyro_bias *g, double *state, double *out)
+{
+    const char *who = "ofk_gyro_bias_step";
+    return solve_second_chain(c, who, "gyro bias", g && state, variant, x, u, valid, batch, n, d, nrm, omega_raw, nullptr, wgt, r, [&] {
+        TRY(check_bias(c, g, who));
+        if (g->mode != OFK_BIAS_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode must be OFK_BIAS_ON", who);
+        return (int)OFK_OK;
+    }, state, [&](double *dom, double *drec) {
+        ofk_launch_gyro_bias_apply(c->stream, dom, 3, nullptr, drec, batch, 0);
+    }, "k_bias_solve", [&](const ofk_stage_in &in, const double *w, double *dout, double *drec, double *) {
+        if (bias_estimates(*g)) ofk_launch_bias_solve(c->stream, in, w, g, dout, drec);
+    }, out, state, OFK_BIAS_DOUBLES, nullptr);
 }
 
 extern "C" int ofk_velocity_solve_plane(ofk_ctx *c, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
@@ -2310,6 +2439,7 @@ static int stream_begin_impl(ofk_ctx *c, const uint8_t *first_bgr, int batch, in
     TRY(grid_prepare(c, c->grid, batch, h, w, "ofk_stream_begin"));
     TRY(stream_alloc(c));
     if (c->zone_tab) TRY(zones_clear(c, c->max_batch));          // new streams start without zones (a table that was never used is clear)
+    c->bias_fresh = 1; c->bias_batch = 0;                        // ... and with the gyro bias of the setting
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     TRY(stream_ingest(c, 0, first_bgr, batch, h, w, lv));
     TRY(stream_detect(c, nullptr, nullptr, batch, h, w, p, c->pts_prev, c->counts));
@@ -2468,6 +2598,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     TRY(check_grid(c, &c->grid, h, w, "ofk_stream_step"));
     TRY(fm_check_step(c, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     TRY(second_prepare(c, B, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
+    TRY(bias_check_step(c, B, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     const int defer = second_on(c) && fu && fu->filter ? 1 : 0;   // the second-stage kernel corrects
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
@@ -2476,6 +2607,13 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     if (zones_on) { TRY(check_zones(c, &c->zones, "ofk_stream_step")); TRY(zones_alloc(c)); }
     TRY(solve_points_prepare(c, B));
     OFK_HIP(c, hipMemcpyAsync(c->sensors, sensors, (size_t)B * OFK_SENSOR_DOUBLES * 8, hipMemcpyHostToDevice, c->stream));
+    double *const bias_ist = bias_on(c) && fu && fu->use_imu ? c->imu_state : nullptr;
+    if (bias_on(c)) ofk_launch_gyro_bias_apply(c->stream, c->sensors + 4, OFK_SENSOR_DOUBLES, bias_ist, c->bias_rec, B, 0);   // everything below reads omega - b^
+    struct bias_restore {                                        // a step that ends early still puts the IMU state's raw omega back
+        ofk_ctx *c; double *ist; int B;
+        void now() { if (ist) ofk_launch_gyro_bias_apply(c->stream, nullptr, 0, ist, c->bias_rec, B, 1); ist = nullptr; }
+        ~bias_restore() { now(); }
+    } restore = {c, bias_ist, B};
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
     if (fu && fu->redetect_replace && few) {
@@ -2504,6 +2642,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
                                           c->rob_stats);
         else
             ofk_launch_stream_fuse(c->stream, in, c->imu_dv, p->use_feasibility, p->feas_T);
+        if (bias_on(c) && bias_estimates(c->bias)) ofk_launch_stream_bias(c->stream, in, 1, 0, 0.0, rob ? c->rob_w : nullptr, &c->bias, c->bias_rec);
         for (const second_setting &s : SECOND) if (s.mode(c)) s.stream(c, in, rob ? c->rob_w : nullptr);
     } else
         solve_pairs(c, c->stream, v.solve_prev, v.solve_next, c->status, c->counts, c->sensors, p, nullptr, c->records, 0, B, true);
@@ -2538,6 +2677,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     if (!hold)
         ofk_launch_update_tracks(c->stream, c->pts_next, c->status, c->counts, c->max_pts, any ? c->pts_new : nullptr, any ? c->new_counts : nullptr,
                                  c->pts_prev, c->counts, p->max_corners, B);
+    restore.now();                                               // the step's last launch: the IMU state's raw omega back, bit for bit
     TRY(check_launch(c, "ofk_stream_step"));
     if (records) OFK_HIP(c, hipMemcpyAsync(records, c->records, (size_t)B * OFK_RECORD_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
     if (fu && fused) OFK_HIP(c, hipMemcpyAsync(fused, c->fused, (size_t)B * 64, hipMemcpyDeviceToHost, c->stream));

@@ -98,6 +98,8 @@ struct ofk_ctx {
     double *cov_rec; int cov_batch;          // [B][OFK_COV_DOUBLES] (lazily allocated); problems of the latest run / step with it on, 0 = none
     ofk_joint joint;                         // ofk_set_joint: mode OFK_JOINT_OFF unless set
     double *joint_rec; int joint_batch;      // [B][OFK_JOINT_DOUBLES] (lazily allocated); problems of the latest run / step with it on, 0 = none
+    ofk_gyro_bias bias;                      // ofk_set_gyro_bias: mode OFK_BIAS_OFF unless set
+    double *bias_rec; int bias_batch, bias_fresh;   // [B][OFK_BIAS_DOUBLES] state and record (lazily allocated); streams of the latest step with it on, 0 = none; the state is still to be set from the setting
     ofk_plane plane;                         // ofk_set_plane: mode OFK_PLANE_OFF unless set
     double *plane_rec; int plane_batch;      // [B][OFK_PLANE_DOUBLES] (lazily allocated); problems of the latest run / step with it on, 0 = none
     ofk_epipolar epi;                        // ofk_set_epipolar: mode OFK_EPI_OFF unless set
@@ -252,6 +254,12 @@ void ofk_launch_stream_cov(hipStream_t s, const ofk_stream_in &in, const double 
 void ofk_launch_stream_joint(hipStream_t s, const ofk_stream_in &in, const double *weights, const ofk_joint *j, double *joint);
 void ofk_launch_stream_plane(hipStream_t s, const ofk_stream_in &in, const double *weights, const ofk_plane *p, double *plane);
 void ofk_launch_stream_epi(hipStream_t s, const ofk_stream_in &in, const double *weights, const ofk_epipolar *e, double *epi, double *pts);
+// the gyro bias (ofk.h: ofk_set_gyro_bias; k_bias.inc): apply / restore on `batch` omegas `stride` doubles apart, the filter step behind a
+// stream step's solve kernel (fused: k_stream_fuse[_robust] ran, else the plain step's) and behind a stage entry's
+void ofk_launch_gyro_bias_apply(hipStream_t s, double *omega, int stride, double *imu_state, double *bias, int batch, int restore);
+void ofk_launch_stream_bias(hipStream_t s, const ofk_stream_in &in, int fused, int use_feas, double feas_T, const double *weights,
+                            const ofk_gyro_bias *g, double *bias);
+void ofk_launch_bias_solve(hipStream_t s, const ofk_stage_in &in, const double *weights, const ofk_gyro_bias *g, const double *out, double *bias);
 void ofk_launch_kf_records_cov(hipStream_t s, int ns, int nm, const double *mats, double *x, double *P, const double *records, double *cov,
                                const ofk_cov *c, double z_sign, int z_source, int batch);
 void ofk_launch_records_f32(hipStream_t s, const double *records, float *dst, int batch);

@@ -30,6 +30,7 @@ SYMBOLS = (
     "ofk_set_robust", "ofk_get_robust", "ofk_robust_download", "ofk_velocity_solve_robust", "ofk_robust_pairs",
     "ofk_set_cov", "ofk_get_cov", "ofk_cov_download", "ofk_velocity_solve_cov",
     "ofk_set_joint", "ofk_get_joint", "ofk_joint_download", "ofk_velocity_solve_joint",
+    "ofk_set_gyro_bias", "ofk_get_gyro_bias", "ofk_gyro_bias_reset", "ofk_gyro_bias_download", "ofk_gyro_bias_step",
     "ofk_set_plane", "ofk_get_plane", "ofk_plane_download", "ofk_velocity_solve_plane",
     "ofk_set_epipolar", "ofk_get_epipolar", "ofk_epipolar_download", "ofk_epipolar_points_download", "ofk_velocity_solve_epipolar",
     "ofk_set_track_gate", "ofk_get_track_gate", "ofk_track_gate_download", "ofk_lk_pyr_fb",
@@ -73,6 +74,8 @@ COV_MODES = {"off": COV_OFF, "propagate": COV_PROPAGATE, "residual": COV_RESIDUA
 COV_DOUBLES = 24
 JOINT_OFF, JOINT_ON = 0, 1                               # ofk_set_joint / ofk_velocity_solve_joint
 JOINT_DOUBLES = 32
+BIAS_OFF, BIAS_ON = 0, 1                                 # ofk_set_gyro_bias / ofk_gyro_bias_step
+BIAS_DOUBLES = 32
 PLANE_OFF, PLANE_ON = 0, 1                               # ofk_set_plane / ofk_velocity_solve_plane
 PLANE_DOUBLES = 32
 EPI_OFF, EPI_ON = 0, 1                                   # ofk_set_epipolar / ofk_velocity_solve_epipolar
@@ -157,6 +160,21 @@ def joint_setting(mode=True, sigma_flow=0.2, sigma_omega=None, omega_from_imu=Fa
     the resident paths); sigma_omega None = every axis free (+inf), a scalar or three values (+inf: free, 0: held)."""
     so = np.broadcast_to(np.asarray(np.inf if sigma_omega is None else sigma_omega, np.float64), (3,))
     return Joint(int(mode), float(sigma_flow), (C.c_double * 3)(*so.tolist()), int(bool(omega_from_imu)))
+
+
+class GyroBias(C.Structure):
+    """ofk_gyro_bias (include/ofk.h): the setting of a stream's gyro bias."""
+    _fields_ = [("mode", C.c_int), ("sigma_flow", C.c_double), ("sigma_gyro", C.c_double), ("q", C.c_double), ("p0", C.c_double * 3),
+                ("b0", C.c_double * 3), ("nis_max", C.c_double), ("update", C.c_int)]
+
+
+def gyro_bias_setting(mode=True, sigma_flow=0.2, sigma_gyro=0.0, q=1e-12, p0=1e-2, b0=0.0, nis_max=0.0, update=True):
+    """A GyroBias structure from names: mode True / False (or BIAS_*); sigma_flow in the units of the points the entry takes (pixels in
+    the stream steps); sigma_gyro, p0 and b0 in rad per frame interval, q their variance per step; p0 and b0 a scalar or three values
+    (p0 0: the axis is held at b0); nis_max 0 = no gate; update False applies b0 and never changes it."""
+    p = np.broadcast_to(np.asarray(p0, np.float64), (3,)); b = np.broadcast_to(np.asarray(b0, np.float64), (3,))
+    return GyroBias(int(mode), float(sigma_flow), float(sigma_gyro), float(q), (C.c_double * 3)(*p.tolist()), (C.c_double * 3)(*b.tolist()),
+                    float(nis_max), int(bool(update)))
 
 
 class Plane(C.Structure):
@@ -374,7 +392,7 @@ class Fusion(C.Structure):
 
 
 # the struct settings: ofk_set_<name> / ofk_get_<name> take the context and a pointer to the struct
-SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate),
+SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("gyro_bias", GyroBias), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate),
             ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion))
 
 _lib = None
@@ -448,6 +466,8 @@ def load_library():
         L.ofk_joint_download.argtypes = [vp, vp]
         L.ofk_velocity_solve_joint.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Joint), vp, vp]
         L.ofk_velocity_solve_cov.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Cov), vp, vp]
+        L.ofk_gyro_bias_reset.argtypes = [vp, vp, i]; L.ofk_gyro_bias_download.argtypes = [vp, vp]
+        L.ofk_gyro_bias_step.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(GyroBias), vp, vp]
         L.ofk_plane_download.argtypes = [vp, vp]
         L.ofk_velocity_solve_plane.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, C.POINTER(Robust), C.POINTER(Plane), vp, vp]
         L.ofk_epipolar_download.argtypes = [vp, vp]; L.ofk_epipolar_points_download.argtypes = [vp, vp]
@@ -1171,6 +1191,54 @@ class Context:
     def joint_download(self, batch):
         """joint [batch, 32] of the latest run / step with the setting on."""
         return self._records_download("joint", batch, JOINT_DOUBLES)
+
+    def set_gyro_bias(self, gyro_bias=None, **settings):
+        """ofk_set_gyro_bias: a GyroBias (or gyro_bias_setting's keywords); None or mode False switches it off.  Every later stream step
+        takes the stream's bias out of omega in front of everything and, with update on, filters it from the flow."""
+        self._set_struct(self._L.ofk_set_gyro_bias, gyro_bias, settings, gyro_bias_setting, lock=False)
+
+    def get_gyro_bias(self):
+        return self._get_struct(self._L.ofk_get_gyro_bias, GyroBias)
+
+    def gyro_bias_reset(self, state):
+        """ofk_gyro_bias_reset: state [batch, 9] = b (3), P upper triangle (6), loaded into the first `batch` streams."""
+        state = _arr(np.atleast_2d(np.asarray(state, np.float64)), np.float64)
+        if state.ndim != 2 or state.shape[1] != 9:
+            raise ValueError(f"gyro_bias_reset: state {state.shape} must be [batch, 9]")
+        with self._lock:
+            self._ck(self._L.ofk_gyro_bias_reset(self._h, _p(state), state.shape[0]))
+
+    def gyro_bias_download(self, batch):
+        """bias [batch, 32] of the latest stream step with the setting on."""
+        return self._records_download("gyro_bias", batch, BIAS_DOUBLES)
+
+    def gyro_bias_step(self, variant, x, u, d=None, nrm=None, omega=None, state=None, valid=None, robust=None, gyro_bias=None, **settings):
+        """ofk_gyro_bias_step: velocity_solve's arguments (NODE or SIM; omega the raw gyro), an optional Robust, the setting (a GyroBias, or
+        gyro_bias_setting's keywords) and state [B,32] (None: the setting's own start).  Returns out [B,8], state [B,32] after the step
+        (single problem: [8], [32])."""
+        gv = gyro_bias if gyro_bias is not None else gyro_bias_setting(**settings)
+        x = _arr(x, np.float64); u = _arr(u, np.float64)
+        if u.shape[:-1] != x.shape[:-1] or x.shape[-1] != 2 or u.shape[-1] < 2:
+            raise ValueError(f"gyro_bias_step: x {x.shape} must be [..., n, 2] and u {u.shape} [..., n, >=2] over the same points")
+        single = x.ndim == 2
+        if single:
+            x = x[None]; u = u[None]
+        B, n, _ = x.shape
+        if not n:
+            raise ValueError("gyro_bias_step: no points")
+        u = _arr(u[..., :2], np.float64)
+        nrm = _arr(nrm, np.float64, (B, 3))
+        d = _opt(d, np.float64, (B,)); omega = _opt(omega, np.float64, (B, 3)); valid = _opt(valid, np.uint8, (B, n))
+        if state is None:
+            st = np.zeros((B, BIAS_DOUBLES), np.float64)
+            st[:, 0:3] = list(gv.b0); st[:, [3, 6, 8]] = np.asarray(list(gv.p0)) ** 2
+        else:
+            st = _arr(np.array(state, np.float64), np.float64, (B, BIAS_DOUBLES))
+        out = np.zeros((B, SOLVE_DOUBLES), np.float64)
+        with self._lock:
+            self._ck(self._L.ofk_gyro_bias_step(self._h, int(variant), _p(x), _p(u), _p(valid), B, n, _p(d), _p(nrm), _p(omega), None,
+                                                C.byref(robust) if robust is not None else None, C.byref(gv), _p(st), _p(out)))
+        return (out[0], st[0]) if single else (out, st)
 
     def velocity_solve_plane(self, variant, x, u, d=None, nrm=None, omega=None, t=None, valid=None, robust=None, plane=None, **settings):
         """ofk_velocity_solve_plane: velocity_solve's arguments (NODE or SIM), an optional Robust and the plane setting (a Plane, or

@@ -156,6 +156,9 @@ class PipelineConfig:
     # and plane displacement are written into the points on the device in front of the solve stage; the velocity is then the
     # displacement per frame interval
     finite_motion: object = None
+    # gyro bias (ofk.h: ofk_set_gyro_bias): None, True (the defaults) or an ofk.GyroBias: every stream filters its gyro's bias from the
+    # flow and takes it out of omega in front of each step; FlowPipeline ignores it (independent pairs carry no state)
+    gyro_bias: object = None
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -247,6 +250,15 @@ class PipelineConfig:
             raise ValueError(f"finite_motion {m!r} is neither None, True nor an ofk.FiniteMotion")
         m = ofk.finite_motion_setting(m.mode, m.min_depth)       # range-checked
         return None if m.mode == ofk.FM_OFF else m
+
+    def gyro_bias_setting(self):
+        """The ofk.GyroBias structure of this configuration, None when the gyro bias is off."""
+        if self.gyro_bias is None or self.gyro_bias is False:
+            return None
+        m = ofk.gyro_bias_setting() if self.gyro_bias is True else self.gyro_bias
+        if not isinstance(m, ofk.GyroBias):
+            raise ValueError(f"gyro_bias {m!r} is neither None, True nor an ofk.GyroBias")
+        return None if m.mode == ofk.BIAS_OFF else m
 
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
@@ -356,14 +368,14 @@ class FusionConfig:
 
 def _apply_settings(ctx, cfg, zones):
     """The settings a PipelineConfig switches on, on a fresh context, in the order the library's checks were written for; zones:
-    whether the exclusion zones are among them (they belong to the stream steps)."""
+    whether the exclusion zones and the gyro bias are among them (they belong to the stream steps)."""
     if cfg.lk_seed != "off":
         ctx.set_lk_seed(cfg.lk_seed, cfg.seed_gain)
     steps = [(ctx.set_robust, cfg.robust_setting), (ctx.set_track_gate, cfg.track_gate_setting), (ctx.set_corner_grid, cfg.corner_grid_setting),
              (ctx.set_cov, cfg.cov_setting), (ctx.set_joint, cfg.joint_setting), (ctx.set_plane, cfg.plane_setting),
              (ctx.set_epipolar, cfg.epipolar_setting)]
     if zones:
-        steps.append((ctx.set_zones, cfg.zones_setting))
+        steps += [(ctx.set_zones, cfg.zones_setting), (ctx.set_gyro_bias, cfg.gyro_bias_setting)]
     steps += [(ctx.set_camera, cfg.camera_setting), (ctx.set_rolling_shutter, cfg.rolling_shutter_setting),
               (ctx.set_finite_motion, cfg.finite_motion_setting)]
     for setter, setting in steps:                                # every *_setting() is None when its setting is off
@@ -439,6 +451,11 @@ class FlowStream:
         """[batch, 32] joint records (ofk.h: ofk_set_joint) of the latest step with the joint solve on: rec[:, 0:3] is the refined omega,
         rec[:, 3:6] its correction, rec[:, 10] the flag, ofk.cov_matrix(rec[:, 15:21]) C_omega, ofk.cov_matrix(rec[:, 21:27]) C_v."""
         return self.ctx.joint_download(self.batch)
+
+    def gyro_bias(self):
+        """[batch, 32] bias records (ofk.h: ofk_set_gyro_bias) of the latest step with the gyro bias on: rec[:, 0:3] is the bias,
+        ofk.cov_matrix(rec[:, 3:9]) its covariance, rec[:, 9:12] the raw omega, rec[:, 12:15] the omega the step used, rec[:, 18] the flag."""
+        return self.ctx.gyro_bias_download(self.batch)
 
     def covariances(self):
         """[batch, 24] cov records (ofk.h: ofk_set_cov) of the latest step with the covariance on; ofk.cov_matrix(rec[:, 0:6]) is C_v,

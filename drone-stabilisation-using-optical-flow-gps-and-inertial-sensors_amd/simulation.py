@@ -49,6 +49,17 @@ def solve_lgs_robust(x, u, d, n, omega, t, **settings):
     return out[:3].copy(), R, out[5:8].copy(), w, st
 
 
+def gyro_bias_step(x, u, d, n, omega_raw, state=None, **settings):
+    """One step of a stream's gyro bias without images (ofk.h: ofk_gyro_bias_step): solve_lgs (t = 0) at omega_raw less the bias, then
+    the filter step.  state: the [32] of the previous call (None: the setting's start); settings: ofk.gyro_bias_setting's keywords.
+    Returns (v, R, s, state [32])."""
+    x = np.asarray(x, np.float64)
+    out, st = ofk.default_context().gyro_bias_step(ofk.SOLVE_SIM, x[:, :2], np.asarray(u, np.float64)[:, :2], d=float(np.ravel(d)[0]), nrm=n,
+                                                   omega=omega_raw, state=state, **settings)
+    R = np.array([out[3]]) if (int(out[4]) == 3 and 3 * len(x) > 3) else np.empty(0)
+    return out[:3].copy(), R, out[5:8].copy(), st
+
+
 def solve_lgs_joint(x, u, d, n, omega, t, sigma_flow, sigma_omega=None):
     """solve_lgs with the gyro refined from the flow (ofk.h: ofk_velocity_solve_joint).  sigma_flow: the flow noise in the units of x
     and u; sigma_omega: None (every axis free), a scalar or three values (inf: free, 0: held).

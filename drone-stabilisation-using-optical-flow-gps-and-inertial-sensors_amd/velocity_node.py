@@ -84,6 +84,18 @@ def solve_lgs_cov(x, u, d, n, omega, mode="propagate", **sigmas):
     return out[:3].copy(), R, rank, out[5:8].copy(), ofk.cov_matrix(cov[0:6]), cov
 
 
+def gyro_bias_step(x, u, d, n, omega_raw, state=None, **settings):
+    """One step of a stream's gyro bias without images (ofk.h: ofk_gyro_bias_step): solve_lgs at omega_raw less the bias, then the
+    filter step that refines the bias from the flow.  state: the [32] returned by the previous call (None: the setting's start);
+    settings: ofk.gyro_bias_setting's keywords, sigma_flow in the units of x and u.
+    Returns (v, R, rank, s, state [32]); state[0:3] is the bias, state[12:15] the omega the solve used, state[18] the flag."""
+    x = np.asarray(x, np.float64); u = np.asarray(u, np.float64)
+    out, st = ofk.default_context().gyro_bias_step(ofk.SOLVE_NODE, x[:, :2], u[:, :2], d=float(d), nrm=n, omega=omega_raw, state=state, **settings)
+    rank = int(out[4])
+    R = np.array([out[3]]) if (rank == 3 and 3 * len(x) > 3) else np.empty(0)
+    return out[:3].copy(), R, rank, out[5:8].copy(), st
+
+
 def solve_lgs_joint(x, u, d, n, omega, sigma_flow, sigma_omega=None):
     """solve_lgs with the gyro refined from the flow (ofk.h: ofk_velocity_solve_joint): velocity and rotation from one 6-unknown
     least squares.  sigma_flow: the flow noise in the units of x and u; sigma_omega: None (every axis free), a scalar or three
@@ -154,6 +166,7 @@ class optical_fusion:
     _corner_grid = {}                                            # PipelineConfig's grid_cell / grid_cap / grid_max_rank; empty: no grid
     _cov = {}                                                    # PipelineConfig's covariance fields (cov, sigma_*, ...); empty: no covariance
     _joint = {}                                                  # PipelineConfig's joint fields (joint, joint_sigma_flow_px, omega_prior, ...); empty: the gyro is taken as exact
+    _gyro_bias = {}                                              # PipelineConfig's gyro_bias field; empty: the gyro is taken as unbiased
     _plane = {}                                                  # PipelineConfig's plane fields (plane, plane_sigma_flow_px, normal_prior, ...); empty: the normal is taken as exact
     _epipolar = {}                                               # PipelineConfig's epipolar fields (epipolar, epi_anchor_px, epi_sigma_max, ...); empty: every depth is the plane's
     _zones = {}                                                  # PipelineConfig's zones / zone_* fields; empty: no exclusion zones
@@ -315,7 +328,7 @@ class optical_fusion:
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
                                  **self._cov, **self._joint, **self._plane, **self._epipolar, **self._zones, **self._camera, **self._rolling_shutter,
-                                 **self._finite_motion)
+                                 **self._finite_motion, **self._gyro_bias)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -355,6 +368,8 @@ class optical_fusion:
                 self.vel_err = np.sqrt(np.maximum(cv[[6, 9, 11]], 0.0))
         if self._joint and r[15]:
             self.last_joint = fs.rotations()[0]
+        if self._gyro_bias:
+            self.last_gyro_bias = fs.gyro_bias()[0]
         if self._plane and r[15]:
             self.last_plane = fs.planes()[0]
         if self._epipolar and r[15]:
@@ -419,7 +434,7 @@ class optical_fusion:
             self.vel_err = np.sqrt(np.maximum(np.diag(Rm @ ofk.cov_matrix(cv[6:12]) @ Rm.T), 0.0))
 
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
-                 rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None):
+                 rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None, gyro_bias=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -456,7 +471,10 @@ class optical_fusion:
         finite_motion: None (the flow is taken as the instantaneous motion field), True, an ofk.FiniteMotion or a dict of
         ofk.finite_motion_setting's keywords, e.g. dict(min_depth=0.1): the restored pipeline then writes the frame pair's exact
         rotation and plane displacement into the points on the device in front of the solve (ofk.h: ofk_set_finite_motion); the
-        velocity is then the mean over the frame interval, and the node's omega has to be per frame interval."""
+        velocity is then the mean over the frame interval, and the node's omega has to be per frame interval.
+        gyro_bias: None (the gyro is taken as unbiased), True, an ofk.GyroBias or a dict of ofk.gyro_bias_setting's keywords, e.g.
+        dict(sigma_gyro=2e-5, p0=1e-2): the stream then filters the gyro's bias from the flow and takes it out of omega in front of
+        every step (ofk.h: ofk_set_gyro_bias); self.last_gyro_bias is the record, its slots 0-2 the bias."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -525,6 +543,13 @@ class optical_fusion:
             PipelineConfig(**self._finite_motion).finite_motion_setting()   # invalid fields fail here, not at the first frame
         else:
             self._finite_motion = {}
+        if gyro_bias is not None and gyro_bias is not False:
+            gb = gyro_bias if gyro_bias is True or isinstance(gyro_bias, ofk.GyroBias) else ofk.gyro_bias_setting(**dict(gyro_bias))
+            self._gyro_bias = dict(gyro_bias=gb)
+            PipelineConfig(**self._gyro_bias).gyro_bias_setting()    # invalid fields fail here, not at the first frame
+        else:
+            self._gyro_bias = {}
+        self.last_gyro_bias = None
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

@@ -666,6 +666,56 @@ int ofk_velocity_solve_joint(ofk_ctx *ctx, int variant, const double *x, const d
                              const double *d, const double *nrm, const double *omega, const double *t, const double *wgt,
                              const ofk_robust *r, const ofk_joint *j, double *out, double *joint);
 
+/* The gyro bias of a stream: filtered from the flow, taken out of omega in front of every step.  The joint solve above repairs the gyro
+ * one frame at a time, with six unknowns where the plain solve has three, and forgets what it found; a gyro bias is constant over
+ * seconds, so a stream learns it once and subtracts it before anything reads omega.  Off by default; with it off there is no
+ * allocation and no launch and every entry point returns the bits it always did.  All arithmetic is f64, in the order written here.
+ * Model: omega_true = omega_gyro - b, b a random walk of variance q per step, the gyro's white noise sigma_gyro.  State per stream: b^ (3)
+ * and P (3 x 3, symmetric), in rad per frame interval, the units of sensor slots 4-6.  An axis with p0[k] == 0 is held at b0[k] (the
+ * joint solve's "0 holds"): it is never estimated and its rows of P stay as they are (0 from the setting).
+ * Apply (k_gyro_bias_apply, directly behind the sensors' upload): the raw omega goes into the bias record and the device copy of the
+ * sensor rows gets slots 4-6 := omega - b^, one subtraction per axis; under ofk_fusion.use_imu the IMU state's slots 18-20 likewise, and
+ * then that omega is the record's raw one.  LK's seed, the rolling shutter's gyro mode, the finite-motion rewrite, the feasibility rule,
+ * every solve and every second-stage kernel read the corrected omega; none of them changes.  Under use_imu the same kernel ends the step
+ * by putting the IMU state's raw bits back, so a step with no ofk_imu_push in between does not subtract twice.  The caller's sensor array
+ * is never written.
+ * Filter step (k_stream_bias, directly behind the solve kernel, in front of any second-stage kernel; update != 0 and at least one axis
+ * estimated): the joint solve's core over the joint solve's point set at omega0 = the corrected omega, prior variance +inf on the
+ * estimated axes E and 0 on the held ones, d sigma_f as for the joint solve; nothing but the bias record is written.  Then
+ *   predict    P_kk += q for k in E, on every step, whatever follows
+ *   flag 1, 2  the core's own (not attempted / unobservable): reported, no update
+ *   z = -delta_E,  R = C_omega,EE + sigma_gyro^2 I,  S = P_EE + R;  S^-1 from the solve's eigen-decomposition over the |E| largest
+ *              eigenvalues; a value of S or NIS that is not finite or an eigenvalue that is not positive: flag 2, no update
+ *   NIS = z^T (S^-1 z);  nis_max > 0 and not NIS <= nis_max: flag 3, no update
+ *   K = P S^-1 (held columns of S^-1 are 0),  b^_i += K_i0 z_0 + K_i1 z_1 + K_i2 z_2,  P := P - (K S) K^T,  then P_ij := (P_ij + P_ji) / 2
+ * Bias record, OFK_BIAS_DOUBLES per stream: 0-2 b^ after the step; 3-8 P, upper triangle (xx xy xz yy yz zz); 9-11 raw omega; 12-14 the
+ * omega used; 15-17 delta (0 with a flag set); 18 flag (0 updated, 1 not attempted, 2 unobservable, 3 gated, 4 apply only: update == 0
+ * or no axis estimated); 19 NIS (0 unless the flag is 0 or 3); 20 updates so far; 21 steps so far; 22-27 R, upper triangle (0 unless
+ * the flag is 0 or 3); 28 kept points; 29-31 reserved, 0.
+ * ofk_set_gyro_bias (NULL or mode OFK_BIAS_OFF: off) is a context setting read by ofk_stream_step[_jpeg] and
+ * ofk_stream_step_fused[_jpeg]; ofk_pairs_run ignores it, as it ignores the zones: independent pairs carry no state.  The state is
+ * (b0, diag(p0^2)) with both counters 0 when the setting is set and at every ofk_stream_begin[_jpeg].  update == 0 applies b^ and never
+ * changes it (a calibrated gyro).  Refused with OFK_E_INVALID, the previous setting staying in place: an unknown mode; sigma_flow not
+ * finite or <= 0; sigma_gyro, q, nis_max or a p0 negative or not finite; a b0 not finite; update not 0/1.  With update on the steps
+ * refuse OFK_SOLVE_OFMODULE, OFK_FLOW_ROTATIONAL and OFK_KEEP_LEGACY: not the sensor model, as for the joint solve.
+ * ofk_gyro_bias_reset: state [batch][9] = b^ (3), P upper triangle (6), all finite, loaded into the first `batch` streams, their
+ * counters 0 (a hot start); the setting must be on.  ofk_gyro_bias_download: rec [batch][OFK_BIAS_DOUBLES] of the latest step with the
+ * setting on (`batch` is that step's own); OFK_E_INVALID before such a step.
+ * ofk_gyro_bias_step is one step without images: apply on omega_raw [batch][3], ofk_velocity_solve[_robust] at the corrected omega
+ * (n <= 4096; NODE or SIM; wgt must be NULL; r NULL: the plain solve), then the filter step over the same points.  state
+ * [batch][OFK_BIAS_DOUBLES] goes in (slots 0-8, 20 and 21 are read) and comes out as the step's bias record; out as ofk_velocity_solve. */
+#define OFK_BIAS_OFF 0
+#define OFK_BIAS_ON 1
+#define OFK_BIAS_DOUBLES 32
+typedef struct ofk_gyro_bias { int mode; double sigma_flow; double sigma_gyro; double q; double p0[3]; double b0[3]; double nis_max; int update; } ofk_gyro_bias;
+int ofk_set_gyro_bias(ofk_ctx *ctx, const ofk_gyro_bias *g);
+int ofk_get_gyro_bias(const ofk_ctx *ctx, ofk_gyro_bias *g);
+int ofk_gyro_bias_reset(ofk_ctx *ctx, const double *state, int batch);
+int ofk_gyro_bias_download(ofk_ctx *ctx, double *rec);
+int ofk_gyro_bias_step(ofk_ctx *ctx, int variant, const double *x, const double *u, const uint8_t *valid, int batch, int n,
+                       const double *d, const double *nrm, const double *omega_raw, const double *wgt, const ofk_robust *r,
+                       const ofk_gyro_bias *g, double *state, double *out);
+
 /* The plane solve: the ground normal refined from the flow.  Every solve of the library - plain, robust, joint, the covariance, the
  * feasibility rule - takes the plane's normal as exact: the IMU's R [0,0,1], under ofk_fusion.use_imu the resident IMU state's, so
  * level ground is assumed.  A normal that is off is a common-mode error no residual sees (ofk_cov's sigma_normal only books it); the
