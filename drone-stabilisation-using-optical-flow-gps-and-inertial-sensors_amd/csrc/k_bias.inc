@@ -85,10 +85,13 @@ __device__ void bias_filter(const bias_cfg &c, const double *jr, double *r)
     if (c.nis_max > 0.0 && !(nis <= c.nis_max)) { r[18] = 3.0; return; }
     double K[3][3], T[3][3], Pn[3][3];
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) K[i][j] = P[i][0] * Si[0][j] + P[i][1] * Si[1][j] + P[i][2] * Si[2][j];
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) T[i][j] = K[i][0] * S[0][j] + K[i][1] * S[1][j] + K[i][2] * S[2][j];
+    // P - P S^-1 P = R S^-1 P: a product, where the difference cancels once P is large against R.  T = S^-1 P; rows and columns of
+    // held axes keep P's own values
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) T[i][j] = Si[i][0] * P[0][j] + Si[i][1] * P[1][j] + Si[i][2] * P[2][j];
     for (int i = 0; i < 3; ++i) {
         bh[i] += K[i][0] * z[0] + K[i][1] * z[1] + K[i][2] * z[2];
-        for (int j = 0; j < 3; ++j) Pn[i][j] = P[i][j] - (T[i][0] * K[j][0] + T[i][1] * K[j][1] + T[i][2] * K[j][2]);
+        for (int j = 0; j < 3; ++j)
+            Pn[i][j] = c.est[i] && c.est[j] ? Rm[i][0] * T[0][j] + Rm[i][1] * T[1][j] + Rm[i][2] * T[2][j] : P[i][j];
     }
     for (int k = 0; k < 3; ++k) { r[k] = bh[k]; r[15 + k] = jr[3 + k]; }
     r[3] = Pn[0][0]; r[4] = (Pn[0][1] + Pn[1][0]) / 2.0; r[5] = (Pn[0][2] + Pn[2][0]) / 2.0;

@@ -1189,6 +1189,7 @@ static int check_bias(ofk_ctx *c, const ofk_gyro_bias *v, const char *who)
     if (!(std::isfinite(v->nis_max) && v->nis_max >= 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: nis_max %g is not finite or negative", who, v->nis_max);
     for (int k = 0; k < 3; ++k) {
         if (!(std::isfinite(v->p0[k]) && v->p0[k] >= 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: p0[%d] is not finite or negative (%g)", who, k, v->p0[k]);
+        if (!std::isfinite(v->p0[k] * v->p0[k])) return ofk_fail(c, OFK_E_INVALID, "%s: the square of p0[%d] is not finite (%g)", who, k, v->p0[k]);
         if (!std::isfinite(v->b0[k])) return ofk_fail(c, OFK_E_INVALID, "%s: b0[%d] is not finite (%g)", who, k, v->b0[k]);
     }
     if (v->update != 0 && v->update != 1) return ofk_fail(c, OFK_E_INVALID, "%s: update is 0 or 1", who);

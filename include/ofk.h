@@ -687,7 +687,9 @@ int ofk_velocity_solve_joint(ofk_ctx *ctx, int variant, const double *x, const d
  *   z = -delta_E,  R = C_omega,EE + sigma_gyro^2 I,  S = P_EE + R;  S^-1 from the solve's eigen-decomposition over the |E| largest
  *              eigenvalues; a value of S or NIS that is not finite or an eigenvalue that is not positive: flag 2, no update
  *   NIS = z^T (S^-1 z);  nis_max > 0 and not NIS <= nis_max: flag 3, no update
- *   K = P S^-1 (held columns of S^-1 are 0),  b^_i += K_i0 z_0 + K_i1 z_1 + K_i2 z_2,  P := P - (K S) K^T,  then P_ij := (P_ij + P_ji) / 2
+ *   K = P S^-1 (held columns of S^-1 are 0),  b^_i += K_i0 z_0 + K_i1 z_1 + K_i2 z_2,  P_EE := R (S^-1 P)_EE,  then P_ij := (P_ij + P_ji) / 2
+ *              R S^-1 P is P - P S^-1 P written as a product: the difference cancels once P is large against R (a wide prior) and
+ *              can leave P indefinite, the product cannot.  Rows and columns of held axes are not written.
  * Bias record, OFK_BIAS_DOUBLES per stream: 0-2 b^ after the step; 3-8 P, upper triangle (xx xy xz yy yz zz); 9-11 raw omega; 12-14 the
  * omega used; 15-17 delta (0 with a flag set); 18 flag (0 updated, 1 not attempted, 2 unobservable, 3 gated, 4 apply only: update == 0
  * or no axis estimated); 19 NIS (0 unless the flag is 0 or 3); 20 updates so far; 21 steps so far; 22-27 R, upper triangle (0 unless
@@ -696,7 +698,8 @@ int ofk_velocity_solve_joint(ofk_ctx *ctx, int variant, const double *x, const d
  * ofk_stream_step_fused[_jpeg]; ofk_pairs_run ignores it, as it ignores the zones: independent pairs carry no state.  The state is
  * (b0, diag(p0^2)) with both counters 0 when the setting is set and at every ofk_stream_begin[_jpeg].  update == 0 applies b^ and never
  * changes it (a calibrated gyro).  Refused with OFK_E_INVALID, the previous setting staying in place: an unknown mode; sigma_flow not
- * finite or <= 0; sigma_gyro, q, nis_max or a p0 negative or not finite; a b0 not finite; update not 0/1.  With update on the steps
+ * finite or <= 0; sigma_gyro, q, nis_max or a p0 negative or not finite; a p0 whose square is not finite (the start state diag(p0^2)
+ * must be one ofk_gyro_bias_reset would take), by ofk_gyro_bias_step as well; a b0 not finite; update not 0/1.  With update on the steps
  * refuse OFK_SOLVE_OFMODULE, OFK_FLOW_ROTATIONAL and OFK_KEEP_LEGACY: not the sensor model, as for the joint solve.
  * ofk_gyro_bias_reset: state [batch][9] = b^ (3), P upper triangle (6), all finite, loaded into the first `batch` streams, their
  * counters 0 (a hot start); the setting must be on.  ofk_gyro_bias_download: rec [batch][OFK_BIAS_DOUBLES] of the latest step with the

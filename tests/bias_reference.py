@@ -5,7 +5,7 @@ Model: omega_true = omega_gyro - b, b a random walk of variance q per step, the 
   apply        omega_used = omega_raw - b^
   filter step  joint_solve at omega_used with the estimated axes free and the held ones held: delta, C_omega.  Predict P_kk += q on the
                estimated axes E; flag 1 / 2 of the solve: nothing more; z = -delta_E, R = C_omega,EE + sigma_gyro^2 I, S = P_EE + R,
-               NIS = z^T S^-1 z (gate: flag 3), K = P_.E S^-1, b^ += K z, P -= K S K^T, symmetrised.
+               NIS = z^T S^-1 z (gate: flag 3), K = P_.E S^-1, b^ += K z, P_EE := R (S^-1 P)_EE, symmetrised.
 The inverse of S comes from numpy's eigh where the device runs a cyclic Jacobi: close, not bit-identical.
 Nothing here imports the package: the tests feed it what the device downloaded."""
 import numpy as np
@@ -71,7 +71,8 @@ def filter_step(s, r, joint):
         return r
     K = P @ Si
     b = b + K @ z
-    Pn = P - (K @ S) @ K.T
+    Pn = P.copy()                                                # R S^-1 P = P - P S^-1 P as a product: nothing cancels under a wide prior
+    Pn[np.ix_(E, E)] = (R @ (Si @ P))[np.ix_(E, E)]
     Pn = 0.5 * (Pn + Pn.T)
     r[0:3] = b; r[3:9] = jr.tri(Pn); r[15:18] = rec[3:6]; r[18] = 0.0; r[20] += 1.0
     return r

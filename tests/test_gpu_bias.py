@@ -125,18 +125,23 @@ def bias_keywords(**over):
     return dict(dict(sigma_flow=SIGMA_FLOW_PX, sigma_gyro=SIGMA_GYRO, q=1e-10, p0=(5e-3, 5e-3, 5e-3), b0=(2e-4, -1e-4, 1e-4), nis_max=0.0, update=True), **over)
 
 
-def run(ofk, fusion_name, bias=None, corrections=None, robust=None, extra=None, reset=None):
-    """2 streams x 3 steps.  bias: gyro_bias_setting's keywords (run A) or None (run B); corrections: per step the [2, 3] that run B takes
-    off the gyro on the host (sensors and IMU messages); extra: further PipelineConfig fields; reset: a state for gyro_bias_reset behind
-    begin.  Returns per step what the device reported."""
+def run(ofk, fusion_name, bias=None, corrections=None, robust=None, extra=None, reset=None, B=2, steps_n=3, drop=None, nan_gyro=None,
+        blank=None, fusion=None):
+    """B streams (the two clips in turn) x steps_n steps.  bias: gyro_bias_setting's keywords (run A) or None (run B); corrections: per
+    step the [B, 3] that run B takes off the gyro on the host (sensors and IMU messages); extra: further PipelineConfig fields; reset: a
+    state for gyro_bias_reset behind begin.  drop / nan_gyro: the step (1 ..) at which stream 1's range / second gyro axis (sensors and
+    IMU messages) is NaN (stream 0's where there is one stream).  blank: a stream whose first frame is a uniform 128.  fusion: a FusionConfig in place of fusion_name's.
+    Returns per step what the device reported."""
     from of_amd.pipeline import FlowStream
     from stream_oracle import imu_messages
-    B = 2
     frames, info = ssr.stream_frames()
+    frames = frames[np.arange(B) % 2]
+    if blank is not None:
+        frames = frames.copy(); frames[blank, 0] = 128
     cfg = ssr.pipeline_config(**dict(dict(robust=robust, robust_hypotheses=16, robust_iters=3, robust_seed=5) if robust else {}, **(extra or {})))
-    fusion = ssr.make_fusion(fusion_name)
+    fusion = ssr.make_fusion(fusion_name) if fusion is None else fusion
     use_imu = fusion is not None and fusion.use_imu
-    sensors = ssr.stream_sensors(ofk, info)
+    sensors = ssr.stream_sensors(ofk, info)[np.arange(B) % 2]
     fs = FlowStream(ssr.W, ssr.H, batch=B, cfg=cfg, min_features=10, mask_radius=8, fusion=fusion)
     steps = []
     try:
@@ -146,13 +151,21 @@ def run(ofk, fusion_name, bias=None, corrections=None, robust=None, extra=None, 
         if reset is not None:
             fs.ctx.gyro_bias_reset(reset)
         rng = np.random.default_rng(31)
-        for t in range(1, 4):
+        for t in range(1, steps_n + 1):
             corr = np.zeros((B, 3)) if corrections is None else corrections[t - 1]
-            sr = sensors.copy()
-            sr[:, 4:7] = sensors[:, 4:7] - corr
+            given = sensors.copy()
+            if drop == t:
+                given[min(B, 2) - 1, 0] = np.nan
+            if nan_gyro == t:
+                given[min(B, 2) - 1, 5] = np.nan
+            sr = given.copy()
+            sr[:, 4:7] = given[:, 4:7] - corr
             imu = raw = None
             if use_imu:
-                msgs = np.stack([imu_messages(rng, 0.1 * t + 10 * s, 3, rate=np.asarray(info["omega"]) + ssr.GYRO_OFF) for s in range(B)])
+                msgs = np.stack([imu_messages(rng, 0.1 * t + 10 * s, 3, rate=np.asarray(info["omega"]) + ssr.GYRO_OFF) for s in range(min(B, 2))])
+                msgs = msgs[np.arange(B) % 2]                    # past two streams the clips' messages in turn, as the frames
+                if nan_gyro == t:
+                    msgs[min(B, 2) - 1, :, 7] = np.nan
                 raw = msgs[:, -1, 6:9].copy()
                 msgs[:, :, 6:9] = msgs[:, :, 6:9] - corr[:, None, :]
                 fs.push_imu(msgs)
@@ -167,7 +180,7 @@ def run(ofk, fusion_name, bias=None, corrections=None, robust=None, extra=None, 
             nxt, keep = fs.ctx.stream_last_points(ssr.CORNERS)
             imu_after = fs.ctx.imu_state(B)[0] if use_imu else None
             steps.append(dict(rec=rec, fused=fused, old=old_tracks, n=old_counts, nxt=nxt, keep=keep, imu=imu, x=x, P=P, imu_after=imu_after,
-                              sr=sr, tracks=tracks.copy(), counts=counts.copy(), raw=raw if use_imu else sensors[:, 4:7].copy(),
+                              sr=sr, tracks=tracks.copy(), counts=counts.copy(), raw=raw if use_imu else given[:, 4:7].copy(),
                               bias=fs.gyro_bias() if bias is not None else None,
                               weights=fs.ctx.robust_download(B)[0] if robust else None))
     finally:
@@ -175,11 +188,17 @@ def run(ofk, fusion_name, bias=None, corrections=None, robust=None, extra=None, 
     return steps, fusion
 
 
-def assert_twin(a_steps, b_steps, use_imu, tag):
-    """Every output of run A equals run B's bit for bit; the IMU state but for its omega, which A holds raw and B corrected."""
+def assert_twin(a_steps, b_steps, use_imu, tag, counted=False):
+    """Every output of run A equals run B's bit for bit; the IMU state but for its omega, which A holds raw and B corrected.  counted:
+    the point arrays are compared up to each stream's count (a stream without tracks leaves the rows behind its count as they were)."""
+    rows = {"tracks": "counts", "nxt": "n", "keep": "n"}
     for t, (a, b) in enumerate(zip(a_steps, b_steps)):
         for k in ("rec", "fused", "x", "P", "tracks", "counts", "nxt", "keep"):
-            if a[k] is not None:
+            if a[k] is not None and counted and k in rows:
+                assert np.array_equal(a[rows[k]], b[rows[k]]), (tag, t, rows[k], a[rows[k]], b[rows[k]])
+                for s, n in enumerate(a[rows[k]]):
+                    assert np.array_equal(bits(a[k][s, :n]), bits(b[k][s, :n])), (tag, t, k, s, a[k][s, :n], b[k][s, :n])
+            elif a[k] is not None:
                 assert np.array_equal(bits(a[k]), bits(b[k])), (tag, t, k, a[k], b[k])
         if use_imu:
             rest = np.r_[0:18, 21:24]
@@ -187,11 +206,14 @@ def assert_twin(a_steps, b_steps, use_imu, tag):
             assert np.array_equal(bits(a["imu_after"][:, 18:21]), bits(a["raw"])), (tag, t, "the IMU state's omega is the raw one again")
 
 
-def twin(ofk, fusion_name, bias, robust=None, extra=None, reference=True, reset=None):
-    a, fusion = run(ofk, fusion_name, bias=bias, robust=robust, extra=extra, reset=reset)
+def twin(ofk, fusion_name, bias, robust=None, extra=None, reference=True, reset=None, **how):
+    """how: run's further keywords (B, steps_n, drop, nan_gyro, blank, fusion), the same in both runs."""
+    counted = how.get("blank") is not None
+    a, fusion = run(ofk, fusion_name, bias=bias, robust=robust, extra=extra, reset=reset, **how)
+    B = how.get("B", 2)
     use_imu = fusion is not None and fusion.use_imu
     s = br.setting(**{k: v for k, v in bias.items()})
-    start = np.stack([br.initial_state(s)] * 2)
+    start = np.stack([br.initial_state(s)] * B)
     if reset is not None:
         start[:, 0:9] = reset
     before = [start[:, 0:3]] + [st["bias"][:, 0:3] for st in a[:-1]]
@@ -199,12 +221,12 @@ def twin(ofk, fusion_name, bias, robust=None, extra=None, reference=True, reset=
     for t, st in enumerate(a):                                   # the omega used is the host's difference, to the bit
         assert np.array_equal(bits(st["bias"][:, 9:12]), bits(st["raw"])), (fusion_name, t)
         assert np.array_equal(bits(st["bias"][:, 12:15]), bits(st["raw"] - corrections[t])), (fusion_name, t)
-    b, _ = run(ofk, fusion_name, bias=None, corrections=corrections, robust=robust, extra=extra)
-    assert_twin(a, b, use_imu, (fusion_name, robust, extra))
+    b, _ = run(ofk, fusion_name, bias=None, corrections=corrections, robust=robust, extra=extra, **how)
+    assert_twin(a, b, use_imu, (fusion_name, robust, extra), counted)
     if reference:
         state = start
         for t, st in enumerate(a):
-            for k in range(2):
+            for k in range(B):
                 n = int(st["n"][k])
                 used = st["raw"][k] - state[k, 0:3]
                 nrm = st["imu"][k, 15:18] if use_imu else None

@@ -1,4 +1,4 @@
-"""What the eleven struct settings and the three point corrections promise at the C boundary (include/ofk.h), pinned byte for byte.
+"""What the twelve struct settings and the three point corrections promise at the C boundary (include/ofk.h), pinned byte for byte.
 
 Every ofk_set_* / ofk_get_* pair: get after a valid set returns the same bytes; NULL switches the setting off the way that setter
 does it (they differ: which fields are cleared, whether a struct whose mode is OFF counts as NULL); an invalid struct is refused with
@@ -60,11 +60,14 @@ def cases(ofk):
                             "ofk_set_rolling_shutter: readout 1.5 outside -1..1 frame intervals", dict(mode=0)),
         "finite_motion": (ofk.FiniteMotion, ofk.FiniteMotion(ofk.FM_EXACT, 0.25), ofk.FiniteMotion(ofk.FM_EXACT, 2.0),
                           "ofk_set_finite_motion: min_depth 2 outside (0, 1]", dict(mode=0)),
+        "gyro_bias": (ofk.GyroBias, ofk.GyroBias(1, 0.3, 2e-5, 1e-12, d3(1e-2, 0.0, 1e4), d3(1e-3, -2e-3, 0.0), 9.5, 1),
+                      ofk.GyroBias(1, 0.3, 2e-5, 1e-12, d3(1e-2, 1e160, 1e4), d3(1e-3, -2e-3, 0.0), 9.5, 1),
+                      "ofk_set_gyro_bias: the square of p0[1] is not finite (1e+160)", dict(mode=0)),
     }
 
 
-NAMES = ["robust", "cov", "joint", "plane", "epipolar", "track_gate", "corner_grid", "zones", "camera", "rolling_shutter", "finite_motion"]
-OFF_IS_NULL = ("robust", "camera", "rolling_shutter", "finite_motion")        # a struct whose mode is OFF is not read beyond the mode
+NAMES = ["robust", "cov", "joint", "plane", "epipolar", "track_gate", "corner_grid", "zones", "camera", "rolling_shutter", "finite_motion", "gyro_bias"]
+OFF_IS_NULL = ("robust", "camera", "rolling_shutter", "finite_motion", "gyro_bias")        # a struct whose mode is OFF is not read beyond the mode
 OFF_IS_COPIED = ("joint", "plane", "epipolar")                                 # ... is checked and copied whole
 
 
