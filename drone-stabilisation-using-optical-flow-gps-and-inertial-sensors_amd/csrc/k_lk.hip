@@ -2,6 +2,7 @@
 //   k_lk15q   the pipeline's kernel: 15 x 15 window, FOUR points per wave (a 16-lane DPP row per point) — see its own header below;
 //   k_lk15    windows <= 15 on levels too small or too oddly sized for k_lk15q: one wave per point, lane = (row, 4-pixel segment);
 //   k_lk<W>   windows up to 21 / 31: one wave per point, generic.
+//   k_lk_light<W>  the lighting-insensitive tracker of ofk_set_lk_light (at the end of this file): k_lk's structure at every window.
 // Common to all three: a 64-thread workgroup (= one wave) tracks its point(s) through all pyramid levels, coarse to fine:
 //   * the (win+3)^2 neighbourhood of the previous-frame level is staged into LDS, the Scharr derivatives of its
 //     (win+1)^2 core are computed there (never materialised in HBM), and each lane keeps its <= NPL window
@@ -359,6 +360,54 @@ void ofk_launch_lk(hipStream_t s, const uint8_t *prev, const uint8_t *next, size
     for (int l = 0; l <= lv.n; ++l) quad = quad && (lv.w[l] & 3) == 0 && lv.w[l] >= 40 && lv.h[l] >= 32 && (lv.off[l] & 3) == 0;
 #define LK_ROUTE(F) \
     launch_lk_flagged<F>(s, quad, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win, max_count, eps * eps, min_eig_thr, next_pts, status, err, batch)
+    switch (flags & (LK_SEED | LK_EIG)) {
+    case LK_SEED: return LK_ROUTE(LK_SEED);
+    case LK_EIG: return LK_ROUTE(LK_EIG);
+    case LK_SEED | LK_EIG: return LK_ROUTE(LK_SEED | LK_EIG);
+    default: return LK_ROUTE(0);
+    }
+#undef LK_ROUTE
+}
+
+// ================================================================================================
+// k_lk_light — the lighting-insensitive tracker (ofk.h: ofk_lk_light): per-window gain and bias taken out of the mismatch vector
+// and of the residual.  One wave per point at every window (k_lk's structure); the body is k_lk_light.inc.  light_mode
+// (OFK_LIGHT_BIAS / _GAIN) and the clamp [gain_lo, gain_hi] are wave-uniform kernel arguments.  The kernels above are not touched
+// by it: ofk_launch_lk_light does its own routing and is only called with the setting on.
+template <int WMAX, int FLAGS>
+__global__ __launch_bounds__(64) void k_lk_light(const uint8_t *__restrict__ prev, const uint8_t *__restrict__ next,
+                                                 size_t pyr_stride, ofk_levels lv, const float *__restrict__ prev_pts,
+                                                 const int *__restrict__ counts, int pts_stride, int win, int max_count,
+                                                 double eps2, double min_eig_thr, int light_mode, double gain_lo, double gain_hi,
+                                                 float *next_pts, uint8_t *__restrict__ status, float *__restrict__ err)
+{
+#include "k_lk_light.inc"
+}
+
+template <int FLAGS>
+static void launch_lk_light_flagged(hipStream_t s, const uint8_t *prev, const uint8_t *next, size_t pyr_stride, const ofk_levels &lv,
+                                    const float *prev_pts, const int *counts, int pts_stride, int win, int max_count, double eps2,
+                                    double min_eig_thr, int mode, double gain_lo, double gain_hi, float *next_pts, uint8_t *status,
+                                    float *err, int batch)
+{
+    auto k = win <= 15 ? k_lk_light<15, FLAGS> : win <= 21 ? k_lk_light<21, FLAGS> : k_lk_light<31, FLAGS>;
+    hipLaunchKernelGGL(k, dim3(pts_stride, batch), dim3(64), 0, s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win, max_count,
+                       eps2, min_eig_thr, mode, gain_lo, gain_hi, next_pts, status, err);
+}
+
+// ofk_launch_lk with the setting on (light.mode is OFK_LIGHT_BIAS or _GAIN and light.gain_max has passed the setter's check)
+void ofk_launch_lk_light(hipStream_t s, const uint8_t *prev, const uint8_t *next, size_t pyr_stride, const ofk_levels &lv,
+                         const float *prev_pts, const int *counts, int pts_stride, int win, int max_count, double eps,
+                         double min_eig_thr, float *next_pts, uint8_t *status, float *err, int batch, int flags, const ofk_lk_light &light)
+{
+    if (max_count < 0) max_count = 0;
+    if (max_count > 100) max_count = 100;
+    if (eps < 0) eps = 0;
+    if (eps > 10) eps = 10;
+    const double gain_lo = 1.0 / light.gain_max;                 // formed once, here: the kernels and the reference clamp to the same two doubles
+#define LK_ROUTE(F) \
+    launch_lk_light_flagged<F>(s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win, max_count, eps * eps, min_eig_thr, light.mode, \
+                               gain_lo, light.gain_max, next_pts, status, err, batch)
     switch (flags & (LK_SEED | LK_EIG)) {
     case LK_SEED: return LK_ROUTE(LK_SEED);
     case LK_EIG: return LK_ROUTE(LK_EIG);

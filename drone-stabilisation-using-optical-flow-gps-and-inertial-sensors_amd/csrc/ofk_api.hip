@@ -147,6 +147,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->overlap = 1;
     c->gray_direct_set = -1;
     c->lk_seed_mode = OFK_SEED_OFF; c->lk_seed_gain = 1.0;
+    c->light = ofk_lk_light{OFK_LIGHT_OFF, 4.0};
     c->robust = ofk_robust{OFK_ROBUST_OFF, 4.685, 5, 64, 0ull, 0};
     c->gate = ofk_track_gate{OFK_FB_OFF, 0.5, -1, 0.0};
     c->cov = ofk_cov{OFK_COV_OFF, 0.0, 0.0, 0.0, {0.0, 0.0, 0.0}, 0.0, 0.0, 0, 0, 0.0, 0.0};
@@ -856,10 +857,40 @@ static int points_download(ofk_ctx *c, const point_setting &s, const char *who, 
     return OFK_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ lighting-insensitive LK setting
+static int check_light(ofk_ctx *c, const ofk_lk_light *l, const char *who)
+{
+    if (l->mode != OFK_LIGHT_OFF && l->mode != OFK_LIGHT_BIAS && l->mode != OFK_LIGHT_GAIN)
+        return ofk_fail(c, OFK_E_INVALID, "%s: light mode %d is none of OFK_LIGHT_OFF, _BIAS, _GAIN", who, l->mode);
+    if (!(std::isfinite(l->gain_max) && l->gain_max > 1.0))
+        return ofk_fail(c, OFK_E_INVALID, "%s: gain_max = %g must be finite and above 1", who, l->gain_max);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_lk_light(ofk_ctx *c, const ofk_lk_light *l)
+{
+    return setting_set(c, &ofk_ctx::light, l && l->mode == OFK_LIGHT_OFF ? nullptr : l, [](ofk_lk_light &s) { s.mode = OFK_LIGHT_OFF; },
+                       [c](const ofk_lk_light *v) { return check_light(c, v, "ofk_set_lk_light"); });
+}
+extern "C" int ofk_get_lk_light(const ofk_ctx *c, ofk_lk_light *l) { return setting_get(c, &ofk_ctx::light, l); }
+
+// The one place LK is launched from: the setting off is ofk_launch_lk, the kernels and the launch of before the setting existed.
+static void launch_lk(hipStream_t s, const uint8_t *prev, const uint8_t *next, size_t pyr_stride, const ofk_levels &lv, const float *prev_pts,
+                      const int *counts, int pts_stride, int win, int max_count, double eps, double min_eig_thr, float *next_pts,
+                      uint8_t *status, float *err, int batch, int flags, const ofk_lk_light &light)
+{
+    if (light.mode == OFK_LIGHT_OFF)
+        ofk_launch_lk(s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win, max_count, eps, min_eig_thr, next_pts, status, err, batch, flags);
+    else
+        ofk_launch_lk_light(s, prev, next, pyr_stride, lv, prev_pts, counts, pts_stride, win, max_count, eps, min_eig_thr, next_pts, status, err, batch,
+                            flags, light);
+}
+
 // Rules 2-5 of the track gates (ofk.h) behind a forward LK of the view on stream s: the backward LK, which is the forward launch with
 // the two pyramids swapped and a level table of the gate's depth, then k_track_gate.  The view's gate buffers exist (gate_alloc).
+// light: the forward pass's ofk_lk_light; the backward pass tracks under the same mode.
 static int gate_tracks(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, int win, int max_level, int max_count, double eps,
-                       double min_eig_thr, const ofk_track_gate &g)
+                       double min_eig_thr, const ofk_track_gate &g, const ofk_lk_light &light)
 {
     const bool fb = g.fb_mode != OFK_FB_OFF;
     if (fb) {
@@ -867,8 +898,8 @@ static int gate_tracks(ofk_ctx *c, hipStream_t s, const View &v, const ofk_level
         const ofk_levels lb = ofk_make_levels(lv.h[0], lv.w[0], win, depth);
         const bool seeded = g.fb_mode == OFK_FB_SEEDED;            // LK's next_pts is in/out: the search starts at the original points
         if (seeded) OFK_HIP(c, hipMemcpyAsync(v.pts_back, v.pts_prev, (size_t)v.nb * c->max_pts * 8, hipMemcpyDeviceToDevice, s));
-        ofk_launch_lk(s, v.pyr[1], v.pyr[0], c->pyr_stride, lb, v.pts_next, v.counts, c->max_pts, win, max_count, eps, min_eig_thr, v.pts_back,
-                      v.status_back, v.err_back, v.nb, seeded ? OFK_LK_USE_INITIAL_FLOW : 0);
+        launch_lk(s, v.pyr[1], v.pyr[0], c->pyr_stride, lb, v.pts_next, v.counts, c->max_pts, win, max_count, eps, min_eig_thr, v.pts_back,
+                  v.status_back, v.err_back, v.nb, seeded ? OFK_LK_USE_INITIAL_FLOW : 0, light);
     }
     ofk_launch_track_gate(s, v.pts_prev, fb ? v.pts_back : nullptr, fb ? v.status_back : nullptr, v.err, v.counts, c->max_pts, fb ? 1 : 0,
                           (float)(g.fb_thr * g.fb_thr), g.err_max != 0.0 ? 1 : 0, (float)g.err_max, v.status, fb ? v.fb2 : nullptr, v.gate_stats,
@@ -878,6 +909,7 @@ static int gate_tracks(ofk_ctx *c, hipStream_t s, const View &v, const ofk_level
 
 // The track step of the resident chains: with ofk_set_lk_seed on, the start positions are written where LK reads them (imu_state: the
 // source k_stream_fuse uses under use_imu, NULL = the sensors only) and LK starts there;
+// with ofk_set_lk_light on, both LK passes are the lighting-insensitive kernels;
 // with ofk_set_track_gate on, the gates follow on the same stream.  With ofk_set_camera on (the view's ideal buffers exist:
 // solve_points_prepare) the sensors speak of the ideal image, so the predictor runs on the ideal points and its seeds are brought back into
 // the image; behind the gates the ideal points of both sets are written for the solve stage - one launch, unless the seed needed
@@ -893,9 +925,9 @@ static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv,
         ofk_launch_camera(s, &c->camera, 1, v.pts_next, v.pts_next, nullptr, nullptr, v.counts, c->max_pts, v.nb);
     } else if (seeded)
         ofk_launch_seed_points(s, v.pts_prev, v.counts, c->max_pts, v.sensors, imu_state, c->lk_seed_mode, c->lk_seed_gain, v.pts_next, v.nb);
-    ofk_launch_lk(s, v.pyr[0], v.pyr[1], c->pyr_stride, lv, v.pts_prev, v.counts, c->max_pts, p->win, p->max_count, p->eps, p->min_eig_thr,
-                  v.pts_next, v.status, v.err, v.nb, seeded ? OFK_LK_USE_INITIAL_FLOW : 0);
-    if (gate_on(c->gate)) TRY(gate_tracks(c, s, v, lv, p->win, p->max_level, p->max_count, p->eps, p->min_eig_thr, c->gate));
+    launch_lk(s, v.pyr[0], v.pyr[1], c->pyr_stride, lv, v.pts_prev, v.counts, c->max_pts, p->win, p->max_count, p->eps, p->min_eig_thr,
+              v.pts_next, v.status, v.err, v.nb, seeded ? OFK_LK_USE_INITIAL_FLOW : 0, c->light);
+    if (gate_on(c->gate)) TRY(gate_tracks(c, s, v, lv, p->win, p->max_level, p->max_count, p->eps, p->min_eig_thr, c->gate, c->light));
     if (cam && seeded) ofk_launch_camera(s, &c->camera, 0, v.pts_next, v.pts_next_u, nullptr, nullptr, v.counts, c->max_pts, v.nb);
     else if (cam) ofk_launch_camera(s, &c->camera, 0, v.pts_prev, v.pts_prev_u, v.pts_next, v.pts_next_u, v.counts, c->max_pts, v.nb);
     if (rs_on(c)) {
@@ -973,7 +1005,7 @@ extern "C" int ofk_track_gate_download(ofk_ctx *c, float *fb2, float *back_pts, 
 static int lk_pyr_impl(ofk_ctx *c, const char *who, const uint8_t *prev, const uint8_t *next, int batch, int h, int w, const float *prev_pts,
                        const int *counts, int pts_stride, int win, int max_level, int max_count, double eps, double min_eig_thr,
                        const float *init_pts, int flags, float *next_pts, uint8_t *status, float *err, const ofk_track_gate *g = nullptr,
-                       float *back_pts = nullptr, uint8_t *back_status = nullptr, float *fb2 = nullptr)
+                       float *back_pts = nullptr, uint8_t *back_status = nullptr, float *fb2 = nullptr, const ofk_lk_light *light = nullptr)
 {
     TRY(check_geom(c, batch, h, w, who));
     if (!prev || !next || !prev_pts || !counts || !next_pts || !status || !err) return ofk_fail(c, OFK_E_INVALID, "%s: NULL buffer", who);
@@ -987,6 +1019,9 @@ static int lk_pyr_impl(ofk_ctx *c, const char *who, const uint8_t *prev, const u
         if ((flags & OFK_LK_GET_MIN_EIGENVALS) && g->err_max != 0.0)
             return ofk_fail(c, OFK_E_INVALID, "%s: err_max with OFK_LK_GET_MIN_EIGENVALS: err is no residual then", who);
     }
+    const bool lit = light && light->mode != OFK_LIGHT_OFF;
+    if (lit) TRY(check_light(c, light, who));
+    const ofk_lk_light lt = lit ? *light : ofk_lk_light{OFK_LIGHT_OFF, 4.0};
     const bool gated = g && gate_on(*g);
     const bool seeded = (flags & OFK_LK_USE_INITIAL_FLOW) != 0;
     if (seeded) {
@@ -1006,10 +1041,10 @@ static int lk_pyr_impl(ofk_ctx *c, const char *who, const uint8_t *prev, const u
     if (seeded) TRY(h2d(c, c->pts_next, (size_t)c->max_pts * 8, init_pts, (size_t)pts_stride * 8, batch));   // in/out, as cv2's nextPts
     OFK_HIP(c, hipMemcpyAsync(c->counts, counts, (size_t)batch * 4, hipMemcpyHostToDevice, c->stream));
     build_pyramids(c, c->stream, c->pyr[0], c->pyr[1], lv, batch);
-    ofk_launch_lk(c->stream, c->pyr[0], c->pyr[1], c->pyr_stride, lv, c->pts_prev, c->counts, c->max_pts, win, max_count, eps,
-                  min_eig_thr, c->pts_next, c->status, c->err, batch, flags);
+    launch_lk(c->stream, c->pyr[0], c->pyr[1], c->pyr_stride, lv, c->pts_prev, c->counts, c->max_pts, win, max_count, eps,
+              min_eig_thr, c->pts_next, c->status, c->err, batch, flags, lt);
     if (gated) {
-        TRY(gate_tracks(c, c->stream, view_of(c, 0, batch, 0), lv, win, max_level, max_count, eps, min_eig_thr, *g));
+        TRY(gate_tracks(c, c->stream, view_of(c, 0, batch, 0), lv, win, max_level, max_count, eps, min_eig_thr, *g, lt));
         c->gate_batch = batch; c->gate_fb = g->fb_mode != OFK_FB_OFF;
     }
     TRY(check_launch(c, "k_lk"));
@@ -1049,6 +1084,15 @@ extern "C" int ofk_lk_pyr_fb(ofk_ctx *c, const uint8_t *prev, const uint8_t *nex
 {
     return lk_pyr_impl(c, "ofk_lk_pyr_fb", prev, next, batch, h, w, prev_pts, counts, pts_stride, win, max_level, max_count, eps, min_eig_thr,
                        init_pts, flags, next_pts, status, err, g, back_pts, back_status, fb2);
+}
+
+extern "C" int ofk_lk_pyr_light(ofk_ctx *c, const uint8_t *prev, const uint8_t *next, int batch, int h, int w, const float *prev_pts,
+                                const int *counts, int pts_stride, int win, int max_level, int max_count, double eps, double min_eig_thr,
+                                const float *init_pts, int flags, float *next_pts, uint8_t *status, float *err, const ofk_track_gate *g,
+                                float *back_pts, uint8_t *back_status, float *fb2, const ofk_lk_light *light)
+{
+    return lk_pyr_impl(c, "ofk_lk_pyr_light", prev, next, batch, h, w, prev_pts, counts, pts_stride, win, max_level, max_count, eps, min_eig_thr,
+                       init_pts, flags, next_pts, status, err, g, back_pts, back_status, fb2, light);
 }
 
 static bool seed_mode_ok(int mode) { return mode == OFK_SEED_OFF || mode == OFK_SEED_MODEL || mode == OFK_SEED_ROTATION; }

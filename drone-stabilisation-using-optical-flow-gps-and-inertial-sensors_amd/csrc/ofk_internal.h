@@ -84,6 +84,7 @@ struct ofk_ctx {
     int cur_batch, cur_h, cur_w;    // resident pair geometry (ofk_pairs_upload)
     int prof_mask;
     int lk_seed_mode; double lk_seed_gain;   // ofk_set_lk_seed: OFK_SEED_OFF unless set
+    ofk_lk_light light;                      // ofk_set_lk_light: mode OFK_LIGHT_OFF (gain_max 4) unless set
     ofk_robust robust;                       // ofk_set_robust: loss OFK_ROBUST_OFF unless set
     double *rob_work, *rob_w, *rob_wtmp, *rob_stats;   // [B][7][max_pts] per-point terms, [B][max_pts] weights (+ a scratch copy), [B][OFK_ROBUST_DOUBLES]; one lazy allocation (rob_work owns it)
     int rob_batch;                           // problems of the latest robust run / step (ofk_robust_download), 0 = none
@@ -218,6 +219,10 @@ void ofk_launch_finite_correct(hipStream_t s, const ofk_finite_motion *fm, const
 void ofk_launch_lk(hipStream_t s, const uint8_t *prev, const uint8_t *next, size_t pyr_stride, const ofk_levels &lv,
                    const float *prev_pts, const int *counts, int pts_stride, int win, int max_count, double eps,
                    double min_eig_thr, float *next_pts, uint8_t *status, float *err, int batch, int flags = 0);   // flags: OFK_LK_*
+// the lighting-insensitive tracker (ofk.h: ofk_lk_light; k_lk_light.inc): ofk_launch_lk's arguments and a setting that is on
+void ofk_launch_lk_light(hipStream_t s, const uint8_t *prev, const uint8_t *next, size_t pyr_stride, const ofk_levels &lv,
+                         const float *prev_pts, const int *counts, int pts_stride, int win, int max_count, double eps,
+                         double min_eig_thr, float *next_pts, uint8_t *status, float *err, int batch, int flags, const ofk_lk_light &light);
 // start positions of a seeded LK (ofk.h: ofk_set_lk_seed): seed_out[b][p] for p < counts[b]; imu_state NULL = sensors only
 void ofk_launch_seed_points(hipStream_t s, const float *pts, const int *counts, int pts_stride, const double *sensors,
                             const double *imu_state, int mode, double gain, float *seed_out, int batch);

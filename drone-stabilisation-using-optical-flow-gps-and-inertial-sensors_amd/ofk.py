@@ -34,6 +34,7 @@ SYMBOLS = (
     "ofk_set_plane", "ofk_get_plane", "ofk_plane_download", "ofk_velocity_solve_plane",
     "ofk_set_epipolar", "ofk_get_epipolar", "ofk_epipolar_download", "ofk_epipolar_points_download", "ofk_velocity_solve_epipolar",
     "ofk_set_track_gate", "ofk_get_track_gate", "ofk_track_gate_download", "ofk_lk_pyr_fb",
+    "ofk_set_lk_light", "ofk_get_lk_light", "ofk_lk_pyr_light",
     "ofk_set_corner_grid", "ofk_get_corner_grid", "ofk_corner_grid_download", "ofk_select_corners_grid", "ofk_good_features_grid",
     "ofk_set_zones", "ofk_get_zones", "ofk_zones_step", "ofk_zones_reset", "ofk_zones_download",
     "ofk_set_camera", "ofk_get_camera", "ofk_undistort_points", "ofk_distort_points", "ofk_camera_download",
@@ -85,6 +86,8 @@ EPI_DOUBLES = 32
 EPI_SIGMA_MAX = 0.008                                    # radians; tests/test_epi_reference.py measures it
 FB_OFF, FB_PLAIN, FB_SEEDED = 0, 1, 2                    # ofk_set_track_gate / ofk_lk_pyr_fb
 FB_MODES = {"off": FB_OFF, "plain": FB_PLAIN, "seeded": FB_SEEDED}
+LIGHT_OFF, LIGHT_BIAS, LIGHT_GAIN = 0, 1, 2              # ofk_set_lk_light / ofk_lk_pyr_light
+LIGHT_MODES = {"off": LIGHT_OFF, "bias": LIGHT_BIAS, "gain": LIGHT_GAIN}
 GRID_MAX_CELLS = 2048                                   # OFK_GRID_MAX_CELLS: cells of a corner grid over one frame
 ZONES_OFF, ZONES_HULL = 0, 1                             # ofk_set_zones
 ZONES_MODES = {"off": ZONES_OFF, "hull": ZONES_HULL}
@@ -242,6 +245,37 @@ def track_gate_setting(fb="off", fb_thr=0.5, fb_level=-1, err_max=0.0):
     return TrackGate(fb, fb_thr, fb_level, err_max)
 
 
+class LkLight(C.Structure):
+    """ofk_lk_light (include/ofk.h): the per-window gain and bias of the lighting-insensitive LK."""
+    _fields_ = [("mode", C.c_int), ("gain_max", C.c_double)]
+
+
+def lk_light_setting(mode="gain", gain_max=4.0):
+    """An LkLight structure from names: mode "off" / "bias" (a brightness offset per window) / "gain" (a gain and an offset), or
+    LIGHT_*; the gain is clamped to [1 / gain_max, gain_max]."""
+    if isinstance(mode, str):
+        if mode not in LIGHT_MODES:
+            raise ValueError(f"lk light mode {mode!r} is none of {sorted(LIGHT_MODES)}")
+        mode = LIGHT_MODES[mode]
+    mode, gain_max = int(mode), float(gain_max)
+    if mode not in LIGHT_MODES.values():
+        raise ValueError(f"lk light mode {mode} is none of LIGHT_OFF, LIGHT_BIAS, LIGHT_GAIN")
+    if not (np.isfinite(gain_max) and gain_max > 1.0):
+        raise ValueError(f"lk light gain_max {gain_max} must be finite and above 1")
+    return LkLight(mode, gain_max)
+
+
+def _light(light):
+    """None, a mode name or an LkLight -> an LkLight that is on, or None."""
+    if light is None:
+        return None
+    m = lk_light_setting(light) if isinstance(light, (str, int)) and not isinstance(light, bool) else light
+    if not isinstance(m, LkLight):
+        raise ValueError(f"light {light!r} is neither None, a mode of {sorted(LIGHT_MODES)} nor an ofk.LkLight")
+    m = lk_light_setting(m.mode, m.gain_max)                    # range-checked
+    return None if m.mode == LIGHT_OFF else m
+
+
 class CornerGrid(C.Structure):
     """ofk_corner_grid (include/ofk.h): the per-cell cap inside the greedy corner selection."""
     _fields_ = [("cell", C.c_int), ("cap", C.c_int), ("max_rank", C.c_int)]
@@ -392,7 +426,7 @@ class Fusion(C.Structure):
 
 
 # the struct settings: ofk_set_<name> / ofk_get_<name> take the context and a pointer to the struct
-SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("gyro_bias", GyroBias), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate),
+SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("gyro_bias", GyroBias), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate), ("lk_light", LkLight),
             ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion))
 
 _lib = None
@@ -486,6 +520,7 @@ def load_library():
         L.ofk_finite_correct_points.argtypes = [vp, C.POINTER(FiniteMotion), vp, vp, vp, i, i, vp, vp, vp]
         L.ofk_finite_download.argtypes = [vp, vp, vp, i]
         L.ofk_lk_pyr_fb.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, i, vp, vp, vp, C.POINTER(TrackGate), vp, vp, vp]
+        L.ofk_lk_pyr_light.argtypes = L.ofk_lk_pyr_fb.argtypes + [C.POINTER(LkLight)]
         L.ofk_imu_propagate.argtypes = [vp, vp, vp, i]
         L.ofk_post_solve.argtypes = [vp, vp, vp, vp, vp, i, vp]
         L.ofk_associate_sensors.argtypes = [vp, vp, i, vp, vp, vp, i, vp, vp, i, vp, vp, vp]
@@ -759,12 +794,14 @@ class Context:
         return pts, cnt
 
     def lk_pyr(self, prev, nxt, prev_pts, counts=None, win=15, max_level=3, max_count=20, eps=0.03, min_eig_thr=1e-4, next_pts=None,
-               flags=0):
+               flags=0, light=None):
         """Batched calcOpticalFlowPyrLK.  Single image: prev_pts (N,1,2)/(N,2) -> (next (N,1,2), status (N,1), err (N,1)).
         Batch: prev_pts [B,S,2] + counts [B] -> (next [B,S,2], status [B,S], err [B,S]).
         flags: LK_USE_INITIAL_FLOW (the search starts at next_pts, same shape as prev_pts) | LK_GET_MIN_EIGENVALS (err = level-0
-        minEig); with flags == 0 and no next_pts this is ofk_lk_pyr, otherwise ofk_lk_pyr_ex."""
+        minEig); with flags == 0 and no next_pts this is ofk_lk_pyr, otherwise ofk_lk_pyr_ex.
+        light: None, "bias", "gain" or an LkLight - the lighting-insensitive tracker, ofk_lk_pyr_light (only when given and on)."""
         flags = int(flags)
+        light = _light(light)
         if flags & ~(LK_USE_INITIAL_FLOW | LK_GET_MIN_EIGENVALS):
             raise ValueError(f"lk_pyr: unknown flag bits {flags:#x}")
         if flags & LK_USE_INITIAL_FLOW and next_pts is None:
@@ -797,7 +834,11 @@ class Context:
             return z, np.zeros((0, 1), np.uint8), np.zeros((0, 1), np.float32)
         nxt_pts = np.zeros((B, S, 2), np.float32); st = np.zeros((B, S), np.uint8); err = np.zeros((B, S), np.float32)
         with self._lock:
-            if flags == 0:
+            if light is not None:
+                self._ck(self._L.ofk_lk_pyr_light(self._h, _p(prev), _p(nxt), B, h, w, _p(pp), _p(counts), S, int(win), int(max_level),
+                                                  int(max_count), float(eps), float(min_eig_thr), _p(init) if init is not None else None,
+                                                  flags, _p(nxt_pts), _p(st), _p(err), None, None, None, None, C.byref(light)))
+            elif flags == 0:
                 self._ck(self._L.ofk_lk_pyr(self._h, _p(prev), _p(nxt), B, h, w, _p(pp), _p(counts), S, int(win), int(max_level),
                                             int(max_count), float(eps), float(min_eig_thr), _p(nxt_pts), _p(st), _p(err)))
             else:
@@ -841,6 +882,17 @@ class Context:
 
     def get_track_gate(self):
         return self._get_struct(self._L.ofk_get_track_gate, TrackGate)
+
+    def set_lk_light(self, light=None, **settings):
+        """ofk_set_lk_light: an LkLight, a mode name (or lk_light_setting's keywords); None or mode "off" switches it off.  Every
+        later pairs_run and stream step tracks with a gain and a bias per window taken out (the backward pass of a forward-backward
+        gate too); everything behind LK sees only different next / status / err."""
+        if isinstance(light, (str, int)):
+            light = lk_light_setting(light, **settings); settings = {}
+        self._set_struct(self._L.ofk_set_lk_light, light, settings, lk_light_setting, lock=True)
+
+    def get_lk_light(self):
+        return self._get_struct(self._L.ofk_get_lk_light, LkLight)
 
     def set_corner_grid(self, grid=None, **settings):
         """ofk_set_corner_grid: a CornerGrid (or corner_grid_setting's keywords); None switches the grid off.  Every later corner
@@ -1002,10 +1054,12 @@ class Context:
         return self.track_gate_download(batch, points=False)["stats"]
 
     def lk_pyr_fb(self, prev, nxt, prev_pts, counts, gate=None, win=15, max_level=3, max_count=20, eps=0.03, min_eig_thr=1e-4,
-                  next_pts=None, flags=0, **settings):
+                  next_pts=None, flags=0, light=None, **settings):
         """ofk_lk_pyr_fb: the batched lk_pyr (prev, nxt [B,h,w]; prev_pts [B,S,2]; counts [B]) with the track gates behind it.
-        gate: a TrackGate, or track_gate_setting's keywords.  -> dict(next_pts, status (gated), err, back_pts, back_status, fb2)."""
+        gate: a TrackGate, or track_gate_setting's keywords.  -> dict(next_pts, status (gated), err, back_pts, back_status, fb2).
+        light: None, "bias", "gain" or an LkLight - both passes under ofk_lk_light, ofk_lk_pyr_light (only when given and on)."""
         g = gate if gate is not None else track_gate_setting(**settings)
+        light = _light(light)
         flags = int(flags)
         if flags & LK_USE_INITIAL_FLOW and next_pts is None:
             raise ValueError("lk_pyr_fb: LK_USE_INITIAL_FLOW needs next_pts")
@@ -1025,10 +1079,11 @@ class Context:
                 raise ValueError(f"lk_pyr_fb: next_pts {init.shape} does not match prev_pts {pp.shape}")
         out = dict(next_pts=np.zeros((B, S, 2), np.float32), status=np.zeros((B, S), np.uint8), err=np.zeros((B, S), np.float32),
                    back_pts=np.zeros((B, S, 2), np.float32), back_status=np.zeros((B, S), np.uint8), fb2=np.zeros((B, S), np.float32))
+        args = (self._h, _p(prev), _p(nxt), B, h, w, _p(pp), _p(counts), S, int(win), int(max_level), int(max_count), float(eps),
+                float(min_eig_thr), _p(init), flags, _p(out["next_pts"]), _p(out["status"]), _p(out["err"]), C.byref(g), _p(out["back_pts"]),
+                _p(out["back_status"]), _p(out["fb2"]))
         with self._lock:
-            self._ck(self._L.ofk_lk_pyr_fb(self._h, _p(prev), _p(nxt), B, h, w, _p(pp), _p(counts), S, int(win), int(max_level), int(max_count),
-                                           float(eps), float(min_eig_thr), _p(init), flags, _p(out["next_pts"]), _p(out["status"]),
-                                           _p(out["err"]), C.byref(g), _p(out["back_pts"]), _p(out["back_status"]), _p(out["fb2"])))
+            self._ck(self._L.ofk_lk_pyr_fb(*args) if light is None else self._L.ofk_lk_pyr_light(*args, C.byref(light)))
         return out
 
     # ------------------------------------------------------------------ estimation

@@ -92,6 +92,9 @@ class PipelineConfig:
     fb_thr: float = 0.5
     fb_level: int = -1
     err_max: float = 0.0
+    # lighting-insensitive LK (ofk.h: ofk_set_lk_light): None, "bias" (a brightness offset per window), "gain" (a gain and an offset)
+    # or an ofk.LkLight; the forward LK and the backward pass of fb_check then track under it
+    lk_light: object = None
     # corner grid (ofk.h: ofk_set_corner_grid): at most grid_cap corners per grid_cell x grid_cell pixel cell in every selection,
     # grid_cell 0 = off; grid_max_rank > 0: only that many leading candidates are looked at
     grid_cell: int = 0
@@ -189,6 +192,10 @@ class PipelineConfig:
         if self.fb_check == "off" and self.err_max == 0.0:
             return None
         return ofk.track_gate_setting(self.fb_check, self.fb_thr, self.fb_level, self.err_max)
+
+    def lk_light_setting(self):
+        """The ofk.LkLight structure of this configuration, None when the lighting-insensitive LK is off."""
+        return ofk._light(self.lk_light)
 
     def corner_grid_setting(self):
         """The ofk.CornerGrid structure of this configuration, None when the grid is off."""
@@ -371,7 +378,8 @@ def _apply_settings(ctx, cfg, zones):
     whether the exclusion zones and the gyro bias are among them (they belong to the stream steps)."""
     if cfg.lk_seed != "off":
         ctx.set_lk_seed(cfg.lk_seed, cfg.seed_gain)
-    steps = [(ctx.set_robust, cfg.robust_setting), (ctx.set_track_gate, cfg.track_gate_setting), (ctx.set_corner_grid, cfg.corner_grid_setting),
+    steps = [(ctx.set_robust, cfg.robust_setting), (ctx.set_track_gate, cfg.track_gate_setting), (ctx.set_lk_light, cfg.lk_light_setting),
+             (ctx.set_corner_grid, cfg.corner_grid_setting),
              (ctx.set_cov, cfg.cov_setting), (ctx.set_joint, cfg.joint_setting), (ctx.set_plane, cfg.plane_setting),
              (ctx.set_epipolar, cfg.epipolar_setting)]
     if zones:

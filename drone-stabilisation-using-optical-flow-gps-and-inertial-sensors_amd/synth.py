@@ -237,6 +237,22 @@ def warp_frame(bgr, H):
     return out
 
 
+def apply_exposure(img, gain=1.0, bias=0.0, vignette=0.0):
+    """A gray [h,w] or BGR [h,w,3] uint8 frame under another exposure: clip(rint(img * gain * f + bias), 0, 255) with the vignette
+    f = 1 - vignette * r^2, r^2 = ((x - w/2)^2 + (y - h/2)^2) / ((w/2)^2 + (h/2)^2) - what auto-exposure and a lens's fall-off do
+    between the two frames of a pair (ofk.h: ofk_lk_light)."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise ValueError(f"apply_exposure: {img.dtype} {img.shape} is no gray or BGR uint8 frame")
+    h, w = img.shape[:2]
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    r2 = ((xx - w / 2.0) ** 2 + (yy - h / 2.0) ** 2) / ((w / 2.0) ** 2 + (h / 2.0) ** 2)
+    f = 1.0 - float(vignette) * r2
+    if img.ndim == 3:
+        f = f[..., None]
+    return np.clip(np.rint(img.astype(np.float64) * float(gain) * f + float(bias)), 0, 255).astype(np.uint8)
+
+
 def render_sequence(h, w, seed, n_frames, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.003), d=1.0, n=(0, 0, 1),
                     scaling=None, margin=96, camera=None, rolling_shutter=None, motion="linear"):
     """`n_frames` BGR frames of one stream under constant per-frame motion: frame k shows the texture through H^k.

@@ -546,6 +546,46 @@ int ofk_lk_pyr_fb(ofk_ctx *ctx, const uint8_t *prev, const uint8_t *next, int ba
                   const float *init_pts, int flags, float *next_pts, uint8_t *status, float *err, const ofk_track_gate *g,
                   float *back_pts, uint8_t *back_status, float *fb2);
 
+/* Lighting-insensitive LK: a gain alpha and a bias beta per window and Newton step, so that the tracker matches alpha J + beta
+ * against I instead of J against I (auto-exposure between the two frames, vignetting across them).  Off by default; with it off
+ * every entry point launches the kernels and returns the bits it always did.  With it on the tracker is kernels of its own
+ * (k_lk_light, one wave per point); pyramid, level walk, bounds tests, the fixed-point bilinear weights, Ip / Ixp / Iyp, A11 / A12 /
+ * A22, minEig, the status rules, the 2x2 solve, both stopping rules, OFK_LK_USE_INITIAL_FLOW and OFK_LK_GET_MIN_EIGENVALS are those
+ * of ofk_lk_pyr_ex.  What changes is the mismatch vector and the residual err.  N = win * win; every sum below is an exact 64-bit
+ * integer over the window and does not depend on the order of summation; I is the descaled template sample Ip (<= 8160), J the
+ * interpolated next-frame sample of the step.
+ *   1. Template sums, once per level: SI = sum I, SII = sum I^2, SIx = sum Ix, SIy = sum Iy, SIIx = sum I Ix, SIIy = sum I Iy.
+ *   2. Per Newton step: SJ = sum J, SJJ = sum J^2, SJx = sum J Ix, SJy = sum J Iy.
+ *   3. vI = N SII - SI^2, vJ = N SJJ - SJ^2.
+ *   4. alpha, in f64: 1 in mode OFK_LIGHT_BIAS or when vI <= 0 or vJ <= 0; otherwise sqrt((double)vI / (double)vJ) - one division,
+ *      one square root, both IEEE-rounded - clamped to [lo, gain_max] with lo = 1.0 / gain_max formed once on the host.
+ *   5. Mismatch vector, in f64 in exactly this order, no contraction: cJx = N SJx - SJ SIx, cIx = N SIIx - SI SIx,
+ *      b1 = (float)(((alpha * (double)cJx - (double)cIx) / (double)N) * 2^-20); b2 likewise with y.  This is
+ *      sum (alpha J + beta - I) Ix with beta = mean I - alpha mean J.
+ *   6. err, without OFK_LK_GET_MIN_EIGENVALS: at the final position SJ, SJJ and alpha as above, a12 = (int64)llrint(alpha * 4096),
+ *      r_k = a12 (N J_k - SJ) - 4096 (N I_k - SI), err = (float)((double)sum |r_k| / (4096.0 * N * 32 * N)): the mean absolute
+ *      residual of the compensated window in the units of the plain err, so ofk_track_gate.err_max keeps its meaning.
+ * ofk_set_lk_light (NULL or mode OFK_LIGHT_OFF: off) is a context setting read by the forward LK of ofk_pairs_run (every slice),
+ * ofk_stream_step[_jpeg] and ofk_stream_step_fused[_jpeg] and by the backward pass of their forward-backward gate; everything
+ * behind LK sees only different next / status / err.  An unknown mode, or a gain_max that is not finite or is <= 1, returns
+ * OFK_E_INVALID and leaves the previous setting in place.  ofk_lk_pyr, ofk_lk_pyr_ex and ofk_lk_pyr_fb do not read the setting.
+ * ofk_lk_pyr_light = ofk_lk_pyr_fb plus the setting as an argument (forward and backward pass): light == NULL or mode
+ * OFK_LIGHT_OFF is ofk_lk_pyr_fb itself, the same launches and the same bits; any other light is held to the setter's rules before
+ * any launch. */
+#define OFK_LIGHT_OFF 0
+#define OFK_LIGHT_BIAS 1   /* beta alone (alpha = 1) */
+#define OFK_LIGHT_GAIN 2   /* alpha and beta */
+typedef struct ofk_lk_light {
+    int    mode;       /* OFK_LIGHT_* */
+    double gain_max;   /* finite, > 1; default 4: alpha is clamped to [1 / gain_max, gain_max] */
+} ofk_lk_light;
+int ofk_set_lk_light(ofk_ctx *ctx, const ofk_lk_light *light);   /* NULL or OFF: off */
+int ofk_get_lk_light(const ofk_ctx *ctx, ofk_lk_light *light);
+int ofk_lk_pyr_light(ofk_ctx *ctx, const uint8_t *prev, const uint8_t *next, int batch, int h, int w, const float *prev_pts,
+                     const int *counts, int pts_stride, int win, int max_level, int max_count, double eps, double min_eig_thr,
+                     const float *init_pts, int flags, float *next_pts, uint8_t *status, float *err, const ofk_track_gate *g,
+                     float *back_pts, uint8_t *back_status, float *fb2, const ofk_lk_light *light);
+
 /* The velocity covariance: first-order error propagation through the velocity solve, and a filter correct that uses it in the place of
  * the constant R.  (The reference carries vel_err, feat_err, flow_err, ang_err, d_err, normal_err through every callback of its node
  * and never reads them; its simulation.py estimates the same dependence from 100 noisy re-solves per step.)  Off by default; with it
