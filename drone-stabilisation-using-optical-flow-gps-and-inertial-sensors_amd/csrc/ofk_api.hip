@@ -159,6 +159,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->camera = ofk_camera{OFK_CAMERA_OFF, 20, 1.0, 1.0, 0.0, 0.0, {0, 0, 0, 0, 0, 0, 0, 0}, 1.0, 1.0, 0.0, 0.0};
     c->rs = ofk_rshutter{OFK_RS_OFF, 0, 0.0, 0.5, 1.0};
     c->fm = ofk_finite_motion{OFK_FM_OFF, 0.1};
+    c->tt = ofk_track_table{OFK_TT_OFF, OFK_TT_SEED_OFF, 1.0};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -212,7 +213,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
                     c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec, c->joint_rec, c->bias_rec, c->plane_rec, c->epi_rec,
-                    c->zone_tab, c->pts_prev_u};
+                    c->zone_tab, c->pts_prev_u, c->ttr.ids};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
@@ -916,7 +917,10 @@ static int gate_tracks(ofk_ctx *c, hipStream_t s, const View &v, const ofk_level
 // the previous points' earlier.  With ofk_set_rolling_shutter on, one k_rs_correct launch follows: it reads the raw rows and the
 // ideal points (the camera's, corrected in place, or the raw points themselves) and writes what the solve stage reads.  With
 // ofk_set_finite_motion on, one k_finite_correct launch follows that: in place on those buffers, or from the raw points into them.
-static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, const ofk_params *p, const double *imu_state)
+// tt != NULL (a stream step with ofk_set_track_table's seed on; the view is the whole batch): the k_track_seed launch of rule 5 behind
+// the model seeds, and LK starts at what both have written.
+static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, const ofk_params *p, const double *imu_state,
+                 const ofk_tt_rows *tt = nullptr)
 {
     const bool seeded = c->lk_seed_mode != OFK_SEED_OFF, cam = camera_on(c);
     if (seeded && cam) {
@@ -925,8 +929,9 @@ static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv,
         ofk_launch_camera(s, &c->camera, 1, v.pts_next, v.pts_next, nullptr, nullptr, v.counts, c->max_pts, v.nb);
     } else if (seeded)
         ofk_launch_seed_points(s, v.pts_prev, v.counts, c->max_pts, v.sensors, imu_state, c->lk_seed_mode, c->lk_seed_gain, v.pts_next, v.nb);
+    if (tt) ofk_launch_track_seed(s, v.pts_prev, v.counts, c->max_pts, tt->age, tt->flow_xy, (float)c->tt.gain, seeded ? 1 : 0, v.pts_next, v.nb);
     launch_lk(s, v.pyr[0], v.pyr[1], c->pyr_stride, lv, v.pts_prev, v.counts, c->max_pts, p->win, p->max_count, p->eps, p->min_eig_thr,
-              v.pts_next, v.status, v.err, v.nb, seeded ? OFK_LK_USE_INITIAL_FLOW : 0, c->light);
+              v.pts_next, v.status, v.err, v.nb, seeded || tt ? OFK_LK_USE_INITIAL_FLOW : 0, c->light);
     if (gate_on(c->gate)) TRY(gate_tracks(c, s, v, lv, p->win, p->max_level, p->max_count, p->eps, p->min_eig_thr, c->gate, c->light));
     if (cam && seeded) ofk_launch_camera(s, &c->camera, 0, v.pts_next, v.pts_next_u, nullptr, nullptr, v.counts, c->max_pts, v.nb);
     else if (cam) ofk_launch_camera(s, &c->camera, 0, v.pts_prev, v.pts_prev_u, v.pts_next, v.pts_next_u, v.counts, c->max_pts, v.nb);
@@ -2430,6 +2435,137 @@ extern "C" int ofk_zones_step(ofk_ctx *c, const float *old_pts, const float *new
     return d2h(c, mask_out, c->mask, c->img_stride, (size_t)h * w, batch);
 }
 
+// ------------------------------------------------------------------------------------------------ track table
+static int check_tt(ofk_ctx *c, const ofk_track_table *t, const char *who)
+{
+    if (t->mode != OFK_TT_OFF && t->mode != OFK_TT_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_TT_OFF nor OFK_TT_ON", who, t->mode);
+    if (t->mode == OFK_TT_OFF) return OFK_OK;
+    if (t->seed != OFK_TT_SEED_OFF && t->seed != OFK_TT_SEED_FLOW)
+        return ofk_fail(c, OFK_E_INVALID, "%s: seed %d is neither OFK_TT_SEED_OFF nor OFK_TT_SEED_FLOW", who, t->seed);
+    if (!std::isfinite(t->gain)) return ofk_fail(c, OFK_E_INVALID, "%s: gain = %g must be finite", who, t->gain);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_track_table(ofk_ctx *c, const ofk_track_table *t)
+{
+    return setting_set(c, &ofk_ctx::tt, t && t->mode == OFK_TT_OFF ? nullptr : t, [](ofk_track_table &s) { s.mode = OFK_TT_OFF; },
+                       [c](const ofk_track_table *v) { return check_tt(c, v, "ofk_set_track_table"); });
+}
+extern "C" int ofk_get_track_table(const ofk_ctx *c, ofk_track_table *t) { return setting_get(c, &ofk_ctx::tt, t); }
+
+// the table's arrays over `np` rows and `batch` streams carved out of base (NULL: nothing is carved); returns the bytes they take
+static size_t tt_carve(ofk_tt_rows &t, uint8_t *base, size_t np, size_t batch)
+{
+    size_t o = 0;
+    auto take = [&](size_t bytes) { uint8_t *p = base ? base + o : nullptr; o += up(bytes, 256); return p; };
+    t.ids = (unsigned *)take(np * 4); t.age = (int *)take(np * 4); t.birth_step = (int *)take(np * 4);
+    t.birth_xy = (float *)take(np * 8); t.flow_xy = (float *)take(np * 8); t.step_ids = (unsigned *)take(np * 4);
+    t.head = (int *)take(batch * 8); t.stats = (int *)take(batch * OFK_TT_STATS * 4);
+    return o;
+}
+// the resident table, allocated (and cleared) when a stream first begins or steps with the setting on
+static int tt_alloc(ofk_ctx *c)
+{
+    if (c->ttr.ids) return OFK_OK;                               // one allocation, carved into the eight arrays
+    ofk_tt_rows t;
+    const size_t np = (size_t)c->max_batch * c->max_pts, bytes = tt_carve(t, nullptr, np, (size_t)c->max_batch);
+    uint8_t *base = nullptr;
+    OFK_HIP(c, hipMalloc((void **)&base, bytes));
+    OFK_HIP(c, hipMemsetAsync(base, 0, bytes, c->stream));
+    tt_carve(c->ttr, base, np, (size_t)c->max_batch);
+    return OFK_OK;
+}
+static bool tt_on(const ofk_ctx *c) { return c->tt.mode != OFK_TT_OFF; }
+
+extern "C" int ofk_track_table_download(ofk_ctx *c, uint32_t *ids, int *age, int *birth_step, float *birth_xy, float *flow_xy, uint32_t *step_ids,
+                                        int stride, int *stats)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->tt_batch < 1 || !c->ttr.ids) return ofk_fail(c, OFK_E_INVALID, "ofk_track_table_download: no stream has run with ofk_set_track_table on yet");
+    if ((ids || age || birth_step || birth_xy || flow_xy || step_ids) && stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_track_table_download: stride %d", stride);
+    TRY(enter(c));
+    const int B = c->tt_batch;
+    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    const ofk_tt_rows &t = c->ttr;
+    struct { void *dst; const void *src; size_t el; } rows[] = {{ids, t.ids, 4}, {age, t.age, 4}, {birth_step, t.birth_step, 4}, {birth_xy, t.birth_xy, 8},
+                                                                 {flow_xy, t.flow_xy, 8}, {step_ids, t.step_ids, 4}};
+    for (const auto &r : rows)
+        if (r.dst) OFK_HIP(c, hipMemcpy2DAsync(r.dst, (size_t)stride * r.el, r.src, mp * r.el, n * r.el, B, hipMemcpyDeviceToHost, c->stream));
+    if (stats) OFK_HIP(c, hipMemcpyAsync(stats, t.stats, (size_t)B * OFK_TT_STATS * 4, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+// rules 3 and 6 on host buffers: device scratch only
+extern "C" int ofk_track_table_step(ofk_ctx *c, const ofk_track_table *set, uint32_t *ids, int *age, int *birth_step, float *birth_xy, float *flow_xy,
+                                    int *head, const float *prev_pts, const float *next_pts, const uint8_t *status, int *counts,
+                                    const float *new_pts, const int *new_counts, int max_total, int batch, int stride, uint32_t *step_ids, int *stats)
+{
+    const char *who = "ofk_track_table_step";
+    if (!c) return OFK_E_INVALID;
+    if (!ids || !age || !birth_step || !birth_xy || !flow_xy || !head || !prev_pts || !next_pts || !status || !counts)
+        return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
+    if (batch < 1 || stride < 1) return ofk_fail(c, OFK_E_INVALID, "%s: batch %d / stride %d", who, batch, stride);
+    if ((new_pts == nullptr) != (new_counts == nullptr)) return ofk_fail(c, OFK_E_INVALID, "%s: new_pts and new_counts come together", who);
+    if (max_total < 0 || max_total > stride) return ofk_fail(c, OFK_E_INVALID, "%s: max_total %d outside 0..%d", who, max_total, stride);
+    TRY(check_counts(c, who, counts, batch, stride));
+    if (set) TRY(check_tt(c, set, who));
+    const size_t np = (size_t)batch * stride;
+    Bump bp;
+    TRY(est_begin(c, np * 64 + (size_t)batch * 64 + 24 * 256, bp));
+    ofk_tt_rows t;
+    t.ids = (unsigned *)bp.put(ids, np * 4); t.age = (int *)bp.put(age, np * 4); t.birth_step = (int *)bp.put(birth_step, np * 4);
+    t.birth_xy = (float *)bp.put(birth_xy, np * 8); t.flow_xy = (float *)bp.put(flow_xy, np * 8);
+    t.step_ids = (unsigned *)bp.take(np * 4); t.head = (int *)bp.put(head, (size_t)batch * 8); t.stats = (int *)bp.take((size_t)batch * OFK_TT_STATS * 4);
+    const float *d_prev = (const float *)bp.put(prev_pts, np * 8), *d_next = (const float *)bp.put(next_pts, np * 8);
+    const uint8_t *d_st = (const uint8_t *)bp.put(status, np);
+    const int *d_cnt = (const int *)bp.put(counts, (size_t)batch * 4);
+    const float *d_new = (const float *)bp.put(new_pts, np * 8);
+    const int *d_nc = (const int *)bp.put(new_counts, (size_t)batch * 4);
+    if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    OFK_HIP(c, hipMemsetAsync(t.step_ids, 0, np * 4, c->stream));
+    const bool seed = set && set->mode != OFK_TT_OFF && set->seed == OFK_TT_SEED_FLOW;
+    ofk_launch_track_table_update(c->stream, t, d_prev, d_next, d_st, d_cnt, stride, d_new, d_nc, max_total, seed ? 1 : 0, seed ? (float)set->gain : 0.f, batch);
+    TRY(check_launch(c, "k_track_table_update"));
+    int *h_stats = (int *)malloc((size_t)batch * OFK_TT_STATS * 4);
+    if (!h_stats) return ofk_fail(c, OFK_E_INVALID, "%s: out of host memory", who);
+    struct { void *dst; const void *src; size_t bytes; } back[] = {{ids, t.ids, np * 4}, {age, t.age, np * 4}, {birth_step, t.birth_step, np * 4},
+        {birth_xy, t.birth_xy, np * 8}, {flow_xy, t.flow_xy, np * 8}, {step_ids, t.step_ids, np * 4}, {head, t.head, (size_t)batch * 8},
+        {h_stats, t.stats, (size_t)batch * OFK_TT_STATS * 4}};
+    hipError_t e = hipSuccess;
+    for (const auto &r : back)
+        if (r.dst && e == hipSuccess) e = hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) {
+        for (int b = 0; b < batch; ++b) counts[b] = h_stats[(size_t)b * OFK_TT_STATS];
+        if (stats) memcpy(stats, h_stats, (size_t)batch * OFK_TT_STATS * 4);
+    }
+    free(h_stats);
+    if (e != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: download failed: %s", who, hipGetErrorString(e));
+    return OFK_OK;
+}
+
+// rule 5 on host buffers: device scratch only
+extern "C" int ofk_track_seed_points(ofk_ctx *c, const float *pts, const int *counts, int batch, int stride, const int *age, const float *flow_xy,
+                                     double gain, int keep_age0, float *seed_io)
+{
+    const char *who = "ofk_track_seed_points";
+    if (!c) return OFK_E_INVALID;
+    if (!pts || !counts || !age || !flow_xy || !seed_io || batch < 1 || stride < 1) return ofk_fail(c, OFK_E_INVALID, "%s: bad argument", who);
+    if (!std::isfinite(gain)) return ofk_fail(c, OFK_E_INVALID, "%s: gain = %g must be finite", who, gain);
+    TRY(check_counts(c, who, counts, batch, stride));
+    const size_t np = (size_t)batch * stride;
+    Bump bp;
+    TRY(est_begin(c, np * 28 + (size_t)batch * 4 + 8 * 256, bp));
+    const float *d_pts = (const float *)bp.put(pts, np * 8), *d_flow = (const float *)bp.put(flow_xy, np * 8);
+    float *d_seed = (float *)bp.put(seed_io, np * 8);
+    const int *d_age = (const int *)bp.put(age, np * 4), *d_cnt = (const int *)bp.put(counts, (size_t)batch * 4);
+    if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    ofk_launch_track_seed(c->stream, d_pts, d_cnt, stride, d_age, d_flow, (float)gain, keep_age0 ? 1 : 0, d_seed, batch);
+    TRY(check_launch(c, "k_track_seed"));
+    return get(c, seed_io, d_seed, np * 8);
+}
+
 // ------------------------------------------------------------------------------------------------ video streams
 static int stream_alloc(ofk_ctx *c)
 {
@@ -2488,6 +2624,12 @@ static int stream_begin_impl(ofk_ctx *c, const uint8_t *first_bgr, int batch, in
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     TRY(stream_ingest(c, 0, first_bgr, batch, h, w, lv));
     TRY(stream_detect(c, nullptr, nullptr, batch, h, w, p, c->pts_prev, c->counts));
+    c->tt_batch = c->tt_live = 0;                                // ... and with a new track table, if the setting is on
+    if (tt_on(c)) {
+        TRY(tt_alloc(c));
+        ofk_launch_track_table_begin(c->stream, c->ttr, c->pts_prev, c->counts, c->max_pts, batch);
+        c->tt_batch = c->tt_live = batch;
+    }
     c->stream_h = h; c->stream_w = w; c->stream_batch = batch;
     return stream_fetch_tracks(c, batch, p->max_corners, tracks, counts);
 }
@@ -2659,6 +2801,14 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         void now() { if (ist) ofk_launch_gyro_bias_apply(c->stream, nullptr, 0, ist, c->bias_rec, B, 1); ist = nullptr; }
         ~bias_restore() { now(); }
     } restore = {c, bias_ist, B};
+    const bool table = tt_on(c);
+    if (table) {
+        TRY(tt_alloc(c));
+        if (c->tt_live != B) ofk_launch_track_table_begin(c->stream, c->ttr, c->pts_prev, c->counts, c->max_pts, B);   // no table of these tracks yet
+        c->tt_batch = c->tt_live = B;
+    } else
+        c->tt_live = 0;                                          // the tracks move on without their table
+    const bool flow_seed = table && c->tt.seed == OFK_TT_SEED_FLOW;
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
     if (fu && fu->redetect_replace && few) {
@@ -2671,11 +2821,12 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         }
         TRY(stream_detect(c, zones_on ? c->mask : nullptr, c->limit, B, h, w, p, c->pts_new, c->new_counts));
         ofk_launch_replace_tracks(c->stream, c->limit, c->pts_new, c->new_counts, c->max_pts, c->pts_prev, c->counts, B);
+        if (table) ofk_launch_track_table_replace(c->stream, c->ttr, c->limit, c->pts_new, c->new_counts, c->max_pts, B);
     }
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)
     const View v = view_of(c, 0, B, 0);                          // the solve stage reads v.solve_*; the tracks, the zones and the re-detection stay in the image
-    TRY(track(c, c->stream, v, lv, p, fu && fu->use_imu ? c->imu_state : nullptr));
+    TRY(track(c, c->stream, v, lv, p, fu && fu->use_imu ? c->imu_state : nullptr, flow_seed ? &c->ttr : nullptr));
     if (zones_on)                                                // the solve stage turns the status into its keep flags: rule 1 needs both
         OFK_HIP(c, hipMemcpyAsync(c->zone_status, c->status, (size_t)B * c->max_pts, hipMemcpyDeviceToDevice, c->stream));
     if (fu) {
@@ -2719,9 +2870,13 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         TRY(stream_detect(c, c->mask, c->limit, B, h, w, p, c->pts_new, c->new_counts, c->pts_prev, c->counts));
     }
     // tracks := new[status == 1] ++ re-detected (node:134,166); the new frame becomes the previous one (node:175)
-    if (!hold)
+    if (!hold) {
+        if (table)                                               // in front of it: it overwrites pts_prev and counts
+            ofk_launch_track_table_update(c->stream, c->ttr, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, any ? c->pts_new : nullptr,
+                                          any ? c->new_counts : nullptr, p->max_corners, flow_seed ? 1 : 0, flow_seed ? (float)c->tt.gain : 0.f, B);
         ofk_launch_update_tracks(c->stream, c->pts_next, c->status, c->counts, c->max_pts, any ? c->pts_new : nullptr, any ? c->new_counts : nullptr,
                                  c->pts_prev, c->counts, p->max_corners, B);
+    }
     restore.now();                                               // the step's last launch: the IMU state's raw omega back, bit for bit
     TRY(check_launch(c, "ofk_stream_step"));
     if (records) OFK_HIP(c, hipMemcpyAsync(records, c->records, (size_t)B * OFK_RECORD_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));

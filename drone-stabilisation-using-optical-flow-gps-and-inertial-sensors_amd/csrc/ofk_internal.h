@@ -19,6 +19,9 @@ struct ofk_levels {
     size_t off[OFK_MAX_LEVELS];     // byte offset of level l inside one image's pyramid slab (256-B aligned)
 };
 
+// the track table's arrays (ofk.h: ofk_set_track_table), rows `stride` apart per stream
+struct ofk_tt_rows { unsigned *ids; int *age, *birth_step; float *birth_xy, *flow_xy; unsigned *step_ids; int *head, *stats; };
+
 struct ofk_comm;
 struct ofk_ctx {
     int device;
@@ -115,6 +118,9 @@ struct ofk_ctx {
     int rs_batch;                            // images of the latest run / step with the rolling shutter on (ofk_rs_download), 0 = none
     ofk_finite_motion fm;                    // ofk_set_finite_motion: mode OFK_FM_OFF unless set; with it on the solve stage reads pts_prev_u / pts_next_u too
     int fm_batch;                            // images of the latest run / step with the finite motion on (ofk_finite_download), 0 = none
+    ofk_track_table tt;                      // ofk_set_track_table: mode OFK_TT_OFF (gain 1) unless set
+    ofk_tt_rows ttr;                         // the table's device rows, [B][max_pts] each, head [B][2], stats [B][OFK_TT_STATS]; one lazy allocation (ttr.ids owns it)
+    int tt_batch, tt_live;                   // streams of the latest begin / step with the table on (ofk_track_table_download), 0 = none; streams whose rows match their current tracks
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -230,6 +236,16 @@ void ofk_launch_seed_points(hipStream_t s, const float *pts, const int *counts, 
 void ofk_launch_track_gate(hipStream_t s, const float *prev_pts, const float *back_pts, const uint8_t *st_back, const float *err,
                            const int *counts, int pts_stride, int fb_on, float thr2, int err_on, float err_max, uint8_t *status, float *fb2,
                            int *stats, int batch);
+// the track table (ofk.h: ofk_set_track_table; k_track_table.inc): rule 1 on freshly detected tracks, rule 2 behind k_replace_tracks,
+// rules 3 and 6 in front of k_update_tracks (its arguments; new_counts NULL = no re-detection), rule 5 into LK's start positions
+void ofk_launch_track_table_begin(hipStream_t s, const ofk_tt_rows &t, const float *pts, const int *counts, int stride, int batch);
+void ofk_launch_track_table_replace(hipStream_t s, const ofk_tt_rows &t, const int *limit, const float *new_pts, const int *new_counts,
+                                    int stride, int batch);
+void ofk_launch_track_table_update(hipStream_t s, const ofk_tt_rows &t, const float *prev_pts, const float *next_pts, const uint8_t *status,
+                                   const int *counts_in, int stride, const float *new_pts, const int *new_counts, int max_total, int seed_on,
+                                   float gain, int batch);
+void ofk_launch_track_seed(hipStream_t s, const float *pts, const int *counts, int stride, const int *age, const float *flow_xy, float gain,
+                           int keep_age0, float *seed, int batch);
 void ofk_launch_pairs_solve(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status,
                             const int *counts, int pts_stride, const double *sensors, int variant, int use_feas,
                             double feas_T, const int *cand_count, double *records, int batch);

@@ -40,6 +40,7 @@ SYMBOLS = (
     "ofk_set_camera", "ofk_get_camera", "ofk_undistort_points", "ofk_distort_points", "ofk_camera_download",
     "ofk_set_rolling_shutter", "ofk_get_rolling_shutter", "ofk_rs_correct_points", "ofk_rs_download",
     "ofk_set_finite_motion", "ofk_get_finite_motion", "ofk_finite_correct_points", "ofk_finite_download",
+    "ofk_set_track_table", "ofk_get_track_table", "ofk_track_table_download", "ofk_track_table_step", "ofk_track_seed_points",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
     "ofk_stream_begin_jpeg", "ofk_stream_step_jpeg",
@@ -100,6 +101,10 @@ RS_MODES = {"off": RS_OFF, "flow": RS_FLOW, "gyro": RS_GYRO}
 RS_MAX_ROWS = 65536
 FM_OFF, FM_EXACT = 0, 1                                  # ofk_set_finite_motion / ofk_finite_correct_points
 FM_MODES = {"off": FM_OFF, "exact": FM_EXACT}
+TT_OFF, TT_ON = 0, 1                                     # ofk_set_track_table
+TT_SEED_OFF, TT_SEED_FLOW = 0, 1
+TT_SEEDS = {"off": TT_SEED_OFF, "flow": TT_SEED_FLOW}
+TT_STATS = 8                                             # count, kept, lost, born, oldest age, step, next_id, rows seeded from their flow
 FLOW_LK, FLOW_ROTATIONAL = 0, 1
 KEEP_STATUS, KEEP_LEGACY = 0, 1
 CONTROL_SENSORS, CONTROL_IMU = 0, 1
@@ -418,6 +423,30 @@ def finite_motion_setting(mode="exact", min_depth=0.1):
     return FiniteMotion(mode, min_depth)
 
 
+class TrackTable(C.Structure):
+    """ofk_track_table (include/ofk.h): an id, an age, a birth and the last flow per track of a stream, and LK seeded from that flow."""
+    _fields_ = [("mode", C.c_int), ("seed", C.c_int), ("gain", C.c_double)]
+
+
+def track_table_setting(seed="off", gain=1.0, mode=TT_ON):
+    """A TrackTable structure from names: seed "off" / "flow" (or TT_SEED_*): LK starts at each track's position plus gain times its
+    last flow; mode TT_ON / TT_OFF.  Newborn tracks have no flow: at a reduced pyramid depth they need lk_seed or slow motion."""
+    mode = int(mode)
+    if mode not in (TT_OFF, TT_ON):
+        raise ValueError(f"track-table mode {mode} is none of TT_OFF, TT_ON")
+    if isinstance(seed, str):
+        if seed not in TT_SEEDS:
+            raise ValueError(f"track-table seed {seed!r} is none of {sorted(TT_SEEDS)}")
+        seed = TT_SEEDS[seed]
+    seed = int(seed)
+    if seed not in TT_SEEDS.values():
+        raise ValueError(f"track-table seed {seed} is none of TT_SEED_OFF, TT_SEED_FLOW")
+    gain = float(gain)
+    if mode != TT_OFF and not np.isfinite(gain):
+        raise ValueError(f"track-table gain {gain} must be finite")
+    return TrackTable(mode, seed, gain)
+
+
 class Fusion(C.Structure):
     """ofk_fusion (include/ofk.h): what ofk_stream_step_fused does between LK and the next frame."""
     _fields_ = [("use_imu", C.c_int), ("flow", C.c_int), ("keep", C.c_int), ("filter", C.c_int), ("control", C.c_int),
@@ -427,7 +456,8 @@ class Fusion(C.Structure):
 
 # the struct settings: ofk_set_<name> / ofk_get_<name> take the context and a pointer to the struct
 SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("gyro_bias", GyroBias), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate), ("lk_light", LkLight),
-            ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion))
+            ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion),
+            ("track_table", TrackTable))
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -519,6 +549,9 @@ def load_library():
         L.ofk_rs_download.argtypes = [vp, vp, vp, i]
         L.ofk_finite_correct_points.argtypes = [vp, C.POINTER(FiniteMotion), vp, vp, vp, i, i, vp, vp, vp]
         L.ofk_finite_download.argtypes = [vp, vp, vp, i]
+        L.ofk_track_table_download.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, vp]
+        L.ofk_track_table_step.argtypes = [vp, C.POINTER(TrackTable), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp]
+        L.ofk_track_seed_points.argtypes = [vp, vp, vp, i, i, vp, vp, d, i, vp]
         L.ofk_lk_pyr_fb.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, i, vp, vp, vp, C.POINTER(TrackGate), vp, vp, vp]
         L.ofk_lk_pyr_light.argtypes = L.ofk_lk_pyr_fb.argtypes + [C.POINTER(LkLight)]
         L.ofk_imu_propagate.argtypes = [vp, vp, vp, i]
@@ -915,6 +948,69 @@ class Context:
 
     def get_zones(self):
         return self._get_struct(self._L.ofk_get_zones, Zones)
+
+    def set_track_table(self, track_table=None, **settings):
+        """ofk_set_track_table: a TrackTable (or track_table_setting's keywords); None or mode TT_OFF switches it off.  Every later
+        stream begin and step keeps an id, an age, a birth and the last flow per track on the device; with seed "flow" LK starts
+        at each track's position plus its last flow.  pairs_run ignores the setting."""
+        self._set_struct(self._L.ofk_set_track_table, track_table, settings, track_table_setting, lock=True)
+
+    def get_track_table(self):
+        return self._get_struct(self._L.ofk_get_track_table, TrackTable)
+
+    def track_table_download(self, batch=None, stride=None):
+        """ofk_track_table_download -> dict(ids, step_ids [batch,stride] u32, age, birth_step [batch,stride] i32, birth_xy, flow_xy
+        [batch,stride,2] f32, stats [batch,8] i32: count, kept, lost, born, oldest age, step, next_id, rows seeded from their flow) of
+        the streams of the latest begin or step with the setting on.  Rows are in the order of the tracks that call returned; the
+        first stats[:, 0] of a stream are its tracks."""
+        S = self.max_pts if stride is None else int(stride)
+        if S < 1:
+            raise ValueError(f"track_table_download: stride {S}")
+        u, n, f = ((S,), np.uint32), ((S,), np.int32), ((S, 2), np.float32)
+        ids, age, bs, bxy, fxy, sid, st = self._rows(
+            "track_table_download", self.max_batch if batch is None else int(batch),
+            lambda *p: self._L.ofk_track_table_download(self._h, *p[:6], S, p[6]), u, n, n, f, f, u, ((TT_STATS,), np.int32))
+        return dict(ids=ids, age=age, birth_step=bs, birth_xy=bxy, flow_xy=fxy, step_ids=sid, stats=st)
+
+    def track_table_step(self, table, head, prev_pts, next_pts, status, counts, new_pts=None, new_counts=None, max_total=None,
+                         track_table=None):
+        """ofk_track_table_step, the stage entry: one update of the table on host arrays.  table: dict(ids, age, birth_step [B,S],
+        birth_xy, flow_xy [B,S,2]); head [B,2] = step, next_id; prev_pts / next_pts [B,S,2], status [B,S], counts [B]; new_pts [B,S,2]
+        / new_counts [B] the re-detected corners (None: none); max_total (default S); track_table: the setting whose seed and gain the
+        last statistic takes.  -> (table, head, counts, step_ids [B,S], stats [B,8]), new arrays.  Touches no resident state."""
+        pp = _arr(prev_pts, np.float32)
+        if pp.ndim != 3 or pp.shape[2] != 2 or pp.shape[1] < 1:
+            raise ValueError(f"track_table_step: prev_pts {pp.shape} is not [B, S >= 1, 2]")
+        B, S = pp.shape[:2]
+        pn = _arr(next_pts, np.float32, (B, S, 2)); st = _arr(status, np.uint8, (B, S))
+        cn = np.array(_arr(counts, np.int32, (B,)))
+        ids = np.array(_arr(table["ids"], np.uint32, (B, S))); age = np.array(_arr(table["age"], np.int32, (B, S)))
+        bs = np.array(_arr(table["birth_step"], np.int32, (B, S)))
+        bxy = np.array(_arr(table["birth_xy"], np.float32, (B, S, 2))); fxy = np.array(_arr(table["flow_xy"], np.float32, (B, S, 2)))
+        hd = np.array(_arr(head, np.int32, (B, 2)))
+        if (new_pts is None) != (new_counts is None):
+            raise ValueError("track_table_step: new_pts and new_counts come together")
+        nw = _opt(new_pts, np.float32, (B, S, 2)); nc = _opt(new_counts, np.int32, (B,))
+        sid = np.zeros((B, S), np.uint32); stats = np.zeros((B, TT_STATS), np.int32)
+        with self._lock:
+            self._ck(self._L.ofk_track_table_step(self._h, C.byref(track_table) if track_table is not None else None, _p(ids), _p(age), _p(bs),
+                                                  _p(bxy), _p(fxy), _p(hd), _p(pp), _p(pn), _p(st), _p(cn), _p(nw), _p(nc),
+                                                  S if max_total is None else int(max_total), B, S, _p(sid), _p(stats)))
+        return dict(ids=ids, age=age, birth_step=bs, birth_xy=bxy, flow_xy=fxy), hd, cn, sid, stats
+
+    def track_seed_points(self, pts, counts, age, flow_xy, gain=1.0, seed=None):
+        """ofk_track_seed_points, the stage entry: LK's start positions for pts [B,S,2] (counts [B]) from the tracks' age [B,S] and
+        last flow [B,S,2].  seed: the model seeds [B,S,2] that rows of age 0 keep (None: they start at the point).  Entries beyond
+        counts[b] are the points (or `seed`).  Touches no resident state."""
+        pp = _arr(pts, np.float32)
+        if pp.ndim != 3 or pp.shape[2] != 2 or pp.shape[1] < 1:
+            raise ValueError(f"track_seed_points: pts {pp.shape} is not [B, S >= 1, 2]")
+        B, S = pp.shape[:2]
+        cn = _arr(counts, np.int32, (B,)); ag = _arr(age, np.int32, (B, S)); fl = _arr(flow_xy, np.float32, (B, S, 2))
+        out = np.array(pp if seed is None else _arr(seed, np.float32, (B, S, 2)))
+        with self._lock:
+            self._ck(self._L.ofk_track_seed_points(self._h, _p(pp), _p(cn), B, S, _p(ag), _p(fl), float(gain), 0 if seed is None else 1, _p(out)))
+        return out
 
     def zones_reset(self, batch=None):
         """ofk_zones_reset: the zone tables of the first `batch` streams (all by default) are cleared."""

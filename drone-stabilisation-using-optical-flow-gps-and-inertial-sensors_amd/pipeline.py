@@ -162,6 +162,10 @@ class PipelineConfig:
     # gyro bias (ofk.h: ofk_set_gyro_bias): None, True (the defaults) or an ofk.GyroBias: every stream filters its gyro's bias from the
     # flow and takes it out of omega in front of each step; FlowPipeline ignores it (independent pairs carry no state)
     gyro_bias: object = None
+    # track table (ofk.h: ofk_set_track_table): None, True (the table alone) or an ofk.TrackTable: every stream keeps an id, an age, a
+    # birth and the last flow per track on the device, and with seed "flow" starts LK at each track's position plus that flow;
+    # FlowPipeline ignores it (independent pairs have no tracks)
+    track_table: object = None
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -266,6 +270,16 @@ class PipelineConfig:
         if not isinstance(m, ofk.GyroBias):
             raise ValueError(f"gyro_bias {m!r} is neither None, True nor an ofk.GyroBias")
         return None if m.mode == ofk.BIAS_OFF else m
+
+    def track_table_setting(self):
+        """The ofk.TrackTable structure of this configuration, None when the track table is off."""
+        if self.track_table is None or self.track_table is False:
+            return None
+        m = ofk.track_table_setting() if self.track_table is True else self.track_table
+        if not isinstance(m, ofk.TrackTable):
+            raise ValueError(f"track_table {m!r} is neither None, True nor an ofk.TrackTable")
+        m = ofk.track_table_setting(m.seed, m.gain, m.mode)      # range-checked
+        return None if m.mode == ofk.TT_OFF else m
 
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
@@ -375,7 +389,7 @@ class FusionConfig:
 
 def _apply_settings(ctx, cfg, zones):
     """The settings a PipelineConfig switches on, on a fresh context, in the order the library's checks were written for; zones:
-    whether the exclusion zones and the gyro bias are among them (they belong to the stream steps)."""
+    whether the exclusion zones, the gyro bias and the track table are among them (they belong to the stream steps)."""
     if cfg.lk_seed != "off":
         ctx.set_lk_seed(cfg.lk_seed, cfg.seed_gain)
     steps = [(ctx.set_robust, cfg.robust_setting), (ctx.set_track_gate, cfg.track_gate_setting), (ctx.set_lk_light, cfg.lk_light_setting),
@@ -383,7 +397,7 @@ def _apply_settings(ctx, cfg, zones):
              (ctx.set_cov, cfg.cov_setting), (ctx.set_joint, cfg.joint_setting), (ctx.set_plane, cfg.plane_setting),
              (ctx.set_epipolar, cfg.epipolar_setting)]
     if zones:
-        steps += [(ctx.set_zones, cfg.zones_setting), (ctx.set_gyro_bias, cfg.gyro_bias_setting)]
+        steps += [(ctx.set_zones, cfg.zones_setting), (ctx.set_gyro_bias, cfg.gyro_bias_setting), (ctx.set_track_table, cfg.track_table_setting)]
     steps += [(ctx.set_camera, cfg.camera_setting), (ctx.set_rolling_shutter, cfg.rolling_shutter_setting),
               (ctx.set_finite_motion, cfg.finite_motion_setting)]
     for setter, setting in steps:                                # every *_setting() is None when its setting is off
@@ -479,6 +493,18 @@ class FlowStream:
         """(prev, next) [batch, max_pts, 2] f32: the points the solve stage of the latest step saw (camera model, rolling shutter or
         finite motion on)."""
         return _ideal_points(self.ctx, self.batch)
+
+    def track_table(self):
+        """The streams' track tables behind the latest begin or step (ofk.h: ofk_set_track_table): dict(ids, age, birth_step, birth_xy,
+        flow_xy: per stream the rows of the tracks that call returned, in their order; step_ids: per stream the ids of the rows the
+        latest step tracked, stream_last_points' rows; stats [batch, 8] i32: count, kept, lost, born, oldest age, step, next_id, rows
+        seeded from their flow)."""
+        t = self.ctx.track_table_download(self.batch)
+        st = t["stats"]
+        out = {k: [t[k][b, :st[b, 0]] for b in range(self.batch)] for k in ("ids", "age", "birth_step", "birth_xy", "flow_xy")}
+        out["step_ids"] = [t["step_ids"][b, :st[b, 1] + st[b, 2]] for b in range(self.batch)]
+        out["stats"] = st
+        return out
 
     def begin(self, first_bgr):
         return self.ctx.stream_begin(first_bgr, self._params)

@@ -173,6 +173,7 @@ class optical_fusion:
     _camera = {}                                                 # PipelineConfig's camera field; empty: the points are taken as ideal pinhole samples
     _lk_light = {}                                               # PipelineConfig's lk_light field; empty: LK assumes brightness constancy
     _finite_motion = {}                                          # PipelineConfig's finite_motion field; empty: the solve takes the flow as the instantaneous field
+    _track_table = {}                                            # PipelineConfig's track_table field; empty: the tracks are anonymous points
     _rolling_shutter = {}                                        # PipelineConfig's rolling_shutter field; empty: every row is taken as exposed at the time stamp
     feature_params = dict(qualityLevel=0.7, minDistance=10, blockSize=12)
     lk_params = dict(winSize=(15, 15), maxLevel=3, criteria=(cv2.TERM_CRITERIA_EPS | cv2.TERM_CRITERIA_COUNT, 20, 0.03))
@@ -329,7 +330,7 @@ class optical_fusion:
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
                                  **self._cov, **self._joint, **self._plane, **self._epipolar, **self._zones, **self._camera, **self._rolling_shutter,
-                                 **self._finite_motion, **self._gyro_bias, **self._lk_light)
+                                 **self._finite_motion, **self._gyro_bias, **self._lk_light, **self._track_table)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -435,7 +436,8 @@ class optical_fusion:
             self.vel_err = np.sqrt(np.maximum(np.diag(Rm @ ofk.cov_matrix(cv[6:12]) @ Rm.T), 0.0))
 
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
-                 rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None, gyro_bias=None, lk_light=None):
+                 rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None, gyro_bias=None, lk_light=None,
+                 track_table=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -478,7 +480,11 @@ class optical_fusion:
         every step (ofk.h: ofk_set_gyro_bias); self.last_gyro_bias is the record, its slots 0-2 the bias.
         lk_light: None (LK assumes brightness constancy between the two frames), "bias", "gain", an ofk.LkLight or a dict of
         ofk.lk_light_setting's keywords, e.g. dict(mode="gain", gain_max=4): LK then takes a gain and a bias per window out, which
-        is what a camera under auto-exposure needs (ofk.h: ofk_set_lk_light)."""
+        is what a camera under auto-exposure needs (ofk.h: ofk_set_lk_light).
+        track_table: None (the tracks are anonymous points), True (the table alone), an ofk.TrackTable or a dict of
+        ofk.track_table_setting's keywords, e.g. dict(seed="flow"): the stream then keeps an id, an age, a birth and the last flow
+        per track on the device, and with seed "flow" starts LK at each track's position plus that flow (ofk.h:
+        ofk_set_track_table); self._stream.track_table() reads the table."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -560,6 +566,12 @@ class optical_fusion:
             PipelineConfig(**self._lk_light).lk_light_setting()      # invalid fields fail here, not at the first frame
         else:
             self._lk_light = {}
+        if track_table is not None and track_table is not False:
+            tt = track_table if track_table is True or isinstance(track_table, ofk.TrackTable) else ofk.track_table_setting(**dict(track_table))
+            self._track_table = dict(track_table=tt)
+            PipelineConfig(**self._track_table).track_table_setting()    # invalid fields fail here, not at the first frame
+        else:
+            self._track_table = {}
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

@@ -236,6 +236,67 @@ int ofk_get_lk_seed(const ofk_ctx *ctx, int *mode, double *gain);
 int ofk_predict_points(ofk_ctx *ctx, const float *pts, const int *counts, int batch, int stride, const double *sensors, int mode,
                        double gain, float *seed_out);
 
+/* Track table: an identity per track of a video stream, resident on the device, and LK seeded from each track's own last flow.
+ * A stream hands back anonymous points; with ofk_set_track_table on, every row of the tracks a call returns has an id, an age, a
+ * birth step, a birth position and the flow of the step it last survived.  Off by default; with it off every stream step launches
+ * the kernels and returns the bits it always did.  Streams only: ofk_pairs_run ignores the setting.
+ * State per stream: step (i32), next_id (u32; it wraps around after 2^32 births, which is not handled), per track row r < count:
+ * id (u32), age (i32, steps survived), birth_step (i32), birth_xy (2 x f32), flow_xy (2 x f32); and step_ids [max_pts] u32.  Rows are
+ * in the order of the `tracks` the same call returns.
+ *   1. Begin (ofk_stream_begin[_jpeg]): step = 0; row r < n: id = r, age = 0, birth_step = 0, birth_xy = the position, flow_xy = 0;
+ *      next_id = n.
+ *   2. Replace (ofk_fusion.redetect_replace, the streams whose budget is positive, behind k_replace_tracks): rows r < n =
+ *      max(new count, 0) get id = next_id + r, age = 0, birth_step = step, birth_xy = the new position, flow_xy = 0; next_id += n.
+ *      Other streams are untouched.
+ *   3. Update (in front of k_update_tracks, on the steps that launch it): step_ids[i] = id[i] for i < n_old, the ids of the rows
+ *      ofk_stream_last_points and the records' points speak of.  The rows with status[i] != 0 are kept in order, status being what
+ *      k_update_tracks reads: the keep flags behind the gates, the feasibility rule and the robust drop.  A kept row keeps id and
+ *      birth_*, age + 1, flow = next[i] - prev[i] per coordinate, one f32 subtraction of the raw pixels.  Then
+ *      extra = max(0, min(new count, max_total - kept)) rows (0 without a re-detection) are appended: id = next_id + j, age = 0,
+ *      birth_step = step + 1, birth_xy = the position, flow = 0.  next_id += extra; step += 1.
+ *   4. A held step (ofk_fusion.hold_on_skip, not solved) leaves table, step, next_id, step_ids and the statistics as they were (a
+ *      replace in front of it has happened).
+ *   5. Seed (seed = OFK_TT_SEED_FLOW), behind k_seed_points and, with a camera, behind the launch that brings the model seeds back
+ *      into the image - the last flow lives in raw pixels.  A row with age >= 1: t = (float)gain * flow (one f32 multiply),
+ *      s = pos + t (one f32 add), no contraction; the seed is s if |s.x| <= 1e6 and |s.y| <= 1e6 (false for a NaN), else the point
+ *      itself.  A row with age == 0 keeps what ofk_set_lk_seed wrote if that setting is on, else it gets the point itself.  LK (the
+ *      lighting-insensitive one if selected) then runs with OFK_LK_USE_INITIAL_FLOW; a seed equal to the point gives the plain
+ *      result bit for bit.  The gate's backward pass is unchanged.  Newborn tracks have no flow: at a reduced pyramid depth they
+ *      need ofk_set_lk_seed or slow motion.
+ *   6. Statistics per stream, int[OFK_TT_STATS]: count, kept, lost = n_old - kept, born, oldest age, step, next_id, the rows
+ *      i < n_old of this step that rule 5 seeded from their flow (0 with the seed off).  Begin: n, 0, 0, n, 0, 0, n, 0.  Replace:
+ *      n, 0, the count before, n, 0, step, next_id, 0.
+ * ofk_set_track_table: NULL or mode OFK_TT_OFF switches the feature off.  OFK_E_INVALID, the setting staying as it was: a mode
+ * that is neither OFK_TT_OFF nor OFK_TT_ON, a seed that is neither OFK_TT_SEED_OFF nor OFK_TT_SEED_FLOW, a gain that is not finite.
+ * The buffers (32 bytes per track and the per-stream words) are allocated when a stream first begins or steps with the setting on;
+ * streams that step with the setting on without a table of their current tracks (the setting came on, or was off for a step, after
+ * ofk_stream_begin) start one there by rule 1, in front of everything else in the step.
+ * ofk_track_table_download, the streams of the latest begin or step with the setting on, the first min(stride, max_pts) rows of
+ * each (every output may be NULL; OFK_E_INVALID before such a call): ids, age, birth_step, step_ids [batch][stride], birth_xy,
+ * flow_xy [batch][stride][2], stats [batch][OFK_TT_STATS].
+ * ofk_track_table_step, rule 3 and 6 on host buffers (it touches no resident state): the table rows in and out in place (ids, age,
+ * birth_step [batch][stride], birth_xy, flow_xy [batch][stride][2]), head [batch][2] = step, next_id in and out, prev_pts / next_pts
+ * [batch][stride][2], status [batch][stride], counts [batch] in (n_old) and out (the new count), new_pts / new_counts (NULL: none),
+ * max_total <= stride, step_ids [batch][stride] and stats out (either may be NULL).  t: the setting whose seed and gain the eighth
+ * statistic takes (NULL: seed off).
+ * ofk_track_seed_points, rule 5 on host buffers: pts [batch][stride][2], counts, age [batch][stride], flow_xy, gain; seed_io holds
+ * the model seeds on entry when keep_age0 != 0 (age-0 rows stay as they are), and the start positions on return. */
+#define OFK_TT_OFF        0
+#define OFK_TT_ON         1
+#define OFK_TT_SEED_OFF   0
+#define OFK_TT_SEED_FLOW  1
+#define OFK_TT_STATS      8
+typedef struct ofk_track_table { int mode; int seed; double gain; } ofk_track_table;
+int ofk_set_track_table(ofk_ctx *ctx, const ofk_track_table *t);
+int ofk_get_track_table(const ofk_ctx *ctx, ofk_track_table *t);
+int ofk_track_table_download(ofk_ctx *ctx, uint32_t *ids, int *age, int *birth_step, float *birth_xy, float *flow_xy, uint32_t *step_ids,
+                             int stride, int *stats);
+int ofk_track_table_step(ofk_ctx *ctx, const ofk_track_table *t, uint32_t *ids, int *age, int *birth_step, float *birth_xy, float *flow_xy,
+                         int *head, const float *prev_pts, const float *next_pts, const uint8_t *status, int *counts, const float *new_pts,
+                         const int *new_counts, int max_total, int batch, int stride, uint32_t *step_ids, int *stats);
+int ofk_track_seed_points(ofk_ctx *ctx, const float *pts, const int *counts, int batch, int stride, const int *age, const float *flow_xy,
+                          double gain, int keep_age0, float *seed_io);
+
 /* Camera model: the lens distortion undone on the device before the solve.  The solve stage reads a point as a sample of an ideal
  * pinhole image, x = (px - cx) * scaling (sensors[19..21]); the reference's camera is a wide-angle module whose lens moves a point by
  * tens of pixels at the border.  With ofk_set_camera on, the resident chains keep everything that lives in the image on the raw
