@@ -199,3 +199,5 @@ void ofk_launch_track_gate(hipStream_t s, const float *prev_pts, const float *ba
 #include "k_rshutter.inc"
 #include "k_finite.inc"
 #include "k_track_table.inc"
+#include "k_lstsq.inc"
+#include "k_track_depth.inc"

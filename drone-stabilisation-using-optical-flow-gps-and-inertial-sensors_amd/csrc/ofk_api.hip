@@ -160,6 +160,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->rs = ofk_rshutter{OFK_RS_OFF, 0, 0.0, 0.5, 1.0};
     c->fm = ofk_finite_motion{OFK_FM_OFF, 0.1};
     c->tt = ofk_track_table{OFK_TT_OFF, OFK_TT_SEED_OFF, 1.0};
+    c->td = ofk_track_depth{OFK_TD_OFF, 0.2, 0.5, 3.0, 0.0, 3, 0.25, 8, 1};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -213,7 +214,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
                     c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec, c->joint_rec, c->bias_rec, c->plane_rec, c->epi_rec,
-                    c->zone_tab, c->pts_prev_u, c->ttr.ids};
+                    c->zone_tab, c->pts_prev_u, c->ttr.ids, c->tdr.rho};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
@@ -2566,6 +2567,155 @@ extern "C" int ofk_track_seed_points(ofk_ctx *c, const float *pts, const int *co
     return get(c, seed_io, d_seed, np * 8);
 }
 
+// ------------------------------------------------------------------------------------------------ depth per track
+static int check_td(ofk_ctx *c, const ofk_track_depth *t, const char *who)
+{
+    if (t->mode != OFK_TD_OFF && t->mode != OFK_TD_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_TD_OFF nor OFK_TD_ON", who, t->mode);
+    if (t->mode == OFK_TD_OFF) return OFK_OK;
+    if (!std::isfinite(t->sigma_flow) || !std::isfinite(t->b_min) || !std::isfinite(t->gate) || !std::isfinite(t->q) || !std::isfinite(t->rel_max))
+        return ofk_fail(c, OFK_E_INVALID, "%s: sigma_flow, b_min, gate, q and rel_max must be finite", who);
+    if (!(t->sigma_flow > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: sigma_flow = %g must be positive", who, t->sigma_flow);
+    if (t->b_min < 0.0 || t->gate < 0.0 || t->q < 0.0)
+        return ofk_fail(c, OFK_E_INVALID, "%s: b_min = %g, gate = %g and q = %g must not be negative", who, t->b_min, t->gate, t->q);
+    if (t->min_obs < 1) return ofk_fail(c, OFK_E_INVALID, "%s: min_obs = %d must be at least 1", who, t->min_obs);
+    if (!(t->rel_max > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: rel_max = %g must be positive", who, t->rel_max);
+    if (t->min_rows < 3) return ofk_fail(c, OFK_E_INVALID, "%s: min_rows = %d must be at least 3", who, t->min_rows);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_track_depth(ofk_ctx *c, const ofk_track_depth *t)
+{
+    return setting_set(c, &ofk_ctx::td, t && t->mode == OFK_TD_OFF ? nullptr : t, [](ofk_track_depth &s) { s.mode = OFK_TD_OFF; },
+                       [c](const ofk_track_depth *v) { return check_td(c, v, "ofk_set_track_depth"); });
+}
+extern "C" int ofk_get_track_depth(const ofk_ctx *c, ofk_track_depth *t) { return setting_get(c, &ofk_ctx::td, t); }
+
+static bool td_on(const ofk_ctx *c) { return c->td.mode != OFK_TD_OFF; }
+
+// the state's arrays over `np` rows and the records of `batch` streams carved out of base (NULL: nothing is carved); returns the bytes
+static size_t td_carve(ofk_td_rows &t, uint8_t *base, size_t np, size_t batch)
+{
+    size_t o = 0;
+    auto take = [&](size_t bytes) { uint8_t *p = base ? base + o : nullptr; o += up(bytes, 256); return p; };
+    t.rho = (double *)take(np * 8); t.var = (double *)take(np * 8); t.nobs = (int *)take(np * 4); t.rec = (double *)take(batch * OFK_TD_DOUBLES * 8);
+    return o;
+}
+// the resident state, allocated (and cleared) by the first step with the setting on
+static int td_alloc(ofk_ctx *c)
+{
+    if (c->tdr.rho) return OFK_OK;                               // one allocation, carved into the four arrays
+    ofk_td_rows t;
+    const size_t np = (size_t)c->max_batch * c->max_pts, bytes = td_carve(t, nullptr, np, (size_t)c->max_batch);
+    uint8_t *base = nullptr;
+    OFK_HIP(c, hipMalloc((void **)&base, bytes));
+    OFK_HIP(c, hipMemsetAsync(base, 0, bytes, c->stream));
+    td_carve(c->tdr, base, np, (size_t)c->max_batch);
+    return OFK_OK;
+}
+
+// The steps' own refusals with the setting on (ofk.h); fu: a fused step's.
+static int td_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const char *who)
+{
+    if (!td_on(c)) return OFK_OK;
+    if (c->tt.mode == OFK_TT_OFF)
+        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_track_depth is on without ofk_set_track_table: the depths are kept per row of the table", who);
+    if (variant == OFK_SOLVE_OFMODULE || (fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY)))
+        return refuse_not_sensor_model(c, who, NO_OFMODULE | NO_ROTATIONAL | NO_LEGACY, "depth per track", "ofk_set_track_depth");
+    return OFK_OK;
+}
+
+// depths for the current tracks of the first B streams: zeroed rows unless they are live already
+static int td_begin(ofk_ctx *c, int B)
+{
+    TRY(td_alloc(c));
+    if (c->td_live != B) ofk_launch_track_depth_begin(c->stream, c->tdr, c->counts, c->max_pts, B);
+    c->td_batch = c->td_live = B;
+    return OFK_OK;
+}
+
+extern "C" int ofk_track_depth_download(ofk_ctx *c, double *rho, double *var, int *nobs, int stride, double *rec)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->td_batch < 1 || !c->tdr.rho) return ofk_fail(c, OFK_E_INVALID, "ofk_track_depth_download: no stream has stepped with ofk_set_track_depth on yet");
+    if ((rho || var || nobs) && stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_track_depth_download: stride %d", stride);
+    TRY(enter(c));
+    const int B = c->td_batch;
+    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    const ofk_td_rows &t = c->tdr;
+    struct { void *dst; const void *src; size_t el; } rows[] = {{rho, t.rho, 8}, {var, t.var, 8}, {nobs, t.nobs, 4}};
+    for (const auto &r : rows)
+        if (r.dst) OFK_HIP(c, hipMemcpy2DAsync(r.dst, (size_t)stride * r.el, r.src, mp * r.el, n * r.el, B, hipMemcpyDeviceToHost, c->stream));
+    if (rec) OFK_HIP(c, hipMemcpyAsync(rec, t.rec, (size_t)B * OFK_TD_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+extern "C" int ofk_track_depth_reset(ofk_ctx *c, int b, const double *rho, const double *var, const int *nobs, int n)
+{
+    const char *who = "ofk_track_depth_reset";
+    if (!c) return OFK_E_INVALID;
+    if (!rho || !var || !nobs) return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
+    if (c->stream_batch < 1 || b < 0 || b >= c->stream_batch) return ofk_fail(c, OFK_E_INVALID, "%s: stream %d is none of the %d active streams", who, b, c->stream_batch);
+    if (n < 0 || n > c->max_pts) return ofk_fail(c, OFK_E_INVALID, "%s: n %d outside 0..%d", who, n, c->max_pts);
+    for (int i = 0; i < n; ++i)
+        if (nobs[i] < 0) return ofk_fail(c, OFK_E_INVALID, "%s: nobs[%d] = %d is negative", who, i, nobs[i]);
+    TRY(enter(c));
+    TRY(td_begin(c, c->stream_batch));
+    const size_t o = (size_t)b * c->max_pts;
+    if (n) {
+        OFK_HIP(c, hipMemcpyAsync(c->tdr.rho + o, rho, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        OFK_HIP(c, hipMemcpyAsync(c->tdr.var + o, var, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        OFK_HIP(c, hipMemcpyAsync(c->tdr.nobs + o, nobs, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    TRY(check_launch(c, who));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));                  // the host buffers are the caller's again
+    return OFK_OK;
+}
+
+// rules 1-4 on host buffers: device scratch only
+extern "C" int ofk_track_depth_step(ofk_ctx *c, const ofk_track_depth *set, const double *x, const double *u, const uint8_t *status, const int *counts,
+                                    const double *omega, const double *v, const int *solved, double *rho, double *var, int *nobs,
+                                    const int *new_counts, int max_total, int batch, int stride, double *rec)
+{
+    const char *who = "ofk_track_depth_step";
+    if (!c) return OFK_E_INVALID;
+    if (!set || !x || !u || !status || !counts || !omega || !v || !solved || !rho || !var || !nobs) return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
+    if (batch < 1 || stride < 1) return ofk_fail(c, OFK_E_INVALID, "%s: batch %d / stride %d", who, batch, stride);
+    if (max_total < 0 || max_total > stride) return ofk_fail(c, OFK_E_INVALID, "%s: max_total %d outside 0..%d", who, max_total, stride);
+    if (set->mode == OFK_TD_OFF) return ofk_fail(c, OFK_E_INVALID, "%s: the setting is off", who);
+    TRY(check_td(c, set, who));
+    TRY(check_counts(c, who, counts, batch, stride));
+    const size_t np = (size_t)batch * stride, B = (size_t)batch;
+    double *h_rec = (double *)calloc(B * OFK_RECORD_DOUBLES, 8);   // the step's records as the kernel reads them: v, solved
+    if (!h_rec) return ofk_fail(c, OFK_E_INVALID, "%s: out of host memory", who);
+    for (size_t b = 0; b < B; ++b) {
+        for (int k = 0; k < 3; ++k) h_rec[b * OFK_RECORD_DOUBLES + k] = v[3 * b + k];
+        h_rec[b * OFK_RECORD_DOUBLES + 15] = solved[b] ? 1.0 : 0.0;
+    }
+    Bump bp;
+    int rc = est_begin(c, np * 53 + B * (OFK_RECORD_DOUBLES * 8 + OFK_TD_DOUBLES * 8 + 32) + 16 * 256, bp);
+    if (rc != OFK_OK) { free(h_rec); return rc; }
+    ofk_td_rows t;
+    t.rho = bp.put(rho, np * 8); t.var = bp.put(var, np * 8); t.nobs = (int *)bp.put(nobs, np * 4); t.rec = bp.take(B * OFK_TD_DOUBLES * 8);
+    ofk_td_in in = {};
+    in.x = bp.put(x, np * 16); in.u = bp.put(u, np * 16); in.status = (const uint8_t *)bp.put(status, np);
+    in.counts = (const int *)bp.put(counts, B * 4); in.stride = stride;
+    in.new_counts = (const int *)bp.put(new_counts, B * 4); in.max_total = max_total;
+    in.omega = bp.put(omega, B * 24); in.omega_stride = 3;
+    in.v = bp.put(h_rec, B * OFK_RECORD_DOUBLES * 8); in.plain = 0;
+    hipError_t e = bp.rc == OFK_OK ? hipStreamSynchronize(c->stream) : hipErrorUnknown;   // h_rec has been read
+    free(h_rec);
+    if (e != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    ofk_launch_track_depth_step(c->stream, t, in, set, batch);
+    TRY(check_launch(c, "k_track_depth_step"));
+    OFK_HIP(c, hipMemcpyAsync(rho, t.rho, np * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipMemcpyAsync(var, t.var, np * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipMemcpyAsync(nobs, t.nobs, np * 4, hipMemcpyDeviceToHost, c->stream));
+    if (rec) OFK_HIP(c, hipMemcpyAsync(rec, t.rec, B * OFK_TD_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ video streams
 static int stream_alloc(ofk_ctx *c)
 {
@@ -2625,6 +2775,7 @@ static int stream_begin_impl(ofk_ctx *c, const uint8_t *first_bgr, int batch, in
     TRY(stream_ingest(c, 0, first_bgr, batch, h, w, lv));
     TRY(stream_detect(c, nullptr, nullptr, batch, h, w, p, c->pts_prev, c->counts));
     c->tt_batch = c->tt_live = 0;                                // ... and with a new track table, if the setting is on
+    c->td_batch = c->td_live = 0;                                // ... and without depths: the first step with that setting on starts them
     if (tt_on(c)) {
         TRY(tt_alloc(c));
         ofk_launch_track_table_begin(c->stream, c->ttr, c->pts_prev, c->counts, c->max_pts, batch);
@@ -2786,6 +2937,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     TRY(fm_check_step(c, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     TRY(second_prepare(c, B, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     TRY(bias_check_step(c, B, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
+    TRY(td_check_step(c, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     const int defer = second_on(c) && fu && fu->filter ? 1 : 0;   // the second-stage kernel corrects
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
@@ -2808,6 +2960,9 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         c->tt_batch = c->tt_live = B;
     } else
         c->tt_live = 0;                                          // the tracks move on without their table
+    const bool depth = td_on(c);                                 // td_check_step: then the table is on
+    if (depth) TRY(td_begin(c, B));
+    else c->td_live = 0;                                         // the tracks move on without their depths
     const bool flow_seed = table && c->tt.seed == OFK_TT_SEED_FLOW;
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
@@ -2822,6 +2977,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         TRY(stream_detect(c, zones_on ? c->mask : nullptr, c->limit, B, h, w, p, c->pts_new, c->new_counts));
         ofk_launch_replace_tracks(c->stream, c->limit, c->pts_new, c->new_counts, c->max_pts, c->pts_prev, c->counts, B);
         if (table) ofk_launch_track_table_replace(c->stream, c->ttr, c->limit, c->pts_new, c->new_counts, c->max_pts, B);
+        if (depth) ofk_launch_track_depth_replace(c->stream, c->tdr, c->limit, c->new_counts, c->max_pts, B);
     }
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)
@@ -2871,6 +3027,15 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     }
     // tracks := new[status == 1] ++ re-detected (node:134,166); the new frame becomes the previous one (node:175)
     if (!hold) {
+        if (depth) {                                             // in front of the table's update, on what k_update_tracks is about to read
+            const bool imu = fu && fu->use_imu;
+            ofk_td_in in = {};
+            in.prev_pts = v.solve_prev; in.next_pts = v.solve_next; in.status = c->status; in.counts = c->counts; in.stride = c->max_pts;
+            in.new_counts = any ? c->new_counts : nullptr; in.max_total = p->max_corners; in.sensors = c->sensors;
+            in.omega = imu ? c->imu_state + 18 : c->sensors + 4; in.omega_stride = imu ? OFK_IMU_STATE : OFK_SENSOR_DOUBLES;
+            in.v = c->records; in.plain = fu ? 0 : 1;
+            ofk_launch_track_depth_step(c->stream, c->tdr, in, &c->td, B);
+        }
         if (table)                                               // in front of it: it overwrites pts_prev and counts
             ofk_launch_track_table_update(c->stream, c->ttr, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, any ? c->pts_new : nullptr,
                                           any ? c->new_counts : nullptr, p->max_corners, flow_seed ? 1 : 0, flow_seed ? (float)c->tt.gain : 0.f, B);

@@ -22,6 +22,19 @@ struct ofk_levels {
 // the track table's arrays (ofk.h: ofk_set_track_table), rows `stride` apart per stream
 struct ofk_tt_rows { unsigned *ids; int *age, *birth_step; float *birth_xy, *flow_xy; unsigned *step_ids; int *head, *stats; };
 
+// the depth per track (ofk.h: ofk_set_track_depth): the state's arrays, rows `stride` apart per stream in the table's row order, and the
+// records [B][OFK_TD_DOUBLES]; what one step reads
+struct ofk_td_rows { double *rho, *var; int *nobs; double *rec; };
+struct ofk_td_in {
+    const float *prev_pts, *next_pts;                            // the solve's resident points, or
+    const double *x, *u;                                         // the stage entry's [B][stride][2] (then prev_pts / next_pts / sensors are NULL)
+    const uint8_t *status; const int *counts; int stride;        // what k_update_tracks reads
+    const int *new_counts; int max_total;                        // NULL: no re-detection
+    const double *sensors;                                       // scaling, cx, cy of the resident points
+    const double *omega; int omega_stride;                       // the omega the solve read, doubles between streams
+    const double *v; int plain;                                  // [B][OFK_RECORD_DOUBLES]: v in 0-2, solved in 15 (plain: rank 3 in slot 4)
+};
+
 struct ofk_comm;
 struct ofk_ctx {
     int device;
@@ -121,6 +134,9 @@ struct ofk_ctx {
     ofk_track_table tt;                      // ofk_set_track_table: mode OFK_TT_OFF (gain 1) unless set
     ofk_tt_rows ttr;                         // the table's device rows, [B][max_pts] each, head [B][2], stats [B][OFK_TT_STATS]; one lazy allocation (ttr.ids owns it)
     int tt_batch, tt_live;                   // streams of the latest begin / step with the table on (ofk_track_table_download), 0 = none; streams whose rows match their current tracks
+    ofk_track_depth td;                      // ofk_set_track_depth: mode OFK_TD_OFF unless set
+    ofk_td_rows tdr;                         // the depth state's device rows, [B][max_pts] each, and records; one lazy allocation (tdr.rho owns it)
+    int td_batch, td_live;                   // streams of the latest step with the depths on (ofk_track_depth_download), 0 = none; streams whose rows match their current tracks
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -246,6 +262,10 @@ void ofk_launch_track_table_update(hipStream_t s, const ofk_tt_rows &t, const fl
                                    float gain, int batch);
 void ofk_launch_track_seed(hipStream_t s, const float *pts, const int *counts, int stride, const int *age, const float *flow_xy, float gain,
                            int keep_age0, float *seed, int batch);
+// the depth per track (ofk.h: ofk_set_track_depth; k_track_depth.inc): beside the table's begin and replace, rules 1-4 in front of its update
+void ofk_launch_track_depth_begin(hipStream_t s, const ofk_td_rows &t, const int *counts, int stride, int batch);
+void ofk_launch_track_depth_replace(hipStream_t s, const ofk_td_rows &t, const int *limit, const int *new_counts, int stride, int batch);
+void ofk_launch_track_depth_step(hipStream_t s, const ofk_td_rows &t, const ofk_td_in &in, const ofk_track_depth *d, int batch);
 void ofk_launch_pairs_solve(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status,
                             const int *counts, int pts_stride, const double *sensors, int variant, int use_feas,
                             double feas_T, const int *cand_count, double *records, int batch);

@@ -41,6 +41,7 @@ SYMBOLS = (
     "ofk_set_rolling_shutter", "ofk_get_rolling_shutter", "ofk_rs_correct_points", "ofk_rs_download",
     "ofk_set_finite_motion", "ofk_get_finite_motion", "ofk_finite_correct_points", "ofk_finite_download",
     "ofk_set_track_table", "ofk_get_track_table", "ofk_track_table_download", "ofk_track_table_step", "ofk_track_seed_points",
+    "ofk_set_track_depth", "ofk_get_track_depth", "ofk_track_depth_download", "ofk_track_depth_reset", "ofk_track_depth_step",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
     "ofk_stream_begin_jpeg", "ofk_stream_step_jpeg",
@@ -105,6 +106,8 @@ TT_OFF, TT_ON = 0, 1                                     # ofk_set_track_table
 TT_SEED_OFF, TT_SEED_FLOW = 0, 1
 TT_SEEDS = {"off": TT_SEED_OFF, "flow": TT_SEED_FLOW}
 TT_STATS = 8                                             # count, kept, lost, born, oldest age, step, next_id, rows seeded from their flow
+TD_OFF, TD_ON = 0, 1                                     # ofk_set_track_depth
+TD_DOUBLES = 32                                          # v_map, flag, mature, updated, initialised, 3 skip counts, C_map, v, solved, reset
 FLOW_LK, FLOW_ROTATIONAL = 0, 1
 KEEP_STATUS, KEEP_LEGACY = 0, 1
 CONTROL_SENSORS, CONTROL_IMU = 0, 1
@@ -447,6 +450,30 @@ def track_table_setting(seed="off", gain=1.0, mode=TT_ON):
     return TrackTable(mode, seed, gain)
 
 
+class TrackDepth(C.Structure):
+    """ofk_track_depth (include/ofk.h): an inverse depth per track of a stream, filtered over the frames, and the velocity from them."""
+    _fields_ = [("mode", C.c_int), ("sigma_flow", C.c_double), ("b_min", C.c_double), ("gate", C.c_double), ("q", C.c_double),
+                ("min_obs", C.c_int), ("rel_max", C.c_double), ("min_rows", C.c_int), ("update", C.c_int)]
+
+
+def track_depth_setting(mode=True, sigma_flow=0.2, b_min=0.5, gate=3.0, q=0.0, min_obs=3, rel_max=0.25, min_rows=8, update=True):
+    """A TrackDepth structure from names: mode True / False (or TD_*); sigma_flow and b_min in the units of the points the entry takes
+    (pixels in the stream steps); gate in sigmas, on the cross-flow and on the innovation (0: no gates); q the variance a depth gains
+    per step; a row is mature (enters the map solve) from min_obs measurements on with sqrt(var) <= rel_max * rho; the map solve needs
+    min_rows (>= 3) mature rows; update False predicts the depths it has and takes no measurement into them."""
+    mode = int(mode)
+    if mode not in (TD_OFF, TD_ON):
+        raise ValueError(f"track-depth mode {mode} is none of TD_OFF, TD_ON")
+    t = TrackDepth(mode, float(sigma_flow), float(b_min), float(gate), float(q), int(min_obs), float(rel_max), int(min_rows), int(bool(update)))
+    if mode != TD_OFF:
+        if not all(np.isfinite(x) for x in (t.sigma_flow, t.b_min, t.gate, t.q, t.rel_max)):
+            raise ValueError("track-depth sigma_flow, b_min, gate, q and rel_max must be finite")
+        if not (t.sigma_flow > 0 and t.b_min >= 0 and t.gate >= 0 and t.q >= 0 and t.rel_max > 0 and t.min_obs >= 1 and t.min_rows >= 3):
+            raise ValueError(f"track-depth setting outside its range: sigma_flow {t.sigma_flow} > 0, b_min {t.b_min} >= 0, gate {t.gate} >= 0, "
+                             f"q {t.q} >= 0, min_obs {t.min_obs} >= 1, rel_max {t.rel_max} > 0, min_rows {t.min_rows} >= 3")
+    return t
+
+
 class Fusion(C.Structure):
     """ofk_fusion (include/ofk.h): what ofk_stream_step_fused does between LK and the next frame."""
     _fields_ = [("use_imu", C.c_int), ("flow", C.c_int), ("keep", C.c_int), ("filter", C.c_int), ("control", C.c_int),
@@ -457,7 +484,7 @@ class Fusion(C.Structure):
 # the struct settings: ofk_set_<name> / ofk_get_<name> take the context and a pointer to the struct
 SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("gyro_bias", GyroBias), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate), ("lk_light", LkLight),
             ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion),
-            ("track_table", TrackTable))
+            ("track_table", TrackTable), ("track_depth", TrackDepth))
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -552,6 +579,9 @@ def load_library():
         L.ofk_track_table_download.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, vp]
         L.ofk_track_table_step.argtypes = [vp, C.POINTER(TrackTable), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp]
         L.ofk_track_seed_points.argtypes = [vp, vp, vp, i, i, vp, vp, d, i, vp]
+        L.ofk_track_depth_download.argtypes = [vp, vp, vp, vp, i, vp]
+        L.ofk_track_depth_reset.argtypes = [vp, i, vp, vp, vp, i]
+        L.ofk_track_depth_step.argtypes = [vp, C.POINTER(TrackDepth), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
         L.ofk_lk_pyr_fb.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, i, vp, vp, vp, C.POINTER(TrackGate), vp, vp, vp]
         L.ofk_lk_pyr_light.argtypes = L.ofk_lk_pyr_fb.argtypes + [C.POINTER(LkLight)]
         L.ofk_imu_propagate.argtypes = [vp, vp, vp, i]
@@ -1011,6 +1041,56 @@ class Context:
         with self._lock:
             self._ck(self._L.ofk_track_seed_points(self._h, _p(pp), _p(cn), B, S, _p(ag), _p(fl), float(gain), 0 if seed is None else 1, _p(out)))
         return out
+
+    def set_track_depth(self, track_depth=None, **settings):
+        """ofk_set_track_depth: a TrackDepth (or track_depth_setting's keywords); None or mode False switches it off.  Every later
+        stream step filters an inverse depth per row of the track table (which must be on) and solves v_map from the depths of the
+        earlier frames.  pairs_run ignores the setting."""
+        self._set_struct(self._L.ofk_set_track_depth, track_depth, settings, track_depth_setting, lock=True)
+
+    def get_track_depth(self):
+        return self._get_struct(self._L.ofk_get_track_depth, TrackDepth)
+
+    def track_depth_download(self, batch=None, stride=None):
+        """ofk_track_depth_download -> dict(rho, var [batch,stride] f64, nobs [batch,stride] i32, rec [batch,32]) of the streams of the
+        latest step with the setting on, rows in the order of the tracks that step returned.  rec: v_map 0-2, map flag 3, mature rows
+        4, rows updated 5, initialised 6, skipped for |b| 7, cross-flow 8, innovation 9, C_map's upper triangle 10-15, the v the
+        measurements read 16-18, solved 19, rows reset 20."""
+        S = self.max_pts if stride is None else int(stride)
+        if S < 1:
+            raise ValueError(f"track_depth_download: stride {S}")
+        f, n = ((S,), np.float64), ((S,), np.int32)
+        rho, var, nobs, rec = self._rows("track_depth_download", self.max_batch if batch is None else int(batch),
+                                         lambda *p: self._L.ofk_track_depth_download(self._h, *p[:3], S, p[3]), f, f, n, ((TD_DOUBLES,), np.float64))
+        return dict(rho=rho, var=var, nobs=nobs, rec=rec)
+
+    def track_depth_reset(self, stream, rho, var, nobs):
+        """ofk_track_depth_reset: the first len(rho) rows of active stream `stream` are loaded from rho, var, nobs."""
+        rho = _arr(rho, np.float64).ravel()
+        var = _arr(var, np.float64, rho.shape); nobs = _arr(nobs, np.int32, rho.shape)
+        with self._lock:
+            self._ck(self._L.ofk_track_depth_reset(self._h, int(stream), _p(rho), _p(var), _p(nobs), len(rho)))
+
+    def track_depth_step(self, x, u, status, counts, omega, v, solved, state, new_counts=None, max_total=None, track_depth=None, **settings):
+        """ofk_track_depth_step, the stage entry: one step of the depths on host arrays.  x, u [B,S,2] f64 in the units of the setting;
+        status [B,S], counts [B]; omega, v [B,3]; solved [B]; state: dict(rho, var [B,S] f64, nobs [B,S] i32); new_counts [B] the
+        re-detected corners (None: none); max_total (default S); the setting a TrackDepth or track_depth_setting's keywords.
+        -> (state, rec [B,32]), new arrays.  Touches no resident state."""
+        td = track_depth if track_depth is not None else track_depth_setting(**settings)
+        xx = _arr(x, np.float64)
+        if xx.ndim != 3 or xx.shape[2] != 2 or xx.shape[1] < 1:
+            raise ValueError(f"track_depth_step: x {xx.shape} is not [B, S >= 1, 2]")
+        B, S = xx.shape[:2]
+        uu = _arr(u, np.float64, (B, S, 2)); st = _arr(status, np.uint8, (B, S)); cn = _arr(counts, np.int32, (B,))
+        om = _arr(omega, np.float64, (B, 3)); vv = _arr(v, np.float64, (B, 3)); so = _arr(solved, np.int32, (B,))
+        rho = np.array(_arr(state["rho"], np.float64, (B, S))); var = np.array(_arr(state["var"], np.float64, (B, S)))
+        nobs = np.array(_arr(state["nobs"], np.int32, (B, S)))
+        nc = _opt(new_counts, np.int32, (B,))
+        rec = np.zeros((B, TD_DOUBLES), np.float64)
+        with self._lock:
+            self._ck(self._L.ofk_track_depth_step(self._h, C.byref(td), _p(xx), _p(uu), _p(st), _p(cn), _p(om), _p(vv), _p(so), _p(rho), _p(var),
+                                                  _p(nobs), _p(nc), S if max_total is None else int(max_total), B, S, _p(rec)))
+        return dict(rho=rho, var=var, nobs=nobs), rec
 
     def zones_reset(self, batch=None):
         """ofk_zones_reset: the zone tables of the first `batch` streams (all by default) are cleared."""

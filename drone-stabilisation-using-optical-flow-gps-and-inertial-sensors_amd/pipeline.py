@@ -166,6 +166,10 @@ class PipelineConfig:
     # birth and the last flow per track on the device, and with seed "flow" starts LK at each track's position plus that flow;
     # FlowPipeline ignores it (independent pairs have no tracks)
     track_table: object = None
+    # depth per track (ofk.h: ofk_set_track_depth): None, True (the defaults) or an ofk.TrackDepth: every stream filters an inverse
+    # depth per row of its track table (which must be on) and solves a velocity from the depths of the earlier frames;
+    # FlowPipeline ignores it
+    track_depth: object = None
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -281,6 +285,16 @@ class PipelineConfig:
         m = ofk.track_table_setting(m.seed, m.gain, m.mode)      # range-checked
         return None if m.mode == ofk.TT_OFF else m
 
+    def track_depth_setting(self):
+        """The ofk.TrackDepth structure of this configuration, None when the depths are off."""
+        if self.track_depth is None or self.track_depth is False:
+            return None
+        m = ofk.track_depth_setting() if self.track_depth is True else self.track_depth
+        if not isinstance(m, ofk.TrackDepth):
+            raise ValueError(f"track_depth {m!r} is neither None, True nor an ofk.TrackDepth")
+        m = ofk.track_depth_setting(m.mode, m.sigma_flow, m.b_min, m.gate, m.q, m.min_obs, m.rel_max, m.min_rows, m.update)   # range-checked
+        return None if m.mode == ofk.TD_OFF else m
+
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
                           int(self.win), int(self.max_level), int(self.max_count), float(self.eps), float(self.min_eig_thr),
@@ -389,7 +403,7 @@ class FusionConfig:
 
 def _apply_settings(ctx, cfg, zones):
     """The settings a PipelineConfig switches on, on a fresh context, in the order the library's checks were written for; zones:
-    whether the exclusion zones, the gyro bias and the track table are among them (they belong to the stream steps)."""
+    whether the exclusion zones, the gyro bias, the track table and the depths per track are among them (they belong to the stream steps)."""
     if cfg.lk_seed != "off":
         ctx.set_lk_seed(cfg.lk_seed, cfg.seed_gain)
     steps = [(ctx.set_robust, cfg.robust_setting), (ctx.set_track_gate, cfg.track_gate_setting), (ctx.set_lk_light, cfg.lk_light_setting),
@@ -397,7 +411,8 @@ def _apply_settings(ctx, cfg, zones):
              (ctx.set_cov, cfg.cov_setting), (ctx.set_joint, cfg.joint_setting), (ctx.set_plane, cfg.plane_setting),
              (ctx.set_epipolar, cfg.epipolar_setting)]
     if zones:
-        steps += [(ctx.set_zones, cfg.zones_setting), (ctx.set_gyro_bias, cfg.gyro_bias_setting), (ctx.set_track_table, cfg.track_table_setting)]
+        steps += [(ctx.set_zones, cfg.zones_setting), (ctx.set_gyro_bias, cfg.gyro_bias_setting), (ctx.set_track_table, cfg.track_table_setting),
+                  (ctx.set_track_depth, cfg.track_depth_setting)]
     steps += [(ctx.set_camera, cfg.camera_setting), (ctx.set_rolling_shutter, cfg.rolling_shutter_setting),
               (ctx.set_finite_motion, cfg.finite_motion_setting)]
     for setter, setting in steps:                                # every *_setting() is None when its setting is off
@@ -504,6 +519,18 @@ class FlowStream:
         out = {k: [t[k][b, :st[b, 0]] for b in range(self.batch)] for k in ("ids", "age", "birth_step", "birth_xy", "flow_xy")}
         out["step_ids"] = [t["step_ids"][b, :st[b, 1] + st[b, 2]] for b in range(self.batch)]
         out["stats"] = st
+        return out
+
+    def depths(self):
+        """The streams' depths per track behind the latest step (ofk.h: ofk_set_track_depth): dict(rho, var, nobs, ids: per stream the
+        rows of the tracks that step returned, in their order, ids joined from the track table; rec [batch, 32]: rec[:, 0:3] is v_map,
+        rec[:, 3] its flag, rec[:, 4] the mature rows it used, ofk.cov_matrix(rec[:, 10:16]) C_map)."""
+        d = self.ctx.track_depth_download(self.batch)
+        t = self.ctx.track_table_download(self.batch)
+        cnt = t["stats"][:, 0]
+        out = {k: [d[k][b, :cnt[b]] for b in range(self.batch)] for k in ("rho", "var", "nobs")}
+        out["ids"] = [t["ids"][b, :cnt[b]] for b in range(self.batch)]
+        out["rec"] = d["rec"]
         return out
 
     def begin(self, first_bgr):

@@ -60,6 +60,13 @@ def gyro_bias_step(x, u, d, n, omega_raw, state=None, **settings):
     return out[:3].copy(), R, out[5:8].copy(), st
 
 
+def track_depth_step(x, u, omega, v, state=None, **kw):
+    """One step of a stream's depths per track without images (ofk.h: ofk_track_depth_step); velocity_node.track_depth_step's
+    arguments and returns: (state dict(rho, var, nobs), rec [32])."""
+    from .velocity_node import track_depth_step as step
+    return step(np.asarray(x, np.float64)[:, :2], np.asarray(u, np.float64)[:, :2], omega, v, state=state, **kw)
+
+
 def solve_lgs_joint(x, u, d, n, omega, t, sigma_flow, sigma_omega=None):
     """solve_lgs with the gyro refined from the flow (ofk.h: ofk_velocity_solve_joint).  sigma_flow: the flow noise in the units of x
     and u; sigma_omega: None (every axis free), a scalar or three values (inf: free, 0: held).

@@ -96,6 +96,36 @@ def gyro_bias_step(x, u, d, n, omega_raw, state=None, **settings):
     return out[:3].copy(), R, rank, out[5:8].copy(), st
 
 
+def track_depth_step(x, u, omega, v, state=None, status=None, solved=True, new_count=None, max_total=None, **settings):
+    """One step of a stream's depths per track without images (ofk.h: ofk_track_depth_step): the map solve from the depths in
+    `state`, then measurement, prediction and compaction.  x, u [n,2]: the solve's points and flow; omega, v: what the step's solve
+    read and returned; state: the dict(rho, var, nobs) of the previous call (None: no depth yet); status [n] (None: all kept);
+    new_count: corners re-detected behind the kept rows; max_total: the most rows the stream holds (None: whatever fits); settings:
+    ofk.track_depth_setting's keywords, sigma_flow and b_min in the units of x and u.
+    Returns (state, rec [32]): the kept rows in order and the appended ones behind them; rec[0:3] is v_map, rec[3] its flag."""
+    x = np.asarray(x, np.float64).reshape(-1, 2); u = np.asarray(u, np.float64).reshape(-1, 2)
+    n = len(x)
+    if n < 1:
+        raise ValueError("track_depth_step: no points")
+    st = np.ones(n, np.uint8) if status is None else (np.asarray(status).reshape(n) != 0).astype(np.uint8)
+    kept, born = int(st.sum()), 0 if new_count is None else max(int(new_count), 0)
+    S = max(n, kept + born)                                      # room for the appended rows
+    if max_total is not None:
+        born = max(0, min(born, int(max_total) - kept))
+
+    def rows(a, dtype, *tail):                                   # [1, S, ...]: the n rows, zeros behind them
+        out = np.zeros((1, S) + tail, dtype)
+        if a is not None:
+            out[0, :n] = np.asarray(a, dtype).reshape((n,) + tail)
+        return out
+    state = state or {}
+    out, rec = ofk.default_context().track_depth_step(
+        rows(x, np.float64, 2), rows(u, np.float64, 2), rows(st, np.uint8), [n], [omega], [v], [1 if solved else 0],
+        dict(rho=rows(state.get("rho"), np.float64), var=rows(state.get("var"), np.float64), nobs=rows(state.get("nobs"), np.int32)),
+        new_counts=None if new_count is None else [born], max_total=S, **settings)
+    return {k: a[0, :kept + born].copy() for k, a in out.items()}, rec[0]
+
+
 def solve_lgs_joint(x, u, d, n, omega, sigma_flow, sigma_omega=None):
     """solve_lgs with the gyro refined from the flow (ofk.h: ofk_velocity_solve_joint): velocity and rotation from one 6-unknown
     least squares.  sigma_flow: the flow noise in the units of x and u; sigma_omega: None (every axis free), a scalar or three
@@ -174,6 +204,7 @@ class optical_fusion:
     _lk_light = {}                                               # PipelineConfig's lk_light field; empty: LK assumes brightness constancy
     _finite_motion = {}                                          # PipelineConfig's finite_motion field; empty: the solve takes the flow as the instantaneous field
     _track_table = {}                                            # PipelineConfig's track_table field; empty: the tracks are anonymous points
+    _track_depth = {}                                            # PipelineConfig's track_depth field; empty: no depth per track
     _rolling_shutter = {}                                        # PipelineConfig's rolling_shutter field; empty: every row is taken as exposed at the time stamp
     feature_params = dict(qualityLevel=0.7, minDistance=10, blockSize=12)
     lk_params = dict(winSize=(15, 15), maxLevel=3, criteria=(cv2.TERM_CRITERIA_EPS | cv2.TERM_CRITERIA_COUNT, 20, 0.03))
@@ -330,7 +361,7 @@ class optical_fusion:
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
                                  **self._cov, **self._joint, **self._plane, **self._epipolar, **self._zones, **self._camera, **self._rolling_shutter,
-                                 **self._finite_motion, **self._gyro_bias, **self._lk_light, **self._track_table)
+                                 **self._finite_motion, **self._gyro_bias, **self._lk_light, **self._track_table, **self._track_depth)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -374,6 +405,9 @@ class optical_fusion:
             self.last_gyro_bias = fs.gyro_bias()[0]
         if self._plane and r[15]:
             self.last_plane = fs.planes()[0]
+        if self._track_depth:
+            dp = fs.depths()
+            self.last_track_depth = {k: dp[k][0] for k in ("rho", "var", "nobs", "ids", "rec")}
         if self._epipolar and r[15]:
             rec, pts = fs.structure()
             self.last_epipolar = (rec[0], pts[0])
@@ -437,7 +471,7 @@ class optical_fusion:
 
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
                  rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None, gyro_bias=None, lk_light=None,
-                 track_table=None):
+                 track_table=None, track_depth=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -484,7 +518,11 @@ class optical_fusion:
         track_table: None (the tracks are anonymous points), True (the table alone), an ofk.TrackTable or a dict of
         ofk.track_table_setting's keywords, e.g. dict(seed="flow"): the stream then keeps an id, an age, a birth and the last flow
         per track on the device, and with seed "flow" starts LK at each track's position plus that flow (ofk.h:
-        ofk_set_track_table); self._stream.track_table() reads the table."""
+        ofk_set_track_table); self._stream.track_table() reads the table.
+        track_depth: None (no depth per track), True, an ofk.TrackDepth or a dict of ofk.track_depth_setting's keywords, e.g.
+        dict(q=1e-6): the stream then filters an inverse depth per track on the device and solves a velocity from the depths of the
+        earlier frames (ofk.h: ofk_set_track_depth); it switches the track table on when track_table is None.
+        self.last_track_depth is dict(rho, var, nobs, ids, rec), rec[0:3] that velocity and rec[3] its flag."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -572,6 +610,15 @@ class optical_fusion:
             PipelineConfig(**self._track_table).track_table_setting()    # invalid fields fail here, not at the first frame
         else:
             self._track_table = {}
+        if track_depth is not None and track_depth is not False:
+            td = track_depth if track_depth is True or isinstance(track_depth, ofk.TrackDepth) else ofk.track_depth_setting(**dict(track_depth))
+            self._track_depth = dict(track_depth=td)
+            PipelineConfig(**self._track_depth).track_depth_setting()    # invalid fields fail here, not at the first frame
+            if not self._track_table:
+                self._track_table = dict(track_table=True)           # the depths are kept per row of the table
+        else:
+            self._track_depth = {}
+        self.last_track_depth = None
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

@@ -297,6 +297,68 @@ int ofk_track_table_step(ofk_ctx *ctx, const ofk_track_table *t, uint32_t *ids, 
 int ofk_track_seed_points(ofk_ctx *ctx, const float *pts, const int *counts, int batch, int stride, const int *age, const float *flow_xy,
                           double gain, int keep_age0, float *seed_io);
 
+/* Depth per track: an inverse depth per row of the track table, filtered over the frames on the device, and the velocity solved from
+ * the depths of the earlier frames (v_map), which needs neither the ground plane nor this frame's range reading.  Off by default;
+ * with it off every stream step allocates, launches and returns what it always did.  Streams only: ofk_pairs_run ignores the setting.
+ * It needs ofk_set_track_table on.  Nothing of the records, `fused`, the tracks or the table changes with it on: v_map is reported
+ * in a record of its own.
+ * State per track row, in the table's row order, in arrays of their own: rho (f64, the inverse depth at the row's current position),
+ * var (f64), nobs (i32, measurements taken; 0 = no depth yet).  Per stream a record of OFK_TD_DOUBLES.
+ * Points and units: the points are the solve's own (the ideal points behind the camera, rolling-shutter and finite-motion rewrites);
+ * x = (next - c) * scaling, u = (next - prev) * scaling as the solve forms them, p = (x, y, 1), q = (u, 0) + p x omega, omega what the
+ * step's solve read (the sensors' behind the gyro-bias apply, the IMU state's under use_imu); v = fields 0-2 of the step's record as
+ * the chain left it; solved = record[15] != 0 (ofk_stream_step's record carries no such flag: there it is rank = record[4] >= 3).
+ * sigma_flow and b_min are given in pixels and multiplied by the stream's `scaling` in the stream steps; ofk_track_depth_step takes
+ * them in the units of its points.  All arithmetic is f64 without contraction in the order written; the sums are the solve's (four
+ * waves over the rows i = tid + 256 k, the shuffle butterfly, (s0 + s1) + (s2 + s3)).
+ * One launch, k_track_depth_step, directly in front of k_track_table_update on exactly the steps that launch it (a held step leaves
+ * state and record alone), on the status and counts k_update_tracks reads.  n = min(max(counts, 0), stride).  In order:
+ *   1. Map solve, from the state as the previous step left it.  Mature rows: status != 0, nobs >= min_obs, rho > 0 and
+ *      var <= (rel_max * rho)^2.  Their rows rho_i X_i v = X_i q_i enter the solve's own least squares with (sA, sB) = (rho_i, 1):
+ *      its ten sums, its Jacobi, its rank rule.  v_map = M^+ g, C_map = sigma_flow^2 M^-1; the depths' variances are NOT propagated
+ *      into C_map, which is therefore a lower bound.  Map flag 1 (v_map and C_map read 0): fewer than min_rows mature rows,
+ *      rank < 3, or a sum that is not finite.  Nothing of this step's record is read, so v_map does not depend on this frame's d.
+ *   2. Measurement, where solved and v is finite, for the rows with status != 0: a = (q - q_z p)_xy, b = (v_x - v_z x, v_y - v_z y),
+ *      bb = b.b, |b| = sqrt(bb), z = kappa = a.b / bb, r = (a x b) / |b|.  The row is skipped and counted if |b| < b_min (slot 7); else
+ *      if gate > 0 and r r > (gate gate)(sigma_flow sigma_flow) (slot 8); else if z is not finite (slot 7).  R = sigma_flow^2 / bb.
+ *      nobs == 0: (rho, var, nobs) = (z, R, 1) if z > 0 (slot 6), else the row stays.  Any other row, with update != 0: nu = z - rho,
+ *      S = var + R; skipped and counted if gate > 0 and nu nu > (gate gate) S (slot 9); else K = var / S, rho = rho + K nu,
+ *      var = var R / S (product form: it cannot go negative), nobs += 1 (slot 5).  update == 0 leaves rows with nobs >= 1 to rule 3.
+ *   3. Prediction to the next frame (P' = v + omega x P gives Z+ = Z g), every kept row with nobs >= 1.  Solved:
+ *      w = omega_x y - omega_y x, g = (1 + rho v_z) + w; g finite and >= 0.1: J = (1 + w) / (g g), rho = rho / g, var = var J J + q;
+ *      otherwise the row is reset to (0, 0, 0) (slot 20).  Not solved: var = var + q.
+ *   4. Compaction: the rows with status != 0 move up in order, extra = max(0, min(new count, max_total - kept, stride - kept)) rows
+ *      (0 without a re-detection) are appended as (0, 0, 0).  Rows beyond are not defined.
+ * Record: 0-2 v_map, 3 map flag, 4 mature rows used, 5 rows updated, 6 rows initialised, 7 skipped for |b| (or z not finite), 8 skipped
+ * for the cross-flow, 9 skipped for the innovation, 10-15 C_map's upper triangle, 16-18 the v rule 2 read, 19 solved, 20 rows reset by
+ * rule 3, the rest 0.
+ * The rows are zeroed where the table's begin and replace rules run; streams that step with the setting on without depths of their
+ * current tracks start there with zeroed rows.  The buffers (20 bytes per track, the records) are allocated by the first step with
+ * the setting on.
+ * ofk_set_track_depth: NULL or mode OFK_TD_OFF switches the feature off.  OFK_E_INVALID, the setting staying as it was: a mode that is
+ * neither, sigma_flow <= 0, b_min < 0, gate < 0 (0: no gates), q < 0, min_obs < 1, rel_max <= 0, min_rows < 3, a value that is not
+ * finite.  Defaults behind "off": 0.2, 0.5, 3, 0, 3, 0.25, 8, update 1.
+ * OFK_E_INVALID before any launch from a stream step with the setting on: ofk_set_track_table off; OFK_SOLVE_OFMODULE,
+ * OFK_FLOW_ROTATIONAL, OFK_KEEP_LEGACY (not the sensor model).
+ * ofk_track_depth_download, the streams of the latest step with the setting on, the first min(stride, max_pts) rows of each (every
+ * output may be NULL): rho, var [batch][stride] f64, nobs [batch][stride] i32, rec [batch][OFK_TD_DOUBLES].
+ * ofk_track_depth_reset: rows 0..n-1 of active stream b are loaded from rho, var, nobs (n <= max_pts, nobs >= 0) - a depth hint from
+ * outside, e.g. a row with nobs 1 and a wide var; the other rows stay (streams without depths of their tracks get zeroed rows first).
+ * ofk_track_depth_step, rules 1-4 on host buffers (it touches no resident state): x, u [batch][stride][2] f64, status
+ * [batch][stride], counts [batch], omega, v [batch][3], solved [batch] i32, the state rho, var, nobs [batch][stride] in and out in
+ * place, new_counts [batch] (NULL: none), max_total <= stride, rec [batch][OFK_TD_DOUBLES] out (may be NULL). */
+#define OFK_TD_OFF      0
+#define OFK_TD_ON       1
+#define OFK_TD_DOUBLES  32
+typedef struct ofk_track_depth { int mode; double sigma_flow; double b_min; double gate; double q; int min_obs; double rel_max; int min_rows; int update; } ofk_track_depth;
+int ofk_set_track_depth(ofk_ctx *ctx, const ofk_track_depth *t);
+int ofk_get_track_depth(const ofk_ctx *ctx, ofk_track_depth *t);
+int ofk_track_depth_download(ofk_ctx *ctx, double *rho, double *var, int *nobs, int stride, double *rec);
+int ofk_track_depth_reset(ofk_ctx *ctx, int b, const double *rho, const double *var, const int *nobs, int n);
+int ofk_track_depth_step(ofk_ctx *ctx, const ofk_track_depth *t, const double *x, const double *u, const uint8_t *status, const int *counts,
+                         const double *omega, const double *v, const int *solved, double *rho, double *var, int *nobs, const int *new_counts,
+                         int max_total, int batch, int stride, double *rec);
+
 /* Camera model: the lens distortion undone on the device before the solve.  The solve stage reads a point as a sample of an ideal
  * pinhole image, x = (px - cx) * scaling (sensors[19..21]); the reference's camera is a wide-angle module whose lens moves a point by
  * tens of pixels at the border.  With ofk_set_camera on, the resident chains keep everything that lives in the image on the raw
