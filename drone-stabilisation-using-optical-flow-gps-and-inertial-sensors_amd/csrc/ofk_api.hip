@@ -161,6 +161,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->fm = ofk_finite_motion{OFK_FM_OFF, 0.1};
     c->tt = ofk_track_table{OFK_TT_OFF, OFK_TT_SEED_OFF, 1.0};
     c->td = ofk_track_depth{OFK_TD_OFF, 0.2, 0.5, 3.0, 0.0, 3, 0.25, 8, 1};
+    c->tpl = ofk_track_template{OFK_TPL_OFF, 15, 0.8, 3, 2.0, OFK_TPL_KEEP, 6, 2.0, 1.5};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -214,7 +215,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
                     c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec, c->joint_rec, c->bias_rec, c->plane_rec, c->epi_rec,
-                    c->zone_tab, c->pts_prev_u, c->ttr.ids, c->tdr.rho};
+                    c->zone_tab, c->pts_prev_u, c->ttr.ids, c->tdr.rho, c->tpr.tmpl[0]};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
@@ -920,8 +921,10 @@ static int gate_tracks(ofk_ctx *c, hipStream_t s, const View &v, const ofk_level
 // ofk_set_finite_motion on, one k_finite_correct launch follows that: in place on those buffers, or from the raw points into them.
 // tt != NULL (a stream step with ofk_set_track_table's seed on; the view is the whole batch): the k_track_seed launch of rule 5 behind
 // the model seeds, and LK starts at what both have written.
+// tp != NULL (a stream step with ofk_set_track_template on; the view is the whole batch, age the table's): rules 1-5 of the templates
+// directly behind the gates, on the raw points and the status everything below reads.
 static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, const ofk_params *p, const double *imu_state,
-                 const ofk_tt_rows *tt = nullptr)
+                 const ofk_tt_rows *tt = nullptr, const ofk_tp_rows *tp = nullptr, const int *age = nullptr)
 {
     const bool seeded = c->lk_seed_mode != OFK_SEED_OFF, cam = camera_on(c);
     if (seeded && cam) {
@@ -934,6 +937,11 @@ static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv,
     launch_lk(s, v.pyr[0], v.pyr[1], c->pyr_stride, lv, v.pts_prev, v.counts, c->max_pts, p->win, p->max_count, p->eps, p->min_eig_thr,
               v.pts_next, v.status, v.err, v.nb, seeded || tt ? OFK_LK_USE_INITIAL_FLOW : 0, c->light);
     if (gate_on(c->gate)) TRY(gate_tracks(c, s, v, lv, p->win, p->max_level, p->max_count, p->eps, p->min_eig_thr, c->gate, c->light));
+    if (tp) {
+        ofk_launch_track_affine(s, v.pts_prev, v.pts_next, v.status, v.counts, c->max_pts, lv.h[0], lv.w[0], &c->tpl, tp->L, tp->rec, v.nb);
+        ofk_launch_track_template(s, *tp, v.pyr[0] + lv.off[0], v.pyr[1] + lv.off[0], c->pyr_stride, lv.h[0], lv.w[0], v.pts_prev, v.pts_next, v.status,
+                                  age, v.counts, c->max_pts, &c->tpl, v.nb);
+    }
     if (cam && seeded) ofk_launch_camera(s, &c->camera, 0, v.pts_next, v.pts_next_u, nullptr, nullptr, v.counts, c->max_pts, v.nb);
     else if (cam) ofk_launch_camera(s, &c->camera, 0, v.pts_prev, v.pts_prev_u, v.pts_next, v.pts_next_u, v.counts, c->max_pts, v.nb);
     if (rs_on(c)) {
@@ -2716,6 +2724,170 @@ extern "C" int ofk_track_depth_step(ofk_ctx *c, const ofk_track_depth *set, cons
     return OFK_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ track templates
+static int check_tpl(ofk_ctx *c, const ofk_track_template *t, const char *who)
+{
+    if (t->mode != OFK_TPL_OFF && t->mode != OFK_TPL_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_TPL_OFF nor OFK_TPL_ON", who, t->mode);
+    if (t->mode == OFK_TPL_OFF) return OFK_OK;
+    if (!std::isfinite(t->ncc_min) || !std::isfinite(t->anchor_max) || !std::isfinite(t->fit_gate) || !std::isfinite(t->scale_max))
+        return ofk_fail(c, OFK_E_INVALID, "%s: ncc_min, anchor_max, fit_gate and scale_max must be finite", who);
+    if (t->win < 5 || t->win > 31 || t->win % 2 == 0) return ofk_fail(c, OFK_E_INVALID, "%s: win = %d must be odd and in 5..31", who, t->win);
+    if (t->ncc_min < -1.0 || t->ncc_min > 1.0) return ofk_fail(c, OFK_E_INVALID, "%s: ncc_min = %g outside [-1, 1]", who, t->ncc_min);
+    if (t->anchor_iters < 0 || t->anchor_iters > 8) return ofk_fail(c, OFK_E_INVALID, "%s: anchor_iters = %d outside 0..8", who, t->anchor_iters);
+    if (!(t->anchor_max > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: anchor_max = %g must be positive", who, t->anchor_max);
+    if (t->outside != OFK_TPL_KEEP && t->outside != OFK_TPL_DROP) return ofk_fail(c, OFK_E_INVALID, "%s: outside = %d is neither OFK_TPL_KEEP nor OFK_TPL_DROP", who, t->outside);
+    if (t->fit_min < 3) return ofk_fail(c, OFK_E_INVALID, "%s: fit_min = %d must be at least 3", who, t->fit_min);
+    if (t->fit_gate < 0.0) return ofk_fail(c, OFK_E_INVALID, "%s: fit_gate = %g must not be negative (0: a single fit)", who, t->fit_gate);
+    if (t->scale_max != 0.0 && !(t->scale_max >= 1.0)) return ofk_fail(c, OFK_E_INVALID, "%s: scale_max = %g is neither 0 (never refresh) nor >= 1", who, t->scale_max);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_track_template(ofk_ctx *c, const ofk_track_template *t)
+{
+    const int rc = setting_set(c, &ofk_ctx::tpl, t && t->mode == OFK_TPL_OFF ? nullptr : t, [](ofk_track_template &s) { s.mode = OFK_TPL_OFF; },
+                               [c](const ofk_track_template *v) { return check_tpl(c, v, "ofk_set_track_template"); });
+    if (c && rc == OFK_OK) c->tp_live = 0;                       // templates of another window are no templates: the next step starts over
+    return rc;
+}
+extern "C" int ofk_get_track_template(const ofk_ctx *c, ofk_track_template *t) { return setting_get(c, &ofk_ctx::tpl, t); }
+
+static bool tp_on(const ofk_ctx *c) { return c->tpl.mode != OFK_TPL_OFF; }
+static int tp_stride_of(int win) { return (int)up((size_t)(win + 2) * (win + 2), 4); }
+
+// the state's arrays over `np` rows of `ts` template bytes and the records of `batch` streams carved out of base (NULL: nothing is carved)
+static size_t tp_carve(ofk_tp_rows &t, uint8_t *base, size_t np, size_t batch, size_t ts)
+{
+    size_t o = 0;
+    auto take = [&](size_t bytes) { uint8_t *p = base ? base + o : nullptr; o += up(bytes, 256); return p; };
+    t.tmpl[0] = take(np * ts); t.tmpl[1] = take(np * ts);
+    t.A = (float *)take(np * 16); t.A_new = (float *)take(np * 16);
+    t.ncc = (float *)take(np * 4); t.ncc_new = (float *)take(np * 4); t.move = (float *)take(np * 4);
+    t.flag = take(np); t.flag_new = take(np); t.tstate = take(np);
+    t.L = (float *)take(batch * 16); t.rec = (double *)take(batch * OFK_TPL_DOUBLES * 8);
+    return o;
+}
+static int tp_alloc(ofk_ctx *c)
+{
+    if (c->tpr.tmpl[0]) return OFK_OK;                           // one allocation for the widest window, carved into the arrays
+    ofk_tp_rows t;
+    const size_t np = (size_t)c->max_batch * c->max_pts, ts = (size_t)tp_stride_of(31), bytes = tp_carve(t, nullptr, np, (size_t)c->max_batch, ts);
+    uint8_t *base = nullptr;
+    OFK_HIP(c, hipMalloc((void **)&base, bytes));
+    tp_carve(c->tpr, base, np, (size_t)c->max_batch, ts);          // the context owns it from here on, whatever follows
+    OFK_HIP(c, hipMemsetAsync(base, 0, bytes, c->stream));
+    return OFK_OK;
+}
+
+static int tp_check_step(ofk_ctx *c, const char *who)
+{
+    if (tp_on(c) && c->tt.mode == OFK_TT_OFF)
+        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_track_template is on without ofk_set_track_table: the templates are kept per row of the table", who);
+    return OFK_OK;
+}
+
+// templates for the current tracks of the first B streams: none (tstate 0) unless they are live already
+static int tp_begin(ofk_ctx *c, int B)
+{
+    TRY(tp_alloc(c));
+    if (c->tp_live != B) {
+        OFK_HIP(c, hipMemsetAsync(c->tpr.tstate, 0, (size_t)c->max_batch * c->max_pts, c->stream));
+        OFK_HIP(c, hipMemsetAsync(c->tpr.rec, 0, (size_t)c->max_batch * OFK_TPL_DOUBLES * 8, c->stream));
+        c->tpr.cur = 0; c->tpr.tstride = tp_stride_of(c->tpl.win);
+    }
+    c->tp_batch = c->tp_live = B;
+    return OFK_OK;
+}
+
+extern "C" int ofk_track_template_download(ofk_ctx *c, uint8_t *tmpl, float *A, float *ncc, uint8_t *flag, uint8_t *tstate, int stride, double *rec)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->tp_batch < 1 || !c->tpr.tmpl[0]) return ofk_fail(c, OFK_E_INVALID, "ofk_track_template_download: no stream has stepped with ofk_set_track_template on yet");
+    if ((tmpl || A || ncc || flag || tstate) && stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_track_template_download: stride %d", stride);
+    TRY(enter(c));
+    const int B = c->tp_batch;
+    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    const ofk_tp_rows &t = c->tpr;
+    if (tmpl && tp_stride_of(c->tpl.win) != t.tstride)
+        return ofk_fail(c, OFK_E_INVALID, "ofk_track_template_download: the window was set to %d behind the latest step: its templates are gone", c->tpl.win);
+    struct { void *dst; const void *src; size_t el; } rows[] = {{tmpl, t.tmpl[t.cur], (size_t)t.tstride}, {A, t.A, 16}, {ncc, t.ncc, 4}, {flag, t.flag, 1},
+                                                                 {tstate, t.tstate, 1}};
+    for (const auto &r : rows)
+        if (r.dst) OFK_HIP(c, hipMemcpy2DAsync(r.dst, (size_t)stride * r.el, r.src, mp * r.el, n * r.el, B, hipMemcpyDeviceToHost, c->stream));
+    if (rec) OFK_HIP(c, hipMemcpyAsync(rec, t.rec, (size_t)B * OFK_TPL_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+// rule 1 on host buffers: device scratch only
+extern "C" int ofk_track_affine_fit(ofk_ctx *c, const ofk_track_template *set, const float *prev_pts, const float *next_pts, const uint8_t *status,
+                                    const int *counts, int batch, int stride, int h, int w, double *rec, float *L)
+{
+    const char *who = "ofk_track_affine_fit";
+    if (!c) return OFK_E_INVALID;
+    if (!set || !prev_pts || !next_pts || !status || !counts || !rec) return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
+    if (batch < 1 || stride < 1 || h < 1 || w < 1) return ofk_fail(c, OFK_E_INVALID, "%s: batch %d / stride %d / frame %d x %d", who, batch, stride, w, h);
+    if (set->mode == OFK_TPL_OFF) return ofk_fail(c, OFK_E_INVALID, "%s: the setting is off", who);
+    TRY(check_tpl(c, set, who));
+    TRY(check_counts(c, who, counts, batch, stride));
+    const size_t np = (size_t)batch * stride, B = (size_t)batch;
+    Bump bp;
+    TRY(est_begin(c, np * 17 + B * (4 + 16 + OFK_TPL_DOUBLES * 8) + 8 * 256, bp));
+    const float *d_prev = (const float *)bp.put(prev_pts, np * 8), *d_next = (const float *)bp.put(next_pts, np * 8);
+    const uint8_t *d_st = (const uint8_t *)bp.put(status, np);
+    const int *d_cnt = (const int *)bp.put(counts, B * 4);
+    float *d_L = (float *)bp.take(B * 16);
+    double *d_rec = bp.take(B * OFK_TPL_DOUBLES * 8);
+    if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    OFK_HIP(c, hipMemsetAsync(d_rec, 0, B * OFK_TPL_DOUBLES * 8, c->stream));
+    ofk_launch_track_affine(c->stream, d_prev, d_next, d_st, d_cnt, stride, h, w, set, d_L, d_rec, batch);
+    TRY(check_launch(c, "k_track_affine"));
+    if (L) OFK_HIP(c, hipMemcpyAsync(L, d_L, B * 16, hipMemcpyDeviceToHost, c->stream));
+    return get(c, rec, d_rec, B * OFK_TPL_DOUBLES * 8);
+}
+
+// rules 2-6 on host buffers: device scratch only
+extern "C" int ofk_track_template_step(ofk_ctx *c, const ofk_track_template *set, const uint8_t *prev, const uint8_t *next, int h, int w,
+                                       const float *prev_pts, float *next_pts, uint8_t *status, const int *age, const int *counts, const float *L,
+                                       uint8_t *tmpl, float *A, float *ncc, uint8_t *flag, uint8_t *tstate, const int *new_counts, int max_total,
+                                       int batch, int stride, double *rec)
+{
+    const char *who = "ofk_track_template_step";
+    if (!c) return OFK_E_INVALID;
+    if (!set || !prev || !next || !prev_pts || !next_pts || !status || !age || !counts || !L || !tmpl || !A || !ncc || !flag || !tstate)
+        return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
+    if (batch < 1 || stride < 1 || h < 2 || w < 2) return ofk_fail(c, OFK_E_INVALID, "%s: batch %d / stride %d / frame %d x %d", who, batch, stride, w, h);
+    if (max_total < 0 || max_total > stride) return ofk_fail(c, OFK_E_INVALID, "%s: max_total %d outside 0..%d", who, max_total, stride);
+    if (set->mode == OFK_TPL_OFF) return ofk_fail(c, OFK_E_INVALID, "%s: the setting is off", who);
+    TRY(check_tpl(c, set, who));
+    TRY(check_counts(c, who, counts, batch, stride));
+    const size_t np = (size_t)batch * stride, B = (size_t)batch, px = (size_t)h * w, ts = (size_t)tp_stride_of(set->win);
+    Bump bp;
+    TRY(est_begin(c, 2 * up(B * px, 256) + np * (2 * ts + 2 * 16 + 3 * 4 + 3 + 2 * 8 + 1 + 4) + B * (4 + 4 + 16 + OFK_TPL_DOUBLES * 8) + 24 * 256, bp));
+    const uint8_t *d_prev = (const uint8_t *)bp.put(prev, B * px), *d_next = (const uint8_t *)bp.put(next, B * px);
+    ofk_tp_rows t = {};
+    t.tmpl[0] = (uint8_t *)bp.put(tmpl, np * ts); t.tmpl[1] = (uint8_t *)bp.take(np * ts); t.cur = 0; t.tstride = (int)ts;
+    t.A = (float *)bp.put(A, np * 16); t.A_new = (float *)bp.take(np * 16);
+    t.ncc = (float *)bp.put(ncc, np * 4); t.ncc_new = (float *)bp.take(np * 4); t.move = (float *)bp.take(np * 4);
+    t.flag = (uint8_t *)bp.put(flag, np); t.flag_new = (uint8_t *)bp.take(np); t.tstate = (uint8_t *)bp.put(tstate, np);
+    t.L = (float *)bp.put(L, B * 16); t.rec = bp.take(B * OFK_TPL_DOUBLES * 8);
+    const float *d_pp = (const float *)bp.put(prev_pts, np * 8);
+    float *d_np = (float *)bp.put(next_pts, np * 8);
+    uint8_t *d_st = (uint8_t *)bp.put(status, np);
+    const int *d_age = (const int *)bp.put(age, np * 4), *d_cnt = (const int *)bp.put(counts, B * 4), *d_nc = (const int *)bp.put(new_counts, B * 4);
+    if (bp.rc) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    OFK_HIP(c, hipMemsetAsync(t.rec, 0, B * OFK_TPL_DOUBLES * 8, c->stream));
+    OFK_HIP(c, hipMemcpyAsync(t.tmpl[1], t.tmpl[0], np * ts, hipMemcpyDeviceToDevice, c->stream));   // rows beyond the kept ones come back as they went in
+    ofk_launch_track_template(c->stream, t, d_prev, d_next, px, h, w, d_pp, d_np, d_st, d_age, d_cnt, stride, set, batch);
+    ofk_launch_track_template_update(c->stream, t, d_st, d_cnt, stride, d_nc, max_total, set, batch);
+    TRY(check_launch(c, "k_track_template"));
+    struct { void *dst; const void *src; size_t bytes; } back[] = {{next_pts, d_np, np * 8}, {status, d_st, np}, {tmpl, t.tmpl[1], np * ts}, {A, t.A, np * 16},
+        {ncc, t.ncc, np * 4}, {flag, t.flag, np}, {tstate, t.tstate, np}, {rec, t.rec, B * OFK_TPL_DOUBLES * 8}};
+    for (const auto &r : back)
+        if (r.dst) OFK_HIP(c, hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ video streams
 static int stream_alloc(ofk_ctx *c)
 {
@@ -2776,6 +2948,7 @@ static int stream_begin_impl(ofk_ctx *c, const uint8_t *first_bgr, int batch, in
     TRY(stream_detect(c, nullptr, nullptr, batch, h, w, p, c->pts_prev, c->counts));
     c->tt_batch = c->tt_live = 0;                                // ... and with a new track table, if the setting is on
     c->td_batch = c->td_live = 0;                                // ... and without depths: the first step with that setting on starts them
+    c->tp_batch = c->tp_live = 0;                                // ... and without templates
     if (tt_on(c)) {
         TRY(tt_alloc(c));
         ofk_launch_track_table_begin(c->stream, c->ttr, c->pts_prev, c->counts, c->max_pts, batch);
@@ -2938,6 +3111,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     TRY(second_prepare(c, B, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     TRY(bias_check_step(c, B, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     TRY(td_check_step(c, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
+    TRY(tp_check_step(c, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     const int defer = second_on(c) && fu && fu->filter ? 1 : 0;   // the second-stage kernel corrects
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
@@ -2963,6 +3137,9 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     const bool depth = td_on(c);                                 // td_check_step: then the table is on
     if (depth) TRY(td_begin(c, B));
     else c->td_live = 0;                                         // the tracks move on without their depths
+    const bool templ = tp_on(c);                                 // tp_check_step: then the table is on
+    if (templ) TRY(tp_begin(c, B));
+    else c->tp_live = 0;                                         // the tracks move on without their templates
     const bool flow_seed = table && c->tt.seed == OFK_TT_SEED_FLOW;
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
@@ -2982,7 +3159,8 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)
     const View v = view_of(c, 0, B, 0);                          // the solve stage reads v.solve_*; the tracks, the zones and the re-detection stay in the image
-    TRY(track(c, c->stream, v, lv, p, fu && fu->use_imu ? c->imu_state : nullptr, flow_seed ? &c->ttr : nullptr));
+    TRY(track(c, c->stream, v, lv, p, fu && fu->use_imu ? c->imu_state : nullptr, flow_seed ? &c->ttr : nullptr, templ ? &c->tpr : nullptr,
+              c->ttr.age));
     if (zones_on)                                                // the solve stage turns the status into its keep flags: rule 1 needs both
         OFK_HIP(c, hipMemcpyAsync(c->zone_status, c->status, (size_t)B * c->max_pts, hipMemcpyDeviceToDevice, c->stream));
     if (fu) {
@@ -3035,6 +3213,10 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
             in.omega = imu ? c->imu_state + 18 : c->sensors + 4; in.omega_stride = imu ? OFK_IMU_STATE : OFK_SENSOR_DOUBLES;
             in.v = c->records; in.plain = fu ? 0 : 1;
             ofk_launch_track_depth_step(c->stream, c->tdr, in, &c->td, B);
+        }
+        if (templ) {                                             // rule 6, with the keep rule of the two launches below; the templates change buffers
+            ofk_launch_track_template_update(c->stream, c->tpr, c->status, c->counts, c->max_pts, any ? c->new_counts : nullptr, p->max_corners, &c->tpl, B);
+            c->tpr.cur ^= 1;
         }
         if (table)                                               // in front of it: it overwrites pts_prev and counts
             ofk_launch_track_table_update(c->stream, c->ttr, c->pts_prev, c->pts_next, c->status, c->counts, c->max_pts, any ? c->pts_new : nullptr,

@@ -35,6 +35,14 @@ struct ofk_td_in {
     const double *v; int plain;                                  // [B][OFK_RECORD_DOUBLES]: v in 0-2, solved in 15 (plain: rank 3 in slot 4)
 };
 
+// the track templates (ofk.h: ofk_set_track_template): the state's arrays, rows `stride` apart per stream in the table's row order;
+// tmpl[cur] holds the templates, tmpl[cur ^ 1] takes them from the compaction; *_new, move: what the latest k_track_template found
+struct ofk_tp_rows {
+    uint8_t *tmpl[2]; int cur, tstride;
+    float *A, *A_new, *ncc, *ncc_new, *move; uint8_t *flag, *flag_new, *tstate;
+    float *L; double *rec;                                       // [B][4], [B][OFK_TPL_DOUBLES]
+};
+
 struct ofk_comm;
 struct ofk_ctx {
     int device;
@@ -137,6 +145,9 @@ struct ofk_ctx {
     ofk_track_depth td;                      // ofk_set_track_depth: mode OFK_TD_OFF unless set
     ofk_td_rows tdr;                         // the depth state's device rows, [B][max_pts] each, and records; one lazy allocation (tdr.rho owns it)
     int td_batch, td_live;                   // streams of the latest step with the depths on (ofk_track_depth_download), 0 = none; streams whose rows match their current tracks
+    ofk_track_template tpl;                  // ofk_set_track_template: mode OFK_TPL_OFF unless set
+    ofk_tp_rows tpr;                         // the templates' device rows, [B][max_pts] each, and records; one lazy allocation (tpr.tmpl[0] owns it)
+    int tp_batch, tp_live;                   // streams of the latest step with the templates on (ofk_track_template_download), 0 = none; streams whose rows match their current tracks
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -266,6 +277,14 @@ void ofk_launch_track_seed(hipStream_t s, const float *pts, const int *counts, i
 void ofk_launch_track_depth_begin(hipStream_t s, const ofk_td_rows &t, const int *counts, int stride, int batch);
 void ofk_launch_track_depth_replace(hipStream_t s, const ofk_td_rows &t, const int *limit, const int *new_counts, int stride, int batch);
 void ofk_launch_track_depth_step(hipStream_t s, const ofk_td_rows &t, const ofk_td_in &in, const ofk_track_depth *d, int batch);
+// the track templates (ofk.h: ofk_set_track_template; k_track_template.inc): rule 1, rules 2-5 behind the gates, rule 6 in front of the table's update
+void ofk_launch_track_affine(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts, int stride,
+                             int h, int w, const ofk_track_template *d, float *L, double *rec, int batch);
+void ofk_launch_track_template(hipStream_t s, const ofk_tp_rows &t, const uint8_t *prev_img, const uint8_t *next_img, size_t img_stride, int h,
+                               int w, const float *prev_pts, float *next_pts, uint8_t *status, const int *age, const int *counts, int stride,
+                               const ofk_track_template *d, int batch);
+void ofk_launch_track_template_update(hipStream_t s, const ofk_tp_rows &t, const uint8_t *status, const int *counts, int stride,
+                                      const int *new_counts, int max_total, const ofk_track_template *d, int batch);
 void ofk_launch_pairs_solve(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status,
                             const int *counts, int pts_stride, const double *sensors, int variant, int use_feas,
                             double feas_T, const int *cand_count, double *records, int batch);

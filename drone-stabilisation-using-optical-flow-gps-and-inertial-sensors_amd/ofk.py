@@ -42,6 +42,7 @@ SYMBOLS = (
     "ofk_set_finite_motion", "ofk_get_finite_motion", "ofk_finite_correct_points", "ofk_finite_download",
     "ofk_set_track_table", "ofk_get_track_table", "ofk_track_table_download", "ofk_track_table_step", "ofk_track_seed_points",
     "ofk_set_track_depth", "ofk_get_track_depth", "ofk_track_depth_download", "ofk_track_depth_reset", "ofk_track_depth_step",
+    "ofk_set_track_template", "ofk_get_track_template", "ofk_track_template_download", "ofk_track_affine_fit", "ofk_track_template_step",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
     "ofk_stream_begin_jpeg", "ofk_stream_step_jpeg",
@@ -108,6 +109,11 @@ TT_SEEDS = {"off": TT_SEED_OFF, "flow": TT_SEED_FLOW}
 TT_STATS = 8                                             # count, kept, lost, born, oldest age, step, next_id, rows seeded from their flow
 TD_OFF, TD_ON = 0, 1                                     # ofk_set_track_depth
 TD_DOUBLES = 32                                          # v_map, flag, mature, updated, initialised, 3 skip counts, C_map, v, solved, reset
+TPL_OFF, TPL_ON = 0, 1                                   # ofk_set_track_template
+TPL_DOUBLES = 32                                         # M, t, fit flag, rows of the two fits, rms, nine counts, largest move
+TPL_KEEP, TPL_DROP = 0, 1
+TPL_OUTSIDE = {"keep": TPL_KEEP, "drop": TPL_DROP}
+TPL_NOT_TRACKED, TPL_PASS, TPL_FAIL, TPL_ABANDONED, TPL_OUTSIDE_ROW, TPL_FLAT, TPL_NO_TEMPLATE, TPL_CAPTURED = 0, 1, 2, 3, 4, 5, 6, 16
 FLOW_LK, FLOW_ROTATIONAL = 0, 1
 KEEP_STATUS, KEEP_LEGACY = 0, 1
 CONTROL_SENSORS, CONTROL_IMU = 0, 1
@@ -474,6 +480,43 @@ def track_depth_setting(mode=True, sigma_flow=0.2, b_min=0.5, gate=3.0, q=0.0, m
     return t
 
 
+class TrackTemplate(C.Structure):
+    """ofk_track_template (include/ofk.h): the birth patch per track of a stream, the score against it and the re-anchoring."""
+    _fields_ = [("mode", C.c_int), ("win", C.c_int), ("ncc_min", C.c_double), ("anchor_iters", C.c_int), ("anchor_max", C.c_double),
+                ("outside", C.c_int), ("fit_min", C.c_int), ("fit_gate", C.c_double), ("scale_max", C.c_double)]
+
+
+def tpl_stride(win):
+    """Bytes between the templates of two rows: (win + 2)^2 rounded up to a multiple of 4."""
+    return ((int(win) + 2) ** 2 + 3) // 4 * 4
+
+
+def track_template_setting(mode=True, win=15, ncc_min=0.8, anchor_iters=3, anchor_max=2.0, outside="keep", fit_min=6, fit_gate=2.0, scale_max=1.5):
+    """A TrackTemplate structure from names: mode True / False (or TPL_*); win the odd template window (5..31); a row whose score
+    against its template is below ncc_min is dropped; anchor_iters (0: score only) steps of at most anchor_max px in all pull the
+    position back; outside "keep" / "drop" (or TPL_KEEP / TPL_DROP): rows whose window leaves the frame; the step map is fitted to at
+    least fit_min rows, a second time over the rows within fit_gate px (0: once); a template is captured afresh when the accumulated
+    map's area scale leaves [1 / scale_max^2, scale_max^2] (0: never)."""
+    mode = int(mode)
+    if mode not in (TPL_OFF, TPL_ON):
+        raise ValueError(f"track-template mode {mode} is none of TPL_OFF, TPL_ON")
+    if isinstance(outside, str):
+        if outside not in TPL_OUTSIDE:
+            raise ValueError(f"track-template outside {outside!r} is none of {sorted(TPL_OUTSIDE)}")
+        outside = TPL_OUTSIDE[outside]
+    t = TrackTemplate(mode, int(win), float(ncc_min), int(anchor_iters), float(anchor_max), int(outside), int(fit_min), float(fit_gate),
+                      float(scale_max))
+    if mode != TPL_OFF:
+        if not all(np.isfinite(x) for x in (t.ncc_min, t.anchor_max, t.fit_gate, t.scale_max)):
+            raise ValueError("track-template ncc_min, anchor_max, fit_gate and scale_max must be finite")
+        if not (5 <= t.win <= 31 and t.win % 2 == 1 and -1 <= t.ncc_min <= 1 and 0 <= t.anchor_iters <= 8 and t.anchor_max > 0
+                and t.outside in (TPL_KEEP, TPL_DROP) and t.fit_min >= 3 and t.fit_gate >= 0 and (t.scale_max == 0 or t.scale_max >= 1)):
+            raise ValueError(f"track-template setting outside its range: win {t.win} odd in 5..31, ncc_min {t.ncc_min} in [-1, 1], "
+                             f"anchor_iters {t.anchor_iters} in 0..8, anchor_max {t.anchor_max} > 0, outside {t.outside} in (0, 1), "
+                             f"fit_min {t.fit_min} >= 3, fit_gate {t.fit_gate} >= 0, scale_max {t.scale_max} 0 or >= 1")
+    return t
+
+
 class Fusion(C.Structure):
     """ofk_fusion (include/ofk.h): what ofk_stream_step_fused does between LK and the next frame."""
     _fields_ = [("use_imu", C.c_int), ("flow", C.c_int), ("keep", C.c_int), ("filter", C.c_int), ("control", C.c_int),
@@ -484,7 +527,7 @@ class Fusion(C.Structure):
 # the struct settings: ofk_set_<name> / ofk_get_<name> take the context and a pointer to the struct
 SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("gyro_bias", GyroBias), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate), ("lk_light", LkLight),
             ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion),
-            ("track_table", TrackTable), ("track_depth", TrackDepth))
+            ("track_table", TrackTable), ("track_depth", TrackDepth), ("track_template", TrackTemplate))
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -582,6 +625,9 @@ def load_library():
         L.ofk_track_depth_download.argtypes = [vp, vp, vp, vp, i, vp]
         L.ofk_track_depth_reset.argtypes = [vp, i, vp, vp, vp, i]
         L.ofk_track_depth_step.argtypes = [vp, C.POINTER(TrackDepth), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
+        L.ofk_track_template_download.argtypes = [vp, vp, vp, vp, vp, vp, i, vp]
+        L.ofk_track_affine_fit.argtypes = [vp, C.POINTER(TrackTemplate), vp, vp, vp, vp, i, i, i, i, vp, vp]
+        L.ofk_track_template_step.argtypes = [vp, C.POINTER(TrackTemplate), vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
         L.ofk_lk_pyr_fb.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, i, d, d, vp, i, vp, vp, vp, C.POINTER(TrackGate), vp, vp, vp]
         L.ofk_lk_pyr_light.argtypes = L.ofk_lk_pyr_fb.argtypes + [C.POINTER(LkLight)]
         L.ofk_imu_propagate.argtypes = [vp, vp, vp, i]
@@ -1091,6 +1137,75 @@ class Context:
             self._ck(self._L.ofk_track_depth_step(self._h, C.byref(td), _p(xx), _p(uu), _p(st), _p(cn), _p(om), _p(vv), _p(so), _p(rho), _p(var),
                                                   _p(nobs), _p(nc), S if max_total is None else int(max_total), B, S, _p(rec)))
         return dict(rho=rho, var=var, nobs=nobs), rec
+
+    def set_track_template(self, track_template=None, **settings):
+        """ofk_set_track_template: a TrackTemplate (or track_template_setting's keywords); None or mode False switches it off.  Every
+        later stream step keeps the birth patch of every row of the track table (which must be on), scores the tracked window against
+        it through the accumulated map and pulls the position back onto it.  pairs_run ignores the setting."""
+        self._set_struct(self._L.ofk_set_track_template, track_template, settings, track_template_setting, lock=True)
+
+    def get_track_template(self):
+        return self._get_struct(self._L.ofk_get_track_template, TrackTemplate)
+
+    def track_template_download(self, batch=None, stride=None):
+        """ofk_track_template_download -> dict(tmpl [batch,stride,tpl_stride(win)] u8, A [batch,stride,4] f32, ncc [batch,stride] f32,
+        flag, tstate [batch,stride] u8, rec [batch,32]) of the streams of the latest step with the setting on, rows in the order of the
+        tracks that step returned.  rec: M 0-3, t 4-5, fit flag 6, rows of the two fits 7-8, rms 9, rows scored 10, dropped 11, moved 12,
+        abandoned 13, outside 14, flat 15, captured 16, without a template 17, marked for refresh 18, largest move 19."""
+        S = self.max_pts if stride is None else int(stride)
+        if S < 1:
+            raise ValueError(f"track_template_download: stride {S}")
+        ts = tpl_stride(self.get_track_template().win)
+        u = ((S,), np.uint8)
+        tmpl, A, ncc, flag, tstate, rec = self._rows(
+            "track_template_download", self.max_batch if batch is None else int(batch),
+            lambda *p: self._L.ofk_track_template_download(self._h, *p[:5], S, p[5]), ((S, ts), np.uint8), ((S, 4), np.float32),
+            ((S,), np.float32), u, u, ((TPL_DOUBLES,), np.float64))
+        return dict(tmpl=tmpl, A=A, ncc=ncc, flag=flag, tstate=tstate, rec=rec)
+
+    def track_affine_fit(self, prev_pts, next_pts, status, counts, h, w, track_template=None, **settings):
+        """ofk_track_affine_fit, the stage entry of the templates' step map: prev_pts, next_pts [B,S,2] f32, status [B,S], counts [B],
+        the frame's h and w -> (rec [B,32] with slots 0-9 filled, L [B,4] f32)."""
+        tp = track_template if track_template is not None else track_template_setting(**settings)
+        pp = _arr(prev_pts, np.float32)
+        if pp.ndim != 3 or pp.shape[2] != 2 or pp.shape[1] < 1:
+            raise ValueError(f"track_affine_fit: prev_pts {pp.shape} is not [B, S >= 1, 2]")
+        B, S = pp.shape[:2]
+        nn = _arr(next_pts, np.float32, (B, S, 2)); st = _arr(status, np.uint8, (B, S)); cn = _arr(counts, np.int32, (B,))
+        rec = np.zeros((B, TPL_DOUBLES), np.float64); L = np.zeros((B, 4), np.float32)
+        with self._lock:
+            self._ck(self._L.ofk_track_affine_fit(self._h, C.byref(tp), _p(pp), _p(nn), _p(st), _p(cn), B, S, int(h), int(w), _p(rec), _p(L)))
+        return rec, L
+
+    def track_template_step(self, prev, next, prev_pts, next_pts, status, age, counts, L, state, new_counts=None, max_total=None,
+                            track_template=None, **settings):
+        """ofk_track_template_step, the stage entry of rules 2-6 on host arrays: prev, next [B,h,w] u8 gray; prev_pts, next_pts [B,S,2]
+        f32; status [B,S]; age [B,S] i32; counts [B]; L [B,4] f32 (track_affine_fit's); state: dict(tmpl [B,S,tpl_stride(win)] u8,
+        A [B,S,4] f32, ncc [B,S] f32, flag, tstate [B,S] u8); new_counts [B] the re-detected corners (None: none); max_total (default
+        S).  -> (next_pts, status: rows as tracked; state: compacted; rec [B,32] with slots 10-19 filled), new arrays.  Touches no
+        resident state."""
+        tp = track_template if track_template is not None else track_template_setting(**settings)
+        g0 = _arr(prev, np.uint8)
+        if g0.ndim != 3:
+            raise ValueError(f"track_template_step: prev {g0.shape} is not [B, h, w]")
+        B, h, w = g0.shape
+        g1 = _arr(next, np.uint8, (B, h, w))
+        pp = _arr(prev_pts, np.float32)
+        if pp.ndim != 3 or pp.shape[0] != B or pp.shape[2] != 2 or pp.shape[1] < 1:
+            raise ValueError(f"track_template_step: prev_pts {pp.shape} is not [{B}, S >= 1, 2]")
+        S, ts = pp.shape[1], tpl_stride(tp.win)
+        nn = np.array(_arr(next_pts, np.float32, (B, S, 2))); st = np.array(_arr(status, np.uint8, (B, S)))
+        ag = _arr(age, np.int32, (B, S)); cn = _arr(counts, np.int32, (B,)); LL = _arr(L, np.float32, (B, 4))
+        tm = np.array(_arr(state["tmpl"], np.uint8, (B, S, ts))); A = np.array(_arr(state["A"], np.float32, (B, S, 4)))
+        ncc = np.array(_arr(state["ncc"], np.float32, (B, S))); fl = np.array(_arr(state["flag"], np.uint8, (B, S)))
+        tst = np.array(_arr(state["tstate"], np.uint8, (B, S)))
+        nc = _opt(new_counts, np.int32, (B,))
+        rec = np.zeros((B, TPL_DOUBLES), np.float64)
+        with self._lock:
+            self._ck(self._L.ofk_track_template_step(self._h, C.byref(tp), _p(g0), _p(g1), h, w, _p(pp), _p(nn), _p(st), _p(ag), _p(cn), _p(LL),
+                                                     _p(tm), _p(A), _p(ncc), _p(fl), _p(tst), _p(nc), S if max_total is None else int(max_total),
+                                                     B, S, _p(rec)))
+        return nn, st, dict(tmpl=tm, A=A, ncc=ncc, flag=fl, tstate=tst), rec
 
     def zones_reset(self, batch=None):
         """ofk_zones_reset: the zone tables of the first `batch` streams (all by default) are cleared."""

@@ -170,6 +170,10 @@ class PipelineConfig:
     # depth per row of its track table (which must be on) and solves a velocity from the depths of the earlier frames;
     # FlowPipeline ignores it
     track_depth: object = None
+    # track templates (ofk.h: ofk_set_track_template): None, True (the defaults) or an ofk.TrackTemplate: every stream keeps the patch
+    # each track of its table (which must be on) was born with, scores the tracked window against it through the accumulated image
+    # deformation, drops the rows that no longer match and pulls the others back onto it; FlowPipeline ignores it
+    track_template: object = None
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -295,6 +299,16 @@ class PipelineConfig:
         m = ofk.track_depth_setting(m.mode, m.sigma_flow, m.b_min, m.gate, m.q, m.min_obs, m.rel_max, m.min_rows, m.update)   # range-checked
         return None if m.mode == ofk.TD_OFF else m
 
+    def track_template_setting(self):
+        """The ofk.TrackTemplate structure of this configuration, None when the templates are off."""
+        if self.track_template is None or self.track_template is False:
+            return None
+        m = ofk.track_template_setting() if self.track_template is True else self.track_template
+        if not isinstance(m, ofk.TrackTemplate):
+            raise ValueError(f"track_template {m!r} is neither None, True nor an ofk.TrackTemplate")
+        m = ofk.track_template_setting(m.mode, m.win, m.ncc_min, m.anchor_iters, m.anchor_max, m.outside, m.fit_min, m.fit_gate, m.scale_max)   # range-checked
+        return None if m.mode == ofk.TPL_OFF else m
+
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
                           int(self.win), int(self.max_level), int(self.max_count), float(self.eps), float(self.min_eig_thr),
@@ -403,7 +417,8 @@ class FusionConfig:
 
 def _apply_settings(ctx, cfg, zones):
     """The settings a PipelineConfig switches on, on a fresh context, in the order the library's checks were written for; zones:
-    whether the exclusion zones, the gyro bias, the track table and the depths per track are among them (they belong to the stream steps)."""
+    whether the exclusion zones, the gyro bias, the track table, the depths per track and the track templates are among them (they
+    belong to the stream steps)."""
     if cfg.lk_seed != "off":
         ctx.set_lk_seed(cfg.lk_seed, cfg.seed_gain)
     steps = [(ctx.set_robust, cfg.robust_setting), (ctx.set_track_gate, cfg.track_gate_setting), (ctx.set_lk_light, cfg.lk_light_setting),
@@ -412,7 +427,7 @@ def _apply_settings(ctx, cfg, zones):
              (ctx.set_epipolar, cfg.epipolar_setting)]
     if zones:
         steps += [(ctx.set_zones, cfg.zones_setting), (ctx.set_gyro_bias, cfg.gyro_bias_setting), (ctx.set_track_table, cfg.track_table_setting),
-                  (ctx.set_track_depth, cfg.track_depth_setting)]
+                  (ctx.set_track_depth, cfg.track_depth_setting), (ctx.set_track_template, cfg.track_template_setting)]
     steps += [(ctx.set_camera, cfg.camera_setting), (ctx.set_rolling_shutter, cfg.rolling_shutter_setting),
               (ctx.set_finite_motion, cfg.finite_motion_setting)]
     for setter, setting in steps:                                # every *_setting() is None when its setting is off
@@ -529,6 +544,21 @@ class FlowStream:
         t = self.ctx.track_table_download(self.batch)
         cnt = t["stats"][:, 0]
         out = {k: [d[k][b, :cnt[b]] for b in range(self.batch)] for k in ("rho", "var", "nobs")}
+        out["ids"] = [t["ids"][b, :cnt[b]] for b in range(self.batch)]
+        out["rec"] = d["rec"]
+        return out
+
+    def templates(self):
+        """The streams' track templates behind the latest step (ofk.h: ofk_set_track_template): dict(tmpl, A, ncc, flag, tstate, ids: per
+        stream the rows of the tracks that step returned, in their order, ids joined from the track table; tmpl as
+        [rows, win + 2, win + 2]; rec [batch, 32]: rec[:, 0:4] the step map M, rec[:, 4:6] t, rec[:, 6] the fit flag, rec[:, 10:20] the
+        counts and the largest move)."""
+        d = self.ctx.track_template_download(self.batch)
+        t = self.ctx.track_table_download(self.batch)
+        cnt = t["stats"][:, 0]
+        e = self.ctx.get_track_template().win + 2
+        out = {k: [d[k][b, :cnt[b]] for b in range(self.batch)] for k in ("A", "ncc", "flag", "tstate")}
+        out["tmpl"] = [d["tmpl"][b, :cnt[b], :e * e].reshape(-1, e, e) for b in range(self.batch)]
         out["ids"] = [t["ids"][b, :cnt[b]] for b in range(self.batch)]
         out["rec"] = d["rec"]
         return out

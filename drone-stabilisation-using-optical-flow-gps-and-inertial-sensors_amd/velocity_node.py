@@ -126,6 +126,50 @@ def track_depth_step(x, u, omega, v, state=None, status=None, solved=True, new_c
     return {k: a[0, :kept + born].copy() for k, a in out.items()}, rec[0]
 
 
+def track_template_step(prev, next, prev_pts, next_pts, state=None, status=None, age=None, L=None, new_count=None, max_total=None, **settings):
+    """One step of a stream's track templates on two gray frames (ofk.h: ofk_track_affine_fit, ofk_track_template_step): the step map
+    fitted to the tracked rows (unless L [4] is given), then capture, score, re-anchoring, verdict and compaction.  prev, next [h,w]
+    u8; prev_pts, next_pts [n,2]: LK's; state: the dict(tmpl, A, ncc, flag, tstate) of the previous call (None: no template yet);
+    status [n] (None: all tracked); age [n] (None: 1 where the state has rows, else 0); new_count: corners re-detected behind the
+    kept rows; settings: ofk.track_template_setting's keywords.
+    Returns (next_pts [n,2], status [n], state, rec [32]): the rows as tracked with the corrected positions and the verdicts' status,
+    the state of the kept rows in order with the appended ones behind them."""
+    pp = np.asarray(prev_pts, np.float32).reshape(-1, 2); nn = np.asarray(next_pts, np.float32).reshape(-1, 2)
+    n = len(pp)
+    if n < 1:
+        raise ValueError("track_template_step: no points")
+    tp = ofk.track_template_setting(**settings)
+    ts = ofk.tpl_stride(tp.win)
+    st = np.ones(n, np.uint8) if status is None else (np.asarray(status).reshape(n) != 0).astype(np.uint8)
+    born = 0 if new_count is None else max(int(new_count), 0)
+    S = n + born                                                 # room for the appended rows
+    state = state or {}
+    have = len(state["tstate"]) if "tstate" in state else 0
+
+    def rows(a, dtype, *tail):                                   # [1, S, ...]: the n rows, zeros behind them
+        out = np.zeros((1, S) + tail, dtype)
+        if a is not None:
+            a = np.asarray(a, dtype).reshape((-1,) + tail)[:n]
+            out[0, :len(a)] = a
+        return out
+    ag = rows((np.arange(n) < have).astype(np.int32) if age is None else age, np.int32)
+    ctx = ofk.default_context()
+    g0 = np.ascontiguousarray(prev, np.uint8)[None]; g1 = np.ascontiguousarray(next, np.uint8)[None]
+    rec1 = np.zeros(ofk.TPL_DOUBLES)
+    if L is None:
+        r, Lf = ctx.track_affine_fit(rows(pp, np.float32, 2), rows(nn, np.float32, 2), rows(st, np.uint8), [n], g0.shape[1], g0.shape[2], tp)
+        rec1, L = r[0], Lf[0]
+    nx, so, out, rec = ctx.track_template_step(
+        g0, g1, rows(pp, np.float32, 2), rows(nn, np.float32, 2), rows(st, np.uint8), ag, [n], np.asarray(L, np.float32).reshape(1, 4),
+        dict(tmpl=rows(state.get("tmpl"), np.uint8, ts), A=rows(state.get("A"), np.float32, 4), ncc=rows(state.get("ncc"), np.float32),
+             flag=rows(state.get("flag"), np.uint8), tstate=rows(state.get("tstate"), np.uint8)),
+        new_counts=None if new_count is None else [born], max_total=S if max_total is None else min(int(max_total), S), track_template=tp)
+    kept = int((so[0, :n] != 0).sum())
+    total = kept + (0 if new_count is None else max(0, min(born, (S if max_total is None else min(int(max_total), S)) - kept)))
+    rec = rec[0].copy(); rec[:10] = rec1[:10]
+    return nx[0, :n].copy(), so[0, :n].copy(), {k: a[0, :total].copy() for k, a in out.items()}, rec
+
+
 def solve_lgs_joint(x, u, d, n, omega, sigma_flow, sigma_omega=None):
     """solve_lgs with the gyro refined from the flow (ofk.h: ofk_velocity_solve_joint): velocity and rotation from one 6-unknown
     least squares.  sigma_flow: the flow noise in the units of x and u; sigma_omega: None (every axis free), a scalar or three
@@ -205,6 +249,7 @@ class optical_fusion:
     _finite_motion = {}                                          # PipelineConfig's finite_motion field; empty: the solve takes the flow as the instantaneous field
     _track_table = {}                                            # PipelineConfig's track_table field; empty: the tracks are anonymous points
     _track_depth = {}                                            # PipelineConfig's track_depth field; empty: no depth per track
+    _track_template = {}                                         # PipelineConfig's track_template field; empty: no template per track
     _rolling_shutter = {}                                        # PipelineConfig's rolling_shutter field; empty: every row is taken as exposed at the time stamp
     feature_params = dict(qualityLevel=0.7, minDistance=10, blockSize=12)
     lk_params = dict(winSize=(15, 15), maxLevel=3, criteria=(cv2.TERM_CRITERIA_EPS | cv2.TERM_CRITERIA_COUNT, 20, 0.03))
@@ -361,7 +406,8 @@ class optical_fusion:
                                  win=int(self.lk_params["winSize"][0]), max_level=int(self.lk_params["maxLevel"]), max_count=cnt, eps=eps,
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
                                  **self._cov, **self._joint, **self._plane, **self._epipolar, **self._zones, **self._camera, **self._rolling_shutter,
-                                 **self._finite_motion, **self._gyro_bias, **self._lk_light, **self._track_table, **self._track_depth)
+                                 **self._finite_motion, **self._gyro_bias, **self._lk_light, **self._track_table, **self._track_depth,
+                                 **self._track_template)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -408,6 +454,9 @@ class optical_fusion:
         if self._track_depth:
             dp = fs.depths()
             self.last_track_depth = {k: dp[k][0] for k in ("rho", "var", "nobs", "ids", "rec")}
+        if self._track_template:
+            tp = fs.templates()
+            self.last_track_template = {k: tp[k][0] for k in ("A", "ncc", "flag", "tstate", "ids", "rec")}
         if self._epipolar and r[15]:
             rec, pts = fs.structure()
             self.last_epipolar = (rec[0], pts[0])
@@ -471,7 +520,7 @@ class optical_fusion:
 
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
                  rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None, gyro_bias=None, lk_light=None,
-                 track_table=None, track_depth=None):
+                 track_table=None, track_depth=None, track_template=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -522,7 +571,11 @@ class optical_fusion:
         track_depth: None (no depth per track), True, an ofk.TrackDepth or a dict of ofk.track_depth_setting's keywords, e.g.
         dict(q=1e-6): the stream then filters an inverse depth per track on the device and solves a velocity from the depths of the
         earlier frames (ofk.h: ofk_set_track_depth); it switches the track table on when track_table is None.
-        self.last_track_depth is dict(rho, var, nobs, ids, rec), rec[0:3] that velocity and rec[3] its flag."""
+        self.last_track_depth is dict(rho, var, nobs, ids, rec), rec[0:3] that velocity and rec[3] its flag.
+        track_template: None (no template per track), True, an ofk.TrackTemplate or a dict of ofk.track_template_setting's keywords,
+        e.g. dict(ncc_min=0.9): the stream then keeps the patch every track was born with, drops the tracks that no longer match it
+        and pulls the others back onto it (ofk.h: ofk_set_track_template); it switches the track table on when track_table is None.
+        self.last_track_template is dict(A, ncc, flag, tstate, ids, rec)."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -619,6 +672,15 @@ class optical_fusion:
         else:
             self._track_depth = {}
         self.last_track_depth = None
+        if track_template is not None and track_template is not False:
+            tp = track_template if track_template is True or isinstance(track_template, ofk.TrackTemplate) else ofk.track_template_setting(**dict(track_template))
+            self._track_template = dict(track_template=tp)
+            PipelineConfig(**self._track_template).track_template_setting()    # invalid fields fail here, not at the first frame
+            if not self._track_table:
+                self._track_table = dict(track_table=True)           # the templates are kept per row of the table
+        else:
+            self._track_template = {}
+        self.last_track_template = None
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

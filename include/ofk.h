@@ -359,6 +359,98 @@ int ofk_track_depth_step(ofk_ctx *ctx, const ofk_track_depth *t, const double *x
                          const double *omega, const double *v, const int *solved, double *rho, double *var, int *nobs, const int *new_counts,
                          int max_total, int batch, int stride, double *rec);
 
+/* Track templates: the patch a track was born with, kept per row of the track table, the window of every later frame compared with
+ * it through the accumulated image deformation, and the position pulled back onto it (the monitoring half of Shi and Tomasi's "Good
+ * Features to Track").  LK tracks frame to frame, every step starts from the previous step's result, so its sub-pixel errors add up,
+ * and the forward-backward gate and err_max see two neighbouring frames only.  Off by default; with it off every stream step
+ * allocates, launches and returns what it always did.  Streams only: ofk_pairs_run ignores the setting.  It needs
+ * ofk_set_track_table on.  Everything lives in raw pixels of pyramid level 0, like the table's flow_xy; the camera, rolling-shutter
+ * and finite-motion rewrites run behind it and read the status and the next points it leaves, as do the solves, the zones' copy of
+ * the status, the depths and the table's flow_xy.
+ * State per track row, in the table's row order, in arrays of their own: tmpl ((win+2)^2 u8, row-major, the window plus a rim of one
+ * pixel for the gradients; `tmpl_stride` = (win+2)^2 rounded up to a multiple of 4 bytes apart), A (4 f32, row-major: template offsets
+ * to image offsets), ncc (f32, the latest score), flag (u8, the latest verdict, | OFK_TPL_CAPTURED on the step that captured the
+ * row), tstate (u8: 0 no template, 1 has one).  Per stream a record of OFK_TPL_DOUBLES.
+ * The sampler S(img, p, A, o), o = (ox, oy) integers: sx = (a00 ox + a01 oy) + p.x, sy = (a10 ox + a11 oy) + p.y in f32;
+ * ix = floorf(sx), qx = rint((sx - ix) 32) with ties to even, likewise y; outside if sx or sy is not finite, ix < 0, iy < 0,
+ * ix + 1 > w - 1 or iy + 1 > h - 1; otherwise the integer I00 (32-qx)(32-qy) + I01 qx (32-qy) + I10 (32-qx) qy + I11 qx qy, the value
+ * at scale 1024.  Every sum below is over such integers and exact in int64, so it does not depend on the order of the additions.
+ *   1. Step map (k_track_affine, one workgroup per stream, behind LK and the track gates).  n = min(max(counts, 0), stride); the
+ *      rows i < n with status != 0; x = prev - c, y = next - c in f64, c = (w/2, h/2).  Minimise sum |M x + t - y|^2: the sums of
+ *      z z^T, z y_0 and z y_1 with z = (x_0, x_1, 1) in the solve's order (i = tid + 256 k, the shuffle butterfly,
+ *      (s0 + s1) + (s2 + s3)), k_lstsq.inc's Jacobi once and its rank rule with the row count for `rows`, both right-hand sides from the
+ *      one decomposition.  fit_gate > 0: a second fit over the rows with |M x + t - y|^2 <= fit_gate^2 under the first; it replaces
+ *      the first when at least fit_min rows remain and it has rank 3 and finite sums.  L = I with fit flag 1 when fewer than
+ *      fit_min rows are present, the rank is below 3 or a sum is not finite.  L is M rounded to f32 once; the record carries f64.
+ *   2. Capture (k_track_template, one wave per row, for every row i < n): a row with age == 0 or tstate == 0 takes
+ *      (S(prev level 0, prev point, I, o) + 512) >> 10 for o in -h-1..h+1, h = (win-1)/2, as its template, A = I, tstate = 1.  If a
+ *      sample is outside the row has no template: tstate = 0, and with status != 0 its flag is NO_TEMPLATE, the row kept as LK left it.
+ *   3. Score, rows with status != 0 and a template.  A' = L A, each entry L_r0 a_0c + L_r1 a_1c in f32.  T(o) the template's inner
+ *      window, g(o) = (T(o + e_x) - T(o - e_x), T(o + e_y) - T(o - e_y)), J(o) = S(next level 0, p, A', o), D = J - 1024 T, N = win^2,
+ *      vT = N sum T^2 - (sum T)^2, vJ = N sum J^2 - (sum J)^2, cTJ = N sum T J - sum T sum J, rho = (double)cTJ /
+ *      sqrt((double)vT (double)vJ), stored as f32.  At p = LK's next point: OUTSIDE if a sample is outside (the row is kept, or with
+ *      outside = OFK_TPL_DROP status = 0, without a score); else FLAT if vT <= 0 or vJ <= 0 (kept without a verdict).
+ *   4. Re-anchor, at most anchor_iters times from p = LK's next point.  Gc = N sum g g^T - (sum g)(sum g)^T, bc = N sum g D -
+ *      (sum g)(sum D) (a bias between the frames drops out); det = Gc00 Gc11 - Gc01 Gc01 in f64, det <= 0: no anchor.
+ *      delta = (Gc11 bc.x - Gc01 bc.y, Gc00 bc.y - Gc01 bc.x) / det / 512; s = A' delta in f64; q = (float)((double)p - s).  The anchor
+ *      is abandoned (p = LK's point again, the score the one taken there, flag ABANDONED) if s is not finite, if |q - p_LK| exceeds
+ *      (float)anchor_max in x or y (f32), or if a sample at q is outside.  Otherwise p = q, and the walk stops when s.s < 1e-4.
+ *   5. Verdict at the final p: FLAT (next stays LK's) if vJ <= 0 there; rho < ncc_min (f64): status = 0, next stays LK's, FAIL;
+ *      otherwise next = p, PASS (ABANDONED where rule 4 says so).  Rows with status == 0 on entry are not touched (NOT_TRACKED).
+ *   6. Compaction (k_track_template_update, one workgroup per stream, directly in front of k_track_table_update on the steps that
+ *      launch it, with its keep rule status != 0): the kept rows carry tmpl, A', ncc, flag and tstate up in order; a kept row with a
+ *      template whose det A' (a00 a11 - a01 a10 in f32) exceeds (float)scale_max^2 or falls below (float)(1 / scale_max^2), or is no
+ *      number, gets tstate = 0 (scale_max = 0: never) and is captured afresh by the next step at its position then; the
+ *      extra = max(0, min(new count, max_total - kept, stride - kept)) appended rows get A = I, ncc = 0, flag 0, tstate = 0.  The
+ *      templates move from one buffer into a second one, which the host swaps.  The counts of the record come from the flags by
+ *      ballot and popcount.
+ * A held step runs rules 1-5 and not rule 6: A, the scores, the flags, the counts and the templates of rows with tstate = 1 stay; rows
+ * with tstate = 0 may be captured, as the next step would with the same bits.
+ * Record: 0-3 M, 4-5 t, 6 fit flag, 7 / 8 rows in the first / second fit, 9 rms residual in px of the rows of the fit that stands,
+ * 10 rows scored (PASS, FAIL, ABANDONED), 11 rows dropped (FAIL, and OUTSIDE under OFK_TPL_DROP), 12 rows moved, 13 abandoned, 14 outside, 15 flat, 16 captured, 17 without a
+ * template, 18 marked for refresh, 19 largest move in px (x or y), 20-31 0.  Slots 10-19 are written by rule 6.
+ * Streams that step with the setting on without templates of their current tracks (the setting switched on in mid-stream, or set
+ * again) start with tstate = 0 everywhere.  The buffers are allocated by the first step with the setting on, once and for the widest
+ * window, so that a later win needs no reallocation: two template buffers of 1092 bytes per row of max_batch x max_pts (about 70 MB at
+ * 64 streams of 500 rows; the default window of 15 uses 27 % of it) and 47 bytes per row for the rest.
+ * ofk_set_track_template: NULL or mode OFK_TPL_OFF switches the feature off.  OFK_E_INVALID, the setting staying as it was: a mode
+ * that is neither, win even or outside 5..31, ncc_min outside [-1, 1], anchor_iters outside 0..8, anchor_max <= 0, outside neither
+ * OFK_TPL_KEEP nor OFK_TPL_DROP, fit_min < 3, fit_gate < 0 (0: a single fit), scale_max neither 0 nor >= 1, a value that is not
+ * finite.  Defaults behind "off": 15, 0.8, 3, 2.0, keep, 6, 2.0, 1.5.
+ * OFK_E_INVALID before any launch from a stream step with the setting on: ofk_set_track_table off.
+ * ofk_track_template_download, the streams of the latest step with the setting on, the first min(stride, max_pts) rows of each (every
+ * output may be NULL): tmpl [batch][stride][tmpl_stride of the setting], A [batch][stride][4], ncc [batch][stride] f32, flag, tstate
+ * [batch][stride] u8, rec [batch][OFK_TPL_DOUBLES].
+ * ofk_track_affine_fit, rule 1 on host buffers: prev_pts, next_pts [batch][stride][2] f32, status [batch][stride], counts [batch], the
+ * frame's h and w; rec [batch][OFK_TPL_DOUBLES] out (slots 0-9, the rest 0), L [batch][4] f32 out (may be NULL).
+ * ofk_track_template_step, rules 2-6 on host buffers (it touches no resident state): prev, next [batch][h][w] gray; prev_pts
+ * [batch][stride][2]; next_pts and status in and out in place, rows as tracked; age [batch][stride] i32; counts [batch]; L
+ * [batch][4] f32; the state tmpl [batch][stride][tmpl_stride], A, ncc, flag, tstate in and out in place, compacted; new_counts
+ * [batch] (NULL: none), max_total <= stride; rec [batch][OFK_TPL_DOUBLES] out (slots 10-19, the rest 0; may be NULL). */
+#define OFK_TPL_OFF          0
+#define OFK_TPL_ON           1
+#define OFK_TPL_DOUBLES      32
+#define OFK_TPL_KEEP         0
+#define OFK_TPL_DROP         1
+#define OFK_TPL_NOT_TRACKED  0
+#define OFK_TPL_PASS         1
+#define OFK_TPL_FAIL         2
+#define OFK_TPL_ABANDONED    3
+#define OFK_TPL_OUTSIDE      4
+#define OFK_TPL_FLAT         5
+#define OFK_TPL_NO_TEMPLATE  6
+#define OFK_TPL_CAPTURED     16
+typedef struct ofk_track_template { int mode; int win; double ncc_min; int anchor_iters; double anchor_max; int outside; int fit_min; double fit_gate; double scale_max; } ofk_track_template;
+int ofk_set_track_template(ofk_ctx *ctx, const ofk_track_template *t);
+int ofk_get_track_template(const ofk_ctx *ctx, ofk_track_template *t);
+int ofk_track_template_download(ofk_ctx *ctx, uint8_t *tmpl, float *A, float *ncc, uint8_t *flag, uint8_t *tstate, int stride, double *rec);
+int ofk_track_affine_fit(ofk_ctx *ctx, const ofk_track_template *t, const float *prev_pts, const float *next_pts, const uint8_t *status,
+                         const int *counts, int batch, int stride, int h, int w, double *rec, float *L);
+int ofk_track_template_step(ofk_ctx *ctx, const ofk_track_template *t, const uint8_t *prev, const uint8_t *next, int h, int w,
+                            const float *prev_pts, float *next_pts, uint8_t *status, const int *age, const int *counts, const float *L,
+                            uint8_t *tmpl, float *A, float *ncc, uint8_t *flag, uint8_t *tstate, const int *new_counts, int max_total,
+                            int batch, int stride, double *rec);
+
 /* Camera model: the lens distortion undone on the device before the solve.  The solve stage reads a point as a sample of an ideal
  * pinhole image, x = (px - cx) * scaling (sensors[19..21]); the reference's camera is a wide-angle module whose lens moves a point by
  * tens of pixels at the border.  With ofk_set_camera on, the resident chains keep everything that lives in the image on the raw
