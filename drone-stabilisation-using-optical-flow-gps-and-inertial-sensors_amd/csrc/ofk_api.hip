@@ -162,6 +162,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->tt = ofk_track_table{OFK_TT_OFF, OFK_TT_SEED_OFF, 1.0};
     c->td = ofk_track_depth{OFK_TD_OFF, 0.2, 0.5, 3.0, 0.0, 3, 0.25, 8, 1};
     c->tpl = ofk_track_template{OFK_TPL_OFF, 15, 0.8, 3, 2.0, OFK_TPL_KEEP, 6, 2.0, 1.5};
+    c->key = ofk_keyframe{OFK_KEY_OFF, 0.2, 2.0, 8, 0.5, 0.5, 0};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -215,7 +216,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
                     c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec, c->joint_rec, c->bias_rec, c->plane_rec, c->epi_rec,
-                    c->zone_tab, c->pts_prev_u, c->ttr.ids, c->tdr.rho, c->tpr.tmpl[0]};
+                    c->zone_tab, c->pts_prev_u, c->ttr.ids, c->tdr.rho, c->tpr.tmpl[0], c->kfr.key_xy};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
@@ -923,8 +924,10 @@ static int gate_tracks(ofk_ctx *c, hipStream_t s, const View &v, const ofk_level
 // the model seeds, and LK starts at what both have written.
 // tp != NULL (a stream step with ofk_set_track_template on; the view is the whole batch, age the table's): rules 1-5 of the templates
 // directly behind the gates, on the raw points and the status everything below reads.
+// key_copy != NULL (a stream step with ofk_set_keyframe on): where the finite-motion rewrite is in place, the ideal next points in
+// front of it are kept there.
 static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv, const ofk_params *p, const double *imu_state,
-                 const ofk_tt_rows *tt = nullptr, const ofk_tp_rows *tp = nullptr, const int *age = nullptr)
+                 const ofk_tt_rows *tt = nullptr, const ofk_tp_rows *tp = nullptr, const int *age = nullptr, float *key_copy = nullptr)
 {
     const bool seeded = c->lk_seed_mode != OFK_SEED_OFF, cam = camera_on(c);
     if (seeded && cam) {
@@ -952,6 +955,7 @@ static int track(ofk_ctx *c, hipStream_t s, const View &v, const ofk_levels &lv,
     }
     if (fm_on(c)) {
         const bool id = cam || rs_on(c);
+        if (id && key_copy) OFK_HIP(c, hipMemcpyAsync(key_copy, v.pts_next_u, (size_t)v.nb * c->max_pts * 8, hipMemcpyDeviceToDevice, s));
         ofk_launch_finite_correct(s, &c->fm, id ? v.pts_prev_u : v.pts_prev, id ? v.pts_next_u : v.pts_next, v.pts_prev_u, v.pts_next_u, v.counts,
                                   c->max_pts, v.sensors, imu_state, v.nb);
     }
@@ -2888,6 +2892,154 @@ extern "C" int ofk_track_template_step(ofk_ctx *c, const ofk_track_template *set
     return OFK_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ keyframe per stream
+static int check_key(ofk_ctx *c, const ofk_keyframe *k, const char *who)
+{
+    if (k->mode != OFK_KEY_OFF && k->mode != OFK_KEY_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_KEY_OFF nor OFK_KEY_ON", who, k->mode);
+    if (k->mode == OFK_KEY_OFF) return OFK_OK;
+    if (!std::isfinite(k->sigma_flow) || !std::isfinite(k->gate) || !std::isfinite(k->min_share) || !std::isfinite(k->rot_max))
+        return ofk_fail(c, OFK_E_INVALID, "%s: sigma_flow, gate, min_share and rot_max must be finite", who);
+    if (!(k->sigma_flow > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: sigma_flow = %g must be positive", who, k->sigma_flow);
+    if (k->gate < 0.0) return ofk_fail(c, OFK_E_INVALID, "%s: gate = %g must not be negative", who, k->gate);
+    if (k->min_rows < 3) return ofk_fail(c, OFK_E_INVALID, "%s: min_rows = %d must be at least 3", who, k->min_rows);
+    if (k->min_share < 0.0 || k->min_share > 1.0) return ofk_fail(c, OFK_E_INVALID, "%s: min_share = %g outside [0, 1]", who, k->min_share);
+    if (!(k->rot_max > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: rot_max = %g must be positive", who, k->rot_max);
+    if (k->max_age < 0) return ofk_fail(c, OFK_E_INVALID, "%s: max_age = %d must not be negative", who, k->max_age);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_keyframe(ofk_ctx *c, const ofk_keyframe *k)
+{
+    return setting_set(c, &ofk_ctx::key, k && k->mode == OFK_KEY_OFF ? nullptr : k, [](ofk_keyframe &s) { s.mode = OFK_KEY_OFF; },
+                       [c](const ofk_keyframe *v) { return check_key(c, v, "ofk_set_keyframe"); });
+}
+extern "C" int ofk_get_keyframe(const ofk_ctx *c, ofk_keyframe *k) { return setting_get(c, &ofk_ctx::key, k); }
+
+static bool kf_on(const ofk_ctx *c) { return c->key.mode != OFK_KEY_OFF; }
+
+// the state's arrays over `np` rows and the state of `batch` streams carved out of base (NULL: nothing is carved); returns the bytes
+static size_t kf_carve(ofk_kf_rows &t, uint8_t *base, size_t np, size_t batch)
+{
+    size_t o = 0;
+    auto take = [&](size_t bytes) { uint8_t *p = base ? base + o : nullptr; o += up(bytes, 256); return p; };
+    t.key_xy = (float *)take(np * 8); t.member = take(np); t.st = (double *)take(batch * OFK_KEY_STATE * 8);
+    t.ist = (int *)take(batch * OFK_KEY_INTS * 4); t.rec = (double *)take(batch * OFK_KEY_DOUBLES * 8);
+    t.next_copy = (float *)take(np * 8);
+    return o;
+}
+// the resident state, allocated (and cleared) by the first step with the setting on
+static int kf_alloc(ofk_ctx *c)
+{
+    if (c->kfr.key_xy) return OFK_OK;                            // one allocation, carved into the arrays
+    ofk_kf_rows t;
+    const size_t np = (size_t)c->max_batch * c->max_pts, bytes = kf_carve(t, nullptr, np, (size_t)c->max_batch);
+    uint8_t *base = nullptr;
+    OFK_HIP(c, hipMalloc((void **)&base, bytes));
+    kf_carve(c->kfr, base, np, (size_t)c->max_batch);            // the context owns it from here on, whatever follows
+    OFK_HIP(c, hipMemsetAsync(base, 0, bytes, c->stream));
+    return OFK_OK;
+}
+
+// The steps' own refusals with the setting on (ofk.h); fu: a fused step's.
+static int kf_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const char *who)
+{
+    if (!kf_on(c)) return OFK_OK;
+    if (c->tt.mode == OFK_TT_OFF)
+        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_keyframe is on without ofk_set_track_table: the keyframe is kept per row of the table", who);
+    if (variant == OFK_SOLVE_OFMODULE || (fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY)))
+        return refuse_not_sensor_model(c, who, NO_OFMODULE | NO_ROTATIONAL | NO_LEGACY, "keyframe", "ofk_set_keyframe");
+    return OFK_OK;
+}
+
+// a keyframe state for the current tracks of the first B streams: begun afresh unless it is live already
+static int kf_begin(ofk_ctx *c, int B)
+{
+    TRY(kf_alloc(c));
+    if (c->kf_live != B) ofk_launch_keyframe_begin(c->stream, c->kfr, c->counts, c->max_pts, B);
+    c->kf_batch = c->kf_live = B;
+    return OFK_OK;
+}
+
+extern "C" int ofk_keyframe_download(ofk_ctx *c, float *key_xy, uint8_t *member, int stride, double *R_acc, double *rec)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->kf_batch < 1 || !c->kfr.key_xy) return ofk_fail(c, OFK_E_INVALID, "ofk_keyframe_download: no stream has stepped with ofk_set_keyframe on yet");
+    if ((key_xy || member) && stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_keyframe_download: stride %d", stride);
+    TRY(enter(c));
+    const int B = c->kf_batch;
+    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    const ofk_kf_rows &t = c->kfr;
+    if (key_xy) OFK_HIP(c, hipMemcpy2DAsync(key_xy, (size_t)stride * 8, t.key_xy, mp * 8, n * 8, B, hipMemcpyDeviceToHost, c->stream));
+    if (member) OFK_HIP(c, hipMemcpy2DAsync(member, (size_t)stride, t.member, mp, n, B, hipMemcpyDeviceToHost, c->stream));
+    if (R_acc) OFK_HIP(c, hipMemcpy2DAsync(R_acc, 72, t.st, OFK_KEY_STATE * 8, 72, B, hipMemcpyDeviceToHost, c->stream));
+    if (rec) OFK_HIP(c, hipMemcpyAsync(rec, t.rec, (size_t)B * OFK_KEY_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+extern "C" int ofk_keyframe_reset(ofk_ctx *c, int b, const double *anchor)
+{
+    const char *who = "ofk_keyframe_reset";
+    if (!c) return OFK_E_INVALID;
+    if (c->stream_batch < 1 || b < 0 || b >= c->stream_batch) return ofk_fail(c, OFK_E_INVALID, "%s: stream %d is none of the %d active streams", who, b, c->stream_batch);
+    const double zero[3] = {0.0, 0.0, 0.0}, *p = anchor ? anchor : zero;
+    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return ofk_fail(c, OFK_E_INVALID, "%s: the position must be finite", who);
+    TRY(enter(c));
+    TRY(kf_begin(c, c->stream_batch));
+    ofk_launch_keyframe_reset(c->stream, c->kfr, b, c->max_pts, p);
+    TRY(check_launch(c, who));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+// rules 1-5 on host buffers: device scratch only
+extern "C" int ofk_keyframe_step(ofk_ctx *c, const ofk_keyframe *set, const float *next_pts, const uint8_t *status, const int *counts,
+                                 const double *sensors, const double *v_uav, const int *solved, const int *step, float *key_xy, uint8_t *member,
+                                 double *state, int *istate, const int *new_counts, int max_total, int batch, int stride, double *rec)
+{
+    const char *who = "ofk_keyframe_step";
+    if (!c) return OFK_E_INVALID;
+    if (!set || !next_pts || !status || !counts || !sensors || !v_uav || !solved || !step || !key_xy || !member || !state || !istate)
+        return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
+    if (batch < 1 || stride < 1) return ofk_fail(c, OFK_E_INVALID, "%s: batch %d / stride %d", who, batch, stride);
+    if (max_total < 0 || max_total > stride) return ofk_fail(c, OFK_E_INVALID, "%s: max_total %d outside 0..%d", who, max_total, stride);
+    if (set->mode == OFK_KEY_OFF) return ofk_fail(c, OFK_E_INVALID, "%s: the setting is off", who);
+    TRY(check_key(c, set, who));
+    TRY(check_counts(c, who, counts, batch, stride));
+    const size_t np = (size_t)batch * stride, B = (size_t)batch;
+    double *h_rec = (double *)calloc(B * OFK_RECORD_DOUBLES, 8);   // the step's records as the kernel reads them: v_uav, solved
+    if (!h_rec) return ofk_fail(c, OFK_E_INVALID, "%s: out of host memory", who);
+    for (size_t b = 0; b < B; ++b) {
+        for (int k = 0; k < 3; ++k) h_rec[b * OFK_RECORD_DOUBLES + 8 + k] = v_uav[3 * b + k];
+        h_rec[b * OFK_RECORD_DOUBLES + 15] = solved[b] ? 1.0 : 0.0;
+    }
+    Bump bp;
+    int rc = est_begin(c, np * 18 + B * ((OFK_RECORD_DOUBLES + OFK_KEY_DOUBLES + OFK_KEY_STATE + OFK_SENSOR_DOUBLES) * 8 + OFK_KEY_INTS * 4 + 12) + 16 * 256, bp);
+    if (rc != OFK_OK) { free(h_rec); return rc; }
+    ofk_kf_rows t = {};
+    t.key_xy = (float *)bp.put(key_xy, np * 8); t.member = (uint8_t *)bp.put(member, np); t.st = bp.put(state, B * OFK_KEY_STATE * 8);
+    t.ist = (int *)bp.put(istate, B * OFK_KEY_INTS * 4); t.rec = bp.take(B * OFK_KEY_DOUBLES * 8);
+    ofk_kf_in in = {};
+    in.next_pts = (const float *)bp.put(next_pts, np * 8); in.status = (const uint8_t *)bp.put(status, np);
+    in.counts = (const int *)bp.put(counts, B * 4); in.stride = stride;
+    in.new_counts = (const int *)bp.put(new_counts, B * 4); in.max_total = max_total;
+    in.sensors = bp.put(sensors, B * OFK_SENSOR_DOUBLES * 8); in.imu = nullptr;
+    in.v = bp.put(h_rec, B * OFK_RECORD_DOUBLES * 8); in.plain = 0;
+    in.step = (const int *)bp.put(step, B * 4); in.step_stride = 1;
+    hipError_t e = bp.rc == OFK_OK ? hipStreamSynchronize(c->stream) : hipErrorUnknown;   // h_rec has been read
+    free(h_rec);
+    if (e != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    ofk_launch_keyframe_step(c->stream, t, in, set, batch);
+    TRY(check_launch(c, "k_keyframe_step"));
+    OFK_HIP(c, hipMemcpyAsync(key_xy, t.key_xy, np * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipMemcpyAsync(member, t.member, np, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipMemcpyAsync(state, t.st, B * OFK_KEY_STATE * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipMemcpyAsync(istate, t.ist, B * OFK_KEY_INTS * 4, hipMemcpyDeviceToHost, c->stream));
+    if (rec) OFK_HIP(c, hipMemcpyAsync(rec, t.rec, B * OFK_KEY_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ video streams
 static int stream_alloc(ofk_ctx *c)
 {
@@ -2949,6 +3101,7 @@ static int stream_begin_impl(ofk_ctx *c, const uint8_t *first_bgr, int batch, in
     c->tt_batch = c->tt_live = 0;                                // ... and with a new track table, if the setting is on
     c->td_batch = c->td_live = 0;                                // ... and without depths: the first step with that setting on starts them
     c->tp_batch = c->tp_live = 0;                                // ... and without templates
+    c->kf_batch = c->kf_live = 0;                                // ... and without a keyframe
     if (tt_on(c)) {
         TRY(tt_alloc(c));
         ofk_launch_track_table_begin(c->stream, c->ttr, c->pts_prev, c->counts, c->max_pts, batch);
@@ -3112,6 +3265,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     TRY(bias_check_step(c, B, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     TRY(td_check_step(c, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     TRY(tp_check_step(c, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
+    TRY(kf_check_step(c, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     const int defer = second_on(c) && fu && fu->filter ? 1 : 0;   // the second-stage kernel corrects
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
@@ -3140,6 +3294,9 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     const bool templ = tp_on(c);                                 // tp_check_step: then the table is on
     if (templ) TRY(tp_begin(c, B));
     else c->tp_live = 0;                                         // the tracks move on without their templates
+    const bool keyf = kf_on(c);                                  // kf_check_step: then the table is on
+    if (keyf) TRY(kf_begin(c, B));
+    else c->kf_live = 0;                                         // the tracks move on without their keyframe
     const bool flow_seed = table && c->tt.seed == OFK_TT_SEED_FLOW;
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
@@ -3155,12 +3312,13 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         ofk_launch_replace_tracks(c->stream, c->limit, c->pts_new, c->new_counts, c->max_pts, c->pts_prev, c->counts, B);
         if (table) ofk_launch_track_table_replace(c->stream, c->ttr, c->limit, c->pts_new, c->new_counts, c->max_pts, B);
         if (depth) ofk_launch_track_depth_replace(c->stream, c->tdr, c->limit, c->new_counts, c->max_pts, B);
+        if (keyf) ofk_launch_keyframe_replace(c->stream, c->kfr, c->limit, c->new_counts, c->max_pts, B);
     }
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)
     const View v = view_of(c, 0, B, 0);                          // the solve stage reads v.solve_*; the tracks, the zones and the re-detection stay in the image
     TRY(track(c, c->stream, v, lv, p, fu && fu->use_imu ? c->imu_state : nullptr, flow_seed ? &c->ttr : nullptr, templ ? &c->tpr : nullptr,
-              c->ttr.age));
+              c->ttr.age, keyf ? c->kfr.next_copy : nullptr));
     if (zones_on)                                                // the solve stage turns the status into its keep flags: rule 1 needs both
         OFK_HIP(c, hipMemcpyAsync(c->zone_status, c->status, (size_t)B * c->max_pts, hipMemcpyDeviceToDevice, c->stream));
     if (fu) {
@@ -3205,6 +3363,15 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     }
     // tracks := new[status == 1] ++ re-detected (node:134,166); the new frame becomes the previous one (node:175)
     if (!hold) {
+        if (keyf) {                                              // in front of the depths', the templates' and the table's update
+            ofk_kf_in in = {};                                   // the ideal next points in front of the finite-motion rewrite
+            in.next_pts = !fm_on(c) ? v.solve_next : camera_on(c) || rs_on(c) ? c->kfr.next_copy : v.pts_next;
+            in.status = c->status; in.counts = c->counts; in.stride = c->max_pts;
+            in.new_counts = any ? c->new_counts : nullptr; in.max_total = p->max_corners; in.sensors = c->sensors;
+            in.imu = fu && fu->use_imu ? c->imu_state : nullptr; in.v = c->records; in.plain = fu ? 0 : 1;
+            in.step = c->ttr.head; in.step_stride = 2;
+            ofk_launch_keyframe_step(c->stream, c->kfr, in, &c->key, B);
+        }
         if (depth) {                                             // in front of the table's update, on what k_update_tracks is about to read
             const bool imu = fu && fu->use_imu;
             ofk_td_in in = {};

@@ -43,6 +43,19 @@ struct ofk_tp_rows {
     float *L; double *rec;                                       // [B][4], [B][OFK_TPL_DOUBLES]
 };
 
+// the keyframe (ofk.h: ofk_set_keyframe): the state's arrays, rows `stride` apart per stream in the table's row order, the per-stream
+// state [B][OFK_KEY_STATE] / [B][OFK_KEY_INTS] and the records [B][OFK_KEY_DOUBLES]; next_copy: the ideal next points in front of an
+// in-place finite-motion rewrite; what one step reads
+struct ofk_kf_rows { float *key_xy; uint8_t *member; double *st; int *ist; double *rec; float *next_copy; };
+struct ofk_kf_in {
+    const float *next_pts;                                       // the ideal next points, [B][stride][2]
+    const uint8_t *status; const int *counts; int stride;        // what k_update_tracks reads
+    const int *new_counts; int max_total;                        // NULL: no re-detection
+    const double *sensors, *imu;                                 // [B][OFK_SENSOR_DOUBLES]; the IMU state under use_imu, else NULL
+    const double *v; int plain;                                  // [B][OFK_RECORD_DOUBLES]: v_uav in 8-10, solved in 15 (plain: rank 3 in slot 4)
+    const int *step; int step_stride;                            // the table's step per stream, ints between streams
+};
+
 struct ofk_comm;
 struct ofk_ctx {
     int device;
@@ -148,6 +161,9 @@ struct ofk_ctx {
     ofk_track_template tpl;                  // ofk_set_track_template: mode OFK_TPL_OFF unless set
     ofk_tp_rows tpr;                         // the templates' device rows, [B][max_pts] each, and records; one lazy allocation (tpr.tmpl[0] owns it)
     int tp_batch, tp_live;                   // streams of the latest step with the templates on (ofk_track_template_download), 0 = none; streams whose rows match their current tracks
+    ofk_keyframe key;                        // ofk_set_keyframe: mode OFK_KEY_OFF unless set
+    ofk_kf_rows kfr;                         // the keyframe's device rows and per-stream state; one lazy allocation (kfr.key_xy owns it)
+    int kf_batch, kf_live;                   // streams of the latest step with the keyframe on (ofk_keyframe_download), 0 = none; streams whose rows match their current tracks
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
 };
@@ -277,6 +293,11 @@ void ofk_launch_track_seed(hipStream_t s, const float *pts, const int *counts, i
 void ofk_launch_track_depth_begin(hipStream_t s, const ofk_td_rows &t, const int *counts, int stride, int batch);
 void ofk_launch_track_depth_replace(hipStream_t s, const ofk_td_rows &t, const int *limit, const int *new_counts, int stride, int batch);
 void ofk_launch_track_depth_step(hipStream_t s, const ofk_td_rows &t, const ofk_td_in &in, const ofk_track_depth *d, int batch);
+// the keyframe (ofk.h: ofk_set_keyframe; k_keyframe.inc): beside the table's begin and replace, rules 1-5 in front of the depths' step
+void ofk_launch_keyframe_begin(hipStream_t s, const ofk_kf_rows &t, const int *counts, int stride, int batch);
+void ofk_launch_keyframe_replace(hipStream_t s, const ofk_kf_rows &t, const int *limit, const int *new_counts, int stride, int batch);
+void ofk_launch_keyframe_reset(hipStream_t s, const ofk_kf_rows &t, int b, int stride, const double *p);
+void ofk_launch_keyframe_step(hipStream_t s, const ofk_kf_rows &t, const ofk_kf_in &in, const ofk_keyframe *k, int batch);
 // the track templates (ofk.h: ofk_set_track_template; k_track_template.inc): rule 1, rules 2-5 behind the gates, rule 6 in front of the table's update
 void ofk_launch_track_affine(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts, int stride,
                              int h, int w, const ofk_track_template *d, float *L, double *rec, int batch);

@@ -42,6 +42,7 @@ SYMBOLS = (
     "ofk_set_finite_motion", "ofk_get_finite_motion", "ofk_finite_correct_points", "ofk_finite_download",
     "ofk_set_track_table", "ofk_get_track_table", "ofk_track_table_download", "ofk_track_table_step", "ofk_track_seed_points",
     "ofk_set_track_depth", "ofk_get_track_depth", "ofk_track_depth_download", "ofk_track_depth_reset", "ofk_track_depth_step",
+    "ofk_set_keyframe", "ofk_get_keyframe", "ofk_keyframe_download", "ofk_keyframe_reset", "ofk_keyframe_step",
     "ofk_set_track_template", "ofk_get_track_template", "ofk_track_template_download", "ofk_track_affine_fit", "ofk_track_template_step",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
@@ -109,6 +110,11 @@ TT_SEEDS = {"off": TT_SEED_OFF, "flow": TT_SEED_FLOW}
 TT_STATS = 8                                             # count, kept, lost, born, oldest age, step, next_id, rows seeded from their flow
 TD_OFF, TD_ON = 0, 1                                     # ofk_set_track_depth
 TD_DOUBLES = 32                                          # v_map, flag, mature, updated, initialised, 3 skip counts, C_map, v, solved, reset
+KEY_OFF, KEY_ON = 0, 1                                   # ofk_set_keyframe
+KEY_DOUBLES, KEY_STATE, KEY_INTS = 32, 16, 4             # the record; R_acc, anchor, pos; key_step, members_at_key, keyframes, dead-reckoned steps
+KEY_MIN_DEPTH = 0.1
+KEY_SOLVED, KEY_UNSOLVED, KEY_NONE = 0, 1, 2             # the record's flag
+KEY_RE_FLAG, KEY_RE_ROWS, KEY_RE_SHARE, KEY_RE_ANGLE, KEY_RE_AGE = 1, 2, 3, 4, 5   # the record's re-key reason
 TPL_OFF, TPL_ON = 0, 1                                   # ofk_set_track_template
 TPL_DOUBLES = 32                                         # M, t, fit flag, rows of the two fits, rms, nine counts, largest move
 TPL_KEEP, TPL_DROP = 0, 1
@@ -480,6 +486,29 @@ def track_depth_setting(mode=True, sigma_flow=0.2, b_min=0.5, gate=3.0, q=0.0, m
     return t
 
 
+class Keyframe(C.Structure):
+    """ofk_keyframe (include/ofk.h): the displacement of a stream against a frame that is held fixed."""
+    _fields_ = [("mode", C.c_int), ("sigma_flow", C.c_double), ("gate", C.c_double), ("min_rows", C.c_int), ("min_share", C.c_double),
+                ("rot_max", C.c_double), ("max_age", C.c_int)]
+
+
+def keyframe_setting(mode=True, sigma_flow=0.2, gate=2.0, min_rows=8, min_share=0.5, rot_max=0.5, max_age=0):
+    """A Keyframe structure from names: mode True / False (or KEY_*); sigma_flow and gate in pixels (gate 0: a single solve); the key
+    solve needs min_rows (>= 3) rows; the keyframe is replaced when fewer than min_rows or fewer than min_share of its members are
+    alive, when the accumulated rotation exceeds rot_max (rad) or when it is older than max_age steps (0: no limit)."""
+    mode = int(mode)
+    if mode not in (KEY_OFF, KEY_ON):
+        raise ValueError(f"keyframe mode {mode} is none of KEY_OFF, KEY_ON")
+    k = Keyframe(mode, float(sigma_flow), float(gate), int(min_rows), float(min_share), float(rot_max), int(max_age))
+    if mode != KEY_OFF:
+        if not all(np.isfinite(x) for x in (k.sigma_flow, k.gate, k.min_share, k.rot_max)):
+            raise ValueError("keyframe sigma_flow, gate, min_share and rot_max must be finite")
+        if not (k.sigma_flow > 0 and k.gate >= 0 and k.min_rows >= 3 and 0 <= k.min_share <= 1 and k.rot_max > 0 and k.max_age >= 0):
+            raise ValueError(f"keyframe setting outside its range: sigma_flow {k.sigma_flow} > 0, gate {k.gate} >= 0, min_rows {k.min_rows} >= 3, "
+                             f"min_share {k.min_share} in [0, 1], rot_max {k.rot_max} > 0, max_age {k.max_age} >= 0")
+    return k
+
+
 class TrackTemplate(C.Structure):
     """ofk_track_template (include/ofk.h): the birth patch per track of a stream, the score against it and the re-anchoring."""
     _fields_ = [("mode", C.c_int), ("win", C.c_int), ("ncc_min", C.c_double), ("anchor_iters", C.c_int), ("anchor_max", C.c_double),
@@ -527,7 +556,7 @@ class Fusion(C.Structure):
 # the struct settings: ofk_set_<name> / ofk_get_<name> take the context and a pointer to the struct
 SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("gyro_bias", GyroBias), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate), ("lk_light", LkLight),
             ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion),
-            ("track_table", TrackTable), ("track_depth", TrackDepth), ("track_template", TrackTemplate))
+            ("track_table", TrackTable), ("track_depth", TrackDepth), ("track_template", TrackTemplate), ("keyframe", Keyframe))
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -625,6 +654,9 @@ def load_library():
         L.ofk_track_depth_download.argtypes = [vp, vp, vp, vp, i, vp]
         L.ofk_track_depth_reset.argtypes = [vp, i, vp, vp, vp, i]
         L.ofk_track_depth_step.argtypes = [vp, C.POINTER(TrackDepth), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
+        L.ofk_keyframe_download.argtypes = [vp, vp, vp, i, vp, vp]
+        L.ofk_keyframe_reset.argtypes = [vp, i, vp]
+        L.ofk_keyframe_step.argtypes = [vp, C.POINTER(Keyframe), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
         L.ofk_track_template_download.argtypes = [vp, vp, vp, vp, vp, vp, i, vp]
         L.ofk_track_affine_fit.argtypes = [vp, C.POINTER(TrackTemplate), vp, vp, vp, vp, i, i, i, i, vp, vp]
         L.ofk_track_template_step.argtypes = [vp, C.POINTER(TrackTemplate), vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
@@ -1206,6 +1238,56 @@ class Context:
                                                      _p(tm), _p(A), _p(ncc), _p(fl), _p(tst), _p(nc), S if max_total is None else int(max_total),
                                                      B, S, _p(rec)))
         return nn, st, dict(tmpl=tm, A=A, ncc=ncc, flag=fl, tstate=tst), rec
+
+    def set_keyframe(self, keyframe=None, **settings):
+        """ofk_set_keyframe: a Keyframe (or keyframe_setting's keywords); None or mode False switches it off.  Every later stream step
+        solves the stream's displacement against a keyframe of its track table (which must be on) and reports a position that does
+        not drift with the flow.  pairs_run ignores the setting."""
+        self._set_struct(self._L.ofk_set_keyframe, keyframe, settings, keyframe_setting, lock=True)
+
+    def get_keyframe(self):
+        return self._get_struct(self._L.ofk_get_keyframe, Keyframe)
+
+    def keyframe_download(self, batch=None, stride=None):
+        """ofk_keyframe_download -> dict(key_xy [batch,stride,2] f32, member [batch,stride] u8, R_acc [batch,3,3], rec [batch,32]) of the
+        streams of the latest step with the setting on, rows in the order of the tracks that step returned.  rec: T 0-2, flag 3, rows
+        of the first / the gated solve 4 / 5, rms px 6, members_at_key 7, key_step 8, re-key reason 9, D 10-12, pos 13-15, anchor
+        16-18, angle 19, C_T's upper triangle 20-25, keyframes 26, dead-reckoned steps 27, live 28, gated 29, the reasons as bits 30."""
+        S = self.max_pts if stride is None else int(stride)
+        if S < 1:
+            raise ValueError(f"keyframe_download: stride {S}")
+        kx, mem, R, rec = self._rows("keyframe_download", self.max_batch if batch is None else int(batch),
+                                     lambda *p: self._L.ofk_keyframe_download(self._h, p[0], p[1], S, p[2], p[3]), ((S, 2), np.float32),
+                                     ((S,), np.uint8), ((3, 3), np.float64), ((KEY_DOUBLES,), np.float64))
+        return dict(key_xy=kx, member=mem, R_acc=R, rec=rec)
+
+    def keyframe_reset(self, stream, anchor=None):
+        """ofk_keyframe_reset: active stream `stream` starts over at the position `anchor` (None: zero) and keys at its next step."""
+        a = None if anchor is None else _arr(anchor, np.float64, (3,))
+        with self._lock:
+            self._ck(self._L.ofk_keyframe_reset(self._h, int(stream), _p(a)))
+
+    def keyframe_step(self, next_pts, status, counts, sensors, v_uav, solved, step, state, new_counts=None, max_total=None, keyframe=None,
+                      **settings):
+        """ofk_keyframe_step, the stage entry: rules 1-5 on host arrays.  next_pts [B,S,2] f32 ideal next points; status [B,S], counts
+        [B]; sensors [B,28]; v_uav [B,3], solved [B] of the step's record; step [B] the table's step; state: dict(key_xy [B,S,2] f32,
+        member [B,S] u8, state [B,16] f64, istate [B,4] i32); new_counts [B] the re-detected corners (None: none); max_total (default
+        S); the setting a Keyframe or keyframe_setting's keywords.  -> (state, rec [B,32]), new arrays.  Touches no resident state."""
+        kf = keyframe if keyframe is not None else keyframe_setting(**settings)
+        nn = _arr(next_pts, np.float32)
+        if nn.ndim != 3 or nn.shape[2] != 2 or nn.shape[1] < 1:
+            raise ValueError(f"keyframe_step: next_pts {nn.shape} is not [B, S >= 1, 2]")
+        B, S = nn.shape[:2]
+        st = _arr(status, np.uint8, (B, S)); cn = _arr(counts, np.int32, (B,)); sn = _arr(sensors, np.float64, (B, SENSOR_DOUBLES))
+        vu = _arr(v_uav, np.float64, (B, 3)); so = _arr(solved, np.int32, (B,)); sp = _arr(step, np.int32, (B,))
+        kx = np.array(_arr(state["key_xy"], np.float32, (B, S, 2))); mem = np.array(_arr(state["member"], np.uint8, (B, S)))
+        sd = np.array(_arr(state["state"], np.float64, (B, KEY_STATE))); si = np.array(_arr(state["istate"], np.int32, (B, KEY_INTS)))
+        nc = _opt(new_counts, np.int32, (B,))
+        rec = np.zeros((B, KEY_DOUBLES), np.float64)
+        with self._lock:
+            self._ck(self._L.ofk_keyframe_step(self._h, C.byref(kf), _p(nn), _p(st), _p(cn), _p(sn), _p(vu), _p(so), _p(sp), _p(kx), _p(mem),
+                                               _p(sd), _p(si), _p(nc), S if max_total is None else int(max_total), B, S, _p(rec)))
+        return dict(key_xy=kx, member=mem, state=sd, istate=si), rec
 
     def zones_reset(self, batch=None):
         """ofk_zones_reset: the zone tables of the first `batch` streams (all by default) are cleared."""

@@ -174,6 +174,10 @@ class PipelineConfig:
     # each track of its table (which must be on) was born with, scores the tracked window against it through the accumulated image
     # deformation, drops the rows that no longer match and pulls the others back onto it; FlowPipeline ignores it
     track_template: object = None
+    # keyframe (ofk.h: ofk_set_keyframe): None, True (the defaults) or an ofk.Keyframe: every stream solves its displacement against a
+    # held frame of its track table (which must be on) and reports a position that does not drift with the flow; FlowPipeline
+    # ignores it
+    keyframe: object = None
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -299,6 +303,16 @@ class PipelineConfig:
         m = ofk.track_depth_setting(m.mode, m.sigma_flow, m.b_min, m.gate, m.q, m.min_obs, m.rel_max, m.min_rows, m.update)   # range-checked
         return None if m.mode == ofk.TD_OFF else m
 
+    def keyframe_setting(self):
+        """The ofk.Keyframe structure of this configuration, None when the keyframe is off."""
+        if self.keyframe is None or self.keyframe is False:
+            return None
+        m = ofk.keyframe_setting() if self.keyframe is True else self.keyframe
+        if not isinstance(m, ofk.Keyframe):
+            raise ValueError(f"keyframe {m!r} is neither None, True nor an ofk.Keyframe")
+        m = ofk.keyframe_setting(m.mode, m.sigma_flow, m.gate, m.min_rows, m.min_share, m.rot_max, m.max_age)   # range-checked
+        return None if m.mode == ofk.KEY_OFF else m
+
     def track_template_setting(self):
         """The ofk.TrackTemplate structure of this configuration, None when the templates are off."""
         if self.track_template is None or self.track_template is False:
@@ -417,8 +431,8 @@ class FusionConfig:
 
 def _apply_settings(ctx, cfg, zones):
     """The settings a PipelineConfig switches on, on a fresh context, in the order the library's checks were written for; zones:
-    whether the exclusion zones, the gyro bias, the track table, the depths per track and the track templates are among them (they
-    belong to the stream steps)."""
+    whether the exclusion zones, the gyro bias, the track table, the depths per track, the track templates and the keyframe are among
+    them (they belong to the stream steps)."""
     if cfg.lk_seed != "off":
         ctx.set_lk_seed(cfg.lk_seed, cfg.seed_gain)
     steps = [(ctx.set_robust, cfg.robust_setting), (ctx.set_track_gate, cfg.track_gate_setting), (ctx.set_lk_light, cfg.lk_light_setting),
@@ -427,7 +441,8 @@ def _apply_settings(ctx, cfg, zones):
              (ctx.set_epipolar, cfg.epipolar_setting)]
     if zones:
         steps += [(ctx.set_zones, cfg.zones_setting), (ctx.set_gyro_bias, cfg.gyro_bias_setting), (ctx.set_track_table, cfg.track_table_setting),
-                  (ctx.set_track_depth, cfg.track_depth_setting), (ctx.set_track_template, cfg.track_template_setting)]
+                  (ctx.set_track_depth, cfg.track_depth_setting), (ctx.set_track_template, cfg.track_template_setting),
+                  (ctx.set_keyframe, cfg.keyframe_setting)]
     steps += [(ctx.set_camera, cfg.camera_setting), (ctx.set_rolling_shutter, cfg.rolling_shutter_setting),
               (ctx.set_finite_motion, cfg.finite_motion_setting)]
     for setter, setting in steps:                                # every *_setting() is None when its setting is off
@@ -561,6 +576,21 @@ class FlowStream:
         out["tmpl"] = [d["tmpl"][b, :cnt[b], :e * e].reshape(-1, e, e) for b in range(self.batch)]
         out["ids"] = [t["ids"][b, :cnt[b]] for b in range(self.batch)]
         out["rec"] = d["rec"]
+        return out
+
+    def position(self):
+        """The streams' position against their keyframes behind the latest step (ofk.h: ofk_set_keyframe): dict(pos, D, T [batch, 3]:
+        the position, the displacement since the keyframe and the key solve's translation; flag [batch] (ofk.KEY_SOLVED, _UNSOLVED,
+        _NONE); C_T [batch, 3, 3]; R_acc [batch, 3, 3]; live, members_at_key, key_step, keyframes, dead_reckoned, reason [batch];
+        ids: per stream the ids of the keyframe's members among the tracks that step returned, from the track table; rec)."""
+        d = self.ctx.keyframe_download(self.batch)
+        t = self.ctx.track_table_download(self.batch)
+        cnt, rec = t["stats"][:, 0], d["rec"]
+        out = dict(pos=rec[:, 13:16].copy(), D=rec[:, 10:13].copy(), T=rec[:, 0:3].copy(), flag=rec[:, 3].astype(np.int32),
+                   C_T=ofk.cov_matrix(rec[:, 20:26]), R_acc=d["R_acc"], rec=rec)
+        for k, s in (("members_at_key", 7), ("key_step", 8), ("reason", 9), ("keyframes", 26), ("dead_reckoned", 27), ("live", 28)):
+            out[k] = rec[:, s].astype(np.int32)
+        out["ids"] = [t["ids"][b, :cnt[b]][d["member"][b, :cnt[b]] != 0] for b in range(self.batch)]
         return out
 
     def begin(self, first_bgr):

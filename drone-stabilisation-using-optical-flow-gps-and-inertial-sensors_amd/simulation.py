@@ -60,6 +60,13 @@ def gyro_bias_step(x, u, d, n, omega_raw, state=None, **settings):
     return out[:3].copy(), R, out[5:8].copy(), st
 
 
+def keyframe_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None, **kw):
+    """One step of a stream's keyframe without images (ofk.h: ofk_keyframe_step); velocity_node.keyframe_step's arguments and returns:
+    (state dict(key_xy, member, state, istate), rec [32])."""
+    from .velocity_node import keyframe_step as step
+    return step(np.asarray(next_pts, np.float32)[:, :2], sensors, v_uav, state=state, **kw)
+
+
 def track_depth_step(x, u, omega, v, state=None, **kw):
     """One step of a stream's depths per track without images (ofk.h: ofk_track_depth_step); velocity_node.track_depth_step's
     arguments and returns: (state dict(rho, var, nobs), rec [32])."""

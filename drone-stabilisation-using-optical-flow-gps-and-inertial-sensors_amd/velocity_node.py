@@ -126,6 +126,44 @@ def track_depth_step(x, u, omega, v, state=None, status=None, solved=True, new_c
     return {k: a[0, :kept + born].copy() for k, a in out.items()}, rec[0]
 
 
+def keyframe_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None, status=None, solved=True, step=0, new_count=None, max_total=None,
+                  **settings):
+    """One step of a stream's keyframe without images (ofk.h: ofk_keyframe_step): rotate, key solve, position, re-key decision and
+    compaction.  next_pts [n,2]: the ideal next points in pixels; sensors [28]: the step's sensor row; v_uav, solved: the step
+    record's fields 8-10 and its solved flag (the dead reckoning without a key solve); state: the dict(key_xy, member, state, istate)
+    of the previous call (None: no keyframe yet, position zero); status [n] (None: all kept); step: the track table's step;
+    new_count: corners re-detected behind the kept rows; max_total: the most rows the stream holds (None: whatever fits); settings:
+    ofk.keyframe_setting's keywords.
+    Returns (state, rec [32]): the kept rows in order and the appended ones behind them; rec[13:16] is the position, rec[3] the flag."""
+    pts = np.asarray(next_pts, np.float32).reshape(-1, 2)
+    n = len(pts)
+    if n < 1:
+        raise ValueError("keyframe_step: no points")
+    st = np.ones(n, np.uint8) if status is None else (np.asarray(status).reshape(n) != 0).astype(np.uint8)
+    kept, born = int(st.sum()), 0 if new_count is None else max(int(new_count), 0)
+    S = max(n, kept + born)                                      # room for the appended rows
+    if max_total is not None:
+        born = max(0, min(born, int(max_total) - kept))
+
+    def rows(a, dtype, *tail):                                   # [1, S, ...]: the n rows, zeros behind them
+        out = np.zeros((1, S) + tail, dtype)
+        if a is not None:
+            out[0, :n] = np.asarray(a, dtype).reshape((n,) + tail)
+        return out
+    state = state or {}
+    sd = np.zeros((1, ofk.KEY_STATE)); sd[0, [0, 4, 8]] = 1.0
+    if state.get("state") is not None:
+        sd[0] = np.asarray(state["state"], np.float64).reshape(ofk.KEY_STATE)
+    si = np.zeros((1, ofk.KEY_INTS), np.int32) if state.get("istate") is None else np.asarray(state["istate"], np.int32).reshape(1, ofk.KEY_INTS)
+    out, rec = ofk.default_context().keyframe_step(
+        rows(pts, np.float32, 2), rows(st, np.uint8), [n], np.asarray(sensors, np.float64).reshape(1, ofk.SENSOR_DOUBLES), [v_uav],
+        [1 if solved else 0], [int(step)], dict(key_xy=rows(state.get("key_xy"), np.float32, 2), member=rows(state.get("member"), np.uint8),
+                                                  state=sd, istate=si),
+        new_counts=None if new_count is None else [born], max_total=S, **settings)
+    return dict(key_xy=out["key_xy"][0, :kept + born].copy(), member=out["member"][0, :kept + born].copy(), state=out["state"][0].copy(),
+                istate=out["istate"][0].copy()), rec[0]
+
+
 def track_template_step(prev, next, prev_pts, next_pts, state=None, status=None, age=None, L=None, new_count=None, max_total=None, **settings):
     """One step of a stream's track templates on two gray frames (ofk.h: ofk_track_affine_fit, ofk_track_template_step): the step map
     fitted to the tracked rows (unless L [4] is given), then capture, score, re-anchoring, verdict and compaction.  prev, next [h,w]
@@ -249,6 +287,7 @@ class optical_fusion:
     _finite_motion = {}                                          # PipelineConfig's finite_motion field; empty: the solve takes the flow as the instantaneous field
     _track_table = {}                                            # PipelineConfig's track_table field; empty: the tracks are anonymous points
     _track_depth = {}                                            # PipelineConfig's track_depth field; empty: no depth per track
+    _keyframe = {}                                               # PipelineConfig's keyframe field; empty: no position against a keyframe
     _track_template = {}                                         # PipelineConfig's track_template field; empty: no template per track
     _rolling_shutter = {}                                        # PipelineConfig's rolling_shutter field; empty: every row is taken as exposed at the time stamp
     feature_params = dict(qualityLevel=0.7, minDistance=10, blockSize=12)
@@ -407,7 +446,7 @@ class optical_fusion:
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
                                  **self._cov, **self._joint, **self._plane, **self._epipolar, **self._zones, **self._camera, **self._rolling_shutter,
                                  **self._finite_motion, **self._gyro_bias, **self._lk_light, **self._track_table, **self._track_depth,
-                                 **self._track_template)
+                                 **self._track_template, **self._keyframe)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -454,6 +493,10 @@ class optical_fusion:
         if self._track_depth:
             dp = fs.depths()
             self.last_track_depth = {k: dp[k][0] for k in ("rho", "var", "nobs", "ids", "rec")}
+        if self._keyframe:
+            kp = fs.position()
+            self.last_keyframe = {k: kp[k][0] for k in ("pos", "D", "T", "flag", "C_T", "R_acc", "live", "members_at_key", "key_step", "keyframes",
+                                                        "dead_reckoned", "reason", "ids", "rec")}
         if self._track_template:
             tp = fs.templates()
             self.last_track_template = {k: tp[k][0] for k in ("A", "ncc", "flag", "tstate", "ids", "rec")}
@@ -520,7 +563,7 @@ class optical_fusion:
 
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
                  rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None, gyro_bias=None, lk_light=None,
-                 track_table=None, track_depth=None, track_template=None):
+                 track_table=None, track_depth=None, track_template=None, keyframe=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -575,7 +618,11 @@ class optical_fusion:
         track_template: None (no template per track), True, an ofk.TrackTemplate or a dict of ofk.track_template_setting's keywords,
         e.g. dict(ncc_min=0.9): the stream then keeps the patch every track was born with, drops the tracks that no longer match it
         and pulls the others back onto it (ofk.h: ofk_set_track_template); it switches the track table on when track_table is None.
-        self.last_track_template is dict(A, ncc, flag, tstate, ids, rec)."""
+        self.last_track_template is dict(A, ncc, flag, tstate, ids, rec).
+        keyframe: None (no position against a keyframe), True, an ofk.Keyframe or a dict of ofk.keyframe_setting's keywords, e.g.
+        dict(min_share=0.7): the stream then solves its displacement against a held frame and reports a position that does not drift
+        with the flow (ofk.h: ofk_set_keyframe); it switches the track table on when track_table is None.  self.last_keyframe is
+        FlowStream.position()'s dictionary for the one stream."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -681,6 +728,15 @@ class optical_fusion:
         else:
             self._track_template = {}
         self.last_track_template = None
+        if keyframe is not None and keyframe is not False:
+            kf = keyframe if keyframe is True or isinstance(keyframe, ofk.Keyframe) else ofk.keyframe_setting(**dict(keyframe))
+            self._keyframe = dict(keyframe=kf)
+            PipelineConfig(**self._keyframe).keyframe_setting()          # invalid fields fail here, not at the first frame
+            if not self._track_table:
+                self._track_table = dict(track_table=True)           # the keyframe is kept per row of the table
+        else:
+            self._keyframe = {}
+        self.last_keyframe = None
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

@@ -451,6 +451,104 @@ int ofk_track_template_step(ofk_ctx *ctx, const ofk_track_template *t, const uin
                             uint8_t *tmpl, float *A, float *ncc, uint8_t *flag, uint8_t *tstate, const int *new_counts, int max_total,
                             int batch, int stride, double *rec);
 
+/* Keyframe per stream: the displacement against a frame that is held fixed.  Every solve works on one frame pair, so a stream knows
+ * its position only as a sum of per-frame velocities, whose error grows without bound.  With this setting on a stream keeps, per row
+ * of the track table, the row's ideal pixel in a KEYFRAME and, per stream, the rotation accumulated since; every step solves the
+ * translation T of P_c = R_acc P_K + T from finite motion's relation (n.p_c)/d [q~]x T = [q~]x (p_c - q~), q~ = R_acc p_K
+ * renormalised, which is exact for a pair any distance apart and linear in T.  Off by default; with it off every stream step
+ * allocates, launches and returns what it always did.  Streams only: ofk_pairs_run ignores the setting.  It needs ofk_set_track_table
+ * on.  Nothing of the records, `fused`, the tracks, the table, the depths or the templates changes with it on: the position is
+ * reported in a record of its own, not fed back.  It removes the drift of the flow, not of the gyro: R_acc is the product of the
+ * steps' rotations, and a constant error in omega is ofk_set_gyro_bias's job.
+ * State per track row, in the table's row order, in arrays of their own: key_xy (2 f32, the row's ideal pixel in the keyframe),
+ * member (u8, 1 = the row was alive at the keyframe).  Per stream: state [OFK_KEY_STATE] f64 = R_acc (0-8, row-major), anchor (9-11),
+ * pos (12-14), 15 unused; istate [OFK_KEY_INTS] i32 = key_step, members_at_key, keyframes so far, dead-reckoned steps; a record of
+ * OFK_KEY_DOUBLES.
+ * The points are the ideal NEXT points of the step: behind the camera model and the rolling shutter, in FRONT of the finite-motion
+ * rewrite (which replaces the next point by q~ of the neighbouring pair).  With finite motion on beside a camera or a rolling shutter
+ * that rewrite is in place, and the step keeps one device copy of the next points in front of it; otherwise the buffers the rewrite
+ * read are intact behind the solve.
+ * Per stream: sn = the sensor row; d = sn[0]; n = sn[1..3], omega = sn[4..6], R_world = sn[7..15] (under use_imu the IMU state's
+ * normal, ang and rotation); offset = sn[16..18]; scaling, c = sn[19], sn[20..21].  omega is what the step's solve read (behind the
+ * gyro-bias apply).  sigma_flow and gate are given in pixels and multiplied by `scaling`.  v_uav = fields 8-10 of the step's record as
+ * the chain left it, solved = record[15] != 0 (ofk_stream_step: rank = record[4] >= 3), and v_uav finite.  step = the table's step.
+ * All arithmetic is f64 without contraction in the order written; sums of three are (a + b) + c; the sums over rows are the solve's
+ * (four waves over the rows i = tid + 256 k, the shuffle butterfly, (s0 + s1) + (s2 + s3)); Jacobi and rank rule are the solve's.
+ * One launch, k_keyframe_step, one workgroup per stream, on exactly the steps that launch k_track_table_update (a held step leaves
+ * state and record alone) and in front of the depths', the templates' and the table's update, on the status and counts
+ * k_update_tracks reads.  n = min(max(counts, 0), stride).  In order:
+ *   1. Rotate (every step, solved or not).  th2 = (o0 o0 + o1 o1) + o2 o2; A = 1, B = 0.5 if th2 < 1e-16, else th = sqrt(th2),
+ *      A = sin(th) / th, B = (1 - cos(th)) / th2 (rs_rotate3's coefficients, for a rotation by +omega).  K = [omega]x,
+ *      K2_ij = o_i o_j - (i == j ? th2 : 0); E_ij = ((i == j ? 1 : 0) + A K_ij) + B K2_ij; R_acc_ij = (E_i0 R_0j + E_i1 R_1j) + E_i2 R_2j.
+ *      angle = acos(min(1, max(-1, (((R00 + R11) + R22) - 1) / 2))), fmin / fmax: a trace that is no number reads -1, the angle pi.
+ *   2. Key solve over the rows i < n with status != 0 and member != 0 (their number is `live`).  k = (key_xy - c) scaling,
+ *      p = (next - c) scaling; (X, Y, Z) = R_acc (k, 1), each (R_i0 kx + R_i1 ky) + R_i2.  The row is left out unless
+ *      Z >= OFK_KEY_MIN_DEPTH, den = (n0 px + n1 py) + n2 has |den| >= 1e-12 and s = nq / den > 0, with a = X / Z, b = Y / Z,
+ *      nq = (n0 a + n1 b) + n2 (each false for NaN).  x^ = (a, b), u^ = (s (px - a), s (py - b)), sA = nq / d: the row enters the
+ *      solve's sums as acc_point(x^, (u^, 0), sA, 1).  T = M^+ g.  Flag 2: members_at_key == 0 (no keyframe; nothing is solved).
+ *      Flag 1: fewer than min_rows rows, rank < 3 or a sum that is not finite.  Flag 0 otherwise.
+ *      gate > 0 and flag 0: r = u^ - sA (T_xy - T_z x^); a second solve over the rows with r.r <= (gate scaling)^2; it replaces the
+ *      first when it has at least min_rows rows, rank 3 and finite sums.  rms = sqrt(sum r.r / rows) / scaling over the rows and
+ *      under the T of the solve that stands.  C_T = (sigma_flow scaling)^2 M^-1 of that solve from the same Jacobi, entry (i, j) =
+ *      ((V_i0 V_j0 / l0 + V_i1 V_j1 / l1) + V_i2 V_j2 / l2); the points' correlation over frames is not in it: a lower bound.
+ *   3. Position.  Flag 0: w_i = T_i + (offset_i - ((R_i0 offset_0 + R_i1 offset_1) + R_i2 offset_2)), D_i = (Rw_i0 w_0 + Rw_i1 w_1) +
+ *      Rw_i2 w_2, pos = anchor + D; a D that is not finite (an offset or an R_world that is no number) makes the flag 1, T and rms
+ *      0, and the step goes on as below.  This is v_uav's sign convention: to first order D is the sum of the records' fields 8-10 since
+ *      the keyframe.  Any other flag: pos += v_uav where the step's record is solved, pos stays otherwise; D = pos - anchor; the
+ *      dead-reckoned count goes up by one.
+ *   4. Re-key, when any of these holds; the record carries the lowest number and the set as bits (1 << (number - 1)):
+ *      1 flag != 0;  2 live < min_rows;  3 live < min_share members_at_key (in f64);  4 angle > rot_max;
+ *      5 max_age > 0 and (step + 1) - key_step > max_age.
+ *   5. Compaction: the rows with status != 0 move up in order with key_xy and member;
+ *      extra = max(0, min(new count, max_total - kept, stride - kept)) rows (0 without a re-detection) are appended with member 0
+ *      and key_xy 0: raw detections without an ideal position, they join at the next re-key.  On a re-key every kept row gets
+ *      key_xy = its ideal next point and member = 1, anchor = pos, R_acc = I, members_at_key = kept, key_step = step + 1, and the
+ *      keyframe count goes up by one.  Rows beyond are not defined.
+ * Record: 0-2 T, 3 flag, 4 / 5 rows of the first / the gated solve (5: 0 when none ran), 6 rms in px, 7 members_at_key and 8 key_step
+ * behind rule 5, 9 re-key reason (0: none), 10-12 D, 13-15 pos, 16-18 anchor behind rule 5, 19 angle of R_acc in front of rule 5,
+ * 20-25 C_T's upper triangle, 26 keyframes so far, 27 dead-reckoned steps, 28 live, 29 1 where the gated solve stands, 30 the reasons
+ * as bits, 31 0.  T, rms and C_T read 0 unless flag 0.
+ * k_keyframe_begin / k_keyframe_replace run where the table's begin and replace rules run: both clear the members and
+ * members_at_key; begin also zeroes anchor, pos and the counts, sets R_acc = I and the record to zero with flag 2.  The first step
+ * behind them reports flag 2, dead-reckons once and keys on the rows it tracked.  Streams that step with the setting on without
+ * such state (switched on in mid-stream) start the same way.  The buffers (17 bytes per track, the per-stream state) are allocated
+ * by the first step with the setting on.
+ * ofk_set_keyframe: NULL or mode OFK_KEY_OFF switches the feature off.  OFK_E_INVALID, the setting staying as it was: a mode that is
+ * neither, sigma_flow <= 0, gate < 0 (0: a single solve), min_rows < 3, min_share outside [0, 1], rot_max <= 0, max_age < 0 (0: no
+ * limit), a value that is not finite.  Defaults behind "off": 0.2, 2.0, 8, 0.5, 0.5, 0.
+ * OFK_E_INVALID before any launch from a stream step with the setting on: ofk_set_track_table off; OFK_SOLVE_OFMODULE,
+ * OFK_FLOW_ROTATIONAL, OFK_KEEP_LEGACY (not the sensor model).
+ * ofk_keyframe_download, the streams of the latest step with the setting on, the first min(stride, max_pts) rows of each (every
+ * output may be NULL): key_xy [batch][stride][2] f32, member [batch][stride] u8, R_acc [batch][9], rec [batch][OFK_KEY_DOUBLES].
+ * ofk_keyframe_reset: anchor = pos = the given position (NULL: zero) for active stream b, R_acc = I, the members cleared, the record
+ * zero but for flag 2, pos, anchor, key_step and the two counts: the next step reports flag 2, dead-reckons from there and keys (streams without state get it first).
+ * ofk_keyframe_step, rules 1-5 on host buffers (it touches no resident state): next_pts [batch][stride][2] f32 ideal next points,
+ * status [batch][stride], counts [batch], sensors [batch][OFK_SENSOR_DOUBLES], v_uav [batch][3], solved [batch] i32, step [batch]
+ * i32, the state key_xy, member, state [batch][OFK_KEY_STATE], istate [batch][OFK_KEY_INTS] in and out in place, new_counts [batch]
+ * (NULL: none), max_total <= stride, rec [batch][OFK_KEY_DOUBLES] out (may be NULL). */
+#define OFK_KEY_OFF        0
+#define OFK_KEY_ON         1
+#define OFK_KEY_DOUBLES    32
+#define OFK_KEY_STATE      16
+#define OFK_KEY_INTS       4
+#define OFK_KEY_MIN_DEPTH  0.1
+#define OFK_KEY_SOLVED     0
+#define OFK_KEY_UNSOLVED   1
+#define OFK_KEY_NONE       2
+#define OFK_KEY_RE_FLAG    1
+#define OFK_KEY_RE_ROWS    2
+#define OFK_KEY_RE_SHARE   3
+#define OFK_KEY_RE_ANGLE   4
+#define OFK_KEY_RE_AGE     5
+typedef struct ofk_keyframe { int mode; double sigma_flow; double gate; int min_rows; double min_share; double rot_max; int max_age; } ofk_keyframe;
+int ofk_set_keyframe(ofk_ctx *ctx, const ofk_keyframe *k);
+int ofk_get_keyframe(const ofk_ctx *ctx, ofk_keyframe *k);
+int ofk_keyframe_download(ofk_ctx *ctx, float *key_xy, uint8_t *member, int stride, double *R_acc, double *rec);
+int ofk_keyframe_reset(ofk_ctx *ctx, int b, const double *anchor);
+int ofk_keyframe_step(ofk_ctx *ctx, const ofk_keyframe *k, const float *next_pts, const uint8_t *status, const int *counts,
+                      const double *sensors, const double *v_uav, const int *solved, const int *step, float *key_xy, uint8_t *member,
+                      double *state, int *istate, const int *new_counts, int max_total, int batch, int stride, double *rec);
+
 /* Camera model: the lens distortion undone on the device before the solve.  The solve stage reads a point as a sample of an ideal
  * pinhole image, x = (px - cx) * scaling (sensors[19..21]); the reference's camera is a wide-angle module whose lens moves a point by
  * tens of pixels at the border.  With ofk_set_camera on, the resident chains keep everything that lives in the image on the raw
