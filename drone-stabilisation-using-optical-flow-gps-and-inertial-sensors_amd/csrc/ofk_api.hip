@@ -163,6 +163,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->td = ofk_track_depth{OFK_TD_OFF, 0.2, 0.5, 3.0, 0.0, 3, 0.25, 8, 1};
     c->tpl = ofk_track_template{OFK_TPL_OFF, 15, 0.8, 3, 2.0, OFK_TPL_KEEP, 6, 2.0, 1.5};
     c->key = ofk_keyframe{OFK_KEY_OFF, 0.2, 2.0, 8, 0.5, 0.5, 0};
+    c->krot = ofk_keyframe_rotation{OFK_KEYROT_OFF, OFK_KEYROT_GYRO, {1, 1, 1}, 0.0, 1e-4, 1e-3, 2, 0.1};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -216,7 +217,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
                     c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec, c->joint_rec, c->bias_rec, c->plane_rec, c->epi_rec,
-                    c->zone_tab, c->pts_prev_u, c->ttr.ids, c->tdr.rho, c->tpr.tmpl[0], c->kfr.key_xy};
+                    c->zone_tab, c->pts_prev_u, c->ttr.ids, c->tdr.rho, c->tpr.tmpl[0], c->kfr.key_xy, c->kr_st};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
@@ -2917,6 +2918,58 @@ extern "C" int ofk_get_keyframe(const ofk_ctx *c, ofk_keyframe *k) { return sett
 
 static bool kf_on(const ofk_ctx *c) { return c->key.mode != OFK_KEY_OFF; }
 
+// the keyframe's rotation (ofk.h: ofk_set_keyframe_rotation)
+static int check_keyrot(ofk_ctx *c, const ofk_keyframe_rotation *r, const char *who)
+{
+    if (r->mode != OFK_KEYROT_OFF && r->mode != OFK_KEYROT_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_KEYROT_OFF nor OFK_KEYROT_ON", who, r->mode);
+    if (r->mode == OFK_KEYROT_OFF) return OFK_OK;
+    if (r->source != OFK_KEYROT_GYRO && r->source != OFK_KEYROT_ATTITUDE)
+        return ofk_fail(c, OFK_E_INVALID, "%s: source %d is neither OFK_KEYROT_GYRO nor OFK_KEYROT_ATTITUDE", who, r->source);
+    if (!(r->sigma_gyro >= 0.0) || !(r->sigma_bias >= 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: sigma_gyro and sigma_bias must not be negative or NaN", who);
+    if (!(r->sigma_att >= 0.0) || !std::isfinite(r->sigma_att)) return ofk_fail(c, OFK_E_INVALID, "%s: sigma_att = %g must be finite and not negative", who, r->sigma_att);
+    if (r->iters < 1 || r->iters > OFK_KEYROT_MAX_ITERS) return ofk_fail(c, OFK_E_INVALID, "%s: iters = %d outside 1..%d", who, r->iters, OFK_KEYROT_MAX_ITERS);
+    if (!(r->delta_max > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: delta_max = %g must be positive", who, r->delta_max);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_keyframe_rotation(ofk_ctx *c, const ofk_keyframe_rotation *r)
+{
+    return setting_set(c, &ofk_ctx::krot, r && r->mode == OFK_KEYROT_OFF ? nullptr : r, [](ofk_keyframe_rotation &s) { s.mode = OFK_KEYROT_OFF; },
+                       [c](const ofk_keyframe_rotation *v) { return check_keyrot(c, v, "ofk_set_keyframe_rotation"); });
+}
+extern "C" int ofk_get_keyframe_rotation(const ofk_ctx *c, ofk_keyframe_rotation *r) { return setting_get(c, &ofk_ctx::krot, r); }
+
+static bool kr_on(const ofk_ctx *c) { return c->krot.mode != OFK_KEYROT_OFF; }
+// every axis held by the setting alone: the plain kernel runs (ofk.h)
+static bool kr_all_held(const ofk_keyframe_rotation *r)
+{
+    if (!r->axes[0] && !r->axes[1] && !r->axes[2]) return true;
+    return r->source == OFK_KEYROT_ATTITUDE ? r->sigma_att == 0.0 : r->sigma_gyro == 0.0 && r->sigma_bias == 0.0;
+}
+// the rotation state and records of max_batch streams, allocated (and cleared) by the first step with the setting on
+static int kr_alloc(ofk_ctx *c)
+{
+    if (c->kr_st) return OFK_OK;
+    const size_t sb = up((size_t)c->max_batch * OFK_KEYROT_STATE * 8, 256), bytes = sb + (size_t)c->max_batch * OFK_KEYROT_DOUBLES * 8;
+    uint8_t *base = nullptr;
+    OFK_HIP(c, hipMalloc((void **)&base, bytes));
+    c->kr_st = (double *)base; c->kr_rec = (double *)(base + sb);
+    OFK_HIP(c, hipMemsetAsync(base, 0, bytes, c->stream));
+    return OFK_OK;
+}
+// the launch of rules 1-5: k_keyframe_step, or with the rotation on (r, not all held) k_keyframe_step_rot in its place
+static void launch_key_step(ofk_ctx *c, const ofk_kf_rows &t, const ofk_kf_in &in, const ofk_keyframe *k, const ofk_keyframe_rotation *r,
+                            double *rst, double *rrec, int batch)
+{
+    if (!r) { ofk_launch_keyframe_step(c->stream, t, in, k, batch); return; }
+    if (kr_all_held(r)) {
+        ofk_launch_keyframe_step(c->stream, t, in, k, batch);
+        ofk_launch_keyrot_clear(c->stream, nullptr, rrec, nullptr, 0, OFK_KEYROT_HELD, batch);
+        return;
+    }
+    ofk_launch_keyframe_step_rot(c->stream, t, in, k, r, rst, rrec, batch);
+}
+
 // the state's arrays over `np` rows and the state of `batch` streams carved out of base (NULL: nothing is carved); returns the bytes
 static size_t kf_carve(ofk_kf_rows &t, uint8_t *base, size_t np, size_t batch)
 {
@@ -2943,6 +2996,8 @@ static int kf_alloc(ofk_ctx *c)
 // The steps' own refusals with the setting on (ofk.h); fu: a fused step's.
 static int kf_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const char *who)
 {
+    if (kr_on(c) && !kf_on(c))
+        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_keyframe_rotation is on without ofk_set_keyframe: it refines the keyframe's rotation", who);
     if (!kf_on(c)) return OFK_OK;
     if (c->tt.mode == OFK_TT_OFF)
         return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_keyframe is on without ofk_set_track_table: the keyframe is kept per row of the table", who);
@@ -2955,8 +3010,27 @@ static int kf_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const ch
 static int kf_begin(ofk_ctx *c, int B)
 {
     TRY(kf_alloc(c));
-    if (c->kf_live != B) ofk_launch_keyframe_begin(c->stream, c->kfr, c->counts, c->max_pts, B);
+    if (c->kf_live != B) { ofk_launch_keyframe_begin(c->stream, c->kfr, c->counts, c->max_pts, B); c->kr_live = 0; }
     c->kf_batch = c->kf_live = B;
+    return OFK_OK;
+}
+// behind kf_begin with the rotation on: its state in step with the keyframe's, cleared where that began afresh
+static int kr_begin(ofk_ctx *c, int B)
+{
+    TRY(kr_alloc(c));
+    if (c->kr_live != B) ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, nullptr, 0, OFK_KEYROT_NONE, B);
+    c->kr_batch = c->kr_live = B;
+    return OFK_OK;
+}
+
+extern "C" int ofk_keyframe_rotation_download(ofk_ctx *c, double *rec)
+{
+    if (!c) return OFK_E_INVALID;
+    if (c->kr_batch < 1 || !c->kr_rec) return ofk_fail(c, OFK_E_INVALID, "ofk_keyframe_rotation_download: no stream has stepped with ofk_set_keyframe_rotation on yet");
+    if (!rec) return ofk_fail(c, OFK_E_INVALID, "ofk_keyframe_rotation_download: NULL argument");
+    TRY(enter(c));
+    OFK_HIP(c, hipMemcpyAsync(rec, c->kr_rec, (size_t)c->kr_batch * OFK_KEYROT_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
 }
 
@@ -2987,24 +3061,29 @@ extern "C" int ofk_keyframe_reset(ofk_ctx *c, int b, const double *anchor)
     TRY(enter(c));
     TRY(kf_begin(c, c->stream_batch));
     ofk_launch_keyframe_reset(c->stream, c->kfr, b, c->max_pts, p);
+    if (c->kr_st && c->kr_live == c->stream_batch) ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, nullptr, b, OFK_KEYROT_NONE, 1);
     TRY(check_launch(c, who));
     OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
 }
 
-// rules 1-5 on host buffers: device scratch only
-extern "C" int ofk_keyframe_step(ofk_ctx *c, const ofk_keyframe *set, const float *next_pts, const uint8_t *status, const int *counts,
-                                 const double *sensors, const double *v_uav, const int *solved, const int *step, float *key_xy, uint8_t *member,
-                                 double *state, int *istate, const int *new_counts, int max_total, int batch, int stride, double *rec)
+// rules 1-5 on host buffers: device scratch only; rot != NULL: with the rotation's rule 2 (rstate in and out, rrec out)
+static int keyframe_step_host(ofk_ctx *c, const char *who, const ofk_keyframe *set, const ofk_keyframe_rotation *rot, const float *next_pts,
+                              const uint8_t *status, const int *counts, const double *sensors, const double *v_uav, const int *solved,
+                              const int *step, float *key_xy, uint8_t *member, double *state, int *istate, const int *new_counts, int max_total,
+                              int batch, int stride, double *rec, double *rstate, double *rrec)
 {
-    const char *who = "ofk_keyframe_step";
-    if (!c) return OFK_E_INVALID;
     if (!set || !next_pts || !status || !counts || !sensors || !v_uav || !solved || !step || !key_xy || !member || !state || !istate)
         return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
     if (batch < 1 || stride < 1) return ofk_fail(c, OFK_E_INVALID, "%s: batch %d / stride %d", who, batch, stride);
     if (max_total < 0 || max_total > stride) return ofk_fail(c, OFK_E_INVALID, "%s: max_total %d outside 0..%d", who, max_total, stride);
     if (set->mode == OFK_KEY_OFF) return ofk_fail(c, OFK_E_INVALID, "%s: the setting is off", who);
     TRY(check_key(c, set, who));
+    if (rot) {
+        if (!rstate) return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
+        if (rot->mode == OFK_KEYROT_OFF) return ofk_fail(c, OFK_E_INVALID, "%s: the rotation setting is off", who);
+        TRY(check_keyrot(c, rot, who));
+    }
     TRY(check_counts(c, who, counts, batch, stride));
     const size_t np = (size_t)batch * stride, B = (size_t)batch;
     double *h_rec = (double *)calloc(B * OFK_RECORD_DOUBLES, 8);   // the step's records as the kernel reads them: v_uav, solved
@@ -3014,7 +3093,7 @@ extern "C" int ofk_keyframe_step(ofk_ctx *c, const ofk_keyframe *set, const floa
         h_rec[b * OFK_RECORD_DOUBLES + 15] = solved[b] ? 1.0 : 0.0;
     }
     Bump bp;
-    int rc = est_begin(c, np * 18 + B * ((OFK_RECORD_DOUBLES + OFK_KEY_DOUBLES + OFK_KEY_STATE + OFK_SENSOR_DOUBLES) * 8 + OFK_KEY_INTS * 4 + 12) + 16 * 256, bp);
+    int rc = est_begin(c, np * 18 + B * ((OFK_RECORD_DOUBLES + OFK_KEY_DOUBLES + OFK_KEY_STATE + OFK_SENSOR_DOUBLES + OFK_KEYROT_STATE + OFK_KEYROT_DOUBLES) * 8 + OFK_KEY_INTS * 4 + 12) + 18 * 256, bp);
     if (rc != OFK_OK) { free(h_rec); return rc; }
     ofk_kf_rows t = {};
     t.key_xy = (float *)bp.put(key_xy, np * 8); t.member = (uint8_t *)bp.put(member, np); t.st = bp.put(state, B * OFK_KEY_STATE * 8);
@@ -3026,11 +3105,16 @@ extern "C" int ofk_keyframe_step(ofk_ctx *c, const ofk_keyframe *set, const floa
     in.sensors = bp.put(sensors, B * OFK_SENSOR_DOUBLES * 8); in.imu = nullptr;
     in.v = bp.put(h_rec, B * OFK_RECORD_DOUBLES * 8); in.plain = 0;
     in.step = (const int *)bp.put(step, B * 4); in.step_stride = 1;
+    double *d_rst = rot ? bp.put(rstate, B * OFK_KEYROT_STATE * 8) : nullptr, *d_rrec = rot ? bp.take(B * OFK_KEYROT_DOUBLES * 8) : nullptr;
     hipError_t e = bp.rc == OFK_OK ? hipStreamSynchronize(c->stream) : hipErrorUnknown;   // h_rec has been read
     free(h_rec);
     if (e != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
-    ofk_launch_keyframe_step(c->stream, t, in, set, batch);
-    TRY(check_launch(c, "k_keyframe_step"));
+    launch_key_step(c, t, in, set, rot, d_rst, d_rrec, batch);
+    TRY(check_launch(c, rot ? "k_keyframe_step_rot" : "k_keyframe_step"));
+    if (rot) {
+        OFK_HIP(c, hipMemcpyAsync(rstate, d_rst, B * OFK_KEYROT_STATE * 8, hipMemcpyDeviceToHost, c->stream));
+        if (rrec) OFK_HIP(c, hipMemcpyAsync(rrec, d_rrec, B * OFK_KEYROT_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
+    }
     OFK_HIP(c, hipMemcpyAsync(key_xy, t.key_xy, np * 8, hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipMemcpyAsync(member, t.member, np, hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipMemcpyAsync(state, t.st, B * OFK_KEY_STATE * 8, hipMemcpyDeviceToHost, c->stream));
@@ -3038,6 +3122,26 @@ extern "C" int ofk_keyframe_step(ofk_ctx *c, const ofk_keyframe *set, const floa
     if (rec) OFK_HIP(c, hipMemcpyAsync(rec, t.rec, B * OFK_KEY_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
     OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
+}
+
+extern "C" int ofk_keyframe_step(ofk_ctx *c, const ofk_keyframe *set, const float *next_pts, const uint8_t *status, const int *counts,
+                                 const double *sensors, const double *v_uav, const int *solved, const int *step, float *key_xy, uint8_t *member,
+                                 double *state, int *istate, const int *new_counts, int max_total, int batch, int stride, double *rec)
+{
+    if (!c) return OFK_E_INVALID;
+    return keyframe_step_host(c, "ofk_keyframe_step", set, nullptr, next_pts, status, counts, sensors, v_uav, solved, step, key_xy, member, state,
+                              istate, new_counts, max_total, batch, stride, rec, nullptr, nullptr);
+}
+
+extern "C" int ofk_keyframe_rotation_step(ofk_ctx *c, const ofk_keyframe *set, const ofk_keyframe_rotation *rot, const float *next_pts,
+                                          const uint8_t *status, const int *counts, const double *sensors, const double *v_uav,
+                                          const int *solved, const int *step, float *key_xy, uint8_t *member, double *state, int *istate,
+                                          const int *new_counts, int max_total, int batch, int stride, double *rec, double *rstate, double *rrec)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!rot) return ofk_fail(c, OFK_E_INVALID, "ofk_keyframe_rotation_step: NULL argument");
+    return keyframe_step_host(c, "ofk_keyframe_rotation_step", set, rot, next_pts, status, counts, sensors, v_uav, solved, step, key_xy, member,
+                              state, istate, new_counts, max_total, batch, stride, rec, rstate, rrec);
 }
 
 // ------------------------------------------------------------------------------------------------ video streams
@@ -3102,6 +3206,7 @@ static int stream_begin_impl(ofk_ctx *c, const uint8_t *first_bgr, int batch, in
     c->td_batch = c->td_live = 0;                                // ... and without depths: the first step with that setting on starts them
     c->tp_batch = c->tp_live = 0;                                // ... and without templates
     c->kf_batch = c->kf_live = 0;                                // ... and without a keyframe
+    c->kr_batch = c->kr_live = 0;                                // ... and without its rotation state
     if (tt_on(c)) {
         TRY(tt_alloc(c));
         ofk_launch_track_table_begin(c->stream, c->ttr, c->pts_prev, c->counts, c->max_pts, batch);
@@ -3297,6 +3402,9 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     const bool keyf = kf_on(c);                                  // kf_check_step: then the table is on
     if (keyf) TRY(kf_begin(c, B));
     else c->kf_live = 0;                                         // the tracks move on without their keyframe
+    const bool krot = keyf && kr_on(c);                          // kf_check_step: never without the keyframe
+    if (krot) TRY(kr_begin(c, B));
+    else c->kr_live = 0;                                         // the keyframes move on without their R_world(key)
     const bool flow_seed = table && c->tt.seed == OFK_TT_SEED_FLOW;
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
@@ -3313,6 +3421,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         if (table) ofk_launch_track_table_replace(c->stream, c->ttr, c->limit, c->pts_new, c->new_counts, c->max_pts, B);
         if (depth) ofk_launch_track_depth_replace(c->stream, c->tdr, c->limit, c->new_counts, c->max_pts, B);
         if (keyf) ofk_launch_keyframe_replace(c->stream, c->kfr, c->limit, c->new_counts, c->max_pts, B);
+        if (krot) ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, c->limit, 0, OFK_KEYROT_NONE, B);
     }
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)
@@ -3370,7 +3479,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
             in.new_counts = any ? c->new_counts : nullptr; in.max_total = p->max_corners; in.sensors = c->sensors;
             in.imu = fu && fu->use_imu ? c->imu_state : nullptr; in.v = c->records; in.plain = fu ? 0 : 1;
             in.step = c->ttr.head; in.step_stride = 2;
-            ofk_launch_keyframe_step(c->stream, c->kfr, in, &c->key, B);
+            launch_key_step(c, c->kfr, in, &c->key, krot ? &c->krot : nullptr, c->kr_st, c->kr_rec, B);
         }
         if (depth) {                                             // in front of the table's update, on what k_update_tracks is about to read
             const bool imu = fu && fu->use_imu;

@@ -163,6 +163,9 @@ struct ofk_ctx {
     int tp_batch, tp_live;                   // streams of the latest step with the templates on (ofk_track_template_download), 0 = none; streams whose rows match their current tracks
     ofk_keyframe key;                        // ofk_set_keyframe: mode OFK_KEY_OFF unless set
     ofk_kf_rows kfr;                         // the keyframe's device rows and per-stream state; one lazy allocation (kfr.key_xy owns it)
+    ofk_keyframe_rotation krot;              // ofk_set_keyframe_rotation: mode OFK_KEYROT_OFF unless set
+    double *kr_st, *kr_rec;                  // [max_batch][OFK_KEYROT_STATE], [max_batch][OFK_KEYROT_DOUBLES]; one lazy allocation (kr_st owns it)
+    int kr_batch, kr_live;                   // (kr_live: streams whose rotation state is in step with their keyframe) streams of the latest step with the rotation on (ofk_keyframe_rotation_download), 0 = none
     int kf_batch, kf_live;                   // streams of the latest step with the keyframe on (ofk_keyframe_download), 0 = none; streams whose rows match their current tracks
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
@@ -298,6 +301,11 @@ void ofk_launch_keyframe_begin(hipStream_t s, const ofk_kf_rows &t, const int *c
 void ofk_launch_keyframe_replace(hipStream_t s, const ofk_kf_rows &t, const int *limit, const int *new_counts, int stride, int batch);
 void ofk_launch_keyframe_reset(hipStream_t s, const ofk_kf_rows &t, int b, int stride, const double *p);
 void ofk_launch_keyframe_step(hipStream_t s, const ofk_kf_rows &t, const ofk_kf_in &in, const ofk_keyframe *k, int batch);
+// the keyframe's rotation (ofk.h: ofk_set_keyframe_rotation; k_keyframe_rot.inc): k_keyframe_step's launch with the joint rule 2, and the
+// rotation state cleared beside the keyframe's begin (limit NULL), replace (limit) and reset (one stream b0)
+void ofk_launch_keyframe_step_rot(hipStream_t s, const ofk_kf_rows &t, const ofk_kf_in &in, const ofk_keyframe *k, const ofk_keyframe_rotation *r,
+                                  double *rst, double *rrec, int batch);
+void ofk_launch_keyrot_clear(hipStream_t s, double *rst, double *rrec, const int *limit, int b0, int flag, int batch);
 // the track templates (ofk.h: ofk_set_track_template; k_track_template.inc): rule 1, rules 2-5 behind the gates, rule 6 in front of the table's update
 void ofk_launch_track_affine(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts, int stride,
                              int h, int w, const ofk_track_template *d, float *L, double *rec, int batch);

@@ -43,6 +43,7 @@ SYMBOLS = (
     "ofk_set_track_table", "ofk_get_track_table", "ofk_track_table_download", "ofk_track_table_step", "ofk_track_seed_points",
     "ofk_set_track_depth", "ofk_get_track_depth", "ofk_track_depth_download", "ofk_track_depth_reset", "ofk_track_depth_step",
     "ofk_set_keyframe", "ofk_get_keyframe", "ofk_keyframe_download", "ofk_keyframe_reset", "ofk_keyframe_step",
+    "ofk_set_keyframe_rotation", "ofk_get_keyframe_rotation", "ofk_keyframe_rotation_download", "ofk_keyframe_rotation_step",
     "ofk_set_track_template", "ofk_get_track_template", "ofk_track_template_download", "ofk_track_affine_fit", "ofk_track_template_step",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
@@ -115,6 +116,10 @@ KEY_DOUBLES, KEY_STATE, KEY_INTS = 32, 16, 4             # the record; R_acc, an
 KEY_MIN_DEPTH = 0.1
 KEY_SOLVED, KEY_UNSOLVED, KEY_NONE = 0, 1, 2             # the record's flag
 KEY_RE_FLAG, KEY_RE_ROWS, KEY_RE_SHARE, KEY_RE_ANGLE, KEY_RE_AGE = 1, 2, 3, 4, 5   # the record's re-key reason
+KEYROT_OFF, KEYROT_ON = 0, 1                             # ofk_set_keyframe_rotation
+KEYROT_GYRO, KEYROT_ATTITUDE = 0, 1                      # where R_acc comes from
+KEYROT_DOUBLES, KEYROT_STATE, KEYROT_MAX_ITERS = 40, 12, 8   # the record; R_world at the keyframe, valid, its key_step
+KEYROT_OK, KEYROT_NONE, KEYROT_SINGULAR, KEYROT_LARGE, KEYROT_HELD = 0, 1, 2, 3, 4   # the record's flag
 TPL_OFF, TPL_ON = 0, 1                                   # ofk_set_track_template
 TPL_DOUBLES = 32                                         # M, t, fit flag, rows of the two fits, rms, nine counts, largest move
 TPL_KEEP, TPL_DROP = 0, 1
@@ -546,6 +551,35 @@ def track_template_setting(mode=True, win=15, ncc_min=0.8, anchor_iters=3, ancho
     return t
 
 
+class KeyframeRotation(C.Structure):
+    """ofk_keyframe_rotation (include/ofk.h): the keyframe's accumulated rotation refined from the flow."""
+    _fields_ = [("mode", C.c_int), ("source", C.c_int), ("axes", C.c_int * 3), ("sigma_gyro", C.c_double), ("sigma_bias", C.c_double),
+                ("sigma_att", C.c_double), ("iters", C.c_int), ("delta_max", C.c_double)]
+
+
+def keyframe_rotation_setting(mode=True, source="gyro", axes=(1, 1, 1), sigma_gyro=0.0, sigma_bias=1e-4, sigma_att=1e-3, iters=2, delta_max=0.1):
+    """A KeyframeRotation structure from names: mode True / False (or KEYROT_*); source "gyro" (R_acc is the product of the steps'
+    rotations; prior variance age sigma_gyro^2 + (age sigma_bias)^2 per axis, in rad and rad per frame) or "attitude" (R_acc from
+    R_world of the sensor rows; prior variance 2 sigma_att^2); axes: which of the three are estimated (0: held); iters Gauss-Newton
+    steps; a correction beyond delta_max rad is refused."""
+    mode = int(mode)
+    if mode not in (KEYROT_OFF, KEYROT_ON):
+        raise ValueError(f"keyframe-rotation mode {mode} is none of KEYROT_OFF, KEYROT_ON")
+    src = {"gyro": KEYROT_GYRO, "attitude": KEYROT_ATTITUDE}.get(source, source)
+    if src not in (KEYROT_GYRO, KEYROT_ATTITUDE):
+        raise ValueError(f"keyframe-rotation source {source!r} is none of 'gyro', 'attitude'")
+    ax = [int(bool(a)) for a in axes]
+    if len(ax) != 3:
+        raise ValueError("keyframe-rotation axes must be three flags")
+    r = KeyframeRotation(mode, int(src), (C.c_int * 3)(*ax), float(sigma_gyro), float(sigma_bias), float(sigma_att), int(iters), float(delta_max))
+    if mode != KEYROT_OFF:
+        if not (r.sigma_gyro >= 0 and r.sigma_bias >= 0 and r.sigma_att >= 0 and np.isfinite(r.sigma_att) and 1 <= r.iters <= KEYROT_MAX_ITERS
+                and r.delta_max > 0):
+            raise ValueError(f"keyframe-rotation setting outside its range: sigma_gyro {r.sigma_gyro} >= 0, sigma_bias {r.sigma_bias} >= 0, "
+                             f"sigma_att {r.sigma_att} finite >= 0, iters {r.iters} in 1..{KEYROT_MAX_ITERS}, delta_max {r.delta_max} > 0")
+    return r
+
+
 class Fusion(C.Structure):
     """ofk_fusion (include/ofk.h): what ofk_stream_step_fused does between LK and the next frame."""
     _fields_ = [("use_imu", C.c_int), ("flow", C.c_int), ("keep", C.c_int), ("filter", C.c_int), ("control", C.c_int),
@@ -556,7 +590,8 @@ class Fusion(C.Structure):
 # the struct settings: ofk_set_<name> / ofk_get_<name> take the context and a pointer to the struct
 SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("gyro_bias", GyroBias), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate), ("lk_light", LkLight),
             ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion),
-            ("track_table", TrackTable), ("track_depth", TrackDepth), ("track_template", TrackTemplate), ("keyframe", Keyframe))
+            ("track_table", TrackTable), ("track_depth", TrackDepth), ("track_template", TrackTemplate), ("keyframe", Keyframe),
+            ("keyframe_rotation", KeyframeRotation))
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -657,6 +692,9 @@ def load_library():
         L.ofk_keyframe_download.argtypes = [vp, vp, vp, i, vp, vp]
         L.ofk_keyframe_reset.argtypes = [vp, i, vp]
         L.ofk_keyframe_step.argtypes = [vp, C.POINTER(Keyframe), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
+        L.ofk_keyframe_rotation_download.argtypes = [vp, vp]
+        L.ofk_keyframe_rotation_step.argtypes = [vp, C.POINTER(Keyframe), C.POINTER(KeyframeRotation), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i,
+                                                 i, i, vp, vp, vp]
         L.ofk_track_template_download.argtypes = [vp, vp, vp, vp, vp, vp, i, vp]
         L.ofk_track_affine_fit.argtypes = [vp, C.POINTER(TrackTemplate), vp, vp, vp, vp, i, i, i, i, vp, vp]
         L.ofk_track_template_step.argtypes = [vp, C.POINTER(TrackTemplate), vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
@@ -1267,16 +1305,27 @@ class Context:
         with self._lock:
             self._ck(self._L.ofk_keyframe_reset(self._h, int(stream), _p(a)))
 
-    def keyframe_step(self, next_pts, status, counts, sensors, v_uav, solved, step, state, new_counts=None, max_total=None, keyframe=None,
-                      **settings):
-        """ofk_keyframe_step, the stage entry: rules 1-5 on host arrays.  next_pts [B,S,2] f32 ideal next points; status [B,S], counts
-        [B]; sensors [B,28]; v_uav [B,3], solved [B] of the step's record; step [B] the table's step; state: dict(key_xy [B,S,2] f32,
-        member [B,S] u8, state [B,16] f64, istate [B,4] i32); new_counts [B] the re-detected corners (None: none); max_total (default
-        S); the setting a Keyframe or keyframe_setting's keywords.  -> (state, rec [B,32]), new arrays.  Touches no resident state."""
-        kf = keyframe if keyframe is not None else keyframe_setting(**settings)
+    def set_keyframe_rotation(self, rotation=None, **settings):
+        """ofk_set_keyframe_rotation: a KeyframeRotation (or keyframe_rotation_setting's keywords); None or mode False switches it off.
+        Every later stream step with ofk_set_keyframe on (it must be) solves the keyframe's translation together with a correction of
+        the accumulated rotation, under a prior from the source's sigmas."""
+        self._set_struct(self._L.ofk_set_keyframe_rotation, rotation, settings, keyframe_rotation_setting, lock=True)
+
+    def get_keyframe_rotation(self):
+        return self._get_struct(self._L.ofk_get_keyframe_rotation, KeyframeRotation)
+
+    def keyframe_rotation_download(self, batch=None):
+        """ofk_keyframe_rotation_download -> rec [batch,40] of the streams of the latest step with the setting on: delta 0-2, flag 3
+        (KEYROT_*), R^ 4-12, C_delta's upper triangle 13-18, C_T's 19-24, the reduced system's eigenvalues 25-27, the prior's sigmas
+        28-30, Gauss-Newton steps 31, the plain first solve's T 32-34, attitude source used 35, age 36, rows 37."""
+        rec, = self._rows("keyframe_rotation_download", self.max_batch if batch is None else int(batch),
+                          lambda p: self._L.ofk_keyframe_rotation_download(self._h, p), ((KEYROT_DOUBLES,), np.float64))
+        return rec
+
+    def _keyframe_step(self, who, kf, rot, next_pts, status, counts, sensors, v_uav, solved, step, state, new_counts, max_total):
         nn = _arr(next_pts, np.float32)
         if nn.ndim != 3 or nn.shape[2] != 2 or nn.shape[1] < 1:
-            raise ValueError(f"keyframe_step: next_pts {nn.shape} is not [B, S >= 1, 2]")
+            raise ValueError(f"{who}: next_pts {nn.shape} is not [B, S >= 1, 2]")
         B, S = nn.shape[:2]
         st = _arr(status, np.uint8, (B, S)); cn = _arr(counts, np.int32, (B,)); sn = _arr(sensors, np.float64, (B, SENSOR_DOUBLES))
         vu = _arr(v_uav, np.float64, (B, 3)); so = _arr(solved, np.int32, (B,)); sp = _arr(step, np.int32, (B,))
@@ -1284,10 +1333,37 @@ class Context:
         sd = np.array(_arr(state["state"], np.float64, (B, KEY_STATE))); si = np.array(_arr(state["istate"], np.int32, (B, KEY_INTS)))
         nc = _opt(new_counts, np.int32, (B,))
         rec = np.zeros((B, KEY_DOUBLES), np.float64)
+        mt = S if max_total is None else int(max_total)
+        if rot is None:
+            with self._lock:
+                self._ck(self._L.ofk_keyframe_step(self._h, C.byref(kf), _p(nn), _p(st), _p(cn), _p(sn), _p(vu), _p(so), _p(sp), _p(kx), _p(mem),
+                                                   _p(sd), _p(si), _p(nc), mt, B, S, _p(rec)))
+            return dict(key_xy=kx, member=mem, state=sd, istate=si), rec
+        rs = np.zeros((B, KEYROT_STATE), np.float64) if state.get("rstate") is None else np.array(_arr(state["rstate"], np.float64, (B, KEYROT_STATE)))
+        rrec = np.zeros((B, KEYROT_DOUBLES), np.float64)
         with self._lock:
-            self._ck(self._L.ofk_keyframe_step(self._h, C.byref(kf), _p(nn), _p(st), _p(cn), _p(sn), _p(vu), _p(so), _p(sp), _p(kx), _p(mem),
-                                               _p(sd), _p(si), _p(nc), S if max_total is None else int(max_total), B, S, _p(rec)))
-        return dict(key_xy=kx, member=mem, state=sd, istate=si), rec
+            self._ck(self._L.ofk_keyframe_rotation_step(self._h, C.byref(kf), C.byref(rot), _p(nn), _p(st), _p(cn), _p(sn), _p(vu), _p(so), _p(sp),
+                                                        _p(kx), _p(mem), _p(sd), _p(si), _p(nc), mt, B, S, _p(rec), _p(rs), _p(rrec)))
+        return dict(key_xy=kx, member=mem, state=sd, istate=si, rstate=rs), rec, rrec
+
+    def keyframe_step(self, next_pts, status, counts, sensors, v_uav, solved, step, state, new_counts=None, max_total=None, keyframe=None,
+                      **settings):
+        """ofk_keyframe_step, the stage entry: rules 1-5 on host arrays.  next_pts [B,S,2] f32 ideal next points; status [B,S], counts
+        [B]; sensors [B,28]; v_uav [B,3], solved [B] of the step's record; step [B] the table's step; state: dict(key_xy [B,S,2] f32,
+        member [B,S] u8, state [B,16] f64, istate [B,4] i32); new_counts [B] the re-detected corners (None: none); max_total (default
+        S); the setting a Keyframe or keyframe_setting's keywords.  -> (state, rec [B,32]), new arrays.  Touches no resident state."""
+        kf = keyframe if keyframe is not None else keyframe_setting(**settings)
+        return self._keyframe_step("keyframe_step", kf, None, next_pts, status, counts, sensors, v_uav, solved, step, state, new_counts, max_total)
+
+    def keyframe_rotation_step(self, next_pts, status, counts, sensors, v_uav, solved, step, state, new_counts=None, max_total=None,
+                               keyframe=None, rotation=None):
+        """ofk_keyframe_rotation_step, the stage entry: keyframe_step's arguments; state may carry rstate [B,12] f64 (absent: zero, no
+        R_world at the keyframe); keyframe: a Keyframe (None: the defaults), rotation: a KeyframeRotation (None: the defaults).
+        -> (state with rstate, rec [B,32], rrec [B,40]), new arrays.  Touches no resident state."""
+        kf = keyframe if keyframe is not None else keyframe_setting()
+        rot = rotation if rotation is not None else keyframe_rotation_setting()
+        return self._keyframe_step("keyframe_rotation_step", kf, rot, next_pts, status, counts, sensors, v_uav, solved, step, state, new_counts,
+                                   max_total)
 
     def zones_reset(self, batch=None):
         """ofk_zones_reset: the zone tables of the first `batch` streams (all by default) are cleared."""

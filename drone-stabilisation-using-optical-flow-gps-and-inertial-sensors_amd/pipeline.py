@@ -178,6 +178,9 @@ class PipelineConfig:
     # held frame of its track table (which must be on) and reports a position that does not drift with the flow; FlowPipeline
     # ignores it
     keyframe: object = None
+    # keyframe_rotation (ofk.h: ofk_set_keyframe_rotation): None, True (the defaults) or an ofk.KeyframeRotation: the keyframe's solve
+    # refines the accumulated rotation together with the translation; it needs keyframe on
+    keyframe_rotation: object = None
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -313,6 +316,18 @@ class PipelineConfig:
         m = ofk.keyframe_setting(m.mode, m.sigma_flow, m.gate, m.min_rows, m.min_share, m.rot_max, m.max_age)   # range-checked
         return None if m.mode == ofk.KEY_OFF else m
 
+    def keyframe_rotation_setting(self):
+        """The ofk.KeyframeRotation structure of this configuration, None when the rotation is not refined."""
+        if self.keyframe_rotation is None or self.keyframe_rotation is False:
+            return None
+        m = ofk.keyframe_rotation_setting() if self.keyframe_rotation is True else self.keyframe_rotation
+        if not isinstance(m, ofk.KeyframeRotation):
+            raise ValueError(f"keyframe_rotation {m!r} is neither None, True nor an ofk.KeyframeRotation")
+        m = ofk.keyframe_rotation_setting(m.mode, m.source, tuple(m.axes), m.sigma_gyro, m.sigma_bias, m.sigma_att, m.iters, m.delta_max)   # range-checked
+        if m.mode != ofk.KEYROT_OFF and self.keyframe_setting() is None:
+            raise ValueError("keyframe_rotation needs keyframe on")
+        return None if m.mode == ofk.KEYROT_OFF else m
+
     def track_template_setting(self):
         """The ofk.TrackTemplate structure of this configuration, None when the templates are off."""
         if self.track_template is None or self.track_template is False:
@@ -442,7 +457,7 @@ def _apply_settings(ctx, cfg, zones):
     if zones:
         steps += [(ctx.set_zones, cfg.zones_setting), (ctx.set_gyro_bias, cfg.gyro_bias_setting), (ctx.set_track_table, cfg.track_table_setting),
                   (ctx.set_track_depth, cfg.track_depth_setting), (ctx.set_track_template, cfg.track_template_setting),
-                  (ctx.set_keyframe, cfg.keyframe_setting)]
+                  (ctx.set_keyframe, cfg.keyframe_setting), (ctx.set_keyframe_rotation, cfg.keyframe_rotation_setting)]
     steps += [(ctx.set_camera, cfg.camera_setting), (ctx.set_rolling_shutter, cfg.rolling_shutter_setting),
               (ctx.set_finite_motion, cfg.finite_motion_setting)]
     for setter, setting in steps:                                # every *_setting() is None when its setting is off
@@ -581,7 +596,7 @@ class FlowStream:
     def position(self):
         """The streams' position against their keyframes behind the latest step (ofk.h: ofk_set_keyframe): dict(pos, D, T [batch, 3]:
         the position, the displacement since the keyframe and the key solve's translation; flag [batch] (ofk.KEY_SOLVED, _UNSOLVED,
-        _NONE); C_T [batch, 3, 3]; R_acc [batch, 3, 3]; live, members_at_key, key_step, keyframes, dead_reckoned, reason [batch];
+        _NONE); with ofk_set_keyframe_rotation on T, pos and C_T are those of the solve that stands; C_T [batch, 3, 3]; R_acc [batch, 3, 3]; live, members_at_key, key_step, keyframes, dead_reckoned, reason [batch];
         ids: per stream the ids of the keyframe's members among the tracks that step returned, from the track table; rec)."""
         d = self.ctx.keyframe_download(self.batch)
         t = self.ctx.track_table_download(self.batch)
@@ -592,6 +607,15 @@ class FlowStream:
             out[k] = rec[:, s].astype(np.int32)
         out["ids"] = [t["ids"][b, :cnt[b]][d["member"][b, :cnt[b]] != 0] for b in range(self.batch)]
         return out
+
+    def key_rotation(self):
+        """The keyframes' rotation refined from the flow behind the latest step (ofk.h: ofk_set_keyframe_rotation): dict(delta
+        [batch, 3]; R_hat, C_delta [batch, 3, 3]; flag [batch] (ofk.KEYROT_*); prior [batch, 3]: the prior's sigma per axis (0: held);
+        eig [batch, 3]: the reduced system's eigenvalues; iterations [batch]; rec [batch, 40])."""
+        rec = self.ctx.keyframe_rotation_download(self.batch)
+        return dict(delta=rec[:, 0:3].copy(), R_hat=rec[:, 4:13].reshape(-1, 3, 3).copy(), C_delta=ofk.cov_matrix(rec[:, 13:19]),
+                    flag=rec[:, 3].astype(np.int32), prior=rec[:, 28:31].copy(), eig=rec[:, 25:28].copy(), iterations=rec[:, 31].astype(np.int32),
+                    rec=rec)
 
     def begin(self, first_bgr):
         return self.ctx.stream_begin(first_bgr, self._params)

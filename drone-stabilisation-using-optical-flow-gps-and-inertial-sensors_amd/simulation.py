@@ -67,6 +67,13 @@ def keyframe_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None, **kw):
     return step(np.asarray(next_pts, np.float32)[:, :2], sensors, v_uav, state=state, **kw)
 
 
+def keyframe_rotation_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None, **kw):
+    """keyframe_step with the accumulated rotation refined from the flow (ofk.h: ofk_keyframe_rotation_step);
+    velocity_node.keyframe_rotation_step's arguments and returns: (state with rstate, rec [32], rrec [40])."""
+    from .velocity_node import keyframe_rotation_step as step
+    return step(np.asarray(next_pts, np.float32)[:, :2], sensors, v_uav, state=state, **kw)
+
+
 def track_depth_step(x, u, omega, v, state=None, **kw):
     """One step of a stream's depths per track without images (ofk.h: ofk_track_depth_step); velocity_node.track_depth_step's
     arguments and returns: (state dict(rho, var, nobs), rec [32])."""

@@ -126,19 +126,13 @@ def track_depth_step(x, u, omega, v, state=None, status=None, solved=True, new_c
     return {k: a[0, :kept + born].copy() for k, a in out.items()}, rec[0]
 
 
-def keyframe_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None, status=None, solved=True, step=0, new_count=None, max_total=None,
-                  **settings):
-    """One step of a stream's keyframe without images (ofk.h: ofk_keyframe_step): rotate, key solve, position, re-key decision and
-    compaction.  next_pts [n,2]: the ideal next points in pixels; sensors [28]: the step's sensor row; v_uav, solved: the step
-    record's fields 8-10 and its solved flag (the dead reckoning without a key solve); state: the dict(key_xy, member, state, istate)
-    of the previous call (None: no keyframe yet, position zero); status [n] (None: all kept); step: the track table's step;
-    new_count: corners re-detected behind the kept rows; max_total: the most rows the stream holds (None: whatever fits); settings:
-    ofk.keyframe_setting's keywords.
-    Returns (state, rec [32]): the kept rows in order and the appended ones behind them; rec[13:16] is the position, rec[3] the flag."""
+def _keyframe_stage(who, next_pts, sensors, v_uav, state, status, solved, step, new_count, max_total):
+    """What keyframe_step and keyframe_rotation_step hand to their stage entry: the one stream's rows padded to a batch of one with room
+    for the appended rows.  -> (the positional arguments up to the state dict, keywords new_counts / max_total, rows kept + born)."""
     pts = np.asarray(next_pts, np.float32).reshape(-1, 2)
     n = len(pts)
     if n < 1:
-        raise ValueError("keyframe_step: no points")
+        raise ValueError(f"{who}: no points")
     st = np.ones(n, np.uint8) if status is None else (np.asarray(status).reshape(n) != 0).astype(np.uint8)
     kept, born = int(st.sum()), 0 if new_count is None else max(int(new_count), 0)
     S = max(n, kept + born)                                      # room for the appended rows
@@ -155,13 +149,47 @@ def keyframe_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None, status=N
     if state.get("state") is not None:
         sd[0] = np.asarray(state["state"], np.float64).reshape(ofk.KEY_STATE)
     si = np.zeros((1, ofk.KEY_INTS), np.int32) if state.get("istate") is None else np.asarray(state["istate"], np.int32).reshape(1, ofk.KEY_INTS)
-    out, rec = ofk.default_context().keyframe_step(
-        rows(pts, np.float32, 2), rows(st, np.uint8), [n], np.asarray(sensors, np.float64).reshape(1, ofk.SENSOR_DOUBLES), [v_uav],
-        [1 if solved else 0], [int(step)], dict(key_xy=rows(state.get("key_xy"), np.float32, 2), member=rows(state.get("member"), np.uint8),
-                                                  state=sd, istate=si),
-        new_counts=None if new_count is None else [born], max_total=S, **settings)
-    return dict(key_xy=out["key_xy"][0, :kept + born].copy(), member=out["member"][0, :kept + born].copy(), state=out["state"][0].copy(),
-                istate=out["istate"][0].copy()), rec[0]
+    rs = None if state.get("rstate") is None else np.asarray(state["rstate"], np.float64).reshape(1, ofk.KEYROT_STATE)
+    args = (rows(pts, np.float32, 2), rows(st, np.uint8), [n], np.asarray(sensors, np.float64).reshape(1, ofk.SENSOR_DOUBLES), [v_uav],
+            [1 if solved else 0], [int(step)], dict(key_xy=rows(state.get("key_xy"), np.float32, 2), member=rows(state.get("member"), np.uint8),
+                                                      state=sd, istate=si, rstate=rs))
+    return args, dict(new_counts=None if new_count is None else [born], max_total=S), kept + born
+
+
+def _keyframe_state(out, count):
+    """The one stream's state of a stage entry's batch of one: the kept rows in order and the appended ones behind them."""
+    res = dict(key_xy=out["key_xy"][0, :count].copy(), member=out["member"][0, :count].copy(), state=out["state"][0].copy(),
+               istate=out["istate"][0].copy())
+    if "rstate" in out:
+        res["rstate"] = out["rstate"][0].copy()
+    return res
+
+
+def keyframe_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None, status=None, solved=True, step=0, new_count=None, max_total=None,
+                  **settings):
+    """One step of a stream's keyframe without images (ofk.h: ofk_keyframe_step): rotate, key solve, position, re-key decision and
+    compaction.  next_pts [n,2]: the ideal next points in pixels; sensors [28]: the step's sensor row; v_uav, solved: the step
+    record's fields 8-10 and its solved flag (the dead reckoning without a key solve); state: the dict(key_xy, member, state, istate)
+    of the previous call (None: no keyframe yet, position zero); status [n] (None: all kept); step: the track table's step;
+    new_count: corners re-detected behind the kept rows; max_total: the most rows the stream holds (None: whatever fits); settings:
+    ofk.keyframe_setting's keywords.
+    Returns (state, rec [32]): the kept rows in order and the appended ones behind them; rec[13:16] is the position, rec[3] the flag."""
+    args, kw, count = _keyframe_stage("keyframe_step", next_pts, sensors, v_uav, state, status, solved, step, new_count, max_total)
+    out, rec = ofk.default_context().keyframe_step(*args, **kw, **settings)
+    return _keyframe_state(out, count), rec[0]
+
+
+def keyframe_rotation_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None, status=None, solved=True, step=0, new_count=None,
+                           max_total=None, keyframe=None, rotation=None):
+    """keyframe_step with the accumulated rotation refined from the flow (ofk.h: ofk_keyframe_rotation_step).  keyframe_step's
+    arguments; state may also carry rstate [12]; keyframe / rotation: None (the defaults), a dict of ofk.keyframe_setting's /
+    ofk.keyframe_rotation_setting's keywords, or the structures.
+    Returns (state with rstate, rec [32], rrec [40]): rrec[0:3] is the correction, rrec[3] its flag (ofk.KEYROT_*)."""
+    kf = keyframe if isinstance(keyframe, ofk.Keyframe) else ofk.keyframe_setting(**dict(keyframe or {}))
+    rot = rotation if isinstance(rotation, ofk.KeyframeRotation) else ofk.keyframe_rotation_setting(**dict(rotation or {}))
+    args, kw, count = _keyframe_stage("keyframe_rotation_step", next_pts, sensors, v_uav, state, status, solved, step, new_count, max_total)
+    out, rec, rrec = ofk.default_context().keyframe_rotation_step(*args, **kw, keyframe=kf, rotation=rot)
+    return _keyframe_state(out, count), rec[0], rrec[0]
 
 
 def track_template_step(prev, next, prev_pts, next_pts, state=None, status=None, age=None, L=None, new_count=None, max_total=None, **settings):
@@ -287,6 +315,7 @@ class optical_fusion:
     _finite_motion = {}                                          # PipelineConfig's finite_motion field; empty: the solve takes the flow as the instantaneous field
     _track_table = {}                                            # PipelineConfig's track_table field; empty: the tracks are anonymous points
     _track_depth = {}                                            # PipelineConfig's track_depth field; empty: no depth per track
+    _keyframe_rotation = {}                                      # PipelineConfig's keyframe_rotation field; empty: R_acc is taken as exact
     _keyframe = {}                                               # PipelineConfig's keyframe field; empty: no position against a keyframe
     _track_template = {}                                         # PipelineConfig's track_template field; empty: no template per track
     _rolling_shutter = {}                                        # PipelineConfig's rolling_shutter field; empty: every row is taken as exposed at the time stamp
@@ -446,7 +475,7 @@ class optical_fusion:
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
                                  **self._cov, **self._joint, **self._plane, **self._epipolar, **self._zones, **self._camera, **self._rolling_shutter,
                                  **self._finite_motion, **self._gyro_bias, **self._lk_light, **self._track_table, **self._track_depth,
-                                 **self._track_template, **self._keyframe)
+                                 **self._track_template, **self._keyframe, **self._keyframe_rotation)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -497,6 +526,9 @@ class optical_fusion:
             kp = fs.position()
             self.last_keyframe = {k: kp[k][0] for k in ("pos", "D", "T", "flag", "C_T", "R_acc", "live", "members_at_key", "key_step", "keyframes",
                                                         "dead_reckoned", "reason", "ids", "rec")}
+        if self._keyframe_rotation:
+            kq = fs.key_rotation()
+            self.last_keyframe_rotation = {k: kq[k][0] for k in ("delta", "R_hat", "C_delta", "flag", "prior", "eig", "iterations", "rec")}
         if self._track_template:
             tp = fs.templates()
             self.last_track_template = {k: tp[k][0] for k in ("A", "ncc", "flag", "tstate", "ids", "rec")}
@@ -563,7 +595,7 @@ class optical_fusion:
 
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
                  rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None, gyro_bias=None, lk_light=None,
-                 track_table=None, track_depth=None, track_template=None, keyframe=None):
+                 track_table=None, track_depth=None, track_template=None, keyframe=None, keyframe_rotation=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -622,7 +654,11 @@ class optical_fusion:
         keyframe: None (no position against a keyframe), True, an ofk.Keyframe or a dict of ofk.keyframe_setting's keywords, e.g.
         dict(min_share=0.7): the stream then solves its displacement against a held frame and reports a position that does not drift
         with the flow (ofk.h: ofk_set_keyframe); it switches the track table on when track_table is None.  self.last_keyframe is
-        FlowStream.position()'s dictionary for the one stream."""
+        FlowStream.position()'s dictionary for the one stream.
+        keyframe_rotation: None (R_acc is taken as exact), True, an ofk.KeyframeRotation or a dict of ofk.keyframe_rotation_setting's
+        keywords, e.g. dict(sigma_bias=1e-3): the key solve then refines the accumulated rotation with the translation (ofk.h:
+        ofk_set_keyframe_rotation); it needs keyframe.  self.last_keyframe_rotation is FlowStream.key_rotation()'s dictionary for the
+        one stream."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -737,6 +773,14 @@ class optical_fusion:
         else:
             self._keyframe = {}
         self.last_keyframe = None
+        if keyframe_rotation is not None and keyframe_rotation is not False:
+            kq = keyframe_rotation if keyframe_rotation is True or isinstance(keyframe_rotation, ofk.KeyframeRotation) \
+                else ofk.keyframe_rotation_setting(**dict(keyframe_rotation))
+            self._keyframe_rotation = dict(keyframe_rotation=kq)
+            PipelineConfig(**self._keyframe, **self._keyframe_rotation).keyframe_rotation_setting()   # needs the keyframe; fails here
+        else:
+            self._keyframe_rotation = {}
+        self.last_keyframe_rotation = None
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

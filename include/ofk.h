@@ -549,6 +549,89 @@ int ofk_keyframe_step(ofk_ctx *ctx, const ofk_keyframe *k, const float *next_pts
                       const double *sensors, const double *v_uav, const int *solved, const int *step, float *key_xy, uint8_t *member,
                       double *state, int *istate, const int *new_counts, int max_total, int batch, int stride, double *rec);
 
+/* Keyframe rotation: the accumulated rotation refined from the flow.  The key solve of ofk_set_keyframe takes R_acc, the bare product
+ * of the steps' rotations, as exact, and loses about 1.5 d |error of R_acc|: gyro noise, a scale-factor error or a time-stamp offset
+ * all accumulate in it over a keyframe's life.  With this setting on beside ofk_set_keyframe, rule 2 of the keyframe solves the
+ * translation T together with a small rotation delta, R^ = exp([delta]x) R_acc, under a Gaussian prior on delta; rules 1 and 3-5 run
+ * unchanged on the T and R^ that stand, and the keyframe's record and state keep their layout.  Off by default; with it off every
+ * step allocates, launches and returns what it always did.  k_keyframe_step_rot is launched in k_keyframe_step's place, on exactly
+ * the same steps; when every axis is held by the setting alone (axes all 0, or the sigmas of the source all 0) k_keyframe_step itself
+ * runs and state and record are those of the setting off (rotation record: flag OFK_KEYROT_HELD, otherwise zero).
+ * R_acc in the state stays the SOURCE's rotation: every step estimates delta from it afresh, nothing of delta^ is carried forward.
+ * (The key pixels' noise is common to all steps of one keyframe; a recursion over steps that ignores this is overconfident.)
+ * State of the setting's own per stream, rstate [OFK_KEYROT_STATE] f64: R_world at the keyframe (0-8, row-major), 9: 1 = valid, 10:
+ * the key_step it belongs to, 11 unused.  Rule 5 writes it on every re-key (R_world of the step: sn[7..15], under use_imu the IMU
+ * state's rotation; valid = 1; key_step = step + 1); k_keyrot_clear zeroes it, and sets the rotation record to zero with flag
+ * OFK_KEYROT_NONE, where k_keyframe_begin, k_keyframe_replace (the streams with a budget) and k_keyframe_reset run.  A held step
+ * leaves it alone.
+ * Arithmetic, sums over rows, Jacobi: as ofk_set_keyframe states them.  sf = sigma_flow scaling.  In order, in the rules' places:
+ *   1'. Source.  OFK_KEYROT_GYRO: R_acc is rule 1's product.  OFK_KEYROT_ATTITUDE, where members_at_key != 0, rstate is valid and
+ *       its key_step is the keyframe's: R_acc_ij = (Rw_0i K_0j + Rw_1i K_1j) + Rw_2i K_2j, K = R_world at the keyframe, in the
+ *       product's place (it is what rule 5 stores); otherwise the step runs as source gyro, prior included (record 35 says which).
+ *       Prior variance per axis, age = (step + 1) - key_step in f64: gyro age sigma_gyro^2 + (age sigma_bias)(age sigma_bias);
+ *       attitude 2 (sigma_att sigma_att).  Axis k is HELD when axes[k] == 0 or the variance is not > 0; otherwise its prior
+ *       precision in the rows' units is L_k = sf^2 / variance (an infinite variance: 0, the axis is free).
+ *   2'. The first walk under R_acc is rule 2's; it gives the plain T, flag and row count.  Unless the plain flag is 0 the joint
+ *       solve is not attempted (OFK_KEYROT_NONE); with all axes held it is not either (OFK_KEYROT_HELD).  Otherwise, with the row's
+ *       x^ = (a, b), u^, sA under the current R^ = exp([delta]x) R_acc (rule 1's coefficients), to first order in a further rotation
+ *       delta' composed on the left: u^ = sA (T_xy - T_z x^) + B delta', B = [[-ab, 1 + a^2, -b], [-(1 + b^2), ab, a]] (the
+ *       derivative of x^; rotfield's sign for a rotation by +omega).  In the solve's own cross-product rows, p = (a, b, 1),
+ *       N = [p]x^T [p]x = (p.p) I - p p^T, c_k = (B_0k, B_1k, 0), q = (u^, 0), a walk adds to the solve's eleven sums (M, g of
+ *       acc_point) eighteen more: M_Td[i][k] += sA (N c_k)_i, M_dd[k][l] += c_k . (N c_l) (k <= l), g_d[k] += c_k . (N q); every
+ *       product with N is (N_i0 x + N_i1 y).  One Gauss-Newton step from sums with at least min_rows rows: Jacobi of M (it must
+ *       pass the solve's rank rule with rank 3, all sums finite), Mi = M^-1 from it as rule 2 writes C_T, Y = Mi M_Td, t0 = Mi g;
+ *       S_kl = (M_dd_kl + (k == l ? L_k : 0)) - ((M_Td_0k Y_0l + M_Td_1k Y_1l) + M_Td_2k Y_2l), h_k = (g_d_k - L_k delta_k) -
+ *       ((M_Td_0k t0_0 + M_Td_1k t0_1) + M_Td_2k t0_2); a held axis has its row and column of S zero, the diagonal 1 and h 0.
+ *       Jacobi of S; it must be finite with every eigenvalue > 0 and > eps max(3 rows, 3) times the largest, else
+ *       OFK_KEYROT_SINGULAR.  delta' = S^-1 h through the eigenvectors as the solve does; T = t0 - Y delta'; delta += delta'.  No
+ *       6 x 6 is factorised.  `iters` such steps, the first on the first walk's sums, each further one on a walk under the new R^.
+ *       gate > 0: the rows inside are those whose residual r = u^ - sA (T_xy - T_z x^) under the first joint solve's R^ and T has
+ *       r.r <= (gate scaling)^2; over them `iters` further steps starting from the first solve's delta, each on a walk of its own;
+ *       they replace the first solve when every walk had min_rows rows and every step stood.  |delta^| > delta_max:
+ *       OFK_KEYROT_LARGE (not finite: _SINGULAR).  With any flag but OFK_KEYROT_OK the plain rule 2 runs on, gate and all, and gives
+ *       the bits of the setting off.  rms: over the rows of the solve that stands, under its R^ and T, divided by their number.
+ *       C_delta = sf^2 S^-1 (held axes 0); C_T = sf^2 (Mi + Y S^-1 Y^T), the marginal with the rotation's share in it; both of the
+ *       last step of the solve that stands.  The prior is what keeps them honest within one step; like rule 2's C_T they ignore that
+ *       the key pixels' noise is shared across the steps of a keyframe.
+ *   3-5. As ofk_set_keyframe, with R^ in the lever-arm term and in the angle of rule 4 (record 19) where the joint solve stands.
+ *       The state's R_acc is the source's.  Rule 3's D is first formed under R^ and the joint T; one that is not finite withdraws the
+ *       joint solve in front of the plain rule 2 (the rotation's flag OFK_KEYROT_NONE, delta^ and slots 32-34 zero), which then runs
+ *       as with the setting off and refuses the step itself.
+ * The keyframe's record: T, rms, rows (5: the first gated walk's), gated and C_T are those of the solve that stands.
+ * Rotation record, OFK_KEYROT_DOUBLES: 0-2 delta^ (also the refused one under _LARGE; else 0), 3 flag, 4-12 R^ (R_acc where the plain
+ * solve stands), 13-18 C_delta's upper triangle, 19-24 C_T's (the keyframe record's 20-25), 25-27 the eigenvalues of S descending
+ * (a held axis contributes its 1), 28-30 the prior's sigma per axis (0: held, inf: free), 31 Gauss-Newton steps of the solve that
+ * stands (0: plain), 32-34 the plain first solve's T, 35 1 where R_acc came from the attitudes, 36 age, 37 rows of the standing joint
+ * solve's last walk, 38-39 0.
+ * ofk_set_keyframe_rotation: NULL or mode OFK_KEYROT_OFF switches it off.  OFK_E_INVALID, the setting staying as it was: an unknown
+ * mode or source, a sigma that is negative or not finite (sigma_gyro and sigma_bias may be +inf: free), iters outside
+ * 1..OFK_KEYROT_MAX_ITERS, delta_max <= 0 or NaN.  Defaults behind "off": gyro, axes 1 1 1, sigma_gyro 0, sigma_bias 1e-4, sigma_att
+ * 1e-3, iters 2, delta_max 0.1.  OFK_E_INVALID before any launch from a stream step with the setting on and ofk_set_keyframe off.
+ * ofk_keyframe_rotation_download: rec [batch][OFK_KEYROT_DOUBLES] of the streams of the latest step with the setting on.
+ * ofk_keyframe_reset also clears the stream's rotation state.
+ * ofk_keyframe_rotation_step: ofk_keyframe_step's arguments and meaning (it touches no resident state), plus the rotation setting r,
+ * rstate [batch][OFK_KEYROT_STATE] in and out in place and rrec [batch][OFK_KEYROT_DOUBLES] out (may be NULL). */
+#define OFK_KEYROT_OFF        0
+#define OFK_KEYROT_ON         1
+#define OFK_KEYROT_GYRO       0
+#define OFK_KEYROT_ATTITUDE   1
+#define OFK_KEYROT_DOUBLES    40
+#define OFK_KEYROT_STATE      12
+#define OFK_KEYROT_MAX_ITERS  8
+#define OFK_KEYROT_OK         0
+#define OFK_KEYROT_NONE       1
+#define OFK_KEYROT_SINGULAR   2
+#define OFK_KEYROT_LARGE      3
+#define OFK_KEYROT_HELD       4
+typedef struct ofk_keyframe_rotation { int mode; int source; int axes[3]; double sigma_gyro, sigma_bias, sigma_att; int iters; double delta_max; } ofk_keyframe_rotation;
+int ofk_set_keyframe_rotation(ofk_ctx *ctx, const ofk_keyframe_rotation *r);
+int ofk_get_keyframe_rotation(const ofk_ctx *ctx, ofk_keyframe_rotation *r);
+int ofk_keyframe_rotation_download(ofk_ctx *ctx, double *rec);
+int ofk_keyframe_rotation_step(ofk_ctx *ctx, const ofk_keyframe *k, const ofk_keyframe_rotation *r, const float *next_pts,
+                               const uint8_t *status, const int *counts, const double *sensors, const double *v_uav, const int *solved,
+                               const int *step, float *key_xy, uint8_t *member, double *state, int *istate, const int *new_counts,
+                               int max_total, int batch, int stride, double *rec, double *rstate, double *rrec);
+
 /* Camera model: the lens distortion undone on the device before the solve.  The solve stage reads a point as a sample of an ideal
  * pinhole image, x = (px - cx) * scaling (sensors[19..21]); the reference's camera is a wide-angle module whose lens moves a point by
  * tens of pixels at the border.  With ofk_set_camera on, the resident chains keep everything that lives in the image on the raw
