@@ -207,6 +207,8 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     return OFK_OK;
 }
 
+static void track_free(ofk_ctx *c);                             // the per-track states' allocations (TRACK[], below)
+
 extern "C" int ofk_destroy(ofk_ctx *c)
 {
     if (!c) return OFK_OK;
@@ -217,8 +219,9 @@ extern "C" int ofk_destroy(ofk_ctx *c)
     void *ptrs[] = {c->eig, c->mask, c->deriv, c->cand, c->cand_seg, c->seg_count, c->cand_count, c->sel_hist, c->sel_keys, c->maxbits, c->pts_prev, c->pts_next, c->status, c->err,
                     c->counts, c->sensors, c->records, c->dev_flags, c->scratch, c->pts_new, c->new_counts, c->limit,
                     c->imu_state, c->imu_dv, c->kf_mats, c->kf_x, c->kf_P, c->fused, c->imu_msgs, c->imu_counts, c->rob_work, c->pts_back, c->grid_stats, c->cov_rec, c->joint_rec, c->bias_rec, c->plane_rec, c->epi_rec,
-                    c->zone_tab, c->pts_prev_u, c->ttr.ids, c->tdr.rho, c->tpr.tmpl[0], c->kfr.key_xy, c->kr_st};
+                    c->zone_tab, c->pts_prev_u};
     for (void *p : ptrs) if (p) hipFree(p);
+    track_free(c);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
     if (c->ev) { for (int i = 0; i < c->ev_cap; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]); free(c->ev); }
@@ -2449,6 +2452,152 @@ extern "C" int ofk_zones_step(ofk_ctx *c, const float *old_pts, const float *new
     return d2h(c, mask_out, c->mask, c->img_stride, (size_t)h * w, batch);
 }
 
+// ------------------------------------------------------------------------------------------------ the per-track states of a stream
+// One row per state that a stream keeps per track, in the order in which a step begins them (the keyframe in front of its rotation: a
+// keyframe that begins afresh takes the rotation state with it).  Each state lives in ONE lazy allocation, cleared when it is made and
+// carved into the arrays of its list; the first array owns it.
+struct track_array { size_t at, row, stream; };                  // where ofk_ctx holds the pointer; its bytes per row of the table, per stream
+#define TRACK_ARRAY(member, row, stream) {offsetof(ofk_ctx, member), (size_t)(row), (size_t)(stream)}
+#define TRACK_LIST(a) a, (int)(sizeof(a) / sizeof(a[0]))
+static int tp_stride_of(int win) { return (int)up((size_t)(win + 2) * (win + 2), 4); }
+static const track_array TT_ARRAYS[] = {TRACK_ARRAY(ttr.ids, 4, 0), TRACK_ARRAY(ttr.age, 4, 0), TRACK_ARRAY(ttr.birth_step, 4, 0), TRACK_ARRAY(ttr.birth_xy, 8, 0),
+    TRACK_ARRAY(ttr.flow_xy, 8, 0), TRACK_ARRAY(ttr.step_ids, 4, 0), TRACK_ARRAY(ttr.head, 0, 8), TRACK_ARRAY(ttr.stats, 0, OFK_TT_STATS * 4)};
+static const track_array TD_ARRAYS[] = {TRACK_ARRAY(tdr.rho, 8, 0), TRACK_ARRAY(tdr.var, 8, 0), TRACK_ARRAY(tdr.nobs, 4, 0), TRACK_ARRAY(tdr.rec, 0, OFK_TD_DOUBLES * 8)};
+static const track_array TP_ARRAYS[] = {                         // the templates of the widest window
+    TRACK_ARRAY(tpr.tmpl[0], tp_stride_of(31), 0), TRACK_ARRAY(tpr.tmpl[1], tp_stride_of(31), 0), TRACK_ARRAY(tpr.A, 16, 0), TRACK_ARRAY(tpr.A_new, 16, 0),
+    TRACK_ARRAY(tpr.ncc, 4, 0), TRACK_ARRAY(tpr.ncc_new, 4, 0), TRACK_ARRAY(tpr.move, 4, 0), TRACK_ARRAY(tpr.flag, 1, 0), TRACK_ARRAY(tpr.flag_new, 1, 0),
+    TRACK_ARRAY(tpr.tstate, 1, 0), TRACK_ARRAY(tpr.L, 0, 16), TRACK_ARRAY(tpr.rec, 0, OFK_TPL_DOUBLES * 8)};
+static const track_array KF_ARRAYS[] = {TRACK_ARRAY(kfr.key_xy, 8, 0), TRACK_ARRAY(kfr.member, 1, 0), TRACK_ARRAY(kfr.st, 0, OFK_KEY_STATE * 8),
+    TRACK_ARRAY(kfr.ist, 0, OFK_KEY_INTS * 4), TRACK_ARRAY(kfr.rec, 0, OFK_KEY_DOUBLES * 8), TRACK_ARRAY(kfr.next_copy, 8, 0)};
+static const track_array KR_ARRAYS[] = {TRACK_ARRAY(kr_st, 0, OFK_KEYROT_STATE * 8), TRACK_ARRAY(kr_rec, 0, OFK_KEYROT_DOUBLES * 8)};
+
+enum { TS_TABLE, TS_DEPTH, TS_TEMPLATE, TS_KEY, TS_KEYROT };
+struct track_state {
+    const char *set, *download, *began;                          // the setter's and the download's names, "run" / "stepped": for messages
+    bool (*on)(const ofk_ctx *);
+    int ofk_ctx::*batch, ofk_ctx::*live;                         // streams of the latest begin / step with it on; streams whose rows match their tracks
+    const track_array *arrays; int narrays;
+    int (*begin)(ofk_ctx *, int B);                              // what a state that is not live queues to begin afresh
+    void (*replace)(ofk_ctx *, int B);                           // beside k_replace_tracks; NULL: nothing
+    int needs; const char *why;                                  // the state it is refused without (-1: none), and the refusal's last clause
+    const char *model;                                           // not NULL: the sensor model only; what the refusal calls it
+};
+static const track_state TRACK[] = {
+    {"ofk_set_track_table", "ofk_track_table_download", "run", [](const ofk_ctx *c) { return c->tt.mode != OFK_TT_OFF; },
+     &ofk_ctx::tt_batch, &ofk_ctx::tt_live, TRACK_LIST(TT_ARRAYS),
+     [](ofk_ctx *c, int B) -> int { ofk_launch_track_table_begin(c->stream, c->ttr, c->pts_prev, c->counts, c->max_pts, B); return OFK_OK; },
+     [](ofk_ctx *c, int B) { ofk_launch_track_table_replace(c->stream, c->ttr, c->limit, c->pts_new, c->new_counts, c->max_pts, B); }, -1, nullptr, nullptr},
+    {"ofk_set_track_depth", "ofk_track_depth_download", "stepped", [](const ofk_ctx *c) { return c->td.mode != OFK_TD_OFF; },
+     &ofk_ctx::td_batch, &ofk_ctx::td_live, TRACK_LIST(TD_ARRAYS),
+     [](ofk_ctx *c, int B) -> int { ofk_launch_track_depth_begin(c->stream, c->tdr, c->counts, c->max_pts, B); return OFK_OK; },
+     [](ofk_ctx *c, int B) { ofk_launch_track_depth_replace(c->stream, c->tdr, c->limit, c->new_counts, c->max_pts, B); },
+     TS_TABLE, "the depths are kept per row of the table", "depth per track"},
+    {"ofk_set_track_template", "ofk_track_template_download", "stepped", [](const ofk_ctx *c) { return c->tpl.mode != OFK_TPL_OFF; },
+     &ofk_ctx::tp_batch, &ofk_ctx::tp_live, TRACK_LIST(TP_ARRAYS),
+     [](ofk_ctx *c, int) -> int {                                // none (tstate 0); rows of age 0 are captured anew whatever replaced them
+         OFK_HIP(c, hipMemsetAsync(c->tpr.tstate, 0, (size_t)c->max_batch * c->max_pts, c->stream));
+         OFK_HIP(c, hipMemsetAsync(c->tpr.rec, 0, (size_t)c->max_batch * OFK_TPL_DOUBLES * 8, c->stream));
+         c->tpr.cur = 0; c->tpr.tstride = tp_stride_of(c->tpl.win);
+         return OFK_OK;
+     },
+     nullptr, TS_TABLE, "the templates are kept per row of the table", nullptr},
+    {"ofk_set_keyframe", "ofk_keyframe_download", "stepped", [](const ofk_ctx *c) { return c->key.mode != OFK_KEY_OFF; },
+     &ofk_ctx::kf_batch, &ofk_ctx::kf_live, TRACK_LIST(KF_ARRAYS),
+     [](ofk_ctx *c, int B) -> int { ofk_launch_keyframe_begin(c->stream, c->kfr, c->counts, c->max_pts, B); c->kr_live = 0; return OFK_OK; },
+     [](ofk_ctx *c, int B) { ofk_launch_keyframe_replace(c->stream, c->kfr, c->limit, c->new_counts, c->max_pts, B); },
+     TS_TABLE, "the keyframe is kept per row of the table", "keyframe"},
+    {"ofk_set_keyframe_rotation", "ofk_keyframe_rotation_download", "stepped", [](const ofk_ctx *c) { return c->krot.mode != OFK_KEYROT_OFF; },
+     &ofk_ctx::kr_batch, &ofk_ctx::kr_live, TRACK_LIST(KR_ARRAYS),     // in step with the keyframe's: cleared where that began afresh
+     [](ofk_ctx *c, int B) -> int { ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, nullptr, 0, OFK_KEYROT_NONE, B); return OFK_OK; },
+     [](ofk_ctx *c, int B) { ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, c->limit, 0, OFK_KEYROT_NONE, B); },
+     TS_KEY, "it refines the keyframe's rotation", nullptr},
+};
+
+static void *&track_slot(ofk_ctx *c, const track_array &a) { return *(void **)((char *)c + a.at); }
+static void track_free(ofk_ctx *c)
+{
+    for (const track_state &s : TRACK) if (track_slot(c, s.arrays[0])) hipFree(track_slot(c, s.arrays[0]));
+}
+// the state's arrays over max_batch streams of max_pts rows, allocated (and cleared) by the first begin or step with the setting on
+static int track_alloc(ofk_ctx *c, const track_state &s)
+{
+    if (track_slot(c, s.arrays[0])) return OFK_OK;
+    const size_t np = (size_t)c->max_batch * c->max_pts;
+    auto bytes_of = [&](const track_array &a) { return up(np * a.row + c->max_batch * a.stream, 256); };
+    size_t bytes = 0;
+    for (int i = 0; i < s.narrays; ++i) bytes += bytes_of(s.arrays[i]);
+    uint8_t *base = nullptr;
+    OFK_HIP(c, hipMalloc((void **)&base, bytes));
+    for (int i = 0; i < s.narrays; ++i) { track_slot(c, s.arrays[i]) = base; base += bytes_of(s.arrays[i]); }   // the context owns it from here on
+    OFK_HIP(c, hipMemsetAsync(track_slot(c, s.arrays[0]), 0, bytes, c->stream));
+    return OFK_OK;
+}
+// the state for the current tracks of the first B streams: begun afresh unless it is live already
+static int track_begin(ofk_ctx *c, const track_state &s, int B)
+{
+    TRY(track_alloc(c, s));
+    if (c->*s.live != B) TRY(s.begin(c, B));
+    c->*s.batch = c->*s.live = B;
+    return OFK_OK;
+}
+// The steps' own refusals with a state on (ofk.h), in their precedence; fu: a fused step's.
+static int track_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const char *who)
+{
+    static const int order[] = {TS_DEPTH, TS_TEMPLATE, TS_KEYROT, TS_KEY};
+    for (int k : order) {
+        const track_state &s = TRACK[k];
+        if (!s.on(c)) continue;
+        if (!TRACK[s.needs].on(c)) return ofk_fail(c, OFK_E_INVALID, "%s: %s is on without %s: %s", who, s.set, TRACK[s.needs].set, s.why);
+        if (s.model && (variant == OFK_SOLVE_OFMODULE || (fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY))))
+            return refuse_not_sensor_model(c, who, NO_OFMODULE | NO_ROTATIONAL | NO_LEGACY, s.model, s.set);
+    }
+    return OFK_OK;
+}
+// What a download of a state begins with: refused before any begin or step with the setting on, and for rows without a stride.
+static int track_download_begin(ofk_ctx *c, const track_state &s, bool rows, int stride)
+{
+    if (c->*s.batch < 1 || !track_slot(c, s.arrays[0])) return ofk_fail(c, OFK_E_INVALID, "%s: no stream has %s with %s on yet", s.download, s.began, s.set);
+    if (rows && stride < 1) return ofk_fail(c, OFK_E_INVALID, "%s: stride %d", s.download, stride);
+    return enter(c);
+}
+// ... and ends with: per row {dst (NULL: skipped), src, bytes per element}, the first min(stride, max_pts) rows of B streams into a host
+// pitch of `stride` elements; pitch != 0: one element per stream out of a device pitch of that many bytes (a record, or its head)
+struct download_row { void *dst; const void *src; size_t el, pitch; };
+static int rows_download(ofk_ctx *c, int B, int stride, const download_row *rows, int n)
+{
+    const size_t k = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    for (int i = 0; i < n; ++i) {
+        const download_row &r = rows[i];
+        if (!r.dst) continue;
+        if (!r.pitch) OFK_HIP(c, hipMemcpy2DAsync(r.dst, (size_t)stride * r.el, r.src, mp * r.el, k * r.el, B, hipMemcpyDeviceToHost, c->stream));
+        else if (r.pitch == r.el) OFK_HIP(c, hipMemcpyAsync(r.dst, r.src, (size_t)B * r.el, hipMemcpyDeviceToHost, c->stream));
+        else OFK_HIP(c, hipMemcpy2DAsync(r.dst, r.el, r.src, r.pitch, r.el, B, hipMemcpyDeviceToHost, c->stream));
+    }
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+// What the stage entries stage on the host and fetch back.  host_buf frees a temporary where its entry returns.
+struct host_buf { void *p; ~host_buf() { free(p); } };
+// the step's records as the kernels read them: v in slots v0 .. v0 + 2, solved in 15; NULL: out of host memory
+static double *stage_step_records(const double *v, const int *solved, size_t B, int v0)
+{
+    double *h = (double *)calloc(B * OFK_RECORD_DOUBLES, 8);
+    for (size_t b = 0; h && b < B; ++b) {
+        for (int k = 0; k < 3; ++k) h[b * OFK_RECORD_DOUBLES + v0 + k] = v[3 * b + k];
+        h[b * OFK_RECORD_DOUBLES + 15] = solved[b] ? 1.0 : 0.0;
+    }
+    return h;
+}
+struct back_row { void *dst; const void *src; size_t bytes; };   // dst NULL: skipped
+static int fetch_back(ofk_ctx *c, const char *who, const back_row *rows, int n)
+{
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n && e == hipSuccess; ++i)
+        if (rows[i].dst) e = hipMemcpyAsync(rows[i].dst, rows[i].src, rows[i].bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    return e == hipSuccess ? OFK_OK : ofk_fail(c, OFK_E_HIP, "%s: download failed: %s", who, hipGetErrorString(e));
+}
+
 // ------------------------------------------------------------------------------------------------ track table
 static int check_tt(ofk_ctx *c, const ofk_track_table *t, const char *who)
 {
@@ -2467,47 +2616,15 @@ extern "C" int ofk_set_track_table(ofk_ctx *c, const ofk_track_table *t)
 }
 extern "C" int ofk_get_track_table(const ofk_ctx *c, ofk_track_table *t) { return setting_get(c, &ofk_ctx::tt, t); }
 
-// the table's arrays over `np` rows and `batch` streams carved out of base (NULL: nothing is carved); returns the bytes they take
-static size_t tt_carve(ofk_tt_rows &t, uint8_t *base, size_t np, size_t batch)
-{
-    size_t o = 0;
-    auto take = [&](size_t bytes) { uint8_t *p = base ? base + o : nullptr; o += up(bytes, 256); return p; };
-    t.ids = (unsigned *)take(np * 4); t.age = (int *)take(np * 4); t.birth_step = (int *)take(np * 4);
-    t.birth_xy = (float *)take(np * 8); t.flow_xy = (float *)take(np * 8); t.step_ids = (unsigned *)take(np * 4);
-    t.head = (int *)take(batch * 8); t.stats = (int *)take(batch * OFK_TT_STATS * 4);
-    return o;
-}
-// the resident table, allocated (and cleared) when a stream first begins or steps with the setting on
-static int tt_alloc(ofk_ctx *c)
-{
-    if (c->ttr.ids) return OFK_OK;                               // one allocation, carved into the eight arrays
-    ofk_tt_rows t;
-    const size_t np = (size_t)c->max_batch * c->max_pts, bytes = tt_carve(t, nullptr, np, (size_t)c->max_batch);
-    uint8_t *base = nullptr;
-    OFK_HIP(c, hipMalloc((void **)&base, bytes));
-    OFK_HIP(c, hipMemsetAsync(base, 0, bytes, c->stream));
-    tt_carve(c->ttr, base, np, (size_t)c->max_batch);
-    return OFK_OK;
-}
-static bool tt_on(const ofk_ctx *c) { return c->tt.mode != OFK_TT_OFF; }
-
 extern "C" int ofk_track_table_download(ofk_ctx *c, uint32_t *ids, int *age, int *birth_step, float *birth_xy, float *flow_xy, uint32_t *step_ids,
                                         int stride, int *stats)
 {
     if (!c) return OFK_E_INVALID;
-    if (c->tt_batch < 1 || !c->ttr.ids) return ofk_fail(c, OFK_E_INVALID, "ofk_track_table_download: no stream has run with ofk_set_track_table on yet");
-    if ((ids || age || birth_step || birth_xy || flow_xy || step_ids) && stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_track_table_download: stride %d", stride);
-    TRY(enter(c));
-    const int B = c->tt_batch;
-    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    TRY(track_download_begin(c, TRACK[TS_TABLE], ids || age || birth_step || birth_xy || flow_xy || step_ids, stride));
     const ofk_tt_rows &t = c->ttr;
-    struct { void *dst; const void *src; size_t el; } rows[] = {{ids, t.ids, 4}, {age, t.age, 4}, {birth_step, t.birth_step, 4}, {birth_xy, t.birth_xy, 8},
-                                                                 {flow_xy, t.flow_xy, 8}, {step_ids, t.step_ids, 4}};
-    for (const auto &r : rows)
-        if (r.dst) OFK_HIP(c, hipMemcpy2DAsync(r.dst, (size_t)stride * r.el, r.src, mp * r.el, n * r.el, B, hipMemcpyDeviceToHost, c->stream));
-    if (stats) OFK_HIP(c, hipMemcpyAsync(stats, t.stats, (size_t)B * OFK_TT_STATS * 4, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
+    const download_row rows[] = {{ids, t.ids, 4, 0}, {age, t.age, 4, 0}, {birth_step, t.birth_step, 4, 0}, {birth_xy, t.birth_xy, 8, 0},
+                                 {flow_xy, t.flow_xy, 8, 0}, {step_ids, t.step_ids, 4, 0}, {stats, t.stats, OFK_TT_STATS * 4, OFK_TT_STATS * 4}};
+    return rows_download(c, c->tt_batch, stride, rows, 7);
 }
 
 // rules 3 and 6 on host buffers: device scratch only
@@ -2541,21 +2658,14 @@ extern "C" int ofk_track_table_step(ofk_ctx *c, const ofk_track_table *set, uint
     const bool seed = set && set->mode != OFK_TT_OFF && set->seed == OFK_TT_SEED_FLOW;
     ofk_launch_track_table_update(c->stream, t, d_prev, d_next, d_st, d_cnt, stride, d_new, d_nc, max_total, seed ? 1 : 0, seed ? (float)set->gain : 0.f, batch);
     TRY(check_launch(c, "k_track_table_update"));
-    int *h_stats = (int *)malloc((size_t)batch * OFK_TT_STATS * 4);
+    const host_buf h = {malloc((size_t)batch * OFK_TT_STATS * 4)};
+    const int *h_stats = (const int *)h.p;
     if (!h_stats) return ofk_fail(c, OFK_E_INVALID, "%s: out of host memory", who);
-    struct { void *dst; const void *src; size_t bytes; } back[] = {{ids, t.ids, np * 4}, {age, t.age, np * 4}, {birth_step, t.birth_step, np * 4},
-        {birth_xy, t.birth_xy, np * 8}, {flow_xy, t.flow_xy, np * 8}, {step_ids, t.step_ids, np * 4}, {head, t.head, (size_t)batch * 8},
-        {h_stats, t.stats, (size_t)batch * OFK_TT_STATS * 4}};
-    hipError_t e = hipSuccess;
-    for (const auto &r : back)
-        if (r.dst && e == hipSuccess) e = hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) {
-        for (int b = 0; b < batch; ++b) counts[b] = h_stats[(size_t)b * OFK_TT_STATS];
-        if (stats) memcpy(stats, h_stats, (size_t)batch * OFK_TT_STATS * 4);
-    }
-    free(h_stats);
-    if (e != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: download failed: %s", who, hipGetErrorString(e));
+    const back_row back[] = {{ids, t.ids, np * 4}, {age, t.age, np * 4}, {birth_step, t.birth_step, np * 4}, {birth_xy, t.birth_xy, np * 8},
+        {flow_xy, t.flow_xy, np * 8}, {step_ids, t.step_ids, np * 4}, {head, t.head, (size_t)batch * 8}, {h.p, t.stats, (size_t)batch * OFK_TT_STATS * 4}};
+    TRY(fetch_back(c, who, back, 8));
+    for (int b = 0; b < batch; ++b) counts[b] = h_stats[(size_t)b * OFK_TT_STATS];
+    if (stats) memcpy(stats, h_stats, (size_t)batch * OFK_TT_STATS * 4);
     return OFK_OK;
 }
 
@@ -2603,64 +2713,13 @@ extern "C" int ofk_set_track_depth(ofk_ctx *c, const ofk_track_depth *t)
 }
 extern "C" int ofk_get_track_depth(const ofk_ctx *c, ofk_track_depth *t) { return setting_get(c, &ofk_ctx::td, t); }
 
-static bool td_on(const ofk_ctx *c) { return c->td.mode != OFK_TD_OFF; }
-
-// the state's arrays over `np` rows and the records of `batch` streams carved out of base (NULL: nothing is carved); returns the bytes
-static size_t td_carve(ofk_td_rows &t, uint8_t *base, size_t np, size_t batch)
-{
-    size_t o = 0;
-    auto take = [&](size_t bytes) { uint8_t *p = base ? base + o : nullptr; o += up(bytes, 256); return p; };
-    t.rho = (double *)take(np * 8); t.var = (double *)take(np * 8); t.nobs = (int *)take(np * 4); t.rec = (double *)take(batch * OFK_TD_DOUBLES * 8);
-    return o;
-}
-// the resident state, allocated (and cleared) by the first step with the setting on
-static int td_alloc(ofk_ctx *c)
-{
-    if (c->tdr.rho) return OFK_OK;                               // one allocation, carved into the four arrays
-    ofk_td_rows t;
-    const size_t np = (size_t)c->max_batch * c->max_pts, bytes = td_carve(t, nullptr, np, (size_t)c->max_batch);
-    uint8_t *base = nullptr;
-    OFK_HIP(c, hipMalloc((void **)&base, bytes));
-    OFK_HIP(c, hipMemsetAsync(base, 0, bytes, c->stream));
-    td_carve(c->tdr, base, np, (size_t)c->max_batch);
-    return OFK_OK;
-}
-
-// The steps' own refusals with the setting on (ofk.h); fu: a fused step's.
-static int td_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const char *who)
-{
-    if (!td_on(c)) return OFK_OK;
-    if (c->tt.mode == OFK_TT_OFF)
-        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_track_depth is on without ofk_set_track_table: the depths are kept per row of the table", who);
-    if (variant == OFK_SOLVE_OFMODULE || (fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY)))
-        return refuse_not_sensor_model(c, who, NO_OFMODULE | NO_ROTATIONAL | NO_LEGACY, "depth per track", "ofk_set_track_depth");
-    return OFK_OK;
-}
-
-// depths for the current tracks of the first B streams: zeroed rows unless they are live already
-static int td_begin(ofk_ctx *c, int B)
-{
-    TRY(td_alloc(c));
-    if (c->td_live != B) ofk_launch_track_depth_begin(c->stream, c->tdr, c->counts, c->max_pts, B);
-    c->td_batch = c->td_live = B;
-    return OFK_OK;
-}
-
 extern "C" int ofk_track_depth_download(ofk_ctx *c, double *rho, double *var, int *nobs, int stride, double *rec)
 {
     if (!c) return OFK_E_INVALID;
-    if (c->td_batch < 1 || !c->tdr.rho) return ofk_fail(c, OFK_E_INVALID, "ofk_track_depth_download: no stream has stepped with ofk_set_track_depth on yet");
-    if ((rho || var || nobs) && stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_track_depth_download: stride %d", stride);
-    TRY(enter(c));
-    const int B = c->td_batch;
-    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    TRY(track_download_begin(c, TRACK[TS_DEPTH], rho || var || nobs, stride));
     const ofk_td_rows &t = c->tdr;
-    struct { void *dst; const void *src; size_t el; } rows[] = {{rho, t.rho, 8}, {var, t.var, 8}, {nobs, t.nobs, 4}};
-    for (const auto &r : rows)
-        if (r.dst) OFK_HIP(c, hipMemcpy2DAsync(r.dst, (size_t)stride * r.el, r.src, mp * r.el, n * r.el, B, hipMemcpyDeviceToHost, c->stream));
-    if (rec) OFK_HIP(c, hipMemcpyAsync(rec, t.rec, (size_t)B * OFK_TD_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
+    const download_row rows[] = {{rho, t.rho, 8, 0}, {var, t.var, 8, 0}, {nobs, t.nobs, 4, 0}, {rec, t.rec, OFK_TD_DOUBLES * 8, OFK_TD_DOUBLES * 8}};
+    return rows_download(c, c->td_batch, stride, rows, 4);
 }
 
 extern "C" int ofk_track_depth_reset(ofk_ctx *c, int b, const double *rho, const double *var, const int *nobs, int n)
@@ -2673,7 +2732,7 @@ extern "C" int ofk_track_depth_reset(ofk_ctx *c, int b, const double *rho, const
     for (int i = 0; i < n; ++i)
         if (nobs[i] < 0) return ofk_fail(c, OFK_E_INVALID, "%s: nobs[%d] = %d is negative", who, i, nobs[i]);
     TRY(enter(c));
-    TRY(td_begin(c, c->stream_batch));
+    TRY(track_begin(c, TRACK[TS_DEPTH], c->stream_batch));
     const size_t o = (size_t)b * c->max_pts;
     if (n) {
         OFK_HIP(c, hipMemcpyAsync(c->tdr.rho + o, rho, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
@@ -2699,15 +2758,10 @@ extern "C" int ofk_track_depth_step(ofk_ctx *c, const ofk_track_depth *set, cons
     TRY(check_td(c, set, who));
     TRY(check_counts(c, who, counts, batch, stride));
     const size_t np = (size_t)batch * stride, B = (size_t)batch;
-    double *h_rec = (double *)calloc(B * OFK_RECORD_DOUBLES, 8);   // the step's records as the kernel reads them: v, solved
-    if (!h_rec) return ofk_fail(c, OFK_E_INVALID, "%s: out of host memory", who);
-    for (size_t b = 0; b < B; ++b) {
-        for (int k = 0; k < 3; ++k) h_rec[b * OFK_RECORD_DOUBLES + k] = v[3 * b + k];
-        h_rec[b * OFK_RECORD_DOUBLES + 15] = solved[b] ? 1.0 : 0.0;
-    }
+    const host_buf h_rec = {stage_step_records(v, solved, B, 0)};
+    if (!h_rec.p) return ofk_fail(c, OFK_E_INVALID, "%s: out of host memory", who);
     Bump bp;
-    int rc = est_begin(c, np * 53 + B * (OFK_RECORD_DOUBLES * 8 + OFK_TD_DOUBLES * 8 + 32) + 16 * 256, bp);
-    if (rc != OFK_OK) { free(h_rec); return rc; }
+    TRY(est_begin(c, np * 53 + B * (OFK_RECORD_DOUBLES * 8 + OFK_TD_DOUBLES * 8 + 32) + 16 * 256, bp));
     ofk_td_rows t;
     t.rho = bp.put(rho, np * 8); t.var = bp.put(var, np * 8); t.nobs = (int *)bp.put(nobs, np * 4); t.rec = bp.take(B * OFK_TD_DOUBLES * 8);
     ofk_td_in in = {};
@@ -2715,18 +2769,12 @@ extern "C" int ofk_track_depth_step(ofk_ctx *c, const ofk_track_depth *set, cons
     in.counts = (const int *)bp.put(counts, B * 4); in.stride = stride;
     in.new_counts = (const int *)bp.put(new_counts, B * 4); in.max_total = max_total;
     in.omega = bp.put(omega, B * 24); in.omega_stride = 3;
-    in.v = bp.put(h_rec, B * OFK_RECORD_DOUBLES * 8); in.plain = 0;
-    hipError_t e = bp.rc == OFK_OK ? hipStreamSynchronize(c->stream) : hipErrorUnknown;   // h_rec has been read
-    free(h_rec);
-    if (e != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    in.v = bp.put(h_rec.p, B * OFK_RECORD_DOUBLES * 8); in.plain = 0;
+    if (bp.rc != OFK_OK || hipStreamSynchronize(c->stream) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
     ofk_launch_track_depth_step(c->stream, t, in, set, batch);
     TRY(check_launch(c, "k_track_depth_step"));
-    OFK_HIP(c, hipMemcpyAsync(rho, t.rho, np * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipMemcpyAsync(var, t.var, np * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipMemcpyAsync(nobs, t.nobs, np * 4, hipMemcpyDeviceToHost, c->stream));
-    if (rec) OFK_HIP(c, hipMemcpyAsync(rec, t.rec, B * OFK_TD_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
+    const back_row back[] = {{rho, t.rho, np * 8}, {var, t.var, np * 8}, {nobs, t.nobs, np * 4}, {rec, t.rec, B * OFK_TD_DOUBLES * 8}};
+    return fetch_back(c, who, back, 4);
 }
 
 // ------------------------------------------------------------------------------------------------ track templates
@@ -2756,71 +2804,16 @@ extern "C" int ofk_set_track_template(ofk_ctx *c, const ofk_track_template *t)
 }
 extern "C" int ofk_get_track_template(const ofk_ctx *c, ofk_track_template *t) { return setting_get(c, &ofk_ctx::tpl, t); }
 
-static bool tp_on(const ofk_ctx *c) { return c->tpl.mode != OFK_TPL_OFF; }
-static int tp_stride_of(int win) { return (int)up((size_t)(win + 2) * (win + 2), 4); }
-
-// the state's arrays over `np` rows of `ts` template bytes and the records of `batch` streams carved out of base (NULL: nothing is carved)
-static size_t tp_carve(ofk_tp_rows &t, uint8_t *base, size_t np, size_t batch, size_t ts)
-{
-    size_t o = 0;
-    auto take = [&](size_t bytes) { uint8_t *p = base ? base + o : nullptr; o += up(bytes, 256); return p; };
-    t.tmpl[0] = take(np * ts); t.tmpl[1] = take(np * ts);
-    t.A = (float *)take(np * 16); t.A_new = (float *)take(np * 16);
-    t.ncc = (float *)take(np * 4); t.ncc_new = (float *)take(np * 4); t.move = (float *)take(np * 4);
-    t.flag = take(np); t.flag_new = take(np); t.tstate = take(np);
-    t.L = (float *)take(batch * 16); t.rec = (double *)take(batch * OFK_TPL_DOUBLES * 8);
-    return o;
-}
-static int tp_alloc(ofk_ctx *c)
-{
-    if (c->tpr.tmpl[0]) return OFK_OK;                           // one allocation for the widest window, carved into the arrays
-    ofk_tp_rows t;
-    const size_t np = (size_t)c->max_batch * c->max_pts, ts = (size_t)tp_stride_of(31), bytes = tp_carve(t, nullptr, np, (size_t)c->max_batch, ts);
-    uint8_t *base = nullptr;
-    OFK_HIP(c, hipMalloc((void **)&base, bytes));
-    tp_carve(c->tpr, base, np, (size_t)c->max_batch, ts);          // the context owns it from here on, whatever follows
-    OFK_HIP(c, hipMemsetAsync(base, 0, bytes, c->stream));
-    return OFK_OK;
-}
-
-static int tp_check_step(ofk_ctx *c, const char *who)
-{
-    if (tp_on(c) && c->tt.mode == OFK_TT_OFF)
-        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_track_template is on without ofk_set_track_table: the templates are kept per row of the table", who);
-    return OFK_OK;
-}
-
-// templates for the current tracks of the first B streams: none (tstate 0) unless they are live already
-static int tp_begin(ofk_ctx *c, int B)
-{
-    TRY(tp_alloc(c));
-    if (c->tp_live != B) {
-        OFK_HIP(c, hipMemsetAsync(c->tpr.tstate, 0, (size_t)c->max_batch * c->max_pts, c->stream));
-        OFK_HIP(c, hipMemsetAsync(c->tpr.rec, 0, (size_t)c->max_batch * OFK_TPL_DOUBLES * 8, c->stream));
-        c->tpr.cur = 0; c->tpr.tstride = tp_stride_of(c->tpl.win);
-    }
-    c->tp_batch = c->tp_live = B;
-    return OFK_OK;
-}
-
 extern "C" int ofk_track_template_download(ofk_ctx *c, uint8_t *tmpl, float *A, float *ncc, uint8_t *flag, uint8_t *tstate, int stride, double *rec)
 {
     if (!c) return OFK_E_INVALID;
-    if (c->tp_batch < 1 || !c->tpr.tmpl[0]) return ofk_fail(c, OFK_E_INVALID, "ofk_track_template_download: no stream has stepped with ofk_set_track_template on yet");
-    if ((tmpl || A || ncc || flag || tstate) && stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_track_template_download: stride %d", stride);
-    TRY(enter(c));
-    const int B = c->tp_batch;
-    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    TRY(track_download_begin(c, TRACK[TS_TEMPLATE], tmpl || A || ncc || flag || tstate, stride));
     const ofk_tp_rows &t = c->tpr;
     if (tmpl && tp_stride_of(c->tpl.win) != t.tstride)
         return ofk_fail(c, OFK_E_INVALID, "ofk_track_template_download: the window was set to %d behind the latest step: its templates are gone", c->tpl.win);
-    struct { void *dst; const void *src; size_t el; } rows[] = {{tmpl, t.tmpl[t.cur], (size_t)t.tstride}, {A, t.A, 16}, {ncc, t.ncc, 4}, {flag, t.flag, 1},
-                                                                 {tstate, t.tstate, 1}};
-    for (const auto &r : rows)
-        if (r.dst) OFK_HIP(c, hipMemcpy2DAsync(r.dst, (size_t)stride * r.el, r.src, mp * r.el, n * r.el, B, hipMemcpyDeviceToHost, c->stream));
-    if (rec) OFK_HIP(c, hipMemcpyAsync(rec, t.rec, (size_t)B * OFK_TPL_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
+    const download_row rows[] = {{tmpl, t.tmpl[t.cur], (size_t)t.tstride, 0}, {A, t.A, 16, 0}, {ncc, t.ncc, 4, 0}, {flag, t.flag, 1, 0}, {tstate, t.tstate, 1, 0},
+                                 {rec, t.rec, OFK_TPL_DOUBLES * 8, OFK_TPL_DOUBLES * 8}};
+    return rows_download(c, c->tp_batch, stride, rows, 6);
 }
 
 // rule 1 on host buffers: device scratch only
@@ -2885,12 +2878,9 @@ extern "C" int ofk_track_template_step(ofk_ctx *c, const ofk_track_template *set
     ofk_launch_track_template(c->stream, t, d_prev, d_next, px, h, w, d_pp, d_np, d_st, d_age, d_cnt, stride, set, batch);
     ofk_launch_track_template_update(c->stream, t, d_st, d_cnt, stride, d_nc, max_total, set, batch);
     TRY(check_launch(c, "k_track_template"));
-    struct { void *dst; const void *src; size_t bytes; } back[] = {{next_pts, d_np, np * 8}, {status, d_st, np}, {tmpl, t.tmpl[1], np * ts}, {A, t.A, np * 16},
-        {ncc, t.ncc, np * 4}, {flag, t.flag, np}, {tstate, t.tstate, np}, {rec, t.rec, B * OFK_TPL_DOUBLES * 8}};
-    for (const auto &r : back)
-        if (r.dst) OFK_HIP(c, hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
+    const back_row back[] = {{next_pts, d_np, np * 8}, {status, d_st, np}, {tmpl, t.tmpl[1], np * ts}, {A, t.A, np * 16}, {ncc, t.ncc, np * 4}, {flag, t.flag, np},
+                             {tstate, t.tstate, np}, {rec, t.rec, B * OFK_TPL_DOUBLES * 8}};
+    return fetch_back(c, who, back, 8);
 }
 
 // ------------------------------------------------------------------------------------------------ keyframe per stream
@@ -2916,8 +2906,6 @@ extern "C" int ofk_set_keyframe(ofk_ctx *c, const ofk_keyframe *k)
 }
 extern "C" int ofk_get_keyframe(const ofk_ctx *c, ofk_keyframe *k) { return setting_get(c, &ofk_ctx::key, k); }
 
-static bool kf_on(const ofk_ctx *c) { return c->key.mode != OFK_KEY_OFF; }
-
 // the keyframe's rotation (ofk.h: ofk_set_keyframe_rotation)
 static int check_keyrot(ofk_ctx *c, const ofk_keyframe_rotation *r, const char *who)
 {
@@ -2939,23 +2927,11 @@ extern "C" int ofk_set_keyframe_rotation(ofk_ctx *c, const ofk_keyframe_rotation
 }
 extern "C" int ofk_get_keyframe_rotation(const ofk_ctx *c, ofk_keyframe_rotation *r) { return setting_get(c, &ofk_ctx::krot, r); }
 
-static bool kr_on(const ofk_ctx *c) { return c->krot.mode != OFK_KEYROT_OFF; }
 // every axis held by the setting alone: the plain kernel runs (ofk.h)
 static bool kr_all_held(const ofk_keyframe_rotation *r)
 {
     if (!r->axes[0] && !r->axes[1] && !r->axes[2]) return true;
     return r->source == OFK_KEYROT_ATTITUDE ? r->sigma_att == 0.0 : r->sigma_gyro == 0.0 && r->sigma_bias == 0.0;
-}
-// the rotation state and records of max_batch streams, allocated (and cleared) by the first step with the setting on
-static int kr_alloc(ofk_ctx *c)
-{
-    if (c->kr_st) return OFK_OK;
-    const size_t sb = up((size_t)c->max_batch * OFK_KEYROT_STATE * 8, 256), bytes = sb + (size_t)c->max_batch * OFK_KEYROT_DOUBLES * 8;
-    uint8_t *base = nullptr;
-    OFK_HIP(c, hipMalloc((void **)&base, bytes));
-    c->kr_st = (double *)base; c->kr_rec = (double *)(base + sb);
-    OFK_HIP(c, hipMemsetAsync(base, 0, bytes, c->stream));
-    return OFK_OK;
 }
 // the launch of rules 1-5: k_keyframe_step, or with the rotation on (r, not all held) k_keyframe_step_rot in its place
 static void launch_key_step(ofk_ctx *c, const ofk_kf_rows &t, const ofk_kf_in &in, const ofk_keyframe *k, const ofk_keyframe_rotation *r,
@@ -2970,85 +2946,23 @@ static void launch_key_step(ofk_ctx *c, const ofk_kf_rows &t, const ofk_kf_in &i
     ofk_launch_keyframe_step_rot(c->stream, t, in, k, r, rst, rrec, batch);
 }
 
-// the state's arrays over `np` rows and the state of `batch` streams carved out of base (NULL: nothing is carved); returns the bytes
-static size_t kf_carve(ofk_kf_rows &t, uint8_t *base, size_t np, size_t batch)
-{
-    size_t o = 0;
-    auto take = [&](size_t bytes) { uint8_t *p = base ? base + o : nullptr; o += up(bytes, 256); return p; };
-    t.key_xy = (float *)take(np * 8); t.member = take(np); t.st = (double *)take(batch * OFK_KEY_STATE * 8);
-    t.ist = (int *)take(batch * OFK_KEY_INTS * 4); t.rec = (double *)take(batch * OFK_KEY_DOUBLES * 8);
-    t.next_copy = (float *)take(np * 8);
-    return o;
-}
-// the resident state, allocated (and cleared) by the first step with the setting on
-static int kf_alloc(ofk_ctx *c)
-{
-    if (c->kfr.key_xy) return OFK_OK;                            // one allocation, carved into the arrays
-    ofk_kf_rows t;
-    const size_t np = (size_t)c->max_batch * c->max_pts, bytes = kf_carve(t, nullptr, np, (size_t)c->max_batch);
-    uint8_t *base = nullptr;
-    OFK_HIP(c, hipMalloc((void **)&base, bytes));
-    kf_carve(c->kfr, base, np, (size_t)c->max_batch);            // the context owns it from here on, whatever follows
-    OFK_HIP(c, hipMemsetAsync(base, 0, bytes, c->stream));
-    return OFK_OK;
-}
-
-// The steps' own refusals with the setting on (ofk.h); fu: a fused step's.
-static int kf_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const char *who)
-{
-    if (kr_on(c) && !kf_on(c))
-        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_keyframe_rotation is on without ofk_set_keyframe: it refines the keyframe's rotation", who);
-    if (!kf_on(c)) return OFK_OK;
-    if (c->tt.mode == OFK_TT_OFF)
-        return ofk_fail(c, OFK_E_INVALID, "%s: ofk_set_keyframe is on without ofk_set_track_table: the keyframe is kept per row of the table", who);
-    if (variant == OFK_SOLVE_OFMODULE || (fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY)))
-        return refuse_not_sensor_model(c, who, NO_OFMODULE | NO_ROTATIONAL | NO_LEGACY, "keyframe", "ofk_set_keyframe");
-    return OFK_OK;
-}
-
-// a keyframe state for the current tracks of the first B streams: begun afresh unless it is live already
-static int kf_begin(ofk_ctx *c, int B)
-{
-    TRY(kf_alloc(c));
-    if (c->kf_live != B) { ofk_launch_keyframe_begin(c->stream, c->kfr, c->counts, c->max_pts, B); c->kr_live = 0; }
-    c->kf_batch = c->kf_live = B;
-    return OFK_OK;
-}
-// behind kf_begin with the rotation on: its state in step with the keyframe's, cleared where that began afresh
-static int kr_begin(ofk_ctx *c, int B)
-{
-    TRY(kr_alloc(c));
-    if (c->kr_live != B) ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, nullptr, 0, OFK_KEYROT_NONE, B);
-    c->kr_batch = c->kr_live = B;
-    return OFK_OK;
-}
-
 extern "C" int ofk_keyframe_rotation_download(ofk_ctx *c, double *rec)
 {
     if (!c) return OFK_E_INVALID;
-    if (c->kr_batch < 1 || !c->kr_rec) return ofk_fail(c, OFK_E_INVALID, "ofk_keyframe_rotation_download: no stream has stepped with ofk_set_keyframe_rotation on yet");
+    TRY(track_download_begin(c, TRACK[TS_KEYROT], false, 0));
     if (!rec) return ofk_fail(c, OFK_E_INVALID, "ofk_keyframe_rotation_download: NULL argument");
-    TRY(enter(c));
-    OFK_HIP(c, hipMemcpyAsync(rec, c->kr_rec, (size_t)c->kr_batch * OFK_KEYROT_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
+    const download_row row = {rec, c->kr_rec, OFK_KEYROT_DOUBLES * 8, OFK_KEYROT_DOUBLES * 8};
+    return rows_download(c, c->kr_batch, 0, &row, 1);
 }
 
 extern "C" int ofk_keyframe_download(ofk_ctx *c, float *key_xy, uint8_t *member, int stride, double *R_acc, double *rec)
 {
     if (!c) return OFK_E_INVALID;
-    if (c->kf_batch < 1 || !c->kfr.key_xy) return ofk_fail(c, OFK_E_INVALID, "ofk_keyframe_download: no stream has stepped with ofk_set_keyframe on yet");
-    if ((key_xy || member) && stride < 1) return ofk_fail(c, OFK_E_INVALID, "ofk_keyframe_download: stride %d", stride);
-    TRY(enter(c));
-    const int B = c->kf_batch;
-    const size_t n = (size_t)(stride < c->max_pts ? stride : c->max_pts), mp = (size_t)c->max_pts;
+    TRY(track_download_begin(c, TRACK[TS_KEY], key_xy || member, stride));
     const ofk_kf_rows &t = c->kfr;
-    if (key_xy) OFK_HIP(c, hipMemcpy2DAsync(key_xy, (size_t)stride * 8, t.key_xy, mp * 8, n * 8, B, hipMemcpyDeviceToHost, c->stream));
-    if (member) OFK_HIP(c, hipMemcpy2DAsync(member, (size_t)stride, t.member, mp, n, B, hipMemcpyDeviceToHost, c->stream));
-    if (R_acc) OFK_HIP(c, hipMemcpy2DAsync(R_acc, 72, t.st, OFK_KEY_STATE * 8, 72, B, hipMemcpyDeviceToHost, c->stream));
-    if (rec) OFK_HIP(c, hipMemcpyAsync(rec, t.rec, (size_t)B * OFK_KEY_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
+    const download_row rows[] = {{key_xy, t.key_xy, 8, 0}, {member, t.member, 1, 0}, {R_acc, t.st, 72, OFK_KEY_STATE * 8},
+                                 {rec, t.rec, OFK_KEY_DOUBLES * 8, OFK_KEY_DOUBLES * 8}};
+    return rows_download(c, c->kf_batch, stride, rows, 4);
 }
 
 extern "C" int ofk_keyframe_reset(ofk_ctx *c, int b, const double *anchor)
@@ -3059,7 +2973,7 @@ extern "C" int ofk_keyframe_reset(ofk_ctx *c, int b, const double *anchor)
     const double zero[3] = {0.0, 0.0, 0.0}, *p = anchor ? anchor : zero;
     if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return ofk_fail(c, OFK_E_INVALID, "%s: the position must be finite", who);
     TRY(enter(c));
-    TRY(kf_begin(c, c->stream_batch));
+    TRY(track_begin(c, TRACK[TS_KEY], c->stream_batch));
     ofk_launch_keyframe_reset(c->stream, c->kfr, b, c->max_pts, p);
     if (c->kr_st && c->kr_live == c->stream_batch) ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, nullptr, b, OFK_KEYROT_NONE, 1);
     TRY(check_launch(c, who));
@@ -3086,15 +3000,10 @@ static int keyframe_step_host(ofk_ctx *c, const char *who, const ofk_keyframe *s
     }
     TRY(check_counts(c, who, counts, batch, stride));
     const size_t np = (size_t)batch * stride, B = (size_t)batch;
-    double *h_rec = (double *)calloc(B * OFK_RECORD_DOUBLES, 8);   // the step's records as the kernel reads them: v_uav, solved
-    if (!h_rec) return ofk_fail(c, OFK_E_INVALID, "%s: out of host memory", who);
-    for (size_t b = 0; b < B; ++b) {
-        for (int k = 0; k < 3; ++k) h_rec[b * OFK_RECORD_DOUBLES + 8 + k] = v_uav[3 * b + k];
-        h_rec[b * OFK_RECORD_DOUBLES + 15] = solved[b] ? 1.0 : 0.0;
-    }
+    const host_buf h_rec = {stage_step_records(v_uav, solved, B, 8)};
+    if (!h_rec.p) return ofk_fail(c, OFK_E_INVALID, "%s: out of host memory", who);
     Bump bp;
-    int rc = est_begin(c, np * 18 + B * ((OFK_RECORD_DOUBLES + OFK_KEY_DOUBLES + OFK_KEY_STATE + OFK_SENSOR_DOUBLES + OFK_KEYROT_STATE + OFK_KEYROT_DOUBLES) * 8 + OFK_KEY_INTS * 4 + 12) + 18 * 256, bp);
-    if (rc != OFK_OK) { free(h_rec); return rc; }
+    TRY(est_begin(c, np * 18 + B * ((OFK_RECORD_DOUBLES + OFK_KEY_DOUBLES + OFK_KEY_STATE + OFK_SENSOR_DOUBLES + OFK_KEYROT_STATE + OFK_KEYROT_DOUBLES) * 8 + OFK_KEY_INTS * 4 + 12) + 18 * 256, bp));
     ofk_kf_rows t = {};
     t.key_xy = (float *)bp.put(key_xy, np * 8); t.member = (uint8_t *)bp.put(member, np); t.st = bp.put(state, B * OFK_KEY_STATE * 8);
     t.ist = (int *)bp.put(istate, B * OFK_KEY_INTS * 4); t.rec = bp.take(B * OFK_KEY_DOUBLES * 8);
@@ -3103,25 +3012,16 @@ static int keyframe_step_host(ofk_ctx *c, const char *who, const ofk_keyframe *s
     in.counts = (const int *)bp.put(counts, B * 4); in.stride = stride;
     in.new_counts = (const int *)bp.put(new_counts, B * 4); in.max_total = max_total;
     in.sensors = bp.put(sensors, B * OFK_SENSOR_DOUBLES * 8); in.imu = nullptr;
-    in.v = bp.put(h_rec, B * OFK_RECORD_DOUBLES * 8); in.plain = 0;
+    in.v = bp.put(h_rec.p, B * OFK_RECORD_DOUBLES * 8); in.plain = 0;
     in.step = (const int *)bp.put(step, B * 4); in.step_stride = 1;
     double *d_rst = rot ? bp.put(rstate, B * OFK_KEYROT_STATE * 8) : nullptr, *d_rrec = rot ? bp.take(B * OFK_KEYROT_DOUBLES * 8) : nullptr;
-    hipError_t e = bp.rc == OFK_OK ? hipStreamSynchronize(c->stream) : hipErrorUnknown;   // h_rec has been read
-    free(h_rec);
-    if (e != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    if (bp.rc != OFK_OK || hipStreamSynchronize(c->stream) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
     launch_key_step(c, t, in, set, rot, d_rst, d_rrec, batch);
     TRY(check_launch(c, rot ? "k_keyframe_step_rot" : "k_keyframe_step"));
-    if (rot) {
-        OFK_HIP(c, hipMemcpyAsync(rstate, d_rst, B * OFK_KEYROT_STATE * 8, hipMemcpyDeviceToHost, c->stream));
-        if (rrec) OFK_HIP(c, hipMemcpyAsync(rrec, d_rrec, B * OFK_KEYROT_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    OFK_HIP(c, hipMemcpyAsync(key_xy, t.key_xy, np * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipMemcpyAsync(member, t.member, np, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipMemcpyAsync(state, t.st, B * OFK_KEY_STATE * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipMemcpyAsync(istate, t.ist, B * OFK_KEY_INTS * 4, hipMemcpyDeviceToHost, c->stream));
-    if (rec) OFK_HIP(c, hipMemcpyAsync(rec, t.rec, B * OFK_KEY_DOUBLES * 8, hipMemcpyDeviceToHost, c->stream));
-    OFK_HIP(c, hipStreamSynchronize(c->stream));
-    return OFK_OK;
+    const back_row back[] = {{rot ? rstate : nullptr, d_rst, B * OFK_KEYROT_STATE * 8}, {rot ? rrec : nullptr, d_rrec, B * OFK_KEYROT_DOUBLES * 8},
+                             {key_xy, t.key_xy, np * 8}, {member, t.member, np}, {state, t.st, B * OFK_KEY_STATE * 8}, {istate, t.ist, B * OFK_KEY_INTS * 4},
+                             {rec, t.rec, B * OFK_KEY_DOUBLES * 8}};
+    return fetch_back(c, who, back, 7);
 }
 
 extern "C" int ofk_keyframe_step(ofk_ctx *c, const ofk_keyframe *set, const float *next_pts, const uint8_t *status, const int *counts,
@@ -3202,16 +3102,8 @@ static int stream_begin_impl(ofk_ctx *c, const uint8_t *first_bgr, int batch, in
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     TRY(stream_ingest(c, 0, first_bgr, batch, h, w, lv));
     TRY(stream_detect(c, nullptr, nullptr, batch, h, w, p, c->pts_prev, c->counts));
-    c->tt_batch = c->tt_live = 0;                                // ... and with a new track table, if the setting is on
-    c->td_batch = c->td_live = 0;                                // ... and without depths: the first step with that setting on starts them
-    c->tp_batch = c->tp_live = 0;                                // ... and without templates
-    c->kf_batch = c->kf_live = 0;                                // ... and without a keyframe
-    c->kr_batch = c->kr_live = 0;                                // ... and without its rotation state
-    if (tt_on(c)) {
-        TRY(tt_alloc(c));
-        ofk_launch_track_table_begin(c->stream, c->ttr, c->pts_prev, c->counts, c->max_pts, batch);
-        c->tt_batch = c->tt_live = batch;
-    }
+    for (const track_state &s : TRACK) c->*s.batch = c->*s.live = 0;   // ... and without per-track state: the first step with a setting on starts its own,
+    if (TRACK[TS_TABLE].on(c)) TRY(track_begin(c, TRACK[TS_TABLE], batch));   // but for the track table, which begins with the tracks
     c->stream_h = h; c->stream_w = w; c->stream_batch = batch;
     return stream_fetch_tracks(c, batch, p->max_corners, tracks, counts);
 }
@@ -3368,9 +3260,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     TRY(fm_check_step(c, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     TRY(second_prepare(c, B, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     TRY(bias_check_step(c, B, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
-    TRY(td_check_step(c, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
-    TRY(tp_check_step(c, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
-    TRY(kf_check_step(c, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
+    TRY(track_check_step(c, p->solve_variant, fu, fu ? "ofk_stream_step_fused" : "ofk_stream_step"));
     const int defer = second_on(c) && fu && fu->filter ? 1 : 0;   // the second-stage kernel corrects
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     if (c->robust.loss != OFK_ROBUST_OFF) { TRY(robust_alloc(c)); c->rob_batch = B; }
@@ -3386,25 +3276,13 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         void now() { if (ist) ofk_launch_gyro_bias_apply(c->stream, nullptr, 0, ist, c->bias_rec, B, 1); ist = nullptr; }
         ~bias_restore() { now(); }
     } restore = {c, bias_ist, B};
-    const bool table = tt_on(c);
-    if (table) {
-        TRY(tt_alloc(c));
-        if (c->tt_live != B) ofk_launch_track_table_begin(c->stream, c->ttr, c->pts_prev, c->counts, c->max_pts, B);   // no table of these tracks yet
-        c->tt_batch = c->tt_live = B;
-    } else
-        c->tt_live = 0;                                          // the tracks move on without their table
-    const bool depth = td_on(c);                                 // td_check_step: then the table is on
-    if (depth) TRY(td_begin(c, B));
-    else c->td_live = 0;                                         // the tracks move on without their depths
-    const bool templ = tp_on(c);                                 // tp_check_step: then the table is on
-    if (templ) TRY(tp_begin(c, B));
-    else c->tp_live = 0;                                         // the tracks move on without their templates
-    const bool keyf = kf_on(c);                                  // kf_check_step: then the table is on
-    if (keyf) TRY(kf_begin(c, B));
-    else c->kf_live = 0;                                         // the tracks move on without their keyframe
-    const bool krot = keyf && kr_on(c);                          // kf_check_step: never without the keyframe
-    if (krot) TRY(kr_begin(c, B));
-    else c->kr_live = 0;                                         // the keyframes move on without their R_world(key)
+    bool on[sizeof(TRACK) / sizeof(TRACK[0])];                   // track_check_step: none is on without the state it needs
+    for (const track_state &s : TRACK) {
+        on[&s - TRACK] = s.on(c);
+        if (s.on(c)) TRY(track_begin(c, s, B));                  // no state of these tracks yet: begun afresh
+        else c->*s.live = 0;                                     // the tracks move on without it
+    }
+    const bool table = on[TS_TABLE], depth = on[TS_DEPTH], templ = on[TS_TEMPLATE], keyf = on[TS_KEY], krot = on[TS_KEYROT];
     const bool flow_seed = table && c->tt.seed == OFK_TT_SEED_FLOW;
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
@@ -3418,10 +3296,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         }
         TRY(stream_detect(c, zones_on ? c->mask : nullptr, c->limit, B, h, w, p, c->pts_new, c->new_counts));
         ofk_launch_replace_tracks(c->stream, c->limit, c->pts_new, c->new_counts, c->max_pts, c->pts_prev, c->counts, B);
-        if (table) ofk_launch_track_table_replace(c->stream, c->ttr, c->limit, c->pts_new, c->new_counts, c->max_pts, B);
-        if (depth) ofk_launch_track_depth_replace(c->stream, c->tdr, c->limit, c->new_counts, c->max_pts, B);
-        if (keyf) ofk_launch_keyframe_replace(c->stream, c->kfr, c->limit, c->new_counts, c->max_pts, B);
-        if (krot) ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, c->limit, 0, OFK_KEYROT_NONE, B);
+        for (const track_state &s : TRACK) if (on[&s - TRACK] && s.replace) s.replace(c, B);
     }
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)

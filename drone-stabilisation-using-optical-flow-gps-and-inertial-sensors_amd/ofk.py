@@ -846,6 +846,27 @@ class Context:
             self._ck(call(*[_p(b) for b in bufs]))
         return [b[:batch].copy() for b in bufs]
 
+    def _track_download(self, name, batch, stride, rows, streams, keys):
+        """ofk_<name>_download(rows..., stride, streams...) -> dict(zip(keys, arrays)): per (tail, dtype) of `rows` one [batch,stride,*tail]
+        (stride None: max_pts; no rows: the call takes no stride), per (shape, dtype) of `streams` one [batch,*shape]."""
+        who, S = name + "_download", ()
+        if rows:
+            S = (self.max_pts if stride is None else int(stride),)
+            if S[0] < 1:
+                raise ValueError(f"{who}: stride {S[0]}")
+        fn, n = getattr(self._L, "ofk_" + who), len(rows)
+        out = self._rows(who, self.max_batch if batch is None else int(batch), lambda *p: fn(self._h, *p[:n], *S, *p[n:]),
+                         *[(S + tuple(tail), dtype) for tail, dtype in rows], *streams)
+        return dict(zip(keys, out))
+
+    @staticmethod
+    def _stage_rows(who, arr, name, max_total=None, dtype=np.float32):
+        """The first array of a per-track stage entry, [B, S >= 1, 2] -> (array, B, S, max_total or its default S)."""
+        a = _arr(arr, dtype)
+        if a.ndim != 3 or a.shape[2] != 2 or a.shape[1] < 1:
+            raise ValueError(f"{who}: {name} {a.shape} is not [B, S >= 1, 2]")
+        return a, a.shape[0], a.shape[1], a.shape[1] if max_total is None else int(max_total)
+
     def _points_download(self, fn, batch):
         """ofk_camera_download / ofk_rs_download / ofk_finite_download: (prev, next) [batch,max_pts,2] f32."""
         spec = ((self.max_pts, 2), np.float32)
@@ -1109,14 +1130,9 @@ class Context:
         [batch,stride,2] f32, stats [batch,8] i32: count, kept, lost, born, oldest age, step, next_id, rows seeded from their flow) of
         the streams of the latest begin or step with the setting on.  Rows are in the order of the tracks that call returned; the
         first stats[:, 0] of a stream are its tracks."""
-        S = self.max_pts if stride is None else int(stride)
-        if S < 1:
-            raise ValueError(f"track_table_download: stride {S}")
-        u, n, f = ((S,), np.uint32), ((S,), np.int32), ((S, 2), np.float32)
-        ids, age, bs, bxy, fxy, sid, st = self._rows(
-            "track_table_download", self.max_batch if batch is None else int(batch),
-            lambda *p: self._L.ofk_track_table_download(self._h, *p[:6], S, p[6]), u, n, n, f, f, u, ((TT_STATS,), np.int32))
-        return dict(ids=ids, age=age, birth_step=bs, birth_xy=bxy, flow_xy=fxy, step_ids=sid, stats=st)
+        u, n, f = ((), np.uint32), ((), np.int32), ((2,), np.float32)
+        return self._track_download("track_table", batch, stride, (u, n, n, f, f, u), [((TT_STATS,), np.int32)],
+                                    ("ids", "age", "birth_step", "birth_xy", "flow_xy", "step_ids", "stats"))
 
     def track_table_step(self, table, head, prev_pts, next_pts, status, counts, new_pts=None, new_counts=None, max_total=None,
                          track_table=None):
@@ -1124,10 +1140,7 @@ class Context:
         birth_xy, flow_xy [B,S,2]); head [B,2] = step, next_id; prev_pts / next_pts [B,S,2], status [B,S], counts [B]; new_pts [B,S,2]
         / new_counts [B] the re-detected corners (None: none); max_total (default S); track_table: the setting whose seed and gain the
         last statistic takes.  -> (table, head, counts, step_ids [B,S], stats [B,8]), new arrays.  Touches no resident state."""
-        pp = _arr(prev_pts, np.float32)
-        if pp.ndim != 3 or pp.shape[2] != 2 or pp.shape[1] < 1:
-            raise ValueError(f"track_table_step: prev_pts {pp.shape} is not [B, S >= 1, 2]")
-        B, S = pp.shape[:2]
+        pp, B, S, mt = self._stage_rows("track_table_step", prev_pts, "prev_pts", max_total)
         pn = _arr(next_pts, np.float32, (B, S, 2)); st = _arr(status, np.uint8, (B, S))
         cn = np.array(_arr(counts, np.int32, (B,)))
         ids = np.array(_arr(table["ids"], np.uint32, (B, S))); age = np.array(_arr(table["age"], np.int32, (B, S)))
@@ -1140,18 +1153,14 @@ class Context:
         sid = np.zeros((B, S), np.uint32); stats = np.zeros((B, TT_STATS), np.int32)
         with self._lock:
             self._ck(self._L.ofk_track_table_step(self._h, C.byref(track_table) if track_table is not None else None, _p(ids), _p(age), _p(bs),
-                                                  _p(bxy), _p(fxy), _p(hd), _p(pp), _p(pn), _p(st), _p(cn), _p(nw), _p(nc),
-                                                  S if max_total is None else int(max_total), B, S, _p(sid), _p(stats)))
+                                                  _p(bxy), _p(fxy), _p(hd), _p(pp), _p(pn), _p(st), _p(cn), _p(nw), _p(nc), mt, B, S, _p(sid), _p(stats)))
         return dict(ids=ids, age=age, birth_step=bs, birth_xy=bxy, flow_xy=fxy), hd, cn, sid, stats
 
     def track_seed_points(self, pts, counts, age, flow_xy, gain=1.0, seed=None):
         """ofk_track_seed_points, the stage entry: LK's start positions for pts [B,S,2] (counts [B]) from the tracks' age [B,S] and
         last flow [B,S,2].  seed: the model seeds [B,S,2] that rows of age 0 keep (None: they start at the point).  Entries beyond
         counts[b] are the points (or `seed`).  Touches no resident state."""
-        pp = _arr(pts, np.float32)
-        if pp.ndim != 3 or pp.shape[2] != 2 or pp.shape[1] < 1:
-            raise ValueError(f"track_seed_points: pts {pp.shape} is not [B, S >= 1, 2]")
-        B, S = pp.shape[:2]
+        pp, B, S, _ = self._stage_rows("track_seed_points", pts, "pts")
         cn = _arr(counts, np.int32, (B,)); ag = _arr(age, np.int32, (B, S)); fl = _arr(flow_xy, np.float32, (B, S, 2))
         out = np.array(pp if seed is None else _arr(seed, np.float32, (B, S, 2)))
         with self._lock:
@@ -1172,13 +1181,8 @@ class Context:
         latest step with the setting on, rows in the order of the tracks that step returned.  rec: v_map 0-2, map flag 3, mature rows
         4, rows updated 5, initialised 6, skipped for |b| 7, cross-flow 8, innovation 9, C_map's upper triangle 10-15, the v the
         measurements read 16-18, solved 19, rows reset 20."""
-        S = self.max_pts if stride is None else int(stride)
-        if S < 1:
-            raise ValueError(f"track_depth_download: stride {S}")
-        f, n = ((S,), np.float64), ((S,), np.int32)
-        rho, var, nobs, rec = self._rows("track_depth_download", self.max_batch if batch is None else int(batch),
-                                         lambda *p: self._L.ofk_track_depth_download(self._h, *p[:3], S, p[3]), f, f, n, ((TD_DOUBLES,), np.float64))
-        return dict(rho=rho, var=var, nobs=nobs, rec=rec)
+        f = ((), np.float64)
+        return self._track_download("track_depth", batch, stride, (f, f, ((), np.int32)), [((TD_DOUBLES,), np.float64)], ("rho", "var", "nobs", "rec"))
 
     def track_depth_reset(self, stream, rho, var, nobs):
         """ofk_track_depth_reset: the first len(rho) rows of active stream `stream` are loaded from rho, var, nobs."""
@@ -1193,10 +1197,7 @@ class Context:
         re-detected corners (None: none); max_total (default S); the setting a TrackDepth or track_depth_setting's keywords.
         -> (state, rec [B,32]), new arrays.  Touches no resident state."""
         td = track_depth if track_depth is not None else track_depth_setting(**settings)
-        xx = _arr(x, np.float64)
-        if xx.ndim != 3 or xx.shape[2] != 2 or xx.shape[1] < 1:
-            raise ValueError(f"track_depth_step: x {xx.shape} is not [B, S >= 1, 2]")
-        B, S = xx.shape[:2]
+        xx, B, S, mt = self._stage_rows("track_depth_step", x, "x", max_total, np.float64)
         uu = _arr(u, np.float64, (B, S, 2)); st = _arr(status, np.uint8, (B, S)); cn = _arr(counts, np.int32, (B,))
         om = _arr(omega, np.float64, (B, 3)); vv = _arr(v, np.float64, (B, 3)); so = _arr(solved, np.int32, (B,))
         rho = np.array(_arr(state["rho"], np.float64, (B, S))); var = np.array(_arr(state["var"], np.float64, (B, S)))
@@ -1205,7 +1206,7 @@ class Context:
         rec = np.zeros((B, TD_DOUBLES), np.float64)
         with self._lock:
             self._ck(self._L.ofk_track_depth_step(self._h, C.byref(td), _p(xx), _p(uu), _p(st), _p(cn), _p(om), _p(vv), _p(so), _p(rho), _p(var),
-                                                  _p(nobs), _p(nc), S if max_total is None else int(max_total), B, S, _p(rec)))
+                                                  _p(nobs), _p(nc), mt, B, S, _p(rec)))
         return dict(rho=rho, var=var, nobs=nobs), rec
 
     def set_track_template(self, track_template=None, **settings):
@@ -1222,25 +1223,15 @@ class Context:
         flag, tstate [batch,stride] u8, rec [batch,32]) of the streams of the latest step with the setting on, rows in the order of the
         tracks that step returned.  rec: M 0-3, t 4-5, fit flag 6, rows of the two fits 7-8, rms 9, rows scored 10, dropped 11, moved 12,
         abandoned 13, outside 14, flat 15, captured 16, without a template 17, marked for refresh 18, largest move 19."""
-        S = self.max_pts if stride is None else int(stride)
-        if S < 1:
-            raise ValueError(f"track_template_download: stride {S}")
-        ts = tpl_stride(self.get_track_template().win)
-        u = ((S,), np.uint8)
-        tmpl, A, ncc, flag, tstate, rec = self._rows(
-            "track_template_download", self.max_batch if batch is None else int(batch),
-            lambda *p: self._L.ofk_track_template_download(self._h, *p[:5], S, p[5]), ((S, ts), np.uint8), ((S, 4), np.float32),
-            ((S,), np.float32), u, u, ((TPL_DOUBLES,), np.float64))
-        return dict(tmpl=tmpl, A=A, ncc=ncc, flag=flag, tstate=tstate, rec=rec)
+        u = ((), np.uint8)
+        return self._track_download("track_template", batch, stride, (((tpl_stride(self.get_track_template().win),), np.uint8), ((4,), np.float32),
+                                    ((), np.float32), u, u), [((TPL_DOUBLES,), np.float64)], ("tmpl", "A", "ncc", "flag", "tstate", "rec"))
 
     def track_affine_fit(self, prev_pts, next_pts, status, counts, h, w, track_template=None, **settings):
         """ofk_track_affine_fit, the stage entry of the templates' step map: prev_pts, next_pts [B,S,2] f32, status [B,S], counts [B],
         the frame's h and w -> (rec [B,32] with slots 0-9 filled, L [B,4] f32)."""
         tp = track_template if track_template is not None else track_template_setting(**settings)
-        pp = _arr(prev_pts, np.float32)
-        if pp.ndim != 3 or pp.shape[2] != 2 or pp.shape[1] < 1:
-            raise ValueError(f"track_affine_fit: prev_pts {pp.shape} is not [B, S >= 1, 2]")
-        B, S = pp.shape[:2]
+        pp, B, S, _ = self._stage_rows("track_affine_fit", prev_pts, "prev_pts")
         nn = _arr(next_pts, np.float32, (B, S, 2)); st = _arr(status, np.uint8, (B, S)); cn = _arr(counts, np.int32, (B,))
         rec = np.zeros((B, TPL_DOUBLES), np.float64); L = np.zeros((B, 4), np.float32)
         with self._lock:
@@ -1291,13 +1282,8 @@ class Context:
         streams of the latest step with the setting on, rows in the order of the tracks that step returned.  rec: T 0-2, flag 3, rows
         of the first / the gated solve 4 / 5, rms px 6, members_at_key 7, key_step 8, re-key reason 9, D 10-12, pos 13-15, anchor
         16-18, angle 19, C_T's upper triangle 20-25, keyframes 26, dead-reckoned steps 27, live 28, gated 29, the reasons as bits 30."""
-        S = self.max_pts if stride is None else int(stride)
-        if S < 1:
-            raise ValueError(f"keyframe_download: stride {S}")
-        kx, mem, R, rec = self._rows("keyframe_download", self.max_batch if batch is None else int(batch),
-                                     lambda *p: self._L.ofk_keyframe_download(self._h, p[0], p[1], S, p[2], p[3]), ((S, 2), np.float32),
-                                     ((S,), np.uint8), ((3, 3), np.float64), ((KEY_DOUBLES,), np.float64))
-        return dict(key_xy=kx, member=mem, R_acc=R, rec=rec)
+        return self._track_download("keyframe", batch, stride, (((2,), np.float32), ((), np.uint8)), [((3, 3), np.float64), ((KEY_DOUBLES,), np.float64)],
+                                    ("key_xy", "member", "R_acc", "rec"))
 
     def keyframe_reset(self, stream, anchor=None):
         """ofk_keyframe_reset: active stream `stream` starts over at the position `anchor` (None: zero) and keys at its next step."""
@@ -1318,22 +1304,16 @@ class Context:
         """ofk_keyframe_rotation_download -> rec [batch,40] of the streams of the latest step with the setting on: delta 0-2, flag 3
         (KEYROT_*), R^ 4-12, C_delta's upper triangle 13-18, C_T's 19-24, the reduced system's eigenvalues 25-27, the prior's sigmas
         28-30, Gauss-Newton steps 31, the plain first solve's T 32-34, attitude source used 35, age 36, rows 37."""
-        rec, = self._rows("keyframe_rotation_download", self.max_batch if batch is None else int(batch),
-                          lambda p: self._L.ofk_keyframe_rotation_download(self._h, p), ((KEYROT_DOUBLES,), np.float64))
-        return rec
+        return self._track_download("keyframe_rotation", batch, None, (), [((KEYROT_DOUBLES,), np.float64)], ("rec",))["rec"]
 
     def _keyframe_step(self, who, kf, rot, next_pts, status, counts, sensors, v_uav, solved, step, state, new_counts, max_total):
-        nn = _arr(next_pts, np.float32)
-        if nn.ndim != 3 or nn.shape[2] != 2 or nn.shape[1] < 1:
-            raise ValueError(f"{who}: next_pts {nn.shape} is not [B, S >= 1, 2]")
-        B, S = nn.shape[:2]
+        nn, B, S, mt = self._stage_rows(who, next_pts, "next_pts", max_total)
         st = _arr(status, np.uint8, (B, S)); cn = _arr(counts, np.int32, (B,)); sn = _arr(sensors, np.float64, (B, SENSOR_DOUBLES))
         vu = _arr(v_uav, np.float64, (B, 3)); so = _arr(solved, np.int32, (B,)); sp = _arr(step, np.int32, (B,))
         kx = np.array(_arr(state["key_xy"], np.float32, (B, S, 2))); mem = np.array(_arr(state["member"], np.uint8, (B, S)))
         sd = np.array(_arr(state["state"], np.float64, (B, KEY_STATE))); si = np.array(_arr(state["istate"], np.int32, (B, KEY_INTS)))
         nc = _opt(new_counts, np.int32, (B,))
         rec = np.zeros((B, KEY_DOUBLES), np.float64)
-        mt = S if max_total is None else int(max_total)
         if rot is None:
             with self._lock:
                 self._ck(self._L.ofk_keyframe_step(self._h, C.byref(kf), _p(nn), _p(st), _p(cn), _p(sn), _p(vu), _p(so), _p(sp), _p(kx), _p(mem),

@@ -267,76 +267,49 @@ class PipelineConfig:
         m = self.rolling_shutter.setting() if hasattr(self.rolling_shutter, "setting") else self.rolling_shutter
         return None if m.mode == ofk.RS_OFF else m
 
+    def _struct_setting(self, name, cls, maker, rebuild=True):
+        """The setting `name` of this configuration: None / False (off), True (the maker's defaults) or an ofk structure of `cls`
+        -> the structure, None when it is off.  rebuild: made again by `maker` from its fields, by keyword: range-checked."""
+        m = getattr(self, name)
+        if m is None or m is False:
+            return None
+        m = maker() if m is True else m
+        if not isinstance(m, cls):
+            raise ValueError(f"{name} {m!r} is neither None, True nor an ofk.{cls.__name__}")
+        if rebuild:
+            m = maker(**{f: tuple(v) if hasattr(v, "__len__") else v for f, v in ((f[0], getattr(m, f[0])) for f in cls._fields_)})
+        return None if m.mode == 0 else m                        # every one's OFF is 0
+
     def finite_motion_setting(self):
         """The ofk.FiniteMotion structure of this configuration, None when the finite motion is off."""
-        if self.finite_motion is None or self.finite_motion is False:
-            return None
-        m = ofk.finite_motion_setting() if self.finite_motion is True else self.finite_motion
-        if not isinstance(m, ofk.FiniteMotion):
-            raise ValueError(f"finite_motion {m!r} is neither None, True nor an ofk.FiniteMotion")
-        m = ofk.finite_motion_setting(m.mode, m.min_depth)       # range-checked
-        return None if m.mode == ofk.FM_OFF else m
+        return self._struct_setting("finite_motion", ofk.FiniteMotion, ofk.finite_motion_setting)
 
     def gyro_bias_setting(self):
         """The ofk.GyroBias structure of this configuration, None when the gyro bias is off."""
-        if self.gyro_bias is None or self.gyro_bias is False:
-            return None
-        m = ofk.gyro_bias_setting() if self.gyro_bias is True else self.gyro_bias
-        if not isinstance(m, ofk.GyroBias):
-            raise ValueError(f"gyro_bias {m!r} is neither None, True nor an ofk.GyroBias")
-        return None if m.mode == ofk.BIAS_OFF else m
+        return self._struct_setting("gyro_bias", ofk.GyroBias, ofk.gyro_bias_setting, rebuild=False)
 
     def track_table_setting(self):
         """The ofk.TrackTable structure of this configuration, None when the track table is off."""
-        if self.track_table is None or self.track_table is False:
-            return None
-        m = ofk.track_table_setting() if self.track_table is True else self.track_table
-        if not isinstance(m, ofk.TrackTable):
-            raise ValueError(f"track_table {m!r} is neither None, True nor an ofk.TrackTable")
-        m = ofk.track_table_setting(m.seed, m.gain, m.mode)      # range-checked
-        return None if m.mode == ofk.TT_OFF else m
+        return self._struct_setting("track_table", ofk.TrackTable, ofk.track_table_setting)
 
     def track_depth_setting(self):
         """The ofk.TrackDepth structure of this configuration, None when the depths are off."""
-        if self.track_depth is None or self.track_depth is False:
-            return None
-        m = ofk.track_depth_setting() if self.track_depth is True else self.track_depth
-        if not isinstance(m, ofk.TrackDepth):
-            raise ValueError(f"track_depth {m!r} is neither None, True nor an ofk.TrackDepth")
-        m = ofk.track_depth_setting(m.mode, m.sigma_flow, m.b_min, m.gate, m.q, m.min_obs, m.rel_max, m.min_rows, m.update)   # range-checked
-        return None if m.mode == ofk.TD_OFF else m
+        return self._struct_setting("track_depth", ofk.TrackDepth, ofk.track_depth_setting)
 
     def keyframe_setting(self):
         """The ofk.Keyframe structure of this configuration, None when the keyframe is off."""
-        if self.keyframe is None or self.keyframe is False:
-            return None
-        m = ofk.keyframe_setting() if self.keyframe is True else self.keyframe
-        if not isinstance(m, ofk.Keyframe):
-            raise ValueError(f"keyframe {m!r} is neither None, True nor an ofk.Keyframe")
-        m = ofk.keyframe_setting(m.mode, m.sigma_flow, m.gate, m.min_rows, m.min_share, m.rot_max, m.max_age)   # range-checked
-        return None if m.mode == ofk.KEY_OFF else m
+        return self._struct_setting("keyframe", ofk.Keyframe, ofk.keyframe_setting)
 
     def keyframe_rotation_setting(self):
         """The ofk.KeyframeRotation structure of this configuration, None when the rotation is not refined."""
-        if self.keyframe_rotation is None or self.keyframe_rotation is False:
-            return None
-        m = ofk.keyframe_rotation_setting() if self.keyframe_rotation is True else self.keyframe_rotation
-        if not isinstance(m, ofk.KeyframeRotation):
-            raise ValueError(f"keyframe_rotation {m!r} is neither None, True nor an ofk.KeyframeRotation")
-        m = ofk.keyframe_rotation_setting(m.mode, m.source, tuple(m.axes), m.sigma_gyro, m.sigma_bias, m.sigma_att, m.iters, m.delta_max)   # range-checked
-        if m.mode != ofk.KEYROT_OFF and self.keyframe_setting() is None:
+        m = self._struct_setting("keyframe_rotation", ofk.KeyframeRotation, ofk.keyframe_rotation_setting)
+        if m is not None and self.keyframe_setting() is None:
             raise ValueError("keyframe_rotation needs keyframe on")
-        return None if m.mode == ofk.KEYROT_OFF else m
+        return m
 
     def track_template_setting(self):
         """The ofk.TrackTemplate structure of this configuration, None when the templates are off."""
-        if self.track_template is None or self.track_template is False:
-            return None
-        m = ofk.track_template_setting() if self.track_template is True else self.track_template
-        if not isinstance(m, ofk.TrackTemplate):
-            raise ValueError(f"track_template {m!r} is neither None, True nor an ofk.TrackTemplate")
-        m = ofk.track_template_setting(m.mode, m.win, m.ncc_min, m.anchor_iters, m.anchor_max, m.outside, m.fit_min, m.fit_gate, m.scale_max)   # range-checked
-        return None if m.mode == ofk.TPL_OFF else m
+        return self._struct_setting("track_template", ofk.TrackTemplate, ofk.track_template_setting)
 
     def to_params(self):
         return ofk.Params(int(self.max_corners), float(self.quality), float(self.min_distance), int(self.block_size),
@@ -566,17 +539,21 @@ class FlowStream:
         out["stats"] = st
         return out
 
+    def _track_rows(self, d, keys):
+        """Per stream the rows of download d[k], k in keys, of the tracks that the latest step returned, in their order, and under
+        "ids" their ids from the track table."""
+        t = self.ctx.track_table_download(self.batch)
+        cnt = t["stats"][:, 0]
+        out = {k: [d[k][b, :cnt[b]] for b in range(self.batch)] for k in keys}
+        out["ids"] = [t["ids"][b, :cnt[b]] for b in range(self.batch)]
+        return out
+
     def depths(self):
         """The streams' depths per track behind the latest step (ofk.h: ofk_set_track_depth): dict(rho, var, nobs, ids: per stream the
         rows of the tracks that step returned, in their order, ids joined from the track table; rec [batch, 32]: rec[:, 0:3] is v_map,
         rec[:, 3] its flag, rec[:, 4] the mature rows it used, ofk.cov_matrix(rec[:, 10:16]) C_map)."""
         d = self.ctx.track_depth_download(self.batch)
-        t = self.ctx.track_table_download(self.batch)
-        cnt = t["stats"][:, 0]
-        out = {k: [d[k][b, :cnt[b]] for b in range(self.batch)] for k in ("rho", "var", "nobs")}
-        out["ids"] = [t["ids"][b, :cnt[b]] for b in range(self.batch)]
-        out["rec"] = d["rec"]
-        return out
+        return dict(self._track_rows(d, ("rho", "var", "nobs")), rec=d["rec"])
 
     def templates(self):
         """The streams' track templates behind the latest step (ofk.h: ofk_set_track_template): dict(tmpl, A, ncc, flag, tstate, ids: per
@@ -584,13 +561,9 @@ class FlowStream:
         [rows, win + 2, win + 2]; rec [batch, 32]: rec[:, 0:4] the step map M, rec[:, 4:6] t, rec[:, 6] the fit flag, rec[:, 10:20] the
         counts and the largest move)."""
         d = self.ctx.track_template_download(self.batch)
-        t = self.ctx.track_table_download(self.batch)
-        cnt = t["stats"][:, 0]
         e = self.ctx.get_track_template().win + 2
-        out = {k: [d[k][b, :cnt[b]] for b in range(self.batch)] for k in ("A", "ncc", "flag", "tstate")}
-        out["tmpl"] = [d["tmpl"][b, :cnt[b], :e * e].reshape(-1, e, e) for b in range(self.batch)]
-        out["ids"] = [t["ids"][b, :cnt[b]] for b in range(self.batch)]
-        out["rec"] = d["rec"]
+        out = dict(self._track_rows(d, ("A", "ncc", "flag", "tstate", "tmpl")), rec=d["rec"])
+        out["tmpl"] = [m[:, :e * e].reshape(-1, e, e) for m in out["tmpl"]]
         return out
 
     def position(self):
@@ -599,13 +572,12 @@ class FlowStream:
         _NONE); with ofk_set_keyframe_rotation on T, pos and C_T are those of the solve that stands; C_T [batch, 3, 3]; R_acc [batch, 3, 3]; live, members_at_key, key_step, keyframes, dead_reckoned, reason [batch];
         ids: per stream the ids of the keyframe's members among the tracks that step returned, from the track table; rec)."""
         d = self.ctx.keyframe_download(self.batch)
-        t = self.ctx.track_table_download(self.batch)
-        cnt, rec = t["stats"][:, 0], d["rec"]
+        rows, rec = self._track_rows(d, ("member",)), d["rec"]
         out = dict(pos=rec[:, 13:16].copy(), D=rec[:, 10:13].copy(), T=rec[:, 0:3].copy(), flag=rec[:, 3].astype(np.int32),
                    C_T=ofk.cov_matrix(rec[:, 20:26]), R_acc=d["R_acc"], rec=rec)
         for k, s in (("members_at_key", 7), ("key_step", 8), ("reason", 9), ("keyframes", 26), ("dead_reckoned", 27), ("live", 28)):
             out[k] = rec[:, s].astype(np.int32)
-        out["ids"] = [t["ids"][b, :cnt[b]][d["member"][b, :cnt[b]] != 0] for b in range(self.batch)]
+        out["ids"] = [i[m != 0] for i, m in zip(rows["ids"], rows["member"])]
         return out
 
     def key_rotation(self):

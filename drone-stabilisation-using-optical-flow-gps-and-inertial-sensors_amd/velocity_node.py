@@ -96,6 +96,27 @@ def gyro_bias_step(x, u, d, n, omega_raw, state=None, **settings):
     return out[:3].copy(), R, rank, out[5:8].copy(), st
 
 
+def _struct_field(name, value, **beside):
+    """One per-track setting of optical_fusion.__init__ as the PipelineConfig field it becomes: None / False -> {} (off); True, the
+    ofk structure or a dict of ofk.<name>_setting's keywords -> {name: True or the structure}.  Invalid fields fail here, not at the
+    first frame: the field goes through PipelineConfig(**beside, name=...).<name>_setting() once."""
+    if value is None or value is False:
+        return {}
+    field = {name: value if value is True or isinstance(value, dict(ofk.SETTINGS)[name]) else getattr(ofk, name + "_setting")(**dict(value))}
+    getattr(PipelineConfig(**beside, **field), name + "_setting")()
+    return field
+
+
+# optical_fusion.last_<name>: the FlowStream reader and the keys it publishes
+_LAST_PER_TRACK = {
+    "track_depth": (FlowStream.depths, ("rho", "var", "nobs", "ids", "rec")),
+    "keyframe": (FlowStream.position, ("pos", "D", "T", "flag", "C_T", "R_acc", "live", "members_at_key", "key_step", "keyframes", "dead_reckoned",
+                                       "reason", "ids", "rec")),
+    "keyframe_rotation": (FlowStream.key_rotation, ("delta", "R_hat", "C_delta", "flag", "prior", "eig", "iterations", "rec")),
+    "track_template": (FlowStream.templates, ("A", "ncc", "flag", "tstate", "ids", "rec")),
+}
+
+
 def track_depth_step(x, u, omega, v, state=None, status=None, solved=True, new_count=None, max_total=None, **settings):
     """One step of a stream's depths per track without images (ofk.h: ofk_track_depth_step): the map solve from the depths in
     `state`, then measurement, prediction and compaction.  x, u [n,2]: the solve's points and flow; omega, v: what the step's solve
@@ -519,19 +540,10 @@ class optical_fusion:
             self.last_gyro_bias = fs.gyro_bias()[0]
         if self._plane and r[15]:
             self.last_plane = fs.planes()[0]
-        if self._track_depth:
-            dp = fs.depths()
-            self.last_track_depth = {k: dp[k][0] for k in ("rho", "var", "nobs", "ids", "rec")}
-        if self._keyframe:
-            kp = fs.position()
-            self.last_keyframe = {k: kp[k][0] for k in ("pos", "D", "T", "flag", "C_T", "R_acc", "live", "members_at_key", "key_step", "keyframes",
-                                                        "dead_reckoned", "reason", "ids", "rec")}
-        if self._keyframe_rotation:
-            kq = fs.key_rotation()
-            self.last_keyframe_rotation = {k: kq[k][0] for k in ("delta", "R_hat", "C_delta", "flag", "prior", "eig", "iterations", "rec")}
-        if self._track_template:
-            tp = fs.templates()
-            self.last_track_template = {k: tp[k][0] for k in ("A", "ncc", "flag", "tstate", "ids", "rec")}
+        for name, (read, keys) in _LAST_PER_TRACK.items():       # stream 0's entry of every key
+            if getattr(self, "_" + name):
+                d = read(fs)
+                setattr(self, "last_" + name, {k: d[k][0] for k in keys})
         if self._epipolar and r[15]:
             rec, pts = fs.structure()
             self.last_epipolar = (rec[0], pts[0])
@@ -740,47 +752,13 @@ class optical_fusion:
             PipelineConfig(**self._lk_light).lk_light_setting()      # invalid fields fail here, not at the first frame
         else:
             self._lk_light = {}
-        if track_table is not None and track_table is not False:
-            tt = track_table if track_table is True or isinstance(track_table, ofk.TrackTable) else ofk.track_table_setting(**dict(track_table))
-            self._track_table = dict(track_table=tt)
-            PipelineConfig(**self._track_table).track_table_setting()    # invalid fields fail here, not at the first frame
-        else:
-            self._track_table = {}
-        if track_depth is not None and track_depth is not False:
-            td = track_depth if track_depth is True or isinstance(track_depth, ofk.TrackDepth) else ofk.track_depth_setting(**dict(track_depth))
-            self._track_depth = dict(track_depth=td)
-            PipelineConfig(**self._track_depth).track_depth_setting()    # invalid fields fail here, not at the first frame
-            if not self._track_table:
-                self._track_table = dict(track_table=True)           # the depths are kept per row of the table
-        else:
-            self._track_depth = {}
-        self.last_track_depth = None
-        if track_template is not None and track_template is not False:
-            tp = track_template if track_template is True or isinstance(track_template, ofk.TrackTemplate) else ofk.track_template_setting(**dict(track_template))
-            self._track_template = dict(track_template=tp)
-            PipelineConfig(**self._track_template).track_template_setting()    # invalid fields fail here, not at the first frame
-            if not self._track_table:
-                self._track_table = dict(track_table=True)           # the templates are kept per row of the table
-        else:
-            self._track_template = {}
-        self.last_track_template = None
-        if keyframe is not None and keyframe is not False:
-            kf = keyframe if keyframe is True or isinstance(keyframe, ofk.Keyframe) else ofk.keyframe_setting(**dict(keyframe))
-            self._keyframe = dict(keyframe=kf)
-            PipelineConfig(**self._keyframe).keyframe_setting()          # invalid fields fail here, not at the first frame
-            if not self._track_table:
-                self._track_table = dict(track_table=True)           # the keyframe is kept per row of the table
-        else:
-            self._keyframe = {}
-        self.last_keyframe = None
-        if keyframe_rotation is not None and keyframe_rotation is not False:
-            kq = keyframe_rotation if keyframe_rotation is True or isinstance(keyframe_rotation, ofk.KeyframeRotation) \
-                else ofk.keyframe_rotation_setting(**dict(keyframe_rotation))
-            self._keyframe_rotation = dict(keyframe_rotation=kq)
-            PipelineConfig(**self._keyframe, **self._keyframe_rotation).keyframe_rotation_setting()   # needs the keyframe; fails here
-        else:
-            self._keyframe_rotation = {}
-        self.last_keyframe_rotation = None
+        given = dict(track_table=track_table, track_depth=track_depth, track_template=track_template, keyframe=keyframe,
+                     keyframe_rotation=keyframe_rotation)
+        for name, value in given.items():                        # the rotation's check reads the keyframe, set in front of it
+            setattr(self, "_" + name, _struct_field(name, value, **(self._keyframe if name == "keyframe_rotation" else {})))
+        if (self._track_depth or self._track_template or self._keyframe) and not self._track_table:
+            self._track_table = dict(track_table=True)           # the three are kept per row of the table
+        self.last_track_depth = self.last_track_template = self.last_keyframe = self.last_keyframe_rotation = None
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

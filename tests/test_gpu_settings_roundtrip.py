@@ -1,4 +1,4 @@
-"""What the twelve struct settings and the three point corrections promise at the C boundary (include/ofk.h), pinned byte for byte.
+"""What the seventeen struct settings and the three point corrections promise at the C boundary (include/ofk.h), pinned byte for byte.
 
 Every ofk_set_* / ofk_get_* pair: get after a valid set returns the same bytes; NULL switches the setting off the way that setter
 does it (they differ: which fields are cleared, whether a struct whose mode is OFF counts as NULL); an invalid struct is refused with
@@ -63,11 +63,25 @@ def cases(ofk):
         "gyro_bias": (ofk.GyroBias, ofk.GyroBias(1, 0.3, 2e-5, 1e-12, d3(1e-2, 0.0, 1e4), d3(1e-3, -2e-3, 0.0), 9.5, 1),
                       ofk.GyroBias(1, 0.3, 2e-5, 1e-12, d3(1e-2, 1e160, 1e4), d3(1e-3, -2e-3, 0.0), 9.5, 1),
                       "ofk_set_gyro_bias: the square of p0[1] is not finite (1e+160)", dict(mode=0)),
+        "track_table": (ofk.TrackTable, ofk.TrackTable(ofk.TT_ON, ofk.TT_SEED_FLOW, 0.75), ofk.TrackTable(ofk.TT_ON, 5, 0.75),
+                        "ofk_set_track_table: seed 5 is neither OFK_TT_SEED_OFF nor OFK_TT_SEED_FLOW", dict(mode=0)),
+        "track_depth": (ofk.TrackDepth, ofk.TrackDepth(1, 0.3, 0.25, 2.5, 1e-6, 4, 0.3, 9, 0), ofk.TrackDepth(1, 0.3, 0.25, 2.5, 1e-6, 4, 0.3, 2, 0),
+                        "ofk_set_track_depth: min_rows = 2 must be at least 3", dict(mode=0)),
+        "track_template": (ofk.TrackTemplate, ofk.TrackTemplate(1, 9, 0.7, 2, 1.5, ofk.TPL_DROP, 7, 1.5, 1.25),
+                           ofk.TrackTemplate(1, 4, 0.7, 2, 1.5, ofk.TPL_DROP, 7, 1.5, 1.25),
+                           "ofk_set_track_template: win = 4 must be odd and in 5..31", dict(mode=0)),
+        "keyframe": (ofk.Keyframe, ofk.Keyframe(1, 0.3, 1.5, 9, 0.25, 0.4, 12), ofk.Keyframe(1, 0.3, 1.5, 9, 1.5, 0.4, 12),
+                     "ofk_set_keyframe: min_share = 1.5 outside [0, 1]", dict(mode=0)),
+        "keyframe_rotation": (ofk.KeyframeRotation, ofk.KeyframeRotation(1, ofk.KEYROT_ATTITUDE, (C.c_int * 3)(1, 0, 1), 1e-3, 2e-4, 3e-3, 3, 0.05),
+                              ofk.KeyframeRotation(1, ofk.KEYROT_ATTITUDE, (C.c_int * 3)(1, 0, 1), 1e-3, 2e-4, 3e-3, 9, 0.05),
+                              "ofk_set_keyframe_rotation: iters = 9 outside 1..8", dict(mode=0)),    # 8: OFK_KEYROT_MAX_ITERS
     }
 
 
-NAMES = ["robust", "cov", "joint", "plane", "epipolar", "track_gate", "corner_grid", "zones", "camera", "rolling_shutter", "finite_motion", "gyro_bias"]
-OFF_IS_NULL = ("robust", "camera", "rolling_shutter", "finite_motion", "gyro_bias")        # a struct whose mode is OFF is not read beyond the mode
+NAMES = ["robust", "cov", "joint", "plane", "epipolar", "track_gate", "corner_grid", "zones", "camera", "rolling_shutter", "finite_motion", "gyro_bias",
+         "track_table", "track_depth", "track_template", "keyframe", "keyframe_rotation"]
+OFF_IS_NULL = ("robust", "camera", "rolling_shutter", "finite_motion", "gyro_bias", "track_table", "track_depth", "track_template", "keyframe",
+               "keyframe_rotation")       # a struct whose mode is OFF is not read beyond the mode
 OFF_IS_COPIED = ("joint", "plane", "epipolar")                                 # ... is checked and copied whole
 
 
