@@ -13,6 +13,7 @@ import robust_reference as rr
 import robust_stream_oracle as rso
 import zones_reference as zr
 from point_stage_helpers import bits
+from zones_edge_cases import NONE, rejects, run_steps
 
 pytestmark = pytest.mark.gpu
 
@@ -24,44 +25,6 @@ def zctx(ofk):
     c = ofk.Context(0, W, H, B, S, 2)
     yield c
     c.close()
-
-
-def rejects(pts, flow=(0.0, 0.0)):
-    """One stream's step from reject positions: (old, new, status, keep)."""
-    old = np.asarray(pts, np.float32).reshape(-1, 2)
-    return old, old + np.asarray(flow, np.float32), np.ones(len(old), np.uint8), np.zeros(len(old), np.uint8)
-
-
-NONE = rejects(np.zeros((0, 2)))
-
-
-def run_steps(ctx, setting, steps, h, w, masks=None):
-    """steps: per step a list of B streams' (old, new, status, keep).  Compares mask, table and statistics behind every step and
-    returns the reference tables and the last masks."""
-    s = dict(zr.DEFAULT, **setting)
-    ctx.set_zones(**s)
-    ctx.zones_reset()
-    tables = [zr.Table() for _ in range(B)]
-    mask = None
-    for k, streams in enumerate(steps):
-        streams = list(streams) + [NONE] * (B - len(streams))
-        old = np.zeros((B, S, 2), np.float32); new = np.zeros((B, S, 2), np.float32)
-        st = np.zeros((B, S), np.uint8); kp = np.ones((B, S), np.uint8); counts = np.zeros(B, np.int32)
-        for b, (o, n, a, q) in enumerate(streams):
-            m = len(o)
-            old[b, :m], new[b, :m], st[b, :m], kp[b, :m], counts[b] = o, n, a, q, m
-            old[b, m:] = 7.0; st[b, m:] = 1; kp[b, m:] = 0       # behind the count: never read
-        mask_in = None if masks is None else masks[k]
-        mask = ctx.zones_step(old, new, st, kp, counts, h, w, mask_in)
-        got = ctx.zones_download(B)
-        for b, (o, n, a, q) in enumerate(streams):
-            ref = zr.step(tables[b], s, o, n, a, q, h, w, None if mask_in is None else mask_in[b])
-            tag = (k, b)
-            assert np.array_equal(got["stats"][b], tables[b].stats), (tag, got["stats"][b], tables[b].stats)
-            assert np.array_equal(got["zones"][b], tables[b].zones), (tag, got["zones"][b][:, :12], tables[b].zones[:, :12])
-            assert np.array_equal(bits(got["motion"][b]), bits(tables[b].motion)), (tag, got["motion"][b], tables[b].motion)
-            assert np.array_equal(mask[b], ref), (tag, int(np.count_nonzero(mask[b] != ref)))
-    return tables, mask
 
 
 def test_few_rejects_collinear_and_identical_ones(zctx):
