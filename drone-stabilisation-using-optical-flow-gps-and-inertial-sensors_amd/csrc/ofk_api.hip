@@ -164,6 +164,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->tpl = ofk_track_template{OFK_TPL_OFF, 15, 0.8, 3, 2.0, OFK_TPL_KEEP, 6, 2.0, 1.5};
     c->key = ofk_keyframe{OFK_KEY_OFF, 0.2, 2.0, 8, 0.5, 0.5, 0};
     c->krot = ofk_keyframe_rotation{OFK_KEYROT_OFF, OFK_KEYROT_GYRO, {1, 1, 1}, 0.0, 1e-4, 1e-3, 2, 0.1};
+    c->posf = ofk_pos_filter{OFK_POSF_OFF, 1.0, 1e-3, 0.0, 1.0, 0.5, 0.0, 1e-3, 0.0, 0.0, 1.0, 0.0, 0.0};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -2470,8 +2471,10 @@ static const track_array TP_ARRAYS[] = {                         // the template
 static const track_array KF_ARRAYS[] = {TRACK_ARRAY(kfr.key_xy, 8, 0), TRACK_ARRAY(kfr.member, 1, 0), TRACK_ARRAY(kfr.st, 0, OFK_KEY_STATE * 8),
     TRACK_ARRAY(kfr.ist, 0, OFK_KEY_INTS * 4), TRACK_ARRAY(kfr.rec, 0, OFK_KEY_DOUBLES * 8), TRACK_ARRAY(kfr.next_copy, 8, 0)};
 static const track_array KR_ARRAYS[] = {TRACK_ARRAY(kr_st, 0, OFK_KEYROT_STATE * 8), TRACK_ARRAY(kr_rec, 0, OFK_KEYROT_DOUBLES * 8)};
+static const track_array PF_ARRAYS[] = {TRACK_ARRAY(pf_x, 0, OFK_POSF_STATES * 8), TRACK_ARRAY(pf_P, 0, OFK_POSF_STATES * OFK_POSF_STATES * 8),
+    TRACK_ARRAY(pf_rec, 0, OFK_POSF_DOUBLES * 8), TRACK_ARRAY(pf_in, 0, OFK_POSF_INPUT * 8), TRACK_ARRAY(pf_ist, 0, OFK_POSF_INTS * 4)};
 
-enum { TS_TABLE, TS_DEPTH, TS_TEMPLATE, TS_KEY, TS_KEYROT };
+enum { TS_TABLE, TS_DEPTH, TS_TEMPLATE, TS_KEY, TS_KEYROT, TS_POSF };
 struct track_state {
     const char *set, *download, *began;                          // the setter's and the download's names, "run" / "stepped": for messages
     bool (*on)(const ofk_ctx *);
@@ -2511,6 +2514,14 @@ static const track_state TRACK[] = {
      [](ofk_ctx *c, int B) -> int { ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, nullptr, 0, OFK_KEYROT_NONE, B); return OFK_OK; },
      [](ofk_ctx *c, int B) { ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, c->limit, 0, OFK_KEYROT_NONE, B); },
      TS_KEY, "it refines the keyframe's rotation", nullptr},
+    {"ofk_set_pos_filter", "ofk_pos_filter_download", "stepped", [](const ofk_ctx *c) { return c->posf.mode != OFK_POSF_OFF; },
+     &ofk_ctx::pf_batch, &ofk_ctx::pf_live, TRACK_LIST(PF_ARRAYS),     // per stream, not per track: a replacement of the tracks re-keys, the filter runs on
+     [](ofk_ctx *c, int B) -> int {                              // not started, at zero; an input handed in before the first step stays
+         const double zero[3] = {0.0, 0.0, 0.0};
+         ofk_launch_pos_filter_clear(c->stream, c->pf_x, c->pf_P, c->pf_ist, c->pf_rec, nullptr, 0, zero, B);
+         return OFK_OK;
+     },
+     nullptr, TS_KEY, "it fuses the keyframe's displacement", nullptr},
 };
 
 static void *&track_slot(ofk_ctx *c, const track_array &a) { return *(void **)((char *)c + a.at); }
@@ -2543,7 +2554,7 @@ static int track_begin(ofk_ctx *c, const track_state &s, int B)
 // The steps' own refusals with a state on (ofk.h), in their precedence; fu: a fused step's.
 static int track_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const char *who)
 {
-    static const int order[] = {TS_DEPTH, TS_TEMPLATE, TS_KEYROT, TS_KEY};
+    static const int order[] = {TS_DEPTH, TS_TEMPLATE, TS_KEYROT, TS_POSF, TS_KEY};
     for (int k : order) {
         const track_state &s = TRACK[k];
         if (!s.on(c)) continue;
@@ -3044,6 +3055,93 @@ extern "C" int ofk_keyframe_rotation_step(ofk_ctx *c, const ofk_keyframe *set, c
                               state, istate, new_counts, max_total, batch, stride, rec, rstate, rrec);
 }
 
+// ------------------------------------------------------------------------------------------------ position filter
+static int check_posf(ofk_ctx *c, const ofk_pos_filter *f, const char *who)
+{
+    if (f->mode != OFK_POSF_OFF && f->mode != OFK_POSF_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_POSF_OFF nor OFK_POSF_ON", who, f->mode);
+    if (f->mode == OFK_POSF_OFF) return OFK_OK;
+    const double all[] = {f->dt, f->sigma_v, f->floor, f->infl, f->share, f->q_p, f->q_v, f->q_b, f->p0_p, f->p0_v, f->p0_b, f->nis_max};
+    if (!all_finite(all, sizeof all / 8)) return ofk_fail(c, OFK_E_INVALID, "%s: every field must be finite", who);
+    if (!(f->dt > 0.0) || !(f->infl > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: dt = %g and infl = %g must be positive", who, f->dt, f->infl);
+    if (f->sigma_v < 0.0 || f->floor < 0.0 || f->q_p < 0.0 || f->q_v < 0.0 || f->q_b < 0.0 || f->p0_p < 0.0 || f->p0_v < 0.0 || f->p0_b < 0.0)
+        return ofk_fail(c, OFK_E_INVALID, "%s: sigma_v, floor, q_* and p0_* must not be negative", who);
+    if (f->share < 0.0 || f->share > 1.0) return ofk_fail(c, OFK_E_INVALID, "%s: share = %g outside [0, 1]", who, f->share);
+    if (f->nis_max < 0.0) return ofk_fail(c, OFK_E_INVALID, "%s: nis_max = %g must not be negative", who, f->nis_max);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_pos_filter(ofk_ctx *c, const ofk_pos_filter *f)
+{
+    return setting_set(c, &ofk_ctx::posf, f && f->mode == OFK_POSF_OFF ? nullptr : f, [](ofk_pos_filter &s) { s.mode = OFK_POSF_OFF; },
+                       [c](const ofk_pos_filter *v) { return check_posf(c, v, "ofk_set_pos_filter"); });
+}
+extern "C" int ofk_get_pos_filter(const ofk_ctx *c, ofk_pos_filter *f) { return setting_get(c, &ofk_ctx::posf, f); }
+
+extern "C" int ofk_pos_filter_input(ofk_ctx *c, const double *input)
+{
+    const char *who = "ofk_pos_filter_input";
+    if (!c) return OFK_E_INVALID;
+    if (c->stream_batch < 1) return ofk_fail(c, OFK_E_INVALID, "%s: no active streams", who);
+    if (!input) return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
+    TRY(enter(c));
+    TRY(track_alloc(c, TRACK[TS_POSF]));
+    OFK_HIP(c, hipMemcpyAsync(c->pf_in, input, (size_t)c->stream_batch * OFK_POSF_INPUT * 8, hipMemcpyHostToDevice, c->stream));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+extern "C" int ofk_pos_filter_reset(ofk_ctx *c, int b, const double *pos)
+{
+    const char *who = "ofk_pos_filter_reset";
+    if (!c) return OFK_E_INVALID;
+    if (c->stream_batch < 1 || b < 0 || b >= c->stream_batch) return ofk_fail(c, OFK_E_INVALID, "%s: stream %d is none of the %d active streams", who, b, c->stream_batch);
+    const double zero[3] = {0.0, 0.0, 0.0}, *p = pos ? pos : zero;
+    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return ofk_fail(c, OFK_E_INVALID, "%s: the position must be finite", who);
+    TRY(enter(c));
+    TRY(track_begin(c, TRACK[TS_POSF], c->stream_batch));
+    ofk_launch_pos_filter_clear(c->stream, c->pf_x, c->pf_P, c->pf_ist, c->pf_rec, c->pf_in, b, p, 1);
+    TRY(check_launch(c, who));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+extern "C" int ofk_pos_filter_download(ofk_ctx *c, double *x, double *P, int *istate, double *rec)
+{
+    if (!c) return OFK_E_INVALID;
+    TRY(track_download_begin(c, TRACK[TS_POSF], false, 0));
+    const download_row rows[] = {{x, c->pf_x, OFK_POSF_STATES * 8, OFK_POSF_STATES * 8},
+                                 {P, c->pf_P, OFK_POSF_STATES * OFK_POSF_STATES * 8, OFK_POSF_STATES * OFK_POSF_STATES * 8},
+                                 {istate, c->pf_ist, OFK_POSF_INTS * 4, OFK_POSF_INTS * 4}, {rec, c->pf_rec, OFK_POSF_DOUBLES * 8, OFK_POSF_DOUBLES * 8}};
+    return rows_download(c, c->pf_batch, 0, rows, 4);
+}
+
+// rules 1-8 on host buffers: device scratch only
+extern "C" int ofk_pos_filter_step(ofk_ctx *c, const ofk_pos_filter *f, const double *v_uav, const int *solved, const double *key_rec,
+                                   const double *R_world, const double *input, double *x, double *P, int *istate, int batch, double *rec)
+{
+    const char *who = "ofk_pos_filter_step";
+    if (!c) return OFK_E_INVALID;
+    if (!f || !v_uav || !solved || !key_rec || !R_world || !x || !P || !istate) return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
+    if (batch < 1) return ofk_fail(c, OFK_E_INVALID, "%s: batch %d", who, batch);
+    if (f->mode == OFK_POSF_OFF) return ofk_fail(c, OFK_E_INVALID, "%s: the setting is off", who);
+    TRY(check_posf(c, f, who));
+    const size_t B = (size_t)batch, NN = OFK_POSF_STATES * OFK_POSF_STATES;
+    const host_buf h_rec = {stage_step_records(v_uav, solved, B, 8)};
+    if (!h_rec.p) return ofk_fail(c, OFK_E_INVALID, "%s: out of host memory", who);
+    Bump bp;
+    TRY(est_begin(c, B * ((OFK_RECORD_DOUBLES + OFK_KEY_DOUBLES + 9 + OFK_POSF_INPUT + OFK_POSF_STATES + NN + OFK_POSF_DOUBLES) * 8 + OFK_POSF_INTS * 4) + 9 * 256, bp));
+    const double *d_v = bp.put(h_rec.p, B * OFK_RECORD_DOUBLES * 8), *d_key = bp.put(key_rec, B * OFK_KEY_DOUBLES * 8), *d_rw = bp.put(R_world, B * 72);
+    double *d_in = input ? bp.put(input, B * OFK_POSF_INPUT * 8) : bp.take(B * OFK_POSF_INPUT * 8);
+    double *d_x = bp.put(x, B * OFK_POSF_STATES * 8), *d_P = bp.put(P, B * NN * 8), *d_rec = bp.take(B * OFK_POSF_DOUBLES * 8);
+    int *d_ist = (int *)bp.put(istate, B * OFK_POSF_INTS * 4);
+    if (!input && bp.rc == OFK_OK && hipMemsetAsync(d_in, 0, B * OFK_POSF_INPUT * 8, c->stream) != hipSuccess) bp.rc = OFK_E_HIP;
+    if (bp.rc != OFK_OK || hipStreamSynchronize(c->stream) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    ofk_launch_pos_filter_step(c->stream, f, d_x, d_P, d_ist, d_rec, d_in, d_v, 0, d_key, d_rw, 9, batch);
+    TRY(check_launch(c, "k_pos_filter_step"));
+    const back_row back[] = {{x, d_x, B * OFK_POSF_STATES * 8}, {P, d_P, B * NN * 8}, {istate, d_ist, B * OFK_POSF_INTS * 4}, {rec, d_rec, B * OFK_POSF_DOUBLES * 8}};
+    return fetch_back(c, who, back, 4);
+}
+
 // ------------------------------------------------------------------------------------------------ video streams
 static int stream_alloc(ofk_ctx *c)
 {
@@ -3102,6 +3200,7 @@ static int stream_begin_impl(ofk_ctx *c, const uint8_t *first_bgr, int batch, in
     const ofk_levels lv = ofk_make_levels(h, w, p->win, p->max_level);
     TRY(stream_ingest(c, 0, first_bgr, batch, h, w, lv));
     TRY(stream_detect(c, nullptr, nullptr, batch, h, w, p, c->pts_prev, c->counts));
+    if (c->pf_in) OFK_HIP(c, hipMemsetAsync(c->pf_in, 0, (size_t)c->max_batch * OFK_POSF_INPUT * 8, c->stream));   // no position input waits for the new streams
     for (const track_state &s : TRACK) c->*s.batch = c->*s.live = 0;   // ... and without per-track state: the first step with a setting on starts its own,
     if (TRACK[TS_TABLE].on(c)) TRY(track_begin(c, TRACK[TS_TABLE], batch));   // but for the track table, which begins with the tracks
     c->stream_h = h; c->stream_w = w; c->stream_batch = batch;
@@ -3355,6 +3454,9 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
             in.imu = fu && fu->use_imu ? c->imu_state : nullptr; in.v = c->records; in.plain = fu ? 0 : 1;
             in.step = c->ttr.head; in.step_stride = 2;
             launch_key_step(c, c->kfr, in, &c->key, krot ? &c->krot : nullptr, c->kr_st, c->kr_rec, B);
+            if (on[TS_POSF])                                     // directly behind it, on the record it has just written
+                ofk_launch_pos_filter_step(c->stream, &c->posf, c->pf_x, c->pf_P, c->pf_ist, c->pf_rec, c->pf_in, c->records, fu ? 0 : 1, c->kfr.rec,
+                                           in.imu ? c->imu_state + 6 : c->sensors + 7, in.imu ? OFK_IMU_STATE : OFK_SENSOR_DOUBLES, B);
         }
         if (depth) {                                             // in front of the table's update, on what k_update_tracks is about to read
             const bool imu = fu && fu->use_imu;

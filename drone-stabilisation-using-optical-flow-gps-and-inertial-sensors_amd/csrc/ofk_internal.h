@@ -166,6 +166,10 @@ struct ofk_ctx {
     ofk_keyframe_rotation krot;              // ofk_set_keyframe_rotation: mode OFK_KEYROT_OFF unless set
     double *kr_st, *kr_rec;                  // [max_batch][OFK_KEYROT_STATE], [max_batch][OFK_KEYROT_DOUBLES]; one lazy allocation (kr_st owns it)
     int kr_batch, kr_live;                   // (kr_live: streams whose rotation state is in step with their keyframe) streams of the latest step with the rotation on (ofk_keyframe_rotation_download), 0 = none
+    ofk_pos_filter posf;                     // ofk_set_pos_filter: mode OFK_POSF_OFF unless set
+    double *pf_x, *pf_P, *pf_rec, *pf_in;    // [max_batch][12], [max_batch][144], [max_batch][OFK_POSF_DOUBLES], [max_batch][OFK_POSF_INPUT]; one lazy allocation (pf_x owns it)
+    int *pf_ist;                             // [max_batch][OFK_POSF_INTS]
+    int pf_batch, pf_live;                   // streams of the latest step with the position filter on (ofk_pos_filter_download), 0 = none; streams whose filter runs on
     int kf_batch, kf_live;                   // streams of the latest step with the keyframe on (ofk_keyframe_download), 0 = none; streams whose rows match their current tracks
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
@@ -306,6 +310,12 @@ void ofk_launch_keyframe_step(hipStream_t s, const ofk_kf_rows &t, const ofk_kf_
 void ofk_launch_keyframe_step_rot(hipStream_t s, const ofk_kf_rows &t, const ofk_kf_in &in, const ofk_keyframe *k, const ofk_keyframe_rotation *r,
                                   double *rst, double *rrec, int batch);
 void ofk_launch_keyrot_clear(hipStream_t s, double *rst, double *rrec, const int *limit, int b0, int flag, int batch);
+// the position filter (ofk.h: ofk_set_pos_filter; k_pos_filter.inc): rules 1-8 in one launch behind the keyframe's step (v: the step's
+// records, plain as ofk_kf_in's; key_rec: the keyframe's records; rw: R_world, rw_stride doubles apart), and the state of `batch`
+// streams from b0 on set back to "not started" at the position p (input NULL: the input rows stay)
+void ofk_launch_pos_filter_step(hipStream_t s, const ofk_pos_filter *f, double *x, double *P, int *ist, double *rec, double *input, const double *v,
+                                int plain, const double *key_rec, const double *rw, int rw_stride, int batch);
+void ofk_launch_pos_filter_clear(hipStream_t s, double *x, double *P, int *ist, double *rec, double *input, int b0, const double *p, int batch);
 // the track templates (ofk.h: ofk_set_track_template; k_track_template.inc): rule 1, rules 2-5 behind the gates, rule 6 in front of the table's update
 void ofk_launch_track_affine(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts, int stride,
                              int h, int w, const ofk_track_template *d, float *L, double *rec, int batch);

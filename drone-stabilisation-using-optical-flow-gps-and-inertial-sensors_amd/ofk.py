@@ -44,6 +44,7 @@ SYMBOLS = (
     "ofk_set_track_depth", "ofk_get_track_depth", "ofk_track_depth_download", "ofk_track_depth_reset", "ofk_track_depth_step",
     "ofk_set_keyframe", "ofk_get_keyframe", "ofk_keyframe_download", "ofk_keyframe_reset", "ofk_keyframe_step",
     "ofk_set_keyframe_rotation", "ofk_get_keyframe_rotation", "ofk_keyframe_rotation_download", "ofk_keyframe_rotation_step",
+    "ofk_set_pos_filter", "ofk_get_pos_filter", "ofk_pos_filter_input", "ofk_pos_filter_reset", "ofk_pos_filter_download", "ofk_pos_filter_step",
     "ofk_set_track_template", "ofk_get_track_template", "ofk_track_template_download", "ofk_track_affine_fit", "ofk_track_template_step",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
@@ -120,6 +121,9 @@ KEYROT_OFF, KEYROT_ON = 0, 1                             # ofk_set_keyframe_rota
 KEYROT_GYRO, KEYROT_ATTITUDE = 0, 1                      # where R_acc comes from
 KEYROT_DOUBLES, KEYROT_STATE, KEYROT_MAX_ITERS = 40, 12, 8   # the record; R_world at the keyframe, valid, its key_step
 KEYROT_OK, KEYROT_NONE, KEYROT_SINGULAR, KEYROT_LARGE, KEYROT_HELD = 0, 1, 2, 3, 4   # the record's flag
+POSF_OFF, POSF_ON = 0, 1                                 # ofk_set_pos_filter
+POSF_STATES, POSF_INPUT, POSF_INTS, POSF_DOUBLES = 12, 12, 16, 48   # x = (p, v, b, c); the input row; the counts; the record
+POSF_NOT, POSF_APPLIED, POSF_GATED, POSF_REFUSED = 0, 1, 2, 3       # an update's outcome in the record
 TPL_OFF, TPL_ON = 0, 1                                   # ofk_set_track_template
 TPL_DOUBLES = 32                                         # M, t, fit flag, rows of the two fits, rms, nine counts, largest move
 TPL_KEEP, TPL_DROP = 0, 1
@@ -580,6 +584,33 @@ def keyframe_rotation_setting(mode=True, source="gyro", axes=(1, 1, 1), sigma_gy
     return r
 
 
+class PosFilter(C.Structure):
+    """ofk_pos_filter (include/ofk.h): keyframe displacement, velocity and position fixes fused in a filter with a cloned state."""
+    _fields_ = [("mode", C.c_int), ("dt", C.c_double), ("sigma_v", C.c_double), ("floor", C.c_double), ("infl", C.c_double), ("share", C.c_double),
+                ("q_p", C.c_double), ("q_v", C.c_double), ("q_b", C.c_double), ("p0_p", C.c_double), ("p0_v", C.c_double), ("p0_b", C.c_double),
+                ("nis_max", C.c_double)]
+
+
+def pos_filter_setting(mode=True, dt=1.0, sigma_v=1e-3, floor=0.0, infl=1.0, share=0.5, q_p=0.0, q_v=1e-3, q_b=0.0, p0_p=0.0, p0_v=1.0, p0_b=0.0,
+                       nis_max=0.0):
+    """A PosFilter structure from names: mode True / False (or POSF_*); dt: the step's length in the time unit of v; sigma_v: the
+    sigma of v_uav as a velocity measurement (0: not used); the keyframe's D enters with C = infl^2 R_world C_T R_world^T + floor^2 I,
+    of which `share` is the key pixels' part, added once per keyframe to the clone; q_p, q_v, q_b: process noise per step; p0_p,
+    p0_v, p0_b: the prior's sigmas (a block with p0 = q = 0 is held); nis_max: an update whose NIS exceeds it is gated (0: none)."""
+    mode = int(mode)
+    if mode not in (POSF_OFF, POSF_ON):
+        raise ValueError(f"position-filter mode {mode} is none of POSF_OFF, POSF_ON")
+    f = PosFilter(mode, *[float(v) for v in (dt, sigma_v, floor, infl, share, q_p, q_v, q_b, p0_p, p0_v, p0_b, nis_max)])
+    if mode != POSF_OFF:
+        vals = [getattr(f, n) for n, _ in PosFilter._fields_[1:]]
+        if not all(np.isfinite(v) for v in vals):
+            raise ValueError("every field of the position-filter setting must be finite")
+        if not (f.dt > 0 and f.infl > 0 and 0 <= f.share <= 1 and min(f.sigma_v, f.floor, f.q_p, f.q_v, f.q_b, f.p0_p, f.p0_v, f.p0_b, f.nis_max) >= 0):
+            raise ValueError(f"position-filter setting outside its range: dt {f.dt} > 0, infl {f.infl} > 0, share {f.share} in [0, 1], "
+                             f"sigma_v, floor, q_*, p0_* and nis_max >= 0")
+    return f
+
+
 class Fusion(C.Structure):
     """ofk_fusion (include/ofk.h): what ofk_stream_step_fused does between LK and the next frame."""
     _fields_ = [("use_imu", C.c_int), ("flow", C.c_int), ("keep", C.c_int), ("filter", C.c_int), ("control", C.c_int),
@@ -591,7 +622,7 @@ class Fusion(C.Structure):
 SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("gyro_bias", GyroBias), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate), ("lk_light", LkLight),
             ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion),
             ("track_table", TrackTable), ("track_depth", TrackDepth), ("track_template", TrackTemplate), ("keyframe", Keyframe),
-            ("keyframe_rotation", KeyframeRotation))
+            ("keyframe_rotation", KeyframeRotation), ("pos_filter", PosFilter))
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -695,6 +726,10 @@ def load_library():
         L.ofk_keyframe_rotation_download.argtypes = [vp, vp]
         L.ofk_keyframe_rotation_step.argtypes = [vp, C.POINTER(Keyframe), C.POINTER(KeyframeRotation), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i,
                                                  i, i, vp, vp, vp]
+        L.ofk_pos_filter_input.argtypes = [vp, vp]
+        L.ofk_pos_filter_reset.argtypes = [vp, i, vp]
+        L.ofk_pos_filter_download.argtypes = [vp, vp, vp, vp, vp]
+        L.ofk_pos_filter_step.argtypes = [vp, C.POINTER(PosFilter), vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
         L.ofk_track_template_download.argtypes = [vp, vp, vp, vp, vp, vp, i, vp]
         L.ofk_track_affine_fit.argtypes = [vp, C.POINTER(TrackTemplate), vp, vp, vp, vp, i, i, i, i, vp, vp]
         L.ofk_track_template_step.argtypes = [vp, C.POINTER(TrackTemplate), vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
@@ -1344,6 +1379,63 @@ class Context:
         rot = rotation if rotation is not None else keyframe_rotation_setting()
         return self._keyframe_step("keyframe_rotation_step", kf, rot, next_pts, status, counts, sensors, v_uav, solved, step, state, new_counts,
                                    max_total)
+
+    def set_pos_filter(self, pos_filter=None, **settings):
+        """ofk_set_pos_filter: a PosFilter (or pos_filter_setting's keywords); None or mode False switches it off.  Every later stream
+        step with ofk_set_keyframe on (it must be) runs the stream's position filter behind the keyframe's step.  pairs_run ignores it."""
+        self._set_struct(self._L.ofk_set_pos_filter, pos_filter, settings, pos_filter_setting, lock=True)
+
+    def get_pos_filter(self):
+        return self._get_struct(self._L.ofk_get_pos_filter, PosFilter)
+
+    def pos_filter_input(self, input):
+        """ofk_pos_filter_input: input [active streams, 12] f64 for the next step that is not held: du 0-2, fix valid 3, the fix 4-6, its
+        sigmas 7-9."""
+        a = _arr(input, np.float64)
+        if a.ndim != 2 or a.shape[1] != POSF_INPUT or a.shape[0] > self.max_batch:
+            raise ValueError(f"pos_filter_input: input {a.shape} is not [streams <= {self.max_batch}, {POSF_INPUT}]")
+        full = np.zeros((self.max_batch, POSF_INPUT), np.float64)    # the library reads a row per active stream
+        full[:len(a)] = a
+        with self._lock:
+            self._ck(self._L.ofk_pos_filter_input(self._h, _p(full)))
+
+    def pos_filter_reset(self, stream, pos=None):
+        """ofk_pos_filter_reset: active stream `stream` starts over at the position `pos` (None: zero) with its next step."""
+        a = None if pos is None else _arr(pos, np.float64, (3,))
+        with self._lock:
+            self._ck(self._L.ofk_pos_filter_reset(self._h, int(stream), _p(a)))
+
+    def pos_filter_download(self, batch=None):
+        """ofk_pos_filter_download -> dict(x [batch,12], P [batch,12,12], istate [batch,16] i32, rec [batch,48]) of the streams of the
+        latest step with the setting on.  rec: x 0-11, P_pp's upper triangle 12-17, P_vv's 18-23, trace of P_bb 24, per update
+        (velocity 25-29, displacement 30-34, fix 35-39) outcome, NIS, innovation; cloned 40, fresh 41, steps 42, clones 43, updates
+        applied / gated / refused 44-46, started this step 47."""
+        x, P, ist, rec = self._rows("pos_filter_download", self.max_batch if batch is None else int(batch),
+                                    lambda *p: self._L.ofk_pos_filter_download(self._h, *p), ((POSF_STATES,), np.float64),
+                                    ((POSF_STATES, POSF_STATES), np.float64), ((POSF_INTS,), np.int32), ((POSF_DOUBLES,), np.float64))
+        return dict(x=x, P=P, istate=ist, rec=rec)
+
+    def pos_filter_step(self, v_uav, solved, key_rec, R_world, state=None, input=None, pos_filter=None, **settings):
+        """ofk_pos_filter_step, the stage entry: rules 1-8 on host arrays.  v_uav [B,3], solved [B] of the step's record; key_rec
+        [B,32] the keyframe's record of the step; R_world [B,3,3]; state: dict(x [B,12], P [B,12,12], istate [B,16] i32) of the
+        previous call (None: not started, at zero); input [B,12] (None: none); the setting a PosFilter or pos_filter_setting's
+        keywords.  -> (state, rec [B,48]), new arrays.  Touches no resident state."""
+        f = pos_filter if pos_filter is not None else pos_filter_setting(**settings)
+        vu = _arr(v_uav, np.float64)
+        if vu.ndim != 2 or vu.shape[1] != 3 or vu.shape[0] < 1:
+            raise ValueError(f"pos_filter_step: v_uav {vu.shape} is not [B >= 1, 3]")
+        B = vu.shape[0]
+        so = _arr(solved, np.int32, (B,)); kr = _arr(key_rec, np.float64, (B, KEY_DOUBLES)); rw = _arr(R_world, np.float64, (B, 3, 3))
+        state = state or {}
+        x = np.zeros((B, POSF_STATES), np.float64) if state.get("x") is None else np.array(_arr(state["x"], np.float64, (B, POSF_STATES)))
+        P = np.zeros((B, POSF_STATES, POSF_STATES), np.float64) if state.get("P") is None \
+            else np.array(_arr(state["P"], np.float64, (B, POSF_STATES, POSF_STATES)))
+        ist = np.zeros((B, POSF_INTS), np.int32) if state.get("istate") is None else np.array(_arr(state["istate"], np.int32, (B, POSF_INTS)))
+        inp = _opt(input, np.float64, (B, POSF_INPUT))
+        rec = np.zeros((B, POSF_DOUBLES), np.float64)
+        with self._lock:
+            self._ck(self._L.ofk_pos_filter_step(self._h, C.byref(f), _p(vu), _p(so), _p(kr), _p(rw), _p(inp), _p(x), _p(P), _p(ist), B, _p(rec)))
+        return dict(x=x, P=P, istate=ist), rec
 
     def zones_reset(self, batch=None):
         """ofk_zones_reset: the zone tables of the first `batch` streams (all by default) are cleared."""

@@ -181,6 +181,9 @@ class PipelineConfig:
     # keyframe_rotation (ofk.h: ofk_set_keyframe_rotation): None, True (the defaults) or an ofk.KeyframeRotation: the keyframe's solve
     # refines the accumulated rotation together with the translation; it needs keyframe on
     keyframe_rotation: object = None
+    # pos_filter (ofk.h: ofk_set_pos_filter): None, True (the defaults) or an ofk.PosFilter: every stream fuses the keyframe's
+    # displacement, the step's velocity and position fixes in a filter with a cloned state; it needs keyframe on; FlowPipeline ignores it
+    pos_filter: object = None
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -307,6 +310,18 @@ class PipelineConfig:
             raise ValueError("keyframe_rotation needs keyframe on")
         return m
 
+    def pos_filter_setting(self):
+        """The ofk.PosFilter structure of this configuration, None when the position filter is off."""
+        if self.pos_filter is None or self.pos_filter is False:
+            return None
+        m = ofk.pos_filter_setting() if self.pos_filter is True else self.pos_filter
+        if not isinstance(m, ofk.PosFilter):
+            raise ValueError(f"pos_filter {m!r} is neither None, True nor an ofk.PosFilter")
+        m = ofk.pos_filter_setting(*[getattr(m, n) for n, _ in ofk.PosFilter._fields_])   # range-checked
+        if m.mode != ofk.POSF_OFF and self.keyframe_setting() is None:
+            raise ValueError("pos_filter needs keyframe on")
+        return None if m.mode == ofk.POSF_OFF else m
+
     def track_template_setting(self):
         """The ofk.TrackTemplate structure of this configuration, None when the templates are off."""
         return self._struct_setting("track_template", ofk.TrackTemplate, ofk.track_template_setting)
@@ -430,7 +445,8 @@ def _apply_settings(ctx, cfg, zones):
     if zones:
         steps += [(ctx.set_zones, cfg.zones_setting), (ctx.set_gyro_bias, cfg.gyro_bias_setting), (ctx.set_track_table, cfg.track_table_setting),
                   (ctx.set_track_depth, cfg.track_depth_setting), (ctx.set_track_template, cfg.track_template_setting),
-                  (ctx.set_keyframe, cfg.keyframe_setting), (ctx.set_keyframe_rotation, cfg.keyframe_rotation_setting)]
+                  (ctx.set_keyframe, cfg.keyframe_setting), (ctx.set_keyframe_rotation, cfg.keyframe_rotation_setting),
+                  (ctx.set_pos_filter, cfg.pos_filter_setting)]
     steps += [(ctx.set_camera, cfg.camera_setting), (ctx.set_rolling_shutter, cfg.rolling_shutter_setting),
               (ctx.set_finite_motion, cfg.finite_motion_setting)]
     for setter, setting in steps:                                # every *_setting() is None when its setting is off
@@ -588,6 +604,36 @@ class FlowStream:
         return dict(delta=rec[:, 0:3].copy(), R_hat=rec[:, 4:13].reshape(-1, 3, 3).copy(), C_delta=ofk.cov_matrix(rec[:, 13:19]),
                     flag=rec[:, 3].astype(np.int32), prior=rec[:, 28:31].copy(), eig=rec[:, 25:28].copy(), iterations=rec[:, 31].astype(np.int32),
                     rec=rec)
+
+    def position_input(self, du=None, fix=None, fix_sigma=None):
+        """What the position filter takes in with the next step that is not held (ofk.h: ofk_pos_filter_input): du [batch, 3] the
+        velocity increment over the step in the world frame (None: none); fix [batch, 3] an absolute position with fix_sigma (a
+        number, [3] or [batch, 3]; None with a fix: ValueError).  A row of fix with a NaN marks a stream without a fix."""
+        row = np.zeros((self.batch, ofk.POSF_INPUT), np.float64)
+        if du is not None:
+            row[:, 0:3] = np.broadcast_to(np.asarray(du, np.float64), (self.batch, 3))
+        if fix is not None:
+            if fix_sigma is None:
+                raise ValueError("position_input: a fix needs fix_sigma")
+            f = np.broadcast_to(np.asarray(fix, np.float64), (self.batch, 3))
+            has = np.isfinite(f).all(axis=1)
+            row[:, 3] = has
+            row[:, 4:7] = np.where(has[:, None], f, 0.0)
+            row[:, 7:10] = np.broadcast_to(np.asarray(fix_sigma, np.float64), (self.batch, 3))
+        self.ctx.pos_filter_input(row)
+
+    def fused_position(self):
+        """The streams' position filter behind the latest step (ofk.h: ofk_set_pos_filter): dict(p, v, b, c [batch, 3]; P [batch, 12,
+        12]; P_pp [batch, 3, 3]; nis, outcome [batch, 3] and innovation [batch, 3, 3] of the velocity, displacement and fix updates
+        (outcome ofk.POSF_*); cloned [batch]; counts: dict(steps, fresh, clones [batch], velocity, displacement, fix [batch, 3]:
+        applied, gated, refused); rec [batch, 48])."""
+        d = self.ctx.pos_filter_download(self.batch)
+        x, rec, ist = d["x"], d["rec"], d["istate"]
+        upd = rec[:, 25:40].reshape(-1, 3, 5)
+        return dict(p=x[:, 0:3].copy(), v=x[:, 3:6].copy(), b=x[:, 6:9].copy(), c=x[:, 9:12].copy(), P=d["P"], P_pp=d["P"][:, 0:3, 0:3].copy(),
+                    nis=upd[:, :, 1].copy(), outcome=upd[:, :, 0].astype(np.int32), innovation=upd[:, :, 2:5].copy(), cloned=rec[:, 40].astype(np.int32),
+                    counts=dict(steps=ist[:, 0].copy(), fresh=ist[:, 1].copy(), clones=ist[:, 2].copy(), velocity=ist[:, 4:7].copy(),
+                                displacement=ist[:, 7:10].copy(), fix=ist[:, 10:13].copy()), rec=rec)
 
     def begin(self, first_bgr):
         return self.ctx.stream_begin(first_bgr, self._params)

@@ -74,6 +74,13 @@ def keyframe_rotation_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None,
     return step(np.asarray(next_pts, np.float32)[:, :2], sensors, v_uav, state=state, **kw)
 
 
+def pos_filter_step(v_uav, key_rec, R_world=None, state=None, **kw):
+    """One step of a stream's position filter without images (ofk.h: ofk_pos_filter_step); velocity_node.pos_filter_step's arguments
+    and returns: (state dict(x, P, istate), rec [48])."""
+    from .velocity_node import pos_filter_step as step
+    return step(v_uav, key_rec, R_world, state=state, **kw)
+
+
 def track_depth_step(x, u, omega, v, state=None, **kw):
     """One step of a stream's depths per track without images (ofk.h: ofk_track_depth_step); velocity_node.track_depth_step's
     arguments and returns: (state dict(rho, var, nobs), rec [32])."""

@@ -213,6 +213,30 @@ def keyframe_rotation_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None,
     return _keyframe_state(out, count), rec[0], rrec[0]
 
 
+def pos_filter_step(v_uav, key_rec, R_world=None, state=None, solved=True, du=None, fix=None, fix_sigma=None, **settings):
+    """One step of a stream's position filter without images (ofk.h: ofk_pos_filter_step): predict, the velocity, displacement and fix
+    updates, the clone at a re-key.  v_uav [3], solved: the step record's fields 8-10 and its solved flag; key_rec [32]: the
+    keyframe's record of the step (keyframe_step's rec); R_world [3,3] (None: the identity); state: the dict(x, P, istate) of the
+    previous call (None: not started, at zero; dict(x=[px, py, pz, 0, ...]) starts elsewhere); du [3]: the velocity increment of
+    the step; fix [3] with fix_sigma (a number or [3]): an absolute position; settings: ofk.pos_filter_setting's keywords.
+    Returns (state, rec [48]): rec[0:3] is the position, rec[25], rec[30], rec[35] the updates' outcomes (ofk.POSF_*)."""
+    inp = np.zeros((1, ofk.POSF_INPUT), np.float64)
+    if du is not None:
+        inp[0, 0:3] = np.asarray(du, np.float64).reshape(3)
+    if fix is not None:
+        if fix_sigma is None:
+            raise ValueError("pos_filter_step: a fix needs fix_sigma")
+        inp[0, 3] = 1.0
+        inp[0, 4:7] = np.asarray(fix, np.float64).reshape(3)
+        inp[0, 7:10] = np.broadcast_to(np.asarray(fix_sigma, np.float64), (3,))
+    st = None if state is None else {k: None if state.get(k) is None else np.asarray(state[k])[None] for k in ("x", "P", "istate")}
+    rw = np.eye(3) if R_world is None else np.asarray(R_world, np.float64).reshape(3, 3)
+    out, rec = ofk.default_context().pos_filter_step(np.asarray(v_uav, np.float64).reshape(1, 3), [1 if solved else 0],
+                                                     np.asarray(key_rec, np.float64).reshape(1, ofk.KEY_DOUBLES), rw[None], state=st, input=inp,
+                                                     **settings)
+    return {k: a[0].copy() for k, a in out.items()}, rec[0]
+
+
 def track_template_step(prev, next, prev_pts, next_pts, state=None, status=None, age=None, L=None, new_count=None, max_total=None, **settings):
     """One step of a stream's track templates on two gray frames (ofk.h: ofk_track_affine_fit, ofk_track_template_step): the step map
     fitted to the tracked rows (unless L [4] is given), then capture, score, re-anchoring, verdict and compaction.  prev, next [h,w]
@@ -337,6 +361,8 @@ class optical_fusion:
     _track_table = {}                                            # PipelineConfig's track_table field; empty: the tracks are anonymous points
     _track_depth = {}                                            # PipelineConfig's track_depth field; empty: no depth per track
     _keyframe_rotation = {}                                      # PipelineConfig's keyframe_rotation field; empty: R_acc is taken as exact
+    _pos_filter = {}                                             # PipelineConfig's pos_filter field; empty: no position filter
+    _fix = None                                                  # (position, sigma) of call_fix, handed to the filter with the next frame
     _keyframe = {}                                               # PipelineConfig's keyframe field; empty: no position against a keyframe
     _track_template = {}                                         # PipelineConfig's track_template field; empty: no template per track
     _rolling_shutter = {}                                        # PipelineConfig's rolling_shutter field; empty: every row is taken as exposed at the time stamp
@@ -496,7 +522,7 @@ class optical_fusion:
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
                                  **self._cov, **self._joint, **self._plane, **self._epipolar, **self._zones, **self._camera, **self._rolling_shutter,
                                  **self._finite_motion, **self._gyro_bias, **self._lk_light, **self._track_table, **self._track_depth,
-                                 **self._track_template, **self._keyframe, **self._keyframe_rotation)
+                                 **self._track_template, **self._keyframe, **self._keyframe_rotation, **self._pos_filter)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -518,6 +544,9 @@ class optical_fusion:
         # carries what call_imu does not own
         sc, ccx, ccy = self._camera["camera"].sensor_slots() if self._camera else (self.scaling, translation[0], translation[1])
         sensors = ofk.make_sensors(1, d=self.d, offset=self.offset, scaling=sc, cx=ccx, cy=ccy)
+        if self._pos_filter and self._fix is not None:           # call_fix: with this frame's step (a held step keeps it on the device)
+            fs.position_input(fix=self._fix[0], fix_sigma=self._fix[1])
+            self._fix = None
         rec, fused, tracks, counts = fs.step_fused([frame] if is_jpeg else frame[None], sensors)
         self._imu_stale = True                                   # the step wrote self.vel = v_uav on the device (node:261)
         nxt, keep = fs.ctx.stream_last_points(max(1, len(old)))
@@ -544,11 +573,27 @@ class optical_fusion:
             if getattr(self, "_" + name):
                 d = read(fs)
                 setattr(self, "last_" + name, {k: d[k][0] for k in keys})
+        if self._pos_filter:
+            fp = fs.fused_position()
+            self.last_position = {k: ({n: a[0] for n, a in v.items()} if isinstance(v, dict) else v[0]) for k, v in fp.items()}
         if self._epipolar and r[15]:
             rec, pts = fs.structure()
             self.last_epipolar = (rec[0], pts[0])
         self.init = False
         self.got_picture_ = True
+
+    def call_fix(self, position, sigma):
+        """An absolute position fix (GPS, a marker) for the position filter: position [3] in the world frame, sigma a number or [3].
+        It is stored and enters the filter with the next frame's step (ofk.h: ofk_pos_filter_input); a later call before that frame
+        replaces it.  ValueError without pos_filter, or for a fix or a sigma that is not finite and positive."""
+        if not self._pos_filter:
+            raise ValueError("call_fix: optical_fusion was built without pos_filter")
+        p = np.asarray(position, np.float64).reshape(3)
+        s = np.array(np.broadcast_to(np.asarray(sigma, np.float64), (3,)))
+        if not (np.isfinite(p).all() and np.isfinite(s).all() and (s > 0).all()):
+            raise ValueError(f"call_fix: position {p} must be finite and sigma {s} finite and positive")
+        with self._lock:
+            self._fix = (p, s)
 
     def _ctx(self):
         return ofk.default_context()
@@ -607,7 +652,7 @@ class optical_fusion:
 
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
                  rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None, gyro_bias=None, lk_light=None,
-                 track_table=None, track_depth=None, track_template=None, keyframe=None, keyframe_rotation=None):
+                 track_table=None, track_depth=None, track_template=None, keyframe=None, keyframe_rotation=None, pos_filter=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -670,7 +715,11 @@ class optical_fusion:
         keyframe_rotation: None (R_acc is taken as exact), True, an ofk.KeyframeRotation or a dict of ofk.keyframe_rotation_setting's
         keywords, e.g. dict(sigma_bias=1e-3): the key solve then refines the accumulated rotation with the translation (ofk.h:
         ofk_set_keyframe_rotation); it needs keyframe.  self.last_keyframe_rotation is FlowStream.key_rotation()'s dictionary for the
-        one stream."""
+        one stream.
+        pos_filter: None (no position filter), True, an ofk.PosFilter or a dict of ofk.pos_filter_setting's keywords, e.g.
+        dict(sigma_v=2e-3, nis_max=16): the stream then fuses the keyframe's displacement, the step's velocity and the fixes of
+        call_fix in a filter with a cloned state (ofk.h: ofk_set_pos_filter); it switches the keyframe and the track table on when
+        they are None.  self.last_position is FlowStream.fused_position()'s dictionary for the one stream."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -752,13 +801,16 @@ class optical_fusion:
             PipelineConfig(**self._lk_light).lk_light_setting()      # invalid fields fail here, not at the first frame
         else:
             self._lk_light = {}
+        if pos_filter is not None and pos_filter is not False and keyframe is None:
+            keyframe = True                                      # the filter fuses the keyframe's displacement
         given = dict(track_table=track_table, track_depth=track_depth, track_template=track_template, keyframe=keyframe,
-                     keyframe_rotation=keyframe_rotation)
-        for name, value in given.items():                        # the rotation's check reads the keyframe, set in front of it
-            setattr(self, "_" + name, _struct_field(name, value, **(self._keyframe if name == "keyframe_rotation" else {})))
+                     keyframe_rotation=keyframe_rotation, pos_filter=pos_filter)
+        for name, value in given.items():                        # the rotation's and the filter's checks read the keyframe, set in front of them
+            setattr(self, "_" + name, _struct_field(name, value, **(self._keyframe if name in ("keyframe_rotation", "pos_filter") else {})))
         if (self._track_depth or self._track_template or self._keyframe) and not self._track_table:
             self._track_table = dict(track_table=True)           # the three are kept per row of the table
-        self.last_track_depth = self.last_track_template = self.last_keyframe = self.last_keyframe_rotation = None
+        self.last_track_depth = self.last_track_template = self.last_keyframe = self.last_keyframe_rotation = self.last_position = None
+        self._fix = None
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False
         self._stream = None

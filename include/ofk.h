@@ -632,6 +632,95 @@ int ofk_keyframe_rotation_step(ofk_ctx *ctx, const ofk_keyframe *k, const ofk_ke
                                const int *step, float *key_xy, uint8_t *member, double *state, int *istate, const int *new_counts,
                                int max_total, int batch, int stride, double *rec, double *rstate, double *rrec);
 
+/* Position filter per stream: keyframe, velocity and position fixes fused.  The keyframe's D is drift-free while the keyframe lives, but
+ * its pos re-anchors at every re-key, so its error is a random walk over the re-keys; a fix (GPS, a marker) has no way into a stream;
+ * and the key pixels' noise is common to all steps of one keyframe, so a filter that took D every step as an independent position
+ * measurement would be overconfident.  With this setting on beside ofk_set_keyframe every stream keeps a Kalman filter with a CLONED
+ * state on the device: the position at the keyframe is carried beside the current one, D measures their difference, and a re-key
+ * copies the current position, with its covariance and cross-covariances, into the clone.  Off by default; with it off every step
+ * allocates, launches and returns what it always did.  Reported, not fed back: nothing else reads p.  Streams only: ofk_pairs_run
+ * ignores it.
+ * State per stream: x [OFK_POSF_STATES = 12] f64 = (p 0-2: position, world frame, v_uav's convention; v 3-5: velocity per unit of dt,
+ * in v_uav's units; b 6-8: accelerometer bias as in ekf6; c 9-11: the clone of p at the keyframe); P [12][12] f64 row-major; istate
+ * [OFK_POSF_INTS = 16] i32: 0 steps, 1 fresh (1 = no D update since the last clone), 2 clones, 3 started, 4-6 the velocity updates
+ * applied / gated / refused, 7-9 the displacement's, 10-12 the fix's, 13-15 unused.
+ * Input row per stream, [OFK_POSF_INPUT = 12] f64, consumed and zeroed by the next step that runs the filter (not held, the setting
+ * on): 0-2 du, the velocity increment over the step in the world frame (zeros: none; a component that is not finite is taken as 0;
+ * under OFK_CONTROL_IMU the caller passes what ofk_imu_state returns as dv - the fuse kernel's own use of imu_dv is not touched), 3
+ * fix valid (0 / not 0), 4-6 the fix's position, 7-9 its sigma per axis, 10-11 unused.
+ * k_pos_filter_step runs on exactly the steps that launch the keyframe's step kernel, in one launch directly behind it; a held step
+ * leaves state, record and input alone.  It reads the step's record (v_uav 8-10; "solved" as rule 3 of the keyframe defines it), the
+ * keyframe's record of this step (flag 3, re-key reason 9, D 10-12, C_T 20-25) and R_world as the keyframe read it (sensor slots
+ * 7-15, the IMU state's under use_imu).  All arithmetic is f64 in the order written, no fused multiply-add; a sum of three terms is
+ * (t0 + t1) + t2.  In order:
+ *   1. Start, where istate[3] == 0 (behind ofk_stream_begin, behind ofk_pos_filter_reset, on the first step with the setting on after
+ *      one without it; on host buffers: whatever the caller hands in with istate[3] == 0): p = c = x[0..2] as it stands (the given
+ *      position; zero by default), v = b = 0; P = 0 but for the diagonals of the blocks pp, pc, cp, cc = p0_p^2, vv = p0_v^2, bb =
+ *      p0_b^2; fresh = 1, started = 1.
+ *   2. Predict.  p_k = p_k + dt v_k (the old v); v_k = (v_k + du_k) - dt b_k.  P = F P F^T + Q entry by entry, with f_i = dt for
+ *      i < 3, -dt for 3 <= i < 6 and no term for i >= 6 (likewise f_j): P'_ij = (P_ij + f_i P_i+3,j) + f_j (P_i,j+3 + f_i P_i+3,j+3),
+ *      every P on the right the old one; then P'_ii += q^2 with q = q_p, q_v, q_b for the blocks p, v, b and nothing for c.
+ *   3. Velocity update, when sigma_v > 0 and the step's record is solved with a finite v_uav: H = [0 I 0 0], z = v_uav,
+ *      R = (sigma_v sigma_v) I.
+ *   4. Displacement update, when the keyframe's flag is OFK_KEY_SOLVED at this step and D, C_T and R_world are finite:
+ *      M = R_world C_T, W = M R_world^T (upper triangle, mirrored), C_ij = (infl infl) W_ij, + floor floor on the diagonal.  If fresh:
+ *      P_cc += share C entry by entry, fresh = 0 - the key pixels' share of the noise is common to all steps of this keyframe, hence
+ *      part of the uncertainty of where the key is, not white noise.  Then H = [I 0 0 -I], z = D, R = (1 - share) C.
+ *   5. Fix update, when input slot 3 is set and the fix and its sigmas are finite and the sigmas > 0: H = [I 0 0 0], R = diag(sigma_k
+ *      sigma_k).
+ *   6. Every update, with a the block of +I and c the block of -I (none in rules 3 and 5, whose terms with c drop out):
+ *      S_mn = (((P_am,an - P_am,cn) - P_cm,an) + P_cm,cn) + R_mn; y_m = z_m - (x_am - x_cm).  Cholesky of S's lower triangle: d0 =
+ *      S_00, l00 = sqrt d0, l10 = S_10 / l00, l20 = S_20 / l00, d1 = S_11 - l10 l10, l11 = sqrt d1, l21 = (S_21 - l20 l10) / l11, d2
+ *      = (S_22 - l20 l20) - l21 l21, l22 = sqrt d2.  A pivot d_m that is not finite or not > tiny_m = 2^-48 (((|P_am,am| + |P_am,cm|) +
+ *      |P_cm,am|) + |P_cm,cm|), the rounding of the entries it was formed from (0 where they are 0): REFUSED, state untouched,
+ *      counted (NIS 0).  With a prior on p of 1e6 and more the blocks pp, pc and cc are nearly equal numbers whose difference f64
+ *      no longer holds; the floor keeps a displacement update from taking that noise for information until a fix has brought p
+ *      down.  (The filter is a covariance filter in f64: a prior on v or b whose dt^2-fold exceeds about 1e15 times the variance
+ *      of p it is added to erases that variance, and P_pp may come out of the first velocity update negative.  Keep p0_v and p0_b
+ *      within 1e7 of p0_p, or start them together.)  w = L^-1 y forward (w2 = ((y2 - l20 w0) - l21 w1) / l22), NIS = (w0 w0 + w1 w1) + w2 w2; not finite: refused as well.
+ *      nis_max > 0 and NIS > nis_max: GATED, state untouched, counted.  Otherwise (P H^T)_in = P_i,an - P_i,cn, (H P)_mj = P_am,j -
+ *      P_cm,j; row i of K solves S k = (P H^T)_i: forward t as w, back k2 = t2 / l22, k1 = (t1 - l21 k2) / l11, k0 = ((t0 - l10 k1)
+ *      - l20 k2) / l00.  x_i += (K_i0 y0 + K_i1 y1) + K_i2 y2.  Joseph form: B_ij = P_ij - ((K_i0 (HP)_0j + K_i1 (HP)_1j) + K_i2
+ *      (HP)_2j); (B H^T)_in = B_i,an - B_i,cn; (K R)_in = (K_i0 R_0n + K_i1 R_1n) + K_i2 R_2n; P_ij = (B_ij - (three-term sum of
+ *      (B H^T)_in K_jn)) + (three-term sum of (K R)_in K_jn); then P_ij = (P_ij + P_ji) / 2.  A block whose prior and process noise
+ *      are both 0 (say p0_b = q_b = 0) stays exactly 0 through all of this: that is how a block is held.
+ *   7. Clone, when the keyframe's record reports a re-key (field 9 != 0), whatever its flag: c = p; rows and columns 9-11 of P become
+ *      rows and columns 0-2 (block cc becomes block pp); fresh = 1, clones + 1.  The keyframe's own anchor / pos are not used.
+ *   8. steps + 1; the counts; the record, OFK_POSF_DOUBLES = 48: 0-11 x; 12-17 P_pp's upper triangle, 18-23 P_vv's, 24 the trace of
+ *      P_bb; per update (velocity 25-29, displacement 30-34, fix 35-39) its outcome (OFK_POSF_NOT attempted, _APPLIED, _GATED,
+ *      _REFUSED), NIS and innovation y; 40 cloned this step, 41 fresh, 42 steps, 43 clones, 44-46 updates applied / gated / refused
+ *      over the three kinds, 47 rule 1 ran this step.  The input row is zeroed.
+ * ofk_set_pos_filter: NULL or mode OFK_POSF_OFF switches it off.  OFK_E_INVALID, the setting staying as it was: an unknown mode, dt <=
+ * 0, a negative sigma_v, floor, q or p0, infl <= 0, share outside [0, 1], nis_max < 0, anything not finite.  Defaults behind "off":
+ * dt 1, sigma_v 1e-3, floor 0, infl 1, share 0.5, q_p 0, q_v 1e-3, q_b 0, p0_p 0, p0_v 1, p0_b 0 (the bias is held), nis_max 0 (no
+ * gate).  OFK_E_INVALID before any launch from a stream step with the setting on and ofk_set_keyframe off; the keyframe's own
+ * refusals then apply unchanged.  The state is allocated by the first step (or reset, or input) with need of it; ofk_stream_begin
+ * resets it and clears the input rows.
+ * ofk_pos_filter_input: input [batch of the active streams][OFK_POSF_INPUT], kept for the next step that is not held (a second call
+ * replaces the rows).  ofk_pos_filter_reset: active stream b starts over at pos (NULL: zero) with its next step; its input row is
+ * cleared.  ofk_pos_filter_download: x, P, istate, rec of the streams of the latest step with the setting on; any may be NULL.
+ * ofk_pos_filter_step: rules 1-8 on host buffers, touching no resident state, through the same kernel: v_uav [batch][3], solved
+ * [batch], key_rec [batch][OFK_KEY_DOUBLES], R_world [batch][9], input [batch][OFK_POSF_INPUT] (NULL: none; not modified); x, P,
+ * istate in and out in place; rec out (may be NULL). */
+#define OFK_POSF_OFF      0
+#define OFK_POSF_ON       1
+#define OFK_POSF_STATES   12
+#define OFK_POSF_INPUT    12
+#define OFK_POSF_INTS     16
+#define OFK_POSF_DOUBLES  48
+#define OFK_POSF_NOT      0
+#define OFK_POSF_APPLIED  1
+#define OFK_POSF_GATED    2
+#define OFK_POSF_REFUSED  3
+typedef struct ofk_pos_filter { int mode; double dt, sigma_v, floor, infl, share, q_p, q_v, q_b, p0_p, p0_v, p0_b, nis_max; } ofk_pos_filter;
+int ofk_set_pos_filter(ofk_ctx *ctx, const ofk_pos_filter *f);
+int ofk_get_pos_filter(const ofk_ctx *ctx, ofk_pos_filter *f);
+int ofk_pos_filter_input(ofk_ctx *ctx, const double *input);
+int ofk_pos_filter_reset(ofk_ctx *ctx, int b, const double *pos);
+int ofk_pos_filter_download(ofk_ctx *ctx, double *x, double *P, int *istate, double *rec);
+int ofk_pos_filter_step(ofk_ctx *ctx, const ofk_pos_filter *f, const double *v_uav, const int *solved, const double *key_rec,
+                        const double *R_world, const double *input, double *x, double *P, int *istate, int batch, double *rec);
+
 /* Camera model: the lens distortion undone on the device before the solve.  The solve stage reads a point as a sample of an ideal
  * pinhole image, x = (px - cx) * scaling (sensors[19..21]); the reference's camera is a wide-angle module whose lens moves a point by
  * tens of pixels at the border.  With ofk_set_camera on, the resident chains keep everything that lives in the image on the raw
