@@ -1,5 +1,5 @@
 // k_bias.inc — the gyro bias of a stream (ofk.h: ofk_set_gyro_bias): filtered from the flow, taken out of omega in front of every step.
-// Included by k_estimate.hip behind k_joint.inc, whose core (joint_core, joint_inverse) and the shells of k_second.inc it shares.
+// Included by k_estimate.hip behind k_joint.inc, whose core (joint_core), k_lstsq.inc's joint_inverse and k_second.inc's shells it shares.
 // DESIGN.md, "gyro bias", has the model.
 //
 // k_gyro_bias_apply  one thread per stream, directly behind the sensors' upload: raw omega into the bias record, omega - b^ into the
@@ -49,7 +49,7 @@ void ofk_launch_gyro_bias_apply(hipStream_t s, double *omega, int stride, double
 __device__ void bias_filter(const bias_cfg &c, const double *jr, double *r)
 {
     double bh[3] = {r[0], r[1], r[2]};
-    double P[3][3] = {{r[3], r[4], r[5]}, {r[4], r[6], r[7]}, {r[5], r[7], r[8]}};
+    double P[3][3]; sym3_from6(r + 3, P);
     int ne = 0;
     for (int k = 0; k < 3; ++k)
         if (c.est[k]) { P[k][k] += c.q; ++ne; }
@@ -57,8 +57,7 @@ __device__ void bias_filter(const bias_cfg &c, const double *jr, double *r)
     r[28] = jr[11];
     const int core = (int)jr[10];
     if (core != 0) { r[18] = (double)core; return; }
-    double z[3], S[3][3], Rm[3][3];
-    const double Cw[3][3] = {{jr[15], jr[16], jr[17]}, {jr[16], jr[18], jr[19]}, {jr[17], jr[19], jr[20]}};
+    double z[3], S[3][3], Rm[3][3], Cw[3][3]; sym3_from6(jr + 15, Cw);
     bool fin = true;
     for (int i = 0; i < 3; ++i) {
         z[i] = c.est[i] ? -jr[3 + i] : 0.0;

@@ -1,6 +1,6 @@
 // k_cov.inc — the velocity covariance (ofk.h: ofk_set_cov): first-order error propagation through the velocity solve, and the filter
-// correct that uses it.  Included by k_estimate.hip, whose helpers (point_terms, pair_point, fuse_terms, wave_sum, jacobi3, the Kalman
-// recursions) it shares.  DESIGN.md, "velocity covariance", has the derivation.
+// correct that uses it.  Included by k_estimate.hip, whose helpers (point_terms, pair_point, fuse_terms, wave_sum, jacobi3,
+// eig_inverse3, the Kalman recursions) it shares.  DESIGN.md, "velocity covariance", has the derivation.
 //
 // One team per problem behind whichever solve kernel ran, plain or robust: a single wave (NW = 1, beside the response kernel / LK of
 // large batches) or a 256-thread workgroup (NW = 4).  The team reads v from the record, walks the kept points once and sums, with
@@ -119,8 +119,7 @@ __device__ __forceinline__ void cov_void(double *o)
 // A (symmetric, upper triangle s6) sandwiched: Mi S Mi, scaled; Mi full 3x3.
 __device__ void cov_sandwich(const double Mi[3][3], const double *s6, double scale, double C[3][3])
 {
-    const double S[3][3] = {{s6[0], s6[1], s6[2]}, {s6[1], s6[3], s6[4]}, {s6[2], s6[4], s6[5]}};
-    double T[3][3];
+    double S[3][3], T[3][3]; sym3_from6(s6, S);
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) T[i][j] = Mi[i][0] * S[0][j] + Mi[i][1] * S[1][j] + Mi[i][2] * S[2][j];
     for (int i = 0; i < 3; ++i) for (int j = i; j < 3; ++j) C[i][j] = C[j][i] = scale * (T[i][0] * Mi[j][0] + T[i][1] * Mi[j][1] + T[i][2] * Mi[j][2]);
 }
@@ -132,11 +131,10 @@ __device__ void cov_finish(const double *s, const cov_cfg &cc, double sf, double
 {
     const double m = s[COV_CNT];
     if (!usable || !(rank >= 3.0) || !(m > 0.0) || (cc.mode == OFK_COV_RESIDUAL && !(2.0 * m > 3.0))) { cov_void(o); return; }
-    double A[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}}, lam[3], V[3][3], Mi[3][3];
+    double A[3][3], lam[3], V[3][3], Mi[3][3]; sym3_from6(s, A);
     jacobi3(A, lam, V);
     if (!(lam[2] > 0.0)) { cov_void(o); return; }
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) Mi[i][j] = V[i][0] * V[j][0] / lam[0] + V[i][1] * V[j][1] / lam[1] + V[i][2] * V[j][2] / lam[2];
+    eig_inverse3(lam, V, Mi);
     const double s2 = 2.0 * m > 3.0 ? rss / (2.0 * m - 3.0) : 0.0;
     double Cf[3][3], Cx[3][3];
     if (cc.mode == OFK_COV_RESIDUAL) {
@@ -207,7 +205,7 @@ __device__ bool kf_correct_cov_dev(int ns, int nm, const double *H, const double
     for (int i = 0; i < nm * nm; ++i) Re[i] = Rm[i];
     if (cc.filter_r && cv[13] == 0.0) {
         const double *t6 = cv + (z_source ? 6 : 0);
-        const double C[3][3] = {{t6[0], t6[1], t6[2]}, {t6[1], t6[3], t6[4]}, {t6[2], t6[4], t6[5]}};
+        double C[3][3]; sym3_from6(t6, C);
         for (int i = 0; i < 3 && i < nm; ++i)
             for (int j = 0; j < 3 && j < nm; ++j) Re[i * nm + j] = z_sign * z_sign * C[i][j] + (i == j ? cc.r_floor : 0.0);
     }

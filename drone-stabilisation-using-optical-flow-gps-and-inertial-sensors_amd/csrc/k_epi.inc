@@ -59,15 +59,13 @@ __device__ bool epi_direction(const double *s, bool usable, const double *rec03,
     for (int k = 0; k < EPI_SUMS1; ++k) fin = fin && isfinite(s[k]);
     const double m = s[EPI_CNT];
     if (!fin || !(m >= 3.0)) return false;
-    double A[3][3] = {{s[EPI_N], s[EPI_N + 1], s[EPI_N + 2]}, {s[EPI_N + 1], s[EPI_N + 3], s[EPI_N + 4]}, {s[EPI_N + 2], s[EPI_N + 4], s[EPI_N + 5]}};
-    double ln[3], Vn[3][3], W[3][3];
+    double A[3][3], ln[3], Vn[3][3], W[3][3]; sym3_from6(s + EPI_N, A);
     jacobi3(A, ln, Vn);
     if (!(isfinite(ln[0]) && ln[2] > 2.220446049250313e-16 * 3.0 * m * ln[0])) return false;
     const double is[3] = {1.0 / sqrt(ln[0]), 1.0 / sqrt(ln[1]), 1.0 / sqrt(ln[2])};
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) W[i][j] = Vn[i][0] * Vn[j][0] * is[0] + Vn[i][1] * Vn[j][1] * is[1] + Vn[i][2] * Vn[j][2] * is[2];
-    const double E[3][3] = {{s[EPI_E], s[EPI_E + 1], s[EPI_E + 2]}, {s[EPI_E + 1], s[EPI_E + 3], s[EPI_E + 4]}, {s[EPI_E + 2], s[EPI_E + 4], s[EPI_E + 5]}};
-    double T[3][3], G[3][3];
+    double E[3][3], T[3][3], G[3][3]; sym3_from6(s + EPI_E, E);
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) T[i][j] = E[i][0] * W[0][j] + E[i][1] * W[1][j] + E[i][2] * W[2][j];
     for (int i = 0; i < 3; ++i)
         for (int j = i; j < 3; ++j) G[i][j] = G[j][i] = W[i][0] * T[0][j] + W[i][1] * T[1][j] + W[i][2] * T[2][j];
@@ -95,8 +93,7 @@ __device__ int epi_finish(const double *s, const epi_cfg &ec, double tnt, double
     er[4] = sqrt(sig2); er[16] = l1;
     for (int k = 0; k < 3; ++k) { t[k] *= sgn; er[k] = t[k]; }
     er[5] = s[EPI_RSS]; er[12] = s[EPI_ACNT]; er[13] = sgn > 0.0 ? s[EPI_NLE] : s[EPI_NGE];
-    const double Hm[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
-    double P[3][3], T[3][3], G[3][3], lh[3], Vh[3][3];
+    double Hm[3][3], P[3][3], T[3][3], G[3][3], lh[3], Vh[3][3]; sym3_from6(s + EPI_H, Hm);
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) P[i][j] = (i == j ? 1.0 : 0.0) - t[i] * t[j];
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) T[i][j] = Hm[i][0] * P[0][j] + Hm[i][1] * P[1][j] + Hm[i][2] * P[2][j];
     for (int i = 0; i < 3; ++i)

@@ -1,6 +1,6 @@
 // k_joint.inc — the joint velocity and rotation solve (ofk.h: ofk_set_joint): the gyro refined from the flow.  Included by
-// k_estimate.hip, whose helpers (point_terms, pair_point, resid_point, wave_sum, jacobi3, lever_rotate, the Kalman recursions) it
-// shares.  DESIGN.md, "joint solve", has the derivation.
+// k_estimate.hip, whose helpers (point_terms, pair_point, resid_point, wave_sum, jacobi3, joint_inverse, lever_rotate, the Kalman
+// recursions) it shares.  DESIGN.md, "joint solve", has the derivation.
 //
 // One team per problem behind whichever solve kernel ran, plain or robust: a single wave (NW = 1) or a 256-thread workgroup (NW = 4).
 // The flow is linear in (v, omega): with omega = omega0 + delta point i's rows are a X v + b N delta = b X q0, p = (x, y, 1), X = [p]x,
@@ -45,16 +45,6 @@ __device__ __forceinline__ void joint_point(double *s, int variant, double x, do
     s[JOINT_C + 0] += wb * c0; s[JOINT_C + 1] += wb * c1; s[JOINT_C + 2] += wb * c2;
 }
 
-__device__ __forceinline__ void joint_inverse(const double lam[3], const double V[3][3], int take, double Ai[3][3])
-{
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double t = 0.0;
-            for (int k = 0; k < take; ++k) t += V[i][k] * V[j][k] / lam[k];
-            Ai[i][j] = t;
-        }
-}
-
 // One lane: the joint record from the sums.  vs: the solve's v; usable: the solve solved with rank 3, scaling and d are not 0;
 // dsf2 = (d sigma_f)^2 in the units of the points; ovar: the prior variances (+inf: free, 0: held).  jr is written in full.  Returns
 // whether (v, omh) replace the record's fields (flag 0 with at least one axis estimated).
@@ -67,7 +57,7 @@ __device__ bool joint_finish(const double *s, bool usable, const double *vs, con
     bool fin = isfinite(dsf2) && isfinite(vs[0]) && isfinite(vs[1]) && isfinite(vs[2]);
     for (int k = 0; k < JOINT_SUMS; ++k) fin = fin && isfinite(s[k]);
     if (!usable || !fin || !(s[JOINT_CNT] > 0.0)) return false;
-    double A[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}}, lam[3], V[3][3], Mi[3][3];
+    double A[3][3], lam[3], V[3][3], Mi[3][3]; sym3_from6(s, A);
     jacobi3(A, lam, V);
     if (!(lam[2] > 0.0)) return false;
     joint_inverse(lam, V, 3, Mi);
@@ -77,9 +67,7 @@ __device__ bool joint_finish(const double *s, bool usable, const double *vs, con
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) G[i][j] = Mi[i][0] * K[0][j] + Mi[i][1] * K[1][j] + Mi[i][2] * K[2][j];
     bool held[3]; int ne = 0;
     for (int k = 0; k < 3; ++k) { held[k] = !(ovar[k] > 0.0); ne += held[k] ? 0 : 1; }
-    const double Dm[3][3] = {{s[JOINT_D], s[JOINT_D + 1], s[JOINT_D + 2]}, {s[JOINT_D + 1], s[JOINT_D + 3], s[JOINT_D + 4]},
-                             {s[JOINT_D + 2], s[JOINT_D + 4], s[JOINT_D + 5]}};
-    double S[3][3];
+    double Dm[3][3], S[3][3]; sym3_from6(s + JOINT_D, Dm);
     for (int i = 0; i < 3; ++i)
         for (int j = i; j < 3; ++j) {
             double t = Dm[i][j] - (K[0][i] * G[0][j] + K[1][i] * G[1][j] + K[2][i] * G[2][j]);

@@ -86,7 +86,7 @@
     const int live = (int)block_sum(live_d, s_red);
     acc_block_sum(a1);
 #if KF_ROT
-    kr_block_sum(J1, s_jp);
+    block_sums<KR_SUMS, KR_SUMS>(J1, s_jp);
 #endif
     double T[3] = {0.0, 0.0, 0.0}, s3[3];
     bool fin = true;
@@ -218,13 +218,13 @@
         else
 #endif
         if (flag == OFK_KEY_SOLVED) {
-            double A[3][3] = {{as.m00, as.m01, as.m02}, {as.m01, as.m11, as.m12}, {as.m02, as.m12, as.m22}}, lam[3], V[3][3];
+            double A[3][3], lam[3], V[3][3], Mi[3][3]; sym3_from6(as, A);
             jacobi3(A, lam, V);
+            eig_inverse3(lam, V, Mi);
             const double sf2 = sf * sf;
             int s = 20;
             for (int i = 0; i < 3; ++i)
-                for (int j = i; j < 3; ++j)
-                    o[s++] = sf2 * ((V[i][0] * V[j][0] / lam[0] + V[i][1] * V[j][1] / lam[1]) + V[i][2] * V[j][2] / lam[2]);
+                for (int j = i; j < 3; ++j) o[s++] = sf2 * Mi[i][j];
         }
         const int mk_out = rekey ? kept : mk, ks_out = rekey ? step + 1 : key_step, nkey_out = nkey + (rekey ? 1 : 0);
         const int ndead_out = ndead + (flag != OFK_KEY_SOLVED ? 1 : 0);

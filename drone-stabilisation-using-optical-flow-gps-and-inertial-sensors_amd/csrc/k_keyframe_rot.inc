@@ -2,8 +2,9 @@
 // the key solve widened to (T, delta), R^ = exp([delta]x) R_acc, under a Gaussian prior on delta.  Included by k_tracks.hip behind
 // k_keyframe.inc, whose body (k_keyframe_body.inc) it compiles a second time with KF_ROT 1; k_keyframe_step itself is the same text
 // with KF_ROT 0.  Like it: one workgroup per stream, only that stream's rows and state, plain vector stores, no atomics, f64 in the
-// order ofk.h states.  The eighteen extra sums of a walk go through LDS partials in block_sum's order; the 3 x 3 work is done by every
-// thread, the covariances by thread 0 alone, which parks them in LDS until the record is written.
+// order ofk.h states.  The eighteen extra sums of a walk go through k_lstsq.inc's block_sums, like the Acc beside them and in the same
+// LDS rows; the 3 x 3 work (its sym3_from6, eig_inverse3, eig_solve3, all_finite_sum) is done by every thread, the covariances by
+// thread 0 alone, which parks them in LDS until the record is written.
 
 #define KR_SUMS 18                                               // M_Td 0-8 (row i of T, column k of delta), M_dd 9-14 (upper triangle), g_d 15-17
 
@@ -27,39 +28,6 @@ __device__ __forceinline__ void kr_point(double *J, double a, double b, double u
     const double q0 = n00 * u0 + n01 * u1, q1 = n01 * u0 + n11 * u1;
 #pragma unroll
     for (int k = 0; k < 3; ++k) J[15 + k] += cx[k] * q0 + cy[k] * q1;
-}
-
-// acc_block_sum's exchange for the eighteen: wave butterfly, one LDS round, (s0 + s1) + (s2 + s3)
-__device__ __forceinline__ void kr_block_sum(double *J, double (*part)[KR_SUMS])
-{
-#pragma unroll
-    for (int k = 0; k < KR_SUMS; ++k) J[k] = wave_sum(J[k]);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < KR_SUMS; ++k) part[threadIdx.x >> 6][k] = J[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < KR_SUMS; ++k) J[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
-}
-
-// acc_block_sum with the partials in the caller's LDS: the same additions in the same order
-__device__ __forceinline__ void kr_acc_sum(Acc &a, double (*part)[KR_SUMS])
-{
-    double v[11] = {a.m00, a.m01, a.m02, a.m11, a.m12, a.m22, a.g0, a.g1, a.g2, a.bb, a.cnt};
-    static_assert(KR_SUMS >= 11, "the partials hold an Acc");
-#pragma unroll
-    for (int k = 0; k < 11; ++k) v[k] = wave_sum(v[k]);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 11; ++k) part[threadIdx.x >> 6][k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 11; ++k) v[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
-    a.m00 = v[0]; a.m01 = v[1]; a.m02 = v[2]; a.m11 = v[3]; a.m12 = v[4]; a.m22 = v[5]; a.g0 = v[6]; a.g1 = v[7]; a.g2 = v[8]; a.bb = v[9]; a.cnt = v[10];
 }
 
 // R = exp([o]x) R0 with rule 1's coefficients
@@ -99,8 +67,9 @@ __device__ __forceinline__ void kr_walk(const ofk_kf_rows &t, const ofk_kf_in &i
         if (gate && !(kf_row(t, in.next_pts, r, fg, x, y, u0, u1, sA) && kf_res2(x, y, u0, u1, sA, Tg) <= g2)) continue;
         if (kf_row(t, in.next_pts, r, f, x, y, u0, u1, sA)) { acc_point(a, x, y, u0, u1, 0.0, sA, 1.0); kr_point(J, x, y, u0, u1, sA); }
     }
-    kr_acc_sum(a, part);
-    kr_block_sum(J, part);
+    double v[11];
+    acc_pack(a, v); block_sums<11, KR_SUMS>(v, part); acc_unpack(a, v);
+    block_sums<KR_SUMS, KR_SUMS>(J, part);
 }
 
 // One Gauss-Newton step from the reduced sums: the Schur complement on the T block.  dl: the correction so far (the prior is on
@@ -109,22 +78,18 @@ __device__ __forceinline__ void kr_walk(const ofk_kf_rows &t, const ofk_kf_in &i
 __device__ bool kr_solve(const Acc &a, const double *J, const kr_prior &pr, const double *dl, double sf2, double *ds, double *T, double *cov)
 {
     const double EPS = 2.220446049250313e-16;
-    double A[3][3] = {{a.m00, a.m01, a.m02}, {a.m01, a.m11, a.m12}, {a.m02, a.m12, a.m22}}, lam[3], V[3][3];
+    double A[3][3], lam[3], V[3][3]; sym3_from6(a, A);
+    const double g[3] = {a.g0, a.g1, a.g2};
     jacobi3(A, lam, V);
-    const double rows = 3.0 * a.cnt, cut = EPS * (rows > 3.0 ? rows : 3.0);
-    double chk = ((lam[0] - lam[0]) + (lam[1] - lam[1])) + (lam[2] - lam[2]);
-    for (int k = 0; k < KR_SUMS; ++k) chk += J[k] - J[k];
-    chk += ((a.g0 - a.g0) + (a.g1 - a.g1)) + (a.g2 - a.g2);
-    if (!(chk == 0.0) || !(lam[2] > lam[0] * cut) || !(lam[2] > 0.0)) return false;
+    const double rows = 3.0 * a.cnt, cut = EPS * (rows > 3.0 ? rows : 3.0);   // times lam[0] below: not rank_cut's order
+    if (!(all_finite_sum(lam, 3) && all_finite_sum(J, KR_SUMS) && all_finite_sum(g, 3)) || !(lam[2] > lam[0] * cut) || !(lam[2] > 0.0)) return false;
     double Mi[3][3], Y[3][3], t0[3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) Mi[i][j] = (V[i][0] * V[j][0] / lam[0] + V[i][1] * V[j][1] / lam[1]) + V[i][2] * V[j][2] / lam[2];
+    eig_inverse3(lam, V, Mi);
     for (int i = 0; i < 3; ++i) {
         for (int k = 0; k < 3; ++k) Y[i][k] = (Mi[i][0] * J[k] + Mi[i][1] * J[3 + k]) + Mi[i][2] * J[6 + k];
-        t0[i] = (Mi[i][0] * a.g0 + Mi[i][1] * a.g1) + Mi[i][2] * a.g2;
+        t0[i] = (Mi[i][0] * g[0] + Mi[i][1] * g[1]) + Mi[i][2] * g[2];
     }
-    const double dd[3][3] = {{J[9], J[10], J[11]}, {J[10], J[12], J[13]}, {J[11], J[13], J[14]}};
-    double S[3][3], h[3];
+    double dd[3][3], S[3][3], h[3]; sym3_from6(J + 9, dd);
     for (int k = 0; k < 3; ++k) {
         for (int l = k; l < 3; ++l) {
             double v = (dd[k][l] + (k == l ? pr.lam[k] : 0.0)) - ((J[k] * Y[0][l] + J[3 + k] * Y[1][l]) + J[6 + k] * Y[2][l]);
@@ -135,20 +100,16 @@ __device__ bool kr_solve(const Acc &a, const double *J, const kr_prior &pr, cons
     }
     double ls[3], U[3][3];
     jacobi3(S, ls, U);
-    const double c2 = ((ls[0] - ls[0]) + (ls[1] - ls[1])) + (ls[2] - ls[2]) + (((h[0] - h[0]) + (h[1] - h[1])) + (h[2] - h[2]));
-    if (!(c2 == 0.0) || !(ls[2] > ls[0] * cut) || !(ls[2] > 0.0)) return false;
-    ds[0] = ds[1] = ds[2] = 0.0;
-    for (int k = 0; k < 3; ++k) {
-        const double c = ((U[0][k] * h[0] + U[1][k] * h[1]) + U[2][k] * h[2]) / ls[k];
-        ds[0] += c * U[0][k]; ds[1] += c * U[1][k]; ds[2] += c * U[2][k];
-    }
+    if (!(all_finite_sum(ls, 3) && all_finite_sum(h, 3)) || !(ls[2] > ls[0] * cut) || !(ls[2] > 0.0)) return false;
+    eig_solve3(ls, U, h, nullptr, ds);
     for (int k = 0; k < 3; ++k) if (pr.held[k]) ds[k] = 0.0;
     for (int i = 0; i < 3; ++i) T[i] = t0[i] - ((Y[i][0] * ds[0] + Y[i][1] * ds[1]) + Y[i][2] * ds[2]);
     if (threadIdx.x == 0) {
         double Si[3][3], Z[3][3];
+        eig_inverse3(ls, U, Si);
         for (int k = 0; k < 3; ++k)
             for (int l = 0; l < 3; ++l)
-                Si[k][l] = pr.held[k] || pr.held[l] ? 0.0 : (U[k][0] * U[l][0] / ls[0] + U[k][1] * U[l][1] / ls[1]) + U[k][2] * U[l][2] / ls[2];
+                if (pr.held[k] || pr.held[l]) Si[k][l] = 0.0;
         for (int i = 0; i < 3; ++i)
             for (int k = 0; k < 3; ++k) Z[i][k] = (Y[i][0] * Si[0][k] + Y[i][1] * Si[1][k]) + Y[i][2] * Si[2][k];
         int s = 0;

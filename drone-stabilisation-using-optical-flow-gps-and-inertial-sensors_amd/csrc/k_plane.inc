@@ -1,6 +1,6 @@
 // k_plane.inc — the plane solve (ofk.h: ofk_set_plane): the ground normal refined from the flow.  Included by k_estimate.hip, whose
-// helpers (point_terms, pair_point, cross_p, wave_sum, jacobi3, lever_rotate, the Kalman recursions) it shares.  DESIGN.md, "plane
-// solve", has the derivation.
+// helpers (point_terms, pair_point, cross_p, wave_sum, jacobi3, eig_inverse3, lever_rotate, the Kalman recursions) it shares.
+// DESIGN.md, "plane solve", has the derivation.
 //
 // One team per problem behind whichever solve kernel ran, plain or robust: a single wave (NW = 1) or a 256-thread workgroup (NW = 4).
 // With m = n / d the plane's inverse-distance vector, p = (x, y, 1), X = [p]x and the solve's q, sA, sB at the sensors' n0, d0, point
@@ -101,11 +101,10 @@ __device__ int plane_finish(const double *s, int k, bool usable, const double *r
     if (fin && s[PLANE_CNT] > 0.0) {
         F = s[PLANE_RSS] + lam * (st.tau[0] * st.tau[0] + st.tau[1] * st.tau[1]);
         if (k == 0) st.f0 = F;
-        double A[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}}, lm[3], V[3][3];
+        double A[3][3], lm[3], V[3][3]; sym3_from6(s, A);
         jacobi3(A, lm, V);
         if (lm[2] > 0.0 && isfinite(lm[0])) {
-            for (int i = 0; i < 3; ++i)
-                for (int j = 0; j < 3; ++j) Mi[i][j] = V[i][0] * V[j][0] / lm[0] + V[i][1] * V[j][1] / lm[1] + V[i][2] * V[j][2] / lm[2];
+            eig_inverse3(lm, V, Mi);
             if (held) { flag = 0; done = true; }
             else {
                 const double *K = s + PLANE_K, *gv = s + PLANE_GV, *gt = s + PLANE_GT;

@@ -1,6 +1,6 @@
 // k_track_depth.inc — an inverse depth per track of a video stream (ofk.h: ofk_set_track_depth): rho, its variance and the number of
 // measurements per row of the track table, filtered over the frames, and the velocity solved from the depths of the earlier frames.
-// Included by k_tracks.hip behind k_lstsq.inc, whose sums, reduction, Jacobi and rank rule the map solve shares.  The rows of one
+// Included by k_tracks.hip behind k_lstsq.inc, whose sums, reduction, solve and eig_inverse3 the map solve shares.  The rows of one
 // stream are only ever touched by that stream's workgroup, with plain vector stores and no atomics, so a second launch on the same
 // inputs gives the same bits.  All arithmetic is f64 in the order ofk.h states (the build has no FMA contraction).
 
@@ -139,17 +139,16 @@ __global__ __launch_bounds__(256) void k_track_depth_step(ofk_td_rows t, ofk_td_
     if (tid == 0) {
         double *o = t.rec + (size_t)b * OFK_TD_DOUBLES;
         for (int k = 0; k < OFK_TD_DOUBLES; ++k) o[k] = 0.0;
-        double vm[3] = {0.0, 0.0, 0.0}, s3[3];
+        double vm[3] = {0.0, 0.0, 0.0}, s3[3], lam[3], V[3][3];
         bool fin = true;
-        const int rank = a.cnt >= (double)cfg.min_rows ? solve_from_acc(a, vm, s3, fin) : 0;
+        const int rank = a.cnt >= (double)cfg.min_rows ? solve_from_acc(a, vm, s3, fin, lam, V) : 0;
         const bool ok = rank == 3 && fin;
-        if (ok) {                                                // C_map = sigma_flow^2 M^-1 from the same Jacobi
-            double A[3][3] = {{a.m00, a.m01, a.m02}, {a.m01, a.m11, a.m12}, {a.m02, a.m12, a.m22}}, lam[3], V[3][3];
-            jacobi3(A, lam, V);
+        if (ok) {                                                // C_map = sigma_flow^2 M^-1 from the solve's own decomposition
+            double Mi[3][3];
+            eig_inverse3(lam, V, Mi);
             int s = 10;
             for (int i = 0; i < 3; ++i)
-                for (int j = i; j < 3; ++j)
-                    o[s++] = sf2 * ((V[i][0] * V[j][0] / lam[0] + V[i][1] * V[j][1] / lam[1]) + V[i][2] * V[j][2] / lam[2]);
+                for (int j = i; j < 3; ++j) o[s++] = sf2 * Mi[i][j];
             o[0] = vm[0]; o[1] = vm[1]; o[2] = vm[2];
         }
         o[3] = ok ? 0.0 : 1.0; o[4] = a.cnt;

@@ -1,8 +1,8 @@
 // k_track_template.inc — a template per track of a video stream (ofk.h: ofk_set_track_template): the patch a track was born with, the
 // accumulated linear map from that patch to the current frame, the score of the current window against it and the position pulled
-// back onto it.  Included by k_tracks.hip behind k_lstsq.inc (the step map's Jacobi).  Every image sum is a sum of integers in int64,
-// so its result does not depend on the order of the additions; the f32 and f64 steps are in the order ofk.h states (the build has no
-// FMA contraction).  No atomics: a second launch on the same inputs gives the same bits.
+// back onto it.  Included by k_tracks.hip behind k_lstsq.inc (the step map's block_sums, Jacobi, rank_cut and eig_solve3).  Every
+// image sum is a sum of integers in int64, so its result does not depend on the order of the additions; the f32 and f64 steps are in
+// the order ofk.h states (the build has no FMA contraction).  No atomics: a second launch on the same inputs gives the same bits.
 
 struct tp_cfg { int win, iters, outside, fit_min; double ncc_min, anchor_max, fit_gate, scale_max; };
 
@@ -10,40 +10,20 @@ struct tp_cfg { int win, iters, outside, fit_min; double ncc_min, anchor_max, fi
 #define TP_SUMS 13
 struct tp_sums { double v[TP_SUMS]; };                        // xx xy x yy y n | x*Y0 y*Y0 Y0 | x*Y1 y*Y1 Y1 | rr
 
-__device__ __forceinline__ void tp_block_sum(tp_sums &a, double (*s_part)[TP_SUMS])
-{
-#pragma unroll
-    for (int k = 0; k < TP_SUMS; ++k) a.v[k] = wave_sum(a.v[k]);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < TP_SUMS; ++k) s_part[threadIdx.x >> 6][k] = a.v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < TP_SUMS; ++k) a.v[k] = (s_part[0][k] + s_part[1][k]) + (s_part[2][k] + s_part[3][k]);
-}
-
 // the 3 x 3 normal equations of both image coordinates at once: k_lstsq.inc's Jacobi and rank rule over `n` rows.  fit: M (row-major), t.
 __device__ bool tp_solve(const tp_sums &a, double *fit)
 {
     const double *s = a.v;
-    double fin = 0.0;
-    for (int k = 0; k < 12; ++k) fin += s[k] - s[k];            // NaN unless every sum is finite
-    if (!(fin == 0.0)) return false;
-    double A[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}}, lam[3], V[3][3];
+    if (!all_finite_sum(s, 12)) return false;
+    double A[3][3], lam[3], V[3][3]; sym3_from6(s, A);
     jacobi3(A, lam, V);
-    if (!((lam[0] - lam[0]) + (lam[1] - lam[1]) + (lam[2] - lam[2]) == 0.0)) return false;
-    const double tol = lam[0] * 2.220446049250313e-16 * (s[5] > 3.0 ? s[5] : 3.0);
+    if (!all_finite_sum(lam, 3)) return false;
+    const double tol = rank_cut(lam[0], s[5]);
     for (int k = 0; k < 3; ++k)
         if (!(lam[k] > tol && lam[k] > 0.0)) return false;       // rank below 3
     for (int r = 0; r < 2; ++r) {
-        const double *g = s + 6 + 3 * r;
-        double u[3] = {0.0, 0.0, 0.0};
-        for (int k = 0; k < 3; ++k) {
-            const double c = (V[0][k] * g[0] + V[1][k] * g[1] + V[2][k] * g[2]) / lam[k];
-            u[0] += c * V[0][k]; u[1] += c * V[1][k]; u[2] += c * V[2][k];
-        }
+        double u[3];
+        eig_solve3(lam, V, s + 6 + 3 * r, nullptr, u);
         fit[2 * r] = u[0]; fit[2 * r + 1] = u[1]; fit[4 + r] = u[2];
     }
     return true;
@@ -96,7 +76,7 @@ __global__ __launch_bounds__(256) void k_track_affine(const float *__restrict__ 
             }
             a.v[12] += rr; a.v[5] += 1.0;
         }
-        tp_block_sum(a, s_part);
+        block_sums<TP_SUMS, TP_SUMS>(a.v, s_part);
         if (pass == 2) { rms = a.v[5] > 0.0 ? sqrt(a.v[12] / a.v[5]) : 0.0; continue; }
         if (tid == 0) {
             double f[6];
