@@ -92,7 +92,9 @@ __device__ __forceinline__ double kf_res2(double a, double b, double u0, double 
 __global__ __launch_bounds__(256) void k_keyframe_step(ofk_kf_rows t, ofk_kf_in in, kf_cfg cfg)
 {
 #define KF_ROT 0
+#define KF_MAP 0
 #include "k_keyframe_body.inc"
+#undef KF_MAP
 #undef KF_ROT
 }
 

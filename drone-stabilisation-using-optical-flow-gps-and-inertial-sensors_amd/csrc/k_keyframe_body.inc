@@ -1,5 +1,7 @@
 // k_keyframe_body.inc — rules 1-5 of ofk_set_keyframe, the body of k_keyframe_step (KF_ROT 0) and of k_keyframe_step_rot (KF_ROT 1,
 // k_keyframe_rot.inc: rule 2 widened by ofk_set_keyframe_rotation).  With KF_ROT 0 the text is k_keyframe_step's as it always was.
+// KF_MAP 1 (k_keyframe_map.inc, with KF_ROT 0): rules M1-M5 of ofk_set_keyframe_map around them, the body of k_keyframe_step_map;
+// with KF_MAP 0 nothing of it is compiled.
     __shared__ int s_wave[4];
     __shared__ int s_base;
     __shared__ double s_red[4];
@@ -68,6 +70,32 @@
     const double angle = acos(fmin(1.0, fmax(-1.0, cs)));
 #endif
 
+#if KF_MAP
+    // M1. capture; M2's live map rows and M4's mature rows in the same walk
+    int *ms = km.mstate + (size_t)b * 2;
+    const int cap_for = ms[0];
+    const bool capture = mk != 0 && cap_for != key_step;
+    double mcnt[3] = {0.0, 0.0, 0.0};                            // captured, live map rows, mature among the live rows
+    for (int i = tid; i < n; i += 256) {
+        const size_t r = base + i;
+        bool mature = false;
+        if (km.rho) { const double rho = km.rho[r], lim = mc.rel_max * rho; mature = km.nobs[r] >= mc.min_obs && rho > 0.0 && km.var[r] <= lim * lim; }
+        const bool mem = t.member[r] != 0;
+        if (capture && mem) {
+            km.key_rho[r] = mature ? km.rho[r] : 0.0; km.key_var[r] = mature ? km.var[r] : 0.0;
+            if (mature) mcnt[0] += 1.0;
+        }
+        if (in.status[r] != 0 && mem) {
+            if (km.key_rho[r] > 0.0) mcnt[1] += 1.0;
+            if (mature) mcnt[2] += 1.0;
+        }
+    }
+    __shared__ double s_mc[4][3];
+    block_sums<3, 3>(mcnt, s_mc);
+    const int map_rows = capture ? (int)mcnt[0] : ms[1], live_map = (int)mcnt[1], ready = (int)mcnt[2];
+    const bool use_map = map_rows >= mc.min_rows && live_map >= mc.min_rows;   // uniform over the workgroup
+#endif
+
     // 2. the key solve
     Acc a1; acc_zero(a1);
     double live_d = 0.0;
@@ -123,6 +151,16 @@
     }
     if (!jok)
 #endif
+#if KF_MAP
+    // M3. the map solve in rule 2's place; where it does not stand the plain rule 2 goes on below as it always did
+    km_res mo;
+    const bool plain_ok = flag == OFK_KEY_SOLVED;
+    const bool mok = use_map && km_solve(t, in, km, base, n, f, cfg, mc, sf * sf, g2, s_red, mo);
+    if (mok) {
+        flag = OFK_KEY_SOLVED; T[0] = mo.T[0]; T[1] = mo.T[1]; T[2] = mo.T[2]; rows2 = mo.rows2; gated = mo.gated; as = mo.as; a1.cnt = mo.rows1;
+    }
+    if (!mok)
+#endif
     if (flag == OFK_KEY_SOLVED && cfg.gate > 0.0) {              // uniform over the workgroup
         Acc a2; acc_zero(a2);
         for (int i = tid; i < n; i += 256) {
@@ -142,6 +180,10 @@
     double rms = 0.0;
 #if KF_ROT
     if (jok) rms = jo.rms;
+    else
+#endif
+#if KF_MAP
+    if (mok) rms = mo.rms;
     else
 #endif
     if (flag == OFK_KEY_SOLVED) {
@@ -182,6 +224,10 @@
     if ((double)live < cfg.min_share * (double)mk) bits |= 4;
     if (angle > cfg.rot_max) bits |= 8;
     if (cfg.max_age > 0 && (step + 1) - key_step > cfg.max_age) bits |= 16;
+#if KF_MAP
+    // M4. a keyframe without a map, and depths that would give it one
+    if (mc.ready_share > 0.0 && map_rows < mc.min_rows && ready >= mc.min_rows && (double)ready >= mc.ready_share * (double)live) bits |= 32;
+#endif
     const bool rekey = bits != 0;
     const int reason = bits ? __ffs(bits) : 0;
 
@@ -196,6 +242,10 @@
         float kx = t.key_xy[2 * r], ky = t.key_xy[2 * r + 1];
         uint8_t m = t.member[r];
         if (rekey) { kx = in.next_pts[2 * r]; ky = in.next_pts[2 * r + 1]; m = 1; }
+#if KF_MAP
+        double krho = km.key_rho[r], kvar = km.key_var[r];          // M5: they move with key_xy; a re-key empties them until M1 fills them
+        if (rekey) { krho = 0.0; kvar = 0.0; }
+#endif
         const unsigned long long bal = __ballot(keep);
         if (lane == 0) s_wave[wave] = __popcll(bal);
         __syncthreads();
@@ -204,12 +254,18 @@
         const int p = off + __popcll(bal & ((1ull << lane) - 1));
         __syncthreads();                                        // every thread has read the rows of this chunk: safe to overwrite
         if (keep) { const size_t w = base + p; t.key_xy[2 * w] = kx; t.key_xy[2 * w + 1] = ky; t.member[w] = m; }
+#if KF_MAP
+        if (keep) { const size_t w = base + p; km.key_rho[w] = krho; km.key_var[w] = kvar; }
+#endif
         if (tid == 0) s_base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
         __syncthreads();
     }
     const int kept = s_base;
     const int extra = in.new_counts ? max(0, min(min(in.new_counts[b], in.max_total - kept), in.stride - kept)) : 0;
     for (int i = tid; i < extra; i += 256) { const size_t w = base + kept + i; t.key_xy[2 * w] = 0.f; t.key_xy[2 * w + 1] = 0.f; t.member[w] = 0; }
+#if KF_MAP
+    for (int i = tid; i < extra; i += 256) { const size_t w = base + kept + i; km.key_rho[w] = 0.0; km.key_var[w] = 0.0; }
+#endif
     if (tid == 0) {
         double *o = t.rec + (size_t)b * OFK_KEY_DOUBLES;
         for (int k = 0; k < OFK_KEY_DOUBLES; ++k) o[k] = 0.0;
@@ -241,6 +297,17 @@
         for (int k = 0; k < 3; ++k) { o[10 + k] = D[k]; o[13 + k] = pos[k]; o[16 + k] = anchor[k]; }
         o[19] = angle; o[26] = (double)nkey_out; o[27] = (double)ndead_out; o[28] = (double)live; o[29] = gated ? 1.0 : 0.0;
         o[30] = (double)bits;
+#if KF_MAP
+        const int cap_out = capture ? key_step : cap_for;
+        ms[0] = cap_out; ms[1] = rekey ? 0 : map_rows;
+        double *q = km.mrec + (size_t)b * OFK_KEYMAP_DOUBLES;
+        for (int k = 0; k < OFK_KEYMAP_DOUBLES; ++k) q[k] = 0.0;
+        q[0] = (double)(mok ? OFK_KEYMAP_USED : use_map ? OFK_KEYMAP_FELL_BACK : map_rows < mc.min_rows ? OFK_KEYMAP_NONE : OFK_KEYMAP_FEW);
+        q[1] = (double)map_rows; q[2] = (double)live_map;
+        if (use_map) { q[3] = mo.rows1; q[4] = mo.rows2; q[5] = mo.sumw; q[6] = mo.spread; }
+        if (use_map && plain_ok) for (int k = 0; k < 3; ++k) q[7 + k] = T1[k];
+        q[10] = capture ? mcnt[0] : 0.0; q[11] = (double)cap_out;
+#endif
 #if KF_ROT
         if (rekey) { for (int k = 0; k < 9; ++k) rst[k] = rw[k]; rst[9] = 1.0; rst[10] = (double)ks_out; }
         double *q = rrec_all + (size_t)b * OFK_KEYROT_DOUBLES;

@@ -198,7 +198,9 @@ __global__ __launch_bounds__(256) void k_keyframe_step_rot(ofk_kf_rows t, ofk_kf
                                                            double *__restrict__ rrec_all)
 {
 #define KF_ROT 1
+#define KF_MAP 0
 #include "k_keyframe_body.inc"
+#undef KF_MAP
 #undef KF_ROT
 }
 

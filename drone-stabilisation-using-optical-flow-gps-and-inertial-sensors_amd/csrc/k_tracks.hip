@@ -204,4 +204,5 @@ void ofk_launch_track_gate(hipStream_t s, const float *prev_pts, const float *ba
 #include "k_track_template.inc"
 #include "k_keyframe.inc"
 #include "k_keyframe_rot.inc"
+#include "k_keyframe_map.inc"
 #include "k_pos_filter.inc"

@@ -164,6 +164,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->tpl = ofk_track_template{OFK_TPL_OFF, 15, 0.8, 3, 2.0, OFK_TPL_KEEP, 6, 2.0, 1.5};
     c->key = ofk_keyframe{OFK_KEY_OFF, 0.2, 2.0, 8, 0.5, 0.5, 0};
     c->krot = ofk_keyframe_rotation{OFK_KEYROT_OFF, OFK_KEYROT_GYRO, {1, 1, 1}, 0.0, 1e-4, 1e-3, 2, 0.1};
+    c->kmap = ofk_keyframe_map{OFK_KEYMAP_OFF, 3, 0.02, 8, 0.5, 1};
     c->posf = ofk_pos_filter{OFK_POSF_OFF, 1.0, 1e-3, 0.0, 1.0, 0.5, 0.0, 1e-3, 0.0, 0.0, 1.0, 0.0, 0.0};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
@@ -2471,10 +2472,12 @@ static const track_array TP_ARRAYS[] = {                         // the template
 static const track_array KF_ARRAYS[] = {TRACK_ARRAY(kfr.key_xy, 8, 0), TRACK_ARRAY(kfr.member, 1, 0), TRACK_ARRAY(kfr.st, 0, OFK_KEY_STATE * 8),
     TRACK_ARRAY(kfr.ist, 0, OFK_KEY_INTS * 4), TRACK_ARRAY(kfr.rec, 0, OFK_KEY_DOUBLES * 8), TRACK_ARRAY(kfr.next_copy, 8, 0)};
 static const track_array KR_ARRAYS[] = {TRACK_ARRAY(kr_st, 0, OFK_KEYROT_STATE * 8), TRACK_ARRAY(kr_rec, 0, OFK_KEYROT_DOUBLES * 8)};
+static const track_array KM_ARRAYS[] = {TRACK_ARRAY(kmr.key_rho, 8, 0), TRACK_ARRAY(kmr.key_var, 8, 0), TRACK_ARRAY(kmr.mstate, 0, 8),
+    TRACK_ARRAY(kmr.mrec, 0, OFK_KEYMAP_DOUBLES * 8)};
 static const track_array PF_ARRAYS[] = {TRACK_ARRAY(pf_x, 0, OFK_POSF_STATES * 8), TRACK_ARRAY(pf_P, 0, OFK_POSF_STATES * OFK_POSF_STATES * 8),
     TRACK_ARRAY(pf_rec, 0, OFK_POSF_DOUBLES * 8), TRACK_ARRAY(pf_in, 0, OFK_POSF_INPUT * 8), TRACK_ARRAY(pf_ist, 0, OFK_POSF_INTS * 4)};
 
-enum { TS_TABLE, TS_DEPTH, TS_TEMPLATE, TS_KEY, TS_KEYROT, TS_POSF };
+enum { TS_TABLE, TS_DEPTH, TS_TEMPLATE, TS_KEY, TS_KEYROT, TS_KEYMAP, TS_POSF };
 struct track_state {
     const char *set, *download, *began;                          // the setter's and the download's names, "run" / "stepped": for messages
     bool (*on)(const ofk_ctx *);
@@ -2506,7 +2509,7 @@ static const track_state TRACK[] = {
      nullptr, TS_TABLE, "the templates are kept per row of the table", nullptr},
     {"ofk_set_keyframe", "ofk_keyframe_download", "stepped", [](const ofk_ctx *c) { return c->key.mode != OFK_KEY_OFF; },
      &ofk_ctx::kf_batch, &ofk_ctx::kf_live, TRACK_LIST(KF_ARRAYS),
-     [](ofk_ctx *c, int B) -> int { ofk_launch_keyframe_begin(c->stream, c->kfr, c->counts, c->max_pts, B); c->kr_live = 0; return OFK_OK; },
+     [](ofk_ctx *c, int B) -> int { ofk_launch_keyframe_begin(c->stream, c->kfr, c->counts, c->max_pts, B); c->kr_live = c->km_live = 0; return OFK_OK; },
      [](ofk_ctx *c, int B) { ofk_launch_keyframe_replace(c->stream, c->kfr, c->limit, c->new_counts, c->max_pts, B); },
      TS_TABLE, "the keyframe is kept per row of the table", "keyframe"},
     {"ofk_set_keyframe_rotation", "ofk_keyframe_rotation_download", "stepped", [](const ofk_ctx *c) { return c->krot.mode != OFK_KEYROT_OFF; },
@@ -2514,6 +2517,11 @@ static const track_state TRACK[] = {
      [](ofk_ctx *c, int B) -> int { ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, nullptr, 0, OFK_KEYROT_NONE, B); return OFK_OK; },
      [](ofk_ctx *c, int B) { ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, c->limit, 0, OFK_KEYROT_NONE, B); },
      TS_KEY, "it refines the keyframe's rotation", nullptr},
+    {"ofk_set_keyframe_map", "ofk_keyframe_map_download", "stepped", [](const ofk_ctx *c) { return c->kmap.mode != OFK_KEYMAP_OFF; },
+     &ofk_ctx::km_batch, &ofk_ctx::km_live, TRACK_LIST(KM_ARRAYS),     // in step with the keyframe's: cleared where that began afresh
+     [](ofk_ctx *c, int B) -> int { ofk_launch_keymap_clear(c->stream, c->kmr, c->kfr.ist, nullptr, c->counts, c->max_pts, 0, 0, B); return OFK_OK; },
+     [](ofk_ctx *c, int B) { ofk_launch_keymap_clear(c->stream, c->kmr, c->kfr.ist, c->limit, c->new_counts, c->max_pts, 0, 1, B); },
+     TS_KEY, "it solves the keyframe's translation", nullptr},
     {"ofk_set_pos_filter", "ofk_pos_filter_download", "stepped", [](const ofk_ctx *c) { return c->posf.mode != OFK_POSF_OFF; },
      &ofk_ctx::pf_batch, &ofk_ctx::pf_live, TRACK_LIST(PF_ARRAYS),     // per stream, not per track: a replacement of the tracks re-keys, the filter runs on
      [](ofk_ctx *c, int B) -> int {                              // not started, at zero; an input handed in before the first step stays
@@ -2554,11 +2562,15 @@ static int track_begin(ofk_ctx *c, const track_state &s, int B)
 // The steps' own refusals with a state on (ofk.h), in their precedence; fu: a fused step's.
 static int track_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const char *who)
 {
-    static const int order[] = {TS_DEPTH, TS_TEMPLATE, TS_KEYROT, TS_POSF, TS_KEY};
+    static const int order[] = {TS_DEPTH, TS_TEMPLATE, TS_KEYROT, TS_KEYMAP, TS_POSF, TS_KEY};
     for (int k : order) {
         const track_state &s = TRACK[k];
         if (!s.on(c)) continue;
         if (!TRACK[s.needs].on(c)) return ofk_fail(c, OFK_E_INVALID, "%s: %s is on without %s: %s", who, s.set, TRACK[s.needs].set, s.why);
+        if (k == TS_KEYMAP) {                                    // the map is the depths', frozen; the joint solve is not in it
+            if (!TRACK[TS_DEPTH].on(c)) return ofk_fail(c, OFK_E_INVALID, "%s: %s is on without %s: the map is the depth state at the keyframe", who, s.set, TRACK[TS_DEPTH].set);
+            if (TRACK[TS_KEYROT].on(c)) return ofk_fail(c, OFK_E_INVALID, "%s: %s is on beside %s: the joint solve over map rows is not built", who, s.set, TRACK[TS_KEYROT].set);
+        }
         if (s.model && (variant == OFK_SOLVE_OFMODULE || (fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY))))
             return refuse_not_sensor_model(c, who, NO_OFMODULE | NO_ROTATIONAL | NO_LEGACY, s.model, s.set);
     }
@@ -2944,10 +2956,33 @@ static bool kr_all_held(const ofk_keyframe_rotation *r)
     if (!r->axes[0] && !r->axes[1] && !r->axes[2]) return true;
     return r->source == OFK_KEYROT_ATTITUDE ? r->sigma_att == 0.0 : r->sigma_gyro == 0.0 && r->sigma_bias == 0.0;
 }
-// the launch of rules 1-5: k_keyframe_step, or with the rotation on (r, not all held) k_keyframe_step_rot in its place
-static void launch_key_step(ofk_ctx *c, const ofk_kf_rows &t, const ofk_kf_in &in, const ofk_keyframe *k, const ofk_keyframe_rotation *r,
-                            double *rst, double *rrec, int batch)
+// the keyframe's map (ofk.h: ofk_set_keyframe_map)
+static int check_keymap(ofk_ctx *c, const ofk_keyframe_map *m, const char *who)
 {
+    if (m->mode != OFK_KEYMAP_OFF && m->mode != OFK_KEYMAP_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_KEYMAP_OFF nor OFK_KEYMAP_ON", who, m->mode);
+    if (m->mode == OFK_KEYMAP_OFF) return OFK_OK;
+    if (!std::isfinite(m->rel_max) || !std::isfinite(m->ready_share)) return ofk_fail(c, OFK_E_INVALID, "%s: rel_max and ready_share must be finite", who);
+    if (m->min_obs < 1) return ofk_fail(c, OFK_E_INVALID, "%s: min_obs = %d must be at least 1", who, m->min_obs);
+    if (!(m->rel_max > 0.0)) return ofk_fail(c, OFK_E_INVALID, "%s: rel_max = %g must be positive", who, m->rel_max);
+    if (m->min_rows < 3) return ofk_fail(c, OFK_E_INVALID, "%s: min_rows = %d must be at least 3", who, m->min_rows);
+    if (m->ready_share < 0.0 || m->ready_share > 1.0) return ofk_fail(c, OFK_E_INVALID, "%s: ready_share = %g outside [0, 1]", who, m->ready_share);
+    if (m->weights != 0 && m->weights != 1) return ofk_fail(c, OFK_E_INVALID, "%s: weights = %d is neither 0 nor 1", who, m->weights);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_keyframe_map(ofk_ctx *c, const ofk_keyframe_map *m)
+{
+    return setting_set(c, &ofk_ctx::kmap, m && m->mode == OFK_KEYMAP_OFF ? nullptr : m, [](ofk_keyframe_map &s) { s.mode = OFK_KEYMAP_OFF; },
+                       [c](const ofk_keyframe_map *v) { return check_keymap(c, v, "ofk_set_keyframe_map"); });
+}
+extern "C" int ofk_get_keyframe_map(const ofk_ctx *c, ofk_keyframe_map *m) { return setting_get(c, &ofk_ctx::kmap, m); }
+
+// the launch of rules 1-5: k_keyframe_step, or with the rotation on (r, not all held) k_keyframe_step_rot in its place, or with the
+// map on (m, mr; never beside r) k_keyframe_step_map
+static void launch_key_step(ofk_ctx *c, const ofk_kf_rows &t, const ofk_kf_in &in, const ofk_keyframe *k, const ofk_keyframe_rotation *r,
+                            double *rst, double *rrec, int batch, const ofk_keyframe_map *m = nullptr, const ofk_km_rows *mr = nullptr)
+{
+    if (m) { ofk_launch_keyframe_step_map(c->stream, t, in, k, m, *mr, batch); return; }
     if (!r) { ofk_launch_keyframe_step(c->stream, t, in, k, batch); return; }
     if (kr_all_held(r)) {
         ofk_launch_keyframe_step(c->stream, t, in, k, batch);
@@ -2964,6 +2999,15 @@ extern "C" int ofk_keyframe_rotation_download(ofk_ctx *c, double *rec)
     if (!rec) return ofk_fail(c, OFK_E_INVALID, "ofk_keyframe_rotation_download: NULL argument");
     const download_row row = {rec, c->kr_rec, OFK_KEYROT_DOUBLES * 8, OFK_KEYROT_DOUBLES * 8};
     return rows_download(c, c->kr_batch, 0, &row, 1);
+}
+
+extern "C" int ofk_keyframe_map_download(ofk_ctx *c, double *key_rho, double *key_var, int stride, double *rec)
+{
+    if (!c) return OFK_E_INVALID;
+    TRY(track_download_begin(c, TRACK[TS_KEYMAP], key_rho || key_var, stride));
+    const download_row rows[] = {{key_rho, c->kmr.key_rho, 8, 0}, {key_var, c->kmr.key_var, 8, 0},
+                                 {rec, c->kmr.mrec, OFK_KEYMAP_DOUBLES * 8, OFK_KEYMAP_DOUBLES * 8}};
+    return rows_download(c, c->km_batch, stride, rows, 3);
 }
 
 extern "C" int ofk_keyframe_download(ofk_ctx *c, float *key_xy, uint8_t *member, int stride, double *R_acc, double *rec)
@@ -2987,16 +3031,20 @@ extern "C" int ofk_keyframe_reset(ofk_ctx *c, int b, const double *anchor)
     TRY(track_begin(c, TRACK[TS_KEY], c->stream_batch));
     ofk_launch_keyframe_reset(c->stream, c->kfr, b, c->max_pts, p);
     if (c->kr_st && c->kr_live == c->stream_batch) ofk_launch_keyrot_clear(c->stream, c->kr_st, c->kr_rec, nullptr, b, OFK_KEYROT_NONE, 1);
+    if (c->kmr.key_rho && c->km_live == c->stream_batch) ofk_launch_keymap_clear(c->stream, c->kmr, c->kfr.ist, nullptr, nullptr, c->max_pts, b, 0, 1);
     TRY(check_launch(c, who));
     OFK_HIP(c, hipStreamSynchronize(c->stream));
     return OFK_OK;
 }
 
-// rules 1-5 on host buffers: device scratch only; rot != NULL: with the rotation's rule 2 (rstate in and out, rrec out)
+// what ofk_keyframe_map_step adds to ofk_keyframe_step's arguments
+struct host_map { const ofk_keyframe_map *set; const double *rho, *var; const int *nobs; double *key_rho, *key_var; int *mstate; double *mrec; };
+// rules 1-5 on host buffers: device scratch only; rot != NULL: with the rotation's rule 2 (rstate in and out, rrec out); hm != NULL:
+// with the map's rules M1-M5 (never beside rot)
 static int keyframe_step_host(ofk_ctx *c, const char *who, const ofk_keyframe *set, const ofk_keyframe_rotation *rot, const float *next_pts,
                               const uint8_t *status, const int *counts, const double *sensors, const double *v_uav, const int *solved,
                               const int *step, float *key_xy, uint8_t *member, double *state, int *istate, const int *new_counts, int max_total,
-                              int batch, int stride, double *rec, double *rstate, double *rrec)
+                              int batch, int stride, double *rec, double *rstate, double *rrec, const host_map *hm = nullptr)
 {
     if (!set || !next_pts || !status || !counts || !sensors || !v_uav || !solved || !step || !key_xy || !member || !state || !istate)
         return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
@@ -3009,12 +3057,19 @@ static int keyframe_step_host(ofk_ctx *c, const char *who, const ofk_keyframe *s
         if (rot->mode == OFK_KEYROT_OFF) return ofk_fail(c, OFK_E_INVALID, "%s: the rotation setting is off", who);
         TRY(check_keyrot(c, rot, who));
     }
+    if (hm) {
+        if (!hm->set || !hm->key_rho || !hm->key_var || !hm->mstate) return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
+        if ((hm->rho == nullptr) != (hm->var == nullptr) || (hm->rho == nullptr) != (hm->nobs == nullptr))
+            return ofk_fail(c, OFK_E_INVALID, "%s: rho, var and nobs come together", who);
+        if (hm->set->mode == OFK_KEYMAP_OFF) return ofk_fail(c, OFK_E_INVALID, "%s: the map setting is off", who);
+        TRY(check_keymap(c, hm->set, who));
+    }
     TRY(check_counts(c, who, counts, batch, stride));
     const size_t np = (size_t)batch * stride, B = (size_t)batch;
     const host_buf h_rec = {stage_step_records(v_uav, solved, B, 8)};
     if (!h_rec.p) return ofk_fail(c, OFK_E_INVALID, "%s: out of host memory", who);
     Bump bp;
-    TRY(est_begin(c, np * 18 + B * ((OFK_RECORD_DOUBLES + OFK_KEY_DOUBLES + OFK_KEY_STATE + OFK_SENSOR_DOUBLES + OFK_KEYROT_STATE + OFK_KEYROT_DOUBLES) * 8 + OFK_KEY_INTS * 4 + 12) + 18 * 256, bp));
+    TRY(est_begin(c, np * (18 + (hm ? 36 : 0)) + B * ((OFK_RECORD_DOUBLES + OFK_KEY_DOUBLES + OFK_KEY_STATE + OFK_SENSOR_DOUBLES + OFK_KEYROT_STATE + OFK_KEYROT_DOUBLES + OFK_KEYMAP_DOUBLES) * 8 + OFK_KEY_INTS * 4 + 20) + 26 * 256, bp));
     ofk_kf_rows t = {};
     t.key_xy = (float *)bp.put(key_xy, np * 8); t.member = (uint8_t *)bp.put(member, np); t.st = bp.put(state, B * OFK_KEY_STATE * 8);
     t.ist = (int *)bp.put(istate, B * OFK_KEY_INTS * 4); t.rec = bp.take(B * OFK_KEY_DOUBLES * 8);
@@ -3026,13 +3081,21 @@ static int keyframe_step_host(ofk_ctx *c, const char *who, const ofk_keyframe *s
     in.v = bp.put(h_rec.p, B * OFK_RECORD_DOUBLES * 8); in.plain = 0;
     in.step = (const int *)bp.put(step, B * 4); in.step_stride = 1;
     double *d_rst = rot ? bp.put(rstate, B * OFK_KEYROT_STATE * 8) : nullptr, *d_rrec = rot ? bp.take(B * OFK_KEYROT_DOUBLES * 8) : nullptr;
+    ofk_km_rows mr = {};
+    if (hm) {
+        mr.key_rho = bp.put(hm->key_rho, np * 8); mr.key_var = bp.put(hm->key_var, np * 8); mr.mstate = (int *)bp.put(hm->mstate, B * 8);
+        mr.mrec = bp.take(B * OFK_KEYMAP_DOUBLES * 8);
+        mr.rho = bp.put(hm->rho, np * 8); mr.var = bp.put(hm->var, np * 8); mr.nobs = (const int *)bp.put(hm->nobs, np * 4);
+    }
     if (bp.rc != OFK_OK || hipStreamSynchronize(c->stream) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
-    launch_key_step(c, t, in, set, rot, d_rst, d_rrec, batch);
-    TRY(check_launch(c, rot ? "k_keyframe_step_rot" : "k_keyframe_step"));
-    const back_row back[] = {{rot ? rstate : nullptr, d_rst, B * OFK_KEYROT_STATE * 8}, {rot ? rrec : nullptr, d_rrec, B * OFK_KEYROT_DOUBLES * 8},
+    launch_key_step(c, t, in, set, rot, d_rst, d_rrec, batch, hm ? hm->set : nullptr, &mr);
+    TRY(check_launch(c, hm ? "k_keyframe_step_map" : rot ? "k_keyframe_step_rot" : "k_keyframe_step"));
+    const back_row back[] = {{hm ? hm->key_rho : nullptr, mr.key_rho, np * 8}, {hm ? hm->key_var : nullptr, mr.key_var, np * 8},
+                             {hm ? hm->mstate : nullptr, mr.mstate, B * 8}, {hm ? hm->mrec : nullptr, mr.mrec, B * OFK_KEYMAP_DOUBLES * 8},
+                             {rot ? rstate : nullptr, d_rst, B * OFK_KEYROT_STATE * 8}, {rot ? rrec : nullptr, d_rrec, B * OFK_KEYROT_DOUBLES * 8},
                              {key_xy, t.key_xy, np * 8}, {member, t.member, np}, {state, t.st, B * OFK_KEY_STATE * 8}, {istate, t.ist, B * OFK_KEY_INTS * 4},
                              {rec, t.rec, B * OFK_KEY_DOUBLES * 8}};
-    return fetch_back(c, who, back, 7);
+    return fetch_back(c, who, back, 11);
 }
 
 extern "C" int ofk_keyframe_step(ofk_ctx *c, const ofk_keyframe *set, const float *next_pts, const uint8_t *status, const int *counts,
@@ -3053,6 +3116,18 @@ extern "C" int ofk_keyframe_rotation_step(ofk_ctx *c, const ofk_keyframe *set, c
     if (!rot) return ofk_fail(c, OFK_E_INVALID, "ofk_keyframe_rotation_step: NULL argument");
     return keyframe_step_host(c, "ofk_keyframe_rotation_step", set, rot, next_pts, status, counts, sensors, v_uav, solved, step, key_xy, member,
                               state, istate, new_counts, max_total, batch, stride, rec, rstate, rrec);
+}
+
+extern "C" int ofk_keyframe_map_step(ofk_ctx *c, const ofk_keyframe *set, const ofk_keyframe_map *map, const float *next_pts, const uint8_t *status,
+                                     const int *counts, const double *sensors, const double *v_uav, const int *solved, const int *step,
+                                     float *key_xy, uint8_t *member, double *state, int *istate, const int *new_counts, int max_total, int batch,
+                                     int stride, double *rec, const double *rho, const double *var, const int *nobs, double *key_rho,
+                                     double *key_var, int *mstate, double *mrec)
+{
+    if (!c) return OFK_E_INVALID;
+    const host_map hm = {map, rho, var, nobs, key_rho, key_var, mstate, mrec};
+    return keyframe_step_host(c, "ofk_keyframe_map_step", set, nullptr, next_pts, status, counts, sensors, v_uav, solved, step, key_xy, member,
+                              state, istate, new_counts, max_total, batch, stride, rec, nullptr, nullptr, &hm);
 }
 
 // ------------------------------------------------------------------------------------------------ position filter
@@ -3381,7 +3456,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         if (s.on(c)) TRY(track_begin(c, s, B));                  // no state of these tracks yet: begun afresh
         else c->*s.live = 0;                                     // the tracks move on without it
     }
-    const bool table = on[TS_TABLE], depth = on[TS_DEPTH], templ = on[TS_TEMPLATE], keyf = on[TS_KEY], krot = on[TS_KEYROT];
+    const bool table = on[TS_TABLE], depth = on[TS_DEPTH], templ = on[TS_TEMPLATE], keyf = on[TS_KEY], krot = on[TS_KEYROT], kmap = on[TS_KEYMAP];
     const bool flow_seed = table && c->tt.seed == OFK_TT_SEED_FLOW;
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
@@ -3453,7 +3528,9 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
             in.new_counts = any ? c->new_counts : nullptr; in.max_total = p->max_corners; in.sensors = c->sensors;
             in.imu = fu && fu->use_imu ? c->imu_state : nullptr; in.v = c->records; in.plain = fu ? 0 : 1;
             in.step = c->ttr.head; in.step_stride = 2;
-            launch_key_step(c, c->kfr, in, &c->key, krot ? &c->krot : nullptr, c->kr_st, c->kr_rec, B);
+            ofk_km_rows mr = c->kmr;                             // the depths as the previous step left them: their step is behind this launch
+            mr.rho = c->tdr.rho; mr.var = c->tdr.var; mr.nobs = c->tdr.nobs;
+            launch_key_step(c, c->kfr, in, &c->key, krot ? &c->krot : nullptr, c->kr_st, c->kr_rec, B, kmap ? &c->kmap : nullptr, &mr);
             if (on[TS_POSF])                                     // directly behind it, on the record it has just written
                 ofk_launch_pos_filter_step(c->stream, &c->posf, c->pf_x, c->pf_P, c->pf_ist, c->pf_rec, c->pf_in, c->records, fu ? 0 : 1, c->kfr.rec,
                                            in.imu ? c->imu_state + 6 : c->sensors + 7, in.imu ? OFK_IMU_STATE : OFK_SENSOR_DOUBLES, B);

@@ -55,6 +55,10 @@ struct ofk_kf_in {
     const double *v; int plain;                                  // [B][OFK_RECORD_DOUBLES]: v_uav in 8-10, solved in 15 (plain: rank 3 in slot 4)
     const int *step; int step_stride;                            // the table's step per stream, ints between streams
 };
+// the keyframe's map (ofk.h: ofk_set_keyframe_map): key_rho, key_var [B][stride] in the table's row order; mstate [B][2] =
+// (captured_for, map_rows); mrec [B][OFK_KEYMAP_DOUBLES]; rho, var, nobs: the depth state as the previous step left it, read only
+// (NULL: the stream has none, no row is mature)
+struct ofk_km_rows { double *key_rho, *key_var; int *mstate; double *mrec; const double *rho, *var; const int *nobs; };
 
 struct ofk_comm;
 struct ofk_ctx {
@@ -166,6 +170,9 @@ struct ofk_ctx {
     ofk_keyframe_rotation krot;              // ofk_set_keyframe_rotation: mode OFK_KEYROT_OFF unless set
     double *kr_st, *kr_rec;                  // [max_batch][OFK_KEYROT_STATE], [max_batch][OFK_KEYROT_DOUBLES]; one lazy allocation (kr_st owns it)
     int kr_batch, kr_live;                   // (kr_live: streams whose rotation state is in step with their keyframe) streams of the latest step with the rotation on (ofk_keyframe_rotation_download), 0 = none
+    ofk_keyframe_map kmap;                   // ofk_set_keyframe_map: mode OFK_KEYMAP_OFF unless set
+    ofk_km_rows kmr;                         // the map's device rows and per-stream state (rho, var, nobs unused here); one lazy allocation (kmr.key_rho owns it)
+    int km_batch, km_live;                   // streams of the latest step with the map on (ofk_keyframe_map_download), 0 = none; streams whose map is in step with their keyframe
     ofk_pos_filter posf;                     // ofk_set_pos_filter: mode OFK_POSF_OFF unless set
     double *pf_x, *pf_P, *pf_rec, *pf_in;    // [max_batch][12], [max_batch][144], [max_batch][OFK_POSF_DOUBLES], [max_batch][OFK_POSF_INPUT]; one lazy allocation (pf_x owns it)
     int *pf_ist;                             // [max_batch][OFK_POSF_INTS]
@@ -310,6 +317,13 @@ void ofk_launch_keyframe_step(hipStream_t s, const ofk_kf_rows &t, const ofk_kf_
 void ofk_launch_keyframe_step_rot(hipStream_t s, const ofk_kf_rows &t, const ofk_kf_in &in, const ofk_keyframe *k, const ofk_keyframe_rotation *r,
                                   double *rst, double *rrec, int batch);
 void ofk_launch_keyrot_clear(hipStream_t s, double *rst, double *rrec, const int *limit, int b0, int flag, int batch);
+// the keyframe's map (ofk.h: ofk_set_keyframe_map; k_keyframe_map.inc): k_keyframe_step's launch with rules M1-M5 around it, and the
+// map cleared beside the keyframe's begin (limit NULL, counts), replace (limit, the new counts, keep_rec) and reset (one stream b0,
+// counts NULL: every row)
+void ofk_launch_keyframe_step_map(hipStream_t s, const ofk_kf_rows &t, const ofk_kf_in &in, const ofk_keyframe *k, const ofk_keyframe_map *m,
+                                  const ofk_km_rows &r, int batch);
+void ofk_launch_keymap_clear(hipStream_t s, const ofk_km_rows &r, const int *key_ist, const int *limit, const int *counts, int stride, int b0,
+                             int keep_rec, int batch);
 // the position filter (ofk.h: ofk_set_pos_filter; k_pos_filter.inc): rules 1-8 in one launch behind the keyframe's step (v: the step's
 // records, plain as ofk_kf_in's; key_rec: the keyframe's records; rw: R_world, rw_stride doubles apart), and the state of `batch`
 // streams from b0 on set back to "not started" at the position p (input NULL: the input rows stay)

@@ -44,6 +44,7 @@ SYMBOLS = (
     "ofk_set_track_depth", "ofk_get_track_depth", "ofk_track_depth_download", "ofk_track_depth_reset", "ofk_track_depth_step",
     "ofk_set_keyframe", "ofk_get_keyframe", "ofk_keyframe_download", "ofk_keyframe_reset", "ofk_keyframe_step",
     "ofk_set_keyframe_rotation", "ofk_get_keyframe_rotation", "ofk_keyframe_rotation_download", "ofk_keyframe_rotation_step",
+    "ofk_set_keyframe_map", "ofk_get_keyframe_map", "ofk_keyframe_map_download", "ofk_keyframe_map_step",
     "ofk_set_pos_filter", "ofk_get_pos_filter", "ofk_pos_filter_input", "ofk_pos_filter_reset", "ofk_pos_filter_download", "ofk_pos_filter_step",
     "ofk_set_track_template", "ofk_get_track_template", "ofk_track_template_download", "ofk_track_affine_fit", "ofk_track_template_step",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
@@ -121,6 +122,10 @@ KEYROT_OFF, KEYROT_ON = 0, 1                             # ofk_set_keyframe_rota
 KEYROT_GYRO, KEYROT_ATTITUDE = 0, 1                      # where R_acc comes from
 KEYROT_DOUBLES, KEYROT_STATE, KEYROT_MAX_ITERS = 40, 12, 8   # the record; R_world at the keyframe, valid, its key_step
 KEYROT_OK, KEYROT_NONE, KEYROT_SINGULAR, KEYROT_LARGE, KEYROT_HELD = 0, 1, 2, 3, 4   # the record's flag
+KEYMAP_OFF, KEYMAP_ON = 0, 1                             # ofk_set_keyframe_map
+KEYMAP_DOUBLES = 32                                      # the record
+KEYMAP_USED, KEYMAP_NONE, KEYMAP_FEW, KEYMAP_FELL_BACK = 0, 1, 2, 3   # the record's flag
+KEY_RE_MAP = 6                                           # the keyframe record's re-key reason: depths that would give the keyframe a map
 POSF_OFF, POSF_ON = 0, 1                                 # ofk_set_pos_filter
 POSF_STATES, POSF_INPUT, POSF_INTS, POSF_DOUBLES = 12, 12, 16, 48   # x = (p, v, b, c); the input row; the counts; the record
 POSF_NOT, POSF_APPLIED, POSF_GATED, POSF_REFUSED = 0, 1, 2, 3       # an update's outcome in the record
@@ -584,6 +589,28 @@ def keyframe_rotation_setting(mode=True, source="gyro", axes=(1, 1, 1), sigma_gy
     return r
 
 
+class KeyframeMap(C.Structure):
+    """ofk_keyframe_map (include/ofk.h): the key solve against the per-track depths frozen at the keyframe."""
+    _fields_ = [("mode", C.c_int), ("min_obs", C.c_int), ("rel_max", C.c_double), ("min_rows", C.c_int), ("ready_share", C.c_double),
+                ("weights", C.c_int)]
+
+
+def keyframe_map_setting(mode=True, min_obs=3, rel_max=0.02, min_rows=8, ready_share=0.5, weights=1):
+    """A KeyframeMap structure from names: mode True / False (or KEYMAP_*); a depth enters the map with at least min_obs measurements
+    and a sigma of at most rel_max of itself; the map is used with at least min_rows rows captured and alive; a keyframe without a
+    map is replaced once ready_share of its live rows have such a depth (0: never); weights 1: each row weighted by its depth's
+    variance times its parallax."""
+    mode = int(mode)
+    if mode not in (KEYMAP_OFF, KEYMAP_ON):
+        raise ValueError(f"keyframe-map mode {mode} is none of KEYMAP_OFF, KEYMAP_ON")
+    m = KeyframeMap(mode, int(min_obs), float(rel_max), int(min_rows), float(ready_share), int(weights))
+    if mode != KEYMAP_OFF:
+        if not (m.min_obs >= 1 and np.isfinite(m.rel_max) and m.rel_max > 0 and m.min_rows >= 3 and 0 <= m.ready_share <= 1 and m.weights in (0, 1)):
+            raise ValueError(f"keyframe-map setting outside its range: min_obs {m.min_obs} >= 1, rel_max {m.rel_max} finite > 0, "
+                             f"min_rows {m.min_rows} >= 3, ready_share {m.ready_share} in [0, 1], weights {m.weights} in (0, 1)")
+    return m
+
+
 class PosFilter(C.Structure):
     """ofk_pos_filter (include/ofk.h): keyframe displacement, velocity and position fixes fused in a filter with a cloned state."""
     _fields_ = [("mode", C.c_int), ("dt", C.c_double), ("sigma_v", C.c_double), ("floor", C.c_double), ("infl", C.c_double), ("share", C.c_double),
@@ -622,7 +649,7 @@ class Fusion(C.Structure):
 SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("gyro_bias", GyroBias), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate), ("lk_light", LkLight),
             ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion),
             ("track_table", TrackTable), ("track_depth", TrackDepth), ("track_template", TrackTemplate), ("keyframe", Keyframe),
-            ("keyframe_rotation", KeyframeRotation), ("pos_filter", PosFilter))
+            ("keyframe_rotation", KeyframeRotation), ("keyframe_map", KeyframeMap), ("pos_filter", PosFilter))
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -726,6 +753,9 @@ def load_library():
         L.ofk_keyframe_rotation_download.argtypes = [vp, vp]
         L.ofk_keyframe_rotation_step.argtypes = [vp, C.POINTER(Keyframe), C.POINTER(KeyframeRotation), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i,
                                                  i, i, vp, vp, vp]
+        L.ofk_keyframe_map_download.argtypes = [vp, vp, vp, i, vp]
+        L.ofk_keyframe_map_step.argtypes = [vp, C.POINTER(Keyframe), C.POINTER(KeyframeMap), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp,
+                                            vp, vp, vp, vp, vp, vp, vp]
         L.ofk_pos_filter_input.argtypes = [vp, vp]
         L.ofk_pos_filter_reset.argtypes = [vp, i, vp]
         L.ofk_pos_filter_download.argtypes = [vp, vp, vp, vp, vp]
@@ -1379,6 +1409,50 @@ class Context:
         rot = rotation if rotation is not None else keyframe_rotation_setting()
         return self._keyframe_step("keyframe_rotation_step", kf, rot, next_pts, status, counts, sensors, v_uav, solved, step, state, new_counts,
                                    max_total)
+
+    def set_keyframe_map(self, keyframe_map=None, **settings):
+        """ofk_set_keyframe_map: a KeyframeMap (or keyframe_map_setting's keywords); None or mode False switches it off.  Every later
+        stream step with ofk_set_keyframe and ofk_set_track_depth on (both must be) freezes the depths at each keyframe and solves the
+        key translation against them instead of the ground plane.  pairs_run ignores the setting."""
+        self._set_struct(self._L.ofk_set_keyframe_map, keyframe_map, settings, keyframe_map_setting, lock=True)
+
+    def get_keyframe_map(self):
+        return self._get_struct(self._L.ofk_get_keyframe_map, KeyframeMap)
+
+    def keyframe_map_download(self, batch=None, stride=None):
+        """ofk_keyframe_map_download -> dict(key_rho, key_var [batch,stride] f64, rec [batch,32]) of the streams of the latest step with
+        the setting on, rows in the order of the tracks that step returned.  rec: flag 0 (KEYMAP_*), map_rows 1, live map rows 2, rows
+        of the first / the gated map solve 3 / 4, sum of weights 5, spread px 6, the plain first solve's T 7-9, rows captured this
+        step 10, captured_for 11."""
+        f = ((), np.float64)
+        return self._track_download("keyframe_map", batch, stride, (f, f), [((KEYMAP_DOUBLES,), np.float64)], ("key_rho", "key_var", "rec"))
+
+    def keyframe_map_step(self, next_pts, status, counts, sensors, v_uav, solved, step, state, depth=None, new_counts=None, max_total=None,
+                          keyframe=None, keyframe_map=None):
+        """ofk_keyframe_map_step, the stage entry: keyframe_step's arguments; state also carries key_rho, key_var [B,S] f64 and mstate
+        [B,2] i32 (absent: zero); depth: dict(rho, var [B,S] f64, nobs [B,S] i32) as the previous depth step left it (None: no depth
+        state); keyframe: a Keyframe (None: the defaults), keyframe_map: a KeyframeMap (None: the defaults).
+        -> (state with key_rho, key_var, mstate; rec [B,32]; mrec [B,32]), new arrays.  Touches no resident state."""
+        who = "keyframe_map_step"
+        kf = keyframe if keyframe is not None else keyframe_setting()
+        km = keyframe_map if keyframe_map is not None else keyframe_map_setting()
+        nn, B, S, mt = self._stage_rows(who, next_pts, "next_pts", max_total)
+        st = _arr(status, np.uint8, (B, S)); cn = _arr(counts, np.int32, (B,)); sn = _arr(sensors, np.float64, (B, SENSOR_DOUBLES))
+        vu = _arr(v_uav, np.float64, (B, 3)); so = _arr(solved, np.int32, (B,)); sp = _arr(step, np.int32, (B,))
+        kx = np.array(_arr(state["key_xy"], np.float32, (B, S, 2))); mem = np.array(_arr(state["member"], np.uint8, (B, S)))
+        sd = np.array(_arr(state["state"], np.float64, (B, KEY_STATE))); si = np.array(_arr(state["istate"], np.int32, (B, KEY_INTS)))
+        own = lambda name, dtype, shape: np.zeros(shape, dtype) if state.get(name) is None else np.array(_arr(state[name], dtype, shape))
+        kr = own("key_rho", np.float64, (B, S)); kv = own("key_var", np.float64, (B, S)); ms = own("mstate", np.int32, (B, 2))
+        rho = var = nobs = None
+        if depth is not None:
+            rho = _arr(depth["rho"], np.float64, (B, S)); var = _arr(depth["var"], np.float64, (B, S)); nobs = _arr(depth["nobs"], np.int32, (B, S))
+        nc = _opt(new_counts, np.int32, (B,))
+        rec = np.zeros((B, KEY_DOUBLES), np.float64); mrec = np.zeros((B, KEYMAP_DOUBLES), np.float64)
+        with self._lock:
+            self._ck(self._L.ofk_keyframe_map_step(self._h, C.byref(kf), C.byref(km), _p(nn), _p(st), _p(cn), _p(sn), _p(vu), _p(so), _p(sp), _p(kx),
+                                                   _p(mem), _p(sd), _p(si), _p(nc), mt, B, S, _p(rec), _p(rho), _p(var), _p(nobs), _p(kr), _p(kv),
+                                                   _p(ms), _p(mrec)))
+        return dict(key_xy=kx, member=mem, state=sd, istate=si, key_rho=kr, key_var=kv, mstate=ms), rec, mrec
 
     def set_pos_filter(self, pos_filter=None, **settings):
         """ofk_set_pos_filter: a PosFilter (or pos_filter_setting's keywords); None or mode False switches it off.  Every later stream

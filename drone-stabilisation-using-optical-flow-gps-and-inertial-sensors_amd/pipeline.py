@@ -181,6 +181,10 @@ class PipelineConfig:
     # keyframe_rotation (ofk.h: ofk_set_keyframe_rotation): None, True (the defaults) or an ofk.KeyframeRotation: the keyframe's solve
     # refines the accumulated rotation together with the translation; it needs keyframe on
     keyframe_rotation: object = None
+    # keyframe_map (ofk.h: ofk_set_keyframe_map): None, True (the defaults) or an ofk.KeyframeMap: the keyframe's translation is
+    # solved against the per-track depths frozen at the keyframe, not the ground plane; it needs keyframe and track_depth on;
+    # FlowPipeline ignores it
+    keyframe_map: object = None
     # pos_filter (ofk.h: ofk_set_pos_filter): None, True (the defaults) or an ofk.PosFilter: every stream fuses the keyframe's
     # displacement, the step's velocity and position fixes in a filter with a cloned state; it needs keyframe on; FlowPipeline ignores it
     pos_filter: object = None
@@ -308,6 +312,15 @@ class PipelineConfig:
         m = self._struct_setting("keyframe_rotation", ofk.KeyframeRotation, ofk.keyframe_rotation_setting)
         if m is not None and self.keyframe_setting() is None:
             raise ValueError("keyframe_rotation needs keyframe on")
+        return m
+
+    def keyframe_map_setting(self):
+        """The ofk.KeyframeMap structure of this configuration, None when the key solve is the plane's."""
+        m = self._struct_setting("keyframe_map", ofk.KeyframeMap, ofk.keyframe_map_setting)
+        if m is not None and (self.keyframe_setting() is None or self.track_depth_setting() is None):
+            raise ValueError("keyframe_map needs keyframe and track_depth on")
+        if m is not None and self.keyframe_rotation_setting() is not None:
+            raise ValueError("keyframe_map beside keyframe_rotation: the joint solve over map rows is not built")
         return m
 
     def pos_filter_setting(self):
@@ -446,7 +459,7 @@ def _apply_settings(ctx, cfg, zones):
         steps += [(ctx.set_zones, cfg.zones_setting), (ctx.set_gyro_bias, cfg.gyro_bias_setting), (ctx.set_track_table, cfg.track_table_setting),
                   (ctx.set_track_depth, cfg.track_depth_setting), (ctx.set_track_template, cfg.track_template_setting),
                   (ctx.set_keyframe, cfg.keyframe_setting), (ctx.set_keyframe_rotation, cfg.keyframe_rotation_setting),
-                  (ctx.set_pos_filter, cfg.pos_filter_setting)]
+                  (ctx.set_keyframe_map, cfg.keyframe_map_setting), (ctx.set_pos_filter, cfg.pos_filter_setting)]
     steps += [(ctx.set_camera, cfg.camera_setting), (ctx.set_rolling_shutter, cfg.rolling_shutter_setting),
               (ctx.set_finite_motion, cfg.finite_motion_setting)]
     for setter, setting in steps:                                # every *_setting() is None when its setting is off
@@ -604,6 +617,19 @@ class FlowStream:
         return dict(delta=rec[:, 0:3].copy(), R_hat=rec[:, 4:13].reshape(-1, 3, 3).copy(), C_delta=ofk.cov_matrix(rec[:, 13:19]),
                     flag=rec[:, 3].astype(np.int32), prior=rec[:, 28:31].copy(), eig=rec[:, 25:28].copy(), iterations=rec[:, 31].astype(np.int32),
                     rec=rec)
+
+    def key_map(self):
+        """The keyframes' maps behind the latest step (ofk.h: ofk_set_keyframe_map): dict(flag [batch] (ofk.KEYMAP_*); map_rows,
+        live_rows, rows, rows_gated, captured, captured_for [batch]; weight_sum, spread [batch]; T_plain [batch, 3]: the plain first
+        solve's translation where both ran; key_rho, key_var, ids: per stream the rows of the tracks that step returned, in their
+        order, ids joined from the track table; rec [batch, 32])."""
+        d = self.ctx.keyframe_map_download(self.batch)
+        rec = d["rec"]
+        out = dict(self._track_rows(d, ("key_rho", "key_var")), flag=rec[:, 0].astype(np.int32), weight_sum=rec[:, 5].copy(), spread=rec[:, 6].copy(),
+                   T_plain=rec[:, 7:10].copy(), rec=rec)
+        for k, s in (("map_rows", 1), ("live_rows", 2), ("rows", 3), ("rows_gated", 4), ("captured", 10), ("captured_for", 11)):
+            out[k] = rec[:, s].astype(np.int32)
+        return out
 
     def position_input(self, du=None, fix=None, fix_sigma=None):
         """What the position filter takes in with the next step that is not held (ofk.h: ofk_pos_filter_input): du [batch, 3] the

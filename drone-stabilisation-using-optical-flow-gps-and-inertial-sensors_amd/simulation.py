@@ -74,6 +74,14 @@ def keyframe_rotation_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None,
     return step(np.asarray(next_pts, np.float32)[:, :2], sensors, v_uav, state=state, **kw)
 
 
+def keyframe_map_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None, depth=None, **kw):
+    """keyframe_step with the key translation solved against the per-track depths frozen at the keyframe (ofk.h:
+    ofk_keyframe_map_step); velocity_node.keyframe_map_step's arguments and returns: (state with key_rho, key_var, mstate; rec [32];
+    mrec [32])."""
+    from .velocity_node import keyframe_map_step as step
+    return step(np.asarray(next_pts, np.float32)[:, :2], sensors, v_uav, state=state, depth=depth, **kw)
+
+
 def pos_filter_step(v_uav, key_rec, R_world=None, state=None, **kw):
     """One step of a stream's position filter without images (ofk.h: ofk_pos_filter_step); velocity_node.pos_filter_step's arguments
     and returns: (state dict(x, P, istate), rec [48])."""

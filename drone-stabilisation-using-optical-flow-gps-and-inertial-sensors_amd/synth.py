@@ -254,13 +254,18 @@ def apply_exposure(img, gain=1.0, bias=0.0, vignette=0.0):
 
 
 def render_sequence(h, w, seed, n_frames, v=(0.003, -0.002, 0.001), omega=(0.002, -0.001, 0.003), d=1.0, n=(0, 0, 1),
-                    scaling=None, margin=96, camera=None, rolling_shutter=None, motion="linear"):
+                    scaling=None, margin=96, camera=None, rolling_shutter=None, motion="linear", relief=None):
     """`n_frames` BGR frames of one stream under constant per-frame motion: frame k shows the texture through H^k.
+    relief (default None: the one plane): render_pair's dict(rect=(x0, y0, x1, y1), height=h), the rect in the pixels of frame 0: a
+    second plane at distance d (1 - h) with the same normal, painted like the ground; frame k shows it through its own homography
+    Hr^k (info["H_relief"]) over the pixels that Hr^-k takes into the rect.  Not with a camera or a rolling shutter.
     motion: pixel_homography's ("finite": every step is the exact rigid motion with the plane n, d in the axes of the step's later
     frame; not with a rolling shutter).
     Returns (frames [n,h,w,3] uint8, info dict as render_pair).  camera: as in render_pair.  rolling_shutter: as in render_pair, with
     row y of frame k seen through (I + tau G) H^k, tau = readout * (y / h - anchor), G = H - I: the linearised motion over the row
     time behind the k whole steps (I + (k + tau) G itself would drift from H^k with k)."""
+    if relief is not None and (camera is not None or rolling_shutter is not None):
+        raise ValueError("render_sequence: relief is rendered for the ideal pinhole with a global shutter alone")
     if camera is not None:
         scaling, cx, cy, xx, yy, margin = _camera_view(h, w, camera, margin)
     else:
@@ -272,6 +277,12 @@ def render_sequence(h, w, seed, n_frames, v=(0.003, -0.002, 0.001), omega=(0.002
     if rolling_shutter is not None and motion != "linear":
         raise ValueError("render_sequence: a rolling shutter is rendered through the linearised homography: motion must be 'linear'")
     H = pixel_homography(v, omega, d, n, scaling, cx, cy, motion)
+    if relief is not None:
+        x0, y0, x1, y1 = (int(c) for c in relief["rect"])
+        hr = float(relief["height"])
+        if not (0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h and hr < 1.0):
+            raise ValueError(f"render_sequence: relief rect {relief['rect']} outside the {w} x {h} frame or height {hr} not below 1")
+        Hr, Hrk = pixel_homography(v, omega, d * (1.0 - hr), n, scaling, cx, cy, motion), np.eye(3)
     frames = np.empty((n_frames, h, w, 3), np.uint8)
     Hk = np.eye(3)
     tau = None if rolling_shutter is None else _row_times(h, rolling_shutter)
@@ -286,7 +297,20 @@ def render_sequence(h, w, seed, n_frames, v=(0.003, -0.002, 0.001), omega=(0.002
         base, tint = _bilinear(T, sx, sy), _bilinear(T2, sx, sy)
         for ch, g in enumerate((0.10, -0.06, 0.08)):
             frames[k, ..., ch] = np.clip(np.rint(base + g * (tint - 127.5)), 0, 255).astype(np.uint8)
+        if relief is not None:
+            Hri = np.linalg.inv(Hrk)
+            den = Hri[2, 0] * xx + Hri[2, 1] * yy + Hri[2, 2]
+            qx = (Hri[0, 0] * xx + Hri[0, 1] * yy + Hri[0, 2]) / den
+            qy = (Hri[1, 0] * xx + Hri[1, 1] * yy + Hri[1, 2]) / den
+            roof = (qx >= x0) & (qx < x1) & (qy >= y0) & (qy < y1)
+            base, tint = _bilinear(T, qx[roof] + margin, qy[roof] + margin), _bilinear(T2, qx[roof] + margin, qy[roof] + margin)
+            for ch, g in enumerate((0.10, -0.06, 0.08)):
+                frames[k, ..., ch][roof] = np.clip(np.rint(base + g * (tint - 127.5)), 0, 255).astype(np.uint8)
+            Hrk = Hr @ Hrk
         Hk = H @ Hk
+    if relief is not None:
+        return frames, dict(H=H, H_relief=Hr, relief=dict(rect=(x0, y0, x1, y1), height=hr), scaling=scaling, cx=cx, cy=cy, v=np.asarray(v, np.float64),
+                            omega=np.asarray(omega, np.float64), d=float(d), n=np.asarray(n, np.float64))
     return frames, dict(H=H, scaling=scaling, cx=cx, cy=cy, v=np.asarray(v, np.float64), omega=np.asarray(omega, np.float64),
                         d=float(d), n=np.asarray(n, np.float64))
 

@@ -213,6 +213,34 @@ def keyframe_rotation_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None,
     return _keyframe_state(out, count), rec[0], rrec[0]
 
 
+def keyframe_map_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None, depth=None, status=None, solved=True, step=0, new_count=None,
+                      max_total=None, keyframe=None, keyframe_map=None):
+    """keyframe_step with the key translation solved against the per-track depths frozen at the keyframe (ofk.h:
+    ofk_keyframe_map_step).  keyframe_step's arguments; state may also carry key_rho, key_var [n] and mstate [2]; depth: the
+    dict(rho, var, nobs) [n] track_depth_step returned for the previous step (None: no depth state); keyframe / keyframe_map: None
+    (the defaults), a dict of ofk.keyframe_setting's / ofk.keyframe_map_setting's keywords, or the structures.
+    Returns (state with key_rho, key_var, mstate; rec [32]; mrec [32]): mrec[0] is the map's flag (ofk.KEYMAP_*)."""
+    kf = keyframe if isinstance(keyframe, ofk.Keyframe) else ofk.keyframe_setting(**dict(keyframe or {}))
+    km = keyframe_map if isinstance(keyframe_map, ofk.KeyframeMap) else ofk.keyframe_map_setting(**dict(keyframe_map or {}))
+    args, kw, count = _keyframe_stage("keyframe_map_step", next_pts, sensors, v_uav, state, status, solved, step, new_count, max_total)
+    n, S = int(args[2][0]), args[0].shape[1]
+
+    def rows(a, dtype):                                          # [1, S]: the n rows, zeros behind them
+        out = np.zeros((1, S), dtype)
+        if a is not None:
+            out[0, :n] = np.asarray(a, dtype).reshape(n)
+        return out
+    state = state or {}
+    st = dict(args[-1], key_rho=rows(state.get("key_rho"), np.float64), key_var=rows(state.get("key_var"), np.float64),
+              mstate=None if state.get("mstate") is None else np.asarray(state["mstate"], np.int32).reshape(1, 2))
+    st.pop("rstate", None)
+    dp = None if depth is None else dict(rho=rows(depth["rho"], np.float64), var=rows(depth["var"], np.float64), nobs=rows(depth["nobs"], np.int32))
+    out, rec, mrec = ofk.default_context().keyframe_map_step(*args[:-1], st, depth=dp, **kw, keyframe=kf, keyframe_map=km)
+    res = _keyframe_state(out, count)
+    res.update(key_rho=out["key_rho"][0, :count].copy(), key_var=out["key_var"][0, :count].copy(), mstate=out["mstate"][0].copy())
+    return res, rec[0], mrec[0]
+
+
 def pos_filter_step(v_uav, key_rec, R_world=None, state=None, solved=True, du=None, fix=None, fix_sigma=None, **settings):
     """One step of a stream's position filter without images (ofk.h: ofk_pos_filter_step): predict, the velocity, displacement and fix
     updates, the clone at a re-key.  v_uav [3], solved: the step record's fields 8-10 and its solved flag; key_rec [32]: the
@@ -362,6 +390,7 @@ class optical_fusion:
     _track_depth = {}                                            # PipelineConfig's track_depth field; empty: no depth per track
     _keyframe_rotation = {}                                      # PipelineConfig's keyframe_rotation field; empty: R_acc is taken as exact
     _pos_filter = {}                                             # PipelineConfig's pos_filter field; empty: no position filter
+    _keyframe_map = {}                                           # PipelineConfig's keyframe_map field; empty: the key solve is the plane's
     _fix = None                                                  # (position, sigma) of call_fix, handed to the filter with the next frame
     _keyframe = {}                                               # PipelineConfig's keyframe field; empty: no position against a keyframe
     _track_template = {}                                         # PipelineConfig's track_template field; empty: no template per track
@@ -522,7 +551,8 @@ class optical_fusion:
                                  use_feasibility=True, feas_T=float(self.T), **self._robust, **self._track_gate, **self._corner_grid,
                                  **self._cov, **self._joint, **self._plane, **self._epipolar, **self._zones, **self._camera, **self._rolling_shutter,
                                  **self._finite_motion, **self._gyro_bias, **self._lk_light, **self._track_table, **self._track_depth,
-                                 **self._track_template, **self._keyframe, **self._keyframe_rotation, **self._pos_filter)
+                                 **self._track_template, **self._keyframe, **self._keyframe_rotation, **self._pos_filter,
+                                 **self._keyframe_map)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -573,6 +603,9 @@ class optical_fusion:
             if getattr(self, "_" + name):
                 d = read(fs)
                 setattr(self, "last_" + name, {k: d[k][0] for k in keys})
+        if self._keyframe_map:
+            km = fs.key_map()
+            self.last_key_map = {k: v[0] for k, v in km.items()}
         if self._pos_filter:
             fp = fs.fused_position()
             self.last_position = {k: ({n: a[0] for n, a in v.items()} if isinstance(v, dict) else v[0]) for k, v in fp.items()}
@@ -652,7 +685,8 @@ class optical_fusion:
 
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
                  rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None, gyro_bias=None, lk_light=None,
-                 track_table=None, track_depth=None, track_template=None, keyframe=None, keyframe_rotation=None, pos_filter=None):
+                 track_table=None, track_depth=None, track_template=None, keyframe=None, keyframe_rotation=None, pos_filter=None,
+                 keyframe_map=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -719,7 +753,11 @@ class optical_fusion:
         pos_filter: None (no position filter), True, an ofk.PosFilter or a dict of ofk.pos_filter_setting's keywords, e.g.
         dict(sigma_v=2e-3, nis_max=16): the stream then fuses the keyframe's displacement, the step's velocity and the fixes of
         call_fix in a filter with a cloned state (ofk.h: ofk_set_pos_filter); it switches the keyframe and the track table on when
-        they are None.  self.last_position is FlowStream.fused_position()'s dictionary for the one stream."""
+        they are None.  self.last_position is FlowStream.fused_position()'s dictionary for the one stream.
+        keyframe_map: None (the key solve is the plane's), True, an ofk.KeyframeMap or a dict of ofk.keyframe_map_setting's keywords,
+        e.g. dict(rel_max=0.05): the key translation is then solved against the per-track depths frozen at the keyframe (ofk.h:
+        ofk_set_keyframe_map); it switches the keyframe, the depths and the track table on when they are None.  self.last_key_map is
+        FlowStream.key_map()'s dictionary for the one stream."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -803,13 +841,20 @@ class optical_fusion:
             self._lk_light = {}
         if pos_filter is not None and pos_filter is not False and keyframe is None:
             keyframe = True                                      # the filter fuses the keyframe's displacement
+        if keyframe_map is not None and keyframe_map is not False:   # the map is the depths', frozen at the keyframe
+            keyframe = True if keyframe is None else keyframe
+            track_depth = True if track_depth is None else track_depth
         given = dict(track_table=track_table, track_depth=track_depth, track_template=track_template, keyframe=keyframe,
-                     keyframe_rotation=keyframe_rotation, pos_filter=pos_filter)
-        for name, value in given.items():                        # the rotation's and the filter's checks read the keyframe, set in front of them
-            setattr(self, "_" + name, _struct_field(name, value, **(self._keyframe if name in ("keyframe_rotation", "pos_filter") else {})))
+                     keyframe_rotation=keyframe_rotation, pos_filter=pos_filter, keyframe_map=keyframe_map)
+        for name, value in given.items():                        # the rotation's, the filter's and the map's checks read the keyframe, set in front of them
+            beside = self._keyframe if name in ("keyframe_rotation", "pos_filter") else {}
+            if name == "keyframe_map":
+                beside = dict(**self._keyframe, **self._track_depth, **self._keyframe_rotation)
+            setattr(self, "_" + name, _struct_field(name, value, **beside))
         if (self._track_depth or self._track_template or self._keyframe) and not self._track_table:
             self._track_table = dict(track_table=True)           # the three are kept per row of the table
         self.last_track_depth = self.last_track_template = self.last_keyframe = self.last_keyframe_rotation = self.last_position = None
+        self.last_key_map = None
         self._fix = None
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False

@@ -632,6 +632,88 @@ int ofk_keyframe_rotation_step(ofk_ctx *ctx, const ofk_keyframe *k, const ofk_ke
                                const int *step, float *key_xy, uint8_t *member, double *state, int *istate, const int *new_counts,
                                int max_total, int batch, int stride, double *rec, double *rstate, double *rrec);
 
+/* Keyframe map: the key solve from per-track depths, not the ground plane.  Rule 2 of ofk_set_keyframe gives every member the depth of
+ * one plane, rho_c = (n.p_c)/d; over a roof, a canopy or a ramp that is wrong, and the range reading d enters every key solve.  With
+ * this setting on beside ofk_set_keyframe and ofk_set_track_depth (both must be on) the depth filter's rho and var are frozen per
+ * track row at the keyframe, and the key translation is solved against them: a translation-only PnP against fixed landmarks that reads
+ * neither n nor d.  Off by default; with it off every step allocates, launches and returns what it always did.  k_keyframe_step_map is
+ * launched in k_keyframe_step's place on exactly its steps; k_track_depth_step is not touched and still runs behind it.  Streams only.
+ * The relation.  For a member, k its scaled key pixel, (X, Y, Z) = R_acc (k, 1), rho_K its inverse z-depth at the keyframe, p its
+ * scaled ideal next point: P_c = (X, Y, Z) / rho_K + T and p = P_c,xy / P_c,z give exactly (rho_K / Z) (T_xy - T_z p) = p - (a, b),
+ * a = X / Z, b = Y / Z: a row of the solve's own form with x^ = p, u^ = p - (a, b), sA = rho_K / Z, linear in T, exact at any distance,
+ * its residual r = u^ - sA (T_xy - T_z x^) a pixel difference in the current frame.  On a plane it is rule 2's row times Z_c.
+ * Where the key depth comes from.  A re-key at table step k keys on the step's ideal next points and sets key_step = k + 1;
+ * k_track_depth_step, behind it in the same step, predicts every depth to that same frame and compacts by the same keep rule.  At the
+ * NEXT launch the depth state therefore holds rho, var, nobs at the keyframe for exactly the member rows, in their order: rule M1
+ * captures them then.
+ * State per track row, in the table's row order: key_rho, key_var (f64; 0, 0 = no map depth).  Per stream: mstate [2] i32 =
+ * (captured_for: the key_step the rows were captured for, map_rows: the mature rows captured; 0 behind a re-key) and a record of
+ * OFK_KEYMAP_DOUBLES.  Arithmetic, sums over rows, Jacobi, rank rule, compaction: as ofk_set_keyframe states them.  A row of the depth
+ * state is MATURE when nobs >= min_obs, rho > 0 and var <= (rel_max rho)(rel_max rho), each false for NaN (this setting's min_obs and
+ * rel_max, not the depth setting's); a stream without depth state has no mature row.  In order, around rules 1-5:
+ *   M1. Capture, in front of rule 2, when members_at_key != 0 and captured_for != key_step: every row i < n with member != 0 gets
+ *       (key_rho, key_var) = (rho, var) where it is mature, else (0, 0); map_rows = the mature ones, captured_for = key_step.
+ *   M2. A LIVE MAP ROW has status != 0, member != 0 and key_rho > 0 (false for NaN).  use_map = map_rows >= min_rows and live map rows
+ *       >= min_rows (this setting's min_rows).  Rule 2's first walk and solve always run as they stand (they give `live`); with use_map
+ *       false all of rule 2 runs, bit for bit: flag OFK_KEYMAP_NONE where map_rows < min_rows, else OFK_KEYMAP_FEW.
+ *   M3. Map solve, over the live map rows.  k, p, (X, Y, Z) as rule 2; the row is left out unless Z >= OFK_KEY_MIN_DEPTH.  a = X / Z,
+ *       b = Y / Z, x^ = p, u^ = (px - a, py - b), sA = key_rho / Z.  sf = sigma_flow scaling.  weights 1: w = sf^2 / (sf^2 +
+ *       ((u0 u0 + u1 u1) key_var) / (key_rho key_rho)), the parallax times the relative depth error beside the pixel noise; weights 0:
+ *       w = 1.  The row enters the sums as acc_point(x^, (u^, 0), sA, 1) with sa2 = sA sA w and sab = sA 1 w (acc_point_w's order) and
+ *       counts as one row.  T = M^+ g; the solve stands with at least min_rows rows (this setting's), rank 3 and finite sums.  gate > 0:
+ *       a second solve over the rows with w r.r <= (gate scaling)^2 under the first T; it replaces the first with at least the
+ *       keyframe's min_rows rows, rank 3 and finite sums.  Over the rows of the solve that stands and under its T: rms = sqrt(sum w r.r
+ *       / rows) / scaling, spread = sqrt(sum w r.r / sum w) / scaling.  C_T = sf^2 M^-1 of that solve as rule 2 writes it.  Where the
+ *       map solve stands (OFK_KEYMAP_USED) flag, T, rows 4 / 5, rms, gated and C_T of the keyframe's record are its own, whatever the
+ *       plain first solve gave, and the rest of rule 2 does not run.  Where it does not (OFK_KEYMAP_FELL_BACK) rule 2 runs on untouched.
+ *       Rule 3 and the keyframe's record keep their layout; a D that is not finite refuses the step as rule 3 says: the keyframe's
+ *       flag is then 1 and its T, rms and C_T 0, while the map record stays as M3 left it - OFK_KEYMAP_USED and slots 3-6 speak of
+ *       M3 alone, the keyframe's flag says whether the step stood.
+ *   M4. Re-key reason 6 (OFK_KEY_RE_MAP, bit 32) beside rule 4's: ready_share > 0, map_rows < min_rows, and among the live rows
+ *       (status != 0, member != 0) `ready` rows of the depth state as it stands are mature with ready >= min_rows and ready >=
+ *       ready_share live (in f64).  Without it a keyframe born before any depth matured would stay a plane keyframe for life.
+ *   M5. Compaction: key_rho and key_var move with key_xy; appended rows and every row of a re-key get (0, 0), and M1 fills them at the
+ *       next launch.
+ * Map record, OFK_KEYMAP_DOUBLES: 0 flag, 1 map_rows behind M1, 2 live map rows, 3 / 4 rows of the first / the gated map solve, 5 sum of
+ * weights, 6 spread (3-6: 0 unless use_map; 4-6: 0 unless the map solve stands), 7-9 the plain first solve's T where use_map and
+ * that solve stood (else 0), 10 rows captured this step, 11 captured_for behind M1, the rest 0.
+ * k_keymap_clear runs behind k_keyframe_begin (and where a stream steps with this setting on without map state: switched on in
+ * mid-stream), k_keyframe_replace (the streams with a budget; the record stays) and k_keyframe_reset: rows (0, 0), map_rows 0,
+ * captured_for = the keyframe's key_step - the depth state of that moment is not the keyframe's, so nothing is captured before the
+ * next re-key, which M4 brings about - and the record zero with flag OFK_KEYMAP_NONE.  The buffers (16 bytes per track, the
+ * per-stream state) are allocated by the first step with the setting on.
+ * Not in it: the joint rotation over map rows (a stream step with ofk_set_keyframe_rotation on beside this setting is refused);
+ * refining key_rho from later frames; the map's common error in the position filter's `share`; pairs.  Beside ofk_set_finite_motion
+ * the depths are taken at the solve's rewritten points and the key solve at the ideal points in front of the rewrite, as each does
+ * without the other; the combination runs (README, "Keyframe map", says what it was measured at).
+ * ofk_set_keyframe_map: NULL or mode OFK_KEYMAP_OFF switches it off.  OFK_E_INVALID, the setting staying as it was: an unknown mode,
+ * min_obs < 1, rel_max <= 0, min_rows < 3, ready_share outside [0, 1], weights not 0 or 1, a value that is not finite.  Defaults behind
+ * "off": 3, 0.02, 8, 0.5, 1.  OFK_E_INVALID before any launch from a stream step with the setting on: ofk_set_keyframe or
+ * ofk_set_track_depth off; ofk_set_keyframe_rotation on.
+ * ofk_keyframe_map_download, the streams of the latest step with the setting on, the first min(stride, max_pts) rows of each (every
+ * output may be NULL): key_rho, key_var [batch][stride] f64, rec [batch][OFK_KEYMAP_DOUBLES].
+ * ofk_keyframe_reset also clears the stream's map.
+ * ofk_keyframe_map_step: ofk_keyframe_step's arguments and meaning (it touches no resident state), plus the map setting m, the depth
+ * state rho, var [batch][stride] f64 and nobs [batch][stride] i32 (read only; all NULL: no depth state), the map state key_rho, key_var
+ * [batch][stride] f64 and mstate [batch][2] i32 in and out in place, and mrec [batch][OFK_KEYMAP_DOUBLES] out (may be NULL). */
+#define OFK_KEYMAP_OFF        0
+#define OFK_KEYMAP_ON         1
+#define OFK_KEYMAP_DOUBLES    32
+#define OFK_KEYMAP_USED       0
+#define OFK_KEYMAP_NONE       1
+#define OFK_KEYMAP_FEW        2
+#define OFK_KEYMAP_FELL_BACK  3
+#define OFK_KEY_RE_MAP        6
+typedef struct ofk_keyframe_map { int mode; int min_obs; double rel_max; int min_rows; double ready_share; int weights; } ofk_keyframe_map;
+int ofk_set_keyframe_map(ofk_ctx *ctx, const ofk_keyframe_map *m);
+int ofk_get_keyframe_map(const ofk_ctx *ctx, ofk_keyframe_map *m);
+int ofk_keyframe_map_download(ofk_ctx *ctx, double *key_rho, double *key_var, int stride, double *rec);
+int ofk_keyframe_map_step(ofk_ctx *ctx, const ofk_keyframe *k, const ofk_keyframe_map *m, const float *next_pts, const uint8_t *status,
+                          const int *counts, const double *sensors, const double *v_uav, const int *solved, const int *step, float *key_xy,
+                          uint8_t *member, double *state, int *istate, const int *new_counts, int max_total, int batch, int stride,
+                          double *rec, const double *rho, const double *var, const int *nobs, double *key_rho, double *key_var, int *mstate,
+                          double *mrec);
+
 /* Position filter per stream: keyframe, velocity and position fixes fused.  The keyframe's D is drift-free while the keyframe lives, but
  * its pos re-anchors at every re-key, so its error is a random walk over the re-keys; a fix (GPS, a marker) has no way into a stream;
  * and the key pixels' noise is common to all steps of one keyframe, so a filter that took D every step as an independent position
