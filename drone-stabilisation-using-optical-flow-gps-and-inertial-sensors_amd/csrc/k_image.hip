@@ -8,6 +8,7 @@
 //             k_pyr_down (other widths): 64x16 output tile / 256-thread block; source tile (136x35) staged into LDS
 //             with dword loads, separable 5-tap pass through a u16 LDS intermediate.
 //   scharr  : 64x16 output tile, 68x18 source tile in LDS, int16x2 (4 B/px) coalesced stores.
+//   warp    : k_warp.inc (included at the end): perspective warp, 4 pixels per lane, byte gathers, dword stores.
 #include "ofk_internal.h"
 
 __device__ __forceinline__ int reflect101(int i, int n)
@@ -585,3 +586,6 @@ void ofk_launch_scharr(hipStream_t s, const uint8_t *src, size_t src_stride, int
     dim3 grid((w + SC_TW - 1) / SC_TW, (h + SC_TH - 1) / SC_TH, batch);
     hipLaunchKernelGGL(k_scharr, grid, dim3(256), 0, s, src, src_stride, h, w, dxdy, dst_stride_elems);
 }
+
+// ------------------------------------------------------------------------------------------------ perspective warp
+#include "k_warp.inc"

@@ -62,6 +62,24 @@ __global__ __launch_bounds__(256) void k_keyframe_reset(ofk_kf_rows t, int b, in
 // what rule 2 needs of one stream, the same in every thread
 struct kf_frame { double R[9], n0, n1, n2, d, cx, cy, sc; };
 
+// Rule 1: R = exp([omega]x) R0, entry by entry as ofk.h writes it (k_stab_pose forms the same product from a copy of the state)
+__device__ __forceinline__ void kf_rotate(double o0, double o1, double o2, const double *R0, double *R)
+{
+    const double th2 = (o0 * o0 + o1 * o1) + o2 * o2;
+    double A = 1.0, B = 0.5;
+    if (!(th2 < 1e-16)) { const double th = sqrt(th2); A = sin(th) / th; B = (1.0 - cos(th)) / th2; }
+    const double om[3] = {o0, o1, o2};
+    const double K[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};
+    double E[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double k2 = om[i] * om[j] - (i == j ? th2 : 0.0);
+            E[3 * i + j] = ((i == j ? 1.0 : 0.0) + A * K[3 * i + j]) + B * k2;
+        }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) R[3 * i + j] = (E[3 * i] * R0[j] + E[3 * i + 1] * R0[3 + j]) + E[3 * i + 2] * R0[6 + j];
+}
+
 // Rule 2's terms of row r; false: the row is left out
 __device__ __forceinline__ bool kf_row(const ofk_kf_rows &t, const float *__restrict__ next, size_t r, const kf_frame &f, double &a, double &b,
                                        double &u0, double &u1, double &sA)

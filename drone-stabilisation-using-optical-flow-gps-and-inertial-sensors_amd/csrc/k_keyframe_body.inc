@@ -23,21 +23,7 @@
     f.d = sn[0]; f.sc = sn[19]; f.cx = sn[20]; f.cy = sn[21];
 
     // 1. rotate
-    {
-        const double th2 = (o0 * o0 + o1 * o1) + o2 * o2;
-        double A = 1.0, B = 0.5;
-        if (!(th2 < 1e-16)) { const double th = sqrt(th2); A = sin(th) / th; B = (1.0 - cos(th)) / th2; }
-        const double om[3] = {o0, o1, o2};
-        const double K[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};
-        double E[9];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                const double k2 = om[i] * om[j] - (i == j ? th2 : 0.0);
-                E[3 * i + j] = ((i == j ? 1.0 : 0.0) + A * K[3 * i + j]) + B * k2;
-            }
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) f.R[3 * i + j] = (E[3 * i] * R0[j] + E[3 * i + 1] * R0[3 + j]) + E[3 * i + 2] * R0[6 + j];
-    }
+    kf_rotate(o0, o1, o2, R0, f.R);
 #if KF_ROT
     // 1'. the source's rotation and the prior of this step (ofk_set_keyframe_rotation)
     __shared__ double s_jp[4][KR_SUMS];

@@ -206,3 +206,4 @@ void ofk_launch_track_gate(hipStream_t s, const float *prev_pts, const float *ba
 #include "k_keyframe_rot.inc"
 #include "k_keyframe_map.inc"
 #include "k_pos_filter.inc"
+#include "k_stabilise.inc"

@@ -166,6 +166,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->krot = ofk_keyframe_rotation{OFK_KEYROT_OFF, OFK_KEYROT_GYRO, {1, 1, 1}, 0.0, 1e-4, 1e-3, 2, 0.1};
     c->kmap = ofk_keyframe_map{OFK_KEYMAP_OFF, 3, 0.02, 8, 0.5, 1};
     c->posf = ofk_pos_filter{OFK_POSF_OFF, 1.0, 1e-3, 0.0, 1.0, 0.5, 0.0, 1e-3, 0.0, 0.0, 1.0, 0.0, 0.0};
+    c->stab = ofk_stabilise{OFK_STAB_OFF, OFK_BORDER_CONSTANT, 0, 0.5, 1};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -224,6 +225,7 @@ extern "C" int ofk_destroy(ofk_ctx *c)
                     c->zone_tab, c->pts_prev_u};
     for (void *p : ptrs) if (p) hipFree(p);
     track_free(c);
+    if (c->sb_frames) hipFree(c->sb_frames);
     if (c->hstage) hipHostFree(c->hstage);
     ofk_jpeg_release(c);
     if (c->ev) { for (int i = 0; i < c->ev_cap; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]); free(c->ev); }
@@ -432,6 +434,27 @@ extern "C" int ofk_scharr_s16(ofk_ctx *c, const uint8_t *gray, int batch, int h,
     ofk_launch_scharr(c->stream, c->pyr[0], c->pyr_stride, h, w, c->deriv, c->img_stride, batch);
     TRY(check_launch(c, "k_scharr"));
     return d2h(c, dxdy, c->deriv, c->img_stride * 4, px * 4, batch);
+}
+
+extern "C" int ofk_warp_perspective(ofk_ctx *c, const uint8_t *src, int sh, int sw, int channels, const double *M, uint8_t *dst, int dh,
+                                    int dw, int border, int border_value, int batch, int *covered)
+{
+    TRY(check_geom(c, batch, sh, sw, "ofk_warp_perspective (source)"));
+    TRY(check_geom(c, batch, dh, dw, "ofk_warp_perspective (destination)"));
+    if (!src || !M || !dst) return ofk_fail(c, OFK_E_INVALID, "ofk_warp_perspective: NULL buffer");
+    if (channels != 1 && channels != 3) return ofk_fail(c, OFK_E_INVALID, "ofk_warp_perspective: %d channels (1 or 3)", channels);
+    if (border != OFK_BORDER_CONSTANT && border != OFK_BORDER_REPLICATE) return ofk_fail(c, OFK_E_INVALID, "ofk_warp_perspective: unknown border %d", border);
+    if (border_value < 0 || border_value > 255) return ofk_fail(c, OFK_E_INVALID, "ofk_warp_perspective: border_value %d outside 0..255", border_value);
+    const size_t m_bytes = up((size_t)batch * 9 * sizeof(double), 256);
+    TRY(ofk_need_scratch(c, m_bytes + (size_t)batch * sizeof(int)));
+    double *d_M = (double *)c->scratch;
+    int *d_cov = covered ? (int *)((char *)c->scratch + m_bytes) : nullptr;
+    TRY(h2d(c, c->bgr[0], c->bgr_stride, src, (size_t)sh * sw * channels, batch));
+    OFK_HIP(c, hipMemcpyAsync(d_M, M, (size_t)batch * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    ofk_launch_warp(c->stream, c->bgr[0], c->bgr_stride, sh, sw, channels, d_M, c->bgr[1], c->bgr_stride, dh, dw, border, border_value, d_cov, batch);
+    TRY(check_launch(c, "k_warp_u8"));
+    if (covered) OFK_HIP(c, hipMemcpyAsync(covered, d_cov, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    return d2h(c, dst, c->bgr[1], c->bgr_stride, (size_t)dh * dw * channels, batch);
 }
 
 static int check_block(ofk_ctx *c, int h, int w, int block)
@@ -2476,8 +2499,10 @@ static const track_array KM_ARRAYS[] = {TRACK_ARRAY(kmr.key_rho, 8, 0), TRACK_AR
     TRACK_ARRAY(kmr.mrec, 0, OFK_KEYMAP_DOUBLES * 8)};
 static const track_array PF_ARRAYS[] = {TRACK_ARRAY(pf_x, 0, OFK_POSF_STATES * 8), TRACK_ARRAY(pf_P, 0, OFK_POSF_STATES * OFK_POSF_STATES * 8),
     TRACK_ARRAY(pf_rec, 0, OFK_POSF_DOUBLES * 8), TRACK_ARRAY(pf_in, 0, OFK_POSF_INPUT * 8), TRACK_ARRAY(pf_ist, 0, OFK_POSF_INTS * 4)};
+static const track_array SB_ARRAYS[] = {TRACK_ARRAY(sb_Bv, 0, 72), TRACK_ARRAY(sb_rec, 0, OFK_STAB_DOUBLES * 8), TRACK_ARRAY(sb_M, 0, 72),
+    TRACK_ARRAY(sb_st, 0, OFK_KEY_STATE * 8), TRACK_ARRAY(sb_ist, 0, OFK_STAB_INTS * 4), TRACK_ARRAY(sb_cov, 0, 4)};
 
-enum { TS_TABLE, TS_DEPTH, TS_TEMPLATE, TS_KEY, TS_KEYROT, TS_KEYMAP, TS_POSF };
+enum { TS_TABLE, TS_DEPTH, TS_TEMPLATE, TS_KEY, TS_KEYROT, TS_KEYMAP, TS_POSF, TS_STAB };
 struct track_state {
     const char *set, *download, *began;                          // the setter's and the download's names, "run" / "stepped": for messages
     bool (*on)(const ofk_ctx *);
@@ -2530,6 +2555,11 @@ static const track_state TRACK[] = {
          return OFK_OK;
      },
      nullptr, TS_KEY, "it fuses the keyframe's displacement", nullptr},
+    {"ofk_set_stabilise", "ofk_stab_download", "stepped", [](const ofk_ctx *c) { return c->stab.mode != OFK_STAB_OFF; },
+     &ofk_ctx::sb_batch, &ofk_ctx::sb_live, TRACK_LIST(SB_ARRAYS),     // per stream, not per track: the view is the identity where the keyframe begins afresh
+     [](ofk_ctx *c, int B) -> int { ofk_launch_stab_clear(c->stream, c->sb_Bv, c->sb_ist, c->sb_rec, nullptr, 0, B); c->sb_h = c->sb_w = 0; return OFK_OK; },
+     [](ofk_ctx *c, int B) { ofk_launch_stab_clear(c->stream, c->sb_Bv, c->sb_ist, c->sb_rec, c->limit, 0, B); },
+     TS_KEY, "it warps into the keyframe's view", nullptr},
 };
 
 static void *&track_slot(ofk_ctx *c, const track_array &a) { return *(void **)((char *)c + a.at); }
@@ -2562,7 +2592,7 @@ static int track_begin(ofk_ctx *c, const track_state &s, int B)
 // The steps' own refusals with a state on (ofk.h), in their precedence; fu: a fused step's.
 static int track_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const char *who)
 {
-    static const int order[] = {TS_DEPTH, TS_TEMPLATE, TS_KEYROT, TS_KEYMAP, TS_POSF, TS_KEY};
+    static const int order[] = {TS_DEPTH, TS_TEMPLATE, TS_KEYROT, TS_KEYMAP, TS_POSF, TS_STAB, TS_KEY};
     for (int k : order) {
         const track_state &s = TRACK[k];
         if (!s.on(c)) continue;
@@ -2571,6 +2601,9 @@ static int track_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const
             if (!TRACK[TS_DEPTH].on(c)) return ofk_fail(c, OFK_E_INVALID, "%s: %s is on without %s: the map is the depth state at the keyframe", who, s.set, TRACK[TS_DEPTH].set);
             if (TRACK[TS_KEYROT].on(c)) return ofk_fail(c, OFK_E_INVALID, "%s: %s is on beside %s: the joint solve over map rows is not built", who, s.set, TRACK[TS_KEYROT].set);
         }
+        if (k == TS_STAB && (camera_on(c) || rs_on(c)))          // the homography holds between ideal global-shutter images
+            return ofk_fail(c, OFK_E_INVALID, "%s: %s is on beside %s: a raw frame needs a remap in front of the warp, which is not built", who, s.set,
+                            camera_on(c) ? "ofk_set_camera" : "ofk_set_rolling_shutter");
         if (s.model && (variant == OFK_SOLVE_OFMODULE || (fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY))))
             return refuse_not_sensor_model(c, who, NO_OFMODULE | NO_ROTATIONAL | NO_LEGACY, s.model, s.set);
     }
@@ -3217,6 +3250,98 @@ extern "C" int ofk_pos_filter_step(ofk_ctx *c, const ofk_pos_filter *f, const do
     return fetch_back(c, who, back, 4);
 }
 
+// ------------------------------------------------------------------------------------------------ stabilised view
+static int check_stab(ofk_ctx *c, const ofk_stabilise *s, const char *who)
+{
+    if (s->mode != OFK_STAB_OFF && s->mode != OFK_STAB_ROTATION && s->mode != OFK_STAB_PLANE)
+        return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is none of OFK_STAB_OFF, OFK_STAB_ROTATION, OFK_STAB_PLANE", who, s->mode);
+    if (s->mode == OFK_STAB_OFF) return OFK_OK;
+    if (s->border != OFK_BORDER_CONSTANT && s->border != OFK_BORDER_REPLICATE) return ofk_fail(c, OFK_E_INVALID, "%s: unknown border %d", who, s->border);
+    if (s->border_value < 0 || s->border_value > 255) return ofk_fail(c, OFK_E_INVALID, "%s: border_value %d outside 0..255", who, s->border_value);
+    if (!std::isfinite(s->min_cover) || s->min_cover < 0.0 || !(s->min_cover < 1.0)) return ofk_fail(c, OFK_E_INVALID, "%s: min_cover = %g outside [0, 1)", who, s->min_cover);
+    if (s->chain != 0 && s->chain != 1) return ofk_fail(c, OFK_E_INVALID, "%s: chain %d is neither 0 nor 1", who, s->chain);
+    return OFK_OK;
+}
+
+extern "C" int ofk_set_stabilise(ofk_ctx *c, const ofk_stabilise *s)
+{
+    return setting_set(c, &ofk_ctx::stab, s && s->mode == OFK_STAB_OFF ? nullptr : s, [](ofk_stabilise &v) { v.mode = OFK_STAB_OFF; },
+                       [c](const ofk_stabilise *v) { return check_stab(c, v, "ofk_set_stabilise"); });
+}
+extern "C" int ofk_get_stabilise(const ofk_ctx *c, ofk_stabilise *s) { return setting_get(c, &ofk_ctx::stab, s); }
+
+// the frames' buffer, [max_batch] images of the context's largest frame, 256-B aligned each
+static int stab_frames_alloc(ofk_ctx *c)
+{
+    if (c->sb_frames) return OFK_OK;
+    c->sb_stride = up(c->P, 256);
+    OFK_HIP(c, hipMalloc((void **)&c->sb_frames, (size_t)c->max_batch * c->sb_stride));
+    return OFK_OK;
+}
+
+extern "C" int ofk_stab_download(ofk_ctx *c, uint8_t *frames, double *rec, int *covered)
+{
+    if (!c) return OFK_E_INVALID;
+    TRY(track_download_begin(c, TRACK[TS_STAB], false, 0));
+    if (frames && !(c->sb_frames && c->sb_h > 0)) return ofk_fail(c, OFK_E_INVALID, "ofk_stab_download: no step has warped a frame yet");
+    if (frames)
+        OFK_HIP(c, hipMemcpy2DAsync(frames, (size_t)c->sb_h * c->sb_w, c->sb_frames, c->sb_stride, (size_t)c->sb_h * c->sb_w, c->sb_batch, hipMemcpyDeviceToHost, c->stream));
+    const download_row rows[] = {{rec, c->sb_rec, OFK_STAB_DOUBLES * 8, OFK_STAB_DOUBLES * 8}, {covered, c->sb_cov, 4, 4}};
+    return rows_download(c, c->sb_batch, 0, rows, 2);
+}
+
+extern "C" int ofk_stab_frames(ofk_ctx *c, uint8_t **device_ptr, size_t *image_stride)
+{
+    if (!c) return OFK_E_INVALID;
+    if (!device_ptr || !image_stride) return ofk_fail(c, OFK_E_INVALID, "ofk_stab_frames: NULL argument");
+    TRY(track_download_begin(c, TRACK[TS_STAB], false, 0));
+    if (!(c->sb_frames && c->sb_h > 0)) return ofk_fail(c, OFK_E_INVALID, "ofk_stab_frames: no step has warped a frame yet");
+    *device_ptr = c->sb_frames; *image_stride = c->sb_stride;
+    return OFK_OK;
+}
+
+extern "C" int ofk_stab_reset(ofk_ctx *c, int b)
+{
+    const char *who = "ofk_stab_reset";
+    if (!c) return OFK_E_INVALID;
+    if (c->stream_batch < 1 || b < 0 || b >= c->stream_batch) return ofk_fail(c, OFK_E_INVALID, "%s: stream %d is none of the %d active streams", who, b, c->stream_batch);
+    TRY(enter(c));
+    TRY(track_begin(c, TRACK[TS_STAB], c->stream_batch));
+    ofk_launch_stab_clear(c->stream, c->sb_Bv, c->sb_ist, c->sb_rec, nullptr, b, 1);
+    TRY(check_launch(c, who));
+    OFK_HIP(c, hipStreamSynchronize(c->stream));
+    return OFK_OK;
+}
+
+// rules 1-4 on host buffers: device scratch only
+extern "C" int ofk_stab_pose(ofk_ctx *c, const ofk_stabilise *s, const double *R, const double *key_rec, const double *sensors, const double *normal,
+                             const int *prev_covered, int h, int w, double *Bv, int *ints, int batch, double *rec)
+{
+    const char *who = "ofk_stab_pose";
+    if (!c) return OFK_E_INVALID;
+    if (!s || !R || !key_rec || !sensors || !Bv || !ints) return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
+    if (batch < 1 || h < 1 || w < 1) return ofk_fail(c, OFK_E_INVALID, "%s: batch %d, frame %d x %d", who, batch, w, h);
+    if (s->mode == OFK_STAB_OFF) return ofk_fail(c, OFK_E_INVALID, "%s: the setting is off", who);
+    TRY(check_stab(c, s, who));
+    const size_t B = (size_t)batch;
+    Bump bp;
+    TRY(est_begin(c, B * ((9 + OFK_KEY_DOUBLES + OFK_SENSOR_DOUBLES + 3 + 9 + OFK_STAB_DOUBLES + 9) * 8 + (1 + OFK_STAB_INTS) * 4) + 9 * 256, bp));
+    ofk_stab_in in = {};
+    in.R = bp.put(R, B * 72); in.R_stride = 9;
+    in.key_rec = bp.put(key_rec, B * OFK_KEY_DOUBLES * 8); in.sensors = bp.put(sensors, B * OFK_SENSOR_DOUBLES * 8);
+    in.normal = normal ? bp.put(normal, B * 24) : in.sensors + 1; in.normal_stride = normal ? 3 : OFK_SENSOR_DOUBLES;
+    int *d_cov = prev_covered ? (int *)bp.put(prev_covered, B * 4) : (int *)bp.take(B * 4);
+    in.cov = d_cov;
+    in.Bv = bp.put(Bv, B * 72); in.ist = (int *)bp.put(ints, B * OFK_STAB_INTS * 4);
+    in.rec = bp.take(B * OFK_STAB_DOUBLES * 8); in.M = bp.take(B * 72);
+    if (!prev_covered && bp.rc == OFK_OK && hipMemsetAsync(d_cov, 0, B * 4, c->stream) != hipSuccess) bp.rc = OFK_E_HIP;
+    if (bp.rc != OFK_OK || hipStreamSynchronize(c->stream) != hipSuccess) return ofk_fail(c, OFK_E_HIP, "%s: upload failed", who);
+    ofk_launch_stab_pose(c->stream, in, s, h, w, batch);
+    TRY(check_launch(c, "k_stab_pose"));
+    const back_row back[] = {{Bv, in.Bv, B * 72}, {ints, in.ist, B * OFK_STAB_INTS * 4}, {rec, in.rec, B * OFK_STAB_DOUBLES * 8}};
+    return fetch_back(c, who, back, 3);
+}
+
 // ------------------------------------------------------------------------------------------------ video streams
 static int stream_alloc(ofk_ctx *c)
 {
@@ -3457,6 +3582,8 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
         else c->*s.live = 0;                                     // the tracks move on without it
     }
     const bool table = on[TS_TABLE], depth = on[TS_DEPTH], templ = on[TS_TEMPLATE], keyf = on[TS_KEY], krot = on[TS_KEYROT], kmap = on[TS_KEYMAP];
+    const bool stab = on[TS_STAB];
+    if (stab) TRY(stab_frames_alloc(c));
     const bool flow_seed = table && c->tt.seed == OFK_TT_SEED_FLOW;
     bool few = false;                                            // the host knows the track counts from the previous call
     for (int b = 0; b < B; ++b) few = few || (c->h_counts && c->h_counts[b] <= min_features);
@@ -3530,10 +3657,24 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
             in.step = c->ttr.head; in.step_stride = 2;
             ofk_km_rows mr = c->kmr;                             // the depths as the previous step left them: their step is behind this launch
             mr.rho = c->tdr.rho; mr.var = c->tdr.var; mr.nobs = c->tdr.nobs;
+            const bool stab_rot = stab && krot && !kr_all_held(&c->krot);      // the view's R: the rotation record's, else rule 1's product anew
+            if (stab && !stab_rot) OFK_HIP(c, hipMemcpyAsync(c->sb_st, c->kfr.st, (size_t)B * OFK_KEY_STATE * 8, hipMemcpyDeviceToDevice, c->stream));
             launch_key_step(c, c->kfr, in, &c->key, krot ? &c->krot : nullptr, c->kr_st, c->kr_rec, B, kmap ? &c->kmap : nullptr, &mr);
             if (on[TS_POSF])                                     // directly behind it, on the record it has just written
                 ofk_launch_pos_filter_step(c->stream, &c->posf, c->pf_x, c->pf_P, c->pf_ist, c->pf_rec, c->pf_in, c->records, fu ? 0 : 1, c->kfr.rec,
                                            in.imu ? c->imu_state + 6 : c->sensors + 7, in.imu ? OFK_IMU_STATE : OFK_SENSOR_DOUBLES, B);
+            if (stab) {                                          // behind both: the view's pose, then the new frame (pyramid slot 1, level 0) into it
+                ofk_stab_in si = {};
+                if (stab_rot) { si.R = c->kr_rec + 4; si.R_stride = OFK_KEYROT_DOUBLES; }
+                else { si.st_copy = c->sb_st; si.omega = in.imu ? c->imu_state + 18 : c->sensors + 4; si.omega_stride = in.imu ? OFK_IMU_STATE : OFK_SENSOR_DOUBLES; }
+                si.key_rec = c->kfr.rec; si.sensors = c->sensors;
+                si.normal = in.imu ? c->imu_state + 15 : c->sensors + 1; si.normal_stride = in.imu ? OFK_IMU_STATE : OFK_SENSOR_DOUBLES;
+                si.cov = c->sb_cov; si.Bv = c->sb_Bv; si.ist = c->sb_ist; si.rec = c->sb_rec; si.M = c->sb_M;
+                ofk_launch_stab_pose(c->stream, si, &c->stab, h, w, B);
+                ofk_launch_warp(c->stream, c->pyr[1], c->pyr_stride, h, w, 1, c->sb_M, c->sb_frames, c->sb_stride, h, w, c->stab.border, c->stab.border_value,
+                                c->sb_cov, B);
+                c->sb_h = h; c->sb_w = w;
+            }
         }
         if (depth) {                                             // in front of the table's update, on what k_update_tracks is about to read
             const bool imu = fu && fu->use_imu;

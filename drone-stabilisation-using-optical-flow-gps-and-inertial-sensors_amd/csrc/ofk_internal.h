@@ -60,6 +60,15 @@ struct ofk_kf_in {
 // (NULL: the stream has none, no row is mature)
 struct ofk_km_rows { double *key_rho, *key_var; int *mstate; double *mrec; const double *rho, *var; const int *nobs; };
 
+// the stabilised view (ofk.h: ofk_set_stabilise): what one k_stab_pose launch reads and writes.  R with R_stride doubles between streams is
+// the rotation used, unless st_copy (the keyframe's state in front of its launch) is given: then R is rule 1's product of it and omega
+struct ofk_stab_in {
+    const double *R; int R_stride; const double *st_copy, *omega; int omega_stride;
+    const double *key_rec, *sensors, *normal; int normal_stride;  // the keyframe's records behind its launch; d, scaling, c; where the keyframe read n
+    const int *cov;                                              // [B] covered pixels of the previous warp (read where ist[3] != 0)
+    double *Bv; int *ist; double *rec, *M;                       // [B][9], [B][OFK_STAB_INTS], [B][OFK_STAB_DOUBLES], [B][9]
+};
+
 struct ofk_comm;
 struct ofk_ctx {
     int device;
@@ -177,6 +186,11 @@ struct ofk_ctx {
     double *pf_x, *pf_P, *pf_rec, *pf_in;    // [max_batch][12], [max_batch][144], [max_batch][OFK_POSF_DOUBLES], [max_batch][OFK_POSF_INPUT]; one lazy allocation (pf_x owns it)
     int *pf_ist;                             // [max_batch][OFK_POSF_INTS]
     int pf_batch, pf_live;                   // streams of the latest step with the position filter on (ofk_pos_filter_download), 0 = none; streams whose filter runs on
+    ofk_stabilise stab;                      // ofk_set_stabilise: mode OFK_STAB_OFF unless set
+    double *sb_Bv, *sb_rec, *sb_M, *sb_st;   // [max_batch][9], [max_batch][OFK_STAB_DOUBLES], [max_batch][9], [max_batch][OFK_KEY_STATE] (the keyframe's state in front of its launch); one lazy allocation (sb_Bv owns it)
+    int *sb_ist, *sb_cov;                    // [max_batch][OFK_STAB_INTS], [max_batch] covered pixels of the latest warp
+    uint8_t *sb_frames; size_t sb_stride;    // [max_batch][sb_stride] the stabilised frames, 256-B aligned per image (an allocation of its own, made by the first step with the setting on)
+    int sb_batch, sb_live, sb_h, sb_w;       // streams of the latest step with the setting on (ofk_stab_download), 0 = none; streams whose view runs on; the frames' geometry
     int kf_batch, kf_live;                   // streams of the latest step with the keyframe on (ofk_keyframe_download), 0 = none; streams whose rows match their current tracks
     hipEvent_t *ev; int ev_cap, ev_n; int *ev_stage;   // pairs of events: start/stop
     char errmsg[512];
@@ -235,6 +249,10 @@ void ofk_launch_pyr_down2(hipStream_t s, const uint8_t *src0, const uint8_t *src
 bool ofk_launch_pyr3(hipStream_t s, uint8_t *pyr0, uint8_t *pyr1, size_t stride, const ofk_levels &lv, int batch, int images);
 void ofk_launch_scharr(hipStream_t s, const uint8_t *src, size_t src_stride, int h, int w, int16_t *dxdy,
                        size_t dst_stride_elems, int batch);
+// the perspective warp (ofk.h: ofk_warp_perspective; k_warp.inc): ch 1 or 3; M [batch][9] f64 destination -> source; every dst image
+// 4-byte aligned; covered [batch] i32 is zeroed and counted, NULL = not counted
+void ofk_launch_warp(hipStream_t s, const uint8_t *src, size_t src_stride, int sh, int sw, int ch, const double *M, uint8_t *dst,
+                     size_t dst_stride, int dh, int dw, int border, int bval, int *covered, int batch);
 int  ofk_launch_mineig(hipStream_t s, const uint8_t *gray, size_t gray_stride, int h, int w, int block, float *eig,
                        size_t eig_stride, unsigned int *maxbits, const uint8_t *mask, size_t mask_stride, int batch);
 void ofk_launch_maxbits(hipStream_t s, const float *eig, size_t eig_stride, const uint8_t *mask, size_t mask_stride,
@@ -330,6 +348,11 @@ void ofk_launch_keymap_clear(hipStream_t s, const ofk_km_rows &r, const int *key
 void ofk_launch_pos_filter_step(hipStream_t s, const ofk_pos_filter *f, double *x, double *P, int *ist, double *rec, double *input, const double *v,
                                 int plain, const double *key_rec, const double *rw, int rw_stride, int batch);
 void ofk_launch_pos_filter_clear(hipStream_t s, double *x, double *P, int *ist, double *rec, double *input, int b0, const double *p, int batch);
+// the stabilised view (ofk.h: ofk_set_stabilise; k_stabilise.inc): rules 1-4 in one launch behind the keyframe's step and the position
+// filter's, in front of k_warp_u8; and the view of `batch` streams from b0 on back to the identity (limit != NULL: where limit[b] > 0,
+// the counts staying)
+void ofk_launch_stab_pose(hipStream_t s, const ofk_stab_in &in, const ofk_stabilise *st, int h, int w, int batch);
+void ofk_launch_stab_clear(hipStream_t s, double *Bv, int *ist, double *rec, const int *limit, int b0, int batch);
 // the track templates (ofk.h: ofk_set_track_template; k_track_template.inc): rule 1, rules 2-5 behind the gates, rule 6 in front of the table's update
 void ofk_launch_track_affine(hipStream_t s, const float *prev_pts, const float *next_pts, const uint8_t *status, const int *counts, int stride,
                              int h, int w, const ofk_track_template *d, float *L, double *rec, int batch);

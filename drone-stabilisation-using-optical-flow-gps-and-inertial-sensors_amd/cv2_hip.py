@@ -1,9 +1,10 @@
 """cv2_hip.py — the cv2 calls on the reference's hot path, with OpenCV's names, signatures and array
 conventions, executed by the HIP kernels of libofk.so.  `import cv2_hip as cv2` in the reference's scripts
-covers: cvtColor(COLOR_BGR2GRAY), goodFeaturesToTrack, calcOpticalFlowPyrLK, KalmanFilter, TERM_CRITERIA_*; undistortPoints and
+covers: cvtColor(COLOR_BGR2GRAY), warpPerspective(INTER_LINEAR), goodFeaturesToTrack, calcOpticalFlowPyrLK, KalmanFilter, TERM_CRITERIA_*; undistortPoints and
 fisheye.undistortPoints / distortPoints belong to the camera model (ofk.h: ofk_set_camera), which the reference does not have.
 
 Reference call sites: of_module.py:40,44,63-76,80,86,88,122,152; velocity_measurment_node:113,120,133,163;
+homography_experiments/homography.py (warpPerspective);
 evaluate_exp.py:65,66,85,98,106; of_library.py:236,238,248,249.
 Semantics are those of oracle/image_oracle.c (OpenCV's published algorithms with exact integer window sums).
 """
@@ -30,6 +31,40 @@ def cvtColor(src, code):
         raise ValueError("cvtColor(BGR2GRAY) expects an HxWx3 uint8 image")
     h, w = src.shape[:2]
     return ofk.default_context(w, h).gray_bgr8(src)
+
+
+INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA, INTER_LANCZOS4 = 0, 1, 2, 3, 4
+WARP_INVERSE_MAP = 16
+BORDER_CONSTANT, BORDER_REPLICATE = 0, 1
+
+
+def warpPerspective(src, M, dsize, dst=None, flags=INTER_LINEAR, borderMode=BORDER_CONSTANT, borderValue=0):
+    """cv2.warpPerspective for HxW or HxWx3 uint8 images, INTER_LINEAR only (cv2's 5-bit fixed-point arithmetic; ofk.h:
+    ofk_warp_perspective states the rule and where the evaluation of the coordinates differs from cv2's).  M maps the source to the
+    destination and is inverted here in float64, unless flags carries WARP_INVERSE_MAP; dsize = (width, height).  borderMode:
+    BORDER_CONSTANT or BORDER_REPLICATE; borderValue: one number 0..255 for every channel (or a sequence of equal numbers)."""
+    flags = int(flags)
+    if flags & ~WARP_INVERSE_MAP != INTER_LINEAR:
+        raise NotImplementedError("warpPerspective: INTER_LINEAR only (other interpolations are out of scope)")
+    if borderMode not in (BORDER_CONSTANT, BORDER_REPLICATE):
+        raise NotImplementedError("warpPerspective: BORDER_CONSTANT and BORDER_REPLICATE only")
+    src = np.asarray(src)
+    if src.dtype != np.uint8 or not (src.ndim == 2 or (src.ndim == 3 and src.shape[2] in (1, 3))) or 0 in src.shape:
+        raise ValueError("warpPerspective expects an HxW, HxWx1 or HxWx3 uint8 image")
+    M = np.asarray(M, np.float64)
+    if M.shape != (3, 3):
+        raise ValueError("warpPerspective: M must be 3x3")
+    bv = np.unique(np.asarray(borderValue, np.float64).reshape(-1)[:max(1, src.shape[2] if src.ndim == 3 else 1)])
+    if len(bv) != 1 or bv[0] != int(bv[0]) or not 0 <= bv[0] <= 255:
+        raise NotImplementedError("warpPerspective: borderValue is one integer 0..255 for every channel")
+    if not flags & WARP_INVERSE_MAP:
+        try:
+            M = np.linalg.inv(M)
+        except np.linalg.LinAlgError:
+            raise ValueError("warpPerspective: M is singular") from None
+    w, h = int(dsize[0]), int(dsize[1])
+    ctx = ofk.default_context(max(w, src.shape[1]), max(h, src.shape[0]))
+    return ctx.warp_perspective(src, M, (h, w), borderMode, int(bv[0]))[0]
 
 
 IMREAD_UNCHANGED, IMREAD_GRAYSCALE, IMREAD_COLOR = -1, 0, 1

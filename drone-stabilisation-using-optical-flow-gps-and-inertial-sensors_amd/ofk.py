@@ -25,7 +25,7 @@ STAGES = ("gray", "pyr", "eig", "nms", "select", "lk", "solve")
 # every entry point include/ofk.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = (
     "ofk_version", "ofk_last_error", "ofk_device_count", "ofk_create", "ofk_destroy", "ofk_sync", "ofk_device_sync",
-    "ofk_gray_bgr8", "ofk_pyr_down_u8", "ofk_pyramid_u8", "ofk_scharr_s16", "ofk_mineig_response", "ofk_select_corners",
+    "ofk_gray_bgr8", "ofk_pyr_down_u8", "ofk_pyramid_u8", "ofk_scharr_s16", "ofk_warp_perspective", "ofk_mineig_response", "ofk_select_corners",
     "ofk_good_features", "ofk_lk_pyr", "ofk_lk_pyr_ex", "ofk_predict_points", "ofk_set_lk_seed", "ofk_get_lk_seed", "ofk_flow_model", "ofk_feasibility", "ofk_velocity_solve", "ofk_imu_propagate",
     "ofk_set_robust", "ofk_get_robust", "ofk_robust_download", "ofk_velocity_solve_robust", "ofk_robust_pairs",
     "ofk_set_cov", "ofk_get_cov", "ofk_cov_download", "ofk_velocity_solve_cov",
@@ -46,6 +46,7 @@ SYMBOLS = (
     "ofk_set_keyframe_rotation", "ofk_get_keyframe_rotation", "ofk_keyframe_rotation_download", "ofk_keyframe_rotation_step",
     "ofk_set_keyframe_map", "ofk_get_keyframe_map", "ofk_keyframe_map_download", "ofk_keyframe_map_step",
     "ofk_set_pos_filter", "ofk_get_pos_filter", "ofk_pos_filter_input", "ofk_pos_filter_reset", "ofk_pos_filter_download", "ofk_pos_filter_step",
+    "ofk_set_stabilise", "ofk_get_stabilise", "ofk_stab_download", "ofk_stab_frames", "ofk_stab_reset", "ofk_stab_pose",
     "ofk_set_track_template", "ofk_get_track_template", "ofk_track_template_download", "ofk_track_affine_fit", "ofk_track_template_step",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
@@ -71,6 +72,8 @@ class Params(C.Structure):
 
 
 LK_USE_INITIAL_FLOW, LK_GET_MIN_EIGENVALS = 4, 8         # cv2's OPTFLOW_* values (ofk_lk_pyr_ex)
+BORDER_CONSTANT, BORDER_REPLICATE = 0, 1                 # ofk_warp_perspective (cv2's BORDER_* values)
+BORDERS = {"constant": BORDER_CONSTANT, "replicate": BORDER_REPLICATE}
 SEED_OFF, SEED_MODEL, SEED_ROTATION = 0, 1, 2           # ofk_set_lk_seed / ofk_predict_points
 SEED_MODES = {"off": SEED_OFF, "model": SEED_MODEL, "rotation": SEED_ROTATION}
 ROBUST_OFF, ROBUST_HUBER, ROBUST_TUKEY = 0, 1, 2         # ofk_set_robust / ofk_velocity_solve_robust
@@ -129,6 +132,11 @@ KEY_RE_MAP = 6                                           # the keyframe record's
 POSF_OFF, POSF_ON = 0, 1                                 # ofk_set_pos_filter
 POSF_STATES, POSF_INPUT, POSF_INTS, POSF_DOUBLES = 12, 12, 16, 48   # x = (p, v, b, c); the input row; the counts; the record
 POSF_NOT, POSF_APPLIED, POSF_GATED, POSF_REFUSED = 0, 1, 2, 3       # an update's outcome in the record
+STAB_OFF, STAB_ROTATION, STAB_PLANE = 0, 1, 2            # ofk_set_stabilise
+STAB_MODES = {"off": STAB_OFF, "rotation": STAB_ROTATION, "plane": STAB_PLANE}
+STAB_DOUBLES, STAB_INTS = 48, 4                          # the record; steps since the last re-base, re-bases, approx, a previous warp exists
+STAB_NONE, STAB_ROTATION_ONLY, STAB_FULL = 0, 1, 2       # the record's flag
+STAB_RB_COVER, STAB_RB_FINITE = 1, 2                     # the record's re-base reason
 TPL_OFF, TPL_ON = 0, 1                                   # ofk_set_track_template
 TPL_DOUBLES = 32                                         # M, t, fit flag, rows of the two fits, rms, nine counts, largest move
 TPL_KEEP, TPL_DROP = 0, 1
@@ -638,6 +646,28 @@ def pos_filter_setting(mode=True, dt=1.0, sigma_v=1e-3, floor=0.0, infl=1.0, sha
     return f
 
 
+class Stabilise(C.Structure):
+    """ofk_stabilise (include/ofk.h): every step's new gray frame warped into the view of the stream's keyframe."""
+    _fields_ = [("mode", C.c_int), ("border", C.c_int), ("border_value", C.c_int), ("min_cover", C.c_double), ("chain", C.c_int)]
+
+
+def stabilise_setting(mode=True, border=BORDER_CONSTANT, border_value=0, min_cover=0.5, chain=1):
+    """A Stabilise structure from names: mode True (the plane's homography) / False, "plane", "rotation" (R alone) or STAB_*; border
+    "constant" / "replicate" or BORDER_*, with border_value 0..255 outside the frame; a view whose warp covered less than min_cover of
+    the frame is re-based on the current keyframe (0: never); chain 1: the view stays the first keyframe's across re-keys, 0: it jumps
+    to each new keyframe."""
+    mode = STAB_MODES[mode] if isinstance(mode, str) else STAB_PLANE if mode is True else int(mode)
+    if mode not in (STAB_OFF, STAB_ROTATION, STAB_PLANE):
+        raise ValueError(f"stabilise mode {mode} is none of STAB_OFF, STAB_ROTATION, STAB_PLANE")
+    m = Stabilise(mode, BORDERS[border] if isinstance(border, str) else int(border), int(border_value), float(min_cover), int(chain))
+    if mode != STAB_OFF:
+        if not (m.border in (BORDER_CONSTANT, BORDER_REPLICATE) and 0 <= m.border_value <= 255 and np.isfinite(m.min_cover) and 0 <= m.min_cover < 1
+                and m.chain in (0, 1)):
+            raise ValueError(f"stabilise setting outside its range: border {m.border} in (0, 1), border_value {m.border_value} in 0..255, "
+                             f"min_cover {m.min_cover} in [0, 1), chain {m.chain} in (0, 1)")
+    return m
+
+
 class Fusion(C.Structure):
     """ofk_fusion (include/ofk.h): what ofk_stream_step_fused does between LK and the next frame."""
     _fields_ = [("use_imu", C.c_int), ("flow", C.c_int), ("keep", C.c_int), ("filter", C.c_int), ("control", C.c_int),
@@ -649,7 +679,7 @@ class Fusion(C.Structure):
 SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("gyro_bias", GyroBias), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate), ("lk_light", LkLight),
             ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion),
             ("track_table", TrackTable), ("track_depth", TrackDepth), ("track_template", TrackTemplate), ("keyframe", Keyframe),
-            ("keyframe_rotation", KeyframeRotation), ("keyframe_map", KeyframeMap), ("pos_filter", PosFilter))
+            ("keyframe_rotation", KeyframeRotation), ("keyframe_map", KeyframeMap), ("pos_filter", PosFilter), ("stabilise", Stabilise))
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -705,6 +735,7 @@ def load_library():
         L.ofk_pyr_down_u8.argtypes = [vp, vp, i, i, i, vp]
         L.ofk_pyramid_u8.argtypes = [vp, vp, i, i, i, i, vp, C.POINTER(i)]
         L.ofk_scharr_s16.argtypes = [vp, vp, i, i, i, vp]
+        L.ofk_warp_perspective.argtypes = [vp, vp, i, i, i, vp, vp, i, i, i, i, i, vp]
         L.ofk_mineig_response.argtypes = [vp, vp, i, i, i, i, vp]
         L.ofk_select_corners.argtypes = [vp, vp, vp, i, i, i, i, d, d, vp, vp]
         L.ofk_good_features.argtypes = [vp, vp, vp, i, i, i, i, d, d, i, vp, vp]
@@ -760,6 +791,10 @@ def load_library():
         L.ofk_pos_filter_reset.argtypes = [vp, i, vp]
         L.ofk_pos_filter_download.argtypes = [vp, vp, vp, vp, vp]
         L.ofk_pos_filter_step.argtypes = [vp, C.POINTER(PosFilter), vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
+        L.ofk_stab_download.argtypes = [vp, vp, vp, vp]
+        L.ofk_stab_frames.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.ofk_stab_reset.argtypes = [vp, i]
+        L.ofk_stab_pose.argtypes = [vp, C.POINTER(Stabilise), vp, vp, vp, vp, vp, i, i, vp, vp, i, vp]
         L.ofk_track_template_download.argtypes = [vp, vp, vp, vp, vp, vp, i, vp]
         L.ofk_track_affine_fit.argtypes = [vp, C.POINTER(TrackTemplate), vp, vp, vp, vp, i, i, i, i, vp, vp]
         L.ofk_track_template_step.argtypes = [vp, C.POINTER(TrackTemplate), vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
@@ -995,6 +1030,36 @@ class Context:
         with self._lock:
             self._ck(self._L.ofk_scharr_s16(self._h, _p(gray), B, h, w, _p(out)))
         return out[0] if single else out
+
+    def warp_perspective(self, src, M, dsize=None, border="constant", border_value=0):
+        """ofk_warp_perspective: cv2's 5-bit bilinear warp with M mapping a DESTINATION pixel to a SOURCE pixel (ofk.h states the rule).
+        M [3,3]: one image, src [h,w] or [h,w,C]; M [B,3,3]: src [B,h,w] or [B,h,w,C]; C is 1 or 3.  dsize (height, width) of the
+        destination, default the source's.  border: "constant" / "replicate" or BORDER_*.  -> (dst in src's layout, covered): the
+        pixels per image whose four taps lie inside the source, an int for one image, [B] int32 otherwise."""
+        M = _arr(M, np.float64)
+        single = M.shape == (3, 3)
+        if single:
+            M = M[None]
+        if M.ndim != 3 or M.shape[1:] != (3, 3):
+            raise ValueError(f"warp_perspective: M {M.shape} is neither [3,3] nor [B,3,3]")
+        src = _arr(src, np.uint8)
+        if single:
+            src = src[None]
+        if src.ndim not in (3, 4) or src.shape[0] != M.shape[0] or 0 in src.shape:
+            raise ValueError(f"warp_perspective: src {src.shape} does not hold one [h,w] or [h,w,C] image per matrix ({M.shape[0]})")
+        ch = src.shape[3] if src.ndim == 4 else 1
+        if ch not in (1, 3):
+            raise ValueError(f"warp_perspective: {ch} channels (1 or 3)")
+        B, sh, sw = src.shape[:3]
+        dh, dw = (sh, sw) if dsize is None else (int(dsize[0]), int(dsize[1]))
+        if dh < 1 or dw < 1:
+            raise ValueError(f"warp_perspective: dsize {dsize}")
+        mode = BORDERS[border] if isinstance(border, str) else int(border)
+        out = np.empty((B, dh, dw) + src.shape[3:], np.uint8)
+        covered = np.zeros(B, np.int32)
+        with self._lock:
+            self._ck(self._L.ofk_warp_perspective(self._h, _p(src), sh, sw, ch, _p(M), _p(out), dh, dw, mode, int(border_value), B, _p(covered)))
+        return (out[0], int(covered[0])) if single else (out, covered)
 
     def mineig(self, gray, block_size):
         gray, single = self._batched(gray, 2)
@@ -1461,6 +1526,67 @@ class Context:
 
     def get_pos_filter(self):
         return self._get_struct(self._L.ofk_get_pos_filter, PosFilter)
+
+    def set_stabilise(self, stabilise=None, **settings):
+        """ofk_set_stabilise: a Stabilise (or stabilise_setting's keywords); None or mode False switches it off.  Every later stream
+        step leaves the step's new gray frame warped into the keyframe's view on the device (stab_download)."""
+        self._set_struct(self._L.ofk_set_stabilise, stabilise, settings, stabilise_setting, lock=True)
+
+    def get_stabilise(self):
+        return self._get_struct(self._L.ofk_get_stabilise, Stabilise)
+
+    def stab_reset(self, stream):
+        """ofk_stab_reset: the view of active stream `stream` starts over at the identity with its next step."""
+        with self._lock:
+            self._ck(self._L.ofk_stab_reset(self._h, int(stream)))
+
+    def stab_download(self, batch=None, h=None, w=None, frames=True):
+        """ofk_stab_download -> dict(frames [batch,h,w] u8 (frames=True; h, w: the streams' frame), rec [batch,48], covered [batch] i32) of
+        the streams of the latest step with the setting on.  rec: M 0-8 (view pixel -> frame pixel), Bv 9-17, R 18-26, T 27-29, flag 30
+        (STAB_*), re-base reason 31, steps since the last re-base 32, re-bases 33, approx 34, re-keyed 35, the previous cover 36."""
+        B = self.max_batch if batch is None else int(batch)
+        if not 0 <= B <= self.max_batch:
+            raise ValueError(f"stab_download: batch {batch} outside 0..{self.max_batch}")
+        rec = np.zeros((self.max_batch, STAB_DOUBLES), np.float64)
+        cov = np.zeros(self.max_batch, np.int32)
+        fr = None
+        if frames:
+            if h is None or w is None or int(h) * int(w) > self.max_w * self.max_h or int(h) < 1 or int(w) < 1:
+                raise ValueError(f"stab_download: frames need the streams' h, w (got {h}, {w})")
+            fr = np.zeros((self.max_batch, int(h), int(w)), np.uint8)
+        with self._lock:
+            self._ck(self._L.ofk_stab_download(self._h, _p(fr), _p(rec), _p(cov)))
+        out = dict(rec=rec[:B].copy(), covered=cov[:B].copy())
+        if frames:
+            out["frames"] = fr[:B].copy()
+        return out
+
+    def stab_frames(self):
+        """ofk_stab_frames -> (device pointer of the stabilised frames, bytes between images), for consumers on the device."""
+        ptr, stride = C.c_void_p(), C.c_size_t()
+        with self._lock:
+            self._ck(self._L.ofk_stab_frames(self._h, C.byref(ptr), C.byref(stride)))
+        return ptr.value, stride.value
+
+    def stab_pose(self, R, key_rec, sensors, h, w, state=None, normal=None, prev_covered=None, stabilise=None, **settings):
+        """ofk_stab_pose, the stage entry: rules 1-4 on host arrays.  R [B,3,3] the rotation the key solve used; key_rec [B,32] the
+        keyframe's records; sensors [B,28]; h, w the frame; state: dict(Bv [B,3,3], ints [B,4]) of the previous call (None: the
+        identity, zero); normal [B,3] (None: the sensor rows'); prev_covered [B] the previous warp's covered counts (read where
+        ints[:, 3] != 0); the setting a Stabilise or stabilise_setting's keywords.  -> (state, rec [B,48]), new arrays."""
+        st = stabilise if stabilise is not None else stabilise_setting(**settings)
+        Rm = _arr(R, np.float64)
+        if Rm.ndim != 3 or Rm.shape[1:] != (3, 3) or Rm.shape[0] < 1:
+            raise ValueError(f"stab_pose: R {Rm.shape} is not [B >= 1, 3, 3]")
+        B = Rm.shape[0]
+        kr = _arr(key_rec, np.float64, (B, KEY_DOUBLES)); sn = _arr(sensors, np.float64, (B, SENSOR_DOUBLES))
+        nr = _opt(normal, np.float64, (B, 3)); pc = _opt(prev_covered, np.int32, (B,))
+        state = state or {}
+        Bv = np.tile(np.eye(3), (B, 1, 1)) if state.get("Bv") is None else np.array(_arr(state["Bv"], np.float64, (B, 3, 3)))
+        ints = np.zeros((B, STAB_INTS), np.int32) if state.get("ints") is None else np.array(_arr(state["ints"], np.int32, (B, STAB_INTS)))
+        rec = np.zeros((B, STAB_DOUBLES), np.float64)
+        with self._lock:
+            self._ck(self._L.ofk_stab_pose(self._h, C.byref(st), _p(Rm), _p(kr), _p(sn), _p(nr), _p(pc), int(h), int(w), _p(Bv), _p(ints), B, _p(rec)))
+        return dict(Bv=Bv, ints=ints), rec
 
     def pos_filter_input(self, input):
         """ofk_pos_filter_input: input [active streams, 12] f64 for the next step that is not held: du 0-2, fix valid 3, the fix 4-6, its

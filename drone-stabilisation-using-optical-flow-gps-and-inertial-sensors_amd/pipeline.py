@@ -188,6 +188,10 @@ class PipelineConfig:
     # pos_filter (ofk.h: ofk_set_pos_filter): None, True (the defaults) or an ofk.PosFilter: every stream fuses the keyframe's
     # displacement, the step's velocity and position fixes in a filter with a cloned state; it needs keyframe on; FlowPipeline ignores it
     pos_filter: object = None
+    # stabilise (ofk.h: ofk_set_stabilise): None, True (the defaults) or an ofk.Stabilise: every stream step leaves the step's new gray
+    # frame warped into the view of the stream's keyframe on the device; it needs keyframe on and neither a camera model nor a
+    # rolling shutter; FlowPipeline ignores it
+    stabilise: object = None
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -335,6 +339,15 @@ class PipelineConfig:
             raise ValueError("pos_filter needs keyframe on")
         return None if m.mode == ofk.POSF_OFF else m
 
+    def stabilise_setting(self):
+        """The ofk.Stabilise structure of this configuration, None when no stabilised view is kept."""
+        m = self._struct_setting("stabilise", ofk.Stabilise, ofk.stabilise_setting)
+        if m is not None and self.keyframe_setting() is None:
+            raise ValueError("stabilise needs keyframe on")
+        if m is not None and (self.camera_setting() is not None or self.rolling_shutter_setting() is not None):
+            raise ValueError("stabilise beside a camera model or a rolling shutter: a raw frame needs a remap in front of the warp, which is not built")
+        return m
+
     def track_template_setting(self):
         """The ofk.TrackTemplate structure of this configuration, None when the templates are off."""
         return self._struct_setting("track_template", ofk.TrackTemplate, ofk.track_template_setting)
@@ -459,7 +472,8 @@ def _apply_settings(ctx, cfg, zones):
         steps += [(ctx.set_zones, cfg.zones_setting), (ctx.set_gyro_bias, cfg.gyro_bias_setting), (ctx.set_track_table, cfg.track_table_setting),
                   (ctx.set_track_depth, cfg.track_depth_setting), (ctx.set_track_template, cfg.track_template_setting),
                   (ctx.set_keyframe, cfg.keyframe_setting), (ctx.set_keyframe_rotation, cfg.keyframe_rotation_setting),
-                  (ctx.set_keyframe_map, cfg.keyframe_map_setting), (ctx.set_pos_filter, cfg.pos_filter_setting)]
+                  (ctx.set_keyframe_map, cfg.keyframe_map_setting), (ctx.set_pos_filter, cfg.pos_filter_setting),
+                  (ctx.set_stabilise, cfg.stabilise_setting)]
     steps += [(ctx.set_camera, cfg.camera_setting), (ctx.set_rolling_shutter, cfg.rolling_shutter_setting),
               (ctx.set_finite_motion, cfg.finite_motion_setting)]
     for setter, setting in steps:                                # every *_setting() is None when its setting is off
@@ -629,6 +643,23 @@ class FlowStream:
                    T_plain=rec[:, 7:10].copy(), rec=rec)
         for k, s in (("map_rows", 1), ("live_rows", 2), ("rows", 3), ("rows_gated", 4), ("captured", 10), ("captured_for", 11)):
             out[k] = rec[:, s].astype(np.int32)
+        return out
+
+    def stabilised(self, frames=True):
+        """The stabilised view behind the latest step (ofk.h: ofk_set_stabilise): dict(frames [batch, h, w] u8: the step's new gray
+        frame in the view of the stream's first keyframe (frames=False: left on the device); M [batch, 3, 3]: view pixel -> frame pixel;
+        Bv, R [batch, 3, 3], T [batch, 3]; flag [batch] (ofk.STAB_*); rebase [batch]: the step's re-base reason (0: none); cover
+        [batch]: the share of the view the frame filled; covered, steps, rebases, approx, rekeyed [batch]; rec [batch, 48])."""
+        h, w = self.ctx.max_h, self.ctx.max_w
+        d = self.ctx.stab_download(self.batch, h, w, frames=frames)
+        rec = d["rec"]
+        out = dict(M=rec[:, 0:9].reshape(-1, 3, 3).copy(), Bv=rec[:, 9:18].reshape(-1, 3, 3).copy(), R=rec[:, 18:27].reshape(-1, 3, 3).copy(),
+                   T=rec[:, 27:30].copy(), flag=rec[:, 30].astype(np.int32), rebase=rec[:, 31].astype(np.int32), covered=d["covered"],
+                   cover=d["covered"] / float(h * w), rec=rec)
+        for k, slot in (("steps", 32), ("rebases", 33), ("approx", 34), ("rekeyed", 35)):
+            out[k] = rec[:, slot].astype(np.int32)
+        if frames:
+            out["frames"] = d["frames"]
         return out
 
     def position_input(self, du=None, fix=None, fix_sigma=None):

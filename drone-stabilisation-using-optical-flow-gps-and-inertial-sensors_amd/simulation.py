@@ -82,6 +82,13 @@ def keyframe_map_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None, dept
     return step(np.asarray(next_pts, np.float32)[:, :2], sensors, v_uav, state=state, depth=depth, **kw)
 
 
+def stabilise_step(R, key_rec, sensors, h, w, state=None, **kw):
+    """One step of a stream's stabilised view without images (ofk.h: ofk_stab_pose); velocity_node.stabilise_step's arguments and
+    returns: (state dict(Bv, ints), rec [48])."""
+    from .velocity_node import stabilise_step as step
+    return step(R, key_rec, sensors, h, w, state=state, **kw)
+
+
 def pos_filter_step(v_uav, key_rec, R_world=None, state=None, **kw):
     """One step of a stream's position filter without images (ofk.h: ofk_pos_filter_step); velocity_node.pos_filter_step's arguments
     and returns: (state dict(x, P, istate), rec [48])."""

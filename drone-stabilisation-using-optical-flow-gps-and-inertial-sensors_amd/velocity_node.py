@@ -241,6 +241,24 @@ def keyframe_map_step(next_pts, sensors, v_uav=(0.0, 0.0, 0.0), state=None, dept
     return res, rec[0], mrec[0]
 
 
+def stabilise_step(R, key_rec, sensors, h, w, state=None, normal=None, prev_covered=None, **settings):
+    """One step of a stream's stabilised view without images (ofk.h: ofk_stab_pose): the pixel homography M that warps the step's
+    frame into the view, and the view kept across re-keys.  R [3,3]: the rotation the key solve used; key_rec [32]: the keyframe's
+    record of the step; sensors [28]: the step's sensor row; h, w: the frame; state: the dict the previous call returned (None: the
+    identity); normal [3]: the IMU state's normal under use_imu (None: the sensor row's); prev_covered: the covered pixels of the
+    previous warp (None: none yet); settings: ofk.stabilise_setting's keywords.
+    Returns (state dict(Bv [3,3], ints [4]), rec [48]): rec[0:9] is M, rec[30] the flag (ofk.STAB_*), rec[31] the re-base reason."""
+    st = None
+    if state is not None:
+        st = dict(Bv=np.asarray(state["Bv"], np.float64).reshape(1, 3, 3), ints=np.array(state["ints"], np.int32).reshape(1, ofk.STAB_INTS))
+        st["ints"][0, 3] = 0 if prev_covered is None else 1
+    out, rec = ofk.default_context().stab_pose(np.asarray(R, np.float64).reshape(1, 3, 3), np.asarray(key_rec, np.float64).reshape(1, ofk.KEY_DOUBLES),
+                                               np.asarray(sensors, np.float64).reshape(1, ofk.SENSOR_DOUBLES), h, w, state=st,
+                                               normal=None if normal is None else np.asarray(normal, np.float64).reshape(1, 3),
+                                               prev_covered=None if prev_covered is None else [int(prev_covered)], **settings)
+    return dict(Bv=out["Bv"][0], ints=out["ints"][0]), rec[0]
+
+
 def pos_filter_step(v_uav, key_rec, R_world=None, state=None, solved=True, du=None, fix=None, fix_sigma=None, **settings):
     """One step of a stream's position filter without images (ofk.h: ofk_pos_filter_step): predict, the velocity, displacement and fix
     updates, the clone at a re-key.  v_uav [3], solved: the step record's fields 8-10 and its solved flag; key_rec [32]: the
@@ -391,6 +409,7 @@ class optical_fusion:
     _keyframe_rotation = {}                                      # PipelineConfig's keyframe_rotation field; empty: R_acc is taken as exact
     _pos_filter = {}                                             # PipelineConfig's pos_filter field; empty: no position filter
     _keyframe_map = {}                                           # PipelineConfig's keyframe_map field; empty: the key solve is the plane's
+    _stabilise = {}                                              # PipelineConfig's stabilise field; empty: no stabilised view
     _fix = None                                                  # (position, sigma) of call_fix, handed to the filter with the next frame
     _keyframe = {}                                               # PipelineConfig's keyframe field; empty: no position against a keyframe
     _track_template = {}                                         # PipelineConfig's track_template field; empty: no template per track
@@ -552,7 +571,7 @@ class optical_fusion:
                                  **self._cov, **self._joint, **self._plane, **self._epipolar, **self._zones, **self._camera, **self._rolling_shutter,
                                  **self._finite_motion, **self._gyro_bias, **self._lk_light, **self._track_table, **self._track_depth,
                                  **self._track_template, **self._keyframe, **self._keyframe_rotation, **self._pos_filter,
-                                 **self._keyframe_map)
+                                 **self._keyframe_map, **self._stabilise)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -606,6 +625,9 @@ class optical_fusion:
         if self._keyframe_map:
             km = fs.key_map()
             self.last_key_map = {k: v[0] for k, v in km.items()}
+        if self._stabilise:
+            sv = fs.stabilised()
+            self.last_stabilised = {k: v[0] for k, v in sv.items()}
         if self._pos_filter:
             fp = fs.fused_position()
             self.last_position = {k: ({n: a[0] for n, a in v.items()} if isinstance(v, dict) else v[0]) for k, v in fp.items()}
@@ -686,7 +708,7 @@ class optical_fusion:
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
                  rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None, gyro_bias=None, lk_light=None,
                  track_table=None, track_depth=None, track_template=None, keyframe=None, keyframe_rotation=None, pos_filter=None,
-                 keyframe_map=None):
+                 keyframe_map=None, stabilise=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -757,7 +779,11 @@ class optical_fusion:
         keyframe_map: None (the key solve is the plane's), True, an ofk.KeyframeMap or a dict of ofk.keyframe_map_setting's keywords,
         e.g. dict(rel_max=0.05): the key translation is then solved against the per-track depths frozen at the keyframe (ofk.h:
         ofk_set_keyframe_map); it switches the keyframe, the depths and the track table on when they are None.  self.last_key_map is
-        FlowStream.key_map()'s dictionary for the one stream."""
+        FlowStream.key_map()'s dictionary for the one stream.
+        stabilise: None (no stabilised view), True, an ofk.Stabilise or a dict of ofk.stabilise_setting's keywords, e.g.
+        dict(mode="rotation", min_cover=0.7): every frame's step then leaves the gray frame warped into the view of the stream's first
+        keyframe (ofk.h: ofk_set_stabilise); it switches the keyframe and the track table on when they are None and does not go with a
+        camera model or a rolling shutter.  self.last_stabilised is FlowStream.stabilised()'s dictionary for the one stream."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -841,20 +867,24 @@ class optical_fusion:
             self._lk_light = {}
         if pos_filter is not None and pos_filter is not False and keyframe is None:
             keyframe = True                                      # the filter fuses the keyframe's displacement
+        if stabilise is not None and stabilise is not False and keyframe is None:
+            keyframe = True                                      # the view is the keyframe's
         if keyframe_map is not None and keyframe_map is not False:   # the map is the depths', frozen at the keyframe
             keyframe = True if keyframe is None else keyframe
             track_depth = True if track_depth is None else track_depth
         given = dict(track_table=track_table, track_depth=track_depth, track_template=track_template, keyframe=keyframe,
-                     keyframe_rotation=keyframe_rotation, pos_filter=pos_filter, keyframe_map=keyframe_map)
+                     keyframe_rotation=keyframe_rotation, pos_filter=pos_filter, keyframe_map=keyframe_map, stabilise=stabilise)
         for name, value in given.items():                        # the rotation's, the filter's and the map's checks read the keyframe, set in front of them
             beside = self._keyframe if name in ("keyframe_rotation", "pos_filter") else {}
+            if name == "stabilise":
+                beside = dict(**self._keyframe, **self._camera, **self._rolling_shutter)
             if name == "keyframe_map":
                 beside = dict(**self._keyframe, **self._track_depth, **self._keyframe_rotation)
             setattr(self, "_" + name, _struct_field(name, value, **beside))
         if (self._track_depth or self._track_template or self._keyframe) and not self._track_table:
             self._track_table = dict(track_table=True)           # the three are kept per row of the table
         self.last_track_depth = self.last_track_template = self.last_keyframe = self.last_keyframe_rotation = self.last_position = None
-        self.last_key_map = None
+        self.last_key_map = self.last_stabilised = None
         self._fix = None
         self._imu = {}                                           # host copy of the attributes call_imu owns (see the properties above)
         self._imu_pending, self._imu_stale, self._imu_host_dirty = [], False, False

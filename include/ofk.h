@@ -72,6 +72,32 @@ int ofk_pyramid_u8(ofk_ctx *ctx, const uint8_t *gray, int batch, int h, int w, i
  * dxdy [batch][h][w][2] int16 = (dx, dy), REFLECT_101 at the image border. */
 int ofk_scharr_s16(ofk_ctx *ctx, const uint8_t *gray, int batch, int h, int w, int16_t *dxdy);
 
+/* cv2.warpPerspective(src, M, dsize, flags = INTER_LINEAR | WARP_INVERSE_MAP, borderMode, borderValue) — the warp of the reference's
+ * homography experiment (homography_experiments/homography.py), for `batch` images in one launch.
+ * src [batch][sh][sw][channels] u8 -> dst [batch][dh][dw][channels] u8, channels 1 or 3 (interleaved).  M [batch][9] f64, row-major
+ * 3x3 per image, maps a DESTINATION pixel to a SOURCE pixel (the caller inverts a source -> destination matrix).
+ * The rule, per destination pixel with integer (x, y); all f64, every product and sum rounded on its own (no contraction), in this order:
+ *   1. X = (M0 x + M1 y) + M2,  Y = (M3 x + M4 y) + M5,  W = (M6 x + M7 y) + M8.
+ *   2. iw = (W != 0) ? 32.0 / W : 0.0 — one IEEE divide; no test on the sign of W, as in cv2.  fx = X iw, fy = Y iw.
+ *   3. ok = |fx| <= 2^30 && |fy| <= 2^30 (false for NaN).  A pixel that is not ok gets border_value in every channel, under either
+ *      border mode, and is not covered.
+ *   4. ix = rint(fx), iy = rint(fy), ties to even.  sx = ix >> 5, ax = ix & 31, sy = iy >> 5, ay = iy & 31 (arithmetic shift: floor):
+ *      cv2's 5 fractional bits of INTER_LINEAR.
+ *   5. The taps are (sx, sy), (sx+1, sy), (sx, sy+1), (sx+1, sy+1) = p00, p01, p10, p11.  A tap outside [0, sw) x [0, sh) reads
+ *      border_value under OFK_BORDER_CONSTANT and the pixel at the clamped coordinates under OFK_BORDER_REPLICATE.
+ *   6. Per channel: out = ((32-ax)(32-ay) p00 + ax (32-ay) p01 + (32-ax) ay p10 + ax ay p11 + 512) >> 10, in integers.  (cv2's
+ *      fixed-point sum exactly: its 15-bit weights (a/32)(b/32) 2^15 are the integers 32 a b, which sum to 2^15 without a fix-up,
+ *      and (32 s + 2^14) >> 15 = (s + 512) >> 10.)
+ *   7. A pixel is COVERED when it is ok and all four taps are inside the source.  covered [batch] i32 (nullable): covered pixels per image.
+ * This is cv2's interpolation arithmetic, not its evaluation of the coordinates (cv2 steps X, Y, W along a row block by block, which
+ * may round a tie differently).
+ * OFK_E_INVALID before any launch: channels other than 1 and 3; batch, sh x sw or dh x dw beyond the context's; a border other than
+ * the two; border_value outside 0..255; a NULL src, M or dst. */
+#define OFK_BORDER_CONSTANT   0
+#define OFK_BORDER_REPLICATE  1
+int ofk_warp_perspective(ofk_ctx *ctx, const uint8_t *src, int sh, int sw, int channels, const double *M, uint8_t *dst, int dh, int dw,
+                         int border, int border_value, int batch, int *covered);
+
 /* Shi-Tomasi response inside cv2.goodFeaturesToTrack (of_module.py:44,86; node:120,163; evaluate_exp.py:66,106;
  * of_library.py:238): Sobel-3 -> structure tensor box(block_size) -> min eigenvalue, f32 map [batch][h][w].
  * block_size 1..45. */
@@ -802,6 +828,78 @@ int ofk_pos_filter_reset(ofk_ctx *ctx, int b, const double *pos);
 int ofk_pos_filter_download(ofk_ctx *ctx, double *x, double *P, int *istate, double *rec);
 int ofk_pos_filter_step(ofk_ctx *ctx, const ofk_pos_filter *f, const double *v_uav, const int *solved, const double *key_rec,
                         const double *R_world, const double *input, double *x, double *P, int *istate, int batch, double *rec);
+
+/* Stabilised view per stream: every step's new gray frame resampled into the view of the stream's keyframe.  A stream with
+ * ofk_set_keyframe on knows the rigid motion P_c = R P_K + T that ties the current frame to the keyframe, and the ground plane (n, d) of
+ * the sensor row; for ground on that plane the motion is one homography per frame, K (I + T n' / (d - n.T)) R K^-1 (what
+ * synth.pixel_homography(motion = "finite") renders with).  With this setting on every stream step leaves on the device the step's new
+ * gray frame warped through it (k_warp_u8, ofk_warp_perspective's rule) into a view that stays that of the FIRST keyframe across
+ * re-keys.  Off by default; with it off every step allocates, launches and returns what it always did.  Nothing is fed back: records,
+ * `fused`, tracks, the table, depths, templates, the keyframe's state and record and the position filter keep their bits.  Streams only:
+ * ofk_pairs_run ignores the setting.
+ * State per stream: Bv [9] f64, row-major 3 x 3, view -> keyframe in normalised coordinates; ints [OFK_STAB_INTS] = steps since the
+ * last re-base, re-bases, approx, 1 where a previous warp's covered count exists; covered, one i32, of the latest warp; a record of
+ * OFK_STAB_DOUBLES.  Bv = I, the ints zero: by the first step with the setting on behind ofk_stream_begin (or switched on in
+ * mid-stream) and by ofk_stab_reset; Bv = I alone where the replace re-detection resets the keyframe (the streams with a budget).
+ * Two launches, k_stab_pose (one thread per stream) and k_warp_u8, on exactly the steps that launch the keyframe's kernel, behind it and
+ * behind the position filter's; a held step leaves state, record, count and frame alone.  All arithmetic f64 without contraction in the
+ * order written; sums of three are (a + b) + c; 3 x 3 products are (A_i0 B_0j + A_i1 B_1j) + A_i2 B_2j.  In order:
+ *   1. Inputs.  R and T are the ones the keyframe's rule 2 used at this step, in front of its rule 5.  With ofk_set_keyframe_rotation on
+ *      (and not every axis held by the setting alone) R = slots 4-12 of the rotation record.  Otherwise the keyframe's state is copied
+ *      device to device in front of the keyframe's launch and R is its rule 1's product of that copy's R_acc and the omega the keyframe
+ *      read, by the same device code.  T = slots 0-2 of the keyframe's record, kflag = its slot 3, rekey = its slot 9 != 0.
+ *      n = sn[1..3] (under use_imu the IMU state's normal), d = sn[0], as the keyframe read them.
+ *   2. Normalised homography G, key -> current.  den = d - ((n0 T0 + n1 T1) + n2 T2).  kflag OFK_KEY_NONE (no keyframe): flag
+ *      OFK_STAB_NONE, G = I.  Otherwise flag OFK_STAB_FULL when the mode is OFK_STAB_PLANE, kflag is OFK_KEY_SOLVED, |den| >= 1e-12 and
+ *      R, T, n and den are finite: C_ij = (i == j ? 1 : 0) + (T_i n_j) / den, G = C R.  Otherwise (mode OFK_STAB_ROTATION, an unsolved
+ *      key step, a plane through the camera, something that is no number) flag OFK_STAB_ROTATION_ONLY, G = R.
+ *   3. View.  A = G B, B = Bv (I on a re-base, rule 4).  K = [[f, 0, cx], [0, f, cy], [0, 0, 1]], f = 1.0 / scaling, (scaling, cx, cy) =
+ *      sn[19..21]: P = K A with P_0j = f A_0j + cx A_2j, P_1j = f A_1j + cy A_2j, P_2j = A_2j; M = P K^-1 with M_i0 = P_i0 scaling,
+ *      M_i1 = P_i1 scaling, M_i2 = P_i2 - (P_i0 (cx scaling) + P_i1 (cy scaling)).  M maps a pixel of the view to a pixel of the new
+ *      frame: the warp's destination -> source matrix.  Behind the warp: rekey and chain = 1: Bv = A (the view stays the first
+ *      keyframe's); rekey and chain = 0: Bv = I (the view jumps to the new keyframe); no rekey: Bv = B.  A rekey under a flag other than
+ *      OFK_STAB_FULL raises the approx count: the view has lost that step's translation.
+ *   4. Re-base, decided in front of rule 3.  OFK_STAB_RB_COVER: min_cover > 0, a previous warp of the stream exists and its covered
+ *      count, in f64, is below min_cover (h w).  OFK_STAB_RB_FINITE: no re-base by cover and an entry of M that is not finite; A and M
+ *      are formed again with B = I.  A re-base sets the steps since the last one to zero and raises the re-base count; any other step
+ *      raises the steps.  The view is then the current keyframe's.
+ *   5. Warp.  k_warp_u8 over level 0 of the step's new frame (the bytes ofk_resident_pyramid returns for it behind the step, JPEG steps
+ *      included), one channel, h x w -> h x w, the setting's border and border_value, into a resident [B][h][w] u8 buffer, 256-B
+ *      aligned per image, allocated by the first step with the setting on; covered as ofk_warp_perspective counts it.
+ * Record: 0-8 M, 9-17 Bv behind the step, 18-26 R, 27-29 T, 30 flag, 31 re-base reason (0: none), 32 steps since the last re-base,
+ * 33 re-bases, 34 approx, 35 1 on a rekey, 36 the previous warp's covered count as rule 4 read it (-1: none), 37-47 0.
+ * ofk_set_stabilise: NULL or mode OFK_STAB_OFF switches it off.  OFK_E_INVALID, the setting staying as it was: an unknown mode or border,
+ * border_value outside 0..255, min_cover outside [0, 1) or not finite (0: no re-base by cover), chain neither 0 nor 1.  Defaults
+ * behind "off": OFK_STAB_PLANE, OFK_BORDER_CONSTANT, 0, 0.5, 1.
+ * OFK_E_INVALID before any launch from a stream step with the setting on: ofk_set_keyframe off; ofk_set_camera or
+ * ofk_set_rolling_shutter on (the homography holds between ideal global-shutter images; a raw frame behind a lens needs a remap in
+ * front of the warp, which is not built).
+ * ofk_stab_download, the streams of the latest step with the setting on (every output may be NULL): frames [batch][h][w] u8, rec
+ * [batch][OFK_STAB_DOUBLES], covered [batch] i32.  ofk_stab_frames: the DEVICE pointer of the frames and the bytes between images, for
+ * consumers on the device (valid until the context is destroyed; written by every step).  ofk_stab_reset: active stream b starts over
+ * (Bv = I, the ints and the record zero but for M = Bv = I).
+ * ofk_stab_pose, rules 1-4 on host buffers (it touches no resident state): R [batch][9] the rotation used, key_rec
+ * [batch][OFK_KEY_DOUBLES], sensors [batch][OFK_SENSOR_DOUBLES], normal [batch][3] (NULL: the sensor rows'), prev_covered [batch] (NULL:
+ * zeros; read where ints[b][3] != 0), h, w the frame, Bv [batch][9] and ints [batch][OFK_STAB_INTS] in and out in place, rec
+ * [batch][OFK_STAB_DOUBLES] out (may be NULL). */
+#define OFK_STAB_OFF            0
+#define OFK_STAB_ROTATION       1
+#define OFK_STAB_PLANE          2
+#define OFK_STAB_DOUBLES        48
+#define OFK_STAB_INTS           4
+#define OFK_STAB_NONE           0
+#define OFK_STAB_ROTATION_ONLY  1
+#define OFK_STAB_FULL           2
+#define OFK_STAB_RB_COVER       1
+#define OFK_STAB_RB_FINITE      2
+typedef struct ofk_stabilise { int mode; int border; int border_value; double min_cover; int chain; } ofk_stabilise;
+int ofk_set_stabilise(ofk_ctx *ctx, const ofk_stabilise *s);
+int ofk_get_stabilise(const ofk_ctx *ctx, ofk_stabilise *s);
+int ofk_stab_download(ofk_ctx *ctx, uint8_t *frames, double *rec, int *covered);
+int ofk_stab_frames(ofk_ctx *ctx, uint8_t **device_ptr, size_t *image_stride);
+int ofk_stab_reset(ofk_ctx *ctx, int b);
+int ofk_stab_pose(ofk_ctx *ctx, const ofk_stabilise *s, const double *R, const double *key_rec, const double *sensors, const double *normal,
+                  const int *prev_covered, int h, int w, double *Bv, int *ints, int batch, double *rec);
 
 /* Camera model: the lens distortion undone on the device before the solve.  The solve stage reads a point as a sample of an ideal
  * pinhole image, x = (px - cx) * scaling (sensors[19..21]); the reference's camera is a wide-angle module whose lens moves a point by
