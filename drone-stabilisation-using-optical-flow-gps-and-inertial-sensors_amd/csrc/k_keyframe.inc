@@ -19,13 +19,15 @@ __device__ __forceinline__ void kf_clear_state(const ofk_kf_rows &t, int b, int 
         is[1] = 0;
 }
 
+__device__ __forceinline__ void kf_fresh_row(const ofk_kf_rows &t, size_t w) { t.key_xy[2 * w] = 0.f; t.key_xy[2 * w + 1] = 0.f; t.member[w] = 0; }   // no member
+
 // the rows of freshly detected tracks (beside k_track_table_begin): no members, no keyframe, the position at zero
 __global__ __launch_bounds__(256) void k_keyframe_begin(ofk_kf_rows t, const int *__restrict__ counts, int stride)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
     const int n = min(max(counts[b], 0), stride);
     const size_t base = (size_t)b * stride;
-    for (int i = tid; i < n; i += 256) { t.key_xy[2 * (base + i)] = 0.f; t.key_xy[2 * (base + i) + 1] = 0.f; t.member[base + i] = 0; }
+    for (int i = tid; i < n; i += 256) kf_fresh_row(t, base + i);
     kf_clear_state(t, b, tid, true);
 }
 
@@ -34,10 +36,10 @@ __global__ __launch_bounds__(256) void k_keyframe_replace(ofk_kf_rows t, const i
                                                           int stride)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
-    if (limit[b] <= 0) return;
+    if (!rows_stream_on(b, 0, gridDim.x, limit)) return;
     const int n = min(max(new_counts[b], 0), stride);
     const size_t base = (size_t)b * stride;
-    for (int i = tid; i < n; i += 256) { t.key_xy[2 * (base + i)] = 0.f; t.key_xy[2 * (base + i) + 1] = 0.f; t.member[base + i] = 0; }
+    for (int i = tid; i < n; i += 256) kf_fresh_row(t, base + i);
     kf_clear_state(t, b, tid, false);
 }
 
@@ -103,9 +105,8 @@ __device__ __forceinline__ double kf_res2(double a, double b, double u0, double 
 }
 
 // Rules 1-5 of ofk.h.  One workgroup per stream; every thread holds the stream's sums behind acc_block_sum and solves the 3 x 3 itself,
-// so that the gate and the residual need no broadcast.  The compaction is the table's: a chunk of 256 rows is read completely before
-// any of its rows is written, and a row only moves to a position <= its own.  Thread 0 writes the state and the record at the end;
-// nothing reads them behind the first barrier.
+// so that the gate and the residual need no broadcast.  The compaction is the table's, k_rows.inc's walk.  Thread 0 writes the state
+// and the record at the end; nothing reads them behind the first barrier.
 // The body is k_keyframe_body.inc, which k_keyframe_rot.inc compiles a second time with the joint rule 2 (KF_ROT 1).
 __global__ __launch_bounds__(256) void k_keyframe_step(ofk_kf_rows t, ofk_kf_in in, kf_cfg cfg)
 {

@@ -2,10 +2,9 @@
 // k_keyframe_rot.inc: rule 2 widened by ofk_set_keyframe_rotation).  With KF_ROT 0 the text is k_keyframe_step's as it always was.
 // KF_MAP 1 (k_keyframe_map.inc, with KF_ROT 0): rules M1-M5 of ofk_set_keyframe_map around them, the body of k_keyframe_step_map;
 // with KF_MAP 0 nothing of it is compiled.
-    __shared__ int s_wave[4];
-    __shared__ int s_base;
+    __shared__ row_walk s_rows;
     __shared__ double s_red[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int n = min(max(in.counts[b], 0), in.stride);
     const size_t base = (size_t)b * in.stride;
     const double *sn = in.sensors + (size_t)b * OFK_SENSOR_DOUBLES;
@@ -217,9 +216,8 @@
     const bool rekey = bits != 0;
     const int reason = bits ? __ffs(bits) : 0;
 
-    // 5. compaction
-    if (tid == 0) s_base = 0;
-    __syncthreads();                                            // also: every thread has read the state
+    // 5. compaction: the table's walk (k_rows.inc)
+    rows_begin(s_rows);                                         // its barrier also: every thread has read the state
     for (int i0 = 0; i0 < n; i0 += 256) {
         const int i = i0 + tid;
         const bool inside = i < n;
@@ -232,25 +230,18 @@
         double krho = km.key_rho[r], kvar = km.key_var[r];          // M5: they move with key_xy; a re-key empties them until M1 fills them
         if (rekey) { krho = 0.0; kvar = 0.0; }
 #endif
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int off = s_base;
-        for (int q = 0; q < wave; ++q) off += s_wave[q];
-        const int p = off + __popcll(bal & ((1ull << lane) - 1));
-        __syncthreads();                                        // every thread has read the rows of this chunk: safe to overwrite
+        const int p = rows_place(s_rows, keep);
         if (keep) { const size_t w = base + p; t.key_xy[2 * w] = kx; t.key_xy[2 * w + 1] = ky; t.member[w] = m; }
 #if KF_MAP
         if (keep) { const size_t w = base + p; km.key_rho[w] = krho; km.key_var[w] = kvar; }
 #endif
-        if (tid == 0) s_base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
+        rows_next(s_rows);
     }
-    const int kept = s_base;
-    const int extra = in.new_counts ? max(0, min(min(in.new_counts[b], in.max_total - kept), in.stride - kept)) : 0;
-    for (int i = tid; i < extra; i += 256) { const size_t w = base + kept + i; t.key_xy[2 * w] = 0.f; t.key_xy[2 * w + 1] = 0.f; t.member[w] = 0; }
+    const int kept = s_rows.base;
+    const int extra = rows_extra(in.new_counts, b, in.max_total, in.stride, kept);
+    for (int i = tid; i < extra; i += 256) kf_fresh_row(t, base + kept + i);
 #if KF_MAP
-    for (int i = tid; i < extra; i += 256) { const size_t w = base + kept + i; km.key_rho[w] = 0.0; km.key_var[w] = 0.0; }
+    for (int i = tid; i < extra; i += 256) km_fresh_row(km, base + kept + i);
 #endif
     if (tid == 0) {
         double *o = t.rec + (size_t)b * OFK_KEY_DOUBLES;

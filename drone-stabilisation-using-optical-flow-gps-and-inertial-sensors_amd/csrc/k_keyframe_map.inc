@@ -8,6 +8,8 @@
 struct km_cfg { int min_obs, min_rows, weights; double rel_max, ready_share; };
 typedef ofk_km_rows km_rows;                                     // ofk_internal.h
 
+__device__ __forceinline__ void km_fresh_row(const km_rows &m, size_t w) { m.key_rho[w] = 0.0; m.key_var[w] = 0.0; }   // no key depth
+
 // acc_point_w's arithmetic (k_robust.inc) with the row always counted: rows are rows, not weight sums
 __device__ __forceinline__ void km_point(Acc &a, double x, double y, double q0, double q1, double sA, double w)
 {
@@ -104,10 +106,10 @@ __global__ __launch_bounds__(256) void k_keymap_clear(km_rows m, const int *__re
                                                       const int *__restrict__ counts, int stride, int b0, int keep_rec)
 {
     const int b = b0 + blockIdx.x, tid = threadIdx.x;
-    if (limit && limit[b] <= 0) return;
+    if (!rows_stream_on(b, b0, gridDim.x, limit)) return;
     const int n = counts ? min(max(counts[b], 0), stride) : stride;
     const size_t base = (size_t)b * stride;
-    for (int i = tid; i < n; i += 256) { m.key_rho[base + i] = 0.0; m.key_var[base + i] = 0.0; }
+    for (int i = tid; i < n; i += 256) km_fresh_row(m, base + i);
     if (tid == 0) { m.mstate[(size_t)b * 2] = key_ist[(size_t)b * OFK_KEY_INTS]; m.mstate[(size_t)b * 2 + 1] = 0; }
     if (!keep_rec && tid < OFK_KEYMAP_DOUBLES) m.mrec[(size_t)b * OFK_KEYMAP_DOUBLES + tid] = tid == 0 ? (double)OFK_KEYMAP_NONE : 0.0;
 }

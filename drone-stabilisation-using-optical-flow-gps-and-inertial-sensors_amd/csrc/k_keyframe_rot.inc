@@ -210,7 +210,7 @@ __global__ __launch_bounds__(64) void k_keyrot_clear(double *__restrict__ rst, d
                                                      int flag)
 {
     const int b = b0 + blockIdx.x, tid = threadIdx.x;
-    if (limit && limit[b] <= 0) return;
+    if (!rows_stream_on(b, b0, gridDim.x, limit)) return;
     if (rst && tid < OFK_KEYROT_STATE) rst[(size_t)b * OFK_KEYROT_STATE + tid] = 0.0;
     if (tid < OFK_KEYROT_DOUBLES) rrec[(size_t)b * OFK_KEYROT_DOUBLES + tid] = tid == 3 ? (double)flag : 0.0;
 }

@@ -266,6 +266,7 @@ __global__ __launch_bounds__(64) void k_pos_filter_clear(double *__restrict__ x_
                                                          double p2)
 {
     const int b = b0 + blockIdx.x, lane = threadIdx.x;
+    if (!rows_stream_on(b, b0, gridDim.x, nullptr)) return;
     const int ax = lane < 3 ? lane : lane - 9;                  // the axis of a position slot
     const double pa = ax == 0 ? p0 : ax == 1 ? p1 : p2;
     for (int e = lane; e < PF_NN; e += 64) P_all[(size_t)b * PF_NN + e] = 0.0;

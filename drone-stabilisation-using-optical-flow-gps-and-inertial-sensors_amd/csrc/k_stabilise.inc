@@ -104,7 +104,7 @@ __global__ __launch_bounds__(64) void k_stab_pose(stab_args a)
 __global__ __launch_bounds__(64) void k_stab_clear(double *Bv, int *ist, double *rec, const int *__restrict__ limit, int b0, int batch)
 {
     const int b = b0 + blockIdx.x * 64 + threadIdx.x;
-    if (b >= b0 + batch || (limit && limit[b] <= 0)) return;
+    if (!rows_stream_on(b, b0, batch, limit)) return;
     for (int k = 0; k < 9; ++k) Bv[(size_t)b * 9 + k] = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
     if (!limit) {
         for (int k = 0; k < OFK_STAB_INTS; ++k) ist[(size_t)b * OFK_STAB_INTS + k] = 0;

@@ -6,13 +6,15 @@
 
 struct td_cfg { double sf, b_min, gate, q, rel_max; int min_obs, min_rows, update; };
 
+__device__ __forceinline__ void td_fresh_row(const ofk_td_rows &t, size_t w) { t.rho[w] = 0.0; t.var[w] = 0.0; t.nobs[w] = 0; }   // no depth yet
+
 // the rows of freshly detected tracks (beside k_track_table_begin): no depth yet, and an empty record.  One workgroup per stream.
 __global__ __launch_bounds__(256) void k_track_depth_begin(ofk_td_rows t, const int *__restrict__ counts, int stride)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
     const int n = min(max(counts[b], 0), stride);
     const size_t base = (size_t)b * stride;
-    for (int i = tid; i < n; i += 256) { t.rho[base + i] = 0.0; t.var[base + i] = 0.0; t.nobs[base + i] = 0; }
+    for (int i = tid; i < n; i += 256) td_fresh_row(t, base + i);
     if (tid < OFK_TD_DOUBLES) t.rec[(size_t)b * OFK_TD_DOUBLES + tid] = 0.0;
 }
 
@@ -21,10 +23,10 @@ __global__ __launch_bounds__(256) void k_track_depth_replace(ofk_td_rows t, cons
                                                              int stride)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
-    if (limit[b] <= 0) return;
+    if (!rows_stream_on(b, 0, gridDim.x, limit)) return;
     const int n = min(max(new_counts[b], 0), stride);
     const size_t base = (size_t)b * stride;
-    for (int i = tid; i < n; i += 256) { t.rho[base + i] = 0.0; t.var[base + i] = 0.0; t.nobs[base + i] = 0; }
+    for (int i = tid; i < n; i += 256) td_fresh_row(t, base + i);
 }
 
 // Point r's terms: the stage entry's x and u as they are, the resident points as pair_point forms them (k_estimate.hip).
@@ -37,17 +39,16 @@ __device__ __forceinline__ void td_point(const ofk_td_in &in, size_t r, double c
     ux = (X - (double)in.prev_pts[2 * r]) * scaling; uy = (Y - (double)in.prev_pts[2 * r + 1]) * scaling;
 }
 
-// Rules 1-4 of ofk.h, in front of k_track_table_update and with its prefix.  One workgroup per stream.
+// Rules 1-4 of ofk.h, in front of k_track_table_update and with its walk (k_rows.inc).  One workgroup per stream.
 //   1. the map solve over the mature rows of the state as the previous step left it: the ten sums of acc_point with (sA, sB) =
 //      (rho_i, 1), acc_block_sum, solve_from_acc; it reads nothing of this step's record
-//   2.-4. per chunk of 256 rows: measurement, prediction, and the kept rows move up in order.  A chunk is read completely before any
-//      of its rows is written, and a row only moves to a position <= its own, so no row is overwritten before it has been read.
+//   2.-4. per chunk of 256 rows: measurement, prediction, and the kept rows move up in order, in place.
 // The counts are ballots summed per wave and across the waves through LDS.  Thread 0 solves the 3 x 3 behind the walk and writes the
 // record.
 __global__ __launch_bounds__(256) void k_track_depth_step(ofk_td_rows t, ofk_td_in in, td_cfg cfg)
 {
-    __shared__ int s_wave[4], s_cnt[4][6];
-    __shared__ int s_base;
+    __shared__ row_walk s_rows;
+    __shared__ int s_cnt[4][6];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = min(max(in.counts[b], 0), in.stride);
     const size_t base = (size_t)b * in.stride;
@@ -75,8 +76,7 @@ __global__ __launch_bounds__(256) void k_track_depth_step(ofk_td_rows t, ofk_td_
 
     // 2.-4.
     int c_upd = 0, c_ini = 0, c_b = 0, c_r = 0, c_nu = 0, c_rst = 0;    // wave-uniform
-    if (tid == 0) s_base = 0;
-    __syncthreads();
+    rows_begin(s_rows);
     for (int i0 = 0; i0 < n; i0 += 256) {
         const int i = i0 + tid;
         const bool inside = i < n;
@@ -120,20 +120,13 @@ __global__ __launch_bounds__(256) void k_track_depth_step(ofk_td_rows t, ofk_td_
         }
         c_upd += __popcll(__ballot(upd)); c_ini += __popcll(__ballot(ini)); c_b += __popcll(__ballot(skb));
         c_r += __popcll(__ballot(skr)); c_nu += __popcll(__ballot(sknu)); c_rst += __popcll(__ballot(rst));
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int off = s_base;
-        for (int q = 0; q < wave; ++q) off += s_wave[q];
-        const int pos = off + __popcll(bal & ((1ull << lane) - 1));
-        __syncthreads();                                        // every thread has read the rows of this chunk: safe to overwrite
+        const int pos = rows_place(s_rows, keep);
         if (keep) { const size_t w = base + pos; t.rho[w] = rho; t.var[w] = var; t.nobs[w] = nobs; }
-        if (tid == 0) s_base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
+        rows_next(s_rows);
     }
-    const int kept = s_base;
-    const int extra = in.new_counts ? max(0, min(min(in.new_counts[b], in.max_total - kept), in.stride - kept)) : 0;
-    for (int i = tid; i < extra; i += 256) { const size_t w = base + kept + i; t.rho[w] = 0.0; t.var[w] = 0.0; t.nobs[w] = 0; }
+    const int kept = s_rows.base;
+    const int extra = rows_extra(in.new_counts, b, in.max_total, in.stride, kept);
+    for (int i = tid; i < extra; i += 256) td_fresh_row(t, base + kept + i);
     if (lane == 0) { int *s = s_cnt[wave]; s[0] = c_upd; s[1] = c_ini; s[2] = c_b; s[3] = c_r; s[4] = c_nu; s[5] = c_rst; }
     __syncthreads();
     if (tid == 0) {

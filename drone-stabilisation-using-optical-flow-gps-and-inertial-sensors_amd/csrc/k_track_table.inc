@@ -3,6 +3,12 @@
 // flow.  Included by k_tracks.hip.  The rows of one stream are only ever touched by that stream's workgroup, with plain vector
 // stores and no atomics, so a second launch on the same inputs gives the same bits.
 
+// A fresh row at index w: the track `id`, born in `step` at (x, y), not tracked yet.
+__device__ __forceinline__ void tt_fresh_row(const ofk_tt_rows &t, size_t w, unsigned id, int step, float x, float y)
+{
+    t.ids[w] = id; t.age[w] = 0; t.birth_step[w] = step; t.birth_xy[2 * w] = x; t.birth_xy[2 * w + 1] = y; t.flow_xy[2 * w] = 0.f; t.flow_xy[2 * w + 1] = 0.f;
+}
+
 // rule 1: the table of tracks that have just been detected.  One workgroup per stream.
 __global__ __launch_bounds__(256) void k_track_table_begin(ofk_tt_rows t, const float *__restrict__ pts, const int *__restrict__ counts,
                                                            int stride)
@@ -10,12 +16,7 @@ __global__ __launch_bounds__(256) void k_track_table_begin(ofk_tt_rows t, const 
     const int b = blockIdx.x, tid = threadIdx.x;
     const int n = min(max(counts[b], 0), stride);
     const size_t base = (size_t)b * stride;
-    for (int i = tid; i < n; i += 256) {
-        const size_t r = base + i;
-        t.ids[r] = (unsigned)i; t.age[r] = 0; t.birth_step[r] = 0;
-        t.birth_xy[2 * r] = pts[2 * r]; t.birth_xy[2 * r + 1] = pts[2 * r + 1];
-        t.flow_xy[2 * r] = 0.f; t.flow_xy[2 * r + 1] = 0.f;
-    }
+    for (int i = tid; i < n; i += 256) tt_fresh_row(t, base + i, (unsigned)i, 0, pts[2 * (base + i)], pts[2 * (base + i) + 1]);
     if (tid == 0) {
         t.head[2 * b] = 0; t.head[2 * b + 1] = n;
         int *s = t.stats + (size_t)b * OFK_TT_STATS;
@@ -28,19 +29,14 @@ __global__ __launch_bounds__(256) void k_track_table_replace(ofk_tt_rows t, cons
                                                              const int *__restrict__ new_counts, int stride)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
-    if (limit[b] <= 0) return;
+    if (!rows_stream_on(b, 0, gridDim.x, limit)) return;
     const int n = min(max(new_counts[b], 0), stride);
     const int step = t.head[2 * b];
     const unsigned nid = (unsigned)t.head[2 * b + 1];
     const int before = t.stats[(size_t)b * OFK_TT_STATS];
     const size_t base = (size_t)b * stride;
     __syncthreads();                                            // every thread holds the head before one of them rewrites it
-    for (int i = tid; i < n; i += 256) {
-        const size_t r = base + i;
-        t.ids[r] = nid + (unsigned)i; t.age[r] = 0; t.birth_step[r] = step;
-        t.birth_xy[2 * r] = new_pts[2 * r]; t.birth_xy[2 * r + 1] = new_pts[2 * r + 1];
-        t.flow_xy[2 * r] = 0.f; t.flow_xy[2 * r + 1] = 0.f;
-    }
+    for (int i = tid; i < n; i += 256) tt_fresh_row(t, base + i, nid + (unsigned)i, step, new_pts[2 * (base + i)], new_pts[2 * (base + i) + 1]);
     if (tid == 0) {
         t.head[2 * b + 1] = (int)(nid + (unsigned)n);
         int *s = t.stats + (size_t)b * OFK_TT_STATS;
@@ -48,25 +44,23 @@ __global__ __launch_bounds__(256) void k_track_table_replace(ofk_tt_rows t, cons
     }
 }
 
-// rules 3 and 6, in front of k_update_tracks and with its prefix: the rows of the kept points move up in order, in place, the
-// re-detected corners are appended.  One workgroup per stream.  A chunk of 256 rows is read completely before any of its rows is
-// written, and a row only moves to a position <= its own, so no row is overwritten before it has been read.  The counts are ballots
-// summed per wave and across the waves through LDS; the oldest age is an LDS maximum.
+// rules 3 and 6, in front of k_update_tracks and with its walk (k_rows.inc): the rows of the kept points move up in order, in place,
+// the re-detected corners are appended.  One workgroup per stream.  The seeded count is a ballot summed per wave and across the waves
+// through LDS; the oldest age is an LDS maximum.
 __global__ __launch_bounds__(256) void k_track_table_update(ofk_tt_rows t, const float *__restrict__ prev_pts, const float *__restrict__ next_pts,
                                                             const uint8_t *__restrict__ status, const int *__restrict__ counts_in, int stride,
                                                             const float *__restrict__ new_pts, const int *__restrict__ new_counts,
                                                             int max_total, int seed_on, float gain)
 {
-    __shared__ int s_wave[4], s_seed[4], s_age[256];
-    __shared__ int s_base;
+    __shared__ row_walk s_rows;
+    __shared__ int s_seed[4], s_age[256];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = min(max(counts_in[b], 0), stride);
     const int step = t.head[2 * b];
     const unsigned nid = (unsigned)t.head[2 * b + 1];
     const size_t base = (size_t)b * stride;
     int c_seed = 0, oldest = 0;                                  // wave-uniform / per thread
-    if (tid == 0) s_base = 0;
-    __syncthreads();
+    rows_begin(s_rows);
     for (int i0 = 0; i0 < n; i0 += 256) {
         const int i = i0 + tid;
         const bool in = i < n;
@@ -81,13 +75,7 @@ __global__ __launch_bounds__(256) void k_track_table_update(ofk_tt_rows t, const
         const float sx = px + tx, sy = py + ty;
         const bool seeded = in && seed_on && age >= 1 && fabsf(sx) <= 1e6f && fabsf(sy) <= 1e6f;
         c_seed += __popcll(__ballot(seeded));
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int off = s_base;
-        for (int q = 0; q < wave; ++q) off += s_wave[q];
-        const int pos = off + __popcll(bal & ((1ull << lane) - 1));
-        __syncthreads();                                        // every thread has read the rows of this chunk: safe to overwrite
+        const int pos = rows_place(s_rows, keep);
         if (keep) {
             const size_t w = base + pos;
             t.ids[w] = id; t.age[w] = age + 1; t.birth_step[w] = bs;
@@ -95,17 +83,11 @@ __global__ __launch_bounds__(256) void k_track_table_update(ofk_tt_rows t, const
             t.flow_xy[2 * w] = nx - px; t.flow_xy[2 * w + 1] = ny - py;
             oldest = max(oldest, age + 1);
         }
-        if (tid == 0) s_base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
+        rows_next(s_rows);
     }
-    const int kept = s_base;
-    const int extra = new_counts ? max(0, min(min(new_counts[b], max_total - kept), stride - kept)) : 0;
-    for (int i = tid; i < extra; i += 256) {
-        const size_t w = base + kept + i, q = base + i;
-        t.ids[w] = nid + (unsigned)i; t.age[w] = 0; t.birth_step[w] = step + 1;
-        t.birth_xy[2 * w] = new_pts[2 * q]; t.birth_xy[2 * w + 1] = new_pts[2 * q + 1];
-        t.flow_xy[2 * w] = 0.f; t.flow_xy[2 * w + 1] = 0.f;
-    }
+    const int kept = s_rows.base;
+    const int extra = rows_extra(new_counts, b, max_total, stride, kept);
+    for (int i = tid; i < extra; i += 256) tt_fresh_row(t, base + kept + i, nid + (unsigned)i, step + 1, new_pts[2 * (base + i)], new_pts[2 * (base + i) + 1]);
     s_age[tid] = oldest;
     if (lane == 0) s_seed[wave] = c_seed;
     __syncthreads();

@@ -264,25 +264,31 @@ __global__ __launch_bounds__(256) void k_track_template(tp_state t, const uint8_
 }
 
 // ---------------------------------------------------------------------------------------------- rule 6: compaction
-// In front of k_track_table_update, with its keep rule and its prefix.  One workgroup per stream.  The scalars of a step (A_new,
-// ncc_new, flag_new) move into the state's arrays at the kept rows' new places; tstate moves in place (a chunk is read completely before
-// any of its rows is written, and a row only moves to a position <= its own); the templates move from one buffer into the other, a
-// wave per row in 4-byte words, and the host swaps the two.  The counts are ballots summed per wave and across the waves.
+// A fresh row at index q: no template yet (rule 2 captures one), the identity map, nothing scored.
+__device__ __forceinline__ void tp_fresh_row(const tp_state &t, size_t q)
+{
+    t.A[4 * q] = 1.f; t.A[4 * q + 1] = 0.f; t.A[4 * q + 2] = 0.f; t.A[4 * q + 3] = 1.f;
+    t.ncc[q] = 0.f; t.flag[q] = OFK_TPL_NOT_TRACKED; t.tstate[q] = 0;
+}
+
+// In front of k_track_table_update, with its keep rule and its walk (k_rows.inc).  One workgroup per stream.  The scalars of a step
+// (A_new, ncc_new, flag_new) move into the state's arrays at the kept rows' new places; tstate moves in place; the templates move from
+// one buffer into the other, a wave per row in 4-byte words (the host swaps the two), their places reaching the waves through s_pos behind
+// rows_next's barrier and changing only behind the next rows_place's, when every wave has copied.  The counts are ballots summed per wave.
 __global__ __launch_bounds__(256) void k_track_template_update(tp_state t, const uint8_t *__restrict__ status, const int *__restrict__ counts_in,
                                                                int stride, const int *__restrict__ new_counts, int max_total, tp_cfg cfg,
                                                                double *__restrict__ rec)
 {
-    __shared__ int s_wave[4], s_cnt[4][9], s_pos[256];
+    __shared__ row_walk s_rows;
+    __shared__ int s_cnt[4][9], s_pos[256];
     __shared__ float s_move[4];
-    __shared__ int s_base;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = min(max(counts_in[b], 0), stride);
     const size_t base = (size_t)b * stride;
     const float s2 = (float)(cfg.scale_max * cfg.scale_max), s2i = (float)(1.0 / (cfg.scale_max * cfg.scale_max));
     int cnt[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};                    // scored dropped moved abandoned outside flat captured no-template refresh
     float mv = 0.f;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
+    rows_begin(s_rows);
     for (int i0 = 0; i0 < n; i0 += 256) {
         const int i = i0 + tid;
         const bool in = i < n;
@@ -303,19 +309,14 @@ __global__ __launch_bounds__(256) void k_track_template_update(tp_state t, const
                            in && verdict == OFK_TPL_NO_TEMPLATE, refresh};
 #pragma unroll
         for (int k = 0; k < 9; ++k) cnt[k] += __popcll(__ballot(f[k]));
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int off = s_base;
-        for (int q = 0; q < wave; ++q) off += s_wave[q];
-        const int pos = off + __popcll(bal & ((1ull << lane) - 1));
+        const int pos = rows_place(s_rows, keep);
         s_pos[tid] = keep ? pos : -1;
-        __syncthreads();                                        // every thread has read the rows of this chunk: safe to overwrite
         if (keep) {
             const size_t q = base + pos;
             t.A[4 * q] = a0; t.A[4 * q + 1] = a1; t.A[4 * q + 2] = a2; t.A[4 * q + 3] = a3;
             t.ncc[q] = ncc; t.flag[q] = (uint8_t)fl; t.tstate[q] = (uint8_t)ts;
         }
+        rows_next(s_rows);
         const int words = t.tstride >> 2;
         for (int j = wave; j < 256; j += 4) {
             const int q = s_pos[j];
@@ -324,16 +325,10 @@ __global__ __launch_bounds__(256) void k_track_template_update(tp_state t, const
             uint32_t *dst = (uint32_t *)(t.tmpl_next + (base + q) * t.tstride);
             for (int k = lane; k < words; k += 64) dst[k] = src[k];
         }
-        if (tid == 0) s_base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
     }
-    const int kept = s_base;
-    const int extra = new_counts ? max(0, min(min(new_counts[b], max_total - kept), stride - kept)) : 0;
-    for (int i = tid; i < extra; i += 256) {
-        const size_t q = base + kept + i;
-        t.A[4 * q] = 1.f; t.A[4 * q + 1] = 0.f; t.A[4 * q + 2] = 0.f; t.A[4 * q + 3] = 1.f;
-        t.ncc[q] = 0.f; t.flag[q] = OFK_TPL_NOT_TRACKED; t.tstate[q] = 0;
-    }
+    const int kept = s_rows.base;
+    const int extra = rows_extra(new_counts, b, max_total, stride, kept);
+    for (int i = tid; i < extra; i += 256) tp_fresh_row(t, base + kept + i);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mv = fmaxf(mv, __shfl_xor(mv, o));
     if (lane == 0) {

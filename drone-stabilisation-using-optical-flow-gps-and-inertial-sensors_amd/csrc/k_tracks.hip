@@ -3,6 +3,7 @@
 // few features were left re-detect with a mask of discs around the old positions and append.  gfx950.
 #include "ofk_internal.h"
 #include <stdlib.h>
+#include "k_rows.inc"
 
 // mask := 1, then zero a disc of `radius` around every track (centre = truncated position, dx^2+dy^2 <= r^2).
 // grid (pts_stride, batch); block 256.  Streams whose limit is <= 0 (no re-detection this step) are skipped.
@@ -41,43 +42,34 @@ void ofk_launch_redetect_limits(hipStream_t s, const int *counts, int min_feat, 
     hipLaunchKernelGGL(k_redetect_limits, dim3((batch + 63) / 64), dim3(64), 0, s, counts, min_feat, max_feat, limit, batch);
 }
 
-// tracks := next_pts[status == 1] in order (node:134), then the re-detected corners appended (node:166).  One block per stream.
+// tracks := next_pts[status == 1] in order (node:134), then the re-detected corners appended (node:166).  One block per stream, k_rows.inc's walk.
 __global__ __launch_bounds__(256) void k_update_tracks(const float *__restrict__ next_pts, const uint8_t *__restrict__ status,
                                                        const int *__restrict__ counts_in, int pts_stride,
                                                        const float *__restrict__ new_pts, const int *__restrict__ new_counts,
                                                        float *__restrict__ tracks, int *__restrict__ counts_out, int max_total)
 {
-    __shared__ int s_wave[4];
-    __shared__ int s_base;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ row_walk s_rows;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int n = counts_in[b];
     const float *src = next_pts + (size_t)b * pts_stride * 2;
     const uint8_t *st = status + (size_t)b * pts_stride;
     float *dst = tracks + (size_t)b * pts_stride * 2;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
+    rows_begin(s_rows);
     for (int i0 = 0; i0 < n; i0 += 256) {
         const int i = i0 + tid;
         const bool keep = i < n && st[i] != 0;
         const float x = keep ? src[2 * i] : 0.f, y = keep ? src[2 * i + 1] : 0.f;
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int off = s_base;
-        for (int q = 0; q < wave; ++q) off += s_wave[q];
-        const int pos = off + __popcll(bal & ((1ull << lane) - 1));
-        __syncthreads();                                        // every thread has read the old tracks of this chunk: safe to overwrite
+        const int pos = rows_place(s_rows, keep);
         if (keep) { dst[2 * pos] = x; dst[2 * pos + 1] = y; }
-        if (tid == 0) s_base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
+        rows_next(s_rows);
     }
-    int total = s_base;
-    const int extra = new_counts ? min(new_counts[b], max_total - total) : 0;
+    const int total = s_rows.base;
+    const int extra = rows_extra(new_counts, b, max_total, pts_stride, total);   // pts_stride >= max_total on the stream path: its clamp is idle there
     for (int i = tid; i < extra; i += 256) {
         dst[2 * (total + i)] = new_pts[((size_t)b * pts_stride + i) * 2];
         dst[2 * (total + i) + 1] = new_pts[((size_t)b * pts_stride + i) * 2 + 1];
     }
-    if (tid == 0) counts_out[b] = total + max(extra, 0);
+    if (tid == 0) counts_out[b] = total + extra;
 }
 
 void ofk_launch_update_tracks(hipStream_t s, const float *next_pts, const uint8_t *status, const int *counts_in, int pts_stride,
@@ -94,7 +86,7 @@ __global__ __launch_bounds__(256) void k_replace_tracks(const int *__restrict__ 
                                                         int *__restrict__ counts)
 {
     const int b = blockIdx.x;
-    if (limit[b] <= 0) return;
+    if (!rows_stream_on(b, 0, gridDim.x, limit)) return;
     const int n = max(new_counts[b], 0);
     for (int i = threadIdx.x; i < 2 * n; i += 256) tracks[(size_t)b * pts_stride * 2 + i] = new_pts[(size_t)b * pts_stride * 2 + i];
     if (threadIdx.x == 0) counts[b] = n;

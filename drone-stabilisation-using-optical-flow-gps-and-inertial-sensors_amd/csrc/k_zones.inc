@@ -69,7 +69,8 @@ __global__ __launch_bounds__(256) void k_zones_update(const float *__restrict__ 
     unsigned short *s_lab = (unsigned short *)(s_dyn + 2 * (size_t)pts_stride), *s_idx = s_lab + pts_stride;
     __shared__ int s_vx[OFK_ZONE_MAX][OFK_ZONE_VERTS], s_vy[OFK_ZONE_MAX][OFK_ZONE_VERTS];
     __shared__ int s_nv[OFK_ZONE_MAX], s_ttl[OFK_ZONE_MAX], s_ref[OFK_ZONE_MAX], s_owner[OFK_ZONE_MAX], s_ocnt[OFK_ZONE_MAX];
-    __shared__ int s_wave[4], s_cnt[4][2], s_base, s_flag, s_ins, s_evi;
+    __shared__ row_walk s_rows;
+    __shared__ int s_cnt[4][2], s_flag, s_ins, s_evi;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = max(0, min(counts[b], pts_stride));
     const size_t base = (size_t)b * pts_stride;
@@ -87,10 +88,9 @@ __global__ __launch_bounds__(256) void k_zones_update(const float *__restrict__ 
         const int ttl = tab[tid * OFK_ZONE_INTS];
         s_ttl[tid] = ttl; s_nv[tid] = ttl > 0 ? min(tab[tid * OFK_ZONE_INTS + 1], OFK_ZONE_VERTS) : 0; s_ref[tid] = 0; s_owner[tid] = -1; s_ocnt[tid] = 0;
     }
-    if (tid == 0) s_base = 0;
-    __syncthreads();
+    rows_begin(s_rows);                                          // its barrier also: the zones are in LDS
 
-    // A
+    // A: k_rows.inc's walk, into LDS
     int c_rej = 0, c_abs = 0;                                    // wave-uniform
     for (int i0 = 0; i0 < n; i0 += 256) {
         const int i = i0 + tid;
@@ -103,21 +103,14 @@ __global__ __launch_bounds__(256) void k_zones_update(const float *__restrict__ 
                 if (s_nv[z] > 0 && zone_inside(px, py, s_vx[z], s_vy[z], s_nv[z], set.radius)) { s_ref[z] = 1; absorbed = true; }
         }
         const bool in = rej && !absorbed;
-        const unsigned long long bal = __ballot(in);
         c_rej += __popcll(__ballot(rej)); c_abs += __popcll(__ballot(absorbed));
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int off = s_base;
-        for (int q = 0; q < wave; ++q) off += s_wave[q];
-        const int pos = off + __popcll(bal & ((1ull << lane) - 1));
+        const int pos = rows_place(s_rows, in);
         if (in) { s_xy[pos] = (int)((unsigned)(px & 0xffff) | ((unsigned)py << 16)); s_idx[pos] = (unsigned short)i; s_lab[pos] = (unsigned short)pos; }
-        __syncthreads();
-        if (tid == 0) s_base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
+        rows_next(s_rows);
     }
     if (lane == 0) { s_cnt[wave][0] = c_rej; s_cnt[wave][1] = c_abs; }
     __syncthreads();
-    const int m = s_base;
+    const int m = s_rows.base;
     if (tid < OFK_ZONE_MAX && s_ref[tid]) { s_ttl[tid] = set.ttl; tab[tid * OFK_ZONE_INTS] = set.ttl; }
 
     // B

@@ -3568,7 +3568,11 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     if (zones_on) { TRY(check_zones(c, &c->zones, "ofk_stream_step")); TRY(zones_alloc(c)); }
     TRY(solve_points_prepare(c, B));
     OFK_HIP(c, hipMemcpyAsync(c->sensors, sensors, (size_t)B * OFK_SENSOR_DOUBLES * 8, hipMemcpyHostToDevice, c->stream));
-    double *const bias_ist = bias_on(c) && fu && fu->use_imu ? c->imu_state : nullptr;
+    // the step's omega, ground normal and R_world: the resident IMU state's (imu: for the kernels that choose themselves) or the sensor rows'
+    struct step_source { const double *imu, *omega, *normal, *rw; int stride; };
+    const step_source src = fu && fu->use_imu ? step_source{c->imu_state, c->imu_state + 18, c->imu_state + 15, c->imu_state + 6, OFK_IMU_STATE}
+                                              : step_source{nullptr, c->sensors + 4, c->sensors + 1, c->sensors + 7, OFK_SENSOR_DOUBLES};
+    double *const bias_ist = bias_on(c) && src.imu ? c->imu_state : nullptr;
     if (bias_on(c)) ofk_launch_gyro_bias_apply(c->stream, c->sensors + 4, OFK_SENSOR_DOUBLES, bias_ist, c->bias_rec, B, 0);   // everything below reads omega - b^
     struct bias_restore {                                        // a step that ends early still puts the IMU state's raw omega back
         ofk_ctx *c; double *ist; int B;
@@ -3602,7 +3606,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
     TRY(stream_ingest(c, 1, next_bgr, B, h, w, lv));
     // track (node:133), solve on the tracked points (node:229-258)
     const View v = view_of(c, 0, B, 0);                          // the solve stage reads v.solve_*; the tracks, the zones and the re-detection stay in the image
-    TRY(track(c, c->stream, v, lv, p, fu && fu->use_imu ? c->imu_state : nullptr, flow_seed ? &c->ttr : nullptr, templ ? &c->tpr : nullptr,
+    TRY(track(c, c->stream, v, lv, p, src.imu, flow_seed ? &c->ttr : nullptr, templ ? &c->tpr : nullptr,
               c->ttr.age, keyf ? c->kfr.next_copy : nullptr));
     if (zones_on)                                                // the solve stage turns the status into its keep flags: rule 1 needs both
         OFK_HIP(c, hipMemcpyAsync(c->zone_status, c->status, (size_t)B * c->max_pts, hipMemcpyDeviceToDevice, c->stream));
@@ -3653,7 +3657,7 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
             in.next_pts = !fm_on(c) ? v.solve_next : camera_on(c) || rs_on(c) ? c->kfr.next_copy : v.pts_next;
             in.status = c->status; in.counts = c->counts; in.stride = c->max_pts;
             in.new_counts = any ? c->new_counts : nullptr; in.max_total = p->max_corners; in.sensors = c->sensors;
-            in.imu = fu && fu->use_imu ? c->imu_state : nullptr; in.v = c->records; in.plain = fu ? 0 : 1;
+            in.imu = src.imu; in.v = c->records; in.plain = fu ? 0 : 1;
             in.step = c->ttr.head; in.step_stride = 2;
             ofk_km_rows mr = c->kmr;                             // the depths as the previous step left them: their step is behind this launch
             mr.rho = c->tdr.rho; mr.var = c->tdr.var; mr.nobs = c->tdr.nobs;
@@ -3662,13 +3666,13 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
             launch_key_step(c, c->kfr, in, &c->key, krot ? &c->krot : nullptr, c->kr_st, c->kr_rec, B, kmap ? &c->kmap : nullptr, &mr);
             if (on[TS_POSF])                                     // directly behind it, on the record it has just written
                 ofk_launch_pos_filter_step(c->stream, &c->posf, c->pf_x, c->pf_P, c->pf_ist, c->pf_rec, c->pf_in, c->records, fu ? 0 : 1, c->kfr.rec,
-                                           in.imu ? c->imu_state + 6 : c->sensors + 7, in.imu ? OFK_IMU_STATE : OFK_SENSOR_DOUBLES, B);
+                                           src.rw, src.stride, B);
             if (stab) {                                          // behind both: the view's pose, then the new frame (pyramid slot 1, level 0) into it
                 ofk_stab_in si = {};
                 if (stab_rot) { si.R = c->kr_rec + 4; si.R_stride = OFK_KEYROT_DOUBLES; }
-                else { si.st_copy = c->sb_st; si.omega = in.imu ? c->imu_state + 18 : c->sensors + 4; si.omega_stride = in.imu ? OFK_IMU_STATE : OFK_SENSOR_DOUBLES; }
+                else { si.st_copy = c->sb_st; si.omega = src.omega; si.omega_stride = src.stride; }
                 si.key_rec = c->kfr.rec; si.sensors = c->sensors;
-                si.normal = in.imu ? c->imu_state + 15 : c->sensors + 1; si.normal_stride = in.imu ? OFK_IMU_STATE : OFK_SENSOR_DOUBLES;
+                si.normal = src.normal; si.normal_stride = src.stride;
                 si.cov = c->sb_cov; si.Bv = c->sb_Bv; si.ist = c->sb_ist; si.rec = c->sb_rec; si.M = c->sb_M;
                 ofk_launch_stab_pose(c->stream, si, &c->stab, h, w, B);
                 ofk_launch_warp(c->stream, c->pyr[1], c->pyr_stride, h, w, 1, c->sb_M, c->sb_frames, c->sb_stride, h, w, c->stab.border, c->stab.border_value,
@@ -3677,11 +3681,10 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
             }
         }
         if (depth) {                                             // in front of the table's update, on what k_update_tracks is about to read
-            const bool imu = fu && fu->use_imu;
             ofk_td_in in = {};
             in.prev_pts = v.solve_prev; in.next_pts = v.solve_next; in.status = c->status; in.counts = c->counts; in.stride = c->max_pts;
             in.new_counts = any ? c->new_counts : nullptr; in.max_total = p->max_corners; in.sensors = c->sensors;
-            in.omega = imu ? c->imu_state + 18 : c->sensors + 4; in.omega_stride = imu ? OFK_IMU_STATE : OFK_SENSOR_DOUBLES;
+            in.omega = src.omega; in.omega_stride = src.stride;
             in.v = c->records; in.plain = fu ? 0 : 1;
             ofk_launch_track_depth_step(c->stream, c->tdr, in, &c->td, B);
         }

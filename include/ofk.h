@@ -278,7 +278,8 @@ int ofk_predict_points(ofk_ctx *ctx, const float *pts, const int *counts, int ba
  *      ofk_stream_last_points and the records' points speak of.  The rows with status[i] != 0 are kept in order, status being what
  *      k_update_tracks reads: the keep flags behind the gates, the feasibility rule and the robust drop.  A kept row keeps id and
  *      birth_*, age + 1, flow = next[i] - prev[i] per coordinate, one f32 subtraction of the raw pixels.  Then
- *      extra = max(0, min(new count, max_total - kept)) rows (0 without a re-detection) are appended: id = next_id + j, age = 0,
+ *      extra = max(0, min(new count, max_total - kept, stride - kept)) rows (0 without a re-detection; max_total <= stride wherever
+ *      this runs, so the last term is idle) are appended, as for every other state of the rows: id = next_id + j, age = 0,
  *      birth_step = step + 1, birth_xy = the position, flow = 0.  next_id += extra; step += 1.
  *   4. A held step (ofk_fusion.hold_on_skip, not solved) leaves table, step, next_id, step_ids and the statistics as they were (a
  *      replace in front of it has happened).
