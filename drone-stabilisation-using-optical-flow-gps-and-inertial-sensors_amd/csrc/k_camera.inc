@@ -4,8 +4,7 @@
 // iteration count is a kernel argument, so the loop is wave-uniform.  Nothing is written beyond counts[b]; no atomics, no LDS.  The
 // kernel is latency-bound and tiny (a few hundred points per image): it is not tuned beyond the launch count.
 // src and dst may be the same buffer (the seeds are distorted in place): each thread reads its point before it writes it.
-
-struct cam_xy { double x, y; };
+#include "k_camera_map.inc"                                     // cam_xy, cam_distort: the forward map, shared with the rectifying warp
 
 template <int MODEL> __device__ __forceinline__ cam_xy cam_undistort(const ofk_camera &c, double x0, double y0)
 {
@@ -31,25 +30,6 @@ template <int MODEL> __device__ __forceinline__ cam_xy cam_undistort(const ofk_c
     }
     const double s = td < 1e-8 ? 1.0 : tan(t) / td;
     return {x0 * s, y0 * s};
-}
-
-template <int MODEL> __device__ __forceinline__ cam_xy cam_distort(const ofk_camera &c, double x, double y)
-{
-    if (MODEL == OFK_CAMERA_BROWN) {
-        const double k1 = c.k[0], k2 = c.k[1], p1 = c.k[2], p2 = c.k[3], k3 = c.k[4], k4 = c.k[5], k5 = c.k[6], k6 = c.k[7];
-        const double r2 = x * x + y * y;
-        const double cd = (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1.0 + ((k6 * r2 + k5) * r2 + k4) * r2);
-        const double dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
-        const double dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y;
-        return {x * cd + dx, y * cd + dy};
-    }
-    const double k1 = c.k[0], k2 = c.k[1], k3 = c.k[2], k4 = c.k[3];
-    const double r = sqrt(x * x + y * y);
-    const double t = atan(r);
-    const double t2 = t * t, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
-    const double td = t * (1.0 + k1 * t2 + k2 * t4 + k3 * t6 + k4 * t8);
-    const double s = r < 1e-8 ? 1.0 : td / r;
-    return {x * s, y * s};
 }
 
 // the one rounding to f32 and the fallback: a result LK or the solve could not use is the linear map of the input (lx, ly)

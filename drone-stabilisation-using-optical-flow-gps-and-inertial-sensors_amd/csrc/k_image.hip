@@ -8,7 +8,8 @@
 //             k_pyr_down (other widths): 64x16 output tile / 256-thread block; source tile (136x35) staged into LDS
 //             with dword loads, separable 5-tap pass through a u16 LDS intermediate.
 //   scharr  : 64x16 output tile, 68x18 source tile in LDS, int16x2 (4 B/px) coalesced stores.
-//   warp    : k_warp.inc (included at the end): perspective warp, 4 pixels per lane, byte gathers, dword stores.
+//   warp    : k_warp.inc (included at the end): perspective warp, 4 pixels per lane, byte gathers, dword stores;
+//             k_warp_lens.inc behind it: the same warp with the lens's forward map behind the homography (rectification).
 #include "ofk_internal.h"
 
 __device__ __forceinline__ int reflect101(int i, int n)
@@ -589,3 +590,5 @@ void ofk_launch_scharr(hipStream_t s, const uint8_t *src, size_t src_stride, int
 
 // ------------------------------------------------------------------------------------------------ perspective warp
 #include "k_warp.inc"
+#include "k_camera_map.inc"
+#include "k_warp_lens.inc"

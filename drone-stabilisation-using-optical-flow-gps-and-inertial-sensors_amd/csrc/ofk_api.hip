@@ -167,6 +167,7 @@ extern "C" int ofk_create(int device, int max_w, int max_h, int max_batch, int m
     c->kmap = ofk_keyframe_map{OFK_KEYMAP_OFF, 3, 0.02, 8, 0.5, 1};
     c->posf = ofk_pos_filter{OFK_POSF_OFF, 1.0, 1e-3, 0.0, 1.0, 0.5, 0.0, 1e-3, 0.0, 0.0, 1.0, 0.0, 0.0};
     c->stab = ofk_stabilise{OFK_STAB_OFF, OFK_BORDER_CONSTANT, 0, 0.5, 1};
+    c->rect = ofk_rectify{OFK_RECTIFY_OFF, 0.0};
     // Slice and auxiliary streams are created when a call first needs them (need_streams): the runtime multiplexes HIP streams
     // onto a few hardware queues (4 by default), and two streams of one queue run in order - an idle stream would cost a real one
     // its concurrency.
@@ -2319,6 +2320,46 @@ extern "C" int ofk_camera_download(ofk_ctx *c, float *prev_ideal, float *next_id
     return points_download(c, POINTS[POINTS_CAMERA], "ofk_camera_download", prev_ideal, next_ideal, stride);
 }
 
+// the warp through a lens: ofk_warp_perspective's buffers and checks, ofk_undistort_points' camera checks
+extern "C" int ofk_warp_lens(ofk_ctx *c, const ofk_camera *m, const uint8_t *src, int sh, int sw, int channels, const double *M, uint8_t *dst, int dh,
+                             int dw, int border, int border_value, double r_max, int batch, int *covered)
+{
+    const char *who = "ofk_warp_lens";
+    if (!c) return OFK_E_INVALID;
+    TRY(check_geom(c, batch, sh, sw, "ofk_warp_lens (source)"));
+    TRY(check_geom(c, batch, dh, dw, "ofk_warp_lens (destination)"));
+    if (!m || !src || !dst) return ofk_fail(c, OFK_E_INVALID, "%s: NULL argument", who);
+    if (channels != 1 && channels != 3) return ofk_fail(c, OFK_E_INVALID, "%s: %d channels (1 or 3)", who, channels);
+    if (border != OFK_BORDER_CONSTANT && border != OFK_BORDER_REPLICATE) return ofk_fail(c, OFK_E_INVALID, "%s: unknown border %d", who, border);
+    if (border_value < 0 || border_value > 255) return ofk_fail(c, OFK_E_INVALID, "%s: border_value %d outside 0..255", who, border_value);
+    if (!std::isfinite(r_max) || r_max < 0.0) return ofk_fail(c, OFK_E_INVALID, "%s: r_max = %g is negative or not finite", who, r_max);
+    TRY(check_camera(c, m, false, who));
+    const size_t m_bytes = up((size_t)batch * 9 * sizeof(double), 256);
+    TRY(ofk_need_scratch(c, m_bytes + (size_t)batch * sizeof(int)));
+    double *d_M = M ? (double *)c->scratch : nullptr;
+    int *d_cov = covered ? (int *)((char *)c->scratch + m_bytes) : nullptr;
+    TRY(h2d(c, c->bgr[0], c->bgr_stride, src, (size_t)sh * sw * channels, batch));
+    if (M) OFK_HIP(c, hipMemcpyAsync(d_M, M, (size_t)batch * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    ofk_launch_warp_lens(c->stream, m, r_max, c->bgr[0], c->bgr_stride, sh, sw, channels, d_M, c->bgr[1], c->bgr_stride, dh, dw, border, border_value, d_cov, batch);
+    TRY(check_launch(c, "k_warp_lens_u8"));
+    if (covered) OFK_HIP(c, hipMemcpyAsync(covered, d_cov, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    return d2h(c, dst, c->bgr[1], c->bgr_stride, (size_t)dh * dw * channels, batch);
+}
+
+// ------------------------------------------------------------------------------------------------ rectify setting
+static int check_rectify(ofk_ctx *c, const ofk_rectify *r, const char *who)
+{
+    if (r->mode != OFK_RECTIFY_OFF && r->mode != OFK_RECTIFY_ON) return ofk_fail(c, OFK_E_INVALID, "%s: mode %d is neither OFK_RECTIFY_OFF nor OFK_RECTIFY_ON", who, r->mode);
+    if (!std::isfinite(r->r_max) || r->r_max < 0.0) return ofk_fail(c, OFK_E_INVALID, "%s: r_max = %g is negative or not finite", who, r->r_max);
+    return OFK_OK;
+}
+extern "C" int ofk_set_rectify(ofk_ctx *c, const ofk_rectify *r)
+{
+    return setting_set(c, &ofk_ctx::rect, r && r->mode == OFK_RECTIFY_OFF ? nullptr : r, [](ofk_rectify &s) { s.mode = OFK_RECTIFY_OFF; },
+                       [c](const ofk_rectify *v) { return check_rectify(c, v, "ofk_set_rectify"); });
+}
+extern "C" int ofk_get_rectify(const ofk_ctx *c, ofk_rectify *r) { return setting_get(c, &ofk_ctx::rect, r); }
+
 // ------------------------------------------------------------------------------------------------ rolling-shutter and finite-motion stage entries
 // Both ends of every point through one launch.  Device scratch only, so resident points and settings are not touched; the outputs go
 // up first: entries beyond counts[b] keep their contents.  have: the setting's struct is there; id0 / id1: optional, both or neither;
@@ -2601,9 +2642,10 @@ static int track_check_step(ofk_ctx *c, int variant, const ofk_fusion *fu, const
             if (!TRACK[TS_DEPTH].on(c)) return ofk_fail(c, OFK_E_INVALID, "%s: %s is on without %s: the map is the depth state at the keyframe", who, s.set, TRACK[TS_DEPTH].set);
             if (TRACK[TS_KEYROT].on(c)) return ofk_fail(c, OFK_E_INVALID, "%s: %s is on beside %s: the joint solve over map rows is not built", who, s.set, TRACK[TS_KEYROT].set);
         }
-        if (k == TS_STAB && (camera_on(c) || rs_on(c)))          // the homography holds between ideal global-shutter images
+        // the homography holds between ideal global-shutter images; ofk_set_rectify puts the lens's map behind it, nothing undoes the shutter
+        if (k == TS_STAB && ((camera_on(c) && c->rect.mode == OFK_RECTIFY_OFF) || rs_on(c)))
             return ofk_fail(c, OFK_E_INVALID, "%s: %s is on beside %s: a raw frame needs a remap in front of the warp, which is not built", who, s.set,
-                            camera_on(c) ? "ofk_set_camera" : "ofk_set_rolling_shutter");
+                            camera_on(c) && c->rect.mode == OFK_RECTIFY_OFF ? "ofk_set_camera" : "ofk_set_rolling_shutter");
         if (s.model && (variant == OFK_SOLVE_OFMODULE || (fu && (fu->flow == OFK_FLOW_ROTATIONAL || fu->keep == OFK_KEEP_LEGACY))))
             return refuse_not_sensor_model(c, who, NO_OFMODULE | NO_ROTATIONAL | NO_LEGACY, s.model, s.set);
     }
@@ -3675,8 +3717,12 @@ static int stream_step_impl(ofk_ctx *c, const uint8_t *next_bgr, const double *s
                 si.normal = src.normal; si.normal_stride = src.stride;
                 si.cov = c->sb_cov; si.Bv = c->sb_Bv; si.ist = c->sb_ist; si.rec = c->sb_rec; si.M = c->sb_M;
                 ofk_launch_stab_pose(c->stream, si, &c->stab, h, w, B);
-                ofk_launch_warp(c->stream, c->pyr[1], c->pyr_stride, h, w, 1, c->sb_M, c->sb_frames, c->sb_stride, h, w, c->stab.border, c->stab.border_value,
-                                c->sb_cov, B);
+                if (camera_on(c))                                // accepted with ofk_set_rectify on only: the raw frame through the lens's map
+                    ofk_launch_warp_lens(c->stream, &c->camera, c->rect.r_max, c->pyr[1], c->pyr_stride, h, w, 1, c->sb_M, c->sb_frames, c->sb_stride, h, w,
+                                         c->stab.border, c->stab.border_value, c->sb_cov, B);
+                else
+                    ofk_launch_warp(c->stream, c->pyr[1], c->pyr_stride, h, w, 1, c->sb_M, c->sb_frames, c->sb_stride, h, w, c->stab.border, c->stab.border_value,
+                                    c->sb_cov, B);
                 c->sb_h = h; c->sb_w = w;
             }
         }

@@ -187,6 +187,7 @@ struct ofk_ctx {
     int *pf_ist;                             // [max_batch][OFK_POSF_INTS]
     int pf_batch, pf_live;                   // streams of the latest step with the position filter on (ofk_pos_filter_download), 0 = none; streams whose filter runs on
     ofk_stabilise stab;                      // ofk_set_stabilise: mode OFK_STAB_OFF unless set
+    ofk_rectify rect;                        // ofk_set_rectify: mode OFK_RECTIFY_OFF unless set; with it and the camera on the view's warp is k_warp_lens_u8
     double *sb_Bv, *sb_rec, *sb_M, *sb_st;   // [max_batch][9], [max_batch][OFK_STAB_DOUBLES], [max_batch][9], [max_batch][OFK_KEY_STATE] (the keyframe's state in front of its launch); one lazy allocation (sb_Bv owns it)
     int *sb_ist, *sb_cov;                    // [max_batch][OFK_STAB_INTS], [max_batch] covered pixels of the latest warp
     uint8_t *sb_frames; size_t sb_stride;    // [max_batch][sb_stride] the stabilised frames, 256-B aligned per image (an allocation of its own, made by the first step with the setting on)
@@ -253,6 +254,10 @@ void ofk_launch_scharr(hipStream_t s, const uint8_t *src, size_t src_stride, int
 // 4-byte aligned; covered [batch] i32 is zeroed and counted, NULL = not counted
 void ofk_launch_warp(hipStream_t s, const uint8_t *src, size_t src_stride, int sh, int sw, int ch, const double *M, uint8_t *dst,
                      size_t dst_stride, int dh, int dw, int border, int bval, int *covered, int batch);
+// the same warp through a lens (ofk.h: ofk_warp_lens; k_warp_lens.inc): M maps a destination pixel to an IDEAL pixel of `cam`, NULL = the
+// identity; cam->model BROWN or FISHEYE; r_max 0 = no limit
+void ofk_launch_warp_lens(hipStream_t s, const ofk_camera *cam, double r_max, const uint8_t *src, size_t src_stride, int sh, int sw, int ch,
+                          const double *M, uint8_t *dst, size_t dst_stride, int dh, int dw, int border, int bval, int *covered, int batch);
 int  ofk_launch_mineig(hipStream_t s, const uint8_t *gray, size_t gray_stride, int h, int w, int block, float *eig,
                        size_t eig_stride, unsigned int *maxbits, const uint8_t *mask, size_t mask_stride, int batch);
 void ofk_launch_maxbits(hipStream_t s, const float *eig, size_t eig_stride, const uint8_t *mask, size_t mask_stride,

@@ -190,8 +190,46 @@ def undistortPoints(src, cameraMatrix, distCoeffs, R=None, P=None, criteria=None
     return _lens_points("undistortPoints", False, "brown", src, cameraMatrix, k, P, iters)
 
 
+def _lens_image(who, model, src, K, k, Knew, dsize, flags, dst=None):
+    if int(flags) != INTER_LINEAR:
+        raise NotImplementedError(f"{who}: INTER_LINEAR only (other interpolations are out of scope)")
+    src = np.asarray(src)
+    if src.dtype != np.uint8 or not (src.ndim == 2 or (src.ndim == 3 and src.shape[2] in (1, 3))) or 0 in src.shape:
+        raise ValueError(f"{who} expects an HxW, HxWx1 or HxWx3 uint8 image")
+    fx, fy, cx, cy = _camera_matrix(K, "cameraMatrix")
+    fo_x, fo_y, co_x, co_y = (fx, fy, cx, cy) if Knew is None else _camera_matrix(Knew, "newCameraMatrix")
+    cam = ofk.camera_setting(model, fx, fy, cx, cy, k, None, fo_x, fo_y, co_x, co_y)
+    h, w = src.shape[:2] if dsize is None else (int(dsize[1]), int(dsize[0]))
+    if dst is not None and not (isinstance(dst, np.ndarray) and dst.dtype == np.uint8 and dst.shape == (h, w) + src.shape[2:]):
+        raise ValueError(f"{who}: dst must be a uint8 array of the result's shape {(h, w) + src.shape[2:]}")
+    ctx = ofk.default_context(max(w, src.shape[1]), max(h, src.shape[0]))
+    img = src[:, :, 0] if src.ndim == 3 and src.shape[2] == 1 else src
+    out = ctx.warp_lens(img, cam, None, (h, w))[0].reshape((h, w) + src.shape[2:])
+    if dst is None:
+        return out
+    dst[...] = out                                               # cv2 fills a dst of the right size and type in place and returns it
+    return dst
+
+
+def undistort(src, cameraMatrix, distCoeffs, dst=None, newCameraMatrix=None, *, flags=INTER_LINEAR):
+    """cv2.undistort for HxW or HxWx3 uint8 images: the image rectified into newCameraMatrix (None = cameraMatrix), same size, constant
+    border 0 (ofk.h: ofk_warp_lens states the rule; it is the project's, not cv2's block-wise fixed-point map).  4, 5 or 8 distortion
+    coefficients; a skewed matrix is refused; a dst of the result's shape and type is filled and returned, any other is refused.  flags
+    is not cv2's: it is here to refuse an interpolation other than INTER_LINEAR."""
+    k = [] if distCoeffs is None else np.asarray(distCoeffs, np.float64).reshape(-1)
+    if len(k) not in (0, 4, 5, 8):
+        raise ValueError(f"undistort: {len(k)} distortion coefficients (4, 5 or 8 are supported)")
+    return _lens_image("undistort", "brown", src, cameraMatrix, k, newCameraMatrix, None, flags, dst)
+
+
 class fisheye:
-    """cv2.fisheye's point functions (the equidistant model, D = k1..k4)."""
+    """cv2.fisheye's point functions and undistortImage (the equidistant model, D = k1..k4)."""
+
+    @staticmethod
+    def undistortImage(distorted, K, D, Knew=None, new_size=None, *, flags=INTER_LINEAR):
+        """cv2.fisheye.undistortImage: the fisheye image rectified into Knew, new_size = (width, height) (None: the source's).  Knew
+        None = K here (cv2's default, the identity matrix, leaves a view one pixel wide).  flags as in undistort."""
+        return _lens_image("fisheye.undistortImage", "fisheye", distorted, K, fisheye._d(D, "undistortImage"), Knew, new_size, flags)
 
     @staticmethod
     def _d(D, who):

@@ -25,7 +25,7 @@ STAGES = ("gray", "pyr", "eig", "nms", "select", "lk", "solve")
 # every entry point include/ofk.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = (
     "ofk_version", "ofk_last_error", "ofk_device_count", "ofk_create", "ofk_destroy", "ofk_sync", "ofk_device_sync",
-    "ofk_gray_bgr8", "ofk_pyr_down_u8", "ofk_pyramid_u8", "ofk_scharr_s16", "ofk_warp_perspective", "ofk_mineig_response", "ofk_select_corners",
+    "ofk_gray_bgr8", "ofk_pyr_down_u8", "ofk_pyramid_u8", "ofk_scharr_s16", "ofk_warp_perspective", "ofk_warp_lens", "ofk_mineig_response", "ofk_select_corners",
     "ofk_good_features", "ofk_lk_pyr", "ofk_lk_pyr_ex", "ofk_predict_points", "ofk_set_lk_seed", "ofk_get_lk_seed", "ofk_flow_model", "ofk_feasibility", "ofk_velocity_solve", "ofk_imu_propagate",
     "ofk_set_robust", "ofk_get_robust", "ofk_robust_download", "ofk_velocity_solve_robust", "ofk_robust_pairs",
     "ofk_set_cov", "ofk_get_cov", "ofk_cov_download", "ofk_velocity_solve_cov",
@@ -47,6 +47,7 @@ SYMBOLS = (
     "ofk_set_keyframe_map", "ofk_get_keyframe_map", "ofk_keyframe_map_download", "ofk_keyframe_map_step",
     "ofk_set_pos_filter", "ofk_get_pos_filter", "ofk_pos_filter_input", "ofk_pos_filter_reset", "ofk_pos_filter_download", "ofk_pos_filter_step",
     "ofk_set_stabilise", "ofk_get_stabilise", "ofk_stab_download", "ofk_stab_frames", "ofk_stab_reset", "ofk_stab_pose",
+    "ofk_set_rectify", "ofk_get_rectify",
     "ofk_set_track_template", "ofk_get_track_template", "ofk_track_template_download", "ofk_track_affine_fit", "ofk_track_template_step",
     "ofk_post_solve", "ofk_kf_predict_update", "ofk_of_simulation", "ofk_of_simulation_rng", "ofk_noise_normals", "ofk_feas_simulation", "ofk_hist_overlap", "ofk_associate_sensors", "ofk_feature_eval", "ofk_d_split", "ofk_pairs_upload", "ofk_pairs_upload_jpeg", "ofk_jpeg_stage", "ofk_jpeg_stage_error", "ofk_pairs_upload_staged", "ofk_jpeg_info", "ofk_jpeg_destuff", "ofk_jpeg_decode_bgr8", "ofk_jpeg_last_iterations", "ofk_pairs_set_sensors",
     "ofk_pairs_run", "ofk_pairs_download", "ofk_pairs_export_records_f32", "ofk_stream_begin", "ofk_stream_step",
@@ -133,6 +134,7 @@ POSF_OFF, POSF_ON = 0, 1                                 # ofk_set_pos_filter
 POSF_STATES, POSF_INPUT, POSF_INTS, POSF_DOUBLES = 12, 12, 16, 48   # x = (p, v, b, c); the input row; the counts; the record
 POSF_NOT, POSF_APPLIED, POSF_GATED, POSF_REFUSED = 0, 1, 2, 3       # an update's outcome in the record
 STAB_OFF, STAB_ROTATION, STAB_PLANE = 0, 1, 2            # ofk_set_stabilise
+RECTIFY_OFF, RECTIFY_ON = 0, 1                           # ofk_set_rectify
 STAB_MODES = {"off": STAB_OFF, "rotation": STAB_ROTATION, "plane": STAB_PLANE}
 STAB_DOUBLES, STAB_INTS = 48, 4                          # the record; steps since the last re-base, re-bases, approx, a previous warp exists
 STAB_NONE, STAB_ROTATION_ONLY, STAB_FULL = 0, 1, 2       # the record's flag
@@ -668,6 +670,23 @@ def stabilise_setting(mode=True, border=BORDER_CONSTANT, border_value=0, min_cov
     return m
 
 
+class Rectify(C.Structure):
+    """ofk_rectify (include/ofk.h): the stabilised view of a stream behind a lens, resampled through the lens's forward map."""
+    _fields_ = [("mode", C.c_int), ("r_max", C.c_double)]
+
+
+def rectify_setting(mode=True, r_max=0.0):
+    """A Rectify structure from names: mode True / False or RECTIFY_*; r_max the largest ideal normalised radius that is sampled
+    (0: no bound) - 1.05 * CameraModel.ideal_radius(h, w) keeps a folding Brown polynomial out of the view."""
+    mode = RECTIFY_ON if mode is True else RECTIFY_OFF if mode is False else int(mode)
+    if mode not in (RECTIFY_OFF, RECTIFY_ON):
+        raise ValueError(f"rectify mode {mode} is neither RECTIFY_OFF nor RECTIFY_ON")
+    r = Rectify(mode, float(r_max))
+    if mode != RECTIFY_OFF and not (np.isfinite(r.r_max) and r.r_max >= 0):
+        raise ValueError(f"rectify r_max {r.r_max} is negative or not finite")
+    return r
+
+
 class Fusion(C.Structure):
     """ofk_fusion (include/ofk.h): what ofk_stream_step_fused does between LK and the next frame."""
     _fields_ = [("use_imu", C.c_int), ("flow", C.c_int), ("keep", C.c_int), ("filter", C.c_int), ("control", C.c_int),
@@ -679,7 +698,7 @@ class Fusion(C.Structure):
 SETTINGS = (("robust", Robust), ("cov", Cov), ("joint", Joint), ("gyro_bias", GyroBias), ("plane", Plane), ("epipolar", Epipolar), ("track_gate", TrackGate), ("lk_light", LkLight),
             ("corner_grid", CornerGrid), ("zones", Zones), ("camera", Camera), ("rolling_shutter", RShutter), ("finite_motion", FiniteMotion),
             ("track_table", TrackTable), ("track_depth", TrackDepth), ("track_template", TrackTemplate), ("keyframe", Keyframe),
-            ("keyframe_rotation", KeyframeRotation), ("keyframe_map", KeyframeMap), ("pos_filter", PosFilter), ("stabilise", Stabilise))
+            ("keyframe_rotation", KeyframeRotation), ("keyframe_map", KeyframeMap), ("pos_filter", PosFilter), ("stabilise", Stabilise), ("rectify", Rectify))
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -736,6 +755,7 @@ def load_library():
         L.ofk_pyramid_u8.argtypes = [vp, vp, i, i, i, i, vp, C.POINTER(i)]
         L.ofk_scharr_s16.argtypes = [vp, vp, i, i, i, vp]
         L.ofk_warp_perspective.argtypes = [vp, vp, i, i, i, vp, vp, i, i, i, i, i, vp]
+        L.ofk_warp_lens.argtypes = [vp, C.POINTER(Camera), vp, i, i, i, vp, vp, i, i, i, i, d, i, vp]
         L.ofk_mineig_response.argtypes = [vp, vp, i, i, i, i, vp]
         L.ofk_select_corners.argtypes = [vp, vp, vp, i, i, i, i, d, d, vp, vp]
         L.ofk_good_features.argtypes = [vp, vp, vp, i, i, i, i, d, d, i, vp, vp]
@@ -1059,6 +1079,41 @@ class Context:
         covered = np.zeros(B, np.int32)
         with self._lock:
             self._ck(self._L.ofk_warp_perspective(self._h, _p(src), sh, sw, ch, _p(M), _p(out), dh, dw, mode, int(border_value), B, _p(covered)))
+        return (out[0], int(covered[0])) if single else (out, covered)
+
+    def warp_lens(self, src, camera, M=None, dsize=None, border="constant", border_value=0, r_max=0.0):
+        """ofk_warp_lens: the warp of raw images of `camera` (a Camera; fo_x != fo_y is accepted) through the lens's forward map, M
+        mapping a DESTINATION pixel to an IDEAL pixel of the camera's output matrix (ofk.h states the rule).  Layouts as
+        warp_perspective.  M None: the identity for every image, plain rectification (cv2.undistort); then src [h,w] or [h,w,3] is one
+        image and [B,h,w,C] (or [B,h,w] with w != 3) a batch.  r_max: ideal normalised radius beyond which a pixel is border (0: no
+        bound).  -> (dst in src's layout, covered)."""
+        src = _arr(src, np.uint8)
+        if M is None:
+            single = src.ndim == 2 or (src.ndim == 3 and src.shape[2] == 3)
+        else:
+            M = _arr(M, np.float64)
+            single = M.shape == (3, 3)
+            if single:
+                M = M[None]
+            if M.ndim != 3 or M.shape[1:] != (3, 3):
+                raise ValueError(f"warp_lens: M {M.shape} is neither [3,3] nor [B,3,3]")
+        if single:
+            src = src[None]
+        if src.ndim not in (3, 4) or 0 in src.shape or (M is not None and src.shape[0] != M.shape[0]):
+            raise ValueError(f"warp_lens: src {src.shape} does not hold one [h,w] or [h,w,C] image per matrix")
+        ch = src.shape[3] if src.ndim == 4 else 1
+        if ch not in (1, 3):
+            raise ValueError(f"warp_lens: {ch} channels (1 or 3)")
+        B, sh, sw = src.shape[:3]
+        dh, dw = (sh, sw) if dsize is None else (int(dsize[0]), int(dsize[1]))
+        if dh < 1 or dw < 1:
+            raise ValueError(f"warp_lens: dsize {dsize}")
+        mode = BORDERS[border] if isinstance(border, str) else int(border)
+        out = np.empty((B, dh, dw) + src.shape[3:], np.uint8)
+        covered = np.zeros(B, np.int32)
+        with self._lock:
+            self._ck(self._L.ofk_warp_lens(self._h, C.byref(camera), _p(src), sh, sw, ch, _p(M), _p(out), dh, dw, mode, int(border_value), float(r_max), B,
+                                           _p(covered)))
         return (out[0], int(covered[0])) if single else (out, covered)
 
     def mineig(self, gray, block_size):
@@ -1534,6 +1589,14 @@ class Context:
 
     def get_stabilise(self):
         return self._get_struct(self._L.ofk_get_stabilise, Stabilise)
+
+    def set_rectify(self, rectify=None, **settings):
+        """ofk_set_rectify: a Rectify (or rectify_setting's keywords); None or mode False switches it off.  With it and set_camera on,
+        a stream step with set_stabilise on is accepted and warps its raw frame through the lens's map into the ideal view."""
+        self._set_struct(self._L.ofk_set_rectify, rectify, settings, rectify_setting, lock=True)
+
+    def get_rectify(self):
+        return self._get_struct(self._L.ofk_get_rectify, Rectify)
 
     def stab_reset(self, stream):
         """ofk_stab_reset: the view of active stream `stream` starts over at the identity with its next step."""

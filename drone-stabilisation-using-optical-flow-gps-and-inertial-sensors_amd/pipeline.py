@@ -41,6 +41,41 @@ class CameraModel:
         m = self.setting()
         return 1.0 / m.fo_x, m.co_x, m.co_y
 
+    def ideal_radius(self, h, w):
+        """The largest ideal normalised radius over the border pixels of the raw h x w frame (the undistort rule of ofk.h on the host,
+        float64, the setting's iteration count): what the lens sees at most.  ofk.rectify_setting(r_max=1.05 * cam.ideal_radius(h, w))
+        keeps ideal points beyond it, where a Brown polynomial folds back into the frame, out of a rectified view."""
+        m = self.setting()
+        xs, ys = np.arange(int(w), dtype=np.float64), np.arange(int(h), dtype=np.float64)
+        px = np.concatenate([xs, xs, np.zeros(len(ys)), np.full(len(ys), float(w - 1))])
+        py = np.concatenate([np.zeros(len(xs)), np.full(len(xs), float(h - 1)), ys, ys])
+        x0, y0 = (px - m.cx) / m.fx, (py - m.cy) / m.fy
+        k = list(m.k)
+        with np.errstate(all="ignore"):
+            if m.model == ofk.CAMERA_BROWN:
+                k1, k2, p1, p2, k3, k4, k5, k6 = k
+                x, y = x0.copy(), y0.copy()
+                for _ in range(m.iters):
+                    r2 = x * x + y * y
+                    icd = (1.0 + ((k6 * r2 + k5) * r2 + k4) * r2) / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2)
+                    dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+                    dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+                    x, y = (x0 - dx) * icd, (y0 - dy) * icd
+            else:
+                k1, k2, k3, k4 = k[:4]
+                td = np.sqrt(x0 * x0 + y0 * y0)
+                t = td.copy()
+                for _ in range(m.iters):
+                    t2 = t * t; t4 = t2 * t2; t6 = t4 * t2; t8 = t4 * t4
+                    t = t - (t * (1.0 + k1 * t2 + k2 * t4 + k3 * t6 + k4 * t8) - td) / (1.0 + 3.0 * k1 * t2 + 5.0 * k2 * t4 + 7.0 * k3 * t6 + 9.0 * k4 * t8)
+                s = np.where(td < 1e-8, 1.0, np.tan(t) / td)
+                x, y = x0 * s, y0 * s
+            r = float(np.sqrt(x * x + y * y).max())
+        if not np.isfinite(r):
+            raise ValueError(f"ideal_radius: the undistort iteration of this lens does not stay finite on the border of a {w} x {h} frame "
+                             f"(the model does not cover the frame): choose r_max by hand")
+        return r
+
 
 @dataclass
 class RollingShutter:
@@ -189,9 +224,13 @@ class PipelineConfig:
     # displacement, the step's velocity and position fixes in a filter with a cloned state; it needs keyframe on; FlowPipeline ignores it
     pos_filter: object = None
     # stabilise (ofk.h: ofk_set_stabilise): None, True (the defaults) or an ofk.Stabilise: every stream step leaves the step's new gray
-    # frame warped into the view of the stream's keyframe on the device; it needs keyframe on and neither a camera model nor a
-    # rolling shutter; FlowPipeline ignores it
+    # frame warped into the view of the stream's keyframe on the device; it needs keyframe on and no rolling shutter, and beside a
+    # camera model it needs rectify on; FlowPipeline ignores it
     stabilise: object = None
+    # rectify (ofk.h: ofk_set_rectify): None, True (the defaults) or an ofk.Rectify: with a camera model on, the stabilised view is
+    # accepted and every step's raw frame is warped through the lens's forward map into the ideal view; inert without a camera or
+    # without stabilise; FlowPipeline ignores it
+    rectify: object = None
 
     # the three parameter sets the reference carries inline
     @classmethod
@@ -344,9 +383,15 @@ class PipelineConfig:
         m = self._struct_setting("stabilise", ofk.Stabilise, ofk.stabilise_setting)
         if m is not None and self.keyframe_setting() is None:
             raise ValueError("stabilise needs keyframe on")
-        if m is not None and (self.camera_setting() is not None or self.rolling_shutter_setting() is not None):
-            raise ValueError("stabilise beside a camera model or a rolling shutter: a raw frame needs a remap in front of the warp, which is not built")
+        if m is not None and self.rolling_shutter_setting() is not None:
+            raise ValueError("stabilise beside a rolling shutter: the homography holds between global-shutter images, and nothing undoes the row time in the frame")
+        if m is not None and self.camera_setting() is not None and self.rectify_setting() is None:
+            raise ValueError("stabilise beside a camera model without rectify: a raw frame needs the lens's map behind the warp (rectify=True)")
         return m
+
+    def rectify_setting(self):
+        """The ofk.Rectify structure of this configuration, None when the view is not resampled through the lens."""
+        return self._struct_setting("rectify", ofk.Rectify, ofk.rectify_setting)
 
     def track_template_setting(self):
         """The ofk.TrackTemplate structure of this configuration, None when the templates are off."""
@@ -473,7 +518,7 @@ def _apply_settings(ctx, cfg, zones):
                   (ctx.set_track_depth, cfg.track_depth_setting), (ctx.set_track_template, cfg.track_template_setting),
                   (ctx.set_keyframe, cfg.keyframe_setting), (ctx.set_keyframe_rotation, cfg.keyframe_rotation_setting),
                   (ctx.set_keyframe_map, cfg.keyframe_map_setting), (ctx.set_pos_filter, cfg.pos_filter_setting),
-                  (ctx.set_stabilise, cfg.stabilise_setting)]
+                  (ctx.set_rectify, cfg.rectify_setting), (ctx.set_stabilise, cfg.stabilise_setting)]
     steps += [(ctx.set_camera, cfg.camera_setting), (ctx.set_rolling_shutter, cfg.rolling_shutter_setting),
               (ctx.set_finite_motion, cfg.finite_motion_setting)]
     for setter, setting in steps:                                # every *_setting() is None when its setting is off

@@ -259,6 +259,17 @@ def stabilise_step(R, key_rec, sensors, h, w, state=None, normal=None, prev_cove
     return dict(Bv=out["Bv"][0], ints=out["ints"][0]), rec[0]
 
 
+def rectify_frame(frame, camera, M=None, dsize=None, border="constant", border_value=0, r_max=0.0):
+    """A raw frame of `camera` (a pipeline.CameraModel, an ofk.Camera or a dict of CameraModel's fields) rectified on the device (ofk.h:
+    ofk_warp_lens): frame [h,w] or [h,w,3] uint8; M [3,3] maps a pixel of the output to an IDEAL pixel of the camera (None: the identity,
+    cv2.undistort's result); dsize (height, width), None = the frame's; r_max: ideal normalised radius beyond which a pixel is border,
+    e.g. 1.05 * camera.ideal_radius(h, w).  Returns (image in the frame's layout, covered pixels)."""
+    cam = camera if isinstance(camera, ofk.Camera) else (camera if isinstance(camera, CameraModel) else CameraModel(**dict(camera))).setting()
+    frame = np.asarray(frame, np.uint8)
+    h, w = frame.shape[:2] if dsize is None else dsize
+    return ofk.default_context(max(int(w), frame.shape[1]), max(int(h), frame.shape[0])).warp_lens(frame, cam, M, dsize, border, border_value, r_max)
+
+
 def pos_filter_step(v_uav, key_rec, R_world=None, state=None, solved=True, du=None, fix=None, fix_sigma=None, **settings):
     """One step of a stream's position filter without images (ofk.h: ofk_pos_filter_step): predict, the velocity, displacement and fix
     updates, the clone at a re-key.  v_uav [3], solved: the step record's fields 8-10 and its solved flag; key_rec [32]: the
@@ -410,6 +421,7 @@ class optical_fusion:
     _pos_filter = {}                                             # PipelineConfig's pos_filter field; empty: no position filter
     _keyframe_map = {}                                           # PipelineConfig's keyframe_map field; empty: the key solve is the plane's
     _stabilise = {}                                              # PipelineConfig's stabilise field; empty: no stabilised view
+    _rectify = {}                                                # PipelineConfig's rectify field; empty: the view is not resampled through the lens
     _fix = None                                                  # (position, sigma) of call_fix, handed to the filter with the next frame
     _keyframe = {}                                               # PipelineConfig's keyframe field; empty: no position against a keyframe
     _track_template = {}                                         # PipelineConfig's track_template field; empty: no template per track
@@ -571,7 +583,7 @@ class optical_fusion:
                                  **self._cov, **self._joint, **self._plane, **self._epipolar, **self._zones, **self._camera, **self._rolling_shutter,
                                  **self._finite_motion, **self._gyro_bias, **self._lk_light, **self._track_table, **self._track_depth,
                                  **self._track_template, **self._keyframe, **self._keyframe_rotation, **self._pos_filter,
-                                 **self._keyframe_map, **self._stabilise)
+                                 **self._keyframe_map, **self._stabilise, **self._rectify)
             self._stream = FlowStream(w, h, batch=1, cfg=cfg, device=int(os.environ.get("OFK_DEVICE", "0")), min_features=int(self.min_feat),
                                       mask_radius=30, fusion=FusionConfig.node())
             self._stream_dim = (h, w)
@@ -708,7 +720,7 @@ class optical_fusion:
     def __init__(self, spin=True, synthetic_test=True, robust=None, track_gate=None, corner_grid=None, cov=None, zones=None, camera=None,
                  rolling_shutter=None, joint=None, plane=None, finite_motion=None, epipolar=None, gyro_bias=None, lk_light=None,
                  track_table=None, track_depth=None, track_template=None, keyframe=None, keyframe_rotation=None, pos_filter=None,
-                 keyframe_map=None, stabilise=None):
+                 keyframe_map=None, stabilise=None, rectify=None):
         """robust: None (the reference's plain solve) or a dict of PipelineConfig's robust_* settings without the prefix, e.g.
         dict(loss="tukey", hypotheses=64, drop=True): the restored pipeline then solves robustly (ofk.h: ofk_set_robust).
         track_gate: None (every point LK reports as tracked is used) or a dict of ofk.track_gate_setting's keywords, e.g.
@@ -783,7 +795,10 @@ class optical_fusion:
         stabilise: None (no stabilised view), True, an ofk.Stabilise or a dict of ofk.stabilise_setting's keywords, e.g.
         dict(mode="rotation", min_cover=0.7): every frame's step then leaves the gray frame warped into the view of the stream's first
         keyframe (ofk.h: ofk_set_stabilise); it switches the keyframe and the track table on when they are None and does not go with a
-        camera model or a rolling shutter.  self.last_stabilised is FlowStream.stabilised()'s dictionary for the one stream."""
+        rolling shutter, nor with a camera model unless rectify is on.  self.last_stabilised is FlowStream.stabilised()'s dictionary
+        for the one stream.
+        rectify: None, True, an ofk.Rectify or a dict of ofk.rectify_setting's keywords, e.g. dict(r_max=1.3): with a camera model the
+        stabilised view is accepted and every raw frame is warped through the lens's forward map into it (ofk.h: ofk_set_rectify)."""
         self._lock = threading.RLock()
         r = dict(robust or {})
         self._robust = dict(robust=r.pop("loss", "tukey"), **{"robust_" + k: v for k, v in r.items()}) if robust else {}
@@ -872,12 +887,13 @@ class optical_fusion:
         if keyframe_map is not None and keyframe_map is not False:   # the map is the depths', frozen at the keyframe
             keyframe = True if keyframe is None else keyframe
             track_depth = True if track_depth is None else track_depth
+        self._rectify = _struct_field("rectify", rectify)
         given = dict(track_table=track_table, track_depth=track_depth, track_template=track_template, keyframe=keyframe,
                      keyframe_rotation=keyframe_rotation, pos_filter=pos_filter, keyframe_map=keyframe_map, stabilise=stabilise)
         for name, value in given.items():                        # the rotation's, the filter's and the map's checks read the keyframe, set in front of them
             beside = self._keyframe if name in ("keyframe_rotation", "pos_filter") else {}
             if name == "stabilise":
-                beside = dict(**self._keyframe, **self._camera, **self._rolling_shutter)
+                beside = dict(**self._keyframe, **self._camera, **self._rolling_shutter, **self._rectify)
             if name == "keyframe_map":
                 beside = dict(**self._keyframe, **self._track_depth, **self._keyframe_rotation)
             setattr(self, "_" + name, _struct_field(name, value, **beside))

@@ -98,6 +98,32 @@ int ofk_scharr_s16(ofk_ctx *ctx, const uint8_t *gray, int batch, int h, int w, i
 int ofk_warp_perspective(ofk_ctx *ctx, const uint8_t *src, int sh, int sw, int channels, const double *M, uint8_t *dst, int dh, int dw,
                          int border, int border_value, int batch, int *covered);
 
+/* The same warp through a lens: image rectification (cv2.undistort, cv2.fisheye.undistortImage) and, with a matrix, the warp of a raw
+ * frame into an ideal view - one kernel, k_warp_lens_u8: the perspective warp with the lens's forward map behind the homography.
+ * src [batch][sh][sw][channels] u8, the RAW images of camera `cam` -> dst [batch][dh][dw][channels] u8; channels 1 or 3.  M [batch][9]
+ * f64 maps a DESTINATION pixel to an IDEAL pixel of the source camera, i.e. a pixel of the output matrix (fo_x, fo_y, co_x, co_y) of
+ * `cam`; M == NULL is the identity for every image: plain rectification into that matrix.  One camera per call.
+ * The rule, per destination pixel with integer (x, y); all f64, every product and sum rounded on its own (no contraction), in this order:
+ *   1. Normalised matrix, once per image: Mn[0..2] = (M[0..2] - co_x M[6..8]) / fo_x, Mn[3..5] = (M[3..5] - co_y M[6..8]) / fo_y,
+ *      Mn[6..8] = M[6..8].
+ *   2. X = (Mn0 x + Mn1 y) + Mn2, Y and W alike.  iw = (W != 0) ? 1.0 / W : 0.0 - no test on the sign of W, as in the plain warp.
+ *      xn = X iw, yn = Y iw: the ideal normalised coordinates.
+ *   3. (xd, yd) = the forward map of ofk_set_camera ("Distort") on (xn, yn), its expressions unchanged.  Where the Brown model's k4, k5
+ *      and k6 (k[5..7]) are all 0 the divide by the denominator, which is exactly 1.0, is left out; no bit of the frame depends on it.
+ *   4. fx = (xd cam.fx + cam.cx) 32, fy = (yd cam.fy + cam.cy) 32.
+ *   5. A pixel is OUTSIDE unless |fx| <= 2^30 and |fy| <= 2^30 (false for NaN) and, where r_max > 0, xn xn + yn yn <= r_max r_max
+ *      (false for NaN).  An outside pixel gets border_value in every channel, under either border mode, and is not covered.  r_max
+ *      bounds the ideal radius: a Brown polynomial with k1 < 0 folds back far outside the field of view, and ideal points out there
+ *      would sample the inside of the raw frame (cv2.undistort shows that artefact).  0: no bound.
+ *   6. Steps 4-7 of ofk_warp_perspective on (fx, fy): rint to even, 5 fractional bits, four taps, (sum + 512) >> 10, the border per
+ *      tap, covered = not outside and all four taps inside.  The same device code.
+ * Parity with cv2 is not claimed (cv2 interpolates a block-wise fixed-point map); this rule defines the result.
+ * OFK_E_INVALID before any launch: ofk_warp_perspective's refusals (M may be NULL here); a NULL cam or one ofk_undistort_points would
+ * refuse (model OFK_CAMERA_OFF included; fo_x != fo_y is accepted); r_max negative or not finite.  It touches no resident state. */
+struct ofk_camera;                                              /* defined with ofk_set_camera, below */
+int ofk_warp_lens(ofk_ctx *ctx, const struct ofk_camera *cam, const uint8_t *src, int sh, int sw, int channels, const double *M, uint8_t *dst,
+                  int dh, int dw, int border, int border_value, double r_max, int batch, int *covered);
+
 /* Shi-Tomasi response inside cv2.goodFeaturesToTrack (of_module.py:44,86; node:120,163; evaluate_exp.py:66,106;
  * of_library.py:238): Sobel-3 -> structure tensor box(block_size) -> min eigenvalue, f32 map [batch][h][w].
  * block_size 1..45. */
@@ -874,7 +900,7 @@ int ofk_pos_filter_step(ofk_ctx *ctx, const ofk_pos_filter *f, const double *v_u
  * behind "off": OFK_STAB_PLANE, OFK_BORDER_CONSTANT, 0, 0.5, 1.
  * OFK_E_INVALID before any launch from a stream step with the setting on: ofk_set_keyframe off; ofk_set_camera or
  * ofk_set_rolling_shutter on (the homography holds between ideal global-shutter images; a raw frame behind a lens needs a remap in
- * front of the warp, which is not built).
+ * front of the warp, which is not built).  With ofk_set_rectify on the camera is accepted (below); the rolling shutter never is.
  * ofk_stab_download, the streams of the latest step with the setting on (every output may be NULL): frames [batch][h][w] u8, rec
  * [batch][OFK_STAB_DOUBLES], covered [batch] i32.  ofk_stab_frames: the DEVICE pointer of the frames and the bytes between images, for
  * consumers on the device (valid until the context is destroyed; written by every step).  ofk_stab_reset: active stream b starts over
@@ -961,6 +987,22 @@ int ofk_get_camera(const ofk_ctx *ctx, ofk_camera *cam);
 int ofk_undistort_points(ofk_ctx *ctx, const ofk_camera *cam, const float *pts, const int *counts, int batch, int stride, float *out);
 int ofk_distort_points(ofk_ctx *ctx, const ofk_camera *cam, const float *pts, const int *counts, int batch, int stride, float *out);
 int ofk_camera_download(ofk_ctx *ctx, float *prev_ideal, float *next_ideal, int stride);
+
+/* Rectified view: the stabilised view of a stream behind a lens.  The view and the matrix M of ofk_set_stabilise live in IDEAL pixels
+ * (with a camera set the caller keeps sensors[19..21] = 1 / fo, co_x, co_y), the step's new frame in raw ones.  With this setting on AND
+ * ofk_set_camera on, a stream step with ofk_set_stabilise on is accepted and its rule 5 launches k_warp_lens_u8 (ofk_warp_lens's rule)
+ * with the context's camera and this r_max in the place of k_warp_u8: the same M (the view's pose does not change), level 0 of the new
+ * frame (JPEG steps included), the same buffer, border, border_value, covered count and min_cover re-base.  Without a camera the
+ * setting is inert and the plain warp runs; without the stabilised view it launches nothing; with it off (the default) every step
+ * does what it always did, the refusal of the view beside ofk_set_camera included.  The view beside ofk_set_rolling_shutter stays
+ * refused either way.  ofk_pairs_run ignores the setting.
+ * ofk_set_rectify: NULL or mode OFK_RECTIFY_OFF switches it off.  OFK_E_INVALID, the setting staying as it was: a mode other than the
+ * two, r_max negative or not finite (0: no bound).  Defaults behind "off": r_max 0. */
+#define OFK_RECTIFY_OFF 0
+#define OFK_RECTIFY_ON  1
+typedef struct ofk_rectify { int mode; double r_max; } ofk_rectify;
+int ofk_set_rectify(ofk_ctx *ctx, const ofk_rectify *r);
+int ofk_get_rectify(const ofk_ctx *ctx, ofk_rectify *r);
 
 /* Rolling shutter: the per-row capture time undone on the device before the solve.  The reference's camera exposes its rows one after
  * the other: a point in row y of a frame of H rows is seen readout * (y / H - anchor) frame intervals away from the frame's time
